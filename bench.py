@@ -19,12 +19,22 @@ the B distinct stereo pairs sit in a pinned host ring, an upload context copies 
 idle one of two frame stores while the other one is being processed (vsl_event hand-offs, no host round trip),
 and the per-pair match counts are read back per batch.  It reports the PCIe rate achieved and which side bounds.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--passes P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--passes P] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel, timed with HIP events on the stream the
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, the K timed steps, the
+outputs (--dump-outputs DIR) and ONE JSON line on rank 0 (`value`, `ms_per_step`, `config`, `per_rank`).  The rest --
+the streaming mode above, the per-stage times and rooflines, the CPU baseline and the output check against the oracle,
+the BA / pose-graph / BoW / end-to-end legs below and, for N > 1, the multi-rank global BA -- runs with --full only.
+
+--dump-outputs DIR writes what the timed path left in HBM after its last step as DIR/<name>.npy (float32 / float64, a
+few MB): keypoint and match counts of every stereo frame, and the keypoints (position, angle, descriptor bytes) and
+match lists of a fixed, seeded sample of the frames.  The inputs depend on the arguments only, so two builds can be
+compared output for output.
+
+With --full the line carries more.  `roofline` is for the dominant kernel, timed with HIP events on the stream the
 kernels run on; `cpu_baseline` is the CPU oracle (a port of the reference's path, the reference itself cannot be
-built offline) timed on this box's host cores on a bounded sample of the same frames -- and the timed run's outputs
+built offline) timed on the host's cores on a bounded sample of the same frames -- and the timed run's outputs
 for those frames are compared with the oracle's (`outputs_equal_oracle_sample`).
 
 At N = 1 the line also carries: `local_ba` / `global_ba` (ms per LM iteration, BASELINE configs[2] / [4]); `bow` (DBoW2
@@ -95,6 +105,45 @@ def distinct_stereo_frames(seeds, n_variants, workers):
     else:
         parts = [_gen_scene(j) for j in jobs]
     return np.concatenate(parts, axis=0)
+
+
+DUMP_SAMPLE_FRAMES = 32   # stereo frames whose keypoints and matches --dump-outputs writes (<= 15 MB at 1500 features)
+DUMP_SAMPLE_SEED = 2024
+
+
+def dump_outputs(dirname, units, counts, B, Bu):
+    """--dump-outputs: the outputs of the timed path's last step (every pass recomputes the same frames, so the frame
+    stores hold them after the timed region), as float arrays.  Counts for all B stereo frames; keypoints and match
+    lists for a fixed, seeded sample of them.  Stereo frame f lives in unit f // Bu, images 2k / 2k+1 and pair k for
+    k = f % Bu."""
+    os.makedirs(dirname, exist_ok=True)
+    sample = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, min(DUMP_SAMPLE_FRAMES, B), replace=False))
+    xy, ang, desc, n_kp, pairs, n_m = [], [], [], [], [], []
+    for f in sample:
+        fr = units[f // Bu][2]
+        k = int(f % Bu)
+        for slot in (2 * k, 2 * k + 1):
+            p, a, d = fr.keypoints(slot)
+            xy.append(p)
+            ang.append(a)
+            desc.append(d.view(np.uint8).reshape(-1, 32))   # the 256-bit descriptor as its 32 bytes
+            n_kp.append(len(p))
+        m = fr.matches(k)
+        pairs.append(m)
+        n_m.append(len(m))
+    arrays = {
+        "keypoints_per_image": np.concatenate([c[0] for c in counts]).astype(np.float64),   # (2B,) left, right, ...
+        "matches_per_pair": np.concatenate([c[1] for c in counts]).astype(np.float64),      # (B,)
+        "sample_stereo_frames": sample.astype(np.float64),
+        "sample_keypoints_per_image": np.asarray(n_kp, np.float64),
+        "sample_keypoints_xy": np.concatenate(xy).astype(np.float64).reshape(-1, 2),
+        "sample_keypoints_angle": np.concatenate(ang).astype(np.float64),
+        "sample_descriptor_bytes": np.concatenate(desc).astype(np.float32),
+        "sample_matches_per_pair": np.asarray(n_m, np.float64),
+        "sample_matches": np.concatenate(pairs).astype(np.float64).reshape(-1, 2),         # (left, right) keypoint indices
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def streaming_measurement(vsl, units, ring, Bu, slot_pairs, seconds, device, expect_matches):
@@ -472,6 +521,12 @@ def main():
     ap.add_argument("--e2e-radius", type=float, default=2.674,
                     help="circle radius: 2 pi r / step = 560 frames per lap, so the revisit is > loop_closing_time (500) frames later")
     ap.add_argument("--no-bow", dest="bow", action="store_false", help="skip the BoW transform / score measurement (k = 10, L = 6 vocabulary)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure: streaming mode, per-stage times and "
+                         "rooflines, CPU baseline and oracle check, BA / pose graph / BoW / end-to-end legs, and the "
+                         "multi-rank global BA for N > 1 (the --no-* and leg options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64, a few MB)")
     ap.add_argument("--rehearse-plumbing", action="store_true",
                     help="NO GPU work: the launcher / rank / timing / JSON plumbing with a sleeping step (CPU tests of "
                          "--gpus N; set VSL_BENCH_BACKEND=gloo).  The line says so and carries no value.")
@@ -593,7 +648,7 @@ def main():
     counts = [frames.counts(n_img, Bu) for _, _, frames in units]
     # the resident run's OUTPUTS for the frames the CPU baseline will redo (rank 0, N = 1): keypoints, descriptors, matches
     sample_out = []
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         for nfr in range(min(args.cpu_frames, B)):
             fr = units[nfr // Bu][2]
             k = nfr % Bu
@@ -604,6 +659,8 @@ def main():
     ctx, frames = units[0][1], units[0][2]
     if not (nk.min() > 0 and nm.min() > 0):
         raise SystemExit("benchmark produced empty outputs: keypoints %s matches %s" % (nk.min(), nm.min()))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, units, counts, B, Bu)
 
     out = None
     if rank == 0:
@@ -634,6 +691,8 @@ def main():
                        "synthetic_input_generation_s": round(t_gen, 2)},
         }
 
+    # ---- everything below the headline figure: --full only
+    if args.full and rank == 0:
         # ---- streaming mode (N = 1): the same hot path fed from the pinned host ring, upload inside the timed region
         if args.stream_seconds > 0 and world == 1 and S >= 2:
             out.update(streaming_measurement(vsl, units, ring, Bu, slot_pairs, args.stream_seconds, local_rank,
@@ -1142,7 +1201,7 @@ def main():
     # is the last thing before the line is printed, under a watchdog: if a collective does not come back (a rank lost, a
     # communicator that never forms) rank 0 still prints the frame-pipeline line -- with the failure named -- and every
     # rank leaves.
-    if args.gba and world > 1:
+    if args.full and args.gba and world > 1:
         import threading
 
         def give_up():

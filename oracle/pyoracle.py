@@ -328,12 +328,11 @@ _REF = None
 def ref_lib():
     """oracle/_ref/libdbow2_ref.so: the REFERENCE's own BowVector.cpp / FeatureVector.cpp (compiled where they lie by
     `make -C oracle ref`) behind oracle/ref_dbow2_driver.cpp.  Returns None when it is neither prebuilt nor buildable
-    (no /root/reference on this machine)."""
+    (the Makefile's target builds it where the reference sources are readable and keeps any prebuilt file elsewhere)."""
     global _REF
     if _REF is None:
         so = _DIR / "_ref" / "libdbow2_ref.so"
-        if Path("/root/reference/thirdparty/DBoW2_ORBSLAM/DBoW2/BowVector.cpp").exists():
-            subprocess.run(["make", "-C", str(_DIR), "ref"], check=True, capture_output=True)
+        subprocess.run(["make", "-C", str(_DIR), "ref"], check=True, capture_output=True)
         if not so.exists():
             return None
         _REF = C.CDLL(str(so))

@@ -267,9 +267,10 @@ def test_bench_gpus_2_runs_the_global_ba_all_reduce_leg():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["VSL_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "32",
-                        "--scenes", "8", "--passes", "1", "--cpu-frames", "0", "--stream-seconds", "0", "--no-ba", "--no-e2e",
-                        "--no-bow", "--gen-workers", "2", "--gba-kf", "60", "--gba-lms", "6000", "--profile-steps", "1"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0",
+                        "--batch", "32", "--scenes", "8", "--passes", "1", "--cpu-frames", "0", "--stream-seconds", "0",
+                        "--no-ba", "--no-e2e", "--no-bow", "--gen-workers", "2", "--gba-kf", "60", "--gba-lms", "6000",
+                        "--profile-steps", "1"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

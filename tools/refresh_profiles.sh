@@ -11,7 +11,7 @@ ROUND=${1:-r04}
 O=$R/gpurun_out/refresh
 rm -rf $O && mkdir -p $O  # (clear the LOCAL gpurun_out/refresh too before a new run: gpurun merges, it does not delete)
 cd /tmp && export TMPDIR=/tmp
-LITE="--cpu-frames 0 --no-ba --no-gba --no-e2e --no-bow --stream-seconds 0 --gen-workers 1"
+LITE="--full --cpu-frames 0 --no-ba --no-gba --no-e2e --no-bow --stream-seconds 0 --gen-workers 1"
 # (no forked generator workers under the profiler: the frames are generated once here and cached under /tmp)
 python3 $R/bench.py --streams 1 --batch 512 --passes 1 --steps 1 --warmup 0 --cpu-frames 0 --no-ba --no-gba --no-e2e --no-bow --stream-seconds 0 > /dev/null 2>&1
 # HBM traffic: FETCH_SIZE and WRITE_SIZE in separate passes, plus the calibration of both counters on known byte counts
@@ -30,7 +30,7 @@ echo e2e; (cd $R && LOOK=90 bash tools/e2e_profile.sh $ROUND > $O/e2e_profile.lo
 # --pmc passes); into the box's profiles/ as well, so that the bench line's local_ba / global_ba rooflines carry THIS build's
 echo ba_pmc; (cd $R && bash tools/ba_pmc.sh $ROUND > $O/ba_pmc.log 2>&1; cp gpurun_out/${ROUND}_ba_pmc_traffic.json $O/ 2>/dev/null; cp gpurun_out/${ROUND}_ba_pmc_traffic.json profiles/ 2>/dev/null)
 cd /tmp
-echo bench; (cd $R && python3 bench.py > $O/bench_line.json 2> $O/bench.err)
+echo bench; (cd $R && python3 bench.py --full > $O/bench_line.json 2> $O/bench.err)
 # BoW (K8 / K9) and the ORB front end: kernel durations on the k = 10 / L = 6 vocabulary
 echo bow; rocprofv3 --kernel-trace --stats --output-format csv -d $O/bow -- python3 $R/tools/bow_probe.py --no-oracle > $O/bow.log 2>&1
 # kernel durations: one stream (the isolated durations the roofline uses) and the default two-stream run
