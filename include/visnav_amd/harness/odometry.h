@@ -40,8 +40,15 @@
 #include "sim3.h"
 #include "tracking.h"
 
+// The device stereo stage (OdometryOptions::device_stereo) is referenced weakly: the CPU-baseline build of the same
+// application links a C ABI that does not define it (oracle/Makefile cpu_baseline), and refuses the option there.
+#pragma weak vsl_frames_stereo_inliers
+#pragma weak vsl_frames_download_inliers
+
 namespace visnav {
 namespace harness {
+
+inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
 
 struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.cpp:258-309
   int num_features_per_image = 1500;
@@ -69,6 +76,10 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   // descriptors are copied device-to-device into the map's pool.  Same kernels, same matches, same
   // trajectory as the operator-by-operator sequence (tests/test_headless_gpu.py); fewer PCIe round trips.
   bool fused_tracking = false;
+  // with fused_tracking: the epipolar filter and the triangulation of the stereo inliers run on the device
+  // (vsl_frames_stereo_inliers on the keyframe's pair slot); add_new_landmarks takes the device's p_c.  Same inliers,
+  // same points, same trajectory as the host restatement (tests/test_stereo_gpu.py).
+  bool device_stereo = false;
   // src/slam.cpp:244-247, :274-294 (the reference's defaults are true / true / true; they need --voc-path)
   bool enable_relocalization = false;
   bool enable_loop_closure = false;
@@ -157,9 +168,11 @@ inline void localize_camera(const Sophus::SE3d& current_pose, const std::shared_
 }
 
 // vo_utils.h:228-322
+// stereo_p_c (nullable): the triangulated point of every stereo inlier, 3 doubles each in md_stereo.inliers order (the device
+// stereo stage's output); without it the points are triangulated here
 inline void add_new_landmarks(const FrameCamId fcidl, const FrameCamId fcidr, const KeypointsData& kdl, const KeypointsData& kdr,
                               const Calibration& calib_cam, const MatchData& md_stereo, const LandmarkMatchData& md,
-                              Landmarks& landmarks, TrackId& next_landmark_id) {
+                              Landmarks& landmarks, TrackId& next_landmark_id, const std::vector<double>* stereo_p_c = nullptr) {
   const Pose T_0_1 = inverse(to_pose(calib_cam.T_i_c[0])) * to_pose(calib_cam.T_i_c[1]);
   const Pose T_w_c = to_pose(md.T_w_c);
   std::map<FeatureId, FeatureId> stereo_of;  // left feature -> right feature (first inlier pair wins, like the linear scan)
@@ -181,12 +194,17 @@ inline void add_new_landmarks(const FrameCamId fcidl, const FrameCamId fcidr, co
       lm.all_obs.emplace(fcidr, st->second);
     }
   }
-  for (const auto& kv : md_stereo.inliers) {
-    const FeatureId f_idl = kv.first, f_idr = kv.second;
+  for (size_t k = 0; k < md_stereo.inliers.size(); k++) {
+    const FeatureId f_idl = md_stereo.inliers[k].first, f_idr = md_stereo.inliers[k].second;
     if (localized.count(f_idl)) continue;  // already attached to an existing landmark
-    const Vec3 b1 = unproject(calib_cam.intrinsics[fcidl.cam_id], kdl.corners.at(f_idl));
-    const Vec3 b2 = unproject(calib_cam.intrinsics[fcidr.cam_id], kdr.corners.at(f_idr));
-    const Vec3 p_c = triangulate_midpoint(b1, b2, T_0_1.R, T_0_1.t);
+    Vec3 p_c;
+    if (stereo_p_c) {
+      p_c = Vec3((*stereo_p_c)[3 * k], (*stereo_p_c)[3 * k + 1], (*stereo_p_c)[3 * k + 2]);
+    } else {
+      const Vec3 b1 = unproject(calib_cam.intrinsics[fcidl.cam_id], kdl.corners.at(f_idl));
+      const Vec3 b2 = unproject(calib_cam.intrinsics[fcidr.cam_id], kdr.corners.at(f_idr));
+      p_c = triangulate_midpoint(b1, b2, T_0_1.R, T_0_1.t);
+    }
     Landmark l;
     l.p = to_eigen(T_w_c * p_c);
     l.p_c = to_eigen(inverse(T_w_c) * (T_w_c * p_c));
@@ -350,13 +368,14 @@ class Odometry {
       const Mat3 E = compute_essential(T_0_1);
       if (opt.fused_tracking) {
         fused_track(md);  // before the downloads below: they synchronise the stream
-        fused_stereo(kdl, kdr, md_stereo);
+        fused_stereo(kdl, kdr, md_stereo, E);
         fused_prefetch(next_left);
       } else {
         matchDescriptors(kdl.corner_descriptors, kdr.corner_descriptors, md_stereo.matches, opt.feature_match_max_dist,
                          opt.feature_match_test_next_best);
       }
-      find_inliers_essential(kdl, kdr, calib_cam.intrinsics[0], calib_cam.intrinsics[1], E, 1e-3, md_stereo);
+      const bool dev_st = opt.fused_tracking && opt.device_stereo;  // then fused_stereo filled md_stereo.inliers
+      if (!dev_st) find_inliers_essential(kdl, kdr, calib_cam.intrinsics[0], calib_cam.intrinsics[1], E, 1e-3, md_stereo);
       auto t3 = Clk::now();
       feature_corners[fcidl] = kdl;
       feature_corners[fcidr] = kdr;
@@ -367,7 +386,7 @@ class Odometry {
       localize(fcidl, img_left, kdl, md);
       auto t5 = Clk::now();
       const size_t lm_before = landmarks.size();
-      add_new_landmarks(fcidl, fcidr, kdl, kdr, calib_cam, md_stereo, md, landmarks, next_landmark_id);
+      add_new_landmarks(fcidl, fcidr, kdl, kdr, calib_cam, md_stereo, md, landmarks, next_landmark_id, dev_st ? &stereo_p_c : nullptr);
       if (std::getenv("VISNAV_AMD_TRACE_FRAMES")) {
         unsigned long long hl = 1469598103934665603ull, hr = hl, hm = hl;
         for (const auto& d : kdl.corner_descriptors) hl = (hl ^ (unsigned long long)(d.to_string().substr(0, 64).size() + d.count())) * 1099511628211ull;
@@ -709,6 +728,7 @@ class Odometry {
   bool map_dirty = true;
   std::vector<TrackId> table_ids;    // landmark table row -> TrackId
   std::unordered_map<TrackId, std::vector<int32_t>> lm_pool;  // landmark -> pool entries of its observation descriptors
+  std::vector<double> stereo_p_c;    // device_stereo: p_c of the keyframe's stereo inliers (3 doubles each, inlier order)
 
   void fused_init(const GreyImage& img) {
     if (dev_frames) return;
@@ -805,15 +825,33 @@ class Odometry {
     if (with_desc) kd.corner_descriptors.resize((size_t)n);
   }
 
-  void fused_stereo(KeypointsData& kdl, KeypointsData& kdr, MatchData& md_stereo) {
+  // with opt.device_stereo: the epipolar inliers (findInliersEssential with E and threshold 1e-3, as next_step) and their
+  // triangulated points (stereo_p_c) come from the device stage on the same pair slot
+  void fused_stereo(KeypointsData& kdl, KeypointsData& kdr, MatchData& md_stereo, const Mat3& E) {
     const int32_t sp[2] = {cur_base, cur_base + 1};
     vsl_ctx* c = amd::ctx();
     amd::check(vsl_frames_match(c, dev_frames, sp, 1, opt.feature_match_max_dist, opt.feature_match_test_next_best), "vsl_frames_match");
+    if (opt.device_stereo) {
+      const auto& ca = calib_cam.intrinsics[0];
+      const auto& cb = calib_cam.intrinsics[1];
+      amd::check(vsl_frames_stereo_inliers(c, dev_frames, 0, 1, amd::camera_model_id(ca->name()), ca->data(),
+                                           amd::camera_model_id(cb->name()), cb->data(), &E.m[0][0], &T_0_1.R.m[0][0], &T_0_1.t.x,
+                                           1e-3, 1),
+                 "vsl_frames_stereo_inliers");
+    }
     std::vector<int32_t> out(2 * (size_t)opt.num_features_per_image);
     int n = 0;
     amd::check(vsl_frames_download_matches(c, dev_frames, 0, opt.num_features_per_image, out.data(), &n), "vsl_frames_download_matches");
     md_stereo.matches.clear();
     for (int i = 0; i < n; i++) md_stereo.matches.emplace_back(out[2 * i], out[2 * i + 1]);
+    if (opt.device_stereo) {
+      stereo_p_c.resize(3 * (size_t)opt.num_features_per_image);
+      amd::check(vsl_frames_download_inliers(c, dev_frames, 0, opt.num_features_per_image, out.data(), stereo_p_c.data(), &n),
+                 "vsl_frames_download_inliers");
+      stereo_p_c.resize(3 * (size_t)n);
+      md_stereo.inliers.clear();
+      for (int i = 0; i < n; i++) md_stereo.inliers.emplace_back(out[2 * i], out[2 * i + 1]);
+    }
     fused_download_corners(cur_base, kdl);
     fused_download_corners(cur_base + 1, kdr);
   }

@@ -3,6 +3,7 @@
 // (this repository's own build and tests: Eigen, Sophus, Pangolin, TBB and the reference's
 // common_types.h are not available offline).  Layouts match what the wrappers rely on:
 //   Eigen::Vector2d / Vector3d : 2 / 3 contiguous doubles
+//   Eigen::Matrix3d            : 9 doubles, column-major
 //   Sophus::SE3d::data()       : qx qy qz qw tx ty tz            (include/visnav/serialization.h:153-162)
 //   pangolin::ManagedImage<T>  : pitch, ptr, w, h                (pangolin/image/image.h)
 //   visnav::KeypointsData      : include/visnav/common_types.h:111-122
@@ -37,6 +38,15 @@ struct VectorNd {
 };
 typedef VectorNd<2> Vector2d;
 typedef VectorNd<3> Vector3d;
+// 3 x 3, column-major like Eigen's default storage: m(i, j) = data()[i + 3 j]
+struct Matrix3d {
+  double v[9];
+  Matrix3d() { for (int i = 0; i < 9; i++) v[i] = 0; }
+  double& operator()(int i, int j) { return v[i + 3 * j]; }
+  const double& operator()(int i, int j) const { return v[i + 3 * j]; }
+  double* data() { return v; }
+  const double* data() const { return v; }
+};
 template <class T>
 using aligned_allocator = std::allocator<T>;
 }  // namespace Eigen

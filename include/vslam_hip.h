@@ -253,6 +253,35 @@ int vsl_frames_download_matches(vsl_ctx* ctx, vsl_frames* f, int pair, int cap_p
 int vsl_frames_download_counts(vsl_ctx* ctx, vsl_frames* f, int n_images, int32_t* n_keypoints,
                                int n_pairs, int32_t* n_matches);
 
+/* Stereo stage of a keyframe after the matcher (src/slam.cpp:1136-1150 + the triangulation of add_new_landmarks,
+ * include/visnav/vo_utils.h:232-317): for every pair slot p in [first_pair, first_pair + n_pairs), the matches that
+ * vsl_frames_match left there (left id i, right id j, in the slots of pair_slots[p]) are kept iff
+ *   !(|unproject(a, corner_i) . (E * unproject(b, corner_j))| > threshold)
+ * -- findInliersEssential (include/visnav/matching_utils.h:64-88); a NaN error counts as an inlier like there -- in
+ * match order (ascending left id), and every inlier is triangulated by the midpoint of the two rays in the LEFT camera's
+ * frame, p_c = R_0_1 p_1 + t_0_1 convention (R9_0_1 row-major m[i][j], t3_0_1).  model_* = VSL_CAM_*, intr8_* as in
+ * vsl_project_landmarks, E9 row-major (computeEssential, matching_utils.h:56-62).  triangulate == 0 or a null R9_0_1 /
+ * t3_0_1: inlier lists only.  Asynchronous; the output buffers ([max_pairs][F][2] pairs, [max_pairs][F][3] points,
+ * [max_pairs] counts) are allocated by the first call on a store.  Results are bit-identical to the host restatement
+ * (include/visnav_amd/harness/odometry.h find_inliers_essential, harness/pnp.h triangulate_midpoint) for ds, pinhole
+ * and eucm; kb4 goes through the device sin / cos (DESIGN.md "Stereo inliers and triangulation"). */
+int vsl_frames_stereo_inliers(vsl_ctx* ctx, vsl_frames* f, int first_pair, int n_pairs, int model_a, const double* intr8_a,
+                              int model_b, const double* intr8_b, const double* E9, const double* R9_0_1,
+                              const double* t3_0_1, double threshold, int triangulate);
+/* Synchronize and copy one pair's inlier list (i, j) and, if points_c is not null, its triangulated points (3 doubles
+ * each; the pair's last stage call must have triangulated) in one round trip.  cap_pairs < count: VSL_ERR_CAPACITY. */
+int vsl_frames_download_inliers(vsl_ctx* ctx, vsl_frames* f, int pair, int cap_pairs, int32_t* pairs, double* points_c,
+                                int* n_out);
+/* Synchronize and copy the inlier counts of pair slots [0, n_pairs). */
+int vsl_frames_download_inlier_counts(vsl_ctx* ctx, vsl_frames* f, int n_pairs, int32_t* counts);
+/* The same stage on host buffers for one pair (include/visnav_amd/matching_utils.h findInliersEssential): kp_*_xy are
+ * corner positions (2 doubles each), matches n_matches (i, j) pairs with i < n_a, j < n_b (else VSL_ERR_INVALID).
+ * pairs_out: capacity n_matches pairs; points_out (nullable; needs R9_0_1 and t3_0_1): capacity 3 * n_matches. */
+int vsl_find_inliers_essential(vsl_ctx* ctx, int model_a, const double* intr8_a, int model_b, const double* intr8_b,
+                               const double* E9, const double* kp_a_xy, int n_a, const double* kp_b_xy, int n_b,
+                               const int32_t* matches, int n_matches, double threshold, const double* R9_0_1,
+                               const double* t3_0_1, int32_t* pairs_out, double* points_out, int* n_out);
+
 /* Diagnostic: number of corner candidates (3x3 local maxima above the quality threshold) each of
  * the first n_images slots produced in its last detect call -- the input size of the selection
  * stage, needed to price its traffic. */

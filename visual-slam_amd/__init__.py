@@ -29,6 +29,7 @@ STAGES = ["response", "select", "describe", "match", "match_finalize", "ba_linea
           "ba_solve", "bow_transform", "bow_score", "ba_finish", "ba_step"]
 
 OK = 0
+CAM_DS, CAM_PINHOLE, CAM_EUCM, CAM_KB4 = 0, 1, 2, 3  # VSL_CAM_*
 ERR = {-1: "VSL_ERR_INVALID", -2: "VSL_ERR_HIP", -3: "VSL_ERR_NOMEM", -4: "VSL_ERR_CAPACITY",
        -5: "VSL_ERR_NO_DEVICE", -6: "VSL_ERR_IO", -7: "VSL_ERR_NUMERIC"}
 
@@ -100,6 +101,23 @@ def _img(img):
     img = np.ascontiguousarray(img, dtype=np.uint8)
     assert img.ndim == 2
     return img, img.ctypes.data_as(u8p), img.shape[1], img.shape[0], C.c_size_t(img.strides[0])
+
+
+def _mat9(M):
+    return None if M is None else np.ascontiguousarray(np.asarray(M, np.float64).reshape(9))
+
+
+def _vec3(v):
+    return None if v is None else np.ascontiguousarray(np.asarray(v, np.float64).reshape(3))
+
+
+def _cam(cam):
+    """(VSL_CAM_* model, intrinsics) -> (model, 8 doubles fx fy cx cy p1..p4, zero-padded)."""
+    model, intr = cam
+    i8 = np.zeros(8, np.float64)
+    intr = np.asarray(intr, np.float64).reshape(-1)
+    i8[:len(intr)] = intr
+    return int(model), i8
 
 
 class Context:
@@ -252,6 +270,28 @@ class Context:
                                               C.c_double(dist_2_best), pairs.ctypes.data_as(i32p),
                                               C.byref(n)))
         return pairs[:n.value].copy()
+
+    # ---- matching_utils.h drop-in
+    def find_inliers_essential(self, cam_a, cam_b, E, kp_a_xy, kp_b_xy, matches, threshold=1e-3, R=None, t=None,
+                               points=True):
+        """vsl_find_inliers_essential: findInliersEssential on host buffers for one pair, plus (with R, t = R_0_1, t_0_1
+        and points=True) the midpoint triangulation of every inlier.  Returns (pairs (n, 2) int32, points (n, 3) or None)."""
+        E9, R9, t3 = _mat9(E), _mat9(R), _vec3(t)
+        (ma, ia), (mb, ib) = _cam(cam_a), _cam(cam_b)
+        a = np.ascontiguousarray(kp_a_xy, np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(kp_b_xy, np.float64).reshape(-1, 2)
+        m = np.ascontiguousarray(matches, np.int32).reshape(-1, 2)
+        want = bool(points) and R9 is not None and t3 is not None
+        out = np.zeros((max(len(m), 1), 2), np.int32)
+        pts = np.zeros((max(len(m), 1), 3), np.float64)
+        n = C.c_int32()
+        self._ck(self.L.vsl_find_inliers_essential(
+            self.h, ma, ia.ctypes.data_as(f64p), mb, ib.ctypes.data_as(f64p), E9.ctypes.data_as(f64p),
+            a.ctypes.data_as(f64p), len(a), b.ctypes.data_as(f64p), len(b), m.ctypes.data_as(i32p), len(m),
+            C.c_double(threshold), R9.ctypes.data_as(f64p) if R9 is not None else None,
+            t3.ctypes.data_as(f64p) if t3 is not None else None, out.ctypes.data_as(i32p),
+            pts.ctypes.data_as(f64p) if want else None, C.byref(n)))
+        return out[:n.value].copy(), (pts[:n.value].copy() if want else None)
 
     # ---- vo_utils.h drop-ins
     def project_landmarks(self, pose7, model, intr8, width, height, points, cam_z_threshold=0.1):
@@ -707,6 +747,31 @@ class Frames:
         self.ctx._ck(self.ctx.L.vsl_frames_download_matches(self.ctx.h, self.h, int(pair), self.F,
                                                             out.ctypes.data_as(i32p), C.byref(n)))
         return out[:n.value].copy()
+
+    def stereo_inliers(self, first_pair, n_pairs, cam_a, cam_b, E, R=None, t=None, threshold=1e-3, triangulate=True):
+        """vsl_frames_stereo_inliers (asynchronous): epipolar inliers of the matches in pair slots
+        [first_pair, first_pair + n_pairs) and, with R / t (R_0_1, t_0_1), their midpoint triangulation in the left
+        camera's frame.  cam_a / cam_b = (VSL_CAM_* model, 8 intrinsics); E, R row-major 3 x 3."""
+        E9, R9, t3 = _mat9(E), _mat9(R), _vec3(t)
+        (ma, ia), (mb, ib) = _cam(cam_a), _cam(cam_b)
+        self.ctx._ck(self.ctx.L.vsl_frames_stereo_inliers(
+            self.ctx.h, self.h, int(first_pair), int(n_pairs), ma, ia.ctypes.data_as(f64p), mb, ib.ctypes.data_as(f64p),
+            E9.ctypes.data_as(f64p), R9.ctypes.data_as(f64p) if R9 is not None else None,
+            t3.ctypes.data_as(f64p) if t3 is not None else None, C.c_double(threshold), int(bool(triangulate))))
+
+    def inliers(self, pair, points=True):
+        """(pairs (n, 2) int32, points_c (n, 3) float64 or None) of one pair slot."""
+        out = np.zeros((self.F, 2), np.int32)
+        pts = np.zeros((self.F, 3), np.float64) if points else None
+        n = C.c_int32()
+        self.ctx._ck(self.ctx.L.vsl_frames_download_inliers(self.ctx.h, self.h, int(pair), self.F, out.ctypes.data_as(i32p),
+                                                            pts.ctypes.data_as(f64p) if points else None, C.byref(n)))
+        return out[:n.value].copy(), (pts[:n.value].copy() if points else None)
+
+    def inlier_counts(self, n_pairs):
+        c = np.zeros(max(n_pairs, 1), np.int32)
+        self.ctx._ck(self.ctx.L.vsl_frames_download_inlier_counts(self.ctx.h, self.h, int(n_pairs), c.ctypes.data_as(i32p)))
+        return c[:n_pairs].copy()
 
     def candidate_counts(self, n_images):
         nc = np.zeros(max(n_images, 1), np.int32)

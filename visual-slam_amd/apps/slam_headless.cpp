@@ -5,7 +5,7 @@
 // libvslam_hip.so; there is no CPU fallback.
 //
 //   slam_headless --dataset-path <dir with cam0/ cam1/ ...> --cam-calib <calib.json>
-//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N]
+//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -51,6 +51,7 @@ int main(int argc, char** argv) {
     else if (a == "--async-ba") opt.async_ba = true;
     else if (a == "--ba-merge-after") opt.ba_merge_after = std::atoi(need("--ba-merge-after").c_str());  // with --async-ba: deterministic hand-over
     else if (a == "--fused") opt.fused_tracking = true;
+    else if (a == "--device-stereo") opt.device_stereo = true;  // with --fused: epipolar inliers + triangulation on the device
     else if (a == "--no-lookahead") lookahead = false;
     else if (a == "--replicas") replicas = std::atoi(need("--replicas").c_str());
     else if (a == "--kf-min-inliers") opt.new_kf_min_inliers = std::atoi(need("--kf-min-inliers").c_str());
@@ -79,6 +80,14 @@ int main(int argc, char** argv) {
   }
   if (dataset.empty() || calib_path.empty()) {
     std::fprintf(stderr, "usage: slam_headless --dataset-path DIR --cam-calib FILE [--frames N] [--async-ba] [--traj FILE]\n");
+    return 2;
+  }
+  if (opt.device_stereo && !opt.fused_tracking) {
+    std::fprintf(stderr, "--device-stereo needs --fused (it runs on the frame store's pair slot)\n");
+    return 2;
+  }
+  if (opt.device_stereo && !device_stereo_available()) {
+    std::fprintf(stderr, "--device-stereo: this build's C ABI has no device stereo stage (vsl_frames_stereo_inliers)\n");
     return 2;
   }
   Calibration calib;
@@ -255,12 +264,12 @@ int main(int argc, char** argv) {
   const StageClock& c = odo.clock;
   std::printf(
       "{\"frames\": %d, \"keyframes\": %d, \"streams\": %d, \"streams_agree\": %s, \"frames_per_s\": %.2f, \"ms_per_frame\": %.3f, \"image_decode_s\": %.3f, "
-      "\"ate_rmse_m\": %.6f, \"ate_associations\": %d, \"landmarks\": %zu, \"active_landmarks\": %zu, \"async_ba\": %s, \"fused_tracking\": %s, "
+      "\"ate_rmse_m\": %.6f, \"ate_associations\": %d, \"landmarks\": %zu, \"active_landmarks\": %zu, \"async_ba\": %s, \"fused_tracking\": %s, \"device_stereo\": %s, "
       "\"stage_ms_total\": {\"detect\": %.1f, \"stereo_match\": %.1f, \"project_match\": %.1f, \"localize\": %.1f, \"map\": %.1f, "
       "\"ba\": %.1f, \"bow\": %.1f, \"loop\": %.1f, \"global_ba\": %.1f}, \"ba_runs\": %d, \"bow_vectors\": %zu, "
       "\"tracking_lost\": %d, \"relocalized\": %d, \"loops_closed\": %d, \"global_ba_runs\": %d, \"reloc_check_ok\": %d, \"reloc_check_err_m\": %.6f}\n",
       n_frames, n_kf, replicas, replicas_agree ? "true" : "false", replicas * n_frames / run_s, 1e3 * run_s / n_frames, decode_s, ate, n_assoc, odo.landmarks.size(), n_active,
-      opt.async_ba ? "true" : "false", opt.fused_tracking ? "true" : "false", c.detect_ms, c.stereo_match_ms, c.project_match_ms, c.localize_ms, c.map_ms, c.ba_ms, c.bow_ms, odo.loop_ms, odo.gba_ms, c.ba_runs, odo.bow_vectors.size(),
+      opt.async_ba ? "true" : "false", opt.fused_tracking ? "true" : "false", opt.device_stereo ? "true" : "false", c.detect_ms, c.stereo_match_ms, c.project_match_ms, c.localize_ms, c.map_ms, c.ba_ms, c.bow_ms, odo.loop_ms, odo.gba_ms, c.ba_runs, odo.bow_vectors.size(),
       odo.n_tracking_lost, odo.n_relocalized, odo.n_loops_closed, odo.n_global_ba, reloc_ok, reloc_err_m);
   amd::release_thread_ctx();  // the main thread's context (image registration), before static / thread-local teardown
   return 0;

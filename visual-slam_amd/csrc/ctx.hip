@@ -265,7 +265,8 @@ extern "C" int vsl_frames_destroy(vsl_frames* f) {
   (void)hipDeviceSynchronize();
   void* ptrs[] = {f->images, f->response, f->meta, f->cand, f->kp_xy, f->kp_count,
                   f->kp_moments, f->kp_angle, f->kp_desc, f->pair_slots, f->best_key, f->second_key,
-                  f->matches, f->match_count, f->tie_count, f->tie_rec, f->sel_grid, f->exact_list, f->tile_off, f->tile_ent};
+                  f->matches, f->match_count, f->tie_count, f->tie_rec, f->sel_grid, f->exact_list, f->tile_off, f->tile_ent,
+                  f->st_pairs, f->st_points, f->st_count};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete f;

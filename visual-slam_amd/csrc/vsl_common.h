@@ -178,6 +178,11 @@ struct vsl_frames {
   int exact_fallbacks = 0;            // how often that fallback ran (diagnostic)
   bool store_response = false;  // K1 writes the fp32 response image only for the parity hook
   std::vector<int32_t> pair_cache;  // host copy of pair_slots (skip the upload when unchanged)
+  // stereo stage (stereo.hip), allocated by its first call: epipolar inliers of each pair and their triangulated points
+  int32_t* st_pairs = nullptr;        // [max_pairs][F][2]  (left id, right id), match order
+  double* st_points = nullptr;        // [max_pairs][F][3]  p_c in the left camera's frame (first triangulating call)
+  int32_t* st_count = nullptr;        // [max_pairs]
+  std::vector<uint8_t> st_has_points; // [max_pairs]: the pair's last stage call triangulated
 };
 
 int vsl_frames_alloc(vsl_ctx* ctx, int max_images, int w, int h, int F, int max_pairs, vsl_frames** out);
