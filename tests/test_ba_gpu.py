@@ -175,7 +175,8 @@ def test_device_decided_loop_equals_the_host_decided_one(ctx, orc, synth, seed, 
     assert s_dev.initial_cost == s_host.initial_cost
     assert s_dev.final_cost == pytest.approx(s_host.final_cost, rel=1e-13)
     assert s_dev.final_cost == pytest.approx(s_cpu.final_cost, rel=1e-7)
-    # (the radius update's cube is rounded once on both sides; a last-bit difference there would show up here)
+    # (the radius update's cube is pow on the host and an fma expansion on the device: they can differ in the last bit,
+    # and a difference that mattered would show up here)
     assert np.allclose(a_dev.poses, a_host.poses, rtol=0, atol=1e-12)
     assert np.allclose(a_dev.points, a_host.points, rtol=0, atol=1e-9)
     # a second solve on the same context: the records of the first one must not be mistaken for this one's

@@ -26,12 +26,12 @@
 // (6C)^2*8 + 6C*8 + n_lms*96 out.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <numeric>
 #include <thread>
 
 #include "vsl_common.h"
+#include "lm_policy.h"
 #include "ba_device.h"
 #include "ba_large.h"
 
@@ -1503,10 +1503,6 @@ int camera_band_order(const vsl_ba_problem* gp, const std::vector<int>& cam_free
   return half;
 }
 
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // set-up phase times on stderr when VSL_BA_TRACE is set (developer aid)
 struct BaTrace {
   bool on;
@@ -2210,16 +2206,15 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   double cost = sc[0], gmax = sc[1];
   sum.initial_cost = cost;
 
-  double radius = 1e4, decrease_factor = 2.0;
-  int iteration = 0, invalid = 0;
+  LmState lm;
+  int iteration = 0, term;
   sum.termination = 0;
-  if (opt->verbosity >= 2)
-    fprintf(stderr, "iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n%4d % .6e\n", 0, cost);
+  if (opt->verbosity >= 2) lm_print_header(cost);
   // One host round trip per LM iteration: the whole iteration is enqueued without waiting -- Schur, Cholesky,
   // back-substitution, model / step norms, candidate parameters AND the linearisation at the candidate (into the
   // second set of blocks: its cost is the candidate's cost, and if the step is accepted it is the next iteration's
   // linearisation already) -- then ONE copy brings back [Cholesky ok, finite] + 7 scalars and the host applies the
-  // [upstream] Ceres step policy.  A rejected or invalid step swaps the sets back; its speculative work (~60 us of
+  // [upstream] Ceres step policy (lm_policy.h).  A rejected or invalid step swaps the sets back; its speculative work (~60 us of
   // device time) is the price.  (The first version synchronised three times per iteration: after the Cholesky, after
   // the candidate cost, after the re-linearisation.)
   double* hsc = nullptr;
@@ -2231,10 +2226,9 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   const int* hflag = (const int*)(hsc + 16);
   while (true) {
     if (iteration >= opt->max_num_iterations) { sum.termination = 0; break; }
-    if (gmax <= 1e-10) { sum.termination = 2; break; }
-    if (radius <= 1e-32) { sum.termination = 4; break; }
+    if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
     iteration++;
-    if ((rc = ba_schur(ctx, st, true, radius, 0, D.L, true, true))) return rc;
+    if ((rc = ba_schur(ctx, st, true, lm.radius, 0, D.L, true, true))) return rc;
     if ((rc = ba_solve_enqueue(ctx, st))) return rc;  // flag[1] = Cholesky ok
     {
       VslStage s(ctx, VSL_STAGE_BA_SOLVE);
@@ -2264,31 +2258,20 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const double model_change = hsc[2], step_norm = sqrt(hsc[3]), x_norm = sqrt(hsc[4]), cand_cost = hsc[5];
     const bool ok = hflag[0] != 0 && hflag[1] != 0 && model_change > 0.0;
-    if (!ok) {
-      st.swap_sets();
-      if (++invalid >= 5) { sum.termination = 4; break; }
-      radius *= 0.5;
-      if (opt->verbosity >= 2) fprintf(stderr, "%4d  invalid step, radius %.3e\n", iteration, radius);
+    const double radius_used = lm.radius;
+    LmInfo info;
+    const int verdict = lm_judge(lm, ok, cost, cand_cost, model_change, step_norm, x_norm, &info);
+    if (verdict != LM_ACCEPTED) st.swap_sets();  // (accepted: the sets stay swapped, the speculative linearisation is the current one)
+    if (verdict >= 0) { sum.termination = verdict; break; }
+    if (verdict == LM_INVALID) {
+      if (opt->verbosity >= 2) lm_print_invalid(iteration, lm.radius);
       continue;  // the LM diagonal is reused (the Jacobian is unchanged)
     }
-    invalid = 0;
-    if (step_norm <= 1e-8 * (x_norm + 1e-8)) { st.swap_sets(); sum.termination = 3; break; }
-    const double cost_change = cost - cand_cost;
-    if (fabs(cost_change) <= 1e-6 * cost) { st.swap_sets(); sum.termination = 1; break; }
-    const double rel = cost_change / model_change;
-    if (opt->verbosity >= 2)
-      fprintf(stderr, "%4d % .6e % .3e % .3e % .3e % .3e % .3e\n", iteration, cand_cost, cost_change, gmax, step_norm, rel, radius);
-    if (rel > 1e-3) {
-      cost = cand_cost;   // the sets stay swapped: the speculative linearisation is the current one
+    if (opt->verbosity >= 2) lm_print_row(iteration, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
+    if (verdict == LM_ACCEPTED) {
+      cost = cand_cost;
       gmax = hsc[6];
       sum.successful_steps++;
-      radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-      radius = std::min(1e16, radius);
-      decrease_factor = 2.0;
-    } else {
-      st.swap_sets();
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.0;
     }
   }
   sum.iterations = iteration;
@@ -2773,14 +2756,15 @@ extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduc
   double h2[2];
   if ((rc = D2H(h2, bufA.as<double>() + n, 8))) return rc;
   sum.initial_cost = h2[0];
-  double radius = 1e4, decrease = 2.0, cost = sum.initial_cost, gmax = INFINITY;
-  int it = 0, invalid = 0, refresh = 1;
+  LmState lm;
+  double cost = sum.initial_cost, gmax = INFINITY;
+  int it = 0, term, refresh = 1;
   bool have_h2 = false;
   double* const hostpack = packC.as<double>() + 8;  // [cost | max |gradient|] behind the 8 doubles of packC: one copy brings both
   sum.termination = 0;
-  if (verbosity >= 2) fprintf(stderr, "iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n%4d % .6e\n", 0, cost);
+  if (verbosity >= 2) lm_print_header(cost);
   while (true) {
-    if ((rc = vsl_ba_session_reduce_dev(s, radius, packB.as<double>(), gl.as<double>()))) return rc;
+    if ((rc = vsl_ba_session_reduce_dev(s, lm.radius, packB.as<double>(), gl.as<double>()))) return rc;
     if ((rc = AR(packB.as<double>(), nB, 0))) return rc;
     if (refresh) {
       if ((rc = AR(gl.as<double>(), 1, 1))) return rc;
@@ -2800,10 +2784,9 @@ extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduc
       sum.termination = 0;
       break;
     }
-    if (have_h2 && gmax <= 1e-10) { sum.termination = 2; break; }
-    if (radius <= 1e-32) { sum.termination = 4; break; }
+    if ((term = lm_gate(lm, have_h2 ? gmax : INFINITY)) >= 0) { sum.termination = term; break; }
     it++;
-    if ((rc = vsl_ba_session_step_dev(s, packB.as<double>(), radius, refresh, packC.as<double>()))) return rc;
+    if ((rc = vsl_ba_session_step_dev(s, packB.as<double>(), lm.radius, refresh, packC.as<double>()))) return rc;
     if ((rc = AR(packC.as<double>(), 8, 0))) return rc;
     double c[10];
     if ((rc = D2H(c, packC.p, 80))) return rc;
@@ -2811,39 +2794,26 @@ extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduc
       cost = c[8];
       gmax = c[9];
       have_h2 = true;
-      if (gmax <= 1e-10) {
+      if (gmax <= LM_GRADIENT_TOLERANCE) {  // lm_gate's first test, one step late
         it--;
         sum.termination = 2;
         break;
       }
     }
     const double cams_step2 = c[5] / world, cams_x2 = c[6] / world;
-    const bool ok = c[0] == 0.0 && c[1] > 0.0;
-    if (!ok) {
-      if (++invalid >= 5) { sum.termination = 4; break; }
-      radius *= 0.5;
-      refresh = 0;
-      continue;
-    }
-    invalid = 0;
     const double step_norm = sqrt(std::max(c[2] - (world - 1) * cams_step2, 0.0));
     const double x_norm = sqrt(std::max(c[3] - (world - 1) * cams_x2, 0.0));
-    if (step_norm <= 1e-8 * (x_norm + 1e-8)) { sum.termination = 3; break; }
-    const double cost_change = cost - c[4];
-    if (fabs(cost_change) <= 1e-6 * cost) { sum.termination = 1; break; }
-    const double rel = cost_change / c[1];
-    if (verbosity >= 2) fprintf(stderr, "%4d % .6e % .3e % .3e % .3e % .3e % .3e\n", it, c[4], cost_change, gmax, step_norm, rel, radius);
-    if (rel > 1e-3) {
+    const double radius_used = lm.radius;
+    LmInfo info;
+    const int verdict = lm_judge(lm, c[0] == 0.0 && c[1] > 0.0, cost, c[4], c[1], step_norm, x_norm, &info);
+    if (verdict >= 0) { sum.termination = verdict; break; }
+    refresh = verdict == LM_ACCEPTED;
+    if (verdict == LM_INVALID) continue;
+    if (verbosity >= 2) lm_print_row(it, c[4], info.cost_change, gmax, step_norm, info.rel, radius_used);
+    if (verdict == LM_ACCEPTED) {
       if ((rc = vsl_ba_session_accept(s))) return rc;
-      if ((rc = vsl_ba_session_linearize(s, 1))) return rc;
-      refresh = 1;
+      if ((rc = vsl_ba_session_linearize(s, 1))) return rc;  // (the next iteration reads this point's cost from it)
       sum.successful_steps++;
-      radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3)));
-      decrease = 2.0;
-    } else {
-      radius /= decrease;
-      decrease *= 2.0;
-      refresh = 0;
     }
   }
   sum.iterations = it;
@@ -3419,18 +3389,15 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   if ((rc = read_scalars(ctx, st, h, 2))) return rc;
   double cost = h[0], gmax = h[1];
   sum.initial_cost = cost;
-  double radius = 1e4, decrease_factor = 2.0;
-  bool have_diag = true;  // stats(true) above wrote the LM diagonal of the current Jacobian
-  int iteration = 0, invalid = 0;
+  LmState lm;  // (stats(true) above wrote the LM diagonal of the current Jacobian)
+  int iteration = 0, term;
   sum.termination = 0;
-  if (opt->verbosity >= 2) fprintf(stderr, "iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n%4d % .6e\n", 0, cost);
+  if (opt->verbosity >= 2) lm_print_header(cost);
   while (true) {
     if (iteration >= opt->max_num_iterations) { sum.termination = 0; break; }
-    if (gmax <= 1e-10) { sum.termination = 2; break; }
-    if (radius <= 1e-32) { sum.termination = 4; break; }
+    if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
     iteration++;
-    (void)have_diag;
-    const double inv_radius = 1.0 / radius;
+    const double inv_radius = 1.0 / lm.radius;
     // reduced system: J^T J of the camera side, damping, Schur corrections (camera-camera, then the border)
     VSL_HIP(ctx, hipMemsetAsync(Sf.p, 0, 8 * (size_t)nt * nt, q));
     VSL_HIP(ctx, hipMemsetAsync(rhsf.p, 0, 8 * (size_t)nt, q));
@@ -3479,20 +3446,16 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     VSL_HIP(ctx, hipStreamSynchronize(q));
     const double model_change = h[2], step_norm = sqrt(h[3] + h[6]), x_norm = sqrt(h[4] + h[7]), cand_cost = h[5];
     const bool ok = hflag[0] != 0 && hflag[1] != 0 && model_change > 0.0;
-    if (!ok) {
-      if (++invalid >= 5) { sum.termination = 4; break; }
-      radius *= 0.5;
-      if (opt->verbosity >= 2) fprintf(stderr, "%4d  invalid step, radius %.3e\n", iteration, radius);
+    const double radius_used = lm.radius;
+    LmInfo info;
+    const int verdict = lm_judge(lm, ok, cost, cand_cost, model_change, step_norm, x_norm, &info);
+    if (verdict >= 0) { sum.termination = verdict; break; }
+    if (verdict == LM_INVALID) {
+      if (opt->verbosity >= 2) lm_print_invalid(iteration, lm.radius);
       continue;  // the LM diagonal is reused (the Jacobian is unchanged)
     }
-    invalid = 0;
-    if (step_norm <= 1e-8 * (x_norm + 1e-8)) { sum.termination = 3; break; }
-    const double cost_change = cost - cand_cost;
-    if (fabs(cost_change) <= 1e-6 * cost) { sum.termination = 1; break; }
-    const double rel = cost_change / model_change;
-    if (opt->verbosity >= 2)
-      fprintf(stderr, "%4d % .6e % .3e % .3e % .3e % .3e % .3e\n", iteration, cand_cost, cost_change, gmax, step_norm, rel, radius);
-    if (rel > 1e-3) {
+    if (opt->verbosity >= 2) lm_print_row(iteration, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
+    if (verdict == LM_ACCEPTED) {
       std::swap(st.poses.p, st.cand_poses.p);
       std::swap(st.points.p, st.cand_points.p);
       VSL_HIP(ctx, hipMemcpyAsync(st.intr.p, cand_intr.p, 8 * 16, hipMemcpyDeviceToDevice, q));
@@ -3502,12 +3465,6 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
       if ((rc = read_scalars(ctx, st, h, 2))) return rc;
       gmax = h[1];
       sum.successful_steps++;
-      radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-      radius = std::min(1e16, radius);
-      decrease_factor = 2.0;
-    } else {
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.0;
     }
   }
   sum.iterations = iteration;

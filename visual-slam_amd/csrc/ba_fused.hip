@@ -38,11 +38,11 @@
 // Algorithmic bytes per LM iteration: n_obs * 24 + n_lms * 24 + n_cams * 56 + 128 in;
 // (6C)^2 * 8 + 6C * 8 + n_lms * 96 out.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 
 #include "ba_device.h"
 #include "dpp_chol.h"
+#include "lm_policy.h"
 #include "vsl_common.h"
 
 namespace {
@@ -953,9 +953,9 @@ __global__ __launch_bounds__(BF_THREADS) void baf_step_kernel(BfArgs a, const do
 // ---------------------------------------------------------------------------------------------------------------
 // The Levenberg-Marquardt decision on the device (one wavefront): what the host loop of vsl_ba_fused_solve does with
 // the mailbox after an iteration -- gradient tolerance, step validity, parameter / function tolerance, the
-// [upstream] Ceres trust-region update, accept / reject -- on the same numbers in the same order (IEEE double
-// throughout; the cube of the radius update is formed in double-double and rounded once, as the host's pow is), so the
-// trajectory is the host-decided one.  box = [cost | max landmark gradient | (int) Cholesky ok | . | gabs[128] |
+// [upstream] Ceres trust-region update, accept / reject -- through the same lm_gate / lm_judge (lm_policy.h) on the same
+// numbers in the same order (IEEE double throughout; only the cube of the radius update differs in form, see lm_cube),
+// so the trajectory is the host-decided one.  box = [cost | max landmark gradient | (int) Cholesky ok | . | gabs[128] |
 // 5 step partials per workgroup], the kernels' outputs in DEVICE memory; rec = one record per loop body in pinned host
 // memory: [seq, done, termination, iteration, successful, cost, radius, gmax, step norm, rel, candidate cost, cost change,
 // cur], seq written last behind a system-scope fence -- the host polls it.
@@ -1005,50 +1005,26 @@ __global__ __launch_bounds__(64) void baf_decide_kernel(BfLm* __restrict__ lm, c
   if (lane != 0) return;
   const double gmax = fmax(box[1], gm);
   const int chol_ok = *(const int*)(box + 2);
-  double step_norm = 0.0, rel = 0.0, cost_change = 0.0;
+  const bool ok = chol_ok != 0 && bad == 0.0 && model_change > 0.0;
+  double step_norm = 0.0;
   const double radius_used = st.radius;
-  int term = -1;
-  if (gmax <= 1e-10) {
-    term = 2;
-  } else if (st.radius <= 1e-32) {
-    term = 4;
-  } else {
+  LmState pol = {st.radius, st.decrease, st.invalid};
+  LmInfo info = {0.0, 0.0};
+  int term = lm_gate(pol, gmax);
+  if (term == LM_GO) {
     st.iteration++;
     step_norm = sqrt(step2);
-    const double x_norm = sqrt(x2);
-    const bool ok = chol_ok != 0 && bad == 0.0 && model_change > 0.0;
-    if (!ok) {
-      if (++st.invalid >= 5)
-        term = 4;
-      else
-        st.radius *= 0.5;
-    } else {
-      st.invalid = 0;
-      cost_change = st.cost - cand_cost;
-      if (step_norm <= 1e-8 * (x_norm + 1e-8)) {
-        term = 3;
-      } else if (fabs(cost_change) <= 1e-6 * st.cost) {
-        term = 1;
-      } else {
-        rel = cost_change / model_change;
-        if (rel > 1e-3) {
-          st.cost = cand_cost;
-          st.cur ^= 1;
-          st.successful++;
-          const double y = 2.0 * rel - 1.0;
-          const double p = y * y, pe = fma(y, y, -p);   // y^2 = p + pe
-          const double q = p * y, qe = fma(p, y, -q);   // p y = q + qe
-          const double y3 = q + (qe + pe * y);          // y^3 rounded once
-          st.radius = st.radius / fmax(1.0 / 3.0, 1.0 - y3);
-          st.radius = fmin(1e16, st.radius);
-          st.decrease = 2.0;
-        } else {
-          st.radius = st.radius / st.decrease;
-          st.decrease *= 2.0;
-        }
-      }
+    const int verdict = lm_judge(pol, ok, st.cost, cand_cost, model_change, step_norm, sqrt(x2), &info);
+    if (verdict >= 0) term = verdict;
+    if (verdict == LM_ACCEPTED) {
+      st.cost = cand_cost;
+      st.cur ^= 1;
+      st.successful++;
     }
   }
+  st.radius = pol.radius;
+  st.decrease = pol.decrease;
+  st.invalid = pol.invalid;
   if (term < 0 && st.iteration >= max_iters) term = 0;
   if (term >= 0) {
     st.termination = term;
@@ -1066,11 +1042,11 @@ __global__ __launch_bounds__(64) void baf_decide_kernel(BfLm* __restrict__ lm, c
   rec[6] = radius_used;
   rec[7] = gmax;
   rec[8] = step_norm;
-  rec[9] = rel;
+  rec[9] = info.rel;
   rec[10] = cand_cost;
-  rec[11] = cost_change;
+  rec[11] = info.cost_change;
   rec[12] = (double)st.cur;
-  rec[13] = (double)(chol_ok != 0 && bad == 0.0 && model_change > 0.0);
+  rec[13] = (double)ok;
   __threadfence_system();
   *(volatile double*)rec = (double)(body + 1);
 }
@@ -1078,11 +1054,13 @@ __global__ __launch_bounds__(64) void baf_decide_kernel(BfLm* __restrict__ lm, c
 // state of a fresh solve: the scaling pass left the initial cost in box[0]; record 0 carries it to the host
 __global__ void baf_lm_init_kernel(BfLm* __restrict__ lm, const double* __restrict__ box, double* __restrict__ rec_base) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const LmState pol;
   BfLm st;
   st.cost = box[0];
-  st.radius = 1e4;
-  st.decrease = 2.0;
-  st.iteration = st.invalid = st.successful = 0;
+  st.radius = pol.radius;
+  st.decrease = pol.decrease;
+  st.invalid = pol.invalid;
+  st.iteration = st.successful = 0;
   st.termination = -1;
   st.cur = st.done = st.bodies = st.pad = 0;
   *lm = st;
@@ -1092,10 +1070,6 @@ __global__ void baf_lm_init_kernel(BfLm* __restrict__ lm, const double* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-double bf_now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // The static layout of a solve, written straight into ONE pinned host block that goes to the device with ONE copy
 // (eleven pageable hipMemcpyAsync calls were 0.15 ms, the std::vector passes of the first version 0.9 ms at 157 k
 // observations):  [poses | points | intr | cam_intr | cam_free | obs_uv | obs_meta | lm_start | lm_pres | wg_info].
@@ -1265,12 +1239,12 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
                        int* handled) {
   *handled = 0;
   if (prob->n_cams > BF_CAMS) return VSL_OK;
-  const double t_start = bf_now_ms();
+  const double t_start = now_ms();
   const bool trace = getenv("VSL_BA_TRACE") != nullptr;  // phase times on stderr (developer aid)
   double t_lap = t_start;
   auto lap = [&](const char* what) {
     if (!trace) return;
-    const double t = bf_now_ms();
+    const double t = now_ms();
     fprintf(stderr, "  [fused ba] %-32s %8.3f ms\n", what, t - t_lap);
     t_lap = t;
   };
@@ -1454,7 +1428,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
     memset(last, 0, sizeof(last));
     int seen = 0;
     bool over = max_bodies == 0;
-    if (opt->verbosity >= 2) fprintf(stderr, "iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n");
+    if (opt->verbosity >= 2) lm_print_header();
     while (!over) {
       volatile double* r = recs + (size_t)BF_REC * (seen + 1);
       // wait for the decision of body `seen` (spin on pinned memory; a device error ends the wait through the query)
@@ -1472,7 +1446,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
       seen++;
       if (opt->verbosity >= 2) {
         if (last[13] != 0.0)
-          fprintf(stderr, "%4d % .6e % .3e % .3e % .3e % .3e % .3e\n", (int)last[3], last[10], last[11], last[7], last[8], last[9], last[6]);
+          lm_print_row((int)last[3], last[10], last[11], last[7], last[8], last[9], last[6]);
         else
           fprintf(stderr, "%4d  invalid step or termination before a step, radius %.3e\n", (int)last[3], last[6]);
       }
@@ -1505,16 +1479,15 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   double cost = mail[0];
   sum.initial_cost = cost;
 
-  double radius = 1e4, decrease_factor = 2.0;
-  int iteration = 0, invalid = 0;
+  LmState lm;
+  int iteration = 0, term;
   sum.termination = 0;
-  if (opt->verbosity >= 2)
-    fprintf(stderr, "iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n%4d % .6e\n", 0, cost);
+  if (opt->verbosity >= 2) lm_print_header(cost);
   while (true) {
     if (iteration >= opt->max_num_iterations) { sum.termination = 0; break; }
     // the whole iteration is enqueued without waiting; the gradient norm of the CURRENT point comes back with it
     // (it is a by-product of the Schur kernel), so the gradient-tolerance test is taken before the iteration counts
-    const double inv_radius = 1.0 / radius;
+    const double inv_radius = 1.0 / lm.radius;
     {
       VslStage s(ctx, VSL_STAGE_BA_SCHUR);
       if (T <= BF_WAVES)
@@ -1546,8 +1519,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
     BF_HIP(hipStreamSynchronize(ctx->stream));
     double gmax = mail[1];
     for (int x = 0; x < n; x++) gmax = std::max(gmax, (double)gabs[x]);
-    if (gmax <= 1e-10) { sum.termination = 2; break; }
-    if (radius <= 1e-32) { sum.termination = 4; break; }
+    if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
     iteration++;
     double model_change = 0, cand_cost = 0, step2 = 0, x2 = 0, bad = 0;
     for (int g = 0; g < G; g++) {  // workgroup order: fixed
@@ -1559,32 +1531,22 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
     }
     const double step_norm = sqrt(step2), x_norm = sqrt(x2);
     const bool ok = *chol_ok != 0 && bad == 0.0 && model_change > 0.0;
-    if (!ok) {
-      if (++invalid >= 5) { sum.termination = 4; break; }
-      radius *= 0.5;
-      if (opt->verbosity >= 2) fprintf(stderr, "%4d  invalid step, radius %.3e\n", iteration, radius);
+    const double radius_used = lm.radius;
+    LmInfo info;
+    const int verdict = lm_judge(lm, ok, cost, cand_cost, model_change, step_norm, x_norm, &info);
+    if (verdict >= 0) { sum.termination = verdict; break; }
+    if (verdict == LM_INVALID) {
+      if (opt->verbosity >= 2) lm_print_invalid(iteration, lm.radius);
       continue;
     }
-    invalid = 0;
-    if (step_norm <= 1e-8 * (x_norm + 1e-8)) { sum.termination = 3; break; }
-    const double cost_change = cost - cand_cost;
-    if (fabs(cost_change) <= 1e-6 * cost) { sum.termination = 1; break; }
-    const double rel = cost_change / model_change;
-    if (opt->verbosity >= 2)
-      fprintf(stderr, "%4d % .6e % .3e % .3e % .3e % .3e % .3e\n", iteration, cand_cost, cost_change, gmax, step_norm, rel, radius);
-    if (rel > 1e-3) {
+    if (opt->verbosity >= 2) lm_print_row(iteration, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
+    if (verdict == LM_ACCEPTED) {
       cost = cand_cost;
       std::swap(poses, cand_poses);
       std::swap(points, cand_points);
       a.poses = poses;
       a.points = points;
       sum.successful_steps++;
-      radius = radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-      radius = std::min(1e16, radius);
-      decrease_factor = 2.0;
-    } else {
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.0;
     }
   }
   sum.iterations = iteration;
@@ -1604,7 +1566,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   sum.solve_ms = dms[2];
   vsl_ctx_set_profiling(ctx, prof_was ? 1 : 0);
   lap("download");
-  sum.total_ms = bf_now_ms() - t_start;
+  sum.total_ms = now_ms() - t_start;
   if (opt->verbosity >= 1)
     fprintf(stderr, "vsl BA: iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", sum.iterations,
             sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "vsl_common.h"
+#include "lm_policy.h"
 
 namespace {
 
@@ -651,22 +652,22 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
   double cost = 0;
   if ((rc = pgo_linearize(ctx, st, opt, true, &cost))) return rc;
   sum.initial_cost = cost;
-  double radius = 1e4, decrease = 2.0, gmax = 1e300;
-  int it = 0, invalid = 0;
+  LmState lm;
+  double gmax = 1e300;
+  int it = 0, term;
   bool need_gmax = true;
   while (true) {
     if (it >= opt->max_num_iterations) { sum.termination = 0; break; }
-    if (!need_gmax && gmax <= 1e-10) { sum.termination = 2; break; }
-    if (radius <= 1e-32) { sum.termination = 4; break; }
+    if ((term = lm_gate(lm, need_gmax ? INFINITY : gmax)) >= 0) { sum.termination = term; break; }
     if (n == 0) { sum.termination = 2; break; }
     // damped system + gradient norm
     if (st.ld > 0)
       hipLaunchKernelGGL(pgo_damp_band_kernel, dim3((unsigned)((st.h_elems + 255) / 256)), dim3(256), 0, s, n, st.h_elems, st.ld,
-                         st.H.as<double>(), st.g.as<double>(), st.scale.as<double>(), 1.0 / radius, st.A.as<double>(), st.b.as<double>(),
+                         st.H.as<double>(), st.g.as<double>(), st.scale.as<double>(), 1.0 / lm.radius, st.A.as<double>(), st.b.as<double>(),
                          st.gabs.as<double>());
     else
       hipLaunchKernelGGL(pgo_damp_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, n, st.H.as<double>(), st.g.as<double>(),
-                         st.scale.as<double>(), 1.0 / radius, st.A.as<double>(), st.b.as<double>(), st.gabs.as<double>());
+                         st.scale.as<double>(), 1.0 / lm.radius, st.A.as<double>(), st.b.as<double>(), st.gabs.as<double>());
     const bool gmax_pending = need_gmax;
     if (need_gmax) {
       // max |gradient| of this linearisation: reduced here, READ with the step's scalars below (round 4: one host round
@@ -714,36 +715,25 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
     }
     if (gmax_pending) {
       gmax = sc[0];
-      if (gmax <= 1e-10) {
+      if (gmax <= LM_GRADIENT_TOLERANCE) {  // lm_gate's first test, one step late
         it--;
         sum.termination = 2;
         break;
       }
     }
     if (st.ld > 0) sc[1] -= sc[5];
-    const bool ok = finite != 0 && sc[1] > 0.0;
-    if (!ok) {
-      if (++invalid >= 5) { sum.termination = 4; break; }
-      radius *= 0.5;
-      continue;
-    }
-    invalid = 0;
     const double model = sc[1], step_norm = sqrt(sc[2]), x_norm = sqrt(sc[3]), cand_cost = sc[4];
-    if (step_norm <= 1e-8 * (x_norm + 1e-8)) { sum.termination = 3; break; }
-    const double change = cost - cand_cost;
-    if (fabs(change) <= 1e-6 * cost) { sum.termination = 1; break; }
-    const double rel = change / model;
-    if (opt->verbosity >= 2) fprintf(stderr, "pgo %3d cost %.6e change %.3e |g| %.3e step %.3e rho %.3e radius %.3e\n", it, cand_cost, change, gmax, step_norm, rel, radius);
-    if (rel > 1e-3) {
+    const double radius_used = lm.radius;
+    LmInfo info;
+    const int verdict = lm_judge(lm, finite != 0 && model > 0.0, cost, cand_cost, model, step_norm, x_norm, &info);
+    if (verdict >= 0) { sum.termination = verdict; break; }
+    if (verdict == LM_INVALID) continue;
+    if (opt->verbosity >= 2) fprintf(stderr, "pgo %3d cost %.6e change %.3e |g| %.3e step %.3e rho %.3e radius %.3e\n", it, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
+    if (verdict == LM_ACCEPTED) {
       std::swap(st.poses.p, st.cand.p);
-      if ((rc = pgo_linearize(ctx, st, opt, false, &cost))) return rc;
+      if ((rc = pgo_linearize(ctx, st, opt, false, &cost))) return rc;  // (the accepted point's cost comes from here)
       need_gmax = true;
       sum.successful_steps++;
-      radius = std::min(1e16, radius / std::max(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3)));
-      decrease = 2.0;
-    } else {
-      radius /= decrease;
-      decrease *= 2.0;
     }
   }
   sum.iterations = it;

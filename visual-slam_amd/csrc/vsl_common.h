@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -29,6 +30,11 @@
 #define VSL_TILE_LY 7
 #endif
 #define VSL_TIE_OVERFLOW_FLAG 0x40000000u  // set in tie_count by exact_bits_kernel when an image's list overflowed
+
+// wall clock in milliseconds (host timings of the summaries and traces)
+inline double now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 struct vsl_ctx {
   int device = 0;
