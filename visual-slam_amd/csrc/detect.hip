@@ -471,7 +471,6 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
 //   terminate and the result is the sequential one).  Acceptance stops at num_features.
 #define SEL_THREADS 1024
 #define SEL_CHUNK 8192
-#define SEL_EMPTY 0xFFFFFFFFu
 #define SEL_BINS 1024      // response bins of the counting sort (= threads of the workgroup)
 #define SEL_MAX_BLOCKERS 6  // blockers of a candidate kept in registers, 10 bits each in one 64-bit word (more: the cell lists are walked again)
 static_assert(SEL_THREADS <= 1024 && SEL_MAX_BLOCKERS * 10 <= 64, "blocker packing");
@@ -484,45 +483,92 @@ struct SelShared {
   int n_chunk;
 };
 
-// Exclusive prefix count of `p` over the workgroup (thread order) and the total.
+// Exclusive prefix count of `p` over the workgroup (thread order) and the total.  The sixteen wave totals are
+// scanned across a row of sixteen lanes (four DPP row shifts) and picked by lane index: sixteen `w < wave`
+// select masks would live in 32 SGPRs all through the greedy loop.
 __device__ __forceinline__ int block_scan(bool p, int* wave_tot, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned long long m = __ballot(p);
-  const int within = __popcll(m & ((1ull << lane) - 1ull));
+  const int within = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  const int mine = __popcll(m);
   __syncthreads();
-  if (lane == 0) wave_tot[wave] = __popcll(m);
+  if (lane == 0) wave_tot[wave] = mine;
   __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 16; w++) {
-    const int v = wave_tot[w];
-    off += (w < wave) ? v : 0;
-    tot += v;
-  }
-  total = tot;
-  return off + within;
+  int x = wave_tot[lane & 15];
+  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);  // row_shr:1, lanes shifted in from outside the row read 0
+  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);
+  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, true);
+  total = __builtin_amdgcn_readlane(x, 15);
+  return __builtin_amdgcn_readlane(x, wave) - mine + within;
 }
 
-// Static LDS: sized for up to SEL_MAX_CELLS 8x8-px cells (752x480 needs 96 x 62 = 5952 with the empty ring); gfx950 lets one
-// workgroup own (almost) all 160 KiB of its CU's LDS.
+// Static LDS: sized for up to SEL_MAX_CELLS 8x8-px cells (752x480 needs 96 x 62 = 5952 with the empty ring).  The
+// workgroup must leave room on its CU for a workgroup of any other kernel of the pass (describe_tile_kernel is
+// the largest at 39,344 B of the CU's 163,840 B; tests/test_select_footprint.py holds the sum), so the grid is
+// packed: a corner accepted into a cell is identified by the low three bits of x and of y (the cell fixes the
+// rest) -- one byte per slot, two slots = one u16 per cell -- and a list head is a batch rank < 1024 in a u16.
 #define SEL_MAX_CELLS 6144
+#define SEL_ACC_VALID 0x40u   // slot byte: valid | (y & 7) << 3 | (x & 7); 0 = empty
+#define SEL_HEAD_EMPTY 0xFFFFu
 // the key array is padded by one key per 32 (bank-conflict relief for the strided layouts of the sort)
 #define SEL_KEYS_PADDED (SEL_CHUNK + SEL_CHUNK / 32)
 #define SEL_PHYS(i) ((i) + ((i) >> 5))
-#define SEL_LDS_BYTES (SEL_KEYS_PADDED * 8 + SEL_MAX_CELLS * 2 * 4 + SEL_THREADS * 4 * 3 + SEL_MAX_CELLS * 4 + 2048)
-static_assert(SEL_LDS_BYTES <= 160 * 1024, "selection kernel LDS budget");
+// keys | SelShared | three SEL_THREADS-word arrays (bin counters of the sort, then batch nodes + states) | packed
+// grid (2 B accepted slots + 2 B list head per cell) | pad.  The last of the three arrays, the grid and the pad
+// together are the SEL_CHUNK-word staging array of the in-bin ranking (the grid is initialised after it).
+#define SEL_GRID_BYTES (SEL_MAX_CELLS * 2 * 2)
+#define SEL_STAGE_PAD (SEL_CHUNK * 4 - SEL_THREADS * 4 - SEL_GRID_BYTES)
+#define SEL_LDS_BYTES (SEL_KEYS_PADDED * 8 + 2048 + SEL_THREADS * 4 * 3 + SEL_GRID_BYTES + SEL_STAGE_PAD)
+static_assert(SEL_STAGE_PAD >= 0, "ranking staging array");
+static_assert(SEL_LDS_BYTES <= 160 * 1024 - 39344, "selection kernel LDS budget: one describe_tile_kernel workgroup fits beside it");
 
-// Register-blocked bitonic network on N = 1024 << LOGK keys in LDS (descending): a thread holds the 1 << LOGK
-// keys whose indices differ in bits b .. b+LOGK-1, so up to LOGK consecutive sub-steps are compare-exchanges
-// between its own registers; between such groups the keys pass through LDS once to change b.
-template <int LOGK>
-__device__ __forceinline__ void sel_sort_blocked(uint64_t* keys, int tid, int log_n) {
+// Exchange of the 16-bit half `idx & 1` of the 32-bit word that holds element idx of a u16 array (LDS has no
+// 16-bit exchange): returns the old half.
+__device__ __forceinline__ uint32_t sel_xchg16(volatile uint16_t* arr, int idx, uint32_t v) {
+  uint32_t* word = (uint32_t*)arr + (idx >> 1);
+  const int s = (idx & 1) * 16;
+  uint32_t old = *(volatile uint32_t*)word;
+  for (;;) {
+    const uint32_t got = atomicCAS(word, old, (old & ~(0xFFFFu << s)) | (v << s));
+    if (got == old) break;
+    old = got;
+  }
+  return (old >> s) & 0xFFFFu;
+}
+
+// A list head as a batch rank, -1 = none.
+__device__ __forceinline__ int sel_head_rank(uint32_t h) { return h == SEL_HEAD_EMPTY ? -1 : (int)h; }
+
+// Put slot byte b into the first empty slot of cell idx (nothing if both are taken: a third corner at distance
+// >= 8 from two others does not fit into an 8 x 8 cell).
+__device__ __forceinline__ void sel_acc_insert(volatile uint16_t* arr, int idx, uint32_t b) {
+  uint32_t* word = (uint32_t*)arr + (idx >> 1);
+  const int s = (idx & 1) * 16;
+  uint32_t old = *(volatile uint32_t*)word;
+  for (;;) {
+    const uint32_t cur = (old >> s) & 0xFFFFu;
+    if ((cur & 0xFF00u) != 0u) break;
+    const uint32_t got = atomicCAS(word, old, old | (b << (s + ((cur & 0xFFu) ? 8 : 0))));
+    if (got == old) break;
+    old = got;
+  }
+}
+
+// Register-blocked bitonic network on N = REPS * (1024 << LOGK) keys in LDS (descending): a thread holds the
+// 1 << LOGK keys whose indices differ in bits b .. b+LOGK-1, so up to LOGK consecutive sub-steps are
+// compare-exchanges between its own registers; between such groups the keys pass through LDS once to change b.
+// REPS = 2: a thread does this for two such sets in turn (four keys in registers, not eight, for 8192 keys).
+template <int LOGK, int REPS>
+__device__ __forceinline__ void sel_sort_blocked(uint64_t* keys, int tid0, int log_n) {
   constexpr int KPT = 1 << LOGK;
   for (int m = 1; m <= log_n; m++) {
     const int k = 1 << m;
     for (int top = m - 1; top >= 0;) {
       const int b = top >= LOGK - 1 ? top - (LOGK - 1) : 0;  // this group: bits top .. b
       const int nb = top - b + 1;
+#pragma unroll 1
+      for (int tid = tid0; tid < REPS * SEL_THREADS; tid += SEL_THREADS) {
       const int t_hi = tid >> b, t_lo = tid & ((1 << b) - 1);
       const int i0 = (t_hi << (b + LOGK)) | t_lo;  // index of the thread's key r = 0; key r sits at i0 | (r << b)
       uint64_t rk[KPT];
@@ -545,6 +591,7 @@ __device__ __forceinline__ void sel_sort_blocked(uint64_t* keys, int tid, int lo
       }
 #pragma unroll
       for (int r = 0; r < KPT; r++) keys[SEL_PHYS(i0 | (r << b))] = rk[r];
+      }
       __syncthreads();
       top = b - 1;
     }
@@ -561,7 +608,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
                                                              int w, int h, size_t cand_cap, int F, int first,
                                                              int num_features, int border, double quality,
                                                              uint32_t* __restrict__ grid_scratch, int bucket_cap) {
-  __shared__ __align__(16) unsigned char smem[GRID_GLOBAL ? (SEL_KEYS_PADDED * 8 + SEL_THREADS * 4 * 3 + 2048) : SEL_LDS_BYTES];
+  __shared__ __align__(16) unsigned char smem[SEL_LDS_BYTES];
   const int slot = first + blockIdx.x;
   const uint64_t* __restrict__ cand = cand_all + (size_t)slot * cand_cap;
   const int n_cand_raw = meta[(size_t)slot * VSL_META_STRIDE + VSL_META_NCAND];
@@ -570,21 +617,18 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
   // clamping, so its nine list heads / eighteen accepted slots are independent loads issued together
   const int gw = (w + 7) / 8 + 2, gh = (h + 7) / 8 + 2, cells = (gw * gh + 1) & ~1;  // (even: the arrays behind stay 8-byte aligned)
   // LDS carve-up (all regions 8-byte aligned)
-  uint64_t* keys = (uint64_t*)smem;                 // SEL_CHUNK sorted keys
-  SelShared* sh = (SelShared*)(keys + SEL_KEYS_PADDED);
-  // cells * 2 accepted corners, packed x | y << 16, then cells batch list heads (-1 = empty); volatile:
+  uint64_t* keys = (uint64_t*)smem;                 // SEL_CHUNK sorted keys (8 B), or their pixel positions (4 B, unpadded) after the in-bin ranking
+  uint32_t* keys32 = (uint32_t*)smem;
+  SelShared* sh = (SelShared*)(smem + SEL_KEYS_PADDED * 8);
+  int* next = (int*)(smem + SEL_KEYS_PADDED * 8 + 2048);  // SEL_THREADS
+  // cells u16 with the two accepted slots of a cell, then cells u16 batch list heads (SEL_HEAD_EMPTY = none); volatile:
   // the global variant must not keep them in registers / stale L1 lines between workgroup barriers
-  volatile uint32_t* acc = GRID_GLOBAL ? (volatile uint32_t*)(grid_scratch + (size_t)slot * cells * 3) : (volatile uint32_t*)(sh + 1);
-  volatile int* head = (volatile int*)(acc + 2 * (size_t)cells);
-  int* next = GRID_GLOBAL ? (int*)(sh + 1) : (int*)(head + cells);  // SEL_THREADS
+  volatile uint16_t* acc = GRID_GLOBAL ? (volatile uint16_t*)(grid_scratch + (size_t)slot * cells) : (volatile uint16_t*)(next + 3 * SEL_THREADS);
+  volatile uint16_t* head = acc + cells;
   // batch member u: node[u] = (position x | y << 16, next member of its cell's list) -- one 8-byte read per list step
   unsigned long long* node = (unsigned long long*)next;  // SEL_THREADS (the space of `next` and the array after it)
   int* state = next + 2 * SEL_THREADS;              // SEL_THREADS: 0 undecided, 1 accepted, 2 rejected
   const int tid = threadIdx.x;
-
-  for (int i = tid; i < 2 * cells; i += SEL_THREADS) acc[i] = SEL_EMPTY;
-  for (int i = tid; i < cells; i += SEL_THREADS) head[i] = -1;
-  __syncthreads();
 
   int n_acc = 0, n_out = 0;
   unsigned long long hi = ~0ull;  // keys >= hi have been consumed
@@ -600,11 +644,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
   // bits of the response -- SEL_BINS bins between the threshold and the maximum (both known), bin 0 = largest --
   // puts every key into its bin's slot range, and a key's final rank inside its bin is the number of larger keys
   // there (bins hold a handful of keys: the responses of real images spread over ~6 binades = ~850 bins).  Four
-  // passes with a handful of workgroup barriers instead of the 35 LDS exchanges of the bitonic network for 8192
+  // passes with a handful of workgroup barriers instead of the 49 LDS exchanges of the bitonic network for 8192
   // keys, which stays as the path for later chunks and for bins fuller than bucket_cap (plateaus of equal responses).
   int* bcount = next;                    // the three arrays alias next / cxy / state, which only the greedy uses
   int* bstart = next + SEL_THREADS;
   int* bcursor = next + 2 * SEL_THREADS;
+  uint32_t* stage = (uint32_t*)bcursor;  // SEL_CHUNK positions in rank order: over bcursor (dead by then), the LDS grid and the pad
   static_assert(SEL_BINS == SEL_THREADS, "one bin per thread");
   const uint32_t hi_max = (uint32_t)vsl_float_to_ordered(maxv) ^ 0x80000000u;
   const uint32_t hi_floor = (uint32_t)vsl_float_to_ordered(thr) ^ 0x80000000u;
@@ -653,6 +698,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
     bucket_sort = remaining <= SEL_CHUNK && fullest <= bucket_cap;
     __syncthreads();
   }
+  // the grid starts empty (two cells per word); the counting sort does this itself after its staging array is dead
+  if (!bucket_sort) {
+    for (int i = tid; i < cells; i += SEL_THREADS) ((volatile uint32_t*)acc)[i] = i < (cells >> 1) ? 0u : ~0u;
+    __syncthreads();
+  }
+  bool compact = false;  // the sorted chunk is keys32[r], not keys[SEL_PHYS(r)]
 
   while (remaining > 0 && n_acc < num_features) {
     // ---- choose the chunk [lo, hi): all remaining keys, or the SEL_CHUNK largest of them
@@ -698,27 +749,22 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
       }
       __syncthreads();
       n_chunk = remaining;
-      unsigned long long mykey[SEL_CHUNK / SEL_THREADS];
-      int mypos[SEL_CHUNK / SEL_THREADS];
-#pragma unroll
-      for (int k = 0; k < SEL_CHUNK / SEL_THREADS; k++) {
-        const int p = tid + SEL_THREADS * k;
-        mypos[k] = -1;
-        if (p < n_chunk) {
-          const unsigned long long key = keys[SEL_PHYS(p)];
-          const int bin = (int)(bin_top - min((uint32_t)(key >> 32) >> bshift, bin_top));
-          const int s0 = bstart[bin], e0 = s0 + bcount[bin];
-          int larger = 0;
-          for (int q = s0; q < e0; q++) larger += keys[SEL_PHYS(q)] > key;
-          mykey[k] = key;
-          mypos[k] = s0 + larger;
-        }
+      // only the pixel position of a key is read once it is ranked: it goes to its rank in the staging array (no
+      // key is held in registers across a barrier), and the staging array is copied over the keys
+      for (int p = tid; p < n_chunk; p += SEL_THREADS) {
+        const unsigned long long key = keys[SEL_PHYS(p)];
+        const int bin = (int)(bin_top - min((uint32_t)(key >> 32) >> bshift, bin_top));
+        const int s0 = bstart[bin], e0 = s0 + bcount[bin];
+        int larger = 0;
+        for (int q = s0; q < e0; q++) larger += keys[SEL_PHYS(q)] > key;
+        stage[s0 + larger] = (uint32_t)key;
       }
       __syncthreads();
-#pragma unroll
-      for (int k = 0; k < SEL_CHUNK / SEL_THREADS; k++)
-        if (mypos[k] >= 0) keys[SEL_PHYS(mypos[k])] = mykey[k];
+      for (int p = tid; p < n_chunk; p += SEL_THREADS) keys32[p] = stage[p];
       __syncthreads();
+      for (int i = tid; i < cells; i += SEL_THREADS) ((volatile uint32_t*)acc)[i] = i < (cells >> 1) ? 0u : ~0u;
+      __syncthreads();
+      compact = true;
       bucket_sort = false;
     } else {
       // ---- gather the chunk into LDS and pad to a power of two
@@ -737,13 +783,13 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
       while (N < n_chunk) N <<= 1;
       for (int i = n_chunk + tid; i < N; i += SEL_THREADS) keys[SEL_PHYS(i)] = 0ull;
       __syncthreads();
-      // ---- bitonic sort, descending.  With 2, 4 or 8 keys per thread (N = 2048 / 4096 / 8192) the network is
-      // register-blocked (sel_sort_blocked): ceil(m / log2(keys per thread)) LDS exchanges for the stage k = 2^m,
-      // e.g. 35 workgroup barriers for 8192 keys instead of 91 (one per sub-step).
+      // ---- bitonic sort, descending.  With 2 or 4 keys per thread in registers (N = 2048; 4096 and, in two turns,
+      // 8192) the network is register-blocked (sel_sort_blocked): ceil(m / log2(keys in registers)) LDS exchanges for
+      // the stage k = 2^m, e.g. 49 workgroup barriers for 8192 keys instead of 91 (one per sub-step).
       if (N >= 2048) {
-        if (N == 8192) sel_sort_blocked<3>(keys, tid, 13);
-        else if (N == 4096) sel_sort_blocked<2>(keys, tid, 12);
-        else sel_sort_blocked<1>(keys, tid, 11);
+        if (N == 8192) sel_sort_blocked<2, 2>(keys, tid, 13);
+        else if (N == 4096) sel_sort_blocked<2, 1>(keys, tid, 12);
+        else sel_sort_blocked<1, 1>(keys, tid, 11);
       } else {
         for (int k = 2; k <= N; k <<= 1) {
           for (int j = k >> 1; j > 0; j >>= 1) {
@@ -765,38 +811,35 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
     // ---- greedy, SEL_THREADS ranks per batch
     for (int r0 = 0; r0 < n_chunk && n_acc < num_features; r0 += SEL_THREADS) {
       const int r = r0 + tid;
-      int px = 0, py = 0, cell = 0, cx = 0, cy = 0;
+      int px = 0, py = 0, cell = 0;
       bool alive = false;
       if (r < n_chunk) {
-        const uint32_t pix = (uint32_t)(keys[SEL_PHYS(r)] & 0xFFFFFFFFull);
+        const uint32_t pix = compact ? keys32[r] : (uint32_t)(keys[SEL_PHYS(r)] & 0xFFFFFFFFull);
         py = (int)(pix >> 16);
         px = (int)(pix & 0xFFFFu);
-        cx = (px >> 3) + 1;
-        cy = (py >> 3) + 1;
-        cell = cy * gw + cx;
-        alive = true;
-        uint32_t a18[18];
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-          const int c2 = cell + (k / 3 - 1) * gw + (k % 3 - 1);
-          // both slots of a cell in one 8-byte read (the LDS pipe, not the instruction count, is what this phase waits for)
-          const unsigned long long two = *(volatile const unsigned long long*)&acc[2 * c2];
-          a18[2 * k] = (uint32_t)two;
-          a18[2 * k + 1] = (uint32_t)(two >> 32);
-        }
+        cell = ((py >> 3) + 1) * gw + (px >> 3) + 1;
+        // a slot of the neighbour cell at offset (ox, oy) holds the low bits of a corner there: its distance is
+        // (x & 7) - 8 ox - slot x, likewise in y -- the px - ax, py - ay of the unpacked coordinates
+        const int lx = px & 7, ly = py & 7;
         int near = 0;  // branch-free: eighteen short-circuit tests compile to eighteen exec-mask branches
 #pragma unroll
-        for (int k = 0; k < 18; k++) {
-          const uint32_t a = a18[k];
-          const int dx = px - (int)(a & 0xFFFF), dy = py - (int)(a >> 16);
-          const unsigned d2 = (unsigned)(dx * dx) + (unsigned)(dy * dy);  // (an empty slot decodes to 65535, 65535: masked below)
-          near |= (int)(a != SEL_EMPTY) & (int)(d2 < 64u);
+        for (int oy = -1; oy <= 1; oy++) {
+          const int row = cell + oy * gw;
+          const uint32_t t0 = acc[row - 1], t1 = acc[row], t2 = acc[row + 1];  // a row of three cells at a time
+#pragma unroll
+          for (int k = 0; k < 6; k++) {
+            const uint32_t b = ((k >> 1) == 0 ? t0 : (k >> 1) == 1 ? t1 : t2) >> (8 * (k & 1));
+            const int dx = lx - 8 * ((k >> 1) - 1) - (int)(b & 7u), dy = ly - 8 * oy - (int)((b >> 3) & 7u);
+            const unsigned d2 = (unsigned)(dx * dx) + (unsigned)(dy * dy);
+            near |= (int)((b & SEL_ACC_VALID) != 0u) & (int)(d2 < 64u);
+          }
         }
         alive = near == 0;
       }
       state[tid] = alive ? 0 : 2;
       {
-        const int nxt = alive ? atomicExch((int*)&head[cell], tid) : -1;
+        const uint32_t prev = alive ? sel_xchg16(head, cell, (uint32_t)tid) : SEL_HEAD_EMPTY;
+        const int nxt = sel_head_rank(prev);
         node[tid] = ((unsigned long long)(uint32_t)nxt << 32) | ((uint32_t)px | ((uint32_t)py << 16));
       }
       __syncthreads();
@@ -808,24 +851,28 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
       unsigned long long blk = 0ull;  // the last SEL_MAX_BLOCKERS blockers, 10 bits each (batch-local ranks): a register ARRAY
                                       // indexed by nb costs six compare / select pairs per insertion
       if (alive) {
-        int h9[9];
+#pragma unroll 1
+        for (int oy = -1; oy <= 1; oy++) {  // a row of three list heads at a time
+          const int row = cell + oy * gw;
+          uint32_t h3[3];
 #pragma unroll
-        for (int k = 0; k < 9; k++) h9[k] = head[cell + (k / 3 - 1) * gw + (k % 3 - 1)];
+          for (int k = 0; k < 3; k++) h3[k] = head[row + k - 1];
 #pragma unroll
-        for (int k = 0; k < 9; k++)
-          for (int u = h9[k]; u >= 0;) {
-            const unsigned long long nd = node[u];
-            const int uu = u;
-            u = (int)(nd >> 32);
-            if (uu < tid) {
-              const uint32_t q = (uint32_t)nd;
-              const int dx = px - (int)(q & 0xFFFF), dy = py - (int)(q >> 16);
-              if (dx * dx + dy * dy < 64) {
-                blk = (blk << 10) | (unsigned long long)(unsigned)uu;
-                nb++;
+          for (int k = 0; k < 3; k++)
+            for (int u = sel_head_rank(h3[k]); u >= 0;) {
+              const unsigned long long nd = node[u];
+              const int uu = u;
+              u = (int)(nd >> 32);
+              if (uu < tid) {
+                const uint32_t q = (uint32_t)nd;
+                const int dx = px - (int)(q & 0xFFFF), dy = py - (int)(q >> 16);
+                if (dx * dx + dy * dy < 64) {
+                  blk = (blk << 10) | (unsigned long long)(unsigned)uu;
+                  nb++;
+                }
               }
             }
-          }
+        }
       }
       bool undecided = alive;
       while (__ballot(undecided) != 0ull) {
@@ -841,7 +888,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
               }
           } else {  // crowded neighbourhood: walk the cell lists again
             for (int k = 0; k < 9; k++)
-                for (int u = head[cell + (k / 3 - 1) * gw + (k % 3 - 1)], un = -1; u >= 0; u = un) {
+                for (int u = sel_head_rank(head[cell + (k / 3 - 1) * gw + (k % 3 - 1)]), un = -1; u >= 0; u = un) {
                   const unsigned long long nd = node[u];
                   un = (int)(nd >> 32);
                   if (u < tid) {
@@ -875,11 +922,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
         out[2 * pos] = px;
         out[2 * pos + 1] = py;
       }
-      if (keep) {
-        const uint32_t packed = (uint32_t)px | ((uint32_t)py << 16);
-        if (atomicCAS((uint32_t*)&acc[2 * cell], SEL_EMPTY, packed) != SEL_EMPTY) atomicCAS((uint32_t*)&acc[2 * cell + 1], SEL_EMPTY, packed);
-      }
-      if (alive) head[cell] = -1;
+      if (keep) sel_acc_insert(acc, cell, SEL_ACC_VALID | (uint32_t)((py & 7) << 3) | (uint32_t)(px & 7));
+      if (alive) head[cell] = (uint16_t)SEL_HEAD_EMPTY;
       n_acc = min(num_features, n_acc + total);
       n_out += total_out;
       __syncthreads();
@@ -921,7 +965,7 @@ int vsl_launch_detect(vsl_ctx* ctx, vsl_frames* f, int first, int n, int num_fea
   const int cells = (((f->w + 7) / 8 + 2) * ((f->h + 7) / 8 + 2) + 1) & ~1;  // with the ring of empty cells, even (as select_kernel counts them)
   const bool grid_global = cells > SEL_MAX_CELLS;
   if (grid_global && !f->sel_grid) {
-    VSL_HIP(ctx, hipMalloc((void**)&f->sel_grid, sizeof(uint32_t) * 3 * (size_t)cells * f->max_images));
+    VSL_HIP(ctx, hipMalloc((void**)&f->sel_grid, sizeof(uint32_t) * (size_t)cells * f->max_images));
   }
   const int w = f->w, h = f->h;
   {

@@ -161,7 +161,7 @@ struct vsl_frames {
   int32_t* tile_off = nullptr;     // [max_images][tiles + 1]: keypoints of an image by 64 x 64 tile (describe.hip), null when the tile kernel does not apply
   uint32_t* tile_ent = nullptr;    // [max_images][F]: (keypoint << 12) | (y in tile << 6) | x in tile, tile-major
   int tiles_x = 0, tiles = 0;
-  uint32_t* sel_grid = nullptr;    // [max_images][cells][3]: selection grid of images too large for LDS (lazy)
+  uint32_t* sel_grid = nullptr;    // [max_images][cells]: packed selection grid (u16 accepted slots, then u16 list heads) of images too large for LDS (lazy)
   // rBRIEF near-tie records (see describe.hip)
   int32_t* tie_count = nullptr;    // [1]
   int32_t* tie_rec = nullptr;      // [tie_cap][4]  (slot, keypoint, bit, unused)
