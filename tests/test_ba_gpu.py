@@ -295,6 +295,53 @@ def test_bundle_adjust_is_run_to_run_reproducible(ctx, orc, synth):
     assert np.array_equal(a1.poses, a2.poses) and np.array_equal(a1.points, a2.points)
 
 
+def test_context_arena_reuse_and_growth_leave_the_results_unchanged(vsl, orc, synth):
+    # vsl_bundle_adjust borrows ONE cached device arena from its context on both of its paths (dev_arena.h).  On one
+    # context: A (fused path, small) allocates it; B (ba.hip's loop under "ba_no_fused", larger) makes it grow; A reuses
+    # the grown block; a pose graph (an arena of its own) must leave it alone; A once more.  Every BA solve equals, bit
+    # for bit, the same solve on a fresh context (fixed-order reductions on these paths: see the test above).
+    def problem(seed, n_kf, n_lms, n_fixed):
+        d = synth.ba_problem(seed, n_kf=n_kf, n_lms=n_lms)
+        d["cam_fixed"][:] = 0
+        d["cam_fixed"][:n_fixed] = 1
+        return d
+
+    dA, dB = problem(330, 4, 60, 3), problem(272, 7, 1237, 2)
+    g = synth.pose_graph(21, 30, 10, meas_noise=0.0, drift=0.02)
+
+    def solve(c, d, no_fused):
+        a = _arr(orc, d)
+        c.set_diagnostic("ba_no_fused", no_fused)
+        try:
+            s = c.bundle_adjust(a, max_iters=8)
+        finally:
+            c.set_diagnostic("ba_no_fused", 0)
+        return s, a
+
+    plan = [(dA, 0), (dB, 1), (dA, 0), None, (dA, 0)]   # None: the pose graph
+    shared = vsl.Context(0)
+    try:
+        got = []
+        for step in plan:
+            if step is None:
+                pg = orc.PgoArrays(g["poses"], g["node_fixed"], g["edge_a"], g["edge_b"], g["edge_meas"])
+                assert shared.pose_graph_optimize(pg, True, 1.0, 20).iterations > 0
+            else:
+                got.append(solve(shared, *step))
+    finally:
+        shared.close()
+    assert len(got) == 4
+    for (s, a), step in zip(got, [p for p in plan if p is not None]):
+        fresh = vsl.Context(0)
+        try:
+            es, ea = solve(fresh, *step)
+        finally:
+            fresh.close()
+        assert s.iterations > 0
+        assert (s.iterations, s.termination, s.successful_steps, s.final_cost) == (es.iterations, es.termination, es.successful_steps, es.final_cost)
+        assert np.array_equal(a.poses, ea.poses) and np.array_equal(a.points, ea.points)
+
+
 @pytest.mark.parametrize("dense", [0, 1])
 def test_large_system_bundle_adjust_is_run_to_run_reproducible(ctx, orc, synth, dense):
     # large-system path: the Schur complement is a gather over per-block pair lists SORTED after their (atomic) fill, the

@@ -32,6 +32,7 @@
 
 #include "vsl_common.h"
 #include "lm_policy.h"
+#include "dev_arena.h"
 #include "ba_device.h"
 #include "ba_large.h"
 
@@ -1277,22 +1278,6 @@ __global__ void ba_raw_blocks_kernel(BaDims D, const double* __restrict__ poses,
 }
 
 // ------------------------------------------------------------------------------- host-side state
-struct DevBuf {
-  void* p = nullptr;
-  bool owned = false;  // arena-backed buffers (BaState) are not freed one by one
-  ~DevBuf() {
-    if (p && owned) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() {
-    return (T*)p;
-  }
-  hipError_t alloc(size_t bytes) {
-    owned = true;
-    return hipMalloc(&p, bytes > 0 ? bytes : 8);
-  }
-};
-
 struct BaState {
   BaDims D;
   int G = 1, lm_per_wg = 1, nb_obs = 1, nb_upd = 1;
@@ -1300,18 +1285,31 @@ struct BaState {
   int bl_seg = 1;  // ... in bal_cam_kernel (recompute form: an observation is a chain of dependent gathers, one per thread)
   bool small = true;
   std::vector<int> perm;  // sorted position -> caller observation index
-  DevBuf poses, cand_poses, points, cand_points, intr, cam_intr, cam_free, free_cams, obs_cam, obs_lm, obs_uv, lm_start,
-      cam_start, cam_obs, r, F, E, scale_c, scale_l, n2l, grad_l, H, g_c, diag_c, diag_l, gabs, S, rhs, S_part, rhs_part,
-      Pinv, bl, dc, dl, partials, scalars, flag, cam_part;
+  // ONE device allocation per solve (dev_arena.h), carved into the buffers below: vsl_bundle_adjust borrows the
+  // context's cached arena, a session and the parity hooks own theirs
+  DevArena arena;
+  double *poses = nullptr, *cand_poses = nullptr, *points = nullptr, *cand_points = nullptr, *intr = nullptr, *obs_uv = nullptr;
+  double *r = nullptr, *F = nullptr, *E = nullptr, *scale_c = nullptr, *scale_l = nullptr, *n2l = nullptr, *grad_l = nullptr;
+  double *H = nullptr, *g_c = nullptr, *diag_c = nullptr, *diag_l = nullptr, *gabs = nullptr, *S = nullptr, *rhs = nullptr;
+  double *S_part = nullptr, *rhs_part = nullptr, *Pinv = nullptr, *bl = nullptr, *dc = nullptr, *dl = nullptr;
+  double *partials = nullptr, *scalars = nullptr, *cam_part = nullptr;
+  int *cam_intr = nullptr, *cam_free = nullptr, *free_cams = nullptr, *obs_cam = nullptr, *obs_lm = nullptr;
+  int *lm_start = nullptr, *cam_start = nullptr, *cam_obs = nullptr;
+  int* flag = nullptr;  // 128 bytes behind scalars: one copy brings both back
   // second linearisation set (vsl_bundle_adjust linearises the CANDIDATE point speculatively, before the host has
   // read the step's verdict; an accepted step swaps the sets, a rejected one leaves the current set untouched)
-  DevBuf r2, F2, E2, n2l2, grad_l2, H2, g_c2, diag_c2, diag_l2;
+  double *r2 = nullptr, *F2 = nullptr, *E2 = nullptr, *n2l2 = nullptr, *grad_l2 = nullptr, *H2 = nullptr, *g_c2 = nullptr;
+  double *diag_c2 = nullptr, *diag_l2 = nullptr;
   bool want_alt_set = false;
+  double* diagc_keep = nullptr;  // sessions (want_diagc_keep): clamp(diag H_full), reused across rejected steps
+  bool want_diagc_keep = false;
   // large systems, gather form of the Schur complement (ba_schur_gather_kernel): per-block pair lists, built on the
   // first use for the landmark range they cover, and the per-observation W / Y blocks of the current linearisation
-  DevBuf pair_cnt, pair_start, pairs, Wg, Yg, cam_pos;
+  int *pair_cnt = nullptr, *pair_start = nullptr, *pairs = nullptr, *cam_pos = nullptr;
+  double *Wg = nullptr, *Yg = nullptr;
   // recompute form of a session's iteration (ba_large.h): landmark runs of the workgroups, their partial sums
-  DevBuf wg_lm, lpart, pbs, cam_lm, cam_uv;  // pbs[3 l + x] = scale_l (P^-1 b)_l: what the reduced right-hand side needs of a landmark
+  int *wg_lm = nullptr, *cam_lm = nullptr;
+  double *lpart = nullptr, *cam_uv = nullptr, *pbs = nullptr;  // pbs[3 l + x] = scale_l (P^-1 b)_l: what the reduced right-hand side needs of a landmark
   int n_wg = 0;
   bool large_fused = false;
   int n_slots = 0, hbp1 = 0;
@@ -1325,31 +1323,14 @@ struct BaState {
   bool cyclic = false;  // band form whose band closes on itself (camera loop in trajectory order): wrap blocks in the leading slots of the first rows
   int ldS = 0, offS = 0, bw = 0;
   size_t s_elems = 0;  // doubles to allocate / clear / exchange for S
-  double* S_eff() { return (double*)S.p + offS; }
-  // ONE device allocation per solve, carved into the buffers above (40 hipMalloc calls cost more than 3 LM iterations);
-  // vsl_bundle_adjust lends the context's cached arena, a session owns its own
-  void* arena = nullptr;
-  size_t arena_cap = 0;
-  bool arena_owned = false;
-  vsl_ctx* arena_lender = nullptr;
-  ~BaState() {
-    if (arena && arena_owned) (void)hipFree(arena);
-    if (arena_lender) arena_lender->ba_arena_busy = false;
-  }
+  double* S_eff() { return S + offS; }
   void swap_sets() {
-    std::swap(r.p, r2.p); std::swap(F.p, F2.p); std::swap(E.p, E2.p); std::swap(n2l.p, n2l2.p);
-    std::swap(grad_l.p, grad_l2.p); std::swap(H.p, H2.p); std::swap(g_c.p, g_c2.p); std::swap(diag_c.p, diag_c2.p);
-    std::swap(diag_l.p, diag_l2.p);
-    std::swap(poses.p, cand_poses.p); std::swap(points.p, cand_points.p);
+    std::swap(r, r2); std::swap(F, F2); std::swap(E, E2); std::swap(n2l, n2l2);
+    std::swap(grad_l, grad_l2); std::swap(H, H2); std::swap(g_c, g_c2); std::swap(diag_c, diag_c2);
+    std::swap(diag_l, diag_l2);
+    std::swap(poses, cand_poses); std::swap(points, cand_points);
   }
 };
-
-#define BA_HIP(call)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (call);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      return vsl_fail(ctx, VSL_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-  } while (0)
 
 int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
   if (!ctx) return VSL_ERR_INVALID;
@@ -1363,13 +1344,6 @@ int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
       return vsl_fail(ctx, VSL_ERR_INVALID, "observation %d references camera %d / landmark %d out of range", i, p->obs_cam[i], p->obs_lm[i]);
   for (int c = 0; c < p->n_cams; c++)
     if (p->cam_intr[c] < 0 || p->cam_intr[c] > 1) return vsl_fail(ctx, VSL_ERR_INVALID, "cam_intr[%d] = %d not in {0,1}", c, p->cam_intr[c]);
-  return VSL_OK;
-}
-
-template <class T>
-int upload(vsl_ctx* ctx, DevBuf& b, const T* src, size_t n) {
-  BA_HIP(b.alloc(sizeof(T) * n));
-  if (n) BA_HIP(hipMemcpyAsync(b.p, src, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
   return VSL_OK;
 }
 
@@ -1516,8 +1490,8 @@ struct BaTrace {
   }
 };
 
-int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaState& st, bool allow_band = false,
-             const vsl_ba_problem* graph_prob = nullptr) {
+int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaState& st, ArenaPolicy arena_policy,
+             bool allow_band = false, const vsl_ba_problem* graph_prob = nullptr) {
   BaTrace tr;
   BaDims& D = st.D;
   D.C = p->n_cams;
@@ -1709,90 +1683,64 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   // enough workgroups per camera that a camera's observations are ~2 slices of 256 per workgroup (1 when cameras are many)
   st.cb_seg = D.nfree > 0 ? std::max(1, std::min(32, (int)(D.O / std::max(1, D.nfree) / 512))) : 1;
   st.bl_seg = st.cb_seg;  // (one workgroup per 256 observations of a camera measured 121 us against 80: more gathers in flight than the L2 holds)
-  struct Want { DevBuf* b; size_t bytes; };
-  std::vector<Want> want = {
-      {&st.poses, 8 * 7 * C}, {&st.points, 8 * 3 * L}, {&st.intr, 8 * 16}, {&st.cam_intr, 4 * C}, {&st.cam_free, 4 * C},
-      {&st.free_cams, 4 * free_cams.size()}, {&st.obs_cam, 4 * O}, {&st.obs_lm, 4 * O}, {&st.obs_uv, 16 * O},
-      {&st.lm_start, 4 * (L + 1)}, {&st.cam_start, 4 * (C + 1)}, {&st.cam_obs, 4 * O},
-      {&st.cand_poses, 8 * 7 * C}, {&st.cand_points, 8 * 3 * L}, {&st.r, 16 * O}, {&st.F, 96 * O}, {&st.E, 48 * O},
-      {&st.scale_c, 8 * n}, {&st.scale_l, 24 * L}, {&st.n2l, 24 * L}, {&st.grad_l, 24 * L},
-      {&st.cam_part, 8 * 33 * (size_t)std::max(1, D.nfree) * std::max(st.cb_seg, st.bl_seg)}, {&st.H, 8 * 36 * (size_t)D.nfree}, {&st.g_c, 8 * n},
-      {&st.diag_c, 8 * n}, {&st.diag_l, 24 * L}, {&st.gabs, 8 * (n + 3 * L)}, {&st.S, 8 * st.s_elems}, {&st.rhs, 8 * n},
-      {&st.Pinv, 72 * L}, {&st.bl, 24 * L}, {&st.dc, 8 * n}, {&st.dl, 24 * L},
-      {&st.partials, 8 * (size_t)(2 * std::max(st.nb_obs, st.nb_upd) + 16)}, {&st.scalars, 8 * 16 + sizeof(int) * 4}};
+  const size_t nfree = (size_t)D.nfree, pair_elems = std::max<size_t>(n_pairs < ((size_t)1 << 31) ? n_pairs : 1, 1);
+  ArenaPlan plan(56);
+  plan.add(st.poses, 7 * C); plan.add(st.points, 3 * L); plan.add(st.intr, 16); plan.add(st.cam_intr, C); plan.add(st.cam_free, C);
+  plan.add(st.free_cams, free_cams.size()); plan.add(st.obs_cam, O); plan.add(st.obs_lm, O); plan.add(st.obs_uv, 2 * O);
+  plan.add(st.lm_start, L + 1); plan.add(st.cam_start, C + 1); plan.add(st.cam_obs, O);
+  plan.add(st.cand_poses, 7 * C); plan.add(st.cand_points, 3 * L); plan.add(st.r, 2 * O); plan.add(st.F, 12 * O); plan.add(st.E, 6 * O);
+  plan.add(st.scale_c, n); plan.add(st.scale_l, 3 * L); plan.add(st.n2l, 3 * L); plan.add(st.grad_l, 3 * L);
+  plan.add(st.cam_part, 33 * std::max<size_t>(1, nfree) * std::max(st.cb_seg, st.bl_seg)); plan.add(st.H, 36 * nfree); plan.add(st.g_c, n);
+  plan.add(st.diag_c, n); plan.add(st.diag_l, 3 * L); plan.add(st.gabs, n + 3 * L); plan.add(st.S, st.s_elems); plan.add(st.rhs, n);
+  plan.add(st.Pinv, 9 * L); plan.add(st.bl, 3 * L); plan.add(st.dc, n); plan.add(st.dl, 3 * L);
+  plan.add(st.partials, (size_t)(2 * std::max(st.nb_obs, st.nb_upd) + 16));
+  plan.add(st.scalars, 16 + 2 /* = 4 ints */);  // 16 scalars, then flag: 4 ints in the 16 bytes of 2 doubles
   if (st.small) {
-    want.push_back({&st.S_part, 8 * n * n * st.G});
-    want.push_back({&st.rhs_part, 8 * n * st.G});
+    plan.add(st.S_part, n * n * st.G);
+    plan.add(st.rhs_part, n * st.G);
   } else {
     st.hbp1 = st.banded ? (st.bw - 5) / 6 + 1 : 0;
     st.n_slots = st.banded ? D.nfree * st.hbp1 : D.nfree * (D.nfree + 1) / 2;
     st.n_pairs_cap = n_pairs;
     st.pair_l0 = st.pair_lc = -1;
-    want.push_back({&st.pair_cnt, 4 * ((size_t)st.n_slots + 1)});
-    want.push_back({&st.pair_start, 4 * ((size_t)st.n_slots + 1)});
-    want.push_back({&st.pairs, 8 * std::max<size_t>(n_pairs < ((size_t)1 << 31) ? n_pairs : 1, 1)});
-    want.push_back({&st.cam_pos, 4 * O});
-    want.push_back({&st.Wg, 8 * 18 * O});
-    want.push_back({&st.Yg, 8 * 18 * O});
-    want.push_back({&st.wg_lm, 4 * ((size_t)st.n_wg + 1)});
-    want.push_back({&st.lpart, 8 * 4 * (size_t)std::max(1, st.n_wg)});
-    want.push_back({&st.pbs, 24 * L});
-    want.push_back({&st.cam_lm, 4 * O});
-    want.push_back({&st.cam_uv, 16 * O});
+    plan.add(st.pair_cnt, (size_t)st.n_slots + 1);
+    plan.add(st.pair_start, (size_t)st.n_slots + 1);
+    plan.add(st.pairs, 2 * pair_elems);
+    plan.add(st.cam_pos, O);
+    plan.add(st.Wg, 18 * O);
+    plan.add(st.Yg, 18 * O);
+    plan.add(st.wg_lm, (size_t)st.n_wg + 1);
+    plan.add(st.lpart, 4 * (size_t)std::max(1, st.n_wg));
+    plan.add(st.pbs, 3 * L);
+    plan.add(st.cam_lm, O);
+    plan.add(st.cam_uv, 2 * O);
   }
   if (st.want_alt_set) {
-    const Want alt[] = {{&st.r2, 16 * O}, {&st.F2, 96 * O}, {&st.E2, 48 * O}, {&st.n2l2, 24 * L}, {&st.grad_l2, 24 * L},
-                        {&st.H2, 8 * 36 * (size_t)D.nfree}, {&st.g_c2, 8 * n}, {&st.diag_c2, 8 * n}, {&st.diag_l2, 24 * L}};
-    want.insert(want.end(), std::begin(alt), std::end(alt));
+    plan.add(st.r2, 2 * O); plan.add(st.F2, 12 * O); plan.add(st.E2, 6 * O); plan.add(st.n2l2, 3 * L); plan.add(st.grad_l2, 3 * L);
+    plan.add(st.H2, 36 * nfree); plan.add(st.g_c2, n); plan.add(st.diag_c2, n); plan.add(st.diag_l2, 3 * L);
   }
-  size_t total = 0;
-  for (auto& wnt : want) total += (std::max<size_t>(wnt.bytes, 8) + 255) & ~(size_t)255;
-  if (ctx->ba_arena_busy || !st.want_alt_set) {   // sessions (and nested use) own their arena
-    BA_HIP(hipMalloc(&st.arena, total));
-    st.arena_cap = total;
-    st.arena_owned = true;
-  } else {
-    if (ctx->ba_arena_cap < total) {
-      BA_HIP(hipStreamSynchronize(ctx->stream));
-      if (ctx->ba_arena) (void)hipFree(ctx->ba_arena);
-      ctx->ba_arena = nullptr;
-      ctx->ba_arena_cap = 0;
-      const size_t cap = total + total / 4;
-      BA_HIP(hipMalloc(&ctx->ba_arena, cap));
-      ctx->ba_arena_cap = cap;
-    }
-    st.arena = ctx->ba_arena;
-    st.arena_cap = ctx->ba_arena_cap;
-    ctx->ba_arena_busy = true;
-    st.arena_lender = ctx;
-  }
-  {
-    size_t off = 0;
-    for (auto& wnt : want) {
-      wnt.b->p = (char*)st.arena + off;
-      off += (std::max<size_t>(wnt.bytes, 8) + 255) & ~(size_t)255;
-    }
-  }
-  st.flag.p = (char*)st.scalars.p + 8 * 16;  // behind the 16 scalars: one copy brings both back
+  if (st.want_diagc_keep) plan.add(st.diagc_keep, std::max<size_t>(n, 1));
+  VSL_HIP(ctx, st.arena.acquire(ctx, arena_policy, plan));
+  st.flag = (int*)(st.scalars + 16);
   tr.lap("arena");
-  auto up = [&](DevBuf& bf, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(bf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+  auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
   };
-  BA_HIP(up(st.poses, p->poses, 8 * 7 * C));
-  BA_HIP(up(st.points, p->points, 8 * 3 * L));
-  BA_HIP(up(st.intr, p->intr, 8 * 16));
-  BA_HIP(up(st.cam_intr, p->cam_intr, 4 * C));
-  BA_HIP(up(st.cam_free, cam_free.data(), 4 * C));
-  BA_HIP(up(st.free_cams, free_cams.data(), 4 * free_cams.size()));
-  BA_HIP(up(st.obs_cam, s_cam, 4 * O));
-  BA_HIP(up(st.obs_lm, s_lm, 4 * O));
-  BA_HIP(up(st.obs_uv, s_uv, 16 * O));
-  BA_HIP(up(st.lm_start, lm_start.data(), 4 * (L + 1)));
-  BA_HIP(up(st.cam_start, cam_start.data(), 4 * (C + 1)));
-  BA_HIP(up(st.cam_obs, cam_obs.data(), 4 * O));
-  if (!st.small) BA_HIP(up(st.cam_pos, cam_pos.data(), 4 * O));
-  if (!st.small && st.n_wg > 0) BA_HIP(up(st.wg_lm, wg_lm.data(), 4 * wg_lm.size()));
-  BA_HIP(hipStreamSynchronize(ctx->stream));  // the uploads above read host vectors that die here
+  VSL_HIP(ctx, up(st.poses, p->poses, 8 * 7 * C));
+  VSL_HIP(ctx, up(st.points, p->points, 8 * 3 * L));
+  VSL_HIP(ctx, up(st.intr, p->intr, 8 * 16));
+  VSL_HIP(ctx, up(st.cam_intr, p->cam_intr, 4 * C));
+  VSL_HIP(ctx, up(st.cam_free, cam_free.data(), 4 * C));
+  VSL_HIP(ctx, up(st.free_cams, free_cams.data(), 4 * free_cams.size()));
+  VSL_HIP(ctx, up(st.obs_cam, s_cam, 4 * O));
+  VSL_HIP(ctx, up(st.obs_lm, s_lm, 4 * O));
+  VSL_HIP(ctx, up(st.obs_uv, s_uv, 16 * O));
+  VSL_HIP(ctx, up(st.lm_start, lm_start.data(), 4 * (L + 1)));
+  VSL_HIP(ctx, up(st.cam_start, cam_start.data(), 4 * (C + 1)));
+  VSL_HIP(ctx, up(st.cam_obs, cam_obs.data(), 4 * O));
+  if (!st.small) VSL_HIP(ctx, up(st.cam_pos, cam_pos.data(), 4 * O));
+  if (!st.small && st.n_wg > 0) VSL_HIP(ctx, up(st.wg_lm, wg_lm.data(), 4 * wg_lm.size()));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the uploads above read host vectors that die here
   tr.lap("uploads");
   return VSL_OK;
 }
@@ -1803,13 +1751,10 @@ int ba_linearize(vsl_ctx* ctx, BaState& st, bool scaled, int cost_slot = 0) {
   const BaDims& D = st.D;
   {
     VslStage s(ctx, VSL_STAGE_BA_LIN);
-    hipLaunchKernelGGL(ba_linearize_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses.as<double>(),
-                       st.points.as<double>(), st.intr.as<double>(), st.cam_intr.as<int>(), st.cam_free.as<int>(),
-                       st.obs_cam.as<int>(), st.obs_lm.as<int>(), st.obs_uv.as<double>(),
-                       scaled ? st.scale_c.as<double>() : nullptr, scaled ? st.scale_l.as<double>() : nullptr,
-                       st.r.as<double>(), st.F.as<double>(), st.E.as<double>(), st.partials.as<double>(), 1);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials.as<double>(), st.nb_obs,
-                       st.scalars.as<double>(), cost_slot, 0);
+    hipLaunchKernelGGL(ba_linearize_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr,
+                       st.cam_intr, st.cam_free, st.obs_cam, st.obs_lm, st.obs_uv, scaled ? st.scale_c : nullptr,
+                       scaled ? st.scale_l : nullptr, st.r, st.F, st.E, st.partials, 1);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, cost_slot, 0);
     VSL_CHECK_LAUNCH(ctx);
   }
   return VSL_OK;
@@ -1818,14 +1763,13 @@ int ba_linearize(vsl_ctx* ctx, BaState& st, bool scaled, int cost_slot = 0) {
 int ba_columns(vsl_ctx* ctx, BaState& st) {
   const BaDims& D = st.D;
   VslStage s(ctx, VSL_STAGE_BA_LIN);
-  hipLaunchKernelGGL(ba_lm_cols_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start.as<int>(),
-                     st.r.as<double>(), st.E.as<double>(), st.n2l.as<double>(), st.grad_l.as<double>());
+  hipLaunchKernelGGL(ba_lm_cols_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.r, st.E, st.n2l,
+                     st.grad_l);
   if (D.nfree > 0) {
-    hipLaunchKernelGGL(ba_cam_block_kernel, dim3(D.nfree, st.cb_seg), dim3(256), 0, ctx->stream, st.free_cams.as<int>(),
-                       st.cam_start.as<int>(), st.cam_obs.as<int>(), st.r.as<double>(), st.F.as<double>(),
-                       st.cam_part.as<double>());
-    hipLaunchKernelGGL(ba_cam_block_finish_kernel, dim3((D.nfree * 27 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree,
-                       st.cb_seg, st.cam_part.as<double>(), st.H.as<double>(), st.g_c.as<double>());
+    hipLaunchKernelGGL(ba_cam_block_kernel, dim3(D.nfree, st.cb_seg), dim3(256), 0, ctx->stream, st.free_cams, st.cam_start,
+                       st.cam_obs, st.r, st.F, st.cam_part);
+    hipLaunchKernelGGL(ba_cam_block_finish_kernel, dim3((D.nfree * 27 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.cb_seg,
+                       st.cam_part, st.H, st.g_c);
   }
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
@@ -1841,18 +1785,14 @@ unsigned gather_grid(const BaState& st) {
 // block pair lists of the gather-form Schur complement for landmarks [l0, l0 + lc): built once per solve / session
 int ba_pair_lists(vsl_ctx* ctx, BaState& st, int l0, int lc) {
   if (st.pair_l0 == l0 && st.pair_lc == lc) return VSL_OK;
-  VSL_HIP(ctx, hipMemsetAsync(st.pair_cnt.p, 0, sizeof(int) * ((size_t)st.n_slots + 1), ctx->stream));
-  hipLaunchKernelGGL(ba_pair_list_kernel<false>, dim3((lc + 255) / 256), dim3(256), 0, ctx->stream, l0, lc,
-                     st.lm_start.as<int>(), st.obs_cam.as<int>(), st.cam_free.as<int>(), st.cam_pos.as<int>(), st.hbp1,
-                     st.cyclic ? st.D.nfree : 0, st.pair_cnt.as<int>(), (const int*)nullptr, (int*)nullptr);
-  hipLaunchKernelGGL(ba_pair_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, st.n_slots, st.pair_cnt.as<int>(),
-                     st.pair_start.as<int>());
-  VSL_HIP(ctx, hipMemsetAsync(st.pair_cnt.p, 0, sizeof(int) * ((size_t)st.n_slots + 1), ctx->stream));
-  hipLaunchKernelGGL(ba_pair_list_kernel<true>, dim3((lc + 255) / 256), dim3(256), 0, ctx->stream, l0, lc,
-                     st.lm_start.as<int>(), st.obs_cam.as<int>(), st.cam_free.as<int>(), st.cam_pos.as<int>(), st.hbp1,
-                     st.cyclic ? st.D.nfree : 0, st.pair_cnt.as<int>(), st.pair_start.as<int>(), st.pairs.as<int>());
-  hipLaunchKernelGGL(ba_pair_sort_kernel, dim3(st.n_slots), dim3(64), 0, ctx->stream, st.pair_start.as<int>(),
-                     st.pairs.as<int>());
+  VSL_HIP(ctx, hipMemsetAsync(st.pair_cnt, 0, sizeof(int) * ((size_t)st.n_slots + 1), ctx->stream));
+  hipLaunchKernelGGL(ba_pair_list_kernel<false>, dim3((lc + 255) / 256), dim3(256), 0, ctx->stream, l0, lc, st.lm_start, st.obs_cam,
+                     st.cam_free, st.cam_pos, st.hbp1, st.cyclic ? st.D.nfree : 0, st.pair_cnt, (const int*)nullptr, (int*)nullptr);
+  hipLaunchKernelGGL(ba_pair_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, st.n_slots, st.pair_cnt, st.pair_start);
+  VSL_HIP(ctx, hipMemsetAsync(st.pair_cnt, 0, sizeof(int) * ((size_t)st.n_slots + 1), ctx->stream));
+  hipLaunchKernelGGL(ba_pair_list_kernel<true>, dim3((lc + 255) / 256), dim3(256), 0, ctx->stream, l0, lc, st.lm_start, st.obs_cam,
+                     st.cam_free, st.cam_pos, st.hbp1, st.cyclic ? st.D.nfree : 0, st.pair_cnt, st.pair_start, st.pairs);
+  hipLaunchKernelGGL(ba_pair_sort_kernel, dim3(st.n_slots), dim3(64), 0, ctx->stream, st.pair_start, st.pairs);
   VSL_CHECK_LAUNCH(ctx);
   st.pair_l0 = l0;
   st.pair_lc = lc;
@@ -1866,57 +1806,45 @@ int ba_schur(vsl_ctx* ctx, BaState& st, bool damp, double radius, int l0, int lc
   if (n == 0) return VSL_OK;
   VslStage s(ctx, VSL_STAGE_BA_SCHUR);
   const double inv_radius = damp ? 1.0 / radius : 0.0;
-  const double* dgl = damp ? st.diag_l.as<double>() : nullptr;
-  const double* dgc = damp ? st.diag_c.as<double>() : nullptr;
-  double* Pinv = keep_backsub ? st.Pinv.as<double>() : nullptr;
-  double* bl = keep_backsub ? st.bl.as<double>() : nullptr;
+  const double* dgl = damp ? st.diag_l : nullptr;
+  const double* dgc = damp ? st.diag_c : nullptr;
+  double* Pinv = keep_backsub ? st.Pinv : nullptr;
+  double* bl = keep_backsub ? st.bl : nullptr;
   if (st.small) {
     const int lpw = ((lc + st.G - 1) / st.G + SCH_LB - 1) / SCH_LB * SCH_LB;
     const int G = lpw > 0 ? (lc + lpw - 1) / lpw : 0;
     const bool block3 = !ctx->ba_schur_entries;
     if (G > 0) {
       if (block3)
-        hipLaunchKernelGGL(ba_schur_small_kernel<true>, dim3(G), dim3(SCH_THREADS), 0, ctx->stream, D, st.lm_start.as<int>(),
-                           st.obs_cam.as<int>(), st.cam_free.as<int>(), st.r.as<double>(), st.F.as<double>(),
-                           st.E.as<double>(), dgl, inv_radius, l0, lc, lpw, st.S_part.as<double>(),
-                           st.rhs_part.as<double>(), Pinv, bl);
+        hipLaunchKernelGGL(ba_schur_small_kernel<true>, dim3(G), dim3(SCH_THREADS), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                           st.cam_free, st.r, st.F, st.E, dgl, inv_radius, l0, lc, lpw, st.S_part, st.rhs_part, Pinv, bl);
       else
-        hipLaunchKernelGGL(ba_schur_small_kernel<false>, dim3(G), dim3(SCH_THREADS), 0, ctx->stream, D, st.lm_start.as<int>(),
-                           st.obs_cam.as<int>(), st.cam_free.as<int>(), st.r.as<double>(), st.F.as<double>(),
-                           st.E.as<double>(), dgl, inv_radius, l0, lc, lpw, st.S_part.as<double>(),
-                           st.rhs_part.as<double>(), Pinv, bl);
+        hipLaunchKernelGGL(ba_schur_small_kernel<false>, dim3(G), dim3(SCH_THREADS), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                           st.cam_free, st.r, st.F, st.E, dgl, inv_radius, l0, lc, lpw, st.S_part, st.rhs_part, Pinv, bl);
     }
-    hipLaunchKernelGGL(ba_schur_finish_kernel, dim3((n * n + n + 15) / 16), dim3(256), 0, ctx->stream, n, G,
-                       st.S_part.as<double>(), st.rhs_part.as<double>(), st.H.as<double>(), st.g_c.as<double>(), dgc,
-                       inv_radius, st.S.as<double>(), st.rhs.as<double>(), block3 ? 1 : 0);
+    hipLaunchKernelGGL(ba_schur_finish_kernel, dim3((n * n + n + 15) / 16), dim3(256), 0, ctx->stream, n, G, st.S_part, st.rhs_part,
+                       st.H, st.g_c, dgc, inv_radius, st.S, st.rhs, block3 ? 1 : 0);
   } else {
-    VSL_HIP(ctx, hipMemsetAsync(st.S.p, 0, sizeof(double) * st.s_elems, ctx->stream));
-    VSL_HIP(ctx, hipMemsetAsync(st.rhs.p, 0, sizeof(double) * n, ctx->stream));
+    VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * st.s_elems, ctx->stream));
+    VSL_HIP(ctx, hipMemsetAsync(st.rhs, 0, sizeof(double) * n, ctx->stream));
     const int lower_mode = st.banded ? 2 : ((lower_only && n > 128) ? 1 : 0);  // n <= 128 is solved by ba_chol_small_kernel (full matrix)
     // (pair lists index with 32-bit positions: a problem with 2^31 pairs or more keeps the atomic form)
     if (lc > 0 && (ctx->ba_schur_atomics || st.n_pairs_cap >= ((size_t)1 << 31)))
-      hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((lc + 3) / 4), dim3(256), 0, ctx->stream, D, st.lm_start.as<int>(),
-                         st.obs_cam.as<int>(), st.cam_free.as<int>(), st.r.as<double>(), st.F.as<double>(),
-                         st.E.as<double>(), dgl, inv_radius, l0, lc, st.S_eff(), st.rhs.as<double>(), Pinv, bl, lower_mode,
-                         st.ldS);
+      hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((lc + 3) / 4), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                         st.cam_free, st.r, st.F, st.E, dgl, inv_radius, l0, lc, st.S_eff(), st.rhs, Pinv, bl, lower_mode, st.ldS);
     else if (lc > 0) {
       int rc = ba_pair_lists(ctx, st, l0, lc);
       if (rc) return rc;
-      hipLaunchKernelGGL(ba_schur_prep_kernel, dim3((lc + 3) / 4), dim3(256), 0, ctx->stream, D, st.lm_start.as<int>(),
-                         st.obs_cam.as<int>(), st.cam_free.as<int>(), st.cam_pos.as<int>(), st.r.as<double>(), st.F.as<double>(),
-                         st.E.as<double>(), dgl, inv_radius, l0, lc, st.Wg.as<double>(), st.Yg.as<double>(), st.rhs.as<double>(),
-                         Pinv, st.bl.as<double>());
+      hipLaunchKernelGGL(ba_schur_prep_kernel, dim3((lc + 3) / 4), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                         st.cam_free, st.cam_pos, st.r, st.F, st.E, dgl, inv_radius, l0, lc, st.Wg, st.Yg, st.rhs, Pinv, st.bl);
       if (D.nfree > 0)
-        hipLaunchKernelGGL(ba_schur_rhs_kernel, dim3(D.nfree), dim3(64), 0, ctx->stream, D.nfree, st.free_cams.as<int>(),
-                           st.cam_start.as<int>(), st.cam_obs.as<int>(), st.obs_lm.as<int>(), st.Yg.as<double>(),
-                           st.bl.as<double>(), l0, lc, st.rhs.as<double>());
+        hipLaunchKernelGGL(ba_schur_rhs_kernel, dim3(D.nfree), dim3(64), 0, ctx->stream, D.nfree, st.free_cams, st.cam_start,
+                           st.cam_obs, st.obs_lm, st.Yg, st.bl, l0, lc, st.rhs);
       hipLaunchKernelGGL(ba_schur_gather_kernel, dim3(gather_grid(st)), dim3(64), 0, ctx->stream, st.n_slots, st.hbp1,
-                         st.pair_start.as<int>(), st.pairs.as<int>(), st.Wg.as<double>(), st.Yg.as<double>(), st.S_eff(),
-                         st.ldS, lower_mode);
+                         st.pair_start, st.pairs, st.Wg, st.Yg, st.S_eff(), st.ldS, lower_mode);
     }
-    hipLaunchKernelGGL(ba_add_cam_blocks_kernel, dim3((D.nfree * 36 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree,
-                       st.H.as<double>(), st.g_c.as<double>(), dgc, inv_radius, st.S_eff(), st.rhs.as<double>(), st.ldS,
-                       st.banded ? 1 : 0);
+    hipLaunchKernelGGL(ba_add_cam_blocks_kernel, dim3((D.nfree * 36 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.H, st.g_c,
+                       dgc, inv_radius, st.S_eff(), st.rhs, st.ldS, st.banded ? 1 : 0);
   }
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
@@ -1927,15 +1855,13 @@ int ba_schur(vsl_ctx* ctx, BaState& st, bool damp, double radius, int l0, int lc
 int ba_solve_enqueue(vsl_ctx* ctx, BaState& st, bool flags_set = false) {
   const int n = st.D.n;
   VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-  if ((n == 0 || n > 128) && !flags_set) hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, ctx->stream, st.flag.as<int>());
+  if ((n == 0 || n > 128) && !flags_set) hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, ctx->stream, st.flag);
   if (n == 0) return VSL_OK;
   if (n <= 128) {
-    hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, ctx->stream, n, st.S.as<double>(), st.rhs.as<double>(),
-                       st.dc.as<double>(), st.flag.as<int>() + 1, st.flag.as<int>());
+    hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, ctx->stream, n, st.S, st.rhs, st.dc, st.flag + 1, st.flag);
   } else {
     // dc = -(S^-1 rhs): the solver writes the negated solution as well
-    int rc = vsl_chol_solve_band_dev(ctx, st.S_eff(), st.rhs.as<double>(), n, st.ldS, st.bw, st.flag.as<int>() + 1, st.cyclic ? 1 : 0,
-                                     st.dc.as<double>());
+    int rc = vsl_chol_solve_band_dev(ctx, st.S_eff(), st.rhs, n, st.ldS, st.bw, st.flag + 1, st.cyclic ? 1 : 0, st.dc);
     if (rc) return rc;
   }
   VSL_CHECK_LAUNCH(ctx);
@@ -1950,18 +1876,17 @@ int ba_solve(vsl_ctx* ctx, BaState& st, bool& ok) {
   VslStage s(ctx, VSL_STAGE_BA_SOLVE);
   int flag = 1;
   if (n <= 128) {
-    hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, ctx->stream, n,
-                       st.S.as<double>(), st.rhs.as<double>(), st.dc.as<double>(), st.flag.as<int>());
+    hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, ctx->stream, n, st.S, st.rhs, st.dc, st.flag);
     VSL_CHECK_LAUNCH(ctx);
-    VSL_HIP(ctx, hipMemcpyAsync(&flag, st.flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(&flag, st.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   } else {
     // blocked right-looking Cholesky + substitutions (chol.hip); rhs <- S^-1 rhs
-    int rc = vsl_chol_solve_band_dev(ctx, st.S_eff(), st.rhs.as<double>(), n, st.ldS, st.bw, st.flag.as<int>(), st.cyclic ? 1 : 0);
+    int rc = vsl_chol_solve_band_dev(ctx, st.S_eff(), st.rhs, n, st.ldS, st.bw, st.flag, st.cyclic ? 1 : 0);
     if (rc) return rc;
-    hipLaunchKernelGGL(ba_negate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.rhs.as<double>(), st.dc.as<double>());
+    hipLaunchKernelGGL(ba_negate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.rhs, st.dc);
     VSL_CHECK_LAUNCH(ctx);
-    VSL_HIP(ctx, hipMemcpyAsync(&flag, st.flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(&flag, st.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   ok = flag != 0;
@@ -1969,7 +1894,7 @@ int ba_solve(vsl_ctx* ctx, BaState& st, bool& ok) {
 }
 
 int read_scalars(vsl_ctx* ctx, BaState& st, double* out, int n) {
-  VSL_HIP(ctx, hipMemcpyAsync(out, st.scalars.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(out, st.scalars, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VSL_OK;
 }
@@ -1977,18 +1902,18 @@ int read_scalars(vsl_ctx* ctx, BaState& st, double* out, int n) {
 BlArgs bal_args(BaState& st) {
   BlArgs a;
   a.D = st.D;
-  a.poses = st.poses.as<double>();
-  a.points = st.points.as<double>();
-  a.intr = st.intr.as<double>();
-  a.cam_intr = st.cam_intr.as<int>();
-  a.cam_free = st.cam_free.as<int>();
-  a.obs_cam = st.obs_cam.as<int>();
-  a.obs_lm = st.obs_lm.as<int>();
-  a.obs_uv = st.obs_uv.as<double>();
-  a.lm_start = st.lm_start.as<int>();
-  a.wg_lm = st.wg_lm.as<int>();
-  a.scale_c = st.scale_c.as<double>();
-  a.scale_l = st.scale_l.as<double>();
+  a.poses = st.poses;
+  a.points = st.points;
+  a.intr = st.intr;
+  a.cam_intr = st.cam_intr;
+  a.cam_free = st.cam_free;
+  a.obs_cam = st.obs_cam;
+  a.obs_lm = st.obs_lm;
+  a.obs_uv = st.obs_uv;
+  a.lm_start = st.lm_start;
+  a.wg_lm = st.wg_lm;
+  a.scale_c = st.scale_c;
+  a.scale_l = st.scale_l;
   return a;
 }
 
@@ -1998,13 +1923,11 @@ int bal_init_pass(vsl_ctx* ctx, BaState& st) {
   VslStage s(ctx, VSL_STAGE_BA_LIN);
   const BlArgs a = bal_args(st);
   hipLaunchKernelGGL(bal_prep_kernel<true>, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, (const int*)nullptr, 0.0,
-                     (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, st.n2l.as<double>(),
-                     st.lpart.as<double>());
-  hipLaunchKernelGGL(bal_cam_kernel<true>, dim3(D.nfree, st.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams.as<int>(),
-                     st.cam_start.as<int>(), st.cam_lm.as<int>(), st.cam_uv.as<double>(), (const double*)nullptr, st.cam_part.as<double>());
+                     (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, st.n2l, st.lpart);
+  hipLaunchKernelGGL(bal_cam_kernel<true>, dim3(D.nfree, st.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams, st.cam_start,
+                     st.cam_lm, st.cam_uv, (const double*)nullptr, st.cam_part);
   hipLaunchKernelGGL(bal_cam_finish_kernel, dim3((D.nfree * 33 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.bl_seg, 0,
-                     st.cam_part.as<double>(), st.H.as<double>(), st.g_c.as<double>(), st.rhs.as<double>(), st.n_wg,
-                     st.lpart.as<double>(), st.scalars.as<double>(), (double*)nullptr);
+                     st.cam_part, st.H, st.g_c, st.rhs, st.n_wg, st.lpart, st.scalars, (double*)nullptr);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }
@@ -2015,19 +1938,17 @@ int bal_reduce(vsl_ctx* ctx, BaState& st, double radius, double* gl_out) {
   const BaDims& D = st.D;
   VslStage s(ctx, VSL_STAGE_BA_SCHUR);
   const BlArgs a = bal_args(st);
-  VSL_HIP(ctx, hipMemsetAsync(st.S.p, 0, sizeof(double) * st.s_elems, ctx->stream));
+  VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * st.s_elems, ctx->stream));
   int rc = ba_pair_lists(ctx, st, 0, D.L);
   if (rc) return rc;
-  hipLaunchKernelGGL(bal_prep_kernel<false>, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.cam_pos.as<int>(),
-                     1.0 / radius, st.Yg.as<double>(), st.Pinv.as<double>(), st.bl.as<double>(), st.pbs.as<double>(),
-                     (double*)nullptr, st.lpart.as<double>());
-  hipLaunchKernelGGL(bal_cam_kernel<false>, dim3(D.nfree, st.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams.as<int>(),
-                     st.cam_start.as<int>(), st.cam_lm.as<int>(), st.cam_uv.as<double>(), st.pbs.as<double>(), st.cam_part.as<double>());
+  hipLaunchKernelGGL(bal_prep_kernel<false>, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.cam_pos, 1.0 / radius, st.Yg,
+                     st.Pinv, st.bl, st.pbs, (double*)nullptr, st.lpart);
+  hipLaunchKernelGGL(bal_cam_kernel<false>, dim3(D.nfree, st.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams, st.cam_start,
+                     st.cam_lm, st.cam_uv, st.pbs, st.cam_part);
   hipLaunchKernelGGL(bal_cam_finish_kernel, dim3((D.nfree * 33 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.bl_seg, 1,
-                     st.cam_part.as<double>(), st.H.as<double>(), st.g_c.as<double>(), st.rhs.as<double>(), st.n_wg,
-                     st.lpart.as<double>(), st.scalars.as<double>(), gl_out);
+                     st.cam_part, st.H, st.g_c, st.rhs, st.n_wg, st.lpart, st.scalars, gl_out);
   hipLaunchKernelGGL(ba_schur_gather_kernel, dim3(gather_grid(st)), dim3(64), 0, ctx->stream, st.n_slots, st.hbp1,
-                     st.pair_start.as<int>(), st.pairs.as<int>(), st.Yg.as<double>(), st.Yg.as<double>(), st.S_eff(), st.ldS,
+                     st.pair_start, st.pairs, st.Yg, st.Yg, st.S_eff(), st.ldS,
                      st.banded ? 2 : (D.n > 128 ? 1 : 0));  // n <= 128 is solved by ba_chol_small_kernel (full matrix)
   // (the camera blocks are added by the caller together with the packing: sess_add_pack_kernel)
   VSL_CHECK_LAUNCH(ctx);
@@ -2039,14 +1960,11 @@ int bal_step(vsl_ctx* ctx, BaState& st, double* packC_dev) {
   const BaDims& D = st.D;
   VslStage s(ctx, VSL_STAGE_BA_STEP);
   const BlArgs a = bal_args(st);
-  hipLaunchKernelGGL(bal_pose_kernel, dim3(1), dim3(1024), 0, ctx->stream, D, st.cam_free.as<int>(), st.poses.as<double>(),
-                     st.dc.as<double>(), st.scale_c.as<double>(), st.cand_poses.as<double>(), st.scalars.as<double>(),
-                     st.flag.as<int>());
-  hipLaunchKernelGGL(bal_step_kernel, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.Pinv.as<double>(),
-                     st.bl.as<double>(), st.dc.as<double>(), st.cand_poses.as<double>(), st.cand_points.as<double>(),
-                     st.lpart.as<double>(), st.flag.as<int>());
-  hipLaunchKernelGGL(bal_step_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, st.n_wg, st.lpart.as<double>(),
-                     st.scalars.as<double>(), st.flag.as<int>(), packC_dev);
+  hipLaunchKernelGGL(bal_pose_kernel, dim3(1), dim3(1024), 0, ctx->stream, D, st.cam_free, st.poses, st.dc, st.scale_c,
+                     st.cand_poses, st.scalars, st.flag);
+  hipLaunchKernelGGL(bal_step_kernel, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.Pinv, st.bl, st.dc, st.cand_poses,
+                     st.cand_points, st.lpart, st.flag);
+  hipLaunchKernelGGL(bal_step_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, st.n_wg, st.lpart, st.scalars, st.flag, packC_dev);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }
@@ -2066,16 +1984,15 @@ extern "C" int vsl_ba_residuals_jacobians(vsl_ctx* ctx, const vsl_ba_problem* pr
   if (!r || !J_pose || !J_point) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_residuals_jacobians: null output");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   BaState st;
-  if ((rc = ba_setup(ctx, prob, nullptr, st))) return rc;
+  if ((rc = ba_setup(ctx, prob, nullptr, st, ArenaPolicy::OWNED))) return rc;
   const BaDims& D = st.D;
-  hipLaunchKernelGGL(ba_raw_blocks_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses.as<double>(),
-                     st.points.as<double>(), st.intr.as<double>(), st.cam_intr.as<int>(), st.obs_cam.as<int>(),
-                     st.obs_lm.as<int>(), st.obs_uv.as<double>(), st.r.as<double>(), st.F.as<double>(), st.E.as<double>());
+  hipLaunchKernelGGL(ba_raw_blocks_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr, st.cam_intr,
+                     st.obs_cam, st.obs_lm, st.obs_uv, st.r, st.F, st.E);
   VSL_CHECK_LAUNCH(ctx);
   std::vector<double> hr(2 * (size_t)D.O), hF(12 * (size_t)D.O), hE(6 * (size_t)D.O);
-  VSL_HIP(ctx, hipMemcpyAsync(hr.data(), st.r.p, 8 * hr.size(), hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(hF.data(), st.F.p, 8 * hF.size(), hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(hE.data(), st.E.p, 8 * hE.size(), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(hr.data(), st.r, 8 * hr.size(), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(hF.data(), st.F, 8 * hF.size(), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(hE.data(), st.E, 8 * hE.size(), hipMemcpyDeviceToHost, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int q = 0; q < D.O; q++) {  // back to the caller's observation order
     const size_t i = st.perm.empty() ? (size_t)q : (size_t)st.perm[q];
@@ -2093,7 +2010,7 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
   if (!opt || !S || !g || !cost || !n_free) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_linearize: null argument");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   BaState st;
-  if ((rc = ba_setup(ctx, prob, opt, st))) return rc;
+  if ((rc = ba_setup(ctx, prob, opt, st, ArenaPolicy::OWNED))) return rc;
   const BaDims& D = st.D;
   int l0 = 0, lc = D.L;
   if (lm_count >= 0) {
@@ -2106,26 +2023,25 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
     // restrict to the observations of the landmark range: zero the others' blocks so that the camera
     // sums and the cost only see the range (observations are sorted by landmark => one contiguous run)
     std::vector<int> lm_start(D.L + 1);
-    VSL_HIP(ctx, hipMemcpyAsync(lm_start.data(), st.lm_start.p, sizeof(int) * lm_start.size(), hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(lm_start.data(), st.lm_start, sizeof(int) * lm_start.size(), hipMemcpyDeviceToHost, ctx->stream));
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t o0 = (size_t)lm_start[l0], o1 = (size_t)lm_start[l0 + lc];
     if (o0 > 0) {
-      VSL_HIP(ctx, hipMemsetAsync(st.r.p, 0, 16 * o0, ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.F.p, 0, 96 * o0, ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.E.p, 0, 48 * o0, ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(st.r, 0, 16 * o0, ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(st.F, 0, 96 * o0, ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(st.E, 0, 48 * o0, ctx->stream));
     }
     if (o1 < (size_t)D.O) {
-      VSL_HIP(ctx, hipMemsetAsync(st.r.as<double>() + 2 * o1, 0, 16 * ((size_t)D.O - o1), ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.F.as<double>() + 12 * o1, 0, 96 * ((size_t)D.O - o1), ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.E.as<double>() + 6 * o1, 0, 48 * ((size_t)D.O - o1), ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(st.r + 2 * o1, 0, 16 * ((size_t)D.O - o1), ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(st.F + 12 * o1, 0, 96 * ((size_t)D.O - o1), ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(st.E + 6 * o1, 0, 48 * ((size_t)D.O - o1), ctx->stream));
     }
     const int oc = (int)(o1 - o0);
     const int nb = (oc + 255) / 256;
     if (nb > 0)
-      hipLaunchKernelGGL(ba_cost_kernel, dim3(nb), dim3(256), 0, ctx->stream, D, st.poses.as<double>(), st.points.as<double>(),
-                         st.intr.as<double>(), st.cam_intr.as<int>(), st.obs_cam.as<int>(), st.obs_lm.as<int>(),
-                         st.obs_uv.as<double>(), (int)o0, oc, st.partials.as<double>());
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials.as<double>(), nb, st.scalars.as<double>(), 0, 0);
+      hipLaunchKernelGGL(ba_cost_kernel, dim3(nb), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr, st.cam_intr,
+                         st.obs_cam, st.obs_lm, st.obs_uv, (int)o0, oc, st.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, nb, st.scalars, 0, 0);
     VSL_CHECK_LAUNCH(ctx);
   }
   if ((rc = ba_columns(ctx, st))) return rc;
@@ -2135,8 +2051,8 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
   *cost = sc[0];
   *n_free = D.nfree;
   if (D.n > 0) {
-    VSL_HIP(ctx, hipMemcpy(S, st.S.p, sizeof(double) * (size_t)D.n * D.n, hipMemcpyDeviceToHost));
-    VSL_HIP(ctx, hipMemcpy(g, st.rhs.p, sizeof(double) * D.n, hipMemcpyDeviceToHost));
+    VSL_HIP(ctx, hipMemcpy(S, st.S, sizeof(double) * (size_t)D.n * D.n, hipMemcpyDeviceToHost));
+    VSL_HIP(ctx, hipMemcpy(g, st.rhs, sizeof(double) * D.n, hipMemcpyDeviceToHost));
   }
   return VSL_OK;
 }
@@ -2167,7 +2083,7 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   const double t_start = now_ms();
   BaState st;
   st.want_alt_set = true;
-  if ((rc = ba_setup(ctx, prob, opt, st, true))) return rc;
+  if ((rc = ba_setup(ctx, prob, opt, st, ArenaPolicy::BORROWED, true))) return rc;
   const BaDims& D = st.D;
   const int nc = D.n, nl = 3 * D.L;
   vsl_ba_summary sum;
@@ -2184,20 +2100,17 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   if ((rc = ba_linearize(ctx, st, false))) return rc;
   if ((rc = ba_columns(ctx, st))) return rc;
   const int nmax = std::max(nc, nl);
-  hipLaunchKernelGGL(ba_make_scale_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L,
-                     st.H.as<double>(), st.n2l.as<double>(), st.scale_c.as<double>(), st.scale_l.as<double>());
-  hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D.O, st.cam_free.as<int>(),
-                     st.obs_cam.as<int>(), st.obs_lm.as<int>(), st.scale_c.as<double>(), st.scale_l.as<double>(),
-                     st.F.as<double>(), st.E.as<double>());
+  hipLaunchKernelGGL(ba_make_scale_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, st.H, st.n2l,
+                     st.scale_c, st.scale_l);
+  hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D.O, st.cam_free, st.obs_cam, st.obs_lm,
+                     st.scale_c, st.scale_l, st.F, st.E);
   VSL_CHECK_LAUNCH(ctx);
   if ((rc = ba_columns(ctx, st))) return rc;
 
   auto diag_and_gmax = [&](int slot) -> int {
-    hipLaunchKernelGGL(ba_diag_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, st.H.as<double>(),
-                       st.n2l.as<double>(), st.g_c.as<double>(), st.grad_l.as<double>(), st.scale_c.as<double>(),
-                       st.scale_l.as<double>(), st.diag_c.as<double>(), st.diag_l.as<double>(), st.gabs.as<double>());
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.gabs.as<double>(), (nmax + 255) / 256,
-                       st.scalars.as<double>(), slot, 1);
+    hipLaunchKernelGGL(ba_diag_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, st.H, st.n2l, st.g_c,
+                       st.grad_l, st.scale_c, st.scale_l, st.diag_c, st.diag_l, st.gabs);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.gabs, (nmax + 255) / 256, st.scalars, slot, 1);
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   };
@@ -2232,20 +2145,14 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     if ((rc = ba_solve_enqueue(ctx, st))) return rc;  // flag[1] = Cholesky ok
     {
       VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-      hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start.as<int>(),
-                         st.obs_cam.as<int>(), st.cam_free.as<int>(), st.F.as<double>(), st.E.as<double>(),
-                         st.Pinv.as<double>(), st.bl.as<double>(), st.dc.as<double>(), st.dl.as<double>(), st.flag.as<int>());
-      hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam.as<int>(),
-                         st.obs_lm.as<int>(), st.cam_free.as<int>(), st.r.as<double>(), st.F.as<double>(), st.E.as<double>(),
-                         st.dc.as<double>(), st.dl.as<double>(), st.partials.as<double>());
-      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials.as<double>(), st.nb_obs,
-                         st.scalars.as<double>(), 2, 0);
-      hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free.as<int>(),
-                         st.poses.as<double>(), st.points.as<double>(), st.dc.as<double>(), st.dl.as<double>(),
-                         st.scale_c.as<double>(), st.scale_l.as<double>(), st.cand_poses.as<double>(),
-                         st.cand_points.as<double>(), st.partials.as<double>(), st.nb_upd);
-      hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, st.partials.as<double>(), st.nb_upd,
-                         st.scalars.as<double>(), 3);
+      hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                         st.cam_free, st.F, st.E, st.Pinv, st.bl, st.dc, st.dl, st.flag);
+      hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, st.r,
+                         st.F, st.E, st.dc, st.dl, st.partials);
+      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, 2, 0);
+      hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
+                         st.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, st.partials, st.nb_upd);
+      hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, st.partials, st.nb_upd, st.scalars, 3);
       VSL_CHECK_LAUNCH(ctx);
     }
     // speculative: the candidate becomes the current point, its linearisation goes to the other set;
@@ -2254,7 +2161,7 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     if ((rc = ba_linearize(ctx, st, true, 5))) return rc;
     if ((rc = ba_columns(ctx, st))) return rc;
     if ((rc = diag_and_gmax(6))) return rc;
-    VSL_HIP(ctx, hipMemcpyAsync(hsc, st.scalars.p, 16 * sizeof(double) + 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hsc, st.scalars, 16 * sizeof(double) + 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const double model_change = hsc[2], step_norm = sqrt(hsc[3]), x_norm = sqrt(hsc[4]), cand_cost = hsc[5];
     const bool ok = hflag[0] != 0 && hflag[1] != 0 && model_change > 0.0;
@@ -2276,8 +2183,8 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   }
   sum.iterations = iteration;
   sum.final_cost = cost;
-  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.poses.p, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.points.p, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.poses, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   double ms;
   int64_t cnt;
@@ -2311,7 +2218,6 @@ struct vsl_ba_session {
   BaState st;
   vsl_ba_options opt;
   int lm_first = 0, lm_count = 0, n_lms_total = 0;
-  DevBuf diagc_keep;  // clamp(diag H_full): reused across rejected steps
   bool solo = false;  // vsl_ba_session_solve without a collective: S stays where it is (no copy into packB and back)
 };
 
@@ -2484,7 +2390,8 @@ extern "C" int vsl_ba_session_create(vsl_ctx* ctx, const vsl_ba_problem* prob, c
   s->lm_first = lm_first;
   s->lm_count = lm_count;
   s->n_lms_total = prob->n_lms;
-  if ((rc = ba_setup(ctx, &sub, opt, s->st, true, prob))) {  // band order from the FULL problem: identical on every rank
+  s->st.want_diagc_keep = true;
+  if ((rc = ba_setup(ctx, &sub, opt, s->st, ArenaPolicy::OWNED, true, prob))) {  // band order from the FULL problem: identical on every rank
     delete s;
     return rc;
   }
@@ -2496,13 +2403,9 @@ extern "C" int vsl_ba_session_create(vsl_ctx* ctx, const vsl_ba_problem* prob, c
     st.large_fused = !st.small && st.n_wg > 0 && st.D.nfree > 0 && !ctx->ba_no_fused && !env_no_fused &&
                      !ctx->ba_schur_atomics && st.n_pairs_cap < ((size_t)1 << 31);
     if (st.large_fused) {
-      hipLaunchKernelGGL(bal_cam_major_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D.O, st.cam_obs.as<int>(),
-                         st.obs_lm.as<int>(), st.obs_uv.as<double>(), st.cam_lm.as<int>(), st.cam_uv.as<double>());
+      hipLaunchKernelGGL(bal_cam_major_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D.O, st.cam_obs, st.obs_lm, st.obs_uv,
+                         st.cam_lm, st.cam_uv);
     }
-  }
-  if (s->diagc_keep.alloc(8 * (size_t)(s->st.D.n > 0 ? s->st.D.n : 1)) != hipSuccess) {
-    delete s;
-    return vsl_fail(ctx, VSL_ERR_NOMEM, "device allocation failed");
   }
   *out = s;
   return VSL_OK;
@@ -2553,8 +2456,8 @@ extern "C" int vsl_ba_session_hdiag_cost_dev(vsl_ba_session* s, double* out_dev)
   if (!s || !out_dev) return VSL_ERR_INVALID;
   vsl_ctx* ctx = s->ctx;
   const BaDims& D = s->st.D;
-  hipLaunchKernelGGL(sess_pack_hdiag_kernel, dim3((D.n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, s->st.H.as<double>(),
-                     s->st.scalars.as<double>(), out_dev);
+  hipLaunchKernelGGL(sess_pack_hdiag_kernel, dim3((D.n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, s->st.H, s->st.scalars,
+                     out_dev);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }
@@ -2567,13 +2470,12 @@ extern "C" int vsl_ba_session_set_scale_dev(vsl_ba_session* s, const double* hdi
   BaState& st = s->st;
   const BaDims& D = st.D;
   const int nmax = std::max(D.n, 3 * D.L);
-  hipLaunchKernelGGL(sess_scale_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, hdiag_full_dev,
-                     st.n2l.as<double>(), st.scale_c.as<double>(), st.scale_l.as<double>());
+  hipLaunchKernelGGL(sess_scale_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, hdiag_full_dev, st.n2l,
+                     st.scale_c, st.scale_l);
   VSL_CHECK_LAUNCH(ctx);
   if (st.large_fused) return VSL_OK;
-  hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D.O, st.cam_free.as<int>(),
-                     st.obs_cam.as<int>(), st.obs_lm.as<int>(), st.scale_c.as<double>(), st.scale_l.as<double>(),
-                     st.F.as<double>(), st.E.as<double>());
+  hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D.O, st.cam_free, st.obs_cam, st.obs_lm,
+                     st.scale_c, st.scale_l, st.F, st.E);
   VSL_CHECK_LAUNCH(ctx);
   return ba_columns(ctx, st);
 }
@@ -2591,26 +2493,25 @@ extern "C" int vsl_ba_session_reduce_dev(vsl_ba_session* s, double radius, doubl
   if (st.large_fused) {
     if ((rc = bal_reduce(ctx, st, radius, gmax_l_dev))) return rc;
   } else {
-    hipLaunchKernelGGL(sess_diag_l_kernel, dim3((3 * D.L + 255) / 256), dim3(256), 0, ctx->stream, D.L, st.n2l.as<double>(),
-                       st.grad_l.as<double>(), st.scale_l.as<double>(), st.diag_l.as<double>(), st.gabs.as<double>());
+    hipLaunchKernelGGL(sess_diag_l_kernel, dim3((3 * D.L + 255) / 256), dim3(256), 0, ctx->stream, D.L, st.n2l, st.grad_l,
+                       st.scale_l, st.diag_l, st.gabs);
     if (gmax_l_dev) {
-      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.gabs.as<double>(), 3 * D.L, gmax_l_dev, 0, 1);
+      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.gabs, 3 * D.L, gmax_l_dev, 0, 1);
     }
     VSL_CHECK_LAUNCH(ctx);
     // Schur with landmark damping only: reuse ba_schur with damping, but with a zero camera diagonal
-    VSL_HIP(ctx, hipMemsetAsync(st.diag_c.p, 0, sizeof(double) * (size_t)(n > 0 ? n : 1), ctx->stream));
+    VSL_HIP(ctx, hipMemsetAsync(st.diag_c, 0, sizeof(double) * (size_t)(n > 0 ? n : 1), ctx->stream));
     if ((rc = ba_schur(ctx, st, true, radius, 0, D.L, true, true))) return rc;
   }
   if (n > 0 && st.large_fused) {
-    hipLaunchKernelGGL(sess_add_pack_kernel, dim3((D.nfree * 36 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.H.as<double>(),
-                       st.g_c.as<double>(), st.scalars.as<double>(), st.S_eff(), st.rhs.as<double>(), st.ldS, st.banded ? 1 : 0,
-                       packB_dev + st.s_elems);
+    hipLaunchKernelGGL(sess_add_pack_kernel, dim3((D.nfree * 36 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.H, st.g_c,
+                       st.scalars, st.S_eff(), st.rhs, st.ldS, st.banded ? 1 : 0, packB_dev + st.s_elems);
     VSL_CHECK_LAUNCH(ctx);
-    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(packB_dev, st.S.p, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
+    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(packB_dev, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
   } else if (n > 0) {
-    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(packB_dev, st.S.p, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(sess_pack_b_kernel, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, st.rhs.as<double>(),
-                       st.H.as<double>(), st.g_c.as<double>(), st.scalars.as<double>(), packB_dev + st.s_elems);
+    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(packB_dev, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
+    hipLaunchKernelGGL(sess_pack_b_kernel, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, st.rhs, st.H, st.g_c,
+                       st.scalars, packB_dev + st.s_elems);
     VSL_CHECK_LAUNCH(ctx);
   }
   return VSL_OK;
@@ -2627,10 +2528,10 @@ extern "C" int vsl_ba_session_step_dev(vsl_ba_session* s, const double* packB_fu
   const BaDims& D = st.D;
   const int n = D.n, nl = 3 * D.L;
   if (n > 0) {
-    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(st.S.p, packB_full_dev, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(sess_damp_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.s_elems, packB_full_dev, 1.0 / radius,
-                       refresh_diag, s->diagc_keep.as<double>(), st.S_eff(), st.ldS, st.rhs.as<double>(),
-                       st.large_fused ? st.flag.as<int>() : (int*)nullptr);
+    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(st.S, packB_full_dev, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
+    hipLaunchKernelGGL(sess_damp_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.s_elems, packB_full_dev,
+                       1.0 / radius, refresh_diag, st.diagc_keep, st.S_eff(), st.ldS, st.rhs,
+                       st.large_fused ? st.flag : (int*)nullptr);
     VSL_CHECK_LAUNCH(ctx);
   }
   int rc;
@@ -2644,32 +2545,28 @@ extern "C" int vsl_ba_session_step_dev(vsl_ba_session* s, const double* packB_fu
   bool ok = true;
   if ((rc = ba_solve(ctx, st, ok))) return rc;
   const int okflag = ok ? 1 : 0;
-  VSL_HIP(ctx, hipMemcpyAsync(st.flag.p, &okflag, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(st.flag, &okflag, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (ok) {
-    hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start.as<int>(),
-                       st.obs_cam.as<int>(), st.cam_free.as<int>(), st.F.as<double>(), st.E.as<double>(), st.Pinv.as<double>(),
-                       st.bl.as<double>(), st.dc.as<double>(), st.dl.as<double>());
-    if (n > 0) hipLaunchKernelGGL(ba_all_finite_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.dc.as<double>(), st.flag.as<int>());
-    hipLaunchKernelGGL(ba_all_finite_kernel, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, nl, st.dl.as<double>(), st.flag.as<int>());
-    hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam.as<int>(), st.obs_lm.as<int>(),
-                       st.cam_free.as<int>(), st.r.as<double>(), st.F.as<double>(), st.E.as<double>(), st.dc.as<double>(),
-                       st.dl.as<double>(), st.partials.as<double>());
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials.as<double>(), st.nb_obs, st.scalars.as<double>(), 2, 0);
-    hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free.as<int>(), st.poses.as<double>(),
-                       st.points.as<double>(), st.dc.as<double>(), st.dl.as<double>(), st.scale_c.as<double>(), st.scale_l.as<double>(),
-                       st.cand_poses.as<double>(), st.cand_points.as<double>(), st.partials.as<double>(), st.nb_upd);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials.as<double>(), st.nb_upd, st.scalars.as<double>(), 3, 0);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials.as<double>() + st.nb_upd, st.nb_upd, st.scalars.as<double>(), 4, 0);
-    hipLaunchKernelGGL(sess_cam_norms_kernel, dim3(1), dim3(256), 0, ctx->stream, D, st.cam_free.as<int>(), st.poses.as<double>(),
-                       st.dc.as<double>(), st.scale_c.as<double>(), st.scalars.as<double>());
-    hipLaunchKernelGGL(ba_cost_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.cand_poses.as<double>(), st.cand_points.as<double>(),
-                       st.intr.as<double>(), st.cam_intr.as<int>(), st.obs_cam.as<int>(), st.obs_lm.as<int>(), st.obs_uv.as<double>(), 0,
-                       D.O, st.partials.as<double>());
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials.as<double>(), st.nb_obs, st.scalars.as<double>(), 5, 0);
+    hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                       st.cam_free, st.F, st.E, st.Pinv, st.bl, st.dc, st.dl);
+    if (n > 0) hipLaunchKernelGGL(ba_all_finite_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.dc, st.flag);
+    hipLaunchKernelGGL(ba_all_finite_kernel, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, nl, st.dl, st.flag);
+    hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, st.r,
+                       st.F, st.E, st.dc, st.dl, st.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, 2, 0);
+    hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
+                       st.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, st.partials, st.nb_upd);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_upd, st.scalars, 3, 0);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials + st.nb_upd, st.nb_upd, st.scalars, 4, 0);
+    hipLaunchKernelGGL(sess_cam_norms_kernel, dim3(1), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.dc, st.scale_c,
+                       st.scalars);
+    hipLaunchKernelGGL(ba_cost_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.cand_poses, st.cand_points, st.intr,
+                       st.cam_intr, st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, st.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, 5, 0);
     VSL_CHECK_LAUNCH(ctx);
   }
-  hipLaunchKernelGGL(sess_pack_c_kernel, dim3(1), dim3(64), 0, ctx->stream, st.scalars.as<double>(), st.flag.as<int>(), 0, packC_dev);
+  hipLaunchKernelGGL(sess_pack_c_kernel, dim3(1), dim3(64), 0, ctx->stream, st.scalars, st.flag, 0, packC_dev);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }
@@ -2677,8 +2574,8 @@ extern "C" int vsl_ba_session_step_dev(vsl_ba_session* s, const double* packB_fu
 // The candidate becomes the current estimate.
 extern "C" int vsl_ba_session_accept(vsl_ba_session* s) {
   if (!s) return VSL_ERR_INVALID;
-  std::swap(s->st.poses.p, s->st.cand_poses.p);
-  std::swap(s->st.points.p, s->st.cand_points.p);
+  std::swap(s->st.poses, s->st.cand_poses);
+  std::swap(s->st.points, s->st.cand_points);
   return VSL_OK;
 }
 
@@ -2686,8 +2583,8 @@ extern "C" int vsl_ba_session_accept(vsl_ba_session* s) {
 extern "C" int vsl_ba_session_download(vsl_ba_session* s, double* poses, double* points_own) {
   if (!s) return VSL_ERR_INVALID;
   vsl_ctx* ctx = s->ctx;
-  if (poses) VSL_HIP(ctx, hipMemcpyAsync(poses, s->st.poses.p, sizeof(double) * 7 * (size_t)s->st.D.C, hipMemcpyDeviceToHost, ctx->stream));
-  if (points_own) VSL_HIP(ctx, hipMemcpyAsync(points_own, s->st.points.p, sizeof(double) * 3 * (size_t)s->st.D.L, hipMemcpyDeviceToHost, ctx->stream));
+  if (poses) VSL_HIP(ctx, hipMemcpyAsync(poses, s->st.poses, sizeof(double) * 7 * (size_t)s->st.D.C, hipMemcpyDeviceToHost, ctx->stream));
+  if (points_own) VSL_HIP(ctx, hipMemcpyAsync(points_own, s->st.points, sizeof(double) * 3 * (size_t)s->st.D.L, hipMemcpyDeviceToHost, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VSL_OK;
 }
@@ -2729,9 +2626,16 @@ extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduc
   const int n = st.D.n;
   const size_t elems = st.s_elems, nB = elems + 3 * (size_t)n + 2;
   const double t_start = now_ms();
-  DevBuf bufA, packB, packC, gl, gather;
-  if (bufA.alloc(8 * ((size_t)n + 1)) != hipSuccess || packB.alloc(8 * nB) != hipSuccess || packC.alloc(80) != hipSuccess ||
-      gl.alloc(8) != hipSuccess)
+  const size_t n_gather = points_all_out ? 3 * (size_t)s->n_lms_total : 0;  // every rank's landmarks
+  double *bufA, *packB, *packC, *gl, *gather = nullptr;
+  ArenaPlan plan(5);
+  plan.add(bufA, (size_t)n + 1);
+  plan.add(packB, nB);
+  plan.add(packC, 10);
+  plan.add(gl, 1);
+  if (points_all_out) plan.add(gather, n_gather);
+  DevArena arena;
+  if (arena.acquire(ctx, ArenaPolicy::OWNED, plan) != hipSuccess)
     return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_ba_session_solve: device allocation failed");
   auto AR = [&](double* buf, size_t count, int op) -> int {
     if (!allreduce) return VSL_OK;  // a caller that passes a callback at world 1 gets its (trivial) collectives: tests
@@ -2747,29 +2651,29 @@ extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduc
   s->solo = !allreduce;
   vsl_ba_summary sum;
   memset(&sum, 0, sizeof(sum));
-  VSL_HIP(ctx, hipMemsetAsync(gl.p, 0, 8, ctx->stream));
+  VSL_HIP(ctx, hipMemsetAsync(gl, 0, 8, ctx->stream));
   // iteration 0: cost, Jacobi scaling from the global column norms
   if ((rc = vsl_ba_session_linearize(s, 0))) return rc;
-  if ((rc = vsl_ba_session_hdiag_cost_dev(s, bufA.as<double>()))) return rc;
-  if ((rc = AR(bufA.as<double>(), (size_t)n + 1, 0))) return rc;
-  if ((rc = vsl_ba_session_set_scale_dev(s, bufA.as<double>()))) return rc;
+  if ((rc = vsl_ba_session_hdiag_cost_dev(s, bufA))) return rc;
+  if ((rc = AR(bufA, (size_t)n + 1, 0))) return rc;
+  if ((rc = vsl_ba_session_set_scale_dev(s, bufA))) return rc;
   double h2[2];
-  if ((rc = D2H(h2, bufA.as<double>() + n, 8))) return rc;
+  if ((rc = D2H(h2, bufA + n, 8))) return rc;
   sum.initial_cost = h2[0];
   LmState lm;
   double cost = sum.initial_cost, gmax = INFINITY;
   int it = 0, term, refresh = 1;
   bool have_h2 = false;
-  double* const hostpack = packC.as<double>() + 8;  // [cost | max |gradient|] behind the 8 doubles of packC: one copy brings both
+  double* const hostpack = packC + 8;  // [cost | max |gradient|] behind the 8 doubles of packC: one copy brings both
   sum.termination = 0;
   if (verbosity >= 2) lm_print_header(cost);
   while (true) {
-    if ((rc = vsl_ba_session_reduce_dev(s, lm.radius, packB.as<double>(), gl.as<double>()))) return rc;
-    if ((rc = AR(packB.as<double>(), nB, 0))) return rc;
+    if ((rc = vsl_ba_session_reduce_dev(s, lm.radius, packB, gl))) return rc;
+    if ((rc = AR(packB, nB, 0))) return rc;
     if (refresh) {
-      if ((rc = AR(gl.as<double>(), 1, 1))) return rc;
-      hipLaunchKernelGGL(sess_gmax_c_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, packB.as<double>() + elems + 2 * (size_t)n,
-                         st.scale_c.as<double>(), packB.as<double>() + elems + 3 * (size_t)n, gl.as<double>(), hostpack);
+      if ((rc = AR(gl, 1, 1))) return rc;
+      hipLaunchKernelGGL(sess_gmax_c_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, packB + elems + 2 * (size_t)n, st.scale_c,
+                         packB + elems + 3 * (size_t)n, gl, hostpack);
       VSL_CHECK_LAUNCH(ctx);
       have_h2 = false;  // (cost, |gradient|) of this linearisation: read together with the step's verdict below --
                         // ONE host round trip per iteration; a gradient below tolerance is found one step late, and
@@ -2786,10 +2690,10 @@ extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduc
     }
     if ((term = lm_gate(lm, have_h2 ? gmax : INFINITY)) >= 0) { sum.termination = term; break; }
     it++;
-    if ((rc = vsl_ba_session_step_dev(s, packB.as<double>(), lm.radius, refresh, packC.as<double>()))) return rc;
-    if ((rc = AR(packC.as<double>(), 8, 0))) return rc;
+    if ((rc = vsl_ba_session_step_dev(s, packB, lm.radius, refresh, packC))) return rc;
+    if ((rc = AR(packC, 8, 0))) return rc;
     double c[10];
-    if ((rc = D2H(c, packC.p, 80))) return rc;
+    if ((rc = D2H(c, packC, 80))) return rc;
     if (!have_h2) {
       cost = c[8];
       gmax = c[9];
@@ -2819,17 +2723,16 @@ extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduc
   sum.iterations = it;
   sum.final_cost = cost;
   if (poses_out) {
-    VSL_HIP(ctx, hipMemcpyAsync(poses_out, st.poses.p, sizeof(double) * 7 * (size_t)st.D.C, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(poses_out, st.poses, sizeof(double) * 7 * (size_t)st.D.C, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (points_all_out) {
-    // every rank's landmarks: a zero buffer with the own range filled in, summed over the ranks
-    const size_t total = 3 * (size_t)s->n_lms_total;
-    if (gather.alloc(8 * total) != hipSuccess) return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_ba_session_solve: device allocation failed");
-    VSL_HIP(ctx, hipMemsetAsync(gather.p, 0, 8 * total, ctx->stream));
-    VSL_HIP(ctx, hipMemcpyAsync(gather.as<double>() + 3 * (size_t)s->lm_first, st.points.p, sizeof(double) * 3 * (size_t)st.D.L,
+    // a zero buffer with the own range filled in, summed over the ranks
+    const size_t total = n_gather;
+    VSL_HIP(ctx, hipMemsetAsync(gather, 0, 8 * total, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(gather + 3 * (size_t)s->lm_first, st.points, sizeof(double) * 3 * (size_t)st.D.L,
                                 hipMemcpyDeviceToDevice, ctx->stream));
-    if ((rc = AR(gather.as<double>(), total, 0))) return rc;
-    VSL_HIP(ctx, hipMemcpyAsync(points_all_out, gather.p, 8 * total, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = AR(gather, total, 0))) return rc;
+    VSL_HIP(ctx, hipMemcpyAsync(points_all_out, gather, 8 * total, hipMemcpyDeviceToHost, ctx->stream));
   }
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   sum.total_ms = now_ms() - t_start;
@@ -3332,47 +3235,46 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   vsl_ba_problem p2 = *prob;
   p2.intr = intr_io;
   BaState st;
-  if ((rc = ba_setup(ctx, &p2, opt, st))) return rc;
+  if ((rc = ba_setup(ctx, &p2, opt, st, ArenaPolicy::OWNED))) return rc;
   const BaDims& D = st.D;
   const int n = D.n, nt = n + 16, L3 = 3 * D.L;
-  DevBuf G, scale, n2, grad, diag, Sf, rhsf, df, cand_intr, Tl;
-  BA_HIP(G.alloc(8 * 16 * (size_t)D.O));
-  BA_HIP(scale.alloc(8 * (size_t)nt));
-  BA_HIP(n2.alloc(8 * (size_t)nt));
-  BA_HIP(grad.alloc(8 * (size_t)nt));
-  BA_HIP(diag.alloc(8 * (size_t)nt));
-  BA_HIP(Sf.alloc(8 * (size_t)nt * nt));
-  BA_HIP(rhsf.alloc(8 * (size_t)nt));
-  BA_HIP(df.alloc(8 * (size_t)nt));
-  BA_HIP(cand_intr.alloc(8 * 16));
-  BA_HIP(Tl.alloc(8 * 48 * (size_t)D.L));
+  double *G, *scale, *n2, *grad, *diag, *Sf, *rhsf, *df, *cand_intr, *Tl;
+  ArenaPlan plan(10);
+  plan.add(G, 16 * (size_t)D.O);
+  plan.add(scale, (size_t)nt);
+  plan.add(n2, (size_t)nt);
+  plan.add(grad, (size_t)nt);
+  plan.add(diag, (size_t)nt);
+  plan.add(Sf, (size_t)nt * nt);
+  plan.add(rhsf, (size_t)nt);
+  plan.add(df, (size_t)nt);
+  plan.add(cand_intr, 16);
+  plan.add(Tl, 48 * (size_t)D.L);
+  DevArena arena;
+  VSL_HIP(ctx, arena.acquire(ctx, ArenaPolicy::OWNED, plan));
   vsl_ba_summary sum;
   memset(&sum, 0, sizeof(sum));
   hipStream_t q = ctx->stream;
   const int nbo = st.nb_obs, nbu = st.nb_upd;
-  double* scal = st.scalars.as<double>();
+  double* scal = st.scalars;
 
   auto linearize = [&](bool scaled) -> int {  // at the CURRENT point; scalars[0] = cost
-    hipLaunchKernelGGL(bai_linearize_kernel, dim3(nbo), dim3(256), 0, q, D, st.poses.as<double>(), st.points.as<double>(),
-                       st.intr.as<double>(), st.cam_intr.as<int>(), st.cam_free.as<int>(), st.obs_cam.as<int>(),
-                       st.obs_lm.as<int>(), st.obs_uv.as<double>(), scaled ? scale.as<double>() : (const double*)nullptr,
-                       scaled ? st.scale_l.as<double>() : (const double*)nullptr, st.r.as<double>(), st.F.as<double>(),
-                       st.E.as<double>(), G.as<double>(), st.partials.as<double>());
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials.as<double>(), nbo, scal, 0, 0);
+    hipLaunchKernelGGL(bai_linearize_kernel, dim3(nbo), dim3(256), 0, q, D, st.poses, st.points, st.intr, st.cam_intr, st.cam_free,
+                       st.obs_cam, st.obs_lm, st.obs_uv, scaled ? scale : (const double*)nullptr,
+                       scaled ? st.scale_l : (const double*)nullptr, st.r, st.F, st.E, G, st.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials, nbo, scal, 0, 0);
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   };
   auto stats = [&](bool write_diag) -> int {  // column norms / gradient of the current blocks; scalars[1] = max |gradient|
-    VSL_HIP(ctx, hipMemsetAsync(n2.p, 0, 8 * (size_t)nt, q));
-    VSL_HIP(ctx, hipMemsetAsync(grad.p, 0, 8 * (size_t)nt, q));
-    VSL_HIP(ctx, hipMemsetAsync(st.n2l.p, 0, 8 * (size_t)L3, q));
-    VSL_HIP(ctx, hipMemsetAsync(st.grad_l.p, 0, 8 * (size_t)L3, q));
-    hipLaunchKernelGGL(bai_stats_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free.as<int>(), st.cam_intr.as<int>(),
-                       st.obs_cam.as<int>(), st.obs_lm.as<int>(), st.r.as<double>(), st.F.as<double>(), st.E.as<double>(),
-                       G.as<double>(), n2.as<double>(), grad.as<double>(), st.n2l.as<double>(), st.grad_l.as<double>());
-    hipLaunchKernelGGL(bai_diag_gmax_kernel, dim3(1), dim3(256), 0, q, nt, L3, n2.as<double>(), st.n2l.as<double>(),
-                       grad.as<double>(), st.grad_l.as<double>(), write_diag ? 1 : 0, diag.as<double>(), st.diag_l.as<double>(),
-                       scal, 1);
+    VSL_HIP(ctx, hipMemsetAsync(n2, 0, 8 * (size_t)nt, q));
+    VSL_HIP(ctx, hipMemsetAsync(grad, 0, 8 * (size_t)nt, q));
+    VSL_HIP(ctx, hipMemsetAsync(st.n2l, 0, 8 * (size_t)L3, q));
+    VSL_HIP(ctx, hipMemsetAsync(st.grad_l, 0, 8 * (size_t)L3, q));
+    hipLaunchKernelGGL(bai_stats_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, st.r, st.F,
+                       st.E, G, n2, grad, st.n2l, st.grad_l);
+    hipLaunchKernelGGL(bai_diag_gmax_kernel, dim3(1), dim3(256), 0, q, nt, L3, n2, st.n2l, grad, st.grad_l, write_diag ? 1 : 0,
+                       diag, st.diag_l, scal, 1);
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   };
@@ -3380,11 +3282,10 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   // initial linearisation, Jacobi scaling from the unscaled column norms (once), statistics of the scaled blocks
   if ((rc = linearize(false))) return rc;
   if ((rc = stats(false))) return rc;
-  hipLaunchKernelGGL(bai_make_scale_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, L3, n2.as<double>(),
-                     st.n2l.as<double>(), scale.as<double>(), st.scale_l.as<double>());
-  hipLaunchKernelGGL(bai_apply_scale_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free.as<int>(), st.cam_intr.as<int>(),
-                     st.obs_cam.as<int>(), st.obs_lm.as<int>(), scale.as<double>(), st.scale_l.as<double>(), st.F.as<double>(),
-                     st.E.as<double>(), G.as<double>());
+  hipLaunchKernelGGL(bai_make_scale_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, L3, n2, st.n2l, scale,
+                     st.scale_l);
+  hipLaunchKernelGGL(bai_apply_scale_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, scale,
+                     st.scale_l, st.F, st.E, G);
   if ((rc = stats(true))) return rc;
   if ((rc = read_scalars(ctx, st, h, 2))) return rc;
   double cost = h[0], gmax = h[1];
@@ -3399,50 +3300,40 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     iteration++;
     const double inv_radius = 1.0 / lm.radius;
     // reduced system: J^T J of the camera side, damping, Schur corrections (camera-camera, then the border)
-    VSL_HIP(ctx, hipMemsetAsync(Sf.p, 0, 8 * (size_t)nt * nt, q));
-    VSL_HIP(ctx, hipMemsetAsync(rhsf.p, 0, 8 * (size_t)nt, q));
-    hipLaunchKernelGGL(bai_hess_kernel, dim3(nbo), dim3(256), 0, q, D, nt, st.cam_free.as<int>(), st.cam_intr.as<int>(),
-                       st.obs_cam.as<int>(), st.r.as<double>(), st.F.as<double>(), G.as<double>(), Sf.as<double>(),
-                       rhsf.as<double>());
-    hipLaunchKernelGGL(bai_damp_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, diag.as<double>(), inv_radius, Sf.as<double>());
-    hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, st.lm_start.as<int>(), st.obs_cam.as<int>(),
-                       st.cam_free.as<int>(), st.r.as<double>(), st.F.as<double>(), st.E.as<double>(), st.diag_l.as<double>(),
-                       inv_radius, 0, D.L, Sf.as<double>(), rhsf.as<double>(), st.Pinv.as<double>(), st.bl.as<double>(), 0, nt);
-    hipLaunchKernelGGL(bai_border_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, nt, st.lm_start.as<int>(), st.obs_cam.as<int>(),
-                       st.cam_free.as<int>(), st.cam_intr.as<int>(), st.F.as<double>(), st.E.as<double>(), G.as<double>(),
-                       st.Pinv.as<double>(), st.bl.as<double>(), Tl.as<double>(), Sf.as<double>(), rhsf.as<double>());
-    hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, q, st.flag.as<int>());
+    VSL_HIP(ctx, hipMemsetAsync(Sf, 0, 8 * (size_t)nt * nt, q));
+    VSL_HIP(ctx, hipMemsetAsync(rhsf, 0, 8 * (size_t)nt, q));
+    hipLaunchKernelGGL(bai_hess_kernel, dim3(nbo), dim3(256), 0, q, D, nt, st.cam_free, st.cam_intr, st.obs_cam, st.r, st.F, G, Sf,
+                       rhsf);
+    hipLaunchKernelGGL(bai_damp_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, diag, inv_radius, Sf);
+    hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free, st.r,
+                       st.F, st.E, st.diag_l, inv_radius, 0, D.L, Sf, rhsf, st.Pinv, st.bl, 0, nt);
+    hipLaunchKernelGGL(bai_border_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, nt, st.lm_start, st.obs_cam, st.cam_free,
+                       st.cam_intr, st.F, st.E, G, st.Pinv, st.bl, Tl, Sf, rhsf);
+    hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, q, st.flag);
     if (nt <= 128) {
-      hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, q, nt, Sf.as<double>(), rhsf.as<double>(), df.as<double>(),
-                         st.flag.as<int>() + 1);
+      hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, q, nt, Sf, rhsf, df, st.flag + 1);
     } else {
-      if ((rc = vsl_chol_solve_band_dev(ctx, Sf.as<double>(), rhsf.as<double>(), nt, nt, nt, st.flag.as<int>() + 1))) return rc;
-      hipLaunchKernelGGL(ba_negate_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, rhsf.as<double>(), df.as<double>());
+      if ((rc = vsl_chol_solve_band_dev(ctx, Sf, rhsf, nt, nt, nt, st.flag + 1))) return rc;
+      hipLaunchKernelGGL(ba_negate_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, rhsf, df);
     }
-    hipLaunchKernelGGL(bai_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, q, D, st.lm_start.as<int>(), st.obs_cam.as<int>(),
-                       st.cam_free.as<int>(), st.cam_intr.as<int>(), st.F.as<double>(), st.E.as<double>(), G.as<double>(),
-                       st.Pinv.as<double>(), st.bl.as<double>(), df.as<double>(), st.dl.as<double>());
-    hipLaunchKernelGGL(ba_all_finite2_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, df.as<double>(), L3,
-                       st.dl.as<double>(), st.flag.as<int>());
-    hipLaunchKernelGGL(bai_model_kernel, dim3(nbo), dim3(256), 0, q, D, st.obs_cam.as<int>(), st.obs_lm.as<int>(),
-                       st.cam_free.as<int>(), st.cam_intr.as<int>(), st.r.as<double>(), st.F.as<double>(), st.E.as<double>(),
-                       G.as<double>(), df.as<double>(), st.dl.as<double>(), st.partials.as<double>());
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials.as<double>(), nbo, scal, 2, 0);
+    hipLaunchKernelGGL(bai_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free,
+                       st.cam_intr, st.F, st.E, G, st.Pinv, st.bl, df, st.dl);
+    hipLaunchKernelGGL(ba_all_finite2_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, df, L3, st.dl, st.flag);
+    hipLaunchKernelGGL(bai_model_kernel, dim3(nbo), dim3(256), 0, q, D, st.obs_cam, st.obs_lm, st.cam_free, st.cam_intr, st.r, st.F,
+                       st.E, G, df, st.dl, st.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials, nbo, scal, 2, 0);
     // candidate point and its cost
-    hipLaunchKernelGGL(ba_update_kernel, dim3(nbu), dim3(256), 0, q, D, st.cam_free.as<int>(), st.poses.as<double>(),
-                       st.points.as<double>(), df.as<double>(), st.dl.as<double>(), scale.as<double>(), st.scale_l.as<double>(),
-                       st.cand_poses.as<double>(), st.cand_points.as<double>(), st.partials.as<double>(), nbu);
-    hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, q, st.partials.as<double>(), nbu, scal, 3);
-    hipLaunchKernelGGL(bai_intr_update_kernel, dim3(1), dim3(64), 0, q, n, st.intr.as<double>(), df.as<double>(), scale.as<double>(),
-                       cand_intr.as<double>(), scal, 6);
-    hipLaunchKernelGGL(ba_cost_kernel, dim3(nbo), dim3(256), 0, q, D, st.cand_poses.as<double>(), st.cand_points.as<double>(),
-                       cand_intr.as<double>(), st.cam_intr.as<int>(), st.obs_cam.as<int>(), st.obs_lm.as<int>(),
-                       st.obs_uv.as<double>(), 0, D.O, st.partials.as<double>());
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials.as<double>(), nbo, scal, 5, 0);
+    hipLaunchKernelGGL(ba_update_kernel, dim3(nbu), dim3(256), 0, q, D, st.cam_free, st.poses, st.points, df, st.dl, scale,
+                       st.scale_l, st.cand_poses, st.cand_points, st.partials, nbu);
+    hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, q, st.partials, nbu, scal, 3);
+    hipLaunchKernelGGL(bai_intr_update_kernel, dim3(1), dim3(64), 0, q, n, st.intr, df, scale, cand_intr, scal, 6);
+    hipLaunchKernelGGL(ba_cost_kernel, dim3(nbo), dim3(256), 0, q, D, st.cand_poses, st.cand_points, cand_intr, st.cam_intr,
+                       st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, st.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials, nbo, scal, 5, 0);
     VSL_CHECK_LAUNCH(ctx);
     int hflag[2];
     VSL_HIP(ctx, hipMemcpyAsync(h, scal, sizeof(double) * 8, hipMemcpyDeviceToHost, q));
-    VSL_HIP(ctx, hipMemcpyAsync(hflag, st.flag.p, sizeof(int) * 2, hipMemcpyDeviceToHost, q));
+    VSL_HIP(ctx, hipMemcpyAsync(hflag, st.flag, sizeof(int) * 2, hipMemcpyDeviceToHost, q));
     VSL_HIP(ctx, hipStreamSynchronize(q));
     const double model_change = h[2], step_norm = sqrt(h[3] + h[6]), x_norm = sqrt(h[4] + h[7]), cand_cost = h[5];
     const bool ok = hflag[0] != 0 && hflag[1] != 0 && model_change > 0.0;
@@ -3456,9 +3347,9 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     }
     if (opt->verbosity >= 2) lm_print_row(iteration, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
     if (verdict == LM_ACCEPTED) {
-      std::swap(st.poses.p, st.cand_poses.p);
-      std::swap(st.points.p, st.cand_points.p);
-      VSL_HIP(ctx, hipMemcpyAsync(st.intr.p, cand_intr.p, 8 * 16, hipMemcpyDeviceToDevice, q));
+      std::swap(st.poses, st.cand_poses);
+      std::swap(st.points, st.cand_points);
+      VSL_HIP(ctx, hipMemcpyAsync(st.intr, cand_intr, 8 * 16, hipMemcpyDeviceToDevice, q));
       cost = cand_cost;
       if ((rc = linearize(true))) return rc;
       if ((rc = stats(true))) return rc;   // new LM diagonal
@@ -3469,9 +3360,9 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   }
   sum.iterations = iteration;
   sum.final_cost = cost;
-  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.poses.p, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, q));
-  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.points.p, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, q));
-  VSL_HIP(ctx, hipMemcpyAsync(intr_io, st.intr.p, sizeof(double) * 16, hipMemcpyDeviceToHost, q));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.poses, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, q));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, q));
+  VSL_HIP(ctx, hipMemcpyAsync(intr_io, st.intr, sizeof(double) * 16, hipMemcpyDeviceToHost, q));
   VSL_HIP(ctx, hipStreamSynchronize(q));
   sum.total_ms = now_ms() - t_start;
   if (opt->verbosity >= 1)

@@ -43,6 +43,7 @@
 #include "ba_device.h"
 #include "dpp_chol.h"
 #include "lm_policy.h"
+#include "dev_arena.h"
 #include "vsl_common.h"
 
 namespace {
@@ -1080,9 +1081,9 @@ struct BfLayout {
 BfLayout bf_layout(int C, int L, int O) {
   BfLayout y;
   size_t off = 0;
-  auto take = [&](size_t bytes) {
+  auto take = [&](size_t bytes) {  // (no buffer here is empty: the rule of dev_arena.h)
     const size_t at = off;
-    off += (bytes + 255) & ~(size_t)255;
+    off += arena_slot(bytes);
     return at;
   };
   y.poses = take(56 * (size_t)C);
@@ -1215,23 +1216,6 @@ bool bf_plan(const vsl_ba_problem* p, const BfLayout& y, char* blk, BfPlan& pl) 
   return g > 0;
 }
 
-#define BF_HIP(call)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (call);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      return vsl_fail(ctx, VSL_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-  } while (0)
-
-struct ArenaLoan {  // the context's cached BA arena, or a private allocation when that one is lent out
-  vsl_ctx* ctx = nullptr;
-  void* p = nullptr;
-  bool owned = false, lent = false;
-  ~ArenaLoan() {
-    if (owned && p) (void)hipFree(p);
-    if (lent) ctx->ba_arena_busy = false;
-  }
-};
-
 }  // namespace
 
 // handled = 0: the problem does not fit the fused kernels (nothing was done); otherwise the solve ran (rc tells how).
@@ -1248,7 +1232,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
     fprintf(stderr, "  [fused ba] %-32s %8.3f ms\n", what, t - t_lap);
     t_lap = t;
   };
-  BF_HIP(hipSetDevice(ctx->device));
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
   const size_t C = prob->n_cams, L = prob->n_lms, O = prob->n_obs;
   const BfLayout y = bf_layout((int)C, (int)L, (int)O);
   // the pinned block: the plan first, the kernels' mailbox behind it (one allocation, device-mapped)
@@ -1260,12 +1244,12 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   const size_t mail_doubles = std::max<size_t>(132 + 5 * (size_t)y.g_cap, (size_t)BF_REC * ((size_t)std::max(opt->max_num_iterations, 0) + 4));
   const size_t pin_bytes = y.bytes + 8 * mail_doubles;
   if (ctx->ba_pin_cap < pin_bytes) {
-    BF_HIP(hipStreamSynchronize(ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->ba_pin) (void)hipHostFree(ctx->ba_pin);
     ctx->ba_pin = nullptr;
     ctx->ba_pin_cap = 0;
     const size_t cap = pin_bytes + pin_bytes / 4;
-    BF_HIP(hipHostMalloc((void**)&ctx->ba_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
+    VSL_HIP(ctx, hipHostMalloc((void**)&ctx->ba_pin, cap, hipHostMallocMapped | hipHostMallocCoherent));
     ctx->ba_pin_cap = cap;
   }
   char* blk = (char*)ctx->ba_pin;
@@ -1286,54 +1270,34 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   D.use_huber = opt->use_huber;
   D.huber = opt->huber_parameter;
   const int n = D.n, G = pl.G, NT = pl.NP / 16, T = NT * (NT + 1) / 2;
-  // one arena: the uploaded block, then what the kernels produce
-  struct Want {
-    void** p;
-    size_t bytes;
-  };
+  // one arena (the context's, dev_arena.h): the uploaded block, then what the kernels produce
   char* dblk;
   double *cand_poses, *cand_points, *scale_c, *scale_l, *Pinv, *bl, *S_part, *hc_part, *sc_part, *S, *rhs, *dc, *box;
   BfLm* lm_dev;
-  std::vector<Want> want = {{(void**)&dblk, y.bytes}, {(void**)&cand_poses, 56 * C}, {(void**)&cand_points, 24 * L},
-                            {(void**)&box, 8 * (132 + 5 * (size_t)y.g_cap)}, {(void**)&lm_dev, sizeof(BfLm)},
-                            {(void**)&scale_c, 8 * 128}, {(void**)&scale_l, 24 * L}, {(void**)&Pinv, 72 * L},
-                            {(void**)&bl, 24 * L}, {(void**)&S_part, 2048 * (size_t)T * G},
-                            {(void**)&hc_part, 216 * (size_t)pl.nfree * G}, {(void**)&sc_part, 16 * (size_t)G},
-                            {(void**)&S, 8 * (size_t)n * n}, {(void**)&rhs, 8 * 128}, {(void**)&dc, 8 * 128}};
-  size_t total = 0;
-  for (auto& w : want) total += (std::max<size_t>(w.bytes, 8) + 255) & ~(size_t)255;
-  ArenaLoan loan;
-  loan.ctx = ctx;
-  if (ctx->ba_arena_busy) {
-    BF_HIP(hipMalloc(&loan.p, total));
-    loan.owned = true;
-  } else {
-    if (ctx->ba_arena_cap < total) {
-      BF_HIP(hipStreamSynchronize(ctx->stream));
-      if (ctx->ba_arena) (void)hipFree(ctx->ba_arena);
-      ctx->ba_arena = nullptr;
-      ctx->ba_arena_cap = 0;
-      const size_t cap = total + total / 4;
-      BF_HIP(hipMalloc(&ctx->ba_arena, cap));
-      ctx->ba_arena_cap = cap;
-    }
-    loan.p = ctx->ba_arena;
-    ctx->ba_arena_busy = true;
-    loan.lent = true;
-  }
-  {
-    size_t off = 0;
-    for (auto& w : want) {
-      *w.p = (char*)loan.p + off;
-      off += (std::max<size_t>(w.bytes, 8) + 255) & ~(size_t)255;
-    }
-  }
+  ArenaPlan plan(15);
+  plan.add(dblk, y.bytes);
+  plan.add(cand_poses, 7 * C);
+  plan.add(cand_points, 3 * L);
+  plan.add(box, 132 + 5 * (size_t)y.g_cap);
+  plan.add(lm_dev, 1);
+  plan.add(scale_c, 128);
+  plan.add(scale_l, 3 * L);
+  plan.add(Pinv, 9 * L);
+  plan.add(bl, 3 * L);
+  plan.add(S_part, 256 * (size_t)T * G);
+  plan.add(hc_part, 27 * (size_t)pl.nfree * G);
+  plan.add(sc_part, 2 * (size_t)G);
+  plan.add(S, (size_t)n * n);
+  plan.add(rhs, 128);
+  plan.add(dc, 128);
+  DevArena arena;
+  VSL_HIP(ctx, arena.acquire(ctx, ArenaPolicy::BORROWED, plan));
   volatile double* mail = mailbox;
   volatile int* chol_ok = (volatile int*)(mailbox + 2);
   volatile double* gabs = mailbox + 4;
   volatile double* step_part = mailbox + 132;
   // ONE copy: everything up to the used part of the workgroup records
-  BF_HIP(hipMemcpyAsync(dblk, blk, y.wg_info + 4 * (size_t)BF_INFO * G, hipMemcpyHostToDevice, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(dblk, blk, y.wg_info + 4 * (size_t)BF_INFO * G, hipMemcpyHostToDevice, ctx->stream));
   double* poses = (double*)(dblk + y.poses);
   double* points = (double*)(dblk + y.points);
 
@@ -1458,7 +1422,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
         over = true;  // (cannot happen: the last allowed body sets done)
       }
     }
-    BF_HIP(hipStreamSynchronize(ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     lap("scaling pass + LM loop (device-decided)");
     sum.initial_cost = recs[5];
     if (seen > 0) {
@@ -1474,7 +1438,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
       sum.final_cost = sum.initial_cost;
     }
   } else {
-  BF_HIP(hipStreamSynchronize(ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   lap("arena + upload + scaling pass");
   double cost = mail[0];
   sum.initial_cost = cost;
@@ -1516,7 +1480,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
                          mailbox + 132);
       VSL_CHECK_LAUNCH(ctx);
     }
-    BF_HIP(hipStreamSynchronize(ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     double gmax = mail[1];
     for (int x = 0; x < n; x++) gmax = std::max(gmax, (double)gabs[x]);
     if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
@@ -1553,9 +1517,9 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   sum.final_cost = cost;
   lap("LM loop");
   }  // host-decided loop
-  BF_HIP(hipMemcpyAsync(prob->poses, poses, 56 * C, hipMemcpyDeviceToHost, ctx->stream));
-  BF_HIP(hipMemcpyAsync(prob->points, points, 24 * L, hipMemcpyDeviceToHost, ctx->stream));
-  BF_HIP(hipStreamSynchronize(ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, poses, 56 * C, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->points, points, 24 * L, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   double ms;
   int64_t cnt;
   vsl_ctx_stage_ms(ctx, VSL_STAGE_BA_LIN, &ms, &cnt);  // drains the pending stage events

@@ -15,6 +15,7 @@
 
 #include "vsl_common.h"
 #include "lm_policy.h"
+#include "dev_arena.h"
 
 namespace {
 
@@ -436,22 +437,7 @@ __global__ __launch_bounds__(256) void pgo_reduce_kernel(const double* __restric
   if (threadIdx.x == 0) *out = sh[0];
 }
 
-struct Buf {
-  void* p = nullptr;
-  bool owned = true;  // (PgoState carves its buffers out of ONE allocation: 23 hipMalloc / hipFree pairs were ~1 ms of a 3 ms solve)
-  ~Buf() {
-    if (p && owned) (void)hipFree(p);
-  }
-  template <class T>
-  T* as() {
-    return (T*)p;
-  }
-};
-
 }  // namespace
-
-// (buffers of a solve: sizes collected first, ONE device allocation, carved in 256-byte steps)
-#define PGO_ALLOC(buf, bytes) want.push_back({&(buf), (size_t)(bytes)})
 
 static int pgo_validate(vsl_ctx* ctx, const vsl_pgo_problem* p) {
   if (!ctx) return VSL_ERR_INVALID;
@@ -473,8 +459,12 @@ struct PgoState {
   int ld = 0, bw = 0, cyclic = 0;
   size_t h_elems = 0;
   bool force_dense = false;
-  Buf arena;
-  Buf poses, cand, free_idx, edge_a, edge_b, inc_off, inc, meas, r, Ja, Jb, cost, colsq, scale, H, g, A, b, gabs, part, part2, scalars, flag;
+  // ONE device allocation per solve (dev_arena.h): 23 hipMalloc / hipFree pairs were ~1 ms of a 3 ms solve
+  DevArena arena;
+  double *poses = nullptr, *cand = nullptr, *meas = nullptr, *r = nullptr, *Ja = nullptr, *Jb = nullptr, *cost = nullptr;
+  double *colsq = nullptr, *scale = nullptr, *H = nullptr, *g = nullptr, *A = nullptr, *b = nullptr, *gabs = nullptr;
+  double *part = nullptr, *part2 = nullptr, *scalars = nullptr;
+  int *free_idx = nullptr, *edge_a = nullptr, *edge_b = nullptr, *inc_off = nullptr, *inc = nullptr, *flag = nullptr;
 };
 
 int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
@@ -516,46 +506,35 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
     }
   }
   const size_t N = st.N, E = st.E, n = st.n;
-  struct Want { Buf* b; size_t bytes; };
-  std::vector<Want> want;
-  PGO_ALLOC(st.poses, 56 * N);
-  PGO_ALLOC(st.cand, 56 * N);
-  PGO_ALLOC(st.free_idx, 4 * N);
-  PGO_ALLOC(st.edge_a, 4 * E);
-  PGO_ALLOC(st.edge_b, 4 * E);
-  PGO_ALLOC(st.inc_off, 4 * (N + 1));
-  PGO_ALLOC(st.inc, 8 * E);
-  PGO_ALLOC(st.meas, 48 * E);
-  PGO_ALLOC(st.r, 48 * E);
-  PGO_ALLOC(st.Ja, 288 * E);
-  PGO_ALLOC(st.Jb, 288 * E);
-  PGO_ALLOC(st.cost, 8 * E);
-  PGO_ALLOC(st.colsq, 8 * n);
-  PGO_ALLOC(st.scale, 8 * n);
-  PGO_ALLOC(st.H, 8 * st.h_elems);
-  PGO_ALLOC(st.g, 8 * n);
-  PGO_ALLOC(st.A, 8 * st.h_elems);
-  PGO_ALLOC(st.b, 8 * n);
-  PGO_ALLOC(st.gabs, 8 * n);
-  PGO_ALLOC(st.part, 8 * std::max(std::max(n, N), E));
-  PGO_ALLOC(st.part2, 8 * std::max(std::max(n, N), E));
-  PGO_ALLOC(st.scalars, 64);
-  PGO_ALLOC(st.flag, 8);
-  {
-    size_t total = 0;
-    for (auto& w : want) total += (std::max<size_t>(w.bytes, 8) + 255) & ~(size_t)255;
-    if (hipMalloc(&st.arena.p, total) != hipSuccess)
-      return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_pose_graph_optimize: device allocation of %zu bytes failed", total);
-    size_t off = 0;
-    for (auto& w : want) {
-      w.b->p = (char*)st.arena.p + off;
-      w.b->owned = false;
-      off += (std::max<size_t>(w.bytes, 8) + 255) & ~(size_t)255;
-    }
-  }
+  ArenaPlan plan(23);
+  plan.add(st.poses, 7 * N);
+  plan.add(st.cand, 7 * N);
+  plan.add(st.free_idx, N);
+  plan.add(st.edge_a, E);
+  plan.add(st.edge_b, E);
+  plan.add(st.inc_off, N + 1);
+  plan.add(st.inc, 2 * E);
+  plan.add(st.meas, 6 * E);
+  plan.add(st.r, 6 * E);
+  plan.add(st.Ja, 36 * E);
+  plan.add(st.Jb, 36 * E);
+  plan.add(st.cost, E);
+  plan.add(st.colsq, n);
+  plan.add(st.scale, n);
+  plan.add(st.H, st.h_elems);
+  plan.add(st.g, n);
+  plan.add(st.A, st.h_elems);
+  plan.add(st.b, n);
+  plan.add(st.gabs, n);
+  plan.add(st.part, std::max(std::max(n, N), E));
+  plan.add(st.part2, std::max(std::max(n, N), E));
+  plan.add(st.scalars, 8);
+  plan.add(st.flag, 2);
+  if (st.arena.acquire(ctx, ArenaPolicy::OWNED, plan) != hipSuccess)
+    return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_pose_graph_optimize: device allocation of %zu bytes failed", plan.total());
   hipStream_t s = ctx->stream;
-  if (N) VSL_HIP(ctx, hipMemcpyAsync(st.poses.p, p->poses, 56 * N, hipMemcpyHostToDevice, s));
-  if (N) VSL_HIP(ctx, hipMemcpyAsync(st.free_idx.p, free_idx.data(), 4 * N, hipMemcpyHostToDevice, s));
+  if (N) VSL_HIP(ctx, hipMemcpyAsync(st.poses, p->poses, 56 * N, hipMemcpyHostToDevice, s));
+  if (N) VSL_HIP(ctx, hipMemcpyAsync(st.free_idx, free_idx.data(), 4 * N, hipMemcpyHostToDevice, s));
   // incidence lists in edge order (a counting sort over the nodes keeps the edge indices ascending inside a list)
   std::vector<int> inc_off(N + 1, 0), inc(2 * E);
   for (size_t e = 0; e < E; e++) {
@@ -570,12 +549,12 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
       inc[cur[p->edge_b[e]]++] = 2 * (int)e + 1;
     }
   }
-  VSL_HIP(ctx, hipMemcpyAsync(st.inc_off.p, inc_off.data(), 4 * (N + 1), hipMemcpyHostToDevice, s));
-  if (E) VSL_HIP(ctx, hipMemcpyAsync(st.inc.p, inc.data(), 8 * E, hipMemcpyHostToDevice, s));
+  VSL_HIP(ctx, hipMemcpyAsync(st.inc_off, inc_off.data(), 4 * (N + 1), hipMemcpyHostToDevice, s));
+  if (E) VSL_HIP(ctx, hipMemcpyAsync(st.inc, inc.data(), 8 * E, hipMemcpyHostToDevice, s));
   if (E) {
-    VSL_HIP(ctx, hipMemcpyAsync(st.edge_a.p, p->edge_a, 4 * E, hipMemcpyHostToDevice, s));
-    VSL_HIP(ctx, hipMemcpyAsync(st.edge_b.p, p->edge_b, 4 * E, hipMemcpyHostToDevice, s));
-    VSL_HIP(ctx, hipMemcpyAsync(st.meas.p, p->edge_meas, 48 * E, hipMemcpyHostToDevice, s));
+    VSL_HIP(ctx, hipMemcpyAsync(st.edge_a, p->edge_a, 4 * E, hipMemcpyHostToDevice, s));
+    VSL_HIP(ctx, hipMemcpyAsync(st.edge_b, p->edge_b, 4 * E, hipMemcpyHostToDevice, s));
+    VSL_HIP(ctx, hipMemcpyAsync(st.meas, p->edge_meas, 48 * E, hipMemcpyHostToDevice, s));
   }
   VSL_HIP(ctx, hipStreamSynchronize(s));  // free_idx and the incidence lists are locals
   return VSL_OK;
@@ -586,27 +565,25 @@ int pgo_linearize(vsl_ctx* ctx, PgoState& st, const vsl_ba_options* opt, bool fi
   hipStream_t s = ctx->stream;
   const int E = st.E, n = st.n;
   if (E > 0)
-    hipLaunchKernelGGL(pgo_linearize_kernel<true>, dim3((E + 63) / 64), dim3(64), 0, s, E, st.poses.as<double>(), st.edge_a.as<int>(),
-                       st.edge_b.as<int>(), st.meas.as<double>(), opt->use_huber, opt->huber_parameter, st.r.as<double>(),
-                       st.Ja.as<double>(), st.Jb.as<double>(), st.cost.as<double>());
+    hipLaunchKernelGGL(pgo_linearize_kernel<true>, dim3((E + 63) / 64), dim3(64), 0, s, E, st.poses, st.edge_a, st.edge_b, st.meas,
+                       opt->use_huber, opt->huber_parameter, st.r, st.Ja, st.Jb, st.cost);
   if (first && n > 0) {
-    VSL_HIP(ctx, hipMemsetAsync(st.colsq.p, 0, 8 * (size_t)n, s));
+    VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)n, s));
     if (st.N > 0)
-      hipLaunchKernelGGL(pgo_colsq_kernel, dim3((st.N * 6 + 255) / 256), dim3(256), 0, s, st.N, st.inc_off.as<int>(), st.inc.as<int>(),
-                         st.free_idx.as<int>(), st.Ja.as<double>(), st.Jb.as<double>(), st.colsq.as<double>());
-    hipLaunchKernelGGL(pgo_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.colsq.as<double>(), st.scale.as<double>());
+      hipLaunchKernelGGL(pgo_colsq_kernel, dim3((st.N * 6 + 255) / 256), dim3(256), 0, s, st.N, st.inc_off, st.inc, st.free_idx,
+                         st.Ja, st.Jb, st.colsq);
+    hipLaunchKernelGGL(pgo_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.colsq, st.scale);
   }
   if (n > 0) {
-    VSL_HIP(ctx, hipMemsetAsync(st.H.p, 0, 8 * st.h_elems, s));
-    VSL_HIP(ctx, hipMemsetAsync(st.g.p, 0, 8 * (size_t)n, s));
+    VSL_HIP(ctx, hipMemsetAsync(st.H, 0, 8 * st.h_elems, s));
+    VSL_HIP(ctx, hipMemsetAsync(st.g, 0, 8 * (size_t)n, s));
     if (st.N > 0)
-      hipLaunchKernelGGL(pgo_build_kernel, dim3((st.N * 6 + 255) / 256), dim3(256), 0, s, st.N, n, st.inc_off.as<int>(), st.inc.as<int>(),
-                         st.edge_a.as<int>(), st.edge_b.as<int>(), st.free_idx.as<int>(), st.r.as<double>(), st.Ja.as<double>(),
-                         st.Jb.as<double>(), st.scale.as<double>(), st.H.as<double>(), st.g.as<double>(), st.ld, st.bw, st.cyclic);
+      hipLaunchKernelGGL(pgo_build_kernel, dim3((st.N * 6 + 255) / 256), dim3(256), 0, s, st.N, n, st.inc_off, st.inc, st.edge_a,
+                         st.edge_b, st.free_idx, st.r, st.Ja, st.Jb, st.scale, st.H, st.g, st.ld, st.bw, st.cyclic);
   }
-  hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.cost.as<double>(), E, st.scalars.as<double>(), 0);
+  hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.cost, E, st.scalars, 0);
   VSL_CHECK_LAUNCH(ctx);
-  VSL_HIP(ctx, hipMemcpyAsync(cost_out, st.scalars.p, 8, hipMemcpyDeviceToHost, s));
+  VSL_HIP(ctx, hipMemcpyAsync(cost_out, st.scalars, 8, hipMemcpyDeviceToHost, s));
   VSL_HIP(ctx, hipStreamSynchronize(s));
   return VSL_OK;
 }
@@ -625,14 +602,13 @@ extern "C" int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, cons
   if ((rc = pgo_setup(ctx, prob, st))) return rc;
   // unit scaling: fill scale with ones by pretending every column norm is zero
   if (st.n > 0) {
-    VSL_HIP(ctx, hipMemsetAsync(st.colsq.p, 0, 8 * (size_t)st.n, ctx->stream));
-    hipLaunchKernelGGL(pgo_scale_kernel, dim3((st.n + 255) / 256), dim3(256), 0, ctx->stream, st.n, st.colsq.as<double>(),
-                       st.scale.as<double>());
+    VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)st.n, ctx->stream));
+    hipLaunchKernelGGL(pgo_scale_kernel, dim3((st.n + 255) / 256), dim3(256), 0, ctx->stream, st.n, st.colsq, st.scale);
   }
   double c = 0;
   if ((rc = pgo_linearize(ctx, st, opt, false, &c))) return rc;
-  if (H && st.n) VSL_HIP(ctx, hipMemcpy(H, st.H.p, 8 * (size_t)st.n * st.n, hipMemcpyDeviceToHost));
-  if (g && st.n) VSL_HIP(ctx, hipMemcpy(g, st.g.p, 8 * (size_t)st.n, hipMemcpyDeviceToHost));
+  if (H && st.n) VSL_HIP(ctx, hipMemcpy(H, st.H, 8 * (size_t)st.n * st.n, hipMemcpyDeviceToHost));
+  if (g && st.n) VSL_HIP(ctx, hipMemcpy(g, st.g, 8 * (size_t)st.n, hipMemcpyDeviceToHost));
   if (cost) *cost = c;
   if (n_free) *n_free = st.n / 6;
   return VSL_OK;
@@ -663,23 +639,22 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
     // damped system + gradient norm
     if (st.ld > 0)
       hipLaunchKernelGGL(pgo_damp_band_kernel, dim3((unsigned)((st.h_elems + 255) / 256)), dim3(256), 0, s, n, st.h_elems, st.ld,
-                         st.H.as<double>(), st.g.as<double>(), st.scale.as<double>(), 1.0 / lm.radius, st.A.as<double>(), st.b.as<double>(),
-                         st.gabs.as<double>());
+                         st.H, st.g, st.scale, 1.0 / lm.radius, st.A, st.b, st.gabs);
     else
-      hipLaunchKernelGGL(pgo_damp_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, n, st.H.as<double>(), st.g.as<double>(),
-                         st.scale.as<double>(), 1.0 / lm.radius, st.A.as<double>(), st.b.as<double>(), st.gabs.as<double>());
+      hipLaunchKernelGGL(pgo_damp_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, n, st.H, st.g, st.scale,
+                         1.0 / lm.radius, st.A, st.b, st.gabs);
     const bool gmax_pending = need_gmax;
     if (need_gmax) {
       // max |gradient| of this linearisation: reduced here, READ with the step's scalars below (round 4: one host round
       // trip per iteration instead of three -- a gradient below tolerance is found one step late and that step is dropped)
-      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.gabs.as<double>(), n, st.scalars.as<double>() + 1, 1);
+      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.gabs, n, st.scalars + 1, 1);
       need_gmax = false;
     }
     it++;
     if (st.ld > 0)
-      rc = vsl_chol_solve_band_dev(ctx, st.A.as<double>() + st.ld, st.b.as<double>(), n, st.ld, st.bw, st.flag.as<int>(), st.cyclic);
+      rc = vsl_chol_solve_band_dev(ctx, st.A + st.ld, st.b, n, st.ld, st.bw, st.flag, st.cyclic);
     else
-      rc = vsl_chol_solve_dev(ctx, st.A.as<double>(), st.b.as<double>(), n, st.flag.as<int>());
+      rc = vsl_chol_solve_dev(ctx, st.A, st.b, n, st.flag);
     if (rc) return rc;
     // (the factorisation leaves flag = 1 on success, 0 on a bad pivot; the kernels below only ever CLEAR it -- on a
     // non-finite step --, so one read at the end tells both; after a failed factorisation they run on numbers nobody uses)
@@ -688,29 +663,26 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
     {
       if (st.ld > 0) {
         // model change = sum_i -d_i g_i - sum_e |J_e S d|^2 / 2 (no product with H: the band keeps one triangle only)
-        hipLaunchKernelGGL(pgo_model_edges_kernel, dim3((E + 255) / 256 > 0 ? (E + 255) / 256 : 1), dim3(256), 0, s, E, st.edge_a.as<int>(),
-                           st.edge_b.as<int>(), st.free_idx.as<int>(), st.Ja.as<double>(), st.Jb.as<double>(), st.scale.as<double>(),
-                           st.b.as<double>(), st.part2.as<double>());
-        hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part2.as<double>(), E, st.scalars.as<double>() + 6, 0);
-        hipLaunchKernelGGL(pgo_model_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.g.as<double>(), st.b.as<double>(),
-                           st.part.as<double>(), st.flag.as<int>());
+        hipLaunchKernelGGL(pgo_model_edges_kernel, dim3((E + 255) / 256 > 0 ? (E + 255) / 256 : 1), dim3(256), 0, s, E, st.edge_a,
+                           st.edge_b, st.free_idx, st.Ja, st.Jb, st.scale, st.b, st.part2);
+        hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part2, E, st.scalars + 6, 0);
+        hipLaunchKernelGGL(pgo_model_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.g, st.b, st.part, st.flag);
       } else {
-        hipLaunchKernelGGL(pgo_model_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.H.as<double>(), st.g.as<double>(),
-                           st.b.as<double>(), st.part.as<double>(), st.flag.as<int>());
+        hipLaunchKernelGGL(pgo_model_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.H, st.g, st.b, st.part, st.flag);
       }
-      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part.as<double>(), n, st.scalars.as<double>() + 2, 0);
-      hipLaunchKernelGGL(pgo_update_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, st.free_idx.as<int>(), st.poses.as<double>(),
-                         st.b.as<double>(), st.scale.as<double>(), st.cand.as<double>(), st.part.as<double>(), st.part2.as<double>());
-      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part.as<double>(), N, st.scalars.as<double>() + 3, 0);
-      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part2.as<double>(), N, st.scalars.as<double>() + 4, 0);
+      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part, n, st.scalars + 2, 0);
+      hipLaunchKernelGGL(pgo_update_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, st.free_idx, st.poses, st.b, st.scale,
+                         st.cand, st.part, st.part2);
+      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part, N, st.scalars + 3, 0);
+      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part2, N, st.scalars + 4, 0);
       if (E > 0)
-        hipLaunchKernelGGL(pgo_linearize_kernel<false>, dim3((E + 63) / 64), dim3(64), 0, s, E, st.cand.as<double>(), st.edge_a.as<int>(),
-                           st.edge_b.as<int>(), st.meas.as<double>(), opt->use_huber, opt->huber_parameter, (double*)nullptr,
-                           (double*)nullptr, (double*)nullptr, st.cost.as<double>());
-      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.cost.as<double>(), E, st.scalars.as<double>() + 5, 0);
+        hipLaunchKernelGGL(pgo_linearize_kernel<false>, dim3((E + 63) / 64), dim3(64), 0, s, E, st.cand, st.edge_a, st.edge_b,
+                           st.meas, opt->use_huber, opt->huber_parameter, (double*)nullptr, (double*)nullptr, (double*)nullptr,
+                           st.cost);
+      hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.cost, E, st.scalars + 5, 0);
       VSL_CHECK_LAUNCH(ctx);
-      VSL_HIP(ctx, hipMemcpyAsync(sc, st.scalars.as<double>() + 1, 48, hipMemcpyDeviceToHost, s));
-      VSL_HIP(ctx, hipMemcpyAsync(&finite, st.flag.p, 4, hipMemcpyDeviceToHost, s));
+      VSL_HIP(ctx, hipMemcpyAsync(sc, st.scalars + 1, 48, hipMemcpyDeviceToHost, s));
+      VSL_HIP(ctx, hipMemcpyAsync(&finite, st.flag, 4, hipMemcpyDeviceToHost, s));
       VSL_HIP(ctx, hipStreamSynchronize(s));
     }
     if (gmax_pending) {
@@ -730,7 +702,7 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
     if (verdict == LM_INVALID) continue;
     if (opt->verbosity >= 2) fprintf(stderr, "pgo %3d cost %.6e change %.3e |g| %.3e step %.3e rho %.3e radius %.3e\n", it, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
     if (verdict == LM_ACCEPTED) {
-      std::swap(st.poses.p, st.cand.p);
+      std::swap(st.poses, st.cand);
       if ((rc = pgo_linearize(ctx, st, opt, false, &cost))) return rc;  // (the accepted point's cost comes from here)
       need_gmax = true;
       sum.successful_steps++;
@@ -738,7 +710,7 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
   }
   sum.iterations = it;
   sum.final_cost = cost;
-  if (N) VSL_HIP(ctx, hipMemcpy(prob->poses, st.poses.p, 56 * (size_t)N, hipMemcpyDeviceToHost));
+  if (N) VSL_HIP(ctx, hipMemcpy(prob->poses, st.poses, 56 * (size_t)N, hipMemcpyDeviceToHost));
   if (opt->verbosity >= 1)
     fprintf(stderr, "vsl PGO: iterations %d, initial cost %.6e, final cost %.6e, termination %d\n", sum.iterations, sum.initial_cost,
             sum.final_cost, sum.termination);
