@@ -1,0 +1,263 @@
+// Drives visual-slam_amd/csrc/ba_host_plan.h and chol_layout.h (as plain C++, no HIP); tests/test_ba_host_plan_cpu.py
+// holds the expected values.
+//
+// stdin: one command, its first word:
+//   cyclic n bw                                   -> "ok B nblk" with ok = 0 / 1
+//   layout n half_lin half_cyc allow_band force_dense no_cyclic schur_atomics chol_no_bcr chol_no_fused
+//                                                 -> the layout line
+//   plan allow_band C L O  sch_cmax sch_kmax bl_threads bl_lmw / cam_fixed[C] / O lines "cam lm"
+//                                                 -> every field of the plan, one "name values..." line each
+//   band C L O / cam_fixed[C] / O lines "cam lm"    -> camera_band_order alone: order, half_lin, half_cyc
+//   sub C L O lm_first lm_count / O lines "cam lm"  -> the sub-problem (pixels are (i, -i) for observation i)
+//   threads C L O                                 -> the generated problem (see gen) planned with 1 thread (checksums
+//                                                    of the long arrays), then with 2, 3, 8 threads and thread starts
+//                                                    that fail: one "case" line each, equal = 1 iff every array and
+//                                                    field is the 1-thread plan's
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "ba_host_plan.h"
+
+namespace {
+
+struct Problem {
+  std::vector<uint8_t> fixed;
+  std::vector<int32_t> cam, lm, intr_of;
+  std::vector<double> uv, poses, points;
+  double intr[16] = {0};
+  vsl_ba_problem p;
+  void finish(int C, int L) {
+    const int O = (int)cam.size();
+    intr_of.assign(C, 0);
+    poses.assign(7 * (size_t)C, 0.0);
+    points.assign(3 * (size_t)L, 0.0);
+    memset(&p, 0, sizeof p);
+    p.n_cams = C;
+    p.n_lms = L;
+    p.n_obs = O;
+    p.poses = poses.data();
+    p.cam_fixed = fixed.data();
+    p.cam_intr = intr_of.data();
+    p.intr = intr;
+    p.points = points.data();
+    p.obs_cam = cam.data();
+    p.obs_lm = lm.data();
+    p.obs_uv = uv.data();
+  }
+};
+
+template <class T>
+void line(const char* name, const T* v, size_t n) {
+  printf("%s", name);
+  for (size_t i = 0; i < n; i++) printf(" %lld", (long long)v[i]);
+  printf("\n");
+}
+void line(const char* name, const std::vector<int>& v) { line(name, v.data(), v.size()); }
+
+void print_layout(const BaLayout& y) {
+  printf("layout banded %d cyclic %d renumber %d bw %d ldS %d offS %d s_elems %zu\n", (int)y.banded, (int)y.cyclic, (int)y.renumber,
+         y.bw, y.ldS, y.offS, y.s_elems);
+}
+
+template <class T>
+unsigned long long checksum(const T* v, size_t n) {  // sum (i + 1) v[i] mod 2^64
+  unsigned long long s = 0;
+  for (size_t i = 0; i < n; i++) s += (unsigned long long)(i + 1) * (unsigned long long)(long long)v[i];
+  return s;
+}
+
+// thread starts that fail: the start of team member g_fail_t throws, in every parallel region
+int g_fail_t = 0, g_started = 0;
+std::thread failing_start(HostThreadEntry entry, void* team, int t) {
+  if (t == g_fail_t) throw std::system_error(std::make_error_code(std::errc::resource_unavailable_try_again));
+  g_started++;
+  return std::thread(entry, team, t);
+}
+
+// the generated problem: landmark (48271 i) mod L (unsorted; every landmark the same count when L divides O), camera
+// (lm C / L + (5 (i / L)) mod 9) mod C (a ring, some cameras see a landmark twice), cameras 0, 16, 32 ... fixed
+void gen(int C, int L, int O, Problem& pr) {
+  pr.fixed.resize(C);
+  for (int c = 0; c < C; c++) pr.fixed[c] = c % 16 == 0;
+  pr.cam.resize(O);
+  pr.lm.resize(O);
+  pr.uv.resize(2 * (size_t)O);
+  for (long long i = 0; i < O; i++) {
+    const long long l = i * 48271 % L;
+    pr.lm[i] = (int)l;
+    pr.cam[i] = (int)((l * C / L + (5 * (i / L)) % 9) % C);
+    pr.uv[2 * i] = 0.5 * (double)(i % 1000);
+    pr.uv[2 * i + 1] = 0.25 * (double)(i % 777);
+  }
+  pr.finish(C, L);
+}
+
+bool same(const BaHostPlan& a, const BaHostPlan& b, int O) {
+  const BaLayout &x = a.layout, &y = b.layout;
+  return a.cam_free == b.cam_free && a.free_cams == b.free_cams && a.nfree == b.nfree && a.half_lin == b.half_lin &&
+         a.half_cyc == b.half_cyc && x.banded == y.banded && x.cyclic == y.cyclic && x.renumber == y.renumber && x.bw == y.bw &&
+         x.ldS == y.ldS && x.offS == y.offS && x.s_elems == y.s_elems && a.lm_start == b.lm_start && a.cam_start == b.cam_start &&
+         a.perm == b.perm && !memcmp(a.obs_cam, b.obs_cam, 4 * (size_t)O) && !memcmp(a.obs_lm, b.obs_lm, 4 * (size_t)O) &&
+         !memcmp(a.obs_uv, b.obs_uv, 16 * (size_t)O) && a.cam_obs == b.cam_obs && a.cam_pos == b.cam_pos &&
+         a.kmax_free == b.kmax_free && a.n_pairs == b.n_pairs && a.small == b.small && a.wg_lm == b.wg_lm && a.n_wg == b.n_wg;
+}
+
+const BaPlanLimits kLimits = {22, 24, 512, 256};
+auto no_lap = [](const char*) {};
+
+bool read_obs(int O, Problem& pr) {
+  pr.cam.resize(O);
+  pr.lm.resize(O);
+  pr.uv.resize(2 * (size_t)O);
+  for (int i = 0; i < O; i++) {
+    if (scanf("%d %d", &pr.cam[i], &pr.lm[i]) != 2) return false;
+    pr.uv[2 * (size_t)i] = i;
+    pr.uv[2 * (size_t)i + 1] = -i;
+  }
+  return true;
+}
+
+}  // namespace
+
+int main() {
+  char cmd[16];
+  if (scanf("%15s", cmd) != 1) return 2;
+  if (!strcmp(cmd, "cyclic")) {
+    int n, bw, B = 0, nblk = 0;
+    if (scanf("%d %d", &n, &bw) != 2) return 2;
+    const bool ok = vsl_chol_bcr_cyclic_layout(n, bw, &B, &nblk);
+    printf("%d %d %d\n", (int)ok, ok ? B : 0, ok ? nblk : 0);
+    return 0;
+  }
+  if (!strcmp(cmd, "layout")) {
+    int n, hl, hc, f[6];
+    if (scanf("%d %d %d %d %d %d %d %d %d", &n, &hl, &hc, &f[0], &f[1], &f[2], &f[3], &f[4], &f[5]) != 9) return 2;
+    BaLayoutSwitches sw;
+    sw.allow_band = f[0], sw.force_dense = f[1], sw.no_cyclic = f[2], sw.schur_atomics = f[3], sw.chol_no_bcr = f[4], sw.chol_no_fused = f[5];
+    print_layout(ba_reduced_layout(n, hl, hc, sw));
+    return 0;
+  }
+  if (!strcmp(cmd, "plan")) {
+    int allow_band, C, L, O;
+    BaPlanLimits lim;
+    if (scanf("%d %d %d %d %d %d %d %d", &allow_band, &C, &L, &O, &lim.small_max_free_cams, &lim.small_max_lm_free, &lim.run_max_obs,
+              &lim.run_max_lms) != 8)
+      return 2;
+    Problem pr;
+    pr.fixed.resize(C);
+    for (int c = 0; c < C; c++) {
+      int v;
+      if (scanf("%d", &v) != 1) return 2;
+      pr.fixed[c] = (uint8_t)v;
+    }
+    if (!read_obs(O, pr)) return 2;
+    pr.finish(C, L);
+    BaLayoutSwitches sw;
+    sw.allow_band = allow_band != 0;
+    const BaHostPlan P = ba_host_plan(&pr.p, nullptr, sw, lim, no_lap);
+    line("cam_free", P.cam_free);
+    line("free_cams", P.free_cams);
+    printf("nfree %d\nhalf_lin %d\nhalf_cyc %d\n", P.nfree, P.half_lin, P.half_cyc);
+    print_layout(P.layout);
+    line("lm_start", P.lm_start);
+    line("cam_start", P.cam_start);
+    line("perm", P.perm);
+    printf("own_pointers %d\n", (int)(P.obs_cam == pr.p.obs_cam && P.obs_lm == pr.p.obs_lm && P.obs_uv == pr.p.obs_uv));
+    line("obs_cam", P.obs_cam, (size_t)O);
+    line("obs_lm", P.obs_lm, (size_t)O);
+    printf("obs_u");  // (u = the caller's index of the observation)
+    for (int q = 0; q < O; q++) printf(" %d", (int)P.obs_uv[2 * (size_t)q]);
+    printf("\n");
+    line("cam_obs", P.cam_obs);
+    line("cam_pos", P.cam_pos);
+    printf("kmax_free %d\nn_pairs %zu\nsmall %d\n", P.kmax_free, P.n_pairs, (int)P.small);
+    line("wg_lm", P.wg_lm);
+    printf("n_wg %d\n", P.n_wg);
+    return 0;
+  }
+  if (!strcmp(cmd, "band")) {
+    int C, L, O;
+    if (scanf("%d %d %d", &C, &L, &O) != 3) return 2;
+    Problem pr;
+    pr.fixed.resize(C);
+    std::vector<int> cam_free(C, -1), order;
+    int nfree = 0, half_cyc = -1;
+    for (int c = 0; c < C; c++) {
+      int v;
+      if (scanf("%d", &v) != 1) return 2;
+      pr.fixed[c] = (uint8_t)v;
+      if (!v) cam_free[c] = nfree++;
+    }
+    if (!read_obs(O, pr)) return 2;
+    pr.finish(C, L);
+    std::vector<int> start((size_t)L + 1);
+    const bool sorted_in = ba_landmark_csr(&pr.p, start.data());
+    const int half = camera_band_order(&pr.p, start.data(), sorted_in, cam_free, nfree, order, &half_cyc, HostTeamConfig());
+    line("order", order);
+    printf("half_lin %d\nhalf_cyc %d\n", half, half_cyc);
+    return 0;
+  }
+  if (!strcmp(cmd, "sub")) {
+    int C, L, O, first, count;
+    if (scanf("%d %d %d %d %d", &C, &L, &O, &first, &count) != 5) return 2;
+    Problem pr;
+    pr.fixed.assign(C, 0);
+    if (!read_obs(O, pr)) return 2;
+    pr.finish(C, L);
+    BaSubObs store;
+    const vsl_ba_problem sub = ba_sub_problem(&pr.p, first, count, store);
+    printf("n_cams %d\nn_lms %d\nn_obs %d\npoints_offset %lld\n", sub.n_cams, sub.n_lms, sub.n_obs, (long long)(sub.points - pr.p.points));
+    line("obs_cam", sub.obs_cam, (size_t)sub.n_obs);
+    line("obs_lm", sub.obs_lm, (size_t)sub.n_obs);
+    printf("obs_u");
+    for (int q = 0; q < sub.n_obs; q++) printf(" %d", (int)sub.obs_uv[2 * (size_t)q]);
+    printf("\n");
+    return 0;
+  }
+  if (!strcmp(cmd, "threads")) {
+    int C, L, O;
+    if (scanf("%d %d %d", &C, &L, &O) != 3) return 2;
+    Problem pr;
+    gen(C, L, O, pr);
+    BaLayoutSwitches sw;
+    sw.allow_band = true;
+    HostTeamConfig one;
+    one.threads = 1;
+    const BaHostPlan P = ba_host_plan(&pr.p, nullptr, sw, kLimits, no_lap, one);
+    line("free_cams", P.free_cams);
+    line("cam_free", P.cam_free);
+    printf("half_lin %d\nhalf_cyc %d\n", P.half_lin, P.half_cyc);
+    print_layout(P.layout);
+    printf("kmax_free %d\nn_pairs %zu\nsmall %d\nn_wg %d\n", P.kmax_free, P.n_pairs, (int)P.small, P.n_wg);
+    printf("sum lm_start %llu\n", checksum(P.lm_start.data(), P.lm_start.size()));
+    printf("sum cam_start %llu\n", checksum(P.cam_start.data(), P.cam_start.size()));
+    printf("sum perm %llu\n", checksum(P.perm.data(), P.perm.size()));
+    printf("sum obs_cam %llu\n", checksum(P.obs_cam, (size_t)O));
+    printf("sum obs_lm %llu\n", checksum(P.obs_lm, (size_t)O));
+    printf("sum cam_obs %llu\n", checksum(P.cam_obs.data(), P.cam_obs.size()));
+    printf("sum cam_pos %llu\n", checksum(P.cam_pos.data(), P.cam_pos.size()));
+    printf("sum wg_lm %llu\n", checksum(P.wg_lm.data(), P.wg_lm.size()));
+    double uv_err = 0;  // the pixels went with their observations
+    for (int q = 0; q < O; q++) {
+      const long long i = P.perm[q];
+      uv_err += std::abs(P.obs_uv[2 * (size_t)q] - 0.5 * (double)(i % 1000)) + std::abs(P.obs_uv[2 * (size_t)q + 1] - 0.25 * (double)(i % 777));
+    }
+    printf("uv_err %g\n", uv_err);
+    const int cases[][2] = {{1, 0}, {2, 0}, {2, 1}, {3, 0}, {3, 1}, {3, 2}, {8, 0}, {8, 1}, {8, 2}, {8, 7}};
+    for (const auto& cs : cases) {  // threads, and which start fails: none (0), the 1st, the 2nd, the last
+      {
+        const int nt = cs[0], fail = cs[1];
+        HostTeamConfig cfg;
+        cfg.threads = nt;
+        cfg.start = failing_start;
+        g_fail_t = fail;
+        g_started = 0;
+        const BaHostPlan Q = ba_host_plan(&pr.p, nullptr, sw, kLimits, no_lap, cfg);
+        printf("case threads %d fail_at %d started %d equal %d\n", nt, fail, g_started, (int)same(P, Q, O));
+      }
+    }
+    return 0;
+  }
+  return 3;
+}

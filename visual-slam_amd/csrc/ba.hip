@@ -25,14 +25,14 @@
 // Algorithmic bytes per LM iteration: n_obs*(16 + 8) + n_lms*24 + n_cams*56 + 128 in;
 // (6C)^2*8 + 6C*8 + n_lms*96 out.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <numeric>
-#include <thread>
+#include <new>
 
 #include "vsl_common.h"
 #include "lm_policy.h"
 #include "dev_arena.h"
+#include "ba_host_plan.h"
 #include "ba_device.h"
 #include "ba_large.h"
 
@@ -1347,136 +1347,6 @@ int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
   return VSL_OK;
 }
 
-// host loops of the set-up over ranges of [0, n) on a few threads (the set-up of a 1000-camera solve was ~15 ms of
-// single-threaded loops over 881k observations next to LM iterations of 2.5 ms)
-template <class Fn>
-void host_parallel(int n, Fn fn, int min_parallel = 1 << 19) {
-  const int hw = (int)std::thread::hardware_concurrency();
-  // (starting the threads costs ~0.4 ms: worth it for the global problems only -- a local window of 157k observations
-  // went from 6.0 to 8.1 ms per solve with them)
-  const int nt = n < min_parallel ? 1 : std::max(1, std::min(8, hw > 0 ? hw : 1));
-  if (nt == 1) {
-    fn(0, n, 0);
-    return;
-  }
-  std::vector<std::thread> th;
-  const int chunk = (n + nt - 1) / nt;
-  for (int t = 0; t < nt; t++) {
-    const int a = t * chunk, b = std::min(n, a + chunk);
-    if (a < b) th.emplace_back([=] { fn(a, b, t); });
-  }
-  for (auto& t : th) t.join();
-}
-
-// Band order of the free cameras: reverse Cuthill-McKee on the covisibility graph (two free cameras are adjacent iff
-// some landmark is observed by both: exactly the non-zero 6 x 6 blocks of the reduced camera system).  gp = the
-// problem whose observations define the graph (a session passes the FULL problem so that every rank derives the same
-// order).  order[position] = free index in ascending-camera numbering; returns the block half-bandwidth (max
-// |position difference| over the edges).  A 500-keyframe loop comes out as a band of a few dozen cameras with no
-// corner blocks (the breadth-first levels run both ways round the loop).
-int camera_band_order(const vsl_ba_problem* gp, const std::vector<int>& cam_free0, int nfree, std::vector<int>& order,
-                      int* half_cyclic_natural = nullptr) {
-  const size_t words = ((size_t)nfree + 63) / 64;
-  std::vector<uint64_t> adj((size_t)nfree * words, 0);
-  {
-    std::vector<int> start(gp->n_lms + 1, 0);
-    bool sorted_in = true;
-    for (int i = 0; i < gp->n_obs; i++) {
-      start[gp->obs_lm[i] + 1]++;
-      if (i > 0 && gp->obs_lm[i] < gp->obs_lm[i - 1]) sorted_in = false;
-    }
-    for (int l = 0; l < gp->n_lms; l++) start[l + 1] += start[l];
-    // free-camera index of every observation in landmark order; the reference's own order is landmark order already:
-    // then the threads below look the cameras up themselves (no gathered copy)
-    std::vector<int> cams_v;
-    if (!sorted_in) {
-      cams_v.resize(gp->n_obs);
-      std::vector<int> fill(start.begin(), start.end() - 1);
-      for (int i = 0; i < gp->n_obs; i++) cams_v[fill[gp->obs_lm[i]]++] = cam_free0[gp->obs_cam[i]];
-    }
-    const int* cams_p = sorted_in ? nullptr : cams_v.data();
-    const int32_t* ocam = gp->obs_cam;
-    auto cam_at = [&](int a) { return cams_p ? cams_p[a] : cam_free0[ocam[a]]; };
-    // a private bit matrix per thread, OR-ed together afterwards (shared atomics made the threads fight over its lines)
-    std::vector<std::vector<uint64_t>> priv(8);
-    host_parallel(gp->n_lms, [&](int l0, int l1, int t) {
-      std::vector<uint64_t>& my = priv[t];
-      my.assign((size_t)nfree * words, 0);
-      for (int l = l0; l < l1; l++)
-        for (int a = start[l]; a < start[l + 1]; a++) {
-          const int ca = cam_at(a);
-          if (ca < 0) continue;
-          for (int b = a + 1; b < start[l + 1]; b++) {
-            const int cb = cam_at(b);
-            if (cb < 0 || cb == ca) continue;
-            my[(size_t)ca * words + (cb >> 6)] |= 1ull << (cb & 63);
-            my[(size_t)cb * words + (ca >> 6)] |= 1ull << (ca & 63);
-          }
-        }
-    }, 1 << 15);  // ~k^2 = 80 bit operations per landmark: parallel from 32k landmarks
-    for (auto& my : priv)
-      if (!my.empty())
-        for (size_t i = 0; i < adj.size(); i++) adj[i] |= my[i];
-  }
-  std::vector<std::vector<int>> nb(nfree);
-  std::vector<int> deg(nfree, 0);
-  for (int c = 0; c < nfree; c++)
-    for (size_t w = 0; w < words; w++) {
-      uint64_t m = adj[(size_t)c * words + w];
-      while (m) {
-        const int b = __builtin_ctzll(m);
-        m &= m - 1;
-        nb[c].push_back((int)(w * 64) + b);
-      }
-    }
-  for (int c = 0; c < nfree; c++) deg[c] = (int)nb[c].size();
-  for (int c = 0; c < nfree; c++) std::sort(nb[c].begin(), nb[c].end(), [&](int x, int y) { return deg[x] != deg[y] ? deg[x] < deg[y] : x < y; });
-  std::vector<char> seen(nfree, 0);
-  order.clear();
-  order.reserve(nfree);
-  auto bfs = [&](int root, std::vector<int>& out) {  // Cuthill-McKee from root over the unseen part; returns the last level's first node
-    const size_t first = out.size();
-    out.push_back(root);
-    seen[root] = 1;
-    for (size_t h = first; h < out.size(); h++)
-      for (int v : nb[out[h]])
-        if (!seen[v]) {
-          seen[v] = 1;
-          out.push_back(v);
-        }
-    return out.back();
-  };
-  for (;;) {
-    int root = -1;
-    for (int c = 0; c < nfree; c++)
-      if (!seen[c] && (root < 0 || deg[c] < deg[root])) root = c;
-    if (root < 0) break;
-    // pseudo-peripheral start: two sweeps (the far end of a sweep from a minimum-degree node)
-    std::vector<int> probe;
-    const int far_end = bfs(root, probe);
-    for (int v : probe) seen[v] = 0;
-    bfs(far_end, order);
-  }
-  std::reverse(order.begin(), order.end());
-  std::vector<int> pos(nfree);
-  for (int k = 0; k < nfree; k++) pos[order[k]] = k;
-  int half = 0;
-  for (int c = 0; c < nfree; c++)
-    for (int v : nb[c]) half = std::max(half, std::abs(pos[c] - pos[v]));
-  if (half_cyclic_natural) {
-    // the cameras as they come (ascending index = the reference's keyframe order, i.e. along the trajectory), distances
-    // taken AROUND the ring: a closed loop has half the bandwidth of its best linear order this way
-    int hc = 0;
-    for (int c = 0; c < nfree; c++)
-      for (int v : nb[c]) {
-        const int d = std::abs(c - v);
-        hc = std::max(hc, std::min(d, nfree - d));
-      }
-    *half_cyclic_natural = hc;
-  }
-  return half;
-}
-
 // set-up phase times on stderr when VSL_BA_TRACE is set (developer aid)
 struct BaTrace {
   bool on;
@@ -1501,178 +1371,36 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   D.model1 = p->cam_model[1];
   D.use_huber = o ? o->use_huber : 1;
   D.huber = o ? o->huber_parameter : 1.0;
-  std::vector<int> cam_free(D.C, -1), free_cams;
-  for (int c = 0; c < D.C; c++)
-    if (!p->cam_fixed[c]) {
-      cam_free[c] = (int)free_cams.size();
-      free_cams.push_back(c);
-    }
-  D.nfree = (int)free_cams.size();
-  D.n = 6 * D.nfree;
-  // layout of the reduced camera system (see BaState): dense unless the cameras order into a narrow band
-  st.banded = false;
-  st.ldS = D.n;
-  st.offS = 0;
-  st.bw = D.n;
-  st.s_elems = (size_t)D.n * D.n;
-  if (allow_band && D.n > 128 && !ctx->ba_force_dense) {
-    std::vector<int> order;
-    int half_cyc = 0;
-    const int half = camera_band_order(graph_prob ? graph_prob : p, cam_free, D.nfree, order, &half_cyc);
-    const int bw = 6 * half + 5, bws = bw + VSL_CHOL_NB;
-    // CYCLIC band (round 4): in the cameras' own order with distances around the ring.  Taken when the ring solver has a
-    // block layout for it and its blocks are at most 3/4 of the linear form's (the solve costs ~ block size squared per
-    // level): the 500-keyframe loop of configs[4] has half bandwidth 18 cameras around the ring, 36 in its best line
-    const int bwc = 6 * half_cyc + 5, B_lin = (bw + 1 + 31) / 32 * 32;
-    int B_cyc = 0, nblk_cyc = 0;
-    static const bool env_no_cyclic = getenv("VSL_BA_NO_CYCLIC") != nullptr;
-    if (!ctx->ba_no_cyclic && !env_no_cyclic && !ctx->ba_schur_atomics && !ctx->chol_no_bcr && !ctx->chol_no_fused &&
-        vsl_chol_bcr_cyclic_layout(D.n, bwc, &B_cyc, &nblk_cyc) && 4 * B_cyc <= 3 * B_lin) {
-      st.banded = true;
-      st.cyclic = true;
-      st.bw = bwc;
-      st.ldS = st.offS = bwc + VSL_CHOL_NB;
-      st.s_elems = (size_t)D.n * (bwc + VSL_CHOL_NB + 1) + 64;
-    } else if ((size_t)(bws + 1) * 2 < (size_t)D.n) {  // worth it: the band holds less than half of the matrix
-      std::vector<int> renum(D.nfree);
-      for (int k = 0; k < D.nfree; k++) renum[k] = free_cams[order[k]];
-      free_cams = renum;
-      for (int k = 0; k < D.nfree; k++) cam_free[free_cams[k]] = k;
-      st.banded = true;
-      st.bw = bw;
-      st.ldS = st.offS = bws;
-      st.s_elems = (size_t)D.n * (bws + 1) + 64;  // + slack: the diagonal kernels read (never use) a few entries past a row
-    }
+  // everything the host derives from the problem (ba_host_plan.h); the rest of this function is what needs the device
+  static const bool env_no_cyclic = getenv("VSL_BA_NO_CYCLIC") != nullptr;
+  BaLayoutSwitches sw;
+  sw.allow_band = allow_band;
+  sw.force_dense = ctx->ba_force_dense;
+  sw.no_cyclic = ctx->ba_no_cyclic || env_no_cyclic;
+  sw.schur_atomics = ctx->ba_schur_atomics;
+  sw.chol_no_bcr = ctx->chol_no_bcr;
+  sw.chol_no_fused = ctx->chol_no_fused;
+  BaHostPlan hp;
+  try {
+    hp = ba_host_plan(p, graph_prob, sw, BaPlanLimits{SCH_CMAX, SCH_KMAX, BL_THREADS, BL_LMW}, [&](const char* what) { tr.lap(what); });
+  } catch (const std::bad_alloc&) {
+    return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
   }
+  D.nfree = hp.nfree;
+  D.n = 6 * D.nfree;
+  st.banded = hp.layout.banded;
+  st.cyclic = hp.layout.cyclic;
+  st.bw = hp.layout.bw;
+  st.ldS = hp.layout.ldS;
+  st.offS = hp.layout.offS;
+  st.s_elems = hp.layout.s_elems;
   // (diagnostic read-out for benchmarks: vsl_ctx_last_ba_layout)
   ctx->last_ba_s_elems = (int64_t)st.s_elems;
   ctx->last_ba_banded = st.cyclic ? 2 : (st.banded ? 1 : 0);
   ctx->last_ba_bw = st.bw;
-  tr.lap("free cameras + band order");
-  // sort observations by landmark (stable: keeps the caller's order inside a landmark).  The reference's own order
-  // (map_utils.h:373 / loop_closure_utils.h:700: landmarks, then their observations) -- what
-  // include/visnav_amd/bundle_adjustment.h hands over -- is sorted already: then the caller's arrays ARE the sorted ones
-  // (no permutation, no 24 MB of gathered copies at 881 k observations; st.perm stays empty = identity)
-  std::vector<int> lm_start(D.L + 1, 0), cam_start(D.C + 1, 0);
-  bool sorted_in = true;
-  for (int i = 0; i < D.O; i++) {
-    lm_start[p->obs_lm[i] + 1]++;
-    cam_start[p->obs_cam[i] + 1]++;
-    if (i > 0 && p->obs_lm[i] < p->obs_lm[i - 1]) sorted_in = false;
-  }
-  for (int l = 0; l < D.L; l++) lm_start[l + 1] += lm_start[l];
-  for (int c = 0; c < D.C; c++) cam_start[c + 1] += cam_start[c];
-  std::vector<int> s_cam_v, s_lm_v;
-  std::vector<double> s_uv_v;
-  const int32_t *s_cam = p->obs_cam, *s_lm = p->obs_lm;
-  const double* s_uv = p->obs_uv;
-  st.perm.clear();
-  if (!sorted_in) {
-    st.perm.resize(D.O);
-    {
-      std::vector<int> fill(lm_start.begin(), lm_start.end() - 1);
-      for (int i = 0; i < D.O; i++) st.perm[fill[p->obs_lm[i]]++] = i;
-    }
-    s_cam_v.resize(D.O);
-    s_lm_v.resize(D.O);
-    s_uv_v.resize(2 * (size_t)D.O);
-    host_parallel(D.O, [&](int q0, int q1, int) {
-      for (int q = q0; q < q1; q++) {
-        const int i = st.perm[q];
-        s_cam_v[q] = p->obs_cam[i];
-        s_lm_v[q] = p->obs_lm[i];
-        s_uv_v[2 * (size_t)q] = p->obs_uv[2 * (size_t)i];
-        s_uv_v[2 * (size_t)q + 1] = p->obs_uv[2 * (size_t)i + 1];
-      }
-    });
-    s_cam = s_cam_v.data();
-    s_lm = s_lm_v.data();
-    s_uv = s_uv_v.data();
-  }
-  int kmax_free = 0;
-  size_t n_pairs = 0;  // (observation, observation) pairs of the block lists of the gather-form Schur complement
-  // camera CSR over the sorted observation positions (counts gathered with the landmark counts above) and its inverse:
-  // position of an observation in camera-major order (the gather-form Schur kernels keep their blocks in that order,
-  // so that the blocks of one camera row read one contiguous segment).  ONE parallel region (round 4; three regions and
-  // a serial scatter were 3.9 ms at 881 k observations, of which 1.2 ms starting threads): every thread counts the pairs
-  // of its landmark range and the cameras of its observation chunk; after a barrier thread 0 turns the chunk histograms
-  // into cursors; after another every thread scatters its chunk -- a stable counting sort, the caller's order inside a camera
-  std::vector<int> cam_obs(D.O), cam_pos(D.O);
-  {
-    const int hw = (int)std::thread::hardware_concurrency();
-    const int nt = D.O < (1 << 19) ? 1 : std::max(1, std::min(8, hw > 0 ? hw : 1));
-    std::vector<std::vector<int>> hist(nt, std::vector<int>((size_t)D.C, 0));
-    size_t np_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int km_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::atomic<int> arrived{0};
-    auto barrier = [&](int phase) {  // (phase = how many barriers this thread has passed before)
-      arrived.fetch_add(1, std::memory_order_acq_rel);
-      while (arrived.load(std::memory_order_acquire) < nt * (phase + 1)) std::this_thread::yield();
-    };
-    auto work = [&](int t) {
-      const int l0 = (int)((long long)D.L * t / nt), l1 = (int)((long long)D.L * (t + 1) / nt);
-      const int q0 = (int)((long long)D.O * t / nt), q1 = (int)((long long)D.O * (t + 1) / nt);
-      size_t np = 0;
-      int km = 0;
-      for (int l = l0; l < l1; l++) {
-        int k = 0;
-        for (int q = lm_start[l]; q < lm_start[l + 1]; q++) k += cam_free[s_cam[q]] >= 0;
-        km = std::max(km, k);
-        np += (size_t)k * k;  // upper bound (k (k + 1) / 2 when no camera observes a landmark twice)
-      }
-      np_t[t] = np;
-      km_t[t] = km;
-      std::vector<int>& h = hist[t];
-      for (int q = q0; q < q1; q++) h[s_cam[q]]++;
-      barrier(0);
-      if (t == 0)
-        for (int c = 0; c < D.C; c++) {
-          int at = cam_start[c];
-          for (int u = 0; u < nt; u++) {
-            const int cnt = hist[u][c];
-            hist[u][c] = at;  // becomes thread u's cursor for camera c
-            at += cnt;
-          }
-        }
-      barrier(1);
-      for (int q = q0; q < q1; q++) {
-        const int k = h[s_cam[q]]++;
-        cam_obs[k] = q;
-        cam_pos[q] = k;
-      }
-    };
-    if (nt == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> th;
-      for (int t = 1; t < nt; t++) th.emplace_back(work, t);
-      work(0);
-      for (auto& x : th) x.join();
-    }
-    for (int t = 0; t < nt; t++) {
-      n_pairs += np_t[t];
-      kmax_free = std::max(kmax_free, km_t[t]);
-    }
-  }
-  tr.lap("sort + CSRs");
-  st.small = D.n <= 128 && D.nfree <= SCH_CMAX && kmax_free <= SCH_KMAX;
-  // landmark runs of the recompute-form kernels: <= BL_THREADS observations and <= BL_LMW landmarks per workgroup
-  std::vector<int> wg_lm;
-  if (!st.small) {
-    wg_lm.push_back(0);
-    for (int l = 0, a = 0; l < D.L; l++) {
-      if (lm_start[l + 1] - lm_start[l] > BL_THREADS) {  // a landmark seen by more cameras than a workgroup has threads
-        wg_lm.clear();
-        break;
-      }
-      if (lm_start[l + 1] - lm_start[a] > BL_THREADS || l - a == BL_LMW) {
-        wg_lm.push_back(l);
-        a = l;
-      }
-      if (l == D.L - 1) wg_lm.push_back(D.L);
-    }
-  }
-  st.n_wg = wg_lm.empty() ? 0 : (int)wg_lm.size() - 1;
+  st.perm = std::move(hp.perm);
+  st.small = hp.small;
+  st.n_wg = hp.n_wg;
   st.nb_obs = (D.O + 255) / 256;
   st.nb_upd = (std::max(D.C, D.L) + 255) / 256;
   st.G = std::min(SCH_GMAX, (D.L + SCH_LB - 1) / SCH_LB);
@@ -1683,10 +1411,10 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   // enough workgroups per camera that a camera's observations are ~2 slices of 256 per workgroup (1 when cameras are many)
   st.cb_seg = D.nfree > 0 ? std::max(1, std::min(32, (int)(D.O / std::max(1, D.nfree) / 512))) : 1;
   st.bl_seg = st.cb_seg;  // (one workgroup per 256 observations of a camera measured 121 us against 80: more gathers in flight than the L2 holds)
-  const size_t nfree = (size_t)D.nfree, pair_elems = std::max<size_t>(n_pairs < ((size_t)1 << 31) ? n_pairs : 1, 1);
+  const size_t nfree = (size_t)D.nfree, pair_elems = std::max<size_t>(hp.n_pairs < ((size_t)1 << 31) ? hp.n_pairs : 1, 1);
   ArenaPlan plan(56);
   plan.add(st.poses, 7 * C); plan.add(st.points, 3 * L); plan.add(st.intr, 16); plan.add(st.cam_intr, C); plan.add(st.cam_free, C);
-  plan.add(st.free_cams, free_cams.size()); plan.add(st.obs_cam, O); plan.add(st.obs_lm, O); plan.add(st.obs_uv, 2 * O);
+  plan.add(st.free_cams, hp.free_cams.size()); plan.add(st.obs_cam, O); plan.add(st.obs_lm, O); plan.add(st.obs_uv, 2 * O);
   plan.add(st.lm_start, L + 1); plan.add(st.cam_start, C + 1); plan.add(st.cam_obs, O);
   plan.add(st.cand_poses, 7 * C); plan.add(st.cand_points, 3 * L); plan.add(st.r, 2 * O); plan.add(st.F, 12 * O); plan.add(st.E, 6 * O);
   plan.add(st.scale_c, n); plan.add(st.scale_l, 3 * L); plan.add(st.n2l, 3 * L); plan.add(st.grad_l, 3 * L);
@@ -1701,7 +1429,7 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   } else {
     st.hbp1 = st.banded ? (st.bw - 5) / 6 + 1 : 0;
     st.n_slots = st.banded ? D.nfree * st.hbp1 : D.nfree * (D.nfree + 1) / 2;
-    st.n_pairs_cap = n_pairs;
+    st.n_pairs_cap = hp.n_pairs;
     st.pair_l0 = st.pair_lc = -1;
     plan.add(st.pair_cnt, (size_t)st.n_slots + 1);
     plan.add(st.pair_start, (size_t)st.n_slots + 1);
@@ -1730,16 +1458,16 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   VSL_HIP(ctx, up(st.points, p->points, 8 * 3 * L));
   VSL_HIP(ctx, up(st.intr, p->intr, 8 * 16));
   VSL_HIP(ctx, up(st.cam_intr, p->cam_intr, 4 * C));
-  VSL_HIP(ctx, up(st.cam_free, cam_free.data(), 4 * C));
-  VSL_HIP(ctx, up(st.free_cams, free_cams.data(), 4 * free_cams.size()));
-  VSL_HIP(ctx, up(st.obs_cam, s_cam, 4 * O));
-  VSL_HIP(ctx, up(st.obs_lm, s_lm, 4 * O));
-  VSL_HIP(ctx, up(st.obs_uv, s_uv, 16 * O));
-  VSL_HIP(ctx, up(st.lm_start, lm_start.data(), 4 * (L + 1)));
-  VSL_HIP(ctx, up(st.cam_start, cam_start.data(), 4 * (C + 1)));
-  VSL_HIP(ctx, up(st.cam_obs, cam_obs.data(), 4 * O));
-  if (!st.small) VSL_HIP(ctx, up(st.cam_pos, cam_pos.data(), 4 * O));
-  if (!st.small && st.n_wg > 0) VSL_HIP(ctx, up(st.wg_lm, wg_lm.data(), 4 * wg_lm.size()));
+  VSL_HIP(ctx, up(st.cam_free, hp.cam_free.data(), 4 * C));
+  VSL_HIP(ctx, up(st.free_cams, hp.free_cams.data(), 4 * hp.free_cams.size()));
+  VSL_HIP(ctx, up(st.obs_cam, hp.obs_cam, 4 * O));
+  VSL_HIP(ctx, up(st.obs_lm, hp.obs_lm, 4 * O));
+  VSL_HIP(ctx, up(st.obs_uv, hp.obs_uv, 16 * O));
+  VSL_HIP(ctx, up(st.lm_start, hp.lm_start.data(), 4 * (L + 1)));
+  VSL_HIP(ctx, up(st.cam_start, hp.cam_start.data(), 4 * (C + 1)));
+  VSL_HIP(ctx, up(st.cam_obs, hp.cam_obs.data(), 4 * O));
+  if (!st.small) VSL_HIP(ctx, up(st.cam_pos, hp.cam_pos.data(), 4 * O));
+  if (!st.small && st.n_wg > 0) VSL_HIP(ctx, up(st.wg_lm, hp.wg_lm.data(), 4 * hp.wg_lm.size()));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the uploads above read host vectors that die here
   tr.lap("uploads");
   return VSL_OK;
@@ -2357,32 +2085,18 @@ extern "C" int vsl_ba_session_create(vsl_ctx* ctx, const vsl_ba_problem* prob, c
     return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_session_create: landmark range [%d, %d) must be non-empty and inside [0, %d)", lm_first, lm_first + lm_count, prob->n_lms);
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   BaTrace tr;
-  // sub-problem of the owned landmarks (all cameras)
-  std::vector<int32_t> ocam, olm;
-  std::vector<double> ouv;
-  const bool whole = lm_first == 0 && lm_count == prob->n_lms;  // one rank: the problem itself, no copy
-  if (!whole) {
-    for (int i = 0; i < prob->n_obs; i++) {
-      const int l = prob->obs_lm[i];
-      if (l >= lm_first && l < lm_first + lm_count) {
-        ocam.push_back(prob->obs_cam[i]);
-        olm.push_back(l - lm_first);
-        ouv.push_back(prob->obs_uv[2 * (size_t)i]);
-        ouv.push_back(prob->obs_uv[2 * (size_t)i + 1]);
-      }
+  // sub-problem of the owned landmarks (all cameras); one rank: the problem itself, no copy
+  BaSubObs own;
+  vsl_ba_problem sub = *prob;
+  if (!(lm_first == 0 && lm_count == prob->n_lms)) {
+    try {
+      sub = ba_sub_problem(prob, lm_first, lm_count, own);
+    } catch (const std::bad_alloc&) {
+      return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
     }
-    if (ocam.empty()) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_session_create: landmark range has no observations");
+    if (sub.n_obs == 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_session_create: landmark range has no observations");
   }
   tr.lap("session: sub-problem");
-  vsl_ba_problem sub = *prob;
-  if (!whole) {
-    sub.n_lms = lm_count;
-    sub.n_obs = (int32_t)ocam.size();
-    sub.points = prob->points + 3 * (size_t)lm_first;
-    sub.obs_cam = ocam.data();
-    sub.obs_lm = olm.data();
-    sub.obs_uv = ouv.data();
-  }
   vsl_ba_session* s = new (std::nothrow) vsl_ba_session;
   if (!s) return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
   s->ctx = ctx;

@@ -44,6 +44,7 @@
 #include "dpp_chol.h"
 #include "lm_policy.h"
 #include "dev_arena.h"
+#include "ba_host_plan.h"
 #include "vsl_common.h"
 
 namespace {
@@ -1127,13 +1128,7 @@ bool bf_plan(const vsl_ba_problem* p, const BfLayout& y, char* blk, BfPlan& pl) 
   int* lm_start = (int*)(blk + y.lm_start);
   unsigned* meta = (unsigned*)(blk + y.obs_meta);
   double* s_uv = (double*)(blk + y.obs_uv);
-  memset(lm_start, 0, 4 * ((size_t)L + 1));
-  bool sorted = true;
-  for (int i = 0; i < O; i++) {
-    lm_start[p->obs_lm[i] + 1]++;
-    if (i > 0 && p->obs_lm[i] < p->obs_lm[i - 1]) sorted = false;
-  }
-  for (int l = 0; l < L; l++) lm_start[l + 1] += lm_start[l];
+  const bool sorted = ba_landmark_csr(p, lm_start);
   if (sorted) {
     memcpy(s_uv, p->obs_uv, 16 * (size_t)O);
     // (the camera field is written together with the rest of the word in the landmark loop below: one pass less)

@@ -675,7 +675,6 @@ __global__ __launch_bounds__(CBF_THREADS) void cbf2_backward_kernel(CbfView top,
     cbf_backward<true>(rev, k_end_rev, sh);
 }
 
-#define BCR_MAXB 256  // block size limit of the cyclic reduction: static LDS Us[256][33] + Lp[32][257] = 133 KB (dynamic LDS above 64 KiB is refused by the runtime)
 int vsl_chol_solve_bcr_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out = nullptr);
 
 // Solves S x = b in place (S destroyed, b <- x).  *ok_dev = 1 on success, 0 if S is not SPD.
@@ -837,7 +836,6 @@ extern "C" int vsl_spd_solve(vsl_ctx* ctx, const double* S, const double* b, int
 // Host-only query (no device needed): the ring layout the cyclic solver would use for n unknowns of half bandwidth
 // half_bandwidth -- *block = the kernels' block size, *n_blocks the ring length; returns 0 when there is none
 // (vsl_spd_solve_cyclic / the bundle adjustment then keep the linear band form).
-bool vsl_chol_bcr_cyclic_layout(int n, int bw, int* B_out, int* nblk_out);
 extern "C" int vsl_bcr_cyclic_layout(int n, int half_bandwidth, int* block, int* n_blocks) {
   int B = 0, nb = 0;
   if (n <= 0 || half_bandwidth < 0 || !vsl_chol_bcr_cyclic_layout(n, half_bandwidth, &B, &nb)) return 0;
@@ -848,7 +846,6 @@ extern "C" int vsl_bcr_cyclic_layout(int n, int half_bandwidth, int* block, int*
 
 // Test / diagnostic entry point for the CYCLIC band form: S (dense, row-major, symmetric) has non-zeros only where the
 // cyclic distance min(|i - j|, n - |i - j|) <= half_bandwidth.
-bool vsl_chol_bcr_cyclic_layout(int n, int bw, int* B_out, int* nblk_out);
 extern "C" int vsl_spd_solve_cyclic(vsl_ctx* ctx, const double* S, const double* b, int n, int half_bandwidth, double* x) {
   if (!ctx || !S || !b || !x || n <= 0 || half_bandwidth < 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_spd_solve_cyclic: bad argument");
   const int bw = half_bandwidth, bws = bw + CH_NB;
@@ -1651,22 +1648,6 @@ __global__ void bcr_gather_kernel(const double* __restrict__ bb, int B, const in
     b[o0 + r] = v;
     if (neg_out) neg_out[o0 + r] = -v;
   }
-}
-
-
-// Block layout of the cyclic form: nblk blocks of floor / ceil (n / nblk) unknowns, every one >= bw + 1 (a block couples
-// with its two ring neighbours only) and <= B (the kernels' block size, a multiple of 32 <= BCR_MAXB).  false: no such layout.
-bool vsl_chol_bcr_cyclic_layout(int n, int bw, int* B_out, int* nblk_out) {
-  const int most = n / (bw + 1);  // blocks of >= bw + 1 unknowns each
-  for (int B = (bw + 1 + 31) / 32 * 32; B <= BCR_MAXB; B += 32) {
-    const int nblk = std::max(8, (n + B - 1) / B);  // the fewest blocks of <= B unknowns (fewer blocks: fewer levels)
-    if (nblk <= most) {
-      *B_out = B;
-      *nblk_out = nblk;
-      return true;
-    }
-  }
-  return false;
 }
 
 // S (band storage, n unknowns, half bandwidth bw) x = b by block cyclic reduction; b <- x.  cyclic: the band closes on

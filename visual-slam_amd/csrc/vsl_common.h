@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/vslam_hip.h"
+#include "chol_layout.h"  // VSL_CHOL_NB, BCR_MAXB, vsl_chol_bcr_cyclic_layout: is there a ring of blocks for this cyclic band?
 
 #define VSL_WAVE 64
 #define VSL_META_STRIDE 32  // ints: 128 bytes per image
@@ -204,9 +205,7 @@ int vsl_set_pairs(vsl_ctx* ctx, vsl_frames* f, const int32_t* slot_pairs, int n_
 // dense fp64 Cholesky solve on the device (chol.hip): S x = b in place, *ok_dev = 0 if not SPD
 int vsl_chol_solve_dev(vsl_ctx* ctx, double* S, double* b, int n, int* ok_dev);
 // the same on LAPACK-style lower band storage (chol.hip, "BAND FORM"): S = storage + bws, ld = bws = bw + VSL_CHOL_NB
-#define VSL_CHOL_NB 32
 int vsl_chol_solve_band_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic = 0, double* neg_out = nullptr);
-bool vsl_chol_bcr_cyclic_layout(int n, int bw, int* B_out, int* nblk_out);  // chol.hip: is there a ring of blocks for this cyclic band?
 
 // scratch store of the host-buffer API
 int vsl_ctx_scratch_frames(vsl_ctx* ctx, int w, int h, int feat, vsl_frames** out);
