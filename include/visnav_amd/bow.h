@@ -13,6 +13,14 @@
 #include "dbow2_types.h"
 #include "keypoints.h"
 
+// The device keyframe database (KeyframeDatabaseAmd below) is referenced weakly: the CPU-baseline build of the
+// application links a C ABI without the vsl_bowdb_* entries (oracle/Makefile cpu_baseline) and refuses the option there.
+#pragma weak vsl_bowdb_create
+#pragma weak vsl_bowdb_destroy
+#pragma weak vsl_bowdb_append
+#pragma weak vsl_bowdb_score
+#pragma weak vsl_bowdb_query
+
 namespace visnav {
 
 class ORBVocabularyAmd {
@@ -105,6 +113,109 @@ class ORBVocabularyAmd {
 
  private:
   vsl_voc* voc_ = nullptr;
+};
+
+// The recognition database on the device: what the reference keeps as an inverted file (DBoWInvertedFile, one list of
+// keyframes per vocabulary word, src/slam.cpp:380) plus the keyframes' BowVectors, as ONE device store of vectors
+// (vsl_bowdb).  The walk of the inverted file, the 0.8 rule and the scores of the survivors are one vsl_bowdb_query;
+// index <-> FrameCamId in insertion order, which is the order of every inverted-file list.  Like the inverted file,
+// nothing is ever removed.
+class KeyframeDatabaseAmd {
+ public:
+  struct Survivors {  // the keyframes above the 0.8 rule, in the order the reference's walk first meets them
+    std::vector<FrameCamId> fcids;
+    std::vector<int> counts;      // num_sharing_words (the first shared word counts 0)
+    std::vector<double> scores;   // voc->score(query, keyframe)
+    int n_sharing = 0;            // num_sharing_words.size()
+    int max_count = 0;            // max_num_sharing_words
+  };
+  // n_words = recognition_database.size(): query words at or above it are skipped by the vote
+  explicit KeyframeDatabaseAmd(unsigned n_words = 0) : n_words_(n_words) {}
+  KeyframeDatabaseAmd(const KeyframeDatabaseAmd&) = delete;
+  KeyframeDatabaseAmd& operator=(const KeyframeDatabaseAmd&) = delete;
+  ~KeyframeDatabaseAmd() { release(); }
+  static bool available() {
+    return &vsl_bowdb_create != nullptr && &vsl_bowdb_destroy != nullptr && &vsl_bowdb_append != nullptr &&
+           &vsl_bowdb_score != nullptr && &vsl_bowdb_query != nullptr;
+  }
+  void release() {
+    if (db_) vsl_bowdb_destroy(db_);
+    db_ = nullptr;
+    fcids_.clear();
+    index_.clear();
+  }
+  void resize(unsigned n_words) { n_words_ = n_words; }  // recognition_database.resize(voc->size())
+  unsigned size() const { return n_words_; }
+  size_t keyframes() const { return fcids_.size(); }
+  bool contains(const FrameCamId& f) const { return index_.count(f) != 0; }
+
+  // insert_new_kf_to_db: the keyframe's vector is uploaded once
+  void insert(const FrameCamId& fcid, const DBoW2::BowVector& v) {
+    if (!db_) amd::check(vsl_bowdb_create(amd::ctx(), 1 << 20, 1024, &db_), "KeyframeDatabaseAmd");
+    std::vector<uint32_t> ids;
+    std::vector<double> vals;
+    flatten(v, ids, vals);
+    int idx = -1;
+    amd::check(vsl_bowdb_append(amd::ctx(), db_, ids.data(), vals.data(), (int)ids.size(), &idx), "KeyframeDatabaseAmd::insert");
+    fcids_.push_back(fcid);
+    index_[fcid] = idx;  // a keyframe is inserted once, when it is taken (src/slam.cpp:1219-1258)
+  }
+  // detect_loop_candidates' vote: `excluded` = the connected keyframes with covisible weight >= 30
+  Survivors query_loop(const DBoW2::BowVector& q, const std::vector<FrameCamId>& excluded) const {
+    std::vector<int32_t> ex;
+    for (const auto& f : excluded) {
+      auto it = index_.find(f);
+      if (it != index_.end()) ex.push_back(it->second);
+    }
+    return query(q, ex);
+  }
+  // detect_relocalization_candidate's vote: every stored keyframe takes part
+  Survivors query_reloc(const DBoW2::BowVector& q) const { return query(q, {}); }
+  // voc->score(q, keyframe) for stored keyframes, by index: no stored vector is uploaded again
+  std::vector<double> score(const DBoW2::BowVector& q, const std::vector<FrameCamId>& fcids) const {
+    std::vector<double> s(fcids.size(), 0.0);
+    if (fcids.empty()) return s;
+    std::vector<int32_t> idx;
+    for (const auto& f : fcids) idx.push_back(index_.at(f));
+    std::vector<uint32_t> ids;
+    std::vector<double> vals;
+    flatten(q, ids, vals);
+    amd::check(vsl_bowdb_score(amd::ctx(), db_, ids.data(), vals.data(), (int)ids.size(), idx.data(), (int)idx.size(), s.data()),
+               "KeyframeDatabaseAmd::score");
+    return s;
+  }
+
+ private:
+  static void flatten(const DBoW2::BowVector& v, std::vector<uint32_t>& ids, std::vector<double>& vals) {
+    for (const auto& kv : v) {
+      ids.push_back(kv.first);
+      vals.push_back(kv.second);
+    }
+  }
+  Survivors query(const DBoW2::BowVector& q, const std::vector<int32_t>& ex) const {
+    Survivors out;
+    if (!db_) return out;
+    std::vector<uint32_t> ids;
+    std::vector<double> vals;
+    flatten(q, ids, vals);
+    const int cap = (int)fcids_.size();
+    std::vector<int32_t> idx(cap), cnt(cap);
+    out.scores.resize(cap);
+    int n = 0;
+    amd::check(vsl_bowdb_query(amd::ctx(), db_, ids.data(), vals.data(), (int)ids.size(), n_words_, ex.data(), (int)ex.size(), 0.8f, cap,
+                               idx.data(), cnt.data(), out.scores.data(), &n, &out.n_sharing, &out.max_count),
+               "KeyframeDatabaseAmd::query");
+    out.scores.resize(n);
+    for (int i = 0; i < n; i++) {
+      out.fcids.push_back(fcids_[(size_t)idx[i]]);
+      out.counts.push_back(cnt[i]);
+    }
+    return out;
+  }
+  vsl_bowdb* db_ = nullptr;
+  unsigned n_words_ = 0;
+  std::vector<FrameCamId> fcids_;
+  std::map<FrameCamId, int> index_;
 };
 
 // include/visnav/keypoints.h:243-254 with the reference's argument order; the cv::Ptr<cv::ORB> argument of the

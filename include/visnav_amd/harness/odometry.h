@@ -49,6 +49,8 @@ namespace visnav {
 namespace harness {
 
 inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
+// the device keyframe database (OdometryOptions::device_place_db) is referenced weakly in the same way (bow.h)
+inline bool device_place_db_available() { return KeyframeDatabaseAmd::available(); }
 
 struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.cpp:258-309
   int num_features_per_image = 1500;
@@ -80,6 +82,10 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   // (vsl_frames_stereo_inliers on the keyframe's pair slot); add_new_landmarks takes the device's p_c.  Same inliers,
   // same points, same trajectory as the host restatement (tests/test_stereo_gpu.py).
   bool device_stereo = false;
+  // place recognition (loop detection and relocalisation candidates) against the device keyframe database
+  // (KeyframeDatabaseAmd: one vsl_bowdb_query per keyframe or lost frame) instead of the host inverted file.  Same
+  // candidates, same trajectory (tests/test_place_db_dropin.py); the host inverted file is then never filled.
+  bool device_place_db = false;
   // src/slam.cpp:244-247, :274-294 (the reference's defaults are true / true / true; they need --voc-path)
   bool enable_relocalization = false;
   bool enable_loop_closure = false;
@@ -292,6 +298,7 @@ class Odometry {
   bool tracking_successful = true;
   CovisibilityGraph graph;
   DBoWInvertedFile orb_db;  // resized to the vocabulary size (src/slam.cpp:380)
+  KeyframeDatabaseAmd place_db;  // stands in for orb_db with opt.device_place_db
   ConsistentGroups consistent_groups;
   std::vector<FrameCamId> enough_consistent_candidates;
   std::vector<std::pair<FrameCamId, FrameCamId>> loop_edges;
@@ -329,8 +336,14 @@ class Odometry {
       if (kd.corner_descriptors.size() != kd.corners.size()) fused_download_corners(cur_base, kd);
     }
     ImageRef l(img_left);
-    if (orb_voc && relocalize_camera(fcidl, l.img, calib_cam, graph, orb_voc, orb_db, cameras, vel, current_pose, feature_corners,
-                                     landmarks, opt.motion_threshold, opt.reprojection_error_pnp_inlier_threshold_pixel, md, rng)) {
+    const bool relocalized =
+        !orb_voc ? false
+                 : opt.device_place_db
+                       ? relocalize_camera(fcidl, l.img, calib_cam, graph, orb_voc, place_db, cameras, vel, current_pose, feature_corners,
+                                           landmarks, opt.motion_threshold, opt.reprojection_error_pnp_inlier_threshold_pixel, md, rng)
+                       : relocalize_camera(fcidl, l.img, calib_cam, graph, orb_voc, orb_db, cameras, vel, current_pose, feature_corners,
+                                           landmarks, opt.motion_threshold, opt.reprojection_error_pnp_inlier_threshold_pixel, md, rng);
+    if (relocalized) {
       current_pose = md.T_w_c;
       tracking_successful = true;
       n_relocalized++;
@@ -343,7 +356,8 @@ class Odometry {
     typedef std::chrono::steady_clock Clk;
     auto ms = [](Clk::time_point a, Clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const FrameCamId fcidl(current_frame, 0), fcidr(current_frame, 1);
-    if (orb_voc && orb_db.empty()) orb_db.resize(orb_voc->size());
+    if (orb_voc && opt.device_place_db) place_db.resize(orb_voc->size());
+    else if (orb_voc && orb_db.empty()) orb_db.resize(orb_voc->size());
     std::vector<Eigen::Vector2d, Eigen::aligned_allocator<Eigen::Vector2d>> projected_points;
     std::vector<TrackId> projected_track_ids;
     LandmarkMatchData md;
@@ -416,8 +430,11 @@ class Odometry {
       cam_right.active = true;
       if (opt.enable_loop_closure && orb_voc) {  // src/slam.cpp:1219-1258
         auto tl = Clk::now();
-        bool loop_detected = detect_loop_closure(fcidl, cam_left, cameras, orb_db, orb_voc, graph, consistent_groups,
-                                                 enough_consistent_candidates, opt.num_cov_threshold * 2, opt.num_consistency);
+        bool loop_detected = opt.device_place_db
+                                 ? detect_loop_closure(fcidl, cam_left, cameras, place_db, orb_voc, graph, consistent_groups,
+                                                       enough_consistent_candidates, opt.num_cov_threshold * 2, opt.num_consistency)
+                                 : detect_loop_closure(fcidl, cam_left, cameras, orb_db, orb_voc, graph, consistent_groups,
+                                                       enough_consistent_candidates, opt.num_cov_threshold * 2, opt.num_consistency);
         if (opt.force_loop_from >= 0 && fcidl.frame_id >= opt.force_loop_from && n_loops_closed == 0 &&
             cameras.count(FrameCamId(opt.force_loop_candidate, 0))) {
           enough_consistent_candidates.assign(1, FrameCamId(opt.force_loop_candidate, 0));
@@ -444,7 +461,9 @@ class Odometry {
         }
         loop_ms += ms(tl, Clk::now());
       } else if (orb_voc && graph_needed) {
-        insert_new_kf_to_db(fcidl, cam_left, orb_db);  // relocalisation alone still needs the inverted file
+        // relocalisation alone still needs the inverted file
+        if (opt.device_place_db) insert_new_kf_to_db(fcidl, cam_left, place_db);
+        else insert_new_kf_to_db(fcidl, cam_left, orb_db);
       }
       cameras[fcidl] = cam_left;
       cameras[fcidr] = cam_right;

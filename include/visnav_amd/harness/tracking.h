@@ -97,6 +97,17 @@ inline bool track_camera(const Sophus::SE3d& current_pose, const std::shared_ptr
   return false;
 }
 
+// detect_relocalization_candidate behind the vote (tracking.h:201-221): the five best-scoring keyframes
+inline void best_relocalization_candidates(const std::vector<FrameCamId>& cand, const std::vector<double>& scores,
+                                           std::vector<FrameCamId>& candidate_kf_fcids) {
+  std::vector<std::pair<double, FrameCamId>> score_and_match;
+  for (size_t i = 0; i < cand.size(); i++) score_and_match.emplace_back(scores[i], cand[i]);
+  const int top = std::min((int)score_and_match.size(), 5);
+  std::partial_sort(score_and_match.begin(), score_and_match.begin() + top, score_and_match.end(),
+                    [](const std::pair<double, FrameCamId>& a, const std::pair<double, FrameCamId>& b) { return a.first > b.first; });
+  for (int i = 0; i < top; i++) candidate_kf_fcids.push_back(score_and_match[(size_t)i].second);
+}
+
 // tracking.h:169-222 (the scores of the surviving keyframes in ONE batched launch)
 inline bool detect_relocalization_candidate(const ORBVocabularyAmd* voc, const DBoWInvertedFile& recognition_database,
                                             const DBoW2::BowVector& bow_vector, const Cameras& keyframes,
@@ -128,13 +139,18 @@ inline bool detect_relocalization_candidate(const ORBVocabularyAmd* voc, const D
       cand.push_back(f);
       bows.push_back(&keyframes.at(f).bow_vector);
     }
-  const std::vector<double> scores = voc->score_batch(bow_vector, bows);
-  std::vector<std::pair<double, FrameCamId>> score_and_match;
-  for (size_t i = 0; i < cand.size(); i++) score_and_match.emplace_back(scores[i], cand[i]);
-  const int top = std::min((int)score_and_match.size(), 5);
-  std::partial_sort(score_and_match.begin(), score_and_match.begin() + top, score_and_match.end(),
-                    [](const std::pair<double, FrameCamId>& a, const std::pair<double, FrameCamId>& b) { return a.first > b.first; });
-  for (int i = 0; i < top; i++) candidate_kf_fcids.push_back(score_and_match[(size_t)i].second);
+  best_relocalization_candidates(cand, voc->score_batch(bow_vector, bows), candidate_kf_fcids);
+  return true;
+}
+// ... with the device database: vote, 0.8 rule and scores are ONE query
+inline bool detect_relocalization_candidate(const ORBVocabularyAmd* voc, const KeyframeDatabaseAmd& recognition_database,
+                                            const DBoW2::BowVector& bow_vector, const Cameras& keyframes,
+                                            std::vector<FrameCamId>& candidate_kf_fcids) {
+  (void)voc;
+  (void)keyframes;
+  const KeyframeDatabaseAmd::Survivors sv = recognition_database.query_reloc(bow_vector);
+  if (sv.n_sharing == 0) return false;
+  best_relocalization_candidates(sv.fcids, sv.scores, candidate_kf_fcids);
   return true;
 }
 
@@ -171,9 +187,11 @@ inline void correspondences_with_candidate(const FrameCamId& fcid, const FrameCa
   }
 }
 
-// tracking.h:241-419.  `img` = the decoded left image of frame `fcid` (the reference re-reads it from img_path).
-inline bool relocalize_camera(const FrameCamId& fcid, const pangolin::ManagedImage<uint8_t>& img, const Calibration& calib_cam,
-                              const CovisibilityGraph& graph, const ORBVocabularyAmd* voc, const DBoWInvertedFile& recognition_database,
+// tracking.h:241-419 over either form of the recognition database.  `img` = the decoded left image of frame `fcid` (the
+// reference re-reads it from img_path).
+template <class Database>
+inline bool relocalize_camera_on(const FrameCamId& fcid, const pangolin::ManagedImage<uint8_t>& img, const Calibration& calib_cam,
+                              const CovisibilityGraph& graph, const ORBVocabularyAmd* voc, const Database& recognition_database,
                               const Cameras& keyframes, const Sophus::SE3d vel, const Sophus::SE3d& current_pose,
                               const Corners& feature_corners, const Landmarks& landmarks, double motion_threshold,
                               double reprojection_error_pnp_inlier_threshold_pixel, LandmarkMatchData& lm_match_data, XorShift& rng) {
@@ -217,6 +235,24 @@ inline bool relocalize_camera(const FrameCamId& fcid, const pangolin::ManagedIma
     if (reloc_pose_good) break;
   }
   return reloc_pose_good;
+}
+
+// tracking.h:241-419
+inline bool relocalize_camera(const FrameCamId& fcid, const pangolin::ManagedImage<uint8_t>& img, const Calibration& calib_cam,
+                              const CovisibilityGraph& graph, const ORBVocabularyAmd* voc, const DBoWInvertedFile& recognition_database,
+                              const Cameras& keyframes, const Sophus::SE3d vel, const Sophus::SE3d& current_pose,
+                              const Corners& feature_corners, const Landmarks& landmarks, double motion_threshold,
+                              double reprojection_error_pnp_inlier_threshold_pixel, LandmarkMatchData& lm_match_data, XorShift& rng) {
+  return relocalize_camera_on(fcid, img, calib_cam, graph, voc, recognition_database, keyframes, vel, current_pose, feature_corners, landmarks,
+                              motion_threshold, reprojection_error_pnp_inlier_threshold_pixel, lm_match_data, rng);
+}
+inline bool relocalize_camera(const FrameCamId& fcid, const pangolin::ManagedImage<uint8_t>& img, const Calibration& calib_cam,
+                              const CovisibilityGraph& graph, const ORBVocabularyAmd* voc, const KeyframeDatabaseAmd& recognition_database,
+                              const Cameras& keyframes, const Sophus::SE3d vel, const Sophus::SE3d& current_pose,
+                              const Corners& feature_corners, const Landmarks& landmarks, double motion_threshold,
+                              double reprojection_error_pnp_inlier_threshold_pixel, LandmarkMatchData& lm_match_data, XorShift& rng) {
+  return relocalize_camera_on(fcid, img, calib_cam, graph, voc, recognition_database, keyframes, vel, current_pose, feature_corners, landmarks,
+                              motion_threshold, reprojection_error_pnp_inlier_threshold_pixel, lm_match_data, rng);
 }
 
 }  // namespace harness

@@ -202,6 +202,57 @@ inline double compute_min_connected_covisible(const Camera& new_kf, const Camera
     if (s < min_score) min_score = s;
   return min_score;
 }
+// ... with the keyframes' vectors in the device database: the neighbours are scored by index, nothing is uploaded twice
+inline double compute_min_connected_covisible(const Camera& new_kf, const KeyframeDatabaseAmd& recognition_database, int threshold) {
+  std::vector<FrameCamId> nbs;
+  for (const auto& kv : new_kf.covisible_weights)
+    if (kv.second > threshold) nbs.push_back(kv.first);
+  double min_score = 1;
+  for (double s : recognition_database.score(new_kf.bow_vector, nbs))
+    if (s < min_score) min_score = s;
+  return min_score;
+}
+
+namespace amd {
+// detect_loop_candidates behind the vote (loop_closure_utils.h:199-263): `scored` = the keyframes whose count is above
+// 0.8 of the maximum, in the order of the walk, with their scores.  A graph neighbour adds to the accumulated score
+// when its own count is above the threshold -- that is, when it is one of `scored`.
+inline std::vector<FrameCamId> loop_candidates_of_scored(const FrameCamId& new_kf_fcid, const Camera& new_kf, const CovisibilityGraph& graph,
+                                                         double min_score, const std::vector<FrameCamId>& scored,
+                                                         const std::vector<double>& scores, size_t n_sharing, int max_num_sharing_words) {
+  if (std::getenv("VISNAV_AMD_TRACE")) {
+    std::fprintf(stderr, "  loop candidates of %lld: %zu keyframes share words (max %d), %zu above 0.8 max:", (long long)new_kf_fcid.frame_id,
+                 n_sharing, max_num_sharing_words, scored.size());
+    for (size_t i = 0; i < scored.size(); i++) std::fprintf(stderr, " %lld=%.3f", (long long)scored[i].frame_id, scores[i]);
+    std::fprintf(stderr, " | connected: %zu, bow nnz %zu\n", graph.at(new_kf_fcid).size(), new_kf.bow_vector.size());
+  }
+  std::vector<std::pair<double, FrameCamId>> loop_score_and_match;
+  std::unordered_map<FrameCamId, double, FrameCamIdHash> loop_score;
+  for (size_t i = 0; i < scored.size(); i++) {
+    loop_score[scored[i]] = scores[i];
+    if (scores[i] >= min_score) loop_score_and_match.emplace_back(scores[i], scored[i]);
+  }
+  if (loop_score_and_match.empty()) return {};
+  double best_acc_score = min_score;
+  for (const auto& score_fcid : loop_score_and_match) {
+    double acc_score = score_fcid.first;
+    for (const auto& nb : graph.at(score_fcid.second)) {
+      auto it = loop_score.find(nb);
+      if (it != loop_score.end()) acc_score += it->second;
+    }
+    if (acc_score > best_acc_score) best_acc_score = acc_score;
+  }
+  const double min_score_to_retain = 0.75f * best_acc_score;
+  std::set<FrameCamId> already_added_kf;
+  std::vector<FrameCamId> loop_candidates;
+  for (const auto& score_fcid : loop_score_and_match)
+    if (score_fcid.first > min_score_to_retain && !already_added_kf.count(score_fcid.second)) {
+      loop_candidates.push_back(score_fcid.second);
+      already_added_kf.insert(score_fcid.second);
+    }
+  return loop_candidates;
+}
+}  // namespace amd
 
 // loop_closure_utils.h:141-263.  The reference walks unordered_maps; here candidates are visited in the order their
 // first shared word was met (deterministic), everything else -- the counting quirk (a keyframe's first shared word counts
@@ -245,37 +296,22 @@ inline std::vector<FrameCamId> detect_loop_candidates(const FrameCamId& new_kf_f
       bows.push_back(&keyframes.at(f).bow_vector);
     }
   const std::vector<double> scores = voc->score_batch(new_kf.bow_vector, bows);  // ONE launch for all candidates
-  if (std::getenv("VISNAV_AMD_TRACE")) {
-    std::fprintf(stderr, "  loop candidates of %lld: %zu keyframes share words (max %d), %zu above 0.8 max:", (long long)new_kf_fcid.frame_id,
-                 num_sharing_words.size(), max_num_sharing_words, scored.size());
-    for (size_t i = 0; i < scored.size(); i++) std::fprintf(stderr, " %lld=%.3f", (long long)scored[i].frame_id, scores[i]);
-    std::fprintf(stderr, " | connected: %zu, bow nnz %zu\n", connected_frames.size(), new_kf.bow_vector.size());
-  }
-  std::vector<std::pair<double, FrameCamId>> loop_score_and_match;
-  std::unordered_map<FrameCamId, double, FrameCamIdHash> loop_score;
-  for (size_t i = 0; i < scored.size(); i++) {
-    loop_score[scored[i]] = scores[i];
-    if (scores[i] >= min_score) loop_score_and_match.emplace_back(scores[i], scored[i]);
-  }
-  if (loop_score_and_match.empty()) return {};
-  double best_acc_score = min_score;
-  for (const auto& score_fcid : loop_score_and_match) {
-    double acc_score = score_fcid.first;
-    for (const auto& nb : graph.at(score_fcid.second)) {
-      auto it = num_sharing_words.find(nb);
-      if (it != num_sharing_words.end() && it->second > sharing_words_threshold) acc_score += loop_score.at(nb);
-    }
-    if (acc_score > best_acc_score) best_acc_score = acc_score;
-  }
-  const double min_score_to_retain = 0.75f * best_acc_score;
-  std::set<FrameCamId> already_added_kf;
-  std::vector<FrameCamId> loop_candidates;
-  for (const auto& score_fcid : loop_score_and_match)
-    if (score_fcid.first > min_score_to_retain && !already_added_kf.count(score_fcid.second)) {
-      loop_candidates.push_back(score_fcid.second);
-      already_added_kf.insert(score_fcid.second);
-    }
-  return loop_candidates;
+  return amd::loop_candidates_of_scored(new_kf_fcid, new_kf, graph, min_score, scored, scores, num_sharing_words.size(),
+                                        max_num_sharing_words);
+}
+// ... with the device database: the walk, the 0.8 rule and the scores are ONE query (vsl_bowdb_query); a connected
+// keyframe takes part in the vote only when its covisible weight is below 30
+inline std::vector<FrameCamId> detect_loop_candidates(const FrameCamId& new_kf_fcid, const Camera& new_kf, const Cameras& keyframes,
+                                                      const CovisibilityGraph& graph, double min_score,
+                                                      KeyframeDatabaseAmd& recognition_database, const ORBVocabularyAmd* voc) {
+  (void)keyframes;
+  (void)voc;
+  std::vector<FrameCamId> excluded;
+  for (const auto& f : graph.at(new_kf_fcid))
+    if (recognition_database.contains(f) && new_kf.covisible_weights.at(f) >= 30) excluded.push_back(f);
+  const KeyframeDatabaseAmd::Survivors sv = recognition_database.query_loop(new_kf.bow_vector, excluded);
+  if (sv.n_sharing == 0) return {};
+  return amd::loop_candidates_of_scored(new_kf_fcid, new_kf, graph, min_score, sv.fcids, sv.scores, (size_t)sv.n_sharing, sv.max_count);
 }
 
 // loop_closure_utils.h:269-276
@@ -283,13 +319,25 @@ inline void insert_new_kf_to_db(const FrameCamId& new_kf_fcid, const Camera& new
   for (const auto& wv : new_kf.bow_vector)
     if (wv.first < recognition_database.size()) recognition_database[wv.first].push_back(new_kf_fcid);
 }
+inline void insert_new_kf_to_db(const FrameCamId& new_kf_fcid, const Camera& new_kf, KeyframeDatabaseAmd& recognition_database) {
+  recognition_database.insert(new_kf_fcid, new_kf.bow_vector);
+}
 
-// loop_closure_utils.h:294-388
-inline bool detect_loop_closure(const FrameCamId& new_kf_fcid, const Camera& new_kf, const Cameras& keyframes,
-                                DBoWInvertedFile& recognition_database, const ORBVocabularyAmd* voc, const CovisibilityGraph& graph,
-                                ConsistentGroups& consistent_groups, std::vector<FrameCamId>& enough_consistent_candidates, int threshold,
-                                int num_consistency_threshold) {
-  const double min_score = compute_min_connected_covisible(new_kf, keyframes, voc, threshold);
+namespace amd {
+inline double min_connected_score(const Camera& new_kf, const Cameras& keyframes, const ORBVocabularyAmd* voc, const DBoWInvertedFile&, int threshold) {
+  return compute_min_connected_covisible(new_kf, keyframes, voc, threshold);
+}
+inline double min_connected_score(const Camera& new_kf, const Cameras&, const ORBVocabularyAmd*, const KeyframeDatabaseAmd& db, int threshold) {
+  return compute_min_connected_covisible(new_kf, db, threshold);
+}
+
+// loop_closure_utils.h:294-388 over either form of the recognition database
+template <class Database>
+inline bool detect_loop_closure_on(const FrameCamId& new_kf_fcid, const Camera& new_kf, const Cameras& keyframes,
+                                   Database& recognition_database, const ORBVocabularyAmd* voc, const CovisibilityGraph& graph,
+                                   ConsistentGroups& consistent_groups, std::vector<FrameCamId>& enough_consistent_candidates, int threshold,
+                                   int num_consistency_threshold) {
+  const double min_score = min_connected_score(new_kf, keyframes, voc, recognition_database, threshold);
   const std::vector<FrameCamId> loop_candidates =
       detect_loop_candidates(new_kf_fcid, new_kf, keyframes, graph, min_score, recognition_database, voc);
   if (std::getenv("VISNAV_AMD_TRACE")) {
@@ -336,6 +384,23 @@ inline bool detect_loop_closure(const FrameCamId& new_kf_fcid, const Camera& new
   consistent_groups = current_consistent_groups;
   if (new_kf_fcid.cam_id == 0) insert_new_kf_to_db(new_kf_fcid, new_kf, recognition_database);
   return !enough_consistent_candidates.empty();
+}
+}  // namespace amd
+
+// loop_closure_utils.h:294-388
+inline bool detect_loop_closure(const FrameCamId& new_kf_fcid, const Camera& new_kf, const Cameras& keyframes,
+                                DBoWInvertedFile& recognition_database, const ORBVocabularyAmd* voc, const CovisibilityGraph& graph,
+                                ConsistentGroups& consistent_groups, std::vector<FrameCamId>& enough_consistent_candidates, int threshold,
+                                int num_consistency_threshold) {
+  return amd::detect_loop_closure_on(new_kf_fcid, new_kf, keyframes, recognition_database, voc, graph, consistent_groups,
+                                     enough_consistent_candidates, threshold, num_consistency_threshold);
+}
+inline bool detect_loop_closure(const FrameCamId& new_kf_fcid, const Camera& new_kf, const Cameras& keyframes,
+                                KeyframeDatabaseAmd& recognition_database, const ORBVocabularyAmd* voc, const CovisibilityGraph& graph,
+                                ConsistentGroups& consistent_groups, std::vector<FrameCamId>& enough_consistent_candidates, int threshold,
+                                int num_consistency_threshold) {
+  return amd::detect_loop_closure_on(new_kf_fcid, new_kf, keyframes, recognition_database, voc, graph, consistent_groups,
+                                     enough_consistent_candidates, threshold, num_consistency_threshold);
 }
 
 // loop_closure_utils.h:398-416

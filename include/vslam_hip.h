@@ -560,6 +560,19 @@ int vsl_bowdb_append(vsl_ctx* ctx, vsl_bowdb* db, const uint32_t* ids, const dou
 int vsl_bowdb_info(const vsl_bowdb* db, int* n_vectors, int64_t* n_entries);
 int vsl_bowdb_score(vsl_ctx* ctx, const vsl_bowdb* db, const uint32_t* q_ids, const double* q_vals, int q_nnz,
                     const int32_t* cand_index, int m, double* scores);
+/* Place recognition in one call: the shared-word vote of detect_loop_candidates (loop_closure_utils.h:141-197) and
+ * detect_relocalization_candidate (tracking.h:169-199) against every stored vector, on the device.  A vector's count is
+ * the number of query words with id < n_words it also holds, minus one (the reference's first shared word counts 0);
+ * vectors listed in exclude_index are treated as absent.  *max_count = the largest count, *n_sharing = the number of
+ * vectors sharing at least one word, and the candidates are the vectors with count > (int)(*max_count * keep_fraction)
+ * (float arithmetic; the reference uses 0.8f) in the order the reference's walk of the inverted file meets them:
+ * ascending (first shared word, index).  cand_score = the L1 score against the WHOLE query, bit-equal to
+ * vsl_bowdb_score.  VSL_ERR_CAPACITY when there are more candidates than cap or the query has more than 8192 words;
+ * an empty store or query gives zero counts.  Only a fixed header and the candidates' records cross PCIe. */
+int vsl_bowdb_query(vsl_ctx* ctx, const vsl_bowdb* db, const uint32_t* q_ids, const double* q_vals, int q_nnz,
+                    uint32_t n_words, const int32_t* exclude_index, int n_exclude, float keep_fraction, int cap,
+                    int32_t* cand_index, int32_t* cand_count, double* cand_score, int* n_candidates, int* n_sharing,
+                    int* max_count);
 
 /* Bit-order converters of include/visnav/converter.h:23-33 and :50-61
  * (bitset<256> word layout <-> 32-byte MSB-first row).  Pure host helpers. */

@@ -629,6 +629,25 @@ class BowDatabase:
                                                 len(q_ids), ip, m, scores.ctypes.data_as(f64p)))
         return scores[:m].copy()
 
+    def query(self, q_ids, q_vals, n_words, exclude=(), keep_fraction=0.8, cap=None):
+        """vsl_bowdb_query: the place-recognition vote, the keep_fraction rule and the L1 scores in one device pass.
+        Returns (index, count, score, n_sharing, max_count); the candidates in ascending (first shared word, index)."""
+        q_ids = np.ascontiguousarray(q_ids, np.uint32)
+        q_vals = np.ascontiguousarray(q_vals, np.float64)
+        assert len(q_ids) == len(q_vals)
+        exclude = np.ascontiguousarray(exclude, np.int32)
+        cap = self.info()[0] if cap is None else int(cap)
+        idx = np.zeros(max(cap, 1), np.int32)
+        cnt = np.zeros(max(cap, 1), np.int32)
+        sc = np.zeros(max(cap, 1), np.float64)
+        n, ns, mx = C.c_int32(), C.c_int32(), C.c_int32()
+        self.ctx._ck(self.ctx.L.vsl_bowdb_query(self.ctx.h, self.h, q_ids.ctypes.data_as(u32p), q_vals.ctypes.data_as(f64p),
+                                                len(q_ids), C.c_uint32(int(n_words)), exclude.ctypes.data_as(i32p), len(exclude),
+                                                C.c_float(float(keep_fraction)), cap, idx.ctypes.data_as(i32p),
+                                                cnt.ctypes.data_as(i32p), sc.ctypes.data_as(f64p), C.byref(n), C.byref(ns),
+                                                C.byref(mx)))
+        return idx[:n.value].copy(), cnt[:n.value].copy(), sc[:n.value].copy(), ns.value, mx.value
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.L.vsl_bowdb_destroy(self.h)

@@ -52,6 +52,7 @@ int main(int argc, char** argv) {
     else if (a == "--ba-merge-after") opt.ba_merge_after = std::atoi(need("--ba-merge-after").c_str());  // with --async-ba: deterministic hand-over
     else if (a == "--fused") opt.fused_tracking = true;
     else if (a == "--device-stereo") opt.device_stereo = true;  // with --fused: epipolar inliers + triangulation on the device
+    else if (a == "--device-place-db") opt.device_place_db = true;  // loop / relocalisation candidates by one device query per keyframe
     else if (a == "--no-lookahead") lookahead = false;
     else if (a == "--replicas") replicas = std::atoi(need("--replicas").c_str());
     else if (a == "--kf-min-inliers") opt.new_kf_min_inliers = std::atoi(need("--kf-min-inliers").c_str());
@@ -88,6 +89,10 @@ int main(int argc, char** argv) {
   }
   if (opt.device_stereo && !device_stereo_available()) {
     std::fprintf(stderr, "--device-stereo: this build's C ABI has no device stereo stage (vsl_frames_stereo_inliers)\n");
+    return 2;
+  }
+  if (opt.device_place_db && !device_place_db_available()) {
+    std::fprintf(stderr, "--device-place-db: this build's C ABI has no device keyframe database (vsl_bowdb_query)\n");
     return 2;
   }
   Calibration calib;
@@ -224,8 +229,12 @@ int main(int argc, char** argv) {
       prior.data()[4] += 0.2;
       LandmarkMatchData md;
       XorShift rng;
-      const bool ok = relocalize_camera(probe, l.img, odo.calib_cam, odo.graph, odo.orb_voc, odo.orb_db, odo.cameras, Sophus::SE3d(), prior,
-                                        odo.feature_corners, odo.landmarks, 1.0, opt.reprojection_error_pnp_inlier_threshold_pixel, md, rng);
+      const bool ok =
+          opt.device_place_db
+              ? relocalize_camera(probe, l.img, odo.calib_cam, odo.graph, odo.orb_voc, odo.place_db, odo.cameras, Sophus::SE3d(), prior,
+                                  odo.feature_corners, odo.landmarks, 1.0, opt.reprojection_error_pnp_inlier_threshold_pixel, md, rng)
+              : relocalize_camera(probe, l.img, odo.calib_cam, odo.graph, odo.orb_voc, odo.orb_db, odo.cameras, Sophus::SE3d(), prior,
+                                  odo.feature_corners, odo.landmarks, 1.0, opt.reprojection_error_pnp_inlier_threshold_pixel, md, rng);
       reloc_ok = ok ? 1 : 0;
       if (ok) {
         double e = 0;
@@ -264,12 +273,12 @@ int main(int argc, char** argv) {
   const StageClock& c = odo.clock;
   std::printf(
       "{\"frames\": %d, \"keyframes\": %d, \"streams\": %d, \"streams_agree\": %s, \"frames_per_s\": %.2f, \"ms_per_frame\": %.3f, \"image_decode_s\": %.3f, "
-      "\"ate_rmse_m\": %.6f, \"ate_associations\": %d, \"landmarks\": %zu, \"active_landmarks\": %zu, \"async_ba\": %s, \"fused_tracking\": %s, \"device_stereo\": %s, "
+      "\"ate_rmse_m\": %.6f, \"ate_associations\": %d, \"landmarks\": %zu, \"active_landmarks\": %zu, \"async_ba\": %s, \"fused_tracking\": %s, \"device_stereo\": %s, \"device_place_db\": %s, "
       "\"stage_ms_total\": {\"detect\": %.1f, \"stereo_match\": %.1f, \"project_match\": %.1f, \"localize\": %.1f, \"map\": %.1f, "
       "\"ba\": %.1f, \"bow\": %.1f, \"loop\": %.1f, \"global_ba\": %.1f}, \"ba_runs\": %d, \"bow_vectors\": %zu, "
       "\"tracking_lost\": %d, \"relocalized\": %d, \"loops_closed\": %d, \"global_ba_runs\": %d, \"reloc_check_ok\": %d, \"reloc_check_err_m\": %.6f}\n",
       n_frames, n_kf, replicas, replicas_agree ? "true" : "false", replicas * n_frames / run_s, 1e3 * run_s / n_frames, decode_s, ate, n_assoc, odo.landmarks.size(), n_active,
-      opt.async_ba ? "true" : "false", opt.fused_tracking ? "true" : "false", opt.device_stereo ? "true" : "false", c.detect_ms, c.stereo_match_ms, c.project_match_ms, c.localize_ms, c.map_ms, c.ba_ms, c.bow_ms, odo.loop_ms, odo.gba_ms, c.ba_runs, odo.bow_vectors.size(),
+      opt.async_ba ? "true" : "false", opt.fused_tracking ? "true" : "false", opt.device_stereo ? "true" : "false", opt.device_place_db ? "true" : "false", c.detect_ms, c.stereo_match_ms, c.project_match_ms, c.localize_ms, c.map_ms, c.ba_ms, c.bow_ms, odo.loop_ms, odo.gba_ms, c.ba_runs, odo.bow_vectors.size(),
       odo.n_tracking_lost, odo.n_relocalized, odo.n_loops_closed, odo.n_global_ba, reloc_ok, reloc_err_m);
   amd::release_thread_ctx();  // the main thread's context (image registration), before static / thread-local teardown
   return 0;

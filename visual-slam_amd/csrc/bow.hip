@@ -323,22 +323,19 @@ __global__ __launch_bounds__(1024) void bow_assemble_kernel(const uint32_t* __re
 // 0xFFFFFFFF so that the lower-bound search is branch-free; a wavefront per candidate, BOW_SCORE_U 64-word chunks in flight;
 // matched terms are summed in ascending word order -- the reference's order; unmatched words add nothing there --
 // by walking the chunk's ballot and reading the lane's term with v_readlane.
-__global__ __launch_bounds__(256) void bow_score_lds_kernel(const uint32_t* __restrict__ q_ids, const double* __restrict__ q_vals,
-                                                            int q_nnz, int P, const uint32_t* __restrict__ c_ids,
-                                                            const double* __restrict__ c_vals, const int64_t* __restrict__ off,
-                                                            const int32_t* __restrict__ idx, int m, double* __restrict__ scores) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  double* qv = reinterpret_cast<double*>(smem);                 // [q_nnz] (rounded up to even)
-  uint32_t* qi = reinterpret_cast<uint32_t*>(qv + ((q_nnz + 1) & ~1));  // [P]
-  for (int i = threadIdx.x; i < P; i += 256) qi[i] = i < q_nnz ? q_ids[i] : 0xFFFFFFFFu;
-  for (int i = threadIdx.x; i < q_nnz; i += 256) qv[i] = q_vals[i];
-  __syncthreads();
-  const int cand = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (cand >= m) return;
-  const int lane = threadIdx.x & 63;
-  const int vec = idx ? idx[cand] : cand;
-  const int64_t a = off[vec], b = off[vec + 1];
+// The wavefront's pass over one stored vector [a, b) is shared with the place-recognition query below (VOTE): there the
+// same ballots also give the number of shared words with id < n_words and the smallest of them.
+struct BowVote {
+  int shared;      // query words (id < n_words) also present in the vector
+  uint32_t first;  // the smallest of them (0xFFFFFFFF: none)
+};
+template <bool VOTE>
+__device__ __forceinline__ double bow_score_wave(const uint32_t* __restrict__ qi, const double* __restrict__ qv, int P,
+                                                 const uint32_t* __restrict__ c_ids, const double* __restrict__ c_vals, int64_t a,
+                                                 int64_t b, int lane, uint32_t n_words, BowVote* vote) {
   double score = 0.0;
+  int shared = 0;
+  uint32_t first = 0xFFFFFFFFu;
   // BOW_SCORE_U x 64 words per round.  Measured at M = 100 / 10,000 candidates of ~1500 words: 4 chunks 18 / 64 us;
   // with the next round's words prefetched one round ahead 24 / 64; 8 chunks 22 / 81 (56 VGPRs) -- kept: 4, no prefetch.
   for (int64_t base = a; base < b; base += 64 * BOW_SCORE_U) {
@@ -368,6 +365,13 @@ __global__ __launch_bounds__(256) void bow_score_lds_kernel(const uint32_t* __re
         term[u] = fabs(vi - wi) - fabs(vi) - fabs(wi);
       }
       mask[u] = __ballot(hit);
+      if (VOTE) {  // the stored ids ascend: the first counted hit of the first chunk that has one is the smallest
+        const unsigned long long mc = __ballot(hit && id[u] < n_words);
+        if (mc) {
+          if (shared == 0) first = (uint32_t)__builtin_amdgcn_readlane((int)id[u], __builtin_ctzll(mc));
+          shared += __builtin_popcountll(mc);
+        }
+      }
     }
 #pragma unroll
     for (int u = 0; u < BOW_SCORE_U; u++) {
@@ -381,7 +385,142 @@ __global__ __launch_bounds__(256) void bow_score_lds_kernel(const uint32_t* __re
       }
     }
   }
-  if (lane == 0) scores[cand] = -score / 2.0;
+  if (VOTE) {
+    vote->shared = shared;
+    vote->first = first;
+  }
+  return -score / 2.0;
+}
+
+// the query into LDS: values first (8-byte aligned), then the ids padded to P with the sentinel
+__device__ __forceinline__ void bow_stage_query(const uint32_t* __restrict__ q_ids, const double* __restrict__ q_vals, int q_nnz,
+                                                int P, double* qv, uint32_t* qi) {
+  for (int i = threadIdx.x; i < P; i += 256) qi[i] = i < q_nnz ? q_ids[i] : 0xFFFFFFFFu;
+  for (int i = threadIdx.x; i < q_nnz; i += 256) qv[i] = q_vals[i];
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void bow_score_lds_kernel(const uint32_t* __restrict__ q_ids, const double* __restrict__ q_vals,
+                                                            int q_nnz, int P, const uint32_t* __restrict__ c_ids,
+                                                            const double* __restrict__ c_vals, const int64_t* __restrict__ off,
+                                                            const int32_t* __restrict__ idx, int m, double* __restrict__ scores) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* qv = reinterpret_cast<double*>(smem);                 // [q_nnz] (rounded up to even)
+  uint32_t* qi = reinterpret_cast<uint32_t*>(qv + ((q_nnz + 1) & ~1));  // [P]
+  bow_stage_query(q_ids, q_vals, q_nnz, P, qv, qi);
+  const int cand = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (cand >= m) return;
+  const int lane = threadIdx.x & 63;
+  const int vec = idx ? idx[cand] : cand;
+  const double s = bow_score_wave<false>(qi, qv, P, c_ids, c_vals, off[vec], off[vec + 1], lane, 0u, nullptr);
+  if (lane == 0) scores[cand] = s;
+}
+
+// Place-recognition query (vsl_bowdb_query): the shared-word vote of detect_loop_candidates (loop_closure_utils.h:141-197)
+// and detect_relocalization_candidate (tracking.h:169-199), the 0.8 rule and the L1 scores of the survivors, against
+// EVERY stored vector, with nothing proportional to the store crossing PCIe.
+//   * One kernel for vote and score: the vote of a stored word is the lower-bound search of the query that the score
+//     makes anyway, so counting costs two scalar instructions per chunk on top of bow_score_lds_kernel's pass; a vote-only
+//     pass would save the 8-byte values (2/3 of the bytes) but the survivors would be searched a second time behind a
+//     host round trip for their number.
+//   * Scores for every vector, not only for survivors: the survivors are known only after the maximum over all vectors,
+//     i.e. after this kernel; the ordered sum of the matched terms is short (tens to hundreds of words per vector).
+//   * Wave per vector at every store size (the workgroup-per-candidate form of bow_score_wg_kernel pays off below ~256
+//     candidates of a LIST; a query always walks the whole store, which only grows): one form, one summation routine --
+//     the very code of bow_score_lds_kernel, so the scores are bit-equal to vsl_bowdb_score by construction.
+//   * Excluded vectors (a handful: connected keyframes of weight >= 30) are looked up by the whole wave in the short list
+//     and written as "shares nothing".
+//   * No atomics here: the maximum, the count of sharing vectors and the compaction are one workgroup's job
+//     (bow_query_select_kernel) over the 4-byte shared[] array -- 40 KB at 10,000 keyframes.
+__global__ __launch_bounds__(256) void bow_query_kernel(const uint32_t* __restrict__ q_ids, const double* __restrict__ q_vals,
+                                                        int q_nnz, int P, const uint32_t* __restrict__ c_ids,
+                                                        const double* __restrict__ c_vals, const int64_t* __restrict__ off, int n_vecs,
+                                                        uint32_t n_words, const int32_t* __restrict__ excl, int n_excl,
+                                                        int32_t* __restrict__ shared_out, uint32_t* __restrict__ first_out,
+                                                        double* __restrict__ scores) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* qv = reinterpret_cast<double*>(smem);
+  uint32_t* qi = reinterpret_cast<uint32_t*>(qv + ((q_nnz + 1) & ~1));
+  bow_stage_query(q_ids, q_vals, q_nnz, P, qv, qi);
+  const int vec = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (vec >= n_vecs) return;
+  const int lane = threadIdx.x & 63;
+  bool ex = false;
+  for (int i = lane; i < n_excl; i += 64) ex = ex || excl[i] == vec;
+  BowVote vote = {0, 0xFFFFFFFFu};
+  double s = 0.0;
+  if (!__any(ex)) s = bow_score_wave<true>(qi, qv, P, c_ids, c_vals, off[vec], off[vec + 1], lane, n_words, &vote);
+  if (lane == 0) {
+    shared_out[vec] = vote.shared;
+    first_out[vec] = vote.first;
+    scores[vec] = s;
+  }
+}
+
+// One workgroup: max_count = max(shared - 1) over the sharing vectors, thr = (int)(max_count * keep_fraction) in float
+// (the reference's `(int)(max * 0.8f)`), and the survivors {shared >= 1, shared - 1 > thr} compacted into records.  The
+// slots come from an LDS counter (integer atomics; the host sorts the records by (first word, index) anyway).
+// hdr: max_count, n_sharing, n_survivors (may exceed cap: then only cap records were written), thr.
+struct BowQueryRec {
+  int32_t index, count;
+  uint32_t first, pad;
+  double score;
+};
+__global__ __launch_bounds__(1024) void bow_query_select_kernel(const int32_t* __restrict__ shared_in, const uint32_t* __restrict__ first_in,
+                                                                const double* __restrict__ scores, int n_vecs, float keep_fraction, int cap,
+                                                                int32_t* __restrict__ hdr, BowQueryRec* __restrict__ rec) {
+  __shared__ int wmax[16], wcnt[16];
+  __shared__ int n_out;
+  const int tid = threadIdx.x;
+  int mx = 0, cnt = 0;
+  for (int v = tid; v < n_vecs; v += 1024) {
+    const int s = shared_in[v];
+    if (s >= 1) {
+      mx = max(mx, s - 1);
+      cnt++;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    mx = max(mx, __shfl_xor(mx, d));
+    cnt += __shfl_xor(cnt, d);
+  }
+  if ((tid & 63) == 0) {
+    wmax[tid >> 6] = mx;
+    wcnt[tid >> 6] = cnt;
+  }
+  if (tid == 0) n_out = 0;
+  __syncthreads();
+  mx = 0;
+  cnt = 0;
+#pragma unroll
+  for (int w = 0; w < 16; w++) {
+    mx = max(mx, wmax[w]);
+    cnt += wcnt[w];
+  }
+  const int thr = (int)((float)mx * keep_fraction);
+  for (int v = tid; v < n_vecs; v += 1024) {
+    const int s = shared_in[v];
+    if (s >= 1 && s - 1 > thr) {
+      const int slot = atomicAdd(&n_out, 1);
+      if (slot < cap) {
+        BowQueryRec r;
+        r.index = v;
+        r.count = s - 1;
+        r.first = first_in[v];
+        r.pad = 0;
+        r.score = scores[v];
+        rec[slot] = r;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    hdr[0] = mx;
+    hdr[1] = cnt;
+    hdr[2] = n_out;
+    hdr[3] = thr;
+  }
 }
 
 // K9 for FEW candidates (m <= BOW_WG_MAX_M = 256: loop-closure / relocalisation queries score ~100 keyframes): one WORKGROUP
@@ -992,4 +1131,87 @@ extern "C" int vsl_bowdb_score(vsl_ctx* ctx, const vsl_bowdb* db, const uint32_t
     VSL_HIP(ctx, hipMemcpyAsync(didx, cand_index, 4 * M, hipMemcpyHostToDevice, ctx->stream));
   }
   return bow_score_launch(ctx, q_ids, q_vals, q_nnz, db->ids, db->vals, db->off, didx, m, qs, scores, db->max_nnz);
+}
+
+// The place-recognition query: see bow_query_kernel.  One upload (query + exclusion list), two launches, one download of
+// the header and the first BOW_QUERY_INLINE records; survivors beyond those (rare: the callers see tens) in a second copy.
+#define BOW_QUERY_INLINE 32
+extern "C" int vsl_bowdb_query(vsl_ctx* ctx, const vsl_bowdb* db, const uint32_t* q_ids, const double* q_vals, int q_nnz,
+                               uint32_t n_words, const int32_t* exclude_index, int n_exclude, float keep_fraction, int cap,
+                               int32_t* cand_index, int32_t* cand_count, double* cand_score, int* n_candidates, int* n_sharing,
+                               int* max_count) {
+  if (!ctx || !db || q_nnz < 0 || n_exclude < 0 || cap < 0 || !n_candidates || !n_sharing || !max_count ||
+      (q_nnz > 0 && (!q_ids || !q_vals)) || (n_exclude > 0 && !exclude_index) || (cap > 0 && (!cand_index || !cand_count || !cand_score)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_bowdb_query: bad arguments");
+  *n_candidates = 0;
+  *n_sharing = 0;
+  *max_count = 0;
+  if (q_nnz > BOW_Q_LDS_MAX)
+    return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_bowdb_query: a query of %d words, at most %d are supported", q_nnz, BOW_Q_LDS_MAX);
+  for (int i = 0; i < n_exclude; i++)
+    if (exclude_index[i] < 0 || exclude_index[i] >= db->n_vecs)
+      return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_bowdb_query: excluded vector %d = %d, %d vectors stored", i, exclude_index[i], db->n_vecs);
+  if (db->n_vecs == 0 || q_nnz == 0) return VSL_OK;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t Q = (size_t)q_nnz, N = (size_t)db->n_vecs, E = (size_t)n_exclude, R = (size_t)std::min(cap, db->n_vecs);
+  // device scratch: q_vals (8Q) | scores (8N) | hdr (16) | records (24R) | q_ids (4Q) | shared (4N) | first (4N) | exclusions (4E)
+  void* d = nullptr;
+  int rc = vsl_ctx_dscratch(ctx, 8 * (Q + N) + 16 + sizeof(BowQueryRec) * R + 4 * (Q + 2 * N + E) + 64, &d);
+  if (rc) return rc;
+  double* dqv = (double*)d;
+  double* dsc = dqv + Q;
+  int32_t* dhdr = (int32_t*)(dsc + N);
+  BowQueryRec* drec = (BowQueryRec*)(dhdr + 4);
+  uint32_t* dqi = (uint32_t*)(drec + R);
+  int32_t* dshared = (int32_t*)(dqi + Q);
+  uint32_t* dfirst = (uint32_t*)(dshared + N);
+  int32_t* dex = (int32_t*)(dfirst + N);
+  // pinned: results (16 + 24R) | q_vals (8Q) | q_ids (4Q) | exclusions (4E)
+  const size_t res_bytes = 16 + sizeof(BowQueryRec) * R;
+  void* hp = nullptr;
+  if ((rc = vsl_ctx_hpinned(ctx, res_bytes + 12 * Q + 4 * E + 64, &hp))) return rc;
+  uint8_t* hq = (uint8_t*)hp + res_bytes;
+  memcpy(hq, q_vals, 8 * Q);
+  memcpy(hq + 8 * Q, q_ids, 4 * Q);
+  if (E) memcpy(hq + 12 * Q, exclude_index, 4 * E);
+  VSL_HIP(ctx, hipMemcpyAsync(dqv, hq, 8 * Q, hipMemcpyHostToDevice, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(dqi, hq + 8 * Q, 4 * Q, hipMemcpyHostToDevice, ctx->stream));
+  if (E) VSL_HIP(ctx, hipMemcpyAsync(dex, hq + 12 * Q, 4 * E, hipMemcpyHostToDevice, ctx->stream));
+  {
+    VslStage st(ctx, VSL_STAGE_BOW_SCORE);
+    int P = 1;
+    while (P < q_nnz + 1) P <<= 1;  // at least one 0xFFFFFFFF sentinel behind the query
+    const size_t lds = 8 * (size_t)((q_nnz + 1) & ~1) + 4 * (size_t)P;
+    if (lds > 64 * 1024 && !ctx->bow_query_attr_set) {
+      VSL_HIP(ctx, hipFuncSetAttribute((const void*)bow_query_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
+      ctx->bow_query_attr_set = true;
+    }
+    hipLaunchKernelGGL(bow_query_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), lds, ctx->stream, dqi, dqv, q_nnz, P, db->ids, db->vals,
+                       db->off, db->n_vecs, n_words, dex, n_exclude, dshared, dfirst, dsc);
+    hipLaunchKernelGGL(bow_query_select_kernel, dim3(1), dim3(1024), 0, ctx->stream, dshared, dfirst, dsc, db->n_vecs, keep_fraction, (int)R,
+                       dhdr, drec);
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  const size_t inl = std::min<size_t>(R, BOW_QUERY_INLINE);
+  VSL_HIP(ctx, hipMemcpyAsync(hp, dhdr, 16 + sizeof(BowQueryRec) * inl, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int32_t* hh = (const int32_t*)hp;
+  const int n_surv = hh[2];
+  *max_count = hh[0];
+  *n_sharing = hh[1];
+  if (n_surv > cap) return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_bowdb_query: %d candidates, capacity %d", n_surv, cap);
+  BowQueryRec* hr = (BowQueryRec*)((uint8_t*)hp + 16);
+  if ((size_t)n_surv > inl) {
+    VSL_HIP(ctx, hipMemcpyAsync(hr + inl, drec + inl, sizeof(BowQueryRec) * ((size_t)n_surv - inl), hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  // the host walk meets a keyframe at its first shared word, and the keyframes of one word in insertion order
+  std::sort(hr, hr + n_surv, [](const BowQueryRec& x, const BowQueryRec& y) { return x.first != y.first ? x.first < y.first : x.index < y.index; });
+  for (int i = 0; i < n_surv; i++) {
+    cand_index[i] = hr[i].index;
+    cand_count[i] = hr[i].count;
+    cand_score[i] = hr[i].score;
+  }
+  *n_candidates = n_surv;
+  return VSL_OK;
 }

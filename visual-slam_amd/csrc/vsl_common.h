@@ -75,6 +75,7 @@ struct vsl_ctx {
   size_t ba_pin_cap = 0;    // bytes
   bool select_attr_set = false;
   bool bow_score_attr_set = false;  // per context, hence per device: hipFuncSetAttribute is a per-device setting
+  bool bow_query_attr_set = false;  // the same for the place-recognition query kernel
   double* status_word = nullptr;    // 64 device bytes allocated with the context: the flag of status exchanges between ranks (never null in a live context)
   double tie_eps = 1e-12;  // rBRIEF near-tie guard band (describe.hip)
   bool match_use_i8 = false;            // diagnostic: int8 matrix-core matcher even where the FP4 one applies (<= 2048 features)
