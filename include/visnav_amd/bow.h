@@ -77,13 +77,19 @@ class ORBVocabularyAmd {
     v.clear();
     fv.clear();
     if (!voc_) return;
-    const int cap = 2 * num_features + 512;
+    int cap = 2 * num_features + 512;
     std::vector<uint32_t> ids(cap), fn(cap), ff(cap);
     std::vector<double> vals(cap);
     int nnz = 0, fvn = 0;
-    amd::check(vsl_compute_bow_vector(amd::ctx(), voc_, img_raw.ptr, (int)img_raw.w, (int)img_raw.h, img_raw.pitch, num_features,
-                                      levelsup, cap, ids.data(), vals.data(), &nnz, fn.data(), ff.data(), &fvn),
-               "compute_bow_vector");
+    int rc = vsl_compute_bow_vector(amd::ctx(), voc_, img_raw.ptr, (int)img_raw.w, (int)img_raw.h, img_raw.pitch, num_features,
+                                    levelsup, cap, ids.data(), vals.data(), &nnz, fn.data(), ff.data(), &fvn);
+    if (rc == VSL_ERR_CAPACITY && fvn > cap) {  // retainBest keeps every tie: once more with the reported feature count
+      cap = fvn;
+      ids.resize(cap), fn.resize(cap), ff.resize(cap), vals.resize(cap);
+      rc = vsl_compute_bow_vector(amd::ctx(), voc_, img_raw.ptr, (int)img_raw.w, (int)img_raw.h, img_raw.pitch, num_features,
+                                  levelsup, cap, ids.data(), vals.data(), &nnz, fn.data(), ff.data(), &fvn);
+    }
+    amd::check(rc, "compute_bow_vector");
     for (int i = 0; i < nnz; i++) v.emplace_hint(v.end(), ids[i], vals[i]);
     for (int i = 0; i < fvn; i++) fv[fn[i]].push_back(ff[i]);
   }

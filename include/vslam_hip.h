@@ -533,11 +533,25 @@ int vsl_bow_transform(vsl_ctx* ctx, const vsl_voc* voc, const uint8_t* desc32, i
  * cv::ORB::create(num_features, 1.2, 8, 19, 0, 2, cv::ORB::FAST_SCORE)->detectAndCompute).  cv::ORB is upstream
  * OpenCV: parity with its binary is unpinned; the arithmetic conventions are those written down in
  * oracle/orc_orb.cpp, against which this is bit-exact.  kp5: (x, y in level-0 pixels, angle in degrees,
- * response, octave) per keypoint, desc32: 32 bytes per keypoint in cv::Mat order; cap >= 2 * num_features + 512
- * is always enough (retainBest keeps every keypoint tied with the last one of a level). */
+ * response, octave) per keypoint, desc32: 32 bytes per keypoint in cv::Mat order.
+ * Capacity: retainBest keeps EVERY keypoint tied with the last one of a level, so no function of num_features
+ * bounds the result (a rendered image of saturated dots returns several times num_features); cap = 2 * num_features
+ * + 512 is a good first guess for camera images.  *n_out is always the number of keypoints found.  When it exceeds
+ * cap the call returns VSL_ERR_CAPACITY after filling the first cap entries (cap = 0 with null buffers is a count
+ * query); calling again with cap >= *n_out succeeds. */
 int vsl_orb_detect_describe(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int num_features, int cap,
                             float* kp5, uint8_t* desc32, int* n_out);
-/* compute_bow_vector: that front end followed by vsl_bow_transform (outputs as there, capacity cap). */
+/* Test and diagnostic entries (like vsl_min_eig_response).  vsl_orb_level_sizes: the widths and heights of the 8
+ * pyramid levels of a w x h image.  vsl_orb_stage_images: runs the launches of vsl_orb_detect_describe and copies
+ * out the intermediate images of one level, each a nullable host buffer of level_w[level] * level_h[level] bytes
+ * (dense rows): the pyramid level, the FAST score image, the flags of the strict 3x3 maxima inside the 19-pixel
+ * border (before retainBest), and the 7x7-blurred level the descriptors sample. */
+int vsl_orb_level_sizes(int w, int h, int* level_w, int* level_h);
+int vsl_orb_stage_images(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int level, uint8_t* pyr,
+                         uint8_t* score, uint8_t* nms_flag, uint8_t* blurred);
+/* compute_bow_vector: that front end followed by vsl_bow_transform (outputs as there, capacity cap).  The front
+ * end's capacity is handled inside; when the image has more features than cap the call returns VSL_ERR_CAPACITY
+ * with *nnz = *fv_n = the number of features, the capacity that suffices. */
 int vsl_compute_bow_vector(vsl_ctx* ctx, const vsl_voc* voc, const uint8_t* img, int w, int h, size_t pitch,
                            int num_features, int levelsup, int cap, uint32_t* word_ids, double* word_vals, int* nnz,
                            uint32_t* fv_node, uint32_t* fv_feat, int* fv_n);

@@ -198,10 +198,20 @@ int vsl_bow_transform(vsl_ctx*, const vsl_voc* voc, const uint8_t* desc32, int n
 }
 int vsl_compute_bow_vector(vsl_ctx* c, const vsl_voc* voc, const uint8_t* img, int w, int h, size_t pitch, int num_features, int levelsup,
                            int cap, uint32_t* word_ids, double* word_vals, int* nnz, uint32_t* fv_node, uint32_t* fv_feat, int* fv_n) {
-  std::vector<float> kp(5 * (size_t)cap);
-  std::vector<uint8_t> desc(32 * (size_t)cap);
-  const int n = orc_orb_detect_describe(img, w, h, pitch, num_features, kp.data(), desc.data(), cap);
-  if (n < 0 || n > cap) return fail(c, VSL_ERR_CAPACITY, "ORB capacity");
+  // the oracle stops at its buffer's end without saying how many there were: grow until the result does not fill it
+  std::vector<float> kp;
+  std::vector<uint8_t> desc;
+  int n = 0;
+  for (size_t kcap = 2 * (size_t)num_features + 512;; kcap *= 4) {
+    kp.resize(5 * kcap);
+    desc.resize(32 * kcap);
+    n = orc_orb_detect_describe(img, w, h, pitch, num_features, kp.data(), desc.data(), (int)kcap);
+    if (n < (int)kcap) break;
+  }
+  if (n > cap) {
+    *nnz = *fv_n = n;
+    return fail(c, VSL_ERR_CAPACITY, "ORB capacity");
+  }
   orc_bow_transform(voc->v, desc.data(), n, levelsup, word_ids, word_vals, nnz, fv_node, fv_feat, fv_n);
   return VSL_OK;
 }

@@ -204,13 +204,18 @@ def orb_fast_atan2(y, x):
 
 
 def orb_detect_describe(img, nfeatures=1500):
+    """Every keypoint of the image: retainBest keeps all ties beyond the quota, so the buffer grows until the
+    result no longer fills it (the C entry point stops silently at its capacity)."""
     img = np.ascontiguousarray(img, np.uint8)
-    cap = 2 * nfeatures + 64   # retainBest keeps ties beyond the quota
-    kp = np.zeros((cap, 5), np.float32)
-    desc = np.zeros((cap, 32), np.uint8)
-    n = lib().orc_orb_detect_describe(img.ctypes.data_as(u8p), img.shape[1], img.shape[0], C.c_size_t(img.strides[0]),
-                                      int(nfeatures), kp.ctypes.data_as(f32p), desc.ctypes.data_as(u8p), cap)
-    return kp[:n].copy(), desc[:n].copy()
+    cap = 2 * nfeatures + 64
+    while True:
+        kp = np.zeros((cap, 5), np.float32)
+        desc = np.zeros((cap, 32), np.uint8)
+        n = lib().orc_orb_detect_describe(img.ctypes.data_as(u8p), img.shape[1], img.shape[0], C.c_size_t(img.strides[0]),
+                                          int(nfeatures), kp.ctypes.data_as(f32p), desc.ctypes.data_as(u8p), cap)
+        if n < cap:
+            return kp[:n].copy(), desc[:n].copy()
+        cap *= 4
 
 
 def project_landmarks(pose7, model, intr8, width, height, points, cam_z_threshold=0.1):

@@ -52,3 +52,233 @@ def test_compute_bow_vector_equals_front_end_plus_transform(ctx, orc, vsl, synth
     for g, e in zip(got, exp):
         assert np.array_equal(g, e)
     assert abs(got[1].sum() - 1.0) < 1e-12   # L1-normalised BowVector
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Adversarial images (tests/orb_ref.py).  Every test first asserts FROM THE ORACLE'S OUTPUT ALONE that its image does
+# exercise what it is for, then compares keypoints (as uint32) and descriptors bit for bit with the oracle; the tests
+# marked (S) also compare the stage images of levels 0, 1, 4 and 7 with the numpy restatement (orb_ref.stages), which
+# tests/test_orb_ref_cpu.py pins to the oracle.
+import ctypes as C  # noqa: E402
+
+import orb_ref as R  # noqa: E402
+
+STAGE_LEVELS = (0, 1, 4, 7)
+STAGE_NAMES = ("pyramid", "score", "nms_flag", "blurred")
+
+
+def _same_as_oracle(ctx, orc, img, nf):
+    kp, desc = ctx.orb_detect_describe(img, nf)
+    okp, odesc = orc.orb_detect_describe(img, nf)
+    assert kp.shape == okp.shape, (kp.shape, okp.shape)
+    assert np.array_equal(kp.view(np.uint32), okp.view(np.uint32))
+    assert np.array_equal(desc, odesc)
+    return okp, odesc
+
+
+def _stages_equal_ref(ctx, img):
+    ref = R.stages(np.ascontiguousarray(img))
+    for l in STAGE_LEVELS:
+        got = ctx.orb_stage_images(img, l)
+        for name, g, e in zip(STAGE_NAMES, got, ref[l]):
+            assert g.shape == e.shape, (name, l, g.shape, e.shape)
+            bad = np.argwhere(g != e)
+            assert len(bad) == 0, "%s of level %d differs at %d pixels, first (y, x) = %s" % (name, l, len(bad), bad[0])
+
+
+def _level_xy(okp, level=0):
+    """Integer (x, y) of the oracle's keypoints of one level."""
+    k = okp[okp[:, 4] == level]
+    s = R.level_scales()[level]
+    return {(int(np.rint(x / s)), int(np.rint(y / s))) for x, y in k[:, :2]}
+
+
+@pytest.mark.parametrize("w,h,step,nf", R.DOT_GRIDS)
+def test_orb_tie_overflow_returns_every_tied_keypoint(ctx, orc, w, h, step, nf):
+    img = R.dot_grid(w, h, step)
+    okp, _ = orc.orb_detect_describe(img, nf)
+    n0 = int((okp[:, 4] == 0).sum())
+    assert n0 > 2 * orc.orb_level_quota(nf)[0] + 64       # more ties than the first pass's level-0 segment holds
+    assert np.all(okp[okp[:, 4] == 0, 3] == 254)
+    kp, _ = ctx.orb_detect_describe(img, nf)
+    print("tie overflow %dx%d nf=%d: device %d keypoints, oracle %d (level 0: %d)" % (w, h, nf, len(kp), len(okp), n0))
+    _same_as_oracle(ctx, orc, img, nf)
+
+
+def test_compute_bow_vector_on_the_dot_grid(ctx, orc, vsl, synth, tmp_path):
+    path = tmp_path / "voc.txt"
+    path.write_text(synth.vocabulary_text(5, 10, 3))
+    voc, ovoc = vsl.Vocabulary(ctx, str(path)), orc.Vocabulary(str(path))
+    for w, h, step, nf in (R.DOT_GRIDS[0], (640, 480, 8, 100)):   # 619 features; 4318, beyond every first-guess buffer
+        img = R.dot_grid(w, h, step)
+        okp, odesc = orc.orb_detect_describe(img, nf)
+        assert int((okp[:, 4] == 0).sum()) > 2 * orc.orb_level_quota(nf)[0] + 64   # level 0 overflows its segment
+        if w == 640:   # ... and the total exceeds both first-guess buffers (the library's and the wrapper's)
+            assert len(odesc) > 2 * nf + 64 * 8 and len(odesc) > 2 * nf + 512
+        for g, e in zip(voc.compute_bow_vector(img, nf, 4), ovoc.transform(odesc, 4)):
+            assert np.array_equal(g, e)
+
+
+@pytest.mark.parametrize("dq", [0, -1, 5])
+def test_orb_quota_edges_at_level0(ctx, orc, dq):
+    img = R.graded_dots(R.GRADED_Q)
+    nf = R.nf_for_level0_quota(R.GRADED_Q + dq)
+    assert orc.orb_level_quota(nf)[0] == R.GRADED_Q + dq
+    allkp, _ = orc.orb_detect_describe(img, 50000)        # no cut anywhere: the candidates themselves
+    s0 = allkp[allkp[:, 4] == 0, 3]
+    assert len(s0) == R.GRADED_Q and len(set(s0.tolist())) == R.GRADED_Q   # exactly q strict maxima of distinct scores
+    okp, _ = _same_as_oracle(ctx, orc, img, nf)
+    assert int((okp[:, 4] == 0).sum()) == min(R.GRADED_Q, R.GRADED_Q + dq)
+
+
+@pytest.mark.parametrize("nf", [1, 2, 4, 5, 8])
+def test_orb_zero_quotas(ctx, orc, nf):
+    quota = orc.orb_level_quota(nf)
+    assert np.any(quota == 0)
+    okp, _ = _same_as_oracle(ctx, orc, R.blocky_noise(200, 160, 360), nf)
+    assert len(okp) > 0 and not np.any(np.isin(okp[:, 4].astype(int), np.nonzero(quota == 0)[0]))
+
+
+def test_orb_quota_above_the_candidates_on_every_level(ctx, orc):
+    okp, _ = _same_as_oracle(ctx, orc, R.blocky_noise(100, 81, 181), 50000)
+    per_level = np.bincount(okp[:, 4].astype(int), minlength=8)
+    assert len(okp) > 0 and np.all(per_level < orc.orb_level_quota(50000))
+
+
+def test_orb_fast_edges(ctx, orc):   # (S)
+    img, placed = R.fast_edges()
+    W, H = R.FAST_W, R.FAST_H
+    for x, y, exp in placed:
+        assert orc.orb_fast_score(img, x, y) == exp, (x, y, exp)
+    names = list(R.RINGS)
+    got = {n: orc.orb_fast_score(img, 24 + 16 * (i % 4), 24 + 16 * (i // 4)) for i, n in enumerate(names)}
+    assert got["arc9"] == 59 and got["arc8"] == 0 and got["contrast20"] == 0 and got["contrast21"] == 20
+    assert got["darker9"] > 0 and got["wrap"] == 44 and got["center0"] > 0 and got["center255"] > 0
+    # the apron and the x < W - 3 rule: scored at 3 and W - 4, not at 2 and W - 3
+    assert orc.orb_fast_score(img, 3, 30) > 0 and orc.orb_fast_score(img, W - 4, 30) > 0 and orc.orb_fast_score(img, 90, 3) > 0
+    assert orc.orb_fast_score(img, W - 3, 46) == 0 and orc.orb_fast_score(img, 2, 62) == 0 and orc.orb_fast_score(img, 106, H - 3) == 0
+    okp, _ = _same_as_oracle(ctx, orc, img, 500)
+    xy0 = _level_xy(okp)
+    # the border filter keeps 19 and W - 20 and drops 18 and W - 19, in x and in y
+    assert {(19, 60), (W - 20, 60), (48, 19), (64, H - 20)} <= xy0
+    assert not {(18, 72), (W - 19, 72), (32, 18), (90, H - 19)} & xy0
+    # corners on both sides of the tile seams are found
+    assert {(31, 60), (32, 70), (47, 60), (48, 70), (63, 58), (64, 68), (100, 31), (88, 32), (100, 47), (88, 48), (79, 63),
+            (80, 73)} <= xy0
+    _stages_equal_ref(ctx, img)
+
+
+def test_orb_nms_ties(ctx, orc):   # (S)
+    img, groups = R.nms_ties()
+    okp, _ = _same_as_oracle(ctx, orc, img, 500)
+    xy0 = _level_xy(okp)
+    for name in ("pair", "block", "diagonal"):
+        scores = {orc.orb_fast_score(img, x, y) for x, y in groups[name]}
+        assert scores == {254}, name                         # equal maximal scores, so it is the strict comparison ...
+        assert not set(groups[name]) & xy0, name             # ... that keeps none of them
+    assert set(groups["control"]) <= xy0
+    _stages_equal_ref(ctx, img)
+
+
+@pytest.mark.parametrize("w,h", R.EXTREME_SIZES)
+def test_orb_resize_and_blur_extremes(ctx, orc, w, h):   # (S)
+    from fractions import Fraction
+    lw, lh, _ = orc.orb_level_sizes(w, h)
+    exact = [round(Fraction(w) / Fraction(6, 5) ** l) for l in range(8)]
+    assert [int(v) for v in lw] != exact                     # fp32 division + lrintf and exact arithmetic disagree
+    for name, img in R.extreme_images(w, h).items():
+        _same_as_oracle(ctx, orc, img, 500)
+        _stages_equal_ref(ctx, img)
+
+
+def test_orb_angle_of_symmetric_dots(ctx, orc):
+    img, centres = R.angle_dots()
+    okp, _ = _same_as_oracle(ctx, orc, img, 500)
+    s = R.level_scales()
+    at = {(int(np.rint(k[0])), int(np.rint(k[1]))): k[2] for k in okp if k[4] == 0}
+    assert at[centres["isolated"]] == 0.0 and np.signbit(at[centres["isolated"]]) == False   # noqa: E712  (0 / (0 + eps))
+    assert at[centres[(6, 0)]] == 0.0 and at[centres[(0, 6)]] == 90.0
+    assert at[centres[(-6, 0)]] == 180.0 and at[centres[(0, -6)]] == 270.0
+    for d, lo in (((6, 6), 0), ((-6, 6), 90), ((-6, -6), 180), ((6, -6), 270)):
+        assert abs(at[centres[d]] - (lo + 45)) < 0.3
+    assert s[0] == 1.0
+
+
+def test_orb_one_sided_patch_above_level0(ctx, orc):
+    okp, _ = _same_as_oracle(ctx, orc, R.one_sided_patch(), 500)
+    up = okp[okp[:, 4] > 0]
+    assert len(up) >= 4 and len(set(up[:, 4].tolist())) >= 2
+    # the centroid lies towards the rectangle: every quadrant of directions occurs among the corners
+    assert len({int(a // 90) for a in up[:, 2]}) == 4
+
+
+@pytest.mark.parametrize("w,h,pitch,seed", [(333, 251, 400, 584), (640, 480, 641, 1120)])
+def test_orb_pitch(ctx, orc, w, h, pitch, seed):
+    buf = np.random.default_rng(seed + 1).integers(0, 256, (h + 2, pitch), dtype=np.uint8)   # other content beside the view
+    view = buf[1:h + 1, pitch - w:]
+    view[...] = R.blocky_noise(w, h, seed)
+    assert view.strides == (pitch, 1) and not view.flags["C_CONTIGUOUS"]
+    okp, _ = _same_as_oracle(ctx, orc, view, 1000)          # the oracle wrapper compares against a dense copy
+    assert len(okp) >= 500
+    for l in (0, 1):
+        for g, e in zip(ctx.orb_stage_images(view, l), R.stages(np.ascontiguousarray(view))[l]):
+            assert np.array_equal(g, e)
+
+
+def test_orb_scan_second_trip(ctx, orc):
+    img = R.blocky_noise(R.BIG_W, R.BIG_H, 2124)
+    assert R.BIG_W * R.BIG_H > 1024 * 1024
+    okp, _ = _same_as_oracle(ctx, orc, img, 20000)
+    k0 = okp[okp[:, 4] == 0]
+    assert np.any(k0[:, 1] >= 0.97 * R.BIG_H)                                   # keypoints in the last 3 % of the rows
+    assert np.any(k0[:, 1].astype(np.int64) * R.BIG_W + k0[:, 0].astype(np.int64) >= 1024 * 1024)   # ... in chunks >= 1024
+
+
+def _abi_orb(ctx, img, nf, cap):
+    img = np.ascontiguousarray(img)
+    kp = np.full((max(cap, 1), 5), -1, np.float32)
+    desc = np.full((max(cap, 1), 32), 0xAB, np.uint8)
+    n = C.c_int32(-7)
+    rc = ctx.L.vsl_orb_detect_describe(ctx.h, img.ctypes.data_as(C.POINTER(C.c_uint8)), img.shape[1], img.shape[0],
+                                       C.c_size_t(img.strides[0]), nf, cap,
+                                       kp.ctypes.data_as(C.POINTER(C.c_float)) if cap else None,
+                                       desc.ctypes.data_as(C.POINTER(C.c_uint8)) if cap else None, C.byref(n))
+    return rc, n.value, kp, desc
+
+
+def test_orb_capacity_contract(ctx, orc):
+    for img, nf in ((R.blocky_noise(333, 251, 584), 1000), (R.dot_grid(256, 192, 8), 100)):
+        okp, odesc = orc.orb_detect_describe(img, nf)
+        total = len(okp)
+        assert total > 300
+        for cap in (total - 1, 100, 1):
+            rc, n, kp, desc = _abi_orb(ctx, img, nf, cap)
+            assert rc == -4 and n == total                    # VSL_ERR_CAPACITY, *n_out = the capacity that suffices
+            assert np.array_equal(kp[:cap].view(np.uint32), okp[:cap].view(np.uint32)) and np.array_equal(desc[:cap], odesc[:cap])
+        rc, n, _, _ = _abi_orb(ctx, img, nf, 0)               # count query: null buffers
+        assert rc == -4 and n == total
+        rc, n, kp, desc = _abi_orb(ctx, img, nf, total)
+        assert rc == 0 and n == total and np.array_equal(kp.view(np.uint32), okp.view(np.uint32)) and np.array_equal(desc, odesc)
+    rc, n, _, _ = _abi_orb(ctx, np.full((100, 100), 7, np.uint8), 100, 0)
+    assert rc == 0 and n == 0                                 # nothing found: cap = 0 suffices
+
+
+def test_orb_context_reuse(ctx, orc, vsl):
+    seq = [(R.blocky_noise(1280, 720, 2000), 4000), (R.blocky_noise(64, 64, 128), 8), (R.dot_grid(256, 192, 8), 100),
+           (R.blocky_noise(752, 480, 1232), 1500)]
+    one = vsl.Context(0)
+    try:
+        for img, nf in seq:
+            a = one.orb_detect_describe(img, nf)
+            b = one.orb_detect_describe(img, nf)              # two consecutive identical calls
+            fresh = vsl.Context(0)
+            try:
+                c = fresh.orb_detect_describe(img, nf)
+            finally:
+                fresh.close()
+            okp, odesc = orc.orb_detect_describe(img, nf)
+            assert len(okp) > 0
+            for kp, desc in (a, b, c):
+                assert np.array_equal(kp.view(np.uint32), okp.view(np.uint32)) and np.array_equal(desc, odesc)
+    finally:
+        one.close()

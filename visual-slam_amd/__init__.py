@@ -103,6 +103,14 @@ def _img(img):
     return img, img.ctypes.data_as(u8p), img.shape[1], img.shape[0], C.c_size_t(img.strides[0])
 
 
+def _img_rows(img):
+    """Like _img, but a uint8 view with contiguous rows (a region of a wider buffer) is passed as it is, with its pitch."""
+    if isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.ndim == 2 and img.strides[1] == 1 and \
+            img.strides[0] >= img.shape[1]:
+        return img, img.ctypes.data_as(u8p), img.shape[1], img.shape[0], C.c_size_t(img.strides[0])
+    return _img(img)
+
+
 def _mat9(M):
     return None if M is None else np.ascontiguousarray(np.asarray(M, np.float64).reshape(9))
 
@@ -328,15 +336,37 @@ class Context:
         return pairs[:m.value].copy()
 
     def orb_detect_describe(self, img, num_features=1500):
-        """ORB front end of compute_bow_vector: (kp[n, 5] = x, y, angle_deg, response, octave; desc[n, 32])."""
-        img, p, w, h, pitch = _img(img)
+        """ORB front end of compute_bow_vector: (kp[n, 5] = x, y, angle_deg, response, octave; desc[n, 32]).
+        Every keypoint is returned: retainBest keeps all ties, so when the first buffer (2 * num_features + 512) is too
+        small the call is repeated once with the total that vsl_orb_detect_describe reports."""
+        img, p, w, h, pitch = _img_rows(img)
         cap = 2 * num_features + 512
-        kp = np.zeros((cap, 5), np.float32)
-        desc = np.zeros((cap, 32), np.uint8)
-        n = C.c_int32()
-        self._ck(self.L.vsl_orb_detect_describe(self.h, p, w, h, pitch, int(num_features), cap,
-                                                kp.ctypes.data_as(C.POINTER(C.c_float)), desc.ctypes.data_as(u8p), C.byref(n)))
+        for _ in range(2):
+            kp = np.zeros((max(cap, 1), 5), np.float32)
+            desc = np.zeros((max(cap, 1), 32), np.uint8)
+            n = C.c_int32()
+            rc = self.L.vsl_orb_detect_describe(self.h, p, w, h, pitch, int(num_features), cap,
+                                                kp.ctypes.data_as(C.POINTER(C.c_float)), desc.ctypes.data_as(u8p), C.byref(n))
+            if rc != -4 or n.value <= cap:   # VSL_ERR_CAPACITY: n = the capacity that suffices
+                break
+            cap = n.value
+        self._ck(rc)
         return kp[:n.value].copy(), desc[:n.value].copy()
+
+    def orb_level_sizes(self, w, h):
+        """(widths[8], heights[8]) of the ORB pyramid of a w x h image."""
+        lw, lh = np.zeros(8, np.int32), np.zeros(8, np.int32)
+        self._ck(self.L.vsl_orb_level_sizes(int(w), int(h), lw.ctypes.data_as(i32p), lh.ctypes.data_as(i32p)))
+        return lw, lh
+
+    def orb_stage_images(self, img, level):
+        """Test / diagnostic: (pyramid level, FAST score image, NMS + border flags, blurred level) of one pyramid level,
+        uint8 [H_level, W_level] each, after the same launches as orb_detect_describe."""
+        img, p, w, h, pitch = _img_rows(img)
+        lw, lh = self.orb_level_sizes(w, h)
+        out = [np.zeros((lh[level], lw[level]), np.uint8) for _ in range(4)]
+        self._ck(self.L.vsl_orb_stage_images(self.h, p, w, h, pitch, int(level), *[o.ctypes.data_as(u8p) for o in out]))
+        return tuple(out)
 
     # ---- bundle adjustment
     def _ba_struct(self, arr):
@@ -565,17 +595,23 @@ class Vocabulary:
                 ff[:fvn.value].copy())
 
     def compute_bow_vector(self, img, num_features=1500, levelsup=4):
-        """compute_bow_vector (keypoints.h:243-254): ORB front end + transform, one call."""
-        img, p, w, h, pitch = _img(img)
+        """compute_bow_vector (keypoints.h:243-254): ORB front end + transform, one call.  An image with more features
+        than the first buffers hold (ties are unbounded) is done once more with the count the call reports."""
+        img, p, w, h, pitch = _img_rows(img)
         cap = 2 * num_features + 512
-        ids = np.zeros(cap, np.uint32)
-        vals = np.zeros(cap, np.float64)
-        fn = np.zeros(cap, np.uint32)
-        ff = np.zeros(cap, np.uint32)
-        nnz, fvn = C.c_int32(), C.c_int32()
-        self.ctx._ck(self.ctx.L.vsl_compute_bow_vector(self.ctx.h, self.h, p, w, h, pitch, int(num_features), int(levelsup), cap,
-                                                       ids.ctypes.data_as(u32p), vals.ctypes.data_as(f64p), C.byref(nnz),
-                                                       fn.ctypes.data_as(u32p), ff.ctypes.data_as(u32p), C.byref(fvn)))
+        for _ in range(2):
+            ids = np.zeros(cap, np.uint32)
+            vals = np.zeros(cap, np.float64)
+            fn = np.zeros(cap, np.uint32)
+            ff = np.zeros(cap, np.uint32)
+            nnz, fvn = C.c_int32(), C.c_int32()
+            rc = self.ctx.L.vsl_compute_bow_vector(self.ctx.h, self.h, p, w, h, pitch, int(num_features), int(levelsup), cap,
+                                                   ids.ctypes.data_as(u32p), vals.ctypes.data_as(f64p), C.byref(nnz),
+                                                   fn.ctypes.data_as(u32p), ff.ctypes.data_as(u32p), C.byref(fvn))
+            if rc != -4 or fvn.value <= cap:   # VSL_ERR_CAPACITY: fvn = the capacity that suffices
+                break
+            cap = fvn.value
+        self.ctx._ck(rc)
         return (ids[:nnz.value].copy(), vals[:nnz.value].copy(), fn[:fvn.value].copy(), ff[:fvn.value].copy())
 
     def close(self):

@@ -208,9 +208,12 @@ __global__ __launch_bounds__(1024) void orb_compact_kernel(OrbLevels L, const ui
   }
 }
 
-// exclusive scan of the chunk counts within each level (one workgroup, levels one after the other)
+// exclusive scan of the chunk counts within each level (one workgroup, levels one after the other).
+// level_full = the keypoints of the level, level_count = those that fit its segment: the host redoes the emit
+// with exact segments when the two differ (retainBest keeps ties without limit).
 __global__ __launch_bounds__(1024) void orb_scan_kernel(OrbLevels L, const int32_t* __restrict__ chunk_count,
-                                                        int32_t* __restrict__ chunk_offset, int32_t* __restrict__ level_count) {
+                                                        int32_t* __restrict__ chunk_offset, int32_t* __restrict__ level_count,
+                                                        int32_t* __restrict__ level_full) {
   __shared__ int wave_tot[16];
   __shared__ int base_s;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -241,7 +244,10 @@ __global__ __launch_bounds__(1024) void orb_scan_kernel(OrbLevels L, const int32
       }
       __syncthreads();
     }
-    if (threadIdx.x == 0) level_count[l] = min(base_s, L.seg_cap[l]);
+    if (threadIdx.x == 0) {
+      level_full[l] = base_s;
+      level_count[l] = min(base_s, L.seg_cap[l]);
+    }
     __syncthreads();
   }
 }
@@ -375,118 +381,213 @@ int orb_upload_tables(vsl_ctx* ctx) {
   return VSL_OK;
 }
 
-}  // namespace
+// keypoint-shaped device arrays: n_slots entries each, carved from one allocation
+struct OrbKpBuf {
+  int32_t* xy;
+  int32_t* sl;
+  float* angle;
+  float* cs;
+  uint8_t* desc;
+};
+constexpr size_t kOrbKpBytesPerSlot = 8 + 4 + 4 + 8 + 32;
 
-// kp5: (x, y in level-0 pixels, angle in degrees, response, octave) per keypoint; desc32: 32 bytes each.
-extern "C" int vsl_orb_detect_describe(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int nfeatures, int cap,
-                                       float* kp5, uint8_t* desc32, int* n_out) {
-  if (!ctx || !img || !n_out || w < 64 || h < 64 || pitch < (size_t)w || nfeatures < 1 || cap < 0 || (cap > 0 && (!kp5 || !desc32)))
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_orb_detect_describe: bad arguments (w, h >= 64 required)");
-  *n_out = 0;
+OrbKpBuf orb_carve_kp(void* base, int n_slots) {
+  OrbKpBuf k;
+  k.xy = (int32_t*)base;
+  k.sl = k.xy + 2 * (size_t)n_slots;
+  k.angle = (float*)(k.sl + n_slots);
+  k.cs = k.angle + n_slots;
+  k.desc = (uint8_t*)(k.cs + 2 * (size_t)n_slots);
+  return k;
+}
+
+// seg_base / n_slots from seg_cap
+int orb_place_segments(OrbLevels& L) {
+  int n_slots = 0;
+  for (int l = 0; l < ORB_LEVELS; l++) {
+    L.seg_base[l] = n_slots;
+    n_slots += L.seg_cap[l];
+  }
+  return n_slots;
+}
+
+// everything one image's stages leave on the device
+struct OrbPlan {
+  OrbLevels L;
+  size_t total_pix;
+  int n_slots, n_chunks;
+  uint8_t *pyr, *score, *flag, *blurred;
+  float* tmp;
+  int* hist;
+  int32_t *level_count, *level_full, *cuts, *chunk_count, *chunk_offset;
+  OrbKpBuf kp;
+};
+
+void orb_plan_levels(int w, int h, int nfeatures, OrbPlan& P) {
+  OrbLevels& L = P.L;
+  P.total_pix = 0;
+  const float factor = (float)(1.0 / 1.2f);
+  float ndesired = (float)(nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)ORB_LEVELS)));
+  int sum = 0;
+  for (int l = 0; l < ORB_LEVELS; l++) {
+    const float s = (float)std::pow((double)1.2f, (double)l);
+    L.scale[l] = s;
+    L.W[l] = (int)std::lrintf((float)w / s);
+    L.H[l] = (int)std::lrintf((float)h / s);
+    if (l < ORB_LEVELS - 1) {
+      L.quota[l] = (int)std::lrintf(ndesired);
+      sum += L.quota[l];
+      ndesired *= factor;
+    } else {
+      L.quota[l] = nfeatures - sum > 0 ? nfeatures - sum : 0;
+    }
+    L.pix_off[l] = P.total_pix;
+    P.total_pix += (size_t)L.W[l] * L.H[l];
+    P.total_pix = (P.total_pix + 255) & ~(size_t)255;
+    L.seg_cap[l] = 2 * L.quota[l] + 64;  // enough unless more than quota + 64 keypoints tie with the last one kept
+  }
+  P.n_slots = orb_place_segments(L);
+  L.chunk_base[0] = 0;
+  for (int l = 0; l < ORB_LEVELS; l++) L.chunk_base[l + 1] = L.chunk_base[l] + (L.W[l] * L.H[l] + 1023) / 1024;
+  P.n_chunks = L.chunk_base[ORB_LEVELS];
+}
+
+void orb_launch_emit_angle(hipStream_t st, const OrbPlan& P, const OrbLevels& L, int n_slots, const OrbKpBuf& kp,
+                           const int32_t* level_count) {
+  hipLaunchKernelGGL(orb_compact_kernel<true>, dim3(P.n_chunks), dim3(1024), 0, st, L, (const uint8_t*)P.score, (const uint8_t*)P.flag,
+                     (const int32_t*)P.cuts, P.chunk_count, (const int32_t*)P.chunk_offset, kp.xy, kp.sl);
+  hipLaunchKernelGGL(orb_angle_kernel, dim3((n_slots + 3) / 4), dim3(256), 0, st, L, (const uint8_t*)P.pyr, (const int32_t*)kp.xy,
+                     (const int32_t*)kp.sl, level_count, n_slots, kp.angle);
+}
+
+// The launch sequence of the front end up to the keypoint angles, shared by vsl_orb_detect_describe and the
+// stage export: upload, pyramid, FAST score, NMS + histogram, blur, cut / count / scan / emit, angle.
+int orb_launch_stages(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int nfeatures, OrbPlan& P) {
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   int rc = orb_upload_tables(ctx);
   if (rc) return rc;
-  OrbLevels L;
-  size_t total_pix = 0;
-  int n_slots = 0;
-  {
-    const float factor = (float)(1.0 / 1.2f);
-    float ndesired = (float)(nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)ORB_LEVELS)));
-    int sum = 0;
-    for (int l = 0; l < ORB_LEVELS; l++) {
-      const float s = (float)std::pow((double)1.2f, (double)l);
-      L.scale[l] = s;
-      L.W[l] = (int)std::lrintf((float)w / s);
-      L.H[l] = (int)std::lrintf((float)h / s);
-      if (l < ORB_LEVELS - 1) {
-        L.quota[l] = (int)std::lrintf(ndesired);
-        sum += L.quota[l];
-        ndesired *= factor;
-      } else {
-        L.quota[l] = nfeatures - sum > 0 ? nfeatures - sum : 0;
-      }
-      L.pix_off[l] = total_pix;
-      total_pix += (size_t)L.W[l] * L.H[l];
-      total_pix = (total_pix + 255) & ~(size_t)255;
-      L.seg_base[l] = n_slots;
-      L.seg_cap[l] = 2 * L.quota[l] + 64;  // retainBest keeps every keypoint tied with the last one
-      n_slots += L.seg_cap[l];
-    }
-    L.chunk_base[0] = 0;
-    for (int l = 0; l < ORB_LEVELS; l++) L.chunk_base[l + 1] = L.chunk_base[l] + (L.W[l] * L.H[l] + 1023) / 1024;
-  }
-  const int n_chunks = L.chunk_base[ORB_LEVELS];
-  // scratch: pyramid | score | flag | blurred (u8, total_pix each) | tmp (f32) | hist | level_count | kp_xy | kp_sl | angle | cs | desc
+  orb_plan_levels(w, h, nfeatures, P);
+  const OrbLevels& L = P.L;
+  const size_t total_pix = P.total_pix;
+  const int n_slots = P.n_slots, n_chunks = P.n_chunks;
+  // scratch: pyramid | score | flag | blurred (u8, total_pix each) | tmp (f32) | hist | level_count | cuts | level_full |
+  //          chunk_count | chunk_offset | keypoint arrays
+  const size_t n_ints = 256 * ORB_LEVELS + 32;
   void* d = nullptr;
-  const size_t bytes = 4 * total_pix + 4 * total_pix + 4 * (256 * ORB_LEVELS + 16) + (size_t)n_slots * (8 + 4 + 4 + 8 + 32) +
-                       8 * (size_t)n_chunks + 1024;
+  const size_t bytes = 4 * total_pix + 4 * total_pix + 4 * n_ints + 8 * (size_t)n_chunks + (size_t)n_slots * kOrbKpBytesPerSlot + 1024;
   rc = vsl_ctx_dscratch(ctx, bytes, &d);
   if (rc) return rc;
-  uint8_t* pyr = (uint8_t*)d;
-  uint8_t* score = pyr + total_pix;
-  uint8_t* flag = score + total_pix;
-  uint8_t* blurred = flag + total_pix;
-  float* tmp = (float*)(blurred + total_pix);
-  int* hist = (int*)(tmp + total_pix);
-  int32_t* level_count = hist + 256 * ORB_LEVELS;
-  int32_t* cuts = level_count + ORB_LEVELS;
-  int32_t* kp_xy = level_count + 16;
-  int32_t* kp_sl = kp_xy + 2 * (size_t)n_slots;
-  float* angle = (float*)(kp_sl + n_slots);
-  float* cs = angle + n_slots;
-  int32_t* chunk_count = (int32_t*)(cs + 2 * (size_t)n_slots);
-  int32_t* chunk_offset = chunk_count + n_chunks;
-  uint8_t* ddesc = (uint8_t*)(chunk_offset + n_chunks);
+  P.pyr = (uint8_t*)d;
+  P.score = P.pyr + total_pix;
+  P.flag = P.score + total_pix;
+  P.blurred = P.flag + total_pix;
+  P.tmp = (float*)(P.blurred + total_pix);
+  P.hist = (int*)(P.tmp + total_pix);
+  P.level_count = P.hist + 256 * ORB_LEVELS;
+  P.cuts = P.level_count + ORB_LEVELS;
+  P.level_full = P.cuts + ORB_LEVELS;
+  P.chunk_count = P.hist + n_ints;
+  P.chunk_offset = P.chunk_count + n_chunks;
+  P.kp = orb_carve_kp(P.chunk_offset + n_chunks, n_slots);
   hipStream_t st = ctx->stream;
-  VSL_HIP(ctx, hipMemcpy2DAsync(pyr, w, img, pitch, w, h, hipMemcpyHostToDevice, st));
-  VSL_HIP(ctx, hipMemsetAsync(hist, 0, sizeof(int) * (256 * ORB_LEVELS + 16), st));
+  VSL_HIP(ctx, hipMemcpy2DAsync(P.pyr, w, img, pitch, w, h, hipMemcpyHostToDevice, st));
+  VSL_HIP(ctx, hipMemsetAsync(P.hist, 0, sizeof(int) * n_ints, st));
   for (int l = 1; l < ORB_LEVELS; l++)
-    hipLaunchKernelGGL(orb_resize_kernel, dim3((L.W[l] + 255) / 256, L.H[l]), dim3(256), 0, st, pyr + L.pix_off[l - 1], L.W[l - 1],
-                       L.H[l - 1], pyr + L.pix_off[l], L.W[l], L.H[l], (double)L.W[l - 1] / L.W[l], (double)L.H[l - 1] / L.H[l]);
+    hipLaunchKernelGGL(orb_resize_kernel, dim3((L.W[l] + 255) / 256, L.H[l]), dim3(256), 0, st, P.pyr + L.pix_off[l - 1], L.W[l - 1],
+                       L.H[l - 1], P.pyr + L.pix_off[l], L.W[l], L.H[l], (double)L.W[l - 1] / L.W[l], (double)L.H[l - 1] / L.H[l]);
   {
     const int W = L.W[0], H = L.H[0];  // level 0 is the largest
-    hipLaunchKernelGGL(orb_fast_kernel, dim3((W + 15) / 16, (H + 15) / 16, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)pyr, score);
-    hipLaunchKernelGGL(orb_nms_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)score, flag, hist);
-    hipLaunchKernelGGL(orb_blur_rows_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)pyr, tmp);
-    hipLaunchKernelGGL(orb_blur_cols_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const float*)tmp, blurred);
+    hipLaunchKernelGGL(orb_fast_kernel, dim3((W + 15) / 16, (H + 15) / 16, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)P.pyr, P.score);
+    hipLaunchKernelGGL(orb_nms_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)P.score, P.flag, P.hist);
+    hipLaunchKernelGGL(orb_blur_rows_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)P.pyr, P.tmp);
+    hipLaunchKernelGGL(orb_blur_cols_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const float*)P.tmp, P.blurred);
   }
-  hipLaunchKernelGGL(orb_cut_kernel, dim3(ORB_LEVELS), dim3(256), 0, st, L, (const int*)hist, cuts);
-  hipLaunchKernelGGL(orb_compact_kernel<false>, dim3(n_chunks), dim3(1024), 0, st, L, score, flag, (const int32_t*)cuts, chunk_count,
-                     (const int32_t*)chunk_offset, kp_xy, kp_sl);
-  hipLaunchKernelGGL(orb_scan_kernel, dim3(1), dim3(1024), 0, st, L, (const int32_t*)chunk_count, chunk_offset, level_count);
-  hipLaunchKernelGGL(orb_compact_kernel<true>, dim3(n_chunks), dim3(1024), 0, st, L, score, flag, (const int32_t*)cuts, chunk_count,
-                     (const int32_t*)chunk_offset, kp_xy, kp_sl);
-  hipLaunchKernelGGL(orb_angle_kernel, dim3((n_slots + 3) / 4), dim3(256), 0, st, L, pyr, kp_xy, kp_sl, level_count, n_slots, angle);
+  hipLaunchKernelGGL(orb_cut_kernel, dim3(ORB_LEVELS), dim3(256), 0, st, L, (const int*)P.hist, P.cuts);
+  hipLaunchKernelGGL(orb_compact_kernel<false>, dim3(n_chunks), dim3(1024), 0, st, L, (const uint8_t*)P.score, (const uint8_t*)P.flag,
+                     (const int32_t*)P.cuts, P.chunk_count, (const int32_t*)P.chunk_offset, P.kp.xy, P.kp.sl);
+  hipLaunchKernelGGL(orb_scan_kernel, dim3(1), dim3(1024), 0, st, L, (const int32_t*)P.chunk_count, P.chunk_offset, P.level_count,
+                     P.level_full);
+  orb_launch_emit_angle(st, P, L, n_slots, P.kp, P.level_count);
   VSL_CHECK_LAUNCH(ctx);
-  // host: cos / sin of every angle with libm (fp32 radians -> double cos -> fp32, like the oracle)
-  std::vector<float> h_angle(n_slots), h_cs(2 * (size_t)n_slots, 0.f);
-  int32_t h_count[ORB_LEVELS];
-  VSL_HIP(ctx, hipMemcpyAsync(h_angle.data(), angle, sizeof(float) * n_slots, hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipMemcpyAsync(h_count, level_count, sizeof(h_count), hipMemcpyDeviceToHost, st));
+  return VSL_OK;
+}
+
+// device memory of the rare second emit, released on every way out
+struct OrbOverflowBuf {
+  void* p = nullptr;
+  ~OrbOverflowBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+bool orb_image_args_ok(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch) {
+  return ctx && img && w >= 64 && h >= 64 && pitch >= (size_t)w;
+}
+
+}  // namespace
+
+// kp5: (x, y in level-0 pixels, angle in degrees, response, octave) per keypoint; desc32: 32 bytes each.
+// *n_out = the number of keypoints found, also when it exceeds cap (VSL_ERR_CAPACITY, the first cap are filled).
+extern "C" int vsl_orb_detect_describe(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int nfeatures, int cap,
+                                       float* kp5, uint8_t* desc32, int* n_out) {
+  if (!orb_image_args_ok(ctx, img, w, h, pitch) || !n_out || nfeatures < 1 || cap < 0 || (cap > 0 && (!kp5 || !desc32)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_orb_detect_describe: bad arguments (w, h >= 64 required)");
+  *n_out = 0;
+  OrbPlan P;
+  int rc = orb_launch_stages(ctx, img, w, h, pitch, nfeatures, P);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  OrbLevels L = P.L;
+  int n_slots = P.n_slots;
+  OrbKpBuf kp = P.kp;
+  const int32_t* level_count = P.level_count;
+  std::vector<float> h_angle(n_slots);
+  int32_t h_full[ORB_LEVELS];
+  VSL_HIP(ctx, hipMemcpyAsync(h_angle.data(), kp.angle, sizeof(float) * n_slots, hipMemcpyDeviceToHost, st));
+  VSL_HIP(ctx, hipMemcpyAsync(h_full, P.level_full, sizeof(h_full), hipMemcpyDeviceToHost, st));
   VSL_HIP(ctx, hipStreamSynchronize(st));
+  bool overflow = false;
+  for (int l = 0; l < ORB_LEVELS; l++) overflow = overflow || h_full[l] > L.seg_cap[l];
+  OrbOverflowBuf big;
+  if (overflow) {
+    // more ties than a segment holds: emit again into segments of exactly the counted sizes (the chunk offsets
+    // are relative to the level and stay valid), then the angles of the new slots
+    for (int l = 0; l < ORB_LEVELS; l++) L.seg_cap[l] = h_full[l];
+    n_slots = orb_place_segments(L);
+    VSL_HIP(ctx, hipMalloc(&big.p, (size_t)n_slots * kOrbKpBytesPerSlot + 256));
+    kp = orb_carve_kp(big.p, n_slots);
+    level_count = P.level_full;
+    orb_launch_emit_angle(st, P, L, n_slots, kp, level_count);
+    VSL_CHECK_LAUNCH(ctx);
+    h_angle.resize(n_slots);
+    VSL_HIP(ctx, hipMemcpyAsync(h_angle.data(), kp.angle, sizeof(float) * n_slots, hipMemcpyDeviceToHost, st));
+    VSL_HIP(ctx, hipStreamSynchronize(st));
+  }
+  // host: cos / sin of every angle with libm (fp32 radians -> double cos -> fp32, like the oracle)
+  std::vector<float> h_cs(2 * (size_t)n_slots, 0.f);
   int total = 0;
   for (int l = 0; l < ORB_LEVELS; l++) {
-    for (int i = 0; i < h_count[l]; i++) {
+    for (int i = 0; i < h_full[l]; i++) {
       const int slot = L.seg_base[l] + i;
       const float rad = h_angle[slot] * (float)(M_PI / 180.0);
       h_cs[2 * (size_t)slot] = (float)std::cos((double)rad);
       h_cs[2 * (size_t)slot + 1] = (float)std::sin((double)rad);
     }
-    total += h_count[l];
+    total += h_full[l];
   }
-  VSL_HIP(ctx, hipMemcpyAsync(cs, h_cs.data(), sizeof(float) * 2 * n_slots, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(orb_describe_kernel, dim3((n_slots * 32 + 255) / 256), dim3(256), 0, st, L, blurred, kp_xy, level_count, n_slots, cs,
-                     ddesc);
+  VSL_HIP(ctx, hipMemcpyAsync(kp.cs, h_cs.data(), sizeof(float) * 2 * n_slots, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(orb_describe_kernel, dim3((n_slots * 32 + 255) / 256), dim3(256), 0, st, L, (const uint8_t*)P.blurred,
+                     (const int32_t*)kp.xy, level_count, n_slots, (const float*)kp.cs, kp.desc);
   VSL_CHECK_LAUNCH(ctx);
   std::vector<int32_t> h_xy(2 * (size_t)n_slots), h_sl(n_slots);
   std::vector<uint8_t> h_desc(32 * (size_t)n_slots);
-  VSL_HIP(ctx, hipMemcpyAsync(h_xy.data(), kp_xy, sizeof(int32_t) * 2 * n_slots, hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipMemcpyAsync(h_sl.data(), kp_sl, sizeof(int32_t) * n_slots, hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipMemcpyAsync(h_desc.data(), ddesc, 32 * (size_t)n_slots, hipMemcpyDeviceToHost, st));
+  VSL_HIP(ctx, hipMemcpyAsync(h_xy.data(), kp.xy, sizeof(int32_t) * 2 * n_slots, hipMemcpyDeviceToHost, st));
+  VSL_HIP(ctx, hipMemcpyAsync(h_sl.data(), kp.sl, sizeof(int32_t) * n_slots, hipMemcpyDeviceToHost, st));
+  VSL_HIP(ctx, hipMemcpyAsync(h_desc.data(), kp.desc, 32 * (size_t)n_slots, hipMemcpyDeviceToHost, st));
   VSL_HIP(ctx, hipStreamSynchronize(st));
   int n = 0;
   for (int l = 0; l < ORB_LEVELS && n < cap; l++)
-    for (int i = 0; i < h_count[l] && n < cap; i++) {
+    for (int i = 0; i < h_full[l] && n < cap; i++) {
       const int slot = L.seg_base[l] + i;
       float* k = kp5 + 5 * (size_t)n;
       k[0] = (float)h_xy[2 * (size_t)slot] * L.scale[l];
@@ -497,22 +598,61 @@ extern "C" int vsl_orb_detect_describe(vsl_ctx* ctx, const uint8_t* img, int w, 
       std::memcpy(desc32 + 32 * (size_t)n, h_desc.data() + 32 * (size_t)slot, 32);
       n++;
     }
-  *n_out = n;
+  *n_out = total;
   if (n < total) return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_orb_detect_describe: %d keypoints, capacity %d", total, cap);
   return VSL_OK;
 }
 
+extern "C" int vsl_orb_level_sizes(int w, int h, int* level_w, int* level_h) {
+  if (w < 1 || h < 1 || !level_w || !level_h) return VSL_ERR_INVALID;
+  OrbPlan P;
+  orb_plan_levels(w, h, 1, P);
+  for (int l = 0; l < ORB_LEVELS; l++) {
+    level_w[l] = P.L.W[l];
+    level_h[l] = P.L.H[l];
+  }
+  return VSL_OK;
+}
+
+// Test and diagnostic entry: the stage images of one pyramid level after the launches of vsl_orb_detect_describe.
+extern "C" int vsl_orb_stage_images(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int level, uint8_t* pyr,
+                                    uint8_t* score, uint8_t* nms_flag, uint8_t* blurred) {
+  if (!orb_image_args_ok(ctx, img, w, h, pitch) || level < 0 || level >= ORB_LEVELS)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_orb_stage_images: bad arguments (w, h >= 64, level in [0, %d) required)", ORB_LEVELS);
+  OrbPlan P;
+  // the stage images do not depend on the number of features; 1000 sizes the keypoint segments of the shared launches
+  int rc = orb_launch_stages(ctx, img, w, h, pitch, 1000, P);
+  if (rc) return rc;
+  const size_t n = (size_t)P.L.W[level] * P.L.H[level], off = P.L.pix_off[level];
+  uint8_t* const dst[4] = {pyr, score, nms_flag, blurred};
+  const uint8_t* const src[4] = {P.pyr, P.score, P.flag, P.blurred};
+  for (int i = 0; i < 4; i++)
+    if (dst[i]) VSL_HIP(ctx, hipMemcpyAsync(dst[i], src[i] + off, n, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VSL_OK;
+}
+
 // compute_bow_vector (include/visnav/keypoints.h:243-254): ORB front end + vocabulary transform.
+// More features than cap: VSL_ERR_CAPACITY with *nnz = *fv_n = the number of features (the capacity that suffices).
 extern "C" int vsl_compute_bow_vector(vsl_ctx* ctx, const vsl_voc* voc, const uint8_t* img, int w, int h, size_t pitch,
                                       int num_features, int levelsup, int cap, uint32_t* word_ids, double* word_vals, int* nnz,
                                       uint32_t* fv_node, uint32_t* fv_feat, int* fv_n) {
   if (!ctx || !voc || !nnz || !fv_n || cap < 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_compute_bow_vector: bad arguments");
-  const int kcap = 2 * num_features + 64 * ORB_LEVELS;
+  int kcap = 2 * num_features + 64 * ORB_LEVELS;
   std::vector<float> kp(5 * (size_t)kcap);
   std::vector<uint8_t> desc(32 * (size_t)kcap);
   int n = 0;
   int rc = vsl_orb_detect_describe(ctx, img, w, h, pitch, num_features, kcap, kp.data(), desc.data(), &n);
+  if (rc == VSL_ERR_CAPACITY) {  // ties beyond the usual bound: once more with the reported total
+    kcap = n;
+    kp.resize(5 * (size_t)kcap);
+    desc.resize(32 * (size_t)kcap);
+    rc = vsl_orb_detect_describe(ctx, img, w, h, pitch, num_features, kcap, kp.data(), desc.data(), &n);
+  }
   if (rc) return rc;
-  if (n > cap) return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_compute_bow_vector: %d features, output capacity %d", n, cap);
+  if (n > cap) {
+    *nnz = *fv_n = n;
+    return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_compute_bow_vector: %d features, output capacity %d", n, cap);
+  }
   return vsl_bow_transform(ctx, voc, desc.data(), n, levelsup, word_ids, word_vals, nnz, fv_node, fv_feat, fv_n);
 }
