@@ -44,6 +44,10 @@
 // application links a C ABI that does not define it (oracle/Makefile cpu_baseline), and refuses the option there.
 #pragma weak vsl_frames_stereo_inliers
 #pragma weak vsl_frames_download_inliers
+// ... and so are the batched search of landmark fusion (OdometryOptions::landmark_fusion) and the host-side pool append
+// its fused-tracking bookkeeping uses
+#pragma weak vsl_fuse_search
+#pragma weak vsl_map_append_descriptors
 
 namespace visnav {
 namespace harness {
@@ -51,6 +55,7 @@ namespace harness {
 inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
 // the device keyframe database (OdometryOptions::device_place_db) is referenced weakly in the same way (bow.h)
 inline bool device_place_db_available() { return KeyframeDatabaseAmd::available(); }
+inline bool landmark_fusion_available() { return &vsl_fuse_search != nullptr && &vsl_map_append_descriptors != nullptr; }
 
 struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.cpp:258-309
   int num_features_per_image = 1500;
@@ -90,6 +95,9 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   bool enable_relocalization = false;
   bool enable_loop_closure = false;
   bool enable_global_ba_after_loop_closure = true;
+  // after a loop was closed, merge the landmarks the two passes hold twice (loop_closure.h landmark_fusion: one batched
+  // guided search on the device + the map edits of fusion_plan.h) before optimize() and the global BA see the map
+  bool landmark_fusion = false;
   double motion_threshold = 0.5;
   int num_cov_threshold = 10;
   int num_ess_threshold = 30;
@@ -304,6 +312,7 @@ class Odometry {
   std::vector<std::pair<FrameCamId, FrameCamId>> loop_edges;
   bool pose_graph_opt_done = false;
   int n_tracking_lost = 0, n_relocalized = 0, n_loops_closed = 0, n_global_ba = 0;
+  LandmarkFusionResult fusion_total;  // counts of landmark_fusion over all closed loops (the edit lists stay empty)
   double loop_ms = 0, gba_ms = 0;
 
   // One step of the pipeline on the stereo pair of frame `current_frame` (the right image is only
@@ -428,6 +437,7 @@ class Odometry {
       }
       cam_right.T_w_c = to_se3(to_pose(current_pose) * T_0_1);
       cam_right.active = true;
+      std::vector<std::pair<FrameCamId, Sophus::SE3d>> closed_now;  // (candidate, sim3) of the loops closed in this step
       if (opt.enable_loop_closure && orb_voc) {  // src/slam.cpp:1219-1258
         auto tl = Clk::now();
         bool loop_detected = opt.device_place_db
@@ -455,6 +465,7 @@ class Odometry {
             lco.set_current_kf_fixed = opt.fixed_current_kf;
             loop_closure(fcidl, cam_left, cand, to_se3(T_0_1), sim3, cameras, landmarks, opt.num_ess_threshold, lco);
             n_loops_closed++;
+            closed_now.emplace_back(cand, sim3);
             map_dirty = true;
             if (opt.enable_global_ba_after_loop_closure) pose_graph_opt_done = true;
           }
@@ -469,6 +480,11 @@ class Odometry {
       cameras[fcidr] = cam_right;
       remove_old_keyframes(fcidl, opt.max_num_kfs, cameras, landmarks, kf_frames);
       if (opt.fused_tracking) fused_register_observations(fcidl, fcidr);
+      if (opt.landmark_fusion && !closed_now.empty()) {
+        auto tl = Clk::now();
+        for (const auto& c : closed_now) fuse_landmarks(fcidl, c.first, c.second);
+        loop_ms += ms(tl, Clk::now());
+      }
       auto t6 = Clk::now();
       optimize();
       if (pose_graph_opt_done) {  // src/slam.cpp:1285-1288
@@ -699,6 +715,41 @@ class Odometry {
     opt_finished = false;
     ba_pending = false;
     map_dirty = true;  // landmark positions moved
+  }
+
+  // landmark_fusion of loop_closure.h on the map as loop_closure() left it; with fused_tracking the device map's
+  // descriptor lists follow the edits (an added observation's descriptor joins the pool, a merged track's list moves)
+  void fuse_landmarks(const FrameCamId& fcidl, const FrameCamId& cand, const Sophus::SE3d& sim3) {
+    LandmarkFusionOptions fo;
+    fo.cam_z_threshold = opt.cam_z_threshold;
+    fo.match_max_dist_2d = opt.match_max_dist_2d;
+    fo.feature_match_threshold = opt.feature_match_max_dist;
+    fo.feature_match_dist_2_best = opt.feature_match_test_next_best;
+    LandmarkFusionResult r;
+    landmark_fusion(fcidl, cameras.at(fcidl), cand, sim3, cameras, landmarks, feature_corners, calib_cam, graph, fo, &r);
+    if (opt.fused_tracking) {
+      for (const auto& a : r.additions) {
+        const auto& d = feature_corners.at(std::get<1>(a)).corner_descriptors[(size_t)std::get<2>(a)];
+        int first = 0;
+        amd::check(vsl_map_append_descriptors(dev_map, 1, reinterpret_cast<const uint64_t*>(&d), &first), "vsl_map_append_descriptors");
+        lm_pool[std::get<0>(a)].push_back(first);
+      }
+      for (const auto& m : r.merges) {
+        auto gone = lm_pool.find(m.first);
+        if (gone == lm_pool.end()) continue;
+        auto& keep = lm_pool[m.second];
+        keep.insert(keep.end(), gone->second.begin(), gone->second.end());
+        lm_pool.erase(m.first);
+      }
+    }
+    fusion_total.added += r.added;
+    fusion_total.merged += r.merged;
+    fusion_total.conflicts += r.conflicts;
+    fusion_total.refused += r.refused;
+    map_dirty = true;
+    if (std::getenv("VISNAV_AMD_TRACE"))
+      std::fprintf(stderr, "  landmark fusion keyframe %lld <-> %lld: added %d merged %d conflicts %d refused %d, landmarks %zu\n",
+                   (long long)fcidl.frame_id, (long long)cand.frame_id, r.added, r.merged, r.conflicts, r.refused, landmarks.size());
   }
 
   // src/slam.cpp:1741-1788 + the merge-back of :1410-1447.  The reference runs it in global_ba_thread and merges at a

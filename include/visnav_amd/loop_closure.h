@@ -11,6 +11,8 @@
 //   compute_min_connected_covisible (:109-126), detect_loop_candidates (:141-263), insert_new_kf_to_db (:269-276),
 //   detect_loop_closure (:294-388), loop_align (:398-416), update_stereo_pair (:593-601),
 //   update_landmark_position (:607-621), loop_closure (:633-648)
+// landmark_fusion (:417-427) is declared and left empty upstream; the six-argument form stays that no-op, and an overload
+// does the work: one batched guided search on the device (vsl_fuse_search), then the map edits of fusion_plan.h.
 #pragma once
 #include <cmath>
 #include <map>
@@ -21,6 +23,7 @@
 
 #include "bow.h"
 #include "bundle_adjustment.h"
+#include "fusion_plan.h"
 
 namespace visnav {
 
@@ -452,6 +455,112 @@ inline void loop_closure(const FrameCamId& cur_kf_fcid, Camera cur_kf, const Fra
   pose_graph_optimization(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options);
   update_stereo_pair(cur_kf_fcid, cur_kf, T_0_1, keyframes);
   update_landmark_position(cur_kf_fcid, cur_kf, keyframes, landmarks);
+}
+
+// loop_closure_utils.h:417-427: "Not implemented..." upstream, and the same no-op here
+inline void landmark_fusion(const FrameCamId& cur_kf_fcid, Camera cur_kf, const FrameCamId& loop_candidate_fcid, const Sophus::SE3d& sim3,
+                            Cameras& keyframes, Landmarks& landmarks) {
+  (void)cur_kf_fcid;
+  (void)cur_kf;
+  (void)loop_candidate_fcid;
+  (void)sim3;
+  (void)keyframes;
+  (void)landmarks;
+}
+
+struct LandmarkFusionOptions {  // the matching parameters of project_landmarks / find_matches_landmarks (src/slam.cpp:258-309)
+  double cam_z_threshold = 0.1;
+  double match_max_dist_2d = 20.0;
+  int feature_match_threshold = 70;
+  double feature_match_dist_2_best = 1.2;
+  int max_views = 32;  // at most 64 (vsl_fuse_search)
+};
+
+// The working form, meant to run after loop_closure() has aligned the poses (they are read as they are): the landmarks
+// seen from the loop candidate's neighbourhood (targets, ascending TrackId, with all their all_obs descriptors) are
+// searched in the current keyframe and its covisible left keyframes (views) by ONE vsl_fuse_search call, and the matches
+// become added observations or merged tracks by the rules of fusion_plan.h.
+inline void landmark_fusion(const FrameCamId& cur_kf_fcid, Camera cur_kf, const FrameCamId& loop_candidate_fcid, const Sophus::SE3d& sim3,
+                            Cameras& keyframes, Landmarks& landmarks, const Corners& feature_corners, const Calibration& calib_cam,
+                            const CovisibilityGraph& graph, const LandmarkFusionOptions& options = LandmarkFusionOptions(),
+                            LandmarkFusionResult* result = nullptr) {
+  (void)sim3;
+  if (result) *result = LandmarkFusionResult();
+  // ---- views: the current left keyframe + its covisible left keyframes, the strongest max_views of them
+  std::vector<std::pair<int, FrameCamId>> nbs;  // (-weight, fcid): ascending = heaviest first, ties by FrameCamId
+  for (const auto& kv : cur_kf.covisible_rel_poses) {
+    if (kv.first.cam_id != 0 || kv.first == cur_kf_fcid || !keyframes.count(kv.first) || !feature_corners.count(kv.first)) continue;
+    const auto w = cur_kf.covisible_weights.find(kv.first);
+    nbs.emplace_back(w == cur_kf.covisible_weights.end() ? 0 : -w->second, kv.first);
+  }
+  std::sort(nbs.begin(), nbs.end());
+  const size_t max_views = (size_t)std::max(1, std::min(options.max_views, 64));
+  std::vector<FrameCamId> view_ids;
+  if (feature_corners.count(cur_kf_fcid)) view_ids.push_back(cur_kf_fcid);
+  for (const auto& nb : nbs)
+    if (view_ids.size() < max_views) view_ids.push_back(nb.second);
+  std::sort(view_ids.begin(), view_ids.end());
+  // ---- targets: every landmark observed from the loop candidate or one of its graph neighbours
+  std::set<FrameCamId> old_group;
+  old_group.insert(loop_candidate_fcid);
+  const auto g = graph.find(loop_candidate_fcid);
+  if (g != graph.end()) old_group.insert(g->second.begin(), g->second.end());
+  std::vector<TrackId> table;
+  for (const auto& kv : landmarks)
+    for (const auto& ob : kv.second.all_obs)
+      if (old_group.count(ob.first)) {
+        table.push_back(kv.first);
+        break;
+      }
+  std::sort(table.begin(), table.end());
+  if (view_ids.empty() || table.empty()) return;
+
+  std::vector<double> pose7, kp_xy, points;
+  std::vector<int32_t> kp_start(1, 0), obs_start(1, 0);
+  std::vector<uint64_t> kp_desc, obs_desc;
+  for (const FrameCamId& v : view_ids) {
+    const auto kf = keyframes.find(v);
+    const double* T = (kf != keyframes.end() ? kf->second.T_w_c : cur_kf.T_w_c).data();
+    pose7.insert(pose7.end(), T, T + 7);
+    const KeypointsData& kd = feature_corners.at(v);
+    const size_t n = std::min(kd.corners.size(), kd.corner_descriptors.size());
+    for (size_t i = 0; i < n; i++) {
+      kp_xy.push_back(kd.corners[i][0]);
+      kp_xy.push_back(kd.corners[i][1]);
+      const uint64_t* w = reinterpret_cast<const uint64_t*>(&kd.corner_descriptors[i]);
+      kp_desc.insert(kp_desc.end(), w, w + 4);
+    }
+    kp_start.push_back((int32_t)(kp_xy.size() / 2));
+  }
+  for (const TrackId tid : table) {
+    const Landmark& lm = landmarks.at(tid);
+    points.insert(points.end(), lm.p.data(), lm.p.data() + 3);
+    for (const auto& ob : lm.all_obs) {
+      const auto kd = feature_corners.find(ob.first);
+      if (kd == feature_corners.end() || (size_t)ob.second >= kd->second.corner_descriptors.size()) continue;
+      const uint64_t* w = reinterpret_cast<const uint64_t*>(&kd->second.corner_descriptors[(size_t)ob.second]);
+      obs_desc.insert(obs_desc.end(), w, w + 4);
+    }
+    obs_start.push_back((int32_t)(obs_desc.size() / 4));
+  }
+  const auto& cam = calib_cam.intrinsics[0];
+  const int n_views = (int)view_ids.size();
+  std::vector<int32_t> pairs(2 * (size_t)kp_start.back() + 2), pair_start((size_t)n_views + 1, 0);
+  amd::check(vsl_fuse_search(amd::ctx(), n_views, pose7.data(), amd::camera_model_id(cam->name()), cam->data(), cam->width(),
+                             cam->height(), kp_start.data(), kp_xy.data(), kp_desc.data(), (int)table.size(), points.data(),
+                             obs_start.data(), obs_desc.data(), options.cam_z_threshold, options.match_max_dist_2d,
+                             options.feature_match_threshold, options.feature_match_dist_2_best, pairs.data(), pair_start.data(),
+                             nullptr),
+             "landmark_fusion");
+  std::vector<amd::FusionView> views((size_t)n_views);
+  for (int v = 0; v < n_views; v++) {
+    views[(size_t)v].fcid = view_ids[(size_t)v];
+    for (int32_t i = pair_start[(size_t)v]; i < pair_start[(size_t)v + 1]; i++)
+      views[(size_t)v].pairs.emplace_back((FeatureId)pairs[2 * (size_t)i], pairs[2 * (size_t)i + 1]);
+  }
+  const LandmarkFusionResult r = amd::apply_fusion_plan(
+      views, amd::fusion_obs_lookup(landmarks, std::set<FrameCamId>(view_ids.begin(), view_ids.end())), table, keyframes, landmarks);
+  if (result) *result = r;
 }
 
 }  // namespace visnav

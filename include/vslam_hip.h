@@ -161,6 +161,20 @@ int vsl_find_matches_landmarks(vsl_ctx* ctx, const double* kp_xy, const uint64_t
                                const int32_t* lm_obs_start, int n_lms, const uint64_t* obs_desc,
                                double match_max_dist_2d, int feature_match_threshold,
                                double feature_match_dist_2_best, int32_t* pairs, int* n_out);
+/* The guided search of landmark fusion after a loop closure (visnav::landmark_fusion, include/visnav_amd/loop_closure.h):
+ * vsl_project_landmarks followed by vsl_find_matches_landmarks for n_views (<= 64) views at once -- one upload (landmark
+ * points and observation descriptors once, shared by all views), one chain of launches, one download.  pose7: 7 doubles
+ * per view; one camera model / intrinsics / image size for all views.  View v's keypoints are kp_xy / kp_desc
+ * [kp_start[v], kp_start[v + 1]) (kp_start[0] == 0, likewise lm_obs_start[0] == 0).  On return view v's matches are
+ * pairs[2 * pair_start[v] .. 2 * pair_start[v + 1]): (feature id local to the view, landmark index) in ascending feature
+ * id, element for element what the two single-view calls return on that view (projected order = ascending landmark
+ * index); n_projected[v] (nullable) = the landmarks of view v that passed the projection.  pairs: capacity
+ * 2 * kp_start[n_views]. */
+int vsl_fuse_search(vsl_ctx* ctx, int n_views, const double* pose7, int cam_model, const double* intr8, int width,
+                    int height, const int32_t* kp_start, const double* kp_xy, const uint64_t* kp_desc, int n_lms,
+                    const double* points, const int32_t* lm_obs_start, const uint64_t* obs_desc,
+                    double cam_z_threshold, double match_max_dist_2d, int feature_match_threshold,
+                    double feature_match_dist_2_best, int32_t* pairs, int32_t* pair_start, int32_t* n_projected);
 
 /* ------------------------------------- device-resident batched frame store */
 /*

@@ -335,6 +335,34 @@ class Context:
                                                    pairs.ctypes.data_as(i32p), C.byref(m)))
         return pairs[:m.value].copy()
 
+    def fuse_search(self, poses, model, intr8, width, height, kp_xy, kp_desc, points, lm_obs_start, obs_desc,
+                    cam_z_threshold=0.1, max_dist_2d=20.0, threshold=70, dist_2_best=1.2):
+        """vsl_fuse_search: project_landmarks + find_matches_landmarks for every view in one call.  poses: (V, 7);
+        kp_xy / kp_desc: one array per view.  Returns (list of per-view (n, 2) int32 pairs, n_projected[V])."""
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        intr8 = np.ascontiguousarray(intr8, np.float64)
+        V = len(poses)
+        assert len(kp_xy) == V and len(kp_desc) == V
+        xy = [np.asarray(a, np.float64).reshape(-1, 2) for a in kp_xy]
+        ds = [np.asarray(a, np.uint64).reshape(-1, 4) for a in kp_desc]
+        kp_start = np.concatenate([[0], np.cumsum([len(a) for a in xy])]).astype(np.int32)
+        xy = np.ascontiguousarray(np.concatenate(xy + [np.zeros((0, 2))]), np.float64)
+        ds = np.ascontiguousarray(np.concatenate(ds + [np.zeros((0, 4), np.uint64)]), np.uint64)
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        lm_obs_start = np.ascontiguousarray(lm_obs_start, np.int32)
+        obs_desc = np.ascontiguousarray(obs_desc, np.uint64).reshape(-1, 4)
+        pairs = np.zeros((max(len(xy), 1), 2), np.int32)
+        pair_start = np.zeros(V + 1, np.int32)
+        n_proj = np.zeros(max(V, 1), np.int32)
+        self._ck(self.L.vsl_fuse_search(self.h, V, poses.ctypes.data_as(f64p), int(model), intr8.ctypes.data_as(f64p),
+                                        int(width), int(height), kp_start.ctypes.data_as(i32p), xy.ctypes.data_as(f64p),
+                                        ds.ctypes.data_as(u64p), len(points), points.ctypes.data_as(f64p),
+                                        lm_obs_start.ctypes.data_as(i32p), obs_desc.ctypes.data_as(u64p),
+                                        C.c_double(cam_z_threshold), C.c_double(max_dist_2d), int(threshold),
+                                        C.c_double(dist_2_best), pairs.ctypes.data_as(i32p),
+                                        pair_start.ctypes.data_as(i32p), n_proj.ctypes.data_as(i32p)))
+        return [pairs[pair_start[v]:pair_start[v + 1]].copy() for v in range(V)], n_proj[:V].copy()
+
     def orb_detect_describe(self, img, num_features=1500):
         """ORB front end of compute_bow_vector: (kp[n, 5] = x, y, angle_deg, response, octave; desc[n, 32]).
         Every keypoint is returned: retainBest keeps all ties, so when the first buffer (2 * num_features + 512) is too

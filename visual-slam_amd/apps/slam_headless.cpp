@@ -63,6 +63,7 @@ int main(int argc, char** argv) {
     else if (a == "--relocalization") opt.enable_relocalization = true;   // the reference's ui.relocalization (default on there)
     else if (a == "--loop-closure") opt.enable_loop_closure = true;       // ui.loop_closure
     else if (a == "--no-gba-after-loop") opt.enable_global_ba_after_loop_closure = false;
+    else if (a == "--landmark-fusion") opt.landmark_fusion = true;  // merge the duplicate landmarks of a closed loop (one device search)
     else if (a == "--loop-time") opt.loop_closing_time_threshold = std::atoi(need("--loop-time").c_str());
     else if (a == "--num-consistency") opt.num_consistency = std::atoi(need("--num-consistency").c_str());
     else if (a == "--motion-threshold") opt.motion_threshold = std::atof(need("--motion-threshold").c_str());
@@ -93,6 +94,10 @@ int main(int argc, char** argv) {
   }
   if (opt.device_place_db && !device_place_db_available()) {
     std::fprintf(stderr, "--device-place-db: this build's C ABI has no device keyframe database (vsl_bowdb_query)\n");
+    return 2;
+  }
+  if (opt.landmark_fusion && !landmark_fusion_available()) {
+    std::fprintf(stderr, "--landmark-fusion: this build's C ABI has no batched fusion search (vsl_fuse_search)\n");
     return 2;
   }
   Calibration calib;
@@ -191,8 +196,9 @@ int main(int argc, char** argv) {
       o.next_step(left[i], right[i], (lookahead && i + 1 < n_frames) ? &left[i + 1] : nullptr);
       if (kf_count) *kf_count += kf ? 1 : 0;
       if (kf_count && trace)
-        std::fprintf(stderr, "frame %d kf %d matches %d inliers %d tracking %d lost %d reloc %d loops %d t = %.3f %.3f %.3f\n", i, (int)kf,
+        std::fprintf(stderr, "frame %d kf %d matches %d inliers %d tracking %d lost %d reloc %d loops %d fusion %d/%d/%d/%d t = %.3f %.3f %.3f\n", i, (int)kf,
                      o.last_matches, o.last_inliers, (int)o.tracking_successful, o.n_tracking_lost, o.n_relocalized, o.n_loops_closed,
+                     o.fusion_total.added, o.fusion_total.merged, o.fusion_total.conflicts, o.fusion_total.refused,
                      o.current_pose.data()[4], o.current_pose.data()[5], o.current_pose.data()[6]);
     }
     o.finish();
@@ -276,10 +282,14 @@ int main(int argc, char** argv) {
       "\"ate_rmse_m\": %.6f, \"ate_associations\": %d, \"landmarks\": %zu, \"active_landmarks\": %zu, \"async_ba\": %s, \"fused_tracking\": %s, \"device_stereo\": %s, \"device_place_db\": %s, "
       "\"stage_ms_total\": {\"detect\": %.1f, \"stereo_match\": %.1f, \"project_match\": %.1f, \"localize\": %.1f, \"map\": %.1f, "
       "\"ba\": %.1f, \"bow\": %.1f, \"loop\": %.1f, \"global_ba\": %.1f}, \"ba_runs\": %d, \"bow_vectors\": %zu, "
-      "\"tracking_lost\": %d, \"relocalized\": %d, \"loops_closed\": %d, \"global_ba_runs\": %d, \"reloc_check_ok\": %d, \"reloc_check_err_m\": %.6f}\n",
+      "\"tracking_lost\": %d, \"relocalized\": %d, \"loops_closed\": %d, \"global_ba_runs\": %d, \"reloc_check_ok\": %d, \"reloc_check_err_m\": %.6f",
       n_frames, n_kf, replicas, replicas_agree ? "true" : "false", replicas * n_frames / run_s, 1e3 * run_s / n_frames, decode_s, ate, n_assoc, odo.landmarks.size(), n_active,
       opt.async_ba ? "true" : "false", opt.fused_tracking ? "true" : "false", opt.device_stereo ? "true" : "false", opt.device_place_db ? "true" : "false", c.detect_ms, c.stereo_match_ms, c.project_match_ms, c.localize_ms, c.map_ms, c.ba_ms, c.bow_ms, odo.loop_ms, odo.gba_ms, c.ba_runs, odo.bow_vectors.size(),
       odo.n_tracking_lost, odo.n_relocalized, odo.n_loops_closed, odo.n_global_ba, reloc_ok, reloc_err_m);
+  if (opt.landmark_fusion)  // the line is unchanged without the option
+    std::printf(", \"landmark_fusion\": {\"added\": %d, \"merged\": %d, \"conflicts\": %d, \"refused\": %d}", odo.fusion_total.added,
+                odo.fusion_total.merged, odo.fusion_total.conflicts, odo.fusion_total.refused);
+  std::printf("}\n");
   amd::release_thread_ctx();  // the main thread's context (image registration), before static / thread-local teardown
   return 0;
 }

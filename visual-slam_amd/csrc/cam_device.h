@@ -4,7 +4,12 @@
 // host's, operand for operand and in the same association order: with -ffp-contract=off (csrc/Makefile) and
 // correctly rounded f64 division and sqrt, the pinhole / eucm / ds bearings and the triangulated points are the host's
 // bits.  kb4 calls sin / cos, whose device results may differ from the host libm in the last bit.
+//
+// Also the forward side shared by vo.hip and fuse.hip: quat_rotate_d(), project_exact() -- camera_models.h project(),
+// expression for expression -- and the host helper sqrt_less_threshold() of the guided search's radius test.
 #pragma once
+#include <cmath>
+
 #include "vsl_common.h"
 
 namespace {
@@ -70,6 +75,71 @@ __device__ __forceinline__ CamVec3 cam_triangulate_midpoint(const CamVec3& f1, c
   const CamVec3 p1 = {l1 * d1.x, l1 * d1.y, l1 * d1.z};
   const CamVec3 p2 = {t.x + l2 * d2.x, t.y + l2 * d2.y, t.z + l2 * d2.z};
   return {0.5 * (p1.x + p2.x), 0.5 * (p1.y + p2.y), 0.5 * (p1.z + p2.z)};
+}
+
+__device__ __forceinline__ void quat_rotate_d(const double* q, const double* p, double* out) {
+  double uv[3] = {q[1] * p[2] - q[2] * p[1], q[2] * p[0] - q[0] * p[2], q[0] * p[1] - q[1] * p[0]};
+  for (int i = 0; i < 3; i++) uv[i] = uv[i] + uv[i];
+  const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+  for (int i = 0; i < 3; i++) out[i] = p[i] + q[3] * uv[i] + c[i];
+}
+
+// camera_models.h project(), expression for expression (include/visnav/camera_models.h:75-94, :158-178,
+// :246-270, :341-374)
+__device__ __forceinline__ void project_exact(int model, const double* ip, double x, double y, double z, double& u,
+                                              double& v) {
+  const double fx = ip[0], fy = ip[1], cx = ip[2], cy = ip[3];
+  if (model == VSL_CAM_PINHOLE) {
+    u = fx * x / z + cx;
+    v = fy * y / z + cy;
+  } else if (model == VSL_CAM_EUCM) {
+    const double alpha = ip[4], beta = ip[5];
+    const double d = sqrt(beta * (x * x + y * y) + z * z);
+    u = fx * x / (alpha * d + (1.0 - alpha) * z) + cx;
+    v = fy * y / (alpha * d + (1.0 - alpha) * z) + cy;
+  } else if (model == VSL_CAM_KB4) {
+    const double k1 = ip[4], k2 = ip[5], k3 = ip[6], k4 = ip[7];
+    const double r = sqrt(x * x + y * y);
+    const double theta = atan2(r, z);
+    const double d = theta + k1 * theta * theta * theta + k2 * theta * theta * theta * theta * theta +
+                     k3 * theta * theta * theta * theta * theta * theta * theta +
+                     k4 * theta * theta * theta * theta * theta * theta * theta * theta * theta;
+    if (r == 0.0) {
+      u = cx;
+      v = cy;
+    } else {
+      u = fx * d * x / r + cx;
+      v = fy * d * y / r + cy;
+    }
+  } else {
+    const double xi = ip[4], alpha = ip[5];
+    const double d1 = sqrt(x * x + y * y + z * z);
+    const double d2 = sqrt(x * x + y * y + (xi * d1 + z) * (xi * d1 + z));
+    u = fx * x / (alpha * d2 + (1.0 - alpha) * (xi * d1 + z)) + cx;
+    v = fy * y / (alpha * d2 + (1.0 - alpha) * (xi * d1 + z)) + cy;
+  }
+}
+
+// The smallest double T with !(sqrt(T) < m): for x >= 0, sqrt(x) < m <=> x < T, because the correctly rounded square
+// root is monotone (host libm and the device's fp64 sqrt are both correctly rounded).  Bisection over the bit patterns
+// of the non-negative doubles (they order like the values).
+static inline double sqrt_less_threshold(double m) {
+  if (!(m > 0.0)) return 0.0;  // sqrt(x) < m never holds for x >= 0
+  if (std::isinf(m)) return m;
+  uint64_t lo = 0, hi;          // invariant: sqrt(value(lo)) < m, !(sqrt(value(hi)) < m)
+  {
+    const double inf = INFINITY;
+    memcpy(&hi, &inf, 8);
+  }
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    double v;
+    memcpy(&v, &mid, 8);
+    if (std::sqrt(v) < m) lo = mid; else hi = mid;
+  }
+  double T;
+  memcpy(&T, &hi, 8);
+  return T;
 }
 
 }  // namespace
