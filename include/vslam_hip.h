@@ -411,56 +411,21 @@ int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_opti
 int vsl_ba_residuals_jacobians(vsl_ctx* ctx, const vsl_ba_problem* prob, double* r, double* J_pose,
                                double* J_point);
 
-/* ---- step-wise session: multi-GPU global bundle adjustment ----
- * One process per GPU.  Every rank holds all camera poses and owns the landmark range
- * [lm_first, lm_first + lm_count) with its observations; per LM iteration the ranks SUM-all-reduce
- * the packed partial reduced camera system and five scalars (RCCL over xGMI via torch.distributed;
- * the loop is visual-slam_amd/ba_dist.py).  `_dev` arguments are DEVICE pointers; those calls are
- * asynchronous on the context's stream.  Replaces, for ~500-keyframe maps, the single Ceres solve of
- * global_bundle_adjustment (include/visnav/loop_closure_utils.h:672-748). */
-typedef struct vsl_ba_session vsl_ba_session;
-int vsl_ba_session_create(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
-                          int lm_first, int lm_count, vsl_ba_session** out);
-int vsl_ba_session_destroy(vsl_ba_session* s);
-/* n = 6 * free cameras; owned landmarks / observations; cameras. */
-int vsl_ba_session_dims(const vsl_ba_session* s, int* n, int* n_lms_own, int* n_obs_own, int* n_cams);
-/* use_scale = 0: the Jacobi-scaling pass (column norms, cost); 1: after an accepted step.  Large systems run in the
- * recompute form (visual-slam_amd/csrc/ba_large.h: nothing is stored per observation) -- there the call with
- * use_scale = 1 has nothing to do, vsl_ba_session_reduce_dev evaluates the observations at the current point itself.
- * Diagnostic "ba_no_fused" / VSL_BA_NO_FUSED: the chain over stored residual / Jacobian blocks instead. */
-int vsl_ba_session_linearize(vsl_ba_session* s, int use_scale);
-/* out_dev[n + 1] = [diag(H_part) | cost_part] */
-int vsl_ba_session_hdiag_cost_dev(vsl_ba_session* s, double* out_dev);
-int vsl_ba_session_set_scale_dev(vsl_ba_session* s, const double* hdiag_full_dev);
-/* packB_dev[n*n + 3n + 2] = [S_part | rhs_part | diag(H_part) | g_c part | cost_part | 0];
- * gmax_l_dev[1] (nullable) = max |gradient| over the owned landmark columns */
-int vsl_ba_session_reduce_dev(vsl_ba_session* s, double radius, double* packB_dev, double* gmax_l_dev);
-/* packC_dev[8] = [bad, model_part, step2, x2, cand_cost_part, step2_cams, x2_cams, 0] */
-int vsl_ba_session_step_dev(vsl_ba_session* s, const double* packB_full_dev, double radius,
-                            int refresh_diag, double* packC_dev);
-int vsl_ba_session_accept(vsl_ba_session* s);
-int vsl_ba_session_download(vsl_ba_session* s, double* poses, double* points_own);
-/* Layout of the reduced camera system inside packB: *s_elems doubles -- n * n when dense; in band form (cameras
- * renumbered into a narrow band by reverse Cuthill-McKee on the covisibility graph of the FULL problem, identically
- * on every rank; *banded = 1) or in CYCLIC band form (cameras as they came, the band closes around the loop -- the wrap
- * blocks sit in the leading slots of the first rows; *banded = 2) n * (bandwidth + 33) + 64 -- followed by rhs / diag H /
- * g_c (n each), cost, 0.  Wherever this header says "n*n" for packB read *s_elems. */
-int vsl_ba_session_layout(const vsl_ba_session* s, int64_t* s_elems, int* banded, int* bandwidth);
-
-/* The whole Levenberg-Marquardt loop over a session, host code in C++.  Collectives go through ONE caller-supplied
- * function: in-place all-reduce of `count` doubles at DEVICE pointer buf, op 0 = SUM, 1 = MAX, ordered on hip_stream
- * (the context's stream: an RCCL caller enqueues ncclAllReduce on it and returns; a host-hopping caller synchronises
- * it first); returns 0 on success.  world = 1: allreduce may be NULL.  poses_out [7 * n_cams] and points_all_out
- * [3 * n_lms of the FULL problem] (host, nullable) receive the result on every rank. */
+/* ---- multi-GPU global bundle adjustment ----
+ * visnav::global_bundle_adjustment (include/visnav/loop_closure_utils.h:672-748) over `world` ranks, one process per
+ * GPU: every rank holds all camera poses and owns a contiguous landmark range (balanced by observation count) with its
+ * observations; prob->poses / prob->points are updated in place on every rank.  The Levenberg-Marquardt loop is host
+ * code inside the library.  Collectives go through ONE caller-supplied function: in-place all-reduce of `count` doubles
+ * at DEVICE pointer buf, op 0 = SUM, 1 = MAX, ordered on hip_stream (the context's stream: an RCCL caller enqueues
+ * ncclAllReduce on it and returns; a host-hopping caller synchronises it first); returns 0 on success.  world = 1:
+ * allreduce may be NULL (the single-GPU solve of a large map).  Large systems run in the recompute form
+ * (visual-slam_amd/csrc/ba_large.h: nothing is stored per observation); diagnostic "ba_no_fused" / VSL_BA_NO_FUSED:
+ * the chain over stored residual / Jacobian blocks instead. */
 typedef int (*vsl_allreduce_fn)(void* user, double* buf, int64_t count, int op, void* hip_stream);
-int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduce, void* user, int world, int max_iters,
-                         int verbosity, double* poses_out, double* points_all_out, vsl_ba_summary* summary);
-/* visnav::global_bundle_adjustment over `world` ranks (one process per GPU): landmark ranges balanced by observation
- * count, rank `rank` owns one, prob->poses / prob->points updated in place on every rank. */
 int vsl_global_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
                              vsl_allreduce_fn allreduce, void* user, int rank, int world, vsl_ba_summary* summary);
 /* Diagnostic: storage of the reduced camera system in the last solve the general path (vsl_bundle_adjust beyond the
- * local window, sessions, vsl_global_bundle_adjust) set up on this context: doubles of S, *banded = 0 dense / 1 band (cameras
+ * local window, vsl_global_bundle_adjust) set up on this context: doubles of S, *banded = 0 dense / 1 band (cameras
  * in reverse Cuthill-McKee order) / 2 cyclic band (cameras as they came, the band closes around the loop), bandwidth.
  * Diagnostic "ba_no_cyclic" / VSL_BA_NO_CYCLIC keep form 1 where form 2 would be taken. */
 int vsl_ctx_last_ba_layout(vsl_ctx* ctx, int64_t* s_elems, int* banded, int* bandwidth);

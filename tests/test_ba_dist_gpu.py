@@ -1,4 +1,4 @@
-"""GPU: the multi-GPU global-BA path (vsl_ba_session + visual-slam_amd/ba_dist.py).
+"""GPU: the multi-GPU global-BA path (vsl_global_bundle_adjust + visual-slam_amd/ba_dist.py).
 
 * world size 1: the session-based LM loop reproduces vsl_bundle_adjust and the oracle;
 * world size 2 (two processes sharing the one GPU of the test box, gloo backend -- NCCL refuses two
@@ -336,3 +336,80 @@ def test_a_landmark_with_more_observations_than_a_workgroup_takes_the_stored_blo
     s_cpu = orc.bundle_adjust(a_cpu, max_iters=5)
     assert (s_def.iterations, s_def.termination) == (s_cpu.iterations, s_cpu.termination)
     assert s_def.final_cost == pytest.approx(s_cpu.final_cost, rel=1e-7)
+
+
+def test_session_over_a_small_system_matches_single_call_and_oracle(vsl, orc, synth):
+    """A window whose reduced system is small (16 cameras, 14 free: n = 84 <= 128) through the session loop at world 1:
+    ba_schur_small_kernel and ba_chol_small_kernel under the session's stored-blocks iteration, against the host loop
+    of the single call ("ba_no_fused") and the oracle -- the comparisons and tolerances of
+    test_session_world1_matches_single_call_and_oracle."""
+    import torch
+    ba_dist = importlib.import_module("visual_slam_amd.ba_dist")
+    d = synth.ba_problem(83, n_kf=8, n_lms=300)
+    assert 6 * int((d["cam_fixed"] == 0).sum()) <= 128
+    ctx = vsl.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    a_sess, a_one, a_cpu = _arr(orc, d), _arr(orc, d), _arr(orc, d)
+    s = ba_dist.bundle_adjust_distributed(vsl, ctx, a_sess, max_iters=8)
+    ctx.set_diagnostic("ba_no_fused", 1)
+    try:
+        s1 = ctx.bundle_adjust(a_one, max_iters=8)
+    finally:
+        ctx.set_diagnostic("ba_no_fused", 0)
+    s2 = orc.bundle_adjust(a_cpu, max_iters=8)
+    print("small session:", (s.iterations, s.termination, s.successful_steps), (s1.iterations, s1.termination, s1.successful_steps),
+          (s2.iterations, s2.termination), s.initial_cost, s1.initial_cost, s.final_cost, s1.final_cost, s2.final_cost,
+          np.abs(a_sess.poses - a_one.poses).max(), np.abs(a_sess.points - a_one.points).max())
+    assert (s.iterations, s.termination, s.successful_steps) == (s1.iterations, s1.termination, s1.successful_steps)
+    assert (s.iterations, s.termination) == (s2.iterations, s2.termination)
+    assert s.initial_cost == pytest.approx(s1.initial_cost, rel=1e-12)
+    assert s.final_cost == pytest.approx(s1.final_cost, rel=1e-9)
+    assert s.final_cost == pytest.approx(s2.final_cost, rel=1e-7)
+    assert np.allclose(a_sess.poses, a_one.poses, rtol=0, atol=1e-7)
+    dp = np.abs(a_sess.points - a_one.points).max(1)
+    assert (dp < 1e-6).mean() > 0.97 and dp.max() < 0.05
+    ctx.close()
+
+
+def _worker_world1(rank, port, out_dir):
+    os.environ.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    sys.path.insert(0, str(ROOT))
+    import torch
+    import torch.distributed as dist
+    import __graft_entry__ as entry
+    vsl = entry.load_package()
+    synth = importlib.import_module("visual_slam_amd.synth")
+    ba_dist = importlib.import_module("visual_slam_amd.ba_dist")
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    d = _problem(synth)
+    out = {}
+    for form, no_fused in (("recompute", 0), ("stored", 1)):
+        for how, kw in (("collectives", dict(collectives_at_world_one=True)), ("solo", dict(solo=True))):
+            ctx = vsl.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+            ctx.set_diagnostic("ba_no_fused", no_fused)
+            arr = vsl.BaArrays.from_dict(d)
+            s = ba_dist.bundle_adjust_distributed(vsl, ctx, arr, max_iters=8, **kw)
+            ctx.close()
+            k = form + "_" + how + "_"
+            out[k + "poses"], out[k + "points"] = arr.poses, arr.points
+            out[k + "cost"] = np.array([s.initial_cost, s.final_cost])
+            out[k + "meta"] = np.array([s.iterations, s.termination, s.successful_steps])
+    np.savez(Path(out_dir) / "world1.npz", **out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_collectives_at_world_one_change_no_bit(tmp_path):
+    """A one-rank gloo group: the reduced system packed into packB, all-reduced and unpacked
+    (collectives_at_world_one) against the solve that leaves S where it is (solo), in the recompute form and in the
+    stored-blocks form ("ba_no_fused"): poses, points, costs and the LM trajectory are the same bytes."""
+    import torch.multiprocessing as mp
+    mp.spawn(_worker_world1, args=(_free_port(), str(tmp_path)), nprocs=1, join=True)
+    r = np.load(tmp_path / "world1.npz")
+    for form in ("recompute", "stored"):
+        a, b = form + "_collectives_", form + "_solo_"
+        assert r[a + "meta"].tolist() == r[b + "meta"].tolist() and r[a + "meta"][0] > 0
+        for k in ("poses", "points", "cost"):
+            assert r[a + k].tobytes() == r[b + k].tobytes(), (form, k)
+    # (the two forms are different kernels: equal trajectory, not equal bytes -- test_recompute_form_matches_...)
+    assert r["recompute_solo_meta"].tolist() == r["stored_solo_meta"].tolist()

@@ -24,6 +24,8 @@ def test_hip_library_exports_every_declared_symbol(vsl):
     lib = vsl.load()
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing
+    # the step-wise session protocol is internal (csrc/ba_session.hip): no symbol, no string of it is left in the library
+    assert b"vsl_ba_session_" not in Path(lib._name).read_bytes()
 
 
 def test_version_and_error_strings(vsl):

@@ -1,5 +1,5 @@
 """Multi-GPU global bundle adjustment from Python: a thin wrapper over the C++ Levenberg-Marquardt loop
-`vsl_global_bundle_adjust` / `vsl_ba_session_solve` (visual-slam_amd/csrc/ba.hip), one process per GPU.
+`vsl_global_bundle_adjust` (visual-slam_amd/csrc/ba_session.hip), one process per GPU.
 
 Replaces, for maps too large for one solve to be interactive (~500 keyframes / ~1e5 landmarks, BASELINE.json
 configs[4]), what the reference hands to one ceres::Solve in global_bundle_adjustment

@@ -22,6 +22,10 @@
 //   * large systems (global BA): one wavefront per landmark, fp64 hardware atomics into the dense S,
 //     blocked dense Cholesky (chol.hip).
 //
+// The host-side state (BaState) and the launchers declared in ba_state.h are shared with ba_session.hip, the session
+// solver behind vsl_global_bundle_adjust (large maps, multi-GPU): its recompute-form kernels are ba_large.h, its
+// stored-blocks form runs the kernels of this file.
+//
 // Algorithmic bytes per LM iteration: n_obs*(16 + 8) + n_lms*24 + n_cams*56 + 128 in;
 // (6C)^2*8 + 6C*8 + n_lms*96 out.
 #include <algorithm>
@@ -34,7 +38,7 @@
 #include "dev_arena.h"
 #include "ba_host_plan.h"
 #include "ba_device.h"
-#include "ba_large.h"
+#include "ba_state.h"
 
 namespace {
 
@@ -1277,61 +1281,9 @@ __global__ void ba_raw_blocks_kernel(BaDims D, const double* __restrict__ poses,
   for (int j = 0; j < 6; j++) E[6 * (size_t)i + j] = EE[j];
 }
 
-// ------------------------------------------------------------------------------- host-side state
-struct BaState {
-  BaDims D;
-  int G = 1, lm_per_wg = 1, nb_obs = 1, nb_upd = 1;
-  int cb_seg = 1;  // workgroups per free camera in ba_cam_block_kernel
-  int bl_seg = 1;  // ... in bal_cam_kernel (recompute form: an observation is a chain of dependent gathers, one per thread)
-  bool small = true;
-  std::vector<int> perm;  // sorted position -> caller observation index
-  // ONE device allocation per solve (dev_arena.h), carved into the buffers below: vsl_bundle_adjust borrows the
-  // context's cached arena, a session and the parity hooks own theirs
-  DevArena arena;
-  double *poses = nullptr, *cand_poses = nullptr, *points = nullptr, *cand_points = nullptr, *intr = nullptr, *obs_uv = nullptr;
-  double *r = nullptr, *F = nullptr, *E = nullptr, *scale_c = nullptr, *scale_l = nullptr, *n2l = nullptr, *grad_l = nullptr;
-  double *H = nullptr, *g_c = nullptr, *diag_c = nullptr, *diag_l = nullptr, *gabs = nullptr, *S = nullptr, *rhs = nullptr;
-  double *S_part = nullptr, *rhs_part = nullptr, *Pinv = nullptr, *bl = nullptr, *dc = nullptr, *dl = nullptr;
-  double *partials = nullptr, *scalars = nullptr, *cam_part = nullptr;
-  int *cam_intr = nullptr, *cam_free = nullptr, *free_cams = nullptr, *obs_cam = nullptr, *obs_lm = nullptr;
-  int *lm_start = nullptr, *cam_start = nullptr, *cam_obs = nullptr;
-  int* flag = nullptr;  // 128 bytes behind scalars: one copy brings both back
-  // second linearisation set (vsl_bundle_adjust linearises the CANDIDATE point speculatively, before the host has
-  // read the step's verdict; an accepted step swaps the sets, a rejected one leaves the current set untouched)
-  double *r2 = nullptr, *F2 = nullptr, *E2 = nullptr, *n2l2 = nullptr, *grad_l2 = nullptr, *H2 = nullptr, *g_c2 = nullptr;
-  double *diag_c2 = nullptr, *diag_l2 = nullptr;
-  bool want_alt_set = false;
-  double* diagc_keep = nullptr;  // sessions (want_diagc_keep): clamp(diag H_full), reused across rejected steps
-  bool want_diagc_keep = false;
-  // large systems, gather form of the Schur complement (ba_schur_gather_kernel): per-block pair lists, built on the
-  // first use for the landmark range they cover, and the per-observation W / Y blocks of the current linearisation
-  int *pair_cnt = nullptr, *pair_start = nullptr, *pairs = nullptr, *cam_pos = nullptr;
-  double *Wg = nullptr, *Yg = nullptr;
-  // recompute form of a session's iteration (ba_large.h): landmark runs of the workgroups, their partial sums
-  int *wg_lm = nullptr, *cam_lm = nullptr;
-  double *lpart = nullptr, *cam_uv = nullptr, *pbs = nullptr;  // pbs[3 l + x] = scale_l (P^-1 b)_l: what the reduced right-hand side needs of a landmark
-  int n_wg = 0;
-  bool large_fused = false;
-  int n_slots = 0, hbp1 = 0;
-  size_t n_pairs_cap = 0;
-  int pair_l0 = -1, pair_lc = -1;
-  // Layout of the reduced camera system S: dense (ldS = n, offset 0) or, for large systems whose cameras can be
-  // ordered into a narrow band (reverse Cuthill-McKee on the covisibility graph, ba_setup), LAPACK-style lower band
-  // storage -- row i keeps columns [i - bws, i], bws = bw + VSL_CHOL_NB, entry (i, j) at S[i * ldS + j + offS] with
-  // ldS = offS = bws (chol.hip "BAND FORM").  The free-camera numbering IS the band order.
-  bool banded = false;
-  bool cyclic = false;  // band form whose band closes on itself (camera loop in trajectory order): wrap blocks in the leading slots of the first rows
-  int ldS = 0, offS = 0, bw = 0;
-  size_t s_elems = 0;  // doubles to allocate / clear / exchange for S
-  double* S_eff() { return S + offS; }
-  void swap_sets() {
-    std::swap(r, r2); std::swap(F, F2); std::swap(E, E2); std::swap(n2l, n2l2);
-    std::swap(grad_l, grad_l2); std::swap(H, H2); std::swap(g_c, g_c2); std::swap(diag_c, diag_c2);
-    std::swap(diag_l, diag_l2);
-    std::swap(poses, cand_poses); std::swap(points, cand_points);
-  }
-};
+}  // namespace
 
+// ------------------------------------------------------- host-side state: ba_state.h; set-up and launchers
 int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
   if (!ctx) return VSL_ERR_INVALID;
   if (!p || p->n_cams <= 0 || p->n_lms <= 0 || p->n_obs <= 0 || !p->poses || !p->cam_fixed || !p->cam_intr || !p->intr ||
@@ -1347,22 +1299,10 @@ int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
   return VSL_OK;
 }
 
-// set-up phase times on stderr when VSL_BA_TRACE is set (developer aid)
-struct BaTrace {
-  bool on;
-  double t0;
-  BaTrace() : on(getenv("VSL_BA_TRACE") != nullptr), t0(now_ms()) {}
-  void lap(const char* what) {
-    if (!on) return;
-    const double t = now_ms();
-    fprintf(stderr, "  [ba set-up] %-28s %8.3f ms\n", what, t - t0);
-    t0 = t;
-  }
-};
-
-int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaState& st, ArenaPolicy arena_policy,
-             bool allow_band = false, const vsl_ba_problem* graph_prob = nullptr) {
+int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaState& st, const BaCaller& caller) {
   BaTrace tr;
+  const bool allow_band = caller.use == BaUse::HOST_LOOP || caller.use == BaUse::SESSION;
+  const ArenaPolicy arena_policy = caller.use == BaUse::HOST_LOOP ? ArenaPolicy::BORROWED : ArenaPolicy::OWNED;
   BaDims& D = st.D;
   D.C = p->n_cams;
   D.L = p->n_lms;
@@ -1382,7 +1322,8 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   sw.chol_no_fused = ctx->chol_no_fused;
   BaHostPlan hp;
   try {
-    hp = ba_host_plan(p, graph_prob, sw, BaPlanLimits{SCH_CMAX, SCH_KMAX, BL_THREADS, BL_LMW}, [&](const char* what) { tr.lap(what); });
+    hp = ba_host_plan(p, caller.graph_prob, sw, BaPlanLimits{SCH_CMAX, SCH_KMAX, caller.run_max_obs, caller.run_max_lms},
+                      [&](const char* what) { tr.lap(what); });
   } catch (const std::bad_alloc&) {
     return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
   }
@@ -1400,7 +1341,13 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   ctx->last_ba_bw = st.bw;
   st.perm = std::move(hp.perm);
   st.small = hp.small;
-  st.n_wg = hp.n_wg;
+  // the form of the iteration, BEFORE the arena is planned: only a session runs the recompute form (ba_large.h); "ba_no_fused" /
+  // VSL_BA_NO_FUSED keep it on the operator-by-operator chain over stored r / F / E blocks (A/B runs, tests)
+  static const bool env_no_fused = getenv("VSL_BA_NO_FUSED") != nullptr;
+  st.recompute = caller.use == BaUse::SESSION && ba_recompute_form(hp, ctx->ba_no_fused || env_no_fused, ctx->ba_schur_atomics);
+  BaStored& sb = st.sb;
+  BaRecompute& rc = st.rc;
+  rc.n_wg = st.recompute ? hp.n_wg : 0;
   st.nb_obs = (D.O + 255) / 256;
   st.nb_upd = (std::max(D.C, D.L) + 255) / 256;
   st.G = std::min(SCH_GMAX, (D.L + SCH_LB - 1) / SCH_LB);
@@ -1410,22 +1357,28 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   const size_t n = (size_t)D.n, L = (size_t)D.L, O = (size_t)D.O, C = (size_t)D.C;
   // enough workgroups per camera that a camera's observations are ~2 slices of 256 per workgroup (1 when cameras are many)
   st.cb_seg = D.nfree > 0 ? std::max(1, std::min(32, (int)(D.O / std::max(1, D.nfree) / 512))) : 1;
-  st.bl_seg = st.cb_seg;  // (one workgroup per 256 observations of a camera measured 121 us against 80: more gathers in flight than the L2 holds)
+  rc.bl_seg = st.cb_seg;  // (one workgroup per 256 observations of a camera measured 121 us against 80: more gathers in flight than the L2 holds)
   const size_t nfree = (size_t)D.nfree, pair_elems = std::max<size_t>(hp.n_pairs < ((size_t)1 << 31) ? hp.n_pairs : 1, 1);
   ArenaPlan plan(56);
   plan.add(st.poses, 7 * C); plan.add(st.points, 3 * L); plan.add(st.intr, 16); plan.add(st.cam_intr, C); plan.add(st.cam_free, C);
   plan.add(st.free_cams, hp.free_cams.size()); plan.add(st.obs_cam, O); plan.add(st.obs_lm, O); plan.add(st.obs_uv, 2 * O);
   plan.add(st.lm_start, L + 1); plan.add(st.cam_start, C + 1); plan.add(st.cam_obs, O);
-  plan.add(st.cand_poses, 7 * C); plan.add(st.cand_points, 3 * L); plan.add(st.r, 2 * O); plan.add(st.F, 12 * O); plan.add(st.E, 6 * O);
-  plan.add(st.scale_c, n); plan.add(st.scale_l, 3 * L); plan.add(st.n2l, 3 * L); plan.add(st.grad_l, 3 * L);
-  plan.add(st.cam_part, 33 * std::max<size_t>(1, nfree) * std::max(st.cb_seg, st.bl_seg)); plan.add(st.H, 36 * nfree); plan.add(st.g_c, n);
-  plan.add(st.diag_c, n); plan.add(st.diag_l, 3 * L); plan.add(st.gabs, n + 3 * L); plan.add(st.S, st.s_elems); plan.add(st.rhs, n);
-  plan.add(st.Pinv, 9 * L); plan.add(st.bl, 3 * L); plan.add(st.dc, n); plan.add(st.dl, 3 * L);
-  plan.add(st.partials, (size_t)(2 * std::max(st.nb_obs, st.nb_upd) + 16));
+  plan.add(st.cand_poses, 7 * C); plan.add(st.cand_points, 3 * L);
+  if (!st.recompute) { plan.add(sb.r, 2 * O); plan.add(sb.F, 12 * O); plan.add(sb.E, 6 * O); }
+  plan.add(st.scale_c, n); plan.add(st.scale_l, 3 * L); plan.add(st.n2l, 3 * L);
+  if (!st.recompute) plan.add(sb.grad_l, 3 * L);
+  plan.add(st.cam_part, 33 * std::max<size_t>(1, nfree) * std::max(st.cb_seg, rc.bl_seg)); plan.add(st.H, 36 * nfree); plan.add(st.g_c, n);
+  if (!st.recompute) { plan.add(sb.diag_c, n); plan.add(sb.diag_l, 3 * L); plan.add(sb.gabs, n + 3 * L); }
+  plan.add(st.S, st.s_elems); plan.add(st.rhs, n);
+  plan.add(st.Pinv, 9 * L); plan.add(st.bl, 3 * L); plan.add(st.dc, n);
+  if (!st.recompute) {
+    plan.add(sb.dl, 3 * L);
+    plan.add(sb.partials, (size_t)(2 * std::max(st.nb_obs, st.nb_upd) + 16));
+  }
   plan.add(st.scalars, 16 + 2 /* = 4 ints */);  // 16 scalars, then flag: 4 ints in the 16 bytes of 2 doubles
   if (st.small) {
-    plan.add(st.S_part, n * n * st.G);
-    plan.add(st.rhs_part, n * st.G);
+    plan.add(sb.S_part, n * n * st.G);
+    plan.add(sb.rhs_part, n * st.G);
   } else {
     st.hbp1 = st.banded ? (st.bw - 5) / 6 + 1 : 0;
     st.n_slots = st.banded ? D.nfree * st.hbp1 : D.nfree * (D.nfree + 1) / 2;
@@ -1435,22 +1388,24 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
     plan.add(st.pair_start, (size_t)st.n_slots + 1);
     plan.add(st.pairs, 2 * pair_elems);
     plan.add(st.cam_pos, O);
-    plan.add(st.Wg, 18 * O);
+    if (!st.recompute) plan.add(sb.Wg, 18 * O);
     plan.add(st.Yg, 18 * O);
-    plan.add(st.wg_lm, (size_t)st.n_wg + 1);
-    plan.add(st.lpart, 4 * (size_t)std::max(1, st.n_wg));
-    plan.add(st.pbs, 3 * L);
-    plan.add(st.cam_lm, O);
-    plan.add(st.cam_uv, 2 * O);
   }
-  if (st.want_alt_set) {
-    plan.add(st.r2, 2 * O); plan.add(st.F2, 12 * O); plan.add(st.E2, 6 * O); plan.add(st.n2l2, 3 * L); plan.add(st.grad_l2, 3 * L);
-    plan.add(st.H2, 36 * nfree); plan.add(st.g_c2, n); plan.add(st.diag_c2, n); plan.add(st.diag_l2, 3 * L);
+  if (st.recompute) {
+    plan.add(rc.wg_lm, (size_t)rc.n_wg + 1);
+    plan.add(rc.lpart, 4 * (size_t)rc.n_wg);
+    plan.add(rc.pbs, 3 * L);
+    plan.add(rc.cam_lm, O);
+    plan.add(rc.cam_uv, 2 * O);
   }
-  if (st.want_diagc_keep) plan.add(st.diagc_keep, std::max<size_t>(n, 1));
+  if (caller.use == BaUse::HOST_LOOP) {
+    plan.add(sb.r2, 2 * O); plan.add(sb.F2, 12 * O); plan.add(sb.E2, 6 * O); plan.add(sb.n2l2, 3 * L); plan.add(sb.grad_l2, 3 * L);
+    plan.add(sb.H2, 36 * nfree); plan.add(sb.g_c2, n); plan.add(sb.diag_c2, n); plan.add(sb.diag_l2, 3 * L);
+  }
+  if (caller.use == BaUse::SESSION) plan.add(st.diagc_keep, std::max<size_t>(n, 1));
   VSL_HIP(ctx, st.arena.acquire(ctx, arena_policy, plan));
   st.flag = (int*)(st.scalars + 16);
-  tr.lap("arena");
+  tr.lap("arena", plan.total());
   auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
   };
@@ -1467,35 +1422,33 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   VSL_HIP(ctx, up(st.cam_start, hp.cam_start.data(), 4 * (C + 1)));
   VSL_HIP(ctx, up(st.cam_obs, hp.cam_obs.data(), 4 * O));
   if (!st.small) VSL_HIP(ctx, up(st.cam_pos, hp.cam_pos.data(), 4 * O));
-  if (!st.small && st.n_wg > 0) VSL_HIP(ctx, up(st.wg_lm, hp.wg_lm.data(), 4 * hp.wg_lm.size()));
+  if (st.recompute) VSL_HIP(ctx, up(rc.wg_lm, hp.wg_lm.data(), 4 * hp.wg_lm.size()));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the uploads above read host vectors that die here
   tr.lap("uploads");
   return VSL_OK;
 }
 
-// linearize at (poses, points): r, F, E (scaled when `scaled`), cost -> scalars[0]; per-landmark and
-// per-camera column statistics.
-int ba_linearize(vsl_ctx* ctx, BaState& st, bool scaled, int cost_slot = 0) {
+int ba_linearize(vsl_ctx* ctx, BaCommon& st, BaStored& sb, bool scaled, int cost_slot) {
   const BaDims& D = st.D;
   {
     VslStage s(ctx, VSL_STAGE_BA_LIN);
     hipLaunchKernelGGL(ba_linearize_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr,
                        st.cam_intr, st.cam_free, st.obs_cam, st.obs_lm, st.obs_uv, scaled ? st.scale_c : nullptr,
-                       scaled ? st.scale_l : nullptr, st.r, st.F, st.E, st.partials, 1);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, cost_slot, 0);
+                       scaled ? st.scale_l : nullptr, sb.r, sb.F, sb.E, sb.partials, 1);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, cost_slot, 0);
     VSL_CHECK_LAUNCH(ctx);
   }
   return VSL_OK;
 }
 
-int ba_columns(vsl_ctx* ctx, BaState& st) {
+int ba_columns(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
   const BaDims& D = st.D;
   VslStage s(ctx, VSL_STAGE_BA_LIN);
-  hipLaunchKernelGGL(ba_lm_cols_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.r, st.E, st.n2l,
-                     st.grad_l);
+  hipLaunchKernelGGL(ba_lm_cols_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, sb.r, sb.E, st.n2l,
+                     sb.grad_l);
   if (D.nfree > 0) {
     hipLaunchKernelGGL(ba_cam_block_kernel, dim3(D.nfree, st.cb_seg), dim3(256), 0, ctx->stream, st.free_cams, st.cam_start,
-                       st.cam_obs, st.r, st.F, st.cam_part);
+                       st.cam_obs, sb.r, sb.F, st.cam_part);
     hipLaunchKernelGGL(ba_cam_block_finish_kernel, dim3((D.nfree * 27 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.cb_seg,
                        st.cam_part, st.H, st.g_c);
   }
@@ -1504,14 +1457,13 @@ int ba_columns(vsl_ctx* ctx, BaState& st) {
 }
 
 // workgroups of ba_schur_gather_kernel: one per slot; in band form eight equal row ranges (see the kernel)
-unsigned gather_grid(const BaState& st) {
+static unsigned gather_grid(const BaCommon& st) {
   if (st.hbp1 <= 0) return (unsigned)st.n_slots;
   const int nrows = st.n_slots / st.hbp1;
   return 8u * (unsigned)((nrows + 7) / 8) * (unsigned)st.hbp1;
 }
 
-// block pair lists of the gather-form Schur complement for landmarks [l0, l0 + lc): built once per solve / session
-int ba_pair_lists(vsl_ctx* ctx, BaState& st, int l0, int lc) {
+int ba_pair_lists(vsl_ctx* ctx, BaCommon& st, int l0, int lc) {
   if (st.pair_l0 == l0 && st.pair_lc == lc) return VSL_OK;
   VSL_HIP(ctx, hipMemsetAsync(st.pair_cnt, 0, sizeof(int) * ((size_t)st.n_slots + 1), ctx->stream));
   hipLaunchKernelGGL(ba_pair_list_kernel<false>, dim3((lc + 255) / 256), dim3(256), 0, ctx->stream, l0, lc, st.lm_start, st.obs_cam,
@@ -1527,15 +1479,14 @@ int ba_pair_lists(vsl_ctx* ctx, BaState& st, int l0, int lc) {
   return VSL_OK;
 }
 
-// Schur complement of the landmark blocks over landmarks [l0, l0+lc); damping when diag != null.
-int ba_schur(vsl_ctx* ctx, BaState& st, bool damp, double radius, int l0, int lc, bool keep_backsub, bool lower_only) {
+int ba_schur(vsl_ctx* ctx, BaCommon& st, BaStored& sb, bool damp, double radius, int l0, int lc, bool keep_backsub, bool lower_only) {
   const BaDims& D = st.D;
   const int n = D.n;
   if (n == 0) return VSL_OK;
   VslStage s(ctx, VSL_STAGE_BA_SCHUR);
   const double inv_radius = damp ? 1.0 / radius : 0.0;
-  const double* dgl = damp ? st.diag_l : nullptr;
-  const double* dgc = damp ? st.diag_c : nullptr;
+  const double* dgl = damp ? sb.diag_l : nullptr;
+  const double* dgc = damp ? sb.diag_c : nullptr;
   double* Pinv = keep_backsub ? st.Pinv : nullptr;
   double* bl = keep_backsub ? st.bl : nullptr;
   if (st.small) {
@@ -1545,12 +1496,12 @@ int ba_schur(vsl_ctx* ctx, BaState& st, bool damp, double radius, int l0, int lc
     if (G > 0) {
       if (block3)
         hipLaunchKernelGGL(ba_schur_small_kernel<true>, dim3(G), dim3(SCH_THREADS), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                           st.cam_free, st.r, st.F, st.E, dgl, inv_radius, l0, lc, lpw, st.S_part, st.rhs_part, Pinv, bl);
+                           st.cam_free, sb.r, sb.F, sb.E, dgl, inv_radius, l0, lc, lpw, sb.S_part, sb.rhs_part, Pinv, bl);
       else
         hipLaunchKernelGGL(ba_schur_small_kernel<false>, dim3(G), dim3(SCH_THREADS), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                           st.cam_free, st.r, st.F, st.E, dgl, inv_radius, l0, lc, lpw, st.S_part, st.rhs_part, Pinv, bl);
+                           st.cam_free, sb.r, sb.F, sb.E, dgl, inv_radius, l0, lc, lpw, sb.S_part, sb.rhs_part, Pinv, bl);
     }
-    hipLaunchKernelGGL(ba_schur_finish_kernel, dim3((n * n + n + 15) / 16), dim3(256), 0, ctx->stream, n, G, st.S_part, st.rhs_part,
+    hipLaunchKernelGGL(ba_schur_finish_kernel, dim3((n * n + n + 15) / 16), dim3(256), 0, ctx->stream, n, G, sb.S_part, sb.rhs_part,
                        st.H, st.g_c, dgc, inv_radius, st.S, st.rhs, block3 ? 1 : 0);
   } else {
     VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * st.s_elems, ctx->stream));
@@ -1559,17 +1510,17 @@ int ba_schur(vsl_ctx* ctx, BaState& st, bool damp, double radius, int l0, int lc
     // (pair lists index with 32-bit positions: a problem with 2^31 pairs or more keeps the atomic form)
     if (lc > 0 && (ctx->ba_schur_atomics || st.n_pairs_cap >= ((size_t)1 << 31)))
       hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((lc + 3) / 4), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                         st.cam_free, st.r, st.F, st.E, dgl, inv_radius, l0, lc, st.S_eff(), st.rhs, Pinv, bl, lower_mode, st.ldS);
+                         st.cam_free, sb.r, sb.F, sb.E, dgl, inv_radius, l0, lc, st.S_eff(), st.rhs, Pinv, bl, lower_mode, st.ldS);
     else if (lc > 0) {
       int rc = ba_pair_lists(ctx, st, l0, lc);
       if (rc) return rc;
       hipLaunchKernelGGL(ba_schur_prep_kernel, dim3((lc + 3) / 4), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                         st.cam_free, st.cam_pos, st.r, st.F, st.E, dgl, inv_radius, l0, lc, st.Wg, st.Yg, st.rhs, Pinv, st.bl);
+                         st.cam_free, st.cam_pos, sb.r, sb.F, sb.E, dgl, inv_radius, l0, lc, sb.Wg, st.Yg, st.rhs, Pinv, st.bl);
       if (D.nfree > 0)
         hipLaunchKernelGGL(ba_schur_rhs_kernel, dim3(D.nfree), dim3(64), 0, ctx->stream, D.nfree, st.free_cams, st.cam_start,
                            st.cam_obs, st.obs_lm, st.Yg, st.bl, l0, lc, st.rhs);
       hipLaunchKernelGGL(ba_schur_gather_kernel, dim3(gather_grid(st)), dim3(64), 0, ctx->stream, st.n_slots, st.hbp1,
-                         st.pair_start, st.pairs, st.Wg, st.Yg, st.S_eff(), st.ldS, lower_mode);
+                         st.pair_start, st.pairs, sb.Wg, st.Yg, st.S_eff(), st.ldS, lower_mode);
     }
     hipLaunchKernelGGL(ba_add_cam_blocks_kernel, dim3((D.nfree * 36 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.H, st.g_c,
                        dgc, inv_radius, st.S_eff(), st.rhs, st.ldS, st.banded ? 1 : 0);
@@ -1578,9 +1529,7 @@ int ba_schur(vsl_ctx* ctx, BaState& st, bool damp, double radius, int l0, int lc
   return VSL_OK;
 }
 
-// dc = -(S^-1 rhs), enqueued only: flag[0] = 1 (the finite check clears it), flag[1] = Cholesky succeeded.
-// flags_set: the caller's previous kernel has set both flags (saves the launch)
-int ba_solve_enqueue(vsl_ctx* ctx, BaState& st, bool flags_set = false) {
+int ba_solve_enqueue(vsl_ctx* ctx, BaCommon& st, bool flags_set) {
   const int n = st.D.n;
   VslStage s(ctx, VSL_STAGE_BA_SOLVE);
   if ((n == 0 || n > 128) && !flags_set) hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, ctx->stream, st.flag);
@@ -1596,8 +1545,7 @@ int ba_solve_enqueue(vsl_ctx* ctx, BaState& st, bool flags_set = false) {
   return VSL_OK;
 }
 
-// dc = -(S^-1 rhs).  ok = false if S is not positive definite.
-int ba_solve(vsl_ctx* ctx, BaState& st, bool& ok) {
+int ba_solve(vsl_ctx* ctx, BaCommon& st, bool& ok) {
   const int n = st.D.n;
   ok = true;
   if (n == 0) return VSL_OK;
@@ -1621,83 +1569,82 @@ int ba_solve(vsl_ctx* ctx, BaState& st, bool& ok) {
   return VSL_OK;
 }
 
-int read_scalars(vsl_ctx* ctx, BaState& st, double* out, int n) {
+int read_scalars(vsl_ctx* ctx, BaCommon& st, double* out, int n) {
   VSL_HIP(ctx, hipMemcpyAsync(out, st.scalars, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VSL_OK;
 }
 
-BlArgs bal_args(BaState& st) {
-  BlArgs a;
-  a.D = st.D;
-  a.poses = st.poses;
-  a.points = st.points;
-  a.intr = st.intr;
-  a.cam_intr = st.cam_intr;
-  a.cam_free = st.cam_free;
-  a.obs_cam = st.obs_cam;
-  a.obs_lm = st.obs_lm;
-  a.obs_uv = st.obs_uv;
-  a.lm_start = st.lm_start;
-  a.wg_lm = st.wg_lm;
-  a.scale_c = st.scale_c;
-  a.scale_l = st.scale_l;
-  return a;
+namespace {
+// camera-only parts of the step / x norms (identical on every rank).  A kernel of the session's stored-blocks step that
+// lives here, beside the chain it runs in: compiled in ba_session.hip its LDS reads come out differently
+__global__ __launch_bounds__(256) void sess_cam_norms_kernel(BaDims D, const int* __restrict__ cam_free,
+                                                             const double* __restrict__ poses, const double* __restrict__ dc,
+                                                             const double* __restrict__ scale_c, double* __restrict__ scalars) {
+  __shared__ double sh[256];
+  double step2 = 0, x2 = 0;
+  for (int c = threadIdx.x; c < D.C; c += 256) {
+    const int fc = cam_free[c];
+    if (fc < 0) continue;
+    for (int j = 0; j < 6; j++) {
+      const double d = dc[6 * fc + j] * scale_c[6 * fc + j];
+      step2 += d * d;
+    }
+    for (int j = 0; j < 7; j++) x2 += poses[7 * (size_t)c + j] * poses[7 * (size_t)c + j];
+  }
+  const double a = block_sum_256(step2, sh);
+  __syncthreads();
+  const double b = block_sum_256(x2, sh);
+  if (threadIdx.x == 0) {
+    scalars[6] = a;
+    scalars[7] = b;
+  }
 }
-
-// recompute form (ba_large.h), the Jacobi-scaling pass: unscaled column norms (st.n2l, diag of st.H) and the cost
-int bal_init_pass(vsl_ctx* ctx, BaState& st) {
-  const BaDims& D = st.D;
-  VslStage s(ctx, VSL_STAGE_BA_LIN);
-  const BlArgs a = bal_args(st);
-  hipLaunchKernelGGL(bal_prep_kernel<true>, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, (const int*)nullptr, 0.0,
-                     (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, st.n2l, st.lpart);
-  hipLaunchKernelGGL(bal_cam_kernel<true>, dim3(D.nfree, st.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams, st.cam_start,
-                     st.cam_lm, st.cam_uv, (const double*)nullptr, st.cam_part);
-  hipLaunchKernelGGL(bal_cam_finish_kernel, dim3((D.nfree * 33 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.bl_seg, 0,
-                     st.cam_part, st.H, st.g_c, st.rhs, st.n_wg, st.lpart, st.scalars, (double*)nullptr);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
-}
-
-// recompute form: S (landmark damping only, no camera damping), rhs, H, g_c, P^-1, b at the current point;
-// scalars[0] = cost, gl_out[0] = max |gradient| over the landmark columns (unscaled problem).
-int bal_reduce(vsl_ctx* ctx, BaState& st, double radius, double* gl_out) {
-  const BaDims& D = st.D;
-  VslStage s(ctx, VSL_STAGE_BA_SCHUR);
-  const BlArgs a = bal_args(st);
-  VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * st.s_elems, ctx->stream));
-  int rc = ba_pair_lists(ctx, st, 0, D.L);
-  if (rc) return rc;
-  hipLaunchKernelGGL(bal_prep_kernel<false>, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.cam_pos, 1.0 / radius, st.Yg,
-                     st.Pinv, st.bl, st.pbs, (double*)nullptr, st.lpart);
-  hipLaunchKernelGGL(bal_cam_kernel<false>, dim3(D.nfree, st.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams, st.cam_start,
-                     st.cam_lm, st.cam_uv, st.pbs, st.cam_part);
-  hipLaunchKernelGGL(bal_cam_finish_kernel, dim3((D.nfree * 33 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.bl_seg, 1,
-                     st.cam_part, st.H, st.g_c, st.rhs, st.n_wg, st.lpart, st.scalars, gl_out);
-  hipLaunchKernelGGL(ba_schur_gather_kernel, dim3(gather_grid(st)), dim3(64), 0, ctx->stream, st.n_slots, st.hbp1,
-                     st.pair_start, st.pairs, st.Yg, st.Yg, st.S_eff(), st.ldS,
-                     st.banded ? 2 : (D.n > 128 ? 1 : 0));  // n <= 128 is solved by ba_chol_small_kernel (full matrix)
-  // (the camera blocks are added by the caller together with the packing: sess_add_pack_kernel)
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
-}
-
-// recompute form: candidate (cand_poses, cand_points) from dc, scalars[2..7] as the operator-by-operator chain leaves them
-int bal_step(vsl_ctx* ctx, BaState& st, double* packC_dev) {
-  const BaDims& D = st.D;
-  VslStage s(ctx, VSL_STAGE_BA_STEP);
-  const BlArgs a = bal_args(st);
-  hipLaunchKernelGGL(bal_pose_kernel, dim3(1), dim3(1024), 0, ctx->stream, D, st.cam_free, st.poses, st.dc, st.scale_c,
-                     st.cand_poses, st.scalars, st.flag);
-  hipLaunchKernelGGL(bal_step_kernel, dim3(st.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.Pinv, st.bl, st.dc, st.cand_poses,
-                     st.cand_points, st.lpart, st.flag);
-  hipLaunchKernelGGL(bal_step_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, st.n_wg, st.lpart, st.scalars, st.flag, packC_dev);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
-}
-
 }  // namespace
+
+// ---- what only the session's stored-blocks form launches (ba_session.hip): no stage of their own, as the session runs them
+int ba_apply_scale(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
+  hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D.O, st.cam_free, st.obs_cam, st.obs_lm,
+                     st.scale_c, st.scale_l, sb.F, sb.E);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int ba_schur_gather(vsl_ctx* ctx, BaCommon& st, const double* W, const double* Y, int lower_mode) {
+  hipLaunchKernelGGL(ba_schur_gather_kernel, dim3(gather_grid(st)), dim3(64), 0, ctx->stream, st.n_slots, st.hbp1,
+                     st.pair_start, st.pairs, W, Y, st.S_eff(), st.ldS, lower_mode);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int ba_max_of(vsl_ctx* ctx, const double* v, int n, double* dst) {
+  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, v, n, dst, 0, 1);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int ba_candidate(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
+  const BaDims& D = st.D;
+  const int n = D.n, nl = 3 * D.L;
+  hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                     st.cam_free, sb.F, sb.E, st.Pinv, st.bl, st.dc, sb.dl);
+  if (n > 0) hipLaunchKernelGGL(ba_all_finite_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.dc, st.flag);
+  hipLaunchKernelGGL(ba_all_finite_kernel, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, nl, sb.dl, st.flag);
+  hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, sb.r,
+                     sb.F, sb.E, st.dc, sb.dl, sb.partials);
+  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 2, 0);
+  hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
+                     sb.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, sb.partials, st.nb_upd);
+  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_upd, st.scalars, 3, 0);
+  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials + st.nb_upd, st.nb_upd, st.scalars, 4, 0);
+  hipLaunchKernelGGL(sess_cam_norms_kernel, dim3(1), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.dc, st.scale_c,
+                     st.scalars);
+  hipLaunchKernelGGL(ba_cost_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.cand_poses, st.cand_points, st.intr,
+                     st.cam_intr, st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, sb.partials);
+  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 5, 0);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
 
 int vsl_ba_chol_small_launch(vsl_ctx* ctx, int n, const double* S, const double* rhs, double* dc, int* ok_flag) {
   hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, ctx->stream, n, S, rhs, dc, ok_flag, (int*)nullptr);
@@ -1712,15 +1659,16 @@ extern "C" int vsl_ba_residuals_jacobians(vsl_ctx* ctx, const vsl_ba_problem* pr
   if (!r || !J_pose || !J_point) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_residuals_jacobians: null output");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   BaState st;
-  if ((rc = ba_setup(ctx, prob, nullptr, st, ArenaPolicy::OWNED))) return rc;
+  if ((rc = ba_setup(ctx, prob, nullptr, st, BaCaller{BaUse::PARITY_HOOK}))) return rc;
+  BaStored& sb = st.sb;
   const BaDims& D = st.D;
   hipLaunchKernelGGL(ba_raw_blocks_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr, st.cam_intr,
-                     st.obs_cam, st.obs_lm, st.obs_uv, st.r, st.F, st.E);
+                     st.obs_cam, st.obs_lm, st.obs_uv, sb.r, sb.F, sb.E);
   VSL_CHECK_LAUNCH(ctx);
   std::vector<double> hr(2 * (size_t)D.O), hF(12 * (size_t)D.O), hE(6 * (size_t)D.O);
-  VSL_HIP(ctx, hipMemcpyAsync(hr.data(), st.r, 8 * hr.size(), hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(hF.data(), st.F, 8 * hF.size(), hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(hE.data(), st.E, 8 * hE.size(), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(hr.data(), sb.r, 8 * hr.size(), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(hF.data(), sb.F, 8 * hF.size(), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(hE.data(), sb.E, 8 * hE.size(), hipMemcpyDeviceToHost, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int q = 0; q < D.O; q++) {  // back to the caller's observation order
     const size_t i = st.perm.empty() ? (size_t)q : (size_t)st.perm[q];
@@ -1738,7 +1686,8 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
   if (!opt || !S || !g || !cost || !n_free) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_linearize: null argument");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   BaState st;
-  if ((rc = ba_setup(ctx, prob, opt, st, ArenaPolicy::OWNED))) return rc;
+  if ((rc = ba_setup(ctx, prob, opt, st, BaCaller{BaUse::SINGLE_LINEARIZE}))) return rc;
+  BaStored& sb = st.sb;
   const BaDims& D = st.D;
   int l0 = 0, lc = D.L;
   if (lm_count >= 0) {
@@ -1746,7 +1695,7 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
     l0 = lm_first;
     lc = std::min(lm_count, D.L - lm_first);
   }
-  if ((rc = ba_linearize(ctx, st, false))) return rc;
+  if ((rc = ba_linearize(ctx, st, sb, false))) return rc;
   if (lm_count >= 0) {
     // restrict to the observations of the landmark range: zero the others' blocks so that the camera
     // sums and the cost only see the range (observations are sorted by landmark => one contiguous run)
@@ -1755,25 +1704,25 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t o0 = (size_t)lm_start[l0], o1 = (size_t)lm_start[l0 + lc];
     if (o0 > 0) {
-      VSL_HIP(ctx, hipMemsetAsync(st.r, 0, 16 * o0, ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.F, 0, 96 * o0, ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.E, 0, 48 * o0, ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(sb.r, 0, 16 * o0, ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(sb.F, 0, 96 * o0, ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(sb.E, 0, 48 * o0, ctx->stream));
     }
     if (o1 < (size_t)D.O) {
-      VSL_HIP(ctx, hipMemsetAsync(st.r + 2 * o1, 0, 16 * ((size_t)D.O - o1), ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.F + 12 * o1, 0, 96 * ((size_t)D.O - o1), ctx->stream));
-      VSL_HIP(ctx, hipMemsetAsync(st.E + 6 * o1, 0, 48 * ((size_t)D.O - o1), ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(sb.r + 2 * o1, 0, 16 * ((size_t)D.O - o1), ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(sb.F + 12 * o1, 0, 96 * ((size_t)D.O - o1), ctx->stream));
+      VSL_HIP(ctx, hipMemsetAsync(sb.E + 6 * o1, 0, 48 * ((size_t)D.O - o1), ctx->stream));
     }
     const int oc = (int)(o1 - o0);
     const int nb = (oc + 255) / 256;
     if (nb > 0)
       hipLaunchKernelGGL(ba_cost_kernel, dim3(nb), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr, st.cam_intr,
-                         st.obs_cam, st.obs_lm, st.obs_uv, (int)o0, oc, st.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, nb, st.scalars, 0, 0);
+                         st.obs_cam, st.obs_lm, st.obs_uv, (int)o0, oc, sb.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, nb, st.scalars, 0, 0);
     VSL_CHECK_LAUNCH(ctx);
   }
-  if ((rc = ba_columns(ctx, st))) return rc;
-  if ((rc = ba_schur(ctx, st, false, 1.0, l0, lc, false, false))) return rc;
+  if ((rc = ba_columns(ctx, st, sb))) return rc;
+  if ((rc = ba_schur(ctx, st, sb, false, 1.0, l0, lc, false, false))) return rc;
   double sc[1];
   if ((rc = read_scalars(ctx, st, sc, 1))) return rc;
   *cost = sc[0];
@@ -1810,8 +1759,8 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   }
   const double t_start = now_ms();
   BaState st;
-  st.want_alt_set = true;
-  if ((rc = ba_setup(ctx, prob, opt, st, ArenaPolicy::BORROWED, true))) return rc;
+  if ((rc = ba_setup(ctx, prob, opt, st, BaCaller{BaUse::HOST_LOOP}))) return rc;
+  BaStored& sb = st.sb;
   const BaDims& D = st.D;
   const int nc = D.n, nl = 3 * D.L;
   vsl_ba_summary sum;
@@ -1825,20 +1774,20 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
 
   double sc[8];
   // iteration 0: evaluate, Jacobi scaling from the unscaled Jacobian, then scale it
-  if ((rc = ba_linearize(ctx, st, false))) return rc;
-  if ((rc = ba_columns(ctx, st))) return rc;
+  if ((rc = ba_linearize(ctx, st, sb, false))) return rc;
+  if ((rc = ba_columns(ctx, st, sb))) return rc;
   const int nmax = std::max(nc, nl);
   hipLaunchKernelGGL(ba_make_scale_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, st.H, st.n2l,
                      st.scale_c, st.scale_l);
   hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D.O, st.cam_free, st.obs_cam, st.obs_lm,
-                     st.scale_c, st.scale_l, st.F, st.E);
+                     st.scale_c, st.scale_l, sb.F, sb.E);
   VSL_CHECK_LAUNCH(ctx);
-  if ((rc = ba_columns(ctx, st))) return rc;
+  if ((rc = ba_columns(ctx, st, sb))) return rc;
 
   auto diag_and_gmax = [&](int slot) -> int {
     hipLaunchKernelGGL(ba_diag_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, st.H, st.n2l, st.g_c,
-                       st.grad_l, st.scale_c, st.scale_l, st.diag_c, st.diag_l, st.gabs);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.gabs, (nmax + 255) / 256, st.scalars, slot, 1);
+                       sb.grad_l, st.scale_c, st.scale_l, sb.diag_c, sb.diag_l, sb.gabs);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.gabs, (nmax + 255) / 256, st.scalars, slot, 1);
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   };
@@ -1869,25 +1818,25 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     if (iteration >= opt->max_num_iterations) { sum.termination = 0; break; }
     if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
     iteration++;
-    if ((rc = ba_schur(ctx, st, true, lm.radius, 0, D.L, true, true))) return rc;
+    if ((rc = ba_schur(ctx, st, sb, true, lm.radius, 0, D.L, true, true))) return rc;
     if ((rc = ba_solve_enqueue(ctx, st))) return rc;  // flag[1] = Cholesky ok
     {
       VslStage s(ctx, VSL_STAGE_BA_SOLVE);
       hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                         st.cam_free, st.F, st.E, st.Pinv, st.bl, st.dc, st.dl, st.flag);
-      hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, st.r,
-                         st.F, st.E, st.dc, st.dl, st.partials);
-      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, 2, 0);
+                         st.cam_free, sb.F, sb.E, st.Pinv, st.bl, st.dc, sb.dl, st.flag);
+      hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, sb.r,
+                         sb.F, sb.E, st.dc, sb.dl, sb.partials);
+      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 2, 0);
       hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
-                         st.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, st.partials, st.nb_upd);
-      hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, st.partials, st.nb_upd, st.scalars, 3);
+                         sb.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, sb.partials, st.nb_upd);
+      hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, sb.partials, st.nb_upd, st.scalars, 3);
       VSL_CHECK_LAUNCH(ctx);
     }
     // speculative: the candidate becomes the current point, its linearisation goes to the other set;
     // scalars[5] = cost there, scalars[6] = max |gradient| there (slots 0/1 keep the current point's values)
     st.swap_sets();
-    if ((rc = ba_linearize(ctx, st, true, 5))) return rc;
-    if ((rc = ba_columns(ctx, st))) return rc;
+    if ((rc = ba_linearize(ctx, st, sb, true, 5))) return rc;
+    if ((rc = ba_columns(ctx, st, sb))) return rc;
     if ((rc = diag_and_gmax(6))) return rc;
     VSL_HIP(ctx, hipMemcpyAsync(hsc, st.scalars, 16 * sizeof(double) + 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1927,590 +1876,6 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
             sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
   if (summary) *summary = sum;
   return VSL_OK;
-}
-
-// =================================================================================================
-// Step-wise session: the multi-GPU global-BA path.
-//
-// One process per GPU.  Every rank holds all camera poses and OWNS a contiguous landmark range with
-// its observations (the session is built on that sub-problem).  Per LM iteration the ranks exchange
-//   packB = [ S_part (n*n) | rhs_part (n) | diag(H_part) (n) | g_c part (n) | cost_part | 0 ]  SUM all-reduce
-//   packC = [ bad, model_part, step2_lm, x2_lm, cand_cost_part ]                  SUM all-reduce
-// (plus one MAX all-reduce of the landmark gradient norm after an accepted step, and one SUM of
-// [diag(H_part) | cost_part] for the Jacobi scaling at iteration 0).  Every rank then factorises the
-// same reduced camera system redundantly -- RCCL all-reduce leaves bit-identical buffers on all ranks,
-// so the accept / reject decisions agree without a broadcast.  Landmark damping and back-substitution
-// are local.  The host-side loop lives in visual-slam_amd/ba_dist.py (torch.distributed = RCCL).
-struct vsl_ba_session {
-  vsl_ctx* ctx = nullptr;
-  BaState st;
-  vsl_ba_options opt;
-  int lm_first = 0, lm_count = 0, n_lms_total = 0;
-  bool solo = false;  // vsl_ba_session_solve without a collective: S stays where it is (no copy into packB and back)
-};
-
-namespace {
-__global__ void sess_pack_hdiag_kernel(int nfree, const double* __restrict__ H, const double* __restrict__ scalars,
-                                       double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = 6 * nfree;
-  if (i < n) out[i] = H[36 * (size_t)(i / 6) + 7 * (i % 6)];
-  if (i == 0) out[n] = scalars[0];
-}
-
-__global__ void sess_scale_kernel(int nfree, int L, const double* __restrict__ hdiag_full, const double* __restrict__ n2l,
-                                  double* __restrict__ scale_c, double* __restrict__ scale_l) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 6 * nfree) scale_c[i] = 1.0 / (1.0 + sqrt(hdiag_full[i]));
-  if (i < 3 * L) scale_l[i] = 1.0 / (1.0 + sqrt(n2l[i]));
-}
-
-// landmark LM diagonal (own landmarks) and |gradient| of the unscaled problem for the landmark columns
-__global__ void sess_diag_l_kernel(int L, const double* __restrict__ n2l, const double* __restrict__ grad_l,
-                                   const double* __restrict__ scale_l, double* __restrict__ diag_l, double* __restrict__ gabs) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 3 * L) {
-    diag_l[i] = fmin(fmax(n2l[i], 1e-6), 1e32);
-    gabs[i] = fabs(grad_l[i] / scale_l[i]);
-  }
-}
-
-// packB tail after the n*n block: [rhs_part | diag(H_part) | g_c part (raw sum F^T r) | cost_part | 0]
-__global__ void sess_pack_b_kernel(int nfree, const double* __restrict__ rhs, const double* __restrict__ H,
-                                   const double* __restrict__ g_c, const double* __restrict__ scalars,
-                                   double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = 6 * nfree;
-  if (i < n) {
-    out[i] = rhs[i];
-    out[n + i] = H[36 * (size_t)(i / 6) + 7 * (i % 6)];
-    out[2 * n + i] = g_c[i];
-  }
-  if (i == 0) {
-    out[3 * n] = scalars[0];
-    out[3 * n + 1] = 0.0;
-  }
-}
-
-// ba_add_cam_blocks_kernel (no camera damping) and sess_pack_b_kernel in one launch: S += blockdiag(H), rhs += g_c, and
-// the tail of packB from the sums
-__global__ void sess_add_pack_kernel(int nfree, const double* __restrict__ H, const double* __restrict__ g_c,
-                                     const double* __restrict__ scalars, double* __restrict__ S, double* __restrict__ rhs, int ldS,
-                                     int lower_elems, double* __restrict__ out) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = 6 * nfree;
-  if (t < nfree * 36) {
-    const int fc = t / 36, x = (t % 36) / 6, y = t % 6;
-    if (!(lower_elems && y > x)) S[(size_t)(6 * fc + x) * ldS + 6 * fc + y] += H[t];
-  }
-  if (t < n) {
-    const double r = rhs[t] + g_c[t];
-    rhs[t] = r;
-    out[t] = r;
-    out[n + t] = H[36 * (size_t)(t / 6) + 7 * (t % 6)];
-    out[2 * n + t] = g_c[t];
-  }
-  if (t == 0) {
-    out[3 * n] = scalars[0];
-    out[3 * n + 1] = 0.0;
-  }
-}
-
-// S = S_full + diag(diag_c / radius); diag_c = clamp(diag H_full) when refresh, else kept.  S_full (the first
-// `elems` doubles of packB, dense or band layout) has been copied into S already; this adds the damping to the
-// diagonal (entry (i, i) at S_eff[i * ldS + i]) and unpacks rhs.
-__global__ void sess_damp_kernel(int n, size_t elems, const double* __restrict__ packB, double inv_radius, int refresh,
-                                 double* __restrict__ diag_keep, double* __restrict__ S_eff, int ldS, double* __restrict__ rhs,
-                                 int* __restrict__ flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (flags && i < 2) flags[i] = 1;  // (step finite / factorisation succeeded: what ba_set_flags_kernel would set)
-  if (i < n) {
-    double d = diag_keep[i];
-    if (refresh) {
-      d = fmin(fmax(packB[elems + n + i], 1e-6), 1e32);
-      diag_keep[i] = d;
-    }
-    S_eff[(size_t)i * ldS + i] += d * inv_radius;
-    rhs[i] = packB[elems + i];
-  }
-}
-
-__global__ void sess_pack_c_kernel(const double* __restrict__ scalars, const int* __restrict__ flag, int both,
-                                   double* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    // number of ranks whose step is unusable (both: flag[0] = step finite, flag[1] = factorisation succeeded)
-    out[0] = (flag[0] && (!both || flag[1])) ? 0.0 : 1.0;
-    out[1] = scalars[2];           // model cost change, own observations
-    out[2] = scalars[3];           // squared step norm (own landmarks + cameras, see ba_dist.py)
-    out[3] = scalars[4];           // squared x norm   (own landmarks + cameras)
-    out[4] = scalars[5];           // candidate cost, own observations
-    out[5] = scalars[6];           // squared step norm of the cameras alone (replicated on every rank)
-    out[6] = scalars[7];           // squared x norm of the cameras alone
-    out[7] = 0.0;
-  }
-}
-
-// camera-only parts of the step / x norms (identical on every rank)
-__global__ __launch_bounds__(256) void sess_cam_norms_kernel(BaDims D, const int* __restrict__ cam_free,
-                                                             const double* __restrict__ poses, const double* __restrict__ dc,
-                                                             const double* __restrict__ scale_c, double* __restrict__ scalars) {
-  __shared__ double sh[256];
-  double step2 = 0, x2 = 0;
-  for (int c = threadIdx.x; c < D.C; c += 256) {
-    const int fc = cam_free[c];
-    if (fc < 0) continue;
-    for (int j = 0; j < 6; j++) {
-      const double d = dc[6 * fc + j] * scale_c[6 * fc + j];
-      step2 += d * d;
-    }
-    for (int j = 0; j < 7; j++) x2 += poses[7 * (size_t)c + j] * poses[7 * (size_t)c + j];
-  }
-  const double a = block_sum_256(step2, sh);
-  __syncthreads();
-  const double b = block_sum_256(x2, sh);
-  if (threadIdx.x == 0) {
-    scalars[6] = a;
-    scalars[7] = b;
-  }
-}
-}  // namespace
-
-extern "C" int vsl_ba_session_create(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, int lm_first,
-                                     int lm_count, vsl_ba_session** out) {
-  int rc = ba_validate(ctx, prob);
-  if (rc) return rc;
-  if (!opt || !out) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_session_create: null argument");
-  *out = nullptr;
-  if (lm_first < 0 || lm_count < 1 || lm_first + lm_count > prob->n_lms)
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_session_create: landmark range [%d, %d) must be non-empty and inside [0, %d)", lm_first, lm_first + lm_count, prob->n_lms);
-  VSL_HIP(ctx, hipSetDevice(ctx->device));
-  BaTrace tr;
-  // sub-problem of the owned landmarks (all cameras); one rank: the problem itself, no copy
-  BaSubObs own;
-  vsl_ba_problem sub = *prob;
-  if (!(lm_first == 0 && lm_count == prob->n_lms)) {
-    try {
-      sub = ba_sub_problem(prob, lm_first, lm_count, own);
-    } catch (const std::bad_alloc&) {
-      return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
-    }
-    if (sub.n_obs == 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_session_create: landmark range has no observations");
-  }
-  tr.lap("session: sub-problem");
-  vsl_ba_session* s = new (std::nothrow) vsl_ba_session;
-  if (!s) return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
-  s->ctx = ctx;
-  s->opt = *opt;
-  s->lm_first = lm_first;
-  s->lm_count = lm_count;
-  s->n_lms_total = prob->n_lms;
-  s->st.want_diagc_keep = true;
-  if ((rc = ba_setup(ctx, &sub, opt, s->st, ArenaPolicy::OWNED, true, prob))) {  // band order from the FULL problem: identical on every rank
-    delete s;
-    return rc;
-  }
-  {
-    // the recompute-form iteration (ba_large.h) for large systems in gather form; "ba_no_fused" / VSL_BA_NO_FUSED keep
-    // the operator-by-operator chain over stored r / F / E blocks (A/B runs, tests)
-    static const bool env_no_fused = getenv("VSL_BA_NO_FUSED") != nullptr;
-    BaState& st = s->st;
-    st.large_fused = !st.small && st.n_wg > 0 && st.D.nfree > 0 && !ctx->ba_no_fused && !env_no_fused &&
-                     !ctx->ba_schur_atomics && st.n_pairs_cap < ((size_t)1 << 31);
-    if (st.large_fused) {
-      hipLaunchKernelGGL(bal_cam_major_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D.O, st.cam_obs, st.obs_lm, st.obs_uv,
-                         st.cam_lm, st.cam_uv);
-    }
-  }
-  *out = s;
-  return VSL_OK;
-}
-
-extern "C" int vsl_ba_session_destroy(vsl_ba_session* s) {
-  if (!s) return VSL_OK;
-  (void)hipSetDevice(s->ctx->device);
-  (void)hipStreamSynchronize(s->ctx->stream);
-  delete s;
-  return VSL_OK;
-}
-
-extern "C" int vsl_ba_session_dims(const vsl_ba_session* s, int* n, int* n_lms_own, int* n_obs_own, int* n_cams) {
-  if (!s) return VSL_ERR_INVALID;
-  if (n) *n = s->st.D.n;
-  if (n_lms_own) *n_lms_own = s->st.D.L;
-  if (n_obs_own) *n_obs_own = s->st.D.O;
-  if (n_cams) *n_cams = s->st.D.C;
-  return VSL_OK;
-}
-
-// Layout of the reduced camera system inside packB: *s_elems doubles (n * n dense; n * (ld + 1) + 64 in band form,
-// where the cameras were renumbered into band order -- identical on every rank), then rhs / diag H / g_c / cost.
-extern "C" int vsl_ba_session_layout(const vsl_ba_session* s, int64_t* s_elems, int* banded, int* bandwidth) {
-  if (!s) return VSL_ERR_INVALID;
-  if (s_elems) *s_elems = (int64_t)s->st.s_elems;
-  if (banded) *banded = s->st.cyclic ? 2 : (s->st.banded ? 1 : 0);
-  if (bandwidth) *bandwidth = s->st.bw;
-  return VSL_OK;
-}
-
-// Linearise the owned observations at the current parameters (Jacobi-scaled when use_scale) and
-// compute the per-landmark / per-camera column statistics.
-extern "C" int vsl_ba_session_linearize(vsl_ba_session* s, int use_scale) {
-  if (!s) return VSL_ERR_INVALID;
-  vsl_ctx* ctx = s->ctx;
-  VSL_HIP(ctx, hipSetDevice(ctx->device));
-  if (s->st.large_fused)  // nothing is stored per observation: vsl_ba_session_reduce_dev evaluates at the current point
-    return use_scale ? VSL_OK : bal_init_pass(ctx, s->st);
-  int rc = ba_linearize(ctx, s->st, use_scale != 0);
-  if (rc) return rc;
-  return ba_columns(ctx, s->st);
-}
-
-// out_dev[n + 1] = [diag(H_part) | cost_part]   (device pointer; asynchronous on the context's stream)
-extern "C" int vsl_ba_session_hdiag_cost_dev(vsl_ba_session* s, double* out_dev) {
-  if (!s || !out_dev) return VSL_ERR_INVALID;
-  vsl_ctx* ctx = s->ctx;
-  const BaDims& D = s->st.D;
-  hipLaunchKernelGGL(sess_pack_hdiag_kernel, dim3((D.n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, s->st.H, s->st.scalars,
-                     out_dev);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
-}
-
-// Jacobi scaling from the all-reduced diag(H) (cameras) and the owned landmark column norms; scales the
-// stored Jacobian blocks and refreshes the column statistics.
-extern "C" int vsl_ba_session_set_scale_dev(vsl_ba_session* s, const double* hdiag_full_dev) {
-  if (!s || !hdiag_full_dev) return VSL_ERR_INVALID;
-  vsl_ctx* ctx = s->ctx;
-  BaState& st = s->st;
-  const BaDims& D = st.D;
-  const int nmax = std::max(D.n, 3 * D.L);
-  hipLaunchKernelGGL(sess_scale_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, hdiag_full_dev, st.n2l,
-                     st.scale_c, st.scale_l);
-  VSL_CHECK_LAUNCH(ctx);
-  if (st.large_fused) return VSL_OK;
-  hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D.O, st.cam_free, st.obs_cam, st.obs_lm,
-                     st.scale_c, st.scale_l, st.F, st.E);
-  VSL_CHECK_LAUNCH(ctx);
-  return ba_columns(ctx, st);
-}
-
-// packB_dev[n*n + 3n + 2] = [S_part | rhs_part | diag(H_part) | g_c part | cost_part | 0]: Schur complement of the
-// owned landmarks with THEIR damping (diag_l / radius) plus this rank's camera blocks, no camera damping.
-// gmax_l_dev[1] = max |gradient| over the owned landmark columns (unscaled problem).
-extern "C" int vsl_ba_session_reduce_dev(vsl_ba_session* s, double radius, double* packB_dev, double* gmax_l_dev) {
-  if (!s || !packB_dev || !(radius > 0)) return VSL_ERR_INVALID;
-  vsl_ctx* ctx = s->ctx;
-  BaState& st = s->st;
-  const BaDims& D = st.D;
-  const int n = D.n;
-  int rc;
-  if (st.large_fused) {
-    if ((rc = bal_reduce(ctx, st, radius, gmax_l_dev))) return rc;
-  } else {
-    hipLaunchKernelGGL(sess_diag_l_kernel, dim3((3 * D.L + 255) / 256), dim3(256), 0, ctx->stream, D.L, st.n2l, st.grad_l,
-                       st.scale_l, st.diag_l, st.gabs);
-    if (gmax_l_dev) {
-      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.gabs, 3 * D.L, gmax_l_dev, 0, 1);
-    }
-    VSL_CHECK_LAUNCH(ctx);
-    // Schur with landmark damping only: reuse ba_schur with damping, but with a zero camera diagonal
-    VSL_HIP(ctx, hipMemsetAsync(st.diag_c, 0, sizeof(double) * (size_t)(n > 0 ? n : 1), ctx->stream));
-    if ((rc = ba_schur(ctx, st, true, radius, 0, D.L, true, true))) return rc;
-  }
-  if (n > 0 && st.large_fused) {
-    hipLaunchKernelGGL(sess_add_pack_kernel, dim3((D.nfree * 36 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.H, st.g_c,
-                       st.scalars, st.S_eff(), st.rhs, st.ldS, st.banded ? 1 : 0, packB_dev + st.s_elems);
-    VSL_CHECK_LAUNCH(ctx);
-    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(packB_dev, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
-  } else if (n > 0) {
-    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(packB_dev, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(sess_pack_b_kernel, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, st.rhs, st.H, st.g_c,
-                       st.scalars, packB_dev + st.s_elems);
-    VSL_CHECK_LAUNCH(ctx);
-  }
-  return VSL_OK;
-}
-
-// From the all-reduced packB: damp the cameras, solve, back-substitute the owned landmarks, build the
-// candidate, and report packC_dev[8] (see sess_pack_c_kernel).  refresh_diag = 1 after an accepted step
-// (or at the first iteration), 0 when the Jacobian is unchanged (LM reuses its diagonal).
-extern "C" int vsl_ba_session_step_dev(vsl_ba_session* s, const double* packB_full_dev, double radius, int refresh_diag,
-                                       double* packC_dev) {
-  if (!s || !packB_full_dev || !packC_dev || !(radius > 0)) return VSL_ERR_INVALID;
-  vsl_ctx* ctx = s->ctx;
-  BaState& st = s->st;
-  const BaDims& D = st.D;
-  const int n = D.n, nl = 3 * D.L;
-  if (n > 0) {
-    if (!s->solo) VSL_HIP(ctx, hipMemcpyAsync(st.S, packB_full_dev, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(sess_damp_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.s_elems, packB_full_dev,
-                       1.0 / radius, refresh_diag, st.diagc_keep, st.S_eff(), st.ldS, st.rhs,
-                       st.large_fused ? st.flag : (int*)nullptr);
-    VSL_CHECK_LAUNCH(ctx);
-  }
-  int rc;
-  if (st.large_fused) {
-    // everything is enqueued, nothing is read back here: a failed factorisation leaves flag[1] = 0 and numbers nobody
-    // uses (the caller's one read of packC per iteration sees the step as unusable)
-    if ((rc = ba_solve_enqueue(ctx, st, n > 0))) return rc;
-    if ((rc = bal_step(ctx, st, packC_dev))) return rc;  // (packC written by the step's last kernel)
-    return VSL_OK;
-  }
-  bool ok = true;
-  if ((rc = ba_solve(ctx, st, ok))) return rc;
-  const int okflag = ok ? 1 : 0;
-  VSL_HIP(ctx, hipMemcpyAsync(st.flag, &okflag, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ok) {
-    hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                       st.cam_free, st.F, st.E, st.Pinv, st.bl, st.dc, st.dl);
-    if (n > 0) hipLaunchKernelGGL(ba_all_finite_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.dc, st.flag);
-    hipLaunchKernelGGL(ba_all_finite_kernel, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, nl, st.dl, st.flag);
-    hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, st.r,
-                       st.F, st.E, st.dc, st.dl, st.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, 2, 0);
-    hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
-                       st.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, st.partials, st.nb_upd);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_upd, st.scalars, 3, 0);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials + st.nb_upd, st.nb_upd, st.scalars, 4, 0);
-    hipLaunchKernelGGL(sess_cam_norms_kernel, dim3(1), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.dc, st.scale_c,
-                       st.scalars);
-    hipLaunchKernelGGL(ba_cost_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.cand_poses, st.cand_points, st.intr,
-                       st.cam_intr, st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, st.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, 5, 0);
-    VSL_CHECK_LAUNCH(ctx);
-  }
-  hipLaunchKernelGGL(sess_pack_c_kernel, dim3(1), dim3(64), 0, ctx->stream, st.scalars, st.flag, 0, packC_dev);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
-}
-
-// The candidate becomes the current estimate.
-extern "C" int vsl_ba_session_accept(vsl_ba_session* s) {
-  if (!s) return VSL_ERR_INVALID;
-  std::swap(s->st.poses, s->st.cand_poses);
-  std::swap(s->st.points, s->st.cand_points);
-  return VSL_OK;
-}
-
-// poses[7 * n_cams] (all cameras) and points_own[3 * lm_count] (the owned range), host pointers.
-extern "C" int vsl_ba_session_download(vsl_ba_session* s, double* poses, double* points_own) {
-  if (!s) return VSL_ERR_INVALID;
-  vsl_ctx* ctx = s->ctx;
-  if (poses) VSL_HIP(ctx, hipMemcpyAsync(poses, s->st.poses, sizeof(double) * 7 * (size_t)s->st.D.C, hipMemcpyDeviceToHost, ctx->stream));
-  if (points_own) VSL_HIP(ctx, hipMemcpyAsync(points_own, s->st.points, sizeof(double) * 3 * (size_t)s->st.D.L, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VSL_OK;
-}
-
-// =================================================================================================
-// The Levenberg-Marquardt loop over a session, in C++ (host code of the multi-GPU global bundle adjustment).
-// Collectives go through ONE caller-supplied function -- ncclAllReduce on the context's stream for RCCL
-// (include/visnav_amd/bundle_adjustment.h), a host hop for the gloo tests (visual-slam_amd/ba_dist.py) -- so the loop
-// itself does not depend on a communication library.  Policy = the [upstream] Ceres policy of vsl_bundle_adjust.
-// Per iteration: SUM of packB (the packed partial reduced camera system, band form when the cameras order into a band:
-// ~6 MB in the cyclic band form, ~12 MB in the linear one, instead of 287 MB at 1000 cameras), MAX of one scalar after an accepted step, SUM of the 8 doubles of packC.
-namespace {
-__global__ __launch_bounds__(1024) void sess_gmax_c_kernel(int n, const double* __restrict__ g_c, const double* __restrict__ scale_c,
-                                                           const double* __restrict__ cost_in, const double* __restrict__ gl,
-                                                           double* __restrict__ out) {
-  // out[0] = cost (copied), out[1] = max(max_i |g_c[i] / scale_c[i]|, gl[0])
-  __shared__ double sh[1024];
-  double m = 0;
-  for (int i = threadIdx.x; i < n; i += 1024) m = fmax(m, fabs(g_c[i] / scale_c[i]));
-  sh[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[0] = cost_in[0];
-    out[1] = fmax(sh[0], gl[0]);
-  }
-}
-}  // namespace
-
-extern "C" int vsl_ba_session_solve(vsl_ba_session* s, vsl_allreduce_fn allreduce, void* user, int world, int max_iters,
-                                    int verbosity, double* poses_out, double* points_all_out, vsl_ba_summary* summary) {
-  if (!s || world < 1 || (world > 1 && !allreduce)) return VSL_ERR_INVALID;
-  vsl_ctx* ctx = s->ctx;
-  VSL_HIP(ctx, hipSetDevice(ctx->device));
-  BaState& st = s->st;
-  const int n = st.D.n;
-  const size_t elems = st.s_elems, nB = elems + 3 * (size_t)n + 2;
-  const double t_start = now_ms();
-  const size_t n_gather = points_all_out ? 3 * (size_t)s->n_lms_total : 0;  // every rank's landmarks
-  double *bufA, *packB, *packC, *gl, *gather = nullptr;
-  ArenaPlan plan(5);
-  plan.add(bufA, (size_t)n + 1);
-  plan.add(packB, nB);
-  plan.add(packC, 10);
-  plan.add(gl, 1);
-  if (points_all_out) plan.add(gather, n_gather);
-  DevArena arena;
-  if (arena.acquire(ctx, ArenaPolicy::OWNED, plan) != hipSuccess)
-    return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_ba_session_solve: device allocation failed");
-  auto AR = [&](double* buf, size_t count, int op) -> int {
-    if (!allreduce) return VSL_OK;  // a caller that passes a callback at world 1 gets its (trivial) collectives: tests
-    const int rc = allreduce(user, buf, (int64_t)count, op, (void*)ctx->stream);
-    return rc ? vsl_fail(ctx, VSL_ERR_HIP, "all-reduce callback failed (%d)", rc) : VSL_OK;
-  };
-  auto D2H = [&](void* dst, const void* src, size_t bytes) -> int {
-    VSL_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VSL_OK;
-  };
-  int rc;
-  s->solo = !allreduce;
-  vsl_ba_summary sum;
-  memset(&sum, 0, sizeof(sum));
-  VSL_HIP(ctx, hipMemsetAsync(gl, 0, 8, ctx->stream));
-  // iteration 0: cost, Jacobi scaling from the global column norms
-  if ((rc = vsl_ba_session_linearize(s, 0))) return rc;
-  if ((rc = vsl_ba_session_hdiag_cost_dev(s, bufA))) return rc;
-  if ((rc = AR(bufA, (size_t)n + 1, 0))) return rc;
-  if ((rc = vsl_ba_session_set_scale_dev(s, bufA))) return rc;
-  double h2[2];
-  if ((rc = D2H(h2, bufA + n, 8))) return rc;
-  sum.initial_cost = h2[0];
-  LmState lm;
-  double cost = sum.initial_cost, gmax = INFINITY;
-  int it = 0, term, refresh = 1;
-  bool have_h2 = false;
-  double* const hostpack = packC + 8;  // [cost | max |gradient|] behind the 8 doubles of packC: one copy brings both
-  sum.termination = 0;
-  if (verbosity >= 2) lm_print_header(cost);
-  while (true) {
-    if ((rc = vsl_ba_session_reduce_dev(s, lm.radius, packB, gl))) return rc;
-    if ((rc = AR(packB, nB, 0))) return rc;
-    if (refresh) {
-      if ((rc = AR(gl, 1, 1))) return rc;
-      hipLaunchKernelGGL(sess_gmax_c_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, packB + elems + 2 * (size_t)n, st.scale_c,
-                         packB + elems + 3 * (size_t)n, gl, hostpack);
-      VSL_CHECK_LAUNCH(ctx);
-      have_h2 = false;  // (cost, |gradient|) of this linearisation: read together with the step's verdict below --
-                        // ONE host round trip per iteration; a gradient below tolerance is found one step late, and
-                        // that step is dropped
-    }
-    if (it >= max_iters) {
-      if (!have_h2) {
-        if ((rc = D2H(h2, hostpack, 16))) return rc;
-        cost = h2[0];
-        gmax = h2[1];
-      }
-      sum.termination = 0;
-      break;
-    }
-    if ((term = lm_gate(lm, have_h2 ? gmax : INFINITY)) >= 0) { sum.termination = term; break; }
-    it++;
-    if ((rc = vsl_ba_session_step_dev(s, packB, lm.radius, refresh, packC))) return rc;
-    if ((rc = AR(packC, 8, 0))) return rc;
-    double c[10];
-    if ((rc = D2H(c, packC, 80))) return rc;
-    if (!have_h2) {
-      cost = c[8];
-      gmax = c[9];
-      have_h2 = true;
-      if (gmax <= LM_GRADIENT_TOLERANCE) {  // lm_gate's first test, one step late
-        it--;
-        sum.termination = 2;
-        break;
-      }
-    }
-    const double cams_step2 = c[5] / world, cams_x2 = c[6] / world;
-    const double step_norm = sqrt(std::max(c[2] - (world - 1) * cams_step2, 0.0));
-    const double x_norm = sqrt(std::max(c[3] - (world - 1) * cams_x2, 0.0));
-    const double radius_used = lm.radius;
-    LmInfo info;
-    const int verdict = lm_judge(lm, c[0] == 0.0 && c[1] > 0.0, cost, c[4], c[1], step_norm, x_norm, &info);
-    if (verdict >= 0) { sum.termination = verdict; break; }
-    refresh = verdict == LM_ACCEPTED;
-    if (verdict == LM_INVALID) continue;
-    if (verbosity >= 2) lm_print_row(it, c[4], info.cost_change, gmax, step_norm, info.rel, radius_used);
-    if (verdict == LM_ACCEPTED) {
-      if ((rc = vsl_ba_session_accept(s))) return rc;
-      if ((rc = vsl_ba_session_linearize(s, 1))) return rc;  // (the next iteration reads this point's cost from it)
-      sum.successful_steps++;
-    }
-  }
-  sum.iterations = it;
-  sum.final_cost = cost;
-  if (poses_out) {
-    VSL_HIP(ctx, hipMemcpyAsync(poses_out, st.poses, sizeof(double) * 7 * (size_t)st.D.C, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (points_all_out) {
-    // a zero buffer with the own range filled in, summed over the ranks
-    const size_t total = n_gather;
-    VSL_HIP(ctx, hipMemsetAsync(gather, 0, 8 * total, ctx->stream));
-    VSL_HIP(ctx, hipMemcpyAsync(gather + 3 * (size_t)s->lm_first, st.points, sizeof(double) * 3 * (size_t)st.D.L,
-                                hipMemcpyDeviceToDevice, ctx->stream));
-    if ((rc = AR(gather, total, 0))) return rc;
-    VSL_HIP(ctx, hipMemcpyAsync(points_all_out, gather, 8 * total, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  sum.total_ms = now_ms() - t_start;
-  if (verbosity >= 1)
-    fprintf(stderr, "vsl global BA (%d rank%s, %s system, bandwidth %d of %d): iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n",
-            world, world > 1 ? "s" : "", st.cyclic ? "cyclic band" : (st.banded ? "band" : "dense"), st.bw, n, sum.iterations, sum.initial_cost, sum.final_cost,
-            sum.termination, sum.total_ms);
-  if (summary) *summary = sum;
-  return VSL_OK;
-}
-
-// global_bundle_adjustment (include/visnav/loop_closure_utils.h:672-748) over `world` ranks: landmarks are split into
-// contiguous ranges balanced by observation count, rank `rank` owns one; poses / points of `prob` are updated in place
-// on every rank.  world = 1 (allreduce may be null) is the single-GPU session path.
-extern "C" int vsl_global_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, vsl_allreduce_fn allreduce,
-                                        void* user, int rank, int world, vsl_ba_summary* summary) {
-  int rc = ba_validate(ctx, prob);
-  if (rc) return rc;
-  if (!opt || world < 1 || rank < 0 || rank >= world) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_global_bundle_adjust: bad arguments");
-  // contiguous landmark ranges balanced by observation count (the same rule as visual-slam_amd/dist.py landmark_ranges)
-  std::vector<int64_t> csum(prob->n_lms + 1, 0);
-  for (int i = 0; i < prob->n_obs; i++) csum[prob->obs_lm[i] + 1]++;
-  for (int l = 0; l < prob->n_lms; l++) csum[l + 1] += csum[l];
-  std::vector<int> cuts(world + 1, 0);
-  for (int r = 1; r < world; r++) {
-    const double target = (double)csum[prob->n_lms] * r / world;
-    cuts[r] = (int)(std::lower_bound(csum.begin(), csum.end(), target, [](int64_t v, double t) { return (double)v < t; }) - csum.begin());
-    cuts[r] = std::min(std::max(cuts[r], cuts[r - 1]), prob->n_lms);
-  }
-  cuts[world] = prob->n_lms;
-  // Every rank computes ALL ranges, so decisions about them are identical everywhere (a rank that returned alone
-  // would leave the others waiting in the first all-reduce).  A range emptied by the balancing rule (few, heavy
-  // landmarks) is widened to one landmark; fewer landmarks than ranks is an error on every rank alike.
-  if (prob->n_lms < world)
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_global_bundle_adjust: %d landmarks cannot be split over %d ranks (every rank fails alike)",
-                    prob->n_lms, world);
-  for (int r = 1; r < world; r++) cuts[r] = std::min(std::max(cuts[r], cuts[r - 1] + 1), prob->n_lms - (world - r));
-  const int first = cuts[rank], count = cuts[rank + 1] - cuts[rank];
-  vsl_ba_session* s = nullptr;
-  rc = vsl_ba_session_create(ctx, prob, opt, first, count, &s);
-  if (world > 1 && allreduce) {
-    // rank-local failures (allocation, a bad range) are agreed on BEFORE the first data collective: MAX of a flag
-    double* flag = ctx->status_word;  // allocated with the context: never null, so the collective is always entered
-    int frc = 0;
-    const double mine = rc ? 1.0 : 0.0;
-    double any = mine;
-    if (hipMemcpyAsync(flag, &mine, 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) frc = VSL_ERR_HIP;
-    // (a rank that cannot stage the flag still enters the collective with whatever the word holds: it is about to
-    // fail anyway and must not leave the others hanging)
-    const int arc = allreduce(user, flag, 1, 1, (void*)ctx->stream);
-    if (!arc && !frc && hipMemcpyAsync(&any, flag, 8, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess)
-      (void)hipStreamSynchronize(ctx->stream);
-    if (rc || frc || arc || any != 0.0) {
-      if (s) vsl_ba_session_destroy(s);
-      if (rc) return rc;  // this rank's own message is already in place
-      return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_global_bundle_adjust: set-up failed on %s (all ranks leave together)",
-                      (frc || arc) ? "this rank's status exchange" : "another rank");
-    }
-  } else if (rc) {
-    return rc;
-  }
-  rc = vsl_ba_session_solve(s, allreduce, user, world, opt->max_num_iterations, opt->verbosity, prob->poses, prob->points, summary);
-  vsl_ba_session_destroy(s);
-  return rc;
 }
 
 extern "C" int vsl_ctx_last_ba_layout(vsl_ctx* ctx, int64_t* s_elems, int* banded, int* bandwidth) {
@@ -2949,7 +2314,8 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   vsl_ba_problem p2 = *prob;
   p2.intr = intr_io;
   BaState st;
-  if ((rc = ba_setup(ctx, &p2, opt, st, ArenaPolicy::OWNED))) return rc;
+  if ((rc = ba_setup(ctx, &p2, opt, st, BaCaller{BaUse::SINGLE_LINEARIZE}))) return rc;
+  BaStored& sb = st.sb;
   const BaDims& D = st.D;
   const int n = D.n, nt = n + 16, L3 = 3 * D.L;
   double *G, *scale, *n2, *grad, *diag, *Sf, *rhsf, *df, *cand_intr, *Tl;
@@ -2975,8 +2341,8 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   auto linearize = [&](bool scaled) -> int {  // at the CURRENT point; scalars[0] = cost
     hipLaunchKernelGGL(bai_linearize_kernel, dim3(nbo), dim3(256), 0, q, D, st.poses, st.points, st.intr, st.cam_intr, st.cam_free,
                        st.obs_cam, st.obs_lm, st.obs_uv, scaled ? scale : (const double*)nullptr,
-                       scaled ? st.scale_l : (const double*)nullptr, st.r, st.F, st.E, G, st.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials, nbo, scal, 0, 0);
+                       scaled ? st.scale_l : (const double*)nullptr, sb.r, sb.F, sb.E, G, sb.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, sb.partials, nbo, scal, 0, 0);
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   };
@@ -2984,11 +2350,11 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     VSL_HIP(ctx, hipMemsetAsync(n2, 0, 8 * (size_t)nt, q));
     VSL_HIP(ctx, hipMemsetAsync(grad, 0, 8 * (size_t)nt, q));
     VSL_HIP(ctx, hipMemsetAsync(st.n2l, 0, 8 * (size_t)L3, q));
-    VSL_HIP(ctx, hipMemsetAsync(st.grad_l, 0, 8 * (size_t)L3, q));
-    hipLaunchKernelGGL(bai_stats_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, st.r, st.F,
-                       st.E, G, n2, grad, st.n2l, st.grad_l);
-    hipLaunchKernelGGL(bai_diag_gmax_kernel, dim3(1), dim3(256), 0, q, nt, L3, n2, st.n2l, grad, st.grad_l, write_diag ? 1 : 0,
-                       diag, st.diag_l, scal, 1);
+    VSL_HIP(ctx, hipMemsetAsync(sb.grad_l, 0, 8 * (size_t)L3, q));
+    hipLaunchKernelGGL(bai_stats_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, sb.r, sb.F,
+                       sb.E, G, n2, grad, st.n2l, sb.grad_l);
+    hipLaunchKernelGGL(bai_diag_gmax_kernel, dim3(1), dim3(256), 0, q, nt, L3, n2, st.n2l, grad, sb.grad_l, write_diag ? 1 : 0,
+                       diag, sb.diag_l, scal, 1);
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   };
@@ -2999,7 +2365,7 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   hipLaunchKernelGGL(bai_make_scale_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, L3, n2, st.n2l, scale,
                      st.scale_l);
   hipLaunchKernelGGL(bai_apply_scale_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, scale,
-                     st.scale_l, st.F, st.E, G);
+                     st.scale_l, sb.F, sb.E, G);
   if ((rc = stats(true))) return rc;
   if ((rc = read_scalars(ctx, st, h, 2))) return rc;
   double cost = h[0], gmax = h[1];
@@ -3016,13 +2382,13 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     // reduced system: J^T J of the camera side, damping, Schur corrections (camera-camera, then the border)
     VSL_HIP(ctx, hipMemsetAsync(Sf, 0, 8 * (size_t)nt * nt, q));
     VSL_HIP(ctx, hipMemsetAsync(rhsf, 0, 8 * (size_t)nt, q));
-    hipLaunchKernelGGL(bai_hess_kernel, dim3(nbo), dim3(256), 0, q, D, nt, st.cam_free, st.cam_intr, st.obs_cam, st.r, st.F, G, Sf,
+    hipLaunchKernelGGL(bai_hess_kernel, dim3(nbo), dim3(256), 0, q, D, nt, st.cam_free, st.cam_intr, st.obs_cam, sb.r, sb.F, G, Sf,
                        rhsf);
     hipLaunchKernelGGL(bai_damp_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, diag, inv_radius, Sf);
-    hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free, st.r,
-                       st.F, st.E, st.diag_l, inv_radius, 0, D.L, Sf, rhsf, st.Pinv, st.bl, 0, nt);
+    hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free, sb.r,
+                       sb.F, sb.E, sb.diag_l, inv_radius, 0, D.L, Sf, rhsf, st.Pinv, st.bl, 0, nt);
     hipLaunchKernelGGL(bai_border_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, nt, st.lm_start, st.obs_cam, st.cam_free,
-                       st.cam_intr, st.F, st.E, G, st.Pinv, st.bl, Tl, Sf, rhsf);
+                       st.cam_intr, sb.F, sb.E, G, st.Pinv, st.bl, Tl, Sf, rhsf);
     hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, q, st.flag);
     if (nt <= 128) {
       hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, q, nt, Sf, rhsf, df, st.flag + 1);
@@ -3031,19 +2397,19 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
       hipLaunchKernelGGL(ba_negate_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, rhsf, df);
     }
     hipLaunchKernelGGL(bai_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free,
-                       st.cam_intr, st.F, st.E, G, st.Pinv, st.bl, df, st.dl);
-    hipLaunchKernelGGL(ba_all_finite2_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, df, L3, st.dl, st.flag);
-    hipLaunchKernelGGL(bai_model_kernel, dim3(nbo), dim3(256), 0, q, D, st.obs_cam, st.obs_lm, st.cam_free, st.cam_intr, st.r, st.F,
-                       st.E, G, df, st.dl, st.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials, nbo, scal, 2, 0);
+                       st.cam_intr, sb.F, sb.E, G, st.Pinv, st.bl, df, sb.dl);
+    hipLaunchKernelGGL(ba_all_finite2_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, df, L3, sb.dl, st.flag);
+    hipLaunchKernelGGL(bai_model_kernel, dim3(nbo), dim3(256), 0, q, D, st.obs_cam, st.obs_lm, st.cam_free, st.cam_intr, sb.r, sb.F,
+                       sb.E, G, df, sb.dl, sb.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, sb.partials, nbo, scal, 2, 0);
     // candidate point and its cost
-    hipLaunchKernelGGL(ba_update_kernel, dim3(nbu), dim3(256), 0, q, D, st.cam_free, st.poses, st.points, df, st.dl, scale,
-                       st.scale_l, st.cand_poses, st.cand_points, st.partials, nbu);
-    hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, q, st.partials, nbu, scal, 3);
+    hipLaunchKernelGGL(ba_update_kernel, dim3(nbu), dim3(256), 0, q, D, st.cam_free, st.poses, st.points, df, sb.dl, scale,
+                       st.scale_l, st.cand_poses, st.cand_points, sb.partials, nbu);
+    hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, q, sb.partials, nbu, scal, 3);
     hipLaunchKernelGGL(bai_intr_update_kernel, dim3(1), dim3(64), 0, q, n, st.intr, df, scale, cand_intr, scal, 6);
     hipLaunchKernelGGL(ba_cost_kernel, dim3(nbo), dim3(256), 0, q, D, st.cand_poses, st.cand_points, cand_intr, st.cam_intr,
-                       st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, st.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, st.partials, nbo, scal, 5, 0);
+                       st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, sb.partials);
+    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, sb.partials, nbo, scal, 5, 0);
     VSL_CHECK_LAUNCH(ctx);
     int hflag[2];
     VSL_HIP(ctx, hipMemcpyAsync(h, scal, sizeof(double) * 8, hipMemcpyDeviceToHost, q));

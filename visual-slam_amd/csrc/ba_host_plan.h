@@ -98,7 +98,7 @@ inline void host_team_range(int n, int t, int nt, int* a, int* b) {
 
 // ------------------------------------------------------------------------------- layout of the reduced system
 // Dense (ldS = n, offset 0) or, for large systems whose cameras order into a narrow band, LAPACK-style lower band
-// storage (see BaState in ba.hip).  The switches are the caller's diagnostics, spelled out: every rank of a
+// storage (see BaCommon in ba_state.h).  The switches are the caller's diagnostics, spelled out: every rank of a
 // distributed solve must pass the same ones.
 struct BaLayoutSwitches {
   bool allow_band = false;  // the entry point can use band storage at all
@@ -268,7 +268,7 @@ inline int camera_band_order(const vsl_ba_problem* gp, const int* start, bool so
 }
 
 // ------------------------------------------------------------------------------------------------- the plan
-// kernel limits the plan is cut to (ba.hip passes SCH_CMAX, SCH_KMAX, BL_THREADS, BL_LMW)
+// kernel limits the plan is cut to (ba_setup passes SCH_CMAX, SCH_KMAX of ba.hip and, for a session, BL_THREADS, BL_LMW of ba_large.h)
 struct BaPlanLimits {
   int small_max_free_cams;  // the small-system Schur kernel: free cameras ...
   int small_max_lm_free;    // ... and observations of one landmark that hit free cameras
@@ -300,7 +300,7 @@ struct BaHostPlan {
 };
 
 // p: the problem; gp: the problem whose observations define the covisibility graph (the full problem for a session
-// rank; null or p: the problem itself).  lap(name) is called where a set-up phase ends (BaTrace in ba.hip).
+// rank; null or p: the problem itself).  lap(name) is called where a set-up phase ends (BaTrace in ba_state.h).
 template <class Lap>
 BaHostPlan ba_host_plan(const vsl_ba_problem* p, const vsl_ba_problem* gp, const BaLayoutSwitches& sw, const BaPlanLimits& lim,
                         Lap lap, const HostTeamConfig& threads = HostTeamConfig()) {
@@ -440,6 +440,14 @@ BaHostPlan ba_host_plan(const vsl_ba_problem* p, const vsl_ba_problem* gp, const
   }
   P.n_wg = P.wg_lm.empty() ? 0 : (int)P.wg_lm.size() - 1;
   return P;
+}
+
+// The form of a session's iteration, from the plan and the caller's diagnostics alone (so it is known before the device
+// arena is planned): the recompute form (ba_large.h) for large systems in gather form whose landmarks all fit a
+// workgroup's run; the chain over stored r / F / E blocks otherwise (small systems, "ba_no_fused", "ba_schur_atomics",
+// pair lists beyond 32-bit positions, a landmark seen more often than a run has observations).
+inline bool ba_recompute_form(const BaHostPlan& hp, bool no_fused, bool schur_atomics) {
+  return !hp.small && hp.n_wg > 0 && hp.nfree > 0 && !no_fused && !schur_atomics && hp.n_pairs < ((size_t)1 << 31);
 }
 
 // --------------------------------------------------------------------------------- a session's sub-problem
