@@ -5,6 +5,7 @@
 // BowVector / FeatureVector keep DBoW2's container types (std::map), so the callers' code that walks
 // them (inverted file at loop_closure_utils.h:156) is unchanged.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -20,8 +21,17 @@
 #pragma weak vsl_bowdb_append
 #pragma weak vsl_bowdb_score
 #pragma weak vsl_bowdb_query
+// ... and so are the batched keyframe BoW on the frame store and the reserve its device append needs: the headers
+// still link against a library from before them, and frames_bow_available() tells
+#pragma weak vsl_frames_bow_vectors
+#pragma weak vsl_bowdb_reserve
+#pragma weak vsl_bowdb_info
 
 namespace visnav {
+
+inline bool frames_bow_available() {
+  return &vsl_frames_bow_vectors != nullptr && &vsl_bowdb_reserve != nullptr && &vsl_bowdb_info != nullptr;
+}
 
 class ORBVocabularyAmd {
  public:
@@ -94,6 +104,40 @@ class ORBVocabularyAmd {
     for (int i = 0; i < fvn; i++) fv[fn[i]].push_back(ff[i]);
   }
 
+  // compute_bow_vector for the images in slots [first, first + n) of a frame store in one batched device pass
+  // (vsl_frames_bow_vectors): v[i] / fv[i] are what the single-image call gives for the image in slot first + i.  With
+  // db the vectors are also appended to that device database, in slot order, without coming through the host;
+  // db_index[i] = the index of vector i there.  The database must have room (vsl_bowdb_reserve).
+  void compute_bow_vectors(vsl_frames* frames, int first, int n, int num_features, std::vector<DBoW2::BowVector>& v,
+                           std::vector<DBoW2::FeatureVector>& fv, int levelsup = 4, vsl_bowdb* db = nullptr,
+                           int32_t* db_index = nullptr) const {
+    v.assign((size_t)(n > 0 ? n : 0), DBoW2::BowVector());
+    fv.assign((size_t)(n > 0 ? n : 0), DBoW2::FeatureVector());
+    if (!voc_ || n <= 0) return;
+    if (!frames_bow_available()) amd::check(VSL_ERR_INVALID, "compute_bow_vectors: this libvslam_hip.so has no vsl_frames_bow_vectors");
+    size_t cap = 2 * (size_t)num_features + 512;
+    std::vector<uint32_t> ids, fn, ff;
+    std::vector<double> vals;
+    std::vector<int32_t> nnz((size_t)n), fvn((size_t)n), nfeat((size_t)n);
+    int rc = VSL_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+      ids.resize(cap * n), fn.resize(cap * n), ff.resize(cap * n), vals.resize(cap * n);
+      rc = vsl_frames_bow_vectors(amd::ctx(), frames, first, n, voc_, num_features, levelsup, db, db_index, (int)cap, ids.data(),
+                                  vals.data(), nnz.data(), fn.data(), ff.data(), fvn.data(), nfeat.data());
+      size_t need = 0;
+      for (int32_t c : nfeat) need = std::max(need, (size_t)(c > 0 ? c : 0));
+      if (rc != VSL_ERR_CAPACITY || need <= cap) break;  // retainBest keeps every tie: once more with the reported counts
+      cap = need;                                         // (on the error nothing was appended to db)
+    }
+    amd::check(rc, "compute_bow_vectors");
+    for (int i = 0; i < n; i++) {
+      const size_t o = cap * (size_t)i;
+      for (int j = 0; j < nnz[(size_t)i]; j++) v[(size_t)i].emplace_hint(v[(size_t)i].end(), ids[o + j], vals[o + j]);
+      for (int j = 0; j < fvn[(size_t)i]; j++) fv[(size_t)i][fn[o + j]].push_back(ff[o + j]);
+    }
+  }
+  const vsl_voc* handle() const { return voc_; }
+
   // TemplatedVocabulary.h:1199-1203
   double score(const DBoW2::BowVector& a, const DBoW2::BowVector& b) const {
     std::vector<const DBoW2::BowVector*> one(1, &b);
@@ -157,6 +201,7 @@ class KeyframeDatabaseAmd {
 
   // insert_new_kf_to_db: the keyframe's vector is uploaded once
   void insert(const FrameCamId& fcid, const DBoW2::BowVector& v) {
+    if (index_.count(fcid)) return;  // insert_from_frames already appended this keyframe's vector on the device
     if (!db_) amd::check(vsl_bowdb_create(amd::ctx(), 1 << 20, 1024, &db_), "KeyframeDatabaseAmd");
     std::vector<uint32_t> ids;
     std::vector<double> vals;
@@ -166,7 +211,32 @@ class KeyframeDatabaseAmd {
     fcids_.push_back(fcid);
     index_[fcid] = idx;  // a keyframe is inserted once, when it is taken (src/slam.cpp:1219-1258)
   }
+  // insert_new_kf_to_db for keyframes whose images lie in slots [first, first + n) of a frame store: their BowVectors
+  // are computed by the batched call and appended on the device (fcids[i] <-> slot first + i); v / fv receive them for
+  // the callers that keep them per keyframe.  Same stored vectors, same indices as n compute_bow_vector + insert calls.
+  void insert_from_frames(const std::vector<FrameCamId>& fcids, const ORBVocabularyAmd& voc, vsl_frames* frames, int first,
+                          int num_features, std::vector<DBoW2::BowVector>& v, std::vector<DBoW2::FeatureVector>& fv,
+                          int levelsup = 4) {
+    const int n = (int)fcids.size();
+    if (n == 0) return;
+    if (!db_) amd::check(vsl_bowdb_create(amd::ctx(), 1 << 20, 1024, &db_), "KeyframeDatabaseAmd");
+    if (!frames_bow_available()) amd::check(VSL_ERR_INVALID, "KeyframeDatabaseAmd::insert_from_frames: this libvslam_hip.so has no vsl_frames_bow_vectors");
+    // the device append does not grow the database: room for the most these keyframes can bring (vsl_bowdb_reserve
+    // does nothing while there is room and grows geometrically otherwise).  Features beyond the usual bound --
+    // unbounded ties -- come back as a capacity error of the call.
+    int stored = 0;
+    int64_t entries = 0;
+    amd::check(vsl_bowdb_info(db_, &stored, &entries), "vsl_bowdb_info");
+    amd::check(vsl_bowdb_reserve(amd::ctx(), db_, entries + (int64_t)n * (2 * (int64_t)num_features + 512), stored + n), "vsl_bowdb_reserve");
+    std::vector<int32_t> idx((size_t)n, -1);
+    voc.compute_bow_vectors(frames, first, n, num_features, v, fv, levelsup, db_, idx.data());
+    for (int i = 0; i < n; i++) {
+      fcids_.push_back(fcids[(size_t)i]);
+      index_[fcids[(size_t)i]] = idx[(size_t)i];
+    }
+  }
   // detect_loop_candidates' vote: `excluded` = the connected keyframes with covisible weight >= 30
+  // (a keyframe that insert_from_frames stored before its own query is passed in `excluded` by the caller)
   Survivors query_loop(const DBoW2::BowVector& q, const std::vector<FrameCamId>& excluded) const {
     std::vector<int32_t> ex;
     for (const auto& f : excluded) {
@@ -229,6 +299,18 @@ class KeyframeDatabaseAmd {
 inline void compute_bow_vector(const pangolin::ManagedImage<uint8_t>& img_raw, int num_features, const ORBVocabularyAmd* voc,
                                DBoW2::BowVector& bow_vector, DBoW2::FeatureVector& feature_vector) {
   voc->compute_bow_vector(img_raw, num_features, bow_vector, feature_vector, 4);
+}
+
+// The same for the images in slots [first, first + n) of a frame store, in one batched device pass ...
+inline void compute_bow_vector(vsl_frames* frames, int first, int n, int num_features, const ORBVocabularyAmd* voc,
+                               std::vector<DBoW2::BowVector>& bow_vectors, std::vector<DBoW2::FeatureVector>& feature_vectors) {
+  voc->compute_bow_vectors(frames, first, n, num_features, bow_vectors, feature_vectors, 4);
+}
+// ... which also appends them to the device keyframe database as keyframes fcids[0 .. n)
+inline void compute_bow_vector(vsl_frames* frames, int first, int num_features, const ORBVocabularyAmd* voc,
+                               KeyframeDatabaseAmd& db, const std::vector<FrameCamId>& fcids,
+                               std::vector<DBoW2::BowVector>& bow_vectors, std::vector<DBoW2::FeatureVector>& feature_vectors) {
+  db.insert_from_frames(fcids, *voc, frames, first, num_features, bow_vectors, feature_vectors, 4);
 }
 
 }  // namespace visnav

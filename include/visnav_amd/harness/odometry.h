@@ -55,6 +55,8 @@ namespace harness {
 inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
 // the device keyframe database (OdometryOptions::device_place_db) is referenced weakly in the same way (bow.h)
 inline bool device_place_db_available() { return KeyframeDatabaseAmd::available(); }
+// ... and the batched keyframe BoW on the frame store (OdometryOptions::device_bow; bow.h)
+inline bool device_bow_available() { return frames_bow_available(); }
 inline bool landmark_fusion_available() { return &vsl_fuse_search != nullptr && &vsl_map_append_descriptors != nullptr; }
 
 struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.cpp:258-309
@@ -91,6 +93,11 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   // (KeyframeDatabaseAmd: one vsl_bowdb_query per keyframe or lost frame) instead of the host inverted file.  Same
   // candidates, same trajectory (tests/test_place_db_dropin.py); the host inverted file is then never filled.
   bool device_place_db = false;
+  // with fused_tracking and device_place_db: the keyframe's BoW vector comes from vsl_frames_bow_vectors (n = 1) on the
+  // frame-store slot that already holds the left image, and is appended to the device keyframe database there -- no
+  // second upload of the image, no upload of the vector.  Same vectors, same candidates, same trajectory
+  // (tests/test_frames_bow_headless_gpu.py).
+  bool device_bow = false;
   // src/slam.cpp:244-247, :274-294 (the reference's defaults are true / true / true; they need --voc-path)
   bool enable_relocalization = false;
   bool enable_loop_closure = false;
@@ -430,7 +437,19 @@ class Odometry {
       if (orb_voc) {  // src/slam.cpp:1205-1208
         auto tb = Clk::now();
         ImageRef l(img_left);
-        compute_bow_vector(l.img, opt.num_features_per_image, orb_voc, cam_left.bow_vector, cam_left.feature_vector);
+        if (opt.device_bow) {
+          // the left image lies in slot cur_base: the look-ahead frame went into the OTHER slot pair (fused_prefetch), and
+          // cur_base only flips in the next fused_detect, so the slot cannot have been recycled here
+          if (!opt.fused_tracking || !opt.device_place_db || !dev_frames)
+            amd::check(VSL_ERR_INVALID, "device_bow needs fused_tracking and device_place_db");
+          std::vector<DBoW2::BowVector> bv;
+          std::vector<DBoW2::FeatureVector> fv;
+          compute_bow_vector(dev_frames, cur_base, opt.num_features_per_image, orb_voc, place_db, {fcidl}, bv, fv);
+          cam_left.bow_vector = std::move(bv[0]);
+          cam_left.feature_vector = std::move(fv[0]);
+        } else {
+          compute_bow_vector(l.img, opt.num_features_per_image, orb_voc, cam_left.bow_vector, cam_left.feature_vector);
+        }
         bow_vectors[fcidl] = cam_left.bow_vector;
         feature_vectors[fcidl] = cam_left.feature_vector;
         clock.bow_ms += ms(tb, Clk::now());

@@ -312,6 +312,8 @@ inline std::vector<FrameCamId> detect_loop_candidates(const FrameCamId& new_kf_f
   std::vector<FrameCamId> excluded;
   for (const auto& f : graph.at(new_kf_fcid))
     if (recognition_database.contains(f) && new_kf.covisible_weights.at(f) >= 30) excluded.push_back(f);
+  // with the device BoW (OdometryOptions::device_bow) the keyframe's own vector is already stored: it takes no part
+  if (recognition_database.contains(new_kf_fcid)) excluded.push_back(new_kf_fcid);
   const KeyframeDatabaseAmd::Survivors sv = recognition_database.query_loop(new_kf.bow_vector, excluded);
   if (sv.n_sharing == 0) return {};
   return amd::loop_candidates_of_scored(new_kf_fcid, new_kf, graph, min_score, sv.fcids, sv.scores, (size_t)sv.n_sharing, sv.max_count);

@@ -247,7 +247,8 @@ int vsl_ctx_set_tie_eps(vsl_ctx* ctx, double eps);
  *   "pending_desc_max" (default 64) describe launches a frame store queues without a resolve before it resolves them
  *                                   itself (the launch that crosses the limit included)
  *   "select_bucket_cap" (default 128) fullest response bin the selection kernel's counting sort accepts; 0 = always
- *                                   the bitonic network */
+ *                                   the bitonic network
+ *   "frames_bow_chunk" (default 0)  images per pass of vsl_frames_bow_vectors; 0 = as many as its scratch budget holds */
 int vsl_ctx_set_diagnostic(vsl_ctx* ctx, const char* name, int value);
 
 /* matchDescriptors for n_pairs (slot_a, slot_b) pairs; slot_pairs is a HOST
@@ -566,6 +567,31 @@ int vsl_bowdb_query(vsl_ctx* ctx, const vsl_bowdb* db, const uint32_t* q_ids, co
                     uint32_t n_words, const int32_t* exclude_index, int n_exclude, float keep_fraction, int cap,
                     int32_t* cand_index, int32_t* cand_count, double* cand_score, int* n_candidates, int* n_sharing,
                     int* max_count);
+/* Room for at least cap_entries words and cap_vectors vectors in all (the stored vectors are kept); nothing happens
+ * while there is room, and a capacity that has to grow at least doubles.  vsl_bowdb_append grows the database by
+ * itself; vsl_frames_bow_vectors, which appends on the device, does not. */
+int vsl_bowdb_reserve(vsl_ctx* ctx, vsl_bowdb* db, int64_t cap_entries, int cap_vectors);
+
+/* compute_bow_vector for the images in slots [first, first + n) of a frame store, in one batched pass over the
+ * resident images: per image exactly what vsl_compute_bow_vector returns for it with the same num_features and
+ * levelsup (same words and feature-vector pairs in the same order, same bits of every value).
+ *   Host outputs: with cap_per_image > 0, image i's BowVector is written at word_ids / word_vals + i * cap_per_image
+ * (nnz[i] entries) and its FeatureVector at fv_node / fv_feat + i * cap_per_image (fv_n[i] entries); with
+ * cap_per_image == 0 nothing but n_features / db_index is written (the five arrays and the two counts may be NULL).
+ * n_features[i] (may be NULL) = the number of ORB features of image i, also when the call fails for capacity.
+ *   Database: with db != NULL the n BowVectors are appended on the device in slot order (an empty vector is appended as
+ * an empty vector, as vsl_bowdb_append does) and db_index[i] (may be NULL) = the index vsl_bowdb_append would have
+ * returned.  The append is all or nothing, and it does NOT grow the database: see vsl_bowdb_reserve.
+ *   VSL_ERR_INVALID: images smaller than 64 x 64, a range outside the store, voc == NULL, num_features < 1.
+ *   VSL_ERR_CAPACITY: an image has more features than cap_per_image (> 0) or than one transform takes (8192), or db
+ * has no room for n more vectors and all their words.  On every error the database is unchanged: its counters do
+ * not move, so every query and every later append sees the vectors it held before.  (Device bytes BEHIND the stored
+ * entries and offsets -- unused capacity -- may have been written by the passes before the error.)
+ *   The range is processed in passes of a bounded number of images; the result does not depend on the
+ * passes. */
+int vsl_frames_bow_vectors(vsl_ctx* ctx, vsl_frames* f, int first, int n, const vsl_voc* voc, int num_features, int levelsup,
+                           vsl_bowdb* db, int32_t* db_index, int cap_per_image, uint32_t* word_ids, double* word_vals,
+                           int32_t* nnz, uint32_t* fv_node, uint32_t* fv_feat, int32_t* fv_n, int32_t* n_features);
 
 /* Bit-order converters of include/visnav/converter.h:23-33 and :50-61
  * (bitset<256> word layout <-> 32-byte MSB-first row).  Pure host helpers. */

@@ -618,6 +618,10 @@ class BowDatabase:
                                                  len(ids), C.byref(idx)))
         return idx.value
 
+    def reserve(self, cap_entries, cap_vectors):
+        """Room for cap_entries words and cap_vectors vectors in all (Frames.bow_vectors does not grow the database)."""
+        self.ctx._ck(self.ctx.L.vsl_bowdb_reserve(self.ctx.h, self.h, C.c_int64(int(cap_entries)), int(cap_vectors)))
+
     def info(self):
         n, e = C.c_int32(), C.c_int64()
         self.ctx._ck(self.ctx.L.vsl_bowdb_info(self.h, C.byref(n), C.byref(e)))
@@ -801,6 +805,37 @@ class Frames:
         c = np.zeros(max(n_pairs, 1), np.int32)
         self.ctx._ck(self.ctx.L.vsl_frames_download_inlier_counts(self.ctx.h, self.h, int(n_pairs), c.ctypes.data_as(i32p)))
         return c[:n_pairs].copy()
+
+    def bow_vectors(self, first, n, voc, num_features=1500, levelsup=4, db=None, cap_per_image=None, host_outputs=True):
+        """vsl_frames_bow_vectors: compute_bow_vector for the resident images [first, first + n) in one batched call.
+        Returns a list of per-image (ids, vals, fv_node, fv_feat), exactly what Vocabulary.compute_bow_vector gives for
+        each image; with `db` (a BowDatabase with room: BowDatabase.reserve) the vectors are also appended on the
+        device and the result is (list, indices).  host_outputs=False downloads nothing (the list is None).  An image
+        with more features than the first buffers hold is done once more with the count the call reports."""
+        L, ctx = self.ctx.L, self.ctx
+        n = int(n)
+        cap = (2 * num_features + 512 if cap_per_image is None else int(cap_per_image)) if host_outputs else 0
+        nfeat = np.zeros(max(n, 1), np.int32)
+        index = np.zeros(max(n, 1), np.int32)
+        for attempt in range(2):
+            m = max(n * cap, 1)
+            ids, vals = np.zeros(m, np.uint32), np.zeros(m, np.float64)
+            fn, ff = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+            nnz, fvn = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+            rc = L.vsl_frames_bow_vectors(ctx.h, self.h, int(first), n, voc.h if voc is not None else None, int(num_features),
+                                          int(levelsup), db.h if db is not None else None, index.ctypes.data_as(i32p), cap,
+                                          ids.ctypes.data_as(u32p), vals.ctypes.data_as(f64p), nnz.ctypes.data_as(i32p),
+                                          fn.ctypes.data_as(u32p), ff.ctypes.data_as(u32p), fvn.ctypes.data_as(i32p),
+                                          nfeat.ctypes.data_as(i32p))
+            if rc != -4 or cap == 0 or cap_per_image is not None or nfeat[:n].max(initial=0) <= cap:
+                break
+            cap = int(nfeat[:n].max())   # VSL_ERR_CAPACITY: n_features = the capacities that suffice
+        ctx._ck(rc)
+        out = None
+        if host_outputs:
+            out = [(ids[i * cap:i * cap + nnz[i]].copy(), vals[i * cap:i * cap + nnz[i]].copy(),
+                    fn[i * cap:i * cap + fvn[i]].copy(), ff[i * cap:i * cap + fvn[i]].copy()) for i in range(n)]
+        return (out, index[:n].copy()) if db is not None else out
 
     def candidate_counts(self, n_images):
         nc = np.zeros(max(n_images, 1), np.int32)

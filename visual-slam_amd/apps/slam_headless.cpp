@@ -5,7 +5,7 @@
 // libvslam_hip.so; there is no CPU fallback.
 //
 //   slam_headless --dataset-path <dir with cam0/ cam1/ ...> --cam-calib <calib.json>
-//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N]
+//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -53,6 +53,7 @@ int main(int argc, char** argv) {
     else if (a == "--fused") opt.fused_tracking = true;
     else if (a == "--device-stereo") opt.device_stereo = true;  // with --fused: epipolar inliers + triangulation on the device
     else if (a == "--device-place-db") opt.device_place_db = true;  // loop / relocalisation candidates by one device query per keyframe
+    else if (a == "--device-bow") opt.device_bow = true;  // with --fused --device-place-db: keyframe BoW on the resident slot, appended on the device
     else if (a == "--no-lookahead") lookahead = false;
     else if (a == "--replicas") replicas = std::atoi(need("--replicas").c_str());
     else if (a == "--kf-min-inliers") opt.new_kf_min_inliers = std::atoi(need("--kf-min-inliers").c_str());
@@ -94,6 +95,14 @@ int main(int argc, char** argv) {
   }
   if (opt.device_place_db && !device_place_db_available()) {
     std::fprintf(stderr, "--device-place-db: this build's C ABI has no device keyframe database (vsl_bowdb_query)\n");
+    return 2;
+  }
+  if (opt.device_bow && (!opt.fused_tracking || !opt.device_place_db)) {
+    std::fprintf(stderr, "--device-bow needs --fused and --device-place-db (it runs on the frame store's slot and appends to the device database)\n");
+    return 2;
+  }
+  if (opt.device_bow && !device_bow_available()) {
+    std::fprintf(stderr, "--device-bow: this build's C ABI has no batched keyframe BoW (vsl_frames_bow_vectors)\n");
     return 2;
   }
   if (opt.landmark_fusion && !landmark_fusion_available()) {
@@ -286,6 +295,7 @@ int main(int argc, char** argv) {
       n_frames, n_kf, replicas, replicas_agree ? "true" : "false", replicas * n_frames / run_s, 1e3 * run_s / n_frames, decode_s, ate, n_assoc, odo.landmarks.size(), n_active,
       opt.async_ba ? "true" : "false", opt.fused_tracking ? "true" : "false", opt.device_stereo ? "true" : "false", opt.device_place_db ? "true" : "false", c.detect_ms, c.stereo_match_ms, c.project_match_ms, c.localize_ms, c.map_ms, c.ba_ms, c.bow_ms, odo.loop_ms, odo.gba_ms, c.ba_runs, odo.bow_vectors.size(),
       odo.n_tracking_lost, odo.n_relocalized, odo.n_loops_closed, odo.n_global_ba, reloc_ok, reloc_err_m);
+  if (opt.device_bow) std::printf(", \"device_bow\": true");  // the line is unchanged without the option
   if (opt.landmark_fusion)  // the line is unchanged without the option
     std::printf(", \"landmark_fusion\": {\"added\": %d, \"merged\": %d, \"conflicts\": %d, \"refused\": %d}", odo.fusion_total.added,
                 odo.fusion_total.merged, odo.fusion_total.conflicts, odo.fusion_total.refused);

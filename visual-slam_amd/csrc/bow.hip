@@ -213,13 +213,13 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
 // Keys: (id << shift) | feature index, all-ones = padding (sorts last); K = uint32_t when that fits, else 64 bits.
 // SMALL (<= 2048 features, the reference passes <= 1500): weights and word values live in LDS too; otherwise they stay
 // in global memory (the LDS belongs to the keys).
+// The body is shared by the single-image kernel (blockIdx.x picks the sort) and the batched one (blockIdx.y = image).
 template <int NCAP, class K, bool SMALL>
-__global__ __launch_bounds__(1024) void bow_assemble_kernel(const uint32_t* __restrict__ f_word,
-                                                            const double* __restrict__ f_w,
-                                                            const uint32_t* __restrict__ f_node, int n, int shift,
-                                                            uint32_t* __restrict__ word_ids, double* __restrict__ word_vals,
-                                                            int32_t* __restrict__ counts, uint32_t* __restrict__ fv_node,
-                                                            uint32_t* __restrict__ fv_feat) {
+__device__ __forceinline__ void bow_assemble_body(const uint32_t* __restrict__ f_word, const double* __restrict__ f_w,
+                                                  const uint32_t* __restrict__ f_node, int n, int shift,
+                                                  uint32_t* __restrict__ word_ids, double* __restrict__ word_vals,
+                                                  int32_t* __restrict__ counts, uint32_t* __restrict__ fv_node,
+                                                  uint32_t* __restrict__ fv_feat) {
   __shared__ __attribute__((aligned(16))) K keys[NCAP];
   __shared__ __attribute__((aligned(16))) double w_lds[SMALL ? NCAP : 2];     // the features' weights
   __shared__ __attribute__((aligned(16))) double vals_lds[SMALL ? NCAP : 2];  // the words' values before normalisation
@@ -316,6 +316,55 @@ __global__ __launch_bounds__(1024) void bow_assemble_kernel(const uint32_t* __re
   __syncthreads();
   const double norm = norm_s;
   for (int i = tid; i < uniq; i += 1024) word_vals[i] = norm > 0.0 ? vals_s[i] / norm : vals_s[i];
+}
+
+template <int NCAP, class K, bool SMALL>
+__global__ __launch_bounds__(1024) void bow_assemble_kernel(const uint32_t* __restrict__ f_word,
+                                                            const double* __restrict__ f_w,
+                                                            const uint32_t* __restrict__ f_node, int n, int shift,
+                                                            uint32_t* __restrict__ word_ids, double* __restrict__ word_vals,
+                                                            int32_t* __restrict__ counts, uint32_t* __restrict__ fv_node,
+                                                            uint32_t* __restrict__ fv_feat) {
+  bow_assemble_body<NCAP, K, SMALL>(f_word, f_w, f_node, n, shift, word_ids, word_vals, counts, fv_node, fv_feat);
+}
+
+// K8b for the images of a frame-store pass (vsl_frames_bow_vectors): workgroups (sort, image); image i owns rows
+// [feat_base, feat_base + n_feat) of every per-feature array (feat_base is a multiple of 4: the 16-byte reads of the
+// norm stay aligned) and counts[4 i ..].  The key shift is the one vsl_bow_transform takes for n_feat features.
+template <int NCAP, class K, bool SMALL>
+__global__ __launch_bounds__(1024) void bow_assemble_batch_kernel(const VslOrbImgSeg* __restrict__ seg, const uint32_t* __restrict__ f_word,
+                                                                  const double* __restrict__ f_w, const uint32_t* __restrict__ f_node,
+                                                                  uint32_t* __restrict__ word_ids, double* __restrict__ word_vals,
+                                                                  int32_t* __restrict__ counts, uint32_t* __restrict__ fv_node,
+                                                                  uint32_t* __restrict__ fv_feat) {
+  const int img = blockIdx.y;
+  const size_t base = (size_t)seg[img].feat_base;
+  const int n = seg[img].n_feat;
+  int shift = 32;
+  if (sizeof(K) == 4) {
+    shift = 11;
+    while ((1 << shift) < n) shift++;
+  }
+  bow_assemble_body<NCAP, K, SMALL>(f_word + base, f_w + base, f_node + base, n, shift, word_ids + base, word_vals + base,
+                                    counts + 4 * (size_t)img, fv_node + base, fv_feat + base);
+}
+
+// The BowVectors of a pass into the database, in image order: workgroup i copies vector i behind the vectors before it
+// (entry_base = the entries stored before the pass, off_first = the offset slot of the pass's first vector).
+__global__ __launch_bounds__(256) void bowdb_append_batch_kernel(const VslOrbImgSeg* __restrict__ seg, const uint32_t* __restrict__ word_ids,
+                                                                 const double* __restrict__ word_vals, const int32_t* __restrict__ counts,
+                                                                 int64_t entry_base, uint32_t* __restrict__ db_ids,
+                                                                 double* __restrict__ db_vals, int64_t* __restrict__ off_first) {
+  const int img = blockIdx.x;
+  int64_t dst = entry_base;
+  for (int j = 0; j < img; j++) dst += counts[4 * j];  // uniform: scalar loads
+  const int nnz = counts[4 * img];
+  const size_t src = (size_t)seg[img].feat_base;
+  for (int t = threadIdx.x; t < nnz; t += 256) {
+    db_ids[dst + t] = word_ids[src + t];
+    db_vals[dst + t] = word_vals[src + t];
+  }
+  if (threadIdx.x == 0) off_first[img + 1] = dst + nnz;
 }
 
 // K9: L1 score (ScoringObject.cpp:23-68) of the query against candidates in CSR form; candidate m is vector
@@ -1213,5 +1262,209 @@ extern "C" int vsl_bowdb_query(vsl_ctx* ctx, const vsl_bowdb* db, const uint32_t
     cand_score[i] = hr[i].score;
   }
   *n_candidates = n_surv;
+  return VSL_OK;
+}
+
+extern "C" int vsl_bowdb_reserve(vsl_ctx* ctx, vsl_bowdb* db, int64_t cap_entries, int cap_vectors) {
+  if (!ctx || !db || cap_entries < 0 || cap_vectors < 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_bowdb_reserve: bad arguments");
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  int rc;
+  // geometric, like vsl_bowdb_append: a caller that asks for a little more before every append does not reallocate every time
+  if (cap_entries > db->cap_entries) {
+    const int64_t cap = std::max<int64_t>(2 * db->cap_entries, cap_entries);
+    if ((rc = grow_dev(ctx, &db->ids, (size_t)db->n_entries, (size_t)cap)) || (rc = grow_dev(ctx, &db->vals, (size_t)db->n_entries, (size_t)cap)))
+      return rc;
+    db->cap_entries = cap;
+  }
+  if (cap_vectors > db->cap_vecs) {
+    const int cap = std::max(2 * db->cap_vecs, cap_vectors);
+    if ((rc = grow_dev(ctx, &db->off, (size_t)db->n_vecs + 1, (size_t)cap + 1))) return rc;
+    db->cap_vecs = cap;
+  }
+  return VSL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ vsl_frames_bow_vectors
+// compute_bow_vector + database append for a range of resident images.  A pass of k images is
+//   ORB stages of all k images (orb.hip) -> [sync: keypoint counts + angles] -> libm cos / sin on the host -> describe
+//   -> ONE descent over the pass's dense descriptor array (bow_descend_kernel as it is) -> assembly, workgroups
+//   (sort, image) -> [sync: counts, and the vectors when the caller wants them] -> device copy into the database.
+// The number of launches and synchronisations of a pass does not depend on k.
+#define FRAMES_BOW_SCRATCH_BUDGET ((size_t)1 << 30)  // device scratch of a pass
+#define FRAMES_BOW_MAX_PASS 256                      // images per pass at most
+
+namespace {
+// per-image device bytes of the transform stage: f_w | vals (8) and f_word | f_node | ids | fv_node | fv_feat (4) per row, counts
+size_t frames_bow_transform_bytes(size_t rows, size_t k) { return 36 * rows + 16 * k + 8 * 256; }
+}  // namespace
+
+extern "C" int vsl_frames_bow_vectors(vsl_ctx* ctx, vsl_frames* f, int first, int n, const vsl_voc* voc, int num_features,
+                                      int levelsup, vsl_bowdb* db, int32_t* db_index, int cap_per_image, uint32_t* word_ids,
+                                      double* word_vals, int32_t* nnz, uint32_t* fv_node, uint32_t* fv_feat, int32_t* fv_n,
+                                      int32_t* n_features) {
+  if (!ctx || !f) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_frames_bow_vectors: null context or frame store");
+  if (!voc) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_frames_bow_vectors: voc is NULL");
+  if (f->w < 64 || f->h < 64)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_frames_bow_vectors: the store's images are %d x %d (w, h >= 64 required)", f->w, f->h);
+  if (first < 0 || n < 0 || first > f->max_images || n > f->max_images - first)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_frames_bow_vectors: bad slot range [%d, %d) of %d", first, first + n, f->max_images);
+  if (num_features < 1 || cap_per_image < 0 ||
+      (cap_per_image > 0 && n > 0 && (!word_ids || !word_vals || !nnz || !fv_node || !fv_feat || !fv_n)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_frames_bow_vectors: bad arguments (num_features >= 1; all outputs with cap_per_image > 0)");
+  if (f->device != ctx->device || voc->device != ctx->device || (db && db->device != ctx->device))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_frames_bow_vectors: store, vocabulary and database must live on the context's device");
+  if (n == 0) return VSL_OK;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  // pass size from the scratch budget (or the diagnostic)
+  const size_t feat_rows = (BOW_MAX_N + 3) & ~3;
+  size_t dev1 = 0, pin1 = 0;
+  vsl_orb_batch_bytes(f->w, f->h, num_features, 1, BOW_MAX_N, &dev1, &pin1);
+  const size_t per_image = dev1 + frames_bow_transform_bytes(feat_rows, 1);
+  int pass = (int)std::min<size_t>(FRAMES_BOW_MAX_PASS, std::max<size_t>(1, FRAMES_BOW_SCRATCH_BUDGET / per_image));
+  if (ctx->frames_bow_chunk > 0) pass = std::min(ctx->frames_bow_chunk, FRAMES_BOW_MAX_PASS);
+  pass = std::min(pass, n);
+  size_t orb_dev = 0, orb_pin = 0;
+  vsl_orb_batch_bytes(f->w, f->h, num_features, pass, BOW_MAX_N, &orb_dev, &orb_pin);
+  const size_t rows_cap = feat_rows * (size_t)pass;
+  void* d = nullptr;
+  int rc = vsl_ctx_dscratch(ctx, orb_dev + frames_bow_transform_bytes(rows_cap, (size_t)pass), &d);
+  if (rc) return rc;
+  void* hp = nullptr;
+  if ((rc = vsl_ctx_hpinned(ctx, orb_pin + 16 * (size_t)pass + 20 * rows_cap + 256, &hp))) return rc;
+  // transform arrays behind the ORB scratch (orb_dev is a multiple of 256)
+  double* f_w = (double*)((uint8_t*)d + orb_dev);
+  double* vals = f_w + rows_cap;
+  uint32_t* f_word = (uint32_t*)(vals + rows_cap);
+  uint32_t* f_node = f_word + rows_cap;
+  uint32_t* ids = f_node + rows_cap;
+  uint32_t* fvn = ids + rows_cap;
+  uint32_t* fvf = fvn + rows_cap;
+  int32_t* counts = (int32_t*)(fvf + rows_cap);  // [pass][4]: nnz, fv_n
+  // pinned results behind the ORB staging: counts | vals | ids | fv_node | fv_feat
+  int32_t* h_counts = (int32_t*)((uint8_t*)hp + orb_pin);
+  double* h_vals = (double*)(h_counts + 4 * (size_t)pass);
+  uint32_t* h_ids = (uint32_t*)(h_vals + rows_cap);
+  uint32_t* h_fvn = h_ids + rows_cap;
+  uint32_t* h_fvf = h_fvn + rows_cap;
+
+  hipStream_t st = ctx->stream;
+  // a capacity error does not end the walk: the remaining passes still count their features (n_features is filled)
+  bool failed = false;
+  std::string why;
+  auto capacity = [&](const std::string& msg) {
+    if (!failed) why = msg;
+    failed = true;
+  };
+  if (db && n > db->cap_vecs - db->n_vecs)
+    capacity("the database holds " + std::to_string(db->n_vecs) + " of " + std::to_string(db->cap_vecs) + " vectors, no room for " +
+             std::to_string(n) + " more (vsl_bowdb_reserve)");
+  int64_t new_entries = 0;
+  int new_max_nnz = 0;
+  for (int done = 0; done < n; done += pass) {
+    const int k = std::min(pass, n - done);
+    VslOrbBatch b;
+    b.images = f->images + (size_t)(first + done) * f->w * f->h;
+    b.image_stride = (size_t)f->w * f->h;
+    b.w = f->w;
+    b.h = f->h;
+    b.k = k;
+    b.nfeatures = num_features;
+    b.max_feat = BOW_MAX_N;
+    b.scratch = d;
+    b.pinned = hp;
+    // a shorter last pass carves the same allocations for fewer images
+    if ((rc = vsl_orb_batch_count(ctx, b))) return rc;
+    int max_n = 0;
+    for (int i = 0; i < k; i++) {
+      const int nf = b.n_feat[i];
+      if (n_features) n_features[done + i] = nf;
+      max_n = std::max(max_n, nf);
+      if (nf > BOW_MAX_N)
+        capacity("image " + std::to_string(first + done + i) + " has " + std::to_string(nf) + " features, at most " +
+                 std::to_string(BOW_MAX_N) + " descriptors per transform");
+      else if (cap_per_image > 0 && nf > cap_per_image)
+        capacity("image " + std::to_string(first + done + i) + " has " + std::to_string(nf) + " features, output capacity " +
+                 std::to_string(cap_per_image));
+    }
+    if (failed) continue;
+    if ((rc = vsl_orb_batch_describe(ctx, b))) return rc;
+    if (voc->n_nodes <= 1) {  // empty(): TemplatedVocabulary.h:1135
+      VSL_HIP(ctx, hipMemsetAsync(counts, 0, 16 * (size_t)k, st));
+    } else {
+      VslStage stage(ctx, VSL_STAGE_BOW_TRANSFORM);
+      if (b.n_rows > 0) {
+        const int G = voc->group;
+        const dim3 grid((unsigned)(((size_t)b.n_rows * G + 255) / 256));
+#define BOW_DESCEND(GG)                                                                                                              \
+  hipLaunchKernelGGL(bow_descend_kernel<GG>, grid, dim3(256), 0, st, (const uint4*)b.desc, b.n_rows, voc->sdesc, voc->sinfo, voc->snode, \
+                     voc->sword, voc->sweight, voc->root_nc, voc->L, levelsup, f_word, f_w, f_node)
+        if (G == 16) BOW_DESCEND(16);
+        else if (G == 32) BOW_DESCEND(32);
+        else BOW_DESCEND(64);
+#undef BOW_DESCEND
+      }
+      int shift = 11;
+      while ((1 << shift) < max_n) shift++;
+      const uint64_t max_id = (uint64_t)std::max(voc->n_nodes, voc->n_words);
+      const bool k32 = !ctx->bow_keys64 && max_id + 2 <= (1ull << (32 - shift));
+#define BOW_ASSEMBLE_BATCH(CAP, KT)                                                                                                  \
+  hipLaunchKernelGGL((bow_assemble_batch_kernel<CAP, KT, (CAP <= 2048)>), dim3(2, k), dim3(1024), 0, st, b.seg, f_word, f_w, f_node, ids, \
+                     vals, counts, fvn, fvf)
+      if (max_n <= 2048) {
+        if (k32) BOW_ASSEMBLE_BATCH(2048, uint32_t);
+        else BOW_ASSEMBLE_BATCH(2048, unsigned long long);
+      } else {
+        if (k32) BOW_ASSEMBLE_BATCH(BOW_MAX_N, uint32_t);
+        else BOW_ASSEMBLE_BATCH(BOW_MAX_N, unsigned long long);
+      }
+#undef BOW_ASSEMBLE_BATCH
+      VSL_CHECK_LAUNCH(ctx);
+    }
+    VSL_HIP(ctx, hipMemcpyAsync(h_counts, counts, 16 * (size_t)k, hipMemcpyDeviceToHost, st));
+    if (cap_per_image > 0 && b.n_rows > 0) {
+      const size_t R = (size_t)b.n_rows;
+      VSL_HIP(ctx, hipMemcpyAsync(h_vals, vals, 8 * R, hipMemcpyDeviceToHost, st));
+      VSL_HIP(ctx, hipMemcpyAsync(h_ids, ids, 4 * R, hipMemcpyDeviceToHost, st));
+      VSL_HIP(ctx, hipMemcpyAsync(h_fvn, fvn, 4 * R, hipMemcpyDeviceToHost, st));
+      VSL_HIP(ctx, hipMemcpyAsync(h_fvf, fvf, 4 * R, hipMemcpyDeviceToHost, st));
+    }
+    VSL_HIP(ctx, hipStreamSynchronize(st));
+    int64_t pass_entries = 0;
+    for (int i = 0; i < k; i++) {
+      const int c0 = h_counts[4 * i], c1 = h_counts[4 * i + 1];
+      pass_entries += c0;
+      new_max_nnz = std::max(new_max_nnz, c0);
+      if (cap_per_image > 0) {
+        const size_t src = (size_t)b.feat_base[i], dst = (size_t)(done + i) * cap_per_image;
+        nnz[done + i] = c0;
+        fv_n[done + i] = c1;
+        memcpy(word_ids + dst, h_ids + src, 4 * (size_t)c0);
+        memcpy(word_vals + dst, h_vals + src, 8 * (size_t)c0);
+        memcpy(fv_node + dst, h_fvn + src, 4 * (size_t)c1);
+        memcpy(fv_feat + dst, h_fvf + src, 4 * (size_t)c1);
+      }
+    }
+    if (db) {
+      // the vectors land behind the stored ones; they belong to the database only once its host counters move (below)
+      if (db->n_entries + new_entries + pass_entries > db->cap_entries) {
+        capacity("the database holds " + std::to_string(db->n_entries) + " of " + std::to_string(db->cap_entries) +
+                 " words, no room for the new vectors (vsl_bowdb_reserve)");
+        continue;
+      }
+      hipLaunchKernelGGL(bowdb_append_batch_kernel, dim3(k), dim3(256), 0, st, b.seg, (const uint32_t*)ids, (const double*)vals,
+                         (const int32_t*)counts, db->n_entries + new_entries, db->ids, db->vals, db->off + db->n_vecs + done);
+      VSL_CHECK_LAUNCH(ctx);
+      new_entries += pass_entries;
+    }
+  }
+  VSL_HIP(ctx, hipStreamSynchronize(st));  // the next call may move the scratch
+  if (failed) return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_frames_bow_vectors: %s", why.c_str());
+  if (db) {
+    if (db_index)
+      for (int i = 0; i < n; i++) db_index[i] = db->n_vecs + i;
+    db->n_entries += new_entries;
+    db->n_vecs += n;
+    db->max_nnz = std::max(db->max_nnz, new_max_nnz);
+  }
   return VSL_OK;
 }

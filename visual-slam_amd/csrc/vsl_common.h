@@ -99,6 +99,7 @@ struct vsl_ctx {
   int vo_chain_ticket = 0;              // diagnostic: vsl_map_track draws chain positions from the atomic ticket at every map size
   int pending_desc_max = 64;            // unresolved describe launches a frame store queues before it settles them itself (diagnostic: tests lower it)
   int exact_list_cap = VSL_EXACT_CAP;   // diagnostic: per-image exact-rounding list entries the describe kernels use (tests shrink it to hit the overflow fallback)
+  int frames_bow_chunk = 0;             // diagnostic: images per pass of vsl_frames_bow_vectors (0: as many as the scratch budget holds)
   int k1_list_cap = -1;                // diagnostic: per-wave LDS candidate slots in K1 (tests shrink it to hit the overflow path)
 };
 
@@ -223,3 +224,35 @@ __host__ __device__ inline float vsl_ordered_to_float(int32_t i) {
   memcpy(&f, &j, 4);
   return f;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Batched ORB front end on resident images (orb.hip), driven pass by pass by vsl_frames_bow_vectors (bow.hip).
+// Per-image keypoint segments and the compact feature numbering of a pass, one 128-byte record per image on the device.
+struct VslOrbImgSeg {
+  int32_t seg_base[8], seg_cap[8];  // keypoint slots of each pyramid level inside the image's slot range
+  int32_t feat_off[8];              // first feature of the level, relative to feat_base
+  int32_t feat_base, n_feat;        // the image's features are rows [feat_base, feat_base + n_feat) of the pass's descriptor array
+  int32_t pad[6];
+};
+struct VslOrbBatch {
+  // in
+  const uint8_t* images = nullptr;  // k dense w x h images, image_stride bytes apart (device)
+  size_t image_stride = 0;
+  int w = 0, h = 0, k = 0, nfeatures = 0, max_feat = 0;  // max_feat: most features of an image that can be described
+  void* scratch = nullptr;          // device, pinned: the sizes vsl_orb_batch_bytes reports
+  void* pinned = nullptr;
+  // out (count): features per image and their place in the pass's compact arrays (feat_base is a multiple of 4)
+  std::vector<int32_t> n_feat, feat_base;
+  int n_rows = 0;                   // rows of the compact arrays = feat_base + n_feat of the last image, rounded up to 4
+  // out (describe): valid in stream order
+  const uint8_t* desc = nullptr;        // [n_rows][32]
+  const VslOrbImgSeg* seg = nullptr;    // [k]
+  // internal
+  std::vector<int32_t> full;        // [k][8] keypoints per level
+  std::vector<uint8_t> overflow;    // [k] more ties than the first segments hold
+};
+void vsl_orb_batch_bytes(int w, int h, int nfeatures, int k, int max_feat, size_t* device_bytes, size_t* pinned_bytes);
+// stages up to the keypoint angles of all k images, ONE stream synchronisation: n_feat / feat_base / n_rows
+int vsl_orb_batch_count(vsl_ctx* ctx, VslOrbBatch& b);
+// second emit of the overflowing images (one more synchronisation, only then), libm cos / sin of all angles, describe launch
+int vsl_orb_batch_describe(vsl_ctx* ctx, VslOrbBatch& b);
