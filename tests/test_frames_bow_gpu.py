@@ -327,3 +327,25 @@ def test_determinism_same_context_and_fresh_context(ctx, vsl, synth, ref, tmp_pa
             if c is not ctx:
                 c.close()
     assert runs[0] == runs[1] == runs[2]
+
+
+# 8 ---------------------------------------------------------------------------------------------------------------------
+def test_single_image_call_between_two_batched_calls_shares_the_scratch(ctx, orc, vsl, voc_pair, ref):
+    """Both entry points carve the context's one scratch and one pinned buffer, each in its own way: a single-image
+    call of another size between two batched calls leaves nothing behind that the second one sees."""
+    voc, _ = voc_pair
+    w, h, nf = 161, 123, 300
+    imgs, single, counts = ref[(w, h, nf)]
+    small = R.blocky_noise(96, 80, 9680)
+    f = _store(vsl, ctx, imgs)
+    try:
+        first = _abi(ctx, f, 0, 5, voc, nf, cap=max(counts))
+        kp, desc = ctx.orb_detect_describe(small, nf)
+        second = _abi(ctx, f, 0, 5, voc, nf, cap=max(counts))
+        assert first[0] == 0 and second[0] == 0 and _raw_bytes(first) == _raw_bytes(second)
+        okp, odesc = orc.orb_detect_describe(small, nf)
+        assert len(okp) > 0 and np.array_equal(kp.view(np.uint32), okp.view(np.uint32)) and np.array_equal(desc, odesc)
+        for i, v in enumerate(f.bow_vectors(0, 5, voc, nf, LEVELSUP)):   # ... and they are the right bytes
+            _assert_same(v, single[i])
+    finally:
+        f.close()

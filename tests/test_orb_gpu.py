@@ -282,3 +282,36 @@ def test_orb_context_reuse(ctx, orc, vsl):
                 assert np.array_equal(kp.view(np.uint32), okp.view(np.uint32)) and np.array_equal(desc, odesc)
     finally:
         one.close()
+
+
+def test_orb_more_ties_than_the_plan_has_slots(ctx, orc):
+    """The total exceeds every keypoint slot of the first pass (2 * nf + 64 * 8), not only one level's segment: the
+    call itself does the pass a second time with room for the counted total."""
+    w, h, step, nf = 320, 240, 4, 100
+    img = R.dot_grid(w, h, step)
+    okp, _ = orc.orb_detect_describe(img, nf)
+    n0 = int((okp[:, 4] == 0).sum())
+    print("more ties than slots %dx%d nf=%d: oracle %d keypoints (level 0: %d), plan %d slots" % (w, h, nf, len(okp), n0, 2 * nf + 512))
+    assert len(okp) == 3710 and n0 == 3500 and len(okp) > 2 * nf + 64 * 8
+    _same_as_oracle(ctx, orc, img, nf)
+
+
+def test_orb_no_stale_image_records_on_one_context(ctx, orc, vsl):
+    """ordinary -> tie overflow of the same size (its segments are rewritten on the device) -> ordinary again ->
+    another size, all on one context: every call starts from the plan's segments."""
+    w, h, nf = 160, 120, 20
+    ordinary, dots = R.blocky_noise(w, h, 280), R.dot_grid(w, h, 8)
+    okp, _ = orc.orb_detect_describe(dots, nf)
+    assert int((okp[:, 4] == 0).sum()) > 2 * orc.orb_level_quota(nf)[0] + 64   # level 0 overflows its first segment
+    one = vsl.Context(0)
+    try:
+        got = []
+        for img in (ordinary, dots, ordinary, R.blocky_noise(96, 80, 176)):
+            kp, desc = one.orb_detect_describe(img, nf)
+            okp, odesc = orc.orb_detect_describe(img, nf)
+            assert len(okp) > 0 and kp.shape == okp.shape
+            assert np.array_equal(kp.view(np.uint32), okp.view(np.uint32)) and np.array_equal(desc, odesc)
+            got.append((kp, desc))
+        assert np.array_equal(got[0][0].view(np.uint32), got[2][0].view(np.uint32)) and np.array_equal(got[0][1], got[2][1])
+    finally:
+        one.close()

@@ -3,7 +3,10 @@
 //
 // cv::ORB is [upstream] OpenCV; the arithmetic conventions this file implements are spelled out in
 // oracle/orc_orb.cpp (parity with the OpenCV binary is unpinned; parity with that restatement is bit-exact
-// and tested).  One image per call -- the reference runs this once per keyframe:
+// and tested).  One set of kernels works on a pass of k images at once: the image index rides in the grid and every
+// array is [image][...], so one launch (and one memset, one copy) covers a stage of the whole pass.  A pass takes its
+// images from the frame store (vsl_frames_bow_vectors); vsl_orb_detect_describe -- the reference runs
+// this once per keyframe -- is a pass of one image that comes from the host.  The stages:
 //   pyramid (7 chained bilinear resizes, OpenCV's 8-bit fixed-point weights)  ->  per level: FAST-9/16
 //   score image, strict 3x3 non-maximum suppression + border filter + score histogram, retainBest by the
 //   histogram cut with an order-preserving compaction (count / scan / emit over 1024-pixel chunks), 7x7 Gaussian blur  ->
@@ -34,34 +37,6 @@ __constant__ float c_gauss7[7];
 
 __device__ __forceinline__ int d_reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
-__global__ void orb_resize_kernel(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh,
-                                  double scale_x, double scale_y) {
-  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
-  if (dx >= dw) return;
-  float fx = (float)((dx + 0.5) * scale_x - 0.5);
-  int sx = (int)floorf(fx);
-  fx -= sx;
-  if (sx < 0) {
-    fx = 0;
-    sx = 0;
-  }
-  if (sx >= sw - 1) {
-    fx = 0;
-    sx = sw - 1;
-  }
-  float fy = (float)((dy + 0.5) * scale_y - 0.5);
-  const int sy = (int)floorf(fy);
-  fy -= sy;
-  const int a0 = (short)(int)rintf((1.f - fx) * 2048.f), a1 = (short)(int)rintf(fx * 2048.f);
-  const int b0 = (short)(int)rintf((1.f - fy) * 2048.f), b1 = (short)(int)rintf(fy * 2048.f);
-  const int sy0 = min(max(sy, 0), sh - 1), sy1 = min(max(sy + 1, 0), sh - 1);
-  const int sx1 = min(sx + 1, sw - 1);
-  const int S0 = src[(size_t)sy0 * sw + sx] * a0 + src[(size_t)sy0 * sw + sx1] * a1;
-  const int S1 = src[(size_t)sy1 * sw + sx] * a0 + src[(size_t)sy1 * sw + sx1] * a1;
-  const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-  dst[(size_t)dy * dw + dx] = (uint8_t)min(max(v, 0), 255);
-}
-
 struct OrbLevels {
   int W[ORB_LEVELS], H[ORB_LEVELS];
   int quota[ORB_LEVELS];
@@ -72,210 +47,10 @@ struct OrbLevels {
   int chunk_base[ORB_LEVELS + 1];  // 1024-pixel chunks of the level = [chunk_base[l], chunk_base[l + 1])
 };
 
-// FAST-9/16 score of every pixel: the largest threshold at which it is still a corner, 0 if it is not one at
-// ORB_FAST_THR.  16 x 16 pixel tiles staged in LDS with a 3-pixel apron.
-// All levels in one launch: blockIdx.z = level, the grid is sized for level 0 and the workgroups beyond a
-// smaller level's extent leave at once.
-__global__ __launch_bounds__(256) void orb_fast_kernel(OrbLevels L, const uint8_t* __restrict__ pyr, uint8_t* __restrict__ score_all) {
-  __shared__ uint8_t tile[22][24];
-  const int l = blockIdx.z, W = L.W[l], H = L.H[l];
-  const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
-  if (x0 >= W || y0 >= H) return;
-  const uint8_t* img = pyr + L.pix_off[l];
-  uint8_t* score = score_all + L.pix_off[l];
-  for (int t = threadIdx.x; t < 22 * 22; t += 256) {
-    const int ty = t / 22, tx = t - ty * 22;
-    const int gx = min(max(x0 + tx - 3, 0), W - 1), gy = min(max(y0 + ty - 3, 0), H - 1);
-    tile[ty][tx] = img[(size_t)gy * W + gx];
-  }
-  __syncthreads();
-  const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
-  const int x = x0 + lx, y = y0 + ly;
-  if (x >= W || y >= H) return;
-  int out = 0;
-  if (x >= 3 && y >= 3 && x < W - 3 && y < H - 3) {
-    const int cx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
-    const int cy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
-    const int v = tile[ly + 3][lx + 3];
-    int d[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) d[k] = (int)tile[ly + 3 + cy[k]][lx + 3 + cx[k]] - v;
-    int best = -1;
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      int mn = 1 << 20, mx = -(1 << 20);
-#pragma unroll
-      for (int k = 0; k < 9; k++) {
-        const int dv = d[(s + k) & 15];
-        mn = min(mn, dv);
-        mx = max(mx, dv);
-      }
-      best = max(best, max(mn, -mx));
-    }
-    out = best > ORB_FAST_THR ? best - 1 : 0;
-  }
-  score[(size_t)y * W + x] = (uint8_t)out;
-}
-
-// strict 3x3 maximum + border filter; flags the survivors and histograms their scores
-__global__ void orb_nms_kernel(OrbLevels L, const uint8_t* __restrict__ score_all, uint8_t* __restrict__ flag_all,
-                               int* __restrict__ hist_all) {
-  const int l = blockIdx.z, W = L.W[l], H = L.H[l];
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= W || y >= H) return;
-  const uint8_t* score = score_all + L.pix_off[l];
-  uint8_t* flag = flag_all + L.pix_off[l];
-  int* hist = hist_all + 256 * l;
-  uint8_t f = 0;
-  if (x >= ORB_EDGE && y >= ORB_EDGE && x < W - ORB_EDGE && y < H - ORB_EDGE) {
-    const int s = score[(size_t)y * W + x];
-    if (s > 0) {
-      bool ok = true;
-#pragma unroll
-      for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-        for (int dx = -1; dx <= 1; dx++)
-          if (dx || dy) ok = ok && (s > score[(size_t)(y + dy) * W + x + dx]);
-      if (ok) {
-        f = 1;
-        atomicAdd(&hist[s], 1);
-      }
-    }
-  }
-  flag[(size_t)y * W + x] = f;
-}
-
-
-// retainBest + order-preserving compaction in three small launches over 1024-pixel chunks of all levels:
-//   count (kept keypoints per chunk)  ->  scan (exclusive offsets per level, one workgroup)  ->  emit.
-// cut = the score of the quota-th best keypoint of the level: everything at or above it is kept (ties included).
 __device__ __forceinline__ int orb_level_of_chunk(const OrbLevels& L, int chunk) {
   int l = 0;
   while (l + 1 < ORB_LEVELS && chunk >= L.chunk_base[l + 1]) l++;
   return l;
-}
-
-// cut of every level in one small launch: workgroup = level, thread s = suffix count of the scores >= s
-__global__ __launch_bounds__(256) void orb_cut_kernel(OrbLevels L, const int* __restrict__ hist_all, int32_t* __restrict__ cuts) {
-  __shared__ int h[256];
-  __shared__ int cut_s, total_s;
-  const int l = blockIdx.x, s = threadIdx.x, quota = L.quota[l];
-  h[s] = s ? hist_all[256 * l + s] : 0;
-  if (s == 0) cut_s = 0;
-  __syncthreads();
-  int acc = 0;
-  for (int k = 255; k >= s; k--) acc += h[k];
-  if (s == 1) total_s = acc;
-  if (s >= 1 && acc >= quota) atomicMax(&cut_s, s);
-  __syncthreads();
-  if (s == 0) cuts[l] = quota == 0 ? 256 : (total_s <= quota ? 0 : cut_s);
-}
-
-template <bool EMIT>
-__global__ __launch_bounds__(1024) void orb_compact_kernel(OrbLevels L, const uint8_t* __restrict__ score_all,
-                                                           const uint8_t* __restrict__ flag_all, const int32_t* __restrict__ cuts,
-                                                           int32_t* __restrict__ chunk_count, const int32_t* __restrict__ chunk_offset,
-                                                           int32_t* __restrict__ kp_xy, int32_t* __restrict__ kp_sl) {
-  __shared__ int wave_tot[16];
-  const int chunk = blockIdx.x;
-  const int l = orb_level_of_chunk(L, chunk);
-  const int cut_s = cuts[l];
-  const int W = L.W[l], n_pix = W * L.H[l];
-  const int i = (chunk - L.chunk_base[l]) * 1024 + threadIdx.x;
-  const uint8_t* score = score_all + L.pix_off[l];
-  const bool ok = i < n_pix && flag_all[L.pix_off[l] + i] && score[i] >= cut_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(ok);
-  if (lane == 0) wave_tot[wave] = __popcll(m);
-  __syncthreads();
-  if (!EMIT) {
-    if (threadIdx.x == 0) {
-      int t = 0;
-      for (int w = 0; w < 16; w++) t += wave_tot[w];
-      chunk_count[chunk] = t;
-    }
-    return;
-  }
-  if (ok) {
-    int off = chunk_offset[chunk];
-    for (int w = 0; w < wave; w++) off += wave_tot[w];
-    const int p = off + __popcll(m & ((1ull << lane) - 1ull));
-    if (p < L.seg_cap[l]) {
-      const int y = i / W, x = i - y * W;
-      kp_xy[2 * (size_t)(L.seg_base[l] + p)] = x;
-      kp_xy[2 * (size_t)(L.seg_base[l] + p) + 1] = y;
-      kp_sl[L.seg_base[l] + p] = (int)score[i] | (l << 8);
-    }
-  }
-}
-
-// exclusive scan of the chunk counts within each level (one workgroup, levels one after the other).
-// level_full = the keypoints of the level, level_count = those that fit its segment: the host redoes the emit
-// with exact segments when the two differ (retainBest keeps ties without limit).
-__global__ __launch_bounds__(1024) void orb_scan_kernel(OrbLevels L, const int32_t* __restrict__ chunk_count,
-                                                        int32_t* __restrict__ chunk_offset, int32_t* __restrict__ level_count,
-                                                        int32_t* __restrict__ level_full) {
-  __shared__ int wave_tot[16];
-  __shared__ int base_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int l = 0; l < ORB_LEVELS; l++) {
-    if (threadIdx.x == 0) base_s = 0;
-    __syncthreads();
-    const int c0 = L.chunk_base[l], c1 = L.chunk_base[l + 1];
-    for (int cb = c0; cb < c1; cb += 1024) {
-      const int c = cb + threadIdx.x;
-      const int v = c < c1 ? chunk_count[c] : 0;
-      // inclusive scan inside the wave
-      int x = v;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-      }
-      if (lane == 63) wave_tot[wave] = x;
-      __syncthreads();
-      int off = base_s;
-      for (int w = 0; w < wave; w++) off += wave_tot[w];
-      if (c < c1) chunk_offset[c] = off + x - v;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < 16; w++) t += wave_tot[w];
-        base_s += t;
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      level_full[l] = base_s;
-      level_count[l] = min(base_s, L.seg_cap[l]);
-    }
-    __syncthreads();
-  }
-}
-
-__global__ void orb_blur_rows_kernel(OrbLevels L, const uint8_t* __restrict__ pyr, float* __restrict__ tmp_all) {
-  const int l = blockIdx.z, W = L.W[l], H = L.H[l];
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= W || y >= H) return;
-  const uint8_t* src = pyr + L.pix_off[l];
-  float* tmp = tmp_all + L.pix_off[l];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 7; i++) s = s + c_gauss7[i] * (float)src[(size_t)y * W + d_reflect101(x + i - 3, W)];
-  tmp[(size_t)y * W + x] = s;
-}
-
-__global__ void orb_blur_cols_kernel(OrbLevels L, const float* __restrict__ tmp_all, uint8_t* __restrict__ dst_all) {
-  const int l = blockIdx.z, W = L.W[l], H = L.H[l];
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= W || y >= H) return;
-  const float* tmp = tmp_all + L.pix_off[l];
-  uint8_t* dst = dst_all + L.pix_off[l];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 7; i++) s = s + c_gauss7[i] * tmp[(size_t)d_reflect101(y + i - 3, H) * W + x];
-  const int v = (int)rintf(s);
-  dst[(size_t)y * W + x] = (uint8_t)min(max(v, 0), 255);
 }
 
 __device__ __forceinline__ float d_fast_atan2(float y, float x) {
@@ -295,64 +70,6 @@ __device__ __forceinline__ float d_fast_atan2(float y, float x) {
   if (x < 0) a = 180.f - a;
   if (y < 0) a = 360.f - a;
   return a;
-}
-
-// one wavefront per keypoint slot: intensity centroid over the radius-15 disc, exact integer moments
-__global__ __launch_bounds__(256) void orb_angle_kernel(OrbLevels L, const uint8_t* __restrict__ pyr, const int32_t* __restrict__ kp_xy,
-                                                        const int32_t* __restrict__ kp_sl, const int32_t* __restrict__ level_count,
-                                                        int n_slots, float* __restrict__ angle) {
-  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (slot >= n_slots) return;
-  int l = 0;
-  while (l + 1 < ORB_LEVELS && slot >= L.seg_base[l + 1]) l++;
-  if (slot - L.seg_base[l] >= level_count[l]) return;  // wave-uniform
-  const int W = L.W[l];
-  const uint8_t* center = pyr + L.pix_off[l] + (size_t)kp_xy[2 * (size_t)slot + 1] * W + kp_xy[2 * (size_t)slot];
-  int m_01 = 0, m_10 = 0;
-  // rows v = -15 .. 15 over the lanes (31 rows), each lane walks its row's columns
-  if (lane < 31) {
-    const int v = lane - ORB_HALF_PATCH;
-    const int d = c_umax[v < 0 ? -v : v];
-    int row_sum = 0;
-    for (int u = -d; u <= d; ++u) {
-      const int val = center[u + v * W];
-      row_sum += val;
-      m_10 += u * val;
-    }
-    m_01 = v * row_sum;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m_01 += __shfl_xor(m_01, o);
-    m_10 += __shfl_xor(m_10, o);
-  }
-  if (lane == 0) angle[slot] = d_fast_atan2((float)m_01, (float)m_10);
-  (void)kp_sl;
-}
-
-// one thread per (keypoint slot, descriptor byte)
-__global__ __launch_bounds__(256) void orb_describe_kernel(OrbLevels L, const uint8_t* __restrict__ blurred, const int32_t* __restrict__ kp_xy,
-                                                           const int32_t* __restrict__ level_count, int n_slots,
-                                                           const float* __restrict__ cs, uint8_t* __restrict__ desc) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int slot = t >> 5, j = t & 31;
-  if (slot >= n_slots) return;
-  int l = 0;
-  while (l + 1 < ORB_LEVELS && slot >= L.seg_base[l + 1]) l++;
-  if (slot - L.seg_base[l] >= level_count[l]) return;
-  const int W = L.W[l];
-  const uint8_t* bc = blurred + L.pix_off[l] + (size_t)kp_xy[2 * (size_t)slot + 1] * W + kp_xy[2 * (size_t)slot];
-  const float a = cs[2 * (size_t)slot], b = cs[2 * (size_t)slot + 1];
-  int byte = 0;
-#pragma unroll
-  for (int bit = 0; bit < 8; bit++) {
-    const OrbPat p = c_orb_pattern[8 * j + bit];
-    const float xa = (float)p.xa * a - (float)p.ya * b, ya = (float)p.xa * b + (float)p.ya * a;
-    const float xb = (float)p.xb * a - (float)p.yb * b, yb = (float)p.xb * b + (float)p.yb * a;
-    const int t0 = bc[(int)rintf(ya) * W + (int)rintf(xa)], t1 = bc[(int)rintf(yb) * W + (int)rintf(xb)];
-    byte |= (t0 < t1) << bit;
-  }
-  desc[32 * (size_t)slot + j] = (uint8_t)byte;
 }
 
 bool g_orb_tables_ready[16] = {false};
@@ -382,26 +99,6 @@ int orb_upload_tables(vsl_ctx* ctx) {
   return VSL_OK;
 }
 
-// keypoint-shaped device arrays: n_slots entries each, carved from one allocation
-struct OrbKpBuf {
-  int32_t* xy;
-  int32_t* sl;
-  float* angle;
-  float* cs;
-  uint8_t* desc;
-};
-constexpr size_t kOrbKpBytesPerSlot = 8 + 4 + 4 + 8 + 32;
-
-OrbKpBuf orb_carve_kp(void* base, int n_slots) {
-  OrbKpBuf k;
-  k.xy = (int32_t*)base;
-  k.sl = k.xy + 2 * (size_t)n_slots;
-  k.angle = (float*)(k.sl + n_slots);
-  k.cs = k.angle + n_slots;
-  k.desc = (uint8_t*)(k.cs + 2 * (size_t)n_slots);
-  return k;
-}
-
 // seg_base / n_slots from seg_cap
 int orb_place_segments(OrbLevels& L) {
   int n_slots = 0;
@@ -412,16 +109,11 @@ int orb_place_segments(OrbLevels& L) {
   return n_slots;
 }
 
-// everything one image's stages leave on the device
+// the geometry of one image's pass: levels, quotas, first keypoint segments, 1024-pixel chunks
 struct OrbPlan {
   OrbLevels L;
   size_t total_pix;
   int n_slots, n_chunks;
-  uint8_t *pyr, *score, *flag, *blurred;
-  float* tmp;
-  int* hist;
-  int32_t *level_count, *level_full, *cuts, *chunk_count, *chunk_offset;
-  OrbKpBuf kp;
 };
 
 void orb_plan_levels(int w, int h, int nfeatures, OrbPlan& P) {
@@ -453,219 +145,13 @@ void orb_plan_levels(int w, int h, int nfeatures, OrbPlan& P) {
   P.n_chunks = L.chunk_base[ORB_LEVELS];
 }
 
-void orb_launch_emit_angle(hipStream_t st, const OrbPlan& P, const OrbLevels& L, int n_slots, const OrbKpBuf& kp,
-                           const int32_t* level_count) {
-  hipLaunchKernelGGL(orb_compact_kernel<true>, dim3(P.n_chunks), dim3(1024), 0, st, L, (const uint8_t*)P.score, (const uint8_t*)P.flag,
-                     (const int32_t*)P.cuts, P.chunk_count, (const int32_t*)P.chunk_offset, kp.xy, kp.sl);
-  hipLaunchKernelGGL(orb_angle_kernel, dim3((n_slots + 3) / 4), dim3(256), 0, st, L, (const uint8_t*)P.pyr, (const int32_t*)kp.xy,
-                     (const int32_t*)kp.sl, level_count, n_slots, kp.angle);
-}
-
-// The launch sequence of the front end up to the keypoint angles, shared by vsl_orb_detect_describe and the
-// stage export: upload, pyramid, FAST score, NMS + histogram, blur, cut / count / scan / emit, angle.
-int orb_launch_stages(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int nfeatures, OrbPlan& P) {
-  VSL_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = orb_upload_tables(ctx);
-  if (rc) return rc;
-  orb_plan_levels(w, h, nfeatures, P);
-  const OrbLevels& L = P.L;
-  const size_t total_pix = P.total_pix;
-  const int n_slots = P.n_slots, n_chunks = P.n_chunks;
-  // scratch: pyramid | score | flag | blurred (u8, total_pix each) | tmp (f32) | hist | level_count | cuts | level_full |
-  //          chunk_count | chunk_offset | keypoint arrays
-  const size_t n_ints = 256 * ORB_LEVELS + 32;
-  void* d = nullptr;
-  const size_t bytes = 4 * total_pix + 4 * total_pix + 4 * n_ints + 8 * (size_t)n_chunks + (size_t)n_slots * kOrbKpBytesPerSlot + 1024;
-  rc = vsl_ctx_dscratch(ctx, bytes, &d);
-  if (rc) return rc;
-  P.pyr = (uint8_t*)d;
-  P.score = P.pyr + total_pix;
-  P.flag = P.score + total_pix;
-  P.blurred = P.flag + total_pix;
-  P.tmp = (float*)(P.blurred + total_pix);
-  P.hist = (int*)(P.tmp + total_pix);
-  P.level_count = P.hist + 256 * ORB_LEVELS;
-  P.cuts = P.level_count + ORB_LEVELS;
-  P.level_full = P.cuts + ORB_LEVELS;
-  P.chunk_count = P.hist + n_ints;
-  P.chunk_offset = P.chunk_count + n_chunks;
-  P.kp = orb_carve_kp(P.chunk_offset + n_chunks, n_slots);
-  hipStream_t st = ctx->stream;
-  VSL_HIP(ctx, hipMemcpy2DAsync(P.pyr, w, img, pitch, w, h, hipMemcpyHostToDevice, st));
-  VSL_HIP(ctx, hipMemsetAsync(P.hist, 0, sizeof(int) * n_ints, st));
-  for (int l = 1; l < ORB_LEVELS; l++)
-    hipLaunchKernelGGL(orb_resize_kernel, dim3((L.W[l] + 255) / 256, L.H[l]), dim3(256), 0, st, P.pyr + L.pix_off[l - 1], L.W[l - 1],
-                       L.H[l - 1], P.pyr + L.pix_off[l], L.W[l], L.H[l], (double)L.W[l - 1] / L.W[l], (double)L.H[l - 1] / L.H[l]);
-  {
-    const int W = L.W[0], H = L.H[0];  // level 0 is the largest
-    hipLaunchKernelGGL(orb_fast_kernel, dim3((W + 15) / 16, (H + 15) / 16, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)P.pyr, P.score);
-    hipLaunchKernelGGL(orb_nms_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)P.score, P.flag, P.hist);
-    hipLaunchKernelGGL(orb_blur_rows_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const uint8_t*)P.pyr, P.tmp);
-    hipLaunchKernelGGL(orb_blur_cols_kernel, dim3((W + 255) / 256, H, ORB_LEVELS), dim3(256), 0, st, L, (const float*)P.tmp, P.blurred);
-  }
-  hipLaunchKernelGGL(orb_cut_kernel, dim3(ORB_LEVELS), dim3(256), 0, st, L, (const int*)P.hist, P.cuts);
-  hipLaunchKernelGGL(orb_compact_kernel<false>, dim3(n_chunks), dim3(1024), 0, st, L, (const uint8_t*)P.score, (const uint8_t*)P.flag,
-                     (const int32_t*)P.cuts, P.chunk_count, (const int32_t*)P.chunk_offset, P.kp.xy, P.kp.sl);
-  hipLaunchKernelGGL(orb_scan_kernel, dim3(1), dim3(1024), 0, st, L, (const int32_t*)P.chunk_count, P.chunk_offset, P.level_count,
-                     P.level_full);
-  orb_launch_emit_angle(st, P, L, n_slots, P.kp, P.level_count);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
-}
-
-// device memory of the rare second emit, released on every way out
-struct OrbOverflowBuf {
-  void* p = nullptr;
-  ~OrbOverflowBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 bool orb_image_args_ok(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch) {
   return ctx && img && w >= 64 && h >= 64 && pitch >= (size_t)w;
 }
 
-}  // namespace
-
-// kp5: (x, y in level-0 pixels, angle in degrees, response, octave) per keypoint; desc32: 32 bytes each.
-// *n_out = the number of keypoints found, also when it exceeds cap (VSL_ERR_CAPACITY, the first cap are filled).
-extern "C" int vsl_orb_detect_describe(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int nfeatures, int cap,
-                                       float* kp5, uint8_t* desc32, int* n_out) {
-  if (!orb_image_args_ok(ctx, img, w, h, pitch) || !n_out || nfeatures < 1 || cap < 0 || (cap > 0 && (!kp5 || !desc32)))
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_orb_detect_describe: bad arguments (w, h >= 64 required)");
-  *n_out = 0;
-  OrbPlan P;
-  int rc = orb_launch_stages(ctx, img, w, h, pitch, nfeatures, P);
-  if (rc) return rc;
-  hipStream_t st = ctx->stream;
-  OrbLevels L = P.L;
-  int n_slots = P.n_slots;
-  OrbKpBuf kp = P.kp;
-  const int32_t* level_count = P.level_count;
-  std::vector<float> h_angle(n_slots);
-  int32_t h_full[ORB_LEVELS];
-  VSL_HIP(ctx, hipMemcpyAsync(h_angle.data(), kp.angle, sizeof(float) * n_slots, hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipMemcpyAsync(h_full, P.level_full, sizeof(h_full), hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipStreamSynchronize(st));
-  bool overflow = false;
-  for (int l = 0; l < ORB_LEVELS; l++) overflow = overflow || h_full[l] > L.seg_cap[l];
-  OrbOverflowBuf big;
-  if (overflow) {
-    // more ties than a segment holds: emit again into segments of exactly the counted sizes (the chunk offsets
-    // are relative to the level and stay valid), then the angles of the new slots
-    for (int l = 0; l < ORB_LEVELS; l++) L.seg_cap[l] = h_full[l];
-    n_slots = orb_place_segments(L);
-    VSL_HIP(ctx, hipMalloc(&big.p, (size_t)n_slots * kOrbKpBytesPerSlot + 256));
-    kp = orb_carve_kp(big.p, n_slots);
-    level_count = P.level_full;
-    orb_launch_emit_angle(st, P, L, n_slots, kp, level_count);
-    VSL_CHECK_LAUNCH(ctx);
-    h_angle.resize(n_slots);
-    VSL_HIP(ctx, hipMemcpyAsync(h_angle.data(), kp.angle, sizeof(float) * n_slots, hipMemcpyDeviceToHost, st));
-    VSL_HIP(ctx, hipStreamSynchronize(st));
-  }
-  // host: cos / sin of every angle with libm (fp32 radians -> double cos -> fp32, like the oracle)
-  std::vector<float> h_cs(2 * (size_t)n_slots, 0.f);
-  int total = 0;
-  for (int l = 0; l < ORB_LEVELS; l++) {
-    for (int i = 0; i < h_full[l]; i++) {
-      const int slot = L.seg_base[l] + i;
-      const float rad = h_angle[slot] * (float)(M_PI / 180.0);
-      h_cs[2 * (size_t)slot] = (float)std::cos((double)rad);
-      h_cs[2 * (size_t)slot + 1] = (float)std::sin((double)rad);
-    }
-    total += h_full[l];
-  }
-  VSL_HIP(ctx, hipMemcpyAsync(kp.cs, h_cs.data(), sizeof(float) * 2 * n_slots, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(orb_describe_kernel, dim3((n_slots * 32 + 255) / 256), dim3(256), 0, st, L, (const uint8_t*)P.blurred,
-                     (const int32_t*)kp.xy, level_count, n_slots, (const float*)kp.cs, kp.desc);
-  VSL_CHECK_LAUNCH(ctx);
-  std::vector<int32_t> h_xy(2 * (size_t)n_slots), h_sl(n_slots);
-  std::vector<uint8_t> h_desc(32 * (size_t)n_slots);
-  VSL_HIP(ctx, hipMemcpyAsync(h_xy.data(), kp.xy, sizeof(int32_t) * 2 * n_slots, hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipMemcpyAsync(h_sl.data(), kp.sl, sizeof(int32_t) * n_slots, hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipMemcpyAsync(h_desc.data(), kp.desc, 32 * (size_t)n_slots, hipMemcpyDeviceToHost, st));
-  VSL_HIP(ctx, hipStreamSynchronize(st));
-  int n = 0;
-  for (int l = 0; l < ORB_LEVELS && n < cap; l++)
-    for (int i = 0; i < h_full[l] && n < cap; i++) {
-      const int slot = L.seg_base[l] + i;
-      float* k = kp5 + 5 * (size_t)n;
-      k[0] = (float)h_xy[2 * (size_t)slot] * L.scale[l];
-      k[1] = (float)h_xy[2 * (size_t)slot + 1] * L.scale[l];
-      k[2] = h_angle[slot];
-      k[3] = (float)(h_sl[slot] & 255);
-      k[4] = (float)l;
-      std::memcpy(desc32 + 32 * (size_t)n, h_desc.data() + 32 * (size_t)slot, 32);
-      n++;
-    }
-  *n_out = total;
-  if (n < total) return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_orb_detect_describe: %d keypoints, capacity %d", total, cap);
-  return VSL_OK;
-}
-
-extern "C" int vsl_orb_level_sizes(int w, int h, int* level_w, int* level_h) {
-  if (w < 1 || h < 1 || !level_w || !level_h) return VSL_ERR_INVALID;
-  OrbPlan P;
-  orb_plan_levels(w, h, 1, P);
-  for (int l = 0; l < ORB_LEVELS; l++) {
-    level_w[l] = P.L.W[l];
-    level_h[l] = P.L.H[l];
-  }
-  return VSL_OK;
-}
-
-// Test and diagnostic entry: the stage images of one pyramid level after the launches of vsl_orb_detect_describe.
-extern "C" int vsl_orb_stage_images(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int level, uint8_t* pyr,
-                                    uint8_t* score, uint8_t* nms_flag, uint8_t* blurred) {
-  if (!orb_image_args_ok(ctx, img, w, h, pitch) || level < 0 || level >= ORB_LEVELS)
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_orb_stage_images: bad arguments (w, h >= 64, level in [0, %d) required)", ORB_LEVELS);
-  OrbPlan P;
-  // the stage images do not depend on the number of features; 1000 sizes the keypoint segments of the shared launches
-  int rc = orb_launch_stages(ctx, img, w, h, pitch, 1000, P);
-  if (rc) return rc;
-  const size_t n = (size_t)P.L.W[level] * P.L.H[level], off = P.L.pix_off[level];
-  uint8_t* const dst[4] = {pyr, score, nms_flag, blurred};
-  const uint8_t* const src[4] = {P.pyr, P.score, P.flag, P.blurred};
-  for (int i = 0; i < 4; i++)
-    if (dst[i]) VSL_HIP(ctx, hipMemcpyAsync(dst[i], src[i] + off, n, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return VSL_OK;
-}
-
-// compute_bow_vector (include/visnav/keypoints.h:243-254): ORB front end + vocabulary transform.
-// More features than cap: VSL_ERR_CAPACITY with *nnz = *fv_n = the number of features (the capacity that suffices).
-extern "C" int vsl_compute_bow_vector(vsl_ctx* ctx, const vsl_voc* voc, const uint8_t* img, int w, int h, size_t pitch,
-                                      int num_features, int levelsup, int cap, uint32_t* word_ids, double* word_vals, int* nnz,
-                                      uint32_t* fv_node, uint32_t* fv_feat, int* fv_n) {
-  if (!ctx || !voc || !nnz || !fv_n || cap < 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_compute_bow_vector: bad arguments");
-  int kcap = 2 * num_features + 64 * ORB_LEVELS;
-  std::vector<float> kp(5 * (size_t)kcap);
-  std::vector<uint8_t> desc(32 * (size_t)kcap);
-  int n = 0;
-  int rc = vsl_orb_detect_describe(ctx, img, w, h, pitch, num_features, kcap, kp.data(), desc.data(), &n);
-  if (rc == VSL_ERR_CAPACITY) {  // ties beyond the usual bound: once more with the reported total
-    kcap = n;
-    kp.resize(5 * (size_t)kcap);
-    desc.resize(32 * (size_t)kcap);
-    rc = vsl_orb_detect_describe(ctx, img, w, h, pitch, num_features, kcap, kp.data(), desc.data(), &n);
-  }
-  if (rc) return rc;
-  if (n > cap) {
-    *nnz = *fv_n = n;
-    return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_compute_bow_vector: %d features, output capacity %d", n, cap);
-  }
-  return vsl_bow_transform(ctx, voc, desc.data(), n, levelsup, word_ids, word_vals, nnz, fv_node, fv_feat, fv_n);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// The same stages on k resident images at once (vsl_frames_bow_vectors): the image index rides in the
-// grid, every array is [image][...] so one launch (and one memset, one copy) covers the pass.  The arithmetic of each
-// stage is that of the single-image kernel above, statement for statement; only the addressing differs.  The level
-// geometry is one OrbLevels for the whole store; what differs per image -- the keypoint segments once an image
-// overflowed its first ones, and the place of its features in the pass's compact arrays -- is a VslOrbImgSeg record.
-namespace {
-
+// The device arrays of a pass of k images.  The level geometry is one OrbLevels for the whole pass; what differs per
+// image -- the keypoint segments once an image overflowed its first ones, and the place of its features in the pass's
+// compact arrays -- is a VslOrbImgSeg record.
 struct OrbBatchDev {
   uint8_t *pyr, *score, *flag, *blurred;  // [k][pix_stride]
   float* tmp;                             // [k][pix_stride]
@@ -684,8 +170,9 @@ struct OrbBatchDev {
 #define ORB_INTS_CUTS (256 * ORB_LEVELS + ORB_LEVELS)
 #define ORB_INTS_FULL (256 * ORB_LEVELS + 2 * ORB_LEVELS)
 
-__global__ void orb_resize_batch_kernel(OrbBatchDev D, size_t src_off, int sw, int sh, size_t dst_off, int dw, int dh, double scale_x,
-                                        double scale_y) {
+// one pyramid level from the one above it, blockIdx.z = image
+__global__ void orb_resize_kernel(OrbBatchDev D, size_t src_off, int sw, int sh, size_t dst_off, int dw, int dh, double scale_x,
+                                  double scale_y) {
   const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
   if (dx >= dw) return;
   const uint8_t* src = D.pyr + blockIdx.z * D.pix_stride + src_off;
@@ -714,8 +201,11 @@ __global__ void orb_resize_batch_kernel(OrbBatchDev D, size_t src_off, int sw, i
   dst[(size_t)dy * dw + dx] = (uint8_t)min(max(v, 0), 255);
 }
 
-// blockIdx.z = image * ORB_LEVELS + level in the four image-shaped stages
-__global__ __launch_bounds__(256) void orb_fast_batch_kernel(OrbLevels L, OrbBatchDev D) {
+// FAST-9/16 score of every pixel: the largest threshold at which it is still a corner, 0 if it is not one at
+// ORB_FAST_THR.  16 x 16 pixel tiles staged in LDS with a 3-pixel apron.
+// All levels of all images in one launch: blockIdx.z = image * ORB_LEVELS + level in the four image-shaped stages, the
+// grid is sized for level 0 and the workgroups beyond a smaller level's extent leave at once.
+__global__ __launch_bounds__(256) void orb_fast_kernel(OrbLevels L, OrbBatchDev D) {
   __shared__ uint8_t tile[22][24];
   const int l = blockIdx.z % ORB_LEVELS, W = L.W[l], H = L.H[l];
   const size_t img_off = (size_t)(blockIdx.z / ORB_LEVELS) * D.pix_stride + L.pix_off[l];
@@ -757,7 +247,8 @@ __global__ __launch_bounds__(256) void orb_fast_batch_kernel(OrbLevels L, OrbBat
   score[(size_t)y * W + x] = (uint8_t)out;
 }
 
-__global__ void orb_nms_batch_kernel(OrbLevels L, OrbBatchDev D) {
+// strict 3x3 maximum + border filter; flags the survivors and histograms their scores
+__global__ void orb_nms_kernel(OrbLevels L, OrbBatchDev D) {
   const int l = blockIdx.z % ORB_LEVELS, img = blockIdx.z / ORB_LEVELS, W = L.W[l], H = L.H[l];
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= W || y >= H) return;
@@ -784,7 +275,7 @@ __global__ void orb_nms_batch_kernel(OrbLevels L, OrbBatchDev D) {
   flag[(size_t)y * W + x] = f;
 }
 
-__global__ void orb_blur_rows_batch_kernel(OrbLevels L, OrbBatchDev D) {
+__global__ void orb_blur_rows_kernel(OrbLevels L, OrbBatchDev D) {
   const int l = blockIdx.z % ORB_LEVELS, W = L.W[l], H = L.H[l];
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= W || y >= H) return;
@@ -797,7 +288,7 @@ __global__ void orb_blur_rows_batch_kernel(OrbLevels L, OrbBatchDev D) {
   tmp[(size_t)y * W + x] = s;
 }
 
-__global__ void orb_blur_cols_batch_kernel(OrbLevels L, OrbBatchDev D) {
+__global__ void orb_blur_cols_kernel(OrbLevels L, OrbBatchDev D) {
   const int l = blockIdx.z % ORB_LEVELS, W = L.W[l], H = L.H[l];
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= W || y >= H) return;
@@ -811,8 +302,11 @@ __global__ void orb_blur_cols_batch_kernel(OrbLevels L, OrbBatchDev D) {
   dst[(size_t)y * W + x] = (uint8_t)min(max(v, 0), 255);
 }
 
-// workgroup = (level, image)
-__global__ __launch_bounds__(256) void orb_cut_batch_kernel(OrbLevels L, OrbBatchDev D) {
+// retainBest + order-preserving compaction in three small launches over 1024-pixel chunks of all levels:
+//   count (kept keypoints per chunk)  ->  scan (exclusive offsets per level, one workgroup per image)  ->  emit.
+// cut = the score of the quota-th best keypoint of the level: everything at or above it is kept (ties included).
+// The cuts in one small launch: workgroup = (level, image), thread s = suffix count of the scores >= s
+__global__ __launch_bounds__(256) void orb_cut_kernel(OrbLevels L, OrbBatchDev D) {
   __shared__ int h[256];
   __shared__ int cut_s, total_s;
   const int l = blockIdx.x, s = threadIdx.x, quota = L.quota[l];
@@ -831,7 +325,7 @@ __global__ __launch_bounds__(256) void orb_cut_batch_kernel(OrbLevels L, OrbBatc
 // workgroup = (1024-pixel chunk, image); with a list, blockIdx.y walks the list (the second emit of the images that
 // overflowed) and the segments are those of the image's record
 template <bool EMIT>
-__global__ __launch_bounds__(1024) void orb_compact_batch_kernel(OrbLevels L, OrbBatchDev D, const int32_t* __restrict__ img_list) {
+__global__ __launch_bounds__(1024) void orb_compact_kernel(OrbLevels L, OrbBatchDev D, const int32_t* __restrict__ img_list) {
   __shared__ int wave_tot[16];
   const int chunk = blockIdx.x;
   const int img = img_list ? img_list[blockIdx.y] : (int)blockIdx.y;
@@ -869,8 +363,10 @@ __global__ __launch_bounds__(1024) void orb_compact_batch_kernel(OrbLevels L, Or
   }
 }
 
-// one workgroup per image, levels one after the other
-__global__ __launch_bounds__(1024) void orb_scan_batch_kernel(OrbLevels L, OrbBatchDev D) {
+// exclusive scan of the chunk counts within each level: one workgroup per image, levels one after the other.
+// level_full = the keypoints of the level, level_count = those that fit its first segment: the host redoes the emit
+// with exact segments when the two differ (retainBest keeps ties without limit).
+__global__ __launch_bounds__(1024) void orb_scan_kernel(OrbLevels L, OrbBatchDev D) {
   __shared__ int wave_tot[16];
   __shared__ int base_s;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -919,8 +415,9 @@ __device__ __forceinline__ bool orb_batch_slot_level(const VslOrbImgSeg& S, cons
   return slot - S.seg_base[l] < min(ints[ORB_INTS_FULL + l], S.seg_cap[l]);
 }
 
-// one wavefront per (keypoint slot, image)
-__global__ __launch_bounds__(256) void orb_angle_batch_kernel(OrbLevels L, OrbBatchDev D, const int32_t* __restrict__ img_list, int n_slots) {
+// one wavefront per (keypoint slot, image): intensity centroid over the radius-15 disc, exact integer moments; the rows
+// v = -15 .. 15 go over the lanes, each lane walks its row's columns
+__global__ __launch_bounds__(256) void orb_angle_kernel(OrbLevels L, OrbBatchDev D, const int32_t* __restrict__ img_list, int n_slots) {
   const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (slot >= n_slots) return;
   const int img = img_list ? img_list[blockIdx.y] : (int)blockIdx.y;
@@ -950,9 +447,9 @@ __global__ __launch_bounds__(256) void orb_angle_batch_kernel(OrbLevels L, OrbBa
 }
 
 // one thread per (keypoint slot, descriptor byte), blockIdx.y = image; cos / sin are read and the descriptor is written
-// at the keypoint's FEATURE index (level-major, as the single-image call returns them): the vocabulary descent reads
+// at the keypoint's FEATURE index (level-major, the order vsl_orb_detect_describe returns): the vocabulary descent reads
 // the descriptors of the whole pass as one dense array
-__global__ __launch_bounds__(256) void orb_describe_batch_kernel(OrbLevels L, OrbBatchDev D, int n_slots) {
+__global__ __launch_bounds__(256) void orb_describe_kernel(OrbLevels L, OrbBatchDev D, int n_slots) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int slot = t >> 5, j = t & 31;
   if (slot >= n_slots) return;
@@ -1067,24 +564,27 @@ int vsl_orb_batch_count(vsl_ctx* ctx, VslOrbBatch& b) {
   }
   VSL_HIP(ctx, hipMemcpyAsync(D.seg, Y.h_seg, sizeof(VslOrbImgSeg) * k, hipMemcpyHostToDevice, st));
   const size_t wh = (size_t)b.w * b.h;
-  VSL_HIP(ctx, hipMemcpy2DAsync(D.pyr, D.pix_stride, b.images, b.image_stride, wh, k, hipMemcpyDeviceToDevice, st));
+  if (b.host_image)  // level 0 of the pass's one image, row by row out of host memory
+    VSL_HIP(ctx, hipMemcpy2DAsync(D.pyr, b.w, b.host_image, b.host_pitch, b.w, b.h, hipMemcpyHostToDevice, st));
+  else
+    VSL_HIP(ctx, hipMemcpy2DAsync(D.pyr, D.pix_stride, b.images, b.image_stride, wh, k, hipMemcpyDeviceToDevice, st));
   VSL_HIP(ctx, hipMemsetAsync(D.ints, 0, sizeof(int) * (size_t)k * D.n_ints, st));
   for (int l = 1; l < ORB_LEVELS; l++)
-    hipLaunchKernelGGL(orb_resize_batch_kernel, dim3((L.W[l] + 255) / 256, L.H[l], k), dim3(256), 0, st, D, L.pix_off[l - 1], L.W[l - 1],
+    hipLaunchKernelGGL(orb_resize_kernel, dim3((L.W[l] + 255) / 256, L.H[l], k), dim3(256), 0, st, D, L.pix_off[l - 1], L.W[l - 1],
                        L.H[l - 1], L.pix_off[l], L.W[l], L.H[l], (double)L.W[l - 1] / L.W[l], (double)L.H[l - 1] / L.H[l]);
   {
     const int W = L.W[0], H = L.H[0];
     const unsigned z = (unsigned)(ORB_LEVELS * k);
-    hipLaunchKernelGGL(orb_fast_batch_kernel, dim3((W + 15) / 16, (H + 15) / 16, z), dim3(256), 0, st, L, D);
-    hipLaunchKernelGGL(orb_nms_batch_kernel, dim3((W + 255) / 256, H, z), dim3(256), 0, st, L, D);
-    hipLaunchKernelGGL(orb_blur_rows_batch_kernel, dim3((W + 255) / 256, H, z), dim3(256), 0, st, L, D);
-    hipLaunchKernelGGL(orb_blur_cols_batch_kernel, dim3((W + 255) / 256, H, z), dim3(256), 0, st, L, D);
+    hipLaunchKernelGGL(orb_fast_kernel, dim3((W + 15) / 16, (H + 15) / 16, z), dim3(256), 0, st, L, D);
+    hipLaunchKernelGGL(orb_nms_kernel, dim3((W + 255) / 256, H, z), dim3(256), 0, st, L, D);
+    hipLaunchKernelGGL(orb_blur_rows_kernel, dim3((W + 255) / 256, H, z), dim3(256), 0, st, L, D);
+    hipLaunchKernelGGL(orb_blur_cols_kernel, dim3((W + 255) / 256, H, z), dim3(256), 0, st, L, D);
   }
-  hipLaunchKernelGGL(orb_cut_batch_kernel, dim3(ORB_LEVELS, k), dim3(256), 0, st, L, D);
-  hipLaunchKernelGGL(orb_compact_batch_kernel<false>, dim3(D.n_chunks, k), dim3(1024), 0, st, L, D, (const int32_t*)nullptr);
-  hipLaunchKernelGGL(orb_scan_batch_kernel, dim3(k), dim3(1024), 0, st, L, D);
-  hipLaunchKernelGGL(orb_compact_batch_kernel<true>, dim3(D.n_chunks, k), dim3(1024), 0, st, L, D, (const int32_t*)nullptr);
-  hipLaunchKernelGGL(orb_angle_batch_kernel, dim3((n_slots + 3) / 4, k), dim3(256), 0, st, L, D, (const int32_t*)nullptr, n_slots);
+  hipLaunchKernelGGL(orb_cut_kernel, dim3(ORB_LEVELS, k), dim3(256), 0, st, L, D);
+  hipLaunchKernelGGL(orb_compact_kernel<false>, dim3(D.n_chunks, k), dim3(1024), 0, st, L, D, (const int32_t*)nullptr);
+  hipLaunchKernelGGL(orb_scan_kernel, dim3(k), dim3(1024), 0, st, L, D);
+  hipLaunchKernelGGL(orb_compact_kernel<true>, dim3(D.n_chunks, k), dim3(1024), 0, st, L, D, (const int32_t*)nullptr);
+  hipLaunchKernelGGL(orb_angle_kernel, dim3((n_slots + 3) / 4, k), dim3(256), 0, st, L, D, (const int32_t*)nullptr, n_slots);
   VSL_CHECK_LAUNCH(ctx);
   VSL_HIP(ctx, hipMemcpy2DAsync(Y.h_angle, 4 * (size_t)D.slot_stride, D.angle, 4 * (size_t)D.slot_stride, 4 * (size_t)n_slots, k,
                                 hipMemcpyDeviceToHost, st));
@@ -1147,8 +647,8 @@ int vsl_orb_batch_describe(vsl_ctx* ctx, VslOrbBatch& b) {
   VSL_HIP(ctx, hipMemcpyAsync(D.seg, Y.h_seg, sizeof(VslOrbImgSeg) * k, hipMemcpyHostToDevice, st));
   if (n_over) {
     VSL_HIP(ctx, hipMemcpyAsync(D.img_list, Y.h_list, 4 * (size_t)n_over, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(orb_compact_batch_kernel<true>, dim3(D.n_chunks, n_over), dim3(1024), 0, st, L, D, (const int32_t*)D.img_list);
-    hipLaunchKernelGGL(orb_angle_batch_kernel, dim3((over_slots + 3) / 4, n_over), dim3(256), 0, st, L, D, (const int32_t*)D.img_list,
+    hipLaunchKernelGGL(orb_compact_kernel<true>, dim3(D.n_chunks, n_over), dim3(1024), 0, st, L, D, (const int32_t*)D.img_list);
+    hipLaunchKernelGGL(orb_angle_kernel, dim3((over_slots + 3) / 4, n_over), dim3(256), 0, st, L, D, (const int32_t*)D.img_list,
                        over_slots);
     VSL_CHECK_LAUNCH(ctx);
     // one strided copy for the pass: the rows of the other images arrive again unchanged
@@ -1174,10 +674,138 @@ int vsl_orb_batch_describe(vsl_ctx* ctx, VslOrbBatch& b) {
   }
   if (b.n_rows > 0) {
     VSL_HIP(ctx, hipMemcpyAsync(D.cs, Y.h_cs, 8 * (size_t)b.n_rows, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(orb_describe_batch_kernel, dim3((max_slots * 32 + 255) / 256, k), dim3(256), 0, st, L, D, max_slots);
+    hipLaunchKernelGGL(orb_describe_kernel, dim3((max_slots * 32 + 255) / 256, k), dim3(256), 0, st, L, D, max_slots);
     VSL_CHECK_LAUNCH(ctx);
   }
   b.desc = D.desc;
   b.seg = D.seg;
   return VSL_OK;
+}
+
+namespace {
+
+// The count half of a pass of ONE image that lies in host memory, on the context's scratch and pinned buffer, with room
+// for max_feat features or the plan's keypoint slots (2 * nfeatures + 64 per level), whichever is more.  Y is the pass's
+// carve-up; behind its staging the pinned buffer has 44 bytes per keypoint slot for the caller's downloads.
+int orb_count_one(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int nfeatures, int max_feat, VslOrbBatch& b,
+                  OrbBatchLayout& Y) {
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  orb_plan_levels(w, h, nfeatures, Y.P);
+  max_feat = std::max(max_feat, Y.P.n_slots);
+  orb_batch_layout(w, h, nfeatures, 1, max_feat, nullptr, nullptr, Y);  // the sizes
+  int rc = vsl_ctx_dscratch(ctx, Y.device_bytes, &b.scratch);
+  if (rc) return rc;
+  if ((rc = vsl_ctx_hpinned(ctx, Y.pinned_bytes + 44 * (size_t)Y.D.slot_stride, &b.pinned))) return rc;
+  orb_batch_layout(w, h, nfeatures, 1, max_feat, (uint8_t*)b.scratch, (uint8_t*)b.pinned, Y);
+  b.host_image = img;
+  b.host_pitch = pitch;
+  b.w = w;
+  b.h = h;
+  b.k = 1;
+  b.nfeatures = nfeatures;
+  b.max_feat = max_feat;
+  return vsl_orb_batch_count(ctx, b);
+}
+
+}  // namespace
+
+// kp5: (x, y in level-0 pixels, angle in degrees, response, octave) per keypoint; desc32: 32 bytes each.
+// *n_out = the number of keypoints found, also when it exceeds cap (VSL_ERR_CAPACITY, the first cap are filled).
+// A pass of one image.  retainBest keeps every tie, so an image can hold more keypoints than the plan has slots: the
+// pass is then done once more with room for the counted total (the rare adversarial image costs two passes).
+extern "C" int vsl_orb_detect_describe(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int nfeatures, int cap,
+                                       float* kp5, uint8_t* desc32, int* n_out) {
+  if (!orb_image_args_ok(ctx, img, w, h, pitch) || !n_out || nfeatures < 1 || cap < 0 || (cap > 0 && (!kp5 || !desc32)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_orb_detect_describe: bad arguments (w, h >= 64 required)");
+  *n_out = 0;
+  VslOrbBatch b;
+  OrbBatchLayout Y;
+  int rc = orb_count_one(ctx, img, w, h, pitch, nfeatures, 0, b, Y);
+  if (!rc && b.n_feat[0] > b.max_feat) rc = orb_count_one(ctx, img, w, h, pitch, nfeatures, b.n_feat[0], b, Y);
+  if (rc) return rc;
+  const int total = b.n_feat[0], n = std::min(total, cap);
+  *n_out = total;
+  if (total == 0) return VSL_OK;
+  if ((rc = vsl_orb_batch_describe(ctx, b))) return rc;
+  const OrbLevels& L = Y.P.L;
+  const OrbBatchDev& D = Y.D;
+  const VslOrbImgSeg& S = Y.h_seg[0];  // the segments the keypoints were emitted into
+  const size_t n_slots = (size_t)D.slot_stride;
+  int32_t* h_xy = (int32_t*)((uint8_t*)b.pinned + Y.pinned_bytes);
+  int32_t* h_sl = h_xy + 2 * n_slots;
+  uint8_t* h_desc = (uint8_t*)(h_sl + n_slots);
+  hipStream_t st = ctx->stream;
+  VSL_HIP(ctx, hipMemcpyAsync(h_xy, D.kp_xy, 8 * n_slots, hipMemcpyDeviceToHost, st));
+  VSL_HIP(ctx, hipMemcpyAsync(h_sl, D.kp_sl, 4 * n_slots, hipMemcpyDeviceToHost, st));
+  if (n > 0) VSL_HIP(ctx, hipMemcpyAsync(h_desc, D.desc, 32 * (size_t)n, hipMemcpyDeviceToHost, st));
+  VSL_HIP(ctx, hipStreamSynchronize(st));
+  // the features are level-major, the order of the pass's compact descriptors
+  for (int l = 0; l < ORB_LEVELS; l++)
+    for (int i = 0, f = S.feat_off[l]; i < b.full[l] && f < n; i++, f++) {
+      const int slot = S.seg_base[l] + i;
+      float* k = kp5 + 5 * (size_t)f;
+      k[0] = (float)h_xy[2 * (size_t)slot] * L.scale[l];
+      k[1] = (float)h_xy[2 * (size_t)slot + 1] * L.scale[l];
+      k[2] = Y.h_angle[slot];
+      k[3] = (float)(h_sl[slot] & 255);
+      k[4] = (float)l;
+    }
+  if (n > 0) std::memcpy(desc32, h_desc, 32 * (size_t)n);
+  if (n < total) return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_orb_detect_describe: %d keypoints, capacity %d", total, cap);
+  return VSL_OK;
+}
+
+extern "C" int vsl_orb_level_sizes(int w, int h, int* level_w, int* level_h) {
+  if (w < 1 || h < 1 || !level_w || !level_h) return VSL_ERR_INVALID;
+  OrbPlan P;
+  orb_plan_levels(w, h, 1, P);
+  for (int l = 0; l < ORB_LEVELS; l++) {
+    level_w[l] = P.L.W[l];
+    level_h[l] = P.L.H[l];
+  }
+  return VSL_OK;
+}
+
+// Test and diagnostic entry: the stage images of one pyramid level after the count half of vsl_orb_detect_describe's pass.
+extern "C" int vsl_orb_stage_images(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch, int level, uint8_t* pyr,
+                                    uint8_t* score, uint8_t* nms_flag, uint8_t* blurred) {
+  if (!orb_image_args_ok(ctx, img, w, h, pitch) || level < 0 || level >= ORB_LEVELS)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_orb_stage_images: bad arguments (w, h >= 64, level in [0, %d) required)", ORB_LEVELS);
+  VslOrbBatch b;
+  OrbBatchLayout Y;
+  // the stage images do not depend on the number of features; 1000 sizes the keypoint segments of the pass
+  int rc = orb_count_one(ctx, img, w, h, pitch, 1000, 0, b, Y);
+  if (rc) return rc;
+  const size_t n = (size_t)Y.P.L.W[level] * Y.P.L.H[level], off = Y.P.L.pix_off[level];
+  uint8_t* const dst[4] = {pyr, score, nms_flag, blurred};
+  const uint8_t* const src[4] = {Y.D.pyr, Y.D.score, Y.D.flag, Y.D.blurred};
+  for (int i = 0; i < 4; i++)
+    if (dst[i]) VSL_HIP(ctx, hipMemcpyAsync(dst[i], src[i] + off, n, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VSL_OK;
+}
+
+// compute_bow_vector (include/visnav/keypoints.h:243-254): ORB front end + vocabulary transform.
+// More features than cap: VSL_ERR_CAPACITY with *nnz = *fv_n = the number of features (the capacity that suffices).
+extern "C" int vsl_compute_bow_vector(vsl_ctx* ctx, const vsl_voc* voc, const uint8_t* img, int w, int h, size_t pitch,
+                                      int num_features, int levelsup, int cap, uint32_t* word_ids, double* word_vals, int* nnz,
+                                      uint32_t* fv_node, uint32_t* fv_feat, int* fv_n) {
+  if (!ctx || !voc || !nnz || !fv_n || cap < 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_compute_bow_vector: bad arguments");
+  int kcap = 2 * num_features + 64 * ORB_LEVELS;
+  std::vector<float> kp(5 * (size_t)kcap);
+  std::vector<uint8_t> desc(32 * (size_t)kcap);
+  int n = 0;
+  int rc = vsl_orb_detect_describe(ctx, img, w, h, pitch, num_features, kcap, kp.data(), desc.data(), &n);
+  if (rc == VSL_ERR_CAPACITY) {  // ties beyond the usual bound: once more with the reported total
+    kcap = n;
+    kp.resize(5 * (size_t)kcap);
+    desc.resize(32 * (size_t)kcap);
+    rc = vsl_orb_detect_describe(ctx, img, w, h, pitch, num_features, kcap, kp.data(), desc.data(), &n);
+  }
+  if (rc) return rc;
+  if (n > cap) {
+    *nnz = *fv_n = n;
+    return vsl_fail(ctx, VSL_ERR_CAPACITY, "vsl_compute_bow_vector: %d features, output capacity %d", n, cap);
+  }
+  return vsl_bow_transform(ctx, voc, desc.data(), n, levelsup, word_ids, word_vals, nnz, fv_node, fv_feat, fv_n);
 }

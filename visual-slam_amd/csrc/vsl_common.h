@@ -226,7 +226,8 @@ __host__ __device__ inline float vsl_ordered_to_float(int32_t i) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Batched ORB front end on resident images (orb.hip), driven pass by pass by vsl_frames_bow_vectors (bow.hip).
+// The ORB front end as passes of k images (orb.hip): vsl_frames_bow_vectors (bow.hip) drives it pass by pass on the frame
+// store's images, vsl_orb_detect_describe as a pass of one image from the host.
 // Per-image keypoint segments and the compact feature numbering of a pass, one 128-byte record per image on the device.
 struct VslOrbImgSeg {
   int32_t seg_base[8], seg_cap[8];  // keypoint slots of each pyramid level inside the image's slot range
@@ -238,6 +239,8 @@ struct VslOrbBatch {
   // in
   const uint8_t* images = nullptr;  // k dense w x h images, image_stride bytes apart (device)
   size_t image_stride = 0;
+  const uint8_t* host_image = nullptr;  // instead of `images`, k = 1: one w x h image in host memory, rows host_pitch bytes apart
+  size_t host_pitch = 0;
   int w = 0, h = 0, k = 0, nfeatures = 0, max_feat = 0;  // max_feat: most features of an image that can be described
   void* scratch = nullptr;          // device, pinned: the sizes vsl_orb_batch_bytes reports
   void* pinned = nullptr;
