@@ -4,6 +4,8 @@ atan2: device and glibc differ in the last bits -> same kept set, 1e-12 px); mat
 import numpy as np
 import pytest
 
+from test_fuse_gpu import _case as _fuse_case, _check as _fuse_check
+
 pytestmark = pytest.mark.gpu
 
 INTR = {0: [351.0, 350.0, 365.9, 249.3, -0.2385, 0.5679, 0, 0], 1: [351.0, 350.0, 365.9, 249.3, 0, 0, 0, 0],
@@ -261,3 +263,63 @@ def test_map_descriptors_copied_from_a_frame_slot(vsl, ctx, synth):
         m.append_descriptors_from_frame(fr, 0, np.array([99999], np.int32))
     m.close()
     fr.close()
+
+
+# ---- the seams of the shared kernel set (csrc/guided_search.h): the operators run the per-view kernels as a pass of one
+
+PIN = [100.0, 100.0, 50.0, 40.0, 0, 0, 0, 0]   # u = 100 x / z + 50: x / z = 0.5 lands exactly on u == width == 100
+IDENT = [0.0, 0, 0, 1, 0, 0, 0]
+
+
+def _chunk_points(n, pattern):
+    """n points in front of the PIN camera, all inside the 100 x 80 image.  pattern "mixed": every third point (i % 3 ==
+    2) is mirrored behind the camera, then the last point of every 1024-landmark chunk is put exactly on u == width
+    (kept: the reference rejects u > width only)."""
+    rng = np.random.default_rng(n)
+    z = rng.uniform(1.0, 8.0, n)
+    pts = np.stack([rng.uniform(-0.45, 0.45, n) * z, rng.uniform(-0.35, 0.35, n) * z, z], -1)
+    if pattern == "mixed":
+        pts[2::3] *= -1.0
+        for last in sorted({min(c + 1024, n) - 1 for c in range(0, n, 1024)}):
+            pts[last] = [0.5, 0.0, 1.0]
+    return pts
+
+
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 2049])
+def test_project_landmarks_chunk_boundaries(ctx, orc, n):
+    """One 1024-thread workgroup projects a chunk, one workgroup compacts the row chunk by chunk: sizes around one and
+    two chunks.  n == 1 has a single point, which the mixed pattern puts on the edge: there kept == n, not < n."""
+    for pattern in ("all", "mixed"):
+        pts = _chunk_points(n, pattern)
+        uv, idx = ctx.project_landmarks(IDENT, 1, PIN, 100, 80, pts, 0.1)
+        euv, eidx = orc.project_landmarks(IDENT, 1, PIN, 100, 80, pts, 0.1)
+        assert np.array_equal(idx, eidx), pattern
+        assert np.array_equal(uv.view(np.uint64), euv.view(np.uint64)), pattern
+        if pattern == "all":
+            assert len(idx) == n
+        else:
+            assert 0 < len(idx) < n or n == 1
+            for last in sorted({min(c + 1024, n) - 1 for c in range(0, n, 1024)}):
+                assert uv[idx.tolist().index(last)].tolist() == [100.0, 40.0]
+
+
+@pytest.mark.parametrize("n_proj", [1, 63, 64, 65, 129])
+def test_find_matches_partial_workgroup_and_chunk(ctx, orc, synth, n_proj):
+    """The last partial workgroup of four keypoints x the last partial / first full 64-lane chunk of projections."""
+    found = 0
+    for n_kp in (1, 3, 4, 5):
+        c = _match_case(synth, 1000 * n_kp + n_proj, n_kp, n_proj, 3, planted=1.0)
+        got = ctx.find_matches_landmarks(*c, 20.0, 70, 1.2)
+        assert np.array_equal(got, orc.find_matches_landmarks(*c, 20.0, 70, 1.2)), n_kp
+        found += len(got)
+    assert found > 0
+
+
+def test_fuse_search_views_of_0_1_and_1025_keypoints(ctx, orc, synth):
+    """The per-view kernels with an empty view, a view of one keypoint and a view whose pair compaction crosses the
+    1024 boundary inside a segment that is not the first: every segment == project_landmarks + find_matches_landmarks
+    of that view (device operators and oracle)."""
+    c = _fuse_case(ctx, synth, 7, 0, [0, 1, 1025], 300, 5)
+    got, n_proj = _fuse_check(ctx, orc, c)
+    assert len(got[0]) == 0 and n_proj.min() > 0
+    assert got[2][0, 0] < 1024 and got[2][-1, 0] == 1024   # matched keypoints on both sides of the boundary

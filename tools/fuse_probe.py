@@ -1,4 +1,4 @@
-"""Cost of the batched fusion search (csrc/fuse.hip) next to the per-view loop it replaces, on the same inputs:
+"""Cost of the batched fusion search (vsl_fuse_search, csrc/vo.hip) next to the per-view loop it replaces, on the same inputs:
 16 views x 1500 keypoints x 4000 landmarks with at most 20 observations each (DESIGN.md "Landmark fusion").
 
     python3 tools/fuse_probe.py [--views 16] [--kp 1500] [--lms 4000] [--max-obs 20] [--reps 30] [--warmup 5]

@@ -5,8 +5,8 @@
 // correctly rounded f64 division and sqrt, the pinhole / eucm / ds bearings and the triangulated points are the host's
 // bits.  kb4 calls sin / cos, whose device results may differ from the host libm in the last bit.
 //
-// Also the forward side shared by vo.hip and fuse.hip: quat_rotate_d(), project_exact() -- camera_models.h project(),
-// expression for expression -- and the host helper sqrt_less_threshold() of the guided search's radius test.
+// Also the forward side used by guided_search.h: quat_rotate_d() and project_exact() -- camera_models.h project(),
+// expression for expression.
 #pragma once
 #include <cmath>
 
@@ -118,28 +118,6 @@ __device__ __forceinline__ void project_exact(int model, const double* ip, doubl
     u = fx * x / (alpha * d2 + (1.0 - alpha) * (xi * d1 + z)) + cx;
     v = fy * y / (alpha * d2 + (1.0 - alpha) * (xi * d1 + z)) + cy;
   }
-}
-
-// The smallest double T with !(sqrt(T) < m): for x >= 0, sqrt(x) < m <=> x < T, because the correctly rounded square
-// root is monotone (host libm and the device's fp64 sqrt are both correctly rounded).  Bisection over the bit patterns
-// of the non-negative doubles (they order like the values).
-static inline double sqrt_less_threshold(double m) {
-  if (!(m > 0.0)) return 0.0;  // sqrt(x) < m never holds for x >= 0
-  if (std::isinf(m)) return m;
-  uint64_t lo = 0, hi;          // invariant: sqrt(value(lo)) < m, !(sqrt(value(hi)) < m)
-  {
-    const double inf = INFINITY;
-    memcpy(&hi, &inf, 8);
-  }
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    double v;
-    memcpy(&v, &mid, 8);
-    if (std::sqrt(v) < m) lo = mid; else hi = mid;
-  }
-  double T;
-  memcpy(&T, &hi, 8);
-  return T;
 }
 
 }  // namespace

@@ -1,89 +1,72 @@
-// vo.hip -- per-frame landmark projection and guided descriptor matching.
+// vo.hip -- landmark projection and guided descriptor matching: per frame and, after a loop
+// closure, for all views of a covisibility neighbourhood at once (DESIGN.md "Landmark fusion").
 //
-// Replaces visnav::project_landmarks (include/visnav/vo_utils.h:48-81) and
-// visnav::find_matches_landmarks (include/visnav/vo_utils.h:83-167), which src/slam.cpp runs on EVERY
-// frame (:1099-1114, :1159, :1339).
+// Replaces visnav::project_landmarks (include/visnav/vo_utils.h:48-81) and visnav::find_matches_landmarks
+// (include/visnav/vo_utils.h:83-167), which src/slam.cpp runs on EVERY frame (:1099-1114, :1159, :1339).  The device
+// logic -- the fp64 projection in the oracle's operation order, the order-preserving compaction, the wavefront search
+// with the reference's partial_sort tie order as a state machine -- is in guided_search.h, once; the kernels here say
+// where the operands come from:
 //
-//  * projection: one thread per landmark, fp64 in the oracle's operation order (no FMA), then an
-//    order-preserving compaction -- the output order is the caller's landmark order (the reference
-//    iterates its unordered_map);
-//  * matching: one wavefront per keypoint.  Lanes test 64 projected points at a time against the 2-D
-//    radius (double, sqrt(dx*dx + dy*dy) < r like Eigen's norm()); for every hit, in order, the lanes
-//    stride the landmark's observation descriptors and a wave-wide minimum gives the landmark
-//    distance.  The reference then calls std::partial_sort(first, first + 2, last) on the (landmark,
-//    distance) list; which of two EQUALLY distant landmarks comes first is libstdc++'s heap-select
-//    behaviour, reproduced here as the equivalent streaming state machine over the list:
-//        first two:   top = (d1 < d0) ? e0 : e1,  other = the other one
-//        each later e with d(e) < d(top):   (top, other) = d(other) < d(e) ? (e, other) : (other, e)
-//        result[0] = other, result[1] = top
-//    so ties are broken exactly like the reference (pinned against the oracle, which calls the real
-//    std::partial_sort).
-#include <cmath>
-
-#include "cam_device.h"  // quat_rotate_d, project_exact, sqrt_less_threshold (shared with fuse.hip)
+//   project_kernel             grid (1024-landmark chunk, view), pose of the view from pose8 + 8 * view -> keep, uv
+//   compact_projection_kernel  one workgroup per view loops over the view's row: (uv, landmark) of the kept ones in
+//                              ascending landmark order (the caller's order, the reference iterates its unordered_map;
+//                              that order decides ties in the search) + their count
+//   find_matches_kernel        grid (4 keypoints, view), one wavefront per keypoint: result = landmark index or -1
+//   compact_matches_kernel     one workgroup per view: (feature, landmark) pairs in feature order into the view's own
+//                              segment + their count
+//                              -- these four serve vsl_project_landmarks / vsl_find_matches_landmarks (one view) and
+//                              vsl_fuse_search (all views)
+//   project_compact_kernel     the tracker's projection + compaction in one launch (chained workgroups)
+//   track_matches_kernel       the tracker's search: keypoints of a frame store slot, descriptors through the map's
+//                              pool index, results into the pinned mailbox
+#include "guided_search.h"
 #include "vsl_common.h"
+
+#define VSL_FUSE_MAX_VIEWS 64
 
 namespace {
 
-__global__ __launch_bounds__(256) void project_landmarks_kernel(const double* __restrict__ pose, int model,
-                                                                const double* __restrict__ intr, int width, int height,
-                                                                const double* __restrict__ points, int n, double z_thr,
-                                                                double* __restrict__ uv, uint8_t* __restrict__ keep) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(1024) void project_kernel(const double* __restrict__ pose8, int model,
+                                                       const double* __restrict__ intr, int width, int height,
+                                                       const double* __restrict__ points, int n, double z_thr,
+                                                       double* __restrict__ uv, uint8_t* __restrict__ keep) {
+  const int i = blockIdx.x * 1024 + threadIdx.x;
   if (i >= n) return;
-  const double qi[4] = {-pose[0], -pose[1], -pose[2], pose[3]};
-  const double nt[3] = {pose[4] * -1.0, pose[5] * -1.0, pose[6] * -1.0};
-  double ti[3], rp[3];
-  quat_rotate_d(qi, nt, ti);
-  const double p[3] = {points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]};
-  quat_rotate_d(qi, p, rp);
-  const double pc[3] = {rp[0] + ti[0], rp[1] + ti[1], rp[2] + ti[2]};
-  bool ok = !(pc[2] < z_thr);
-  double u = 0, v = 0;
-  if (ok) {
-    project_exact(model, intr, pc[0], pc[1], pc[2], u, v);
-    ok = !(u > (double)width || v > (double)height || u < 0 || v < 0);
-  }
-  uv[2 * (size_t)i] = u;
-  uv[2 * (size_t)i + 1] = v;
-  keep[i] = ok ? 1 : 0;
+  const size_t o = (size_t)blockIdx.y * (size_t)n + (size_t)i;
+  double u, v;
+  const bool ok = project_in_view(pose8 + 8 * (size_t)blockIdx.y, model, intr, width, height, points + 3 * (size_t)i, z_thr, u, v);
+  uv[2 * o] = u;
+  uv[2 * o + 1] = v;
+  keep[o] = ok ? 1 : 0;
 }
 
-// order-preserving compaction of (uv, index) by keep[]; one workgroup
+// view = blockIdx.x, on the view's row (n entries) of uv / keep / out_uv / out_idx
 __global__ __launch_bounds__(1024) void compact_projection_kernel(const double* __restrict__ uv, const uint8_t* __restrict__ keep,
                                                                   int n, double* __restrict__ out_uv, int32_t* __restrict__ out_idx,
                                                                   int32_t* __restrict__ n_out) {
-  __shared__ int wave_tot[16];
-  __shared__ int base_s;
-  if (threadIdx.x == 0) base_s = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t row = (size_t)blockIdx.x * (size_t)n;
+  uv += 2 * row;
+  keep += row;
+  out_uv += 2 * row;
+  out_idx += row;
+  int base = 0;
   for (int i0 = 0; i0 < n; i0 += 1024) {
     const int i = i0 + threadIdx.x;
     const bool ok = i < n && keep[i];
-    const unsigned long long m = __ballot(ok);
-    if (lane == 0) wave_tot[wave] = __popcll(m);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wave; w++) off += wave_tot[w];
+    int total;
+    const int p = base + wg1024_ordered_slot(ok, total);
     if (ok) {
-      const int p = off + __popcll(m & ((1ull << lane) - 1ull));
       out_uv[2 * (size_t)p] = uv[2 * (size_t)i];
       out_uv[2 * (size_t)p + 1] = uv[2 * (size_t)i + 1];
       out_idx[p] = i;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int t = 0;
-      for (int w = 0; w < 16; w++) t += wave_tot[w];
-      base_s += t;
-    }
-    __syncthreads();
+    base += total;
+    __syncthreads();  // the next chunk rewrites the wave totals
   }
-  if (threadIdx.x == 0) *n_out = base_s;
+  if (threadIdx.x == 0) n_out[blockIdx.x] = base;
 }
 
-// project_landmarks + the order-preserving compaction in ONE launch (vsl_map_track): a workgroup projects 1024 landmarks,
+// Projection + the order-preserving compaction in ONE launch (vsl_map_track): a workgroup projects 1024 landmarks,
 // compacts them in landmark order, and takes its base offset from the chain of its predecessors' totals ("stream
 // scan": block b waits for block b - 1's running total, published as one 64-bit word (epoch << 32 | total) with
 // release / acquire at device scope -- no flags to reset between calls, the epoch changes).  Forward progress of the
@@ -91,7 +74,7 @@ __global__ __launch_bounds__(1024) void compact_projection_kernel(const double* 
 // the hardware's index-order dispatch makes blockIdx the chain position; larger maps (> 262 k landmarks) draw their
 // chain position from an atomic ticket instead, so a workgroup only ever waits for workgroups that have STARTED --
 // the decoupled look-back rule -- whatever the dispatch order (the ticket word is reset by the workgroup that draws
-// the last one).
+// the last one).  The all-views search does not use it: the argument needs ONE chain per grid.
 #define VO_CHAIN_RESIDENT_BLOCKS 256
 struct PoseIntr {
   double v[16];  // pose (qx qy qz qw tx ty tz, pad) | intrinsics (8)
@@ -101,7 +84,6 @@ __global__ __launch_bounds__(1024) void project_compact_kernel(PoseIntr pi, int 
                                                                double* __restrict__ out_uv, int32_t* __restrict__ out_idx,
                                                                int32_t* __restrict__ n_out, unsigned long long* __restrict__ chain,
                                                                unsigned int epoch, unsigned int* __restrict__ ticket) {
-  __shared__ int wave_tot[16];
   __shared__ int base_s;
   __shared__ unsigned int bid_s;
   unsigned int bid = blockIdx.x;
@@ -115,30 +97,11 @@ __global__ __launch_bounds__(1024) void project_compact_kernel(PoseIntr pi, int 
     bid = bid_s;
   }
   const int i = (int)bid * 1024 + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  bool ok = false;
   double u = 0, v = 0;
-  if (i < n) {
-    const double* pose = pi.v;
-    const double qi[4] = {-pose[0], -pose[1], -pose[2], pose[3]};
-    const double nt[3] = {pose[4] * -1.0, pose[5] * -1.0, pose[6] * -1.0};
-    double ti[3], rp[3];
-    quat_rotate_d(qi, nt, ti);
-    const double p[3] = {points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]};
-    quat_rotate_d(qi, p, rp);
-    const double pc[3] = {rp[0] + ti[0], rp[1] + ti[1], rp[2] + ti[2]};
-    ok = !(pc[2] < z_thr);
-    if (ok) {
-      project_exact(model, pi.v + 8, pc[0], pc[1], pc[2], u, v);
-      ok = !(u > (double)width || v > (double)height || u < 0 || v < 0);
-    }
-  }
-  const unsigned long long m = __ballot(ok);
-  if (lane == 0) wave_tot[wave] = __popcll(m);
-  __syncthreads();
+  const bool ok = i < n && project_in_view(pi.v, model, pi.v + 8, width, height, points + 3 * (size_t)i, z_thr, u, v);
+  int total;
+  const int slot = wg1024_ordered_slot(ok, total);
   if (threadIdx.x == 0) {
-    int total = 0;
-    for (int w = 0; w < 16; w++) total += wave_tot[w];
     unsigned long long prev = 0;
     if (bid > 0) {
       do {
@@ -153,150 +116,112 @@ __global__ __launch_bounds__(1024) void project_compact_kernel(PoseIntr pi, int 
   }
   __syncthreads();
   if (ok) {
-    int off = base_s;
-    for (int w = 0; w < wave; w++) off += wave_tot[w];
-    const int p = off + __popcll(m & ((1ull << lane) - 1ull));
+    const int p = base_s + slot;
     out_uv[2 * (size_t)p] = u;
     out_uv[2 * (size_t)p + 1] = v;
     out_idx[p] = i;
   }
 }
 
-// one wavefront per keypoint; result[k] = matched landmark index or -1
-__global__ __launch_bounds__(256) void find_matches_kernel(const double* __restrict__ kp_xy, const uint64_t* __restrict__ kp_desc,
-                                                           int n_kp, const double* __restrict__ proj_uv,
-                                                           const int32_t* __restrict__ proj_lm, int n_proj,
+__device__ __forceinline__ void load_descriptor(const uint64_t* __restrict__ desc, uint32_t (&d)[8]) {
+  const uint32_t* p = (const uint32_t*)desc;
+#pragma unroll
+  for (int q = 0; q < 8; q++) d[q] = p[q];
+}
+
+// view = blockIdx.y, keypoint = 4 * blockIdx.x + wave; result[k0 + k] = landmark index or -1 for the view's keypoints
+// [k0, k0 + n_kp) = [kp_start[view], kp_start[view + 1]), against the view's row (stride n_lms) of compacted
+// projections, n_proj_dev[view] of them (read through L2: a row is shared by every workgroup of the view; DESIGN.md
+// "Landmark fusion" on why it is not staged through LDS).  The one-view host-buffer call passes its header as
+// arguments: a null kp_start means [0, n_kp), a null n_proj_dev means n_proj.
+__global__ __launch_bounds__(256) void find_matches_kernel(const int32_t* __restrict__ kp_start, int n_kp,
+                                                           const double* __restrict__ kp_xy, const uint64_t* __restrict__ kp_desc,
+                                                           const double* __restrict__ proj_uv, const int32_t* __restrict__ proj_lm,
+                                                           const int32_t* __restrict__ n_proj_dev, int n_proj, int n_lms,
                                                            const int32_t* __restrict__ lm_obs_start,
                                                            const uint64_t* __restrict__ obs_desc, double max_dist_sq,
-                                                           int threshold, double dist_2_best, int32_t* __restrict__ result,
-                                                           const int32_t* __restrict__ kp_xy_i32,
-                                                           const int32_t* __restrict__ obs_index,
-                                                           const int32_t* __restrict__ n_kp_dev, int result_cap,
-                                                           const int32_t* __restrict__ n_proj_dev,
-                                                           int32_t* __restrict__ mail_hdr,
-                                                           const int32_t* __restrict__ tie_count_dev,
-                                                           int32_t* __restrict__ mail_xy) {
-  // Device-resident callers (vsl_map_track) pass the keypoints of a frame store slot (int32 positions,
-  // count on the device), the number of projected landmarks on the device, and observation descriptors
-  // through an index into the map's descriptor pool; the host-buffer entry point passes none of them.
-  if (n_kp_dev) n_kp = *n_kp_dev;
-  if (n_proj_dev) n_proj = *n_proj_dev;
-  if (mail_hdr && blockIdx.x == 0 && threadIdx.x == 0) {  // the header of the caller's mailbox (vsl_map_track)
+                                                           int threshold, double dist_2_best, int32_t* __restrict__ result) {
+  const int view = blockIdx.y;
+  const int k0 = kp_start ? kp_start[view] : 0;
+  if (kp_start) n_kp = kp_start[view + 1] - k0;
+  if (n_proj_dev) n_proj = n_proj_dev[view];
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (k >= n_kp) return;  // wave-uniform
+  const size_t kg = (size_t)k0 + (size_t)k;
+  const size_t row = (size_t)view * (size_t)n_lms;
+  uint32_t d[8];
+  load_descriptor(kp_desc + 4 * kg, d);
+  const int res = guided_search_wave(kp_xy[2 * kg], kp_xy[2 * kg + 1], d, proj_uv + 2 * row, proj_lm + row, n_proj, lm_obs_start,
+                                     obs_desc, nullptr, max_dist_sq, threshold, dist_2_best, lane);
+  if (lane == 0) result[kg] = res;
+}
+
+// The tracker's search (vsl_map_track_corners): the keypoints of a frame store slot (int32 positions, count on the
+// device), the number of projected landmarks on the device, observation descriptors through obs_index into the map's
+// descriptor pool.  result and mail_hdr are the caller's pinned mailbox: every slot below result_cap gets its landmark
+// or -1 (nobody memsets the array), the header is (n_proj, the frame store's near-tie count, n_kp), and with mail_xy
+// the keypoint's position rides along (the host needs it for PnP).
+__global__ __launch_bounds__(256) void track_matches_kernel(const int32_t* __restrict__ kp_xy, const uint64_t* __restrict__ kp_desc,
+                                                            const int32_t* __restrict__ n_kp_dev, int result_cap,
+                                                            const double* __restrict__ proj_uv, const int32_t* __restrict__ proj_lm,
+                                                            const int32_t* __restrict__ n_proj_dev,
+                                                            const int32_t* __restrict__ lm_obs_start,
+                                                            const uint64_t* __restrict__ obs_desc,
+                                                            const int32_t* __restrict__ obs_index, double max_dist_sq,
+                                                            int threshold, double dist_2_best, int32_t* __restrict__ result,
+                                                            int32_t* __restrict__ mail_hdr, const int32_t* __restrict__ tie_count_dev,
+                                                            int32_t* __restrict__ mail_xy) {
+  const int n_kp = *n_kp_dev, n_proj = *n_proj_dev;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
     mail_hdr[0] = n_proj;
-    mail_hdr[1] = tie_count_dev ? *tie_count_dev : 0;
+    mail_hdr[1] = *tie_count_dev;
     mail_hdr[2] = n_kp;
   }
   const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (k >= n_kp) {  // wave-uniform; the slot still gets its "no match" (the callers no longer memset the array)
+  if (k >= n_kp) {  // wave-uniform
     if (lane == 0 && k < result_cap) result[k] = -1;
     return;
   }
-  const double kx = kp_xy_i32 ? (double)kp_xy_i32[2 * (size_t)k] : kp_xy[2 * (size_t)k];
-  const double ky = kp_xy_i32 ? (double)kp_xy_i32[2 * (size_t)k + 1] : kp_xy[2 * (size_t)k + 1];
-  if (mail_xy && lane == 0 && kp_xy_i32) {  // the keypoint's position rides along (the host needs it for PnP)
-    mail_xy[2 * (size_t)k] = kp_xy_i32[2 * (size_t)k];
-    mail_xy[2 * (size_t)k + 1] = kp_xy_i32[2 * (size_t)k + 1];
+  const int x = kp_xy[2 * (size_t)k], y = kp_xy[2 * (size_t)k + 1];
+  if (mail_xy && lane == 0) {
+    mail_xy[2 * (size_t)k] = x;
+    mail_xy[2 * (size_t)k + 1] = y;
   }
   uint32_t d[8];
-  {
-    const uint32_t* p = (const uint32_t*)(kp_desc + 4 * (size_t)k);
-#pragma unroll
-    for (int q = 0; q < 8; q++) d[q] = p[q];
-  }
-  int count = 0, top_d = 0, other_d = 0, other_id = 0;
-  for (int base = 0; base < n_proj; base += 64) {
-    const int j = base + lane;
-    bool hit = false;
-    if (j < n_proj) {
-      const double dx = kx - proj_uv[2 * (size_t)j], dy = ky - proj_uv[2 * (size_t)j + 1];
-      // the reference tests (p_2d - kp).norm() < match_max_dist_2d (vo_utils.h:108); max_dist_sq is the host-computed
-      // double T with sqrt(x) < match_max_dist_2d <=> x < T for every x >= 0 (sqrt_less_threshold, cam_device.h): the same
-      // decisions bit for bit without ~40 instructions of fp64 square root per lane and chunk
-      hit = dx * dx + dy * dy < max_dist_sq;
-    }
-    unsigned long long mask = __ballot(hit);
-    while (mask) {
-      const int b = __ffsll((long long)mask) - 1;
-      mask &= mask - 1;
-      const int l = proj_lm[base + b];
-      const int o0 = lm_obs_start[l], o1 = lm_obs_start[l + 1];
-      int best = 256;  // minimal_dist, vo_utils.h:116
-      for (int o = o0 + lane; o < o1; o += 64) {
-        const uint32_t* od = (const uint32_t*)(obs_desc + 4 * (size_t)(obs_index ? obs_index[o] : o));
-        int dist = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) dist += __builtin_popcount(d[q] ^ od[q]);
-        best = min(best, dist);
-      }
-#pragma unroll
-      for (int s = 32; s > 0; s >>= 1) best = min(best, __shfl_xor(best, s));
-      // libstdc++ partial_sort(first, first + 2, last) as a streaming state machine (see the file header)
-      if (count == 0) {
-        other_d = best;
-        other_id = l;
-      } else if (count == 1) {
-        // e0 = (other_id, other_d) so far, e1 = (l, best)
-        if (best < other_d) {  // d1 < d0: top = e0, other = e1
-          top_d = other_d;
-          other_d = best;
-          other_id = l;
-        } else {  // top = e1, other = e0
-          top_d = best;
-        }
-      } else if (best < top_d) {
-        if (other_d < best) {
-          top_d = best;
-        } else {
-          top_d = other_d;
-          other_d = best;
-          other_id = l;
-        }
-      }
-      count++;
-    }
-  }
-  if (lane == 0) {
-    int res = -1;
-    if (count > 0 && !(other_d >= threshold)) {
-      const double second = count < 2 ? 256.0 : (double)top_d;  // vo_utils.h:146-160
-      if (!(second < (double)other_d * dist_2_best)) res = other_id;
-    }
-    result[k] = res;
-  }
+  load_descriptor(kp_desc + 4 * (size_t)k, d);
+  const int res = guided_search_wave((double)x, (double)y, d, proj_uv, proj_lm, n_proj, lm_obs_start, obs_desc, obs_index,
+                                     max_dist_sq, threshold, dist_2_best, lane);
+  if (lane == 0) result[k] = res;
 }
 
-__global__ __launch_bounds__(1024) void compact_matches_kernel(const int32_t* __restrict__ result, int n, int32_t* __restrict__ pairs,
-                                                               int32_t* __restrict__ n_out) {
-  __shared__ int wave_tot[16];
-  __shared__ int base_s;
-  if (threadIdx.x == 0) base_s = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// view = blockIdx.x: the matched keypoints of the view's range (as in find_matches_kernel: a null kp_start means
+// [0, n_kp)), in feature order, as (feature, landmark) pairs at pairs[2 * k0 ..) and their number in n_pairs[view]
+__global__ __launch_bounds__(1024) void compact_matches_kernel(const int32_t* __restrict__ kp_start, int n_kp,
+                                                               const int32_t* __restrict__ result, int32_t* __restrict__ pairs,
+                                                               int32_t* __restrict__ n_pairs) {
+  const int k0 = kp_start ? kp_start[blockIdx.x] : 0;
+  const int n = kp_start ? kp_start[blockIdx.x + 1] - k0 : n_kp;
+  result += k0;
+  pairs += 2 * (size_t)k0;
+  int base = 0;
   for (int i0 = 0; i0 < n; i0 += 1024) {
     const int i = i0 + threadIdx.x;
     const int r = i < n ? result[i] : -1;
-    const bool ok = r >= 0;
-    const unsigned long long m = __ballot(ok);
-    if (lane == 0) wave_tot[wave] = __popcll(m);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wave; w++) off += wave_tot[w];
-    if (ok) {
-      const int p = off + __popcll(m & ((1ull << lane) - 1ull));
+    int total;
+    const int p = base + wg1024_ordered_slot(r >= 0, total);
+    if (r >= 0) {
       pairs[2 * (size_t)p] = i;
       pairs[2 * (size_t)p + 1] = r;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int t = 0;
-      for (int w = 0; w < 16; w++) t += wave_tot[w];
-      base_s += t;
-    }
-    __syncthreads();
+    base += total;
+    __syncthreads();  // the next chunk rewrites the wave totals
   }
-  if (threadIdx.x == 0) *n_out = base_s;
+  if (threadIdx.x == 0) n_pairs[blockIdx.x] = base;
 }
+
+inline size_t up64(size_t b) { return (b + 63) & ~(size_t)63; }
 
 }  // namespace
 
@@ -325,8 +250,8 @@ extern "C" int vsl_project_landmarks(vsl_ctx* ctx, const double* pose7, int cam_
   VSL_HIP(ctx, hipMemcpyAsync(dpose, pose7, 56, hipMemcpyHostToDevice, ctx->stream));
   VSL_HIP(ctx, hipMemcpyAsync(dintr, intr8, 64, hipMemcpyHostToDevice, ctx->stream));
   VSL_HIP(ctx, hipMemcpyAsync(dpts, points, 24 * N, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(project_landmarks_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dpose, cam_model, dintr, width,
-                     height, dpts, n, cam_z_threshold, duv, dkeep);
+  hipLaunchKernelGGL(project_kernel, dim3((n + 1023) / 1024), dim3(1024), 0, ctx->stream, dpose, cam_model, dintr, width, height,
+                     dpts, n, cam_z_threshold, duv, dkeep);
   hipLaunchKernelGGL(compact_projection_kernel, dim3(1), dim3(1024), 0, ctx->stream, duv, dkeep, n, douv, didx, dn);
   VSL_CHECK_LAUNCH(ctx);
   // one round trip: count and full-capacity outputs into pinned memory together
@@ -383,11 +308,11 @@ extern "C" int vsl_find_matches_landmarks(vsl_ctx* ctx, const double* kp_xy, con
   if (T) VSL_HIP(ctx, hipMemcpyAsync(dod, obs_desc, 32 * T, hipMemcpyHostToDevice, ctx->stream));
   VSL_HIP(ctx, hipMemcpyAsync(dplm, proj_lm, 4 * P, hipMemcpyHostToDevice, ctx->stream));
   VSL_HIP(ctx, hipMemcpyAsync(dstart, lm_obs_start, 4 * (L + 1), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(find_matches_kernel, dim3((n_kp + 3) / 4), dim3(256), 0, ctx->stream, dkxy, dkd, n_kp, dpuv, dplm, n_proj,
-                     dstart, dod, sqrt_less_threshold(match_max_dist_2d), feature_match_threshold, feature_match_dist_2_best, dres,
-                     (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, n_kp, (const int32_t*)nullptr,
-                     (int32_t*)nullptr, (const int32_t*)nullptr, (int32_t*)nullptr);
-  hipLaunchKernelGGL(compact_matches_kernel, dim3(1), dim3(1024), 0, ctx->stream, dres, n_kp, dpairs, dn);
+  // one view: its header (keypoints [0, n_kp), n_proj projections) travels as kernel arguments
+  hipLaunchKernelGGL(find_matches_kernel, dim3((n_kp + 3) / 4), dim3(256), 0, ctx->stream, (const int32_t*)nullptr, n_kp, dkxy, dkd,
+                     dpuv, dplm, (const int32_t*)nullptr, n_proj, n_proj, dstart, dod, sqrt_less_threshold(match_max_dist_2d),
+                     feature_match_threshold, feature_match_dist_2_best, dres);
+  hipLaunchKernelGGL(compact_matches_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t*)nullptr, n_kp, dres, dpairs, dn);
   VSL_CHECK_LAUNCH(ctx);
   void* hp = nullptr;
   rc = vsl_ctx_hpinned(ctx, 64 + 8 * K, &hp);
@@ -668,11 +593,10 @@ extern "C" int vsl_map_track_corners(vsl_map* m, vsl_frames* f, int slot, const 
   int32_t* mail = m->mailbox;
   const double max_dist_sq = sqrt_less_threshold(match_max_dist_2d);
   for (int attempt = 0; attempt < 2; attempt++) {
-    hipLaunchKernelGGL(find_matches_kernel, dim3((f->F + 3) / 4), dim3(256), 0, ctx->stream, (const double*)nullptr,
-                       f->kp_desc + 4 * (size_t)slot * f->F, f->F, m->out_uv, m->out_idx, n, m->obs_start, m->pool,
-                       max_dist_sq, feature_match_threshold, feature_match_dist_2_best, mail + 4,
-                       f->kp_xy + 2 * (size_t)slot * f->F, m->obs_index, f->kp_count + slot, f->F, m->counters, mail,
-                       f->ties_pending ? f->tie_count : (const int32_t*)nullptr, corners_xy ? mail + 4 + f->F : (int32_t*)nullptr);
+    hipLaunchKernelGGL(track_matches_kernel, dim3((f->F + 3) / 4), dim3(256), 0, ctx->stream, f->kp_xy + 2 * (size_t)slot * f->F,
+                       f->kp_desc + 4 * (size_t)slot * f->F, f->kp_count + slot, f->F, m->out_uv, m->out_idx, m->counters,
+                       m->obs_start, m->pool, m->obs_index, max_dist_sq, feature_match_threshold, feature_match_dist_2_best,
+                       mail + 4, mail, f->tie_count, corners_xy ? mail + 4 + f->F : (int32_t*)nullptr);
     VSL_CHECK_LAUNCH(ctx);
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // The descriptors of the slot must be final (rBRIEF near-tie guard, describe.hip).  The guard's count came along
@@ -701,6 +625,125 @@ extern "C" int vsl_map_track_corners(vsl_map* m, vsl_frames* f, int slot, const 
     const int32_t* xy = mail + 4 + f->F;
     for (int k = 0; k < 2 * nk; k++) corners_xy[k] = (double)xy[k];
     *n_corners = nk;
+  }
+  return VSL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The guided search of landmark fusion after a loop closure, for ALL views in one call (DESIGN.md "Landmark fusion"):
+// vsl_fuse_search(view v) == vsl_project_landmarks(pose v) followed by vsl_find_matches_landmarks(keypoints of v), pair
+// for pair -- the same four kernels with a view dimension.  One packed upload (landmark points and observation
+// descriptors once, shared by all views), four launches on the context's stream with nothing between them, one download.
+// No workgroup waits for another one: every scan is private to one workgroup, and the prefix over the <= 64 per-view
+// pair counts is taken by the host while it copies the segments out of the pinned download buffer.
+extern "C" int vsl_fuse_search(vsl_ctx* ctx, int n_views, const double* pose7, int cam_model, const double* intr8, int width,
+                               int height, const int32_t* kp_start, const double* kp_xy, const uint64_t* kp_desc, int n_lms,
+                               const double* points, const int32_t* lm_obs_start, const uint64_t* obs_desc,
+                               double cam_z_threshold, double match_max_dist_2d, int feature_match_threshold,
+                               double feature_match_dist_2_best, int32_t* pairs, int32_t* pair_start, int32_t* n_projected) {
+  if (!ctx) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: null context");
+  if (n_views < 0 || n_lms < 0 || cam_model < 0 || cam_model > 3 || !intr8 || !pair_start)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: bad arguments");
+  if (n_views > VSL_FUSE_MAX_VIEWS)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: %d views (at most %d)", n_views, VSL_FUSE_MAX_VIEWS);
+  if (n_views > 0 && (!pose7 || !kp_start)) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: null pose7 / kp_start with %d views", n_views);
+  if (n_lms > 0 && (!points || !lm_obs_start)) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: null points / lm_obs_start with %d landmarks", n_lms);
+  int max_kp = 0;
+  if (n_views > 0) {
+    if (kp_start[0] != 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: kp_start[0] must be 0");
+    for (int v = 0; v < n_views; v++) {
+      if (kp_start[v + 1] < kp_start[v]) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: kp_start not monotone at view %d", v);
+      if (kp_start[v + 1] - kp_start[v] > max_kp) max_kp = kp_start[v + 1] - kp_start[v];
+    }
+  }
+  const int n_kp = n_views > 0 ? kp_start[n_views] : 0;
+  if (n_kp > 0 && (!kp_xy || !kp_desc || !pairs)) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: null kp_xy / kp_desc / pairs with %d keypoints", n_kp);
+  int n_obs = 0;
+  if (n_lms > 0) {
+    if (lm_obs_start[0] != 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: lm_obs_start[0] must be 0");
+    for (int l = 0; l < n_lms; l++)
+      if (lm_obs_start[l + 1] < lm_obs_start[l]) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: lm_obs_start not monotone at landmark %d", l);
+    n_obs = lm_obs_start[n_lms];
+  }
+  if (n_obs > 0 && !obs_desc) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_fuse_search: null obs_desc with %d observations", n_obs);
+  for (int v = 0; v <= n_views; v++) pair_start[v] = 0;
+  if (n_projected)
+    for (int v = 0; v < n_views; v++) n_projected[v] = 0;
+  if (n_views == 0 || n_lms == 0) return VSL_OK;
+
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t V = (size_t)n_views, N = (size_t)n_lms, K = (size_t)n_kp, T = (size_t)n_obs;
+  // the upload block, one layout on the host (pinned) and on the device:
+  //   pose (8 V) | intr (8) | points (3 N) | kp_xy (2 K) | kp_desc (4 K) | obs_desc (4 T) | kp_start (V + 1) | lm_obs_start (N + 1)
+  const size_t o_pose = 0, o_intr = o_pose + 64 * V, o_pts = o_intr + 64, o_kxy = up64(o_pts + 24 * N), o_kd = up64(o_kxy + 16 * K),
+               o_od = up64(o_kd + 32 * K), o_ks = up64(o_od + 32 * T), o_ls = up64(o_ks + 4 * (V + 1)),
+               up_bytes = up64(o_ls + 4 * (N + 1));
+  // the download block: n_proj (V) | n_pairs (V) | pairs (2 K, every view's segment at its kp_start)
+  const size_t o_np = 0, o_nm = up64(4 * V), o_pairs = up64(o_nm + 4 * V), down_bytes = up64(o_pairs + 8 * K);
+  // device-only scratch: uv (2 V N) | out_uv (2 V N) | out_idx (V N) | result (K) | keep (V N)
+  const size_t o_uv = 0, o_ouv = o_uv + up64(16 * V * N), o_oidx = o_ouv + up64(16 * V * N), o_res = o_oidx + up64(4 * V * N),
+               o_keep = o_res + up64(4 * K), scr_bytes = o_keep + up64(V * N);
+  void* dv = nullptr;
+  int rc = vsl_ctx_dscratch(ctx, up_bytes + down_bytes + scr_bytes, &dv);
+  if (rc) return rc;
+  void* hv = nullptr;
+  if ((rc = vsl_ctx_hpinned(ctx, up_bytes + down_bytes, &hv))) return rc;
+  char* h_up = (char*)hv;
+  char* h_down = h_up + up_bytes;
+  char* d_up = (char*)dv;
+  char* d_down = d_up + up_bytes;
+  char* d_scr = d_down + down_bytes;
+
+  for (size_t v = 0; v < V; v++) {
+    std::memcpy(h_up + o_pose + 64 * v, pose7 + 7 * v, 56);
+    std::memset(h_up + o_pose + 64 * v + 56, 0, 8);
+  }
+  std::memcpy(h_up + o_intr, intr8, 64);
+  std::memcpy(h_up + o_pts, points, 24 * N);
+  if (K) std::memcpy(h_up + o_kxy, kp_xy, 16 * K);
+  if (K) std::memcpy(h_up + o_kd, kp_desc, 32 * K);
+  if (T) std::memcpy(h_up + o_od, obs_desc, 32 * T);
+  std::memcpy(h_up + o_ks, kp_start, 4 * (V + 1));
+  std::memcpy(h_up + o_ls, lm_obs_start, 4 * (N + 1));
+  VSL_HIP(ctx, hipMemcpyAsync(d_up, h_up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+
+  const double* d_pose = (const double*)(d_up + o_pose);
+  const double* d_intr = (const double*)(d_up + o_intr);
+  const double* d_pts = (const double*)(d_up + o_pts);
+  const double* d_kxy = (const double*)(d_up + o_kxy);
+  const uint64_t* d_kd = (const uint64_t*)(d_up + o_kd);
+  const uint64_t* d_od = (const uint64_t*)(d_up + o_od);
+  const int32_t* d_ks = (const int32_t*)(d_up + o_ks);
+  const int32_t* d_ls = (const int32_t*)(d_up + o_ls);
+  int32_t* d_np = (int32_t*)(d_down + o_np);
+  int32_t* d_nm = (int32_t*)(d_down + o_nm);
+  int32_t* d_pairs = (int32_t*)(d_down + o_pairs);
+  double* d_uv = (double*)(d_scr + o_uv);
+  double* d_ouv = (double*)(d_scr + o_ouv);
+  int32_t* d_oidx = (int32_t*)(d_scr + o_oidx);
+  int32_t* d_res = (int32_t*)(d_scr + o_res);
+  uint8_t* d_keep = (uint8_t*)(d_scr + o_keep);
+
+  hipLaunchKernelGGL(project_kernel, dim3((n_lms + 1023) / 1024, n_views), dim3(1024), 0, ctx->stream, d_pose, cam_model, d_intr,
+                     width, height, d_pts, n_lms, cam_z_threshold, d_uv, d_keep);
+  hipLaunchKernelGGL(compact_projection_kernel, dim3(n_views), dim3(1024), 0, ctx->stream, d_uv, d_keep, n_lms, d_ouv, d_oidx, d_np);
+  if (max_kp > 0)
+    hipLaunchKernelGGL(find_matches_kernel, dim3((max_kp + 3) / 4, n_views), dim3(256), 0, ctx->stream, d_ks, 0, d_kxy, d_kd, d_ouv,
+                       d_oidx, d_np, 0, n_lms, d_ls, d_od, sqrt_less_threshold(match_max_dist_2d), feature_match_threshold,
+                       feature_match_dist_2_best, d_res);
+  hipLaunchKernelGGL(compact_matches_kernel, dim3(n_views), dim3(1024), 0, ctx->stream, d_ks, 0, d_res, d_pairs, d_nm);
+  VSL_CHECK_LAUNCH(ctx);
+  VSL_HIP(ctx, hipMemcpyAsync(h_down, d_down, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
+  const int32_t* h_np = (const int32_t*)(h_down + o_np);
+  const int32_t* h_nm = (const int32_t*)(h_down + o_nm);
+  const int32_t* h_pairs = (const int32_t*)(h_down + o_pairs);
+  for (size_t v = 0; v < V; v++) {
+    if (n_projected) n_projected[v] = h_np[v];
+    const int32_t m = h_nm[v];
+    if (m > 0) std::memcpy(pairs + 2 * (size_t)pair_start[v], h_pairs + 2 * (size_t)kp_start[v], 8 * (size_t)m);
+    pair_start[v + 1] = pair_start[v] + m;
   }
   return VSL_OK;
 }
