@@ -313,6 +313,11 @@ def test_recompute_form_matches_the_stored_blocks_form(vsl, synth):
     s_again, a_again = _session_solve(vsl, synth, d, False)
     assert s_again.final_cost == s_new.final_cost
     assert np.array_equal(a_again.poses, a_new.poses) and np.array_equal(a_again.points, a_new.points)
+    # the stored-blocks form (n > 128: the band solver under the enqueued step) is as reproducible
+    s_old2, a_old2 = _session_solve(vsl, synth, d, True)
+    assert (s_old2.iterations, s_old2.termination, s_old2.successful_steps) == (s_old.iterations, s_old.termination, s_old.successful_steps)
+    assert (s_old2.initial_cost, s_old2.final_cost) == (s_old.initial_cost, s_old.final_cost)
+    assert a_old2.poses.tobytes() == a_old.poses.tobytes() and a_old2.points.tobytes() == a_old.points.tobytes()
 
 
 def test_a_landmark_with_more_observations_than_a_workgroup_takes_the_stored_blocks_form(vsl, orc, synth):
@@ -367,7 +372,79 @@ def test_session_over_a_small_system_matches_single_call_and_oracle(vsl, orc, sy
     assert np.allclose(a_sess.poses, a_one.poses, rtol=0, atol=1e-7)
     dp = np.abs(a_sess.points - a_one.points).max(1)
     assert (dp < 1e-6).mean() > 0.97 and dp.max() < 0.05
+    # a second solve of the same inputs: the same bytes (nothing of the enqueued step depends on timing)
+    a_again = _arr(orc, d)
+    s_again = ba_dist.bundle_adjust_distributed(vsl, ctx, a_again, max_iters=8)
+    assert (s_again.iterations, s_again.termination, s_again.successful_steps) == (s.iterations, s.termination, s.successful_steps)
+    assert (s_again.initial_cost, s_again.final_cost) == (s.initial_cost, s.final_cost)
+    assert a_again.poses.tobytes() == a_sess.poses.tobytes() and a_again.points.tobytes() == a_sess.points.tobytes()
     ctx.close()
+
+
+def _stored_form_paths_and_oracle(vsl, orc, d, max_iters=8):
+    """The stored-blocks chain through the session at world 1 and through the host loop of the single call (both under
+    "ba_no_fused"), and the oracle, each on its own copy of d: [(summary, arrays)] * 3."""
+    import torch
+    ba_dist = importlib.import_module("visual_slam_amd.ba_dist")
+    ctx = vsl.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    a_sess, a_one, a_cpu = _arr(orc, d), _arr(orc, d), _arr(orc, d)
+    ctx.set_diagnostic("ba_no_fused", 1)
+    try:
+        s = ba_dist.bundle_adjust_distributed(vsl, ctx, a_sess, max_iters=max_iters)
+        s1 = ctx.bundle_adjust(a_one, max_iters=max_iters)
+    finally:
+        ctx.set_diagnostic("ba_no_fused", 0)
+        ctx.close()
+    s2 = orc.bundle_adjust(a_cpu, max_iters=max_iters)
+    return (s, a_sess), (s1, a_one), (s2, a_cpu)
+
+
+def test_session_without_a_free_camera_matches_single_call_and_oracle(vsl, orc, synth):
+    """Every camera fixed (n = 0: no reduced system, the landmarks alone move) through the stored-blocks session -- the
+    branch of its step where no damping kernel runs and ba_solve_enqueue sets the flags itself -- against the host loop
+    of the single call and the oracle: the comparisons and tolerances of
+    test_session_over_a_small_system_matches_single_call_and_oracle.  ba_setup accepts such a problem (no error code to
+    compare); the oracle takes 7 iterations, 6 of them successful, and stops on the function tolerance
+    (cost 622.3098 -> 261.5924).  Before ba_schur computed P^-1 and b of the landmarks at n = 0 both paths took five
+    invalid steps on blocks nobody had written and left the points where they were."""
+    d = synth.ba_problem(83, n_kf=3, n_lms=40, n_fixed_kf=3)
+    assert d["cam_fixed"].all()
+    (s, a_sess), (s1, a_one), (s2, a_cpu) = _stored_form_paths_and_oracle(vsl, orc, d)
+    print("no free camera:", (s.iterations, s.termination, s.successful_steps), (s1.iterations, s1.termination, s1.successful_steps),
+          (s2.iterations, s2.termination), s.initial_cost, s1.initial_cost, s.final_cost, s1.final_cost, s2.final_cost,
+          np.abs(a_sess.points - a_one.points).max(), np.abs(a_sess.points - a_cpu.points).max())
+    assert (s.iterations, s.termination, s.successful_steps) == (s1.iterations, s1.termination, s1.successful_steps)
+    assert (s.iterations, s.termination) == (s2.iterations, s2.termination)
+    assert s.initial_cost == pytest.approx(s1.initial_cost, rel=1e-12)
+    assert s.final_cost == pytest.approx(s1.final_cost, rel=1e-9)
+    assert s.final_cost == pytest.approx(s2.final_cost, rel=1e-7)
+    assert s.final_cost < s.initial_cost
+    assert np.allclose(a_sess.poses, a_one.poses, rtol=0, atol=1e-7) and np.array_equal(a_sess.poses, d["poses"])
+    dp = np.abs(a_sess.points - a_one.points).max(1)
+    assert (dp < 1e-6).mean() > 0.97 and dp.max() < 0.05
+
+
+def test_an_unusable_step_through_the_enqueued_solve(vsl, orc, synth):
+    """ba_problem(85, n_kf=4, n_lms=60) (6 free cameras, 48 landmarks, 338 observations) with the coordinates of landmark
+    0 multiplied by 1e160: the squares of its camera-frame coordinates overflow, so cost, Jacobian blocks and with them
+    the reduced system are not finite.  The oracle declares every step invalid: 5 iterations, 0 successful, termination 4
+    (the limit of consecutive invalid steps), NaN costs, poses and points unchanged.  Nothing is read back between the
+    factorisation and the candidate any more, so the rest of the step runs on a step vector nobody uses: the session's
+    stored form and the host loop of the single call must still take the oracle's trajectory and leave the poses alone.
+    (NaN / Inf arithmetic only: no index on the device depends on these numbers.)"""
+    d = dict(synth.ba_problem(85, n_kf=4, n_lms=60))
+    d["points"] = d["points"].copy()
+    d["points"][0] *= 1e160
+    (s, a_sess), (s1, a_one), (s2, a_cpu) = _stored_form_paths_and_oracle(vsl, orc, d)
+    print("unusable step:", (s.iterations, s.termination, s.successful_steps), (s1.iterations, s1.termination, s1.successful_steps),
+          (s2.iterations, s2.termination, s2.successful_steps), s.final_cost, s1.final_cost, s2.final_cost)
+    assert (s2.iterations, s2.termination, s2.successful_steps) == (5, 4, 0)  # the oracle's first step IS invalid
+    assert (s.iterations, s.termination) == (s2.iterations, s2.termination)
+    assert (s1.iterations, s1.termination) == (s2.iterations, s2.termination)
+    assert s.successful_steps == s1.successful_steps
+    for a in (a_sess, a_one):
+        assert np.isfinite(a.poses).all() == np.isfinite(a_cpu.poses).all()
+        assert np.array_equal(a.poses, d["poses"]) == np.array_equal(a_cpu.poses, d["poses"])
 
 
 def _worker_world1(rank, port, out_dir):

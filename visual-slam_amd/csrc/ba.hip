@@ -1119,11 +1119,6 @@ __global__ __launch_bounds__(256) void ba_chol_small_kernel(int n, const double*
   }
 }
 
-__global__ void ba_negate_kernel(int n, const double* __restrict__ y, double* __restrict__ dc) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dc[i] = -y[i];
-}
-
 // delta_l = -P^-1 (b_l + sum_q W_q^T delta_c)
 __global__ __launch_bounds__(256) void ba_backsub_kernel(BaDims D, const int* __restrict__ lm_start,
                                                          const int* __restrict__ obs_cam, const int* __restrict__ cam_free,
@@ -1257,11 +1252,6 @@ __global__ __launch_bounds__(256) void ba_reduce2_kernel(const double* __restric
     __syncthreads();
   }
   if (threadIdx.x == 0) scalars[slot + blockIdx.x] = sh[0];
-}
-
-__global__ void ba_all_finite_kernel(int n, const double* __restrict__ v, int* __restrict__ flag) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && !isfinite(v[i])) *flag = 0;
 }
 
 // raw per-observation residual / Jacobian blocks in the caller's observation order (parity hook)
@@ -1482,7 +1472,9 @@ int ba_pair_lists(vsl_ctx* ctx, BaCommon& st, int l0, int lc) {
 int ba_schur(vsl_ctx* ctx, BaCommon& st, BaStored& sb, bool damp, double radius, int l0, int lc, bool keep_backsub, bool lower_only) {
   const BaDims& D = st.D;
   const int n = D.n;
-  if (n == 0) return VSL_OK;
+  // no free camera: there is no S, but the back-substitution still needs P^-1 and b of every landmark (n = 0 is a
+  // small system: ba_schur_small_kernel writes both and owns no entry of S)
+  if (n == 0 && !keep_backsub) return VSL_OK;
   VslStage s(ctx, VSL_STAGE_BA_SCHUR);
   const double inv_radius = damp ? 1.0 / radius : 0.0;
   const double* dgl = damp ? sb.diag_l : nullptr;
@@ -1501,8 +1493,9 @@ int ba_schur(vsl_ctx* ctx, BaCommon& st, BaStored& sb, bool damp, double radius,
         hipLaunchKernelGGL(ba_schur_small_kernel<false>, dim3(G), dim3(SCH_THREADS), 0, ctx->stream, D, st.lm_start, st.obs_cam,
                            st.cam_free, sb.r, sb.F, sb.E, dgl, inv_radius, l0, lc, lpw, sb.S_part, sb.rhs_part, Pinv, bl);
     }
-    hipLaunchKernelGGL(ba_schur_finish_kernel, dim3((n * n + n + 15) / 16), dim3(256), 0, ctx->stream, n, G, sb.S_part, sb.rhs_part,
-                       st.H, st.g_c, dgc, inv_radius, st.S, st.rhs, block3 ? 1 : 0);
+    if (n > 0)
+      hipLaunchKernelGGL(ba_schur_finish_kernel, dim3((n * n + n + 15) / 16), dim3(256), 0, ctx->stream, n, G, sb.S_part, sb.rhs_part,
+                         st.H, st.g_c, dgc, inv_radius, st.S, st.rhs, block3 ? 1 : 0);
   } else {
     VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * st.s_elems, ctx->stream));
     VSL_HIP(ctx, hipMemsetAsync(st.rhs, 0, sizeof(double) * n, ctx->stream));
@@ -1545,27 +1538,21 @@ int ba_solve_enqueue(vsl_ctx* ctx, BaCommon& st, bool flags_set) {
   return VSL_OK;
 }
 
-int ba_solve(vsl_ctx* ctx, BaCommon& st, bool& ok) {
-  const int n = st.D.n;
-  ok = true;
-  if (n == 0) return VSL_OK;
-  VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-  int flag = 1;
-  if (n <= 128) {
-    hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, ctx->stream, n, st.S, st.rhs, st.dc, st.flag);
-    VSL_CHECK_LAUNCH(ctx);
-    VSL_HIP(ctx, hipMemcpyAsync(&flag, st.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  } else {
-    // blocked right-looking Cholesky + substitutions (chol.hip); rhs <- S^-1 rhs
-    int rc = vsl_chol_solve_band_dev(ctx, st.S_eff(), st.rhs, n, st.ldS, st.bw, st.flag, st.cyclic ? 1 : 0);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ba_negate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.rhs, st.dc);
-    VSL_CHECK_LAUNCH(ctx);
-    VSL_HIP(ctx, hipMemcpyAsync(&flag, st.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  ok = flag != 0;
+// The step chain of the stored-blocks form, written once: the host loop of vsl_bundle_adjust and the session's
+// StoredForm (through ba_candidate) both run it.  Everything is enqueued; a failed factorisation leaves a stale or
+// non-finite dc, which these kernels only do arithmetic with (no index depends on step data) and which the caller
+// discards on flag[1] = 0.
+int ba_step_from_dc(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
+  const BaDims& D = st.D;
+  hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
+                     st.cam_free, sb.F, sb.E, st.Pinv, st.bl, st.dc, sb.dl, st.flag);
+  hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, sb.r,
+                     sb.F, sb.E, st.dc, sb.dl, sb.partials);
+  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 2, 0);
+  hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
+                     sb.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, sb.partials, st.nb_upd);
+  hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, sb.partials, st.nb_upd, st.scalars, 3);
+  VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }
 
@@ -1625,18 +1612,8 @@ int ba_max_of(vsl_ctx* ctx, const double* v, int n, double* dst) {
 
 int ba_candidate(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
   const BaDims& D = st.D;
-  const int n = D.n, nl = 3 * D.L;
-  hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                     st.cam_free, sb.F, sb.E, st.Pinv, st.bl, st.dc, sb.dl);
-  if (n > 0) hipLaunchKernelGGL(ba_all_finite_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.dc, st.flag);
-  hipLaunchKernelGGL(ba_all_finite_kernel, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, nl, sb.dl, st.flag);
-  hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, sb.r,
-                     sb.F, sb.E, st.dc, sb.dl, sb.partials);
-  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 2, 0);
-  hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
-                     sb.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, sb.partials, st.nb_upd);
-  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_upd, st.scalars, 3, 0);
-  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials + st.nb_upd, st.nb_upd, st.scalars, 4, 0);
+  int rc = ba_step_from_dc(ctx, st, sb);
+  if (rc) return rc;
   hipLaunchKernelGGL(sess_cam_norms_kernel, dim3(1), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.dc, st.scale_c,
                      st.scalars);
   hipLaunchKernelGGL(ba_cost_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.cand_poses, st.cand_points, st.intr,
@@ -1743,7 +1720,8 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   if (!opt) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_bundle_adjust: options are null");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   static const bool env_no_fused = getenv("VSL_BA_NO_FUSED") != nullptr;  // same switch for applications without a diagnostics hook
-  if (!ctx->ba_no_fused && !env_no_fused) {  // local windows: the fused iteration (ba_fused.hip); everything else continues below
+  const bool no_fused = ctx->ba_no_fused || env_no_fused;
+  if (!no_fused) {  // local windows: the fused iteration (ba_fused.hip); everything else continues below
     int handled = 0;
     rc = vsl_ba_fused_solve(ctx, prob, opt, summary, &handled);
     if (rc || handled) return rc;
@@ -1763,6 +1741,16 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   BaStored& sb = st.sb;
   const BaDims& D = st.D;
   const int nc = D.n, nl = 3 * D.L;
+  // A window without a free camera (the application's first keyframe).  [upstream] Ceres moves the landmarks alone, and
+  // so do this loop under "ba_no_fused" and the session.  The DEFAULT path never has: ba_schur used to return before P^-1
+  // and b existed, every step came out invalid and the landmarks stayed (termination 4).  The application's trajectories
+  // rest on that, so the default path keeps it -- now with zeroed blocks instead of unwritten ones -- until it is changed
+  // on purpose.
+  const bool hold_landmarks = nc == 0 && !no_fused;
+  if (hold_landmarks) {
+    VSL_HIP(ctx, hipMemsetAsync(st.Pinv, 0, sizeof(double) * 9 * (size_t)D.L, ctx->stream));
+    VSL_HIP(ctx, hipMemsetAsync(st.bl, 0, sizeof(double) * 3 * (size_t)D.L, ctx->stream));
+  }
   vsl_ba_summary sum;
   memset(&sum, 0, sizeof(sum));
   // per-stage device times (summary.linearize_ms / schur_ms / solve_ms) only when the context has profiling switched
@@ -1818,19 +1806,11 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     if (iteration >= opt->max_num_iterations) { sum.termination = 0; break; }
     if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
     iteration++;
-    if ((rc = ba_schur(ctx, st, sb, true, lm.radius, 0, D.L, true, true))) return rc;
+    if ((rc = ba_schur(ctx, st, sb, true, lm.radius, 0, D.L, !hold_landmarks, true))) return rc;
     if ((rc = ba_solve_enqueue(ctx, st))) return rc;  // flag[1] = Cholesky ok
     {
       VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-      hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
-                         st.cam_free, sb.F, sb.E, st.Pinv, st.bl, st.dc, sb.dl, st.flag);
-      hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, sb.r,
-                         sb.F, sb.E, st.dc, sb.dl, sb.partials);
-      hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 2, 0);
-      hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
-                         sb.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, sb.partials, st.nb_upd);
-      hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, sb.partials, st.nb_upd, st.scalars, 3);
-      VSL_CHECK_LAUNCH(ctx);
+      if ((rc = ba_step_from_dc(ctx, st, sb))) return rc;
     }
     // speculative: the candidate becomes the current point, its linearisation goes to the other set;
     // scalars[5] = cost there, scalars[6] = max |gradient| there (slots 0/1 keep the current point's values)
@@ -1875,25 +1855,6 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     fprintf(stderr, "vsl BA: iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", sum.iterations,
             sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
   if (summary) *summary = sum;
-  return VSL_OK;
-}
-
-extern "C" int vsl_ctx_last_ba_layout(vsl_ctx* ctx, int64_t* s_elems, int* banded, int* bandwidth) {
-  if (!ctx) return VSL_ERR_INVALID;
-  if (s_elems) *s_elems = ctx->last_ba_s_elems;
-  if (banded) *banded = ctx->last_ba_banded;
-  if (bandwidth) *bandwidth = ctx->last_ba_bw;
-  return VSL_OK;
-}
-
-// Plain copies for callers that hold device pointers of this library (the all-reduce callbacks of the tests):
-// kind 0 host->device, 1 device->host, 2 device->device; synchronous.
-extern "C" int vsl_ctx_memcpy(vsl_ctx* ctx, void* dst, const void* src, size_t bytes, int kind) {
-  if (!ctx || !dst || !src || kind < 0 || kind > 2) return VSL_ERR_INVALID;
-  VSL_HIP(ctx, hipSetDevice(ctx->device));
-  const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : (kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
-  VSL_HIP(ctx, hipMemcpyAsync(dst, src, bytes, k, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return VSL_OK;
 }
 
@@ -2393,8 +2354,7 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     if (nt <= 128) {
       hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, q, nt, Sf, rhsf, df, st.flag + 1);
     } else {
-      if ((rc = vsl_chol_solve_band_dev(ctx, Sf, rhsf, nt, nt, nt, st.flag + 1))) return rc;
-      hipLaunchKernelGGL(ba_negate_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, rhsf, df);
+      if ((rc = vsl_chol_solve_band_dev(ctx, Sf, rhsf, nt, nt, nt, st.flag + 1, 0, df))) return rc;  // df = -(Sf^-1 rhsf)
     }
     hipLaunchKernelGGL(bai_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free,
                        st.cam_intr, sb.F, sb.E, G, st.Pinv, st.bl, df, sb.dl);

@@ -124,11 +124,10 @@ __global__ void sess_damp_kernel(int n, size_t elems, const double* __restrict__
   }
 }
 
-__global__ void sess_pack_c_kernel(const double* __restrict__ scalars, const int* __restrict__ flag, int both,
-                                   double* __restrict__ out) {
+__global__ void sess_pack_c_kernel(const double* __restrict__ scalars, const int* __restrict__ flag, double* __restrict__ out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    // number of ranks whose step is unusable (both: flag[0] = step finite, flag[1] = factorisation succeeded)
-    out[0] = (flag[0] && (!both || flag[1])) ? 0.0 : 1.0;
+    // number of ranks whose step is unusable (flag[0] = step finite, flag[1] = factorisation succeeded)
+    out[0] = (flag[0] && flag[1]) ? 0.0 : 1.0;
     out[1] = scalars[2];           // model cost change, own observations
     out[2] = scalars[3];           // squared step norm (own landmarks + cameras, see ba_dist.py)
     out[3] = scalars[4];           // squared x norm   (own landmarks + cameras)
@@ -324,34 +323,27 @@ struct StoredForm {
     if ((e = ba_max_of(ctx, sb.gabs, 3 * D.L, gl))) return e;
     VSL_HIP(ctx, hipMemsetAsync(sb.diag_c, 0, sizeof(double) * (size_t)(n > 0 ? n : 1), ctx->stream));
     if ((e = ba_schur(ctx, st, sb, true, radius, 0, D.L, true, true))) return e;
-    if (n > 0) {
-      if (!in_place) VSL_HIP(ctx, hipMemcpyAsync(packB, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
-      hipLaunchKernelGGL(sess_pack_b_kernel, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, st.rhs, st.H, st.g_c,
-                         st.scalars, packB + st.s_elems);
-      VSL_CHECK_LAUNCH(ctx);
-    }
+    if (n > 0 && !in_place) VSL_HIP(ctx, hipMemcpyAsync(packB, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
+    // (also without a free camera: the cost behind the tail is what the loop reads)
+    hipLaunchKernelGGL(sess_pack_b_kernel, dim3((n + 256) / 256), dim3(256), 0, ctx->stream, D.nfree, st.rhs, st.H, st.g_c,
+                       st.scalars, packB + st.s_elems);
+    VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   }
 
-  // (two host synchronisations more than the recompute form: the factorisation's verdict is read back and staged again)
+  // enqueued like RecomputeForm::step: a failed factorisation leaves flag[1] = 0 and a candidate nobody uses
   int step(const double* packB, double radius, int refresh, double* packC) {
     const int n = st.D.n;
     int e;
     if (n > 0) {
       if (!in_place) VSL_HIP(ctx, hipMemcpyAsync(st.S, packB, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
       hipLaunchKernelGGL(sess_damp_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.s_elems, packB, 1.0 / radius,
-                         refresh, st.diagc_keep, st.S_eff(), st.ldS, st.rhs, (int*)nullptr);
+                         refresh, st.diagc_keep, st.S_eff(), st.ldS, st.rhs, st.flag);  // (sets both flags)
       VSL_CHECK_LAUNCH(ctx);
     }
-    bool ok = true;
-    if ((e = ba_solve(ctx, st, ok))) return e;
-    const int okflag = ok ? 1 : 0;
-    VSL_HIP(ctx, hipMemcpyAsync(st.flag, &okflag, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ok) {
-      if ((e = ba_candidate(ctx, st, sb))) return e;
-    }
-    hipLaunchKernelGGL(sess_pack_c_kernel, dim3(1), dim3(64), 0, ctx->stream, st.scalars, st.flag, 0, packC);
+    if ((e = ba_solve_enqueue(ctx, st, n > 0))) return e;  // (no free camera: it sets the flags itself)
+    if ((e = ba_candidate(ctx, st, sb))) return e;
+    hipLaunchKernelGGL(sess_pack_c_kernel, dim3(1), dim3(64), 0, ctx->stream, st.scalars, st.flag, packC);
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   }

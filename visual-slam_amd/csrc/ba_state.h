@@ -131,10 +131,11 @@ int ba_schur_gather(vsl_ctx* ctx, BaCommon& st, const double* W, const double* Y
 // dc = -(S^-1 rhs), enqueued only: flag[0] = 1 (the finite check clears it), flag[1] = Cholesky succeeded.
 // flags_set: the caller's previous kernel has set both flags (saves the launch)
 int ba_solve_enqueue(vsl_ctx* ctx, BaCommon& st, bool flags_set = false);
-// dc = -(S^-1 rhs).  ok = false if S is not positive definite.  Synchronises.
-int ba_solve(vsl_ctx* ctx, BaCommon& st, bool& ok);
-// from dc: back-substitution (dl), flag[0] &= step finite, scalars[2] = model cost change, candidate (cand_poses,
-// cand_points), scalars[3] / [4] = squared step / x norms, [6] / [7] = those of the cameras alone, [5] = cost at the
+// from dc, the step chain of the stored-blocks form (the host loop and the session both run it): back-substitution (dl),
+// flag[0] &= dc and dl finite, scalars[2] = model cost change, candidate (cand_poses, cand_points), scalars[3] / [4] =
+// squared step / x norms
+int ba_step_from_dc(vsl_ctx* ctx, BaCommon& st, BaStored& sb);
+// ba_step_from_dc and what only a session needs: scalars[6] / [7] = the norms of the cameras alone, [5] = cost at the
 // candidate
 int ba_candidate(vsl_ctx* ctx, BaCommon& st, BaStored& sb);
 // dst[0] = max of the n values of v (ba_reduce_kernel, one workgroup)

@@ -99,6 +99,26 @@ extern "C" int vsl_ctx_synchronize(vsl_ctx* ctx) {
 
 extern "C" void* vsl_ctx_stream(vsl_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
+// Plain copies for callers that hold device pointers of this library (the all-reduce callbacks of the tests):
+// kind 0 host->device, 1 device->host, 2 device->device; synchronous.
+extern "C" int vsl_ctx_memcpy(vsl_ctx* ctx, void* dst, const void* src, size_t bytes, int kind) {
+  if (!ctx || !dst || !src || kind < 0 || kind > 2) return VSL_ERR_INVALID;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : (kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+  VSL_HIP(ctx, hipMemcpyAsync(dst, src, bytes, k, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VSL_OK;
+}
+
+// layout of the reduced camera system of the last bundle adjustment on this context (diagnostic read-out for benchmarks)
+extern "C" int vsl_ctx_last_ba_layout(vsl_ctx* ctx, int64_t* s_elems, int* banded, int* bandwidth) {
+  if (!ctx) return VSL_ERR_INVALID;
+  if (s_elems) *s_elems = ctx->last_ba_s_elems;
+  if (banded) *banded = ctx->last_ba_banded;
+  if (bandwidth) *bandwidth = ctx->last_ba_bw;
+  return VSL_OK;
+}
+
 int vsl_ctx_dscratch(vsl_ctx* ctx, size_t bytes, void** out) {
   if (bytes > ctx->dscratch_cap) {
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
