@@ -13,6 +13,8 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <unordered_map>
+#include <map>
 #include <vector>
 
 #include "keypoints.h"  // context holder + types
@@ -45,66 +47,88 @@ inline int camera_model_id(const std::string& name) {
   std::abort();
 }
 
-template <bool kAllObs>
-inline void run_ba(const Corners& feature_corners, bool use_huber, double huber_parameter, int max_num_iterations,
-                   int verbosity_level, const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam,
-                   Cameras& cameras, Landmarks& landmarks, bool optimize_intrinsics = false) {
-  if (cameras.empty() || landmarks.empty()) return;
-  std::vector<double> poses, points, uv, intr(16, 0.0);
+// The flattened problem: the SoA arrays of vsl_ba_problem with the containers' entries they came from.  `prob` points
+// into the vectors, so a BaFlat stays where it was filled.
+struct BaFlat {
+  std::vector<double> poses, points, uv, intr = std::vector<double>(16, 0.0);
   std::vector<uint8_t> fixed;
   std::vector<int32_t> cam_intr, obs_cam, obs_lm;
-  std::vector<Camera*> cam_ptr;
-  std::vector<Landmark*> lm_ptr;
+  std::vector<Camera*> cam_ptr;      // camera index -> the map's entry (std::map order)
+  std::vector<Landmark*> lm_ptr;     // landmark index -> the map's entry (the container's iteration order)
+  std::vector<FrameCamId> cam_id;
+  std::vector<TrackId> lm_id;
+  vsl_ba_problem prob;
+};
+
+// Cameras / Landmarks / Corners -> f (run_ba and bundle_adjustment_covariance share it).  false: nothing to solve (no
+// camera, no landmark or no observation).
+template <bool kAllObs>
+inline bool flatten_ba(const Corners& feature_corners, const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam,
+                       Cameras& cameras, Landmarks& landmarks, BaFlat& f) {
+  if (cameras.empty() || landmarks.empty()) return false;
   // cameras in std::map order; an observation list (std::map<FrameCamId, FeatureId>) is walked against it with two
   // cursors instead of two tree lookups per observation (20 k observations per local window)
-  std::vector<FrameCamId> cam_id;
   std::vector<const KeypointsData*> cam_kd;
   for (auto& kv : cameras) {  // std::map order == the order Ceres receives the blocks (map_utils.h:359)
-    cam_id.push_back(kv.first);
+    f.cam_id.push_back(kv.first);
     const auto kd = feature_corners.find(kv.first);
     cam_kd.push_back(kd == feature_corners.end() ? nullptr : &kd->second);
-    cam_ptr.push_back(&kv.second);
+    f.cam_ptr.push_back(&kv.second);
     const double* d = kv.second.T_w_c.data();
-    poses.insert(poses.end(), d, d + 7);
-    fixed.push_back(fixed_cameras.count(kv.first) ? 1 : 0);
-    cam_intr.push_back((int32_t)kv.first.cam_id);
+    f.poses.insert(f.poses.end(), d, d + 7);
+    f.fixed.push_back(fixed_cameras.count(kv.first) ? 1 : 0);
+    f.cam_intr.push_back((int32_t)kv.first.cam_id);
   }
   for (auto& kv : landmarks) {
     Landmark& lm = kv.second;
     const auto& track = kAllObs ? lm.all_obs : lm.obs;  // loop_closure_utils.h:706 vs map_utils.h:373
-    const int li = (int)lm_ptr.size();
-    lm_ptr.push_back(&lm);
-    points.insert(points.end(), lm.p.data(), lm.p.data() + 3);
+    const int li = (int)f.lm_ptr.size();
+    f.lm_ptr.push_back(&lm);
+    f.lm_id.push_back(kv.first);
+    f.points.insert(f.points.end(), lm.p.data(), lm.p.data() + 3);
     size_t ci = 0;
     for (const auto& ob : track) {
-      while (ci < cam_id.size() && cam_id[ci] < ob.first) ci++;
-      if (ci == cam_id.size() || ob.first < cam_id[ci] || !cam_kd[ci])  // .at(): std::out_of_range like the reference
+      while (ci < f.cam_id.size() && f.cam_id[ci] < ob.first) ci++;
+      if (ci == f.cam_id.size() || ob.first < f.cam_id[ci] || !cam_kd[ci])  // .at(): std::out_of_range like the reference
         throw std::out_of_range("bundle_adjustment: an observation refers to a camera / keypoint set that is not there");
       const auto& p_2d = cam_kd[ci]->corners[ob.second];
-      obs_cam.push_back((int32_t)ci);
-      obs_lm.push_back(li);
-      uv.push_back(p_2d[0]);
-      uv.push_back(p_2d[1]);
+      f.obs_cam.push_back((int32_t)ci);
+      f.obs_lm.push_back(li);
+      f.uv.push_back(p_2d[0]);
+      f.uv.push_back(p_2d[1]);
     }
   }
-  if (obs_cam.empty()) return;
-  vsl_ba_problem prob;
-  prob.n_cams = (int32_t)cam_ptr.size();
-  prob.n_lms = (int32_t)lm_ptr.size();
-  prob.n_obs = (int32_t)obs_cam.size();
+  if (f.obs_cam.empty()) return false;
+  vsl_ba_problem& prob = f.prob;
+  prob.n_cams = (int32_t)f.cam_ptr.size();
+  prob.n_lms = (int32_t)f.lm_ptr.size();
+  prob.n_obs = (int32_t)f.obs_cam.size();
   for (int k = 0; k < 2; k++) {
     prob.cam_model[k] = camera_model_id(calib_cam.intrinsics[k]->name());
     const double* p = calib_cam.intrinsics[k]->data();
-    for (int j = 0; j < 8; j++) intr[8 * k + j] = p[j];
+    for (int j = 0; j < 8; j++) f.intr[8 * k + j] = p[j];
   }
-  prob.poses = poses.data();
-  prob.cam_fixed = fixed.data();
-  prob.cam_intr = cam_intr.data();
-  prob.intr = intr.data();
-  prob.points = points.data();
-  prob.obs_cam = obs_cam.data();
-  prob.obs_lm = obs_lm.data();
-  prob.obs_uv = uv.data();
+  prob.poses = f.poses.data();
+  prob.cam_fixed = f.fixed.data();
+  prob.cam_intr = f.cam_intr.data();
+  prob.intr = f.intr.data();
+  prob.points = f.points.data();
+  prob.obs_cam = f.obs_cam.data();
+  prob.obs_lm = f.obs_lm.data();
+  prob.obs_uv = f.uv.data();
+  return true;
+}
+
+template <bool kAllObs>
+inline void run_ba(const Corners& feature_corners, bool use_huber, double huber_parameter, int max_num_iterations,
+                   int verbosity_level, const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam,
+                   Cameras& cameras, Landmarks& landmarks, bool optimize_intrinsics = false) {
+  BaFlat f;
+  if (!flatten_ba<kAllObs>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f)) return;
+  std::vector<double>&poses = f.poses, &points = f.points, &intr = f.intr;
+  std::vector<Camera*>& cam_ptr = f.cam_ptr;
+  std::vector<Landmark*>& lm_ptr = f.lm_ptr;
+  vsl_ba_problem& prob = f.prob;
   vsl_ba_options opt;
   opt.use_huber = use_huber ? 1 : 0;
   opt.huber_parameter = huber_parameter;
@@ -161,6 +185,63 @@ inline void bundle_adjustment(const Corners& feature_corners, const BundleAdjust
                               Landmarks& landmarks) {
   amd::run_ba<false>(feature_corners, options.use_huber, options.huber_parameter, options.max_num_iterations,
                      options.verbosity_level, fixed_cameras, calib_cam, cameras, landmarks, options.optimize_intrinsics);
+}
+
+// Marginal covariances of the map as it stands (vsl_ba_covariance; the reference has no counterpart, Ceres offers it as
+// ceres::Covariance beside the ceres::Solve of map_utils.h:405-411).  Nothing is optimised.  The problem is flattened by
+// the same code as bundle_adjustment (inlier observations of the window, Landmark::obs); options: use_huber and
+// huber_parameter.  query_cameras must be free cameras of `cameras`, query_landmarks ids of `landmarks` (else
+// std::out_of_range).  pose_cov_out: 6 x 6 over the tangent (upsilon, omega) of T_w_c exp(delta); landmark_cov_out:
+// 3 x 3 in world coordinates, NaN for a landmark whose own block is singular (a single observation).  Unit: 1 px^2 of
+// observation noise.  Returns the number of such landmarks; std::domain_error when the reduced camera system is singular
+// to working precision (VSL_ERR_NUMERIC: e.g. no fixed camera).
+using PoseCovariance = Eigen::Matrix<double, 6, 6>;
+inline int bundle_adjustment_covariance(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                        const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                        Landmarks& landmarks, const std::vector<FrameCamId>& query_cameras,
+                                        const std::vector<TrackId>& query_landmarks,
+                                        std::map<FrameCamId, PoseCovariance>& pose_cov_out,
+                                        std::unordered_map<TrackId, Eigen::Matrix3d>& landmark_cov_out) {
+  pose_cov_out.clear();
+  landmark_cov_out.clear();
+  if (query_cameras.empty() && query_landmarks.empty()) return 0;
+  amd::BaFlat f;
+  if (!amd::flatten_ba<false>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f))
+    throw std::out_of_range("bundle_adjustment_covariance: the map has no observation");
+  std::vector<int32_t> cams, lms;
+  for (const FrameCamId& id : query_cameras) {
+    const auto it = std::lower_bound(f.cam_id.begin(), f.cam_id.end(), id);
+    if (it == f.cam_id.end() || !(*it == id)) throw std::out_of_range("bundle_adjustment_covariance: unknown camera");
+    cams.push_back((int32_t)(it - f.cam_id.begin()));
+  }
+  if (!query_landmarks.empty()) {
+    std::unordered_map<TrackId, int32_t> index;
+    for (size_t l = 0; l < f.lm_id.size(); l++) index.emplace(f.lm_id[l], (int32_t)l);
+    for (const TrackId id : query_landmarks) lms.push_back(index.at(id));
+  }
+  vsl_ba_options opt;
+  opt.use_huber = options.use_huber ? 1 : 0;
+  opt.huber_parameter = options.huber_parameter;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  std::vector<double> cp(36 * cams.size()), cl(9 * lms.size());
+  int n_degenerate = 0;
+  const int rc = vsl_ba_covariance(amd::ctx(), &f.prob, &opt, cams.data(), (int)cams.size(), cp.data(), lms.data(),
+                                   (int)lms.size(), cl.data(), &n_degenerate);
+  // a reduced camera system that is singular to working precision is a property of the map, not a failure of the call
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
+  amd::check(rc, "bundle_adjustment_covariance");
+  for (size_t q = 0; q < cams.size(); q++) {
+    PoseCovariance& m = pose_cov_out[query_cameras[q]];
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) m(i, j) = cp[36 * q + 6 * i + j];
+  }
+  for (size_t q = 0; q < lms.size(); q++) {
+    Eigen::Matrix3d& m = landmark_cov_out[query_landmarks[q]];
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) m(i, j) = cl[9 * q + 3 * i + j];
+  }
+  return n_degenerate;
 }
 
 // include/visnav/loop_closure_utils.h:672-748.  With rccl_world.h included first and VISNAV_AMD_WORLD > 1 (one process

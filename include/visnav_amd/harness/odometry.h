@@ -49,9 +49,13 @@
 #pragma weak vsl_fuse_search
 #pragma weak vsl_map_append_descriptors
 
+// ... and the marginal covariances of the window (OdometryOptions::ba_covariance_path)
+#pragma weak vsl_ba_covariance
+
 namespace visnav {
 namespace harness {
 
+inline bool ba_covariance_available() { return &vsl_ba_covariance != nullptr; }
 inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
 // the device keyframe database (OdometryOptions::device_place_db) is referenced weakly in the same way (bow.h)
 inline bool device_place_db_available() { return KeyframeDatabaseAmd::available(); }
@@ -105,6 +109,12 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   // after a loop was closed, merge the landmarks the two passes hold twice (loop_closure.h landmark_fusion: one batched
   // guided search on the device + the map edits of fusion_plan.h) before optimize() and the global BA see the map
   bool landmark_fusion = false;
+  // non-empty: after every local bundle adjustment, one text line per keyframe of the window whose pose was optimised
+  // (the oldest keyframe is fixed: it is the gauge and has no covariance) is appended to this file: frame id, sqrt of
+  // the trace of the translational 3 x 3 block of the left camera's pose covariance, sqrt of the trace of the
+  // rotational one (visnav::bundle_adjustment_covariance; units: per pixel of observation noise).  Nothing else
+  // changes: the trajectory is the one of a run without it.
+  std::string ba_covariance_path;
   double motion_threshold = 0.5;
   int num_cov_threshold = 10;
   int num_ess_threshold = 30;
@@ -701,6 +711,7 @@ class Odometry {
     auto work = [this, fid, ba_options] {
       const std::set<FrameCamId> fixed_cameras = {FrameCamId(fid, 0), FrameCamId(fid, 1)};
       bundle_adjustment(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt);
+      if (!opt.ba_covariance_path.empty()) write_window_covariance(fixed_cameras, ba_options);
       if (std::getenv("VISNAV_AMD_TRACE_FRAMES")) {
         double h = 0;
         for (const auto& kv : cameras_opt) h += kv.second.T_w_c.data()[4] * 1.7 + kv.second.T_w_c.data()[5];
@@ -714,6 +725,31 @@ class Odometry {
       submit_job(work);
     else
       work();
+  }
+
+  // OdometryOptions::ba_covariance_path: the pose uncertainty of the window that optimize() has just adjusted
+  void write_window_covariance(const std::set<FrameCamId>& fixed_cameras, const BundleAdjustmentOptions& ba_options) {
+    std::vector<FrameCamId> query;
+    for (const auto& kv : cameras_opt)
+      if (kv.first.cam_id == 0 && !fixed_cameras.count(kv.first)) query.push_back(kv.first);
+    if (query.empty()) return;  // the first keyframe: nothing but the gauge
+    std::map<FrameCamId, PoseCovariance> pose_cov;
+    std::unordered_map<TrackId, Eigen::Matrix3d> landmark_cov;
+    try {
+      bundle_adjustment_covariance(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt, query, {},
+                                   pose_cov, landmark_cov);
+    } catch (const std::domain_error& e) {
+      std::fprintf(stderr, "window covariance skipped: %s\n", e.what());
+      return;
+    }
+    FILE* f = std::fopen(opt.ba_covariance_path.c_str(), "a");
+    if (!f) return;
+    for (const auto& kv : pose_cov) {
+      const PoseCovariance& m = kv.second;
+      std::fprintf(f, "%lld %.9g %.9g\n", (long long)kv.first.frame_id, std::sqrt(m(0, 0) + m(1, 1) + m(2, 2)),
+                   std::sqrt(m(3, 3) + m(4, 4) + m(5, 5)));
+    }
+    std::fclose(f);
   }
 
   // src/slam.cpp:1379-1412

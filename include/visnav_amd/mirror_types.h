@@ -47,6 +47,16 @@ struct Matrix3d {
   double* data() { return v; }
   const double* data() const { return v; }
 };
+// fixed-size R x C matrix of T, column-major like Eigen's default storage (Eigen::Matrix<double, 6, 6>: a pose covariance)
+template <class T, int R, int C>
+struct Matrix {
+  T v[R * C];
+  Matrix() { for (int i = 0; i < R * C; i++) v[i] = T(0); }
+  T& operator()(int i, int j) { return v[i + R * j]; }
+  const T& operator()(int i, int j) const { return v[i + R * j]; }
+  T* data() { return v; }
+  const T* data() const { return v; }
+};
 template <class T>
 using aligned_allocator = std::allocator<T>;
 }  // namespace Eigen

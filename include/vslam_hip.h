@@ -412,6 +412,32 @@ int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_opti
 int vsl_ba_residuals_jacobians(vsl_ctx* ctx, const vsl_ba_problem* prob, double* r, double* J_pose,
                                double* J_point);
 
+/* Marginal covariances of poses and landmarks at the poses / points handed in -- what ceres::Covariance offers beside
+ * the ceres::Solve of include/visnav/map_utils.h:405-411.  Nothing is optimised (opt->max_num_iterations is ignored,
+ * prob->poses / points are only read).  The problem is linearised exactly as vsl_ba_linearize documents it (Huber
+ * corrector when opt->use_huber, no Jacobi scaling, no damping); H = J^T J over the free cameras (tangent (upsilon,
+ * omega) of T * exp(delta)) and all landmarks, covariance = H^-1 in units of 1 px^2 of observation noise.  With S the
+ * reduced camera system of vsl_ba_linearize, P_l = sum E^T E of landmark l and W_c = F_c^T E_c over its observations in
+ * free cameras:
+ *   cov_pose  [36 * n_cam_q] row-major: block q = the 6 x 6 diagonal block of S^-1 of camera cams[q];
+ *   cov_point [9 * n_lm_q]   row-major: block q = P_l^-1 + P_l^-1 (sum_c sum_c' W_c^T [S^-1]_cc' W_c') P_l^-1 of
+ *             landmark lms[q] (P_l^-1 alone when only fixed cameras see it).
+ * cams are CAMERA ids of prob (not free indices): a fixed camera or an id out of range in cams / lms gives
+ * VSL_ERR_INVALID; duplicates are allowed; n_cam_q and n_lm_q may be 0 (then the array pointers may be NULL; with both 0
+ * the call returns VSL_OK and launches nothing); with no free camera a pose query is invalid and landmark queries return
+ * P_l^-1.  S not positive definite to working precision (e.g. no fixed camera: the gauge is free) gives
+ * VSL_ERR_NUMERIC.  A queried landmark whose P_l is not positive definite (e.g. a single observation) gets nine NaN and
+ * is counted in *n_degenerate (nullable); the call still returns VSL_OK.  An empty problem (n_lms = 0 or n_obs = 0) is
+ * VSL_ERR_INVALID.  Every block is exactly symmetric; the result does not depend on what else is queried (a subset
+ * query returns the bits of the same blocks of a full query) and is the same from run to run.
+ * DENSE ONLY: S is formed, factorised and inverted column by column in dense storage whatever its size (the dense path
+ * of vsl_spd_solve); selected inversion on the band / cyclic-band forms of large maps is not implemented.  A queried
+ * landmark may have at most 256 observations (VSL_ERR_INVALID beyond). */
+int vsl_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
+                      const int32_t* cams, int n_cam_q, double* cov_pose,   /* [36*n_cam_q] row-major */
+                      const int32_t* lms,  int n_lm_q,  double* cov_point,  /* [9*n_lm_q]   row-major */
+                      int* n_degenerate);
+
 /* ---- multi-GPU global bundle adjustment ----
  * visnav::global_bundle_adjustment (include/visnav/loop_closure_utils.h:672-748) over `world` ranks, one process per
  * GPU: every rank holds all camera poses and owns a contiguous landmark range (balanced by observation count) with its

@@ -478,6 +478,22 @@ class Context:
                                          C.byref(nf)))
         return S, g, cost.value
 
+    def ba_covariance(self, arr, cams=None, lms=None, use_huber=True, huber=1.0):
+        """Marginal covariances at arr's poses / points (vsl_ba_covariance; nothing is optimised).  cams: camera ids
+        (None: all free cameras), lms: landmark ids (None: none).  Returns (cov_pose [n, 6, 6], cov_point [m, 3, 3],
+        n_degenerate); a landmark whose own block is singular comes back as NaN and is counted."""
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        cams = np.flatnonzero(arr.cam_fixed == 0) if cams is None else cams
+        cams = np.ascontiguousarray(cams, np.int32).reshape(-1)
+        lms = np.ascontiguousarray([] if lms is None else lms, np.int32).reshape(-1)
+        cp, cl = np.zeros((len(cams), 6, 6)), np.zeros((len(lms), 3, 3))
+        nd = C.c_int(0)
+        self._ck(self.L.vsl_ba_covariance(self.h, C.byref(st), C.byref(o), cams.ctypes.data_as(i32p), len(cams),
+                                          cp.ctypes.data_as(f64p), lms.ctypes.data_as(i32p), len(lms),
+                                          cl.ctypes.data_as(f64p), C.byref(nd)))
+        return cp, cl, nd.value
+
     def ba_residuals_jacobians(self, arr):
         st = self._ba_struct(arr)
         n = len(arr.obs_cam)

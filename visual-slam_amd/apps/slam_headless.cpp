@@ -5,7 +5,7 @@
 // libvslam_hip.so; there is no CPU fallback.
 //
 //   slam_headless --dataset-path <dir with cam0/ cam1/ ...> --cam-calib <calib.json>
-//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N]
+//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N] [--ba-covariance FILE]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -59,6 +59,7 @@ int main(int argc, char** argv) {
     else if (a == "--kf-min-inliers") opt.new_kf_min_inliers = std::atoi(need("--kf-min-inliers").c_str());
     else if (a == "--max-kfs") opt.max_num_kfs = std::atoi(need("--max-kfs").c_str());
     else if (a == "--num-features") opt.num_features_per_image = std::atoi(need("--num-features").c_str());
+    else if (a == "--ba-covariance") opt.ba_covariance_path = need("--ba-covariance");  // pose uncertainty of the window after every local BA
     else if (a == "--ba-verbose") opt.ba_verbose = 1;
     else if (a == "--ba-iterations") opt.ba_max_iterations = std::atoi(need("--ba-iterations").c_str());
     else if (a == "--relocalization") opt.enable_relocalization = true;   // the reference's ui.relocalization (default on there)
@@ -104,6 +105,22 @@ int main(int argc, char** argv) {
   if (opt.device_bow && !device_bow_available()) {
     std::fprintf(stderr, "--device-bow: this build's C ABI has no batched keyframe BoW (vsl_frames_bow_vectors)\n");
     return 2;
+  }
+  if (!opt.ba_covariance_path.empty()) {
+    if (!ba_covariance_available()) {
+      std::fprintf(stderr, "--ba-covariance: this build's C ABI has no covariance entry point (vsl_ba_covariance)\n");
+      return 2;
+    }
+    if (replicas != 1) {
+      std::fprintf(stderr, "--ba-covariance needs --replicas 1 (one writer per file)\n");
+      return 2;
+    }
+    FILE* f = std::fopen(opt.ba_covariance_path.c_str(), "w");  // the run appends to an empty file
+    if (!f) {
+      std::fprintf(stderr, "--ba-covariance: cannot write %s\n", opt.ba_covariance_path.c_str());
+      return 2;
+    }
+    std::fclose(f);
   }
   if (opt.landmark_fusion && !landmark_fusion_available()) {
     std::fprintf(stderr, "--landmark-fusion: this build's C ABI has no batched fusion search (vsl_fuse_search)\n");
@@ -174,7 +191,9 @@ int main(int argc, char** argv) {
       KeypointsData kd;
       ImageRef l(left[0]);
       detectKeypointsAndDescriptors(l.img, kd, opt.num_features_per_image, opt.rotate_features);
-      Odometry warm(calib, opt);
+      OdometryOptions warm_opt = opt;
+      warm_opt.ba_covariance_path.clear();  // the file belongs to the run itself
+      Odometry warm(calib, warm_opt);
       warm.orb_voc = o.orb_voc;
       // ... and enough frames (~50 ms of work) for the chip's clock to have ramped up from idle
       const int n_warm = n_frames < 60 ? n_frames : 60;

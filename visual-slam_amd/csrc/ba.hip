@@ -1292,7 +1292,8 @@ int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
 int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaState& st, const BaCaller& caller) {
   BaTrace tr;
   const bool allow_band = caller.use == BaUse::HOST_LOOP || caller.use == BaUse::SESSION;
-  const ArenaPolicy arena_policy = caller.use == BaUse::HOST_LOOP ? ArenaPolicy::BORROWED : ArenaPolicy::OWNED;
+  const ArenaPolicy arena_policy =
+      caller.use == BaUse::HOST_LOOP || caller.use == BaUse::COVARIANCE ? ArenaPolicy::BORROWED : ArenaPolicy::OWNED;
   BaDims& D = st.D;
   D.C = p->n_cams;
   D.L = p->n_lms;
@@ -1393,6 +1394,7 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
     plan.add(sb.H2, 36 * nfree); plan.add(sb.g_c2, n); plan.add(sb.diag_c2, n); plan.add(sb.diag_l2, 3 * L);
   }
   if (caller.use == BaUse::SESSION) plan.add(st.diagc_keep, std::max<size_t>(n, 1));
+  if (caller.extra_bytes) plan.add(st.extra, caller.extra_bytes);
   VSL_HIP(ctx, st.arena.acquire(ctx, arena_policy, plan));
   st.flag = (int*)(st.scalars + 16);
   tr.lap("arena", plan.total());

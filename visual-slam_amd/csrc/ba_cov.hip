@@ -1,0 +1,551 @@
+// ba_cov.hip -- marginal covariances of poses and landmarks of a bundle-adjustment problem (vsl_ba_covariance): what
+// ceres::Covariance offers beside ceres::Solve (include/visnav/map_utils.h:405-411 calls only the latter).
+//
+// Nothing is optimised: the problem is linearised once at the poses and points handed in, exactly as vsl_ba_linearize
+// documents it (Huber corrector on residual and Jacobian blocks, no Jacobi scaling, no damping).  With H = J^T J over
+// the free cameras (6-vector tangent (upsilon, omega) of T exp(delta), free-camera index order) and all landmarks, the
+// covariance is H^-1 (unit: 1 px^2 of observation noise).  By the block inverse of H, with S the reduced camera system,
+// P_l = sum E^T E of landmark l and W_c = F_c^T E_c of its observation in free camera c:
+//   pose block      Sigma_cc = [S^-1]_cc
+//   landmark block  Sigma_ll = P_l^-1 + P_l^-1 (sum_c sum_c' W_c^T [S^-1]_cc' W_c') P_l^-1
+//
+// The chain, all on the context's stream:
+//   ba_linearize -> ba_columns -> ba_schur (ba.hip: the kernels behind vsl_ba_linearize)          S, dense
+//   ba_cov_diag_kernel                                                                             diag S, kept for the pivot test
+//   vsl_chol_factor_dev (chol.hip: the dense panel factorisation)                                  S <- L, inverted diagonal blocks
+//   ba_cov_solve_kernel      L L^T X = E_Q, Q = queried cameras + free cameras observing a queried landmark, six unit
+//                            columns per camera, COV_COLS columns per workgroup
+//   ba_cov_pose_kernel       the diagonal 6 x 6 blocks of X, symmetrised
+//   ba_cov_landmark_kernel   one wavefront per queried landmark: E, F and the corrector re-evaluated at the state
+//                            (ba_device.h / ba_large.h), P_l, W_c, the double sum in ascending (c, c') order
+// Everything runs in a fixed order and without atomics: a column of X has the same bits whichever columns share its
+// workgroup (an output of v_mfma_f64_16x16x4_f64 depends on its own row of A and column of B only), so a subset query
+// returns the bits of the same rows of a full query, and two calls return the same bits.
+//
+// DENSE ONLY.  S is formed and factorised in dense storage whatever its size (the dense path of vsl_spd_solve);
+// selected inversion on the band and cyclic-band forms that vsl_global_bundle_adjust uses for large maps is not
+// implemented, so the cost grows with (6 x free cameras)^2 x columns.  A queried landmark may have at most COV_KMAX
+// observations (its W blocks are kept in LDS).
+//
+// "Not positive definite" is decided to working precision: a pivot L_ii^2 <= 2^-36 S_ii fails the factorisation
+// (VSL_ERR_NUMERIC); the ratio is invariant under a rescaling of the unknowns.  A free gauge (no fixed camera) leaves
+// pivots of rounding-noise size, which a bare "> 0" test lets through about half of the time.  The same rule with
+// 2^-44 on the three pivots of P_l marks a landmark degenerate (a single observation has rank 2).
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "vsl_common.h"
+#include "dev_arena.h"
+#include "ba_host_plan.h"
+#include "ba_device.h"
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"  // ba_large.h: only bl_eval and bl_wave_sum are used here, not its kernels
+#include "ba_large.h"
+#pragma clang diagnostic pop
+#include "ba_state.h"
+
+#define COV_NB VSL_CHOL_NB  // panel width of the solve = the factorisation's (its inverted diagonal blocks are reused)
+#define COV_COLS 16         // right-hand sides of a workgroup: one matrix-instruction tile
+#define COV_THREADS 256
+#define COV_CHUNK 64        // rows (forward) / columns (backward) of L staged in LDS per step: one 16-row tile per wavefront
+#define COV_LP 34           // LDS row pitches (doubles): 2 r + k and 16 k + c fall on distinct banks within a half wavefront
+#define COV_LQ 80
+#define COV_KMAX 256        // observations of a queried landmark (27 doubles of LDS each)
+#define COV_PIVOT_TOL 1.4551915228366852e-11  // 2^-36
+#define COV_LM_TOL 5.6843418860808015e-14     // 2^-44
+
+static_assert(COV_NB == 32 && COV_CHUNK == 16 * (COV_THREADS / 64), "tile arithmetic of ba_cov_solve_kernel");
+
+namespace {
+
+typedef double cov_v4d __attribute__((ext_vector_type(4)));
+
+// entry (row i, right-hand side col) of X: workgroup blocks of n x COV_COLS, row-major
+__device__ __forceinline__ size_t cov_x_at(int n, int i, int col) {
+  return (size_t)(col / COV_COLS) * n * COV_COLS + (size_t)i * COV_COLS + (col % COV_COLS);
+}
+
+__global__ void ba_cov_diag_kernel(int n, const double* __restrict__ S, double* __restrict__ d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = S[(size_t)i * n + i];
+}
+
+// L L^T X = E for the COV_COLS unit columns col_unk[COV_COLS * blockIdx.x ..] (-1: an empty column) of this workgroup,
+// in its n x COV_COLS block of X.  L: the dense factor (n x n row-major, lower triangle), Linv: its inverted COV_NB x
+// COV_NB diagonal blocks (zero above the diagonal, identity-padded in the last one), Sdiag: diag S before the
+// factorisation.  Right-looking in both directions, one panel of COV_NB unknowns per step:
+//   forward   Y_k = Linv_kk B_k, then B_i -= L[i, k] Y_k for the rows below, COV_CHUNK rows of the panel in LDS at a time
+//   backward  X_k = Linv_kk^T Y_k, then Y_c -= L[k, c]^T X_k for the columns before, COV_CHUNK columns at a time
+// every product a chain of eight v_mfma_f64_16x16x4_f64 over the 32 unknowns of the panel, one 16 x 16 tile per wavefront.
+// An entry of X is touched by one lane per step, panels in ascending (descending) order: a fixed summation order per
+// column.  *ok = 0 (by workgroup 0) and nothing written when a pivot fails the test in the file header.
+__global__ __launch_bounds__(COV_THREADS) void ba_cov_solve_kernel(int n, const double* __restrict__ L,
+                                                                   const double* __restrict__ Linv,
+                                                                   const double* __restrict__ Sdiag,
+                                                                   const int* __restrict__ col_unk, double* __restrict__ X,
+                                                                   int* __restrict__ ok) {
+  __shared__ double Li[COV_NB][COV_LP];
+  __shared__ double Bk[COV_NB][COV_COLS];
+  __shared__ double stage[COV_NB * COV_LQ];  // forward: [COV_CHUNK][COV_LP], backward: [COV_NB][COV_LQ]
+  static_assert(COV_CHUNK * COV_LP <= COV_NB * COV_LQ, "the forward view fits");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
+  int bad = *ok ? 0 : 1;
+  for (int i = tid; i < n; i += COV_THREADS) {
+    const double l = L[(size_t)i * n + i], p = l * l;
+    if (!(p > COV_PIVOT_TOL * Sdiag[i]) || !isfinite(p)) bad = 1;
+  }
+  if (__syncthreads_or(bad)) {
+    if (blockIdx.x == 0 && tid == 0) *ok = 0;
+    return;
+  }
+  double* __restrict__ Xw = X + (size_t)blockIdx.x * n * COV_COLS;
+  for (int t = tid; t < n * COV_COLS; t += COV_THREADS)
+    Xw[t] = col_unk[COV_COLS * blockIdx.x + (t % COV_COLS)] == t / COV_COLS ? 1.0 : 0.0;
+  __syncthreads();
+  const int np = (n + COV_NB - 1) / COV_NB;
+  // ---- forward: L Y = E
+  for (int p = 0; p < np; p++) {
+    const int k = p * COV_NB, nb = min(COV_NB, n - k);
+    for (int t = tid; t < COV_NB * COV_NB; t += COV_THREADS) Li[t / COV_NB][t % COV_NB] = Linv[(size_t)p * COV_NB * COV_NB + t];
+    for (int t = tid; t < COV_NB * COV_COLS; t += COV_THREADS) {
+      const int r = t / COV_COLS;
+      Bk[r][t % COV_COLS] = r < nb ? Xw[(size_t)(k + r) * COV_COLS + (t % COV_COLS)] : 0.0;
+    }
+    __syncthreads();
+    cov_v4d acc = {0.0, 0.0, 0.0, 0.0};
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int s = 0; s < COV_NB / 4; s++)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Li[16 * wave + l16][4 * s + kq], Bk[4 * s + kq][l16], acc, 0, 0, 0);
+    }
+    __syncthreads();  // B_k has been read: Y_k takes its place
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int r = 16 * wave + kq + 4 * q;
+        Bk[r][l16] = acc[q];
+        if (r < nb) Xw[(size_t)(k + r) * COV_COLS + l16] = acc[q];
+      }
+    }
+    __syncthreads();
+    for (int i0 = k + COV_NB; i0 < n; i0 += COV_CHUNK) {
+      for (int t = tid; t < COV_CHUNK * COV_NB; t += COV_THREADS) {
+        const int r = t / COV_NB, c = t % COV_NB;
+        stage[r * COV_LP + c] = i0 + r < n ? L[(size_t)(i0 + r) * n + k + c] : 0.0;
+      }
+      __syncthreads();
+      const int r0 = i0 + 16 * wave;
+      if (r0 < n) {
+        cov_v4d a2 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < COV_NB / 4; s++)
+          a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(stage[(16 * wave + l16) * COV_LP + 4 * s + kq], Bk[4 * s + kq][l16], a2, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int r = r0 + kq + 4 * q;
+          if (r < n) Xw[(size_t)r * COV_COLS + l16] -= a2[q];
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // ---- backward: L^T X = Y
+  for (int p = np - 1; p >= 0; p--) {
+    const int k = p * COV_NB, nb = min(COV_NB, n - k);
+    for (int t = tid; t < COV_NB * COV_NB; t += COV_THREADS) Li[t / COV_NB][t % COV_NB] = Linv[(size_t)p * COV_NB * COV_NB + t];
+    for (int t = tid; t < COV_NB * COV_COLS; t += COV_THREADS) {
+      const int r = t / COV_COLS;
+      Bk[r][t % COV_COLS] = r < nb ? Xw[(size_t)(k + r) * COV_COLS + (t % COV_COLS)] : 0.0;
+    }
+    __syncthreads();
+    cov_v4d acc = {0.0, 0.0, 0.0, 0.0};
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int s = 0; s < COV_NB / 4; s++)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Li[4 * s + kq][16 * wave + l16], Bk[4 * s + kq][l16], acc, 0, 0, 0);
+    }
+    __syncthreads();
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int r = 16 * wave + kq + 4 * q;
+        Bk[r][l16] = acc[q];
+        if (r < nb) Xw[(size_t)(k + r) * COV_COLS + l16] = acc[q];
+      }
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < k; c0 += COV_CHUNK) {
+      for (int t = tid; t < COV_NB * COV_CHUNK; t += COV_THREADS) {
+        const int r = t / COV_CHUNK, c = t % COV_CHUNK;
+        stage[r * COV_LQ + c] = (r < nb && c0 + c < k) ? L[(size_t)(k + r) * n + c0 + c] : 0.0;
+      }
+      __syncthreads();
+      const int cc0 = c0 + 16 * wave;
+      if (cc0 < k) {
+        cov_v4d a2 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < COV_NB / 4; s++)
+          a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(stage[(4 * s + kq) * COV_LQ + 16 * wave + l16], Bk[4 * s + kq][l16], a2, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int r = cc0 + kq + 4 * q;
+          if (r < k) Xw[(size_t)r * COV_COLS + l16] -= a2[q];
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// pose block of the camera at position q of Q (free index q_free[q], right-hand sides 6 q .. 6 q + 5): the diagonal
+// block of X, symmetrised (X = S^-1 is symmetric up to rounding; (a + b) / 2 is the same number both ways round)
+__global__ void ba_cov_pose_kernel(int n, int nQ, const int* __restrict__ q_free, const double* __restrict__ X,
+                                   const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 36 * nQ || !*ok) return;
+  const int q = t / 36, a = (t % 36) / 6, b = t % 6, c = q_free[q];
+  out[t] = 0.5 * (X[cov_x_at(n, 6 * c + a, 6 * q + b)] + X[cov_x_at(n, 6 * c + b, 6 * q + a)]);
+}
+
+// One wavefront per queried landmark u (its observations: u_start[u] .. u_start[u + 1] of o_cam / o_uv, ascending free
+// index, fixed cameras first).  sh: 27 doubles per observation (W = F^T E, then T = W^T Z).
+__global__ __launch_bounds__(64) void ba_cov_landmark_kernel(BlArgs a, int n, const int* __restrict__ u_lm,
+                                                             const int* __restrict__ u_start, const int* __restrict__ o_cam,
+                                                             const double* __restrict__ o_uv, const int* __restrict__ qpos,
+                                                             const double* __restrict__ X, const int* __restrict__ ok,
+                                                             double* __restrict__ out, int* __restrict__ degenerate) {
+  extern __shared__ double sh[];
+  __shared__ double M[9];
+  if (!*ok) return;
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int o0 = u_start[u], K = u_start[u + 1] - o0;
+  double* W = sh;
+  double* T = sh + 18 * (size_t)K;
+  const double* pw = a.points + 3 * (size_t)u_lm[u];
+  double P[6] = {0, 0, 0, 0, 0, 0};  // xx xy xz yy yz zz
+  for (int i = lane; i < K; i += 64) {
+    BlObs o;
+    bl_eval<false, true>(a, o_cam[o0 + i], pw, nullptr, o_uv + 2 * (size_t)(o0 + i), o);
+    const double* E = o.E;
+    P[0] += E[0] * E[0] + E[3] * E[3];
+    P[1] += E[0] * E[1] + E[3] * E[4];
+    P[2] += E[0] * E[2] + E[3] * E[5];
+    P[3] += E[1] * E[1] + E[4] * E[4];
+    P[4] += E[1] * E[2] + E[4] * E[5];
+    P[5] += E[2] * E[2] + E[5] * E[5];
+#pragma unroll
+    for (int x = 0; x < 6; x++)
+#pragma unroll
+      for (int y = 0; y < 3; y++) W[18 * i + 3 * x + y] = o.fc >= 0 ? o.F[x] * E[y] + o.F[6 + x] * E[3 + y] : 0.0;
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++) P[j] = bl_wave_sum(P[j]);
+  // P = L D L^T: positive definite to working precision iff every pivot is a fair share of its diagonal entry
+  const double d0 = P[0];
+  const double l1 = P[1] / d0, l2 = P[2] / d0;
+  const double d1 = P[3] - l1 * P[1];
+  const double m = P[4] - l1 * P[2];
+  const double d2 = P[5] - l2 * P[2] - (m / d1) * m;
+  const double P9[9] = {P[0], P[1], P[2], P[1], P[3], P[4], P[2], P[4], P[5]};
+  double Pi[9];
+  const bool pd = d0 > 0.0 && d1 > COV_LM_TOL * P[3] && d2 > COV_LM_TOL * P[5] && isfinite(d0 + d1 + d2) && inv3(P9, Pi);
+  if (!pd) {  // (wave-uniform: every lane holds the same P)
+    if (lane < 9) out[9 * (size_t)u + lane] = __builtin_nan("");
+    if (lane == 0) degenerate[u] = 1;
+    return;
+  }
+  if (lane == 0) degenerate[u] = 0;
+  __syncthreads();
+  // T_i = W_i^T sum_j [S^-1]_{c(i) c(j)} W_j, j ascending
+  for (int i = lane; i < K; i += 64) {
+    const int ci = a.cam_free[o_cam[o0 + i]];
+    double Z[18];
+#pragma unroll
+    for (int e = 0; e < 18; e++) Z[e] = 0.0;
+    if (ci >= 0) {
+      for (int j = 0; j < K; j++) {
+        const int cj = a.cam_free[o_cam[o0 + j]];
+        if (cj < 0) continue;
+        const int col = 6 * qpos[cj];
+        const double* Wj = W + 18 * j;
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+          for (int b = 0; b < 6; b++) {
+            const double s = X[cov_x_at(n, 6 * ci + r, col + b)];
+#pragma unroll
+            for (int y = 0; y < 3; y++) Z[3 * r + y] += s * Wj[3 * b + y];
+          }
+      }
+    }
+#pragma unroll
+    for (int x = 0; x < 3; x++)
+#pragma unroll
+      for (int y = 0; y < 3; y++) {
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) s += W[18 * i + 3 * r + x] * Z[3 * r + y];
+        T[9 * i + 3 * x + y] = s;
+      }
+  }
+  __syncthreads();
+  if (lane < 9) {
+    double s = 0.0;
+    for (int i = 0; i < K; i++) s += T[9 * i + lane];  // ascending c
+    M[lane] = s;
+  }
+  __syncthreads();
+  if (lane < 9) {
+    const int x = lane / 3, y = lane % 3;
+    // Q = P^-1 M P^-1, entries (x, y) and (y, x); the result is symmetrised like the pose blocks
+    double qxy = 0.0, qyx = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        qxy += Pi[3 * x + r] * M[3 * r + c] * Pi[3 * c + y];
+        qyx += Pi[3 * y + r] * M[3 * r + c] * Pi[3 * c + x];
+      }
+    out[9 * (size_t)u + lane] = Pi[3 * x + y] + 0.5 * (qxy + qyx);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+inline size_t cov_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// What the host derives from the query: Q, the unique landmarks and their observation lists
+struct CovPlan {
+  int nfree = 0, nQ = 0, nu = 0, n_o = 0, kmax = 0;
+  std::vector<int> cam_free;          // camera -> free index or -1 (ascending camera id: vsl_ba_linearize's numbering)
+  std::vector<int> q_free, qpos;      // Q in ascending free index, and free index -> position in Q or -1
+  std::vector<int> cam_q2Q, lm_q2u;   // query entry -> position in Q / unique landmark
+  std::vector<int> u_lm, u_start, o_cam;
+  std::vector<double> o_uv;
+};
+
+CovPlan cov_plan(const vsl_ba_problem* p, const int32_t* cams, int n_cam_q, const int32_t* lms, int n_lm_q) {
+  CovPlan P;
+  P.cam_free.assign(p->n_cams, -1);
+  for (int c = 0; c < p->n_cams; c++)
+    if (!p->cam_fixed[c]) P.cam_free[c] = P.nfree++;
+  std::vector<int> lm_slot(p->n_lms, -1);
+  P.lm_q2u.resize(n_lm_q);
+  for (int q = 0; q < n_lm_q; q++) {
+    int& s = lm_slot[lms[q]];
+    if (s < 0) {
+      s = (int)P.u_lm.size();
+      P.u_lm.push_back(lms[q]);
+    }
+    P.lm_q2u[q] = s;
+  }
+  P.nu = (int)P.u_lm.size();
+  P.u_start.assign((size_t)P.nu + 1, 0);
+  if (P.nu > 0)
+    for (int i = 0; i < p->n_obs; i++) {
+      const int s = lm_slot[p->obs_lm[i]];
+      if (s >= 0) P.u_start[s + 1]++;
+    }
+  for (int u = 0; u < P.nu; u++) {
+    P.kmax = std::max(P.kmax, P.u_start[u + 1]);
+    P.u_start[u + 1] += P.u_start[u];
+  }
+  P.n_o = P.u_start[P.nu];
+  std::vector<int> o_idx(P.n_o), fill(P.u_start.begin(), P.u_start.end() - 1);
+  if (P.nu > 0)
+    for (int i = 0; i < p->n_obs; i++) {
+      const int s = lm_slot[p->obs_lm[i]];
+      if (s >= 0) o_idx[fill[s]++] = i;
+    }
+  std::vector<char> inQ(P.nfree, 0);
+  for (int q = 0; q < n_cam_q; q++) inQ[P.cam_free[cams[q]]] = 1;
+  P.o_cam.resize(P.n_o);
+  P.o_uv.resize(2 * (size_t)P.n_o);
+  for (int u = 0; u < P.nu; u++) {
+    // ascending free index (fixed cameras, -1, first), observation order within a camera
+    std::stable_sort(o_idx.begin() + P.u_start[u], o_idx.begin() + P.u_start[u + 1],
+                     [&](int x, int y) { return P.cam_free[p->obs_cam[x]] < P.cam_free[p->obs_cam[y]]; });
+    for (int k = P.u_start[u]; k < P.u_start[u + 1]; k++) {
+      const int i = o_idx[k], fc = P.cam_free[p->obs_cam[i]];
+      P.o_cam[k] = p->obs_cam[i];
+      P.o_uv[2 * (size_t)k] = p->obs_uv[2 * (size_t)i];
+      P.o_uv[2 * (size_t)k + 1] = p->obs_uv[2 * (size_t)i + 1];
+      if (fc >= 0) inQ[fc] = 1;
+    }
+  }
+  P.qpos.assign(P.nfree, -1);
+  for (int c = 0; c < P.nfree; c++)
+    if (inQ[c]) {
+      P.qpos[c] = (int)P.q_free.size();
+      P.q_free.push_back(c);
+    }
+  P.nQ = (int)P.q_free.size();
+  P.cam_q2Q.resize(n_cam_q);
+  for (int q = 0; q < n_cam_q; q++) P.cam_q2Q[q] = P.qpos[P.cam_free[cams[q]]];
+  return P;
+}
+
+// the caller's share of the arena (BaCommon::extra): [inputs, uploaded in one copy | work | outputs, one copy back]
+struct CovBuffers {
+  size_t in_bytes = 0, out_off = 0, out_bytes = 0, total = 0;
+  size_t off_ok, off_col_unk, off_q_free, off_qpos, off_u_lm, off_u_start, off_o_cam, off_o_uv;  // inputs
+  size_t off_Linv, off_Sdiag, off_X;                                                             // work
+  size_t off_pose, off_point, off_deg, off_ok_out;                                               // outputs (relative to out_off)
+};
+
+CovBuffers cov_buffers(const CovPlan& P, int n, int nblk) {
+  CovBuffers B;
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = at;
+    at += cov_pad(bytes);
+    return o;
+  };
+  B.off_ok = take(sizeof(int));
+  B.off_col_unk = take(sizeof(int) * (size_t)nblk * COV_COLS);
+  B.off_q_free = take(sizeof(int) * (size_t)P.nQ);
+  B.off_qpos = take(sizeof(int) * (size_t)P.nfree);
+  B.off_u_lm = take(sizeof(int) * (size_t)P.nu);
+  B.off_u_start = take(sizeof(int) * ((size_t)P.nu + 1));
+  B.off_o_cam = take(sizeof(int) * (size_t)P.n_o);
+  B.off_o_uv = take(sizeof(double) * 2 * (size_t)P.n_o);
+  B.in_bytes = at;
+  B.off_Linv = take(sizeof(double) * (size_t)((n + COV_NB - 1) / COV_NB) * COV_NB * COV_NB);
+  B.off_Sdiag = take(sizeof(double) * (size_t)n);
+  B.off_X = take(sizeof(double) * (size_t)nblk * n * COV_COLS);
+  B.out_off = at;
+  B.off_pose = take(sizeof(double) * 36 * (size_t)P.nQ) - B.out_off;
+  B.off_point = take(sizeof(double) * 9 * (size_t)P.nu) - B.out_off;
+  B.off_deg = take(sizeof(int) * (size_t)P.nu) - B.out_off;
+  B.out_bytes = at - B.out_off;
+  B.total = at;
+  return B;
+}
+
+// everything behind the validation; host_in / host_out outlive the stream work (the caller synchronises on an error)
+int cov_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const CovPlan& P, BaState& st,
+            std::vector<char>& host_in, std::vector<char>& host_out, CovBuffers& B) {
+  const int n = 6 * P.nfree, m = 6 * P.nQ, nblk = (m + COV_COLS - 1) / COV_COLS;
+  B = cov_buffers(P, n, nblk);
+  BaCaller caller{BaUse::COVARIANCE};
+  caller.extra_bytes = B.total;
+  int rc;
+  if ((rc = ba_setup(ctx, prob, opt, st, caller))) return rc;
+  const BaDims& D = st.D;
+  if (D.nfree != P.nfree) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: free-camera count mismatch");
+  char* dev = st.extra;
+  host_in.assign(B.in_bytes, 0);
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes) memcpy(host_in.data() + off, src, bytes);
+  };
+  const int one = 1;
+  put(B.off_ok, &one, sizeof(int));
+  {
+    std::vector<int> col_unk((size_t)nblk * COV_COLS, -1);
+    for (int j = 0; j < m; j++) col_unk[j] = 6 * P.q_free[j / 6] + j % 6;
+    put(B.off_col_unk, col_unk.data(), sizeof(int) * col_unk.size());
+  }
+  put(B.off_q_free, P.q_free.data(), sizeof(int) * P.q_free.size());
+  put(B.off_qpos, P.qpos.data(), sizeof(int) * P.qpos.size());
+  put(B.off_u_lm, P.u_lm.data(), sizeof(int) * P.u_lm.size());
+  put(B.off_u_start, P.u_start.data(), sizeof(int) * P.u_start.size());
+  put(B.off_o_cam, P.o_cam.data(), sizeof(int) * P.o_cam.size());
+  put(B.off_o_uv, P.o_uv.data(), sizeof(double) * P.o_uv.size());
+  VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), B.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  int* ok = (int*)(dev + B.off_ok);
+  double* X = (double*)(dev + B.off_X);
+  if (P.nQ > 0) {
+    // S as vsl_ba_linearize forms it (dense: this use never takes a band form), then its factor and the columns of S^-1
+    double* Linv = (double*)(dev + B.off_Linv);
+    double* Sdiag = (double*)(dev + B.off_Sdiag);
+    if ((rc = ba_linearize(ctx, st, st.sb, false))) return rc;
+    if ((rc = ba_columns(ctx, st, st.sb))) return rc;
+    if ((rc = ba_schur(ctx, st, st.sb, false, 1.0, 0, D.L, false, false))) return rc;
+    VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+    hipLaunchKernelGGL(ba_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.S, Sdiag);
+    VSL_CHECK_LAUNCH(ctx);
+    if ((rc = vsl_chol_factor_dev(ctx, st.S, n, ok, Linv))) return rc;
+    hipLaunchKernelGGL(ba_cov_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, st.S, Linv, Sdiag,
+                       (const int*)(dev + B.off_col_unk), X, ok);
+    hipLaunchKernelGGL(ba_cov_pose_kernel, dim3((36 * P.nQ + 255) / 256), dim3(256), 0, ctx->stream, n, P.nQ,
+                       (const int*)(dev + B.off_q_free), X, ok, (double*)(dev + B.out_off + B.off_pose));
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  if (P.nu > 0) {
+    BlArgs a;
+    memset(&a, 0, sizeof(a));
+    a.D = D;
+    a.poses = st.poses;
+    a.points = st.points;
+    a.intr = st.intr;
+    a.cam_intr = st.cam_intr;
+    a.cam_free = st.cam_free;
+    hipLaunchKernelGGL(ba_cov_landmark_kernel, dim3(P.nu), dim3(64), sizeof(double) * 27 * (size_t)std::max(P.kmax, 1),
+                       ctx->stream, a, n, (const int*)(dev + B.off_u_lm), (const int*)(dev + B.off_u_start),
+                       (const int*)(dev + B.off_o_cam), (const double*)(dev + B.off_o_uv), (const int*)(dev + B.off_qpos), X,
+                       ok, (double*)(dev + B.out_off + B.off_point), (int*)(dev + B.out_off + B.off_deg));
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  host_out.assign(B.out_bytes + sizeof(int), 0);
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + B.out_off, B.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data() + B.out_bytes, ok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int ok_host;
+  memcpy(&ok_host, host_out.data() + B.out_bytes, sizeof(int));
+  if (!ok_host) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_covariance: the reduced camera system is not positive definite");
+  return VSL_OK;
+}
+
+}  // namespace
+
+extern "C" int vsl_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const int32_t* cams,
+                                 int n_cam_q, double* cov_pose, const int32_t* lms, int n_lm_q, double* cov_point,
+                                 int* n_degenerate) {
+  int rc = ba_validate(ctx, prob);  // an empty problem (n_lms = 0, n_obs = 0) ends here
+  if (rc) return rc;
+  if (!opt || n_cam_q < 0 || n_lm_q < 0 || (n_cam_q > 0 && (!cams || !cov_pose)) || (n_lm_q > 0 && (!lms || !cov_point)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: null argument or negative count");
+  for (int q = 0; q < n_cam_q; q++) {
+    if (cams[q] < 0 || cams[q] >= prob->n_cams) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: camera %d out of range", cams[q]);
+    if (prob->cam_fixed[cams[q]]) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: camera %d is fixed", cams[q]);
+  }
+  for (int q = 0; q < n_lm_q; q++)
+    if (lms[q] < 0 || lms[q] >= prob->n_lms) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: landmark %d out of range", lms[q]);
+  if (n_degenerate) *n_degenerate = 0;
+  if (n_cam_q == 0 && n_lm_q == 0) return VSL_OK;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  CovPlan P;
+  try {
+    P = cov_plan(prob, cams, n_cam_q, lms, n_lm_q);
+  } catch (const std::bad_alloc&) {
+    return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+  }
+  if (P.kmax > COV_KMAX)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: a queried landmark has %d observations (at most %d)", P.kmax, COV_KMAX);
+  std::vector<char> host_in, host_out;  // read / written by copies on the stream: they outlive the synchronisation below
+  CovBuffers B;
+  {
+    BaState st;  // holds the loan of the context's arena
+    try {
+      rc = cov_run(ctx, prob, opt, P, st, host_in, host_out, B);
+    } catch (const std::bad_alloc&) {
+      rc = vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    // an error return may leave kernels and copies queued that use the arena and the host buffers: drain the stream
+    // before the loan ends (a later solve on this context gets the same block)
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+  }
+  if (rc) return rc;
+  const double* pose = (const double*)(host_out.data() + B.off_pose);
+  const double* point = (const double*)(host_out.data() + B.off_point);
+  const int* deg = (const int*)(host_out.data() + B.off_deg);
+  for (int q = 0; q < n_cam_q; q++) memcpy(cov_pose + 36 * (size_t)q, pose + 36 * (size_t)P.cam_q2Q[q], 36 * sizeof(double));
+  int nd = 0;
+  for (int q = 0; q < n_lm_q; q++) {
+    memcpy(cov_point + 9 * (size_t)q, point + 9 * (size_t)P.lm_q2u[q], 9 * sizeof(double));
+    nd += deg[P.lm_q2u[q]] ? 1 : 0;
+  }
+  if (n_degenerate) *n_degenerate = nd;
+  return VSL_OK;
+}

@@ -17,12 +17,15 @@
 //                                                                                       (the context's arena, band forms)
 //   SESSION           vsl_global_bundle_adjust: stored blocks OR the recompute form (ba_recompute_form decides), and the
 //                     camera LM diagonal kept across rejected steps                     (owned arena, band forms)
-enum class BaUse { PARITY_HOOK, SINGLE_LINEARIZE, HOST_LOOP, SESSION };
+//   COVARIANCE        vsl_ba_covariance (ba_cov.hip): stored blocks of one linearisation, plus `extra_bytes` of the
+//                     caller's own in the same block (BaCommon::extra)                  (the context's arena, dense S)
+enum class BaUse { PARITY_HOOK, SINGLE_LINEARIZE, HOST_LOOP, SESSION, COVARIANCE };
 
 struct BaCaller {
   BaUse use;
   const vsl_ba_problem* graph_prob = nullptr;  // the problem whose observations define the covisibility graph (a session rank: the FULL problem); null: the problem itself
   int run_max_obs = 0, run_max_lms = 0;        // SESSION: limits of a landmark run of the recompute-form kernels (ba_large.h BL_THREADS, BL_LMW)
+  size_t extra_bytes = 0;                      // COVARIANCE: bytes the caller carves up itself, at BaCommon::extra
 };
 
 // Buffers of the STORED-BLOCKS form: r / F / E of every observation, written by ba_linearize_kernel and read by the
@@ -68,6 +71,7 @@ struct BaCommon {
   int *lm_start = nullptr, *cam_start = nullptr, *cam_obs = nullptr;
   int* flag = nullptr;           // 128 bytes behind scalars: one copy brings both back
   double* diagc_keep = nullptr;  // SESSION: clamp(diag H_full), reused across rejected steps
+  char* extra = nullptr;         // COVARIANCE: BaCaller::extra_bytes of the same block
   // large systems, gather form of the Schur complement (ba_schur_gather_kernel): per-block pair lists, built on the
   // first use for the landmark range they cover, and the per-observation Y blocks of the current linearisation
   int *pair_cnt = nullptr, *pair_start = nullptr, *pairs = nullptr, *cam_pos = nullptr;

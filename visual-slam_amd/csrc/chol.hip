@@ -699,6 +699,34 @@ int vsl_chol_solve_band_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, i
   return rc;
 }
 
+// The panel factorisation on its own: S <- L (lower triangle, in place), Linv <- the inverted diagonal blocks
+// ((n + CH_NB - 1) / CH_NB blocks of CH_NB x CH_NB, identity-padded), *ok_dev = 1 / 0.  The solve below and
+// vsl_chol_factor_dev run it.
+static int chol_factor_panels(vsl_ctx* ctx, double* S, int n, int ld, int bw, int* ok_dev, double* Linv) {
+  const int one = 1;
+  VSL_HIP(ctx, hipMemcpyAsync(ok_dev, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  for (int k = 0, pi = 0; k < n; k += CH_NB, pi++) {
+    const int nb = n - k < CH_NB ? n - k : CH_NB;
+    double* Li = Linv + (size_t)pi * CH_NB * CH_NB;
+    hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(64), 0, ctx->stream, S, ld, k, nb, ok_dev, Li);
+    const int m = std::min(n - k - nb, bw);  // rows below the diagonal block that the band reaches
+    if (m > 0) {
+      const int n_end = k + nb + m;
+      hipLaunchKernelGGL(chol_panel_kernel, dim3((m + 63) / 64), dim3(256), 0, ctx->stream, S, n_end, ld, k, nb, ok_dev, Li);
+      const int T = (m + 63) / 64;
+      hipLaunchKernelGGL(chol_update_kernel, dim3(T * (T + 1) / 2), dim3(256), 0, ctx->stream, S, n_end, ld, k, nb, T, ok_dev);
+    }
+  }
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+// Dense S (n x n row-major, lower triangle read) <- its Cholesky factor, for callers that solve against it themselves
+// (ba_cov.hip: blocks of the inverse).  Linv: VSL_CHOL_NB^2 doubles per panel, device memory of the caller.
+int vsl_chol_factor_dev(vsl_ctx* ctx, double* S, int n, int* ok_dev, double* Linv) {
+  return chol_factor_panels(ctx, S, n, n, n, ok_dev, Linv);
+}
+
 int vsl_chol_solve_band_impl(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev) {
   const int one = 1;
   const int n_panels = (n + CH_NB - 1) / CH_NB;
@@ -754,20 +782,7 @@ int vsl_chol_solve_band_impl(vsl_ctx* ctx, double* S, double* b, int n, int ld, 
   if (rc) return rc;
   double* Linv = (double*)ws;
   double* y = Linv + (size_t)n_panels * CH_NB * CH_NB;
-  VSL_HIP(ctx, hipMemcpyAsync(ok_dev, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  for (int k = 0, pi = 0; k < n; k += CH_NB, pi++) {
-    const int nb = n - k < CH_NB ? n - k : CH_NB;
-    double* Li = Linv + (size_t)pi * CH_NB * CH_NB;
-    hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(64), 0, ctx->stream, S, ld, k, nb, ok_dev, Li);
-    const int m = std::min(n - k - nb, bw);  // rows below the diagonal block that the band reaches
-    if (m > 0) {
-      const int n_end = k + nb + m;
-      hipLaunchKernelGGL(chol_panel_kernel, dim3((m + 63) / 64), dim3(256), 0, ctx->stream, S, n_end, ld, k, nb, ok_dev, Li);
-      const int T = (m + 63) / 64;
-      hipLaunchKernelGGL(chol_update_kernel, dim3(T * (T + 1) / 2), dim3(256), 0, ctx->stream, S, n_end, ld, k, nb, T, ok_dev);
-    }
-  }
-  VSL_CHECK_LAUNCH(ctx);
+  if ((rc = chol_factor_panels(ctx, S, n, ld, bw, ok_dev, Linv))) return rc;
   // (a failed factorisation leaves Linv / y undefined; the caller looks at *ok_dev before using b)
   for (int k = 0, pi = 0; k < n; k += CH_NB, pi++) {
     const int nb = n - k < CH_NB ? n - k : CH_NB;

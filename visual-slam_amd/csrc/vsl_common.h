@@ -209,6 +209,10 @@ int vsl_chol_solve_dev(vsl_ctx* ctx, double* S, double* b, int n, int* ok_dev);
 // the same on LAPACK-style lower band storage (chol.hip, "BAND FORM"): S = storage + bws, ld = bws = bw + VSL_CHOL_NB
 int vsl_chol_solve_band_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic = 0, double* neg_out = nullptr);
 
+// the dense factorisation alone: S <- L in place, Linv <- the inverted VSL_CHOL_NB x VSL_CHOL_NB diagonal blocks of L
+// (one per panel, identity-padded; device memory of the caller), *ok_dev = 0 if S is not SPD
+int vsl_chol_factor_dev(vsl_ctx* ctx, double* S, int n, int* ok_dev, double* Linv);
+
 // scratch store of the host-buffer API
 int vsl_ctx_scratch_frames(vsl_ctx* ctx, int w, int h, int feat, vsl_frames** out);
 
