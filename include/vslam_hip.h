@@ -508,6 +508,16 @@ int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl
  * robustified problem at the given poses. */
 int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, double* H, double* g, double* cost,
                       int* n_free);
+/* Test hook: the same normal equations in the storage vsl_pose_graph_optimize takes for this graph (same decision,
+ * diagnostics "ba_force_dense", "chol_no_bcr", "chol_no_fused" included), copied back and expanded to the dense n x n
+ * matrix on the host: slot j in [i - half_bandwidth, i] of row i is entry (i, j), a j < 0 is column j + n (the cyclic
+ * form's wrap-around corner), every entry is mirrored.  jacobi_scale = 1: scaled on both sides by the solver's
+ * 1 / (1 + sqrt(column norm^2)) of its first linearisation (g likewise); 0: unscaled as vsl_pgo_linearize.
+ * *storage: 0 dense, 1 band, 2 cyclic band; *half_bandwidth: 0 when dense; *stray_nonzeros: non-zero values in slots the
+ * builder must leave untouched (the 32 padding slots left of each row's band, the trailing 64, and in the linear form
+ * the in-band slots of columns below zero). */
+int vsl_pgo_linearize_stored(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, int jacobi_scale, double* H,
+                             double* g, double* cost, int* n_free, int* storage, int* half_bandwidth, int* stray_nonzeros);
 
 /* --------------------------------------------------------------- DBoW2 path */
 /*

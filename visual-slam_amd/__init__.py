@@ -457,6 +457,20 @@ class Context:
                                           C.byref(cost), C.byref(nf)))
         return Hc.reshape(n, n), g[:n].copy(), cost.value
 
+    def pgo_linearize_stored(self, arr, use_huber=True, huber=1.0, jacobi_scale=False):
+        """The normal equations as the solver stores them for this graph, expanded to dense: H, g, cost and
+        info = dict(storage = 0 dense / 1 band / 2 cyclic band, half_bandwidth, stray_nonzeros, n_free)."""
+        st = self._pgo_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * int((arr.node_fixed == 0).sum())
+        Hc, g = np.zeros(n * n), np.zeros(max(n, 1))
+        cost, nf, storage, bw, stray = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.L.vsl_pgo_linearize_stored(self.h, C.byref(st), C.byref(o), int(bool(jacobi_scale)),
+                                                 Hc.ctypes.data_as(f64p), g.ctypes.data_as(f64p), C.byref(cost), C.byref(nf),
+                                                 C.byref(storage), C.byref(bw), C.byref(stray)))
+        return Hc.reshape(n, n), g[:n].copy(), cost.value, dict(storage=storage.value, half_bandwidth=bw.value,
+                                                                 stray_nonzeros=stray.value, n_free=nf.value)
+
     def bundle_adjust_intrinsics(self, arr, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
         """optimize_intrinsics = true: optimises arr.poses / arr.points / arr.intr in place."""
         st = self._ba_struct(arr)

@@ -587,31 +587,85 @@ int pgo_linearize(vsl_ctx* ctx, PgoState& st, const vsl_ba_options* opt, bool fi
   VSL_HIP(ctx, hipStreamSynchronize(s));
   return VSL_OK;
 }
+// The band forms as a dense symmetric matrix (host): slot s of row i, s = 0 .. bw left of the diagonal, is entry
+// (i, i - s); a column below zero is the wrap-around corner of the cyclic form, entry (i, i - s + n); every entry is
+// mirrored.  Returns how many non-zero values lie where pgo_build_kernel writes nothing: the 32 padding slots left of
+// each row's band, the trailing 64, and -- linear form -- the in-band slots of columns below zero.
+int pgo_expand_band(const PgoState& st, const double* Hs, double* H) {
+  const int n = st.n, ld = st.ld;
+  int stray = 0;
+  std::fill(H, H + (size_t)n * n, 0.0);
+  for (int i = 0; i < n; i++) {
+    const double* row = Hs + (size_t)i * (ld + 1);
+    for (int s = ld; s > st.bw; s--) stray += row[ld - s] != 0.0;
+    for (int s = 0; s <= st.bw; s++) {
+      int j = i - s;
+      if (j < 0) {
+        if (!st.cyclic) {
+          stray += row[ld - s] != 0.0;
+          continue;
+        }
+        j += n;
+      }
+      H[(size_t)i * n + j] = H[(size_t)j * n + i] = row[ld - s];
+    }
+  }
+  for (size_t t = (size_t)n * (ld + 1); t < st.h_elems; t++) stray += Hs[t] != 0.0;
+  return stray;
+}
+
+// the two test hooks: the normal equations at the given poses in the storage pgo_setup chose, returned dense
+int pgo_linearize_hook(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const vsl_ba_options* opt, bool force_dense,
+                       bool jacobi_scale, double* H, double* g, double* cost, int* n_free, int* storage, int* half_bandwidth,
+                       int* stray_nonzeros) {
+  int rc = pgo_validate(ctx, prob);
+  if (rc) return rc;
+  if (!opt) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: options are null", who);
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  PgoState st;
+  st.force_dense = force_dense;
+  if ((rc = pgo_setup(ctx, prob, st))) return rc;
+  // unit scaling: fill scale with ones by pretending every column norm is zero
+  if (!jacobi_scale && st.n > 0) {
+    VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)st.n, ctx->stream));
+    hipLaunchKernelGGL(pgo_scale_kernel, dim3((st.n + 255) / 256), dim3(256), 0, ctx->stream, st.n, st.colsq, st.scale);
+  }
+  double c = 0;
+  if ((rc = pgo_linearize(ctx, st, opt, jacobi_scale, &c))) return rc;
+  int stray = 0;
+  if (H && st.n) {
+    if (st.ld > 0) {
+      std::vector<double> Hs(st.h_elems);
+      VSL_HIP(ctx, hipMemcpy(Hs.data(), st.H, 8 * st.h_elems, hipMemcpyDeviceToHost));
+      stray = pgo_expand_band(st, Hs.data(), H);
+    } else {
+      VSL_HIP(ctx, hipMemcpy(H, st.H, 8 * (size_t)st.n * st.n, hipMemcpyDeviceToHost));
+    }
+  }
+  if (g && st.n) VSL_HIP(ctx, hipMemcpy(g, st.g, 8 * (size_t)st.n, hipMemcpyDeviceToHost));
+  if (cost) *cost = c;
+  if (n_free) *n_free = st.n / 6;
+  if (storage) *storage = st.ld > 0 ? (st.cyclic ? 2 : 1) : 0;
+  if (half_bandwidth) *half_bandwidth = st.ld > 0 ? st.bw : 0;
+  if (stray_nonzeros) *stray_nonzeros = stray;
+  return VSL_OK;
+}
 }  // namespace
 
 // H (n x n row-major, n = 6 x free nodes in node order), g and cost of the robustified problem at the given
 // poses, unscaled -- the test hook next to orc_pgo_linearize.
 extern "C" int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, double* H, double* g,
                                  double* cost, int* n_free) {
-  int rc = pgo_validate(ctx, prob);
-  if (rc) return rc;
-  if (!opt) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_linearize: options are null");
-  VSL_HIP(ctx, hipSetDevice(ctx->device));
-  PgoState st;
-  st.force_dense = true;  // (the hook returns H as a dense matrix)
-  if ((rc = pgo_setup(ctx, prob, st))) return rc;
-  // unit scaling: fill scale with ones by pretending every column norm is zero
-  if (st.n > 0) {
-    VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)st.n, ctx->stream));
-    hipLaunchKernelGGL(pgo_scale_kernel, dim3((st.n + 255) / 256), dim3(256), 0, ctx->stream, st.n, st.colsq, st.scale);
-  }
-  double c = 0;
-  if ((rc = pgo_linearize(ctx, st, opt, false, &c))) return rc;
-  if (H && st.n) VSL_HIP(ctx, hipMemcpy(H, st.H, 8 * (size_t)st.n * st.n, hipMemcpyDeviceToHost));
-  if (g && st.n) VSL_HIP(ctx, hipMemcpy(g, st.g, 8 * (size_t)st.n, hipMemcpyDeviceToHost));
-  if (cost) *cost = c;
-  if (n_free) *n_free = st.n / 6;
-  return VSL_OK;
+  return pgo_linearize_hook(ctx, "vsl_pgo_linearize", prob, opt, true, false, H, g, cost, n_free, nullptr, nullptr, nullptr);
+}
+
+// The same in the storage vsl_pose_graph_optimize takes for this graph (dense, band or cyclic band: H is expanded on the
+// host), with the Jacobi scale of the solver's first linearisation when jacobi_scale is set.
+extern "C" int vsl_pgo_linearize_stored(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, int jacobi_scale,
+                                        double* H, double* g, double* cost, int* n_free, int* storage, int* half_bandwidth,
+                                        int* stray_nonzeros) {
+  return pgo_linearize_hook(ctx, "vsl_pgo_linearize_stored", prob, opt, false, jacobi_scale != 0, H, g, cost, n_free, storage,
+                            half_bandwidth, stray_nonzeros);
 }
 
 extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, vsl_ba_summary* summary) {
