@@ -480,6 +480,20 @@ int vsl_spd_solve_cyclic(vsl_ctx* ctx, const double* S, const double* b, int n, 
  * *n_blocks >= 8 blocks of floor / ceil (n / *n_blocks) >= half_bandwidth + 1 unknowns each -- when the cyclic solver takes
  * such a system, 0 when it does not (the bundle adjustment then keeps the linear band form). */
 int vsl_bcr_cyclic_layout(int n, int half_bandwidth, int* block, int* n_blocks);
+/* Diagnostic: the branch the last SPD solve on this context took (vsl_spd_solve, vsl_spd_solve_cyclic and the solves
+ * inside the bundle adjustment and the pose graph), recorded on the host where the branch is chosen.  *path = one of
+ * VSL_SPD_PATH_*; for the two block-cyclic-reduction paths *block = unknowns per block, *n_blocks = blocks and
+ * *levels = reduction levels (eliminations before the last block), otherwise 0.  VSL_SPD_PATH_NONE before any solve. */
+enum {
+  VSL_SPD_PATH_NONE = 0,
+  VSL_SPD_PATH_DENSE_PANELS = 1,   /* dense storage, one launch per 32-column panel step */
+  VSL_SPD_PATH_BAND_PANELS = 2,    /* band storage, one launch per panel step */
+  VSL_SPD_PATH_BAND_FUSED = 3,     /* band storage, the whole solve in one launch of one workgroup */
+  VSL_SPD_PATH_BAND_TWO_ENDED = 4, /* band storage, eliminated from both ends towards a separator */
+  VSL_SPD_PATH_BCR = 5,            /* block cyclic reduction of a long narrow band */
+  VSL_SPD_PATH_BCR_CYCLIC = 6      /* block cyclic reduction of a cyclic band (ring of blocks) */
+};
+int vsl_ctx_last_spd_path(vsl_ctx* ctx, int* path, int* block, int* n_blocks, int* levels);
 
 /* ------------------------------------------------------------ pose graph optimisation */
 /*

@@ -28,6 +28,8 @@ f64p = C.POINTER(C.c_double)
 STAGES = ["response", "select", "describe", "match", "match_finalize", "ba_linearize", "ba_schur",
           "ba_solve", "bow_transform", "bow_score", "ba_finish", "ba_step"]
 
+SPD_PATHS = ["none", "dense_panels", "band_panels", "band_fused", "band_two_ended", "bcr", "bcr_cyclic"]  # VSL_SPD_PATH_*
+
 OK = 0
 CAM_DS, CAM_PINHOLE, CAM_EUCM, CAM_KB4 = 0, 1, 2, 3  # VSL_CAM_*
 ERR = {-1: "VSL_ERR_INVALID", -2: "VSL_ERR_HIP", -3: "VSL_ERR_NOMEM", -4: "VSL_ERR_CAPACITY",
@@ -200,6 +202,13 @@ class Context:
 
     def set_diagnostic(self, name, value):
         self._ck(self.L.vsl_ctx_set_diagnostic(self.h, name.encode(), C.c_int(int(value))))
+
+    def last_spd_path(self):
+        """(path, block, n_blocks, levels) of the last SPD solve on this context: path is a name from SPD_PATHS; block,
+        n_blocks and levels describe the block cyclic reduction and are 0 on the other paths."""
+        p, B, nb, lv = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._ck(self.L.vsl_ctx_last_spd_path(self.h, C.byref(p), C.byref(B), C.byref(nb), C.byref(lv)))
+        return SPD_PATHS[p.value], B.value, nb.value, lv.value
 
     def spd_solve(self, S, b, half_bandwidth=-1):
         """Solves S x = b with the reduced-camera-system solver (dense, or band storage when half_bandwidth >= 0)."""

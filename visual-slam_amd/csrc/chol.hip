@@ -677,6 +677,14 @@ __global__ __launch_bounds__(CBF_THREADS) void cbf2_backward_kernel(CbfView top,
 
 int vsl_chol_solve_bcr_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out = nullptr);
 
+// host-side record of the branch a solve takes (vsl_ctx_last_spd_path)
+static inline void chol_note_path(vsl_ctx* ctx, int path, int block = 0, int nblk = 0, int levels = 0) {
+  ctx->last_spd_path = path;
+  ctx->last_spd_block = block;
+  ctx->last_spd_nblk = nblk;
+  ctx->last_spd_levels = levels;
+}
+
 // Solves S x = b in place (S destroyed, b <- x).  *ok_dev = 1 on success, 0 if S is not SPD.
 // Dense: ld = n, bw = n.  Band: S = storage + bws, ld = bws = bw + CH_NB (see the file header); bw = the largest
 // i - c of a non-zero entry.
@@ -733,6 +741,7 @@ int vsl_chol_solve_band_impl(vsl_ctx* ctx, double* S, double* b, int n, int ld, 
   if (ld != n && bw <= CBF_MAXBW && !ctx->chol_no_fused) {  // narrow band: one launch for the whole solve, or two-ended
     VSL_HIP(ctx, hipMemcpyAsync(ok_dev, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     const bool two_ended = !ctx->chol_one_ended && bw + CH_NB - 1 <= CBF_MAXBW && n >= 8 * (bw + CH_NB);
+    chol_note_path(ctx, two_ended ? VSL_SPD_PATH_BAND_TWO_ENDED : VSL_SPD_PATH_BAND_FUSED);
     if (!two_ended) {
       void* ws = nullptr;
       int rc = vsl_ctx_dscratch(ctx, sizeof(double) * (2 * (size_t)n + 16), &ws);
@@ -777,6 +786,7 @@ int vsl_chol_solve_band_impl(vsl_ctx* ctx, double* S, double* b, int n, int ld, 
     VSL_CHECK_LAUNCH(ctx);
     return VSL_OK;
   }
+  chol_note_path(ctx, ld == n ? VSL_SPD_PATH_DENSE_PANELS : VSL_SPD_PATH_BAND_PANELS);
   void* ws = nullptr;  // inverse diagonal blocks + the intermediate vector y
   int rc = vsl_ctx_dscratch(ctx, sizeof(double) * ((size_t)n_panels * CH_NB * CH_NB + (size_t)n + 8), &ws);
   if (rc) return rc;
@@ -1713,6 +1723,7 @@ int vsl_chol_solve_bcr_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, in
     active = next;
   }
   const int last = active[0];
+  chol_note_path(ctx, cyclic ? VSL_SPD_PATH_BCR_CYCLIC : VSL_SPD_PATH_BCR, B, nblk, (int)levels.size());
   // product targets per level (bcr_gemm_targets_kernel): the remaining blocks with their one or two updates, the new couplings
   std::vector<std::vector<BcrTarget>> targets(levels.size());
   for (size_t l = 0; l < levels.size(); l++) {

@@ -119,6 +119,16 @@ extern "C" int vsl_ctx_last_ba_layout(vsl_ctx* ctx, int64_t* s_elems, int* bande
   return VSL_OK;
 }
 
+// branch of the last SPD solve on this context (chol.hip records it where it chooses)
+extern "C" int vsl_ctx_last_spd_path(vsl_ctx* ctx, int* path, int* block, int* n_blocks, int* levels) {
+  if (!ctx) return VSL_ERR_INVALID;
+  if (path) *path = ctx->last_spd_path;
+  if (block) *block = ctx->last_spd_block;
+  if (n_blocks) *n_blocks = ctx->last_spd_nblk;
+  if (levels) *levels = ctx->last_spd_levels;
+  return VSL_OK;
+}
+
 int vsl_ctx_dscratch(vsl_ctx* ctx, size_t bytes, void** out) {
   if (bytes > ctx->dscratch_cap) {
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -64,6 +64,9 @@ struct vsl_ctx {
   void* bcr_jobs = nullptr;
   size_t bcr_jobs_cap = 0;
   int bcr_key_n = -1, bcr_key_bw = -1;
+  // branch of the last SPD solve (chol.hip; read-out: vsl_ctx_last_spd_path): VSL_SPD_PATH_*, and for the cyclic
+  // reductions the block size, block count and level count
+  int last_spd_path = 0, last_spd_block = 0, last_spd_nblk = 0, last_spd_levels = 0;
   // device arena lent to vsl_bundle_adjust calls on this context (one allocation reused across solves)
   void* ba_arena = nullptr;
   size_t ba_arena_cap = 0;
