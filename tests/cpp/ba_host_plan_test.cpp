@@ -1,4 +1,4 @@
-// Drives visual-slam_amd/csrc/ba_host_plan.h and chol_layout.h (as plain C++, no HIP); tests/test_ba_host_plan_cpu.py
+// Drives visual-slam_amd/csrc/ba_host_plan.h and chol_plan.h (as plain C++, no HIP); tests/test_ba_host_plan_cpu.py
 // holds the expected values.
 //
 // stdin: one command, its first word:

@@ -128,6 +128,28 @@ def test_a_wider_declared_band_gives_the_same_solution(ctx, name, wider):
     _assert_accurate(case, S, b, x, xl, x_ld, path=path, bw=min(wider, case["n"] - 1))
 
 
+def test_plan_cache_follows_size_bandwidth_and_form(vsl, ctx):
+    # the context keeps ONE reduction plan with its job lists on the device, keyed by (n, bandwidth, form): a chain, a
+    # ring, the chain of the ring's very (n, bw), the first chain again -- every solve with the bytes that a context
+    # which has never held another plan gives
+    first, ring, chain = BY_NAME["bcr-b32-8blk-bw0"], BY_NAME["ring-b32-15blk-bw20"], BY_NAME["bcr-b32-15blk-ragged31-bw20"]
+    assert (first["n"], first["path"]) == (256, "bcr")
+    assert (ring["n"], ring["bw_pass"], ring["path"]) == (479, 20, "bcr_cyclic")
+    assert (chain["n"], chain["bw_pass"], chain["path"]) == (479, 20, "bcr")
+    for case in (first, ring, chain, first):
+        S, b = _system(case["name"])[:2]
+        x = _solve(ctx, case, S, b)
+        _assert_path(ctx, case)
+        fresh = vsl.Context(0)
+        try:
+            x_fresh = _solve(fresh, case, S, b)
+            _assert_path(fresh, case)
+        finally:
+            fresh.close()
+        assert x.tobytes() == x_fresh.tobytes(), case["name"]
+        assert np.all(np.isfinite(x))
+
+
 NEGATIVE = [("dense_panels", 97, 48, False, -1, {}), ("band_panels", 467, 20, False, 20, {"chol_no_fused": 1}),
             ("band_fused", 467, 20, False, 20, {"chol_no_bcr": 1, "chol_one_ended": 1}),
             ("band_two_ended", 467, 20, False, 20, {"chol_no_bcr": 1}), ("bcr", 512, 31, False, 31, {}),

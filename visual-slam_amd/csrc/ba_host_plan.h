@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/vslam_hip.h"
-#include "chol_layout.h"
+#include "chol_plan.h"
 
 // ------------------------------------------------------------------------------------------------ thread team
 // Host loops of the set-up on a few threads (the set-up of a 1000-camera solve was ~15 ms of single-threaded loops
@@ -129,8 +129,8 @@ inline BaLayout ba_reduced_layout(int n, int half_lin, int half_cyc, const BaLay
   // level): the 500-keyframe loop of configs[4] has half bandwidth 18 cameras around the ring, 36 in its best line
   const int bwc = 6 * half_cyc + 5, B_lin = (bw + 1 + 31) / 32 * 32;
   int B_cyc = 0, nblk_cyc = 0;
-  if (!sw.no_cyclic && !sw.schur_atomics && !sw.chol_no_bcr && !sw.chol_no_fused &&
-      vsl_chol_bcr_cyclic_layout(n, bwc, &B_cyc, &nblk_cyc) && 4 * B_cyc <= 3 * B_lin) {
+  if (!sw.no_cyclic && !sw.schur_atomics && chol_ring_available(n, bwc, CholSwitches{sw.chol_no_fused, sw.chol_no_bcr, false}, &B_cyc, &nblk_cyc) &&
+      4 * B_cyc <= 3 * B_lin) {
     y.banded = y.cyclic = true;
     y.bw = bwc;
     y.ldS = y.offS = bwc + VSL_CHOL_NB;

@@ -234,7 +234,6 @@ __global__ __launch_bounds__(256) void chol_bwd_kernel(const double* __restrict_
 // bw extra rows through every step (3 x the update work) and the separator system has twice the bandwidth.
 typedef double v4d_t __attribute__((ext_vector_type(4)));
 #define CBF_THREADS 768  // 12 wavefronts = 3 per SIMD (with 9 -- one thread per window row was enough -- one SIMD carried 3 and the window update, bound by its matrix unit, ran at that SIMD's pace)
-#define CBF_MAXBW 512
 #define CBF_SUB 8
 #define CBF_TCH 6  // window tiles per wavefront whose old values are in flight together
 
@@ -675,37 +674,9 @@ __global__ __launch_bounds__(CBF_THREADS) void cbf2_backward_kernel(CbfView top,
     cbf_backward<true>(rev, k_end_rev, sh);
 }
 
-int vsl_chol_solve_bcr_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out = nullptr);
-
-// host-side record of the branch a solve takes (vsl_ctx_last_spd_path)
-static inline void chol_note_path(vsl_ctx* ctx, int path, int block = 0, int nblk = 0, int levels = 0) {
-  ctx->last_spd_path = path;
-  ctx->last_spd_block = block;
-  ctx->last_spd_nblk = nblk;
-  ctx->last_spd_levels = levels;
-}
-
-// Solves S x = b in place (S destroyed, b <- x).  *ok_dev = 1 on success, 0 if S is not SPD.
-// Dense: ld = n, bw = n.  Band: S = storage + bws, ld = bws = bw + CH_NB (see the file header); bw = the largest
-// i - c of a non-zero entry.
-__global__ void chol_negate_kernel(int n, const double* __restrict__ x, double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = -x[i];
-}
-int vsl_chol_solve_band_impl(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev);
-// neg_out (nullable): -x as well (the bundle adjustment's step is the negated solution: saves its launch on the BCR path)
-int vsl_chol_solve_band_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out) {
-  if (cyclic) return vsl_chol_solve_bcr_dev(ctx, S, b, n, ld, bw, ok_dev, 1, neg_out);  // (the caller has checked the layout)
-  if (ld != n && !ctx->chol_no_fused && !ctx->chol_no_bcr && (bw + 1 + 31) / 32 * 32 <= BCR_MAXB &&
-      n >= 8 * ((bw + 1 + 31) / 32 * 32))  // long narrow band: block cyclic reduction over the whole chip
-    return vsl_chol_solve_bcr_dev(ctx, S, b, n, ld, bw, ok_dev, 0, neg_out);
-  const int rc = vsl_chol_solve_band_impl(ctx, S, b, n, ld, bw, ok_dev);
-  if (rc == VSL_OK && neg_out) {
-    hipLaunchKernelGGL(chol_negate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, b, neg_out);
-    VSL_CHECK_LAUNCH(ctx);
-  }
-  return rc;
-}
+// ---------------------------------------------------------------------------------------------------------------
+// HOST SIDE.  Which solver takes a system is decided in ONE place, chol_choose (chol_plan.h, plain C++ with CPU tests):
+// vsl_chol_solve_band_dev asks it once, records the answer (vsl_ctx_last_spd_path) and runs the solver it names.
 
 // The panel factorisation on its own: S <- L (lower triangle, in place), Linv <- the inverted diagonal blocks
 // ((n + CH_NB - 1) / CH_NB blocks of CH_NB x CH_NB, identity-padded), *ok_dev = 1 / 0.  The solve below and
@@ -735,58 +706,9 @@ int vsl_chol_factor_dev(vsl_ctx* ctx, double* S, int n, int* ok_dev, double* Lin
   return chol_factor_panels(ctx, S, n, n, n, ok_dev, Linv);
 }
 
-int vsl_chol_solve_band_impl(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev) {
-  const int one = 1;
+// dense or band storage, one launch per panel step and direction
+static int chol_solve_panels(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev) {
   const int n_panels = (n + CH_NB - 1) / CH_NB;
-  if (ld != n && bw <= CBF_MAXBW && !ctx->chol_no_fused) {  // narrow band: one launch for the whole solve, or two-ended
-    VSL_HIP(ctx, hipMemcpyAsync(ok_dev, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    const bool two_ended = !ctx->chol_one_ended && bw + CH_NB - 1 <= CBF_MAXBW && n >= 8 * (bw + CH_NB);
-    chol_note_path(ctx, two_ended ? VSL_SPD_PATH_BAND_TWO_ENDED : VSL_SPD_PATH_BAND_FUSED);
-    if (!two_ended) {
-      void* ws = nullptr;
-      int rc = vsl_ctx_dscratch(ctx, sizeof(double) * (2 * (size_t)n + 16), &ws);
-      if (rc) return rc;
-      CbfView v = {S, ld, n, n, bw, 0, 0, nullptr, nullptr, b, (double*)ws, (double*)ws + n};
-      hipLaunchKernelGGL(chol_band_fused_kernel, dim3(1), dim3(CBF_THREADS), 0, ctx->stream, v, ok_dev);
-      VSL_CHECK_LAUNCH(ctx);
-      return VSL_OK;
-    }
-    // top chunk [0, s), bottom chunk [n - sp, n) (both whole panels), separator [s, s + sepn) with bw <= sepn <= bw + 31
-    const int s = ((n - bw) / 2) / CH_NB * CH_NB;
-    const int sp = (n - s - bw) / CH_NB * CH_NB;
-    const int sepn = n - s - sp;
-    const int bwm = sepn - 1, ldm = bwm + CH_NB;  // the separator system, dense, in band storage of its own
-    const size_t mid_elems = (size_t)sepn * (ldm + 1) + 64;
-    const size_t need = 4 * (size_t)n + (size_t)sepn * sepn + 4 * (size_t)sepn + mid_elems + 64;
-    void* ws = nullptr;
-    int rc = vsl_ctx_dscratch(ctx, sizeof(double) * need, &ws);
-    if (rc) return rc;
-    double* p = (double*)ws;
-    double *y_top = p, *dinv_top = p + n, *y_rev = p + 2 * (size_t)n, *dinv_rev = p + 3 * (size_t)n;
-    p += 4 * (size_t)n;
-    double* M3 = p;             // sepn x sepn, followed by b3: cleared together
-    double* b3 = p + (size_t)sepn * sepn;
-    p += (size_t)sepn * sepn + sepn;
-    double *bm = p, *ym = p + sepn, *dinvm = p + 2 * (size_t)sepn;
-    p += 3 * (size_t)sepn;
-    double* Am_store = p;       // band storage of the separator system: cleared (explicit zeros outside the lower triangle)
-    VSL_HIP(ctx, hipMemsetAsync(M3, 0, sizeof(double) * ((size_t)sepn * sepn + sepn), ctx->stream));
-    VSL_HIP(ctx, hipMemsetAsync(Am_store, 0, sizeof(double) * mid_elems, ctx->stream));
-    CbfView top = {S, ld, n, s + sepn, bw, 0, 0, nullptr, nullptr, b, y_top, dinv_top};
-    CbfView rev = {S, ld, n, sp + sepn, bw, sp, sepn, M3, b3, b, y_rev, dinv_rev};
-    hipLaunchKernelGGL(cbf2_factor_kernel, dim3(2), dim3(CBF_THREADS), 0, ctx->stream, top, s, rev, sp, ok_dev);
-    double* Am = Am_store + ldm;
-    hipLaunchKernelGGL(cbf2_mid_build_kernel, dim3((sepn * sepn + 255) / 256), dim3(256), 0, ctx->stream, S, ld, s, sepn, M3, b,
-                       b3, Am, ldm, bm, ok_dev);
-    CbfView mid = {Am, ldm, sepn, sepn, bwm, 0, 0, nullptr, nullptr, bm, ym, dinvm};
-    hipLaunchKernelGGL(chol_band_fused_kernel, dim3(1), dim3(CBF_THREADS), 0, ctx->stream, mid, ok_dev);
-    hipLaunchKernelGGL(cbf2_scatter_kernel, dim3((sepn + 255) / 256), dim3(256), 0, ctx->stream, bm, b, s, sepn, ok_dev);
-    rev.sepn = 0;  // the separator's solution is read from b now
-    hipLaunchKernelGGL(cbf2_backward_kernel, dim3(2), dim3(CBF_THREADS), 0, ctx->stream, top, s, rev, sp, ok_dev);
-    VSL_CHECK_LAUNCH(ctx);
-    return VSL_OK;
-  }
-  chol_note_path(ctx, ld == n ? VSL_SPD_PATH_DENSE_PANELS : VSL_SPD_PATH_BAND_PANELS);
   void* ws = nullptr;  // inverse diagonal blocks + the intermediate vector y
   int rc = vsl_ctx_dscratch(ctx, sizeof(double) * ((size_t)n_panels * CH_NB * CH_NB + (size_t)n + 8), &ws);
   if (rc) return rc;
@@ -812,15 +734,91 @@ int vsl_chol_solve_band_impl(vsl_ctx* ctx, double* S, double* b, int n, int ld, 
   return VSL_OK;
 }
 
+// narrow band: one launch of one workgroup for the whole solve
+static int chol_solve_fused(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev) {
+  const int one = 1;
+  VSL_HIP(ctx, hipMemcpyAsync(ok_dev, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  void* ws = nullptr;
+  int rc = vsl_ctx_dscratch(ctx, sizeof(double) * (2 * (size_t)n + 16), &ws);
+  if (rc) return rc;
+  CbfView v = {S, ld, n, n, bw, 0, 0, nullptr, nullptr, b, (double*)ws, (double*)ws + n};
+  hipLaunchKernelGGL(chol_band_fused_kernel, dim3(1), dim3(CBF_THREADS), 0, ctx->stream, v, ok_dev);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+// narrow band, eliminated from both ends (TwoEndedPlan, chol_plan.h: chunks, separator, scratch)
+static int chol_solve_two_ended(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev) {
+  const int one = 1;
+  VSL_HIP(ctx, hipMemcpyAsync(ok_dev, &one, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  const TwoEndedPlan t = chol_two_ended_plan(n, bw);
+  const int s = t.s, sp = t.sp, sepn = t.sepn;
+  void* ws = nullptr;
+  int rc = vsl_ctx_dscratch(ctx, sizeof(double) * t.doubles, &ws);
+  if (rc) return rc;
+  double* p = (double*)ws;
+  double *M3 = p + t.M3, *b3 = p + t.b3, *bm = p + t.bm;
+  VSL_HIP(ctx, hipMemsetAsync(M3, 0, sizeof(double) * ((size_t)sepn * sepn + sepn), ctx->stream));
+  VSL_HIP(ctx, hipMemsetAsync(p + t.Am_store, 0, sizeof(double) * t.mid_elems, ctx->stream));  // explicit zeros outside the lower triangle
+  CbfView top = {S, ld, n, s + sepn, bw, 0, 0, nullptr, nullptr, b, p + t.y_top, p + t.dinv_top};
+  CbfView rev = {S, ld, n, sp + sepn, bw, sp, sepn, M3, b3, b, p + t.y_rev, p + t.dinv_rev};
+  hipLaunchKernelGGL(cbf2_factor_kernel, dim3(2), dim3(CBF_THREADS), 0, ctx->stream, top, s, rev, sp, ok_dev);
+  double* Am = p + t.Am_store + t.ldm;
+  hipLaunchKernelGGL(cbf2_mid_build_kernel, dim3((sepn * sepn + 255) / 256), dim3(256), 0, ctx->stream, S, ld, s, sepn, M3, b,
+                     b3, Am, t.ldm, bm, ok_dev);
+  CbfView mid = {Am, t.ldm, sepn, sepn, t.bwm, 0, 0, nullptr, nullptr, bm, p + t.ym, p + t.dinvm};
+  hipLaunchKernelGGL(chol_band_fused_kernel, dim3(1), dim3(CBF_THREADS), 0, ctx->stream, mid, ok_dev);
+  hipLaunchKernelGGL(cbf2_scatter_kernel, dim3((sepn + 255) / 256), dim3(256), 0, ctx->stream, bm, b, s, sepn, ok_dev);
+  rev.sepn = 0;  // the separator's solution is read from b now
+  hipLaunchKernelGGL(cbf2_backward_kernel, dim3(2), dim3(CBF_THREADS), 0, ctx->stream, top, s, rev, sp, ok_dev);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+__global__ void chol_negate_kernel(int n, const double* __restrict__ x, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = -x[i];
+}
+
+static int chol_solve_bcr(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out);
+
+// Solves S x = b in place (S destroyed, b <- x).  *ok_dev = 1 on success, 0 if S is not SPD.
+// Dense: ld = n, bw = n.  Band: S = storage + bws, ld = bws = bw + CH_NB (see the file header); bw = the largest
+// i - c of a non-zero entry.  cyclic: the band closes on itself and is laid out for the ring (chol_ring_available).
+// neg_out (nullable): -x as well (the bundle adjustment's step is the negated solution: saves its launch on the BCR path)
+int vsl_chol_solve_band_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out) {
+  const CholChoice c = chol_choose(n, ld != n, bw, cyclic != 0, CholSwitches{ctx->chol_no_fused, ctx->chol_no_bcr, ctx->chol_one_ended});
+  if (c.path == VSL_SPD_PATH_NONE)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "cyclic band of %d unknowns, half bandwidth %d: no block layout (the caller checks chol_ring_available)", n, bw);
+  // host-side record of the branch the solve takes (vsl_ctx_last_spd_path)
+  ctx->last_spd_path = c.path;
+  ctx->last_spd_block = c.B;
+  ctx->last_spd_nblk = c.nblk;
+  ctx->last_spd_levels = c.levels;
+  int rc;
+  switch (c.path) {
+    case VSL_SPD_PATH_BCR:
+    case VSL_SPD_PATH_BCR_CYCLIC: return chol_solve_bcr(ctx, S, b, n, ld, bw, ok_dev, cyclic != 0, neg_out);
+    case VSL_SPD_PATH_BAND_TWO_ENDED: rc = chol_solve_two_ended(ctx, S, b, n, ld, bw, ok_dev); break;
+    case VSL_SPD_PATH_BAND_FUSED: rc = chol_solve_fused(ctx, S, b, n, ld, bw, ok_dev); break;
+    default: rc = chol_solve_panels(ctx, S, b, n, ld, bw, ok_dev); break;
+  }
+  if (rc == VSL_OK && neg_out) {
+    hipLaunchKernelGGL(chol_negate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, b, neg_out);
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  return rc;
+}
+
 int vsl_chol_solve_dev(vsl_ctx* ctx, double* S, double* b, int n, int* ok_dev) {
   return vsl_chol_solve_band_dev(ctx, S, b, n, n, n, ok_dev);
 }
 
-// Test / diagnostic entry point: the solver on a caller-provided system (include/vslam_hip.h).
-extern "C" int vsl_spd_solve(vsl_ctx* ctx, const double* S, const double* b, int n, int half_bandwidth, double* x) {
-  if (!ctx || !S || !b || !x || n <= 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_spd_solve: bad argument");
-  const bool band = half_bandwidth >= 0 && half_bandwidth < n - 1;
-  const int bw = band ? half_bandwidth : n, bws = bw + CH_NB;
+// The two test / diagnostic entry points below: S (host, dense row-major) into device storage -- dense, or band storage
+// of half bandwidth bw, a column below zero being column c + n of the wrap-around corner when `cyclic` --, solve, x back.
+static int spd_solve_host(vsl_ctx* ctx, const char* who, const double* S, const double* b, int n, bool band, int bw, int cyclic,
+                          double* x) {
+  const int bws = bw + CH_NB;
   const size_t elems = band ? (size_t)n * (bws + 1) + 64 : (size_t)n * n;
   double *dS = nullptr, *db = nullptr;
   int* dok = nullptr;
@@ -833,7 +831,8 @@ extern "C" int vsl_spd_solve(vsl_ctx* ctx, const double* S, const double* b, int
       // row i keeps columns [i - bws, i] at storage[i * (bws + 1) ...]; entries beyond the half bandwidth stay zero
       std::vector<double> st(elems, 0.0);
       for (int i = 0; i < n; i++)
-        for (int c = std::max(0, i - bw); c <= i; c++) st[(size_t)i * (bws + 1) + (c - i + bws)] = S[(size_t)i * n + c];
+        for (int c = cyclic ? i - bw : std::max(0, i - bw); c <= i; c++)
+          st[(size_t)i * (bws + 1) + (c - i + bws)] = S[(size_t)i * n + (c < 0 ? c + n : c)];
       e = hipMemcpyAsync(dS, st.data(), sizeof(double) * elems, hipMemcpyHostToDevice, ctx->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     } else {
@@ -841,7 +840,7 @@ extern "C" int vsl_spd_solve(vsl_ctx* ctx, const double* S, const double* b, int
     }
     if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
-      rc = band ? vsl_chol_solve_band_dev(ctx, dS + bws, db, n, bws, bw, dok) : vsl_chol_solve_band_dev(ctx, dS, db, n, n, n, dok);
+      rc = band ? vsl_chol_solve_band_dev(ctx, dS + bws, db, n, bws, bw, dok, cyclic) : vsl_chol_solve_band_dev(ctx, dS, db, n, n, n, dok);
       if (rc == VSL_OK) {
         e = hipMemcpyAsync(&ok, dok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(x, db, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
@@ -852,10 +851,17 @@ extern "C" int vsl_spd_solve(vsl_ctx* ctx, const double* S, const double* b, int
   (void)hipFree(dS);
   (void)hipFree(db);
   (void)hipFree(dok);
-  if (e != hipSuccess) return vsl_fail(ctx, VSL_ERR_HIP, "vsl_spd_solve: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return vsl_fail(ctx, VSL_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   if (rc != VSL_OK) return rc;
-  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_spd_solve: matrix is not positive definite");
+  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: matrix is not positive definite", who);
   return VSL_OK;
+}
+
+// Test / diagnostic entry point: the solver on a caller-provided system (include/vslam_hip.h).
+extern "C" int vsl_spd_solve(vsl_ctx* ctx, const double* S, const double* b, int n, int half_bandwidth, double* x) {
+  if (!ctx || !S || !b || !x || n <= 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_spd_solve: bad argument");
+  const bool band = chol_band_declared(n, half_bandwidth);
+  return spd_solve_host(ctx, "vsl_spd_solve", S, b, n, band, band ? half_bandwidth : n, 0, x);
 }
 
 // Host-only query (no device needed): the ring layout the cyclic solver would use for n unknowns of half bandwidth
@@ -873,41 +879,10 @@ extern "C" int vsl_bcr_cyclic_layout(int n, int half_bandwidth, int* block, int*
 // cyclic distance min(|i - j|, n - |i - j|) <= half_bandwidth.
 extern "C" int vsl_spd_solve_cyclic(vsl_ctx* ctx, const double* S, const double* b, int n, int half_bandwidth, double* x) {
   if (!ctx || !S || !b || !x || n <= 0 || half_bandwidth < 0) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_spd_solve_cyclic: bad argument");
-  const int bw = half_bandwidth, bws = bw + CH_NB;
   int Bq, nq;
-  if (!vsl_chol_bcr_cyclic_layout(n, bw, &Bq, &nq))
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_spd_solve_cyclic: %d unknowns with half bandwidth %d have no cyclic block layout (>= 8 blocks of >= bw + 1 and <= %d unknowns)", n, bw, BCR_MAXB);
-  const size_t elems = (size_t)n * (bws + 1) + 64;
-  double *dS = nullptr, *db = nullptr;
-  int* dok = nullptr;
-  VSL_HIP(ctx, hipMalloc((void**)&dS, sizeof(double) * elems));
-  int rc = VSL_OK, ok = 0;
-  hipError_t e = hipMalloc((void**)&db, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dok, sizeof(int));
-  if (e == hipSuccess) {
-    // row i keeps columns [i - bws, i]; a column below zero is column c + n of the wrap-around corner
-    std::vector<double> st(elems, 0.0);
-    for (int i = 0; i < n; i++)
-      for (int c = i - bw; c <= i; c++) st[(size_t)i * (bws + 1) + (c - i + bws)] = S[(size_t)i * n + (c < 0 ? c + n : c)];
-    e = hipMemcpyAsync(dS, st.data(), sizeof(double) * elems, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-      rc = vsl_chol_solve_bcr_dev(ctx, dS + bws, db, n, bws, bw, dok, 1);
-      if (rc == VSL_OK) {
-        e = hipMemcpyAsync(&ok, dok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(x, db, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      }
-    }
-  }
-  (void)hipFree(dS);
-  (void)hipFree(db);
-  (void)hipFree(dok);
-  if (e != hipSuccess) return vsl_fail(ctx, VSL_ERR_HIP, "vsl_spd_solve_cyclic: %s", hipGetErrorString(e));
-  if (rc != VSL_OK) return rc;
-  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_spd_solve_cyclic: matrix is not positive definite");
-  return VSL_OK;
+  if (!vsl_chol_bcr_cyclic_layout(n, half_bandwidth, &Bq, &nq))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_spd_solve_cyclic: %d unknowns with half bandwidth %d have no cyclic block layout (>= 8 blocks of >= bw + 1 and <= %d unknowns)", n, half_bandwidth, BCR_MAXB);
+  return spd_solve_host(ctx, "vsl_spd_solve_cyclic", S, b, n, true, half_bandwidth, 1, x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -922,12 +897,6 @@ extern "C" int vsl_spd_solve_cyclic(vsl_ctx* ctx, const double* S, const double*
 //   under a nested-dissection ordering of the blocks: no pivoting issues for an SPD matrix, no atomics, reproducible.
 // The right-hand side rides along (z_e = L_e^-1 b_e, b_p -= U1^T z_e, b_q -= U2^T z_e) and the solution is recovered
 // level by level in reverse: x_e = L_e^-T (z_e - U1 x_p - U2 x_q).
-struct BcrJob {
-  int e, p, q;      // eliminated block and its two active neighbours (q = -1: none below)
-  int kp, kq;       // indices of K(e, p) and K(q, e) in this level's coupling array
-  int knew;         // index of K(q, p) in the next level's coupling array (-1: none)
-  int u;            // slot of U1 / U2
-};
 
 // band storage -> dense blocks: D[i] (lower triangle, identity-padded past the block's unknowns), C[i] = block (i + 1, i),
 // b[i].  Block i holds the unknowns [off[i], off[i + 1]) (<= B of them).  CYCLIC band (round 4): the storage of row i
@@ -1069,9 +1038,6 @@ __device__ __forceinline__ void bcr_panel_factor_dpp(double (*W)[CH_NB + 1], int
   }
 }
 
-#ifndef BCR_DPP_PANEL
-#define BCR_DPP_PANEL 1  // 0: the round-2 panel factorisation (four 8-column sub-steps), kept for A/B builds
-#endif
 #define BCR_REG_THREADS 512  // 8 wavefronts = 2 per SIMD: 256 VGPRs each, room for the tiles beside the panel factorisation
 template <int SLOTS>  // tiles per wavefront: 14 for B <= 224 (105 tiles), 17 for B <= 256 (136 tiles)
 __device__ __forceinline__ bool bcr_chol_registers(int B, double* __restrict__ Dg, const double* __restrict__ bg, const double* __restrict__ pend0,
@@ -1130,10 +1096,7 @@ __device__ __forceinline__ bool bcr_chol_registers(int B, double* __restrict__ D
     if (tid < CH_NB) W[rows - 1][tid] = bvec[k + tid];
     __syncthreads();
     BCR_STAMP(1)
-    if (BCR_DPP_PANEL)
-      bcr_panel_factor_dpp<BCR_REG_THREADS>(W, rows, sh BCP_TPASS);
-    else
-      cbf_panel_factor<BCR_REG_THREADS>(W, rows, sh);
+    bcr_panel_factor_dpp<BCR_REG_THREADS>(W, rows, sh BCP_TPASS);
     BCR_STAMP(2)
     if (sh.fail_s) return false;  // workgroup-uniform (cbf_panel_factor ends with a barrier)
     // the factored panel, y and the reciprocal pivots to global memory; right-hand side of the rows below
@@ -1418,85 +1381,13 @@ __global__ __launch_bounds__(256) void bcr_trsm_kernel(const BcrJob* __restrict_
   }
 }
 
-// C (B x B) = C - M^T N   (mode 0: D_p -= U1^T U1, lower tiles only; mode 1: D_q -= U2^T U2, lower tiles only) or
-// K(q, p) = -U2^T U1 (mode 2, all tiles): one 32 x 32 tile per workgroup, the two 32-column slabs of M and N in LDS
-__global__ __launch_bounds__(256) void bcr_gemm_kernel(const BcrJob* __restrict__ jobs, int B, int mode0, const double* __restrict__ U,
-                                                       double* __restrict__ D, double* __restrict__ Knext,
-                                                       const int* __restrict__ ok) {
-  if (!*ok) return;
-  const int mode = mode0 + 2 * (int)blockIdx.z;  // one launch does the D_p updates (z = 0) and the new couplings (z = 1)
-  __shared__ double Ms[BCR_MAXB * 33];
-  __shared__ double Ns[BCR_MAXB * 33];
-  const BcrJob jb = jobs[blockIdx.x];
-  const int tiles = B / 32, ti = blockIdx.y / tiles, tj = blockIdx.y - ti * tiles;
-  if (mode != 2 && tj > ti) return;
-  if (mode != 0 && jb.q < 0) return;
-  if (mode == 2 && jb.knew < 0) return;
-  const size_t BB = (size_t)B * B;
-  const double* U1 = U + (size_t)2 * jb.u * BB;
-  const double* U2 = U1 + BB;
-  const double* M = mode == 0 ? U1 : U2;
-  const double* N = mode == 1 ? U2 : U1;
-  const int tid = threadIdx.x;
-  for (int r0 = tid >> 5; r0 < B; r0 += 32) {  // 4 rows of both slabs per thread per round (eight loads in flight)
-    double vm[4], vn[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int r = r0 + 8 * u;
-      vm[u] = r < B ? M[(size_t)r * B + 32 * ti + (tid & 31)] : 0.0;
-      vn[u] = r < B ? N[(size_t)r * B + 32 * tj + (tid & 31)] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int r = r0 + 8 * u;
-      if (r < B) {
-        Ms[r * 33 + (tid & 31)] = vm[u];
-        Ns[r * 33 + (tid & 31)] = vn[u];
-      }
-    }
-  }
-  __syncthreads();
-  const int i0 = (tid >> 4) * 2, j0 = (tid & 15) * 2;  // a 2 x 2 patch of the tile per thread
-  double a00 = 0, a01 = 0, a10 = 0, a11 = 0;
-  for (int k = 0; k < B; k++) {
-    const double m0 = Ms[k * 33 + i0], m1 = Ms[k * 33 + i0 + 1], n0 = Ns[k * 33 + j0], n1 = Ns[k * 33 + j0 + 1];
-    a00 += m0 * n0;
-    a01 += m0 * n1;
-    a10 += m1 * n0;
-    a11 += m1 * n1;
-  }
-  double* Cb = mode == 0 ? D + (size_t)jb.p * BB : (mode == 1 ? D + (size_t)jb.q * BB : Knext + (size_t)jb.knew * BB);
-  const int gi = 32 * ti + i0, gj = 32 * tj + j0;
-  if (mode == 2) {
-    Cb[(size_t)gi * B + gj] = -a00;
-    Cb[(size_t)gi * B + gj + 1] = -a01;
-    Cb[(size_t)(gi + 1) * B + gj] = -a10;
-    Cb[(size_t)(gi + 1) * B + gj + 1] = -a11;
-  } else {
-    Cb[(size_t)gi * B + gj] -= a00;
-    Cb[(size_t)gi * B + gj + 1] -= a01;   // (entries above the diagonal of a diagonal tile are never read)
-    Cb[(size_t)(gi + 1) * B + gj] -= a10;
-    Cb[(size_t)(gi + 1) * B + gj + 1] -= a11;
-  }
-}
-
-// All products of one level in ONE launch, target by target (round 4; the two launches of bcr_gemm_kernel above -- the
-// D_p updates and new couplings, then the D_q updates, because D_p of one job is D_q of the job above it -- kept for A/B
-// builds under BCR_GEMM_TARGETS 0).  A target is a remaining diagonal block with its one or two updates
-// D_x -= U1(b)^T U1(b) + U2(a)^T U2(a) (lower 32 x 32 tiles only) or a new coupling K(q, p) = -U2^T U1 (all tiles); the sum
-// over the two contributions runs in a fixed order.  16 x 16 tiles of the target on v_mfma_f64_16x16x4_f64, operands
-// straight from the row-major U blocks (a k-row of 16 consecutive doubles per 16 lanes), no operand staging in LDS: the 32 x 32-per-workgroup form staged two 224 x 32 slabs
-// (114 KB: one workgroup per compute unit) and spent five LDS reads per four multiply-adds of a 2 x 2 register patch.
-struct BcrTarget {
-  int c_is_k, c_idx;  // destination: Knext[c_idx] (assigned) or D[c_idx] (updated, lower tiles)
-  int m1, n1;         // first product  M^T N: U block slots (2 u + 0 / 1)
-  int m2, n2;         // second product (-1: none)
-  int pad0, pad1;
-};
-
-#ifndef BCR_GEMM_TARGETS
-#define BCR_GEMM_TARGETS 1
-#endif
+// All products of one level in ONE launch, target by target (BcrTarget, chol_plan.h).  A target is a remaining diagonal
+// block with its one or two updates D_x -= U1(b)^T U1(b) + U2(a)^T U2(a) (lower 32 x 32 tiles only; D_p of one job is D_q
+// of the job above it) or a new coupling K(q, p) = -U2^T U1 (all tiles); the sum over the two contributions runs in a
+// fixed order, the order of the plan's jobs.  16 x 16 tiles of the target on v_mfma_f64_16x16x4_f64, operands straight
+// from the row-major U blocks (a k-row of 16 consecutive doubles per 16 lanes), no operand staging in LDS (a form with
+// one 32 x 32 tile per workgroup and two launches per level staged two 224 x 32 slabs -- 114 KB: one workgroup per
+// compute unit -- and spent five LDS reads per four multiply-adds of a 2 x 2 register patch).
 // workgroup = one 16 x 16 tile, the inner dimension split over its four wavefronts (a wavefront's share of one product
 // is B / 16 <= 16 matrix instructions, all of its operand loads -- both products -- issued before the first of them: ONE
 // exposed round trip; with the whole inner dimension per wavefront the loads of a batch took longer than its eight
@@ -1680,175 +1571,84 @@ __global__ void bcr_gather_kernel(const double* __restrict__ bb, int B, const in
 // a RING -- the neighbour below the last block is the first one -- and every level halves the ring: an even ring's last
 // elimination creates the next ring's wrap coupling, an odd ring's wrap coupling moves on unchanged, a ring of two blocks
 // is one coupling (the sum of both) and ends as a chain.
-int vsl_chol_solve_bcr_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out) {
-  int B = (bw + 1 + 31) / 32 * 32, nblk = (n + B - 1) / B;
-  if (cyclic && !vsl_chol_bcr_cyclic_layout(n, bw, &B, &nblk))
-    return vsl_fail(ctx, VSL_ERR_INVALID, "cyclic band of %d unknowns, half bandwidth %d: no block layout (the caller checks vsl_chol_bcr_cyclic_layout)", n, bw);
-  const size_t BB = (size_t)B * B;
-  std::vector<int> off(nblk + 1);
-  for (int i = 0; i <= nblk; i++) off[i] = cyclic ? (int)((long long)i * n / nblk) : std::min(n, i * B);
-  // levels on the host: active block lists, jobs
-  struct LevelOp { int combine = 0, carry = 0; };  // combine: c[0] += c[1]^T before the solves; carry: c[m - 1] -> next c[m' - 1]
-  std::vector<std::vector<BcrJob>> levels;
-  std::vector<LevelOp> ops;
-  std::vector<int> active(nblk), ncoup;
-  for (int i = 0; i < nblk; i++) active[i] = i;
-  int n_u = 0;
-  while (active.size() > 1) {
-    const int m = (int)active.size();
-    std::vector<BcrJob> jobs;
-    std::vector<int> next;
-    LevelOp op;
-    const bool ring = cyclic && m >= 3;  // a ring of two is handled as a chain with one (combined) coupling
-    if (cyclic && m == 2) op.combine = 1;
-    if (ring && (m & 1)) op.carry = 1;
-    for (int j = 0; j < m; j++) {
-      if (j & 1) {
-        BcrJob jb;
-        jb.e = active[j];
-        jb.p = active[j - 1];
-        jb.q = j + 1 < m ? active[j + 1] : (ring ? active[0] : -1);
-        jb.kp = j - 1;
-        jb.kq = j;
-        jb.knew = jb.q >= 0 ? (j - 1) / 2 : -1;
-        jb.u = n_u++;
-        jobs.push_back(jb);
-      } else {
-        next.push_back(active[j]);
-      }
-    }
-    ncoup.push_back(cyclic ? m : m - 1);
-    levels.push_back(jobs);
-    ops.push_back(op);
-    active = next;
-  }
-  const int last = active[0];
-  chol_note_path(ctx, cyclic ? VSL_SPD_PATH_BCR_CYCLIC : VSL_SPD_PATH_BCR, B, nblk, (int)levels.size());
-  // product targets per level (bcr_gemm_targets_kernel): the remaining blocks with their one or two updates, the new couplings
-  std::vector<std::vector<BcrTarget>> targets(levels.size());
-  for (size_t l = 0; l < levels.size(); l++) {
-    std::vector<BcrTarget>& tl = targets[l];
-    std::vector<int> slot_of(nblk, -1);
-    for (const BcrJob& jb : levels[l]) {   // jobs in block order: the update from the block above (as its q) comes first
-      for (int side = 0; side < 2; side++) {
-        const int x = side ? jb.q : jb.p, us = 2 * jb.u + side;
-        if (x < 0) continue;
-        if (slot_of[x] < 0) {
-          slot_of[x] = (int)tl.size();
-          tl.push_back(BcrTarget{0, x, us, us, -1, -1, 0, 0});
-        } else {
-          tl[slot_of[x]].m2 = tl[slot_of[x]].n2 = us;
-        }
-      }
-      if (jb.knew >= 0 && l + 1 < levels.size()) tl.push_back(BcrTarget{1, jb.knew, 2 * jb.u + 1, 2 * jb.u, -1, -1, 0, 0});
-    }
-  }
-  size_t n_k = 0, n_jobs = 0;
-  for (size_t l = 0; l < levels.size(); l++) {
-    n_k += (size_t)ncoup[l];
-    n_jobs += levels[l].size();
-  }
-  // scratch: D | K (all levels) | U | bb | yy | dinv | jobs
-  size_t max_nj = 1;
-  for (auto& lv : levels) max_nj = std::max(max_nj, lv.size());
-  const size_t linv_doubles = ((size_t)n_u + 1) * (size_t)(B / 32) * 1024;  // per eliminated block (+ the last one), kept for the back-substitution
-  const size_t doubles = (size_t)nblk * BB + n_k * BB + (size_t)2 * n_u * BB + 5 * (size_t)nblk * B + linv_doubles + 16;
-  size_t n_targets = 0;
-  for (auto& tl : targets) n_targets += tl.size();
-  const size_t job_only_bytes = ((n_jobs + 1) * sizeof(BcrJob) + 63) / 64 * 64;
-  const size_t tgt_bytes = ((n_targets + 1) * sizeof(BcrTarget) + 63) / 64 * 64;
-  const size_t job_bytes = job_only_bytes + tgt_bytes + sizeof(int) * ((size_t)nblk + 1);
-  void* ws = nullptr;
-  int rc = vsl_ctx_dscratch(ctx, sizeof(double) * doubles + 256, &ws);
-  if (rc) return rc;
-  double* D = (double*)ws;
-  double* K0 = D + (size_t)nblk * BB;
-  double* U = K0 + n_k * BB;
-  double* bb = U + (size_t)2 * n_u * BB;
-  double* yy = bb + (size_t)nblk * B;
-  double* dinv = yy + (size_t)nblk * B;
-  double* pend = dinv + (size_t)nblk * B;  // [nblk][2][B]
-  double* Linv = pend + (size_t)2 * nblk * B;
-  // the job lists depend on (n, bw) only: uploaded once and kept (an upload per solve needs a host synchronisation in
-  // the middle of an otherwise asynchronous LM iteration)
-  if (ctx->bcr_jobs_cap < job_bytes) {
+// The schedule -- block layout, level lists, product targets, scratch and device block -- is a BcrPlan (chol_plan.h).
+
+// The plan of (n, bw, cyclic) with its job block on the device: the context's one cache slot.  The same key again costs
+// nothing (an upload per solve would be a host synchronisation in the middle of an otherwise asynchronous LM iteration);
+// another key waits for the solves in flight, which read the block, before it rebuilds and uploads.
+static int bcr_plan_get(vsl_ctx* ctx, int n, int bw, int cyclic, const BcrPlan** out) {
+  BcrPlanCache& c = ctx->bcr;
+  if (c.n != n || c.bw != bw || c.cyclic != cyclic) {
     VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->bcr_jobs) (void)hipFree(ctx->bcr_jobs);
-    ctx->bcr_jobs = nullptr;
-    ctx->bcr_jobs_cap = 0;
-    ctx->bcr_key_n = ctx->bcr_key_bw = -1;
-    VSL_HIP(ctx, hipMalloc(&ctx->bcr_jobs, 2 * job_bytes));
-    ctx->bcr_jobs_cap = 2 * job_bytes;
-  }
-  BcrJob* jobs_dev = (BcrJob*)ctx->bcr_jobs;
-  std::vector<BcrJob> flat;
-  std::vector<size_t> job_off, k_off;
-  {
-    size_t ko = 0;
-    for (size_t l = 0; l < levels.size(); l++) {
-      job_off.push_back(flat.size());
-      k_off.push_back(ko);
-      flat.insert(flat.end(), levels[l].begin(), levels[l].end());
-      ko += (size_t)ncoup[l];
+    c.n = -1;
+    if (!bcr_plan_build(n, bw, cyclic != 0, &c.plan))
+      return vsl_fail(ctx, VSL_ERR_INVALID, "cyclic band of %d unknowns, half bandwidth %d: no block layout", n, bw);
+    const BcrPlan& p = c.plan;
+    if (c.dev_cap < p.dev_bytes) {
+      if (c.dev) (void)hipFree(c.dev);
+      c.dev = nullptr;
+      c.dev_cap = 0;
+      VSL_HIP(ctx, hipMalloc(&c.dev, 2 * p.dev_bytes));
+      c.dev_cap = 2 * p.dev_bytes;
     }
+    char* dev = (char*)c.dev;
+    hipStream_t q = ctx->stream;  // (the arrays copied from live in the cache until the next change of key, behind a synchronisation)
+    VSL_HIP(ctx, hipMemcpyAsync(dev, p.jobs.data(), p.jobs.size() * sizeof(BcrJob), hipMemcpyHostToDevice, q));
+    if (!p.targets.empty())
+      VSL_HIP(ctx, hipMemcpyAsync(dev + p.dev_targets, p.targets.data(), p.targets.size() * sizeof(BcrTarget), hipMemcpyHostToDevice, q));
+    VSL_HIP(ctx, hipMemcpyAsync(dev + p.dev_off, p.off.data(), p.off.size() * sizeof(int), hipMemcpyHostToDevice, q));
+    c.n = n;
+    c.bw = bw;
+    c.cyclic = cyclic;
   }
-  BcrTarget* targets_dev = (BcrTarget*)((char*)ctx->bcr_jobs + job_only_bytes);
-  int* off_dev = (int*)((char*)ctx->bcr_jobs + job_only_bytes + tgt_bytes);
-  std::vector<BcrTarget> tflat;
-  std::vector<size_t> tgt_off;
-  for (auto& tl : targets) {
-    tgt_off.push_back(tflat.size());
-    tflat.insert(tflat.end(), tl.begin(), tl.end());
-  }
-  const int key_bw = cyclic ? -2 - bw : bw;  // (one cache slot: the cyclic form of the same (n, bw) is another plan)
-  if (ctx->bcr_key_n != n || ctx->bcr_key_bw != key_bw) {
-    VSL_HIP(ctx, hipMemcpyAsync(jobs_dev, flat.data(), flat.size() * sizeof(BcrJob), hipMemcpyHostToDevice, ctx->stream));
-    if (!tflat.empty())
-      VSL_HIP(ctx, hipMemcpyAsync(targets_dev, tflat.data(), tflat.size() * sizeof(BcrTarget), hipMemcpyHostToDevice, ctx->stream));
-    VSL_HIP(ctx, hipMemcpyAsync(off_dev, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `flat` / `tflat` / `off` are on this stack frame
-    ctx->bcr_key_n = n;
-    ctx->bcr_key_bw = key_bw;
-  }
+  *out = &c.plan;
+  return VSL_OK;
+}
+
+static int chol_solve_bcr(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev, int cyclic, double* neg_out) {
+  const BcrPlan* plan = nullptr;
+  int rc = bcr_plan_get(ctx, n, bw, cyclic, &plan);
+  if (rc) return rc;
+  const BcrPlan& p = *plan;
+  void* ws = nullptr;
+  if ((rc = vsl_ctx_dscratch(ctx, sizeof(double) * p.scratch_doubles + 256, &ws))) return rc;
+  const int B = p.B, nblk = p.nblk, last = p.last, levels = p.levels(), tiles = B / 32, t16 = B / 16;
+  const size_t BB = (size_t)B * B;
+  double* w = (double*)ws;
+  double *D = w + p.D, *K0 = w + p.K, *U = w + p.U, *bb = w + p.bb, *yy = w + p.yy, *dinv = w + p.dinv, *pend = w + p.pend, *Linv = w + p.Linv;
+  const BcrJob* jobs_dev = (const BcrJob*)ctx->bcr.dev;
+  const BcrTarget* targets_dev = (const BcrTarget*)((const char*)ctx->bcr.dev + p.dev_targets);
+  const int* off_dev = (const int*)((const char*)ctx->bcr.dev + p.dev_off);
   hipStream_t q = ctx->stream;
   hipLaunchKernelGGL(bcr_extract_kernel, dim3(64, nblk), dim3(256), 0, q, S, ld, n, ld, b, B, nblk, off_dev, cyclic, D, K0, bb, pend, ok_dev);
-  const int tiles = B / 32;
-  for (size_t l = 0; l < levels.size(); l++) {
-    const int nj = (int)levels[l].size();
-    const BcrJob* jl = jobs_dev + job_off[l];
-    double* Kl = K0 + k_off[l] * BB;
-    double* Kn = l + 1 < levels.size() ? K0 + k_off[l + 1] * BB : nullptr;
-    if (ops[l].combine)
+  for (int l = 0; l < levels; l++) {
+    const int nj = p.level_jobs(l);
+    const BcrJob* jl = jobs_dev + p.job_off[l];
+    double* Kl = K0 + p.k_off[l] * BB;
+    double* Kn = l + 1 < levels ? K0 + p.k_off[l + 1] * BB : nullptr;
+    if (p.combine[l])
       hipLaunchKernelGGL(bcr_add_transposed_kernel, dim3((B * B + 255) / 256), dim3(256), 0, q, B, Kl, Kl + BB, ok_dev);
-    if (ops[l].carry && Kn)
-      hipLaunchKernelGGL(bcr_copy_block_kernel, dim3((B * B + 255) / 256), dim3(256), 0, q, B, Kl + (size_t)(ncoup[l] - 1) * BB,
-                         Kn + (size_t)(ncoup[l + 1] - 1) * BB, ok_dev);
+    if (p.carry[l] && Kn)
+      hipLaunchKernelGGL(bcr_copy_block_kernel, dim3((B * B + 255) / 256), dim3(256), 0, q, B, Kl + (size_t)(p.ncoup[l] - 1) * BB,
+                         Kn + (size_t)(p.ncoup[l + 1] - 1) * BB, ok_dev);
     if (B <= 224)
       hipLaunchKernelGGL(bcr_chol_kernel<14>, dim3(nj), dim3(BCR_REG_THREADS), 0, q, jl, B, D, bb, yy, dinv, pend, ok_dev);
     else
       hipLaunchKernelGGL(bcr_chol_kernel<17>, dim3(nj), dim3(BCR_REG_THREADS), 0, q, jl, B, D, bb, yy, dinv, pend, ok_dev);
     hipLaunchKernelGGL(bcr_dinv_kernel, dim3(nj, tiles), dim3(64), 0, q, jl, B, D, dinv, Linv, ok_dev);
     hipLaunchKernelGGL(bcr_trsm_kernel, dim3(nj, 2 * tiles), dim3(256), 0, q, jl, B, D, Linv, Kl, U, yy, pend, ok_dev);
-#if BCR_GEMM_TARGETS
-    {
-      const int t16 = B / 16;
-      hipLaunchKernelGGL(bcr_gemm_targets_kernel, dim3((unsigned)targets[l].size(), t16 * t16), dim3(256), 0, q,
-                         targets_dev + tgt_off[l], B, U, D, Kn, ok_dev);
-    }
-#else
-    hipLaunchKernelGGL(bcr_gemm_kernel, dim3(nj, tiles * tiles, Kn ? 2 : 1), dim3(256), 0, q, jl, B, 0, U, D, Kn, ok_dev);
-    hipLaunchKernelGGL(bcr_gemm_kernel, dim3(nj, tiles * tiles, 1), dim3(256), 0, q, jl, B, 1, U, D, Kn, ok_dev);
-#endif
+    hipLaunchKernelGGL(bcr_gemm_targets_kernel, dim3((unsigned)p.level_targets(l), t16 * t16), dim3(256), 0, q,
+                       targets_dev + p.tgt_off[l], B, U, D, Kn, ok_dev);
   }
   if (B <= 224)
     hipLaunchKernelGGL(bcr_last_kernel<14>, dim3(1), dim3(BCR_REG_THREADS), 0, q, last, B, D, bb, yy, dinv, pend, ok_dev);
   else
     hipLaunchKernelGGL(bcr_last_kernel<17>, dim3(1), dim3(BCR_REG_THREADS), 0, q, last, B, D, bb, yy, dinv, pend, ok_dev);
   hipLaunchKernelGGL(bcr_last_back_kernel, dim3(1), dim3(CBF_THREADS), 0, q, last, B, D, bb, yy, dinv, ok_dev);
-  for (size_t l = levels.size(); l-- > 0;) {
-    const int nj = (int)levels[l].size();
-    hipLaunchKernelGGL(bcr_back_gemv_kernel, dim3(nj, BCR_GV_CHUNKS), dim3(256), 0, q, jobs_dev + job_off[l], B, U, bb, yy, ok_dev);
-    hipLaunchKernelGGL(bcr_back_kernel, dim3(nj), dim3(CBF_THREADS), 0, q, jobs_dev + job_off[l], B, D, Linv, bb, ok_dev);
+  for (int l = levels; l-- > 0;) {
+    const int nj = p.level_jobs(l);
+    hipLaunchKernelGGL(bcr_back_gemv_kernel, dim3(nj, BCR_GV_CHUNKS), dim3(256), 0, q, jobs_dev + p.job_off[l], B, U, bb, yy, ok_dev);
+    hipLaunchKernelGGL(bcr_back_kernel, dim3(nj), dim3(CBF_THREADS), 0, q, jobs_dev + p.job_off[l], B, D, Linv, bb, ok_dev);
   }
   hipLaunchKernelGGL(bcr_gather_kernel, dim3(1, nblk), dim3(256), 0, q, bb, B, off_dev, b, neg_out, ok_dev);
   VSL_CHECK_LAUNCH(ctx);

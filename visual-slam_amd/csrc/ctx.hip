@@ -82,7 +82,7 @@ extern "C" int vsl_ctx_destroy(vsl_ctx* ctx) {
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
   if (ctx->dscratch) (void)hipFree(ctx->dscratch);
   if (ctx->status_word) (void)hipFree(ctx->status_word);
-  if (ctx->bcr_jobs) (void)hipFree(ctx->bcr_jobs);
+  if (ctx->bcr.dev) (void)hipFree(ctx->bcr.dev);
   if (ctx->ba_arena) (void)hipFree(ctx->ba_arena);
   if (ctx->ba_pin) (void)hipHostFree(ctx->ba_pin);
   if (ctx->hpinned) (void)hipHostFree(ctx->hpinned);

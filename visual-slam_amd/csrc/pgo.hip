@@ -490,7 +490,7 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
     st.ld = 0;
     st.h_elems = (size_t)st.n * st.n;
     if (!st.force_dense && !env_dense && !ctx->ba_force_dense && st.n > 128) {
-      if (!ctx->chol_no_bcr && !ctx->chol_no_fused && 2 * bw_cyc < bw_lin && vsl_chol_bcr_cyclic_layout(st.n, bw_cyc, &Bc, &nc)) {
+      if (2 * bw_cyc < bw_lin && chol_ring_available(st.n, bw_cyc, CholSwitches{ctx->chol_no_fused, ctx->chol_no_bcr, ctx->chol_one_ended}, &Bc, &nc)) {
         st.cyclic = 1;
         st.bw = bw_cyc;
       } else if ((size_t)(bw_lin + 33) * 2 < (size_t)st.n) {

@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/vslam_hip.h"
-#include "chol_layout.h"  // VSL_CHOL_NB, BCR_MAXB, vsl_chol_bcr_cyclic_layout: is there a ring of blocks for this cyclic band?
+#include "chol_plan.h"  // VSL_CHOL_NB, BCR_MAXB, chol_choose / chol_ring_available, the plans of the SPD solvers (chol.hip)
 
 #define VSL_WAVE 64
 #define VSL_META_STRIDE 32  // ints: 128 bytes per image
@@ -60,10 +60,8 @@ struct vsl_ctx {
   size_t dscratch_cap = 0;
   void* hpinned = nullptr;
   size_t hpinned_cap = 0;
-  // job lists of the block-cyclic-reduction solver (chol.hip), kept on the device while (n, bandwidth) stay the same
-  void* bcr_jobs = nullptr;
-  size_t bcr_jobs_cap = 0;
-  int bcr_key_n = -1, bcr_key_bw = -1;
+  // plan of the block-cyclic-reduction solver (chol.hip) and its job lists on the device, kept while (n, bandwidth, form) stay the same
+  BcrPlanCache bcr;
   // branch of the last SPD solve (chol.hip; read-out: vsl_ctx_last_spd_path): VSL_SPD_PATH_*, and for the cyclic
   // reductions the block size, block count and level count
   int last_spd_path = 0, last_spd_block = 0, last_spd_nblk = 0, last_spd_levels = 0;
