@@ -5,7 +5,8 @@
 //   pose_graph_optimization    (:446-587)  the edge selection is the reference's (spanning-tree edges, covisibility
 //                                          edges above the essential threshold, the loop constraint), the
 //                                          optimisation itself runs on the MI355X (vsl_pose_graph_optimize)
-// Same names, arguments and in-place update convention as the reference.
+// Same names, arguments and in-place update convention as the reference.  pose_graph_covariance (no counterpart in the
+// reference) returns the marginal covariances of that graph's keyframes (vsl_pgo_covariance).
 // Round 2 adds the loop DETECTION half (host graph / inverted-file bookkeeping restated; the BoW scores of the
 // surviving candidates go to the GPU in one batched launch, ORBVocabularyAmd::score_batch):
 //   compute_min_connected_covisible (:109-126), detect_loop_candidates (:141-263), insert_new_kf_to_db (:269-276),
@@ -131,67 +132,119 @@ inline void construct_visibility_graph(const FrameCamId& new_fcid, const Cameras
   graph[new_fcid] = new_edges;
 }
 
+namespace amd {
+// The pose graph of loop_closure_utils.h:446-587 as the flat arrays of vsl_pgo_problem: what pose_graph_optimization and
+// pose_graph_covariance both start from.  Node 0 = the current keyframe (not part of `keyframes`: the reference adds it
+// as its own block), further nodes in the order the edges touch them; edges: per keyframe along the spanning tree from
+// the current one, its tree edge (unless the covisibility loop adds it anyway) and its covisibility edges above the
+// essential threshold, and the Sim(3) loop constraint.
+struct PgoFlat {
+  std::vector<Camera*> node_cam;
+  std::map<FrameCamId, int> node_of;  // keyframes only: the current keyframe is node 0
+  std::vector<int32_t> ea, eb;
+  std::vector<double> meas, poses;
+  std::vector<uint8_t> fixed;
+  vsl_pgo_problem prob;
+};
+inline void flatten_pose_graph(Camera& cur_kf, const FrameCamId& loop_candidate_fcid, const Sophus::SE3d& sim3, Cameras& keyframes,
+                               int essential_threshold, const LoopClosureOptions& options, PgoFlat& f) {
+  f.node_cam.assign(1, &cur_kf);
+  auto node = [&](const FrameCamId& id) {
+    auto it = f.node_of.find(id);
+    if (it != f.node_of.end()) return it->second;
+    f.node_cam.push_back(&keyframes.at(id));  // .at(): std::out_of_range like the reference
+    f.node_of.emplace(id, (int)f.node_cam.size() - 1);
+    return (int)f.node_cam.size() - 1;
+  };
+  auto add_edge = [&](int a, int b, const Rt& rel) {
+    double l[6];
+    rt_log(rel, l);
+    f.ea.push_back(a);
+    f.eb.push_back(b);
+    f.meas.insert(f.meas.end(), l, l + 6);
+  };
+  auto tree_and_covisibility_edges = [&](int a, const Camera& K) {
+    const bool strong = K.covisible_weights.count(K.last_fcid) && K.covisible_weights.at(K.last_fcid) > essential_threshold;
+    if (!strong && K.last_fcid.frame_id != -1)  // the spanning-tree edge, unless the covisibility loop adds it anyway
+      add_edge(a, node(K.last_fcid), rt_mul(rt_inv(rt_of(K.T_w_c)), rt_of(keyframes.at(K.last_fcid).T_w_c)));
+    for (const auto& kv : K.covisible_weights)
+      if (kv.second > essential_threshold) add_edge(a, node(kv.first), rt_of(K.covisible_rel_poses.at(kv.first)));
+  };
+  tree_and_covisibility_edges(0, cur_kf);
+  add_edge(0, node(loop_candidate_fcid), rt_inv(rt_of(sim3)));  // the Sim(3) constraint (:514-521)
+  for (FrameCamId id = cur_kf.last_fcid; id.frame_id != -1; id = keyframes.at(id).last_fcid) tree_and_covisibility_edges(node(id), keyframes.at(id));
+
+  const int N = (int)f.node_cam.size();
+  f.poses.resize(7 * (size_t)N);
+  f.fixed.assign(N, 0);
+  for (int i = 0; i < N; i++)
+    for (int c = 0; c < 7; c++) f.poses[7 * (size_t)i + c] = f.node_cam[i]->T_w_c.data()[c];
+  f.fixed[0] = options.set_current_kf_fixed ? 1 : 0;
+  f.prob.n_nodes = N;
+  f.prob.n_edges = (int32_t)f.ea.size();
+  f.prob.poses = f.poses.data();
+  f.prob.node_fixed = f.fixed.data();
+  f.prob.edge_a = f.ea.data();
+  f.prob.edge_b = f.eb.data();
+  f.prob.edge_meas = f.meas.data();
+}
+}  // namespace amd
+
 // loop_closure_utils.h:446-587.  cur_kf is not part of `keyframes` (the reference adds it as its own block).
 inline void pose_graph_optimization(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
                                     const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
                                     const LoopClosureOptions& options) {
   (void)cur_kf_fcid;
-  // node 0 = the current keyframe, further nodes are created as edges touch them
-  std::vector<Camera*> node_cam(1, &cur_kf);
-  std::map<FrameCamId, int> node_of;
-  std::vector<int32_t> ea, eb;
-  std::vector<double> meas;
-  auto node = [&](const FrameCamId& f) {
-    auto it = node_of.find(f);
-    if (it != node_of.end()) return it->second;
-    node_cam.push_back(&keyframes.at(f));  // .at(): std::out_of_range like the reference
-    node_of.emplace(f, (int)node_cam.size() - 1);
-    return (int)node_cam.size() - 1;
-  };
-  auto add_edge = [&](int a, int b, const amd::Rt& rel) {
-    double l[6];
-    amd::rt_log(rel, l);
-    ea.push_back(a);
-    eb.push_back(b);
-    meas.insert(meas.end(), l, l + 6);
-  };
-  auto tree_and_covisibility_edges = [&](int a, const Camera& K) {
-    const bool strong = K.covisible_weights.count(K.last_fcid) && K.covisible_weights.at(K.last_fcid) > essential_threshold;
-    if (!strong && K.last_fcid.frame_id != -1)  // the spanning-tree edge, unless the covisibility loop adds it anyway
-      add_edge(a, node(K.last_fcid), amd::rt_mul(amd::rt_inv(amd::rt_of(K.T_w_c)), amd::rt_of(keyframes.at(K.last_fcid).T_w_c)));
-    for (const auto& kv : K.covisible_weights)
-      if (kv.second > essential_threshold) add_edge(a, node(kv.first), amd::rt_of(K.covisible_rel_poses.at(kv.first)));
-  };
-  tree_and_covisibility_edges(0, cur_kf);
-  add_edge(0, node(loop_candidate_fcid), amd::rt_inv(amd::rt_of(sim3)));  // the Sim(3) constraint (:514-521)
-  for (FrameCamId f = cur_kf.last_fcid; f.frame_id != -1; f = keyframes.at(f).last_fcid) tree_and_covisibility_edges(node(f), keyframes.at(f));
-
-  const int N = (int)node_cam.size();
-  std::vector<double> poses(7 * (size_t)N);
-  std::vector<uint8_t> fixed(N, 0);
-  for (int i = 0; i < N; i++)
-    for (int c = 0; c < 7; c++) poses[7 * (size_t)i + c] = node_cam[i]->T_w_c.data()[c];
-  fixed[0] = options.set_current_kf_fixed ? 1 : 0;
-  vsl_pgo_problem prob;
-  prob.n_nodes = N;
-  prob.n_edges = (int32_t)ea.size();
-  prob.poses = poses.data();
-  prob.node_fixed = fixed.data();
-  prob.edge_a = ea.data();
-  prob.edge_b = eb.data();
-  prob.edge_meas = meas.data();
+  amd::PgoFlat f;
+  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  const int N = f.prob.n_nodes;
   vsl_ba_options opt;
   opt.use_huber = 1;
   opt.huber_parameter = 1.0;
   opt.max_num_iterations = 20;
   opt.verbosity = 0;
   vsl_ba_summary sum;
-  amd::check(vsl_pose_graph_optimize(amd::ctx(), &prob, &opt, &sum), "pose_graph_optimization");
+  amd::check(vsl_pose_graph_optimize(amd::ctx(), &f.prob, &opt, &sum), "pose_graph_optimization");
   for (int i = 0; i < N; i++)
-    for (int c = 0; c < 7; c++) node_cam[i]->T_w_c.data()[c] = poses[7 * (size_t)i + c];
+    for (int c = 0; c < 7; c++) f.node_cam[i]->T_w_c.data()[c] = f.poses[7 * (size_t)i + c];
   if (options.verbosity_level >= 1)  // stands in for summary.BriefReport() (:585)
     std::printf("vslam_hip PGO: %d nodes, %d edges, iterations %d, initial cost %.6e, final cost %.6e, termination %d\n", N,
-                prob.n_edges, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination);
+                f.prob.n_edges, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination);
+}
+
+// Marginal covariances of the keyframes of that pose graph as it stands (vsl_pgo_covariance; the reference has no
+// counterpart -- g2o and gtsam offer marginals, Ceres ceres::Covariance): what a caller gates the next loop candidate
+// with after a closure.  Same arguments as pose_graph_optimization and the same graph (amd::flatten_pose_graph, HuberLoss
+// 1.0); nothing is optimised, no pose is written.  query: keyframes of the graph -- cur_kf_fcid for the current one,
+// which must then be free (options.set_current_kf_fixed = false); a keyframe the graph does not reach is
+// std::out_of_range.  cov_out: 6 x 6 over the tangent (upsilon, omega) of T_w_c exp(delta), in the unit of the edge
+// residuals.  std::domain_error when the normal equations are singular to working precision (VSL_ERR_NUMERIC: no fixed
+// node).  Returns the route the device took: 0 dense, 1 band, 2 folded ring.
+inline int pose_graph_covariance(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
+                                 const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
+                                 const LoopClosureOptions& options, const std::vector<FrameCamId>& query,
+                                 std::map<FrameCamId, PoseCovariance>& cov_out) {
+  cov_out.clear();
+  amd::PgoFlat f;
+  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  std::vector<int32_t> nodes;
+  for (const FrameCamId& id : query) nodes.push_back(id == cur_kf_fcid ? 0 : f.node_of.at(id));
+  vsl_ba_options opt;
+  opt.use_huber = 1;
+  opt.huber_parameter = 1.0;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  std::vector<double> cov(36 * nodes.size());
+  int storage = 0;
+  const int rc = vsl_pgo_covariance(amd::ctx(), &f.prob, &opt, nodes.data(), (int)nodes.size(), cov.data(), &storage);
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
+  amd::check(rc, "pose_graph_covariance");
+  for (size_t q = 0; q < nodes.size(); q++) {
+    PoseCovariance& m = cov_out[query[q]];
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) m(i, j) = cov[36 * q + 6 * i + j];
+  }
+  return storage;
 }
 
 

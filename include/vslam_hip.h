@@ -431,8 +431,9 @@ int vsl_ba_residuals_jacobians(vsl_ctx* ctx, const vsl_ba_problem* prob, double*
  * VSL_ERR_INVALID.  Every block is exactly symmetric; the result does not depend on what else is queried (a subset
  * query returns the bits of the same blocks of a full query) and is the same from run to run.
  * DENSE ONLY: S is formed, factorised and inverted column by column in dense storage whatever its size (the dense path
- * of vsl_spd_solve); selected inversion on the band / cyclic-band forms of large maps is not implemented.  A queried
- * landmark may have at most 256 observations (VSL_ERR_INVALID beyond). */
+ * of vsl_spd_solve).  The band primitive now exists (vsl_spd_inverse_band, used by vsl_pgo_covariance); this call does
+ * not use it yet, because S would have to be built in band form through the session set-up.  A queried landmark may
+ * have at most 256 observations (VSL_ERR_INVALID beyond). */
 int vsl_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
                       const int32_t* cams, int n_cam_q, double* cov_pose,   /* [36*n_cam_q] row-major */
                       const int32_t* lms,  int n_lm_q,  double* cov_point,  /* [9*n_lm_q]   row-major */
@@ -476,6 +477,18 @@ int vsl_spd_solve(vsl_ctx* ctx, const double* S, const double* b, int n, int hal
  * closed loop ordered along the trajectory): block cyclic reduction over a ring of blocks.  VSL_ERR_INVALID when the system
  * has no such block layout (fewer than 8 blocks of >= half_bandwidth + 1 unknowns). */
 int vsl_spd_solve_cyclic(vsl_ctx* ctx, const double* S, const double* b, int n, int half_bandwidth, double* x);
+/* Selected inversion: the entries of Z = S^-1 inside the band of S, in O(n half_bandwidth^2) from the band Cholesky
+ * factor (Takahashi's recurrence over the 32-column panels, last panel first; one launch for half_bandwidth <= 512
+ * unless "chol_no_fused" is set).  S: HOST row-major n x n, symmetric positive definite, only the lower triangle is
+ * read and only where |i - j| <= half_bandwidth (cyclic = 1: where min(|i - j|, n - |i - j|) <= half_bandwidth);
+ * whatever else S holds is ignored.  Z (host, n x n row-major) receives the inverse's entries at those positions,
+ * mirrored and exactly symmetric, and exactly 0.0 everywhere else.  A cyclic band is folded into a linear band of at
+ * most twice the half bandwidth (ring position p -> 2 p on the way out, 2 (n - 1 - p) + 1 on the way back) and inverted
+ * there; the ring solver's reduction is not used.  half_bandwidth < 0, a band that is not narrower than the matrix
+ * (half_bandwidth >= n - 1) or a ring whose folded band is not (2 half_bandwidth >= n - 1): the FULL inverse, by the
+ * dense factorisation and one solve per unit column.  VSL_ERR_NUMERIC if S is not positive definite (the context stays
+ * usable); n = 0: VSL_OK, nothing is launched.  The same input gives the same bits. */
+int vsl_spd_inverse_band(vsl_ctx* ctx, const double* S, int n, int half_bandwidth, int cyclic, double* Z);
 /* Host-only (no device needed): 1 and the ring layout -- *block unknowns per solver block (a multiple of 32, <= 256),
  * *n_blocks >= 8 blocks of floor / ceil (n / *n_blocks) >= half_bandwidth + 1 unknowns each -- when the cyclic solver takes
  * such a system, 0 when it does not (the bundle adjustment then keeps the linear band form). */
@@ -518,6 +531,23 @@ typedef struct vsl_pgo_problem {
  * odometry + covisibility edges, and the loop edge that closes the ring) -- in linear / cyclic band storage and solved by
  * the band / ring solvers of the reduced camera system (diagnostic "ba_force_dense" / VSL_PGO_DENSE: always dense). */
 int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, vsl_ba_summary* summary);
+/* Marginal covariances of the pose graph's nodes at the poses handed in: what g2o / gtsam marginals and
+ * ceres::Covariance offer beside the solve.  Nothing is optimised (prob->poses are only read, opt->max_num_iterations
+ * is ignored).  H = J^T J exactly as vsl_pgo_linearize documents it (Huber corrector when opt->use_huber, no Jacobi
+ * scaling, no damping, tangent (upsilon, omega) of T * exp(delta)); block q of cov [36 * n_q, row-major] is the 6 x 6
+ * diagonal block of H^-1 of node nodes[q], in the unit of the edge residuals.  nodes are NODE ids (not free indices):
+ * a fixed node or an id out of range gives VSL_ERR_INVALID; duplicates are allowed; n_q = 0 returns VSL_OK and launches
+ * nothing.  H not positive definite to working precision -- no fixed node (the gauge is free), a free node without an
+ * edge -- gives VSL_ERR_NUMERIC by the rule of vsl_ba_covariance: a pivot L_ii^2 <= 2^-36 H_ii.  Every block is exactly
+ * symmetric, a subset query returns the bits of the same blocks of a full query, two calls return the same bits.
+ * *storage (nullable) reports the route, the decision being vsl_pose_graph_optimize's own:
+ *   0  dense (at most 128 unknowns, a graph that is not narrow, "ba_force_dense" / VSL_PGO_DENSE): dense factor, one
+ *      solve per queried unit column;
+ *   1  linear band in the nodes' own order: selected inversion (vsl_spd_inverse_band's kernels), O(n bandwidth^2);
+ *   2  ring: the free nodes are relabelled by the fold of vsl_spd_inverse_band on the host (a diagonal block does not
+ *      move under a relabelling), H is built in linear band storage of the folded order, then as route 1. */
+int vsl_pgo_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* nodes, int n_q,
+                       double* cov, int* storage);
 /* Test hook: H = J^T J (n x n row-major, n = 6 x free nodes in node order), g = J^T r and the cost of the
  * robustified problem at the given poses. */
 int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, double* H, double* g, double* cost,

@@ -232,6 +232,17 @@ class Context:
                                              x.ctypes.data_as(f64p)))
         return x
 
+    def spd_inverse_band(self, S, half_bandwidth=-1, cyclic=False):
+        """The entries of S^-1 inside the (cyclic) band of S, everything else exactly 0 (vsl_spd_inverse_band: selected
+        inversion on the band Cholesky factor); the full inverse when half_bandwidth < 0 or the band is the whole matrix."""
+        S = np.ascontiguousarray(S, np.float64)
+        n = S.shape[0] if S.ndim == 2 else 0
+        assert S.size == n * n
+        Z = np.zeros((n, n), np.float64)
+        self._ck(self.L.vsl_spd_inverse_band(self.h, S.ctypes.data_as(f64p), n, int(half_bandwidth), int(bool(cyclic)),
+                                             Z.ctypes.data_as(f64p)))
+        return Z
+
     # ---- keypoints.h drop-ins (host buffers)
     def detect_describe(self, img, num_features=1500, rotate=True):
         img, p, w, h, pitch = _img(img)
@@ -479,6 +490,20 @@ class Context:
                                                  C.byref(storage), C.byref(bw), C.byref(stray)))
         return Hc.reshape(n, n), g[:n].copy(), cost.value, dict(storage=storage.value, half_bandwidth=bw.value,
                                                                  stray_nonzeros=stray.value, n_free=nf.value)
+
+    def pgo_covariance(self, arr, nodes=None, use_huber=True, huber=1.0):
+        """Marginal covariances of the pose graph's nodes at arr's poses (vsl_pgo_covariance; nothing is optimised).
+        nodes: node ids (None: all free nodes, ascending).  Returns (cov [n_q, 6, 6], storage) with storage = 0 dense /
+        1 linear band / 2 folded ring: the route the call took."""
+        st = self._pgo_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        nodes = np.flatnonzero(arr.node_fixed == 0) if nodes is None else nodes
+        nodes = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        cov = np.zeros((len(nodes), 6, 6))
+        storage = C.c_int(-1)
+        self._ck(self.L.vsl_pgo_covariance(self.h, C.byref(st), C.byref(o), nodes.ctypes.data_as(i32p), len(nodes),
+                                           cov.ctypes.data_as(f64p), C.byref(storage)))
+        return cov, storage.value
 
     def bundle_adjust_intrinsics(self, arr, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
         """optimize_intrinsics = true: optimises arr.poses / arr.points / arr.intr in place."""

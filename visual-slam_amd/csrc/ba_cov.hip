@@ -22,10 +22,13 @@
 // workgroup (an output of v_mfma_f64_16x16x4_f64 depends on its own row of A and column of B only), so a subset query
 // returns the bits of the same rows of a full query, and two calls return the same bits.
 //
-// DENSE ONLY.  S is formed and factorised in dense storage whatever its size (the dense path of vsl_spd_solve);
-// selected inversion on the band and cyclic-band forms that vsl_global_bundle_adjust uses for large maps is not
-// implemented, so the cost grows with (6 x free cameras)^2 x columns.  A queried landmark may have at most COV_KMAX
-// observations (its W blocks are kept in LDS).
+// DENSE ONLY.  S is formed and factorised in dense storage whatever its size (the dense path of vsl_spd_solve), so the
+// cost grows with (6 x free cameras)^2 x columns.  The band primitive now exists (chol.hip, "SELECTED INVERSION": what
+// vsl_pgo_covariance runs on); this path does not use it yet -- S of a large map would have to be built in the band and
+// cyclic-band forms of vsl_global_bundle_adjust through the session set-up.  A queried landmark may have at most
+// COV_KMAX observations (its W blocks are kept in LDS).
+// The solve kernel is also what vsl_spd_inverse_band and vsl_pgo_covariance use on their dense routes
+// (vsl_cov_unit_columns_dev below).
 //
 // "Not positive definite" is decided to working precision: a pivot L_ii^2 <= 2^-36 S_ii fails the factorisation
 // (VSL_ERR_NUMERIC); the ratio is invariant under a rescaling of the unknowns.  A free gauge (no fixed camera) leaves
@@ -75,7 +78,7 @@ __global__ void ba_cov_diag_kernel(int n, const double* __restrict__ S, double* 
 // L L^T X = E for the COV_COLS unit columns col_unk[COV_COLS * blockIdx.x ..] (-1: an empty column) of this workgroup,
 // in its n x COV_COLS block of X.  L: the dense factor (n x n row-major, lower triangle), Linv: its inverted COV_NB x
 // COV_NB diagonal blocks (zero above the diagonal, identity-padded in the last one), Sdiag: diag S before the
-// factorisation.  Right-looking in both directions, one panel of COV_NB unknowns per step:
+// factorisation (nullable: no pivot test here).  Right-looking in both directions, one panel of COV_NB unknowns per step:
 //   forward   Y_k = Linv_kk B_k, then B_i -= L[i, k] Y_k for the rows below, COV_CHUNK rows of the panel in LDS at a time
 //   backward  X_k = Linv_kk^T Y_k, then Y_c -= L[k, c]^T X_k for the columns before, COV_CHUNK columns at a time
 // every product a chain of eight v_mfma_f64_16x16x4_f64 over the 32 unknowns of the panel, one 16 x 16 tile per wavefront.
@@ -92,10 +95,11 @@ __global__ __launch_bounds__(COV_THREADS) void ba_cov_solve_kernel(int n, const 
   static_assert(COV_CHUNK * COV_LP <= COV_NB * COV_LQ, "the forward view fits");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
   int bad = *ok ? 0 : 1;
-  for (int i = tid; i < n; i += COV_THREADS) {
-    const double l = L[(size_t)i * n + i], p = l * l;
-    if (!(p > COV_PIVOT_TOL * Sdiag[i]) || !isfinite(p)) bad = 1;
-  }
+  if (Sdiag)  // (null: the caller keeps to the factorisation's own pivot test)
+    for (int i = tid; i < n; i += COV_THREADS) {
+      const double l = L[(size_t)i * n + i], p = l * l;
+      if (!(p > COV_PIVOT_TOL * Sdiag[i]) || !isfinite(p)) bad = 1;
+    }
   if (__syncthreads_or(bad)) {
     if (blockIdx.x == 0 && tid == 0) *ok = 0;
     return;
@@ -498,6 +502,15 @@ int cov_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
 }
 
 }  // namespace
+
+int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double* Linv, const double* Sdiag, const int* col_unk,
+                             int nblk, double* X, int* ok_dev) {
+  static_assert(COV_COLS == 16, "vsl_cov_x_at (vsl_common.h) spells the block width out");
+  if (nblk <= 0) return VSL_OK;
+  hipLaunchKernelGGL(ba_cov_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, L, Linv, Sdiag, col_unk, X, ok_dev);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
 
 extern "C" int vsl_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const int32_t* cams,
                                  int n_cam_q, double* cov_pose, const int32_t* lms, int n_lm_q, double* cov_point,

@@ -1654,3 +1654,273 @@ static int chol_solve_bcr(vsl_ctx* ctx, double* S, double* b, int n, int ld, int
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// SELECTED INVERSION: the band of Z = S^-1 from the band Cholesky factor (Takahashi's recurrence), O(n bw^2) where a
+// column-by-column inverse through a dense factor costs O(n^2) per column.  The factorisation is chol_factor_panels: L
+// in place, Linv = the inverted 32 x 32 diagonal blocks.  The panels are visited LAST FIRST; for the columns
+// K = [k, k + nb) with W = the rows [k + nb, min(n, k + nb + bw)) below them and G = L_WK L_KK^-1
+//     Z_WK = -Z_WW G                          (every |i - j| inside W is <= bw - 1: in-band entries of later panels only)
+//     Z_KK = L_KK^-T L_KK^-1 - G^T Z_WK       (lower triangle stored: its mirror is the upper one)
+// RAGGED CORNER.  Z_KK needs the WHOLE product Z_WW G, the rows i - c > bw of a panel column c included.  They are true
+// entries of the inverse outside the band; a step parks them in the 32 padding slots that the band storage keeps left of
+// every row, reads them back for Z_KK and clears them again (zeroing them BEFORE Z_KK is wrong by O(1):
+// tests/test_selinv_ref_cpu.py keeps that on record).  No later step reads them: the next window starts one panel higher.
+// Three phases per step, each a set of independent 16 x 16 tiles of v_mfma_f64_16x16x4_f64 dealt to wavefronts, every
+// tile one chain over its inner index in ascending order -- no atomics, nothing to wait for between workgroups, the
+// same bits from run to run:
+//     G   (rows of W) x 32          inner index: the 32 panel columns          -> scratch
+//     T   Z_WW G, (rows of W) x 32  inner index: the rows of W                 -> Z_WK = -T, ragged rows included
+//     KK  32 x 32, three tiles      inner index: 32 (Linv) + the rows of W     -> Z_KK, then the ragged slots are cleared
+// Z WINDOW.  Z_WW is (bw + 32)^2 doubles at most -- 508 KB at bw = 220 -- and does not fit LDS; an operand tile is used
+// by ONE matrix instruction chain only, so staging it in LDS would add a copy and a barrier without any reuse.  The
+// operands are therefore read straight from global memory in the instruction's own layout: the window was written by
+// the previous steps of the same launch and sits in L2 (G and Z_WK likewise), LDS is not used at all.
+// LAUNCHES.  A step depends on the one before it.  Bands up to CBF_MAXBW run every step in ONE launch of one workgroup
+// (a launch per phase would be 3 n / 32 launches of 5-22 us around a few microseconds of work each); wider bands go
+// panel by panel, G and T spread over several workgroups (chol_selinv_plan).
+#define SI_THREADS 512
+#define SI_WAVES (SI_THREADS / 64)
+
+struct SiArgs {
+  const double* L;     // the factor, band storage (pre-offset)
+  double* Z;           // the inverse's band, same layout
+  const double* Linv;  // inverted diagonal blocks, one per panel
+  double* G;           // scratch: window rows x 32
+  int n, ld, bw;
+};
+
+// One 16 x 16 tile C = sum_kk A(i, kk) B(kk, j), kk = 0 .. K - 1 ascending in two interleaved chains (kk mod 8 < 4 and
+// >= 4) that are added at the end.  fa / fb return 0.0 outside their operand.  Lane l receives C[(l >> 4) + 4 q][l & 15].
+template <class FA, class FB>
+__device__ __forceinline__ v4d_t si_tile(int K, FA&& fa, FB&& fb) {
+  const int lane = threadIdx.x & 63, kq = lane >> 4, l16 = lane & 15;
+  v4d_t a0 = {0.0, 0.0, 0.0, 0.0}, a1 = {0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < K; k0 += 8) {
+    a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(fa(l16, k0 + kq), fb(k0 + kq, l16), a0, 0, 0, 0);
+    a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(fa(l16, k0 + 4 + kq), fb(k0 + 4 + kq, l16), a1, 0, 0, 0);
+  }
+  v4d_t c;
+#pragma unroll
+  for (int q = 0; q < 4; q++) c[q] = a0[q] + a1[q];
+  return c;
+}
+
+struct SiStep {
+  int k, nb, m, base;  // panel columns [k, k + nb), window rows [base, base + m)
+  const double* Li;
+};
+__device__ __forceinline__ SiStep si_step(const SiArgs& a, int pi) {
+  SiStep s;
+  s.k = pi * CH_NB;
+  s.nb = min(CH_NB, a.n - s.k);
+  s.m = min(a.n - s.k - s.nb, a.bw);
+  s.base = s.k + s.nb;
+  s.Li = a.Linv + (size_t)pi * CH_NB * CH_NB;
+  return s;
+}
+
+// G = L_WK L_KK^-1; unit / n_units: this wavefront among those that share the phase
+__device__ __forceinline__ void si_phase_g(const SiArgs& a, const SiStep& s, int unit, int n_units) {
+  const int lane = threadIdx.x & 63, kq = lane >> 4, l16 = lane & 15;
+  const int tiles = 2 * ((s.m + 15) >> 4);
+  for (int t = unit; t < tiles; t += n_units) {
+    const int r0 = 16 * (t >> 1), c0 = 16 * (t & 1);
+    const v4d_t c = si_tile(
+        CH_NB,
+        [&](int i, int kk) { return (r0 + i < s.m && kk < s.nb) ? a.L[(size_t)(s.base + r0 + i) * a.ld + s.k + kk] : 0.0; },
+        [&](int kk, int j) { return s.Li[kk * CH_NB + c0 + j]; });
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int r = r0 + kq + 4 * q;
+      if (r < s.m) a.G[(size_t)r * CH_NB + c0 + l16] = c[q];
+    }
+  }
+}
+
+// Z_WK = -Z_WW G, all rows of the window (the ragged ones land in their rows' padding slots)
+__device__ __forceinline__ void si_phase_t(const SiArgs& a, const SiStep& s, int unit, int n_units) {
+  const int lane = threadIdx.x & 63, kq = lane >> 4, l16 = lane & 15;
+  const int tiles = 2 * ((s.m + 15) >> 4);
+  for (int t = unit; t < tiles; t += n_units) {
+    const int r0 = 16 * (t >> 1), c0 = 16 * (t & 1);
+    const v4d_t c = si_tile(
+        s.m,
+        [&](int i, int j) {  // entry (r0 + i, j) of the symmetric window: the lower triangle is stored
+          const int r = r0 + i;
+          if (r >= s.m || j >= s.m) return 0.0;
+          const int hi = max(r, j), lo = min(r, j);
+          return a.Z[(size_t)(s.base + hi) * a.ld + s.base + lo];
+        },
+        [&](int j, int cc) { return j < s.m ? a.G[(size_t)j * CH_NB + c0 + cc] : 0.0; });
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int r = r0 + kq + 4 * q;
+      if (r < s.m && c0 + l16 < s.nb) a.Z[(size_t)(s.base + r) * a.ld + s.k + c0 + l16] = -c[q];
+    }
+  }
+}
+
+// Z_KK = Linv^T Linv + G^T (Z_WW G), lower triangle; one workgroup.  Ends with the ragged slots cleared.
+__device__ __forceinline__ void si_phase_kk(const SiArgs& a, const SiStep& s) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kq = lane >> 4, l16 = lane & 15;
+  if (wave < 3) {
+    const int a0 = wave == 0 ? 0 : 16, b0 = wave == 2 ? 16 : 0;  // tiles (0, 0), (1, 0), (1, 1)
+    const v4d_t c = si_tile(
+        CH_NB + s.m,
+        [&](int i, int kk) {
+          if (kk < CH_NB) return s.Li[kk * CH_NB + a0 + i];
+          const int r = kk - CH_NB;
+          return r < s.m ? a.G[(size_t)r * CH_NB + a0 + i] : 0.0;
+        },
+        [&](int kk, int j) {
+          if (kk < CH_NB) return s.Li[kk * CH_NB + b0 + j];
+          const int r = kk - CH_NB;
+          return (r < s.m && b0 + j < s.nb) ? -a.Z[(size_t)(s.base + r) * a.ld + s.k + b0 + j] : 0.0;
+        });
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int i = a0 + kq + 4 * q, j = b0 + l16;
+      if (i < s.nb && j <= i && i - j <= a.bw) a.Z[(size_t)(s.k + i) * a.ld + s.k + j] = c[q];  // (a band narrower than the panel)
+    }
+  }
+  __syncthreads();  // the ragged rows of Z_WK have been read
+  for (int idx = threadIdx.x; idx < s.m * CH_NB; idx += blockDim.x) {
+    const int r = idx >> 5, cc = idx & 31;
+    if (cc < s.nb && (s.base + r) - (s.k + cc) > a.bw) a.Z[(size_t)(s.base + r) * a.ld + s.k + cc] = 0.0;
+  }
+}
+
+// every step in one launch of one workgroup.  The phases hand their results on through global memory: a workgroup
+// barrier orders them (all wavefronts of a workgroup share the compute unit's L1)
+__global__ __launch_bounds__(SI_THREADS) void selinv_fused_kernel(SiArgs a, int n_panels, const int* __restrict__ ok) {
+  if (!*ok) return;
+  const int wave = threadIdx.x >> 6;
+  for (int pi = n_panels - 1; pi >= 0; pi--) {
+    const SiStep s = si_step(a, pi);
+    si_phase_g(a, s, wave, SI_WAVES);
+    __syncthreads();
+    si_phase_t(a, s, wave, SI_WAVES);
+    __syncthreads();
+    si_phase_kk(a, s);
+    __syncthreads();
+  }
+}
+
+// panel by panel: phase 0 = G, 1 = T (grids over the tiles), 2 = KK (one workgroup)
+__global__ __launch_bounds__(SI_THREADS) void selinv_step_kernel(SiArgs a, int pi, int phase, const int* __restrict__ ok) {
+  if (!*ok) return;
+  const SiStep s = si_step(a, pi);
+  const int unit = blockIdx.x * SI_WAVES + (threadIdx.x >> 6), n_units = gridDim.x * SI_WAVES;
+  if (phase == 0)
+    si_phase_g(a, s, unit, n_units);
+  else if (phase == 1)
+    si_phase_t(a, s, unit, n_units);
+  else
+    si_phase_kk(a, s);
+}
+
+int vsl_chol_selinv_band_dev(vsl_ctx* ctx, double* S, double* Z, int n, int ld, int bw, int* ok_dev) {
+  if (n <= 0 || bw < 0 || ld != bw + CH_NB) return vsl_fail(ctx, VSL_ERR_INVALID, "selected inversion: %d unknowns, half bandwidth %d, leading dimension %d", n, bw, ld);
+  const SelinvPlan p = chol_selinv_plan(n, bw, ctx->chol_no_fused);
+  void* ws = nullptr;
+  int rc = vsl_ctx_dscratch(ctx, sizeof(double) * p.scratch_doubles, &ws);
+  if (rc) return rc;
+  double* Linv = (double*)ws + p.Linv;
+  if ((rc = chol_factor_panels(ctx, S, n, ld, bw, ok_dev, Linv))) return rc;
+  VSL_HIP(ctx, hipMemsetAsync(Z - ld, 0, sizeof(double) * p.z_elems, ctx->stream));
+  const SiArgs a = {S, Z, Linv, (double*)ws + p.G, n, ld, bw};
+  if (p.fused) {
+    hipLaunchKernelGGL(selinv_fused_kernel, dim3(1), dim3(SI_THREADS), 0, ctx->stream, a, p.n_panels, ok_dev);
+  } else {
+    for (int pi = p.n_panels - 1; pi >= 0; pi--) {
+      const int k = pi * CH_NB, nb = std::min(CH_NB, n - k), m = std::min(n - k - nb, bw);
+      const int tiles = 2 * ((m + 15) / 16), grid = (tiles + SI_WAVES - 1) / SI_WAVES;
+      if (m > 0) {
+        hipLaunchKernelGGL(selinv_step_kernel, dim3(grid), dim3(SI_THREADS), 0, ctx->stream, a, pi, 0, ok_dev);
+        hipLaunchKernelGGL(selinv_step_kernel, dim3(grid), dim3(SI_THREADS), 0, ctx->stream, a, pi, 1, ok_dev);
+      }
+      hipLaunchKernelGGL(selinv_step_kernel, dim3(1), dim3(SI_THREADS), 0, ctx->stream, a, pi, 2, ok_dev);
+    }
+  }
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+// Test / diagnostic entry point (include/vslam_hip.h): S from the host into band storage -- a cyclic band folded into a
+// linear one first (chol_fold_plan) --, the band of the inverse back into a dense n x n array; or the full inverse by
+// the dense factor and one solve per unit column where the band is the whole matrix.
+extern "C" int vsl_spd_inverse_band(vsl_ctx* ctx, const double* S, int n, int half_bandwidth, int cyclic, double* Z) {
+  if (!ctx || n < 0 || (n > 0 && (!S || !Z))) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_spd_inverse_band: bad argument");
+  if (n == 0) return VSL_OK;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  const int bw_in = half_bandwidth;
+  FoldPlan fold;
+  bool band = chol_band_declared(n, bw_in);
+  if (band && cyclic) {
+    fold = chol_fold_plan(n, bw_in);
+    band = fold.band;
+  }
+  const bool ring = band && cyclic;
+  const int bw = !band ? n : (ring ? fold.bw : bw_in);
+  const int bws = bw + CH_NB;
+  const int nblk = (n + 15) / 16;
+  const size_t s_elems = band ? chol_selinv_plan(n, bw, false).z_elems : (size_t)n * n;
+  const size_t z_elems = band ? s_elems : (size_t)nblk * n * 16;
+  const size_t linv_elems = band ? 0 : (size_t)((n + CH_NB - 1) / CH_NB) * CH_NB * CH_NB;
+  // one allocation: S | Z (band) or X (dense) | Linv (dense) | unit columns (dense) | ok
+  double* dev = nullptr;
+  const size_t bytes = sizeof(double) * (s_elems + z_elems + linv_elems) + sizeof(int) * ((size_t)nblk * 16 + 16);
+  VSL_HIP(ctx, hipMalloc((void**)&dev, bytes));
+  double *dS = dev, *dZ = dev + s_elems, *dLinv = dZ + z_elems;
+  int* dcol = (int*)(dLinv + linv_elems);
+  int* dok = dcol + (size_t)nblk * 16;
+  std::vector<double> st, zs(z_elems);
+  std::vector<int> col;
+  int rc = VSL_OK, ok = 0;
+  hipError_t e = hipSuccess;
+  auto ring_of = [&](int i) { return ring ? fold.ring[i] : i; };
+  if (band) {
+    // entry (i, c) of the (folded) matrix, i - c <= bw, at storage[i * (bws + 1) + (c - i + bws)]; a folded pair that
+    // is further apart than half_bandwidth around the ring is not part of the declared band: it stays zero
+    st.assign(s_elems, 0.0);
+    for (int i = 0; i < n; i++)
+      for (int c = std::max(0, i - bw); c <= i; c++) {
+        const int p = ring_of(i), q = ring_of(c), d = std::abs(p - q);
+        if (ring && std::min(d, n - d) > bw_in) continue;
+        st[(size_t)i * (bws + 1) + (c - i + bws)] = S[(size_t)std::max(p, q) * n + std::min(p, q)];
+      }
+    e = hipMemcpyAsync(dS, st.data(), sizeof(double) * s_elems, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) rc = vsl_chol_selinv_band_dev(ctx, dS + bws, dZ + bws, n, bws, bw, dok);
+  } else {
+    col.assign((size_t)nblk * 16, -1);
+    for (int j = 0; j < n; j++) col[j] = j;
+    e = hipMemcpyAsync(dS, S, sizeof(double) * s_elems, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dcol, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) rc = vsl_chol_factor_dev(ctx, dS, n, dok, dLinv);
+    if (e == hipSuccess && rc == VSL_OK) rc = vsl_cov_unit_columns_dev(ctx, n, dS, dLinv, nullptr, dcol, nblk, dZ, dok);
+  }
+  if (e == hipSuccess && rc == VSL_OK) {
+    e = hipMemcpyAsync(&ok, dok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(zs.data(), dZ, sizeof(double) * z_elems, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // also on an error: queued work uses the block freed below
+  if (e == hipSuccess) e = e2;
+  (void)hipFree(dev);
+  if (e != hipSuccess) return vsl_fail(ctx, VSL_ERR_HIP, "vsl_spd_inverse_band: %s", hipGetErrorString(e));
+  if (rc != VSL_OK) return rc;
+  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_spd_inverse_band: matrix is not positive definite");
+  std::fill(Z, Z + (size_t)n * n, 0.0);
+  if (band) {
+    for (int i = 0; i < n; i++)
+      for (int c = std::max(0, i - bw); c <= i; c++) {
+        const int p = ring_of(i), q = ring_of(c), d = std::abs(p - q);
+        if (ring && std::min(d, n - d) > bw_in) continue;
+        Z[(size_t)p * n + q] = Z[(size_t)q * n + p] = zs[(size_t)i * (bws + 1) + (c - i + bws)];
+      }
+  } else {
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j <= i; j++) Z[(size_t)i * n + j] = Z[(size_t)j * n + i] = zs[vsl_cov_x_at(n, i, j)];
+  }
+  return VSL_OK;
+}

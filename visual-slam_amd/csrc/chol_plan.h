@@ -5,6 +5,8 @@
 //   chol_ring_available   may a caller lay a cyclic band out for the ring solver at all
 //   chol_two_ended_plan   chunks, separator and scratch of the two-ended form
 //   bcr_plan_build        block layout, level lists, product targets, scratch and device block of a reduction
+//   chol_fold_plan        a cyclic band folded into a linear one (selected inversion: the ring is never inverted as such)
+//   chol_selinv_plan      launches and scratch of the selected inversion
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -119,6 +121,58 @@ inline TwoEndedPlan chol_two_ended_plan(int n, int bw) {
   t.Am_store = t.dinvm + sepn;
   t.doubles = t.Am_store + t.mid_elems + 64;
   return t;
+}
+
+// ------------------------------------------------------------------------------------------------ selected inversion
+// The band of the inverse (chol.hip, "SELECTED INVERSION") exists for LINEAR bands only.  A cyclic band is FOLDED into a
+// linear one instead of being inverted on the ring solver's reduction: ring position p goes to 2 p on the way out
+// (p < ceil(n / 2)) and to 2 (n - 1 - p) + 1 on the way back, so the two halves of the ring interleave and two positions
+// at cyclic distance d land at most 2 d apart.  A diagonal block of the inverse does not move under the relabelling.
+inline int chol_fold_pos(int n, int p) { return p < (n + 1) / 2 ? 2 * p : 2 * (n - 1 - p) + 1; }
+
+struct FoldPlan {
+  int n = 0;
+  int bw = 0;       // linear half bandwidth of the folded matrix: min(2 * cyclic half bandwidth, n - 1)
+  bool band = false;  // the folded band is narrower than the matrix (chol_band_declared): else the caller inverts densely
+  std::vector<int> pos;   // ring position -> folded position
+  std::vector<int> ring;  // folded position -> ring position
+};
+
+inline FoldPlan chol_fold_plan(int n, int cyclic_bw) {
+  FoldPlan f;
+  f.n = n;
+  f.bw = std::max(0, std::min(2 * cyclic_bw, n - 1));
+  f.band = chol_band_declared(n, 2 * cyclic_bw);
+  f.pos.resize(n);
+  f.ring.resize(n);
+  for (int p = 0; p < n; p++) {
+    f.pos[p] = chol_fold_pos(n, p);
+    f.ring[f.pos[p]] = p;
+  }
+  return f;
+}
+
+// How the recurrence of the selected inversion is launched: bands the single-workgroup kernels take run all panel steps
+// in ONE launch; wider ones go panel by panel (three launches per step, the products spread over several workgroups).
+// scratch_doubles: the inverted diagonal blocks, then G = L_WK L_KK^-1 of the current step (window rows x VSL_CHOL_NB).
+struct SelinvPlan {
+  int n_panels = 0;
+  bool fused = false;
+  int window = 0;  // most rows below a panel that a step reaches: min(bw, n - VSL_CHOL_NB), at least 0
+  size_t Linv = 0, G = 0, scratch_doubles = 0;
+  size_t z_elems = 0;  // doubles of a band array of this system: n rows of bw + VSL_CHOL_NB + 1 slots, plus 64
+};
+
+inline SelinvPlan chol_selinv_plan(int n, int bw, bool no_fused) {
+  SelinvPlan s;
+  s.n_panels = (n + VSL_CHOL_NB - 1) / VSL_CHOL_NB;
+  s.fused = !no_fused && bw <= CBF_MAXBW;
+  s.window = std::max(0, std::min(bw, n - VSL_CHOL_NB));
+  s.Linv = 0;
+  s.G = (size_t)s.n_panels * VSL_CHOL_NB * VSL_CHOL_NB;
+  s.scratch_doubles = s.G + (size_t)(s.window + 16) * VSL_CHOL_NB + 16;
+  s.z_elems = (size_t)n * (bw + VSL_CHOL_NB + 1) + 64;
+  return s;
 }
 
 // ------------------------------------------------------------------------------------------------ cyclic reduction

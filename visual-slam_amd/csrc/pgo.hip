@@ -459,6 +459,9 @@ struct PgoState {
   int ld = 0, bw = 0, cyclic = 0;
   size_t h_elems = 0;
   bool force_dense = false;
+  bool linear_only = false;  // vsl_pgo_covariance on a folded ring: the relabelled graph is a linear band, never a ring again
+  size_t extra_bytes = 0;    // the caller's share of the arena (vsl_pgo_covariance: factor scratch, columns, blocks)
+  char* extra = nullptr;
   // ONE device allocation per solve (dev_arena.h): 23 hipMalloc / hipFree pairs were ~1 ms of a 3 ms solve
   DevArena arena;
   double *poses = nullptr, *cand = nullptr, *meas = nullptr, *r = nullptr, *Ja = nullptr, *Jb = nullptr, *cost = nullptr;
@@ -467,14 +470,14 @@ struct PgoState {
   int *free_idx = nullptr, *edge_a = nullptr, *edge_b = nullptr, *inc_off = nullptr, *inc = nullptr, *flag = nullptr;
 };
 
-int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
+// THE storage decision of a graph (host only): dense, linear band or cyclic band -- st.ld / bw / cyclic / h_elems from
+// st.n = 6 nf unknowns and the edges' distances in free indices.  pgo_setup and vsl_pgo_covariance ask it.
+void pgo_storage(vsl_ctx* ctx, const vsl_pgo_problem* p, const std::vector<int>& free_idx, int nf, PgoState& st) {
   st.N = p->n_nodes;
   st.E = p->n_edges;
-  std::vector<int> free_idx(st.N, -1);
-  int nf = 0;
-  for (int i = 0; i < st.N; i++)
-    if (!p->node_fixed[i]) free_idx[i] = nf++;
   st.n = 6 * nf;
+  st.cyclic = 0;
+  st.bw = 0;
   {
     int lin = 0, cyc = 0;
     for (int e = 0; e < st.E; e++) {
@@ -490,7 +493,7 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
     st.ld = 0;
     st.h_elems = (size_t)st.n * st.n;
     if (!st.force_dense && !env_dense && !ctx->ba_force_dense && st.n > 128) {
-      if (2 * bw_cyc < bw_lin && chol_ring_available(st.n, bw_cyc, CholSwitches{ctx->chol_no_fused, ctx->chol_no_bcr, ctx->chol_one_ended}, &Bc, &nc)) {
+      if (!st.linear_only && 2 * bw_cyc < bw_lin && chol_ring_available(st.n, bw_cyc, CholSwitches{ctx->chol_no_fused, ctx->chol_no_bcr, ctx->chol_one_ended}, &Bc, &nc)) {
         st.cyclic = 1;
         st.bw = bw_cyc;
       } else if ((size_t)(bw_lin + 33) * 2 < (size_t)st.n) {
@@ -505,8 +508,23 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
       }
     }
   }
+}
+
+std::vector<int> pgo_free_index(const vsl_pgo_problem* p, int* nf_out) {
+  std::vector<int> free_idx(p->n_nodes, -1);
+  int nf = 0;
+  for (int i = 0; i < p->n_nodes; i++)
+    if (!p->node_fixed[i]) free_idx[i] = nf++;
+  *nf_out = nf;
+  return free_idx;
+}
+
+int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
+  int nf = 0;
+  const std::vector<int> free_idx = pgo_free_index(p, &nf);
+  pgo_storage(ctx, p, free_idx, nf, st);
   const size_t N = st.N, E = st.E, n = st.n;
-  ArenaPlan plan(23);
+  ArenaPlan plan(24);
   plan.add(st.poses, 7 * N);
   plan.add(st.cand, 7 * N);
   plan.add(st.free_idx, N);
@@ -530,6 +548,7 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
   plan.add(st.part2, std::max(std::max(n, N), E));
   plan.add(st.scalars, 8);
   plan.add(st.flag, 2);
+  plan.add(st.extra, st.extra_bytes);
   if (st.arena.acquire(ctx, ArenaPolicy::OWNED, plan) != hipSuccess)
     return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_pose_graph_optimize: device allocation of %zu bytes failed", plan.total());
   hipStream_t s = ctx->stream;
@@ -769,5 +788,214 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
     fprintf(stderr, "vsl PGO: iterations %d, initial cost %.6e, final cost %.6e, termination %d\n", sum.iterations, sum.initial_cost,
             sum.final_cost, sum.termination);
   if (summary) *summary = sum;
+  return VSL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// vsl_pgo_covariance: the 6 x 6 diagonal blocks of H^-1, H = J^T J of one linearisation at the poses handed in (unit
+// scale, no damping: what vsl_pgo_linearize returns).  Three routes, chosen by pgo_storage as for the solve:
+//   0 dense        vsl_chol_factor_dev, then one solve per queried unit column (ba_cov.hip's kernel) -- O(n^2) per column
+//   1 linear band  vsl_chol_selinv_band_dev (chol.hip "SELECTED INVERSION"): the whole band of H^-1 in O(n bw^2); the
+//                  diagonal blocks lie inside it (bw >= 5)
+//   2 ring         the FREE nodes are relabelled by the fold of chol_plan.h on the host -- free index f becomes
+//                  chol_fold_pos(nf, f), the edges follow, the edge ORDER stays -- so that the ring is a linear band of at
+//                  most twice the node distance; pgo_build_kernel builds that band as for any graph, then route 1.  A
+//                  diagonal block of the inverse does not move under a relabelling of the nodes.
+// "Not positive definite" is the rule of ba_cov.hip on every route: a pivot L_ii^2 <= 2^-36 H_ii, diag H taken before
+// the factorisation.  A block depends on H alone, never on what else is queried; the band routes read the lower
+// triangle of a block and mirror it, the dense route averages the two mirror entries: exactly symmetric either way.
+namespace {
+#define PGC_PIVOT_TOL 1.4551915228366852e-11  // 2^-36
+
+// H: the storage as pgo_build_kernel filled it (ld = 0: dense n x n; else rows of ld + 1 slots, the diagonal last)
+__global__ void pgo_cov_diag_kernel(int n, const double* __restrict__ H, int ld, double* __restrict__ d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[i] = ld > 0 ? H[(size_t)i * (ld + 1) + ld] : H[(size_t)i * n + i];
+}
+
+// band routes: the pivot test on the factor left in the band storage (every failing thread stores the same 0)
+__global__ void pgo_cov_pivot_kernel(int n, const double* __restrict__ L, int ld, const double* __restrict__ d, int* __restrict__ ok) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double l = L[(size_t)i * (ld + 1) + ld], p = l * l;
+  if (!(p > PGC_PIVOT_TOL * d[i]) || !isfinite(p)) *ok = 0;
+}
+
+// block q = rows / columns 6 q_free[q] .. + 5 of the band array Z (storage base), lower triangle mirrored
+__global__ void pgo_cov_blocks_band_kernel(int nQ, const int* __restrict__ q_free, const double* __restrict__ Z, int ld,
+                                           const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 36 * nQ || !*ok) return;
+  const int q = t / 36, a = (t % 36) / 6, b = t % 6;
+  const int i = 6 * q_free[q] + max(a, b), j = 6 * q_free[q] + min(a, b);
+  out[t] = Z[(size_t)i * (ld + 1) + ld - (i - j)];
+}
+
+// dense route: the diagonal block of X (right-hand sides 6 q .. 6 q + 5 belong to q_free[q]), symmetrised
+__global__ void pgo_cov_blocks_dense_kernel(int n, int nQ, const int* __restrict__ q_free, const double* __restrict__ X,
+                                            const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 36 * nQ || !*ok) return;
+  const int q = t / 36, a = (t % 36) / 6, b = t % 6, c = q_free[q];
+  out[t] = 0.5 * (X[vsl_cov_x_at(n, 6 * c + a, 6 * q + b)] + X[vsl_cov_x_at(n, 6 * c + b, 6 * q + a)]);
+}
+
+inline size_t pgc_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// the graph with its free nodes relabelled by the fold: new id chol_fold_pos(nf, f) for free index f, the fixed nodes
+// behind them in their old order
+struct PgoFolded {
+  std::vector<double> poses;
+  std::vector<uint8_t> fixed;
+  std::vector<int32_t> ea, eb;
+  vsl_pgo_problem prob;
+};
+void pgo_fold_problem(const vsl_pgo_problem* p, const std::vector<int>& free_idx, int nf, PgoFolded& F) {
+  const int N = p->n_nodes, E = p->n_edges;
+  std::vector<int> new_of(N);
+  int next_fixed = nf;
+  for (int i = 0; i < N; i++) new_of[i] = free_idx[i] >= 0 ? chol_fold_pos(nf, free_idx[i]) : next_fixed++;
+  F.poses.resize(7 * (size_t)N);
+  F.fixed.resize(N);
+  for (int i = 0; i < N; i++) {
+    memcpy(&F.poses[7 * (size_t)new_of[i]], p->poses + 7 * (size_t)i, 7 * sizeof(double));
+    F.fixed[new_of[i]] = p->node_fixed[i];
+  }
+  F.ea.resize(E);
+  F.eb.resize(E);
+  for (int e = 0; e < E; e++) {
+    F.ea[e] = new_of[p->edge_a[e]];
+    F.eb[e] = new_of[p->edge_b[e]];
+  }
+  F.prob = *p;
+  F.prob.poses = F.poses.data();
+  F.prob.node_fixed = F.fixed.data();
+  F.prob.edge_a = F.ea.data();
+  F.prob.edge_b = F.eb.data();
+}
+
+// q_free: the unique queried nodes as free indices of `prob` (the folded graph on route 2), ascending.  q_free, col_unk
+// and blocks are read / written by copies on the stream: the caller keeps them until it has synchronised.
+int pgo_cov_run(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, bool linear_only,
+                const std::vector<int>& q_free, std::vector<int>& col_unk, std::vector<double>& blocks, int* route) {
+  const int nQ = (int)q_free.size();
+  int nf = 0;
+  for (int i = 0; i < prob->n_nodes; i++) nf += !prob->node_fixed[i];
+  const int n = 6 * nf, m = 6 * nQ, nblk = (m + 15) / 16;
+  PgoState st;
+  st.linear_only = linear_only;
+  {
+    // the decision is needed before the arena is sized: the dense route keeps its columns there
+    PgoState probe;
+    probe.linear_only = linear_only;
+    int nf2 = 0;
+    pgo_storage(ctx, prob, pgo_free_index(prob, &nf2), nf, probe);
+    const bool dense = probe.ld == 0;
+    size_t at = 0;
+    at += pgc_pad(sizeof(double) * (size_t)n);                                                                   // diag H
+    at += pgc_pad(sizeof(int) * (size_t)nQ);                                                                     // q_free
+    at += pgc_pad(sizeof(double) * 36 * (size_t)nQ);                                                             // blocks
+    if (dense) {
+      at += pgc_pad(sizeof(double) * (size_t)((n + VSL_CHOL_NB - 1) / VSL_CHOL_NB) * VSL_CHOL_NB * VSL_CHOL_NB);  // Linv
+      at += pgc_pad(sizeof(int) * (size_t)nblk * 16);                                                            // unit columns
+      at += pgc_pad(sizeof(double) * (size_t)nblk * n * 16);                                                     // X
+    }
+    st.extra_bytes = at;
+  }
+  int rc;
+  if ((rc = pgo_setup(ctx, prob, st))) return rc;
+  hipStream_t s = ctx->stream;
+  const bool dense = st.ld == 0;
+  *route = dense ? 0 : 1;
+  char* x = st.extra;
+  double* Hdiag = (double*)x;
+  x += pgc_pad(sizeof(double) * (size_t)n);
+  int* q_dev = (int*)x;
+  x += pgc_pad(sizeof(int) * (size_t)nQ);
+  double* out = (double*)x;
+  x += pgc_pad(sizeof(double) * 36 * (size_t)nQ);
+  // unit scale (the solver's Jacobi scale is not part of H), one linearisation at the poses as they are
+  VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)n, s));
+  hipLaunchKernelGGL(pgo_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.colsq, st.scale);
+  double cost = 0;
+  if ((rc = pgo_linearize(ctx, st, opt, false, &cost))) return rc;
+  VSL_HIP(ctx, hipMemcpyAsync(q_dev, q_free.data(), sizeof(int) * (size_t)nQ, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(pgo_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.H, st.ld, Hdiag);
+  VSL_CHECK_LAUNCH(ctx);
+  if (dense) {
+    double* Linv = (double*)x;
+    x += pgc_pad(sizeof(double) * (size_t)((n + VSL_CHOL_NB - 1) / VSL_CHOL_NB) * VSL_CHOL_NB * VSL_CHOL_NB);
+    int* col_dev = (int*)x;
+    x += pgc_pad(sizeof(int) * (size_t)nblk * 16);
+    double* X = (double*)x;
+    col_unk.assign((size_t)nblk * 16, -1);
+    for (int j = 0; j < m; j++) col_unk[j] = 6 * q_free[j / 6] + j % 6;
+    VSL_HIP(ctx, hipMemcpyAsync(col_dev, col_unk.data(), sizeof(int) * col_unk.size(), hipMemcpyHostToDevice, s));
+    if ((rc = vsl_chol_factor_dev(ctx, st.H, n, st.flag, Linv))) return rc;
+    if ((rc = vsl_cov_unit_columns_dev(ctx, n, st.H, Linv, Hdiag, col_dev, nblk, X, st.flag))) return rc;
+    hipLaunchKernelGGL(pgo_cov_blocks_dense_kernel, dim3((36 * nQ + 255) / 256), dim3(256), 0, s, n, nQ, q_dev, X, st.flag, out);
+  } else {
+    // st.A: the second band array of the solve, here the band of the inverse
+    if ((rc = vsl_chol_selinv_band_dev(ctx, st.H + st.ld, st.A + st.ld, n, st.ld, st.bw, st.flag))) return rc;
+    hipLaunchKernelGGL(pgo_cov_pivot_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.H, st.ld, Hdiag, st.flag);
+    hipLaunchKernelGGL(pgo_cov_blocks_band_kernel, dim3((36 * nQ + 255) / 256), dim3(256), 0, s, nQ, q_dev, st.A, st.ld, st.flag, out);
+  }
+  VSL_CHECK_LAUNCH(ctx);
+  int ok = 0;
+  blocks.assign(36 * (size_t)nQ, 0.0);
+  VSL_HIP(ctx, hipMemcpyAsync(blocks.data(), out, sizeof(double) * blocks.size(), hipMemcpyDeviceToHost, s));
+  VSL_HIP(ctx, hipMemcpyAsync(&ok, st.flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  VSL_HIP(ctx, hipStreamSynchronize(s));
+  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_pgo_covariance: the normal equations are not positive definite (no fixed node, or a free node without an edge)");
+  return VSL_OK;
+}
+}  // namespace
+
+extern "C" int vsl_pgo_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* nodes, int n_q,
+                                  double* cov, int* storage) {
+  int rc = pgo_validate(ctx, prob);
+  if (rc) return rc;
+  if (!opt || n_q < 0 || (n_q > 0 && (!nodes || !cov)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_covariance: null argument or negative count");
+  for (int q = 0; q < n_q; q++) {
+    if (nodes[q] < 0 || nodes[q] >= prob->n_nodes) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_covariance: node %d out of range", nodes[q]);
+    if (prob->node_fixed[nodes[q]]) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_covariance: node %d is fixed", nodes[q]);
+  }
+  // the route of this graph: the solve's own decision, on the host
+  int nf = 0;
+  const std::vector<int> free_idx = pgo_free_index(prob, &nf);
+  int route;
+  {
+    PgoState probe;
+    pgo_storage(ctx, prob, free_idx, nf, probe);
+    route = probe.ld > 0 ? (probe.cyclic ? 2 : 1) : 0;
+  }
+  if (storage) *storage = route;
+  if (n_q == 0) return VSL_OK;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  // the unique queried nodes, ascending in the free index the device will see
+  std::vector<int> key(n_q), q_free, slot(n_q);
+  for (int q = 0; q < n_q; q++) key[q] = route == 2 ? chol_fold_pos(nf, free_idx[nodes[q]]) : free_idx[nodes[q]];
+  q_free = key;
+  std::sort(q_free.begin(), q_free.end());
+  q_free.erase(std::unique(q_free.begin(), q_free.end()), q_free.end());
+  for (int q = 0; q < n_q; q++) slot[q] = (int)(std::lower_bound(q_free.begin(), q_free.end(), key[q]) - q_free.begin());
+  std::vector<double> blocks;
+  std::vector<int> col_unk;
+  int ran = 0;
+  if (route == 2) {
+    PgoFolded F;
+    pgo_fold_problem(prob, free_idx, nf, F);
+    rc = pgo_cov_run(ctx, &F.prob, opt, true, q_free, col_unk, blocks, &ran);
+    if (rc == VSL_OK && ran == 1) ran = 2;
+  } else {
+    rc = pgo_cov_run(ctx, prob, opt, false, q_free, col_unk, blocks, &ran);
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(ctx->stream);  // queued copies read host buffers that end here
+    return rc;
+  }
+  if (storage) *storage = ran;
+  for (int q = 0; q < n_q; q++) memcpy(cov + 36 * (size_t)q, blocks.data() + 36 * (size_t)slot[q], 36 * sizeof(double));
   return VSL_OK;
 }

@@ -213,6 +213,20 @@ int vsl_chol_solve_band_dev(vsl_ctx* ctx, double* S, double* b, int n, int ld, i
 // the dense factorisation alone: S <- L in place, Linv <- the inverted VSL_CHOL_NB x VSL_CHOL_NB diagonal blocks of L
 // (one per panel, identity-padded; device memory of the caller), *ok_dev = 0 if S is not SPD
 int vsl_chol_factor_dev(vsl_ctx* ctx, double* S, int n, int* ok_dev, double* Linv);
+// SELECTED INVERSION (chol.hip): the band of S^-1.  S and Z are band arrays of the same layout (S = storage + bws,
+// Z = its own storage + bws, ld = bws = bw + VSL_CHOL_NB, chol_selinv_plan(n, bw).z_elems doubles each).  S <- L in
+// place; Z receives every entry (i, j), 0 <= i - j <= bw, of S^-1 and zeros in all other slots.  *ok_dev = 0 (and Z
+// undefined) if S is not positive definite by the factorisation's own pivot test.  Enqueued on the context's stream.
+int vsl_chol_selinv_band_dev(vsl_ctx* ctx, double* S, double* Z, int n, int ld, int bw, int* ok_dev);
+// Columns of the inverse of a DENSE factor (ba_cov.hip: the solve behind vsl_ba_covariance): L L^T X = E for the unit
+// columns col_unk[0 .. 16 nblk) (device; -1: an empty column), sixteen per workgroup.  X: nblk blocks of n x 16 doubles,
+// entry (row i, column j) at vsl_cov_x_at(n, i, j).  L, Linv: what vsl_chol_factor_dev left.  Sdiag (nullable): diag S
+// before the factorisation -- a pivot L_ii^2 <= 2^-36 Sdiag_i clears *ok_dev and nothing is written.
+int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double* Linv, const double* Sdiag, const int* col_unk,
+                             int nblk, double* X, int* ok_dev);
+__host__ __device__ inline size_t vsl_cov_x_at(int n, int i, int col) {
+  return (size_t)(col / 16) * n * 16 + (size_t)i * 16 + (col % 16);
+}
 
 // scratch store of the host-buffer API
 int vsl_ctx_scratch_frames(vsl_ctx* ctx, int w, int h, int feat, vsl_frames** out);
