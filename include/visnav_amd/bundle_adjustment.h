@@ -196,22 +196,26 @@ inline void bundle_adjustment(const Corners& feature_corners, const BundleAdjust
 // observation noise.  Returns the number of such landmarks; std::domain_error when the reduced camera system is singular
 // to working precision (VSL_ERR_NUMERIC: e.g. no fixed camera).
 using PoseCovariance = Eigen::Matrix<double, 6, 6>;
-inline int bundle_adjustment_covariance(const Corners& feature_corners, const BundleAdjustmentOptions& options,
-                                        const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
-                                        Landmarks& landmarks, const std::vector<FrameCamId>& query_cameras,
-                                        const std::vector<TrackId>& query_landmarks,
-                                        std::map<FrameCamId, PoseCovariance>& pose_cov_out,
-                                        std::unordered_map<TrackId, Eigen::Matrix3d>& landmark_cov_out) {
+namespace amd {
+// what the two covariance wrappers share: the flattening (kAllObs as in run_ba), the id -> index maps, the call, the
+// blocks.  kAllObs = false: vsl_ba_covariance on the window's inlier observations; true: vsl_global_ba_covariance on
+// all of them.  *storage_out (nullable): the route of the global call (0 dense, 1 linear band).
+template <bool kAllObs>
+inline int run_ba_covariance(const char* what, const Corners& feature_corners, bool use_huber, double huber_parameter,
+                             const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                             Landmarks& landmarks, const std::vector<FrameCamId>& query_cameras,
+                             const std::vector<TrackId>& query_landmarks, std::map<FrameCamId, PoseCovariance>& pose_cov_out,
+                             std::unordered_map<TrackId, Eigen::Matrix3d>& landmark_cov_out, int* storage_out) {
   pose_cov_out.clear();
   landmark_cov_out.clear();
   if (query_cameras.empty() && query_landmarks.empty()) return 0;
-  amd::BaFlat f;
-  if (!amd::flatten_ba<false>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f))
-    throw std::out_of_range("bundle_adjustment_covariance: the map has no observation");
+  BaFlat f;
+  if (!flatten_ba<kAllObs>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f))
+    throw std::out_of_range(std::string(what) + ": the map has no observation");
   std::vector<int32_t> cams, lms;
   for (const FrameCamId& id : query_cameras) {
     const auto it = std::lower_bound(f.cam_id.begin(), f.cam_id.end(), id);
-    if (it == f.cam_id.end() || !(*it == id)) throw std::out_of_range("bundle_adjustment_covariance: unknown camera");
+    if (it == f.cam_id.end() || !(*it == id)) throw std::out_of_range(std::string(what) + ": unknown camera");
     cams.push_back((int32_t)(it - f.cam_id.begin()));
   }
   if (!query_landmarks.empty()) {
@@ -220,17 +224,19 @@ inline int bundle_adjustment_covariance(const Corners& feature_corners, const Bu
     for (const TrackId id : query_landmarks) lms.push_back(index.at(id));
   }
   vsl_ba_options opt;
-  opt.use_huber = options.use_huber ? 1 : 0;
-  opt.huber_parameter = options.huber_parameter;
+  opt.use_huber = use_huber ? 1 : 0;
+  opt.huber_parameter = huber_parameter;
   opt.max_num_iterations = 0;
   opt.verbosity = 0;
   std::vector<double> cp(36 * cams.size()), cl(9 * lms.size());
   int n_degenerate = 0;
-  const int rc = vsl_ba_covariance(amd::ctx(), &f.prob, &opt, cams.data(), (int)cams.size(), cp.data(), lms.data(),
-                                   (int)lms.size(), cl.data(), &n_degenerate);
+  const int rc = kAllObs ? vsl_global_ba_covariance(ctx(), &f.prob, &opt, cams.data(), (int)cams.size(), cp.data(), lms.data(),
+                                                    (int)lms.size(), cl.data(), &n_degenerate, storage_out)
+                         : vsl_ba_covariance(ctx(), &f.prob, &opt, cams.data(), (int)cams.size(), cp.data(), lms.data(),
+                                             (int)lms.size(), cl.data(), &n_degenerate);
   // a reduced camera system that is singular to working precision is a property of the map, not a failure of the call
-  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
-  amd::check(rc, "bundle_adjustment_covariance");
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(ctx()));
+  check(rc, what);
   for (size_t q = 0; q < cams.size(); q++) {
     PoseCovariance& m = pose_cov_out[query_cameras[q]];
     for (int i = 0; i < 6; i++)
@@ -243,6 +249,18 @@ inline int bundle_adjustment_covariance(const Corners& feature_corners, const Bu
   }
   return n_degenerate;
 }
+}  // namespace amd
+
+inline int bundle_adjustment_covariance(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                        const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                        Landmarks& landmarks, const std::vector<FrameCamId>& query_cameras,
+                                        const std::vector<TrackId>& query_landmarks,
+                                        std::map<FrameCamId, PoseCovariance>& pose_cov_out,
+                                        std::unordered_map<TrackId, Eigen::Matrix3d>& landmark_cov_out) {
+  return amd::run_ba_covariance<false>("bundle_adjustment_covariance", feature_corners, options.use_huber, options.huber_parameter,
+                                       fixed_cameras, calib_cam, cameras, landmarks, query_cameras, query_landmarks, pose_cov_out,
+                                       landmark_cov_out, nullptr);
+}
 
 // include/visnav/loop_closure_utils.h:672-748.  With rccl_world.h included first and VISNAV_AMD_WORLD > 1 (one process
 // per GPU, every rank calling this on the same map) the solve is partitioned over the ranks and all-reduced through
@@ -252,6 +270,23 @@ inline void global_bundle_adjustment(const Corners& feature_corners, const Globa
                                      Landmarks& landmarks) {
   amd::run_ba<true>(feature_corners, options.use_huber, options.huber_parameter, options.max_num_iterations,
                     options.verbosity_level, fixed_cameras, calib_cam, cameras, landmarks);
+}
+
+// Marginal covariances of the map that global_bundle_adjustment works on (vsl_global_ba_covariance): the contract of
+// bundle_adjustment_covariance above, on ALL observations of the landmarks (the flattening of global_bundle_adjustment),
+// with the reduced camera system of a large map kept in band storage.  storage_out (nullable): 0 = the dense route of
+// bundle_adjustment_covariance, 1 = linear band.  Single GPU.
+inline int global_bundle_adjustment_covariance(const Corners& feature_corners, const GlobalBundleAdjustmentOptions& options,
+                                               const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam,
+                                               Cameras& cameras, Landmarks& landmarks,
+                                               const std::vector<FrameCamId>& query_cameras,
+                                               const std::vector<TrackId>& query_landmarks,
+                                               std::map<FrameCamId, PoseCovariance>& pose_cov_out,
+                                               std::unordered_map<TrackId, Eigen::Matrix3d>& landmark_cov_out,
+                                               int* storage_out = nullptr) {
+  return amd::run_ba_covariance<true>("global_bundle_adjustment_covariance", feature_corners, options.use_huber,
+                                      options.huber_parameter, fixed_cameras, calib_cam, cameras, landmarks, query_cameras,
+                                      query_landmarks, pose_cov_out, landmark_cov_out, storage_out);
 }
 
 }  // namespace visnav

@@ -430,14 +430,32 @@ int vsl_ba_residuals_jacobians(vsl_ctx* ctx, const vsl_ba_problem* prob, double*
  * is counted in *n_degenerate (nullable); the call still returns VSL_OK.  An empty problem (n_lms = 0 or n_obs = 0) is
  * VSL_ERR_INVALID.  Every block is exactly symmetric; the result does not depend on what else is queried (a subset
  * query returns the bits of the same blocks of a full query) and is the same from run to run.
- * DENSE ONLY: S is formed, factorised and inverted column by column in dense storage whatever its size (the dense path
- * of vsl_spd_solve).  The band primitive now exists (vsl_spd_inverse_band, used by vsl_pgo_covariance); this call does
- * not use it yet, because S would have to be built in band form through the session set-up.  A queried landmark may
+ * DENSE: S is formed, factorised and inverted column by column in dense storage whatever its size (the dense path of
+ * vsl_spd_solve): the call for a local window.  For the map of a global bundle adjustment use
+ * vsl_global_ba_covariance below, which keeps S and the part of S^-1 it needs in band storage.  A queried landmark may
  * have at most 256 observations (VSL_ERR_INVALID beyond). */
 int vsl_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
                       const int32_t* cams, int n_cam_q, double* cov_pose,   /* [36*n_cam_q] row-major */
                       const int32_t* lms,  int n_lm_q,  double* cov_point,  /* [9*n_lm_q]   row-major */
                       int* n_degenerate);
+
+/* The same covariances for a large map (the problem of vsl_global_bundle_adjust): definition, argument rules, error
+ * codes, the degenerate-landmark rule, the positive-definiteness rule, exact symmetry, run-to-run bit equality and "a
+ * subset query returns the bits of a full query" are those of vsl_ba_covariance, word for word.  What differs is the
+ * storage of the reduced camera system S, reported in *storage (nullable):
+ *   0  dense: exactly the chain of vsl_ba_covariance, and its bits.  Taken at <= 128 unknowns, under the
+ *      "ba_force_dense" diagnostic, and where the band would hold half of the matrix or more;
+ *   1  linear band: the free cameras are ordered by reverse Cuthill-McKee on the covisibility graph (the order of
+ *      vsl_bundle_adjust's band route; the cyclic form is never taken), S is built in LAPACK-style lower band storage,
+ *      and the band of S^-1 comes from selected inversion (vsl_spd_inverse_band's recurrence) in O(n bw^2).  A pose
+ *      block is a diagonal block of that band; a landmark block needs [S^-1]_cc' only for cameras c, c' that observe
+ *      the landmark together, which are the structural non-zeros of S and hence inside the band: no solve per query.
+ * The two routes agree to rounding (the tolerance rule of the tests: 64 cond(H) 2^-52 max|Sigma|), not bit for bit.
+ * With both counts 0 the call returns VSL_OK, launches nothing and still reports the route of the problem. */
+int vsl_global_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
+                             const int32_t* cams, int n_cam_q, double* cov_pose,   /* [36*n_cam_q] row-major */
+                             const int32_t* lms,  int n_lm_q,  double* cov_point,  /* [9*n_lm_q]   row-major */
+                             int* n_degenerate, int* storage);
 
 /* ---- multi-GPU global bundle adjustment ----
  * visnav::global_bundle_adjustment (include/visnav/loop_closure_utils.h:672-748) over `world` ranks, one process per

@@ -542,6 +542,22 @@ class Context:
                                           cl.ctypes.data_as(f64p), C.byref(nd)))
         return cp, cl, nd.value
 
+    def global_ba_covariance(self, arr, cams=None, lms=None, use_huber=True, huber=1.0):
+        """ba_covariance for the map of a global bundle adjustment (vsl_global_ba_covariance): the same blocks, with the
+        reduced camera system of a large map in band storage.  Returns (cov_pose [n, 6, 6], cov_point [m, 3, 3],
+        n_degenerate, storage) with storage = 0 dense (the chain and the bits of ba_covariance) / 1 linear band."""
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        cams = np.flatnonzero(arr.cam_fixed == 0) if cams is None else cams
+        cams = np.ascontiguousarray(cams, np.int32).reshape(-1)
+        lms = np.ascontiguousarray([] if lms is None else lms, np.int32).reshape(-1)
+        cp, cl = np.zeros((len(cams), 6, 6)), np.zeros((len(lms), 3, 3))
+        nd, storage = C.c_int(0), C.c_int(-1)
+        self._ck(self.L.vsl_global_ba_covariance(self.h, C.byref(st), C.byref(o), cams.ctypes.data_as(i32p), len(cams),
+                                                 cp.ctypes.data_as(f64p), lms.ctypes.data_as(i32p), len(lms),
+                                                 cl.ctypes.data_as(f64p), C.byref(nd), C.byref(storage)))
+        return cp, cl, nd.value, storage.value
+
     def ba_residuals_jacobians(self, arr):
         st = self._ba_struct(arr)
         n = len(arr.obs_cam)

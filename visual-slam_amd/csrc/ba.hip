@@ -1289,11 +1289,35 @@ int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
   return VSL_OK;
 }
 
+// the layout switches of a caller: its use and the context's diagnostics
+static BaLayoutSwitches ba_layout_switches(vsl_ctx* ctx, const BaCaller& caller) {
+  static const bool env_no_cyclic = getenv("VSL_BA_NO_CYCLIC") != nullptr;
+  BaLayoutSwitches sw;
+  sw.allow_band = caller.use == BaUse::HOST_LOOP || caller.use == BaUse::SESSION || caller.use == BaUse::GLOBAL_COVARIANCE;
+  sw.force_dense = ctx->ba_force_dense;
+  sw.no_cyclic = ctx->ba_no_cyclic || env_no_cyclic || caller.use == BaUse::GLOBAL_COVARIANCE;
+  sw.schur_atomics = ctx->ba_schur_atomics;
+  sw.chol_no_bcr = ctx->chol_no_bcr;
+  sw.chol_no_fused = ctx->chol_no_fused;
+  return sw;
+}
+
+int ba_layout_of(vsl_ctx* ctx, const vsl_ba_problem* p, const BaCaller& caller, bool* banded) {
+  try {
+    const BaHostPlan hp = ba_host_plan(p, caller.graph_prob, ba_layout_switches(ctx, caller),
+                                       BaPlanLimits{SCH_CMAX, SCH_KMAX, caller.run_max_obs, caller.run_max_lms}, [](const char*) {});
+    *banded = hp.layout.banded;
+  } catch (const std::bad_alloc&) {
+    return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+  }
+  return VSL_OK;
+}
+
 int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaState& st, const BaCaller& caller) {
   BaTrace tr;
-  const bool allow_band = caller.use == BaUse::HOST_LOOP || caller.use == BaUse::SESSION;
   const ArenaPolicy arena_policy =
-      caller.use == BaUse::HOST_LOOP || caller.use == BaUse::COVARIANCE ? ArenaPolicy::BORROWED : ArenaPolicy::OWNED;
+      caller.use == BaUse::HOST_LOOP || caller.use == BaUse::COVARIANCE || caller.use == BaUse::GLOBAL_COVARIANCE ? ArenaPolicy::BORROWED
+                                                                                                                   : ArenaPolicy::OWNED;
   BaDims& D = st.D;
   D.C = p->n_cams;
   D.L = p->n_lms;
@@ -1303,18 +1327,16 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   D.use_huber = o ? o->use_huber : 1;
   D.huber = o ? o->huber_parameter : 1.0;
   // everything the host derives from the problem (ba_host_plan.h); the rest of this function is what needs the device
-  static const bool env_no_cyclic = getenv("VSL_BA_NO_CYCLIC") != nullptr;
-  BaLayoutSwitches sw;
-  sw.allow_band = allow_band;
-  sw.force_dense = ctx->ba_force_dense;
-  sw.no_cyclic = ctx->ba_no_cyclic || env_no_cyclic;
-  sw.schur_atomics = ctx->ba_schur_atomics;
-  sw.chol_no_bcr = ctx->chol_no_bcr;
-  sw.chol_no_fused = ctx->chol_no_fused;
+  const BaLayoutSwitches sw = ba_layout_switches(ctx, caller);
   BaHostPlan hp;
+  size_t extra_bytes = caller.extra_bytes;
   try {
     hp = ba_host_plan(p, caller.graph_prob, sw, BaPlanLimits{SCH_CMAX, SCH_KMAX, caller.run_max_obs, caller.run_max_lms},
                       [&](const char* what) { tr.lap(what); });
+    if (caller.plan_extra) {
+      const int rc = caller.plan_extra(caller.plan_extra_self, hp, &extra_bytes);
+      if (rc) return rc;
+    }
   } catch (const std::bad_alloc&) {
     return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
   }
@@ -1394,7 +1416,7 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
     plan.add(sb.H2, 36 * nfree); plan.add(sb.g_c2, n); plan.add(sb.diag_c2, n); plan.add(sb.diag_l2, 3 * L);
   }
   if (caller.use == BaUse::SESSION) plan.add(st.diagc_keep, std::max<size_t>(n, 1));
-  if (caller.extra_bytes) plan.add(st.extra, caller.extra_bytes);
+  if (extra_bytes) plan.add(st.extra, extra_bytes);
   VSL_HIP(ctx, st.arena.acquire(ctx, arena_policy, plan));
   st.flag = (int*)(st.scalars + 16);
   tr.lap("arena", plan.total());

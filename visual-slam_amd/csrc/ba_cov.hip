@@ -1,5 +1,6 @@
-// ba_cov.hip -- marginal covariances of poses and landmarks of a bundle-adjustment problem (vsl_ba_covariance): what
-// ceres::Covariance offers beside ceres::Solve (include/visnav/map_utils.h:405-411 calls only the latter).
+// ba_cov.hip -- marginal covariances of poses and landmarks of a bundle-adjustment problem (vsl_ba_covariance,
+// vsl_global_ba_covariance): what ceres::Covariance offers beside ceres::Solve (include/visnav/map_utils.h:405-411 calls
+// only the latter).
 //
 // Nothing is optimised: the problem is linearised once at the poses and points handed in, exactly as vsl_ba_linearize
 // documents it (Huber corrector on residual and Jacobian blocks, no Jacobi scaling, no damping).  With H = J^T J over
@@ -22,11 +23,19 @@
 // workgroup (an output of v_mfma_f64_16x16x4_f64 depends on its own row of A and column of B only), so a subset query
 // returns the bits of the same rows of a full query, and two calls return the same bits.
 //
-// DENSE ONLY.  S is formed and factorised in dense storage whatever its size (the dense path of vsl_spd_solve), so the
-// cost grows with (6 x free cameras)^2 x columns.  The band primitive now exists (chol.hip, "SELECTED INVERSION": what
-// vsl_pgo_covariance runs on); this path does not use it yet -- S of a large map would have to be built in the band and
-// cyclic-band forms of vsl_global_bundle_adjust through the session set-up.  A queried landmark may have at most
-// COV_KMAX observations (its W blocks are kept in LDS).
+// TWO ROUTES.  vsl_ba_covariance is the dense one, whatever the size: S is formed and factorised in dense storage (the
+// dense path of vsl_spd_solve), so its cost grows with (6 x free cameras)^2 x columns -- the call for a local window.
+// vsl_global_ba_covariance takes ba_reduced_layout's decision for the problem (linear band allowed, cyclic never):
+// dense -> the chain above, bit for bit; linear band -> the free cameras in reverse Cuthill-McKee order (ba_setup, as
+// for vsl_bundle_adjust), ba_schur into LAPACK-style band storage, and
+//   vsl_chol_selinv_band_dev (chol.hip "SELECTED INVERSION")   S <- L, Z <- the band of S^-1, O(n bw^2)
+//   cov_band_pivot_kernel                                       the pivot test below on the factor in the band
+//   cov_band_pose_kernel                                        diagonal blocks of Z, lower triangle mirrored
+//   ba_cov_landmark_band_kernel                                 the landmark scheme above, [S^-1]_cc' read from Z: cameras
+//                            that observe one landmark are adjacent in the covisibility graph, so the block is in the band
+// Z does not depend on the query, and a landmark's sum runs over its own observations in ascending band position: the
+// subset and run-to-run guarantees hold on this route as well.  A queried landmark may have at most COV_KMAX
+// observations (its W blocks are kept in LDS) on either route.
 // The solve kernel is also what vsl_spd_inverse_band and vsl_pgo_covariance use on their dense routes
 // (vsl_cov_unit_columns_dev below).
 //
@@ -42,6 +51,7 @@
 #include "vsl_common.h"
 #include "dev_arena.h"
 #include "ba_host_plan.h"
+#include "ba_cov_plan.h"
 #include "ba_device.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // ba_large.h: only bl_eval and bl_wave_sum are used here, not its kernels
@@ -49,8 +59,7 @@
 #pragma clang diagnostic pop
 #include "ba_state.h"
 
-#define COV_NB VSL_CHOL_NB  // panel width of the solve = the factorisation's (its inverted diagonal blocks are reused)
-#define COV_COLS 16         // right-hand sides of a workgroup: one matrix-instruction tile
+// (COV_NB, COV_COLS: ba_cov_plan.h)
 #define COV_THREADS 256
 #define COV_CHUNK 64        // rows (forward) / columns (backward) of L staged in LDS per step: one 16-row tile per wavefront
 #define COV_LP 34           // LDS row pitches (doubles): 2 r + k and 16 k + c fall on distinct banks within a half wavefront
@@ -70,9 +79,30 @@ __device__ __forceinline__ size_t cov_x_at(int n, int i, int col) {
   return (size_t)(col / COV_COLS) * n * COV_COLS + (size_t)i * COV_COLS + (col % COV_COLS);
 }
 
-__global__ void ba_cov_diag_kernel(int n, const double* __restrict__ S, double* __restrict__ d) {
+// S: the storage as ba_schur filled it (ld = 0: dense n x n; else band rows of ld + 1 slots, the diagonal last)
+__global__ void ba_cov_diag_kernel(int n, const double* __restrict__ S, int ld, double* __restrict__ d) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) d[i] = S[(size_t)i * n + i];
+  if (i < n) d[i] = ld > 0 ? S[(size_t)i * (ld + 1) + ld] : S[(size_t)i * n + i];
+}
+
+// band routes (here and vsl_pgo_covariance): the pivot test of the file header on the factor left in the band storage
+// (every failing thread stores the same 0)
+__global__ void cov_band_pivot_kernel(int n, const double* __restrict__ L, int ld, const double* __restrict__ d, int* __restrict__ ok) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double l = L[(size_t)i * (ld + 1) + ld], p = l * l;
+  if (!(p > COV_PIVOT_TOL * d[i]) || !isfinite(p)) *ok = 0;
+}
+
+// band routes: block q = rows / columns 6 q_free[q] .. + 5 of the band array Z (storage base) of the inverse.  Only
+// the lower triangle is stored: it is mirrored, so the block is exactly symmetric.
+__global__ void cov_band_pose_kernel(int nQ, const int* __restrict__ q_free, const double* __restrict__ Z, int ld,
+                                     const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 36 * nQ || !*ok) return;
+  const int q = t / 36, a = (t % 36) / 6, b = t % 6;
+  const int i = 6 * q_free[q] + max(a, b), j = 6 * q_free[q] + min(a, b);
+  out[t] = Z[(size_t)i * (ld + 1) + ld - (i - j)];
 }
 
 // L L^T X = E for the COV_COLS unit columns col_unk[COV_COLS * blockIdx.x ..] (-1: an empty column) of this workgroup,
@@ -213,13 +243,40 @@ __global__ void ba_cov_pose_kernel(int n, int nQ, const int* __restrict__ q_free
   out[t] = 0.5 * (X[cov_x_at(n, 6 * c + a, 6 * q + b)] + X[cov_x_at(n, 6 * c + b, 6 * q + a)]);
 }
 
+// Where the landmark kernel reads [S^-1]_{6 ci + r, 6 cj + b} (ci, cj: free indices of two cameras that observe the
+// same landmark).  block(ci, cj) is evaluated once per camera pair, at(h, r, b) once per entry.
+// Dense route: the unit columns X of the cameras of Q (right-hand sides 6 qpos[cj] .. + 5).
+struct CovDenseInverse {
+  int n;
+  const int* __restrict__ qpos;
+  const double* __restrict__ X;
+  struct Block { int row, col; };
+  __device__ __forceinline__ Block block(int ci, int cj) const { return Block{6 * ci, 6 * qpos[cj]}; }
+  __device__ __forceinline__ double at(const Block& h, int r, int b) const { return X[cov_x_at(n, h.row + r, h.col + b)]; }
+};
+// Band route: the band array Z of the inverse (Z = its ORIGIN, storage + ld; cov_band_at of ba_cov_plan.h).  Two free
+// cameras that observe one landmark are adjacent in the covisibility graph, so |ci - cj| <= half and every entry of
+// the block lies inside the band bw = 6 half + 5.  Only the lower triangle is stored: block (ci, cj) with ci < cj is the
+// transpose of block (cj, ci), and the diagonal block is mirrored -- either way entry (max, min).  Z is read in the
+// wavefront's own layout straight from the L2 (a few reads per entry: staging it in LDS would buy nothing).
+struct CovBandInverse {
+  int ld;
+  const double* __restrict__ Z;
+  struct Block { int row, col; };
+  __device__ __forceinline__ Block block(int ci, int cj) const { return Block{6 * ci, 6 * cj}; }
+  __device__ __forceinline__ double at(const Block& h, int r, int b) const {
+    const int i = h.row + r, j = h.col + b;
+    return Z[(size_t)max(i, j) * ld + min(i, j)];
+  }
+};
+
 // One wavefront per queried landmark u (its observations: u_start[u] .. u_start[u + 1] of o_cam / o_uv, ascending free
 // index, fixed cameras first).  sh: 27 doubles per observation (W = F^T E, then T = W^T Z).
-__global__ __launch_bounds__(64) void ba_cov_landmark_kernel(BlArgs a, int n, const int* __restrict__ u_lm,
-                                                             const int* __restrict__ u_start, const int* __restrict__ o_cam,
-                                                             const double* __restrict__ o_uv, const int* __restrict__ qpos,
-                                                             const double* __restrict__ X, const int* __restrict__ ok,
-                                                             double* __restrict__ out, int* __restrict__ degenerate) {
+template <class Inverse>
+__global__ __launch_bounds__(64) void ba_cov_landmark_kernel(BlArgs a, const int* __restrict__ u_lm, const int* __restrict__ u_start,
+                                                             const int* __restrict__ o_cam, const double* __restrict__ o_uv,
+                                                             Inverse inv, const int* __restrict__ ok, double* __restrict__ out,
+                                                             int* __restrict__ degenerate) {
   extern __shared__ double sh[];
   __shared__ double M[9];
   if (!*ok) return;
@@ -272,13 +329,13 @@ __global__ __launch_bounds__(64) void ba_cov_landmark_kernel(BlArgs a, int n, co
       for (int j = 0; j < K; j++) {
         const int cj = a.cam_free[o_cam[o0 + j]];
         if (cj < 0) continue;
-        const int col = 6 * qpos[cj];
+        const typename Inverse::Block h = inv.block(ci, cj);
         const double* Wj = W + 18 * j;
 #pragma unroll
         for (int r = 0; r < 6; r++)
 #pragma unroll
           for (int b = 0; b < 6; b++) {
-            const double s = X[cov_x_at(n, 6 * ci + r, col + b)];
+            const double s = inv.at(h, r, b);
 #pragma unroll
             for (int y = 0; y < 3; y++) Z[3 * r + y] += s * Wj[3 * b + y];
           }
@@ -317,127 +374,67 @@ __global__ __launch_bounds__(64) void ba_cov_landmark_kernel(BlArgs a, int n, co
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline size_t cov_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// (the host plan -- CovPlan, CovBuffers -- is ba_cov_plan.h)
 
-// What the host derives from the query: Q, the unique landmarks and their observation lists
-struct CovPlan {
-  int nfree = 0, nQ = 0, nu = 0, n_o = 0, kmax = 0;
-  std::vector<int> cam_free;          // camera -> free index or -1 (ascending camera id: vsl_ba_linearize's numbering)
-  std::vector<int> q_free, qpos;      // Q in ascending free index, and free index -> position in Q or -1
-  std::vector<int> cam_q2Q, lm_q2u;   // query entry -> position in Q / unique landmark
-  std::vector<int> u_lm, u_start, o_cam;
-  std::vector<double> o_uv;
+// One call of either entry point.  vsl_ba_covariance plans before the set-up (its S is dense, its free cameras are
+// numbered by ascending id); vsl_global_ba_covariance plans inside it (plan_extra below), once the layout of S and the
+// band order are known.
+struct CovCall {
+  vsl_ctx* ctx;
+  const char* name;
+  const vsl_ba_problem* prob;
+  const int32_t* cams;
+  int n_cam_q;
+  const int32_t* lms;
+  int n_lm_q;
+  bool global;
+  bool band = false;  // the route taken: S and the band of its inverse in linear band storage
+  CovPlan P;
+  CovBuffers B;
 };
 
-CovPlan cov_plan(const vsl_ba_problem* p, const int32_t* cams, int n_cam_q, const int32_t* lms, int n_lm_q) {
-  CovPlan P;
-  P.cam_free.assign(p->n_cams, -1);
-  for (int c = 0; c < p->n_cams; c++)
-    if (!p->cam_fixed[c]) P.cam_free[c] = P.nfree++;
-  std::vector<int> lm_slot(p->n_lms, -1);
-  P.lm_q2u.resize(n_lm_q);
-  for (int q = 0; q < n_lm_q; q++) {
-    int& s = lm_slot[lms[q]];
-    if (s < 0) {
-      s = (int)P.u_lm.size();
-      P.u_lm.push_back(lms[q]);
-    }
-    P.lm_q2u[q] = s;
-  }
-  P.nu = (int)P.u_lm.size();
-  P.u_start.assign((size_t)P.nu + 1, 0);
-  if (P.nu > 0)
-    for (int i = 0; i < p->n_obs; i++) {
-      const int s = lm_slot[p->obs_lm[i]];
-      if (s >= 0) P.u_start[s + 1]++;
-    }
-  for (int u = 0; u < P.nu; u++) {
-    P.kmax = std::max(P.kmax, P.u_start[u + 1]);
-    P.u_start[u + 1] += P.u_start[u];
-  }
-  P.n_o = P.u_start[P.nu];
-  std::vector<int> o_idx(P.n_o), fill(P.u_start.begin(), P.u_start.end() - 1);
-  if (P.nu > 0)
-    for (int i = 0; i < p->n_obs; i++) {
-      const int s = lm_slot[p->obs_lm[i]];
-      if (s >= 0) o_idx[fill[s]++] = i;
-    }
-  std::vector<char> inQ(P.nfree, 0);
-  for (int q = 0; q < n_cam_q; q++) inQ[P.cam_free[cams[q]]] = 1;
-  P.o_cam.resize(P.n_o);
-  P.o_uv.resize(2 * (size_t)P.n_o);
-  for (int u = 0; u < P.nu; u++) {
-    // ascending free index (fixed cameras, -1, first), observation order within a camera
-    std::stable_sort(o_idx.begin() + P.u_start[u], o_idx.begin() + P.u_start[u + 1],
-                     [&](int x, int y) { return P.cam_free[p->obs_cam[x]] < P.cam_free[p->obs_cam[y]]; });
-    for (int k = P.u_start[u]; k < P.u_start[u + 1]; k++) {
-      const int i = o_idx[k], fc = P.cam_free[p->obs_cam[i]];
-      P.o_cam[k] = p->obs_cam[i];
-      P.o_uv[2 * (size_t)k] = p->obs_uv[2 * (size_t)i];
-      P.o_uv[2 * (size_t)k + 1] = p->obs_uv[2 * (size_t)i + 1];
-      if (fc >= 0) inQ[fc] = 1;
-    }
-  }
-  P.qpos.assign(P.nfree, -1);
-  for (int c = 0; c < P.nfree; c++)
-    if (inQ[c]) {
-      P.qpos[c] = (int)P.q_free.size();
-      P.q_free.push_back(c);
-    }
-  P.nQ = (int)P.q_free.size();
-  P.cam_q2Q.resize(n_cam_q);
-  for (int q = 0; q < n_cam_q; q++) P.cam_q2Q[q] = P.qpos[P.cam_free[cams[q]]];
-  return P;
+int cov_check_kmax(const CovCall& c) {
+  if (c.P.kmax > COV_KMAX)
+    return vsl_fail(c.ctx, VSL_ERR_INVALID, "%s: a queried landmark has %d observations (at most %d)", c.name, c.P.kmax, COV_KMAX);
+  return VSL_OK;
 }
 
-// the caller's share of the arena (BaCommon::extra): [inputs, uploaded in one copy | work | outputs, one copy back]
-struct CovBuffers {
-  size_t in_bytes = 0, out_off = 0, out_bytes = 0, total = 0;
-  size_t off_ok, off_col_unk, off_q_free, off_qpos, off_u_lm, off_u_start, off_o_cam, off_o_uv;  // inputs
-  size_t off_Linv, off_Sdiag, off_X;                                                             // work
-  size_t off_pose, off_point, off_deg, off_ok_out;                                               // outputs (relative to out_off)
-};
+void cov_size_buffers(CovCall& c, int bw) {
+  const int n = 6 * c.P.nfree;
+  c.B = c.band ? cov_band_buffers(c.P, n, bw) : cov_buffers(c.P, n, (6 * c.P.nQ + COV_COLS - 1) / COV_COLS);
+}
 
-CovBuffers cov_buffers(const CovPlan& P, int n, int nblk) {
-  CovBuffers B;
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = at;
-    at += cov_pad(bytes);
-    return o;
-  };
-  B.off_ok = take(sizeof(int));
-  B.off_col_unk = take(sizeof(int) * (size_t)nblk * COV_COLS);
-  B.off_q_free = take(sizeof(int) * (size_t)P.nQ);
-  B.off_qpos = take(sizeof(int) * (size_t)P.nfree);
-  B.off_u_lm = take(sizeof(int) * (size_t)P.nu);
-  B.off_u_start = take(sizeof(int) * ((size_t)P.nu + 1));
-  B.off_o_cam = take(sizeof(int) * (size_t)P.n_o);
-  B.off_o_uv = take(sizeof(double) * 2 * (size_t)P.n_o);
-  B.in_bytes = at;
-  B.off_Linv = take(sizeof(double) * (size_t)((n + COV_NB - 1) / COV_NB) * COV_NB * COV_NB);
-  B.off_Sdiag = take(sizeof(double) * (size_t)n);
-  B.off_X = take(sizeof(double) * (size_t)nblk * n * COV_COLS);
-  B.out_off = at;
-  B.off_pose = take(sizeof(double) * 36 * (size_t)P.nQ) - B.out_off;
-  B.off_point = take(sizeof(double) * 9 * (size_t)P.nu) - B.out_off;
-  B.off_deg = take(sizeof(int) * (size_t)P.nu) - B.out_off;
-  B.out_bytes = at - B.out_off;
-  B.total = at;
-  return B;
+// BaCaller::plan_extra of vsl_global_ba_covariance
+int cov_plan_extra(void* self, const BaHostPlan& hp, size_t* extra_bytes) {
+  CovCall& c = *static_cast<CovCall*>(self);
+  c.band = hp.layout.banded;
+  // dense: hp.cam_free is the ascending numbering, the plan is vsl_ba_covariance's.  Band: hp.cam_free is the band order.
+  c.P = cov_plan(c.prob, hp.cam_free, hp.nfree, !c.band, c.cams, c.n_cam_q, c.lms, c.n_lm_q);
+  const int rc = cov_check_kmax(c);
+  if (rc) return rc;
+  cov_size_buffers(c, hp.layout.bw);
+  *extra_bytes = c.B.total;
+  return VSL_OK;
 }
 
 // everything behind the validation; host_in / host_out outlive the stream work (the caller synchronises on an error)
-int cov_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const CovPlan& P, BaState& st,
-            std::vector<char>& host_in, std::vector<char>& host_out, CovBuffers& B) {
-  const int n = 6 * P.nfree, m = 6 * P.nQ, nblk = (m + COV_COLS - 1) / COV_COLS;
-  B = cov_buffers(P, n, nblk);
-  BaCaller caller{BaUse::COVARIANCE};
-  caller.extra_bytes = B.total;
+int cov_run(CovCall& c, const vsl_ba_options* opt, BaState& st, std::vector<char>& host_in, std::vector<char>& host_out) {
+  vsl_ctx* ctx = c.ctx;
+  BaCaller caller{c.global ? BaUse::GLOBAL_COVARIANCE : BaUse::COVARIANCE};
+  if (c.global) {
+    caller.plan_extra = cov_plan_extra;
+    caller.plan_extra_self = &c;
+  } else {
+    cov_size_buffers(c, 0);
+    caller.extra_bytes = c.B.total;
+  }
   int rc;
-  if ((rc = ba_setup(ctx, prob, opt, st, caller))) return rc;
+  if ((rc = ba_setup(ctx, c.prob, opt, st, caller))) return rc;
+  const CovPlan& P = c.P;
+  const CovBuffers& B = c.B;
+  const int n = 6 * P.nfree, m = 6 * P.nQ, nblk = (m + COV_COLS - 1) / COV_COLS;
   const BaDims& D = st.D;
-  if (D.nfree != P.nfree) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: free-camera count mismatch");
+  if (D.nfree != P.nfree || st.banded != c.band) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: the set-up and the plan disagree", c.name);
   char* dev = st.extra;
   host_in.assign(B.in_bytes, 0);
   auto put = [&](size_t off, const void* src, size_t bytes) {
@@ -445,13 +442,13 @@ int cov_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
   };
   const int one = 1;
   put(B.off_ok, &one, sizeof(int));
-  {
+  if (!c.band) {
     std::vector<int> col_unk((size_t)nblk * COV_COLS, -1);
     for (int j = 0; j < m; j++) col_unk[j] = 6 * P.q_free[j / 6] + j % 6;
     put(B.off_col_unk, col_unk.data(), sizeof(int) * col_unk.size());
+    put(B.off_qpos, P.qpos.data(), sizeof(int) * P.qpos.size());
   }
   put(B.off_q_free, P.q_free.data(), sizeof(int) * P.q_free.size());
-  put(B.off_qpos, P.qpos.data(), sizeof(int) * P.qpos.size());
   put(B.off_u_lm, P.u_lm.data(), sizeof(int) * P.u_lm.size());
   put(B.off_u_start, P.u_start.data(), sizeof(int) * P.u_start.size());
   put(B.off_o_cam, P.o_cam.data(), sizeof(int) * P.o_cam.size());
@@ -459,22 +456,33 @@ int cov_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
   VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), B.in_bytes, hipMemcpyHostToDevice, ctx->stream));
   int* ok = (int*)(dev + B.off_ok);
   double* X = (double*)(dev + B.off_X);
-  if (P.nQ > 0) {
-    // S as vsl_ba_linearize forms it (dense: this use never takes a band form), then its factor and the columns of S^-1
-    double* Linv = (double*)(dev + B.off_Linv);
-    double* Sdiag = (double*)(dev + B.off_Sdiag);
+  double* Sdiag = (double*)(dev + B.off_Sdiag);
+  double* Zs = (double*)(dev + B.off_Z);  // band route: the storage base of the band of S^-1
+  if (c.band ? P.need_inverse : P.nQ > 0) {
+    // S as vsl_ba_linearize forms it, in the layout of the set-up
     if ((rc = ba_linearize(ctx, st, st.sb, false))) return rc;
     if ((rc = ba_columns(ctx, st, st.sb))) return rc;
     if ((rc = ba_schur(ctx, st, st.sb, false, 1.0, 0, D.L, false, false))) return rc;
     VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-    hipLaunchKernelGGL(ba_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.S, Sdiag);
+    hipLaunchKernelGGL(ba_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.S, c.band ? st.ldS : 0, Sdiag);
     VSL_CHECK_LAUNCH(ctx);
-    if ((rc = vsl_chol_factor_dev(ctx, st.S, n, ok, Linv))) return rc;
-    hipLaunchKernelGGL(ba_cov_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, st.S, Linv, Sdiag,
-                       (const int*)(dev + B.off_col_unk), X, ok);
-    hipLaunchKernelGGL(ba_cov_pose_kernel, dim3((36 * P.nQ + 255) / 256), dim3(256), 0, ctx->stream, n, P.nQ,
-                       (const int*)(dev + B.off_q_free), X, ok, (double*)(dev + B.out_off + B.off_pose));
-    VSL_CHECK_LAUNCH(ctx);
+    if (c.band) {
+      // the band of S^-1 by selected inversion (S <- L in place), then the pivot test on the factor
+      if ((rc = vsl_chol_selinv_band_dev(ctx, st.S_eff(), Zs + st.ldS, n, st.ldS, st.bw, ok))) return rc;
+      if ((rc = vsl_cov_band_pivot_dev(ctx, n, st.S, st.ldS, Sdiag, ok))) return rc;
+      if ((rc = vsl_cov_band_blocks_dev(ctx, P.nQ, (const int*)(dev + B.off_q_free), Zs, st.ldS, ok,
+                                        (double*)(dev + B.out_off + B.off_pose))))
+        return rc;
+    } else {
+      // the dense factor and the columns of S^-1
+      double* Linv = (double*)(dev + B.off_Linv);
+      if ((rc = vsl_chol_factor_dev(ctx, st.S, n, ok, Linv))) return rc;
+      hipLaunchKernelGGL(ba_cov_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, st.S, Linv, Sdiag,
+                         (const int*)(dev + B.off_col_unk), X, ok);
+      hipLaunchKernelGGL(ba_cov_pose_kernel, dim3((36 * P.nQ + 255) / 256), dim3(256), 0, ctx->stream, n, P.nQ,
+                         (const int*)(dev + B.off_q_free), X, ok, (double*)(dev + B.out_off + B.off_pose));
+      VSL_CHECK_LAUNCH(ctx);
+    }
   }
   if (P.nu > 0) {
     BlArgs a;
@@ -485,10 +493,17 @@ int cov_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
     a.intr = st.intr;
     a.cam_intr = st.cam_intr;
     a.cam_free = st.cam_free;
-    hipLaunchKernelGGL(ba_cov_landmark_kernel, dim3(P.nu), dim3(64), sizeof(double) * 27 * (size_t)std::max(P.kmax, 1),
-                       ctx->stream, a, n, (const int*)(dev + B.off_u_lm), (const int*)(dev + B.off_u_start),
-                       (const int*)(dev + B.off_o_cam), (const double*)(dev + B.off_o_uv), (const int*)(dev + B.off_qpos), X,
-                       ok, (double*)(dev + B.out_off + B.off_point), (int*)(dev + B.out_off + B.off_deg));
+    const size_t lds = sizeof(double) * 27 * (size_t)std::max(P.kmax, 1);
+    if (c.band)
+      hipLaunchKernelGGL(ba_cov_landmark_kernel<CovBandInverse>, dim3(P.nu), dim3(64), lds, ctx->stream, a,
+                         (const int*)(dev + B.off_u_lm), (const int*)(dev + B.off_u_start), (const int*)(dev + B.off_o_cam),
+                         (const double*)(dev + B.off_o_uv), CovBandInverse{st.ldS, Zs + st.ldS}, ok,
+                         (double*)(dev + B.out_off + B.off_point), (int*)(dev + B.out_off + B.off_deg));
+    else
+      hipLaunchKernelGGL(ba_cov_landmark_kernel<CovDenseInverse>, dim3(P.nu), dim3(64), lds, ctx->stream, a,
+                         (const int*)(dev + B.off_u_lm), (const int*)(dev + B.off_u_start), (const int*)(dev + B.off_o_cam),
+                         (const double*)(dev + B.off_o_uv), CovDenseInverse{n, (const int*)(dev + B.off_qpos), X}, ok,
+                         (double*)(dev + B.out_off + B.off_point), (int*)(dev + B.out_off + B.off_deg));
     VSL_CHECK_LAUNCH(ctx);
   }
   host_out.assign(B.out_bytes + sizeof(int), 0);
@@ -497,7 +512,70 @@ int cov_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   int ok_host;
   memcpy(&ok_host, host_out.data() + B.out_bytes, sizeof(int));
-  if (!ok_host) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_covariance: the reduced camera system is not positive definite");
+  if (!ok_host) return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: the reduced camera system is not positive definite", c.name);
+  return VSL_OK;
+}
+
+// both entry points: the argument rules, the run, the query -> output maps.  storage: null for vsl_ba_covariance
+int cov_call(CovCall& c, const vsl_ba_options* opt, double* cov_pose, double* cov_point, int* n_degenerate, int* storage) {
+  vsl_ctx* ctx = c.ctx;
+  const vsl_ba_problem* prob = c.prob;
+  const int32_t *cams = c.cams, *lms = c.lms;
+  const int n_cam_q = c.n_cam_q, n_lm_q = c.n_lm_q;
+  int rc = ba_validate(ctx, prob);  // an empty problem (n_lms = 0, n_obs = 0) ends here
+  if (rc) return rc;
+  if (!opt || n_cam_q < 0 || n_lm_q < 0 || (n_cam_q > 0 && (!cams || !cov_pose)) || (n_lm_q > 0 && (!lms || !cov_point)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null argument or negative count", c.name);
+  for (int q = 0; q < n_cam_q; q++) {
+    if (cams[q] < 0 || cams[q] >= prob->n_cams) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: camera %d out of range", c.name, cams[q]);
+    if (prob->cam_fixed[cams[q]]) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: camera %d is fixed", c.name, cams[q]);
+  }
+  for (int q = 0; q < n_lm_q; q++)
+    if (lms[q] < 0 || lms[q] >= prob->n_lms) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: landmark %d out of range", c.name, lms[q]);
+  if (n_degenerate) *n_degenerate = 0;
+  if (n_cam_q == 0 && n_lm_q == 0) {
+    // nothing is launched; the route is still the problem's own (decided on the host)
+    if (storage) {
+      bool banded = false;
+      if ((rc = ba_layout_of(ctx, prob, BaCaller{BaUse::GLOBAL_COVARIANCE}, &banded))) return rc;
+      *storage = banded ? 1 : 0;
+    }
+    return VSL_OK;
+  }
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  if (!c.global) {
+    try {
+      c.P = cov_plan(prob, cams, n_cam_q, lms, n_lm_q);
+    } catch (const std::bad_alloc&) {
+      return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    if ((rc = cov_check_kmax(c))) return rc;
+  }
+  std::vector<char> host_in, host_out;  // read / written by copies on the stream: they outlive the synchronisation below
+  {
+    BaState st;  // holds the loan of the context's arena
+    try {
+      rc = cov_run(c, opt, st, host_in, host_out);
+    } catch (const std::bad_alloc&) {
+      rc = vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    // an error return may leave kernels and copies queued that use the arena and the host buffers: drain the stream
+    // before the loan ends (a later solve on this context gets the same block)
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+  }
+  if (rc) return rc;
+  const CovPlan& P = c.P;
+  const double* pose = (const double*)(host_out.data() + c.B.off_pose);
+  const double* point = (const double*)(host_out.data() + c.B.off_point);
+  const int* deg = (const int*)(host_out.data() + c.B.off_deg);
+  for (int q = 0; q < n_cam_q; q++) memcpy(cov_pose + 36 * (size_t)q, pose + 36 * (size_t)P.cam_q2Q[q], 36 * sizeof(double));
+  int nd = 0;
+  for (int q = 0; q < n_lm_q; q++) {
+    memcpy(cov_point + 9 * (size_t)q, point + 9 * (size_t)P.lm_q2u[q], 9 * sizeof(double));
+    nd += deg[P.lm_q2u[q]] ? 1 : 0;
+  }
+  if (n_degenerate) *n_degenerate = nd;
+  if (storage) *storage = c.band ? 1 : 0;
   return VSL_OK;
 }
 
@@ -512,53 +590,32 @@ int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double*
   return VSL_OK;
 }
 
+int vsl_cov_band_pivot_dev(vsl_ctx* ctx, int n, const double* L, int ld, const double* Sdiag, int* ok_dev) {
+  if (n <= 0) return VSL_OK;
+  hipLaunchKernelGGL(cov_band_pivot_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, L, ld, Sdiag, ok_dev);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_cov_band_blocks_dev(vsl_ctx* ctx, int nQ, const int* q_free, const double* Z, int ld, const int* ok_dev, double* out) {
+  if (nQ <= 0) return VSL_OK;
+  hipLaunchKernelGGL(cov_band_pose_kernel, dim3((36 * nQ + 255) / 256), dim3(256), 0, ctx->stream, nQ, q_free, Z, ld, ok_dev, out);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
 extern "C" int vsl_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const int32_t* cams,
                                  int n_cam_q, double* cov_pose, const int32_t* lms, int n_lm_q, double* cov_point,
                                  int* n_degenerate) {
-  int rc = ba_validate(ctx, prob);  // an empty problem (n_lms = 0, n_obs = 0) ends here
-  if (rc) return rc;
-  if (!opt || n_cam_q < 0 || n_lm_q < 0 || (n_cam_q > 0 && (!cams || !cov_pose)) || (n_lm_q > 0 && (!lms || !cov_point)))
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: null argument or negative count");
-  for (int q = 0; q < n_cam_q; q++) {
-    if (cams[q] < 0 || cams[q] >= prob->n_cams) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: camera %d out of range", cams[q]);
-    if (prob->cam_fixed[cams[q]]) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: camera %d is fixed", cams[q]);
-  }
-  for (int q = 0; q < n_lm_q; q++)
-    if (lms[q] < 0 || lms[q] >= prob->n_lms) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: landmark %d out of range", lms[q]);
-  if (n_degenerate) *n_degenerate = 0;
-  if (n_cam_q == 0 && n_lm_q == 0) return VSL_OK;
-  VSL_HIP(ctx, hipSetDevice(ctx->device));
-  CovPlan P;
-  try {
-    P = cov_plan(prob, cams, n_cam_q, lms, n_lm_q);
-  } catch (const std::bad_alloc&) {
-    return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
-  }
-  if (P.kmax > COV_KMAX)
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_covariance: a queried landmark has %d observations (at most %d)", P.kmax, COV_KMAX);
-  std::vector<char> host_in, host_out;  // read / written by copies on the stream: they outlive the synchronisation below
-  CovBuffers B;
-  {
-    BaState st;  // holds the loan of the context's arena
-    try {
-      rc = cov_run(ctx, prob, opt, P, st, host_in, host_out, B);
-    } catch (const std::bad_alloc&) {
-      rc = vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
-    }
-    // an error return may leave kernels and copies queued that use the arena and the host buffers: drain the stream
-    // before the loan ends (a later solve on this context gets the same block)
-    if (rc) (void)hipStreamSynchronize(ctx->stream);
-  }
-  if (rc) return rc;
-  const double* pose = (const double*)(host_out.data() + B.off_pose);
-  const double* point = (const double*)(host_out.data() + B.off_point);
-  const int* deg = (const int*)(host_out.data() + B.off_deg);
-  for (int q = 0; q < n_cam_q; q++) memcpy(cov_pose + 36 * (size_t)q, pose + 36 * (size_t)P.cam_q2Q[q], 36 * sizeof(double));
-  int nd = 0;
-  for (int q = 0; q < n_lm_q; q++) {
-    memcpy(cov_point + 9 * (size_t)q, point + 9 * (size_t)P.lm_q2u[q], 9 * sizeof(double));
-    nd += deg[P.lm_q2u[q]] ? 1 : 0;
-  }
-  if (n_degenerate) *n_degenerate = nd;
-  return VSL_OK;
+  if (!ctx) return VSL_ERR_INVALID;
+  CovCall c{ctx, "vsl_ba_covariance", prob, cams, n_cam_q, lms, n_lm_q, false};
+  return cov_call(c, opt, cov_pose, cov_point, n_degenerate, nullptr);
+}
+
+extern "C" int vsl_global_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const int32_t* cams,
+                                        int n_cam_q, double* cov_pose, const int32_t* lms, int n_lm_q, double* cov_point,
+                                        int* n_degenerate, int* storage) {
+  if (!ctx) return VSL_ERR_INVALID;
+  CovCall c{ctx, "vsl_global_ba_covariance", prob, cams, n_cam_q, lms, n_lm_q, true};
+  return cov_call(c, opt, cov_pose, cov_point, n_degenerate, storage);
 }

@@ -19,13 +19,24 @@
 //                     camera LM diagonal kept across rejected steps                     (owned arena, band forms)
 //   COVARIANCE        vsl_ba_covariance (ba_cov.hip): stored blocks of one linearisation, plus `extra_bytes` of the
 //                     caller's own in the same block (BaCommon::extra)                  (the context's arena, dense S)
-enum class BaUse { PARITY_HOOK, SINGLE_LINEARIZE, HOST_LOOP, SESSION, COVARIANCE };
+//   GLOBAL_COVARIANCE vsl_global_ba_covariance (ba_cov.hip): as COVARIANCE, but S may take the LINEAR band form (never
+//                     the cyclic one: selected inversion has no ring recurrence).  The caller's share depends on the
+//                     layout and on the band order, so it is asked for through BaCaller::plan_extra once the host plan
+//                     exists                                                            (the context's arena, dense or linear band)
+enum class BaUse { PARITY_HOOK, SINGLE_LINEARIZE, HOST_LOOP, SESSION, COVARIANCE, GLOBAL_COVARIANCE };
+
+struct BaHostPlan;  // ba_host_plan.h
 
 struct BaCaller {
   BaUse use;
   const vsl_ba_problem* graph_prob = nullptr;  // the problem whose observations define the covisibility graph (a session rank: the FULL problem); null: the problem itself
   int run_max_obs = 0, run_max_lms = 0;        // SESSION: limits of a landmark run of the recompute-form kernels (ba_large.h BL_THREADS, BL_LMW)
   size_t extra_bytes = 0;                      // COVARIANCE: bytes the caller carves up itself, at BaCommon::extra
+  // GLOBAL_COVARIANCE: called once the host plan exists and before the arena is planned, with the layout of S and the
+  // free-camera numbering it implies (hp.cam_free: the band order when hp.layout.renumber).  Sets *extra_bytes;
+  // a return other than VSL_OK ends ba_setup with it.  May throw std::bad_alloc.
+  int (*plan_extra)(void* self, const BaHostPlan& hp, size_t* extra_bytes) = nullptr;
+  void* plan_extra_self = nullptr;
 };
 
 // Buffers of the STORED-BLOCKS form: r / F / E of every observation, written by ba_linearize_kernel and read by the
@@ -71,7 +82,7 @@ struct BaCommon {
   int *lm_start = nullptr, *cam_start = nullptr, *cam_obs = nullptr;
   int* flag = nullptr;           // 128 bytes behind scalars: one copy brings both back
   double* diagc_keep = nullptr;  // SESSION: clamp(diag H_full), reused across rejected steps
-  char* extra = nullptr;         // COVARIANCE: BaCaller::extra_bytes of the same block
+  char* extra = nullptr;         // COVARIANCE, GLOBAL_COVARIANCE: the caller's bytes of the same block
   // large systems, gather form of the Schur complement (ba_schur_gather_kernel): per-block pair lists, built on the
   // first use for the landmark range they cover, and the per-observation Y blocks of the current linearisation
   int *pair_cnt = nullptr, *pair_start = nullptr, *pairs = nullptr, *cam_pos = nullptr;
@@ -120,6 +131,8 @@ struct BaTrace {
 int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p);
 // host plan, ONE arena for the caller's use, uploads; synchronises
 int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaState& st, const BaCaller& caller);
+// the layout of S that ba_setup chooses for this caller, decided on the host alone (no device work)
+int ba_layout_of(vsl_ctx* ctx, const vsl_ba_problem* p, const BaCaller& caller, bool* banded);
 // linearize at (poses, points): r, F, E (scaled when `scaled`), cost -> scalars[cost_slot]
 int ba_linearize(vsl_ctx* ctx, BaCommon& st, BaStored& sb, bool scaled, int cost_slot = 0);
 // per-landmark and per-camera column statistics of the stored blocks: n2l, grad_l, H, g_c

@@ -805,7 +805,6 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
 // the factorisation.  A block depends on H alone, never on what else is queried; the band routes read the lower
 // triangle of a block and mirror it, the dense route averages the two mirror entries: exactly symmetric either way.
 namespace {
-#define PGC_PIVOT_TOL 1.4551915228366852e-11  // 2^-36
 
 // H: the storage as pgo_build_kernel filled it (ld = 0: dense n x n; else rows of ld + 1 slots, the diagonal last)
 __global__ void pgo_cov_diag_kernel(int n, const double* __restrict__ H, int ld, double* __restrict__ d) {
@@ -813,23 +812,7 @@ __global__ void pgo_cov_diag_kernel(int n, const double* __restrict__ H, int ld,
   if (i < n) d[i] = ld > 0 ? H[(size_t)i * (ld + 1) + ld] : H[(size_t)i * n + i];
 }
 
-// band routes: the pivot test on the factor left in the band storage (every failing thread stores the same 0)
-__global__ void pgo_cov_pivot_kernel(int n, const double* __restrict__ L, int ld, const double* __restrict__ d, int* __restrict__ ok) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double l = L[(size_t)i * (ld + 1) + ld], p = l * l;
-  if (!(p > PGC_PIVOT_TOL * d[i]) || !isfinite(p)) *ok = 0;
-}
-
-// block q = rows / columns 6 q_free[q] .. + 5 of the band array Z (storage base), lower triangle mirrored
-__global__ void pgo_cov_blocks_band_kernel(int nQ, const int* __restrict__ q_free, const double* __restrict__ Z, int ld,
-                                           const int* __restrict__ ok, double* __restrict__ out) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 36 * nQ || !*ok) return;
-  const int q = t / 36, a = (t % 36) / 6, b = t % 6;
-  const int i = 6 * q_free[q] + max(a, b), j = 6 * q_free[q] + min(a, b);
-  out[t] = Z[(size_t)i * (ld + 1) + ld - (i - j)];
-}
+// (band routes: the pivot test and the blocks are ba_cov.hip's, vsl_cov_band_pivot_dev / vsl_cov_band_blocks_dev)
 
 // dense route: the diagonal block of X (right-hand sides 6 q .. 6 q + 5 belong to q_free[q]), symmetrised
 __global__ void pgo_cov_blocks_dense_kernel(int n, int nQ, const int* __restrict__ q_free, const double* __restrict__ X,
@@ -937,8 +920,8 @@ int pgo_cov_run(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options*
   } else {
     // st.A: the second band array of the solve, here the band of the inverse
     if ((rc = vsl_chol_selinv_band_dev(ctx, st.H + st.ld, st.A + st.ld, n, st.ld, st.bw, st.flag))) return rc;
-    hipLaunchKernelGGL(pgo_cov_pivot_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.H, st.ld, Hdiag, st.flag);
-    hipLaunchKernelGGL(pgo_cov_blocks_band_kernel, dim3((36 * nQ + 255) / 256), dim3(256), 0, s, nQ, q_dev, st.A, st.ld, st.flag, out);
+    if ((rc = vsl_cov_band_pivot_dev(ctx, n, st.H, st.ld, Hdiag, st.flag))) return rc;
+    if ((rc = vsl_cov_band_blocks_dev(ctx, nQ, q_dev, st.A, st.ld, st.flag, out))) return rc;
   }
   VSL_CHECK_LAUNCH(ctx);
   int ok = 0;

@@ -224,6 +224,13 @@ int vsl_chol_selinv_band_dev(vsl_ctx* ctx, double* S, double* Z, int n, int ld, 
 // before the factorisation -- a pivot L_ii^2 <= 2^-36 Sdiag_i clears *ok_dev and nothing is written.
 int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double* Linv, const double* Sdiag, const int* col_unk,
                              int nblk, double* X, int* ok_dev);
+// The band routes of the covariance calls (ba_cov.hip; vsl_pgo_covariance and vsl_global_ba_covariance).  L, Z: the
+// STORAGE base of a band array (rows of ld + 1 slots, the diagonal last).
+// pivot: the factor left by vsl_chol_selinv_band_dev against diag S before the factorisation -- a pivot L_ii^2 <=
+// 2^-36 Sdiag_i clears *ok_dev.  blocks: out[36 q ..] = the diagonal 6 x 6 block of camera / node q_free[q] (device),
+// lower triangle mirrored; nothing written when *ok_dev = 0.
+int vsl_cov_band_pivot_dev(vsl_ctx* ctx, int n, const double* L, int ld, const double* Sdiag, int* ok_dev);
+int vsl_cov_band_blocks_dev(vsl_ctx* ctx, int nQ, const int* q_free, const double* Z, int ld, const int* ok_dev, double* out);
 __host__ __device__ inline size_t vsl_cov_x_at(int n, int i, int col) {
   return (size_t)(col / 16) * n * 16 + (size_t)i * 16 + (col % 16);
 }
