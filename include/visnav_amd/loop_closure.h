@@ -247,6 +247,81 @@ inline int pose_graph_covariance(const FrameCamId& cur_kf_fcid, Camera& cur_kf, 
   return storage;
 }
 
+// JOINT covariance of pairs of keyframes of that graph (vsl_pgo_joint_covariance; gtsam's jointMarginalCovariance): 12 x 12
+// over the tangents of (first, second), [[S_aa, S_ab], [S_ba, S_bb]].  Same arguments and the same graph as
+// pose_graph_covariance; one keyframe of a pair may be the fixed current one (cur_kf_fcid with
+// options.set_current_kf_fixed): its rows and columns are zero.  cov_out: one block per entry of `pairs`, in order.
+// Returns the route.
+using JointPoseCovariance = Eigen::Matrix<double, 12, 12>;
+inline int pose_graph_joint_covariance(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
+                                       const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
+                                       const LoopClosureOptions& options,
+                                       const std::vector<std::pair<FrameCamId, FrameCamId>>& pairs,
+                                       std::vector<JointPoseCovariance>& cov_out) {
+  cov_out.clear();
+  amd::PgoFlat f;
+  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  auto node = [&](const FrameCamId& id) { return (int32_t)(id == cur_kf_fcid ? 0 : f.node_of.at(id)); };
+  std::vector<int32_t> a, b;
+  for (const auto& p : pairs) {
+    a.push_back(node(p.first));
+    b.push_back(node(p.second));
+  }
+  vsl_ba_options opt;
+  opt.use_huber = 1;
+  opt.huber_parameter = 1.0;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  std::vector<double> cov(144 * pairs.size());
+  int storage = 0;
+  const int rc = vsl_pgo_joint_covariance(amd::ctx(), &f.prob, &opt, a.data(), b.data(), (int)pairs.size(), cov.data(), &storage);
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
+  amd::check(rc, "pose_graph_joint_covariance");
+  cov_out.resize(pairs.size());
+  for (size_t q = 0; q < pairs.size(); q++)
+    for (int i = 0; i < 12; i++)
+      for (int j = 0; j < 12; j++) cov_out[q](i, j) = cov[144 * q + 12 * i + j];
+  return storage;
+}
+
+// Is a measured relative pose between two keyframes consistent with that graph (vsl_pgo_edge_consistency): the
+// chi-square gate of a loop candidate, where the reference accepts on the sum of the relative translation alone.
+// Same arguments and the same graph as pose_graph_covariance, plus the candidate: T_a_b = the measured T_w_a^-1 T_w_b of
+// the keyframes a, b (either may be cur_kf_fcid), meas_cov its 6 x 6 covariance over (upsilon, omega) or null for
+// none.  residual = log(T_w_a^-1 T_w_b) - log(T_a_b) at the poses as they stand, residual_cov its first-order
+// covariance from the graph, chi2 = r^T (residual_cov + meas_cov)^-1 r with six degrees of freedom (NaN when that sum
+// is not positive definite).  Returns the route.
+struct LoopCandidateConsistency {
+  double residual[6] = {0, 0, 0, 0, 0, 0};
+  PoseCovariance residual_cov;
+  double chi2 = 0;
+};
+inline int loop_candidate_consistency(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
+                                      const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
+                                      const LoopClosureOptions& options, const FrameCamId& cand_a, const FrameCamId& cand_b,
+                                      const Sophus::SE3d& T_a_b, const PoseCovariance* meas_cov, LoopCandidateConsistency& out) {
+  amd::PgoFlat f;
+  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  const int32_t a = cand_a == cur_kf_fcid ? 0 : f.node_of.at(cand_a), b = cand_b == cur_kf_fcid ? 0 : f.node_of.at(cand_b);
+  double meas[6], mc[36], rc36[36];
+  amd::rt_log(amd::rt_of(T_a_b), meas);
+  if (meas_cov)
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) mc[6 * i + j] = (*meas_cov)(i, j);
+  vsl_ba_options opt;
+  opt.use_huber = 1;
+  opt.huber_parameter = 1.0;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  int storage = 0;
+  const int rc = vsl_pgo_edge_consistency(amd::ctx(), &f.prob, &opt, &a, &b, meas, meas_cov ? mc : nullptr, 1, out.residual, rc36,
+                                          &out.chi2, &storage);
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
+  amd::check(rc, "loop_candidate_consistency");
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) out.residual_cov(i, j) = rc36[6 * i + j];
+  return storage;
+}
 
 // loop_closure_utils.h:109-126
 inline double compute_min_connected_covisible(const Camera& new_kf, const Cameras& keyframes, const ORBVocabularyAmd* voc, int threshold) {

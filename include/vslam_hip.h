@@ -233,6 +233,9 @@ int vsl_ctx_set_tie_eps(vsl_ctx* ctx, double eps);
  *   "chol_no_bcr" (0/1)             long narrow bands by the band Cholesky instead of block cyclic reduction
  *   "chol_one_ended" (0/1)          narrow-band Cholesky eliminated from the top only instead of from both ends
  *   "ba_force_dense" (0/1)          large bundle adjustment with the dense reduced camera system (no band ordering)
+ *   "pgo_cov_no_band_read" (0/1)    vsl_pgo_joint_covariance / vsl_pgo_edge_consistency on the band routes: unit columns
+ *                                   are solved for in-band pairs as well instead of reading the band of the inverse
+ *                                   (agrees to the tolerance, not bit for bit)
  *   "ba_schur_atomics" (0/1)        large-system Schur complement by fp64 atomics instead of the per-block gather
  *   "ba_no_fused" (0/1)             local windows (<= 21 free cameras) by the operator-by-operator kernels instead of the
  *                                   fused four-launch iteration (ba_fused.hip)
@@ -566,6 +569,38 @@ int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl
  *      move under a relabelling), H is built in linear band storage of the folded order, then as route 1. */
 int vsl_pgo_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* nodes, int n_q,
                        double* cov, int* storage);
+/* JOINT marginal covariance of pairs of nodes (gtsam jointMarginalCovariance, g2o computeMarginals on a block pair).
+ * Everything vsl_pgo_covariance documents carries over: Sigma = H^-1 of the same H, the same tangent, nothing optimised,
+ * poses only read, the same VSL_ERR_NUMERIC rule, *storage the same route decision, n_pairs = 0 returns VSL_OK, launches
+ * nothing and still reports the route.  Block q of cov [n_pairs][12][12] row-major is
+ *     [[Sigma_aa, Sigma_ab], [Sigma_ba, Sigma_bb]],  a = pair_a[q], b = pair_b[q]   (NODE ids).
+ * A fixed node may be one of the two: it is the gauge, its rows and columns are exactly 0.0.  a == b, both nodes fixed
+ * or an id out of range give VSL_ERR_INVALID.  Every block is exactly symmetric; (a, b) and (b, a) return the same bits
+ * with the blocks swapped and transposed; the diagonal blocks are the bits vsl_pgo_covariance returns on the same
+ * route; a pair's result depends on H and the route alone (duplicates and permutations allowed); two calls return the
+ * same bits.  Where Sigma_ab comes from, by route:
+ *   0  the unit columns of every distinct queried free node (as vsl_pgo_covariance); entry (i, j) of Sigma_ab is the
+ *      average of the two mirror entries X_b[6 a + i][j] and X_a[6 b + j][i], the rule of the diagonal blocks;
+ *   1, 2  with f the free indices in the order the device sees (route 2: the folded order) and bw the half bandwidth
+ *      of the band it builds: 6 |f_a - f_b| + 5 <= bw -- the whole block lies inside the band of the selected
+ *      inversion and is read from it (stored lower triangle, so no rounding choice); every other pair takes true
+ *      out-of-band entries from a band unit-column solve of the six columns of ONE node, the one with the larger f
+ *      (forward substitution from its own row, back substitution down to the other node's row), single entries, no
+ *      averaging.  Diagnostic "pgo_cov_no_band_read": in-band pairs through the solve as well. */
+int vsl_pgo_joint_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* pair_a,
+                             const int32_t* pair_b, int n_pairs, double* cov, int* storage);
+/* Consistency of candidate edges (a, b, m) with the graph as it stands -- the chi-square gate of a loop candidate.  The
+ * candidate need not be an edge of the graph.  Per candidate:
+ *   resid      r = log(T_a^-1 T_b) - m, the residual of the pose-graph functor (no Huber corrector on the candidate);
+ *   resid_cov  Sigma_r = J_a Sigma_aa J_a^T + J_a Sigma_ab J_b^T + J_b Sigma_ba J_a^T + J_b Sigma_bb J_b^T with the
+ *              6 x 6 Jacobians of r that the linearisation computes and the joint covariance above (same routes, same
+ *              argument rules; the terms of a fixed node are dropped); exactly symmetric (the two mirror sums averaged);
+ *   chi2       r^T (Sigma_r + Sigma_m)^-1 r by a 6 x 6 Cholesky (nullable); Sigma_m = meas_cov [n][36] (its two mirror
+ *              entries averaged), NULL = zero.  A pivot of Sigma_r + Sigma_m that is not positive gives NaN for that
+ *              candidate; the call still returns VSL_OK. */
+int vsl_pgo_edge_consistency(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* cand_a,
+                             const int32_t* cand_b, const double* cand_meas, const double* meas_cov, int n_cand, double* resid,
+                             double* resid_cov, double* chi2, int* storage);
 /* Test hook: H = J^T J (n x n row-major, n = 6 x free nodes in node order), g = J^T r and the cost of the
  * robustified problem at the given poses. */
 int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, double* H, double* g, double* cost,

@@ -1,0 +1,210 @@
+// Stand-alone driver of visual-slam_amd/csrc/pgo_cov_plan.h (plain C++, no HIP): tests/test_pgo_cov_plan_cpu.py builds
+// it with g++ -- once plainly, once under the address and undefined-behaviour sanitizers -- and compares what it prints
+// with values worked out by hand.
+//   check                                       stdin: n_nodes, the fixed flags, n_pairs, the pairs -> "<error> <index>"
+//   plan <folded> <dense> <bw> <no_read> <cand>  stdin as above -> the plan's fields, one per line
+//   sweep                                       properties over chains and rings of many sizes -> "checked <n> solve <m>"
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "pgo_cov_plan.h"
+
+namespace {
+
+struct Input {
+  int n_nodes = 0, n_pairs = 0;
+  std::vector<uint8_t> fixed;
+  std::vector<int32_t> a, b;
+};
+
+bool read_input(Input& in) {
+  if (std::scanf("%d", &in.n_nodes) != 1 || in.n_nodes < 0) return false;
+  in.fixed.resize(in.n_nodes);
+  for (int i = 0; i < in.n_nodes; i++) {
+    int v;
+    if (std::scanf("%d", &v) != 1) return false;
+    in.fixed[i] = (uint8_t)v;
+  }
+  if (std::scanf("%d", &in.n_pairs) != 1 || in.n_pairs < 0) return false;
+  in.a.resize(in.n_pairs);
+  in.b.resize(in.n_pairs);
+  for (int q = 0; q < in.n_pairs; q++)
+    if (std::scanf("%d %d", &in.a[q], &in.b[q]) != 2) return false;
+  return true;
+}
+
+void line(const char* name, const std::vector<int>& v) {
+  std::printf("%s", name);
+  for (int x : v) std::printf(" %d", x);
+  std::printf("\n");
+}
+
+#define REQUIRE(cond)                                                              \
+  do {                                                                             \
+    if (!(cond)) {                                                                 \
+      std::fprintf(stderr, "%s:%d: requirement failed: %s\n", __FILE__, __LINE__, #cond); \
+      std::exit(1);                                                                \
+    }                                                                              \
+  } while (0)
+
+// every property the device code relies on
+void verify(const Input& in, const PgcPlan& P, bool folded, bool dense, int bw, bool no_read, bool cand) {
+  int nf = 0;
+  for (uint8_t f : in.fixed) nf += !f;
+  REQUIRE(P.nf == nf && P.n == 6 * nf && (int)P.pairs.size() == in.n_pairs);
+  // the numbering is a permutation: free nodes onto [0, nf), all nodes onto [0, n_nodes); free nodes first when folded
+  std::set<int> seen_free, seen_node;
+  for (int i = 0, f = 0; i < in.n_nodes; i++) {
+    REQUIRE(P.dev_node[i] >= 0 && P.dev_node[i] < in.n_nodes && seen_node.insert(P.dev_node[i]).second);
+    if (in.fixed[i]) {
+      REQUIRE(P.dev_free[i] == -1);
+      if (folded) REQUIRE(P.dev_node[i] >= nf);
+    } else {
+      REQUIRE(P.dev_free[i] == (folded ? chol_fold_pos(nf, f) : f) && seen_free.insert(P.dev_free[i]).second);
+      REQUIRE(P.dev_free[i] >= 0 && P.dev_free[i] < nf);
+      if (folded) REQUIRE(P.dev_node[i] == P.dev_free[i]);
+      else REQUIRE(P.dev_node[i] == i);
+      f++;
+    }
+  }
+  REQUIRE(P.n_fixed + P.n_read + P.n_solve == in.n_pairs);
+  REQUIRE(std::is_sorted(P.col_nodes.begin(), P.col_nodes.end()));
+  REQUIRE(std::adjacent_find(P.col_nodes.begin(), P.col_nodes.end()) == P.col_nodes.end());
+  REQUIRE(P.nblk == (6 * (int)P.col_nodes.size() + PGC_COLS - 1) / PGC_COLS);
+  REQUIRE((int)P.col_unk.size() == PGC_COLS * P.nblk && (int)P.row_lo.size() == P.nblk);
+  for (size_t j = 0; j < P.col_unk.size(); j++)
+    REQUIRE(j < 6 * P.col_nodes.size() ? P.col_unk[j] == 6 * P.col_nodes[j / 6] + (int)(j % 6) : P.col_unk[j] == -1);
+  std::set<int> used;
+  for (int q = 0; q < in.n_pairs; q++) {
+    const PgcPairDev& d = P.pairs[q];
+    REQUIRE(d.fa == P.dev_free[in.a[q]] && d.fb == P.dev_free[in.b[q]] && d.na == P.dev_node[in.a[q]] && d.nb == P.dev_node[in.b[q]]);
+    const bool one_fixed = d.fa < 0 || d.fb < 0;
+    const bool in_band = !one_fixed && !dense && 6 * std::abs(d.fa - d.fb) + 5 <= bw;
+    REQUIRE(d.kind == (one_fixed ? PGC_ONE_FIXED : (in_band && !no_read ? PGC_READ : PGC_SOLVE)));
+    auto columns_of = [&](int c, int f) { return c >= 0 && c % 6 == 0 && c / 6 < (int)P.col_nodes.size() && P.col_nodes[c / 6] == f; };
+    if (dense) {
+      REQUIRE(d.fa < 0 ? d.ca == -1 : columns_of(d.ca, d.fa));
+      REQUIRE(d.fb < 0 ? d.cb == -1 : columns_of(d.cb, d.fb));
+      if (d.ca >= 0) used.insert(d.ca / 6);
+      if (d.cb >= 0) used.insert(d.cb / 6);
+    } else if (d.kind == PGC_SOLVE) {
+      // the node with the larger device index, whichever way round the pair is given; the block's rows reach the other
+      const int hi = std::max(d.fa, d.fb), lo = std::min(d.fa, d.fb), c = d.fa > d.fb ? d.ca : d.cb;
+      REQUIRE(columns_of(c, hi) && (d.fa > d.fb ? d.cb : d.ca) == -1);
+      for (int blk = c / PGC_COLS; blk <= (c + 5) / PGC_COLS; blk++) REQUIRE(P.row_lo[blk] <= 6 * lo);
+      used.insert(c / 6);
+    } else {
+      REQUIRE(d.ca == -1 && d.cb == -1);
+    }
+  }
+  REQUIRE(used.size() == P.col_nodes.size());  // no column is solved that no pair reads
+  for (int blk = 0; blk < P.nblk; blk++) REQUIRE(P.row_lo[blk] >= 0 && P.row_lo[blk] <= P.n);
+  // the arena: 256-byte aligned, in order, nothing overlaps
+  const size_t np = (size_t)in.n_pairs, nc = cand ? np : 0;
+  const size_t offs[] = {P.off_pairs, P.off_col_unk, P.off_row_lo, P.off_meas, P.off_meas_cov, P.in_bytes, P.off_Hdiag, P.off_Linv,
+                         P.off_X, P.out_off, P.out_off + P.off_cov, P.out_off + P.off_resid, P.out_off + P.off_resid_cov,
+                         P.out_off + P.off_chi2, P.total};
+  const size_t need[] = {sizeof(PgcPairDev) * np, sizeof(int) * P.col_unk.size(), sizeof(int) * P.row_lo.size(), 48 * nc, 288 * nc, 0,
+                         8 * (size_t)P.n, dense ? 8 * (size_t)((P.n + 31) / 32) * 1024 : 0, 8 * (size_t)P.nblk * P.n * PGC_COLS, 0,
+                         1152 * np, 48 * nc, 288 * nc, 8 * nc};
+  for (int i = 0; i < 14; i++) {
+    REQUIRE(offs[i] % 256 == 0 && offs[i] + need[i] <= offs[i + 1]);
+  }
+  REQUIRE(P.out_bytes == P.total - P.out_off);
+}
+
+int sweep() {
+  long checked = 0, solve = 0;
+  unsigned rng = 12345u;
+  auto next = [&]() { return rng = rng * 1664525u + 1013904223u, rng >> 8; };
+  for (int n_nodes : {2, 3, 7, 23, 30, 64, 129})
+    for (int n_fixed : {0, 1, 3})
+      for (int folded = 0; folded < 2; folded++)
+        for (int mode = 0; mode < 3; mode++)  // dense | band | band with the diagnostic
+          for (int bw : {5, 11, 17, 41}) {
+            if (n_fixed >= n_nodes) continue;
+            Input in;
+            in.n_nodes = n_nodes;
+            in.fixed.assign(n_nodes, 0);
+            for (int k = 0; k < n_fixed; k++) in.fixed[next() % n_nodes] = 1;
+            const int np = (int)(next() % 40);
+            for (int q = 0; q < np; q++) {
+              const int a = (int)(next() % n_nodes), b = (int)(next() % n_nodes);
+              if (a == b || (in.fixed[a] && in.fixed[b])) continue;
+              in.a.push_back(a);
+              in.b.push_back(b);
+            }
+            in.n_pairs = (int)in.a.size();
+            REQUIRE(pgc_check_pairs(n_nodes, in.fixed.data(), in.a.data(), in.b.data(), in.n_pairs, nullptr) == PGC_PAIR_OK);
+            for (int cand = 0; cand < 2; cand++) {
+              const PgcPlan P = pgc_plan(n_nodes, in.fixed.data(), folded != 0, mode == 0, bw, mode == 2, in.a.data(), in.b.data(),
+                                         in.n_pairs, cand != 0);
+              verify(in, P, folded != 0, mode == 0, bw, mode == 2, cand != 0);
+              // a pair alone gets the same columns and class as in company: the unordered pair decides
+              for (int q = 0; q < in.n_pairs; q += 7) {
+                const int32_t a1[2] = {in.a[q], in.b[q]}, b1[2] = {in.b[q], in.a[q]};
+                const PgcPlan S = pgc_plan(n_nodes, in.fixed.data(), folded != 0, mode == 0, bw, mode == 2, a1, b1, 2, cand != 0);
+                REQUIRE(S.pairs[0].kind == P.pairs[q].kind && S.pairs[1].kind == P.pairs[q].kind);
+                REQUIRE((S.pairs[0].ca >= 0) == (P.pairs[q].ca >= 0) && (S.pairs[0].cb >= 0) == (P.pairs[q].cb >= 0));
+                REQUIRE(S.pairs[0].ca == S.pairs[1].cb && S.pairs[0].cb == S.pairs[1].ca);
+              }
+              checked++;
+              solve += P.n_solve;
+            }
+          }
+  std::printf("checked %ld solve %ld\n", checked, solve);
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const std::string cmd = argc > 1 ? argv[1] : "";
+  if (cmd == "sweep") return sweep();
+  Input in;
+  if (!read_input(in)) {
+    std::fprintf(stderr, "bad input\n");
+    return 2;
+  }
+  if (cmd == "check") {
+    int bad = -1;
+    const int e = pgc_check_pairs(in.n_nodes, in.fixed.data(), in.a.data(), in.b.data(), in.n_pairs, &bad);
+    std::printf("%d %d\n", e, bad);
+    return 0;
+  }
+  if (cmd == "plan" && argc == 7) {
+    const bool folded = std::atoi(argv[2]) != 0, dense = std::atoi(argv[3]) != 0, no_read = std::atoi(argv[5]) != 0,
+               cand = std::atoi(argv[6]) != 0;
+    const int bw = std::atoi(argv[4]);
+    REQUIRE(pgc_check_pairs(in.n_nodes, in.fixed.data(), in.a.data(), in.b.data(), in.n_pairs, nullptr) == PGC_PAIR_OK);
+    const PgcPlan P = pgc_plan(in.n_nodes, in.fixed.data(), folded, dense, bw, no_read, in.a.data(), in.b.data(), in.n_pairs, cand);
+    verify(in, P, folded, dense, bw, no_read, cand);
+    line("dims", {P.nf, P.n, P.bw, P.nblk, P.n_fixed, P.n_read, P.n_solve});
+    line("dev_free", P.dev_free);
+    line("dev_node", P.dev_node);
+    line("col_nodes", P.col_nodes);
+    line("col_unk", P.col_unk);
+    line("row_lo", P.row_lo);
+    std::vector<int> kind, fa, fb, ca, cb;
+    for (const PgcPairDev& d : P.pairs) {
+      kind.push_back(d.kind);
+      fa.push_back(d.fa);
+      fb.push_back(d.fb);
+      ca.push_back(d.ca);
+      cb.push_back(d.cb);
+    }
+    line("kind", kind);
+    line("fa", fa);
+    line("fb", fb);
+    line("ca", ca);
+    line("cb", cb);
+    line("arena", {(int)P.in_bytes, (int)P.off_X, (int)P.out_off, (int)P.out_bytes, (int)P.total});
+    return 0;
+  }
+  std::fprintf(stderr, "usage: pgo_cov_plan_test check | plan <folded> <dense> <bw> <no_read> <cand> | sweep\n");
+  return 2;
+}

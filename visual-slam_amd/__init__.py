@@ -505,6 +505,41 @@ class Context:
                                            cov.ctypes.data_as(f64p), C.byref(storage)))
         return cov, storage.value
 
+    def pgo_joint_covariance(self, arr, pairs, use_huber=True, huber=1.0):
+        """Joint marginal covariances of pairs of nodes (vsl_pgo_joint_covariance; nothing is optimised).  pairs: [n, 2]
+        node ids (a, b); one of the two may be fixed (zero rows and columns).  Returns (cov [n, 12, 12] in the order
+        (a, b), storage)."""
+        st = self._pgo_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        cov = np.zeros((len(a), 12, 12))
+        storage = C.c_int(-1)
+        self._ck(self.L.vsl_pgo_joint_covariance(self.h, C.byref(st), C.byref(o), a.ctypes.data_as(i32p), b.ctypes.data_as(i32p),
+                                                 len(a), cov.ctypes.data_as(f64p), C.byref(storage)))
+        return cov, storage.value
+
+    def pgo_edge_consistency(self, arr, cand_a, cand_b, cand_meas, meas_cov=None, use_huber=True, huber=1.0):
+        """Residual, residual covariance and chi-square of candidate edges (a, b, meas) against the graph as it stands
+        (vsl_pgo_edge_consistency).  cand_meas: [n, 6]; meas_cov: [n, 6, 6] or None (zero).  Returns (resid [n, 6],
+        resid_cov [n, 6, 6], chi2 [n], storage); chi2 is NaN where resid_cov + meas_cov is not positive definite."""
+        st = self._pgo_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        a = np.ascontiguousarray(cand_a, np.int32).reshape(-1)
+        b = np.ascontiguousarray(cand_b, np.int32).reshape(-1)
+        n = len(a)
+        meas = np.ascontiguousarray(cand_meas, np.float64).reshape(n, 6)
+        mc = None if meas_cov is None else np.ascontiguousarray(meas_cov, np.float64).reshape(n, 36)
+        if len(b) != n:
+            raise ValueError("cand_a and cand_b differ in length")
+        resid, resid_cov, chi2 = np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros(n)
+        storage = C.c_int(-1)
+        self._ck(self.L.vsl_pgo_edge_consistency(self.h, C.byref(st), C.byref(o), a.ctypes.data_as(i32p), b.ctypes.data_as(i32p),
+                                                 meas.ctypes.data_as(f64p), None if mc is None else mc.ctypes.data_as(f64p), n,
+                                                 resid.ctypes.data_as(f64p), resid_cov.ctypes.data_as(f64p),
+                                                 chi2.ctypes.data_as(f64p), C.byref(storage)))
+        return resid, resid_cov, chi2, storage.value
+
     def bundle_adjust_intrinsics(self, arr, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
         """optimize_intrinsics = true: optimises arr.poses / arr.points / arr.intr in place."""
         st = self._ba_struct(arr)

@@ -233,6 +233,137 @@ __global__ __launch_bounds__(COV_THREADS) void ba_cov_solve_kernel(int n, const 
   }
 }
 
+// The same solve against a BAND factor (vsl_cov_band_unit_columns_dev): true entries of the inverse OUTSIDE the band
+// that the selected inversion delivers.  L: the origin of the band array (storage + ld, entry (i, j) at i * ld + j,
+// 0 <= i - j <= bw) that vsl_chol_selinv_band_dev left, Linv: its inverted diagonal blocks.  A panel step reaches the bw
+// rows below (forward) / the bw columns before (backward) the panel only, in chunks of COV_CHUNK through the same LDS
+// stage: O(n bw) per column where the dense kernel is O(n^2).
+//   forward   starts at the panel of the block's first unit row: everything above is exactly zero
+//   backward  stops at the panel of row_lo[block], the lowest row a caller reads (nullable: row 0); rows above that
+//             panel are NOT written
+// SHAPE.  The n x COV_COLS result stays in global memory and the rows a step touches (bw + 32 of them: 14 KB at bw = 77)
+// are updated there, in the L2: the rows of one step are disjoint 16-row tiles of different wavefronts, a tile is read
+// and written once per step, so a sliding window in LDS would save one L2 round trip per tile and step and add the
+// copy in and out of the window at every panel.  Not measured against each other; this is the dense kernel's proven
+// structure with the band's bounds.
+// As there: one lane per entry and step, panels in ascending (descending) order, no atomics -- a column has the same
+// bits whichever columns share its workgroup and wherever the forward pass starts (a zero row contributes +0.0).
+__global__ __launch_bounds__(COV_THREADS) void cov_band_solve_kernel(int n, const double* __restrict__ L, int ld, int bw,
+                                                                     const double* __restrict__ Linv,
+                                                                     const int* __restrict__ col_unk,
+                                                                     const int* __restrict__ row_lo, double* __restrict__ X,
+                                                                     const int* __restrict__ ok) {
+  __shared__ double Li[COV_NB][COV_LP];
+  __shared__ double Bk[COV_NB][COV_COLS];
+  __shared__ double stage[COV_NB * COV_LQ];  // forward: [COV_CHUNK][COV_LP], backward: [COV_NB][COV_LQ]
+  if (!*ok) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
+  int first = n;
+  for (int c = 0; c < COV_COLS; c++) {
+    const int u = col_unk[COV_COLS * blockIdx.x + c];
+    if (u >= 0 && u < first) first = u;
+  }
+  if (first >= n) return;  // (uniform: a block without a column)
+  const int lo = row_lo ? max(0, min(row_lo[blockIdx.x], first)) : 0;
+  const int p_first = first / COV_NB, p_lo = lo / COV_NB, np = (n + COV_NB - 1) / COV_NB;
+  double* __restrict__ Xw = X + (size_t)blockIdx.x * n * COV_COLS;
+  for (int t = tid + p_lo * COV_NB * COV_COLS; t < n * COV_COLS; t += COV_THREADS)
+    Xw[t] = col_unk[COV_COLS * blockIdx.x + (t % COV_COLS)] == t / COV_COLS ? 1.0 : 0.0;
+  __syncthreads();
+  // ---- forward: L Y = E
+  for (int p = p_first; p < np; p++) {
+    const int k = p * COV_NB, nb = min(COV_NB, n - k), iend = min(n, k + COV_NB + bw);
+    for (int t = tid; t < COV_NB * COV_NB; t += COV_THREADS) Li[t / COV_NB][t % COV_NB] = Linv[(size_t)p * COV_NB * COV_NB + t];
+    for (int t = tid; t < COV_NB * COV_COLS; t += COV_THREADS) {
+      const int r = t / COV_COLS;
+      Bk[r][t % COV_COLS] = r < nb ? Xw[(size_t)(k + r) * COV_COLS + (t % COV_COLS)] : 0.0;
+    }
+    __syncthreads();
+    cov_v4d acc = {0.0, 0.0, 0.0, 0.0};
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int s = 0; s < COV_NB / 4; s++)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Li[16 * wave + l16][4 * s + kq], Bk[4 * s + kq][l16], acc, 0, 0, 0);
+    }
+    __syncthreads();  // B_k has been read: Y_k takes its place
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int r = 16 * wave + kq + 4 * q;
+        Bk[r][l16] = acc[q];
+        if (r < nb) Xw[(size_t)(k + r) * COV_COLS + l16] = acc[q];
+      }
+    }
+    __syncthreads();
+    for (int i0 = k + COV_NB; i0 < iend; i0 += COV_CHUNK) {
+      for (int t = tid; t < COV_CHUNK * COV_NB; t += COV_THREADS) {
+        const int r = t / COV_NB, c = t % COV_NB, i = i0 + r, j = k + c;
+        stage[r * COV_LP + c] = (i < n && i - j <= bw) ? L[(size_t)i * ld + j] : 0.0;
+      }
+      __syncthreads();
+      const int r0 = i0 + 16 * wave;
+      if (r0 < iend) {
+        cov_v4d a2 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < COV_NB / 4; s++)
+          a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(stage[(16 * wave + l16) * COV_LP + 4 * s + kq], Bk[4 * s + kq][l16], a2, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int r = r0 + kq + 4 * q;
+          if (r < iend) Xw[(size_t)r * COV_COLS + l16] -= a2[q];
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // ---- backward: L^T X = Y
+  for (int p = np - 1; p >= p_lo; p--) {
+    const int k = p * COV_NB, nb = min(COV_NB, n - k), cbeg = max(p_lo * COV_NB, k - bw);
+    for (int t = tid; t < COV_NB * COV_NB; t += COV_THREADS) Li[t / COV_NB][t % COV_NB] = Linv[(size_t)p * COV_NB * COV_NB + t];
+    for (int t = tid; t < COV_NB * COV_COLS; t += COV_THREADS) {
+      const int r = t / COV_COLS;
+      Bk[r][t % COV_COLS] = r < nb ? Xw[(size_t)(k + r) * COV_COLS + (t % COV_COLS)] : 0.0;
+    }
+    __syncthreads();
+    cov_v4d acc = {0.0, 0.0, 0.0, 0.0};
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int s = 0; s < COV_NB / 4; s++)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Li[4 * s + kq][16 * wave + l16], Bk[4 * s + kq][l16], acc, 0, 0, 0);
+    }
+    __syncthreads();
+    if (wave < COV_NB / 16) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int r = 16 * wave + kq + 4 * q;
+        Bk[r][l16] = acc[q];
+        if (r < nb) Xw[(size_t)(k + r) * COV_COLS + l16] = acc[q];
+      }
+    }
+    __syncthreads();
+    for (int c0 = cbeg; c0 < k; c0 += COV_CHUNK) {
+      for (int t = tid; t < COV_NB * COV_CHUNK; t += COV_THREADS) {
+        const int r = t / COV_CHUNK, c = t % COV_CHUNK, i = k + r, j = c0 + c;
+        stage[r * COV_LQ + c] = (r < nb && j < k && i - j <= bw) ? L[(size_t)i * ld + j] : 0.0;
+      }
+      __syncthreads();
+      const int cc0 = c0 + 16 * wave;
+      if (cc0 < k) {
+        cov_v4d a2 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < COV_NB / 4; s++)
+          a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(stage[(4 * s + kq) * COV_LQ + 16 * wave + l16], Bk[4 * s + kq][l16], a2, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int r = cc0 + kq + 4 * q;
+          if (r < k) Xw[(size_t)r * COV_COLS + l16] -= a2[q];
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // pose block of the camera at position q of Q (free index q_free[q], right-hand sides 6 q .. 6 q + 5): the diagonal
 // block of X, symmetrised (X = S^-1 is symmetric up to rounding; (a + b) / 2 is the same number both ways round)
 __global__ void ba_cov_pose_kernel(int n, int nQ, const int* __restrict__ q_free, const double* __restrict__ X,
@@ -586,6 +717,16 @@ int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double*
   static_assert(COV_COLS == 16, "vsl_cov_x_at (vsl_common.h) spells the block width out");
   if (nblk <= 0) return VSL_OK;
   hipLaunchKernelGGL(ba_cov_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, L, Linv, Sdiag, col_unk, X, ok_dev);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_cov_band_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, int ld, int bw, const double* Linv, const int* col_unk,
+                                  const int* row_lo, int nblk, double* X, const int* ok_dev) {
+  if (nblk <= 0 || n <= 0) return VSL_OK;
+  if (bw < 0 || ld != bw + COV_NB) return vsl_fail(ctx, VSL_ERR_INVALID, "band unit columns: half bandwidth %d, leading dimension %d", bw, ld);
+  hipLaunchKernelGGL(cov_band_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, L + ld, ld, bw, Linv, col_unk, row_lo,
+                     X, ok_dev);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }

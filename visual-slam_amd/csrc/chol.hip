@@ -1847,6 +1847,10 @@ int vsl_chol_selinv_band_dev(vsl_ctx* ctx, double* S, double* Z, int n, int ld, 
   return VSL_OK;
 }
 
+const double* vsl_chol_selinv_linv_dev(vsl_ctx* ctx, int n, int bw) {
+  return (const double*)ctx->dscratch + chol_selinv_plan(n, bw, ctx->chol_no_fused).Linv;
+}
+
 // Test / diagnostic entry point (include/vslam_hip.h): S from the host into band storage -- a cyclic band folded into a
 // linear one first (chol_fold_plan) --, the band of the inverse back into a dense n x n array; or the full inverse by
 // the dense factor and one solve per unit column where the band is the whole matrix.

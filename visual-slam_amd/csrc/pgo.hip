@@ -16,6 +16,7 @@
 #include "vsl_common.h"
 #include "lm_policy.h"
 #include "dev_arena.h"
+#include "pgo_cov_plan.h"
 
 namespace {
 
@@ -981,4 +982,276 @@ extern "C" int vsl_pgo_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, con
   if (storage) *storage = ran;
   for (int q = 0; q < n_q; q++) memcpy(cov + 36 * (size_t)q, blocks.data() + 36 * (size_t)slot[q], 36 * sizeof(double));
   return VSL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// vsl_pgo_joint_covariance / vsl_pgo_edge_consistency: the 12 x 12 joint covariance of pairs of nodes and, on top of it,
+// the covariance and the chi-square of a candidate edge's residual (include/vslam_hip.h has the definitions).  The
+// host plan -- validation, the fold, the class of each pair, the column nodes, the arena -- is pgo_cov_plan.h.  The
+// chain is vsl_pgo_covariance's up to the inverse, then
+//   route 0     unit columns of every distinct queried free node (ba_cov.hip's dense solve)
+//   routes 1, 2 selected inversion and pivot test; for the PGC_SOLVE pairs the band unit-column solve
+//               (vsl_cov_band_unit_columns_dev) with the inverted diagonal blocks the inversion left in its scratch
+//   pgo_joint_blocks_kernel       one thread per entry of a 12 x 12 block
+//   pgo_edge_consistency_kernel   one wavefront per candidate (the edge call only)
+// vsl_pgo_covariance and the solver are not touched by any of it.
+namespace {
+
+// One entry per thread.  Diagonal blocks: the rule of vsl_pgo_covariance on the same route, bit for bit (band: entry
+// (max, min) of Z; dense: the two mirror entries of the node's own columns averaged).  Cross block, entry (row r of node
+// x, column c of node y): with columns for both nodes the average of X_y[6 x + r][c] and X_x[6 y + c][r]; with columns
+// for one of them that single entry; with none entry (max, min) of Z.  Every rule gives (x, r; y, c) and (y, c; x, r)
+// the same number: the block is symmetric and a swapped pair is the swapped, transposed block.
+__global__ void pgo_joint_blocks_kernel(int n, int n_pairs, const PgcPairDev* __restrict__ pairs, int band, const double* __restrict__ Z,
+                                        int ld, const double* __restrict__ X, const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 144 * n_pairs || !*ok) return;
+  const PgcPairDev p = pairs[t / 144];
+  const int I = (t % 144) / 12, J = t % 12;
+  const int fx = I < 6 ? p.fa : p.fb, fy = J < 6 ? p.fa : p.fb;
+  const int cx = I < 6 ? p.ca : p.cb, cy = J < 6 ? p.ca : p.cb;
+  const int r = I % 6, c = J % 6;
+  double v = 0.0;
+  if (fx >= 0 && fy >= 0) {
+    const int i = 6 * fx + r, j = 6 * fy + c;
+    const bool cols = !(band && fx == fy) && (cx >= 0 || cy >= 0);
+    if (!cols)
+      v = Z[(size_t)max(i, j) * (ld + 1) + ld - (max(i, j) - min(i, j))];
+    else if (cx >= 0 && cy >= 0)
+      v = 0.5 * (X[vsl_cov_x_at(n, i, cy + c)] + X[vsl_cov_x_at(n, j, cx + r)]);
+    else if (cy >= 0)
+      v = X[vsl_cov_x_at(n, i, cy + c)];
+    else
+      v = X[vsl_cov_x_at(n, j, cx + r)];
+  }
+  out[t] = v;
+}
+
+// One wavefront per candidate.  Lane 0 evaluates r and both Jacobian blocks with the dual numbers of
+// pgo_linearize_kernel (seed_pose, edge_residual; no corrector); the lanes share T = Sigma J^T (12 x 6) and M = J T
+// (6 x 6), every sum in ascending index order; Sigma_r = (M + M^T) / 2; lane 0 factors Sigma_r + Sigma_m and solves.
+__global__ __launch_bounds__(64) void pgo_edge_consistency_kernel(int n_cand, const double* __restrict__ poses,
+                                                                  const PgcPairDev* __restrict__ pairs, const double* __restrict__ meas,
+                                                                  const double* __restrict__ meas_cov, const double* __restrict__ joint,
+                                                                  const int* __restrict__ ok, double* __restrict__ resid,
+                                                                  double* __restrict__ resid_cov, double* __restrict__ chi2) {
+  __shared__ double Jm[6][12], Tm[12][6], Mm[6][6], rs[6];
+  const int q = blockIdx.x, lane = threadIdx.x;
+  if (q >= n_cand || !*ok) return;
+  const PgcPairDev p = pairs[q];
+  if (lane == 0) {
+    D12 qc[4], tc[3], qn[4], tn[3], rd[6];
+    seed_pose(poses + 7 * (size_t)p.na, 0, qc, tc);
+    seed_pose(poses + 7 * (size_t)p.nb, 6, qn, tn);
+    edge_residual(qc, tc, qn, tn, meas + 6 * (size_t)q, rd);
+    for (int i = 0; i < 6; i++) {
+      rs[i] = rd[i].v;
+      resid[6 * (size_t)q + i] = rd[i].v;
+      // a fixed node does not move: its term is dropped
+      for (int c = 0; c < 6; c++) {
+        Jm[i][c] = p.fa >= 0 ? rd[i].d[c] : 0.0;
+        Jm[i][6 + c] = p.fb >= 0 ? rd[i].d[6 + c] : 0.0;
+      }
+    }
+  }
+  __syncthreads();
+  const double* S = joint + 144 * (size_t)q;
+  for (int t = lane; t < 72; t += 64) {
+    const int a = t / 6, i = t % 6;
+    double s = 0.0;
+    for (int b = 0; b < 12; b++) s += S[12 * a + b] * Jm[i][b];
+    Tm[a][i] = s;
+  }
+  __syncthreads();
+  if (lane < 36) {
+    const int i = lane / 6, j = lane % 6;
+    double s = 0.0;
+    for (int a = 0; a < 12; a++) s += Jm[i][a] * Tm[a][j];
+    Mm[i][j] = s;
+  }
+  __syncthreads();
+  if (lane < 36) {
+    const int i = lane / 6, j = lane % 6;
+    resid_cov[36 * (size_t)q + lane] = 0.5 * (Mm[i][j] + Mm[j][i]);
+  }
+  if (lane == 0) {
+    double A[6][6], y[6];
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) {
+        A[i][j] = 0.5 * (Mm[i][j] + Mm[j][i]);
+        if (meas_cov) A[i][j] += 0.5 * (meas_cov[36 * (size_t)q + 6 * i + j] + meas_cov[36 * (size_t)q + 6 * j + i]);
+      }
+    bool pd = true;
+    double c2 = 0.0;
+    for (int j = 0; j < 6 && pd; j++) {
+      double d = A[j][j];
+      for (int k = 0; k < j; k++) d -= A[j][k] * A[j][k];
+      if (!(d > 0.0) || !isfinite(d)) {
+        pd = false;
+        break;
+      }
+      const double l = sqrt(d);
+      A[j][j] = l;
+      for (int i = j + 1; i < 6; i++) {
+        double s = A[i][j];
+        for (int k = 0; k < j; k++) s -= A[i][k] * A[j][k];
+        A[i][j] = s / l;
+      }
+      double s = rs[j];
+      for (int k = 0; k < j; k++) s -= A[j][k] * y[k];
+      y[j] = s / l;
+      c2 += y[j] * y[j];
+    }
+    chi2[q] = pd ? c2 : __builtin_nan("");
+  }
+}
+
+struct PgoJointCall {
+  const char* name;
+  const int32_t *a, *b;
+  int n_pairs;
+  bool with_cand;
+  const double *cand_meas, *meas_cov;                // the edge call (meas_cov nullable)
+  double *cov, *resid, *resid_cov, *chi2;            // outputs (cov: the joint call; chi2 nullable)
+};
+
+// everything behind the validation; host_in / host_out are read / written by copies on the stream
+int pgo_joint_run(vsl_ctx* ctx, const vsl_pgo_problem* run, const vsl_ba_options* opt, bool folded, const PgoJointCall& c,
+                  const vsl_pgo_problem* orig, std::vector<char>& host_in, std::vector<char>& host_out, bool* dense_out) {
+  int nf = 0;
+  const std::vector<int> run_free = pgo_free_index(run, &nf);
+  PgoState st;
+  st.linear_only = folded;
+  {
+    PgoState probe;
+    probe.linear_only = folded;
+    pgo_storage(ctx, run, run_free, nf, probe);
+    st.bw = probe.bw;
+    st.ld = probe.ld;
+  }
+  const bool dense = st.ld == 0;
+  *dense_out = dense;
+  // (the plan numbers the nodes from the caller's graph: the fold is its own)
+  const PgcPlan P = pgc_plan(orig->n_nodes, orig->node_fixed, folded, dense, st.bw, ctx->pgo_cov_no_band_read, c.a, c.b, c.n_pairs,
+                             c.with_cand);
+  st.extra_bytes = P.total;
+  int rc;
+  if ((rc = pgo_setup(ctx, run, st))) return rc;
+  if ((st.ld == 0) != dense || st.n != P.n) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: the set-up and the plan disagree", c.name);
+  hipStream_t s = ctx->stream;
+  const int n = st.n, np = c.n_pairs;
+  char* dev = st.extra;
+  host_in.assign(P.in_bytes, 0);
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes) memcpy(host_in.data() + off, src, bytes);
+  };
+  put(P.off_pairs, P.pairs.data(), sizeof(PgcPairDev) * P.pairs.size());
+  put(P.off_col_unk, P.col_unk.data(), sizeof(int) * P.col_unk.size());
+  put(P.off_row_lo, P.row_lo.data(), sizeof(int) * P.row_lo.size());
+  if (c.with_cand) {
+    put(P.off_meas, c.cand_meas, sizeof(double) * 6 * (size_t)np);
+    if (c.meas_cov) put(P.off_meas_cov, c.meas_cov, sizeof(double) * 36 * (size_t)np);
+  }
+  VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), P.in_bytes, hipMemcpyHostToDevice, s));
+  const PgcPairDev* pairs = (const PgcPairDev*)(dev + P.off_pairs);
+  const int* col_dev = (const int*)(dev + P.off_col_unk);
+  double* Hdiag = (double*)(dev + P.off_Hdiag);
+  double* X = (double*)(dev + P.off_X);
+  double* out = (double*)(dev + P.out_off + P.off_cov);
+  // unit scale, one linearisation at the poses as they are: vsl_pgo_covariance's H
+  VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)n, s));
+  hipLaunchKernelGGL(pgo_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.colsq, st.scale);
+  double cost = 0;
+  if ((rc = pgo_linearize(ctx, st, opt, false, &cost))) return rc;
+  hipLaunchKernelGGL(pgo_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.H, st.ld, Hdiag);
+  VSL_CHECK_LAUNCH(ctx);
+  if (dense) {
+    double* Linv = (double*)(dev + P.off_Linv);
+    if ((rc = vsl_chol_factor_dev(ctx, st.H, n, st.flag, Linv))) return rc;
+    if ((rc = vsl_cov_unit_columns_dev(ctx, n, st.H, Linv, Hdiag, col_dev, P.nblk, X, st.flag))) return rc;
+  } else {
+    if ((rc = vsl_chol_selinv_band_dev(ctx, st.H + st.ld, st.A + st.ld, n, st.ld, st.bw, st.flag))) return rc;
+    if ((rc = vsl_cov_band_pivot_dev(ctx, n, st.H, st.ld, Hdiag, st.flag))) return rc;
+    if ((rc = vsl_cov_band_unit_columns_dev(ctx, n, st.H, st.ld, st.bw, vsl_chol_selinv_linv_dev(ctx, n, st.bw), col_dev,
+                                            (const int*)(dev + P.off_row_lo), P.nblk, X, st.flag)))
+      return rc;
+  }
+  hipLaunchKernelGGL(pgo_joint_blocks_kernel, dim3((144 * np + 255) / 256), dim3(256), 0, s, n, np, pairs, dense ? 0 : 1, st.A, st.ld, X,
+                     st.flag, out);
+  if (c.with_cand)
+    hipLaunchKernelGGL(pgo_edge_consistency_kernel, dim3(np), dim3(64), 0, s, np, st.poses, pairs, (const double*)(dev + P.off_meas),
+                       c.meas_cov ? (const double*)(dev + P.off_meas_cov) : (const double*)nullptr, out, st.flag,
+                       (double*)(dev + P.out_off + P.off_resid), (double*)(dev + P.out_off + P.off_resid_cov),
+                       (double*)(dev + P.out_off + P.off_chi2));
+  VSL_CHECK_LAUNCH(ctx);
+  int ok = 0;
+  host_out.assign(P.out_bytes, 0);
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, s));
+  VSL_HIP(ctx, hipMemcpyAsync(&ok, st.flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  VSL_HIP(ctx, hipStreamSynchronize(s));
+  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: the normal equations are not positive definite (no fixed node, or a free node without an edge)", c.name);
+  if (c.cov) memcpy(c.cov, host_out.data() + P.off_cov, sizeof(double) * 144 * (size_t)np);
+  if (c.with_cand) {
+    memcpy(c.resid, host_out.data() + P.off_resid, sizeof(double) * 6 * (size_t)np);
+    memcpy(c.resid_cov, host_out.data() + P.off_resid_cov, sizeof(double) * 36 * (size_t)np);
+    if (c.chi2) memcpy(c.chi2, host_out.data() + P.off_chi2, sizeof(double) * (size_t)np);
+  }
+  return VSL_OK;
+}
+
+int pgo_joint_call(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const PgoJointCall& c, int* storage) {
+  int rc = pgo_validate(ctx, prob);
+  if (rc) return rc;
+  if (!opt || c.n_pairs < 0 ||
+      (c.n_pairs > 0 && (!c.a || !c.b || (c.with_cand ? (!c.cand_meas || !c.resid || !c.resid_cov) : !c.cov))))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null argument or negative count", c.name);
+  int bad = 0;
+  switch (pgc_check_pairs(prob->n_nodes, prob->node_fixed, c.a, c.b, c.n_pairs, &bad)) {
+    case PGC_PAIR_RANGE: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d (%d, %d): node out of range", c.name, bad, c.a[bad], c.b[bad]);
+    case PGC_PAIR_SAME: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d names node %d twice", c.name, bad, c.a[bad]);
+    case PGC_PAIR_BOTH_FIXED: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d (%d, %d): both nodes are fixed", c.name, bad, c.a[bad], c.b[bad]);
+    default: break;
+  }
+  int nf = 0;
+  const std::vector<int> free_idx = pgo_free_index(prob, &nf);
+  int route;
+  {
+    PgoState probe;
+    pgo_storage(ctx, prob, free_idx, nf, probe);
+    route = probe.ld > 0 ? (probe.cyclic ? 2 : 1) : 0;
+  }
+  if (storage) *storage = route;
+  if (c.n_pairs == 0) return VSL_OK;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<char> host_in, host_out;
+  PgoFolded F;
+  const vsl_pgo_problem* run = prob;
+  if (route == 2) {
+    pgo_fold_problem(prob, free_idx, nf, F);
+    run = &F.prob;
+  }
+  bool dense = false;
+  rc = pgo_joint_run(ctx, run, opt, route == 2, c, prob, host_in, host_out, &dense);
+  if (rc) {
+    (void)hipStreamSynchronize(ctx->stream);  // queued copies read host buffers that end here
+    return rc;
+  }
+  if (storage) *storage = dense ? 0 : route;
+  return VSL_OK;
+}
+}  // namespace
+
+extern "C" int vsl_pgo_joint_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* pair_a,
+                                        const int32_t* pair_b, int n_pairs, double* cov, int* storage) {
+  if (!ctx) return VSL_ERR_INVALID;
+  const PgoJointCall c{"vsl_pgo_joint_covariance", pair_a, pair_b, n_pairs, false, nullptr, nullptr, cov, nullptr, nullptr, nullptr};
+  return pgo_joint_call(ctx, prob, opt, c, storage);
+}
+
+extern "C" int vsl_pgo_edge_consistency(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* cand_a,
+                                        const int32_t* cand_b, const double* cand_meas, const double* meas_cov, int n_cand,
+                                        double* resid, double* resid_cov, double* chi2, int* storage) {
+  if (!ctx) return VSL_ERR_INVALID;
+  const PgoJointCall c{"vsl_pgo_edge_consistency", cand_a, cand_b, n_cand, true, cand_meas, meas_cov, nullptr, resid, resid_cov, chi2};
+  return pgo_joint_call(ctx, prob, opt, c, storage);
 }

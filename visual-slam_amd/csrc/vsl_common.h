@@ -89,7 +89,8 @@ struct vsl_ctx {
   bool chol_one_ended = false;          // diagnostic: narrow-band Cholesky by one workgroup from the top only (no two-ended split)
   bool chol_no_fused = false;           // diagnostic: band Cholesky as one launch per panel step instead of the fused single-launch kernel
   bool ba_force_dense = false;          // diagnostic: dense reduced camera system even where the band form applies
-  bool ba_schur_atomics = false;        // diagnostic: large-system Schur complement by fp64 atomics (one wavefront per landmark) instead of the per-block gather
+  bool pgo_cov_no_band_read = false;    // diagnostic: vsl_pgo_joint_covariance / vsl_pgo_edge_consistency solve unit columns for in-band pairs too instead of reading the band of the inverse
+  bool ba_schur_atomics = false;       // diagnostic: large-system Schur complement by fp64 atomics (one wavefront per landmark) instead of the per-block gather
   bool ba_no_fused = false;             // diagnostic: local windows by the operator-by-operator kernels of ba.hip instead of the fused iteration (ba_fused.hip)
   bool ba_schur_entries = false;        // diagnostic: single-entry ownership in the small-system Schur kernel instead of 3 x 3 sub-blocks
   int describe_tile_min_images = 96;   // describe launches of at least this many images use the shared-tile kernel (measured break-even ~64 images; diagnostic: 1 forces it, 0 disables it)
@@ -218,6 +219,10 @@ int vsl_chol_factor_dev(vsl_ctx* ctx, double* S, int n, int* ok_dev, double* Lin
 // place; Z receives every entry (i, j), 0 <= i - j <= bw, of S^-1 and zeros in all other slots.  *ok_dev = 0 (and Z
 // undefined) if S is not positive definite by the factorisation's own pivot test.  Enqueued on the context's stream.
 int vsl_chol_selinv_band_dev(vsl_ctx* ctx, double* S, double* Z, int n, int ld, int bw, int* ok_dev);
+// The inverted VSL_CHOL_NB x VSL_CHOL_NB diagonal blocks of L (one per panel, identity-padded) that the last
+// vsl_chol_selinv_band_dev(n, bw) on this context left in the context's device scratch: valid in stream order until the
+// next call that takes that scratch (any band / ring solve or selected inversion).
+const double* vsl_chol_selinv_linv_dev(vsl_ctx* ctx, int n, int bw);
 // Columns of the inverse of a DENSE factor (ba_cov.hip: the solve behind vsl_ba_covariance): L L^T X = E for the unit
 // columns col_unk[0 .. 16 nblk) (device; -1: an empty column), sixteen per workgroup.  X: nblk blocks of n x 16 doubles,
 // entry (row i, column j) at vsl_cov_x_at(n, i, j).  L, Linv: what vsl_chol_factor_dev left.  Sdiag (nullable): diag S
@@ -229,6 +234,12 @@ int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double*
 // pivot: the factor left by vsl_chol_selinv_band_dev against diag S before the factorisation -- a pivot L_ii^2 <=
 // 2^-36 Sdiag_i clears *ok_dev.  blocks: out[36 q ..] = the diagonal 6 x 6 block of camera / node q_free[q] (device),
 // lower triangle mirrored; nothing written when *ok_dev = 0.
+// unit columns: L L^T X = E against the band factor for the unit columns col_unk[0 .. 16 nblk) (device; -1: an empty
+// column), sixteen per workgroup, X as for vsl_cov_unit_columns_dev -- entries of the inverse outside the band.  Linv:
+// vsl_chol_selinv_linv_dev.  row_lo (device, nullable = 0): per block the lowest row a caller reads; the rows above its
+// 32-row panel are left unwritten.  Nothing is written when *ok_dev = 0: run it behind the pivot test.
+int vsl_cov_band_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, int ld, int bw, const double* Linv, const int* col_unk,
+                                  const int* row_lo, int nblk, double* X, const int* ok_dev);
 int vsl_cov_band_pivot_dev(vsl_ctx* ctx, int n, const double* L, int ld, const double* Sdiag, int* ok_dev);
 int vsl_cov_band_blocks_dev(vsl_ctx* ctx, int nQ, const int* q_free, const double* Z, int ld, const int* ok_dev, double* out);
 __host__ __device__ inline size_t vsl_cov_x_at(int n, int i, int col) {
