@@ -311,6 +311,16 @@ int vsl_frames_download_candidate_counts(vsl_ctx* ctx, vsl_frames* f, int n_imag
  * on; the GPU tests run the whole range). */
 int vsl_diag_sqrt_check(vsl_ctx* ctx, uint32_t lo_bits, uint32_t hi_bits, unsigned long long* n_mismatch);
 
+/* Diagnostic: describe GIVEN corners.  Slot first + i gets counts[i] (<= cap <= max_features) corners from
+ * corners_xy[i][cap][2] (pixels, inside the image) and the range is described like the second half of
+ * vsl_frames_detect_describe (the diagnostic knobs choose the kernel).  Returned is what the kernels left BEFORE the
+ * host's near-tie resolution: moments[i][cap][2] = (m01, m10) per corner, the raw near-tie word in *n_ties (count, with
+ * the exact-list overflow flag in bit 30) and the first tie_rec_cap records (slot, keypoint, bit, 0), in no particular
+ * order.  The launch stays pending: vsl_frames_resolve_ties / vsl_frames_download_keypoints finish it as usual. */
+int vsl_diag_frames_describe_at(vsl_ctx* ctx, vsl_frames* f, int first, int n, const int32_t* corners_xy,
+                                const int32_t* counts, int cap, int rotate_features, int32_t* moments,
+                                int32_t* tie_rec, int tie_rec_cap, int* n_ties);
+
 /* ------------------------------------------------ device-resident map (per-frame tracking) */
 /*
  * The single-stream path: what project_landmarks + find_matches_landmarks (include/visnav/vo_utils.h:48-167)

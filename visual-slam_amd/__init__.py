@@ -865,6 +865,26 @@ class Frames:
         self.ctx._ck(self.ctx.L.vsl_frames_detect_describe(self.ctx.h, self.h, int(first), int(n),
                                                            int(num_features), int(rotate)))
 
+    def describe_at(self, first, corners, rotate=True, tie_rec_cap=4096):
+        """Diagnostic (vsl_diag_frames_describe_at): describe the given integer corners -- one (k, 2) array per slot from
+        `first` on -- and return (moments per slot as (k, 2) arrays of (m01, m10), raw near-tie word, tie records (m, 4))
+        as the kernels left them; resolve_ties() / keypoints() finish the launch as after detect_describe."""
+        corners = [np.ascontiguousarray(c, np.int32).reshape(-1, 2) for c in corners]
+        n, cap = len(corners), max(1, max(len(c) for c in corners))
+        xy = np.zeros((n, cap, 2), np.int32)
+        for i, c in enumerate(corners):
+            xy[i, :len(c)] = c
+        counts = np.array([len(c) for c in corners], np.int32)
+        mom = np.zeros((n, cap, 2), np.int32)
+        rec = np.zeros((max(1, tie_rec_cap), 4), np.int32)
+        nt = C.c_int32()
+        self.ctx._ck(self.ctx.L.vsl_diag_frames_describe_at(self.ctx.h, self.h, int(first), n, xy.ctypes.data_as(i32p),
+                                                            counts.ctypes.data_as(i32p), cap, int(rotate),
+                                                            mom.ctypes.data_as(i32p), rec.ctypes.data_as(i32p),
+                                                            int(tie_rec_cap), C.byref(nt)))
+        n_rec = min(nt.value & ((1 << 30) - 1), tie_rec_cap)
+        return [mom[i, :len(c)].copy() for i, c in enumerate(corners)], nt.value, rec[:n_rec].copy()
+
     def resolve_ties(self):
         n = C.c_int32()
         self.ctx._ck(self.ctx.L.vsl_frames_resolve_ties(self.ctx.h, self.h, C.byref(n)))

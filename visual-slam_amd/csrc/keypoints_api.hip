@@ -61,6 +61,39 @@ extern "C" int vsl_frames_exact_fallbacks(const vsl_frames* f) {
   return f ? f->exact_fallbacks : VSL_ERR_INVALID;
 }
 
+extern "C" int vsl_diag_frames_describe_at(vsl_ctx* ctx, vsl_frames* f, int first, int n, const int32_t* corners_xy,
+                                           const int32_t* counts, int cap, int rotate_features, int32_t* moments,
+                                           int32_t* tie_rec, int tie_rec_cap, int* n_ties) {
+  if (!ctx || !f || first < 0 || n < 1 || first + n > f->max_images || !corners_xy || !counts || cap < 1 || cap > f->F ||
+      !moments || tie_rec_cap < 0 || (tie_rec_cap > 0 && !tie_rec) || !n_ties)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_diag_frames_describe_at: bad arguments");
+  for (int i = 0; i < n; i++)
+    if (counts[i] < 0 || counts[i] > cap) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_diag_frames_describe_at: count %d of image %d", counts[i], i);
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = vsl_resolve_ties(ctx, f, nullptr);  // nothing of an earlier launch may be left in the records
+  if (rc) return rc;
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < n; i++) {
+    const size_t base = (size_t)(first + i) * f->F;
+    if (counts[i] > 0)
+      VSL_HIP(ctx, hipMemcpy(f->kp_xy + 2 * base, corners_xy + 2 * (size_t)i * cap, sizeof(int32_t) * 2 * counts[i], hipMemcpyHostToDevice));
+  }
+  VSL_HIP(ctx, hipMemcpy(f->kp_count + first, counts, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  if ((rc = vsl_launch_describe(ctx, f, first, n, rotate_features, 0))) return rc;
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int32_t cnt = 0;
+  VSL_HIP(ctx, hipMemcpy(&cnt, f->tie_count, sizeof(cnt), hipMemcpyDeviceToHost));
+  *n_ties = cnt;  // the raw word: the overflow flag (VSL_TIE_OVERFLOW_FLAG) rides it
+  const int n_rec = std::min(std::min((int)(cnt & (int32_t)(VSL_TIE_OVERFLOW_FLAG - 1)), f->tie_cap), tie_rec_cap);
+  if (n_rec > 0) VSL_HIP(ctx, hipMemcpy(tie_rec, f->tie_rec, sizeof(int32_t) * 4 * n_rec, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) {
+    const size_t base = (size_t)(first + i) * f->F;
+    if (counts[i] > 0)
+      VSL_HIP(ctx, hipMemcpy(moments + 2 * (size_t)i * cap, f->kp_moments + 2 * base, sizeof(int32_t) * 2 * counts[i], hipMemcpyDeviceToHost));
+  }
+  return VSL_OK;
+}
+
 static int check_image(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch) {
   if (!ctx) return VSL_ERR_INVALID;
   if (!img || w < 40 || h < 40 || pitch < (size_t)w)
