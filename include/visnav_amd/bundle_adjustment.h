@@ -272,6 +272,24 @@ inline void global_bundle_adjustment(const Corners& feature_corners, const Globa
                     options.verbosity_level, fixed_cameras, calib_cam, cameras, landmarks);
 }
 
+// global_bundle_adjustment by the matrix-free PCG on the reduced camera system (iterative Schur, include/vslam_hip.h:
+// what ceres::ITERATIVE_SCHUR is to SPARSE_SCHUR) -- for maps whose cameras do not order into a narrow band.  Sets the
+// context's "ba_iterative_schur" diagnostic for the call and puts it back as it found it, also when the call throws.
+// Single GPU: with VISNAV_AMD_WORLD > 1 the call fails (VSL_ERR_INVALID) on every rank alike.
+inline void global_bundle_adjustment_iterative(const Corners& feature_corners, const GlobalBundleAdjustmentOptions& options,
+                                               const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam,
+                                               Cameras& cameras, Landmarks& landmarks) {
+  struct Restore {
+    int was = 0;
+    Restore() {
+      amd::check(vsl_ctx_get_diagnostic(amd::ctx(), "ba_iterative_schur", &was), "global_bundle_adjustment_iterative");
+      amd::check(vsl_ctx_set_diagnostic(amd::ctx(), "ba_iterative_schur", 1), "global_bundle_adjustment_iterative");
+    }
+    ~Restore() { (void)vsl_ctx_set_diagnostic(amd::ctx(), "ba_iterative_schur", was); }
+  } restore;
+  global_bundle_adjustment(feature_corners, options, fixed_cameras, calib_cam, cameras, landmarks);
+}
+
 // Marginal covariances of the map that global_bundle_adjustment works on (vsl_global_ba_covariance): the contract of
 // bundle_adjustment_covariance above, on ALL observations of the landmarks (the flattening of global_bundle_adjustment),
 // with the reduced camera system of a large map kept in band storage.  storage_out (nullable): 0 = the dense route of

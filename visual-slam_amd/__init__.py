@@ -175,7 +175,7 @@ class Context:
     def last_ba_layout(self):
         """(doubles of S, band form, bandwidth) of the last general-path bundle adjustment set up on this context; band form
         0 = dense, 1 = band (cameras in reverse Cuthill-McKee order), 2 = cyclic band (cameras as they came, the band
-        closes around the loop)."""
+        closes around the loop), 3 = matrix-free (iterative Schur: no S, 0 doubles)."""
         e, b, w = C.c_int64(), C.c_int(), C.c_int()
         self._ck(self.L.vsl_ctx_last_ba_layout(self.h, C.byref(e), C.byref(b), C.byref(w)))
         return e.value, b.value, w.value
@@ -560,6 +560,43 @@ class Context:
                                          S.ctypes.data_as(f64p), g.ctypes.data_as(f64p), C.byref(cost),
                                          C.byref(nf)))
         return S, g, cost.value
+
+    def ba_schur_apply(self, arr, x, use_huber=True, huber=1.0):
+        """y = S x with the reduced camera system S of ba_linearize, never formed (vsl_ba_schur_apply)."""
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        nf = int((arr.cam_fixed == 0).sum())
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+        if len(x) != 6 * nf:
+            raise ValueError("x has %d entries, the problem %d unknowns" % (len(x), 6 * nf))
+        y = np.zeros(6 * nf)
+        self._ck(self.L.vsl_ba_schur_apply(self.h, C.byref(st), C.byref(o), x.ctypes.data_as(f64p), y.ctypes.data_as(f64p),
+                                           C.c_int(nf)))
+        return y
+
+    def ba_schur_pcg(self, arr, b=None, tol=1e-8, max_iterations=None, use_huber=True, huber=1.0):
+        """Solves S x = b (b None: g of ba_linearize) by the matrix-free block-Jacobi PCG (vsl_ba_schur_pcg).
+        max_iterations None: 4 n.  Returns (x, iterations, rel_residual)."""
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * int((arr.cam_fixed == 0).sum())
+        if b is not None:
+            b = np.ascontiguousarray(b, np.float64).reshape(-1)
+            if len(b) != n:
+                raise ValueError("b has %d entries, the problem %d unknowns" % (len(b), n))
+        x = np.zeros(n)
+        it, rel = C.c_int(0), C.c_double(0.0)
+        self._ck(self.L.vsl_ba_schur_pcg(self.h, C.byref(st), C.byref(o), None if b is None else b.ctypes.data_as(f64p),
+                                         C.c_double(float(tol)), C.c_int(4 * n if max_iterations is None else int(max_iterations)),
+                                         x.ctypes.data_as(f64p), C.byref(it), C.byref(rel)))
+        return x, it.value, rel.value
+
+    def last_ba_pcg(self):
+        """(solves, iterations_total, iterations_last, rel_residual_last) of the matrix-free route in the last
+        general-path bundle adjustment set up on this context; zeros when it did not take the route."""
+        s, t, l, r = C.c_int64(), C.c_int64(), C.c_int(), C.c_double()
+        self._ck(self.L.vsl_ctx_last_ba_pcg(self.h, C.byref(s), C.byref(t), C.byref(l), C.byref(r)))
+        return s.value, t.value, l.value, r.value
 
     def ba_covariance(self, arr, cams=None, lms=None, use_huber=True, huber=1.0):
         """Marginal covariances at arr's poses / points (vsl_ba_covariance; nothing is optimised).  cams: camera ids

@@ -1293,7 +1293,8 @@ int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p) {
 static BaLayoutSwitches ba_layout_switches(vsl_ctx* ctx, const BaCaller& caller) {
   static const bool env_no_cyclic = getenv("VSL_BA_NO_CYCLIC") != nullptr;
   BaLayoutSwitches sw;
-  sw.allow_band = caller.use == BaUse::HOST_LOOP || caller.use == BaUse::SESSION || caller.use == BaUse::GLOBAL_COVARIANCE;
+  sw.allow_band = (caller.use == BaUse::HOST_LOOP || caller.use == BaUse::SESSION || caller.use == BaUse::GLOBAL_COVARIANCE) &&
+                  !caller.matrix_free;  // (no S: no band order to look for, the cameras keep their own numbering)
   sw.force_dense = ctx->ba_force_dense;
   sw.no_cyclic = ctx->ba_no_cyclic || env_no_cyclic || caller.use == BaUse::GLOBAL_COVARIANCE;
   sw.schur_atomics = ctx->ba_schur_atomics;
@@ -1318,6 +1319,9 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   const ArenaPolicy arena_policy =
       caller.use == BaUse::HOST_LOOP || caller.use == BaUse::COVARIANCE || caller.use == BaUse::GLOBAL_COVARIANCE ? ArenaPolicy::BORROWED
                                                                                                                    : ArenaPolicy::OWNED;
+  ctx->last_pcg_solves = ctx->last_pcg_iterations = 0;  // (read-out of the matrix-free route: vsl_ctx_last_ba_pcg)
+  ctx->last_pcg_iterations_last = 0;
+  ctx->last_pcg_rel_residual = 0.0;
   BaDims& D = st.D;
   D.C = p->n_cams;
   D.L = p->n_lms;
@@ -1331,7 +1335,9 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   BaHostPlan hp;
   size_t extra_bytes = caller.extra_bytes;
   try {
-    hp = ba_host_plan(p, caller.graph_prob, sw, BaPlanLimits{SCH_CMAX, SCH_KMAX, caller.run_max_obs, caller.run_max_lms},
+    // (runs_at_any_size: no system counts as small, so the landmark runs of the recompute form are always cut)
+    hp = ba_host_plan(p, caller.graph_prob, sw,
+                      BaPlanLimits{caller.runs_at_any_size ? 0 : SCH_CMAX, SCH_KMAX, caller.run_max_obs, caller.run_max_lms},
                       [&](const char* what) { tr.lap(what); });
     if (caller.plan_extra) {
       const int rc = caller.plan_extra(caller.plan_extra_self, hp, &extra_bytes);
@@ -1348,16 +1354,28 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   st.ldS = hp.layout.ldS;
   st.offS = hp.layout.offS;
   st.s_elems = hp.layout.s_elems;
-  // (diagnostic read-out for benchmarks: vsl_ctx_last_ba_layout)
-  ctx->last_ba_s_elems = (int64_t)st.s_elems;
-  ctx->last_ba_banded = st.cyclic ? 2 : (st.banded ? 1 : 0);
-  ctx->last_ba_bw = st.bw;
   st.perm = std::move(hp.perm);
   st.small = hp.small;
   // the form of the iteration, BEFORE the arena is planned: only a session runs the recompute form (ba_large.h); "ba_no_fused" /
   // VSL_BA_NO_FUSED keep it on the operator-by-operator chain over stored r / F / E blocks (A/B runs, tests)
   static const bool env_no_fused = getenv("VSL_BA_NO_FUSED") != nullptr;
   st.recompute = caller.use == BaUse::SESSION && ba_recompute_form(hp, ctx->ba_no_fused || env_no_fused, ctx->ba_schur_atomics);
+  st.matrix_free = caller.matrix_free;
+  if (st.matrix_free) {
+    // the matrix-free route works on the Z blocks of the recompute form and on nothing else: no quiet other route
+    if (!st.recompute)
+      return vsl_fail(ctx, VSL_ERR_INVALID,
+                      "bundle adjustment, iterative Schur: needs the recompute form (a free camera, no landmark with more than %d "
+                      "observations, no \"ba_no_fused\" / \"ba_schur_atomics\")", caller.run_max_obs);
+    st.banded = st.cyclic = false;  // S does not exist: no layout
+    st.bw = 0;
+    st.ldS = st.offS = 0;
+    st.s_elems = 0;
+  }
+  // (diagnostic read-out for benchmarks: vsl_ctx_last_ba_layout; 3 = matrix-free)
+  ctx->last_ba_s_elems = (int64_t)st.s_elems;
+  ctx->last_ba_banded = st.matrix_free ? 3 : (st.cyclic ? 2 : (st.banded ? 1 : 0));
+  ctx->last_ba_bw = st.bw;
   BaStored& sb = st.sb;
   BaRecompute& rc = st.rc;
   rc.n_wg = st.recompute ? hp.n_wg : 0;
@@ -1372,7 +1390,7 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   st.cb_seg = D.nfree > 0 ? std::max(1, std::min(32, (int)(D.O / std::max(1, D.nfree) / 512))) : 1;
   rc.bl_seg = st.cb_seg;  // (one workgroup per 256 observations of a camera measured 121 us against 80: more gathers in flight than the L2 holds)
   const size_t nfree = (size_t)D.nfree, pair_elems = std::max<size_t>(hp.n_pairs < ((size_t)1 << 31) ? hp.n_pairs : 1, 1);
-  ArenaPlan plan(56);
+  ArenaPlan plan(66);
   plan.add(st.poses, 7 * C); plan.add(st.points, 3 * L); plan.add(st.intr, 16); plan.add(st.cam_intr, C); plan.add(st.cam_free, C);
   plan.add(st.free_cams, hp.free_cams.size()); plan.add(st.obs_cam, O); plan.add(st.obs_lm, O); plan.add(st.obs_uv, 2 * O);
   plan.add(st.lm_start, L + 1); plan.add(st.cam_start, C + 1); plan.add(st.cam_obs, O);
@@ -1397,9 +1415,11 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
     st.n_slots = st.banded ? D.nfree * st.hbp1 : D.nfree * (D.nfree + 1) / 2;
     st.n_pairs_cap = hp.n_pairs;
     st.pair_l0 = st.pair_lc = -1;
-    plan.add(st.pair_cnt, (size_t)st.n_slots + 1);
-    plan.add(st.pair_start, (size_t)st.n_slots + 1);
-    plan.add(st.pairs, 2 * pair_elems);
+    if (!st.matrix_free) {  // (the matrix-free route gathers nothing: no pair lists)
+      plan.add(st.pair_cnt, (size_t)st.n_slots + 1);
+      plan.add(st.pair_start, (size_t)st.n_slots + 1);
+      plan.add(st.pairs, 2 * pair_elems);
+    }
     plan.add(st.cam_pos, O);
     if (!st.recompute) plan.add(sb.Wg, 18 * O);
     plan.add(st.Yg, 18 * O);
@@ -1410,6 +1430,13 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
     plan.add(rc.pbs, 3 * L);
     plan.add(rc.cam_lm, O);
     plan.add(rc.cam_uv, 2 * O);
+  }
+  if (st.matrix_free) {
+    plan.add(rc.pcg_x, n); plan.add(rc.pcg_r, n); plan.add(rc.pcg_z, n); plan.add(rc.pcg_p, n); plan.add(rc.pcg_q, n);
+    plan.add(rc.pcg_t, 3 * L);
+    plan.add(rc.pcg_part, 6 * nfree * (size_t)rc.bl_seg);
+    plan.add(rc.pcg_minv, 36 * nfree);
+    plan.add(rc.pcg_rec, 1);
   }
   if (caller.use == BaUse::HOST_LOOP) {
     plan.add(sb.r2, 2 * O); plan.add(sb.F2, 12 * O); plan.add(sb.E2, 6 * O); plan.add(sb.n2l2, 3 * L); plan.add(sb.grad_l2, 3 * L);

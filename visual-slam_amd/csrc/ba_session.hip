@@ -36,6 +36,7 @@
 #include "ba_device.h"
 #include "ba_state.h"
 #include "ba_large.h"
+#include "ba_pcg.h"
 
 namespace {
 // ---------------------------------------------------------------------------------------- kernels
@@ -90,7 +91,7 @@ __global__ void sess_add_pack_kernel(int nfree, const double* __restrict__ H, co
   const int n = 6 * nfree;
   if (t < nfree * 36) {
     const int fc = t / 36, x = (t % 36) / 6, y = t % 6;
-    if (!(lower_elems && y > x)) S[(size_t)(6 * fc + x) * ldS + 6 * fc + y] += H[t];
+    if (S && !(lower_elems && y > x)) S[(size_t)(6 * fc + x) * ldS + 6 * fc + y] += H[t];  // (S null: matrix-free, ba_pcg.h)
   }
   if (t < n) {
     const double r = rhs[t] + g_c[t];
@@ -119,7 +120,7 @@ __global__ void sess_damp_kernel(int n, size_t elems, const double* __restrict__
       d = fmin(fmax(packB[elems + n + i], 1e-6), 1e32);
       diag_keep[i] = d;
     }
-    S_eff[(size_t)i * ldS + i] += d * inv_radius;
+    if (S_eff) S_eff[(size_t)i * ldS + i] += d * inv_radius;  // (null: matrix-free, the PCG adds the damping in its product)
     rhs[i] = packB[elems + i];
   }
 }
@@ -189,6 +190,65 @@ struct RecomputeForm {
     return a;
   }
 
+  // ---- the matrix-free route (ba_pcg.h): the operator on this linearisation's H and Z blocks, and one solve
+  BpcgOp pcg_op(const double* diag, double inv_radius) const {
+    BpcgOp a;
+    a.nfree = st.D.nfree;
+    a.nseg = rc.bl_seg;
+    a.free_cams = st.free_cams;
+    a.cam_free = st.cam_free;
+    a.cam_start = st.cam_start;
+    a.cam_lm = rc.cam_lm;
+    a.obs_cam = st.obs_cam;
+    a.cam_pos = st.cam_pos;
+    a.lm_start = st.lm_start;
+    a.wg_lm = rc.wg_lm;
+    a.Z = st.Yg;
+    a.H = st.H;
+    a.diag = diag;
+    a.inv_radius = inv_radius;
+    return a;
+  }
+
+  // y = S v for device vectors (v: n doubles; t and the segment partials are scratch); enqueued
+  int pcg_product(const BpcgOp& a, const BpcgRec* rec, const double* v) {
+    hipLaunchKernelGGL(bpcg_lm_kernel, dim3(rc.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, rec, v, rc.pcg_t);
+    hipLaunchKernelGGL(bpcg_cam_kernel, dim3(a.nfree, a.nseg), dim3(256), 0, ctx->stream, a, rec, (const double*)rc.pcg_t, rc.pcg_part);
+    VSL_CHECK_LAUNCH(ctx);
+    return VSL_OK;
+  }
+
+  // solves S x = b (device, n doubles) into rc.pcg_x: preconditioner, then batches of `poll` enqueued iterations with
+  // one read of the record after each; *h = the record at the end.  Counts the solve in the context's read-out.
+  int pcg_solve(const BpcgOp& a, const double* b, double tol, int max_it, BpcgRec* h) {
+    VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+    const int poll = ba_pcg_poll_of(ctx->ba_pcg_poll);
+    VSL_HIP(ctx, hipMemsetAsync(rc.pcg_rec, 0, sizeof(BpcgRec), ctx->stream));
+    hipLaunchKernelGGL(bpcg_precond_kernel, dim3(a.nfree), dim3(256), 0, ctx->stream, a, rc.pcg_minv, rc.pcg_rec);
+    hipLaunchKernelGGL(bpcg_init_kernel, dim3(1), dim3(BPCG_T), 0, ctx->stream, a.nfree, b, (const double*)rc.pcg_minv, tol, max_it,
+                       rc.pcg_x, rc.pcg_r, rc.pcg_z, rc.pcg_p, rc.pcg_rec);
+    VSL_CHECK_LAUNCH(ctx);
+    const long long max_batches = ba_pcg_max_batches(max_it, poll);
+    for (long long batch = 0;; batch++) {
+      VSL_HIP(ctx, hipMemcpyAsync(h, rc.pcg_rec, sizeof(BpcgRec), hipMemcpyDeviceToHost, ctx->stream));
+      VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      if (h->done || batch >= max_batches) break;
+      for (int k = 0; k < poll; k++) {
+        int e = pcg_product(a, rc.pcg_rec, rc.pcg_p);
+        if (e) return e;
+        hipLaunchKernelGGL(bpcg_step_kernel, dim3(1), dim3(BPCG_T), 0, ctx->stream, a, (const double*)rc.pcg_part,
+                           (const double*)rc.pcg_minv, rc.pcg_x, rc.pcg_r, rc.pcg_z, rc.pcg_p, rc.pcg_q, rc.pcg_rec);
+        VSL_CHECK_LAUNCH(ctx);
+      }
+    }
+    if (!h->done) return vsl_fail(ctx, VSL_ERR_HIP, "iterative Schur: the solve's record never reported an end");
+    ctx->last_pcg_solves++;
+    ctx->last_pcg_iterations += h->iterations;
+    ctx->last_pcg_iterations_last = h->iterations;
+    ctx->last_pcg_rel_residual = ba_pcg_rel_residual(*h);
+    return VSL_OK;
+  }
+
   // once per session: camera-major copies of (landmark, pixel) for bal_cam_kernel
   int prepare() {
     hipLaunchKernelGGL(bal_cam_major_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D.O, st.cam_obs, st.obs_lm, st.obs_uv,
@@ -231,9 +291,11 @@ struct RecomputeForm {
     {
       VslStage s(ctx, VSL_STAGE_BA_SCHUR);
       const BlArgs a = args();
-      VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * st.s_elems, ctx->stream));
-      int e = ba_pair_lists(ctx, st, 0, D.L);
-      if (e) return e;
+      int e;
+      if (!st.matrix_free) {
+        VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * st.s_elems, ctx->stream));
+        if ((e = ba_pair_lists(ctx, st, 0, D.L))) return e;
+      }
       hipLaunchKernelGGL(bal_prep_kernel<false>, dim3(rc.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.cam_pos, 1.0 / radius, st.Yg,
                          st.Pinv, st.bl, rc.pbs, (double*)nullptr, rc.lpart);
       hipLaunchKernelGGL(bal_cam_kernel<false>, dim3(D.nfree, rc.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams, st.cam_start,
@@ -242,13 +304,14 @@ struct RecomputeForm {
                          st.cam_part, st.H, st.g_c, st.rhs, rc.n_wg, rc.lpart, st.scalars, gl);
       VSL_CHECK_LAUNCH(ctx);
       // Y_i W_j^T = Z_i Z_j^T; n <= 128 is solved by ba_chol_small_kernel (full matrix)
-      if ((e = ba_schur_gather(ctx, st, st.Yg, st.Yg, st.banded ? 2 : (D.n > 128 ? 1 : 0)))) return e;
+      if (!st.matrix_free && (e = ba_schur_gather(ctx, st, st.Yg, st.Yg, st.banded ? 2 : (D.n > 128 ? 1 : 0)))) return e;
     }
     // the camera blocks are added together with the packing
     hipLaunchKernelGGL(sess_add_pack_kernel, dim3((D.nfree * 36 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.H, st.g_c,
-                       st.scalars, st.S_eff(), st.rhs, st.ldS, st.banded ? 1 : 0, packB + st.s_elems);
+                       st.scalars, st.matrix_free ? (double*)nullptr : st.S_eff(), st.rhs, st.ldS, st.banded ? 1 : 0,
+                       packB + st.s_elems);
     VSL_CHECK_LAUNCH(ctx);
-    if (!in_place) VSL_HIP(ctx, hipMemcpyAsync(packB, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
+    if (!in_place && !st.matrix_free) VSL_HIP(ctx, hipMemcpyAsync(packB, st.S, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
     return VSL_OK;
   }
 
@@ -256,12 +319,23 @@ struct RecomputeForm {
   // uses (the loop's one read of packC per iteration sees the step as unusable)
   int step(const double* packB, double radius, int refresh, double* packC) {
     const BaDims& D = st.D;
-    if (!in_place) VSL_HIP(ctx, hipMemcpyAsync(st.S, packB, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
+    if (!in_place && !st.matrix_free)
+      VSL_HIP(ctx, hipMemcpyAsync(st.S, packB, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(sess_damp_kernel, dim3((D.n + 255) / 256), dim3(256), 0, ctx->stream, D.n, st.s_elems, packB, 1.0 / radius,
-                       refresh, st.diagc_keep, st.S_eff(), st.ldS, st.rhs, st.flag);  // (sets both flags)
+                       refresh, st.diagc_keep, st.matrix_free ? (double*)nullptr : st.S_eff(), st.ldS, st.rhs, st.flag);  // (sets both flags)
     VSL_CHECK_LAUNCH(ctx);
-    int e = ba_solve_enqueue(ctx, st, true);
-    if (e) return e;
+    int e;
+    if (st.matrix_free) {
+      // dc = -(S^-1 rhs) by the PCG on the same damped, Jacobi-scaled system (same H, Z, rhs, diagonal); a failed pivot or
+      // a breakdown clears flag[1] like a failed factorisation.  The host reads the solve's record once per batch.
+      BpcgRec h;
+      if ((e = pcg_solve(pcg_op(st.diagc_keep, 1.0 / radius), st.rhs, ba_pcg_tol_of_exp(ctx->ba_pcg_tol_exp), ba_pcg_cap(D.n), &h))) return e;
+      hipLaunchKernelGGL(bpcg_finish_kernel, dim3((D.n + 255) / 256), dim3(256), 0, ctx->stream, D.n, rc.pcg_x, rc.pcg_rec, -1.0, st.dc,
+                         st.flag + 1);
+      VSL_CHECK_LAUNCH(ctx);
+    } else if ((e = ba_solve_enqueue(ctx, st, true))) {
+      return e;
+    }
     // candidate (cand_poses, cand_points) from dc, scalars[2..7] as the stored-blocks chain leaves them, packC
     VslStage s(ctx, VSL_STAGE_BA_STEP);
     const BlArgs a = args();
@@ -370,7 +444,8 @@ struct Session {
 };
 
 // sub-problem of the owned landmarks [lm_first, lm_first + lm_count) (all cameras), set-up
-int sess_create(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, int lm_first, int lm_count, Session& s) {
+int sess_create(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, int lm_first, int lm_count, bool matrix_free,
+                Session& s) {
   BaTrace tr;
   BaSubObs own;
   vsl_ba_problem sub = *prob;
@@ -387,7 +462,53 @@ int sess_create(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* 
   s.lm_first = lm_first;
   s.n_lms_total = prob->n_lms;
   // band order from the FULL problem: identical on every rank
-  return ba_setup(ctx, &sub, opt, s.st, BaCaller{BaUse::SESSION, prob, BL_THREADS, BL_LMW});
+  BaCaller caller{BaUse::SESSION, prob, BL_THREADS, BL_LMW};
+  caller.matrix_free = matrix_free;
+  return ba_setup(ctx, &sub, opt, s.st, caller);
+}
+
+// the switch of the matrix-free route: diagnostic "ba_iterative_schur" or the environment variable VSL_BA_ITERATIVE
+bool iterative_schur_on(const vsl_ctx* ctx) {
+  static const bool env_on = getenv("VSL_BA_ITERATIVE") != nullptr;
+  return ctx->ba_iterative_schur || env_on;
+}
+
+// ---- the matrix-free hooks (vsl_ba_schur_apply, vsl_ba_schur_pcg): S of vsl_ba_linearize, never formed
+// set-up and ONE linearisation without Jacobi scaling and without damping: H, Z blocks, and g in st.dc
+int mf_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, BaState& st) {
+  BaCaller caller{BaUse::SESSION, nullptr, BL_THREADS, BL_LMW};
+  caller.matrix_free = true;
+  caller.runs_at_any_size = true;
+  int e = ba_setup(ctx, prob, opt, st, caller);
+  if (e) return e;
+  const BaDims& D = st.D;
+  BaRecompute& rc = st.rc;
+  RecomputeForm f{ctx, st, rc, true};
+  hipLaunchKernelGGL(bpcg_fill_kernel, dim3((D.n + 255) / 256), dim3(256), 0, ctx->stream, (size_t)D.n, 1.0, st.scale_c);
+  hipLaunchKernelGGL(bpcg_fill_kernel, dim3((3 * D.L + 255) / 256), dim3(256), 0, ctx->stream, 3 * (size_t)D.L, 1.0, st.scale_l);
+  VSL_CHECK_LAUNCH(ctx);
+  if ((e = f.prepare())) return e;
+  const BlArgs a = f.args();
+  // (scale = 1 and 1 / radius = 0: the blocks of the unscaled, undamped problem, Huber corrector applied)
+  hipLaunchKernelGGL(bal_prep_kernel<false>, dim3(rc.n_wg), dim3(BL_THREADS), 0, ctx->stream, a, st.cam_pos, 0.0, st.Yg, st.Pinv, st.bl,
+                     rc.pbs, (double*)nullptr, rc.lpart);
+  hipLaunchKernelGGL(bal_cam_kernel<false>, dim3(D.nfree, rc.bl_seg), dim3(256), 0, ctx->stream, a, st.free_cams, st.cam_start, rc.cam_lm,
+                     rc.cam_uv, rc.pbs, st.cam_part);
+  hipLaunchKernelGGL(bal_cam_finish_kernel, dim3((D.nfree * 33 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, rc.bl_seg, 1,
+                     st.cam_part, st.H, st.g_c, st.rhs, rc.n_wg, rc.lpart, st.scalars, st.scalars + 8);
+  hipLaunchKernelGGL(bpcg_add_kernel, dim3((D.n + 255) / 256), dim3(256), 0, ctx->stream, D.n, st.rhs, st.g_c, st.dc);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int mf_check(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const char* who, int* nfree) {
+  int rc = ba_validate(ctx, prob);
+  if (rc) return rc;
+  if (!opt) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: options are null", who);
+  *nfree = 0;
+  for (int c = 0; c < prob->n_cams; c++) *nfree += prob->cam_fixed[c] ? 0 : 1;
+  if (*nfree == 0) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: no free camera, there is no reduced camera system", who);
+  return VSL_OK;
 }
 
 // The Levenberg-Marquardt loop.  poses_out [7 * n_cams] and points_all_out [3 * n_lms of the FULL problem] (host)
@@ -522,7 +643,16 @@ extern "C" int vsl_global_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob
   if (rc) return rc;
   if (!opt || world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce))
     return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_global_bundle_adjust: bad arguments");
+  // the matrix-free route has no distributed form (H would have to be summed and the products exchanged per PCG
+  // iteration): refused on every rank alike, before any collective
+  const bool iterative = iterative_schur_on(ctx);
+  if (iterative && world > 1)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_global_bundle_adjust: iterative Schur (\"ba_iterative_schur\" / VSL_BA_ITERATIVE) runs on one rank only");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
+  // systems of at most 128 unknowns keep their one-workgroup dense solve: the switch is for large maps
+  int nfree_all = 0;
+  for (int c = 0; c < prob->n_cams; c++) nfree_all += prob->cam_fixed[c] ? 0 : 1;
+  const bool matrix_free = iterative && 6 * nfree_all > 128;
   // contiguous landmark ranges balanced by observation count (the same rule as visual-slam_amd/dist.py landmark_ranges)
   std::vector<int64_t> csum(prob->n_lms + 1, 0);
   for (int i = 0; i < prob->n_obs; i++) csum[prob->obs_lm[i] + 1]++;
@@ -543,7 +673,7 @@ extern "C" int vsl_global_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob
   for (int r = 1; r < world; r++) cuts[r] = std::min(std::max(cuts[r], cuts[r - 1] + 1), prob->n_lms - (world - r));
   const int first = cuts[rank], count = cuts[rank + 1] - cuts[rank];
   Session s;
-  rc = sess_create(ctx, prob, opt, first, count, s);
+  rc = sess_create(ctx, prob, opt, first, count, matrix_free, s);
   if (world > 1 && allreduce) {
     // rank-local failures (allocation, a bad range) are agreed on BEFORE the first data collective: MAX of a flag
     double* flag = ctx->status_word;  // allocated with the context: never null, so the collective is always entered
@@ -569,4 +699,57 @@ extern "C" int vsl_global_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob
   if (st.recompute)
     return sess_solve(s, RecomputeForm{ctx, st, st.rc, in_place}, allreduce, user, world, opt, prob->poses, prob->points, summary);
   return sess_solve(s, StoredForm{ctx, st, st.sb, in_place}, allreduce, user, world, opt, prob->poses, prob->points, summary);
+}
+
+// y = S x with S exactly as vsl_ba_linearize documents it, never formed (include/vslam_hip.h)
+extern "C" int vsl_ba_schur_apply(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const double* x, double* y,
+                                  int n_free) {
+  int nfree = 0;
+  int rc = mf_check(ctx, prob, opt, "vsl_ba_schur_apply", &nfree);
+  if (rc) return rc;
+  if (!x || !y || n_free != nfree)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_schur_apply: null vector, or n_free = %d where the problem has %d free cameras", n_free, nfree);
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  BaState st;
+  if ((rc = mf_linearize(ctx, prob, opt, st))) return rc;
+  RecomputeForm f{ctx, st, st.rc, true};
+  const int n = st.D.n;
+  VSL_HIP(ctx, hipMemcpyAsync(st.rc.pcg_p, x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+  const BpcgOp a = f.pcg_op(nullptr, 0.0);
+  if ((rc = f.pcg_product(a, nullptr, st.rc.pcg_p))) return rc;
+  hipLaunchKernelGGL(bpcg_apply_finish_kernel, dim3((nfree + 255) / 256), dim3(256), 0, ctx->stream, a, (const double*)st.rc.pcg_p,
+                     (const double*)st.rc.pcg_part, st.rc.pcg_q);
+  VSL_CHECK_LAUNCH(ctx);
+  VSL_HIP(ctx, hipMemcpyAsync(y, st.rc.pcg_q, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VSL_OK;
+}
+
+// S x = b by block-Jacobi PCG, same S (include/vslam_hip.h)
+extern "C" int vsl_ba_schur_pcg(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const double* b, double tol,
+                                int max_iterations, double* x, int* iterations, double* rel_residual) {
+  int nfree = 0;
+  int rc = mf_check(ctx, prob, opt, "vsl_ba_schur_pcg", &nfree);
+  if (rc) return rc;
+  if (!x || !(tol >= 0.0) || max_iterations < 0)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_schur_pcg: null x, a negative or non-finite tolerance, or a negative iteration count");
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  BaState st;
+  if ((rc = mf_linearize(ctx, prob, opt, st))) return rc;
+  RecomputeForm f{ctx, st, st.rc, true};
+  const int n = st.D.n;
+  if (b) VSL_HIP(ctx, hipMemcpyAsync(st.dc, b, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));  // (else g, where mf_linearize left it)
+  BpcgRec h;
+  if ((rc = f.pcg_solve(f.pcg_op(nullptr, 0.0), st.dc, tol, max_iterations, &h))) return rc;
+  hipLaunchKernelGGL(bpcg_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, (const double*)st.rc.pcg_x,
+                     (const BpcgRec*)st.rc.pcg_rec, 1.0, st.rc.pcg_q, (int*)nullptr);
+  VSL_CHECK_LAUNCH(ctx);
+  VSL_HIP(ctx, hipMemcpyAsync(x, st.rc.pcg_q, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (iterations) *iterations = h.iterations;
+  if (rel_residual) *rel_residual = ba_pcg_rel_residual(h);
+  if (h.status == BPCG_NUMERIC)
+    return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_schur_pcg: %s after %d iterations (S is not positive definite to working precision); x = 0",
+                    h.pivot_fail ? "a preconditioner block has a non-positive pivot" : "breakdown (p.Sp <= 0 or a non-finite value)", h.iterations);
+  return VSL_OK;
 }

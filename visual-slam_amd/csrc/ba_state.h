@@ -8,6 +8,7 @@
 #include "vsl_common.h"
 #include "dev_arena.h"
 #include "ba_device.h"
+#include "ba_pcg_plan.h"
 
 // What the caller of ba_setup runs.  It decides who pays for the arena, whether S may take a band form and which
 // buffers exist:
@@ -37,6 +38,10 @@ struct BaCaller {
   // a return other than VSL_OK ends ba_setup with it.  May throw std::bad_alloc.
   int (*plan_extra)(void* self, const BaHostPlan& hp, size_t* extra_bytes) = nullptr;
   void* plan_extra_self = nullptr;
+  // SESSION, matrix-free (ba_pcg.h): S is not allocated, no pair lists; the PCG's vectors are (BaRecompute::pcg_*).
+  // Needs the recompute form: ba_setup fails with VSL_ERR_INVALID where the plan cannot give it.
+  bool matrix_free = false;
+  bool runs_at_any_size = false;  // matrix-free hooks: landmark runs (and with them the recompute form) also at <= 128 unknowns
 };
 
 // Buffers of the STORED-BLOCKS form: r / F / E of every observation, written by ba_linearize_kernel and read by the
@@ -60,6 +65,11 @@ struct BaRecompute {
   int *wg_lm = nullptr, *cam_lm = nullptr;
   double *lpart = nullptr, *cam_uv = nullptr;
   double* pbs = nullptr;  // pbs[3 l + x] = scale_l (P^-1 b)_l: what the reduced right-hand side needs of a landmark
+  // matrix-free route only (ba_pcg.h): iterate, residual, M^-1 r, direction, S p (n each), t (3 L), segment partials
+  // (6 per free camera and segment), M^-1 (36 per free camera), the solve's record
+  double *pcg_x = nullptr, *pcg_r = nullptr, *pcg_z = nullptr, *pcg_p = nullptr, *pcg_q = nullptr, *pcg_t = nullptr;
+  double *pcg_part = nullptr, *pcg_minv = nullptr;
+  BpcgRec* pcg_rec = nullptr;
 };
 
 // What every form names.  The launchers of a form take this and the form's own struct, nothing else: naming a buffer
@@ -98,6 +108,7 @@ struct BaCommon {
   bool cyclic = false;  // band form whose band closes on itself (camera loop in trajectory order): wrap blocks in the leading slots of the first rows
   int ldS = 0, offS = 0, bw = 0;
   size_t s_elems = 0;  // doubles to allocate / clear / exchange for S
+  bool matrix_free = false;  // S does not exist: the camera step comes from the PCG of ba_pcg.h (S = nullptr, s_elems = 0)
   double* S_eff() { return S + offS; }
 };
 

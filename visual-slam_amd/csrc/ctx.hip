@@ -119,6 +119,15 @@ extern "C" int vsl_ctx_last_ba_layout(vsl_ctx* ctx, int64_t* s_elems, int* bande
   return VSL_OK;
 }
 
+extern "C" int vsl_ctx_last_ba_pcg(vsl_ctx* ctx, int64_t* solves, int64_t* iterations_total, int* iterations_last, double* rel_residual_last) {
+  if (!ctx) return VSL_ERR_INVALID;
+  if (solves) *solves = ctx->last_pcg_solves;
+  if (iterations_total) *iterations_total = ctx->last_pcg_iterations;
+  if (iterations_last) *iterations_last = ctx->last_pcg_iterations_last;
+  if (rel_residual_last) *rel_residual_last = ctx->last_pcg_rel_residual;
+  return VSL_OK;
+}
+
 // branch of the last SPD solve on this context (chol.hip records it where it chooses)
 extern "C" int vsl_ctx_last_spd_path(vsl_ctx* ctx, int* path, int* block, int* n_blocks, int* levels) {
   if (!ctx) return VSL_ERR_INVALID;

@@ -30,6 +30,9 @@ extern "C" int vsl_ctx_set_diagnostic(vsl_ctx* ctx, const char* name, int value)
   else if (k == "ba_host_lm") ctx->ba_host_lm = value != 0;
   else if (k == "ba_no_cyclic") ctx->ba_no_cyclic = value != 0;
   else if (k == "ba_schur_atomics") ctx->ba_schur_atomics = value != 0;
+  else if (k == "ba_iterative_schur") ctx->ba_iterative_schur = value != 0;
+  else if (k == "ba_pcg_poll") ctx->ba_pcg_poll = value < 0 ? 0 : value;
+  else if (k == "ba_pcg_tol_exp") ctx->ba_pcg_tol_exp = value < 0 ? 0 : value;
   else if (k == "ba_force_dense") ctx->ba_force_dense = value != 0;
   else if (k == "pgo_cov_no_band_read") ctx->pgo_cov_no_band_read = value != 0;
   else if (k == "chol_no_fused")ctx->chol_no_fused = value != 0;
@@ -38,6 +41,16 @@ extern "C" int vsl_ctx_set_diagnostic(vsl_ctx* ctx, const char* name, int value)
   else if (k == "frames_bow_chunk") ctx->frames_bow_chunk = value < 0 ? 0 : value;
   else if (k == "select_bucket_cap") ctx->select_bucket_cap = value < 0 ? 0 : value;
   else return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ctx_set_diagnostic: unknown knob '%s'", name);
+  return VSL_OK;
+}
+
+extern "C" int vsl_ctx_get_diagnostic(vsl_ctx* ctx, const char* name, int* value) {
+  if (!ctx || !name || !value) return VSL_ERR_INVALID;
+  const std::string k(name);
+  if (k == "ba_iterative_schur") *value = ctx->ba_iterative_schur ? 1 : 0;
+  else if (k == "ba_pcg_poll") *value = ctx->ba_pcg_poll;
+  else if (k == "ba_pcg_tol_exp") *value = ctx->ba_pcg_tol_exp;
+  else return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ctx_get_diagnostic: knob '%s' cannot be read back", name);
   return VSL_OK;
 }
 

@@ -72,6 +72,11 @@ struct vsl_ctx {
   // pinned, device-mapped mailbox of the fused local-BA iteration (ba_fused.hip): kernels post their scalars there
   int64_t last_ba_s_elems = 0;  // layout of the reduced camera system of the last general-path solve set up on this context
   int last_ba_banded = 0, last_ba_bw = 0;
+  // matrix-free PCG of the last general-path solve on this context (vsl_ctx_last_ba_pcg): solves, iterations in all of
+  // them and in the last one, the last one's ||r|| / ||b||
+  int64_t last_pcg_solves = 0, last_pcg_iterations = 0;
+  int last_pcg_iterations_last = 0;
+  double last_pcg_rel_residual = 0.0;
   void* ba_pin = nullptr;   // [plan of the solve | mailbox]: one copy carries the plan to the device
   size_t ba_pin_cap = 0;    // bytes
   bool select_attr_set = false;
@@ -94,6 +99,9 @@ struct vsl_ctx {
   bool ba_no_fused = false;             // diagnostic: local windows by the operator-by-operator kernels of ba.hip instead of the fused iteration (ba_fused.hip)
   bool ba_schur_entries = false;        // diagnostic: single-entry ownership in the small-system Schur kernel instead of 3 x 3 sub-blocks
   int describe_tile_min_images = 96;   // describe launches of at least this many images use the shared-tile kernel (measured break-even ~64 images; diagnostic: 1 forces it, 0 disables it)
+  bool ba_iterative_schur = false;      // diagnostic / VSL_BA_ITERATIVE: large maps by the matrix-free PCG on the reduced camera system (ba_pcg.h) instead of forming and factorising S
+  int ba_pcg_poll = 0;                  // diagnostic: PCG iterations enqueued between two reads of the solve's record (0: 8)
+  int ba_pcg_tol_exp = 0;               // diagnostic: the solver loop's PCG stops at ||r|| <= 10^-e ||b|| (0: the forcing term 0.1)
   bool ba_no_cyclic = false;            // diagnostic: large reduced camera systems in the linear band form (reverse Cuthill-McKee order) even when the cyclic form is narrower
   bool ba_host_lm = false;              // diagnostic: the fused local iteration with the Levenberg-Marquardt decision on the HOST (one synchronisation per iteration) instead of on the device (ba_fused.hip baf_decide_kernel)
   bool bow_no_wg_score = false;         // diagnostic: wave-per-candidate scoring kernel also for few candidates
