@@ -16,6 +16,7 @@
 // does the work: one batched guided search on the device (vsl_fuse_search), then the map edits of fusion_plan.h.
 #pragma once
 #include <cmath>
+#include <functional>
 #include <map>
 #include <set>
 #include <vector>
@@ -25,6 +26,13 @@
 #include "bow.h"
 #include "bundle_adjustment.h"
 #include "fusion_plan.h"
+
+// The weighted pose-graph entry points (the EdgeInformation overloads below) are referenced weakly, like the optional
+// entry points of bow.h: a build of the same headers on a C ABI without them links, and asking for weights there throws.
+#pragma weak vsl_pose_graph_optimize_w
+#pragma weak vsl_pgo_covariance_w
+#pragma weak vsl_pgo_joint_covariance_w
+#pragma weak vsl_pgo_edge_consistency_w
 
 namespace visnav {
 
@@ -144,8 +152,16 @@ struct PgoFlat {
   std::vector<int32_t> ea, eb;
   std::vector<double> meas, poses;
   std::vector<uint8_t> fixed;
+  std::vector<double> info;  // [n_edges][36] when an EdgeInformation was given, else empty
   vsl_pgo_problem prob;
+  const double* edge_info() const { return info.empty() ? nullptr : info.data(); }  // what the _w entry points take
 };
+}  // namespace amd
+// Information matrix (6 x 6 over (upsilon, omega), the inverse covariance of the edge's measurement) of the pose-graph
+// edge between keyframes a (the functor's T_w_c) and b (T_w_n); an empty function: every edge has identity weight and
+// the calls below ARE the unweighted ones.
+using EdgeInformation = std::function<PoseCovariance(const FrameCamId& a, const FrameCamId& b)>;
+namespace amd {
 inline void flatten_pose_graph(Camera& cur_kf, const FrameCamId& loop_candidate_fcid, const Sophus::SE3d& sim3, Cameras& keyframes,
                                int essential_threshold, const LoopClosureOptions& options, PgoFlat& f) {
   f.node_cam.assign(1, &cur_kf);
@@ -188,15 +204,34 @@ inline void flatten_pose_graph(Camera& cur_kf, const FrameCamId& loop_candidate_
   f.prob.edge_b = f.eb.data();
   f.prob.edge_meas = f.meas.data();
 }
+// ... with the edges' information matrices: cur_kf_fcid names node 0 for the callback
+inline void flatten_pose_graph(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
+                               const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
+                               const LoopClosureOptions& options, const EdgeInformation& information, PgoFlat& f) {
+  flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  f.info.clear();
+  if (!information) return;
+  if (!vsl_pose_graph_optimize_w) throw std::runtime_error("pose graph: this library has no per-edge information matrices");
+  std::vector<FrameCamId> id_of(f.node_cam.size(), cur_kf_fcid);
+  for (const auto& kv : f.node_of) id_of[kv.second] = kv.first;
+  f.info.resize(36 * f.ea.size());
+  for (size_t e = 0; e < f.ea.size(); e++) {
+    const PoseCovariance W = information(id_of[f.ea[e]], id_of[f.eb[e]]);
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) f.info[36 * e + 6 * i + j] = W(i, j);
+  }
+}
 }  // namespace amd
 
 // loop_closure_utils.h:446-587.  cur_kf is not part of `keyframes` (the reference adds it as its own block).
+// The overload with `information` weights every edge (vsl_pose_graph_optimize_w): a loop edge gated with Sigma_m by
+// loop_candidate_consistency enters the solve with Omega = Sigma_m^-1.  std::invalid_argument when a matrix is not
+// positive definite; no pose is written then.
 inline void pose_graph_optimization(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
                                     const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
-                                    const LoopClosureOptions& options) {
-  (void)cur_kf_fcid;
+                                    const LoopClosureOptions& options, const EdgeInformation& information) {
   amd::PgoFlat f;
-  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  amd::flatten_pose_graph(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, information, f);
   const int N = f.prob.n_nodes;
   vsl_ba_options opt;
   opt.use_huber = 1;
@@ -204,12 +239,20 @@ inline void pose_graph_optimization(const FrameCamId& cur_kf_fcid, Camera& cur_k
   opt.max_num_iterations = 20;
   opt.verbosity = 0;
   vsl_ba_summary sum;
-  amd::check(vsl_pose_graph_optimize(amd::ctx(), &f.prob, &opt, &sum), "pose_graph_optimization");
+  const int rc = f.edge_info() ? vsl_pose_graph_optimize_w(amd::ctx(), &f.prob, f.edge_info(), &opt, &sum)
+                               : vsl_pose_graph_optimize(amd::ctx(), &f.prob, &opt, &sum);
+  if (rc == VSL_ERR_INVALID && f.edge_info()) throw std::invalid_argument(vsl_last_error(amd::ctx()));
+  amd::check(rc, "pose_graph_optimization");
   for (int i = 0; i < N; i++)
     for (int c = 0; c < 7; c++) f.node_cam[i]->T_w_c.data()[c] = f.poses[7 * (size_t)i + c];
   if (options.verbosity_level >= 1)  // stands in for summary.BriefReport() (:585)
     std::printf("vslam_hip PGO: %d nodes, %d edges, iterations %d, initial cost %.6e, final cost %.6e, termination %d\n", N,
                 f.prob.n_edges, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination);
+}
+inline void pose_graph_optimization(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
+                                    const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
+                                    const LoopClosureOptions& options) {
+  pose_graph_optimization(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, EdgeInformation());
 }
 
 // Marginal covariances of the keyframes of that pose graph as it stands (vsl_pgo_covariance; the reference has no
@@ -223,10 +266,10 @@ inline void pose_graph_optimization(const FrameCamId& cur_kf_fcid, Camera& cur_k
 inline int pose_graph_covariance(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
                                  const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
                                  const LoopClosureOptions& options, const std::vector<FrameCamId>& query,
-                                 std::map<FrameCamId, PoseCovariance>& cov_out) {
+                                 std::map<FrameCamId, PoseCovariance>& cov_out, const EdgeInformation& information = EdgeInformation()) {
   cov_out.clear();
   amd::PgoFlat f;
-  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  amd::flatten_pose_graph(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, information, f);
   std::vector<int32_t> nodes;
   for (const FrameCamId& id : query) nodes.push_back(id == cur_kf_fcid ? 0 : f.node_of.at(id));
   vsl_ba_options opt;
@@ -236,7 +279,8 @@ inline int pose_graph_covariance(const FrameCamId& cur_kf_fcid, Camera& cur_kf, 
   opt.verbosity = 0;
   std::vector<double> cov(36 * nodes.size());
   int storage = 0;
-  const int rc = vsl_pgo_covariance(amd::ctx(), &f.prob, &opt, nodes.data(), (int)nodes.size(), cov.data(), &storage);
+  const int rc = f.edge_info() ? vsl_pgo_covariance_w(amd::ctx(), &f.prob, f.edge_info(), &opt, nodes.data(), (int)nodes.size(), cov.data(), &storage)
+                               : vsl_pgo_covariance(amd::ctx(), &f.prob, &opt, nodes.data(), (int)nodes.size(), cov.data(), &storage);
   if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
   amd::check(rc, "pose_graph_covariance");
   for (size_t q = 0; q < nodes.size(); q++) {
@@ -257,10 +301,11 @@ inline int pose_graph_joint_covariance(const FrameCamId& cur_kf_fcid, Camera& cu
                                        const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
                                        const LoopClosureOptions& options,
                                        const std::vector<std::pair<FrameCamId, FrameCamId>>& pairs,
-                                       std::vector<JointPoseCovariance>& cov_out) {
+                                       std::vector<JointPoseCovariance>& cov_out,
+                                       const EdgeInformation& information = EdgeInformation()) {
   cov_out.clear();
   amd::PgoFlat f;
-  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  amd::flatten_pose_graph(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, information, f);
   auto node = [&](const FrameCamId& id) { return (int32_t)(id == cur_kf_fcid ? 0 : f.node_of.at(id)); };
   std::vector<int32_t> a, b;
   for (const auto& p : pairs) {
@@ -274,7 +319,8 @@ inline int pose_graph_joint_covariance(const FrameCamId& cur_kf_fcid, Camera& cu
   opt.verbosity = 0;
   std::vector<double> cov(144 * pairs.size());
   int storage = 0;
-  const int rc = vsl_pgo_joint_covariance(amd::ctx(), &f.prob, &opt, a.data(), b.data(), (int)pairs.size(), cov.data(), &storage);
+  const int rc = f.edge_info() ? vsl_pgo_joint_covariance_w(amd::ctx(), &f.prob, f.edge_info(), &opt, a.data(), b.data(), (int)pairs.size(), cov.data(), &storage)
+                               : vsl_pgo_joint_covariance(amd::ctx(), &f.prob, &opt, a.data(), b.data(), (int)pairs.size(), cov.data(), &storage);
   if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
   amd::check(rc, "pose_graph_joint_covariance");
   cov_out.resize(pairs.size());
@@ -299,9 +345,10 @@ struct LoopCandidateConsistency {
 inline int loop_candidate_consistency(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
                                       const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
                                       const LoopClosureOptions& options, const FrameCamId& cand_a, const FrameCamId& cand_b,
-                                      const Sophus::SE3d& T_a_b, const PoseCovariance* meas_cov, LoopCandidateConsistency& out) {
+                                      const Sophus::SE3d& T_a_b, const PoseCovariance* meas_cov, LoopCandidateConsistency& out,
+                                      const EdgeInformation& information = EdgeInformation()) {
   amd::PgoFlat f;
-  amd::flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  amd::flatten_pose_graph(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, information, f);
   const int32_t a = cand_a == cur_kf_fcid ? 0 : f.node_of.at(cand_a), b = cand_b == cur_kf_fcid ? 0 : f.node_of.at(cand_b);
   double meas[6], mc[36], rc36[36];
   amd::rt_log(amd::rt_of(T_a_b), meas);
@@ -314,8 +361,10 @@ inline int loop_candidate_consistency(const FrameCamId& cur_kf_fcid, Camera& cur
   opt.max_num_iterations = 0;
   opt.verbosity = 0;
   int storage = 0;
-  const int rc = vsl_pgo_edge_consistency(amd::ctx(), &f.prob, &opt, &a, &b, meas, meas_cov ? mc : nullptr, 1, out.residual, rc36,
-                                          &out.chi2, &storage);
+  const int rc = f.edge_info() ? vsl_pgo_edge_consistency_w(amd::ctx(), &f.prob, f.edge_info(), &opt, &a, &b, meas, meas_cov ? mc : nullptr, 1,
+                                                            out.residual, rc36, &out.chi2, &storage)
+                               : vsl_pgo_edge_consistency(amd::ctx(), &f.prob, &opt, &a, &b, meas, meas_cov ? mc : nullptr, 1, out.residual, rc36,
+                                                          &out.chi2, &storage);
   if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
   amd::check(rc, "loop_candidate_consistency");
   for (int i = 0; i < 6; i++)

@@ -677,6 +677,36 @@ int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_op
  * the in-band slots of columns below zero). */
 int vsl_pgo_linearize_stored(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, int jacobi_scale, double* H,
                              double* g, double* cost, int* n_free, int* storage, int* half_bandwidth, int* stray_nonzeros);
+/* Per-edge information matrices (g2o EdgeSE3::information, gtsam noise models, the sqrt_information of the Ceres
+ * pose-graph example): the six calls above with one more argument after prob, edge_info [n_edges][36] -- block e is
+ * Omega_e, 6 x 6 row-major in the order (upsilon, omega) of the residual.  The cost is sum_e rho(r_e^T Omega_e r_e) / 2:
+ * with Omega = L L^T (Cholesky) and U = L^T every edge contributes r_w = U r, J_w = U J, and Huber, the Ceres corrector,
+ * H = J_w^T J_w, g, the solve and the marginals act on r_w, J_w exactly as the unweighted calls act on r, J
+ * (opt->huber_parameter is a threshold on the WHITENED norm).  Covariances are then in the units Omega is given in.
+ *   edge_info == NULL   the call IS the unweighted one: same code path, same bits;
+ *   symmetry            the two mirror entries of a block are averaged (the rule of meas_cov);
+ *   not positive definite   a Cholesky pivot L_ii^2 <= 2^-36 Omega_ii, or one that is not finite (the rule of
+ *                       vsl_ba_covariance), gives VSL_ERR_INVALID, vsl_last_error names the lowest such edge index and
+ *                       prob->poses is not written (the marginal calls with n_q / n_pairs / n_cand = 0 launch nothing
+ *                       and so do not look at edge_info at all);
+ *   storage            the dense / band / ring decision does not depend on the weights.
+ * vsl_pgo_edge_consistency_w: edge_info belongs to the GRAPH's edges and shapes H, hence Sigma; the candidate's own
+ * residual stays unwhitened and without corrector, meas_cov keeps its meaning.  Gating a candidate with Sigma_m and then
+ * adding it as an edge with Omega = Sigma_m^-1 makes the gate and the solve agree. */
+int vsl_pose_graph_optimize_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                              vsl_ba_summary* summary);
+int vsl_pgo_linearize_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt, double* H,
+                        double* g, double* cost, int* n_free);
+int vsl_pgo_linearize_stored_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                               int jacobi_scale, double* H, double* g, double* cost, int* n_free, int* storage,
+                               int* half_bandwidth, int* stray_nonzeros);
+int vsl_pgo_covariance_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                         const int32_t* nodes, int n_q, double* cov, int* storage);
+int vsl_pgo_joint_covariance_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                               const int32_t* pair_a, const int32_t* pair_b, int n_pairs, double* cov, int* storage);
+int vsl_pgo_edge_consistency_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                               const int32_t* cand_a, const int32_t* cand_b, const double* cand_meas, const double* meas_cov,
+                               int n_cand, double* resid, double* resid_cov, double* chi2, int* storage);
 
 /* --------------------------------------------------------------- DBoW2 path */
 /*

@@ -458,71 +458,94 @@ class Context:
         st.edge_meas = arr.edge_meas.ctypes.data_as(f64p)
         return st
 
-    def pose_graph_optimize(self, arr, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
-        """arr: object with the numpy fields of vsl_pgo_problem (poses [N, 7] optimised in place)."""
+    @staticmethod
+    def _edge_info(arr, edge_info):
+        """None, or the [E, 6, 6] float64 information matrices of arr's edges, contiguous.  Anything else is a ValueError
+        here, before a native call sees it."""
+        if edge_info is None:
+            return None
+        if not isinstance(edge_info, np.ndarray) or edge_info.dtype != np.float64 or edge_info.shape != (len(arr.edge_a), 6, 6):
+            raise ValueError("edge_info: a float64 array of shape [%d, 6, 6] is needed" % len(arr.edge_a))
+        return np.ascontiguousarray(edge_info)
+
+    def _pgo_call(self, name, info, st, *args):
+        """The unweighted symbol when info is None, else its _w form (edge_info sits directly after prob)."""
+        if info is None:
+            return self._ck(getattr(self.L, name)(self.h, C.byref(st), *args))
+        return self._ck(getattr(self.L, name + "_w")(self.h, C.byref(st), info.ctypes.data_as(f64p), *args))
+
+    def pose_graph_optimize(self, arr, use_huber=True, huber=1.0, max_iters=20, verbosity=0, *, edge_info=None):
+        """arr: object with the numpy fields of vsl_pgo_problem (poses [N, 7] optimised in place).  edge_info: [E, 6, 6]
+        float64 information matrices of the edges (vsl_pose_graph_optimize_w), None: identity."""
+        info = self._edge_info(arr, edge_info)
         st = self._pgo_struct(arr)
         o = self._ba_opts(use_huber, huber, max_iters, verbosity)
         s = BaSummary()
-        self._ck(self.L.vsl_pose_graph_optimize(self.h, C.byref(st), C.byref(o), C.byref(s)))
+        self._pgo_call("vsl_pose_graph_optimize", info, st, C.byref(o), C.byref(s))
         return s
 
-    def pgo_linearize(self, arr, use_huber=True, huber=1.0):
+    def pgo_linearize(self, arr, use_huber=True, huber=1.0, *, edge_info=None):
+        info = self._edge_info(arr, edge_info)
         st = self._pgo_struct(arr)
         o = self._ba_opts(use_huber, huber, 0, 0)
         n = 6 * int((arr.node_fixed == 0).sum())
         H, g = np.zeros((max(n, 1), max(n, 1))), np.zeros(max(n, 1))
         cost, nf = C.c_double(), C.c_int32()
         Hc = np.zeros(n * n)
-        self._ck(self.L.vsl_pgo_linearize(self.h, C.byref(st), C.byref(o), Hc.ctypes.data_as(f64p), g.ctypes.data_as(f64p),
-                                          C.byref(cost), C.byref(nf)))
+        self._pgo_call("vsl_pgo_linearize", info, st, C.byref(o), Hc.ctypes.data_as(f64p), g.ctypes.data_as(f64p),
+                       C.byref(cost), C.byref(nf))
         return Hc.reshape(n, n), g[:n].copy(), cost.value
 
-    def pgo_linearize_stored(self, arr, use_huber=True, huber=1.0, jacobi_scale=False):
+    def pgo_linearize_stored(self, arr, use_huber=True, huber=1.0, jacobi_scale=False, *, edge_info=None):
         """The normal equations as the solver stores them for this graph, expanded to dense: H, g, cost and
         info = dict(storage = 0 dense / 1 band / 2 cyclic band, half_bandwidth, stray_nonzeros, n_free)."""
+        info = self._edge_info(arr, edge_info)
         st = self._pgo_struct(arr)
         o = self._ba_opts(use_huber, huber, 0, 0)
         n = 6 * int((arr.node_fixed == 0).sum())
         Hc, g = np.zeros(n * n), np.zeros(max(n, 1))
         cost, nf, storage, bw, stray = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        self._ck(self.L.vsl_pgo_linearize_stored(self.h, C.byref(st), C.byref(o), int(bool(jacobi_scale)),
-                                                 Hc.ctypes.data_as(f64p), g.ctypes.data_as(f64p), C.byref(cost), C.byref(nf),
-                                                 C.byref(storage), C.byref(bw), C.byref(stray)))
+        self._pgo_call("vsl_pgo_linearize_stored", info, st, C.byref(o), int(bool(jacobi_scale)), Hc.ctypes.data_as(f64p),
+                       g.ctypes.data_as(f64p), C.byref(cost), C.byref(nf), C.byref(storage), C.byref(bw), C.byref(stray))
         return Hc.reshape(n, n), g[:n].copy(), cost.value, dict(storage=storage.value, half_bandwidth=bw.value,
                                                                  stray_nonzeros=stray.value, n_free=nf.value)
 
-    def pgo_covariance(self, arr, nodes=None, use_huber=True, huber=1.0):
+    def pgo_covariance(self, arr, nodes=None, use_huber=True, huber=1.0, *, edge_info=None):
         """Marginal covariances of the pose graph's nodes at arr's poses (vsl_pgo_covariance; nothing is optimised).
         nodes: node ids (None: all free nodes, ascending).  Returns (cov [n_q, 6, 6], storage) with storage = 0 dense /
-        1 linear band / 2 folded ring: the route the call took."""
+        1 linear band / 2 folded ring: the route the call took.  edge_info as in pose_graph_optimize."""
+        info = self._edge_info(arr, edge_info)
         st = self._pgo_struct(arr)
         o = self._ba_opts(use_huber, huber, 0, 0)
         nodes = np.flatnonzero(arr.node_fixed == 0) if nodes is None else nodes
         nodes = np.ascontiguousarray(nodes, np.int32).reshape(-1)
         cov = np.zeros((len(nodes), 6, 6))
         storage = C.c_int(-1)
-        self._ck(self.L.vsl_pgo_covariance(self.h, C.byref(st), C.byref(o), nodes.ctypes.data_as(i32p), len(nodes),
-                                           cov.ctypes.data_as(f64p), C.byref(storage)))
+        self._pgo_call("vsl_pgo_covariance", info, st, C.byref(o), nodes.ctypes.data_as(i32p), len(nodes),
+                       cov.ctypes.data_as(f64p), C.byref(storage))
         return cov, storage.value
 
-    def pgo_joint_covariance(self, arr, pairs, use_huber=True, huber=1.0):
+    def pgo_joint_covariance(self, arr, pairs, use_huber=True, huber=1.0, *, edge_info=None):
         """Joint marginal covariances of pairs of nodes (vsl_pgo_joint_covariance; nothing is optimised).  pairs: [n, 2]
         node ids (a, b); one of the two may be fixed (zero rows and columns).  Returns (cov [n, 12, 12] in the order
-        (a, b), storage)."""
+        (a, b), storage).  edge_info as in pose_graph_optimize."""
+        info = self._edge_info(arr, edge_info)
         st = self._pgo_struct(arr)
         o = self._ba_opts(use_huber, huber, 0, 0)
         pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
         a, b = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
         cov = np.zeros((len(a), 12, 12))
         storage = C.c_int(-1)
-        self._ck(self.L.vsl_pgo_joint_covariance(self.h, C.byref(st), C.byref(o), a.ctypes.data_as(i32p), b.ctypes.data_as(i32p),
-                                                 len(a), cov.ctypes.data_as(f64p), C.byref(storage)))
+        self._pgo_call("vsl_pgo_joint_covariance", info, st, C.byref(o), a.ctypes.data_as(i32p), b.ctypes.data_as(i32p), len(a),
+                       cov.ctypes.data_as(f64p), C.byref(storage))
         return cov, storage.value
 
-    def pgo_edge_consistency(self, arr, cand_a, cand_b, cand_meas, meas_cov=None, use_huber=True, huber=1.0):
+    def pgo_edge_consistency(self, arr, cand_a, cand_b, cand_meas, meas_cov=None, use_huber=True, huber=1.0, *, edge_info=None):
         """Residual, residual covariance and chi-square of candidate edges (a, b, meas) against the graph as it stands
         (vsl_pgo_edge_consistency).  cand_meas: [n, 6]; meas_cov: [n, 6, 6] or None (zero).  Returns (resid [n, 6],
-        resid_cov [n, 6, 6], chi2 [n], storage); chi2 is NaN where resid_cov + meas_cov is not positive definite."""
+        resid_cov [n, 6, 6], chi2 [n], storage); chi2 is NaN where resid_cov + meas_cov is not positive definite.
+        edge_info: information matrices of the GRAPH's edges (they shape the covariance, not the candidate's residual)."""
+        info = self._edge_info(arr, edge_info)
         st = self._pgo_struct(arr)
         o = self._ba_opts(use_huber, huber, 0, 0)
         a = np.ascontiguousarray(cand_a, np.int32).reshape(-1)
@@ -534,10 +557,9 @@ class Context:
             raise ValueError("cand_a and cand_b differ in length")
         resid, resid_cov, chi2 = np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros(n)
         storage = C.c_int(-1)
-        self._ck(self.L.vsl_pgo_edge_consistency(self.h, C.byref(st), C.byref(o), a.ctypes.data_as(i32p), b.ctypes.data_as(i32p),
-                                                 meas.ctypes.data_as(f64p), None if mc is None else mc.ctypes.data_as(f64p), n,
-                                                 resid.ctypes.data_as(f64p), resid_cov.ctypes.data_as(f64p),
-                                                 chi2.ctypes.data_as(f64p), C.byref(storage)))
+        self._pgo_call("vsl_pgo_edge_consistency", info, st, C.byref(o), a.ctypes.data_as(i32p), b.ctypes.data_as(i32p),
+                       meas.ctypes.data_as(f64p), None if mc is None else mc.ctypes.data_as(f64p), n,
+                       resid.ctypes.data_as(f64p), resid_cov.ctypes.data_as(f64p), chi2.ctypes.data_as(f64p), C.byref(storage))
         return resid, resid_cov, chi2, storage.value
 
     def bundle_adjust_intrinsics(self, arr, use_huber=True, huber=1.0, max_iters=20, verbosity=0):

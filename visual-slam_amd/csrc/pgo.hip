@@ -10,6 +10,7 @@
 // walks the node's incident edges in edge order (lists built once per solve on the host): no atomics, results do not
 // depend on timing -- and solved by the blocked Cholesky of chol.hip.  This runs once per loop closure.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -181,13 +182,72 @@ __device__ void seed_pose(const double* p7, int first, D12* q, D12* t) {
   }
 }
 
+// Per-edge information matrices (the _w entry points): Omega_e = L L^T, U = L^T kept as its 21 upper-triangle entries
+// row by row (row i: columns i .. 5).  One thread per edge: the two mirror entries of Omega averaged (the rule of
+// meas_cov), 6 x 6 Cholesky, "not positive definite" by the rule of ba_cov.hip (a pivot L_ii^2 <= 2^-36 Omega_ii, or not
+// finite); the lowest failing edge index is left in *bad (preset above every index; integer atomicMin: independent of timing).
+__global__ __launch_bounds__(64) void pgo_edge_whiten_kernel(int n_edges, const double* __restrict__ info, double* __restrict__ U,
+                                                             int* __restrict__ bad) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= n_edges) return;
+  const double* W = info + 36 * (size_t)e;
+  double L[6][6];
+  bool pd = true;
+  for (int j = 0; j < 6; j++) {
+    const double wjj = W[7 * j];
+    double d = wjj;
+    for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k];
+    if (!isfinite(d) || !(d > 0x1p-36 * wjj)) {
+      pd = false;
+      break;
+    }
+    const double l = sqrt(d);
+    L[j][j] = l;
+    for (int i = j + 1; i < 6; i++) {
+      double s = 0.5 * (W[6 * i + j] + W[6 * j + i]);
+      for (int k = 0; k < j; k++) s -= L[i][k] * L[j][k];
+      L[i][j] = s / l;
+    }
+  }
+  if (!pd) {
+    atomicMin(bad, e);
+    return;
+  }
+  double* Ue = U + 21 * (size_t)e;
+  for (int i = 0, at = 0; i < 6; i++)
+    for (int j = i; j < 6; j++) Ue[at++] = L[j][i];  // (an infinite entry has failed the pivot of its row above)
+}
+
+// r <- U r in place, rows ascending (row i reads entries i .. 5: none of them written yet), each row of U loaded when
+// its turn comes; the sum of a row runs over ascending column index.  T = D12 (value and 12 partials) or double.
+__device__ __forceinline__ double scl(double u, double a) { return u * a; }
+__device__ __forceinline__ D12 scl(double u, const D12& a) {
+  D12 r;
+  r.v = u * a.v;
+#pragma unroll
+  for (int i = 0; i < 12; i++) r.d[i] = u * a.d[i];
+  return r;
+}
+template <class T>
+__device__ __forceinline__ void whiten_rows(const double* __restrict__ Ue, T* r) {
+#pragma unroll
+  for (int i = 0, at = 0; i < 6; i++) {
+    T acc = scl(Ue[at++], r[i]);
+#pragma unroll
+    for (int j = i + 1; j < 6; j++) acc = acc + scl(Ue[at++], r[j]);
+    r[i] = acc;
+  }
+}
+
 // r (6), Ja / Jb (6x6 row-major) per edge, robustified (ceres Corrector with rho'' <= 0: sqrt(rho') on both),
-// cost[e] = rho(|r|^2) / 2
-template <bool JAC>
+// cost[e] = rho(|r|^2) / 2.  WEIGHTED: r and its partials are whitened by the edge's U (pgo_edge_whiten_kernel) before
+// the squared norm is taken -- Huber, the corrector and every consumer of r / Ja / Jb then see U r, U J.
+template <bool JAC, bool WEIGHTED>
 __global__ __launch_bounds__(64) void pgo_linearize_kernel(int n_edges, const double* __restrict__ poses, const int* __restrict__ edge_a,
                                                            const int* __restrict__ edge_b, const double* __restrict__ meas,
-                                                           int use_huber, double huber, double* __restrict__ r_out,
-                                                           double* __restrict__ Ja, double* __restrict__ Jb, double* __restrict__ cost) {
+                                                           const double* __restrict__ U, int use_huber, double huber,
+                                                           double* __restrict__ r_out, double* __restrict__ Ja,
+                                                           double* __restrict__ Jb, double* __restrict__ cost) {
   const int e = blockIdx.x * 64 + threadIdx.x;
   if (e >= n_edges) return;
   const double* pa = poses + 7 * (size_t)edge_a[e];
@@ -198,6 +258,7 @@ __global__ __launch_bounds__(64) void pgo_linearize_kernel(int n_edges, const do
     seed_pose(pa, 0, qc, tc);
     seed_pose(pb, 6, qn, tn);
     edge_residual(qc, tc, qn, tn, meas + 6 * (size_t)e, rd);
+    if (WEIGHTED) whiten_rows(U + 21 * (size_t)e, rd);
     for (int i = 0; i < 6; i++) {
       r[i] = rd[i].v;
       s += r[i] * r[i];
@@ -212,6 +273,7 @@ __global__ __launch_bounds__(64) void pgo_linearize_kernel(int n_edges, const do
     for (int i = 0; i < 6; i++) r_out[6 * (size_t)e + i] = k * r[i];
   } else {
     edge_residual(pa, pa + 4, pb, pb + 4, meas + 6 * (size_t)e, r);
+    if (WEIGHTED) whiten_rows(U + 21 * (size_t)e, r);
     for (int i = 0; i < 6; i++) s += r[i] * r[i];
   }
   double rho0 = s;
@@ -469,6 +531,12 @@ struct PgoState {
   double *colsq = nullptr, *scale = nullptr, *H = nullptr, *g = nullptr, *A = nullptr, *b = nullptr, *gabs = nullptr;
   double *part = nullptr, *part2 = nullptr, *scalars = nullptr;
   int *free_idx = nullptr, *edge_a = nullptr, *edge_b = nullptr, *inc_off = nullptr, *inc = nullptr, *flag = nullptr;
+  // per-edge information matrices (the _w entry points; null: identity weights, the unweighted kernels).  U: what
+  // pgo_edge_whiten_kernel leaves, 21 doubles per edge, null when unweighted; wbad: its lowest failing edge
+  const double* edge_info = nullptr;  // host, [E][36]
+  const char* who = "vsl_pose_graph_optimize";  // the entry point, for the messages of pgo_setup
+  double* U = nullptr;
+  int* wbad = nullptr;
 };
 
 // THE storage decision of a graph (host only): dense, linear band or cyclic band -- st.ld / bw / cyclic / h_elems from
@@ -525,7 +593,7 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
   const std::vector<int> free_idx = pgo_free_index(p, &nf);
   pgo_storage(ctx, p, free_idx, nf, st);
   const size_t N = st.N, E = st.E, n = st.n;
-  ArenaPlan plan(24);
+  ArenaPlan plan(26);
   plan.add(st.poses, 7 * N);
   plan.add(st.cand, 7 * N);
   plan.add(st.free_idx, N);
@@ -550,8 +618,11 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
   plan.add(st.scalars, 8);
   plan.add(st.flag, 2);
   plan.add(st.extra, st.extra_bytes);
+  const bool weighted = st.edge_info && E > 0;
+  plan.add(st.U, weighted ? 21 * E : 0);
+  plan.add(st.wbad, weighted ? 1 : 0);
   if (st.arena.acquire(ctx, ArenaPolicy::OWNED, plan) != hipSuccess)
-    return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_pose_graph_optimize: device allocation of %zu bytes failed", plan.total());
+    return vsl_fail(ctx, VSL_ERR_NOMEM, "%s: device allocation of %zu bytes failed", st.who, plan.total());
   hipStream_t s = ctx->stream;
   if (N) VSL_HIP(ctx, hipMemcpyAsync(st.poses, p->poses, 56 * N, hipMemcpyHostToDevice, s));
   if (N) VSL_HIP(ctx, hipMemcpyAsync(st.free_idx, free_idx.data(), 4 * N, hipMemcpyHostToDevice, s));
@@ -576,7 +647,21 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
     VSL_HIP(ctx, hipMemcpyAsync(st.edge_b, p->edge_b, 4 * E, hipMemcpyHostToDevice, s));
     VSL_HIP(ctx, hipMemcpyAsync(st.meas, p->edge_meas, 48 * E, hipMemcpyHostToDevice, s));
   }
+  static const int none = INT_MAX;  // (static: the asynchronous upload reads it after this function may have returned)
+  int bad = none;
+  if (weighted) {
+    // Omega is staged in Ja (36 E doubles, written by the first linearisation only after this); U once per call
+    VSL_HIP(ctx, hipMemcpyAsync(st.Ja, st.edge_info, 288 * E, hipMemcpyHostToDevice, s));
+    VSL_HIP(ctx, hipMemcpyAsync(st.wbad, &none, 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(pgo_edge_whiten_kernel, dim3((st.E + 63) / 64), dim3(64), 0, s, st.E, st.Ja, st.U, st.wbad);
+    VSL_CHECK_LAUNCH(ctx);
+    VSL_HIP(ctx, hipMemcpyAsync(&bad, st.wbad, 4, hipMemcpyDeviceToHost, s));
+  } else {
+    st.U = nullptr;  // (an empty arena slot still has an address)
+  }
   VSL_HIP(ctx, hipStreamSynchronize(s));  // free_idx and the incidence lists are locals
+  if (bad != none)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "%s: edge_info of edge %d is not positive definite (a pivot L_ii^2 <= 2^-36 Omega_ii, or not finite)", st.who, bad);
   return VSL_OK;
 }
 
@@ -584,9 +669,14 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
 int pgo_linearize(vsl_ctx* ctx, PgoState& st, const vsl_ba_options* opt, bool first, double* cost_out) {
   hipStream_t s = ctx->stream;
   const int E = st.E, n = st.n;
-  if (E > 0)
-    hipLaunchKernelGGL(pgo_linearize_kernel<true>, dim3((E + 63) / 64), dim3(64), 0, s, E, st.poses, st.edge_a, st.edge_b, st.meas,
-                       opt->use_huber, opt->huber_parameter, st.r, st.Ja, st.Jb, st.cost);
+  if (E > 0) {
+    if (st.U)
+      hipLaunchKernelGGL((pgo_linearize_kernel<true, true>), dim3((E + 63) / 64), dim3(64), 0, s, E, st.poses, st.edge_a, st.edge_b,
+                         st.meas, st.U, opt->use_huber, opt->huber_parameter, st.r, st.Ja, st.Jb, st.cost);
+    else
+      hipLaunchKernelGGL((pgo_linearize_kernel<true, false>), dim3((E + 63) / 64), dim3(64), 0, s, E, st.poses, st.edge_a, st.edge_b,
+                         st.meas, (const double*)nullptr, opt->use_huber, opt->huber_parameter, st.r, st.Ja, st.Jb, st.cost);
+  }
   if (first && n > 0) {
     VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)n, s));
     if (st.N > 0)
@@ -635,7 +725,7 @@ int pgo_expand_band(const PgoState& st, const double* Hs, double* H) {
 }
 
 // the two test hooks: the normal equations at the given poses in the storage pgo_setup chose, returned dense
-int pgo_linearize_hook(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const vsl_ba_options* opt, bool force_dense,
+int pgo_linearize_hook(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt, bool force_dense,
                        bool jacobi_scale, double* H, double* g, double* cost, int* n_free, int* storage, int* half_bandwidth,
                        int* stray_nonzeros) {
   int rc = pgo_validate(ctx, prob);
@@ -644,6 +734,8 @@ int pgo_linearize_hook(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* pro
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   PgoState st;
   st.force_dense = force_dense;
+  st.edge_info = edge_info;
+  st.who = who;
   if ((rc = pgo_setup(ctx, prob, st))) return rc;
   // unit scaling: fill scale with ones by pretending every column norm is zero
   if (!jacobi_scale && st.n > 0) {
@@ -676,7 +768,12 @@ int pgo_linearize_hook(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* pro
 // poses, unscaled -- the test hook next to orc_pgo_linearize.
 extern "C" int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, double* H, double* g,
                                  double* cost, int* n_free) {
-  return pgo_linearize_hook(ctx, "vsl_pgo_linearize", prob, opt, true, false, H, g, cost, n_free, nullptr, nullptr, nullptr);
+  return pgo_linearize_hook(ctx, "vsl_pgo_linearize", prob, nullptr, opt, true, false, H, g, cost, n_free, nullptr, nullptr, nullptr);
+}
+// ... of the weighted problem (edge_info: [n_edges][36], Omega_e row-major; NULL: the call above)
+extern "C" int vsl_pgo_linearize_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                                   double* H, double* g, double* cost, int* n_free) {
+  return pgo_linearize_hook(ctx, "vsl_pgo_linearize_w", prob, edge_info, opt, true, false, H, g, cost, n_free, nullptr, nullptr, nullptr);
 }
 
 // The same in the storage vsl_pose_graph_optimize takes for this graph (dense, band or cyclic band: H is expanded on the
@@ -684,16 +781,38 @@ extern "C" int vsl_pgo_linearize(vsl_ctx* ctx, const vsl_pgo_problem* prob, cons
 extern "C" int vsl_pgo_linearize_stored(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, int jacobi_scale,
                                         double* H, double* g, double* cost, int* n_free, int* storage, int* half_bandwidth,
                                         int* stray_nonzeros) {
-  return pgo_linearize_hook(ctx, "vsl_pgo_linearize_stored", prob, opt, false, jacobi_scale != 0, H, g, cost, n_free, storage,
-                            half_bandwidth, stray_nonzeros);
+  return pgo_linearize_hook(ctx, "vsl_pgo_linearize_stored", prob, nullptr, opt, false, jacobi_scale != 0, H, g, cost, n_free,
+                            storage, half_bandwidth, stray_nonzeros);
+}
+extern "C" int vsl_pgo_linearize_stored_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                                          int jacobi_scale, double* H, double* g, double* cost, int* n_free, int* storage,
+                                          int* half_bandwidth, int* stray_nonzeros) {
+  return pgo_linearize_hook(ctx, "vsl_pgo_linearize_stored_w", prob, edge_info, opt, false, jacobi_scale != 0, H, g, cost, n_free,
+                            storage, half_bandwidth, stray_nonzeros);
 }
 
+namespace {
+int pgo_optimize(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                 vsl_ba_summary* summary);
+}
 extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, vsl_ba_summary* summary) {
+  return pgo_optimize(ctx, "vsl_pose_graph_optimize", prob, nullptr, opt, summary);
+}
+// the cost is sum rho(r^T Omega_e r) / 2: Huber on the whitened squared norm (edge_info NULL: the call above)
+extern "C" int vsl_pose_graph_optimize_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                                         vsl_ba_summary* summary) {
+  return pgo_optimize(ctx, "vsl_pose_graph_optimize_w", prob, edge_info, opt, summary);
+}
+namespace {
+int pgo_optimize(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                 vsl_ba_summary* summary) {
   int rc = pgo_validate(ctx, prob);
   if (rc) return rc;
-  if (!opt) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pose_graph_optimize: options are null");
+  if (!opt) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: options are null", who);
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   PgoState st;
+  st.edge_info = edge_info;
+  st.who = who;
   if ((rc = pgo_setup(ctx, prob, st))) return rc;
   hipStream_t s = ctx->stream;
   const int n = st.n, N = st.N, E = st.E;
@@ -749,10 +868,16 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
                          st.cand, st.part, st.part2);
       hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part, N, st.scalars + 3, 0);
       hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.part2, N, st.scalars + 4, 0);
-      if (E > 0)
-        hipLaunchKernelGGL(pgo_linearize_kernel<false>, dim3((E + 63) / 64), dim3(64), 0, s, E, st.cand, st.edge_a, st.edge_b,
-                           st.meas, opt->use_huber, opt->huber_parameter, (double*)nullptr, (double*)nullptr, (double*)nullptr,
-                           st.cost);
+      if (E > 0) {
+        if (st.U)
+          hipLaunchKernelGGL((pgo_linearize_kernel<false, true>), dim3((E + 63) / 64), dim3(64), 0, s, E, st.cand, st.edge_a,
+                             st.edge_b, st.meas, st.U, opt->use_huber, opt->huber_parameter, (double*)nullptr, (double*)nullptr,
+                             (double*)nullptr, st.cost);
+        else
+          hipLaunchKernelGGL((pgo_linearize_kernel<false, false>), dim3((E + 63) / 64), dim3(64), 0, s, E, st.cand, st.edge_a,
+                             st.edge_b, st.meas, (const double*)nullptr, opt->use_huber, opt->huber_parameter, (double*)nullptr,
+                             (double*)nullptr, (double*)nullptr, st.cost);
+      }
       hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.cost, E, st.scalars + 5, 0);
       VSL_CHECK_LAUNCH(ctx);
       VSL_HIP(ctx, hipMemcpyAsync(sc, st.scalars + 1, 48, hipMemcpyDeviceToHost, s));
@@ -791,6 +916,7 @@ extern "C" int vsl_pose_graph_optimize(vsl_ctx* ctx, const vsl_pgo_problem* prob
   if (summary) *summary = sum;
   return VSL_OK;
 }
+}  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
 // vsl_pgo_covariance: the 6 x 6 diagonal blocks of H^-1, H = J^T J of one linearisation at the poses handed in (unit
@@ -860,7 +986,7 @@ void pgo_fold_problem(const vsl_pgo_problem* p, const std::vector<int>& free_idx
 
 // q_free: the unique queried nodes as free indices of `prob` (the folded graph on route 2), ascending.  q_free, col_unk
 // and blocks are read / written by copies on the stream: the caller keeps them until it has synchronised.
-int pgo_cov_run(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, bool linear_only,
+int pgo_cov_run(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt, bool linear_only,
                 const std::vector<int>& q_free, std::vector<int>& col_unk, std::vector<double>& blocks, int* route) {
   const int nQ = (int)q_free.size();
   int nf = 0;
@@ -868,6 +994,8 @@ int pgo_cov_run(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options*
   const int n = 6 * nf, m = 6 * nQ, nblk = (m + 15) / 16;
   PgoState st;
   st.linear_only = linear_only;
+  st.edge_info = edge_info;
+  st.who = who;
   {
     // the decision is needed before the arena is sized: the dense route keeps its columns there
     PgoState probe;
@@ -930,20 +1058,34 @@ int pgo_cov_run(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options*
   VSL_HIP(ctx, hipMemcpyAsync(blocks.data(), out, sizeof(double) * blocks.size(), hipMemcpyDeviceToHost, s));
   VSL_HIP(ctx, hipMemcpyAsync(&ok, st.flag, sizeof(int), hipMemcpyDeviceToHost, s));
   VSL_HIP(ctx, hipStreamSynchronize(s));
-  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_pgo_covariance: the normal equations are not positive definite (no fixed node, or a free node without an edge)");
+  if (!ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: the normal equations are not positive definite (no fixed node, or a free node without an edge)", who);
   return VSL_OK;
 }
 }  // namespace
 
+namespace {
+int pgo_covariance(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                   const int32_t* nodes, int n_q, double* cov, int* storage);
+}
 extern "C" int vsl_pgo_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* nodes, int n_q,
                                   double* cov, int* storage) {
+  return pgo_covariance(ctx, "vsl_pgo_covariance", prob, nullptr, opt, nodes, n_q, cov, storage);
+}
+// H of the weighted problem (the fold keeps the edge order: edge_info follows the edges as it is)
+extern "C" int vsl_pgo_covariance_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                                    const int32_t* nodes, int n_q, double* cov, int* storage) {
+  return pgo_covariance(ctx, "vsl_pgo_covariance_w", prob, edge_info, opt, nodes, n_q, cov, storage);
+}
+namespace {
+int pgo_covariance(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                   const int32_t* nodes, int n_q, double* cov, int* storage) {
   int rc = pgo_validate(ctx, prob);
   if (rc) return rc;
   if (!opt || n_q < 0 || (n_q > 0 && (!nodes || !cov)))
-    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_covariance: null argument or negative count");
+    return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null argument or negative count", who);
   for (int q = 0; q < n_q; q++) {
-    if (nodes[q] < 0 || nodes[q] >= prob->n_nodes) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_covariance: node %d out of range", nodes[q]);
-    if (prob->node_fixed[nodes[q]]) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_covariance: node %d is fixed", nodes[q]);
+    if (nodes[q] < 0 || nodes[q] >= prob->n_nodes) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: node %d out of range", who, nodes[q]);
+    if (prob->node_fixed[nodes[q]]) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: node %d is fixed", who, nodes[q]);
   }
   // the route of this graph: the solve's own decision, on the host
   int nf = 0;
@@ -970,10 +1112,10 @@ extern "C" int vsl_pgo_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, con
   if (route == 2) {
     PgoFolded F;
     pgo_fold_problem(prob, free_idx, nf, F);
-    rc = pgo_cov_run(ctx, &F.prob, opt, true, q_free, col_unk, blocks, &ran);
+    rc = pgo_cov_run(ctx, who, &F.prob, edge_info, opt, true, q_free, col_unk, blocks, &ran);
     if (rc == VSL_OK && ran == 1) ran = 2;
   } else {
-    rc = pgo_cov_run(ctx, prob, opt, false, q_free, col_unk, blocks, &ran);
+    rc = pgo_cov_run(ctx, who, prob, edge_info, opt, false, q_free, col_unk, blocks, &ran);
   }
   if (rc) {
     (void)hipStreamSynchronize(ctx->stream);  // queued copies read host buffers that end here
@@ -983,6 +1125,7 @@ extern "C" int vsl_pgo_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, con
   for (int q = 0; q < n_q; q++) memcpy(cov + 36 * (size_t)q, blocks.data() + 36 * (size_t)slot[q], 36 * sizeof(double));
   return VSL_OK;
 }
+}  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
 // vsl_pgo_joint_covariance / vsl_pgo_edge_consistency: the 12 x 12 joint covariance of pairs of nodes and, on top of it,
@@ -1113,6 +1256,7 @@ struct PgoJointCall {
   bool with_cand;
   const double *cand_meas, *meas_cov;                // the edge call (meas_cov nullable)
   double *cov, *resid, *resid_cov, *chi2;            // outputs (cov: the joint call; chi2 nullable)
+  const double* edge_info = nullptr;                 // the _w calls: information matrices of the graph's own edges
 };
 
 // everything behind the validation; host_in / host_out are read / written by copies on the stream
@@ -1122,6 +1266,8 @@ int pgo_joint_run(vsl_ctx* ctx, const vsl_pgo_problem* run, const vsl_ba_options
   const std::vector<int> run_free = pgo_free_index(run, &nf);
   PgoState st;
   st.linear_only = folded;
+  st.edge_info = c.edge_info;
+  st.who = c.name;
   {
     PgoState probe;
     probe.linear_only = folded;
@@ -1247,11 +1393,27 @@ extern "C" int vsl_pgo_joint_covariance(vsl_ctx* ctx, const vsl_pgo_problem* pro
   const PgoJointCall c{"vsl_pgo_joint_covariance", pair_a, pair_b, n_pairs, false, nullptr, nullptr, cov, nullptr, nullptr, nullptr};
   return pgo_joint_call(ctx, prob, opt, c, storage);
 }
+extern "C" int vsl_pgo_joint_covariance_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                                          const int32_t* pair_a, const int32_t* pair_b, int n_pairs, double* cov, int* storage) {
+  if (!ctx) return VSL_ERR_INVALID;
+  PgoJointCall c{"vsl_pgo_joint_covariance_w", pair_a, pair_b, n_pairs, false, nullptr, nullptr, cov, nullptr, nullptr, nullptr};
+  c.edge_info = edge_info;
+  return pgo_joint_call(ctx, prob, opt, c, storage);
+}
 
 extern "C" int vsl_pgo_edge_consistency(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* cand_a,
                                         const int32_t* cand_b, const double* cand_meas, const double* meas_cov, int n_cand,
                                         double* resid, double* resid_cov, double* chi2, int* storage) {
   if (!ctx) return VSL_ERR_INVALID;
   const PgoJointCall c{"vsl_pgo_edge_consistency", cand_a, cand_b, n_cand, true, cand_meas, meas_cov, nullptr, resid, resid_cov, chi2};
+  return pgo_joint_call(ctx, prob, opt, c, storage);
+}
+// edge_info shapes H and so Sigma; the candidate's residual stays unwhitened, meas_cov keeps its meaning
+extern "C" int vsl_pgo_edge_consistency_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                                          const int32_t* cand_a, const int32_t* cand_b, const double* cand_meas, const double* meas_cov,
+                                          int n_cand, double* resid, double* resid_cov, double* chi2, int* storage) {
+  if (!ctx) return VSL_ERR_INVALID;
+  PgoJointCall c{"vsl_pgo_edge_consistency_w", cand_a, cand_b, n_cand, true, cand_meas, meas_cov, nullptr, resid, resid_cov, chi2};
+  c.edge_info = edge_info;
   return pgo_joint_call(ctx, prob, opt, c, storage);
 }
