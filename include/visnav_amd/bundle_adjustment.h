@@ -15,9 +15,14 @@
 #include <thread>
 #include <unordered_map>
 #include <map>
+#include <utility>
 #include <vector>
 
 #include "keypoints.h"  // context holder + types
+
+// relative_pose_covariance (below) references its entry points weakly, like the _w ones of loop_closure.h
+#pragma weak vsl_ba_relative_pose_covariance
+#pragma weak vsl_global_ba_relative_pose_covariance
 
 namespace visnav {
 
@@ -305,6 +310,93 @@ inline int global_bundle_adjustment_covariance(const Corners& feature_corners, c
   return amd::run_ba_covariance<true>("global_bundle_adjustment_covariance", feature_corners, options.use_huber,
                                       options.huber_parameter, fixed_cameras, calib_cam, cameras, landmarks, query_cameras,
                                       query_landmarks, pose_cov_out, landmark_cov_out, storage_out);
+}
+
+// Covariance and information of the relative poses of camera pairs under the bundle adjustment's posterior
+// (vsl_ba_relative_pose_covariance / vsl_global_ba_relative_pose_covariance): the weights of pose-graph edges whose
+// measurement is read off the map.  Nothing is optimised.  The problem is flattened by flatten_ba exactly as for
+// bundle_adjustment (BundleAdjustmentOptions: inlier observations, the dense route) or global_bundle_adjustment
+// (GlobalBundleAdjustmentOptions: all observations, dense or linear band, *storage_out = 0 / 1).  pairs: (a, b) with a
+// the pose-graph functor's T_w_c and b its T_w_n; both must be cameras of `cameras` (else std::out_of_range), a != b,
+// not both fixed (else std::runtime_error from the call).  out[q]: measurement = log(T_a^-1 T_b) as (upsilon, omega),
+// cov = the covariance of the pose-graph residual, info = cov^-1; valid = false (info NaN) where cov is singular to
+// working precision.  Returns the number of such pairs; std::domain_error when the reduced camera system is singular
+// (no fixed camera).  Each info is a marginal: edges that share a camera are correlated, which per-edge matrices
+// cannot express.  The new C symbols are referenced weakly: a build of this header on a C ABI without them links, and
+// calling these functions there throws.
+struct RelativePoseCovariance {
+  double measurement[6];
+  PoseCovariance cov, info;
+  bool valid = false;
+};
+namespace amd {
+template <bool kAllObs>
+inline int run_relative_pose_covariance(const char* what, const Corners& feature_corners, bool use_huber, double huber_parameter,
+                                        const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                        Landmarks& landmarks, const std::vector<std::pair<FrameCamId, FrameCamId>>& pairs,
+                                        std::vector<RelativePoseCovariance>& out, int* storage_out) {
+  out.clear();
+  if (kAllObs ? !vsl_global_ba_relative_pose_covariance : !vsl_ba_relative_pose_covariance)
+    throw std::runtime_error(std::string(what) + ": this library has no relative-pose covariances");
+  BaFlat f;
+  if (!flatten_ba<kAllObs>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f))
+    throw std::out_of_range(std::string(what) + ": the map has no observation");
+  std::vector<int32_t> a, b;
+  auto index = [&](const FrameCamId& id) {
+    const auto it = std::lower_bound(f.cam_id.begin(), f.cam_id.end(), id);
+    if (it == f.cam_id.end() || !(*it == id)) throw std::out_of_range(std::string(what) + ": unknown camera");
+    return (int32_t)(it - f.cam_id.begin());
+  };
+  for (const auto& p : pairs) {
+    a.push_back(index(p.first));
+    b.push_back(index(p.second));
+  }
+  vsl_ba_options opt;
+  opt.use_huber = use_huber ? 1 : 0;
+  opt.huber_parameter = huber_parameter;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  const size_t n = pairs.size();
+  std::vector<double> meas(6 * n), cov(36 * n), info(36 * n);
+  int n_singular = 0;
+  const int rc = kAllObs ? vsl_global_ba_relative_pose_covariance(ctx(), &f.prob, &opt, a.data(), b.data(), (int)n, nullptr, meas.data(),
+                                                                  cov.data(), info.data(), &n_singular, storage_out)
+                         : vsl_ba_relative_pose_covariance(ctx(), &f.prob, &opt, a.data(), b.data(), (int)n, nullptr, meas.data(),
+                                                           cov.data(), info.data(), &n_singular);
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(ctx()));
+  check(rc, what);
+  out.resize(n);
+  for (size_t q = 0; q < n; q++) {
+    RelativePoseCovariance& r = out[q];
+    r.valid = true;
+    for (int i = 0; i < 6; i++) {
+      r.measurement[i] = meas[6 * q + i];
+      for (int j = 0; j < 6; j++) {
+        r.cov(i, j) = cov[36 * q + 6 * i + j];
+        r.info(i, j) = info[36 * q + 6 * i + j];
+        if (!(r.info(i, j) == r.info(i, j))) r.valid = false;  // NaN: the singular pair
+      }
+    }
+  }
+  return n_singular;
+}
+}  // namespace amd
+
+inline int relative_pose_covariance(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                    const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                    Landmarks& landmarks, const std::vector<std::pair<FrameCamId, FrameCamId>>& pairs,
+                                    std::vector<RelativePoseCovariance>& out) {
+  return amd::run_relative_pose_covariance<false>("relative_pose_covariance", feature_corners, options.use_huber,
+                                                  options.huber_parameter, fixed_cameras, calib_cam, cameras, landmarks, pairs, out,
+                                                  nullptr);
+}
+inline int relative_pose_covariance(const Corners& feature_corners, const GlobalBundleAdjustmentOptions& options,
+                                    const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                    Landmarks& landmarks, const std::vector<std::pair<FrameCamId, FrameCamId>>& pairs,
+                                    std::vector<RelativePoseCovariance>& out, int* storage_out = nullptr) {
+  return amd::run_relative_pose_covariance<true>("relative_pose_covariance (global)", feature_corners, options.use_huber,
+                                                 options.huber_parameter, fixed_cameras, calib_cam, cameras, landmarks, pairs, out,
+                                                 storage_out);
 }
 
 }  // namespace visnav

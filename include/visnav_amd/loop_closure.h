@@ -18,6 +18,7 @@
 #include <cmath>
 #include <functional>
 #include <map>
+#include <memory>
 #include <set>
 #include <vector>
 
@@ -253,6 +254,59 @@ inline void pose_graph_optimization(const FrameCamId& cur_kf_fcid, Camera& cur_k
                                     const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
                                     const LoopClosureOptions& options) {
   pose_graph_optimization(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, EdgeInformation());
+}
+
+// The EdgeInformation of that pose graph from the bundle-adjusted map: the edges amd::flatten_pose_graph creates for
+// this current keyframe and loop candidate are enumerated, and those whose measurement is a relative pose of the map --
+// spanning-tree and covisibility edges between two cameras of the bundle-adjustment problem, not both fixed -- are
+// queried in ONE call of relative_pose_covariance (the global overload: all observations, dense or band).  The returned
+// callable answers those edges with Omega = the inverse covariance of the relative pose under the BA posterior, and every
+// other edge with default_information: the Sim(3) loop edge (current keyframe -> loop candidate: its measurement does
+// not come from the map), a pair that is not in the BA problem with both cameras or has both of them fixed, and a pair
+// whose covariance is singular.  *n_map_edges (nullable): the edges answered from the map.
+namespace amd {
+// the distinct (a, b) of the graph's edges that the map can answer, in edge order
+inline std::vector<std::pair<FrameCamId, FrameCamId>> map_edge_pairs(const FrameCamId& cur_kf_fcid, Camera& cur_kf,
+                                                                      const FrameCamId& loop_candidate_fcid, const Sophus::SE3d& sim3,
+                                                                      Cameras& keyframes, int essential_threshold,
+                                                                      const LoopClosureOptions& options,
+                                                                      const std::set<FrameCamId>& fixed_cameras, const Cameras& cameras) {
+  PgoFlat f;
+  flatten_pose_graph(cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, f);
+  std::vector<FrameCamId> id_of(f.node_cam.size(), cur_kf_fcid);
+  for (const auto& kv : f.node_of) id_of[kv.second] = kv.first;
+  std::vector<std::pair<FrameCamId, FrameCamId>> pairs;
+  std::set<std::pair<FrameCamId, FrameCamId>> seen;
+  for (size_t e = 0; e < f.ea.size(); e++) {
+    const FrameCamId &a = id_of[f.ea[e]], &b = id_of[f.eb[e]];
+    if (a == b || (a == cur_kf_fcid && b == loop_candidate_fcid)) continue;
+    if (!cameras.count(a) || !cameras.count(b) || (fixed_cameras.count(a) && fixed_cameras.count(b))) continue;
+    if (seen.insert(std::make_pair(a, b)).second) pairs.emplace_back(a, b);
+  }
+  return pairs;
+}
+}  // namespace amd
+inline EdgeInformation map_edge_information(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
+                                            const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
+                                            const LoopClosureOptions& options, const Corners& feature_corners,
+                                            const GlobalBundleAdjustmentOptions& ba_options,
+                                            const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                            Landmarks& landmarks, const PoseCovariance& default_information,
+                                            size_t* n_map_edges = nullptr, int* storage_out = nullptr) {
+  const std::vector<std::pair<FrameCamId, FrameCamId>> pairs = amd::map_edge_pairs(
+      cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, fixed_cameras, cameras);
+  auto table = std::make_shared<std::map<std::pair<FrameCamId, FrameCamId>, PoseCovariance>>();
+  if (!pairs.empty()) {
+    std::vector<RelativePoseCovariance> out;
+    relative_pose_covariance(feature_corners, ba_options, fixed_cameras, calib_cam, cameras, landmarks, pairs, out, storage_out);
+    for (size_t q = 0; q < pairs.size(); q++)
+      if (out[q].valid) table->emplace(pairs[q], out[q].info);
+  }
+  if (n_map_edges) *n_map_edges = table->size();
+  return [table, default_information](const FrameCamId& a, const FrameCamId& b) {
+    const auto it = table->find(std::make_pair(a, b));
+    return it == table->end() ? default_information : it->second;
+  };
 }
 
 // Marginal covariances of the keyframes of that pose graph as it stands (vsl_pgo_covariance; the reference has no

@@ -241,6 +241,7 @@ int vsl_ctx_set_tie_eps(vsl_ctx* ctx, double eps);
  *   "pgo_cov_no_band_read" (0/1)    vsl_pgo_joint_covariance / vsl_pgo_edge_consistency on the band routes: unit columns
  *                                   are solved for in-band pairs as well instead of reading the band of the inverse
  *                                   (agrees to the tolerance, not bit for bit)
+ *   "ba_cov_no_band_read" (0/1)     the same for vsl_global_ba_relative_pose_covariance on its band route
  *   "ba_schur_atomics" (0/1)        large-system Schur complement by fp64 atomics instead of the per-block gather
  *   "ba_no_fused" (0/1)             local windows (<= 21 free cameras) by the operator-by-operator kernels instead of the
  *                                   fused four-launch iteration (ba_fused.hip)
@@ -477,6 +478,54 @@ int vsl_global_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl
                              const int32_t* cams, int n_cam_q, double* cov_pose,   /* [36*n_cam_q] row-major */
                              const int32_t* lms,  int n_lm_q,  double* cov_point,  /* [9*n_lm_q]   row-major */
                              int* n_degenerate, int* storage);
+
+/* Covariance and information of RELATIVE poses under the bundle adjustment's posterior: the weights of pose-graph edges
+ * whose measurement is read off the bundle-adjusted map (edge_info of the _w pose-graph calls, meas_cov of
+ * vsl_pgo_edge_consistency).  Nothing is optimised, prob->poses / points are only read; S is exactly the S of
+ * vsl_ba_linearize (Huber corrector when opt->use_huber, no Jacobi scaling, no damping), as for vsl_ba_covariance.
+ * Per pair q, a = pair_a[q], b = pair_b[q] (CAMERA ids of prob, not free indices); every output is nullable:
+ *   joint [n][144]  [[Sigma_aa, Sigma_ab], [Sigma_ba, Sigma_bb]], 12 x 12 row-major: the blocks of S^-1 (= the pose-pose
+ *                   blocks of H^-1), tangent (upsilon, omega) of T * exp(delta).  One of the two cameras may be fixed:
+ *                   its rows and columns are exactly 0.0.  Exactly symmetric; (a, b) and (b, a) return the same bits with
+ *                   the blocks swapped and transposed; the diagonal blocks are the bits vsl_ba_covariance /
+ *                   vsl_global_ba_covariance return for that camera on the same route; a pair's result depends on the
+ *                   problem and the route alone (duplicates and permutations allowed); two calls return the same bits.
+ *   meas  [n][6]    log(T_a^-1 T_b) as (upsilon, omega), by the pose-graph functor's own device code: what goes into
+ *                   vsl_pgo_problem::edge_meas (a = the functor's T_w_c, b = its T_w_n).
+ *   cov   [n][36]   Sigma_r = J Sigma_joint J^T, J = [J_a J_b] the 6 x 6 Jacobians of the pose-graph residual
+ *                   r = log(T_a^-1 T_b) - m with respect to the right perturbations of the two poses (they do not depend
+ *                   on m): resid_cov exactly as vsl_pgo_edge_consistency defines it, with the bundle adjustment's
+ *                   posterior in place of the pose graph's.  The terms of a fixed camera are dropped.  Exactly symmetric
+ *                   (the two mirror sums averaged, every sum in ascending index order).
+ *   info  [n][36]   Omega = Sigma_r^-1 by a 6 x 6 Cholesky factorisation and inverse, exactly symmetric.  A pivot
+ *                   L_ii^2 <= 2^-36 Sigma_r,ii or a non-finite one (the rule of vsl_ba_covariance) writes 36 NaN for the
+ *                   pair and counts it in *n_singular (nullable); the call still returns VSL_OK.  Omega itself is put
+ *                   through the positive-definiteness test of the _w calls before it is returned (failing it is
+ *                   counted as singular as well): a finite Omega is one vsl_pose_graph_optimize_w accepts.
+ * EACH Omega IS A MARGINAL: edges that share a camera are correlated under the posterior, and those correlations
+ * between different edges are not represented by per-edge information matrices.  Landmark cross-covariances are not
+ * offered.
+ * a == b, both cameras fixed or an id out of range give VSL_ERR_INVALID (vsl_last_error names the first offending
+ * pair); so do a null pair list with n_pairs > 0, a negative count and an empty problem.  n_pairs = 0, or all four
+ * outputs NULL, validates, launches nothing and returns VSL_OK.  S not positive definite to working precision (a free
+ * gauge) gives VSL_ERR_NUMERIC.
+ * vsl_ba_relative_pose_covariance is the DENSE route for a local window: the chain of vsl_ba_covariance; every distinct
+ * queried free camera gets its six unit columns, a cross-block entry is the average of its two mirror entries.
+ * vsl_global_ba_relative_pose_covariance takes the layout decision of vsl_global_ba_covariance and reports it in *storage
+ * (nullable, also with n_pairs = 0): 0 = dense, as above bit for bit; 1 = linear band in reverse Cuthill-McKee order
+ * (never cyclic).  There, with f the band position of a free camera and bw the half bandwidth: one camera fixed -- the
+ * other's diagonal block is read from the band of S^-1; 6 |f_a - f_b| + 5 <= bw (every covisible pair) -- the whole cross
+ * block is read from the band (stored lower triangle: no rounding choice); every other pair (a loop edge, a far pair)
+ * takes true out-of-band entries from a band unit-column solve of the six columns of the camera with the larger f.
+ * Diagnostic "ba_cov_no_band_read": in-band pairs through the solve as well (agrees to the tolerance, not bit for bit). */
+int vsl_ba_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
+                                    const int32_t* pair_a, const int32_t* pair_b, int n_pairs,
+                                    double* joint /* [n][144] */, double* meas /* [n][6] */, double* cov /* [n][36] */,
+                                    double* info /* [n][36] */, int* n_singular);
+int vsl_global_ba_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
+                                           const int32_t* pair_a, const int32_t* pair_b, int n_pairs,
+                                           double* joint, double* meas, double* cov, double* info, int* n_singular,
+                                           int* storage);
 
 /* ---- multi-GPU global bundle adjustment ----
  * visnav::global_bundle_adjustment (include/visnav/loop_closure_utils.h:672-748) over `world` ranks, one process per

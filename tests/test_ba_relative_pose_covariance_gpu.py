@@ -1,0 +1,378 @@
+"""GPU: vsl_ba_relative_pose_covariance and vsl_global_ba_relative_pose_covariance (visual-slam_amd/csrc/ba_cov.hip,
+ba_relpose_kernel in pgo.hip) against tests/ba_relpose_ref.py, whose docstring derives the four tolerances (joint:
+ba_cov_ref.Ref.tol; cov: 144 max|J|^2 Ref.tol; info: 36 max|Omega|^2 tol_cov + 64 cond(Sigma_r) 2^-52 max|Omega|; meas:
+pgo_ref.GPU_TOL max|meas|).  The measured maxima are printed beside the bounds (-s).  Bit-for-bit claims are asserted
+with array_equal.
+
+Shapes.  Dense route: 6 free cameras / 60 landmarks (36 unknowns, camera models 0 .. 3, Huber on and off) and 20 free
+cameras (120 unknowns: four panels of 32, one ragged), all pairs, pairs with a fixed camera included.  Band route: the
+open chain of ba_cov_band_ref (348 unknowns, bw = 59) with pairs of all three classes, and the ring (band position !=
+camera id) against inv(S) of Context.ba_linearize under the rule of the ring test of the covariance call."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import ba_cov_band_ref as B
+import ba_cov_ref as R
+import ba_relpose_ref as RP
+import pgo_joint_ref as jr
+import pgo_ref as pg
+
+pytestmark = pytest.mark.gpu
+
+_cache = {}
+
+
+def _small(orc, vsl, synth, model=0, huber=True, n_free=6, seed=5):
+    key = ("small", model, huber, n_free, seed)
+    if key not in _cache:
+        d = R.problem(synth, seed, n_free=n_free, n_lms=60, model=model)
+        rr = RP.RelRef(R.Ref(orc, R.arrays(orc, d), use_huber=huber), d["poses"], d["cam_fixed"])
+        _cache[key] = (d, R.arrays(vsl, d), rr)
+    return _cache[key]
+
+
+def _chain(orc, vsl, synth):
+    if "chain" not in _cache:
+        d = B.open_chain(synth)
+        _cache["chain"] = (d, R.arrays(vsl, d), RP.RelRef(B.chain_ref(orc, synth), d["poses"], d["cam_fixed"]))
+    return _cache["chain"]
+
+
+# open chain, cameras 0 and 1 fixed, band position = free index = camera id - 2.  Adjacent pairs: READ.  (2, 59), (10, 40):
+# SOLVE.  Pairs with camera 0 / 1: ONE_FIXED.  (12, 21): 6 * 9 + 5 = 59, the last distance inside the band; (12, 22) the
+# first outside.  (7, 8): free indices 5 | 6, unknowns 30 .. 41 straddle the 32-column panel boundary.
+CHAIN_PAIRS = ([(a, a + 2) for a in range(0, 58, 2)] + [(a, a + 1) for a in range(2, 58, 9)] +
+               [(2, 59), (10, 40), (40, 10), (0, 7), (33, 1), (59, 2), (12, 21), (12, 22), (22, 12), (7, 8), (58, 59)])
+
+
+def _chain_full(ctx, orc, vsl, synth):
+    if "chain_full" not in _cache:
+        _, arr, _ = _chain(orc, vsl, synth)
+        out = ctx.global_ba_relative_pose_covariance(arr, CHAIN_PAIRS)
+        assert out[5] == 1 and out[4] == 0
+        _cache["chain_full"] = out
+    return _cache["chain_full"]
+
+
+def _errors(rr, pairs, out, label):
+    """Asserts the four tolerances pair by pair; returns and prints the largest error / bound ratios."""
+    joint, meas, cov, info = out[:4]
+    rr.prepare(pairs)
+    worst = dict(joint=(0, 0, 0), meas=(0, 0, 0), cov=(0, 0, 0), info=(0, 0, 0))
+    for k, (a, b) in enumerate(pairs):
+        p = rr.pair(a, b)
+        for name, got, want, tol in (("joint", joint[k], p.joint, p.tol_joint), ("meas", meas[k], p.meas, p.tol_meas),
+                                     ("cov", cov[k], p.cov, p.tol_cov), ("info", info[k], p.info, p.tol_info)):
+            e = float(np.abs(got - want).max())
+            if e / tol >= worst[name][0]:
+                worst[name] = (e / tol, e, tol)
+            assert e <= tol, (label, name, (a, b), e, tol)
+    print("%s, %d pairs: " % (label, len(pairs)) +
+          "; ".join("%s err %.3g (bound %.3g, ratio %.2g)" % (n, w[1], w[2], w[0]) for n, w in worst.items()))
+    return worst
+
+
+def _exact_properties(arr, pairs, out):
+    joint, meas, cov, info = out[:4]
+    assert np.array_equal(joint, joint.transpose(0, 2, 1))
+    assert np.array_equal(cov, cov.transpose(0, 2, 1)) and np.array_equal(info, info.transpose(0, 2, 1))
+    for k, (a, b) in enumerate(pairs):
+        for side, cam in ((0, a), (1, b)):
+            blk = slice(6 * side, 6 * side + 6)
+            if arr.cam_fixed[cam]:
+                assert not joint[k][blk].any() and not joint[k][:, blk].any()
+                assert not np.signbit(joint[k][blk]).any() and not np.signbit(joint[k][:, blk]).any()   # exactly +0.0
+
+
+def _diagonal_blocks(pairs, joint, arr, pose_cov_of):
+    """The diagonal blocks are the bytes of the pose-covariance call on the same route."""
+    free = sorted({c for p in pairs for c in p if not arr.cam_fixed[c]})
+    cp = pose_cov_of(free)
+    at = {c: k for k, c in enumerate(free)}
+    for k, (a, b) in enumerate(pairs):
+        for side, cam in ((0, a), (1, b)):
+            if not arr.cam_fixed[cam]:
+                blk = slice(6 * side, 6 * side + 6)
+                assert joint[k][blk, blk].tobytes() == cp[at[cam]].tobytes(), (a, b)
+
+
+# ------------------------------------------------------------------------------------------------ 1. dense route
+@pytest.mark.parametrize("model", [0, 1, 2, 3])
+@pytest.mark.parametrize("huber", [True, False])
+def test_local_window_all_pairs(ctx, orc, vsl, synth, model, huber):
+    d, arr, rr = _small(orc, vsl, synth, model, huber)
+    pairs = RP.all_pairs(d["cam_fixed"])
+    assert len(pairs) == 27 and any(d["cam_fixed"][a] for a, _ in pairs)
+    poses, points = arr.poses.copy(), arr.points.copy()
+    out = ctx.ba_relative_pose_covariance(arr, pairs, use_huber=huber)
+    assert out[4] == 0 and np.array_equal(arr.poses, poses) and np.array_equal(arr.points, points)
+    _errors(rr, pairs, out, "6 free, model %d, huber %d" % (model, huber))
+    _exact_properties(arr, pairs, out)
+    _diagonal_blocks(pairs, out[0], arr, lambda cams: ctx.ba_covariance(arr, cams=cams, use_huber=huber)[0])
+    # the global call takes the dense route here: the same bits
+    g = ctx.global_ba_relative_pose_covariance(arr, pairs, use_huber=huber)
+    assert g[5] == 0 and g[4] == 0 and all(np.array_equal(x, y) for x, y in zip(out[:4], g[:4]))
+
+
+def test_window_of_twenty_all_pairs(ctx, orc, vsl, synth):
+    d, arr, rr = _small(orc, vsl, synth, n_free=20, seed=6)
+    pairs = RP.all_pairs(d["cam_fixed"])
+    assert len(pairs) == 230 and arr.n_free == 20
+    out = ctx.ba_relative_pose_covariance(arr, pairs)
+    assert out[4] == 0
+    _errors(rr, pairs, out, "20 free")
+    _exact_properties(arr, pairs, out)
+    _diagonal_blocks(pairs, out[0], arr, lambda cams: ctx.ba_covariance(arr, cams=cams)[0])
+
+
+def test_swapped_subset_permuted_duplicated_and_repeated_queries(ctx, orc, vsl, synth):
+    d, arr, rr = _small(orc, vsl, synth)
+    pairs = RP.all_pairs(d["cam_fixed"])
+    full = ctx.ba_relative_pose_covariance(arr, pairs)
+    again = ctx.ba_relative_pose_covariance(arr, pairs)
+    assert all(np.array_equal(x, y) for x, y in zip(full[:4], again[:4]))
+    swapped = [(b, a) for a, b in pairs]
+    sw = ctx.ba_relative_pose_covariance(arr, swapped)
+    perm = np.r_[6:12, 0:6]
+    assert np.array_equal(sw[0], full[0][:, perm][:, :, perm])          # blocks swapped = blocks swapped and transposed
+    _errors(rr, swapped, sw, "reversed edges")                          # the reversed edge has its own J
+    assert np.array_equal(sw[2], sw[2].transpose(0, 2, 1))
+    pick = [13, 2, 26, 2, 13, 0]
+    sub = ctx.ba_relative_pose_covariance(arr, [pairs[k] for k in pick])
+    assert all(np.array_equal(x, y[pick]) for x, y in zip(sub[:4], full[:4]))
+    order = np.random.default_rng(1).permutation(len(pairs))
+    pm = ctx.ba_relative_pose_covariance(arr, [pairs[k] for k in order])
+    assert all(np.array_equal(x, y[order]) for x, y in zip(pm[:4], full[:4]))
+    one = ctx.ba_relative_pose_covariance(arr, [pairs[20]])
+    assert all(np.array_equal(x[0], y[20]) for x, y in zip(one[:4], full[:4]))
+
+
+# ------------------------------------------------------------------------------------------------- 2. band route
+def test_open_chain_band_route(ctx, orc, vsl, synth):
+    d, arr, rr = _chain(orc, vsl, synth)
+    out = _chain_full(ctx, orc, vsl, synth)
+    _errors(rr, CHAIN_PAIRS, out, "open chain, band")
+    _exact_properties(arr, CHAIN_PAIRS, out)
+    _diagonal_blocks(CHAIN_PAIRS, out[0], arr, lambda cams: ctx.global_ba_covariance(arr, cams=cams)[0])
+    # subset, duplicates, a permutation, a swapped out-of-band pair, a second call
+    pick = [40, 3, 40, 29, 31, 36, 0]
+    sub = ctx.global_ba_relative_pose_covariance(arr, [CHAIN_PAIRS[k] for k in pick])
+    assert sub[5] == 1 and all(np.array_equal(x, y[pick]) for x, y in zip(sub[:4], out[:4]))
+    perm = np.r_[6:12, 0:6]
+    k1, k2 = CHAIN_PAIRS.index((10, 40)), CHAIN_PAIRS.index((40, 10))
+    assert np.array_equal(out[0][k2], out[0][k1][perm][:, perm])
+    k1, k2 = CHAIN_PAIRS.index((12, 22)), CHAIN_PAIRS.index((22, 12))
+    assert np.array_equal(out[0][k2], out[0][k1][perm][:, perm])
+    again = ctx.global_ba_relative_pose_covariance(arr, CHAIN_PAIRS)
+    assert all(np.array_equal(x, y) for x, y in zip(again[:4], out[:4]))
+
+
+def test_band_read_and_band_solve_agree(ctx, orc, vsl, synth):
+    d, arr, rr = _chain(orc, vsl, synth)
+    out = _chain_full(ctx, orc, vsl, synth)
+    ctx.set_diagnostic("ba_cov_no_band_read", 1)
+    try:
+        solved = ctx.global_ba_relative_pose_covariance(arr, CHAIN_PAIRS)
+    finally:
+        ctx.set_diagnostic("ba_cov_no_band_read", 0)
+    assert solved[5] == 1 and solved[4] == 0
+    _errors(rr, CHAIN_PAIRS, solved, "open chain, every pair solved")
+    diff = float(np.abs(solved[0] - out[0]).max())
+    in_band = [k for k, (a, b) in enumerate(CHAIN_PAIRS) if a > 1 and b > 1 and 6 * abs(a - b) + 5 <= 59]
+    assert len(in_band) >= 30 and any(not np.array_equal(solved[0][k], out[0][k]) for k in in_band)   # another path
+    print("band read vs band solve: joint %.3g (bound %.3g)" % (diff, rr.ref.tol))
+    assert diff <= rr.ref.tol
+    # the out-of-band pairs and the pairs with a fixed camera take the same path either way: the same bits
+    for k, (a, b) in enumerate(CHAIN_PAIRS):
+        if k not in in_band:
+            assert np.array_equal(solved[0][k], out[0][k]), (a, b)
+
+
+def test_forced_dense_route_agrees_with_the_band(ctx, orc, vsl, synth):
+    d, arr, rr = _chain(orc, vsl, synth)
+    out = _chain_full(ctx, orc, vsl, synth)
+    ctx.set_diagnostic("ba_force_dense", 1)
+    try:
+        dense = ctx.global_ba_relative_pose_covariance(arr, CHAIN_PAIRS)
+        local = ctx.ba_relative_pose_covariance(arr, CHAIN_PAIRS)
+    finally:
+        ctx.set_diagnostic("ba_force_dense", 0)
+    assert dense[5] == 0 and dense[4] == 0
+    assert all(np.array_equal(x, y) for x, y in zip(dense[:4], local[:4]))
+    _errors(rr, CHAIN_PAIRS, dense, "open chain, dense")
+    diff = float(np.abs(dense[0] - out[0]).max())
+    print("band vs dense route: joint %.3g (bound %.3g)" % (diff, rr.ref.tol))
+    assert diff <= rr.ref.tol
+    _diagonal_blocks(CHAIN_PAIRS, local[0], arr, lambda cams: ctx.ba_covariance(arr, cams=cams)[0])
+
+
+def test_ring_band_position_is_not_the_camera_id(ctx, vsl, synth):
+    d = B.ring(synth)
+    arr = R.arrays(vsl, d)
+    assert arr.cam_fixed[0] and arr.cam_fixed[1] and arr.n_free == 126
+    # neighbours along the ring, the pair that closes it, a far pair across it, a fixed camera either way round
+    pairs = [(a, a + 2) for a in range(2, 126, 8)] + [(2, 126), (127, 3), (2, 66), (65, 5), (0, 64), (30, 1), (126, 0)]
+    out = ctx.global_ba_relative_pose_covariance(arr, pairs)
+    assert out[5] == 1 and out[4] == 0
+    S, _, _ = ctx.ba_linearize(arr)
+    Si = np.linalg.inv(S)
+    tol = 64 * np.linalg.cond(S) * R.EPS * np.abs(Si).max()
+    worst = 0.0
+    for k, (a, b) in enumerate(pairs):
+        want = np.zeros((12, 12))
+        for x, cx in enumerate((a, b)):
+            for y, cy in enumerate((a, b)):
+                if cx > 1 and cy > 1:
+                    want[6 * x:6 * x + 6, 6 * y:6 * y + 6] = Si[6 * (cx - 2):6 * (cx - 2) + 6, 6 * (cy - 2):6 * (cy - 2) + 6]
+        worst = max(worst, float(np.abs(out[0][k] - want).max()))
+    print("ring: joint err %.3g (bound %.3g)" % (worst, tol))
+    assert worst <= tol
+    # meas, cov, info through the reference's propagation (long-double J of pgo_ref at the CAMERAS' poses) of inv(S):
+    # a mix-up of camera id and band position in the propagation kernel would show here
+    class _SRef:
+        Sigma, cam_pos = Si, {c: c - 2 for c in range(2, 128)}
+    _SRef.tol = tol
+    _errors(RP.RelRef(_SRef, d["poses"], d["cam_fixed"]), pairs, out, "ring, against inv(S)")
+    _exact_properties(arr, pairs, out)
+    _diagonal_blocks(pairs, out[0], arr, lambda cams: ctx.global_ba_covariance(arr, cams=cams)[0])
+    assert np.all(np.linalg.eigvalsh(out[2]) > 0) and np.all(np.linalg.eigvalsh(out[3]) > 0)
+    ctx.set_diagnostic("ba_cov_no_band_read", 1)
+    try:
+        solved = ctx.global_ba_relative_pose_covariance(arr, pairs)
+    finally:
+        ctx.set_diagnostic("ba_cov_no_band_read", 0)
+    assert solved[5] == 1 and float(np.abs(solved[0] - out[0]).max()) <= tol
+    # the far pair is solved for the camera further down the BAND, whichever way round it is given
+    perm = np.r_[6:12, 0:6]
+    sw = ctx.global_ba_relative_pose_covariance(arr, [(66, 2), (5, 65)])
+    assert np.array_equal(sw[0][0], out[0][pairs.index((2, 66))][perm][:, perm])
+    assert np.array_equal(sw[0][1], out[0][pairs.index((65, 5))][perm][:, perm])
+
+
+# ------------------------------------------------------------------------------------------ 3. Loewner monotonicity
+def test_fewer_observations_never_shrink_the_covariance(ctx, orc, vsl, synth):
+    d, arr, rr = _small(orc, vsl, synth)
+    rng = np.random.default_rng(3)
+    cnt = np.bincount(d["obs_lm"], minlength=len(d["points"]))
+    drop = np.zeros(len(d["obs_lm"]), bool)
+    for i in rng.permutation(len(drop)):
+        if drop.sum() >= len(drop) // 3:
+            break
+        if cnt[d["obs_lm"][i]] > 2:
+            drop[i] = True
+            cnt[d["obs_lm"][i]] -= 1
+    assert drop.sum() == len(drop) // 3 and cnt.min() >= 2
+    e = R.drop_observations(d, drop)
+    rr2 = RP.RelRef(R.Ref(orc, R.arrays(orc, e)), e["poses"], e["cam_fixed"])
+    pairs = RP.all_pairs(d["cam_fixed"])
+    full = ctx.ba_relative_pose_covariance(arr, pairs)
+    less = ctx.ba_relative_pose_covariance(R.arrays(vsl, e), pairs)
+    assert less[4] == 0
+    worst = np.inf
+    for k, (a, b) in enumerate(pairs):
+        lam = float(np.linalg.eigvalsh(less[2][k] - full[2][k])[0])
+        bound = rr.pair(a, b).tol_cov + rr2.pair(a, b).tol_cov
+        worst = min(worst, lam / bound)
+        assert lam >= -bound, (a, b, lam, bound)
+    print("Loewner: smallest eigenvalue of the difference / the bound: %.3g (>= -1 needed)" % worst)
+
+
+# ----------------------------------------------------------------------------------------------------- 4. refusals
+def test_refusals(ctx, vsl, synth, orc):
+    d, arr, _ = _small(orc, vsl, synth)
+    assert list(np.flatnonzero(arr.cam_fixed)) == [0, 1]
+    for pairs, word in (([(2, 3), (4, 4)], "pair 1"), ([(2, 3), (3, 4), (0, 1)], "pair 2"), ([(8, 2)], "pair 0"),
+                        ([(2, 3), (-1, 2)], "pair 1")):
+        for call in (ctx.ba_relative_pose_covariance, ctx.global_ba_relative_pose_covariance):
+            with pytest.raises(vsl.VslError) as e:
+                call(arr, pairs)
+            assert e.value.code == -1 and word in str(e.value), str(e.value)
+    L, st, o = ctx.L, ctx._ba_struct(arr), ctx._ba_opts(True, 1.0, 0, 0)
+    a, b = np.array([2, 3], np.int32), np.array([3, 4], np.int32)
+    ap, bp = a.ctypes.data_as(C.POINTER(C.c_int32)), b.ctypes.data_as(C.POINTER(C.c_int32))
+    storage, ns = C.c_int(-1), C.c_int(-1)
+    # negative count, a null pair list
+    assert L.vsl_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), ap, bp, -1, None, None, None, None, None) == -1
+    assert L.vsl_global_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), None, bp, 2, None, None, None, None, None, None) == -1
+    # n_pairs = 0: nothing is launched, the route is reported
+    assert L.vsl_global_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), None, None, 0, None, None, None, None,
+                                                    C.byref(ns), C.byref(storage)) == 0
+    assert storage.value == 0 and ns.value == 0
+    assert L.vsl_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), None, None, 0, None, None, None, None, None) == 0
+    # all outputs null: validates (also the pairs) and returns
+    assert L.vsl_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), ap, bp, 2, None, None, None, None, None) == 0
+    a[1] = 4                                                 # (4, 4)
+    assert L.vsl_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), ap, bp, 2, None, None, None, None, None) == -1
+    a[:] = [2, 3]
+    # a single output: the bits of the full call
+    full = ctx.ba_relative_pose_covariance(arr, [(2, 3), (3, 4)])
+    info = np.full((2, 6, 6), 7.0)
+    assert L.vsl_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), ap, bp, 2, None, None, None,
+                                             info.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ns)) == 0
+    assert np.array_equal(info, full[3]) and ns.value == 0
+    # an empty problem
+    st.n_obs = 0
+    assert L.vsl_ba_relative_pose_covariance(ctx.h, C.byref(st), C.byref(o), ap, bp, 2, None, None, None, None, None) == -1
+    # the free gauge: VSL_ERR_NUMERIC on both routes, nothing written
+    for dd, call in ((dict(d), ctx.ba_relative_pose_covariance), (B.open_chain(synth, fixed=()), ctx.global_ba_relative_pose_covariance)):
+        dd["cam_fixed"] = np.zeros(len(dd["poses"]), np.uint8)
+        with pytest.raises(vsl.VslError) as e:
+            call(R.arrays(vsl, dd), [(2, 3), (0, 5)])
+        assert e.value.code == -7
+    # band route: n_pairs = 0 reports storage 1
+    _, chain, _ = _chain(orc, vsl, synth)
+    out = ctx.global_ba_relative_pose_covariance(chain, np.zeros((0, 2), np.int32))
+    assert out[5] == 1 and out[0].shape == (0, 12, 12) and out[4] == 0
+
+
+# ------------------------------------------------------------------------------------------------- 5. the arena loan
+def test_a_solve_has_the_same_bits_as_on_a_fresh_context(ctx, orc, vsl, synth):
+    _, arr, _ = _chain(orc, vsl, synth)
+    out = ctx.global_ba_relative_pose_covariance(arr, CHAIN_PAIRS)
+    assert out[5] == 1
+    with pytest.raises(vsl.VslError):
+        ctx.global_ba_relative_pose_covariance(R.arrays(vsl, B.open_chain(synth, fixed=())), CHAIN_PAIRS)
+    a, b = arr.copy(), arr.copy()
+    sa = ctx.bundle_adjust(a, max_iters=4)
+    fresh = vsl.Context(0)
+    try:
+        sb = fresh.bundle_adjust(b, max_iters=4)
+    finally:
+        fresh.close()
+    assert sa.iterations == sb.iterations and sa.final_cost == sb.final_cost
+    assert np.array_equal(a.poses, b.poses) and np.array_equal(a.points, b.points)
+
+
+# -------------------------------------------------------------------------------------- 6. producer meets consumer
+def test_the_pose_graph_accepts_what_the_bundle_adjustment_produces(ctx, orc, vsl, synth):
+    d, arr, rr = _chain(orc, vsl, synth)
+    left = np.arange(0, 60, 2)                               # node i = left camera 2 i; node 0 (camera 0) is fixed
+    edges = [(i, j) for i in range(30) for j in range(i + 1, min(i + 4, 30))] + [(1, 29)]
+    cam_pairs = [(int(left[i]), int(left[j])) for i, j in edges]
+    joint, meas, cov, info, ns, storage = ctx.global_ba_relative_pose_covariance(arr, cam_pairs)
+    assert storage == 1 and ns == 0 and np.isfinite(info).all()
+    g = pg.Graph(arr.poses[left], arr.cam_fixed[left], [e[0] for e in edges], [e[1] for e in edges], meas)
+    assert g.node_fixed[0] == 1 and g.node_fixed.sum() == 1
+    before = g.poses.copy()
+    s = ctx.pose_graph_optimize(g, edge_info=info)           # VSL_ERR_INVALID would raise: every Omega is accepted
+    move = float(np.abs(g.poses - before).max())
+    print("weighted pose graph on its own measurements: initial cost %.3g, poses moved by %.3g" % (s.initial_cost, move))
+    assert s.initial_cost < 1e-20 and move <= 1e-12
+    g.poses[:] = before
+    # the chi-square gate: candidates whose measurement is the returned one plus a known offset
+    cands = [edges.index((3, 4)), edges.index((10, 13)), edges.index((1, 29)), edges.index((0, 2))]
+    rng = np.random.default_rng(8)
+    off = 1e-3 * rng.normal(size=(len(cands), 6))
+    ca, cb = [edges[k][0] for k in cands], [edges[k][1] for k in cands]
+    resid, rcov, chi2, _ = ctx.pgo_edge_consistency(g, ca, cb, meas[cands] + off, cov[cands], edge_info=info)
+    for q, k in enumerate(cands):
+        # r = log(T_a^-1 T_b) - (meas + d) = -d: pins the residual's sign, the tangent order and which node is a
+        assert np.abs(resid[q] + off[q]).max() <= pg.GPU_TOL * np.abs(meas[k]).max() + 2.0 ** -52 * np.abs(meas[k] + off[q]).max()
+        A = pg._ld(rcov[q]) + pg._ld(cov[k])
+        want = jr.chi2_ld(pg._ld(-off[q]), A)
+        bound = 64 * float(np.linalg.cond(np.asarray(A, np.float64))) * (2.0 ** -52 + np.abs(resid[q] + off[q]).max() / np.abs(off[q]).max())
+        rel = abs(chi2[q] - want) / want
+        print("candidate %s: chi2 %.6g, d^T (Sigma_r,pgo + cov)^-1 d %.6g, rel %.3g (bound %.3g)" % (edges[k], chi2[q], want, rel, bound))
+        assert rel <= bound

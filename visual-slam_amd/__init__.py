@@ -652,6 +652,34 @@ class Context:
                                                  cl.ctypes.data_as(f64p), C.byref(nd), C.byref(storage)))
         return cp, cl, nd.value, storage.value
 
+    def _ba_relpose(self, symbol, with_storage, arr, pairs, use_huber, huber):
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        n = len(a)
+        joint, meas, cov, info = np.zeros((n, 12, 12)), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6))
+        ns, storage = C.c_int(0), C.c_int(-1)
+        tail = (C.byref(storage),) if with_storage else ()
+        self._ck(getattr(self.L, symbol)(self.h, C.byref(st), C.byref(o), a.ctypes.data_as(i32p), b.ctypes.data_as(i32p), n,
+                                         joint.ctypes.data_as(f64p), meas.ctypes.data_as(f64p), cov.ctypes.data_as(f64p),
+                                         info.ctypes.data_as(f64p), C.byref(ns), *tail))
+        return (joint, meas, cov, info, ns.value) + ((storage.value,) if with_storage else ())
+
+    def ba_relative_pose_covariance(self, arr, pairs, use_huber=True, huber=1.0):
+        """Covariance and information of the relative poses of camera pairs under the bundle adjustment's posterior at
+        arr's poses / points (vsl_ba_relative_pose_covariance, the dense route; nothing is optimised).  pairs: [n, 2]
+        camera ids (a, b); one of the two may be fixed.  Returns (joint [n, 12, 12], meas [n, 6] = log(T_a^-1 T_b),
+        cov [n, 6, 6] of the pose-graph residual, info [n, 6, 6] = cov^-1 (NaN where singular), n_singular): meas and
+        info are edge_meas and edge_info of a pose graph, cov is meas_cov of pgo_edge_consistency."""
+        return self._ba_relpose("vsl_ba_relative_pose_covariance", False, arr, pairs, use_huber, huber)
+
+    def global_ba_relative_pose_covariance(self, arr, pairs, use_huber=True, huber=1.0):
+        """ba_relative_pose_covariance for the map of a global bundle adjustment
+        (vsl_global_ba_relative_pose_covariance).  Returns (joint, meas, cov, info, n_singular, storage) with storage =
+        0 dense (the bits of ba_relative_pose_covariance) / 1 linear band."""
+        return self._ba_relpose("vsl_global_ba_relative_pose_covariance", True, arr, pairs, use_huber, huber)
+
     def ba_residuals_jacobians(self, arr):
         st = self._ba_struct(arr)
         n = len(arr.obs_cam)

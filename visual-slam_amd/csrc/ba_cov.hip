@@ -52,6 +52,7 @@
 #include "dev_arena.h"
 #include "ba_host_plan.h"
 #include "ba_cov_plan.h"
+#include "ba_pair_plan.h"
 #include "ba_device.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // ba_large.h: only bl_eval and bl_wave_sum are used here, not its kernels
@@ -103,6 +104,38 @@ __global__ void cov_band_pose_kernel(int nQ, const int* __restrict__ q_free, con
   const int q = t / 36, a = (t % 36) / 6, b = t % 6;
   const int i = 6 * q_free[q] + max(a, b), j = 6 * q_free[q] + min(a, b);
   out[t] = Z[(size_t)i * (ld + 1) + ld - (i - j)];
+}
+
+// Joint blocks of camera pairs (vsl_ba_relative_pose_covariance): one thread per entry of a 12 x 12 block, the entry rule
+// of pgo.hip's pgo_joint_blocks_kernel on S^-1.  Diagonal blocks: the rule of the pose kernels of the same route, bit for
+// bit (band: entry (max, min) of Z as cov_band_pose_kernel; dense: the two mirror entries of the camera's own columns
+// averaged as ba_cov_pose_kernel).  Cross block, entry (row r of camera x, column c of camera y): with columns for both
+// cameras the average of X_y[6 x + r][c] and X_x[6 y + c][r]; with columns for one of them that single entry; with none
+// entry (max, min) of Z.  Every rule gives (x, r; y, c) and (y, c; x, r) the same number: the block is symmetric and a
+// swapped pair is the swapped, transposed block.  A fixed camera (f < 0): exactly 0.0.  Z: the storage base.
+__global__ void ba_pair_blocks_kernel(int n, int n_pairs, const PgcPairDev* __restrict__ pairs, int band, const double* __restrict__ Z,
+                                      int ld, const double* __restrict__ X, const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 144 * n_pairs || !*ok) return;
+  const PgcPairDev p = pairs[t / 144];
+  const int I = (t % 144) / 12, J = t % 12;
+  const int fx = I < 6 ? p.fa : p.fb, fy = J < 6 ? p.fa : p.fb;
+  const int cx = I < 6 ? p.ca : p.cb, cy = J < 6 ? p.ca : p.cb;
+  const int r = I % 6, c = J % 6;
+  double v = 0.0;
+  if (fx >= 0 && fy >= 0) {
+    const int i = 6 * fx + r, j = 6 * fy + c;
+    const bool cols = !(band && fx == fy) && (cx >= 0 || cy >= 0);
+    if (!cols)
+      v = Z[(size_t)max(i, j) * (ld + 1) + ld - (max(i, j) - min(i, j))];
+    else if (cx >= 0 && cy >= 0)
+      v = 0.5 * (X[cov_x_at(n, i, cy + c)] + X[cov_x_at(n, j, cx + r)]);
+    else if (cy >= 0)
+      v = X[cov_x_at(n, i, cy + c)];
+    else
+      v = X[cov_x_at(n, j, cx + r)];
+  }
+  out[t] = v;
 }
 
 // L L^T X = E for the COV_COLS unit columns col_unk[COV_COLS * blockIdx.x ..] (-1: an empty column) of this workgroup,
@@ -710,6 +743,169 @@ int cov_call(CovCall& c, const vsl_ba_options* opt, double* cov_pose, double* co
   return VSL_OK;
 }
 
+// ------------------------------------------------------------------ relative-pose covariances of camera pairs
+// vsl_ba_relative_pose_covariance / vsl_global_ba_relative_pose_covariance: the chains of the file header up to the
+// factor (dense) or the band of S^-1 (band), then
+//   dense  ba_cov_solve_kernel for the six unit columns of every distinct queried free camera
+//   band   cov_band_solve_kernel for the PGC_SOLVE pairs (the camera with the larger band position), fed by the inverted
+//          diagonal blocks the selected inversion left in its scratch
+//   ba_pair_blocks_kernel   the 12 x 12 joint blocks
+//   ba_relpose_kernel       (pgo.hip, the functor's own device code) meas, cov = J Sigma J^T, info = cov^-1
+// all on the context's stream inside one arena loan, one synchronisation at the end.
+struct RelCall {
+  vsl_ctx* ctx;
+  const char* name;
+  const vsl_ba_problem* prob;
+  const int32_t *a, *b;
+  int n_pairs;
+  bool global;
+  bool band = false;
+  BaPairPlan P;
+};
+
+// BaCaller::plan_extra of vsl_global_ba_relative_pose_covariance: hp.cam_free is the numbering of S (the band order on
+// the band route, ascending camera id on the dense one)
+int rel_plan_extra(void* self, const BaHostPlan& hp, size_t* extra_bytes) {
+  RelCall& c = *static_cast<RelCall*>(self);
+  c.band = hp.layout.banded;
+  c.P = bpp_plan(hp.cam_free, hp.nfree, c.band, hp.layout.bw, c.ctx->ba_cov_no_band_read, c.a, c.b, c.n_pairs);
+  *extra_bytes = c.P.total;
+  return VSL_OK;
+}
+
+int rel_run(RelCall& c, const vsl_ba_options* opt, BaState& st, std::vector<char>& host_in, std::vector<char>& host_out) {
+  vsl_ctx* ctx = c.ctx;
+  BaCaller caller{c.global ? BaUse::GLOBAL_COVARIANCE : BaUse::COVARIANCE};
+  if (c.global) {
+    caller.plan_extra = rel_plan_extra;
+    caller.plan_extra_self = &c;
+  } else {
+    caller.extra_bytes = c.P.total;
+  }
+  int rc;
+  if ((rc = ba_setup(ctx, c.prob, opt, st, caller))) return rc;
+  const BaPairPlan& P = c.P;
+  const PgcPlan& G = P.G;
+  const int n = G.n, np = c.n_pairs;
+  if (st.D.nfree != G.nf || st.banded != c.band || (c.band && st.bw != G.bw))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "%s: the set-up and the plan disagree", c.name);
+  char* dev = st.extra;
+  host_in.assign(P.in_bytes, 0);
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes) memcpy(host_in.data() + off, src, bytes);
+  };
+  const int one = 1;
+  put(P.off_ok, &one, sizeof(int));
+  put(P.off_pairs, G.pairs.data(), sizeof(PgcPairDev) * G.pairs.size());
+  put(P.off_col_unk, G.col_unk.data(), sizeof(int) * G.col_unk.size());
+  put(P.off_row_lo, G.row_lo.data(), sizeof(int) * G.row_lo.size());
+  VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), P.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  int* ok = (int*)(dev + P.off_ok);
+  const PgcPairDev* pairs = (const PgcPairDev*)(dev + P.off_pairs);
+  const int* col_unk = (const int*)(dev + P.off_col_unk);
+  double* X = (double*)(dev + P.off_X);
+  double* Sdiag = (double*)(dev + P.off_Sdiag);
+  double* Zs = (double*)(dev + P.off_Z);
+  double* joint = (double*)(dev + P.out_off + P.off_joint);
+  // S as vsl_ba_linearize forms it, in the layout of the set-up
+  if ((rc = ba_linearize(ctx, st, st.sb, false))) return rc;
+  if ((rc = ba_columns(ctx, st, st.sb))) return rc;
+  if ((rc = ba_schur(ctx, st, st.sb, false, 1.0, 0, st.D.L, false, false))) return rc;
+  {
+    VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+    hipLaunchKernelGGL(ba_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.S, c.band ? st.ldS : 0, Sdiag);
+    VSL_CHECK_LAUNCH(ctx);
+    if (c.band) {
+      if ((rc = vsl_chol_selinv_band_dev(ctx, st.S_eff(), Zs + st.ldS, n, st.ldS, st.bw, ok))) return rc;
+      if ((rc = vsl_cov_band_pivot_dev(ctx, n, st.S, st.ldS, Sdiag, ok))) return rc;
+      if ((rc = vsl_cov_band_unit_columns_dev(ctx, n, st.S, st.ldS, st.bw, vsl_chol_selinv_linv_dev(ctx, n, st.bw), col_unk,
+                                              (const int*)(dev + P.off_row_lo), G.nblk, X, ok)))
+        return rc;
+    } else {
+      double* Linv = (double*)(dev + P.off_Linv);
+      if ((rc = vsl_chol_factor_dev(ctx, st.S, n, ok, Linv))) return rc;
+      if ((rc = vsl_cov_unit_columns_dev(ctx, n, st.S, Linv, Sdiag, col_unk, G.nblk, X, ok))) return rc;
+    }
+    hipLaunchKernelGGL(ba_pair_blocks_kernel, dim3((144 * np + 255) / 256), dim3(256), 0, ctx->stream, n, np, pairs, c.band ? 1 : 0, Zs,
+                       st.ldS, X, ok, joint);
+    VSL_CHECK_LAUNCH(ctx);
+    if ((rc = vsl_pgo_relpose_dev(ctx, np, st.poses, pairs, joint, ok, (double*)(dev + P.out_off + P.off_meas),
+                                  (double*)(dev + P.out_off + P.off_cov), (double*)(dev + P.out_off + P.off_info),
+                                  (int*)(dev + P.out_off + P.off_sing))))
+      return rc;
+  }
+  host_out.assign(P.out_bytes + sizeof(int), 0);
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data() + P.out_bytes, ok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int ok_host;
+  memcpy(&ok_host, host_out.data() + P.out_bytes, sizeof(int));
+  if (!ok_host) return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: the reduced camera system is not positive definite", c.name);
+  return VSL_OK;
+}
+
+// both entry points.  storage: null for vsl_ba_relative_pose_covariance
+int rel_call(RelCall& c, const vsl_ba_options* opt, double* joint, double* meas, double* cov, double* info, int* n_singular,
+             int* storage) {
+  vsl_ctx* ctx = c.ctx;
+  const vsl_ba_problem* prob = c.prob;
+  int rc = ba_validate(ctx, prob);  // an empty problem (n_lms = 0, n_obs = 0) ends here
+  if (rc) return rc;
+  if (!opt || c.n_pairs < 0 || (c.n_pairs > 0 && (!c.a || !c.b)))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null argument or negative count", c.name);
+  int bad = 0;
+  switch (bpp_check_pairs(prob->n_cams, prob->cam_fixed, c.a, c.b, c.n_pairs, &bad)) {
+    case PGC_PAIR_RANGE: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d (%d, %d): camera out of range", c.name, bad, c.a[bad], c.b[bad]);
+    case PGC_PAIR_SAME: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d names camera %d twice", c.name, bad, c.a[bad]);
+    case PGC_PAIR_BOTH_FIXED: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d (%d, %d): both cameras are fixed", c.name, bad, c.a[bad], c.b[bad]);
+    default: break;
+  }
+  if (n_singular) *n_singular = 0;
+  if (c.n_pairs == 0 || (!joint && !meas && !cov && !info)) {
+    // nothing is launched; the route is still the problem's own (decided on the host)
+    if (storage) {
+      bool banded = false;
+      if ((rc = ba_layout_of(ctx, prob, BaCaller{BaUse::GLOBAL_COVARIANCE}, &banded))) return rc;
+      *storage = banded ? 1 : 0;
+    }
+    return VSL_OK;
+  }
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<char> host_in, host_out;  // read / written by copies on the stream: they outlive the synchronisation below
+  {
+    BaState st;  // holds the loan of the context's arena
+    try {
+      if (!c.global) {
+        // dense S, free cameras numbered by ascending camera id (vsl_ba_linearize's numbering)
+        std::vector<int> cam_free(prob->n_cams, -1);
+        int nfree = 0;
+        for (int i = 0; i < prob->n_cams; i++)
+          if (!prob->cam_fixed[i]) cam_free[i] = nfree++;
+        c.P = bpp_plan(cam_free, nfree, false, 0, false, c.a, c.b, c.n_pairs);
+      }
+      rc = rel_run(c, opt, st, host_in, host_out);
+    } catch (const std::bad_alloc&) {
+      rc = vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    // an error return may leave kernels and copies queued that use the arena and the host buffers: drain the stream
+    // before the loan ends (a later solve on this context gets the same block)
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+  }
+  if (rc) return rc;
+  const BaPairPlan& P = c.P;
+  const size_t np = (size_t)c.n_pairs;
+  if (joint) memcpy(joint, host_out.data() + P.off_joint, sizeof(double) * 144 * np);
+  if (meas) memcpy(meas, host_out.data() + P.off_meas, sizeof(double) * 6 * np);
+  if (cov) memcpy(cov, host_out.data() + P.off_cov, sizeof(double) * 36 * np);
+  if (info) memcpy(info, host_out.data() + P.off_info, sizeof(double) * 36 * np);
+  const int* sing = (const int*)(host_out.data() + P.off_sing);
+  int ns = 0;
+  for (size_t q = 0; q < np; q++) ns += sing[q] ? 1 : 0;
+  if (n_singular) *n_singular = ns;
+  if (storage) *storage = c.band ? 1 : 0;
+  return VSL_OK;
+}
+
 }  // namespace
 
 int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double* Linv, const double* Sdiag, const int* col_unk,
@@ -759,4 +955,20 @@ extern "C" int vsl_global_ba_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob
   if (!ctx) return VSL_ERR_INVALID;
   CovCall c{ctx, "vsl_global_ba_covariance", prob, cams, n_cam_q, lms, n_lm_q, true};
   return cov_call(c, opt, cov_pose, cov_point, n_degenerate, storage);
+}
+
+extern "C" int vsl_ba_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
+                                               const int32_t* pair_a, const int32_t* pair_b, int n_pairs, double* joint, double* meas,
+                                               double* cov, double* info, int* n_singular) {
+  if (!ctx) return VSL_ERR_INVALID;
+  RelCall c{ctx, "vsl_ba_relative_pose_covariance", prob, pair_a, pair_b, n_pairs, false};
+  return rel_call(c, opt, joint, meas, cov, info, n_singular, nullptr);
+}
+
+extern "C" int vsl_global_ba_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
+                                                      const int32_t* pair_a, const int32_t* pair_b, int n_pairs, double* joint,
+                                                      double* meas, double* cov, double* info, int* n_singular, int* storage) {
+  if (!ctx) return VSL_ERR_INVALID;
+  RelCall c{ctx, "vsl_global_ba_relative_pose_covariance", prob, pair_a, pair_b, n_pairs, true};
+  return rel_call(c, opt, joint, meas, cov, info, n_singular, storage);
 }

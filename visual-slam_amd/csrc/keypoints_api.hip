@@ -35,6 +35,7 @@ extern "C" int vsl_ctx_set_diagnostic(vsl_ctx* ctx, const char* name, int value)
   else if (k == "ba_pcg_tol_exp") ctx->ba_pcg_tol_exp = value < 0 ? 0 : value;
   else if (k == "ba_force_dense") ctx->ba_force_dense = value != 0;
   else if (k == "pgo_cov_no_band_read") ctx->pgo_cov_no_band_read = value != 0;
+  else if (k == "ba_cov_no_band_read") ctx->ba_cov_no_band_read = value != 0;
   else if (k == "chol_no_fused")ctx->chol_no_fused = value != 0;
   else if (k == "chol_no_bcr") ctx->chol_no_bcr = value != 0;
   else if (k == "chol_one_ended") ctx->chol_one_ended = value != 0;

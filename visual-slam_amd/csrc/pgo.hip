@@ -18,6 +18,7 @@
 #include "lm_policy.h"
 #include "dev_arena.h"
 #include "pgo_cov_plan.h"
+#include "relpose_math.h"
 
 namespace {
 
@@ -1249,6 +1250,74 @@ __global__ __launch_bounds__(64) void pgo_edge_consistency_kernel(int n_cand, co
   }
 }
 
+// The producer side of the _w entry points (vsl_ba_relative_pose_covariance, ba_cov.hip): one wavefront per pair
+// (a, b) of a bundle-adjustment problem, whose 12 x 12 joint block of S^-1 is in `joint`.  Lane 0 evaluates the
+// functor at a zero measurement with the dual numbers above -- meas = log(T_a^-1 T_b), and the Jacobians of the
+// residual, which do not depend on the measurement; a fixed camera's half of J is zero.  The lanes share T = Sigma J^T
+// and M = J T as in pgo_edge_consistency_kernel (every sum in ascending index order), cov = (M + M^T) / 2.  Lane 0
+// factors cov = L L^T (a pivot L_ii^2 <= 2^-36 cov_ii, or one that is not finite, fails) and inverts L by forward
+// substitution; info_ij = sum_{k >= max(i, j)} Linv_ki Linv_kj, k ascending, one lane per entry: (i, j) and (j, i) sum
+// the same products in the same order.  The result is then put through the pivot test of pgo_edge_whiten_kernel, so a
+// finite info is one that the _w calls accept.  A failing pair gets 36 NaN and singular[q] = 1.  No atomics.
+__global__ __launch_bounds__(64) void ba_relpose_kernel(int n_pairs, const double* __restrict__ poses,
+                                                        const PgcPairDev* __restrict__ pairs, const double* __restrict__ joint,
+                                                        const int* __restrict__ ok, double* __restrict__ meas,
+                                                        double* __restrict__ cov, double* __restrict__ info,
+                                                        int* __restrict__ singular) {
+  __shared__ double Jm[6][12], Tm[12][6], Mm[6][6], Am[6][6], Li[6][6];
+  __shared__ int bad;
+  const int q = blockIdx.x, lane = threadIdx.x;
+  if (q >= n_pairs || !*ok) return;
+  const PgcPairDev p = pairs[q];
+  if (lane == 0) {
+    D12 qc[4], tc[3], qn[4], tn[3], rd[6];
+    const double zero[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    seed_pose(poses + 7 * (size_t)p.na, 0, qc, tc);
+    seed_pose(poses + 7 * (size_t)p.nb, 6, qn, tn);
+    edge_residual(qc, tc, qn, tn, zero, rd);
+    for (int i = 0; i < 6; i++) {
+      meas[6 * (size_t)q + i] = rd[i].v;
+      for (int c = 0; c < 6; c++) {
+        Jm[i][c] = p.fa >= 0 ? rd[i].d[c] : 0.0;
+        Jm[i][6 + c] = p.fb >= 0 ? rd[i].d[6 + c] : 0.0;
+      }
+    }
+    bad = 0;
+  }
+  __syncthreads();
+  const double* S = joint + 144 * (size_t)q;
+  for (int t = lane; t < 72; t += 64) {
+    const int a = t / 6, i = t % 6;
+    double s = 0.0;
+    for (int b = 0; b < 12; b++) s += S[12 * a + b] * Jm[i][b];
+    Tm[a][i] = s;
+  }
+  __syncthreads();
+  if (lane < 36) {
+    const int i = lane / 6, j = lane % 6;
+    double s = 0.0;
+    for (int a = 0; a < 12; a++) s += Jm[i][a] * Tm[a][j];
+    Mm[i][j] = s;
+  }
+  __syncthreads();
+  if (lane < 36) {
+    const int i = lane / 6, j = lane % 6;
+    const double s = 0.5 * (Mm[i][j] + Mm[j][i]);
+    cov[36 * (size_t)q + lane] = s;
+    Am[i][j] = s;
+  }
+  __syncthreads();
+  // the 6 x 6 steps are relpose_math.h's (tests/cpp/relpose_math_test.cpp drives their failure branches on the host)
+  if (lane == 0 && !rpm_factor_invert(Am, Li)) bad = 1;  // Am <- L, Li <- L^-1
+  __syncthreads();
+  if (!bad && lane < 36) Mm[lane / 6][lane % 6] = rpm_info_entry(Li, lane / 6, lane % 6);  // Omega
+  __syncthreads();
+  if (!bad && lane == 0 && !rpm_accepts(Mm, Am)) bad = 1;
+  __syncthreads();
+  if (lane < 36) info[36 * (size_t)q + lane] = bad ? __builtin_nan("") : Mm[lane / 6][lane % 6];
+  if (lane == 0) singular[q] = bad;
+}
+
 struct PgoJointCall {
   const char* name;
   const int32_t *a, *b;
@@ -1386,6 +1455,15 @@ int pgo_joint_call(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_optio
   return VSL_OK;
 }
 }  // namespace
+
+int vsl_pgo_relpose_dev(vsl_ctx* ctx, int n_pairs, const double* poses, const PgcPairDev* pairs, const double* joint,
+                        const int* ok_dev, double* meas, double* cov, double* info, int* singular) {
+  if (n_pairs <= 0) return VSL_OK;
+  hipLaunchKernelGGL(ba_relpose_kernel, dim3(n_pairs), dim3(64), 0, ctx->stream, n_pairs, poses, pairs, joint, ok_dev, meas, cov,
+                     info, singular);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
 
 extern "C" int vsl_pgo_joint_covariance(vsl_ctx* ctx, const vsl_pgo_problem* prob, const vsl_ba_options* opt, const int32_t* pair_a,
                                         const int32_t* pair_b, int n_pairs, double* cov, int* storage) {

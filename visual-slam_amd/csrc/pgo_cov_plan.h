@@ -2,6 +2,7 @@
 // from the graph and the queried pairs before the first byte goes to the device.  Plain C++, no HIP, no vsl_ctx:
 // tests/cpp/pgo_cov_plan_test.cpp drives it under g++.
 //   pgc_check_pairs   the argument rules of a pair list
+//   pgc_classify      from a device numbering: the class of every pair, the unique column nodes, the unit-column blocks
 //   pgc_plan          device numbering (the fold on the ring route), the class of every pair, the unique column nodes
 //                     and each pair's columns among them, the unit-column blocks, the share of the arena
 // THE ORDER THE DEVICE SEES.  Routes 0 and 1 keep the nodes' own order: device free index = free index.  Route 2
@@ -74,29 +75,14 @@ struct PgcPlan {
   size_t out_off = 0, off_cov = 0, off_resid = 0, off_resid_cov = 0, off_chi2 = 0, out_bytes = 0, total = 0;  // outputs relative to out_off
 };
 
-// node_fixed: [n_nodes]; folded: the ring route; dense / bw: the storage decision for the problem the device builds
-// (pgo_storage); no_band_read: the diagnostic that sends in-band pairs through the solve.  The pairs have passed
-// pgc_check_pairs.
-inline PgcPlan pgc_plan(int n_nodes, const uint8_t* node_fixed, bool folded, bool dense, int bw, bool no_band_read,
-                        const int32_t* a, const int32_t* b, int n_pairs, bool with_cand) {
-  PgcPlan P;
+// The part of the plan that follows from a device numbering: P.nf, P.n, P.dev_free, P.dev_node are set by the caller
+// (pgc_plan below for the pose graph; ba_pair_plan.h for the reduced camera system of a bundle adjustment, whose band
+// order is the reverse Cuthill-McKee order of its host plan).  Fills the pairs, their classes, the unique column nodes,
+// the unit-column blocks and row_lo.
+inline void pgc_classify(PgcPlan& P, bool dense, int bw, bool no_band_read, const int32_t* a, const int32_t* b, int n_pairs) {
   P.dense = dense;
-  P.folded = folded;
   P.bw = dense ? 0 : bw;
   P.n_pairs = n_pairs;
-  for (int i = 0; i < n_nodes; i++) P.nf += node_fixed[i] ? 0 : 1;
-  P.n = 6 * P.nf;
-  P.dev_free.assign(n_nodes, -1);
-  P.dev_node.resize(n_nodes);
-  for (int i = 0, f = 0, next_fixed = P.nf; i < n_nodes; i++) {
-    if (node_fixed[i]) {
-      P.dev_node[i] = folded ? next_fixed++ : i;
-    } else {
-      P.dev_free[i] = folded ? chol_fold_pos(P.nf, f) : f;
-      P.dev_node[i] = folded ? P.dev_free[i] : i;
-      f++;
-    }
-  }
   P.pairs.resize(n_pairs);
   for (int q = 0; q < n_pairs; q++) {
     PgcPairDev& d = P.pairs[q];
@@ -141,6 +127,29 @@ inline PgcPlan pgc_plan(int n_nodes, const uint8_t* node_fixed, bool folded, boo
       for (int blk = c / PGC_COLS; blk <= (c + 5) / PGC_COLS; blk++) P.row_lo[blk] = std::min(P.row_lo[blk], lo);
     }
   }
+}
+
+// node_fixed: [n_nodes]; folded: the ring route; dense / bw: the storage decision for the problem the device builds
+// (pgo_storage); no_band_read: the diagnostic that sends in-band pairs through the solve.  The pairs have passed
+// pgc_check_pairs.
+inline PgcPlan pgc_plan(int n_nodes, const uint8_t* node_fixed, bool folded, bool dense, int bw, bool no_band_read,
+                        const int32_t* a, const int32_t* b, int n_pairs, bool with_cand) {
+  PgcPlan P;
+  P.folded = folded;
+  for (int i = 0; i < n_nodes; i++) P.nf += node_fixed[i] ? 0 : 1;
+  P.n = 6 * P.nf;
+  P.dev_free.assign(n_nodes, -1);
+  P.dev_node.resize(n_nodes);
+  for (int i = 0, f = 0, next_fixed = P.nf; i < n_nodes; i++) {
+    if (node_fixed[i]) {
+      P.dev_node[i] = folded ? next_fixed++ : i;
+    } else {
+      P.dev_free[i] = folded ? chol_fold_pos(P.nf, f) : f;
+      P.dev_node[i] = folded ? P.dev_free[i] : i;
+      f++;
+    }
+  }
+  pgc_classify(P, dense, bw, no_band_read, a, b, n_pairs);
   size_t at = 0;
   auto take = [&](size_t bytes) {
     const size_t o = at;

@@ -95,6 +95,7 @@ struct vsl_ctx {
   bool chol_no_fused = false;           // diagnostic: band Cholesky as one launch per panel step instead of the fused single-launch kernel
   bool ba_force_dense = false;          // diagnostic: dense reduced camera system even where the band form applies
   bool pgo_cov_no_band_read = false;    // diagnostic: vsl_pgo_joint_covariance / vsl_pgo_edge_consistency solve unit columns for in-band pairs too instead of reading the band of the inverse
+  bool ba_cov_no_band_read = false;     // diagnostic: the same for vsl_global_ba_relative_pose_covariance on its band route
   bool ba_schur_atomics = false;       // diagnostic: large-system Schur complement by fp64 atomics (one wavefront per landmark) instead of the per-block gather
   bool ba_no_fused = false;             // diagnostic: local windows by the operator-by-operator kernels of ba.hip instead of the fused iteration (ba_fused.hip)
   bool ba_schur_entries = false;        // diagnostic: single-entry ownership in the small-system Schur kernel instead of 3 x 3 sub-blocks
@@ -250,6 +251,13 @@ int vsl_cov_band_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, int ld, 
                                   const int* row_lo, int nblk, double* X, const int* ok_dev);
 int vsl_cov_band_pivot_dev(vsl_ctx* ctx, int n, const double* L, int ld, const double* Sdiag, int* ok_dev);
 int vsl_cov_band_blocks_dev(vsl_ctx* ctx, int nQ, const int* q_free, const double* Z, int ld, const int* ok_dev, double* out);
+// pgo.hip, for vsl_ba_relative_pose_covariance (ba_cov.hip): per pair q of pairs (device; na / nb = row of poses, fa / fb
+// < 0 = fixed) and its 12 x 12 joint covariance joint[144 q ..], with the pose-graph functor's own device code:
+// meas[6 q ..] = log(T_a^-1 T_b), cov[36 q ..] = J Sigma J^T of the functor's residual, info[36 q ..] = its inverse (36
+// NaN and singular[q] = 1 where the 6 x 6 Cholesky fails the 2^-36 pivot rule).  Nothing is written when *ok_dev = 0.
+struct PgcPairDev;
+int vsl_pgo_relpose_dev(vsl_ctx* ctx, int n_pairs, const double* poses, const PgcPairDev* pairs, const double* joint,
+                        const int* ok_dev, double* meas, double* cov, double* info, int* singular);
 __host__ __device__ inline size_t vsl_cov_x_at(int n, int i, int col) {
   return (size_t)(col / 16) * n * 16 + (size_t)i * 16 + (col % 16);
 }
