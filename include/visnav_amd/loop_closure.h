@@ -34,6 +34,9 @@
 #pragma weak vsl_pgo_covariance_w
 #pragma weak vsl_pgo_joint_covariance_w
 #pragma weak vsl_pgo_edge_consistency_w
+// ... and so are the read-out and the parity hook of the far-edge route (pose_graph_optimization_far_edges below)
+#pragma weak vsl_ctx_last_pgo_far
+#pragma weak vsl_pgo_far_solve
 
 namespace visnav {
 
@@ -254,6 +257,38 @@ inline void pose_graph_optimization(const FrameCamId& cur_kf_fcid, Camera& cur_k
                                     const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
                                     const LoopClosureOptions& options) {
   pose_graph_optimization(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, EdgeInformation());
+}
+
+// pose_graph_optimization for graphs with MORE THAN ONE long edge (a second loop closure, a revisit, a second session):
+// the normal equations as a band factor of the near edges plus a low-rank update for the far ones instead of a dense
+// matrix (include/vslam_hip.h "FAR EDGES").  Sets the context's "pgo_far_edges" diagnostic for the
+// call and puts it back as it found it, also when the call throws.  A graph that takes the band or the ring today, or
+// has no admissible split, is solved exactly as by pose_graph_optimization.  report (nullable): what
+// vsl_ctx_last_pgo_far says after the solve (all zero on a library without it: the symbol is referenced weakly).
+struct PoseGraphFarEdges {
+  int taken = 0, far_edges = 0, half_bandwidth = 0, columns = 0;
+  int64_t solves = 0;
+};
+inline void pose_graph_optimization_far_edges(const FrameCamId& cur_kf_fcid, Camera& cur_kf, const FrameCamId& loop_candidate_fcid,
+                                              const Sophus::SE3d& sim3, Cameras& keyframes, int essential_threshold,
+                                              const LoopClosureOptions& options, const EdgeInformation& information = EdgeInformation(),
+                                              PoseGraphFarEdges* report = nullptr) {
+  struct Restore {
+    int was = 0;
+    Restore() {
+      amd::check(vsl_ctx_get_diagnostic(amd::ctx(), "pgo_far_edges", &was), "pose_graph_optimization_far_edges");
+      amd::check(vsl_ctx_set_diagnostic(amd::ctx(), "pgo_far_edges", 1), "pose_graph_optimization_far_edges");
+    }
+    ~Restore() { (void)vsl_ctx_set_diagnostic(amd::ctx(), "pgo_far_edges", was); }
+  } restore;
+  pose_graph_optimization(cur_kf_fcid, cur_kf, loop_candidate_fcid, sim3, keyframes, essential_threshold, options, information);
+  if (report) {
+    *report = PoseGraphFarEdges();
+    if (vsl_ctx_last_pgo_far)
+      amd::check(vsl_ctx_last_pgo_far(amd::ctx(), &report->taken, &report->far_edges, &report->half_bandwidth, &report->columns,
+                                      &report->solves),
+                 "pose_graph_optimization_far_edges");
+  }
 }
 
 // The EdgeInformation of that pose graph from the bundle-adjusted map: the edges amd::flatten_pose_graph creates for

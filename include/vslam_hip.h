@@ -242,6 +242,8 @@ int vsl_ctx_set_tie_eps(vsl_ctx* ctx, double eps);
  *                                   are solved for in-band pairs as well instead of reading the band of the inverse
  *                                   (agrees to the tolerance, not bit for bit)
  *   "ba_cov_no_band_read" (0/1)     the same for vsl_global_ba_relative_pose_covariance on its band route
+ *   "pgo_far_edges" (0/1)           vsl_pose_graph_optimize*: graphs stored densely because of a few long edges by a band
+ *                                   factor plus a low-rank update ("FAR EDGES" below); see vsl_ctx_last_pgo_far
  *   "ba_schur_atomics" (0/1)        large-system Schur complement by fp64 atomics instead of the per-block gather
  *   "ba_no_fused" (0/1)             local windows (<= 21 free cameras) by the operator-by-operator kernels instead of the
  *                                   fused four-launch iteration (ba_fused.hip)
@@ -260,7 +262,7 @@ int vsl_ctx_set_tie_eps(vsl_ctx* ctx, double eps);
  *   "frames_bow_chunk" (default 0)  images per pass of vsl_frames_bow_vectors; 0 = as many as its scratch budget holds */
 int vsl_ctx_set_diagnostic(vsl_ctx* ctx, const char* name, int value);
 /* Reads a diagnostic back, for callers that set one for the length of a call and restore it (the iterative-Schur knobs
- * "ba_iterative_schur", "ba_pcg_poll", "ba_pcg_tol_exp"; any other name: VSL_ERR_INVALID). */
+ * "ba_iterative_schur", "ba_pcg_poll", "ba_pcg_tol_exp", and "pgo_far_edges"; any other name: VSL_ERR_INVALID). */
 int vsl_ctx_get_diagnostic(vsl_ctx* ctx, const char* name, int* value);
 
 /* matchDescriptors for n_pairs (slot_a, slot_b) pairs; slot_pairs is a HOST
@@ -756,6 +758,38 @@ int vsl_pgo_joint_covariance_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const 
 int vsl_pgo_edge_consistency_w(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
                                const int32_t* cand_a, const int32_t* cand_b, const double* cand_meas, const double* meas_cov,
                                int n_cand, double* resid, double* resid_cov, double* chi2, int* storage);
+
+/* FAR EDGES: band factor plus low-rank update.  pgo_storage takes the largest free-index distance
+ * over all edges, so one more long edge -- a second loop closure, a figure-eight, a revisit, a second session -- sends
+ * the whole graph to dense storage.  The route writes the damped, scaled system the dense route would factorise as
+ *     A = M + W W^T,   M: the edges at most d* apart in free index (a linear band) + the LM diagonal,
+ *                      W: n x 6 k, six columns per FAR edge (the scaled rows of [Ja Jb] at its two endpoints)
+ * and solves  y = M^-1 b, Y = M^-1 W, C = I + W^T Y, C z = W^T y, x = y - Y z:  a direct solve, bit-reproducible,
+ * O(n bw^2 + n bw m + m^3) work and O(n (bw + m)) memory, m = 6 k.  d* is chosen on the host (pgo_far_plan.h): among the
+ * distinct edge distances with 1 <= k <= 128 far edges, (bw + 33) * 2 < n for bw = 6 d* + 5, and every component of the
+ * near graph tied to a fixed node, the one with the least operation count.
+ * SWITCH (opt-in; off: every path is unchanged, bit for bit): diagnostic "pgo_far_edges" = 1 or the environment variable
+ * VSL_PGO_FAR_EDGES.  It applies to vsl_pose_graph_optimize and vsl_pose_graph_optimize_w ONLY, and only to a graph that
+ * is stored DENSELY today with more than 128 unknowns and has an admissible split; a graph that takes the band or the
+ * ring keeps it, and without a split the call proceeds as without the switch (vsl_ctx_last_pgo_far says which).  The
+ * marginal-covariance calls (vsl_pgo_covariance*, vsl_pgo_joint_covariance*, vsl_pgo_edge_consistency*) and the hooks
+ * vsl_pgo_linearize*, vsl_pgo_linearize_stored* IGNORE the switch.
+ *
+ * vsl_pgo_far_solve -- the parity hook: H x = b for the H, g of vsl_pgo_linearize_w (Huber corrector, no scaling, no
+ * damping; edge_info NULL: identity weights; b NULL: b = g) through the route at EVERY size.
+ *   max_near_distance >= 0   forces d*: every edge between free nodes farther apart is far; no far edge at all is a plain
+ *                            band solve.  VSL_ERR_INVALID when the band 6 d* + 5 is not narrower than the matrix or more
+ *                            than 128 edges are far.
+ *   max_near_distance = -1   the plan's choice; VSL_ERR_INVALID when no candidate is admissible.
+ * x: n = 6 x free nodes doubles.  *far_edges, *half_bandwidth (nullable): k and 6 d* + 5.  A failed pivot of M (the
+ * factorisation's test, then L_ii^2 <= 2^-36 M_ii as in vsl_pgo_covariance) or of C: VSL_ERR_NUMERIC and x = 0; the
+ * context stays usable.  prob->poses is only read. */
+int vsl_pgo_far_solve(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt, const double* b,
+                      int max_near_distance, double* x, int* far_edges, int* half_bandwidth);
+/* The far-edge route in the last vsl_pose_graph_optimize* on this context: *taken = 1 / 0, the far edges k, the half
+ * bandwidth of the near band, the right-hand-side columns per solve (6 k + 1) and the solves (one per LM iteration).
+ * All zero when the route was not taken; every pointer may be NULL. */
+int vsl_ctx_last_pgo_far(vsl_ctx* ctx, int* taken, int* far_edges, int* half_bandwidth, int* columns, int64_t* solves);
 
 /* --------------------------------------------------------------- DBoW2 path */
 /*

@@ -562,6 +562,33 @@ class Context:
                        resid.ctypes.data_as(f64p), resid_cov.ctypes.data_as(f64p), chi2.ctypes.data_as(f64p), C.byref(storage))
         return resid, resid_cov, chi2, storage.value
 
+    def pgo_far_solve(self, arr, b=None, max_near_distance=-1, use_huber=True, huber=1.0, *, edge_info=None):
+        """Solves H x = b (b None: g) for the H, g of pgo_linearize by the band factor of the near edges plus the
+        low-rank update of the far ones (vsl_pgo_far_solve).  max_near_distance >= 0 forces d*, -1 takes the plan's
+        choice.  Returns (x, far_edges, half_bandwidth).  The switch of the solver itself is
+        set_diagnostic("pgo_far_edges", 1); last_pgo_far() tells whether a solve took the route."""
+        info = self._edge_info(arr, edge_info)
+        st = self._pgo_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * int((arr.node_fixed == 0).sum())
+        if b is not None:
+            b = np.ascontiguousarray(b, np.float64).reshape(-1)
+            if len(b) != n:
+                raise ValueError("b has %d entries, the problem %d unknowns" % (len(b), n))
+        x = np.zeros(max(n, 1))
+        k, bw = C.c_int(0), C.c_int(0)
+        self._ck(self.L.vsl_pgo_far_solve(self.h, C.byref(st), None if info is None else info.ctypes.data_as(f64p), C.byref(o),
+                                          None if b is None else b.ctypes.data_as(f64p), C.c_int(int(max_near_distance)),
+                                          x.ctypes.data_as(f64p), C.byref(k), C.byref(bw)))
+        return x[:n].copy(), k.value, bw.value
+
+    def last_pgo_far(self):
+        """dict(taken, far_edges, half_bandwidth, columns, solves) of the far-edge route in the last pose_graph_optimize
+        on this context; zeros when it did not take the route."""
+        t, k, bw, c, s = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        self._ck(self.L.vsl_ctx_last_pgo_far(self.h, C.byref(t), C.byref(k), C.byref(bw), C.byref(c), C.byref(s)))
+        return dict(taken=t.value, far_edges=k.value, half_bandwidth=bw.value, columns=c.value, solves=s.value)
+
     def bundle_adjust_intrinsics(self, arr, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
         """optimize_intrinsics = true: optimises arr.poses / arr.points / arr.intr in place."""
         st = self._ba_struct(arr)

@@ -281,6 +281,10 @@ __global__ __launch_bounds__(COV_THREADS) void ba_cov_solve_kernel(int n, const 
 // structure with the band's bounds.
 // As there: one lane per entry and step, panels in ascending (descending) order, no atomics -- a column has the same
 // bits whichever columns share its workgroup and wherever the forward pass starts (a zero row contributes +0.0).
+// UNIT = false (vsl_band_rhs_solve_dev: the pose graph's far-edge route, pgo.hip): GENERAL right-hand sides.  The caller
+// has filled X with B; col_unk is not read; row_lo[block] is the block's first non-zero row (n: the block is zero and
+// stays so), where the forward pass starts; the backward pass runs to row 0.  Everything else is the same code.
+template <bool UNIT>
 __global__ __launch_bounds__(COV_THREADS) void cov_band_solve_kernel(int n, const double* __restrict__ L, int ld, int bw,
                                                                      const double* __restrict__ Linv,
                                                                      const int* __restrict__ col_unk,
@@ -292,17 +296,23 @@ __global__ __launch_bounds__(COV_THREADS) void cov_band_solve_kernel(int n, cons
   if (!*ok) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
   int first = n;
-  for (int c = 0; c < COV_COLS; c++) {
-    const int u = col_unk[COV_COLS * blockIdx.x + c];
-    if (u >= 0 && u < first) first = u;
+  if (UNIT) {
+    for (int c = 0; c < COV_COLS; c++) {
+      const int u = col_unk[COV_COLS * blockIdx.x + c];
+      if (u >= 0 && u < first) first = u;
+    }
+  } else {
+    first = max(0, row_lo[blockIdx.x]);
   }
   if (first >= n) return;  // (uniform: a block without a column)
-  const int lo = row_lo ? max(0, min(row_lo[blockIdx.x], first)) : 0;
+  const int lo = (UNIT && row_lo) ? max(0, min(row_lo[blockIdx.x], first)) : 0;
   const int p_first = first / COV_NB, p_lo = lo / COV_NB, np = (n + COV_NB - 1) / COV_NB;
   double* __restrict__ Xw = X + (size_t)blockIdx.x * n * COV_COLS;
-  for (int t = tid + p_lo * COV_NB * COV_COLS; t < n * COV_COLS; t += COV_THREADS)
-    Xw[t] = col_unk[COV_COLS * blockIdx.x + (t % COV_COLS)] == t / COV_COLS ? 1.0 : 0.0;
-  __syncthreads();
+  if (UNIT) {
+    for (int t = tid + p_lo * COV_NB * COV_COLS; t < n * COV_COLS; t += COV_THREADS)
+      Xw[t] = col_unk[COV_COLS * blockIdx.x + (t % COV_COLS)] == t / COV_COLS ? 1.0 : 0.0;
+    __syncthreads();
+  }
   // ---- forward: L Y = E
   for (int p = p_first; p < np; p++) {
     const int k = p * COV_NB, nb = min(COV_NB, n - k), iend = min(n, k + COV_NB + bw);
@@ -921,8 +931,18 @@ int vsl_cov_band_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, int ld, 
                                   const int* row_lo, int nblk, double* X, const int* ok_dev) {
   if (nblk <= 0 || n <= 0) return VSL_OK;
   if (bw < 0 || ld != bw + COV_NB) return vsl_fail(ctx, VSL_ERR_INVALID, "band unit columns: half bandwidth %d, leading dimension %d", bw, ld);
-  hipLaunchKernelGGL(cov_band_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, L + ld, ld, bw, Linv, col_unk, row_lo,
+  hipLaunchKernelGGL(cov_band_solve_kernel<true>, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, L + ld, ld, bw, Linv, col_unk, row_lo,
                      X, ok_dev);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_band_rhs_solve_dev(vsl_ctx* ctx, int n, const double* L, int ld, int bw, const double* Linv, const int* row_first, int nblk,
+                           double* X, const int* ok_dev) {
+  if (nblk <= 0 || n <= 0) return VSL_OK;
+  if (bw < 0 || ld != bw + COV_NB || !row_first) return vsl_fail(ctx, VSL_ERR_INVALID, "band solve: half bandwidth %d, leading dimension %d", bw, ld);
+  hipLaunchKernelGGL(cov_band_solve_kernel<false>, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, L + ld, ld, bw, Linv,
+                     (const int*)nullptr, row_first, X, ok_dev);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }

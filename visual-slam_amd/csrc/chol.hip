@@ -705,6 +705,11 @@ static int chol_factor_panels(vsl_ctx* ctx, double* S, int n, int ld, int bw, in
 int vsl_chol_factor_dev(vsl_ctx* ctx, double* S, int n, int* ok_dev, double* Linv) {
   return chol_factor_panels(ctx, S, n, n, n, ok_dev, Linv);
 }
+// ... and of band storage (pgo.hip's far-edge route solves many right-hand sides against it)
+int vsl_chol_factor_band_dev(vsl_ctx* ctx, double* S, int n, int ld, int bw, int* ok_dev, double* Linv) {
+  if (n <= 0 || bw < 0 || ld != bw + CH_NB) return vsl_fail(ctx, VSL_ERR_INVALID, "band factor: %d unknowns, half bandwidth %d, leading dimension %d", n, bw, ld);
+  return chol_factor_panels(ctx, S, n, ld, bw, ok_dev, Linv);
+}
 
 // dense or band storage, one launch per panel step and direction
 static int chol_solve_panels(vsl_ctx* ctx, double* S, double* b, int n, int ld, int bw, int* ok_dev) {

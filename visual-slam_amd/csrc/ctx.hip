@@ -119,6 +119,16 @@ extern "C" int vsl_ctx_last_ba_layout(vsl_ctx* ctx, int64_t* s_elems, int* bande
   return VSL_OK;
 }
 
+extern "C" int vsl_ctx_last_pgo_far(vsl_ctx* ctx, int* taken, int* far_edges, int* half_bandwidth, int* columns, int64_t* solves) {
+  if (!ctx) return VSL_ERR_INVALID;
+  if (taken) *taken = ctx->last_pgo_far_taken;
+  if (far_edges) *far_edges = ctx->last_pgo_far_k;
+  if (half_bandwidth) *half_bandwidth = ctx->last_pgo_far_bw;
+  if (columns) *columns = ctx->last_pgo_far_cols;
+  if (solves) *solves = ctx->last_pgo_far_solves;
+  return VSL_OK;
+}
+
 extern "C" int vsl_ctx_last_ba_pcg(vsl_ctx* ctx, int64_t* solves, int64_t* iterations_total, int* iterations_last, double* rel_residual_last) {
   if (!ctx) return VSL_ERR_INVALID;
   if (solves) *solves = ctx->last_pcg_solves;

@@ -36,6 +36,7 @@ extern "C" int vsl_ctx_set_diagnostic(vsl_ctx* ctx, const char* name, int value)
   else if (k == "ba_force_dense") ctx->ba_force_dense = value != 0;
   else if (k == "pgo_cov_no_band_read") ctx->pgo_cov_no_band_read = value != 0;
   else if (k == "ba_cov_no_band_read") ctx->ba_cov_no_band_read = value != 0;
+  else if (k == "pgo_far_edges") ctx->pgo_far_edges = value != 0;
   else if (k == "chol_no_fused")ctx->chol_no_fused = value != 0;
   else if (k == "chol_no_bcr") ctx->chol_no_bcr = value != 0;
   else if (k == "chol_one_ended") ctx->chol_one_ended = value != 0;
@@ -51,6 +52,7 @@ extern "C" int vsl_ctx_get_diagnostic(vsl_ctx* ctx, const char* name, int* value
   if (k == "ba_iterative_schur") *value = ctx->ba_iterative_schur ? 1 : 0;
   else if (k == "ba_pcg_poll") *value = ctx->ba_pcg_poll;
   else if (k == "ba_pcg_tol_exp") *value = ctx->ba_pcg_tol_exp;
+  else if (k == "pgo_far_edges") *value = ctx->pgo_far_edges ? 1 : 0;
   else return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ctx_get_diagnostic: knob '%s' cannot be read back", name);
   return VSL_OK;
 }

@@ -6,9 +6,12 @@
 //
 // One thread per edge evaluates the residual and both 6x6 Jacobian blocks with forward-mode dual numbers
 // (12 partials: what ceres::AutoDiffCostFunction<., 6, 7, 7> followed by the SE3 plus-Jacobian computes), the
-// normal equations of the (at most a few thousand) keyframes are accumulated densely -- one thread owns one ROW of H and
-// walks the node's incident edges in edge order (lists built once per solve on the host): no atomics, results do not
-// depend on timing -- and solved by the blocked Cholesky of chol.hip.  This runs once per loop closure.
+// normal equations are accumulated by row owners -- one thread owns one ROW of H and walks the node's incident edges in
+// edge order (lists built once per solve on the host): no atomics, results do not depend on timing -- into the storage
+// pgo_storage picks for the graph: a linear or cyclic band when the graph is narrow in the keyframes' own order (chol.hip's
+// band and ring solvers), dense otherwise (the blocked Cholesky), and, opt-in, a band for the near edges plus a low-rank
+// update for a few far ones where one long edge would otherwise make the whole matrix dense ("FAR EDGES" below,
+// pgo_far_plan.h).  This runs once per loop closure.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -18,6 +21,7 @@
 #include "lm_policy.h"
 #include "dev_arena.h"
 #include "pgo_cov_plan.h"
+#include "pgo_far_plan.h"
 #include "relpose_math.h"
 
 namespace {
@@ -318,11 +322,14 @@ __global__ void pgo_scale_kernel(int n, const double* __restrict__ colsq, double
 // diagonal (the mirror entries belong to the other endpoint's thread), and in the CYCLIC form (`cyclic`) the entries of
 // the wrap-around corner (j - i >= n - bw: nodes that are neighbours around the loop) as (i, j - n) in the leading slots
 // of its row.  ld = 0: dense, every entry.
+// far (nullable; "FAR EDGES" below): an edge with far[e] set stays out of H -- g still sums it -- and its share of H_ii
+// goes to dfar[i] instead.
 __global__ void pgo_build_kernel(int n_nodes, int n, const int* __restrict__ inc_off, const int* __restrict__ inc,
                                  const int* __restrict__ edge_a, const int* __restrict__ edge_b,
                                  const int* __restrict__ free_idx, const double* __restrict__ r, const double* __restrict__ Ja,
                                  const double* __restrict__ Jb, const double* __restrict__ scale, double* __restrict__ H,
-                                 double* __restrict__ g, int ld, int bw, int cyclic) {
+                                 double* __restrict__ g, int ld, int bw, int cyclic, const uint8_t* __restrict__ far = nullptr,
+                                 double* __restrict__ dfar = nullptr) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_nodes * 6) return;
   const int node = t / 6, c = t - node * 6;
@@ -331,7 +338,7 @@ __global__ void pgo_build_kernel(int n_nodes, int n, const int* __restrict__ inc
   const double sx = scale[6 * nx + c];
   const int i = 6 * nx + c;
   double* __restrict__ Hrow = ld > 0 ? H + (size_t)i * (ld + 1) + (ld - i) : H + (size_t)i * n;  // Hrow[j] = entry (i, j)
-  double gacc = 0;
+  double gacc = 0, dacc = 0;  // dacc: the FAR edges' share of H_ii (far != null: they stay out of H, section "FAR EDGES")
   for (int k = inc_off[node]; k < inc_off[node + 1]; k++) {
     const int e = inc[k] >> 1, x = inc[k] & 1;
     const double* Jx = (x ? Jb : Ja) + 36 * (size_t)e;
@@ -342,6 +349,12 @@ __global__ void pgo_build_kernel(int n_nodes, int n, const int* __restrict__ inc
       gv += col[q] * re[q];
     }
     gacc += sx * gv;
+    if (far && far[e]) {
+      double q2 = 0;
+      for (int q = 0; q < 6; q++) q2 += col[q] * col[q];
+      dacc += sx * sx * q2;
+      continue;
+    }
     for (int y = 0; y < 2; y++) {
       const int ny = free_idx[y ? edge_b[e] : edge_a[e]];
       if (ny < 0) continue;
@@ -363,6 +376,7 @@ __global__ void pgo_build_kernel(int n_nodes, int n, const int* __restrict__ inc
     }
   }
   g[6 * nx + c] = gacc;
+  if (dfar) dfar[i] = dacc;
 }
 
 // band forms: A = H (all s_elems slots) with the LM damping on the diagonal, b = -g, gabs
@@ -379,6 +393,95 @@ __global__ void pgo_damp_band_kernel(int n, size_t elems, int ld, const double* 
     gabs[row] = fabs(g[row] / scale[row]);
   }
   A[t] = v;
+}
+
+// ---- FAR EDGES (the host plan is pgo_far_plan.h).  The damped, scaled system the dense route
+// would factorise is A = M + W W^T: M = the linear band of the NEAR edges plus the LM diagonal (pgo_build_kernel with the
+// far flags, then the kernel below), W (n x m, m = 6 k) six columns per far edge e, column r of its block = the scaled
+// row r of [Ja Jb] at the rows of its two endpoints.  With Y = M^-1 [b W] (band factor, vsl_band_rhs_solve_dev):
+//   C = I + W^T Y_W,  C z = W^T y,  x = y - Y_W z
+// Right-hand sides X: blocks of n x 16 (vsl_cov_x_at); column 0 is b, columns 1 + 6 e' .. 6 + 6 e' far edge e'.
+
+// the band route's damping with the diagonal of the FULL H: H_ii = M_ii + (W W^T)_ii, as the dense route sees it
+__global__ void pgo_damp_far_kernel(int n, size_t elems, int ld, const double* __restrict__ H, const double* __restrict__ dfar,
+                                    const double* __restrict__ g, const double* __restrict__ scale, double inv_radius,
+                                    double* __restrict__ A, double* __restrict__ b, double* __restrict__ gabs) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= elems) return;
+  double v = H[t];
+  const size_t row = t / (size_t)(ld + 1);
+  if (row < (size_t)n && t - row * (ld + 1) == (size_t)ld) {
+    v += fmin(fmax(v + dfar[row], 1e-6), 1e32) * inv_radius;
+    b[row] = -g[row];
+    gabs[row] = fabs(g[row] / scale[row]);
+  }
+  A[t] = v;
+}
+
+// X (cleared by the caller) <- [b | W]: one thread per entry of b, then one per non-zero entry of W (72 per far edge)
+__global__ void pgo_far_columns_kernel(int n, int k, const int* __restrict__ far_edges, const int* __restrict__ edge_a,
+                                       const int* __restrict__ edge_b, const int* __restrict__ free_idx,
+                                       const double* __restrict__ Ja, const double* __restrict__ Jb,
+                                       const double* __restrict__ scale, const double* __restrict__ b, double* __restrict__ X) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) {
+    X[vsl_cov_x_at(n, t, 0)] = b[t];
+    return;
+  }
+  const int u = t - n;
+  if (u >= 72 * k) return;
+  const int q = u / 72, side = (u % 72) / 36, r = (u % 36) / 6, c = u % 6, e = far_edges[q];
+  const int row = 6 * free_idx[side ? edge_b[e] : edge_a[e]] + c;  // (a far edge has two free endpoints)
+  X[vsl_cov_x_at(n, row, 1 + 6 * q + r)] = scale[row] * (side ? Jb : Ja)[36 * (size_t)e + 6 * r + c];
+}
+
+// entry `at` (0 .. 11: endpoint a's six rows, then b's) of column j = 6 q + r of W: its row and value
+__device__ __forceinline__ double pgo_far_w(int at, int e, int r, const int* __restrict__ edge_a, const int* __restrict__ edge_b,
+                                            const int* __restrict__ free_idx, const double* __restrict__ Ja,
+                                            const double* __restrict__ Jb, const double* __restrict__ scale, int* row) {
+  const int side = at / 6, c = at - 6 * side;
+  *row = 6 * free_idx[side ? edge_b[e] : edge_a[e]] + c;
+  return scale[*row] * (side ? Jb : Ja)[36 * (size_t)e + 6 * r + c];
+}
+
+// C = I + W^T Y_W (m x m row-major, the lower triangle computed and mirrored: exactly symmetric) and rhs = W^T y.  One
+// thread per (i, j), j = 0 .. m (j = m: the right-hand side); the sum runs over the 12 non-zero rows of W's column i in
+// fixed order.
+__global__ void pgo_far_capacitance_kernel(int n, int m, const int* __restrict__ far_edges, const int* __restrict__ edge_a,
+                                           const int* __restrict__ edge_b, const int* __restrict__ free_idx,
+                                           const double* __restrict__ Ja, const double* __restrict__ Jb,
+                                           const double* __restrict__ scale, const double* __restrict__ X, double* __restrict__ Cm,
+                                           double* __restrict__ rhs) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)m * (m + 1)) return;
+  const int i = (int)(t / (m + 1)), j = (int)(t - (size_t)i * (m + 1));
+  if (j < m && j > i) return;  // the mirror of (j, i)
+  const int e = far_edges[i / 6], r = i % 6, col = j == m ? 0 : 1 + j;
+  double s = 0;
+  for (int at = 0; at < 12; at++) {
+    int row;
+    const double w = pgo_far_w(at, e, r, edge_a, edge_b, free_idx, Ja, Jb, scale, &row);
+    s += w * X[vsl_cov_x_at(n, row, col)];
+  }
+  if (j == m) {
+    rhs[i] = s;
+  } else {
+    if (i == j) s += 1.0;
+    Cm[(size_t)i * m + j] = s;
+    Cm[(size_t)j * m + i] = s;
+  }
+}
+
+// x = y - Y_W z, one thread per row, the m products summed in ascending column order.  A failed pivot of C (*ok_c)
+// clears *flag, which a failed pivot of M has cleared already: the step is an unsuccessful one.
+__global__ void pgo_far_apply_kernel(int n, int m, const double* __restrict__ X, const double* __restrict__ z,
+                                     const int* __restrict__ ok_c, double* __restrict__ x, int* __restrict__ flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (i == 0 && !*ok_c) *flag = 0;
+  double s = 0;
+  for (int j = 0; j < m; j++) s += X[vsl_cov_x_at(n, i, 1 + j)] * z[j];
+  x[i] = X[vsl_cov_x_at(n, i, 0)] - s;
 }
 
 // band forms: the model cost change without H: d^T H d = sum over the edges of |Ja S_a d_a + Jb S_b d_b|^2.
@@ -538,7 +641,23 @@ struct PgoState {
   const char* who = "vsl_pose_graph_optimize";  // the entry point, for the messages of pgo_setup
   double* U = nullptr;
   int* wbad = nullptr;
+  // FAR EDGES.  far_mode: 0 the route is not asked for (every call but the two below), 1 vsl_pose_graph_optimize* with
+  // the switch on (taken when today's decision is dense with n > 128 and the plan finds a split), 2 vsl_pgo_far_solve
+  // (every size; far_max_near as handed in).  far_on: this solve takes it -- the storage is then the linear band of the
+  // near edges, and the plan's share of the arena sits in `extra`.
+  int far_mode = 0, far_max_near = -1;
+  bool far_on = false;
+  PgfPlan far;
+  uint8_t* far_flags = nullptr;
+  int *far_list = nullptr, *far_row_first = nullptr, *far_ok = nullptr;
+  double *far_Linv = nullptr, *far_X = nullptr, *far_C = nullptr, *far_z = nullptr, *far_diag = nullptr, *far_dfar = nullptr;
 };
+
+// the switch of the far-edge route: diagnostic "pgo_far_edges" or the environment variable VSL_PGO_FAR_EDGES
+bool pgo_far_switch(const vsl_ctx* ctx) {
+  static const bool env_on = getenv("VSL_PGO_FAR_EDGES") != nullptr;
+  return ctx->pgo_far_edges || env_on;
+}
 
 // THE storage decision of a graph (host only): dense, linear band or cyclic band -- st.ld / bw / cyclic / h_elems from
 // st.n = 6 nf unknowns and the edges' distances in free indices.  pgo_setup and vsl_pgo_covariance ask it.
@@ -593,6 +712,30 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
   int nf = 0;
   const std::vector<int> free_idx = pgo_free_index(p, &nf);
   pgo_storage(ctx, p, free_idx, nf, st);
+  if (st.far_mode == 1) {
+    // dense by pgo_storage's own rule (not by a diagnostic that asks for dense), and a split exists
+    static const bool env_dense = getenv("VSL_PGO_DENSE") != nullptr;
+    if (st.ld == 0 && st.n > 128 && !st.force_dense && !env_dense && !ctx->ba_force_dense) {
+      st.far = pgf_plan(p->n_nodes, p->node_fixed, p->edge_a, p->edge_b, p->n_edges, -1);
+      st.far_on = st.far.status == PGF_OK;
+    }
+  } else if (st.far_mode == 2) {
+    st.far = pgf_plan(p->n_nodes, p->node_fixed, p->edge_a, p->edge_b, p->n_edges, st.far_max_near);
+    if (st.far.status == PGF_NO_SPLIT)
+      return vsl_fail(ctx, VSL_ERR_INVALID, "%s: no admissible split (every candidate has no far edge, more than %d of them, a band that is not narrow, or a near component without a fixed neighbour)", st.who, PGF_MAX_FAR);
+    if (st.far.status == PGF_BAND_TOO_WIDE)
+      return vsl_fail(ctx, VSL_ERR_INVALID, "%s: max_near_distance %d: the band is not narrower than the matrix (%d unknowns)", st.who, st.far_max_near, st.n);
+    if (st.far.status == PGF_TOO_MANY_FAR)
+      return vsl_fail(ctx, VSL_ERR_INVALID, "%s: max_near_distance %d leaves more than %d far edges", st.who, st.far_max_near, PGF_MAX_FAR);
+    st.far_on = true;
+  }
+  if (st.far_on) {
+    st.cyclic = 0;
+    st.bw = st.far.bw;
+    st.ld = st.bw + 32;
+    st.h_elems = (size_t)st.n * (st.ld + 1) + 64;
+    st.extra_bytes = st.far.total;
+  }
   const size_t N = st.N, E = st.E, n = st.n;
   ArenaPlan plan(26);
   plan.add(st.poses, 7 * N);
@@ -660,6 +803,22 @@ int pgo_setup(vsl_ctx* ctx, const vsl_pgo_problem* p, PgoState& st) {
   } else {
     st.U = nullptr;  // (an empty arena slot still has an address)
   }
+  if (st.far_on) {
+    const PgfPlan& F = st.far;
+    st.far_flags = (uint8_t*)(st.extra + F.off_far);
+    st.far_list = (int*)(st.extra + F.off_far_edges);
+    st.far_row_first = (int*)(st.extra + F.off_row_first);
+    st.far_Linv = (double*)(st.extra + F.off_Linv);
+    st.far_X = (double*)(st.extra + F.off_X);
+    st.far_C = (double*)(st.extra + F.off_C);
+    st.far_z = (double*)(st.extra + F.off_z);
+    st.far_diag = (double*)(st.extra + F.off_diag);
+    st.far_dfar = (double*)(st.extra + F.off_dfar);
+    st.far_ok = (int*)(st.extra + F.off_flag);
+    if (E) VSL_HIP(ctx, hipMemcpyAsync(st.far_flags, F.far.data(), E, hipMemcpyHostToDevice, s));
+    if (F.k) VSL_HIP(ctx, hipMemcpyAsync(st.far_list, F.far_edges.data(), sizeof(int) * (size_t)F.k, hipMemcpyHostToDevice, s));
+    VSL_HIP(ctx, hipMemcpyAsync(st.far_row_first, F.row_first.data(), sizeof(int) * (size_t)F.nblk, hipMemcpyHostToDevice, s));
+  }
   VSL_HIP(ctx, hipStreamSynchronize(s));  // free_idx and the incidence lists are locals
   if (bad != none)
     return vsl_fail(ctx, VSL_ERR_INVALID, "%s: edge_info of edge %d is not positive definite (a pivot L_ii^2 <= 2^-36 Omega_ii, or not finite)", st.who, bad);
@@ -690,7 +849,8 @@ int pgo_linearize(vsl_ctx* ctx, PgoState& st, const vsl_ba_options* opt, bool fi
     VSL_HIP(ctx, hipMemsetAsync(st.g, 0, 8 * (size_t)n, s));
     if (st.N > 0)
       hipLaunchKernelGGL(pgo_build_kernel, dim3((st.N * 6 + 255) / 256), dim3(256), 0, s, st.N, n, st.inc_off, st.inc, st.edge_a,
-                         st.edge_b, st.free_idx, st.r, st.Ja, st.Jb, st.scale, st.H, st.g, st.ld, st.bw, st.cyclic);
+                         st.edge_b, st.free_idx, st.r, st.Ja, st.Jb, st.scale, st.H, st.g, st.ld, st.bw, st.cyclic,
+                         st.far_on ? (const uint8_t*)st.far_flags : (const uint8_t*)nullptr, st.far_on ? st.far_dfar : (double*)nullptr);
   }
   hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, st.cost, E, st.scalars, 0);
   VSL_CHECK_LAUNCH(ctx);
@@ -698,6 +858,33 @@ int pgo_linearize(vsl_ctx* ctx, PgoState& st, const vsl_ba_options* opt, bool fi
   VSL_HIP(ctx, hipStreamSynchronize(s));
   return VSL_OK;
 }
+// FAR EDGES: x = (M + W W^T)^-1 b, enqueued.  M: a band array (st.H or st.A, destroyed: M <- L), b and x: n doubles
+// (may be the same).  pivot_test: diag M (st.far_diag, taken by the caller before this) against the factor by the
+// 2^-36 rule of the covariance calls -- the undamped hook, where a singular M may pass the factorisation's own test on
+// rounding noise.  st.flag is left 1 / 0 as a band solve leaves it.
+int pgo_far_solve_enqueue(vsl_ctx* ctx, PgoState& st, double* M, const double* b, double* x, bool pivot_test) {
+  hipStream_t s = ctx->stream;
+  const int n = st.n, m = st.far.m, k = st.far.k, nblk = st.far.nblk;
+  int rc;
+  if ((rc = vsl_chol_factor_band_dev(ctx, M + st.ld, n, st.ld, st.bw, st.flag, st.far_Linv))) return rc;
+  if (pivot_test && (rc = vsl_cov_band_pivot_dev(ctx, n, M, st.ld, st.far_diag, st.flag))) return rc;
+  VSL_HIP(ctx, hipMemsetAsync(st.far_X, 0, sizeof(double) * (size_t)nblk * n * PGF_COLS, s));
+  hipLaunchKernelGGL(pgo_far_columns_kernel, dim3((n + 72 * k + 255) / 256), dim3(256), 0, s, n, k, st.far_list, st.edge_a, st.edge_b,
+                     st.free_idx, st.Ja, st.Jb, st.scale, b, st.far_X);
+  if ((rc = vsl_band_rhs_solve_dev(ctx, n, M, st.ld, st.bw, st.far_Linv, st.far_row_first, nblk, st.far_X, st.flag))) return rc;
+  static const int one = 1;  // (static: the asynchronous upload reads it after this function may have returned)
+  VSL_HIP(ctx, hipMemcpyAsync(st.far_ok, &one, sizeof(int), hipMemcpyHostToDevice, s));
+  if (m > 0) {
+    hipLaunchKernelGGL(pgo_far_capacitance_kernel, dim3((unsigned)(((size_t)m * (m + 1) + 255) / 256)), dim3(256), 0, s, n, m,
+                       st.far_list, st.edge_a, st.edge_b, st.free_idx, st.Ja, st.Jb, st.scale, st.far_X, st.far_C, st.far_z);
+    if ((rc = vsl_chol_solve_dev(ctx, st.far_C, st.far_z, m, st.far_ok))) return rc;
+  }
+  hipLaunchKernelGGL(pgo_far_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, m, st.far_X, st.far_z, st.far_ok, x, st.flag);
+  VSL_CHECK_LAUNCH(ctx);
+  ctx->last_pgo_far_solves++;
+  return VSL_OK;
+}
+
 // The band forms as a dense symmetric matrix (host): slot s of row i, s = 0 .. bw left of the diagonal, is entry
 // (i, i - s); a column below zero is the wrap-around corner of the cyclic form, entry (i, i - s + n); every entry is
 // mirrored.  Returns how many non-zero values lie where pgo_build_kernel writes nothing: the 32 padding slots left of
@@ -793,6 +980,54 @@ extern "C" int vsl_pgo_linearize_stored_w(vsl_ctx* ctx, const vsl_pgo_problem* p
 }
 
 namespace {
+__global__ void pgo_cov_diag_kernel(int n, const double* __restrict__ H, int ld, double* __restrict__ d);  // (the covariance section)
+}
+// The parity hook of the far-edge route (include/vslam_hip.h): H x = b for the H, g of vsl_pgo_linearize_w through the
+// band factor of the near edges and the low-rank update of the far ones, at every size.
+extern "C" int vsl_pgo_far_solve(vsl_ctx* ctx, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
+                                 const double* b, int max_near_distance, double* x, int* far_edges, int* half_bandwidth) {
+  int rc = pgo_validate(ctx, prob);
+  if (rc) return rc;
+  if (!opt || !x) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_pgo_far_solve: options or x are null");
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  PgoState st;
+  st.edge_info = edge_info;
+  st.who = "vsl_pgo_far_solve";
+  st.far_mode = 2;
+  st.far_max_near = max_near_distance < 0 ? -1 : max_near_distance;
+  if ((rc = pgo_setup(ctx, prob, st))) return rc;
+  hipStream_t s = ctx->stream;
+  const int n = st.n;
+  if (far_edges) *far_edges = st.far.k;
+  if (half_bandwidth) *half_bandwidth = st.far.bw;
+  // unit scale, one linearisation at the poses as they are (vsl_pgo_covariance's)
+  VSL_HIP(ctx, hipMemsetAsync(st.colsq, 0, 8 * (size_t)n, s));
+  hipLaunchKernelGGL(pgo_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.colsq, st.scale);
+  double cost = 0;
+  if ((rc = pgo_linearize(ctx, st, opt, false, &cost))) return rc;
+  if (b)
+    VSL_HIP(ctx, hipMemcpyAsync(st.b, b, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+  else
+    VSL_HIP(ctx, hipMemcpyAsync(st.b, st.g, 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(pgo_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, st.H, st.ld, st.far_diag);
+  VSL_CHECK_LAUNCH(ctx);
+  rc = pgo_far_solve_enqueue(ctx, st, st.H, st.b, st.b, true);
+  int ok = 0;
+  if (rc == VSL_OK) {
+    hipError_t e = hipMemcpyAsync(x, st.b, 8 * (size_t)n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&ok, st.flag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) rc = vsl_fail(ctx, VSL_ERR_HIP, "vsl_pgo_far_solve: copy back -> %s", hipGetErrorString(e));
+  }
+  VSL_HIP(ctx, hipStreamSynchronize(s));  // (also on an error: queued copies read b)
+  if (rc) return rc;
+  if (!ok) {
+    std::fill(x, x + n, 0.0);
+    return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_pgo_far_solve: the band of the near edges or the capacitance matrix is not positive definite (no fixed node, or a near component without one)");
+  }
+  return VSL_OK;
+}
+
+namespace {
 int pgo_optimize(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, const double* edge_info, const vsl_ba_options* opt,
                  vsl_ba_summary* summary);
 }
@@ -814,7 +1049,16 @@ int pgo_optimize(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, con
   PgoState st;
   st.edge_info = edge_info;
   st.who = who;
+  st.far_mode = pgo_far_switch(ctx) ? 1 : 0;
+  ctx->last_pgo_far_taken = ctx->last_pgo_far_k = ctx->last_pgo_far_bw = ctx->last_pgo_far_cols = 0;
+  ctx->last_pgo_far_solves = 0;
   if ((rc = pgo_setup(ctx, prob, st))) return rc;
+  if (st.far_on) {
+    ctx->last_pgo_far_taken = 1;
+    ctx->last_pgo_far_k = st.far.k;
+    ctx->last_pgo_far_bw = st.far.bw;
+    ctx->last_pgo_far_cols = st.far.ncols;
+  }
   hipStream_t s = ctx->stream;
   const int n = st.n, N = st.N, E = st.E;
   vsl_ba_summary sum;
@@ -831,7 +1075,10 @@ int pgo_optimize(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, con
     if ((term = lm_gate(lm, need_gmax ? INFINITY : gmax)) >= 0) { sum.termination = term; break; }
     if (n == 0) { sum.termination = 2; break; }
     // damped system + gradient norm
-    if (st.ld > 0)
+    if (st.far_on)
+      hipLaunchKernelGGL(pgo_damp_far_kernel, dim3((unsigned)((st.h_elems + 255) / 256)), dim3(256), 0, s, n, st.h_elems, st.ld,
+                         st.H, st.far_dfar, st.g, st.scale, 1.0 / lm.radius, st.A, st.b, st.gabs);
+    else if (st.ld > 0)
       hipLaunchKernelGGL(pgo_damp_band_kernel, dim3((unsigned)((st.h_elems + 255) / 256)), dim3(256), 0, s, n, st.h_elems, st.ld,
                          st.H, st.g, st.scale, 1.0 / lm.radius, st.A, st.b, st.gabs);
     else
@@ -845,7 +1092,9 @@ int pgo_optimize(vsl_ctx* ctx, const char* who, const vsl_pgo_problem* prob, con
       need_gmax = false;
     }
     it++;
-    if (st.ld > 0)
+    if (st.far_on)
+      rc = pgo_far_solve_enqueue(ctx, st, st.A, st.b, st.b, false);
+    else if (st.ld > 0)
       rc = vsl_chol_solve_band_dev(ctx, st.A + st.ld, st.b, n, st.ld, st.bw, st.flag, st.cyclic);
     else
       rc = vsl_chol_solve_dev(ctx, st.A, st.b, n, st.flag);

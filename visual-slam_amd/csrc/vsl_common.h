@@ -96,6 +96,11 @@ struct vsl_ctx {
   bool ba_force_dense = false;          // diagnostic: dense reduced camera system even where the band form applies
   bool pgo_cov_no_band_read = false;    // diagnostic: vsl_pgo_joint_covariance / vsl_pgo_edge_consistency solve unit columns for in-band pairs too instead of reading the band of the inverse
   bool ba_cov_no_band_read = false;     // diagnostic: the same for vsl_global_ba_relative_pose_covariance on its band route
+  bool pgo_far_edges = false;           // diagnostic / VSL_PGO_FAR_EDGES: pose graphs that would be stored densely because of a few long edges by a band factor plus a low-rank update (pgo.hip "FAR EDGES")
+  // that route in the last pose-graph solve on this context (vsl_ctx_last_pgo_far): taken, far edges, half bandwidth of
+  // the near band, right-hand-side columns per solve, solves
+  int last_pgo_far_taken = 0, last_pgo_far_k = 0, last_pgo_far_bw = 0, last_pgo_far_cols = 0;
+  int64_t last_pgo_far_solves = 0;
   bool ba_schur_atomics = false;       // diagnostic: large-system Schur complement by fp64 atomics (one wavefront per landmark) instead of the per-block gather
   bool ba_no_fused = false;             // diagnostic: local windows by the operator-by-operator kernels of ba.hip instead of the fused iteration (ba_fused.hip)
   bool ba_schur_entries = false;        // diagnostic: single-entry ownership in the small-system Schur kernel instead of 3 x 3 sub-blocks
@@ -250,6 +255,16 @@ int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double*
 int vsl_cov_band_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, int ld, int bw, const double* Linv, const int* col_unk,
                                   const int* row_lo, int nblk, double* X, const int* ok_dev);
 int vsl_cov_band_pivot_dev(vsl_ctx* ctx, int n, const double* L, int ld, const double* Sdiag, int* ok_dev);
+// GENERAL right-hand sides against a band factor (ba_cov.hip, the same kernel with dense columns in place of unit
+// ones): L L^T X = B in place, X holding B on entry in nblk blocks of n x 16 (vsl_cov_x_at).  L: the storage base, Linv:
+// the inverted diagonal blocks of vsl_chol_factor_band_dev.  row_first (device, [nblk]): the block's first non-zero row
+// (n: the block is zero), where its forward pass starts.  Nothing is done when *ok_dev = 0.
+int vsl_band_rhs_solve_dev(vsl_ctx* ctx, int n, const double* L, int ld, int bw, const double* Linv, const int* row_first, int nblk,
+                           double* X, const int* ok_dev);
+// The band factorisation alone (chol.hip, the panel factor behind the selected inversion): S = storage + ld, ld = bw +
+// VSL_CHOL_NB; S <- L in place, Linv <- the inverted diagonal blocks (VSL_CHOL_NB^2 doubles per panel, identity-padded;
+// device memory of the caller), *ok_dev = 1 / 0.
+int vsl_chol_factor_band_dev(vsl_ctx* ctx, double* S, int n, int ld, int bw, int* ok_dev, double* Linv);
 int vsl_cov_band_blocks_dev(vsl_ctx* ctx, int nQ, const int* q_free, const double* Z, int ld, const int* ok_dev, double* out);
 // pgo.hip, for vsl_ba_relative_pose_covariance (ba_cov.hip): per pair q of pairs (device; na / nb = row of poses, fa / fb
 // < 0 = fixed) and its 12 x 12 joint covariance joint[144 q ..], with the pose-graph functor's own device code:
