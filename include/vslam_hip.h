@@ -332,6 +332,17 @@ int vsl_diag_frames_describe_at(vsl_ctx* ctx, vsl_frames* f, int first, int n, c
                                 const int32_t* counts, int cap, int rotate_features, int32_t* moments,
                                 int32_t* tie_rec, int tie_rec_cap, int* n_ties);
 
+/* Diagnostic: WRITE keypoints into frame-store slots, so that the batched matcher and the stereo stage can be handed
+ * descriptors no image would produce (ragged counts, ties at tile edges, distances planted at the threshold).  Slot
+ * first + i (n >= 1 slots inside [0, max_images)) gets counts[i] (0 .. cap, 1 <= cap <= max_features) descriptors from
+ * desc[i][cap][4] and, if corners_xy is not null, corner positions from corners_xy[i][cap][2]; its keypoint count becomes
+ * counts[i].  Entries past counts[i], and the slot's moments and angles, keep what they held.  The call first settles
+ * the store's pending describe launches like vsl_frames_resolve_ties (no later resolve patches a bit of an injected
+ * descriptor), synchronises, and copies with plain hipMemcpy; no kernel runs.  A null ctx / f / counts / desc, a range
+ * outside the store, a count outside [0, cap] or a cap outside [1, max_features]: VSL_ERR_INVALID, nothing written. */
+int vsl_diag_frames_set_keypoints(vsl_ctx* ctx, vsl_frames* f, int first, int n, const int32_t* counts, int cap,
+                                  const int32_t* corners_xy, const uint64_t* desc);
+
 /* ------------------------------------------------ device-resident map (per-frame tracking) */
 /*
  * The single-stream path: what project_landmarks + find_matches_landmarks (include/visnav/vo_utils.h:48-167)

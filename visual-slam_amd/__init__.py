@@ -999,6 +999,27 @@ class Frames:
         n_rec = min(nt.value & ((1 << 30) - 1), tie_rec_cap)
         return [mom[i, :len(c)].copy() for i, c in enumerate(corners)], nt.value, rec[:n_rec].copy()
 
+    def set_keypoints(self, first, descs, corners=None):
+        """Diagnostic (vsl_diag_frames_set_keypoints): write descriptors -- one (k, 4) uint64 array per slot from `first`
+        on -- and, with `corners` (one (k, 2) integer array per slot), corner positions straight into the store; a slot's
+        keypoint count becomes its k.  Pending describe launches are resolved first."""
+        descs = [np.ascontiguousarray(d, np.uint64).reshape(-1, 4) for d in descs]
+        n, cap = len(descs), max([1] + [len(d) for d in descs])
+        dd = np.zeros((max(n, 1), cap, 4), np.uint64)
+        for i, d in enumerate(descs):
+            dd[i, :len(d)] = d
+        counts = np.array([len(d) for d in descs] or [0], np.int32)
+        xy = None
+        if corners is not None:
+            corners = [np.ascontiguousarray(c, np.int32).reshape(-1, 2) for c in corners]
+            assert [len(c) for c in corners] == [len(d) for d in descs]
+            xy = np.zeros((max(n, 1), cap, 2), np.int32)
+            for i, c in enumerate(corners):
+                xy[i, :len(c)] = c
+        self.ctx._ck(self.ctx.L.vsl_diag_frames_set_keypoints(self.ctx.h, self.h, int(first), n, counts.ctypes.data_as(i32p),
+                                                              cap, xy.ctypes.data_as(i32p) if xy is not None else None,
+                                                              dd.ctypes.data_as(u64p)))
+
     def resolve_ties(self):
         n = C.c_int32()
         self.ctx._ck(self.ctx.L.vsl_frames_resolve_ties(self.ctx.h, self.h, C.byref(n)))

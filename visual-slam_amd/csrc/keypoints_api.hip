@@ -110,6 +110,28 @@ extern "C" int vsl_diag_frames_describe_at(vsl_ctx* ctx, vsl_frames* f, int firs
   return VSL_OK;
 }
 
+extern "C" int vsl_diag_frames_set_keypoints(vsl_ctx* ctx, vsl_frames* f, int first, int n, const int32_t* counts, int cap,
+                                             const int32_t* corners_xy, const uint64_t* desc) {
+  if (!ctx || !f || first < 0 || n < 1 || n > f->max_images || first > f->max_images - n || !counts || !desc || cap < 1 ||
+      cap > f->F)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_diag_frames_set_keypoints: bad arguments");
+  for (int i = 0; i < n; i++)
+    if (counts[i] < 0 || counts[i] > cap) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_diag_frames_set_keypoints: count %d of slot %d", counts[i], first + i);
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = vsl_resolve_ties(ctx, f, nullptr);  // a later resolve must find nothing to patch over what is written here
+  if (rc) return rc;
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < n; i++) {
+    const size_t base = (size_t)(first + i) * f->F;
+    if (counts[i] == 0) continue;
+    VSL_HIP(ctx, hipMemcpy(f->kp_desc + 4 * base, desc + 4 * (size_t)i * cap, sizeof(uint64_t) * 4 * counts[i], hipMemcpyHostToDevice));
+    if (corners_xy)
+      VSL_HIP(ctx, hipMemcpy(f->kp_xy + 2 * base, corners_xy + 2 * (size_t)i * cap, sizeof(int32_t) * 2 * counts[i], hipMemcpyHostToDevice));
+  }
+  VSL_HIP(ctx, hipMemcpy(f->kp_count + first, counts, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  return VSL_OK;
+}
+
 static int check_image(vsl_ctx* ctx, const uint8_t* img, int w, int h, size_t pitch) {
   if (!ctx) return VSL_ERR_INVALID;
   if (!img || w < 40 || h < 40 || pitch < (size_t)w)
