@@ -3,6 +3,7 @@
 // with values worked out by hand.
 //   check                                       stdin: n_nodes, the fixed flags, n_pairs, the pairs -> "<error> <index>"
 //   plan <folded> <dense> <bw> <no_read> <cand>  stdin as above -> the plan's fields, one per line
+//   nodes <folded> <dense> <bw>                 stdin: n_nodes, the fixed flags, n_q, the queried nodes -> the node-list plan
 //   sweep                                       properties over chains and rings of many sizes -> "checked <n> solve <m>"
 #include <cstdio>
 #include <cstdlib>
@@ -50,6 +51,8 @@ void line(const char* name, const std::vector<int>& v) {
       std::exit(1);                                                                \
     }                                                                              \
   } while (0)
+
+void verify_arena(const PgcPlan& P, size_t np, size_t nc, size_t nq);
 
 // every property the device code relies on
 void verify(const Input& in, const PgcPlan& P, bool folded, bool dense, int bw, bool no_read, bool cand) {
@@ -105,20 +108,70 @@ void verify(const Input& in, const PgcPlan& P, bool folded, bool dense, int bw, 
   for (int blk = 0; blk < P.nblk; blk++) REQUIRE(P.row_lo[blk] >= 0 && P.row_lo[blk] <= P.n);
   // the arena: 256-byte aligned, in order, nothing overlaps
   const size_t np = (size_t)in.n_pairs, nc = cand ? np : 0;
-  const size_t offs[] = {P.off_pairs, P.off_col_unk, P.off_row_lo, P.off_meas, P.off_meas_cov, P.in_bytes, P.off_Hdiag, P.off_Linv,
-                         P.off_X, P.out_off, P.out_off + P.off_cov, P.out_off + P.off_resid, P.out_off + P.off_resid_cov,
-                         P.out_off + P.off_chi2, P.total};
-  const size_t need[] = {sizeof(PgcPairDev) * np, sizeof(int) * P.col_unk.size(), sizeof(int) * P.row_lo.size(), 48 * nc, 288 * nc, 0,
-                         8 * (size_t)P.n, dense ? 8 * (size_t)((P.n + 31) / 32) * 1024 : 0, 8 * (size_t)P.nblk * P.n * PGC_COLS, 0,
-                         1152 * np, 48 * nc, 288 * nc, 8 * nc};
-  for (int i = 0; i < 14; i++) {
+  REQUIRE(P.q_free.empty() && P.q_slot.empty());  // a pair plan has no node list
+  verify_arena(P, np, nc, 0);
+}
+
+// the arena of either plan: 256-byte aligned, in order, nothing overlaps, `total` covers every offset
+void verify_arena(const PgcPlan& P, size_t np, size_t nc, size_t nq) {
+  const size_t offs[] = {P.off_pairs, P.off_q_free, P.off_col_unk, P.off_row_lo, P.off_meas, P.off_meas_cov, P.in_bytes, P.off_Hdiag,
+                         P.off_Linv, P.off_X, P.out_off, P.out_off + P.off_blocks, P.out_off + P.off_cov, P.out_off + P.off_resid,
+                         P.out_off + P.off_resid_cov, P.out_off + P.off_chi2, P.total};
+  const size_t need[] = {sizeof(PgcPairDev) * np, sizeof(int) * nq, sizeof(int) * P.col_unk.size(), sizeof(int) * P.row_lo.size(), 48 * nc,
+                         288 * nc, 0, 8 * (size_t)P.n, P.dense ? 8 * (size_t)((P.n + 31) / 32) * 1024 : 0,
+                         8 * (size_t)P.nblk * P.n * PGC_COLS, 0, 288 * nq, 1152 * np, 48 * nc, 288 * nc, 8 * nc};
+  for (int i = 0; i < 16; i++) {
     REQUIRE(offs[i] % 256 == 0 && offs[i] + need[i] <= offs[i + 1]);
+    REQUIRE(offs[i] <= P.total);
   }
   REQUIRE(P.out_bytes == P.total - P.out_off);
 }
 
+// the node-list plan (the marginal call): what pgo_cov.hip and the kernels behind it rely on
+void verify_nodes(const Input& in, const std::vector<int32_t>& nodes, const PgcPlan& P, bool folded, bool dense, int bw) {
+  int nf = 0;
+  for (uint8_t f : in.fixed) nf += !f;
+  REQUIRE(P.nf == nf && P.n == 6 * nf && P.n_pairs == 0 && P.pairs.empty() && P.dense == dense && P.bw == (dense ? 0 : bw));
+  // the numbering is the pair plan's
+  const PgcPlan R = pgc_plan(in.n_nodes, in.fixed.data(), folded, dense, bw, false, nullptr, nullptr, 0, false);
+  REQUIRE(P.dev_free == R.dev_free && P.dev_node == R.dev_node);
+  // unique, ascending, exactly the queried nodes; every query finds its own node
+  REQUIRE(std::is_sorted(P.q_free.begin(), P.q_free.end()));
+  REQUIRE(std::adjacent_find(P.q_free.begin(), P.q_free.end()) == P.q_free.end());
+  std::set<int> asked;
+  REQUIRE(P.q_slot.size() == nodes.size());
+  for (size_t q = 0; q < nodes.size(); q++) {
+    const int f = P.dev_free[nodes[q]];
+    REQUIRE(f >= 0 && f < nf);
+    asked.insert(f);
+    REQUIRE(P.q_slot[q] >= 0 && P.q_slot[q] < (int)P.q_free.size() && P.q_free[P.q_slot[q]] == f);
+  }
+  REQUIRE(asked.size() == P.q_free.size());
+  // dense: six unit columns per unique node, slot s at right-hand sides 6 s .. 6 s + 5 (what the dense block kernel
+  // reads); band: none
+  REQUIRE(P.col_nodes == (dense ? P.q_free : std::vector<int>()));
+  REQUIRE(P.nblk == (6 * (int)P.col_nodes.size() + PGC_COLS - 1) / PGC_COLS);
+  REQUIRE((int)P.col_unk.size() == PGC_COLS * P.nblk && (int)P.row_lo.size() == P.nblk);
+  for (size_t j = 0; j < P.col_unk.size(); j++)
+    REQUIRE(j < 6 * P.col_nodes.size() ? P.col_unk[j] == 6 * P.col_nodes[j / 6] + (int)(j % 6) : P.col_unk[j] == -1);
+  // a dense pair query that names the same nodes solves the same columns in the same workgroups
+  if (dense && nodes.size() >= 2) {
+    std::vector<int32_t> a, b;
+    for (size_t q = 0; q < nodes.size(); q++)
+      if (nodes[q] != nodes[0]) {
+        a.push_back(nodes[0]);
+        b.push_back(nodes[q]);
+      }
+    if (!a.empty()) {
+      const PgcPlan J = pgc_plan(in.n_nodes, in.fixed.data(), folded, true, bw, false, a.data(), b.data(), (int)a.size(), false);
+      REQUIRE(J.col_nodes == P.col_nodes && J.col_unk == P.col_unk && J.nblk == P.nblk);
+    }
+  }
+  verify_arena(P, 0, 0, P.q_free.size());
+}
+
 int sweep() {
-  long checked = 0, solve = 0;
+  long checked = 0, solve = 0, node_lists = 0;
   unsigned rng = 12345u;
   auto next = [&]() { return rng = rng * 1664525u + 1013904223u, rng >> 8; };
   for (int n_nodes : {2, 3, 7, 23, 30, 64, 129})
@@ -155,8 +208,22 @@ int sweep() {
               checked++;
               solve += P.n_solve;
             }
+            if (mode == 2) continue;  // (the diagnostic is a rule of pairs)
+            // node lists over the same graph: empty, one node, random with duplicates, every free node in reverse order
+            std::vector<int32_t> free_nodes;
+            for (int i = 0; i < n_nodes; i++)
+              if (!in.fixed[i]) free_nodes.push_back(i);
+            std::vector<std::vector<int32_t>> lists(4);
+            lists[1].push_back(free_nodes[next() % free_nodes.size()]);
+            for (int q = (int)(next() % 20); q > 0; q--) lists[2].push_back(free_nodes[next() % free_nodes.size()]);
+            lists[3].assign(free_nodes.rbegin(), free_nodes.rend());
+            for (const std::vector<int32_t>& nodes : lists) {
+              const PgcPlan P = pgc_node_plan(n_nodes, in.fixed.data(), folded != 0, mode == 0, bw, nodes.data(), (int)nodes.size());
+              verify_nodes(in, nodes, P, folded != 0, mode == 0, bw);
+              node_lists++;
+            }
           }
-  std::printf("checked %ld solve %ld\n", checked, solve);
+  std::printf("checked %ld solve %ld node_lists %ld\n", checked, solve, node_lists);
   return 0;
 }
 
@@ -205,6 +272,24 @@ int main(int argc, char** argv) {
     line("arena", {(int)P.in_bytes, (int)P.off_X, (int)P.out_off, (int)P.out_bytes, (int)P.total});
     return 0;
   }
-  std::fprintf(stderr, "usage: pgo_cov_plan_test check | plan <folded> <dense> <bw> <no_read> <cand> | sweep\n");
+  if (cmd == "nodes" && argc == 5) {
+    // (the node list arrives in the first column of the pair input: "<node> 0" per line)
+    const bool folded = std::atoi(argv[2]) != 0, dense = std::atoi(argv[3]) != 0;
+    const int bw = std::atoi(argv[4]);
+    for (int32_t v : in.a) REQUIRE(v >= 0 && v < in.n_nodes && !in.fixed[v]);
+    const PgcPlan P = pgc_node_plan(in.n_nodes, in.fixed.data(), folded, dense, bw, in.a.data(), in.n_pairs);
+    verify_nodes(in, in.a, P, folded, dense, bw);
+    line("dims", {P.nf, P.n, P.bw, P.nblk, P.n_pairs});
+    line("dev_free", P.dev_free);
+    line("q_free", P.q_free);
+    line("q_slot", P.q_slot);
+    line("col_nodes", P.col_nodes);
+    line("col_unk", P.col_unk);
+    // every offset, then the sizes that must cover them
+    line("arena", {(int)P.off_pairs, (int)P.off_q_free, (int)P.off_col_unk, (int)P.off_row_lo, (int)P.in_bytes, (int)P.off_Hdiag,
+                   (int)P.off_Linv, (int)P.off_X, (int)P.out_off, (int)P.off_blocks, (int)P.out_bytes, (int)P.total});
+    return 0;
+  }
+  std::fprintf(stderr, "usage: pgo_cov_plan_test check | plan <folded> <dense> <bw> <no_read> <cand> | nodes <folded> <dense> <bw> | sweep\n");
   return 2;
 }

@@ -5,7 +5,7 @@ in the style of ba_cov_ref.py.  numpy only, np.longdouble throughout; imports ne
   log       atan2 everywhere, no series branch in the rotation (only the exact n == 0); the coefficient c of
             V^-1 = I - Om / 2 + c Om^2 by its Taylor series sum |B_2k| theta^(2k-2) / (2k)! below 0.25 (9 terms: the
             next one is below 1e-22) and in closed form above, where 1 - (theta/2) cot(theta/2) >= 5e-3 loses no digits
-  residual  r = log(T_a^-1 T_b) - meas                                    (pgo.hip edge_residual's argument order)
+  residual  r = log(T_a^-1 T_b) - meas                                    (pgo_device.h edge_residual's argument order)
   Jacobians d r / d delta along T * exp(delta), both blocks, by central differences D(h) in long double, Richardson
             extrapolated: J(h) = (4 D(h/2) - D(h)) / 3.  With h = 1e-4: truncation ~ h^4 f^(5) / 480 ~ 1e-18 |f|,
             rounding ~ a few tens of eps |f| / h ~ 1e-14 |f| (eps = 2^-63), both far below 1e-11 max|J|.  The function

@@ -1,5 +1,5 @@
 """GPU: vsl_ba_relative_pose_covariance and vsl_global_ba_relative_pose_covariance (visual-slam_amd/csrc/ba_cov.hip,
-ba_relpose_kernel in pgo.hip) against tests/ba_relpose_ref.py, whose docstring derives the four tolerances (joint:
+ba_relpose_kernel in ba_cov.hip) against tests/ba_relpose_ref.py, whose docstring derives the four tolerances (joint:
 ba_cov_ref.Ref.tol; cov: 144 max|J|^2 Ref.tol; info: 36 max|Omega|^2 tol_cov + 64 cond(Sigma_r) 2^-52 max|Omega|; meas:
 pgo_ref.GPU_TOL max|meas|).  The measured maxima are printed beside the bounds (-s).  Bit-for-bit claims are asserted
 with array_equal.

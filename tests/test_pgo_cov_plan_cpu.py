@@ -1,6 +1,6 @@
-"""The host half of vsl_pgo_joint_covariance / vsl_pgo_edge_consistency (visual-slam_amd/csrc/pgo_cov_plan.h: pair
-validation, the class of each pair, the fold relabelling, the unique column nodes and each pair's columns, the arena),
-compiled with g++ as plain C++ without HIP headers and driven by tests/cpp/pgo_cov_plan_test.cpp.  The literal values
+"""The host half of the pose graph's covariance calls (visual-slam_amd/csrc/pgo_cov_plan.h: pair validation, the class
+of each pair, the fold relabelling, the unique column nodes and each pair's columns, the node-list plan of the marginal
+call, the arena), compiled with g++ as plain C++ without HIP headers and driven by tests/cpp/pgo_cov_plan_test.cpp.  The literal values
 are worked out by hand from the rules in the header; the program itself verifies the plan's properties on every plan it
 prints and over a sweep of sizes.  A second build of the same program runs under AddressSanitizer and
 UndefinedBehaviorSanitizer (a stand-alone program: nothing is loaded into Python)."""
@@ -93,9 +93,58 @@ def test_dense_plan_gives_every_free_node_its_columns(exe):
     assert p["dims"] == [7, 42, 0, 3, 1, 0, 4]
 
 
+def _nodes(nodes):
+    # a node list travels in the first column of the pair input
+    return [(v, 0) for v in nodes]
+
+
+def test_node_list_on_a_dense_four_node_graph(exe):
+    # node 0 fixed: free indices - 0 1 2; the query is permuted and names nodes twice
+    p = _fields(_run(exe, "nodes", 0, 1, 0, stdin=_graph([1, 0, 0, 0], _nodes([3, 1, 3, 2, 1]))))
+    assert p["dims"] == [3, 18, 0, 2, 0]
+    assert p["dev_free"] == [-1, 0, 1, 2]
+    # unique and ascending, whatever the order of the query; every query points at its node's block
+    assert p["q_free"] == [0, 1, 2] and p["q_slot"] == [2, 0, 2, 1, 0]
+    # dense: the column nodes ARE the unique queried nodes, six columns each, sixteen per workgroup
+    assert p["col_nodes"] == [0, 1, 2]
+    assert p["col_unk"] == list(range(18)) + [-1] * 14
+    # q_free 12 B | col_unk 128 B | row_lo 8 B || diag H 144 B | Linv one 32 x 32 panel | X 2 x 18 x 16 || blocks 3 x 288 B
+    assert p["arena"] == [0, 0, 256, 512, 768, 768, 1024, 9216, 13824, 0, 1024, 14848]
+    # a subset gets the same columns for its nodes' own slots: ascending, unique
+    q = _fields(_run(exe, "nodes", 0, 1, 0, stdin=_graph([1, 0, 0, 0], _nodes([3, 3]))))
+    assert q["q_free"] == [2] and q["q_slot"] == [0, 0] and q["col_unk"] == [12, 13, 14, 15, 16, 17] + [-1] * 10
+
+
+def test_node_list_on_a_folded_ring_of_forty(exe):
+    # node 0 fixed, 39 free: free index f goes to 2 f for f <= 19, else to 2 (38 - f) + 1
+    fixed = [1] + [0] * 39
+    p = _fields(_run(exe, "nodes", 1, 0, 17, stdin=_graph(fixed, _nodes([39, 1, 20, 21, 39]))))
+    assert p["dims"] == [39, 234, 17, 0, 0]
+    assert p["dev_free"][:4] == [-1, 0, 2, 4] and p["dev_free"][19:22] == [36, 38, 37] and p["dev_free"][39] == 1
+    assert p["q_free"] == [0, 1, 37, 38] and p["q_slot"] == [1, 0, 3, 2, 1]
+    # band routes: a diagonal block lies inside the band of the inverse, nothing is solved
+    assert p["col_nodes"] == [] and p["col_unk"] == []
+    # q_free 16 B || diag H 1872 B, no Linv, no X || blocks 4 x 288 B
+    assert p["arena"] == [0, 0, 256, 256, 256, 256, 2304, 2304, 2304, 0, 1280, 3584]
+    # the same ring where the folded band is too wide: dense columns in the folded numbering
+    d = _fields(_run(exe, "nodes", 1, 1, 0, stdin=_graph(fixed, _nodes([39, 1]))))
+    assert d["q_free"] == [0, 1] and d["q_slot"] == [1, 0] and d["col_unk"] == list(range(12)) + [-1] * 4
+
+
+def test_empty_node_list(exe):
+    p = _fields(_run(exe, "nodes", 0, 1, 0, stdin=_graph([1, 0, 0, 0], [])))
+    assert p["q_free"] == [] and p["q_slot"] == [] and p["col_nodes"] == [] and p["col_unk"] == []
+    assert p["dims"] == [3, 18, 0, 0, 0]
+    # only the work buffers are left: diag H and the panel of Linv
+    assert p["arena"] == [0, 0, 0, 0, 0, 0, 256, 8448, 8448, 0, 0, 8448]
+
+
 def test_sweep(exe):
     (out,) = _run(exe, "sweep")
     w = out.split()
+    # node lists: four per graph (empty, one node, random with duplicates, all free nodes in reverse) in the dense and
+    # the band mode: 152 graphs per mode
+    assert w[4] == "node_lists" and int(w[5]) == 152 * 2 * 4
     # 7 sizes x 3 fixed counts x both numberings x 3 modes x 4 widths x with / without candidates, less the two
     # combinations with as many fixed nodes as nodes (96 plans)
     assert w[0] == "checked" and int(w[1]) == 7 * 3 * 2 * 3 * 4 * 2 - 96 and w[2] == "solve" and int(w[3]) > 1000
@@ -106,4 +155,7 @@ def test_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     assert _run(san, "sweep")
     assert _run(san, "plan", 1, 0, 11, 0, 1, stdin=_graph(FIXED, PAIRS))
     assert _run(san, "plan", 0, 1, 0, 0, 1, stdin=_graph(FIXED, PAIRS))
+    assert _run(san, "nodes", 1, 0, 11, stdin=_graph(FIXED, _nodes([7, 0, 7, 3])))
+    assert _run(san, "nodes", 0, 1, 0, stdin=_graph(FIXED, _nodes([7, 0, 7, 3])))
+    assert _run(san, "nodes", 0, 1, 0, stdin=_graph(FIXED, []))
     assert _run(san, "check", stdin=_graph(FIXED, [(0, 1), (8, 1)]))

@@ -80,7 +80,7 @@ def test_jacobian_step_halving_disagreement_is_below_the_gpu_bound():
 
 
 def _storage_decision(vsl, g):
-    """The storage rule vsl_pose_graph_optimize documents (pgo.hip pgo_setup), restated from the free indices of the
+    """The storage rule vsl_pose_graph_optimize documents (pgo.hip pgo_storage), restated from the free indices of the
     edges.  A restatement proves nothing about pgo_setup: the check that a topology takes the storage it names is the GPU
     test's assertion on what vsl_pgo_linearize_stored reports.  This only keeps the fixtures' expected values consistent
     with the documented rule and the host-side ring layout without a GPU."""

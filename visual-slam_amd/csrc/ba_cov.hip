@@ -36,8 +36,19 @@
 // Z does not depend on the query, and a landmark's sum runs over its own observations in ascending band position: the
 // subset and run-to-run guarantees hold on this route as well.  A queried landmark may have at most COV_KMAX
 // observations (its W blocks are kept in LDS) on either route.
-// The solve kernel is also what vsl_spd_inverse_band and vsl_pgo_covariance use on their dense routes
-// (vsl_cov_unit_columns_dev below).
+//
+// THE SHARED LAYER.  "diag of the matrix, then its inverse one of two ways, then blocks of the inverse" is one chain for
+// the reduced camera system here and for the pose graph's H (pgo_cov.hip), written once at the end of this file:
+//   vsl_cov_diag_dev          ba_cov_diag_kernel, dense or band storage
+//   vsl_cov_inverse_dev       that, then dense: vsl_chol_factor_dev + unit columns; band: vsl_chol_selinv_band_dev, the
+//                             pivot test, and unit columns against the band factor where the plan has any
+//   vsl_cov_diag_blocks_dev   the 6 x 6 diagonal blocks (dense: from X, mirror entries averaged; band: from Z, mirrored)
+//   vsl_cov_pair_blocks_dev   ba_pair_blocks_kernel: the 12 x 12 joint blocks of pairs
+// Every covariance call of either side goes through them, so a joint call's diagonal blocks are the marginal call's
+// bytes by construction: the same kernels on the same columns (a node-list query and a pair query that name the same
+// nodes get the same ascending unique columns from pgo_cov_plan.h, hence the same workgroups; and were the grouping to
+// differ, a column's bits do not depend on its neighbours, see above).  vsl_spd_inverse_band (chol.hip) uses the dense
+// unit-column solve alone (vsl_cov_unit_columns_dev).
 //
 // "Not positive definite" is decided to working precision: a pivot L_ii^2 <= 2^-36 S_ii fails the factorisation
 // (VSL_ERR_NUMERIC); the ratio is invariant under a rescaling of the unknowns.  A free gauge (no fixed camera) leaves
@@ -59,6 +70,8 @@
 #include "ba_large.h"
 #pragma clang diagnostic pop
 #include "ba_state.h"
+#include "pgo_device.h"
+#include "relpose_math.h"
 
 // (COV_NB, COV_COLS: ba_cov_plan.h)
 #define COV_THREADS 256
@@ -75,18 +88,17 @@ namespace {
 
 typedef double cov_v4d __attribute__((ext_vector_type(4)));
 
-// entry (row i, right-hand side col) of X: workgroup blocks of n x COV_COLS, row-major
-__device__ __forceinline__ size_t cov_x_at(int n, int i, int col) {
-  return (size_t)(col / COV_COLS) * n * COV_COLS + (size_t)i * COV_COLS + (col % COV_COLS);
-}
+// (entry (row i, right-hand side col) of X: vsl_cov_x_at of vsl_common.h -- workgroup blocks of n x COV_COLS, row-major)
+static_assert(COV_COLS == 16, "vsl_cov_x_at (vsl_common.h) spells the block width out");
 
-// S: the storage as ba_schur filled it (ld = 0: dense n x n; else band rows of ld + 1 slots, the diagonal last)
+// S: the storage as ba_schur / pgo_build_kernel filled it (ld = 0: dense n x n; else band rows of ld + 1 slots, the
+// diagonal last)
 __global__ void ba_cov_diag_kernel(int n, const double* __restrict__ S, int ld, double* __restrict__ d) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) d[i] = ld > 0 ? S[(size_t)i * (ld + 1) + ld] : S[(size_t)i * n + i];
 }
 
-// band routes (here and vsl_pgo_covariance): the pivot test of the file header on the factor left in the band storage
+// band routes: the pivot test of the file header on the factor left in the band storage
 // (every failing thread stores the same 0)
 __global__ void cov_band_pivot_kernel(int n, const double* __restrict__ L, int ld, const double* __restrict__ d, int* __restrict__ ok) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,13 +118,14 @@ __global__ void cov_band_pose_kernel(int nQ, const int* __restrict__ q_free, con
   out[t] = Z[(size_t)i * (ld + 1) + ld - (i - j)];
 }
 
-// Joint blocks of camera pairs (vsl_ba_relative_pose_covariance): one thread per entry of a 12 x 12 block, the entry rule
-// of pgo.hip's pgo_joint_blocks_kernel on S^-1.  Diagonal blocks: the rule of the pose kernels of the same route, bit for
-// bit (band: entry (max, min) of Z as cov_band_pose_kernel; dense: the two mirror entries of the camera's own columns
-// averaged as ba_cov_pose_kernel).  Cross block, entry (row r of camera x, column c of camera y): with columns for both
-// cameras the average of X_y[6 x + r][c] and X_x[6 y + c][r]; with columns for one of them that single entry; with none
-// entry (max, min) of Z.  Every rule gives (x, r; y, c) and (y, c; x, r) the same number: the block is symmetric and a
-// swapped pair is the swapped, transposed block.  A fixed camera (f < 0): exactly 0.0.  Z: the storage base.
+// Joint blocks of pairs of cameras (vsl_ba_relative_pose_covariance) or nodes (vsl_pgo_joint_covariance,
+// vsl_pgo_edge_consistency): one thread per entry of a 12 x 12 block of the inverse.  Diagonal blocks: the rule of the
+// pose kernels of the same route, bit for bit (band: entry (max, min) of Z as cov_band_pose_kernel; dense: the two
+// mirror entries of the camera's own columns averaged as ba_cov_pose_kernel).  Cross block, entry (row r of camera x,
+// column c of camera y): with columns for both cameras the average of X_y[6 x + r][c] and X_x[6 y + c][r]; with columns
+// for one of them that single entry; with none entry (max, min) of Z.  Every rule gives (x, r; y, c) and (y, c; x, r)
+// the same number: the block is symmetric and a swapped pair is the swapped, transposed block.  A fixed camera (f < 0):
+// exactly 0.0.  Z: the storage base.
 __global__ void ba_pair_blocks_kernel(int n, int n_pairs, const PgcPairDev* __restrict__ pairs, int band, const double* __restrict__ Z,
                                       int ld, const double* __restrict__ X, const int* __restrict__ ok, double* __restrict__ out) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -129,11 +142,11 @@ __global__ void ba_pair_blocks_kernel(int n, int n_pairs, const PgcPairDev* __re
     if (!cols)
       v = Z[(size_t)max(i, j) * (ld + 1) + ld - (max(i, j) - min(i, j))];
     else if (cx >= 0 && cy >= 0)
-      v = 0.5 * (X[cov_x_at(n, i, cy + c)] + X[cov_x_at(n, j, cx + r)]);
+      v = 0.5 * (X[vsl_cov_x_at(n, i, cy + c)] + X[vsl_cov_x_at(n, j, cx + r)]);
     else if (cy >= 0)
-      v = X[cov_x_at(n, i, cy + c)];
+      v = X[vsl_cov_x_at(n, i, cy + c)];
     else
-      v = X[cov_x_at(n, j, cx + r)];
+      v = X[vsl_cov_x_at(n, j, cx + r)];
   }
   out[t] = v;
 }
@@ -414,7 +427,7 @@ __global__ void ba_cov_pose_kernel(int n, int nQ, const int* __restrict__ q_free
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 36 * nQ || !*ok) return;
   const int q = t / 36, a = (t % 36) / 6, b = t % 6, c = q_free[q];
-  out[t] = 0.5 * (X[cov_x_at(n, 6 * c + a, 6 * q + b)] + X[cov_x_at(n, 6 * c + b, 6 * q + a)]);
+  out[t] = 0.5 * (X[vsl_cov_x_at(n, 6 * c + a, 6 * q + b)] + X[vsl_cov_x_at(n, 6 * c + b, 6 * q + a)]);
 }
 
 // Where the landmark kernel reads [S^-1]_{6 ci + r, 6 cj + b} (ci, cj: free indices of two cameras that observe the
@@ -426,7 +439,7 @@ struct CovDenseInverse {
   const double* __restrict__ X;
   struct Block { int row, col; };
   __device__ __forceinline__ Block block(int ci, int cj) const { return Block{6 * ci, 6 * qpos[cj]}; }
-  __device__ __forceinline__ double at(const Block& h, int r, int b) const { return X[cov_x_at(n, h.row + r, h.col + b)]; }
+  __device__ __forceinline__ double at(const Block& h, int r, int b) const { return X[vsl_cov_x_at(n, h.row + r, h.col + b)]; }
 };
 // Band route: the band array Z of the inverse (Z = its ORIGIN, storage + ld; cov_band_at of ba_cov_plan.h).  Two free
 // cameras that observe one landmark are adjacent in the covisibility graph, so |ci - cj| <= half and every entry of
@@ -547,6 +560,75 @@ __global__ __launch_bounds__(64) void ba_cov_landmark_kernel(BlArgs a, const int
   }
 }
 
+// The producer side of the pose graph's _w entry points (vsl_ba_relative_pose_covariance): one wavefront per pair
+// (a, b) of a bundle-adjustment problem, whose 12 x 12 joint block of S^-1 is in `joint`.  Lane 0 evaluates the pose
+// graph's functor at a zero measurement with its own dual numbers (pgo_device.h) -- meas = log(T_a^-1 T_b), and the
+// Jacobians of the residual, which do not depend on the measurement; a fixed camera's half of J is zero.  The lanes share
+// T = Sigma J^T and M = J T as in pgo_edge_consistency_kernel (pgo_cov.hip; every sum in ascending index order), cov =
+// (M + M^T) / 2.  Lane 0
+// factors cov = L L^T (a pivot L_ii^2 <= 2^-36 cov_ii, or one that is not finite, fails) and inverts L by forward
+// substitution; info_ij = sum_{k >= max(i, j)} Linv_ki Linv_kj, k ascending, one lane per entry: (i, j) and (j, i) sum
+// the same products in the same order.  The result is then put through the pivot test of pgo_edge_whiten_kernel, so a
+// finite info is one that the _w calls accept.  A failing pair gets 36 NaN and singular[q] = 1.  No atomics.
+__global__ __launch_bounds__(64) void ba_relpose_kernel(int n_pairs, const double* __restrict__ poses,
+                                                        const PgcPairDev* __restrict__ pairs, const double* __restrict__ joint,
+                                                        const int* __restrict__ ok, double* __restrict__ meas,
+                                                        double* __restrict__ cov, double* __restrict__ info,
+                                                        int* __restrict__ singular) {
+  __shared__ double Jm[6][12], Tm[12][6], Mm[6][6], Am[6][6], Li[6][6];
+  __shared__ int bad;
+  const int q = blockIdx.x, lane = threadIdx.x;
+  if (q >= n_pairs || !*ok) return;
+  const PgcPairDev p = pairs[q];
+  if (lane == 0) {
+    D12 qc[4], tc[3], qn[4], tn[3], rd[6];
+    const double zero[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    seed_pose(poses + 7 * (size_t)p.na, 0, qc, tc);
+    seed_pose(poses + 7 * (size_t)p.nb, 6, qn, tn);
+    edge_residual(qc, tc, qn, tn, zero, rd);
+    for (int i = 0; i < 6; i++) {
+      meas[6 * (size_t)q + i] = rd[i].v;
+      for (int c = 0; c < 6; c++) {
+        Jm[i][c] = p.fa >= 0 ? rd[i].d[c] : 0.0;
+        Jm[i][6 + c] = p.fb >= 0 ? rd[i].d[6 + c] : 0.0;
+      }
+    }
+    bad = 0;
+  }
+  __syncthreads();
+  const double* S = joint + 144 * (size_t)q;
+  for (int t = lane; t < 72; t += 64) {
+    const int a = t / 6, i = t % 6;
+    double s = 0.0;
+    for (int b = 0; b < 12; b++) s += S[12 * a + b] * Jm[i][b];
+    Tm[a][i] = s;
+  }
+  __syncthreads();
+  if (lane < 36) {
+    const int i = lane / 6, j = lane % 6;
+    double s = 0.0;
+    for (int a = 0; a < 12; a++) s += Jm[i][a] * Tm[a][j];
+    Mm[i][j] = s;
+  }
+  __syncthreads();
+  if (lane < 36) {
+    const int i = lane / 6, j = lane % 6;
+    const double s = 0.5 * (Mm[i][j] + Mm[j][i]);
+    cov[36 * (size_t)q + lane] = s;
+    Am[i][j] = s;
+  }
+  __syncthreads();
+  // the 6 x 6 steps are relpose_math.h's (tests/cpp/relpose_math_test.cpp drives their failure branches on the host)
+  if (lane == 0 && !rpm_factor_invert(Am, Li)) bad = 1;  // Am <- L, Li <- L^-1
+  __syncthreads();
+  if (!bad && lane < 36) Mm[lane / 6][lane % 6] = rpm_info_entry(Li, lane / 6, lane % 6);  // Omega
+  __syncthreads();
+  if (!bad && lane == 0 && !rpm_accepts(Mm, Am)) bad = 1;
+  __syncthreads();
+  if (lane < 36) info[36 * (size_t)q + lane] = bad ? __builtin_nan("") : Mm[lane / 6][lane % 6];
+  if (lane == 0) singular[q] = bad;
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 // (the host plan -- CovPlan, CovBuffers -- is ba_cov_plan.h)
 
@@ -638,25 +720,14 @@ int cov_run(CovCall& c, const vsl_ba_options* opt, BaState& st, std::vector<char
     if ((rc = ba_columns(ctx, st, st.sb))) return rc;
     if ((rc = ba_schur(ctx, st, st.sb, false, 1.0, 0, D.L, false, false))) return rc;
     VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-    hipLaunchKernelGGL(ba_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.S, c.band ? st.ldS : 0, Sdiag);
-    VSL_CHECK_LAUNCH(ctx);
-    if (c.band) {
-      // the band of S^-1 by selected inversion (S <- L in place), then the pivot test on the factor
-      if ((rc = vsl_chol_selinv_band_dev(ctx, st.S_eff(), Zs + st.ldS, n, st.ldS, st.bw, ok))) return rc;
-      if ((rc = vsl_cov_band_pivot_dev(ctx, n, st.S, st.ldS, Sdiag, ok))) return rc;
-      if ((rc = vsl_cov_band_blocks_dev(ctx, P.nQ, (const int*)(dev + B.off_q_free), Zs, st.ldS, ok,
-                                        (double*)(dev + B.out_off + B.off_pose))))
-        return rc;
-    } else {
-      // the dense factor and the columns of S^-1
-      double* Linv = (double*)(dev + B.off_Linv);
-      if ((rc = vsl_chol_factor_dev(ctx, st.S, n, ok, Linv))) return rc;
-      hipLaunchKernelGGL(ba_cov_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, st.S, Linv, Sdiag,
-                         (const int*)(dev + B.off_col_unk), X, ok);
-      hipLaunchKernelGGL(ba_cov_pose_kernel, dim3((36 * P.nQ + 255) / 256), dim3(256), 0, ctx->stream, n, P.nQ,
-                         (const int*)(dev + B.off_q_free), X, ok, (double*)(dev + B.out_off + B.off_pose));
-      VSL_CHECK_LAUNCH(ctx);
-    }
+    // dense: the factor and the columns of S^-1; band: the band of S^-1 (no columns: a pose block lies inside it)
+    const int ld = c.band ? st.ldS : 0;
+    const VslCovInverse inv{n, ld, st.bw, st.S, c.band ? Zs : nullptr, c.band ? nullptr : (double*)(dev + B.off_Linv), Sdiag,
+                            c.band ? nullptr : (const int*)(dev + B.off_col_unk), nullptr, c.band ? 0 : nblk, X, ok};
+    if ((rc = vsl_cov_inverse_dev(ctx, inv))) return rc;
+    if ((rc = vsl_cov_diag_blocks_dev(ctx, n, P.nQ, (const int*)(dev + B.off_q_free), ld, Zs, X, ok,
+                                      (double*)(dev + B.out_off + B.off_pose))))
+      return rc;
   }
   if (P.nu > 0) {
     BlArgs a;
@@ -760,7 +831,7 @@ int cov_call(CovCall& c, const vsl_ba_options* opt, double* cov_pose, double* co
 //   band   cov_band_solve_kernel for the PGC_SOLVE pairs (the camera with the larger band position), fed by the inverted
 //          diagonal blocks the selected inversion left in its scratch
 //   ba_pair_blocks_kernel   the 12 x 12 joint blocks
-//   ba_relpose_kernel       (pgo.hip, the functor's own device code) meas, cov = J Sigma J^T, info = cov^-1
+//   ba_relpose_kernel       (above; the functor's own device code is pgo_device.h) meas, cov = J Sigma J^T, info = cov^-1
 // all on the context's stream inside one arena loan, one synchronisation at the end.
 struct RelCall {
   vsl_ctx* ctx;
@@ -823,26 +894,15 @@ int rel_run(RelCall& c, const vsl_ba_options* opt, BaState& st, std::vector<char
   if ((rc = ba_schur(ctx, st, st.sb, false, 1.0, 0, st.D.L, false, false))) return rc;
   {
     VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-    hipLaunchKernelGGL(ba_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, st.S, c.band ? st.ldS : 0, Sdiag);
+    const VslCovInverse inv{n, c.band ? st.ldS : 0, st.bw, st.S, c.band ? Zs : nullptr, c.band ? nullptr : (double*)(dev + P.off_Linv),
+                            Sdiag, col_unk, (const int*)(dev + P.off_row_lo), G.nblk, X, ok};
+    if ((rc = vsl_cov_inverse_dev(ctx, inv))) return rc;
+    if ((rc = vsl_cov_pair_blocks_dev(ctx, n, np, pairs, c.band ? 1 : 0, Zs, st.ldS, X, ok, joint))) return rc;
+    // meas, cov = J Sigma J^T and info = cov^-1 of every pair, with the pose graph's functor (pgo_device.h)
+    hipLaunchKernelGGL(ba_relpose_kernel, dim3(np), dim3(64), 0, ctx->stream, np, st.poses, pairs, joint, ok,
+                       (double*)(dev + P.out_off + P.off_meas), (double*)(dev + P.out_off + P.off_cov),
+                       (double*)(dev + P.out_off + P.off_info), (int*)(dev + P.out_off + P.off_sing));
     VSL_CHECK_LAUNCH(ctx);
-    if (c.band) {
-      if ((rc = vsl_chol_selinv_band_dev(ctx, st.S_eff(), Zs + st.ldS, n, st.ldS, st.bw, ok))) return rc;
-      if ((rc = vsl_cov_band_pivot_dev(ctx, n, st.S, st.ldS, Sdiag, ok))) return rc;
-      if ((rc = vsl_cov_band_unit_columns_dev(ctx, n, st.S, st.ldS, st.bw, vsl_chol_selinv_linv_dev(ctx, n, st.bw), col_unk,
-                                              (const int*)(dev + P.off_row_lo), G.nblk, X, ok)))
-        return rc;
-    } else {
-      double* Linv = (double*)(dev + P.off_Linv);
-      if ((rc = vsl_chol_factor_dev(ctx, st.S, n, ok, Linv))) return rc;
-      if ((rc = vsl_cov_unit_columns_dev(ctx, n, st.S, Linv, Sdiag, col_unk, G.nblk, X, ok))) return rc;
-    }
-    hipLaunchKernelGGL(ba_pair_blocks_kernel, dim3((144 * np + 255) / 256), dim3(256), 0, ctx->stream, n, np, pairs, c.band ? 1 : 0, Zs,
-                       st.ldS, X, ok, joint);
-    VSL_CHECK_LAUNCH(ctx);
-    if ((rc = vsl_pgo_relpose_dev(ctx, np, st.poses, pairs, joint, ok, (double*)(dev + P.out_off + P.off_meas),
-                                  (double*)(dev + P.out_off + P.off_cov), (double*)(dev + P.out_off + P.off_info),
-                                  (int*)(dev + P.out_off + P.off_sing))))
-      return rc;
   }
   host_out.assign(P.out_bytes + sizeof(int), 0);
   VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -920,7 +980,6 @@ int rel_call(RelCall& c, const vsl_ba_options* opt, double* joint, double* meas,
 
 int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double* Linv, const double* Sdiag, const int* col_unk,
                              int nblk, double* X, int* ok_dev) {
-  static_assert(COV_COLS == 16, "vsl_cov_x_at (vsl_common.h) spells the block width out");
   if (nblk <= 0) return VSL_OK;
   hipLaunchKernelGGL(ba_cov_solve_kernel, dim3(nblk), dim3(COV_THREADS), 0, ctx->stream, n, L, Linv, Sdiag, col_unk, X, ok_dev);
   VSL_CHECK_LAUNCH(ctx);
@@ -954,9 +1013,44 @@ int vsl_cov_band_pivot_dev(vsl_ctx* ctx, int n, const double* L, int ld, const d
   return VSL_OK;
 }
 
-int vsl_cov_band_blocks_dev(vsl_ctx* ctx, int nQ, const int* q_free, const double* Z, int ld, const int* ok_dev, double* out) {
+int vsl_cov_diag_dev(vsl_ctx* ctx, int n, const double* S, int ld, double* diag) {
+  if (n <= 0) return VSL_OK;
+  hipLaunchKernelGGL(ba_cov_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, S, ld, diag);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_cov_inverse_dev(vsl_ctx* ctx, const VslCovInverse& a) {
+  int rc;
+  if ((rc = vsl_cov_diag_dev(ctx, a.n, a.S, a.ld, a.diag))) return rc;
+  if (a.ld == 0) {
+    if ((rc = vsl_chol_factor_dev(ctx, a.S, a.n, a.ok, a.Linv))) return rc;
+    return vsl_cov_unit_columns_dev(ctx, a.n, a.S, a.Linv, a.diag, a.col_unk, a.nblk, a.X, a.ok);
+  }
+  // the band of S^-1 by selected inversion (S <- L in place), then the pivot test on the factor
+  if ((rc = vsl_chol_selinv_band_dev(ctx, a.S + a.ld, a.Z + a.ld, a.n, a.ld, a.bw, a.ok))) return rc;
+  if ((rc = vsl_cov_band_pivot_dev(ctx, a.n, a.S, a.ld, a.diag, a.ok))) return rc;
+  if (a.nblk <= 0) return VSL_OK;
+  return vsl_cov_band_unit_columns_dev(ctx, a.n, a.S, a.ld, a.bw, vsl_chol_selinv_linv_dev(ctx, a.n, a.bw), a.col_unk, a.row_lo,
+                                       a.nblk, a.X, a.ok);
+}
+
+int vsl_cov_diag_blocks_dev(vsl_ctx* ctx, int n, int nQ, const int* q_free, int ld, const double* Z, const double* X,
+                            const int* ok_dev, double* out) {
   if (nQ <= 0) return VSL_OK;
-  hipLaunchKernelGGL(cov_band_pose_kernel, dim3((36 * nQ + 255) / 256), dim3(256), 0, ctx->stream, nQ, q_free, Z, ld, ok_dev, out);
+  if (ld > 0)
+    hipLaunchKernelGGL(cov_band_pose_kernel, dim3((36 * nQ + 255) / 256), dim3(256), 0, ctx->stream, nQ, q_free, Z, ld, ok_dev, out);
+  else
+    hipLaunchKernelGGL(ba_cov_pose_kernel, dim3((36 * nQ + 255) / 256), dim3(256), 0, ctx->stream, n, nQ, q_free, X, ok_dev, out);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_cov_pair_blocks_dev(vsl_ctx* ctx, int n, int n_pairs, const PgcPairDev* pairs, int band, const double* Z, int ld,
+                            const double* X, const int* ok_dev, double* out) {
+  if (n_pairs <= 0) return VSL_OK;
+  hipLaunchKernelGGL(ba_pair_blocks_kernel, dim3((144 * n_pairs + 255) / 256), dim3(256), 0, ctx->stream, n, n_pairs, pairs, band, Z,
+                     ld, X, ok_dev, out);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }

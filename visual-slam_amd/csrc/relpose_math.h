@@ -1,4 +1,4 @@
-// relpose_math.h -- the 6 x 6 arithmetic of ba_relpose_kernel (pgo.hip): Sigma_r -> Omega = Sigma_r^-1 with the pivot
+// relpose_math.h -- the 6 x 6 arithmetic of ba_relpose_kernel (ba_cov.hip): Sigma_r -> Omega = Sigma_r^-1 with the pivot
 // rules that decide "singular".  Plain C++ that compiles for the host and the device alike, so that the branches no
 // bundle-adjustment input reaches (a failing pivot, a non-finite entry, an Omega the _w entry points would refuse) are
 // driven by tests/cpp/relpose_math_test.cpp under g++ on hand-built matrices.  The kernel calls the three steps on

@@ -243,11 +243,10 @@ const double* vsl_chol_selinv_linv_dev(vsl_ctx* ctx, int n, int bw);
 // before the factorisation -- a pivot L_ii^2 <= 2^-36 Sdiag_i clears *ok_dev and nothing is written.
 int vsl_cov_unit_columns_dev(vsl_ctx* ctx, int n, const double* L, const double* Linv, const double* Sdiag, const int* col_unk,
                              int nblk, double* X, int* ok_dev);
-// The band routes of the covariance calls (ba_cov.hip; vsl_pgo_covariance and vsl_global_ba_covariance).  L, Z: the
-// STORAGE base of a band array (rows of ld + 1 slots, the diagonal last).
+// The band routes of the covariance calls (ba_cov.hip).  L, Z: the STORAGE base of a band array (rows of ld + 1 slots,
+// the diagonal last).
 // pivot: the factor left by vsl_chol_selinv_band_dev against diag S before the factorisation -- a pivot L_ii^2 <=
-// 2^-36 Sdiag_i clears *ok_dev.  blocks: out[36 q ..] = the diagonal 6 x 6 block of camera / node q_free[q] (device),
-// lower triangle mirrored; nothing written when *ok_dev = 0.
+// 2^-36 Sdiag_i clears *ok_dev.
 // unit columns: L L^T X = E against the band factor for the unit columns col_unk[0 .. 16 nblk) (device; -1: an empty
 // column), sixteen per workgroup, X as for vsl_cov_unit_columns_dev -- entries of the inverse outside the band.  Linv:
 // vsl_chol_selinv_linv_dev.  row_lo (device, nullable = 0): per block the lowest row a caller reads; the rows above its
@@ -265,14 +264,37 @@ int vsl_band_rhs_solve_dev(vsl_ctx* ctx, int n, const double* L, int ld, int bw,
 // VSL_CHOL_NB; S <- L in place, Linv <- the inverted diagonal blocks (VSL_CHOL_NB^2 doubles per panel, identity-padded;
 // device memory of the caller), *ok_dev = 1 / 0.
 int vsl_chol_factor_band_dev(vsl_ctx* ctx, double* S, int n, int ld, int bw, int* ok_dev, double* Linv);
-int vsl_cov_band_blocks_dev(vsl_ctx* ctx, int nQ, const int* q_free, const double* Z, int ld, const int* ok_dev, double* out);
-// pgo.hip, for vsl_ba_relative_pose_covariance (ba_cov.hip): per pair q of pairs (device; na / nb = row of poses, fa / fb
-// < 0 = fixed) and its 12 x 12 joint covariance joint[144 q ..], with the pose-graph functor's own device code:
-// meas[6 q ..] = log(T_a^-1 T_b), cov[36 q ..] = J Sigma J^T of the functor's residual, info[36 q ..] = its inverse (36
-// NaN and singular[q] = 1 where the 6 x 6 Cholesky fails the 2^-36 pivot rule).  Nothing is written when *ok_dev = 0.
+// THE COVARIANCE CHAIN (ba_cov.hip "THE SHARED LAYER"), one statement for the reduced camera system of a bundle
+// adjustment and the H of a pose graph.  Everything is enqueued on the context's stream; the caller keeps its own
+// VslStage scope and its own ok word (preset to 1 where the factorisation does not set it).
+// diag: diag[i] = S_ii of the storage as built -- ld = 0: dense n x n, else band rows of ld + 1 slots, the diagonal last.
+int vsl_cov_diag_dev(vsl_ctx* ctx, int n, const double* S, int ld, double* diag);
+// inverse: diag S, then by the route ld names
+//   dense (ld = 0)  vsl_chol_factor_dev (S <- L, Linv <- the inverted diagonal blocks), vsl_cov_unit_columns_dev into X
+//   band  (ld > 0)  vsl_chol_selinv_band_dev (S <- L, Z <- the band of S^-1), vsl_cov_band_pivot_dev, and -- nblk > 0
+//                   only -- vsl_cov_band_unit_columns_dev into X with the inverted blocks the inversion left
+struct VslCovInverse {
+  int n = 0, ld = 0, bw = 0;
+  double* S = nullptr;             // the storage base of the matrix
+  double* Z = nullptr;             // band: the storage base of the band of the inverse (same layout as S); dense: null
+  double* Linv = nullptr;          // dense: VSL_CHOL_NB^2 doubles per panel of the caller's; band: not used
+  double* diag = nullptr;          // n doubles
+  const int* col_unk = nullptr;    // [16 nblk] unit columns (device)
+  const int* row_lo = nullptr;     // band: [nblk], see above
+  int nblk = 0;
+  double* X = nullptr;
+  int* ok = nullptr;
+};
+int vsl_cov_inverse_dev(vsl_ctx* ctx, const VslCovInverse& a);
+// diagonal blocks: out[36 q ..] = the 6 x 6 block of camera / node q_free[q] (device) of the inverse.  Dense: from X,
+// whose right-hand sides 6 q .. 6 q + 5 belong to q_free[q], the two mirror entries averaged; band (ld > 0): from Z, the
+// lower triangle mirrored.  Exactly symmetric either way; nothing written when *ok_dev = 0.
+int vsl_cov_diag_blocks_dev(vsl_ctx* ctx, int n, int nQ, const int* q_free, int ld, const double* Z, const double* X,
+                            const int* ok_dev, double* out);
+// pair blocks: out[144 q ..] = the 12 x 12 joint block of pair q (device; pgo_cov_plan.h) -- see ba_pair_blocks_kernel
 struct PgcPairDev;
-int vsl_pgo_relpose_dev(vsl_ctx* ctx, int n_pairs, const double* poses, const PgcPairDev* pairs, const double* joint,
-                        const int* ok_dev, double* meas, double* cov, double* info, int* singular);
+int vsl_cov_pair_blocks_dev(vsl_ctx* ctx, int n, int n_pairs, const PgcPairDev* pairs, int band, const double* Z, int ld,
+                            const double* X, const int* ok_dev, double* out);
 __host__ __device__ inline size_t vsl_cov_x_at(int n, int i, int col) {
   return (size_t)(col / 16) * n * 16 + (size_t)i * 16 + (col % 16);
 }
