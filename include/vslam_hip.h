@@ -447,6 +447,27 @@ int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_opti
 int vsl_ba_residuals_jacobians(vsl_ctx* ctx, const vsl_ba_problem* prob, double* r, double* J_pose,
                                double* J_point);
 
+/* Parity hook for the fused local-window iteration (ba_fused.hip): runs what vsl_bundle_adjust's fused path runs, with
+ * the Levenberg-Marquardt decision on the host, up to and including the first Cholesky solve -- the plan, the upload,
+ * the Jacobi-scaling pass, then the Schur, finish and Cholesky kernels of ONE iteration at 1 / radius = inv_radius
+ * (vsl_bundle_adjust starts at 1e-4; 0 = no damping) -- through the solver's own host code, and copies out what the
+ * kernels left.  Nothing is optimised: prob->poses / points are only read, opt->max_num_iterations is ignored.
+ * With n = 6 * n_free, cameras numbered as for vsl_ba_linearize, H = J^T J with the Huber corrector, D = 1 / (1 +
+ * sqrt(diag H)) over cameras AND landmarks, and the scaled, damped H' = D H D + inv_radius * clamp(diag(D H D), 1e-6, 1e32):
+ *   S        [n * n] row-major, UNPADDED, FULL: both triangles are written by the device (16 x 16 tiles below the
+ *            diagonal are copies of their mirror images, the diagonal tiles are computed whole) -- the reduced camera
+ *            system of H', i.e. in the SCALED variables, damping included
+ *   rhs      [n] the reduced gradient in the same variables (at inv_radius = 0: D_c g of vsl_ba_linearize, S = D_c S D_c)
+ *   scale_c  [n] D of the camera unknowns
+ *   dc       [n] -(S^-1 rhs), the scaled camera step (undefined when *chol_ok == 0)
+ *   cost     1/2 sum rho(|r|^2) at the poses / points handed in
+ *   chol_ok  0 when a pivot of the factorisation was not positive and finite
+ * Every output pointer may be NULL.  *handled = 0 (then *n_free = 0 and nothing else is written): the problem does not
+ * fit the fused kernels -- more than 21 free cameras or none, more than 64 cameras, a landmark with more than 64
+ * observations or seen twice by one free camera -- as for the solve, which then takes the general path. */
+int vsl_ba_fused_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, double inv_radius, double* S,
+                        double* rhs, double* scale_c, double* dc, double* cost, int* chol_ok, int* n_free, int* handled);
+
 /* Marginal covariances of poses and landmarks at the poses / points handed in -- what ceres::Covariance offers beside
  * the ceres::Solve of include/visnav/map_utils.h:405-411.  Nothing is optimised (opt->max_num_iterations is ignored,
  * prob->poses / points are only read).  The problem is linearised exactly as vsl_ba_linearize documents it (Huber

@@ -610,6 +610,22 @@ class Context:
                                          C.byref(nf)))
         return S, g, cost.value
 
+    def ba_fused_system(self, arr, inv_radius=0.0, use_huber=True, huber=1.0):
+        """The scaled, damped reduced system of the fused iteration's first step (vsl_ba_fused_system): a dict with S
+        [n, n] (full, as the device wrote it), rhs, scale_c, dc [n], cost, chol_ok, n_free -- or None when the fused
+        kernels do not take the problem."""
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * int((arr.cam_fixed == 0).sum())
+        S, rhs, scale_c, dc = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n)
+        cost, ok, nf, handled = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.L.vsl_ba_fused_system(self.h, C.byref(st), C.byref(o), C.c_double(inv_radius), S.ctypes.data_as(f64p),
+                                            rhs.ctypes.data_as(f64p), scale_c.ctypes.data_as(f64p), dc.ctypes.data_as(f64p),
+                                            C.byref(cost), C.byref(ok), C.byref(nf), C.byref(handled)))
+        if not handled.value:
+            return None
+        return dict(S=S, rhs=rhs, scale_c=scale_c, dc=dc, cost=cost.value, chol_ok=ok.value, n_free=nf.value)
+
     def ba_schur_apply(self, arr, x, use_huber=True, huber=1.0):
         """y = S x with the reduced camera system S of ba_linearize, never formed (vsl_ba_schur_apply)."""
         st = self._ba_struct(arr)

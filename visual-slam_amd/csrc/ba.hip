@@ -293,6 +293,9 @@ __global__ __launch_bounds__(SCH_THREADS) void ba_schur_small_kernel(
   __shared__ int kcnt[SCH_LB];
   __shared__ int obs_of[SCH_LB][SCH_KMAX];  // observation index of the k-th free-camera observation
   __shared__ int ok_s[SCH_LB];
+  __shared__ int cam_of[SCH_LB][SCH_KMAX];  // free camera of the k-th free-camera observation
+  __shared__ int dup_to[SCH_LB][SCH_KMAX];  // the slot its block is summed into: the first slot of the same camera
+  __shared__ int dupf[SCH_LB];              // the landmark has a camera with more than one observation
   const int n = D.n, tid = threadIdx.x;
   const int wl0 = l_first + blockIdx.x * lm_per_wg;
   const int wl1 = min(l_first + l_count, wl0 + lm_per_wg);
@@ -327,8 +330,8 @@ __global__ __launch_bounds__(SCH_THREADS) void ba_schur_small_kernel(
   for (int s0 = wl0; s0 < wl1; s0 += SCH_LB) {
     const int nl = min(SCH_LB, wl1 - s0);
     // phase A: per landmark P, b, P^-1 and the slot table -- one WAVE per staged landmark: lanes take
-    // the observations (a landmark of the small-system path has at most 64), xor-shuffle tree sums
-    // (fixed order), the free-camera rank of an observation from a ballot prefix
+    // the observations, 64 at a time (fixed cameras are not limited, so a landmark can have more), xor-shuffle
+    // tree sums (fixed order), the free-camera rank of an observation from ballot prefixes
     {
       const int wv = tid >> 6, ln = tid & 63;
       if (wv < nl) {
@@ -350,8 +353,8 @@ __global__ __launch_bounds__(SCH_THREADS) void ba_schur_small_kernel(
           for (int x = 0; x < 3; x++) bb[x] = e[x] * r0 + e[3 + x] * r1;
           fc = cam_free[obs_cam[i]];
         }
-        // landmarks with more than 64 observations cannot occur here (one observation per camera,
-        // at most SCH_CMAX free + the fixed cameras); extra observations are folded in serially anyway
+        // observations beyond the first 64 (many fixed cameras, or cameras that see the landmark more than once)
+        // are folded in serially
         for (int j = o0 + 64 + ln; j < o1; j += 64) {
           const double* e = E + 6 * (size_t)j;
           const double r0 = r[2 * (size_t)j], r1 = r[2 * (size_t)j + 1];
@@ -379,18 +382,46 @@ __global__ __launch_bounds__(SCH_THREADS) void ba_schur_small_kernel(
         if (ln < SCH_CMAX) slot[wv][ln] = -1;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        const unsigned long long fm = __ballot(have && fc >= 0);
-        const int rank = __popcll(fm & ((1ull << ln) - 1ull));
-        if (have && fc >= 0 && rank < SCH_KMAX) {
-          slot[wv][fc] = rank;
-          obs_of[wv][rank] = i;
+        // 64 observations at a time: a window with many FIXED cameras has landmarks with more than 64 observations, and
+        // a free camera among the later ones used to lose its W block (its E^T E was in P all the same)
+        int seen_free = 0;
+        for (int base = o0; base < o1; base += 64) {  // wave-uniform
+          const int j = base + ln;
+          const bool hv = j < o1;
+          const int fcj = base == o0 ? fc : (hv ? cam_free[obs_cam[j]] : -1);
+          const unsigned long long fm = __ballot(hv && fcj >= 0);
+          const int rank = seen_free + __popcll(fm & ((1ull << ln) - 1ull));
+          if (hv && fcj >= 0 && rank < SCH_KMAX) {
+            cam_of[wv][rank] = fcj;
+            obs_of[wv][rank] = j;
+          }
+          seen_free += __popcll(fm);
         }
-        const int k = min(__popcll(fm), SCH_KMAX);
+        // (seen_free <= SCH_KMAX, repeats included: ba_host_plan counts the free-camera observations of every
+        // landmark and sends a problem with more to the large-system kernels -- the min is a logic guard)
+        const int k = min(seen_free, SCH_KMAX);
+        // camera -> slot.  A free camera that observes the landmark more than once owns the slot of its FIRST
+        // observation; the W / Y blocks of the later ones are added to that slot after phase B (two lanes used to write
+        // one slot entry here, and whichever lost the race lost its block)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        bool later = false;
+        if (ln < k) {
+          const int c = cam_of[wv][ln];
+          int first = ln;
+          for (int q = ln - 1; q >= 0; q--)
+            if (cam_of[wv][q] == c) first = q;
+          dup_to[wv][ln] = first;
+          later = first != ln;
+          if (!later) slot[wv][c] = ln;
+        }
+        const bool any_later = __ballot(later) != 0ull;
         double Pi[9];
         const bool ok = o1 > o0 && inv3(P, Pi);
         if (ln == 0) {
           ok_s[wv] = ok;
           kcnt[wv] = ok ? k : 0;
+          dupf[wv] = ok && any_later;
           for (int q = 0; q < 9; q++) Pi_s[wv][q] = ok ? Pi[q] : 0.0;
           for (int q = 0; q < 3; q++) b_s[wv][q] = ok ? bb[q] : 0.0;
           if (Pinv_out)
@@ -418,6 +449,24 @@ __global__ __launch_bounds__(SCH_THREADS) void ba_schur_small_kernel(
       }
     }
     __syncthreads();
+    bool merge = false;  // workgroup-uniform
+    for (int li = 0; li < nl; li++) merge = merge || dupf[li] != 0;
+    if (merge) {  // a thread per entry of a FIRST slot adds the later slots of the same camera, in slot order
+      for (int item = tid; item < nl * SCH_KMAX * 18; item += SCH_THREADS) {
+        const int li = item / (SCH_KMAX * 18), rem = item - li * (SCH_KMAX * 18);
+        const int f = rem / 18, t = rem - f * 18;
+        if (!dupf[li] || f >= kcnt[li] || dup_to[li][f] != f) continue;
+        double w = W[li][f][t], y = Y[li][f][t];
+        for (int q = f + 1; q < kcnt[li]; q++)
+          if (dup_to[li][q] == f) {
+            w += W[li][q][t];
+            y += Y[li][q][t];
+          }
+        W[li][f][t] = w;
+        Y[li][f][t] = y;
+      }
+      __syncthreads();
+    }
     // phase C: owned entries
     for (int li = 0; li < nl; li++) {
       if (!ok_s[li]) continue;

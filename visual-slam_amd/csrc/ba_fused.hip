@@ -1211,30 +1211,48 @@ bool bf_plan(const vsl_ba_problem* p, const BfLayout& y, char* blk, BfPlan& pl) 
   return g > 0;
 }
 
-}  // namespace
 
-// handled = 0: the problem does not fit the fused kernels (nothing was done); otherwise the solve ran (rc tells how).
-int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, vsl_ba_summary* summary,
-                       int* handled) {
-  *handled = 0;
-  if (prob->n_cams > BF_CAMS) return VSL_OK;
-  const double t_start = now_ms();
-  const bool trace = getenv("VSL_BA_TRACE") != nullptr;  // phase times on stderr (developer aid)
-  double t_lap = t_start;
-  auto lap = [&](const char* what) {
-    if (!trace) return;
+// The phase times of a solve on stderr under VSL_BA_TRACE (developer aid).
+struct BfTrace {
+  bool on = false;
+  double t_lap = 0;
+  void lap(const char* what) {
+    if (!on) return;
     const double t = now_ms();
     fprintf(stderr, "  [fused ba] %-32s %8.3f ms\n", what, t - t_lap);
     t_lap = t;
-  };
+  }
+};
+
+// What a fused solve holds once its Jacobi-scaling pass is enqueued: the plan, the arena and the kernels' argument
+// block.  bf_begin fills it; vsl_ba_fused_solve and the parity hook vsl_ba_fused_system both start from it.
+struct BfRun {
+  BfLayout y;
+  BfPlan pl;
+  BfArgs a;
+  DevArena arena;
+  bool device_lm = false;
+  int n = 0, G = 0, T = 0;
+  double* mailbox = nullptr;  // pinned: see bf_begin
+  char* dblk = nullptr;
+  double *poses = nullptr, *points = nullptr, *cand_poses = nullptr, *cand_points = nullptr, *scale_c = nullptr, *scale_l = nullptr,
+         *Pinv = nullptr, *bl = nullptr, *S_part = nullptr, *hc_part = nullptr, *sc_part = nullptr, *S = nullptr, *rhs = nullptr,
+         *dc = nullptr, *box = nullptr;
+  BfLm* lm_dev = nullptr;
+};
+
+// Plan, pinned block, arena, upload and the Jacobi-scaling pass (enqueued, not waited for).  *handled = 0: the problem
+// does not fit the fused kernels and nothing was done.
+int bf_begin(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, bool device_lm, BfRun& r, BfTrace& trace,
+             int* handled) {
+  *handled = 0;
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   const size_t C = prob->n_cams, L = prob->n_lms, O = prob->n_obs;
-  const BfLayout y = bf_layout((int)C, (int)L, (int)O);
+  r.y = bf_layout((int)C, (int)L, (int)O);
+  const BfLayout& y = r.y;
   // the pinned block: the plan first, the kernels' mailbox behind it (one allocation, device-mapped)
   //   mailbox: [0] cost, [1] max |landmark gradient|, [2] (int) Cholesky ok, [4 .. 132) |camera gradient| per unknown,
   //            [132 .. 132 + 5 G) step partials
-  static const bool env_host_lm = getenv("VSL_BA_HOST_LM") != nullptr;
-  bool device_lm = !ctx->ba_host_lm && !env_host_lm;
   // (device-decided loop: the pinned area holds one BF_REC-double record per loop body instead of the kernels' outputs)
   const size_t mail_doubles = std::max<size_t>(132 + 5 * (size_t)y.g_cap, (size_t)BF_REC * ((size_t)std::max(opt->max_num_iterations, 0) + 4));
   const size_t pin_bytes = y.bytes + 8 * mail_doubles;
@@ -1248,12 +1266,13 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
     ctx->ba_pin_cap = cap;
   }
   char* blk = (char*)ctx->ba_pin;
-  double* mailbox = (double*)(blk + y.bytes);
-  BfPlan pl;
+  double* mailbox = r.mailbox = (double*)(blk + y.bytes);
+  BfPlan& pl = r.pl;
   if (!bf_plan(prob, y, blk, pl)) return VSL_OK;
   *handled = 1;
   if (pl.G > 1024) device_lm = false;  // (baf_decide_kernel stages 5 partials of <= 1024 workgroups)
-  lap("plan");
+  r.device_lm = device_lm;
+  trace.lap("plan");
   BaDims D;
   D.C = prob->n_cams;
   D.L = prob->n_lms;
@@ -1264,49 +1283,42 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   D.model1 = prob->cam_model[1];
   D.use_huber = opt->use_huber;
   D.huber = opt->huber_parameter;
-  const int n = D.n, G = pl.G, NT = pl.NP / 16, T = NT * (NT + 1) / 2;
+  const int n = r.n = D.n, G = r.G = pl.G, NT = pl.NP / 16, T = r.T = NT * (NT + 1) / 2;
   // one arena (the context's, dev_arena.h): the uploaded block, then what the kernels produce
-  char* dblk;
-  double *cand_poses, *cand_points, *scale_c, *scale_l, *Pinv, *bl, *S_part, *hc_part, *sc_part, *S, *rhs, *dc, *box;
-  BfLm* lm_dev;
   ArenaPlan plan(15);
-  plan.add(dblk, y.bytes);
-  plan.add(cand_poses, 7 * C);
-  plan.add(cand_points, 3 * L);
-  plan.add(box, 132 + 5 * (size_t)y.g_cap);
-  plan.add(lm_dev, 1);
-  plan.add(scale_c, 128);
-  plan.add(scale_l, 3 * L);
-  plan.add(Pinv, 9 * L);
-  plan.add(bl, 3 * L);
-  plan.add(S_part, 256 * (size_t)T * G);
-  plan.add(hc_part, 27 * (size_t)pl.nfree * G);
-  plan.add(sc_part, 2 * (size_t)G);
-  plan.add(S, (size_t)n * n);
-  plan.add(rhs, 128);
-  plan.add(dc, 128);
-  DevArena arena;
-  VSL_HIP(ctx, arena.acquire(ctx, ArenaPolicy::BORROWED, plan));
-  volatile double* mail = mailbox;
-  volatile int* chol_ok = (volatile int*)(mailbox + 2);
-  volatile double* gabs = mailbox + 4;
-  volatile double* step_part = mailbox + 132;
+  plan.add(r.dblk, y.bytes);
+  plan.add(r.cand_poses, 7 * C);
+  plan.add(r.cand_points, 3 * L);
+  plan.add(r.box, 132 + 5 * (size_t)y.g_cap);
+  plan.add(r.lm_dev, 1);
+  plan.add(r.scale_c, 128);
+  plan.add(r.scale_l, 3 * L);
+  plan.add(r.Pinv, 9 * L);
+  plan.add(r.bl, 3 * L);
+  plan.add(r.S_part, 256 * (size_t)T * G);
+  plan.add(r.hc_part, 27 * (size_t)pl.nfree * G);
+  plan.add(r.sc_part, 2 * (size_t)G);
+  plan.add(r.S, (size_t)n * n);
+  plan.add(r.rhs, 128);
+  plan.add(r.dc, 128);
+  VSL_HIP(ctx, r.arena.acquire(ctx, ArenaPolicy::BORROWED, plan));
+  char* dblk = r.dblk;
   // ONE copy: everything up to the used part of the workgroup records
   VSL_HIP(ctx, hipMemcpyAsync(dblk, blk, y.wg_info + 4 * (size_t)BF_INFO * G, hipMemcpyHostToDevice, ctx->stream));
-  double* poses = (double*)(dblk + y.poses);
-  double* points = (double*)(dblk + y.points);
+  r.poses = (double*)(dblk + y.poses);
+  r.points = (double*)(dblk + y.points);
 
-  BfArgs a;
+  BfArgs& a = r.a;
   a.D = D;
   a.NP = pl.NP;
   a.NPs = pl.NPs;
   a.NT = NT;
   a.T = T;
-  a.poses = poses;
-  a.points = points;
-  a.lm = device_lm ? lm_dev : nullptr;
-  a.poses_alt = cand_poses;
-  a.points_alt = cand_points;
+  a.poses = r.poses;
+  a.points = r.points;
+  a.lm = device_lm ? r.lm_dev : nullptr;
+  a.poses_alt = r.cand_poses;
+  a.points_alt = r.cand_points;
   a.intr = (const double*)(dblk + y.intr);
   a.cam_intr = (const int*)(dblk + y.cam_intr);
   a.cam_free = (const int*)(dblk + y.cam_free);
@@ -1315,21 +1327,13 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   a.lm_start = (const int*)(dblk + y.lm_start);
   a.lm_pres = (const unsigned*)(dblk + y.lm_pres);
   a.wg_info = (const int*)(dblk + y.wg_info);
-  a.scale_c = scale_c;
-  a.scale_l = scale_l;
-  a.Pinv = Pinv;
-  a.bl = bl;
-  a.S_part = S_part;
-  a.hc_part = hc_part;
-  a.sc_part = sc_part;
-
-  vsl_ba_summary sum;
-  memset(&sum, 0, sizeof(sum));
-  const bool prof_was = ctx->profiling;
-  // summary: linearize_ms = scaling pass + step kernels, schur_ms = Schur + finish kernels, solve_ms = the Cholesky
-  const int st_of[5] = {VSL_STAGE_BA_LIN, VSL_STAGE_BA_SCHUR, VSL_STAGE_BA_SOLVE, VSL_STAGE_BA_FINISH, VSL_STAGE_BA_STEP};
-  double base_ms[5];
-  for (int k = 0; k < 5; k++) base_ms[k] = ctx->stage_ms[st_of[k]];
+  a.scale_c = r.scale_c;
+  a.scale_l = r.scale_l;
+  a.Pinv = r.Pinv;
+  a.bl = r.bl;
+  a.S_part = r.S_part;
+  a.hc_part = r.hc_part;
+  a.sc_part = r.sc_part;
 
   if (device_lm)  // (sequence numbers of an earlier solve must not be mistaken for this one's)
     for (int k = 0; k < std::max(opt->max_num_iterations, 0) + 3; k++) mailbox[(size_t)BF_REC * k] = 0.0;
@@ -1337,11 +1341,83 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
   {
     VslStage s(ctx, VSL_STAGE_BA_LIN);
     hipLaunchKernelGGL((baf_schur_kernel<true, 1>), dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, 0.0);
-    hipLaunchKernelGGL(baf_init_finish_kernel, dim3((n + 15) / 16 + 1), dim3(256), 0, ctx->stream, n, pl.nfree, G, hc_part,
-                       sc_part, scale_c, device_lm ? box : mailbox);
-    if (device_lm) hipLaunchKernelGGL(baf_lm_init_kernel, dim3(1), dim3(64), 0, ctx->stream, lm_dev, box, mailbox);
+    hipLaunchKernelGGL(baf_init_finish_kernel, dim3((n + 15) / 16 + 1), dim3(256), 0, ctx->stream, n, pl.nfree, G, r.hc_part,
+                       r.sc_part, r.scale_c, device_lm ? r.box : mailbox);
+    if (device_lm) hipLaunchKernelGGL(baf_lm_init_kernel, dim3(1), dim3(64), 0, ctx->stream, r.lm_dev, r.box, mailbox);
     VSL_CHECK_LAUNCH(ctx);
   }
+  return VSL_OK;
+}
+
+// The linear system of one host-decided iteration at 1 / radius = inv_radius, enqueued: the Schur tiles, their sum with
+// the camera blocks and the damping into S and rhs, the Cholesky solve into dc.  Scalars land in the pinned mailbox.
+int bf_enqueue_system(vsl_ctx* ctx, BfRun& r, double inv_radius) {
+  const BfArgs& a = r.a;
+  const int n = r.n, G = r.G, T = r.T;
+  double* mailbox = r.mailbox;
+  {
+    VslStage s(ctx, VSL_STAGE_BA_SCHUR);
+    if (T <= BF_WAVES)
+      hipLaunchKernelGGL((baf_schur_kernel<false, 1>), dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, inv_radius);
+    else if (T <= 2 * BF_WAVES)
+      hipLaunchKernelGGL((baf_schur_kernel<false, 2>), dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, inv_radius);
+    else
+      hipLaunchKernelGGL((baf_schur_kernel<false, 3>), dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, inv_radius);
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  {
+    VslStage s(ctx, VSL_STAGE_BA_FINISH);
+    hipLaunchKernelGGL(baf_finish_kernel, dim3(16 * T + 1), dim3(256), 0, ctx->stream, n, r.pl.nfree,
+                       G, T, r.S_part, r.hc_part, r.sc_part, r.scale_c, inv_radius, r.S, r.rhs, mailbox, mailbox + 4, (const BfLm*)nullptr);
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  {
+    VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+    hipLaunchKernelGGL(baf_chol_kernel, dim3(1), dim3(BF_THREADS), 0, ctx->stream, n, r.S, r.rhs, r.dc, (int*)(mailbox + 2),
+                       (const BfLm*)nullptr);
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  return VSL_OK;
+}
+
+}  // namespace
+
+// handled = 0: the problem does not fit the fused kernels (nothing was done); otherwise the solve ran (rc tells how).
+int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, vsl_ba_summary* summary,
+                       int* handled) {
+  *handled = 0;
+  if (prob->n_cams > BF_CAMS) return VSL_OK;
+  const double t_start = now_ms();
+  BfTrace trace;
+  trace.on = getenv("VSL_BA_TRACE") != nullptr;
+  trace.t_lap = t_start;
+  auto lap = [&](const char* what) { trace.lap(what); };
+  static const bool env_host_lm = getenv("VSL_BA_HOST_LM") != nullptr;
+  const bool prof_was = ctx->profiling;
+  // summary: linearize_ms = scaling pass + step kernels, schur_ms = Schur + finish kernels, solve_ms = the Cholesky
+  const int st_of[5] = {VSL_STAGE_BA_LIN, VSL_STAGE_BA_SCHUR, VSL_STAGE_BA_SOLVE, VSL_STAGE_BA_FINISH, VSL_STAGE_BA_STEP};
+  double base_ms[5];
+  for (int k = 0; k < 5; k++) base_ms[k] = ctx->stage_ms[st_of[k]];
+  BfRun run;
+  int rc0 = bf_begin(ctx, prob, opt, !ctx->ba_host_lm && !env_host_lm, run, trace, handled);
+  if (rc0 || !*handled) return rc0;
+  const size_t C = prob->n_cams, L = prob->n_lms;
+  const bool device_lm = run.device_lm;
+  const BfPlan& pl = run.pl;
+  BfArgs& a = run.a;
+  const int n = run.n, G = run.G, T = run.T;
+  double* mailbox = run.mailbox;
+  double *poses = run.poses, *points = run.points, *cand_poses = run.cand_poses, *cand_points = run.cand_points;
+  double *S_part = run.S_part, *hc_part = run.hc_part, *sc_part = run.sc_part, *scale_c = run.scale_c, *S = run.S, *rhs = run.rhs,
+         *dc = run.dc, *box = run.box;
+  BfLm* lm_dev = run.lm_dev;
+  volatile double* mail = mailbox;
+  volatile int* chol_ok = (volatile int*)(mailbox + 2);
+  volatile double* gabs = mailbox + 4;
+  volatile double* step_part = mailbox + 132;
+
+  vsl_ba_summary sum;
+  memset(&sum, 0, sizeof(sum));
   if (device_lm) {
     // ---- the device-decided loop: iterations are enqueued ONE AHEAD of the decision the host has seen; a body that
     // runs after the termination returns at its first instruction.  No synchronisation inside the loop: the host polls
@@ -1447,28 +1523,7 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
     // the whole iteration is enqueued without waiting; the gradient norm of the CURRENT point comes back with it
     // (it is a by-product of the Schur kernel), so the gradient-tolerance test is taken before the iteration counts
     const double inv_radius = 1.0 / lm.radius;
-    {
-      VslStage s(ctx, VSL_STAGE_BA_SCHUR);
-      if (T <= BF_WAVES)
-        hipLaunchKernelGGL((baf_schur_kernel<false, 1>), dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, inv_radius);
-      else if (T <= 2 * BF_WAVES)
-        hipLaunchKernelGGL((baf_schur_kernel<false, 2>), dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, inv_radius);
-      else
-        hipLaunchKernelGGL((baf_schur_kernel<false, 3>), dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, inv_radius);
-      VSL_CHECK_LAUNCH(ctx);
-    }
-    {
-      VslStage s(ctx, VSL_STAGE_BA_FINISH);
-      hipLaunchKernelGGL(baf_finish_kernel, dim3(16 * T + 1), dim3(256), 0, ctx->stream, n, pl.nfree,
-                         G, T, S_part, hc_part, sc_part, scale_c, inv_radius, S, rhs, mailbox, mailbox + 4, (const BfLm*)nullptr);
-      VSL_CHECK_LAUNCH(ctx);
-    }
-    {
-      VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-      hipLaunchKernelGGL(baf_chol_kernel, dim3(1), dim3(BF_THREADS), 0, ctx->stream, n, S, rhs, dc, (int*)(mailbox + 2),
-                         (const BfLm*)nullptr);
-      VSL_CHECK_LAUNCH(ctx);
-    }
+    if ((term = bf_enqueue_system(ctx, run, inv_radius))) return term;
     {
       VslStage s(ctx, VSL_STAGE_BA_STEP);
       hipLaunchKernelGGL(baf_step_kernel, dim3(G), dim3(BF_THREADS), 0, ctx->stream, a, dc, cand_poses, cand_points,
@@ -1530,5 +1585,37 @@ int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_op
     fprintf(stderr, "vsl BA: iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", sum.iterations,
             sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
   if (summary) *summary = sum;
+  return VSL_OK;
+}
+
+int ba_validate(vsl_ctx* ctx, const vsl_ba_problem* p);  // ba.hip
+
+// Parity hook (include/vslam_hip.h): the solve's own prefix -- bf_begin, then the linear system of the first
+// host-decided iteration at the caller's 1 / radius -- and what those kernels left, copied out.  No step is taken.
+extern "C" int vsl_ba_fused_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, double inv_radius,
+                                   double* S, double* rhs, double* scale_c, double* dc, double* cost, int* chol_ok, int* n_free,
+                                   int* handled) {
+  int rc = ba_validate(ctx, prob), took = 0;
+  if (rc) return rc;
+  if (!opt) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_fused_system: options are null");
+  if (!(inv_radius >= 0.0) || !std::isfinite(inv_radius))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_fused_system: 1 / radius = %g is not a finite non-negative number", inv_radius);
+  if (handled) *handled = 0;
+  if (n_free) *n_free = 0;
+  if (prob->n_cams > BF_CAMS) return VSL_OK;
+  BfTrace trace;
+  BfRun run;
+  if ((rc = bf_begin(ctx, prob, opt, false, run, trace, &took)) || !took) return rc;
+  if ((rc = bf_enqueue_system(ctx, run, inv_radius))) return rc;
+  const size_t n = (size_t)run.n;
+  if (S) VSL_HIP(ctx, hipMemcpyAsync(S, run.S, 8 * n * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (rhs) VSL_HIP(ctx, hipMemcpyAsync(rhs, run.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (scale_c) VSL_HIP(ctx, hipMemcpyAsync(scale_c, run.scale_c, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (dc) VSL_HIP(ctx, hipMemcpyAsync(dc, run.dc, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (cost) *cost = ((volatile double*)run.mailbox)[0];
+  if (chol_ok) *chol_ok = *(volatile int*)(run.mailbox + 2);
+  if (n_free) *n_free = run.pl.nfree;
+  if (handled) *handled = 1;
   return VSL_OK;
 }
