@@ -483,15 +483,18 @@ struct SelShared {
   int n_chunk;
 };
 
-// Exclusive prefix count of `p` over the workgroup (thread order) and the total.  The sixteen wave totals are
-// scanned across a row of sixteen lanes (four DPP row shifts) and picked by lane index: sixteen `w < wave`
-// select masks would live in 32 SGPRs all through the greedy loop.
-__device__ __forceinline__ int block_scan(bool p, int* wave_tot, int& total) {
+// Exclusive prefix counts of `p` (low 16 bits) and of `q` (high 16 bits) over the workgroup (thread order) and the
+// two totals, packed the same way: a count is at most SEL_THREADS, so the halves never carry into each other and
+// one scan serves both.  The sixteen wave totals are scanned across a row of sixteen lanes (four DPP row shifts)
+// and picked by lane index: sixteen `w < wave` select masks would live in 32 SGPRs all through the greedy loop.
+// One workgroup barrier, between the write of wave_tot and its reads; the CALLER keeps a barrier between the
+// reads of one call and the write of the next (the greedy has two per batch).
+__device__ __forceinline__ int block_scan(bool p, bool q, int* wave_tot, int& total) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned long long m = __ballot(p);
-  const int within = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  const int mine = __popcll(m);
-  __syncthreads();
+  const unsigned long long m = __ballot(p), mq = __ballot(q);
+  const int within = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) |
+                     (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u)) << 16;
+  const int mine = __popcll(m) | __popcll(mq) << 16;
   if (lane == 0) wave_tot[wave] = mine;
   __syncthreads();
   int x = wave_tot[lane & 15];
@@ -516,19 +519,37 @@ __device__ __forceinline__ int block_scan(bool p, int* wave_tot, int& total) {
 #define SEL_PHYS(i) ((i) + ((i) >> 5))
 // keys | SelShared | three SEL_THREADS-word arrays (bin counters of the sort, then batch nodes + states) | packed
 // grid (2 B accepted slots + 2 B list head per cell) | pad.  The last of the three arrays, the grid and the pad
-// together are the SEL_CHUNK-word staging array of the in-bin ranking (the grid is initialised after it).
+// together are the SEL_CHUNK-word staging array of the in-bin ranking when the candidate list is too long for the
+// registers (the grid is initialised after it); the usual ranking from registers needs no staging array.
 #define SEL_GRID_BYTES (SEL_MAX_CELLS * 2 * 2)
 #define SEL_STAGE_PAD (SEL_CHUNK * 4 - SEL_THREADS * 4 - SEL_GRID_BYTES)
 #define SEL_LDS_BYTES (SEL_KEYS_PADDED * 8 + 2048 + SEL_THREADS * 4 * 3 + SEL_GRID_BYTES + SEL_STAGE_PAD)
 static_assert(SEL_STAGE_PAD >= 0, "ranking staging array");
+// A candidate list of at most SEL_CHUNK keys is read from memory once and stays in registers through the counting
+// sort, SEL_KPT keys per thread.  Up to SEL_CHUNK / 2 keys, the ranked positions (4 B) go straight to the part of the
+// key array behind the last padded 8-byte key slot in use, 32-bit word SEL_POS_UPPER onwards.
+#define SEL_KPT (SEL_CHUNK / SEL_THREADS)
+#define SEL_POS_UPPER (2 * SEL_PHYS(SEL_CHUNK / 2))
+static_assert(SEL_POS_UPPER + SEL_CHUNK / 2 <= 2 * SEL_KEYS_PADDED, "ranked positions behind the keys");
 static_assert(SEL_LDS_BYTES <= 160 * 1024 - 39344, "selection kernel LDS budget: one describe_tile_kernel workgroup fits beside it");
 
 // Exchange of the 16-bit half `idx & 1` of the 32-bit word that holds element idx of a u16 array (LDS has no
 // 16-bit exchange): returns the old half.
-__device__ __forceinline__ uint32_t sel_xchg16(volatile uint16_t* arr, int idx, uint32_t v) {
+// The per-cell arrays are volatile in global memory only (SelGrid below): a volatile access through a pointer that
+// may be global or LDS compiles to a FLAT instruction with a full wait behind it, one serial round trip each, where
+// the LDS grid wants plain ds_read / ds_write that are in flight together.  Workgroup barriers order the phases.
+template <bool GRID_GLOBAL> struct SelGrid {
+  typedef typename std::conditional<GRID_GLOBAL, volatile uint16_t, uint16_t>::type u16;
+  typedef typename std::conditional<GRID_GLOBAL, volatile uint32_t, uint32_t>::type u32;
+};
+
+template <class T16>
+__device__ __forceinline__ uint32_t sel_xchg16(T16* arr, int idx, uint32_t v) {
   uint32_t* word = (uint32_t*)arr + (idx >> 1);
   const int s = (idx & 1) * 16;
-  uint32_t old = *(volatile uint32_t*)word;
+  uint32_t old;  // (a stale start value costs one more round)
+  if constexpr (std::is_volatile<T16>::value) old = *(volatile uint32_t*)word;
+  else old = *word;
   for (;;) {
     const uint32_t got = atomicCAS(word, old, (old & ~(0xFFFFu << s)) | (v << s));
     if (got == old) break;
@@ -542,10 +563,13 @@ __device__ __forceinline__ int sel_head_rank(uint32_t h) { return h == SEL_HEAD_
 
 // Put slot byte b into the first empty slot of cell idx (nothing if both are taken: a third corner at distance
 // >= 8 from two others does not fit into an 8 x 8 cell).
-__device__ __forceinline__ void sel_acc_insert(volatile uint16_t* arr, int idx, uint32_t b) {
+template <class T16>
+__device__ __forceinline__ void sel_acc_insert(T16* arr, int idx, uint32_t b) {
   uint32_t* word = (uint32_t*)arr + (idx >> 1);
   const int s = (idx & 1) * 16;
-  uint32_t old = *(volatile uint32_t*)word;
+  uint32_t old;  // (slots only fill up: a stale value fails the exchange)
+  if constexpr (std::is_volatile<T16>::value) old = *(volatile uint32_t*)word;
+  else old = *word;
   for (;;) {
     const uint32_t cur = (old >> s) & 0xFFFFu;
     if ((cur & 0xFF00u) != 0u) break;
@@ -621,10 +645,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
   uint32_t* keys32 = (uint32_t*)smem;
   SelShared* sh = (SelShared*)(smem + SEL_KEYS_PADDED * 8);
   int* next = (int*)(smem + SEL_KEYS_PADDED * 8 + 2048);  // SEL_THREADS
-  // cells u16 with the two accepted slots of a cell, then cells u16 batch list heads (SEL_HEAD_EMPTY = none); volatile:
-  // the global variant must not keep them in registers / stale L1 lines between workgroup barriers
-  volatile uint16_t* acc = GRID_GLOBAL ? (volatile uint16_t*)(grid_scratch + (size_t)slot * cells) : (volatile uint16_t*)(next + 3 * SEL_THREADS);
-  volatile uint16_t* head = acc + cells;
+  // cells u16 with the two accepted slots of a cell, then cells u16 batch list heads (SEL_HEAD_EMPTY = none); volatile
+  // in the global variant, which must not keep them in registers / stale L1 lines between workgroup barriers
+  typedef typename SelGrid<GRID_GLOBAL>::u16 grid_u16;
+  typedef typename SelGrid<GRID_GLOBAL>::u32 grid_u32;
+  grid_u16* acc = GRID_GLOBAL ? (grid_u16*)(grid_scratch + (size_t)slot * cells) : (grid_u16*)(next + 3 * SEL_THREADS);
+  grid_u16* head = acc + cells;
   // batch member u: node[u] = (position x | y << 16, next member of its cell's list) -- one 8-byte read per list step
   unsigned long long* node = (unsigned long long*)next;  // SEL_THREADS (the space of `next` and the array after it)
   int* state = next + 2 * SEL_THREADS;              // SEL_THREADS: 0 undecided, 1 accepted, 2 rejected
@@ -657,16 +683,32 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
   while (bshift < 31 && (hi_max >> bshift) - (hi_floor >> bshift) >= (uint32_t)SEL_BINS) bshift++;
   const uint32_t bin_top = hi_max >> bshift;
   bool bucket_sort = false;
+  // a list of at most SEL_CHUNK keys is held in registers from the histogram to the ranking: rk[k] = cand[tid + k * SEL_THREADS]
+  // (compile-time indices only); a longer list takes the bucket path through memory twice, as before
+  const bool in_regs = n_cand <= SEL_CHUNK;
+  unsigned long long rk[SEL_KPT] = {};
   if (maxv > 0.f) {
     bcount[tid] = 0;
     if (tid == 0) sh->n_chunk = 0;
     __syncthreads();
-    for (int i = tid; i < n_cand; i += SEL_THREADS) {
-      const unsigned long long key = cand[i];
-      if (key > floor_key) {
-        // a provisional candidate above the image maximum cannot exist; the clamp keeps a corrupted list in range
-        const uint32_t kb = min((uint32_t)(key >> 32) >> bshift, bin_top);
-        atomicAdd(&bcount[bin_top - kb], 1);
+    if (in_regs) {
+      // the only read of the list: SEL_KPT independent loads per thread, issued together (0 = no key: below every floor)
+#pragma unroll
+      for (int k = 0; k < SEL_KPT; k++) {
+        const int i = tid + k * SEL_THREADS;
+        rk[k] = i < n_cand ? cand[i] : 0ull;
+      }
+#pragma unroll
+      for (int k = 0; k < SEL_KPT; k++)
+        if (rk[k] > floor_key) atomicAdd(&bcount[bin_top - min((uint32_t)(rk[k] >> 32) >> bshift, bin_top)], 1);
+    } else {
+      for (int i = tid; i < n_cand; i += SEL_THREADS) {
+        const unsigned long long key = cand[i];
+        if (key > floor_key) {
+          // a provisional candidate above the image maximum cannot exist; the clamp keeps a corrupted list in range
+          const uint32_t kb = min((uint32_t)(key >> 32) >> bshift, bin_top);
+          atomicAdd(&bcount[bin_top - kb], 1);
+        }
       }
     }
     __syncthreads();
@@ -698,12 +740,86 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
     bucket_sort = remaining <= SEL_CHUNK && fullest <= bucket_cap;
     __syncthreads();
   }
-  // the grid starts empty (two cells per word); the counting sort does this itself after its staging array is dead
-  if (!bucket_sort) {
-    for (int i = tid; i < cells; i += SEL_THREADS) ((volatile uint32_t*)acc)[i] = i < (cells >> 1) ? 0u : ~0u;
-    __syncthreads();
+  // the grid starts empty (two cells per word).  The counting sort from registers has no staging array over the grid,
+  // so the grid is written here as well and the sort's own barriers stand between these writes and the greedy's
+  // reads; the counting sort through memory does this itself after its staging array is dead.
+  if (!bucket_sort || in_regs)
+    for (int i = tid; i < cells; i += SEL_THREADS) ((grid_u32*)acc)[i] = i < (cells >> 1) ? 0u : ~0u;
+  if (!bucket_sort) __syncthreads();
+  bool compact = false;  // the sorted chunk is keys32[pos_off + r], not keys[SEL_PHYS(r)]
+  int pos_off = 0;
+  if (bucket_sort && remaining > 0) {
+    if (in_regs) {
+      // ---- scatter into the bins' slot ranges, then rank inside each bin (the keys come from the registers)
+#pragma unroll
+      for (int k = 0; k < SEL_KPT; k++)
+        if (rk[k] > floor_key) {
+          const int bin = (int)(bin_top - min((uint32_t)(rk[k] >> 32) >> bshift, bin_top));
+          const int p = bstart[bin] + atomicAdd(&bcursor[bin], 1);  // (SEL_PHYS evaluates its argument twice)
+          keys[SEL_PHYS(p)] = rk[k];
+        }
+      __syncthreads();
+      // Only the pixel position of a key is read once it is ranked.  Up to SEL_CHUNK / 2 keys it goes straight to its
+      // rank behind the key slots in use (no write meets a key that is still being compared).  Beyond that the
+      // positions overwrite the keys, so a thread keeps rank << 32 | position in the key's register until every
+      // thread has finished comparing (~0 = no key).  Either way there is no staging array and no copy pass: the
+      // barrier that stood between the staging writes and the copy's reads, and the one between the copy and the
+      // grid initialisation over the staging array, ordered accesses that no longer exist.
+      // The keys are ranked by slot, not from the registers that scattered them: neighbouring slots lie in the same
+      // bin, so the lanes of a wave walk the same few keys the same number of times.
+      const bool upper = remaining <= SEL_CHUNK / 2;
+#pragma unroll
+      for (int k = 0; k < SEL_KPT; k++) {
+        const int p = tid + k * SEL_THREADS;
+        rk[k] = ~0ull;
+        if (p < remaining) {
+          const unsigned long long key = keys[SEL_PHYS(p)];
+          const int bin = (int)(bin_top - min((uint32_t)(key >> 32) >> bshift, bin_top));
+          const int s0 = bstart[bin], e0 = s0 + bcount[bin];
+          int larger = 0;
+          for (int q = s0; q < e0; q++) larger += keys[SEL_PHYS(q)] > key;
+          if (upper) keys32[SEL_POS_UPPER + s0 + larger] = (uint32_t)key;
+          else rk[k] = ((unsigned long long)(uint32_t)(s0 + larger) << 32) | (uint32_t)key;
+        }
+      }
+      __syncthreads();
+      if (upper) {
+        pos_off = SEL_POS_UPPER;
+      } else {
+#pragma unroll
+        for (int k = 0; k < SEL_KPT; k++)
+          if ((uint32_t)(rk[k] >> 32) < (uint32_t)SEL_CHUNK) keys32[(uint32_t)(rk[k] >> 32)] = (uint32_t)rk[k];
+        __syncthreads();
+      }
+    } else {
+      // ---- the same through memory (more than SEL_CHUNK provisional candidates, at most SEL_CHUNK above the threshold)
+      for (int i = tid; i < n_cand; i += SEL_THREADS) {
+        const unsigned long long key = cand[i];
+        if (key > floor_key) {
+          const int bin = (int)(bin_top - min((uint32_t)(key >> 32) >> bshift, bin_top));
+          const int p = bstart[bin] + atomicAdd(&bcursor[bin], 1);  // (SEL_PHYS evaluates its argument twice)
+          keys[SEL_PHYS(p)] = key;
+        }
+      }
+      __syncthreads();
+      // the position goes to its rank in the staging array (no key is held in registers across a barrier), and the
+      // staging array is copied over the keys
+      for (int p = tid; p < remaining; p += SEL_THREADS) {
+        const unsigned long long key = keys[SEL_PHYS(p)];
+        const int bin = (int)(bin_top - min((uint32_t)(key >> 32) >> bshift, bin_top));
+        const int s0 = bstart[bin], e0 = s0 + bcount[bin];
+        int larger = 0;
+        for (int q = s0; q < e0; q++) larger += keys[SEL_PHYS(q)] > key;
+        stage[s0 + larger] = (uint32_t)key;
+      }
+      __syncthreads();
+      for (int p = tid; p < remaining; p += SEL_THREADS) keys32[p] = stage[p];
+      __syncthreads();
+      for (int i = tid; i < cells; i += SEL_THREADS) ((grid_u32*)acc)[i] = i < (cells >> 1) ? 0u : ~0u;
+      __syncthreads();
+    }
+    compact = true;
   }
-  bool compact = false;  // the sorted chunk is keys32[r], not keys[SEL_PHYS(r)]
 
   while (remaining > 0 && n_acc < num_features) {
     // ---- choose the chunk [lo, hi): all remaining keys, or the SEL_CHUNK largest of them
@@ -737,35 +853,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
       lo = prefix;  // = the SEL_CHUNK-th largest remaining key (keys are unique)
     }
     int n_chunk;
-    if (bucket_sort) {
-      // ---- scatter into the bins' slot ranges, then rank inside each bin
-      for (int i = tid; i < n_cand; i += SEL_THREADS) {
-        const unsigned long long key = cand[i];
-        if (key > floor_key) {
-          const int bin = (int)(bin_top - min((uint32_t)(key >> 32) >> bshift, bin_top));
-          const int p = bstart[bin] + atomicAdd(&bcursor[bin], 1);  // (SEL_PHYS evaluates its argument twice)
-          keys[SEL_PHYS(p)] = key;
-        }
-      }
-      __syncthreads();
-      n_chunk = remaining;
-      // only the pixel position of a key is read once it is ranked: it goes to its rank in the staging array (no
-      // key is held in registers across a barrier), and the staging array is copied over the keys
-      for (int p = tid; p < n_chunk; p += SEL_THREADS) {
-        const unsigned long long key = keys[SEL_PHYS(p)];
-        const int bin = (int)(bin_top - min((uint32_t)(key >> 32) >> bshift, bin_top));
-        const int s0 = bstart[bin], e0 = s0 + bcount[bin];
-        int larger = 0;
-        for (int q = s0; q < e0; q++) larger += keys[SEL_PHYS(q)] > key;
-        stage[s0 + larger] = (uint32_t)key;
-      }
-      __syncthreads();
-      for (int p = tid; p < n_chunk; p += SEL_THREADS) keys32[p] = stage[p];
-      __syncthreads();
-      for (int i = tid; i < cells; i += SEL_THREADS) ((volatile uint32_t*)acc)[i] = i < (cells >> 1) ? 0u : ~0u;
-      __syncthreads();
-      compact = true;
-      bucket_sort = false;
+    if (compact) {
+      n_chunk = remaining;  // the counting sort above ranked all of them (at most SEL_CHUNK: this is the only turn of the loop)
     } else {
       // ---- gather the chunk into LDS and pad to a power of two
       if (tid == 0) sh->n_chunk = 0;
@@ -814,7 +903,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
       int px = 0, py = 0, cell = 0;
       bool alive = false;
       if (r < n_chunk) {
-        const uint32_t pix = compact ? keys32[r] : (uint32_t)(keys[SEL_PHYS(r)] & 0xFFFFFFFFull);
+        const uint32_t pix = compact ? keys32[pos_off + r] :(uint32_t)(keys[SEL_PHYS(r)] & 0xFFFFFFFFull);
         py = (int)(pix >> 16);
         px = (int)(pix & 0xFFFFu);
         cell = ((py >> 3) + 1) * gw + (px >> 3) + 1;
@@ -847,6 +936,9 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
       // decided once all of them are: rejected if one was accepted, accepted otherwise.  The lowest
       // undecided rank never waits, so free-running polling of the LDS state words terminates; no
       // workgroup barrier per dependency level (all 16 waves are resident and keep being scheduled).
+      // The state words are read and written as relaxed workgroup-scope atomics: every turn of the polling loop
+      // loads them again, as a volatile access would, but as plain ds_read / ds_write -- a blocker's six words are
+      // in flight together, where six volatile reads were six serial FLAT round trips.
       int nb = 0;
       unsigned long long blk = 0ull;  // the last SEL_MAX_BLOCKERS blockers, 10 bits each (batch-local ranks): a register ARRAY
                                       // indexed by nb costs six compare / select pairs per insertion
@@ -874,7 +966,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
             }
         }
       }
-      bool undecided = alive;
+      bool undecided = alive, accepted = false;  // accepted: the thread's own decision (its state word is for the others)
       while (__ballot(undecided) != 0ull) {
         if (undecided) {
           bool rej = false, blocked = false;
@@ -882,7 +974,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
 #pragma unroll
             for (int k = 0; k < SEL_MAX_BLOCKERS; k++)
               if (k < nb) {
-                const int su = ((volatile int*)state)[(int)(blk >> (10 * k)) & 1023];
+                const int su = __hip_atomic_load(&state[(int)(blk >> (10 * k)) & 1023], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 rej = rej || (su == 1);
                 blocked = blocked || (su == 0);
               }
@@ -895,7 +987,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
                     const uint32_t q = (uint32_t)nd;
                     const int dx = px - (int)(q & 0xFFFF), dy = py - (int)(q >> 16);
                     if (dx * dx + dy * dy < 64) {
-                      const int su = ((volatile int*)state)[u];
+                      const int su = __hip_atomic_load(&state[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                       rej = rej || (su == 1);
                       blocked = blocked || (su == 0);
                     }
@@ -904,29 +996,40 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
           }
           const int ns = rej ? 2 : (blocked ? 0 : 1);
           if (ns) {
-            ((volatile int*)state)[tid] = ns;
+            __hip_atomic_store(&state[tid], ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             undecided = false;
+            accepted = ns == 1;
           }
         }
         __builtin_amdgcn_s_sleep(1);
       }
-      __syncthreads();
-      const bool accepted = alive && state[tid] == 1;
+      // One scan for both counts: accepted corners (low half) and accepted corners inside the border (high half).
+      // The cap at num_features keeps a PREFIX of the accepted corners in thread order, so a kept corner has only kept
+      // corners before it and its output position is the packed prefix as it stands; when the cap cuts this batch
+      // (workgroup-uniform, and the last batch then), the first corner that is cut has exactly the kept ones before
+      // it and publishes their number inside the border as the batch's total.
+      // Barriers: the one that stood here ordered the polling loop's reads of head / node / state before the reset
+      // of head below and the next batch's writes -- the scan's barrier does that now, every thread reaching it after
+      // its polling loop.  The scan's former leading barrier ordered the previous scan's reads of wave_tot before this
+      // write: with one scan per batch, the trailing barrier of the previous batch stands between them.
+      const bool inside = px >= border && px < w - border && py >= border && py < h - border;
       int total = 0;
-      const int rank = n_acc + block_scan(accepted, sh->wave_tot, total);
-      const bool keep = accepted && rank < num_features;
-      const bool inb = keep && px >= border && px < w - border && py >= border && py < h - border;
-      int total_out = 0;
-      const int pos = n_out + block_scan(inb, sh->wave_tot, total_out);
+      const int pre = block_scan(accepted, accepted && inside, sh->wave_tot, total);
+      const int lim = num_features - n_acc;       // accepted corners this batch may still keep (> 0)
+      const bool cut = (total & 0xFFFF) > lim;
+      const bool keep = accepted && (pre & 0xFFFF) < lim;
+      const bool inb = keep && inside;
       if (inb) {
+        const int pos = n_out + (pre >> 16);
         out[2 * pos] = px;
         out[2 * pos + 1] = py;
       }
+      if (cut && accepted && (pre & 0xFFFF) == lim) sh->sel_k = pre >> 16;
       if (keep) sel_acc_insert(acc, cell, SEL_ACC_VALID | (uint32_t)((py & 7) << 3) | (uint32_t)(px & 7));
       if (alive) head[cell] = (uint16_t)SEL_HEAD_EMPTY;
-      n_acc = min(num_features, n_acc + total);
-      n_out += total_out;
+      n_acc = min(num_features, n_acc + (total & 0xFFFF));
       __syncthreads();
+      n_out += cut ? sh->sel_k : total >> 16;
     }
     hi = lo;
     remaining -= n_chunk;
