@@ -23,6 +23,8 @@
 // relative_pose_covariance (below) references its entry points weakly, like the _w ones of loop_closure.h
 #pragma weak vsl_ba_relative_pose_covariance
 #pragma weak vsl_global_ba_relative_pose_covariance
+// bundle_adjustment_rig (below): likewise
+#pragma weak vsl_bundle_adjust_rig
 
 namespace visnav {
 
@@ -190,6 +192,86 @@ inline void bundle_adjustment(const Corners& feature_corners, const BundleAdjust
                               Landmarks& landmarks) {
   amd::run_ba<false>(feature_corners, options.use_huber, options.huber_parameter, options.max_num_iterations,
                      options.verbosity_level, fixed_cameras, calib_cam, cameras, landmarks, options.optimize_intrinsics);
+}
+
+// Rig-constrained bundle adjustment (vsl_bundle_adjust_rig; the reference has no counterpart: src/slam.cpp:1215 sets
+// T_w_c_right = pose * T_0_1 once and Ceres then moves the two cameras of a frame apart).  One SE(3) block per FRAME,
+// the calibrated extrinsics held fixed.  Bodies are the FrameIds of `cameras` in ascending order; the body frame is
+// camera 0: T_b_c[k] = T_i_c[0]^-1 * T_i_c[k] (k = 0: the identity, exactly).  A body is fixed if any of its cameras is
+// in fixed_cameras.  The body pose handed in is T_w_c of camera 0 where the frame has it, else T_w_c[k] * T_b_c[k]^-1 of
+// the camera that is there.  The problem is flattened by flatten_ba exactly as for bundle_adjustment (lm.obs).  ALL
+// camera poses are written back, derived from the optimised bodies (a frame whose cameras had drifted apart comes back
+// on the calibration), and the landmarks.  A window whose frames are all fixed returns untouched.  optimize_intrinsics is not offered in rig form (std::invalid_argument).
+namespace amd {
+inline void se3_mul7(const double* a, const double* b, double* o) {  // o = a * b, qx qy qz qw tx ty tz
+  const double ax = a[0], ay = a[1], az = a[2], aw = a[3];
+  const double q[4] = {aw * b[0] + ax * b[3] + ay * b[2] - az * b[1], aw * b[1] - ax * b[2] + ay * b[3] + az * b[0],
+                       aw * b[2] + ax * b[1] - ay * b[0] + az * b[3], aw * b[3] - ax * b[0] - ay * b[1] - az * b[2]};
+  const double R[9] = {1 - 2 * (ay * ay + az * az), 2 * (ax * ay - az * aw),     2 * (ax * az + ay * aw),
+                       2 * (ax * ay + az * aw),     1 - 2 * (ax * ax + az * az), 2 * (ay * az - ax * aw),
+                       2 * (ax * az - ay * aw),     2 * (ay * az + ax * aw),     1 - 2 * (ax * ax + ay * ay)};
+  double t[3];
+  for (int i = 0; i < 3; i++) t[i] = a[4 + i] + R[3 * i] * b[4] + R[3 * i + 1] * b[5] + R[3 * i + 2] * b[6];
+  const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int i = 0; i < 4; i++) o[i] = q[i] / n;
+  for (int i = 0; i < 3; i++) o[4 + i] = t[i];
+}
+inline void se3_inv7(const double* a, double* o) {  // o = a^-1
+  const double c[7] = {-a[0], -a[1], -a[2], a[3], 0, 0, 0}, mt[7] = {0, 0, 0, 1, -a[4], -a[5], -a[6]};
+  se3_mul7(c, mt, o);
+}
+}  // namespace amd
+
+inline void bundle_adjustment_rig(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                  const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                  Landmarks& landmarks) {
+  if (&vsl_bundle_adjust_rig == nullptr) throw std::runtime_error("bundle_adjustment_rig: libvslam_hip.so has no vsl_bundle_adjust_rig");
+  if (options.optimize_intrinsics) throw std::invalid_argument("bundle_adjustment_rig: optimize_intrinsics is not offered in rig form");
+  if (calib_cam.T_i_c.size() < 2) throw std::invalid_argument("bundle_adjustment_rig: the calibration needs two extrinsics");
+  amd::BaFlat f;
+  if (!amd::flatten_ba<false>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f)) return;
+  double T_b_c[14] = {0, 0, 0, 1, 0, 0, 0}, T_c_b[14] = {0, 0, 0, 1, 0, 0, 0}, inv0[7];
+  amd::se3_inv7(calib_cam.T_i_c[0].data(), inv0);
+  amd::se3_mul7(inv0, calib_cam.T_i_c[1].data(), T_b_c + 7);
+  amd::se3_inv7(T_b_c + 7, T_c_b + 7);
+  // bodies = frames, ascending: cam_id is in std::map order, i.e. by frame, camera 0 before camera 1
+  std::vector<double> body_poses;
+  std::vector<uint8_t> body_fixed;
+  std::vector<int32_t> cam_body(f.cam_id.size());
+  for (size_t c = 0; c < f.cam_id.size(); c++) {
+    const bool first = c == 0 || f.cam_id[c - 1].frame_id != f.cam_id[c].frame_id;
+    if (first) {
+      double b[7];
+      const int k = (int)f.cam_id[c].cam_id;
+      if (k == 0) std::copy(&f.poses[7 * c], &f.poses[7 * c] + 7, b);
+      else amd::se3_mul7(&f.poses[7 * c], T_c_b + 7 * k, b);
+      body_poses.insert(body_poses.end(), b, b + 7);
+      body_fixed.push_back(0);
+    }
+    cam_body[c] = (int32_t)body_fixed.size() - 1;
+    if (f.fixed[c]) body_fixed.back() = 1;
+  }
+  // a window of fixed frames only (the application's first keyframe): nothing to optimise, as on the default path
+  if (std::find(body_fixed.begin(), body_fixed.end(), (uint8_t)0) == body_fixed.end()) return;
+  vsl_ba_rig rig;
+  rig.n_bodies = (int32_t)body_fixed.size();
+  rig.body_poses = body_poses.data();
+  rig.body_fixed = body_fixed.data();
+  rig.cam_body = cam_body.data();
+  rig.T_b_c = T_b_c;
+  vsl_ba_options opt;
+  opt.use_huber = options.use_huber ? 1 : 0;
+  opt.huber_parameter = options.huber_parameter;
+  opt.max_num_iterations = options.max_num_iterations;
+  opt.verbosity = 0;
+  vsl_ba_summary sum;
+  amd::check(vsl_bundle_adjust_rig(amd::ctx(), &f.prob, &rig, &opt, &sum), "bundle_adjustment_rig");
+  for (size_t c = 0; c < f.cam_ptr.size(); c++) std::copy(&f.poses[7 * c], &f.poses[7 * c] + 7, f.cam_ptr[c]->T_w_c.data());
+  for (size_t l = 0; l < f.lm_ptr.size(); l++)
+    for (int j = 0; j < 3; j++) f.lm_ptr[l]->p.data()[j] = f.points[3 * l + j];
+  if (options.verbosity_level >= 1)
+    std::printf("vslam_hip rig BA: %d bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n",
+                (int)rig.n_bodies, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
 }
 
 // Marginal covariances of the map as it stands (vsl_ba_covariance; the reference has no counterpart, Ceres offers it as

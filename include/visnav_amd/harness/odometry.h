@@ -56,6 +56,8 @@ namespace visnav {
 namespace harness {
 
 inline bool ba_covariance_available() { return &vsl_ba_covariance != nullptr; }
+// the rig-constrained local bundle adjustment (OdometryOptions::rig_ba; weak in bundle_adjustment.h)
+inline bool rig_ba_available() { return &vsl_bundle_adjust_rig != nullptr; }
 inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
 // the device keyframe database (OdometryOptions::device_place_db) is referenced weakly in the same way (bow.h)
 inline bool device_place_db_available() { return KeyframeDatabaseAmd::available(); }
@@ -115,6 +117,9 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   // rotational one (visnav::bundle_adjustment_covariance; units: per pixel of observation noise).  Nothing else
   // changes: the trajectory is the one of a run without it.
   std::string ba_covariance_path;
+  // the local bundle adjustment optimises ONE pose per stereo keyframe with the calibrated extrinsics held fixed
+  // (visnav::bundle_adjustment_rig) instead of two independent cameras.  Off by default: nothing changes without it.
+  bool rig_ba = false;
   double motion_threshold = 0.5;
   int num_cov_threshold = 10;
   int num_ess_threshold = 30;
@@ -710,7 +715,8 @@ class Odometry {
     clock.ba_runs++;
     auto work = [this, fid, ba_options] {
       const std::set<FrameCamId> fixed_cameras = {FrameCamId(fid, 0), FrameCamId(fid, 1)};
-      bundle_adjustment(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt);
+      if (opt.rig_ba) bundle_adjustment_rig(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt);
+      else bundle_adjustment(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt);
       if (!opt.ba_covariance_path.empty()) write_window_covariance(fixed_cameras, ba_options);
       if (std::getenv("VISNAV_AMD_TRACE_FRAMES")) {
         double h = 0;

@@ -632,6 +632,53 @@ int vsl_ctx_memcpy(vsl_ctx* ctx, void* dst, const void* src, size_t bytes, int k
  * parameters a model does not use keep their values).  intr_io [16] in/out; prob->intr is ignored. */
 int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, double* intr_io,
                                  vsl_ba_summary* summary);
+/* ---- rig-constrained bundle adjustment: one pose per stereo frame (visual-slam_amd/csrc/ba_rig.hip) ----
+ * Every other solve above treats the left and the right camera of a stereo frame as two independent SE(3) blocks, as
+ * the reference does (src/slam.cpp:1215 sets T_w_c_right = pose * T_0_1 once and Ceres then moves the two apart).  Here
+ * the unknown is ONE body pose per frame and the calibrated extrinsics are held fixed:
+ *   T_w_c = T_w_b[cam_body[c]] * T_b_c[cam_intr[c]].
+ * prob->cam_fixed is ignored (it may be NULL): a camera is fixed iff its body is.  prob->poses is OUTPUT ONLY: on return
+ * of the solve it holds the camera poses derived from the final bodies.  Unknowns: the free bodies in ascending body id,
+ * 6 each, tangent (upsilon, omega) of T_w_b * exp(delta), then the landmarks.  Residual, camera models, Huber corrector
+ * and cost are exactly those of vsl_bundle_adjust; the pose Jacobian of an observation in camera c is
+ * F_b = F_c Ad(T_b_c^-1), Ad in the (upsilon, omega) order.  Jacobi scaling 1 / (1 + sqrt(diag H)) and LM damping
+ * clamp(diag, 1e-6, 1e32) / radius act on the BODY columns and the landmark columns (the problem Ceres would see if the
+ * cost functor took the body pose); the LM policy is that of every other solve.  The reduced body system (6 x 6 blocks,
+ * half the unknowns of the free form) always goes to the dense SPD solver; every reduction runs in a fixed order (two
+ * solves return the same bits).  With A the block matrix that maps free-body tangents to the tangents of their cameras
+ * (block (c, cam_body[c]) = Ad(T_b_c^-1)) and S_free, g_free of vsl_ba_linearize for cam_fixed[c] =
+ * body_fixed[cam_body[c]], the undamped unscaled rig system is S_rig = A^T S_free A, g_rig = A^T g_free.
+ * VSL_ERR_INVALID, nothing written: a null pointer; cam_body out of range; a body that carries no camera; two cameras of
+ * one body with the same intrinsics block; no free body; an empty problem; an extrinsic that is not finite.  The
+ * quaternions of T_b_c are normalised on the way in.
+ * No fixed body (the gauge is free): the hooks return VSL_ERR_NUMERIC without writing anything -- the undamped reduced
+ * system is singular by construction --; the solve runs the LM policy on the damped system as for any input, a failed
+ * factorisation is an unsuccessful step, and no non-finite value reaches a pose.
+ * NOT COVERED: covariances in rig form, rig global bundle adjustment / sessions / multi-GPU, the intrinsics variant,
+ * optimising the extrinsics, band / ring / matrix-free routes for the reduced system. */
+typedef struct vsl_ba_rig {
+  int32_t n_bodies;
+  double* body_poses;         /* [7*n_bodies] qx qy qz qw tx ty tz (T_w_b), in/out          */
+  const uint8_t* body_fixed;  /* [n_bodies]                                                 */
+  const int32_t* cam_body;    /* [prob->n_cams] body that carries camera c                  */
+  const double* T_b_c;        /* [2][7] extrinsic of intrinsics block 0 / 1 (prob->cam_intr) */
+} vsl_ba_rig;
+/* The solve: updates rig->body_poses, prob->points and prob->poses; summary as for vsl_bundle_adjust. */
+int vsl_bundle_adjust_rig(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                          vsl_ba_summary* summary);
+/* Parity hook, the contract of vsl_ba_linearize: S [(6 n_free)^2] row-major (exactly symmetric), g [6 n_free] and cost
+ * with the Huber corrector, no scaling, no damping, at the bodies / points handed in (nothing is optimised). */
+int vsl_ba_rig_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                         double* S, double* g, double* cost, int* n_free_bodies);
+/* Parity hook, the counterpart of vsl_ba_fused_system: the scaled, damped reduced system of the solve's first step at
+ * 1 / radius = inv_radius (0 = no damping), through the solve's own host code and kernels.  S [n * n], rhs [n],
+ * scale_b [n] (D of the body unknowns), db [n] = -(S^-1 rhs) (undefined when *chol_ok == 0), cost; n = 6 * free bodies.
+ * Every output pointer may be NULL.  A factorisation that fails (a pivot that is not positive and finite, e.g. the free
+ * scale of one camera per body at inv_radius = 0) is reported as *chol_ok = 0 with VSL_OK, as vsl_ba_fused_system does;
+ * with chol_ok NULL it is VSL_ERR_NUMERIC after the other outputs are written. */
+int vsl_ba_rig_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                      double inv_radius, double* S, double* rhs, double* scale_b, double* db, double* cost, int* chol_ok);
+
 /* The solver behind the reduced camera system, on its own (the place Ceres' SPARSE_SCHUR hands S to a Cholesky,
  * include/visnav/map_utils.h:406-411, loop_closure_utils.h:735): solves S x = b for a symmetric positive definite S
  * given as a HOST row-major n x n array of which only the lower triangle is read.  half_bandwidth < 0: dense

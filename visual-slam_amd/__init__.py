@@ -61,6 +61,10 @@ class BaSummary(C.Structure):
                 ("schur_ms", C.c_double), ("solve_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class BaRig(C.Structure):
+    _fields_ = [("n_bodies", C.c_int32), ("body_poses", f64p), ("body_fixed", u8p), ("cam_body", i32p), ("T_b_c", f64p)]
+
+
 class PgoProblem(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("poses", f64p), ("node_fixed", u8p),
                 ("edge_a", i32p), ("edge_b", i32p), ("edge_meas", f64p)]
@@ -626,6 +630,52 @@ class Context:
             return None
         return dict(S=S, rhs=rhs, scale_c=scale_c, dc=dc, cost=cost.value, chol_ok=ok.value, n_free=nf.value)
 
+    # ---- rig-constrained bundle adjustment: one pose per stereo frame (vsl_ba_rig, include/vslam_hip.h)
+    def _ba_rig_structs(self, arr, rig):
+        """The problem struct without cam_fixed (the rig calls ignore it) and the rig struct."""
+        st = self._ba_struct(arr)
+        rg = BaRig()
+        rg.n_bodies = len(rig.body_poses)
+        rg.body_poses = rig.body_poses.ctypes.data_as(f64p)
+        rg.body_fixed = rig.body_fixed.ctypes.data_as(u8p)
+        rg.cam_body = rig.cam_body.ctypes.data_as(i32p)
+        rg.T_b_c = rig.T_b_c.ctypes.data_as(f64p)
+        return st, rg
+
+    def bundle_adjust_rig(self, arr, rig, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
+        """vsl_bundle_adjust_rig: optimises rig.body_poses and arr.points in place; arr.poses receives the camera poses
+        derived from the final bodies.  rig: a RigArrays."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        o = self._ba_opts(use_huber, huber, max_iters, verbosity)
+        s = BaSummary()
+        self._ck(self.L.vsl_bundle_adjust_rig(self.h, C.byref(st), C.byref(rg), C.byref(o), C.byref(s)))
+        return s
+
+    def ba_rig_linearize(self, arr, rig, use_huber=True, huber=1.0):
+        """(S, g, cost) of the reduced BODY system: Huber corrector, no scaling, no damping (vsl_ba_rig_linearize)."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * rig.n_free
+        S, g = np.zeros((n, n)), np.zeros(n)
+        cost, nf = C.c_double(), C.c_int32()
+        self._ck(self.L.vsl_ba_rig_linearize(self.h, C.byref(st), C.byref(rg), C.byref(o), S.ctypes.data_as(f64p),
+                                             g.ctypes.data_as(f64p), C.byref(cost), C.byref(nf)))
+        assert nf.value == rig.n_free
+        return S, g, cost.value
+
+    def ba_rig_system(self, arr, rig, inv_radius=0.0, use_huber=True, huber=1.0):
+        """The scaled, damped reduced body system of the rig solve's first step (vsl_ba_rig_system): a dict with S [n, n],
+        rhs, scale_b, db [n], cost, chol_ok."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * rig.n_free
+        S, rhs, scale_b, db = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n)
+        cost, ok = C.c_double(), C.c_int32()
+        self._ck(self.L.vsl_ba_rig_system(self.h, C.byref(st), C.byref(rg), C.byref(o), C.c_double(inv_radius),
+                                          S.ctypes.data_as(f64p), rhs.ctypes.data_as(f64p), scale_b.ctypes.data_as(f64p),
+                                          db.ctypes.data_as(f64p), C.byref(cost), C.byref(ok)))
+        return dict(S=S, rhs=rhs, scale_b=scale_b, db=db, cost=cost.value, chol_ok=ok.value)
+
     def ba_schur_apply(self, arr, x, use_huber=True, huber=1.0):
         """y = S x with the reduced camera system S of ba_linearize, never formed (vsl_ba_schur_apply)."""
         st = self._ba_struct(arr)
@@ -783,6 +833,25 @@ class BaArrays:
     @property
     def n_free(self):
         return int((self.cam_fixed == 0).sum())
+
+
+class RigArrays:
+    """Owns the contiguous numpy arrays of a vsl_ba_rig (include/vslam_hip.h): body poses [B, 7], body_fixed [B],
+    cam_body [cameras of the BaArrays it goes with], T_b_c [2, 7]: what Context.bundle_adjust_rig / ba_rig_linearize /
+    ba_rig_system take beside a BaArrays."""
+
+    def __init__(self, body_poses, body_fixed, cam_body, T_b_c):
+        self.body_poses = np.ascontiguousarray(body_poses, np.float64).reshape(-1, 7).copy()
+        self.body_fixed = np.ascontiguousarray(body_fixed, np.uint8).copy()
+        self.cam_body = np.ascontiguousarray(cam_body, np.int32).copy()
+        self.T_b_c = np.ascontiguousarray(T_b_c, np.float64).reshape(2, 7).copy()
+
+    def copy(self):
+        return RigArrays(self.body_poses, self.body_fixed, self.cam_body, self.T_b_c)
+
+    @property
+    def n_free(self):
+        return int((self.body_fixed == 0).sum())
 
 
 class Vocabulary:

@@ -5,7 +5,7 @@
 // libvslam_hip.so; there is no CPU fallback.
 //
 //   slam_headless --dataset-path <dir with cam0/ cam1/ ...> --cam-calib <calib.json>
-//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N] [--ba-covariance FILE]
+//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N] [--ba-covariance FILE] [--rig-ba]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -60,6 +60,7 @@ int main(int argc, char** argv) {
     else if (a == "--max-kfs") opt.max_num_kfs = std::atoi(need("--max-kfs").c_str());
     else if (a == "--num-features") opt.num_features_per_image = std::atoi(need("--num-features").c_str());
     else if (a == "--ba-covariance") opt.ba_covariance_path = need("--ba-covariance");  // pose uncertainty of the window after every local BA
+    else if (a == "--rig-ba") opt.rig_ba = true;  // local BA with one pose per stereo keyframe (visnav::bundle_adjustment_rig)
     else if (a == "--ba-verbose") opt.ba_verbose = 1;
     else if (a == "--ba-iterations") opt.ba_max_iterations = std::atoi(need("--ba-iterations").c_str());
     else if (a == "--relocalization") opt.enable_relocalization = true;   // the reference's ui.relocalization (default on there)
@@ -104,6 +105,10 @@ int main(int argc, char** argv) {
   }
   if (opt.device_bow && !device_bow_available()) {
     std::fprintf(stderr, "--device-bow: this build's C ABI has no batched keyframe BoW (vsl_frames_bow_vectors)\n");
+    return 2;
+  }
+  if (opt.rig_ba && !rig_ba_available()) {
+    std::fprintf(stderr, "--rig-ba: this build's C ABI has no rig bundle adjustment (vsl_bundle_adjust_rig)\n");
     return 2;
   }
   if (!opt.ba_covariance_path.empty()) {

@@ -1,0 +1,213 @@
+// ba_rig_plan.h -- the host half of the rig-constrained bundle adjustment (ba_rig.hip): validation of a vsl_ba_rig
+// against its vsl_ba_problem, the free-body numbering, the camera -> (body slot, extrinsic) table, the observations
+// sorted by landmark with the observations of one body ADJACENT inside a landmark, the (landmark, free body) groups
+// that the Schur reduction works on, and the body-major lists of groups and observations that the gathers walk.
+// Plain C++ (no HIP, no other header of the library): tests/cpp/ba_rig_plan_test.cpp drives it on the CPU.
+//
+// Orders, which are the summation orders of the kernels and so part of the result's bits:
+//   observations  by landmark; inside a landmark the observations of fixed bodies first, then by free-body slot; ties by
+//                 the caller's index
+//   groups        one per (landmark, free body) that has an observation, numbered in that order: ascending landmark,
+//                 then ascending slot.  A landmark seen by both cameras of one free body gives ONE group of two
+//                 observations -- the normal stereo case
+//   body lists    groups / observations of a free body in ascending group / sorted-observation number (so a body's
+//                 groups are in ascending landmark: the Schur gather finds a partner by bisection)
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <numeric>
+#include <vector>
+
+enum RigPlanStatus {
+  RIG_PLAN_OK = 0,
+  RIG_PLAN_NULL,            // a null pointer
+  RIG_PLAN_EMPTY,           // no camera, landmark, observation or body
+  RIG_PLAN_INDEX,           // an observation's camera / landmark or a cam_intr out of range
+  RIG_PLAN_CAM_BODY,        // cam_body out of range
+  RIG_PLAN_BODY_NO_CAMERA,  // a body that carries no camera
+  RIG_PLAN_SHARED_INTR,     // two cameras of one body with the same intrinsics block
+  RIG_PLAN_NO_FREE_BODY,    // every body is fixed
+  RIG_PLAN_EXTRINSIC        // an extrinsic that is not finite or has a zero quaternion
+};
+
+inline const char* rig_plan_message(int status) {
+  switch (status) {
+    case RIG_PLAN_OK: return "ok";
+    case RIG_PLAN_NULL: return "null pointer";
+    case RIG_PLAN_EMPTY: return "empty problem";
+    case RIG_PLAN_INDEX: return "observation or cam_intr out of range";
+    case RIG_PLAN_CAM_BODY: return "cam_body out of range";
+    case RIG_PLAN_BODY_NO_CAMERA: return "a body carries no camera";
+    case RIG_PLAN_SHARED_INTR: return "two cameras of one body share an intrinsics block";
+    case RIG_PLAN_NO_FREE_BODY: return "no free body";
+    default: return "extrinsic not finite or its quaternion zero";
+  }
+}
+
+// the fields of vsl_ba_problem / vsl_ba_rig that the plan reads
+struct RigPlanIn {
+  int n_cams = 0, n_lms = 0, n_obs = 0;
+  const int32_t *cam_intr = nullptr, *obs_cam = nullptr, *obs_lm = nullptr;
+  int n_bodies = 0;
+  const uint8_t* body_fixed = nullptr;
+  const int32_t* cam_body = nullptr;
+  const double* T_b_c = nullptr;  // [2][7]
+};
+
+struct RigPlan {
+  int n_free = 0, n_fixed = 0;
+  int first_bad = -1;                 // camera, body or observation the status is about
+  std::vector<int> body_slot;         // [bodies] free-body number, -1 fixed
+  std::vector<int> free_bodies;       // [n_free] body id
+  std::vector<int> cam_slot;          // [cams] slot of the carrying body
+  double T_b_c[14];                   // the two extrinsics, quaternion normalised
+  double T_c_b[24];                   // their inverses as rotation matrix (9, row-major) and translation (3): Ad(T_b_c^-1)
+  std::vector<int> perm;              // [obs] sorted position -> caller's observation
+  std::vector<int> obs_cam, obs_lm;   // [obs] in sorted order
+  std::vector<int> lm_start;          // [lms + 1] sorted observations of a landmark
+  std::vector<int> lm_grp;            // [lms + 1] groups of a landmark
+  std::vector<int> grp_lm, grp_slot, grp_begin, grp_end;  // [groups]; sorted observations [begin, end)
+  std::vector<int> bg_start, bg_grp, bg_lm;               // [n_free + 1], [groups], [groups]: a body's groups and their landmarks
+  std::vector<int> bo_start, bo_obs;                      // [n_free + 1], [free observations]: a body's sorted observations
+  int n_groups() const { return (int)grp_lm.size(); }
+};
+
+// 0 and the plan, or the first rule broken (nothing of `out` is then meaningful except first_bad)
+inline int rig_plan_build(const RigPlanIn& in, RigPlan& out) {
+  out = RigPlan();
+  if (in.n_cams <= 0 || in.n_lms <= 0 || in.n_obs <= 0 || in.n_bodies <= 0) return RIG_PLAN_EMPTY;
+  if (!in.cam_intr || !in.obs_cam || !in.obs_lm || !in.body_fixed || !in.cam_body || !in.T_b_c) return RIG_PLAN_NULL;
+  const int C = in.n_cams, L = in.n_lms, O = in.n_obs, B = in.n_bodies;
+  for (int c = 0; c < C; c++)
+    if (in.cam_intr[c] < 0 || in.cam_intr[c] > 1) { out.first_bad = c; return RIG_PLAN_INDEX; }
+  for (int i = 0; i < O; i++)
+    if (in.obs_cam[i] < 0 || in.obs_cam[i] >= C || in.obs_lm[i] < 0 || in.obs_lm[i] >= L) { out.first_bad = i; return RIG_PLAN_INDEX; }
+  for (int c = 0; c < C; c++)
+    if (in.cam_body[c] < 0 || in.cam_body[c] >= B) { out.first_bad = c; return RIG_PLAN_CAM_BODY; }
+  std::vector<int> seen(2 * (size_t)B, 0);
+  for (int c = 0; c < C; c++)
+    if (seen[2 * (size_t)in.cam_body[c] + in.cam_intr[c]]++) { out.first_bad = c; return RIG_PLAN_SHARED_INTR; }
+  for (int b = 0; b < B; b++)
+    if (!seen[2 * (size_t)b] && !seen[2 * (size_t)b + 1]) { out.first_bad = b; return RIG_PLAN_BODY_NO_CAMERA; }
+  out.body_slot.assign(B, -1);
+  for (int b = 0; b < B; b++) {
+    if (in.body_fixed[b]) { out.n_fixed++; continue; }
+    out.body_slot[b] = out.n_free++;
+    out.free_bodies.push_back(b);
+  }
+  if (out.n_free == 0) return RIG_PLAN_NO_FREE_BODY;
+  for (int k = 0; k < 2; k++) {
+    const double* T = in.T_b_c + 7 * k;
+    double nn = 0;
+    for (int j = 0; j < 7; j++)
+      if (!std::isfinite(T[j])) { out.first_bad = k; return RIG_PLAN_EXTRINSIC; }
+    for (int j = 0; j < 4; j++) nn += T[j] * T[j];
+    nn = std::sqrt(nn);
+    if (!(nn > 0.0) || !std::isfinite(nn)) { out.first_bad = k; return RIG_PLAN_EXTRINSIC; }
+    double* q = out.T_b_c + 7 * k;
+    for (int j = 0; j < 4; j++) q[j] = T[j] / nn;
+    for (int j = 4; j < 7; j++) q[j] = T[j];
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w),     2 * (x * z + y * w),
+                         2 * (x * y + z * w),     1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                         2 * (x * z - y * w),     2 * (y * z + x * w),     1 - 2 * (x * x + y * y)};
+    // T_c_b = (R^T, -R^T t)
+    double* o = out.T_c_b + 12 * k;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) o[3 * i + j] = R[3 * j + i];
+    for (int i = 0; i < 3; i++) o[9 + i] = -(o[3 * i] * q[4] + o[3 * i + 1] * q[5] + o[3 * i + 2] * q[6]);
+  }
+  out.cam_slot.resize(C);
+  for (int c = 0; c < C; c++) out.cam_slot[c] = out.body_slot[in.cam_body[c]];
+
+  out.perm.resize(O);
+  std::iota(out.perm.begin(), out.perm.end(), 0);
+  std::stable_sort(out.perm.begin(), out.perm.end(), [&](int a, int b) {
+    if (in.obs_lm[a] != in.obs_lm[b]) return in.obs_lm[a] < in.obs_lm[b];
+    return out.cam_slot[in.obs_cam[a]] < out.cam_slot[in.obs_cam[b]];
+  });
+  out.obs_cam.resize(O);
+  out.obs_lm.resize(O);
+  out.lm_start.assign(L + 1, 0);
+  for (int q = 0; q < O; q++) {
+    out.obs_cam[q] = in.obs_cam[out.perm[q]];
+    out.obs_lm[q] = in.obs_lm[out.perm[q]];
+    out.lm_start[out.obs_lm[q] + 1]++;
+  }
+  for (int l = 0; l < L; l++) out.lm_start[l + 1] += out.lm_start[l];
+
+  out.lm_grp.assign(L + 1, 0);
+  out.bo_start.assign(out.n_free + 1, 0);
+  out.bg_start.assign(out.n_free + 1, 0);
+  for (int l = 0; l < L; l++) {
+    int q = out.lm_start[l];
+    const int end = out.lm_start[l + 1];
+    while (q < end && out.cam_slot[out.obs_cam[q]] < 0) q++;
+    while (q < end) {
+      const int s = out.cam_slot[out.obs_cam[q]];
+      int e = q;
+      while (e < end && out.cam_slot[out.obs_cam[e]] == s) e++;
+      out.grp_lm.push_back(l);
+      out.grp_slot.push_back(s);
+      out.grp_begin.push_back(q);
+      out.grp_end.push_back(e);
+      out.bg_start[s + 1]++;
+      out.bo_start[s + 1] += e - q;
+      q = e;
+    }
+    out.lm_grp[l + 1] = (int)out.grp_lm.size();
+  }
+  for (int s = 0; s < out.n_free; s++) {
+    out.bg_start[s + 1] += out.bg_start[s];
+    out.bo_start[s + 1] += out.bo_start[s];
+  }
+  const int G = out.n_groups();
+  out.bg_grp.resize(G);
+  out.bg_lm.resize(G);
+  out.bo_obs.resize(out.bo_start[out.n_free]);
+  std::vector<int> gpos(out.bg_start.begin(), out.bg_start.end() - 1), opos(out.bo_start.begin(), out.bo_start.end() - 1);
+  for (int g = 0; g < G; g++) {
+    const int s = out.grp_slot[g];
+    out.bg_grp[gpos[s]] = g;
+    out.bg_lm[gpos[s]++] = out.grp_lm[g];
+    for (int q = out.grp_begin[g]; q < out.grp_end[g]; q++) out.bo_obs[opos[s]++] = q;
+  }
+  return RIG_PLAN_OK;
+}
+
+// the properties the kernels rely on (used by the CPU test on every plan it builds): true when they hold
+inline bool rig_plan_check(const RigPlanIn& in, const RigPlan& p) {
+  const int O = in.n_obs, L = in.n_lms, G = p.n_groups();
+  std::vector<int> hit(O, 0);
+  for (int q = 0; q < O; q++) {
+    if (p.perm[q] < 0 || p.perm[q] >= O || hit[p.perm[q]]++) return false;
+    if (q > 0 && p.obs_lm[q] < p.obs_lm[q - 1]) return false;
+    if (q < p.lm_start[p.obs_lm[q]] || q >= p.lm_start[p.obs_lm[q] + 1]) return false;
+  }
+  if (p.lm_start[L] != O || p.lm_grp[L] != G) return false;
+  size_t free_obs = 0;
+  for (int g = 0; g < G; g++) {
+    const int l = p.grp_lm[g], s = p.grp_slot[g];
+    if (s < 0 || s >= p.n_free || g < p.lm_grp[l] || g >= p.lm_grp[l + 1]) return false;
+    if (p.grp_begin[g] >= p.grp_end[g] || p.grp_begin[g] < p.lm_start[l] || p.grp_end[g] > p.lm_start[l + 1]) return false;
+    if (g > 0 && (p.grp_lm[g - 1] > l || (p.grp_lm[g - 1] == l && (p.grp_slot[g - 1] >= s || p.grp_end[g - 1] != p.grp_begin[g])))) return false;
+    for (int q = p.grp_begin[g]; q < p.grp_end[g]; q++)
+      if (p.cam_slot[p.obs_cam[q]] != s) return false;
+    free_obs += p.grp_end[g] - p.grp_begin[g];
+  }
+  size_t want = 0;
+  for (int q = 0; q < O; q++) want += p.cam_slot[p.obs_cam[q]] >= 0;
+  if (free_obs != want || p.bo_obs.size() != want || p.bg_start[p.n_free] != G) return false;
+  for (int s = 0; s < p.n_free; s++) {
+    for (int k = p.bg_start[s]; k < p.bg_start[s + 1]; k++) {
+      if (p.grp_slot[p.bg_grp[k]] != s || p.bg_lm[k] != p.grp_lm[p.bg_grp[k]]) return false;
+      if (k > p.bg_start[s] && p.bg_lm[k - 1] >= p.bg_lm[k]) return false;  // strictly ascending: bisection finds at most one
+    }
+    for (int k = p.bo_start[s]; k < p.bo_start[s + 1]; k++) {
+      if (p.cam_slot[p.obs_cam[p.bo_obs[k]]] != s) return false;
+      if (k > p.bo_start[s] && p.bo_obs[k - 1] >= p.bo_obs[k]) return false;
+    }
+  }
+  return true;
+}
