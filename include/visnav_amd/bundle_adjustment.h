@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <array>
 #include <set>
 #include <string>
 #include <thread>
@@ -25,6 +26,9 @@
 #pragma weak vsl_global_ba_relative_pose_covariance
 // bundle_adjustment_rig (below): likewise
 #pragma weak vsl_bundle_adjust_rig
+// bundle_adjustment_rig_covariance, rig_relative_pose_covariance, rig_map_edge_information (below): likewise
+#pragma weak vsl_ba_rig_covariance
+#pragma weak vsl_ba_rig_relative_pose_covariance
 
 namespace visnav {
 
@@ -222,56 +226,85 @@ inline void se3_inv7(const double* a, double* o) {  // o = a^-1
 }
 }  // namespace amd
 
-inline void bundle_adjustment_rig(const Corners& feature_corners, const BundleAdjustmentOptions& options,
-                                  const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
-                                  Landmarks& landmarks) {
-  if (&vsl_bundle_adjust_rig == nullptr) throw std::runtime_error("bundle_adjustment_rig: libvslam_hip.so has no vsl_bundle_adjust_rig");
-  if (options.optimize_intrinsics) throw std::invalid_argument("bundle_adjustment_rig: optimize_intrinsics is not offered in rig form");
-  if (calib_cam.T_i_c.size() < 2) throw std::invalid_argument("bundle_adjustment_rig: the calibration needs two extrinsics");
-  amd::BaFlat f;
-  if (!amd::flatten_ba<false>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f)) return;
-  double T_b_c[14] = {0, 0, 0, 1, 0, 0, 0}, T_c_b[14] = {0, 0, 0, 1, 0, 0, 0}, inv0[7];
-  amd::se3_inv7(calib_cam.T_i_c[0].data(), inv0);
-  amd::se3_mul7(inv0, calib_cam.T_i_c[1].data(), T_b_c + 7);
-  amd::se3_inv7(T_b_c + 7, T_c_b + 7);
-  // bodies = frames, ascending: cam_id is in std::map order, i.e. by frame, camera 0 before camera 1
+namespace amd {
+// What the rig calls share: the flattening of bundle_adjustment (flatten_ba, lm.obs) plus the rig of the rules above.
+// Not copyable once filled (prob and rig point into the members).
+struct RigFlat {
+  BaFlat f;
+  double T_b_c[14] = {0, 0, 0, 1, 0, 0, 0}, T_c_b[14] = {0, 0, 0, 1, 0, 0, 0};
   std::vector<double> body_poses;
   std::vector<uint8_t> body_fixed;
-  std::vector<int32_t> cam_body(f.cam_id.size());
+  std::vector<int32_t> cam_body;
+  std::vector<FrameId> body_frame;  // ascending
+  vsl_ba_rig rig;
+  bool any_free = false;
+  RigFlat() = default;
+  RigFlat(const RigFlat&) = delete;
+  RigFlat& operator=(const RigFlat&) = delete;
+  int32_t body_of(FrameId frame) const {  // -1: not a frame of the problem
+    const auto it = std::lower_bound(body_frame.begin(), body_frame.end(), frame);
+    return it == body_frame.end() || *it != frame ? -1 : (int32_t)(it - body_frame.begin());
+  }
+};
+// false: the map has no observation (nothing is filled)
+inline bool flatten_rig(const char* what, const Corners& feature_corners, const std::set<FrameCamId>& fixed_cameras,
+                        Calibration& calib_cam, Cameras& cameras, Landmarks& landmarks, RigFlat& r) {
+  if (calib_cam.T_i_c.size() < 2) throw std::invalid_argument(std::string(what) + ": the calibration needs two extrinsics");
+  BaFlat& f = r.f;
+  if (!flatten_ba<false>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f)) return false;
+  double inv0[7];
+  se3_inv7(calib_cam.T_i_c[0].data(), inv0);
+  se3_mul7(inv0, calib_cam.T_i_c[1].data(), r.T_b_c + 7);
+  se3_inv7(r.T_b_c + 7, r.T_c_b + 7);
+  // bodies = frames, ascending: cam_id is in std::map order, i.e. by frame, camera 0 before camera 1
+  r.cam_body.resize(f.cam_id.size());
   for (size_t c = 0; c < f.cam_id.size(); c++) {
     const bool first = c == 0 || f.cam_id[c - 1].frame_id != f.cam_id[c].frame_id;
     if (first) {
       double b[7];
       const int k = (int)f.cam_id[c].cam_id;
       if (k == 0) std::copy(&f.poses[7 * c], &f.poses[7 * c] + 7, b);
-      else amd::se3_mul7(&f.poses[7 * c], T_c_b + 7 * k, b);
-      body_poses.insert(body_poses.end(), b, b + 7);
-      body_fixed.push_back(0);
+      else se3_mul7(&f.poses[7 * c], r.T_c_b + 7 * k, b);
+      r.body_poses.insert(r.body_poses.end(), b, b + 7);
+      r.body_fixed.push_back(0);
+      r.body_frame.push_back(f.cam_id[c].frame_id);
     }
-    cam_body[c] = (int32_t)body_fixed.size() - 1;
-    if (f.fixed[c]) body_fixed.back() = 1;
+    r.cam_body[c] = (int32_t)r.body_fixed.size() - 1;
+    if (f.fixed[c]) r.body_fixed.back() = 1;
   }
+  r.any_free = std::find(r.body_fixed.begin(), r.body_fixed.end(), (uint8_t)0) != r.body_fixed.end();
+  r.rig.n_bodies = (int32_t)r.body_fixed.size();
+  r.rig.body_poses = r.body_poses.data();
+  r.rig.body_fixed = r.body_fixed.data();
+  r.rig.cam_body = r.cam_body.data();
+  r.rig.T_b_c = r.T_b_c;
+  return true;
+}
+}  // namespace amd
+
+inline void bundle_adjustment_rig(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                  const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                  Landmarks& landmarks) {
+  if (&vsl_bundle_adjust_rig == nullptr) throw std::runtime_error("bundle_adjustment_rig: libvslam_hip.so has no vsl_bundle_adjust_rig");
+  if (options.optimize_intrinsics) throw std::invalid_argument("bundle_adjustment_rig: optimize_intrinsics is not offered in rig form");
+  amd::RigFlat r;
+  if (!amd::flatten_rig("bundle_adjustment_rig", feature_corners, fixed_cameras, calib_cam, cameras, landmarks, r)) return;
   // a window of fixed frames only (the application's first keyframe): nothing to optimise, as on the default path
-  if (std::find(body_fixed.begin(), body_fixed.end(), (uint8_t)0) == body_fixed.end()) return;
-  vsl_ba_rig rig;
-  rig.n_bodies = (int32_t)body_fixed.size();
-  rig.body_poses = body_poses.data();
-  rig.body_fixed = body_fixed.data();
-  rig.cam_body = cam_body.data();
-  rig.T_b_c = T_b_c;
+  if (!r.any_free) return;
+  amd::BaFlat& f = r.f;
   vsl_ba_options opt;
   opt.use_huber = options.use_huber ? 1 : 0;
   opt.huber_parameter = options.huber_parameter;
   opt.max_num_iterations = options.max_num_iterations;
   opt.verbosity = 0;
   vsl_ba_summary sum;
-  amd::check(vsl_bundle_adjust_rig(amd::ctx(), &f.prob, &rig, &opt, &sum), "bundle_adjustment_rig");
+  amd::check(vsl_bundle_adjust_rig(amd::ctx(), &f.prob, &r.rig, &opt, &sum), "bundle_adjustment_rig");
   for (size_t c = 0; c < f.cam_ptr.size(); c++) std::copy(&f.poses[7 * c], &f.poses[7 * c] + 7, f.cam_ptr[c]->T_w_c.data());
   for (size_t l = 0; l < f.lm_ptr.size(); l++)
     for (int j = 0; j < 3; j++) f.lm_ptr[l]->p.data()[j] = f.points[3 * l + j];
   if (options.verbosity_level >= 1)
     std::printf("vslam_hip rig BA: %d bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n",
-                (int)rig.n_bodies, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
+                (int)r.rig.n_bodies, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
 }
 
 // Marginal covariances of the map as it stands (vsl_ba_covariance; the reference has no counterpart, Ceres offers it as
@@ -479,6 +512,169 @@ inline int relative_pose_covariance(const Corners& feature_corners, const Global
   return amd::run_relative_pose_covariance<true>("relative_pose_covariance (global)", feature_corners, options.use_huber,
                                                  options.huber_parameter, fixed_cameras, calib_cam, cameras, landmarks, pairs, out,
                                                  storage_out);
+}
+
+// Covariances of the RIG posterior (vsl_ba_rig_covariance / vsl_ba_rig_relative_pose_covariance): what
+// bundle_adjustment_covariance and relative_pose_covariance are to bundle_adjustment, for a map adjusted by
+// bundle_adjustment_rig.  The rules and the flattening are bundle_adjustment_rig's (amd::flatten_rig): bodies are the
+// FrameIds, the body frame is camera 0, a body is fixed if any of its cameras is in fixed_cameras.  Nothing is
+// optimised and nothing is written to the map; the body poses are derived from `cameras` as they stand.
+// query_frames: free frames of `cameras`; query_cameras: cameras of free frames; query_landmarks: ids of `landmarks`
+// (else std::out_of_range; a fixed frame or a camera of one: std::invalid_argument).  body_cov_out: 6 x 6 over the tangent
+// (upsilon, omega) of T_w_b exp(delta); cam_cov_out: the same for the camera's own right perturbation, comparable with
+// bundle_adjustment_covariance; landmark_cov_out: 3 x 3, NaN for a landmark whose own block is singular.  Returns the
+// number of such landmarks; std::domain_error when the reduced body system is singular to working precision or no frame
+// is fixed (VSL_ERR_NUMERIC).
+inline int bundle_adjustment_rig_covariance(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                            const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                            Landmarks& landmarks, const std::vector<FrameId>& query_frames,
+                                            const std::vector<FrameCamId>& query_cameras, const std::vector<TrackId>& query_landmarks,
+                                            std::map<FrameId, PoseCovariance>& body_cov_out,
+                                            std::map<FrameCamId, PoseCovariance>& cam_cov_out,
+                                            std::unordered_map<TrackId, Eigen::Matrix3d>& landmark_cov_out) {
+  const char* what = "bundle_adjustment_rig_covariance";
+  body_cov_out.clear();
+  cam_cov_out.clear();
+  landmark_cov_out.clear();
+  if (&vsl_ba_rig_covariance == nullptr) throw std::runtime_error(std::string(what) + ": this library has no rig covariances");
+  if (query_frames.empty() && query_cameras.empty() && query_landmarks.empty()) return 0;
+  amd::RigFlat r;
+  if (!amd::flatten_rig(what, feature_corners, fixed_cameras, calib_cam, cameras, landmarks, r))
+    throw std::out_of_range(std::string(what) + ": the map has no observation");
+  const amd::BaFlat& f = r.f;
+  std::vector<int32_t> bodies, cams, lms;
+  for (const FrameId id : query_frames) {
+    bodies.push_back(r.body_of(id));
+    if (bodies.back() < 0) throw std::out_of_range(std::string(what) + ": unknown frame");
+    if (r.body_fixed[bodies.back()]) throw std::invalid_argument(std::string(what) + ": a queried frame is fixed");
+  }
+  for (const FrameCamId& id : query_cameras) {
+    const auto it = std::lower_bound(f.cam_id.begin(), f.cam_id.end(), id);
+    if (it == f.cam_id.end() || !(*it == id)) throw std::out_of_range(std::string(what) + ": unknown camera");
+    cams.push_back((int32_t)(it - f.cam_id.begin()));
+    if (r.body_fixed[r.cam_body[cams.back()]]) throw std::invalid_argument(std::string(what) + ": a queried camera's frame is fixed");
+  }
+  if (!query_landmarks.empty()) {
+    std::unordered_map<TrackId, int32_t> index;
+    for (size_t l = 0; l < f.lm_id.size(); l++) index.emplace(f.lm_id[l], (int32_t)l);
+    for (const TrackId id : query_landmarks) lms.push_back(index.at(id));
+  }
+  vsl_ba_options opt;
+  opt.use_huber = options.use_huber ? 1 : 0;
+  opt.huber_parameter = options.huber_parameter;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  std::vector<double> cb(36 * bodies.size()), cc(36 * cams.size()), cl(9 * lms.size());
+  int n_degenerate = 0;
+  const int rc = vsl_ba_rig_covariance(amd::ctx(), &f.prob, &r.rig, &opt, bodies.data(), (int)bodies.size(), cb.data(), cams.data(),
+                                       (int)cams.size(), cc.data(), lms.data(), (int)lms.size(), cl.data(), &n_degenerate);
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
+  amd::check(rc, what);
+  auto block = [](const std::vector<double>& v, size_t q, PoseCovariance& m) {
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) m(i, j) = v[36 * q + 6 * i + j];
+  };
+  for (size_t q = 0; q < bodies.size(); q++) block(cb, q, body_cov_out[query_frames[q]]);
+  for (size_t q = 0; q < cams.size(); q++) block(cc, q, cam_cov_out[query_cameras[q]]);
+  for (size_t q = 0; q < lms.size(); q++) {
+    Eigen::Matrix3d& m = landmark_cov_out[query_landmarks[q]];
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) m(i, j) = cl[9 * q + 3 * i + j];
+  }
+  return n_degenerate;
+}
+
+// relative_pose_covariance for pairs of FRAMES (bodies) of the rig posterior: out[q] as there, measurement =
+// log(T_a^-1 T_b) of the body poses.  Both frames must be frames of `cameras` (else std::out_of_range), a != b, not both
+// fixed (else std::invalid_argument).  Returns the number of singular pairs.
+inline int rig_relative_pose_covariance(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                        const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                        Landmarks& landmarks, const std::vector<std::pair<FrameId, FrameId>>& pairs,
+                                        std::vector<RelativePoseCovariance>& out) {
+  const char* what = "rig_relative_pose_covariance";
+  out.clear();
+  if (&vsl_ba_rig_relative_pose_covariance == nullptr) throw std::runtime_error(std::string(what) + ": this library has no rig covariances");
+  amd::RigFlat r;
+  if (!amd::flatten_rig(what, feature_corners, fixed_cameras, calib_cam, cameras, landmarks, r))
+    throw std::out_of_range(std::string(what) + ": the map has no observation");
+  std::vector<int32_t> a, b;
+  for (const auto& p : pairs) {
+    a.push_back(r.body_of(p.first));
+    b.push_back(r.body_of(p.second));
+    if (a.back() < 0 || b.back() < 0) throw std::out_of_range(std::string(what) + ": unknown frame");
+    if (a.back() == b.back() || (r.body_fixed[a.back()] && r.body_fixed[b.back()]))
+      throw std::invalid_argument(std::string(what) + ": a pair names one frame twice or two fixed frames");
+  }
+  vsl_ba_options opt;
+  opt.use_huber = options.use_huber ? 1 : 0;
+  opt.huber_parameter = options.huber_parameter;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  const size_t n = pairs.size();
+  std::vector<double> meas(6 * n), cov(36 * n), info(36 * n);
+  int n_singular = 0;
+  const int rc = vsl_ba_rig_relative_pose_covariance(amd::ctx(), &r.f.prob, &r.rig, &opt, a.data(), b.data(), (int)n, nullptr, meas.data(),
+                                                     cov.data(), info.data(), &n_singular);
+  if (rc == VSL_ERR_NUMERIC) throw std::domain_error(vsl_last_error(amd::ctx()));
+  amd::check(rc, what);
+  out.resize(n);
+  for (size_t q = 0; q < n; q++) {
+    RelativePoseCovariance& o = out[q];
+    o.valid = true;
+    for (int i = 0; i < 6; i++) {
+      o.measurement[i] = meas[6 * q + i];
+      for (int j = 0; j < 6; j++) {
+        o.cov(i, j) = cov[36 * q + 6 * i + j];
+        o.info(i, j) = info[36 * q + 6 * i + j];
+        if (!(o.info(i, j) == o.info(i, j))) o.valid = false;  // NaN: the singular pair
+      }
+    }
+  }
+  return n_singular;
+}
+
+// The rig counterpart of map_edge_information (loop_closure.h): edge_meas / edge_info of pose-graph edges between
+// keyframes (FrameIds: the graph's nodes are bodies) from a map adjusted in rig form.  The pairs whose two frames are in
+// `cameras`, differ and are not both fixed are queried in ONE call of rig_relative_pose_covariance; every other pair and
+// every singular pair keeps from_map = false, a zero measurement and default_information.
+struct RigEdgeInformation {
+  std::vector<std::array<double, 6>> edge_meas;  // log(T_a^-1 T_b) of the bodies, (upsilon, omega)
+  std::vector<PoseCovariance> edge_info;
+  std::vector<bool> from_map;
+  size_t n_map_edges = 0;
+};
+inline RigEdgeInformation rig_map_edge_information(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                                   const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam,
+                                                   Cameras& cameras, Landmarks& landmarks,
+                                                   const std::vector<std::pair<FrameId, FrameId>>& edges,
+                                                   const PoseCovariance& default_information) {
+  RigEdgeInformation e;
+  e.edge_meas.assign(edges.size(), std::array<double, 6>{{0, 0, 0, 0, 0, 0}});
+  e.edge_info.assign(edges.size(), default_information);
+  e.from_map.assign(edges.size(), false);
+  std::set<FrameId> frames, fixed;
+  for (const auto& kv : cameras) frames.insert(kv.first.frame_id);
+  for (const FrameCamId& id : fixed_cameras) fixed.insert(id.frame_id);
+  std::vector<std::pair<FrameId, FrameId>> pairs;
+  std::vector<size_t> edge_of;
+  for (size_t q = 0; q < edges.size(); q++) {
+    const FrameId a = edges[q].first, b = edges[q].second;
+    if (a == b || !frames.count(a) || !frames.count(b) || (fixed.count(a) && fixed.count(b))) continue;
+    pairs.push_back(edges[q]);
+    edge_of.push_back(q);
+  }
+  if (pairs.empty()) return e;
+  std::vector<RelativePoseCovariance> out;
+  rig_relative_pose_covariance(feature_corners, options, fixed_cameras, calib_cam, cameras, landmarks, pairs, out);
+  for (size_t k = 0; k < pairs.size(); k++) {
+    if (!out[k].valid) continue;
+    const size_t q = edge_of[k];
+    for (int i = 0; i < 6; i++) e.edge_meas[q][i] = out[k].measurement[i];
+    e.edge_info[q] = out[k].info;
+    e.from_map[q] = true;
+    e.n_map_edges++;
+  }
+  return e;
 }
 
 }  // namespace visnav

@@ -58,6 +58,8 @@ namespace harness {
 inline bool ba_covariance_available() { return &vsl_ba_covariance != nullptr; }
 // the rig-constrained local bundle adjustment (OdometryOptions::rig_ba; weak in bundle_adjustment.h)
 inline bool rig_ba_available() { return &vsl_bundle_adjust_rig != nullptr; }
+// ... and its covariances (OdometryOptions::rig_ba_covariance_path; weak in bundle_adjustment.h)
+inline bool rig_ba_covariance_available() { return &vsl_ba_rig_covariance != nullptr; }
 inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
 // the device keyframe database (OdometryOptions::device_place_db) is referenced weakly in the same way (bow.h)
 inline bool device_place_db_available() { return KeyframeDatabaseAmd::available(); }
@@ -120,6 +122,9 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   // the local bundle adjustment optimises ONE pose per stereo keyframe with the calibrated extrinsics held fixed
   // (visnav::bundle_adjustment_rig) instead of two independent cameras.  Off by default: nothing changes without it.
   bool rig_ba = false;
+  // with rig_ba: after every rig local BA one line per free keyframe of the window from the BODY block of the rig
+  // posterior, in the format of ba_covariance_path (empty: off)
+  std::string rig_ba_covariance_path;
   double motion_threshold = 0.5;
   int num_cov_threshold = 10;
   int num_ess_threshold = 30;
@@ -718,6 +723,7 @@ class Odometry {
       if (opt.rig_ba) bundle_adjustment_rig(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt);
       else bundle_adjustment(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt);
       if (!opt.ba_covariance_path.empty()) write_window_covariance(fixed_cameras, ba_options);
+      if (opt.rig_ba && !opt.rig_ba_covariance_path.empty()) write_window_rig_covariance(fixed_cameras, ba_options);
       if (std::getenv("VISNAV_AMD_TRACE_FRAMES")) {
         double h = 0;
         for (const auto& kv : cameras_opt) h += kv.second.T_w_c.data()[4] * 1.7 + kv.second.T_w_c.data()[5];
@@ -753,6 +759,35 @@ class Odometry {
     for (const auto& kv : pose_cov) {
       const PoseCovariance& m = kv.second;
       std::fprintf(f, "%lld %.9g %.9g\n", (long long)kv.first.frame_id, std::sqrt(m(0, 0) + m(1, 1) + m(2, 2)),
+                   std::sqrt(m(3, 3) + m(4, 4) + m(5, 5)));
+    }
+    std::fclose(f);
+  }
+
+  // OdometryOptions::rig_ba_covariance_path: the same lines from the posterior of the rig problem that optimize() has
+  // just solved -- one body per keyframe, the frame's 6 x 6 body block
+  void write_window_rig_covariance(const std::set<FrameCamId>& fixed_cameras, const BundleAdjustmentOptions& ba_options) {
+    std::set<FrameId> fixed_frames, free_frames;
+    for (const FrameCamId& id : fixed_cameras) fixed_frames.insert(id.frame_id);
+    for (const auto& kv : cameras_opt)
+      if (!fixed_frames.count(kv.first.frame_id)) free_frames.insert(kv.first.frame_id);
+    if (free_frames.empty()) return;  // the first keyframe: nothing but the gauge
+    std::map<FrameId, PoseCovariance> body_cov;
+    std::map<FrameCamId, PoseCovariance> cam_cov;
+    std::unordered_map<TrackId, Eigen::Matrix3d> landmark_cov;
+    try {
+      bundle_adjustment_rig_covariance(corners_opt, ba_options, fixed_cameras, calib_cam_opt, cameras_opt, landmarks_opt,
+                                       std::vector<FrameId>(free_frames.begin(), free_frames.end()), {}, {}, body_cov, cam_cov,
+                                       landmark_cov);
+    } catch (const std::domain_error& e) {
+      std::fprintf(stderr, "window rig covariance skipped: %s\n", e.what());
+      return;
+    }
+    FILE* f = std::fopen(opt.rig_ba_covariance_path.c_str(), "a");
+    if (!f) return;
+    for (const auto& kv : body_cov) {
+      const PoseCovariance& m = kv.second;
+      std::fprintf(f, "%lld %.9g %.9g\n", (long long)kv.first, std::sqrt(m(0, 0) + m(1, 1) + m(2, 2)),
                    std::sqrt(m(3, 3) + m(4, 4) + m(5, 5)));
     }
     std::fclose(f);

@@ -654,8 +654,8 @@ int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* prob, const
  * No fixed body (the gauge is free): the hooks return VSL_ERR_NUMERIC without writing anything -- the undamped reduced
  * system is singular by construction --; the solve runs the LM policy on the damped system as for any input, a failed
  * factorisation is an unsuccessful step, and no non-finite value reaches a pose.
- * NOT COVERED: covariances in rig form, rig global bundle adjustment / sessions / multi-GPU, the intrinsics variant,
- * optimising the extrinsics, band / ring / matrix-free routes for the reduced system. */
+ * NOT COVERED: rig global bundle adjustment / sessions / multi-GPU, the intrinsics variant, optimising the extrinsics,
+ * band / ring / matrix-free routes for the reduced system. */
 typedef struct vsl_ba_rig {
   int32_t n_bodies;
   double* body_poses;         /* [7*n_bodies] qx qy qz qw tx ty tz (T_w_b), in/out          */
@@ -678,6 +678,44 @@ int vsl_ba_rig_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_
  * with chol_ok NULL it is VSL_ERR_NUMERIC after the other outputs are written. */
 int vsl_ba_rig_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
                       double inv_radius, double* S, double* rhs, double* scale_b, double* db, double* cost, int* chol_ok);
+
+/* ---- covariances in rig form (visual-slam_amd/csrc/ba_rig.hip "COVARIANCES", csrc/ba_rig_cov_plan.h) ----
+ * The rig counterparts of vsl_ba_covariance and vsl_ba_relative_pose_covariance: the posterior of the problem the rig
+ * solve adjusts, not of the free window.  The problem is a vsl_ba_problem plus a vsl_ba_rig exactly as
+ * vsl_ba_rig_linearize takes them: prob->cam_fixed is ignored, prob->poses is not read, cameras are
+ * T_w_b[cam_body[c]] * T_b_c[cam_intr[c]].  Nothing is optimised.
+ *   H = J^T J over the free bodies (ascending body id, 6 each, tangent (upsilon, omega) of T_w_b exp(delta)) and all
+ *   landmarks, Huber corrector when opt->use_huber, no Jacobi scaling, no damping; Sigma = H^-1 in units of 1 px^2 of
+ *   observation noise.  With S the reduced body system of vsl_ba_rig_linearize, P_l = sum E^T E of landmark l and, for a
+ *   group (landmark l, free body a), W_a = sum F_b^T E over the group's observations:
+ *   body block      Sigma_bb = the 6 x 6 diagonal block of S^-1
+ *   camera block    Sigma_cc = Ad(T_b_c^-1) Sigma_bb Ad(T_b_c^-1)^T, b = cam_body[c], Ad in the (upsilon, omega) order:
+ *                   the covariance of the camera's own right perturbation, comparable with vsl_ba_covariance's block
+ *   landmark block  Sigma_ll = P_l^-1 + P_l^-1 (sum_a sum_a' W_a^T [S^-1]_aa' W_a') P_l^-1 over the landmark's groups;
+ *                   P_l^-1 alone for a landmark that only fixed bodies see.  A landmark seen by both cameras of a body
+ *                   is one group of two observations and contributes one W.
+ *   relative pose   of two bodies: joint [144], meas = log(T_a^-1 T_b) [6], cov = J Sigma_joint J^T [36], info = cov^-1
+ *                   [36]; outputs, symmetry rules, the fixed-member rule and the singular rule are those of
+ *                   vsl_ba_relative_pose_covariance with bodies in place of cameras.
+ * Arguments: bodies / cams / lms list body, camera and landmark ids; duplicates are allowed, counts may be 0 (with all
+ * counts 0 the call validates, launches nothing and returns VSL_OK).  cov_body [36 n_body_q], cov_cam [36 n_cam_q],
+ * cov_point [9 n_lm_q]; *n_degenerate (nullable) counts the degenerate landmark queries.
+ * VSL_ERR_INVALID: anything vsl_ba_rig_linearize rejects; a fixed body, a camera of a fixed body or an id out of range
+ * in a query; a queried landmark with more than 256 groups; the pair rules of vsl_ba_relative_pose_covariance.
+ * VSL_ERR_NUMERIC: no fixed body (before any device work); S not positive definite to working precision (a pivot
+ * L_ii^2 <= 2^-36 S_ii: e.g. the free scale of one camera per body with one fixed body).
+ * A queried landmark whose P_l fails the 2^-44 pivot rule gets nine NaN and is counted; the call returns VSL_OK.
+ * On every error return the stream is drained before the arena loan ends, and no output is written (the counts included).
+ * Bit-level: every block is exactly symmetric; a subset query returns the bits of the same blocks of a full query; two
+ * calls return the same bits; a relative-pose pair's diagonal blocks are the bits vsl_ba_rig_covariance returns for
+ * those bodies; a camera whose extrinsic is exactly the identity returns its body's block.
+ * NOT COVERED: band and selected-inversion routes for rig maps, landmark cross-covariances. */
+int vsl_ba_rig_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                          const int32_t* bodies, int n_body_q, double* cov_body, const int32_t* cams, int n_cam_q,
+                          double* cov_cam, const int32_t* lms, int n_lm_q, double* cov_point, int* n_degenerate);
+int vsl_ba_rig_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig,
+                                        const vsl_ba_options* opt, const int32_t* body_a, const int32_t* body_b, int n_pairs,
+                                        double* joint, double* meas, double* cov, double* info, int* n_singular);
 
 /* The solver behind the reduced camera system, on its own (the place Ceres' SPARSE_SCHUR hands S to a Cholesky,
  * include/visnav/map_utils.h:406-411, loop_closure_utils.h:735): solves S x = b for a symmetric positive definite S

@@ -676,6 +676,42 @@ class Context:
                                           db.ctypes.data_as(f64p), C.byref(cost), C.byref(ok)))
         return dict(S=S, rhs=rhs, scale_b=scale_b, db=db, cost=cost.value, chol_ok=ok.value)
 
+    def ba_rig_covariance(self, arr, rig, bodies=None, cams=None, lms=None, use_huber=True, huber=1.0):
+        """Marginal covariances of the RIG problem at rig's bodies / arr's points (vsl_ba_rig_covariance; nothing is
+        optimised).  bodies: body ids (None: all free bodies), cams: camera ids (None: none), lms: landmark ids (None:
+        none).  Returns (cov_body [n, 6, 6], cov_cam [m, 6, 6], cov_point [k, 3, 3], n_degenerate); a landmark whose own
+        block is singular comes back as NaN and is counted."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        bodies = np.flatnonzero(rig.body_fixed == 0) if bodies is None else bodies
+        bodies = np.ascontiguousarray(bodies, np.int32).reshape(-1)
+        cams = np.ascontiguousarray([] if cams is None else cams, np.int32).reshape(-1)
+        lms = np.ascontiguousarray([] if lms is None else lms, np.int32).reshape(-1)
+        cb, cc, cl = np.zeros((len(bodies), 6, 6)), np.zeros((len(cams), 6, 6)), np.zeros((len(lms), 3, 3))
+        nd = C.c_int(0)
+        self._ck(self.L.vsl_ba_rig_covariance(self.h, C.byref(st), C.byref(rg), C.byref(o), bodies.ctypes.data_as(i32p),
+                                              len(bodies), cb.ctypes.data_as(f64p), cams.ctypes.data_as(i32p), len(cams),
+                                              cc.ctypes.data_as(f64p), lms.ctypes.data_as(i32p), len(lms),
+                                              cl.ctypes.data_as(f64p), C.byref(nd)))
+        return cb, cc, cl, nd.value
+
+    def ba_rig_relative_pose_covariance(self, arr, rig, pairs, use_huber=True, huber=1.0):
+        """ba_relative_pose_covariance for pairs of BODIES of the rig problem (vsl_ba_rig_relative_pose_covariance).
+        pairs: [n, 2] body ids (a, b); one of the two may be fixed.  Returns (joint [n, 12, 12], meas [n, 6], cov
+        [n, 6, 6], info [n, 6, 6], n_singular)."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        n = len(a)
+        joint, meas, cov, info = np.zeros((n, 12, 12)), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6))
+        ns = C.c_int(0)
+        self._ck(self.L.vsl_ba_rig_relative_pose_covariance(self.h, C.byref(st), C.byref(rg), C.byref(o), a.ctypes.data_as(i32p),
+                                                            b.ctypes.data_as(i32p), n, joint.ctypes.data_as(f64p),
+                                                            meas.ctypes.data_as(f64p), cov.ctypes.data_as(f64p),
+                                                            info.ctypes.data_as(f64p), C.byref(ns)))
+        return joint, meas, cov, info, ns.value
+
     def ba_schur_apply(self, arr, x, use_huber=True, huber=1.0):
         """y = S x with the reduced camera system S of ba_linearize, never formed (vsl_ba_schur_apply)."""
         st = self._ba_struct(arr)

@@ -5,7 +5,7 @@
 // libvslam_hip.so; there is no CPU fallback.
 //
 //   slam_headless --dataset-path <dir with cam0/ cam1/ ...> --cam-calib <calib.json>
-//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N] [--ba-covariance FILE] [--rig-ba]
+//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N] [--ba-covariance FILE] [--rig-ba [--rig-ba-covariance FILE]]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -61,6 +61,7 @@ int main(int argc, char** argv) {
     else if (a == "--num-features") opt.num_features_per_image = std::atoi(need("--num-features").c_str());
     else if (a == "--ba-covariance") opt.ba_covariance_path = need("--ba-covariance");  // pose uncertainty of the window after every local BA
     else if (a == "--rig-ba") opt.rig_ba = true;  // local BA with one pose per stereo keyframe (visnav::bundle_adjustment_rig)
+    else if (a == "--rig-ba-covariance") opt.rig_ba_covariance_path = need("--rig-ba-covariance");  // body uncertainty of the window after every rig local BA
     else if (a == "--ba-verbose") opt.ba_verbose = 1;
     else if (a == "--ba-iterations") opt.ba_max_iterations = std::atoi(need("--ba-iterations").c_str());
     else if (a == "--relocalization") opt.enable_relocalization = true;   // the reference's ui.relocalization (default on there)
@@ -123,6 +124,26 @@ int main(int argc, char** argv) {
     FILE* f = std::fopen(opt.ba_covariance_path.c_str(), "w");  // the run appends to an empty file
     if (!f) {
       std::fprintf(stderr, "--ba-covariance: cannot write %s\n", opt.ba_covariance_path.c_str());
+      return 2;
+    }
+    std::fclose(f);
+  }
+  if (!opt.rig_ba_covariance_path.empty()) {
+    if (!opt.rig_ba) {
+      std::fprintf(stderr, "--rig-ba-covariance needs --rig-ba (it writes the posterior of the rig solve)\n");
+      return 2;
+    }
+    if (!rig_ba_covariance_available()) {
+      std::fprintf(stderr, "--rig-ba-covariance: this build's C ABI has no rig covariance entry point (vsl_ba_rig_covariance)\n");
+      return 2;
+    }
+    if (replicas != 1) {
+      std::fprintf(stderr, "--rig-ba-covariance needs --replicas 1 (one writer per file)\n");
+      return 2;
+    }
+    FILE* f = std::fopen(opt.rig_ba_covariance_path.c_str(), "w");  // the run appends to an empty file
+    if (!f) {
+      std::fprintf(stderr, "--rig-ba-covariance: cannot write %s\n", opt.rig_ba_covariance_path.c_str());
       return 2;
     }
     std::fclose(f);
@@ -198,6 +219,7 @@ int main(int argc, char** argv) {
       detectKeypointsAndDescriptors(l.img, kd, opt.num_features_per_image, opt.rotate_features);
       OdometryOptions warm_opt = opt;
       warm_opt.ba_covariance_path.clear();  // the file belongs to the run itself
+      warm_opt.rig_ba_covariance_path.clear();
       Odometry warm(calib, warm_opt);
       warm.orb_voc = o.orb_voc;
       // ... and enough frames (~50 ms of work) for the chip's clock to have ramped up from idle

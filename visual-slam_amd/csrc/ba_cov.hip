@@ -899,10 +899,10 @@ int rel_run(RelCall& c, const vsl_ba_options* opt, BaState& st, std::vector<char
     if ((rc = vsl_cov_inverse_dev(ctx, inv))) return rc;
     if ((rc = vsl_cov_pair_blocks_dev(ctx, n, np, pairs, c.band ? 1 : 0, Zs, st.ldS, X, ok, joint))) return rc;
     // meas, cov = J Sigma J^T and info = cov^-1 of every pair, with the pose graph's functor (pgo_device.h)
-    hipLaunchKernelGGL(ba_relpose_kernel, dim3(np), dim3(64), 0, ctx->stream, np, st.poses, pairs, joint, ok,
-                       (double*)(dev + P.out_off + P.off_meas), (double*)(dev + P.out_off + P.off_cov),
-                       (double*)(dev + P.out_off + P.off_info), (int*)(dev + P.out_off + P.off_sing));
-    VSL_CHECK_LAUNCH(ctx);
+    if ((rc = vsl_ba_relpose_dev(ctx, np, st.poses, pairs, joint, ok, (double*)(dev + P.out_off + P.off_meas),
+                                 (double*)(dev + P.out_off + P.off_cov), (double*)(dev + P.out_off + P.off_info),
+                                 (int*)(dev + P.out_off + P.off_sing))))
+      return rc;
   }
   host_out.assign(P.out_bytes + sizeof(int), 0);
   VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1051,6 +1051,15 @@ int vsl_cov_pair_blocks_dev(vsl_ctx* ctx, int n, int n_pairs, const PgcPairDev* 
   if (n_pairs <= 0) return VSL_OK;
   hipLaunchKernelGGL(ba_pair_blocks_kernel, dim3((144 * n_pairs + 255) / 256), dim3(256), 0, ctx->stream, n, n_pairs, pairs, band, Z,
                      ld, X, ok_dev, out);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_ba_relpose_dev(vsl_ctx* ctx, int n_pairs, const double* poses, const PgcPairDev* pairs, const double* joint,
+                       const int* ok_dev, double* meas, double* cov, double* info, int* singular) {
+  if (n_pairs <= 0) return VSL_OK;
+  hipLaunchKernelGGL(ba_relpose_kernel, dim3(n_pairs), dim3(64), 0, ctx->stream, n_pairs, poses, pairs, joint, ok_dev, meas, cov, info,
+                     singular);
   VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
 }

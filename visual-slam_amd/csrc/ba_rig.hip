@@ -1,6 +1,8 @@
 // ba_rig.hip -- rig-constrained bundle adjustment: ONE SE(3) block per stereo frame (the body), the calibrated
 // extrinsics T_b_c held fixed, T_w_c = T_w_b * T_b_c[cam_intr].  vsl_bundle_adjust_rig, and the two parity hooks
 // vsl_ba_rig_linearize / vsl_ba_rig_system (include/vslam_hip.h "rig-constrained bundle adjustment").
+// The covariances of the rig posterior (vsl_ba_rig_covariance, vsl_ba_rig_relative_pose_covariance) are
+// the section "COVARIANCES" at the end of this file.
 //
 // Residual, camera models, Huber corrector and cost are those of vsl_bundle_adjust (ba_device.h); what changes is the
 // pose block an observation differentiates against.  With T_c_b = T_b_c^-1 = (R, t),
@@ -37,6 +39,8 @@
 #include "dev_arena.h"
 #include "ba_device.h"
 #include "ba_rig_plan.h"
+#include "ba_rig_cov_plan.h"
+#include "pgo_cov_plan.h"
 
 namespace {
 
@@ -527,6 +531,7 @@ struct RigState {
   int *cam_intr = nullptr, *cam_body = nullptr, *cam_slot = nullptr, *body_slot = nullptr, *obs_cam = nullptr, *obs_lm = nullptr;
   int *lm_start = nullptr, *lm_grp = nullptr, *grp_slot = nullptr, *grp_begin = nullptr, *grp_end = nullptr;
   int *bg_start = nullptr, *bg_grp = nullptr, *bg_lm = nullptr, *bo_start = nullptr, *bo_obs = nullptr;
+  char* extra = nullptr;  // the covariance calls' share of the arena (behind everything else: no other offset moves)
 };
 
 int rig_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt,
@@ -547,7 +552,8 @@ int rig_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const v
 }
 
 // plan -> ONE arena (the context's), uploads; synchronises
-int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt, RigState& st) {
+int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt, RigState& st,
+              size_t extra_bytes = 0) {
   const RigPlan& hp = st.plan;
   RigDims& D = st.D;
   D.C = p->n_cams; D.B = rig->n_bodies; D.L = p->n_lms; D.O = p->n_obs; D.G = hp.n_groups();
@@ -586,6 +592,7 @@ int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, cons
   plan.add(st.grp_slot, G); plan.add(st.grp_begin, G); plan.add(st.grp_end, G);
   plan.add(st.bg_start, nf + 1); plan.add(st.bg_grp, G); plan.add(st.bg_lm, G);
   plan.add(st.bo_start, nf + 1); plan.add(st.bo_obs, hp.bo_obs.size());
+  if (extra_bytes) plan.add(st.extra, extra_bytes);
   hipError_t e = st.arena.acquire(ctx, ArenaPolicy::BORROWED, plan);
   if (e != hipSuccess) return vsl_fail(ctx, e == hipErrorOutOfMemory ? VSL_ERR_NOMEM : VSL_ERR_HIP, "rig bundle adjustment: %zu bytes of device memory: %s", plan.total(), hipGetErrorString(e));
   st.flag = (int*)(st.scalars + 16);
@@ -867,5 +874,414 @@ extern "C" int vsl_bundle_adjust_rig(vsl_ctx* ctx, const vsl_ba_problem* prob, c
     fprintf(stderr, "vsl rig BA: %d free bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", D.nfree,
             sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
   if (summary) *summary = sum;
+  return VSL_OK;
+}
+
+// ================================================================================================== COVARIANCES
+// vsl_ba_rig_covariance / vsl_ba_rig_relative_pose_covariance (include/vslam_hip.h "covariances in rig form", DESIGN.md
+// 28): the posterior of the RIG problem, H = J^T J over [free bodies | landmarks], Sigma = H^-1, at the bodies / points
+// handed in.  Nothing is optimised.  The chain, all on the context's stream inside one arena loan:
+//   rig_cams -> rig_linearize -> rig_columns -> rig_schur      the solve's own kernels, unscaled and undamped: the S of
+//                                                              vsl_ba_rig_linearize, bit for bit
+//   vsl_cov_inverse_dev (ba_cov.hip "THE SHARED LAYER")        diag S, vsl_chol_factor_dev, ba_cov_solve_kernel: the six
+//                                                              unit columns of every body of Q (ba_rig_cov_plan.h)
+//   rig_cov_pose_kernel       body block = the diagonal block of X, mirror entries averaged; camera block =
+//                             Ad(T_c_b) Sigma_bb Ad(T_c_b)^T in registers, averaged with its transpose
+//   rig_cov_landmark_kernel   one wavefront per queried landmark: P_l and the per-GROUP W from the stored F_b, E,
+//                             P_l^-1 + P_l^-1 (sum_a sum_a' W_a^T [S^-1]_aa' W_a') P_l^-1
+//   vsl_cov_pair_blocks_dev, vsl_ba_relpose_dev (ba_cov.hip)   joint blocks of body pairs and the pose graph's functor
+//                                                              on the BODY poses
+// No floating-point atomics; every sum in a fixed order: a subset query returns the bits of a full query (a column of X
+// does not depend on its neighbours, ba_cov.hip), two calls return the same bits, and a pair's diagonal blocks are the
+// marginal call's bits (the same average of the same two entries of the same columns).
+#define RIG_COV_LM_TOL 5.6843418860808015e-14  // 2^-44: the pivot rule of ba_cov.hip for P_l
+
+namespace {
+
+// v (upsilon, omega) -> Ad(T_c_b) v, Ad = [[R, [t]x R], [0, R]], T_c_b = (R row-major 9, t 3): the column form of
+// rig_body_jacobian
+__device__ __forceinline__ void rig_adjoint_apply(const double* __restrict__ Rt, const double* v, double* o) {
+  const double* R = Rt;
+  const double tx = Rt[9], ty = Rt[10], tz = Rt[11];
+  double ru[3], rw[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    ru[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
+    rw[i] = R[3 * i] * v[3] + R[3 * i + 1] * v[4] + R[3 * i + 2] * v[5];
+  }
+  o[0] = ru[0] + (ty * rw[2] - tz * rw[1]);
+  o[1] = ru[1] + (tz * rw[0] - tx * rw[2]);
+  o[2] = ru[2] + (tx * rw[1] - ty * rw[0]);
+  o[3] = rw[0];
+  o[4] = rw[1];
+  o[5] = rw[2];
+}
+
+// One thread per pose query (item): body block A = the diagonal block of X at the body's own columns, the two mirror
+// entries averaged (the rule, and so the bits, of ba_cov_pose_kernel and of a pair block's diagonal); item_ext >= 0: the
+// camera block Ad A Ad^T, B = Ad A column by column, M = B Ad^T row by row, (M + M^T) / 2.  With an identity extrinsic
+// (R = I, t = 0 exactly) every product is the entry itself plus zeros: the camera block equals the body block.
+__global__ __launch_bounds__(64) void rig_cov_pose_kernel(int n, int n_items, const int* __restrict__ item_q,
+                                                          const int* __restrict__ item_ext, const int* __restrict__ q_free,
+                                                          const double* __restrict__ X, const double* __restrict__ tcb,
+                                                          const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_items || !*ok) return;
+  const int q = item_q[t], f = q_free[q], ext = item_ext[t];
+  double A[36];
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++)
+      A[6 * a + b] = 0.5 * (X[vsl_cov_x_at(n, 6 * f + a, 6 * q + b)] + X[vsl_cov_x_at(n, 6 * f + b, 6 * q + a)]);
+  double* o = out + 36 * (size_t)t;
+  if (ext < 0) {
+#pragma unroll
+    for (int e = 0; e < 36; e++) o[e] = A[e];
+    return;
+  }
+  const double* Rt = tcb + 12 * ext;
+  double B[36], M[36];
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    double v[6], w[6];
+#pragma unroll
+    for (int r = 0; r < 6; r++) v[r] = A[6 * r + c];
+    rig_adjoint_apply(Rt, v, w);
+#pragma unroll
+    for (int r = 0; r < 6; r++) B[6 * r + c] = w[r];
+  }
+#pragma unroll
+  for (int r = 0; r < 6; r++) {
+    double w[6];
+    rig_adjoint_apply(Rt, B + 6 * r, w);  // row r of B Ad^T = Ad (row r of B)^T
+#pragma unroll
+    for (int c = 0; c < 6; c++) M[6 * r + c] = w[c];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++) o[6 * a + b] = 0.5 * (M[6 * a + b] + M[6 * b + a]);
+}
+
+// One wavefront per unique queried landmark u (landmark l = u_lm[u]).  Its groups are lm_grp[l] .. lm_grp[l + 1] of the
+// rig plan, ascending free-body slot, each with its adjacent observations [grp_begin, grp_end): a landmark seen by both
+// cameras of a body contributes ONE W.  F, E: the stored blocks of the unscaled rig linearisation (Huber corrector
+// applied).  P_l: every lane sums all observations of the landmark in ascending order (fixed bodies first), the order
+// and the bits of rig_lm_groups_kernel; W of group i by lane i mod 64, its observations ascending.  Dynamic LDS only:
+// M [16 doubles] | W [18 K] | T [9 K], K = groups of the landmark (at most RCP_GMAX).
+__global__ __launch_bounds__(64) void rig_cov_landmark_kernel(int n, const int* __restrict__ u_lm, const int* __restrict__ lm_start,
+                                                              const int* __restrict__ lm_grp, const int* __restrict__ grp_slot,
+                                                              const int* __restrict__ grp_begin, const int* __restrict__ grp_end,
+                                                              const double* __restrict__ F, const double* __restrict__ E,
+                                                              const int* __restrict__ qpos, const double* __restrict__ X,
+                                                              const int* __restrict__ ok, double* __restrict__ out,
+                                                              int* __restrict__ degenerate) {
+  extern __shared__ __attribute__((aligned(16))) double rig_cov_sh[];
+  if (!*ok) return;
+  const int u = blockIdx.x, lane = threadIdx.x, l = u_lm[u];
+  const int g0 = lm_grp[l], K = lm_grp[l + 1] - g0;
+  double* M = rig_cov_sh;
+  double* W = rig_cov_sh + 16;
+  double* T = W + 18 * (size_t)K;
+  double P[6] = {0, 0, 0, 0, 0, 0};  // xx xy xz yy yz zz
+  for (int i = lm_start[l]; i < lm_start[l + 1]; i++) {
+    const double* e = E + 6 * (size_t)i;
+    P[0] += e[0] * e[0] + e[3] * e[3];
+    P[1] += e[0] * e[1] + e[3] * e[4];
+    P[2] += e[0] * e[2] + e[3] * e[5];
+    P[3] += e[1] * e[1] + e[4] * e[4];
+    P[4] += e[1] * e[2] + e[4] * e[5];
+    P[5] += e[2] * e[2] + e[5] * e[5];
+  }
+  for (int i = lane; i < K; i += 64) {
+    double w[18];
+#pragma unroll
+    for (int j = 0; j < 18; j++) w[j] = 0.0;
+    for (int k = grp_begin[g0 + i]; k < grp_end[g0 + i]; k++) {
+      const double* f = F + 12 * (size_t)k;
+      const double* e = E + 6 * (size_t)k;
+#pragma unroll
+      for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) w[3 * a + j] += f[a] * e[j] + f[6 + a] * e[3 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 18; j++) W[18 * i + j] = w[j];
+  }
+  // P = L D L^T: positive definite to working precision iff every pivot is a fair share of its diagonal entry
+  const double d0 = P[0];
+  const double l1 = P[1] / d0, l2 = P[2] / d0;
+  const double d1 = P[3] - l1 * P[1];
+  const double m = P[4] - l1 * P[2];
+  const double d2 = P[5] - l2 * P[2] - (m / d1) * m;
+  const double P9[9] = {P[0], P[1], P[2], P[1], P[3], P[4], P[2], P[4], P[5]};
+  double Pi[9];
+  const bool pd = d0 > 0.0 && d1 > RIG_COV_LM_TOL * P[3] && d2 > RIG_COV_LM_TOL * P[5] && isfinite(d0 + d1 + d2) && inv3(P9, Pi);
+  if (!pd) {  // (wave-uniform: every lane holds the same P)
+    if (lane < 9) out[9 * (size_t)u + lane] = __builtin_nan("");
+    if (lane == 0) degenerate[u] = 1;
+    return;
+  }
+  if (lane == 0) degenerate[u] = 0;
+  __syncthreads();
+  // T_i = W_i^T sum_j [S^-1]_{s(i) s(j)} W_j, j ascending
+  for (int i = lane; i < K; i += 64) {
+    const int row = 6 * grp_slot[g0 + i];
+    double Z[18];
+#pragma unroll
+    for (int e = 0; e < 18; e++) Z[e] = 0.0;
+    for (int j = 0; j < K; j++) {
+      const int col = 6 * qpos[grp_slot[g0 + j]];
+      const double* Wj = W + 18 * j;
+#pragma unroll
+      for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+          const double s = X[vsl_cov_x_at(n, row + r, col + b)];
+#pragma unroll
+          for (int y = 0; y < 3; y++) Z[3 * r + y] += s * Wj[3 * b + y];
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < 3; x++)
+#pragma unroll
+      for (int y = 0; y < 3; y++) {
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) s += W[18 * i + 3 * r + x] * Z[3 * r + y];
+        T[9 * i + 3 * x + y] = s;
+      }
+  }
+  __syncthreads();
+  if (lane < 9) {
+    double s = 0.0;
+    for (int i = 0; i < K; i++) s += T[9 * i + lane];  // ascending slot
+    M[lane] = s;
+  }
+  __syncthreads();
+  if (lane < 9) {
+    const int x = lane / 3, y = lane % 3;
+    // Q = P^-1 M P^-1, entries (x, y) and (y, x); the result is symmetrised like the pose blocks
+    double qxy = 0.0, qyx = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        qxy += Pi[3 * x + r] * M[3 * r + c] * Pi[3 * c + y];
+        qyx += Pi[3 * y + r] * M[3 * r + c] * Pi[3 * c + x];
+      }
+    out[9 * (size_t)u + lane] = Pi[3 * x + y] + 0.5 * (qxy + qyx);
+  }
+}
+
+// the S of vsl_ba_rig_linearize in st.S, the stored blocks in st.cur
+int rig_cov_system(vsl_ctx* ctx, RigState& st) {
+  int rc;
+  if ((rc = rig_linearize(ctx, st, st.cur, false, 0))) return rc;
+  if ((rc = rig_columns(ctx, st, st.cur))) return rc;
+  return rig_schur(ctx, st, false, 0.0);
+}
+
+const char* const RIG_NOT_PD = "%s: the reduced body system is not positive definite";
+
+// everything of the marginal call behind the validation; host_in / host_out outlive the stream work (the caller
+// synchronises on an error)
+int rig_cov_run(vsl_ctx* ctx, const char* who, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                RigState& st, const RigCovPlan& P, std::vector<char>& host_in, std::vector<char>& host_out) {
+  int rc;
+  if ((rc = rig_setup(ctx, prob, rig, opt, st, P.total))) return rc;
+  char* dev = st.extra;
+  const int n = st.D.n;
+  host_in.assign(P.in_bytes, 0);
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes) memcpy(host_in.data() + off, src, bytes);
+  };
+  const int one = 1;
+  put(P.off_ok, &one, sizeof(int));
+  put(P.off_col_unk, P.col_unk.data(), sizeof(int) * P.col_unk.size());
+  put(P.off_q_free, P.q_free.data(), sizeof(int) * P.q_free.size());
+  put(P.off_qpos, P.qpos.data(), sizeof(int) * P.qpos.size());
+  put(P.off_item_q, P.item_q.data(), sizeof(int) * P.item_q.size());
+  put(P.off_item_ext, P.item_ext.data(), sizeof(int) * P.item_ext.size());
+  put(P.off_u_lm, P.u_lm.data(), sizeof(int) * P.u_lm.size());
+  VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), P.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  int* ok = (int*)(dev + P.off_ok);
+  double* X = (double*)(dev + P.off_X);
+  if ((rc = rig_cov_system(ctx, st))) return rc;
+  if (P.nQ > 0) {
+    VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+    const VslCovInverse inv{n, 0, 0, st.S, nullptr, (double*)(dev + P.off_Linv), (double*)(dev + P.off_Sdiag),
+                            (const int*)(dev + P.off_col_unk), nullptr, P.nblk, X, ok};
+    if ((rc = vsl_cov_inverse_dev(ctx, inv))) return rc;
+    if (P.n_items > 0) {
+      hipLaunchKernelGGL(rig_cov_pose_kernel, dim3((P.n_items + 63) / 64), dim3(64), 0, ctx->stream, n, P.n_items,
+                         (const int*)(dev + P.off_item_q), (const int*)(dev + P.off_item_ext), (const int*)(dev + P.off_q_free), X,
+                         st.tcb, ok, (double*)(dev + P.out_off + P.off_pose));
+      VSL_CHECK_LAUNCH(ctx);
+    }
+  }
+  if (P.nu > 0) {
+    const size_t lds = sizeof(double) * (16 + 27 * (size_t)std::max(P.gmax, 1));
+    hipLaunchKernelGGL(rig_cov_landmark_kernel, dim3(P.nu), dim3(64), lds, ctx->stream, n, (const int*)(dev + P.off_u_lm),
+                       st.lm_start, st.lm_grp, st.grp_slot, st.grp_begin, st.grp_end, st.cur.F, st.cur.E,
+                       (const int*)(dev + P.off_qpos), X, ok, (double*)(dev + P.out_off + P.off_point),
+                       (int*)(dev + P.out_off + P.off_deg));
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  host_out.assign(P.out_bytes + sizeof(int), 0);
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data() + P.out_bytes, ok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int ok_host;
+  memcpy(&ok_host, host_out.data() + P.out_bytes, sizeof(int));
+  if (!ok_host) return vsl_fail(ctx, VSL_ERR_NUMERIC, RIG_NOT_PD, who);
+  return VSL_OK;
+}
+
+int rig_rel_run(vsl_ctx* ctx, const char* who, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                RigState& st, const BaPairPlan& P, int np, std::vector<char>& host_in, std::vector<char>& host_out) {
+  int rc;
+  if ((rc = rig_setup(ctx, prob, rig, opt, st, P.total))) return rc;
+  const PgcPlan& G = P.G;
+  char* dev = st.extra;
+  const int n = st.D.n;
+  if (G.n != n) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: the set-up and the plan disagree", who);
+  host_in.assign(P.in_bytes, 0);
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes) memcpy(host_in.data() + off, src, bytes);
+  };
+  const int one = 1;
+  put(P.off_ok, &one, sizeof(int));
+  put(P.off_pairs, G.pairs.data(), sizeof(PgcPairDev) * G.pairs.size());
+  put(P.off_col_unk, G.col_unk.data(), sizeof(int) * G.col_unk.size());
+  put(P.off_row_lo, G.row_lo.data(), sizeof(int) * G.row_lo.size());
+  VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), P.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  int* ok = (int*)(dev + P.off_ok);
+  const PgcPairDev* pairs = (const PgcPairDev*)(dev + P.off_pairs);
+  double* X = (double*)(dev + P.off_X);
+  double* joint = (double*)(dev + P.out_off + P.off_joint);
+  if ((rc = rig_cov_system(ctx, st))) return rc;
+  {
+    VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+    const VslCovInverse inv{n, 0, 0, st.S, nullptr, (double*)(dev + P.off_Linv), (double*)(dev + P.off_Sdiag),
+                            (const int*)(dev + P.off_col_unk), nullptr, G.nblk, X, ok};
+    if ((rc = vsl_cov_inverse_dev(ctx, inv))) return rc;
+    if ((rc = vsl_cov_pair_blocks_dev(ctx, n, np, pairs, 0, nullptr, 0, X, ok, joint))) return rc;
+    // the pose graph's functor on the BODY poses (PgcPairDev::na / nb are body ids)
+    if ((rc = vsl_ba_relpose_dev(ctx, np, st.cur.bodies, pairs, joint, ok, (double*)(dev + P.out_off + P.off_meas),
+                                 (double*)(dev + P.out_off + P.off_cov), (double*)(dev + P.out_off + P.off_info),
+                                 (int*)(dev + P.out_off + P.off_sing))))
+      return rc;
+  }
+  host_out.assign(P.out_bytes + sizeof(int), 0);
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data() + P.out_bytes, ok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int ok_host;
+  memcpy(&ok_host, host_out.data() + P.out_bytes, sizeof(int));
+  if (!ok_host) return vsl_fail(ctx, VSL_ERR_NUMERIC, RIG_NOT_PD, who);
+  return VSL_OK;
+}
+
+}  // namespace
+
+extern "C" int vsl_ba_rig_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                                     const int32_t* bodies, int n_body_q, double* cov_body, const int32_t* cams, int n_cam_q,
+                                     double* cov_cam, const int32_t* lms, int n_lm_q, double* cov_point, int* n_degenerate) {
+  const char* who = "vsl_ba_rig_covariance";
+  std::vector<char> host_in, host_out;  // read / written by copies on the stream: they outlive the synchronisation below
+  RigCovPlan P;
+  int rc;
+  {
+    RigState st;  // holds the loan of the context's arena
+    if ((rc = rig_validate(ctx, who, prob, rig, opt, st.plan))) return rc;
+    if ((n_body_q > 0 && !cov_body) || (n_cam_q > 0 && !cov_cam) || (n_lm_q > 0 && !cov_point))
+      return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null output", who);
+    try {
+      const int e = rcp_plan(st.plan, rig->n_bodies, prob->n_cams, prob->n_lms, prob->cam_intr, bodies, n_body_q, cams, n_cam_q, lms,
+                             n_lm_q, P);
+      if (e != RCP_OK) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: %s (%d)", who, rcp_message(e), P.first_bad);
+    } catch (const std::bad_alloc&) {
+      return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    if (st.plan.n_fixed == 0)
+      return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: no fixed body: the gauge is free and the reduced system singular", who);
+    if (n_body_q == 0 && n_cam_q == 0 && n_lm_q == 0) {  // nothing is launched
+      if (n_degenerate) *n_degenerate = 0;
+      return VSL_OK;
+    }
+    VSL_HIP(ctx, hipSetDevice(ctx->device));
+    try {
+      rc = rig_cov_run(ctx, who, prob, rig, opt, st, P, host_in, host_out);
+    } catch (const std::bad_alloc&) {
+      rc = vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    // an error return may leave kernels and copies queued that use the arena and the host buffers: drain the stream
+    // before the loan ends (a later solve on this context gets the same block)
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+  }
+  if (rc) return rc;
+  const double* pose = (const double*)(host_out.data() + P.off_pose);
+  const double* point = (const double*)(host_out.data() + P.off_point);
+  const int* deg = (const int*)(host_out.data() + P.off_deg);
+  if (n_body_q > 0) memcpy(cov_body, pose, 36 * sizeof(double) * (size_t)n_body_q);
+  if (n_cam_q > 0) memcpy(cov_cam, pose + 36 * (size_t)n_body_q, 36 * sizeof(double) * (size_t)n_cam_q);
+  int nd = 0;
+  for (int q = 0; q < n_lm_q; q++) {
+    memcpy(cov_point + 9 * (size_t)q, point + 9 * (size_t)P.lm_q2u[q], 9 * sizeof(double));
+    nd += deg[P.lm_q2u[q]] ? 1 : 0;
+  }
+  if (n_degenerate) *n_degenerate = nd;
+  return VSL_OK;
+}
+
+extern "C" int vsl_ba_rig_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig,
+                                                   const vsl_ba_options* opt, const int32_t* body_a, const int32_t* body_b,
+                                                   int n_pairs, double* joint, double* meas, double* cov, double* info,
+                                                   int* n_singular) {
+  const char* who = "vsl_ba_rig_relative_pose_covariance";
+  std::vector<char> host_in, host_out;
+  BaPairPlan P;
+  int rc;
+  {
+    RigState st;  // holds the loan of the context's arena
+    if ((rc = rig_validate(ctx, who, prob, rig, opt, st.plan))) return rc;
+    if (n_pairs < 0 || (n_pairs > 0 && (!body_a || !body_b))) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null argument or negative count", who);
+    try {
+      int bad = 0;
+      switch (rcp_pair_plan(st.plan, rig->n_bodies, rig->body_fixed, body_a, body_b, n_pairs, P, &bad)) {
+        case PGC_PAIR_RANGE: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d (%d, %d): body out of range", who, bad, body_a[bad], body_b[bad]);
+        case PGC_PAIR_SAME: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d names body %d twice", who, bad, body_a[bad]);
+        case PGC_PAIR_BOTH_FIXED: return vsl_fail(ctx, VSL_ERR_INVALID, "%s: pair %d (%d, %d): both bodies are fixed", who, bad, body_a[bad], body_b[bad]);
+        default: break;
+      }
+    } catch (const std::bad_alloc&) {
+      return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    if (st.plan.n_fixed == 0)
+      return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: no fixed body: the gauge is free and the reduced system singular", who);
+    if (n_pairs == 0 || (!joint && !meas && !cov && !info)) {  // nothing is launched
+      if (n_singular) *n_singular = 0;
+      return VSL_OK;
+    }
+    VSL_HIP(ctx, hipSetDevice(ctx->device));
+    try {
+      rc = rig_rel_run(ctx, who, prob, rig, opt, st, P, n_pairs, host_in, host_out);
+    } catch (const std::bad_alloc&) {
+      rc = vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // as above: drain before the loan ends
+  }
+  if (rc) return rc;
+  const size_t np = (size_t)n_pairs;
+  if (joint) memcpy(joint, host_out.data() + P.off_joint, sizeof(double) * 144 * np);
+  if (meas) memcpy(meas, host_out.data() + P.off_meas, sizeof(double) * 6 * np);
+  if (cov) memcpy(cov, host_out.data() + P.off_cov, sizeof(double) * 36 * np);
+  if (info) memcpy(info, host_out.data() + P.off_info, sizeof(double) * 36 * np);
+  const int* sing = (const int*)(host_out.data() + P.off_sing);
+  int ns = 0;
+  for (size_t q = 0; q < np; q++) ns += sing[q] ? 1 : 0;
+  if (n_singular) *n_singular = ns;
   return VSL_OK;
 }

@@ -295,6 +295,11 @@ int vsl_cov_diag_blocks_dev(vsl_ctx* ctx, int n, int nQ, const int* q_free, int 
 struct PgcPairDev;
 int vsl_cov_pair_blocks_dev(vsl_ctx* ctx, int n, int n_pairs, const PgcPairDev* pairs, int band, const double* Z, int ld,
                             const double* X, const int* ok_dev, double* out);
+// relative poses: ba_relpose_kernel (ba_cov.hip), one wavefront per pair -- meas [6], cov [36], info [36], singular [1]
+// per pair from its joint block; poses: [7 per node] indexed by PgcPairDev::na / nb (cameras of a free problem, bodies of
+// a rig).  Nothing written when *ok_dev = 0.
+int vsl_ba_relpose_dev(vsl_ctx* ctx, int n_pairs, const double* poses, const PgcPairDev* pairs, const double* joint,
+                       const int* ok_dev, double* meas, double* cov, double* info, int* singular);
 __host__ __device__ inline size_t vsl_cov_x_at(int n, int i, int col) {
   return (size_t)(col / 16) * n * 16 + (size_t)i * 16 + (col % 16);
 }
