@@ -623,6 +623,27 @@ int vsl_ba_schur_pcg(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_opti
  * last solve did not take the route.  Pointers are nullable. */
 int vsl_ctx_last_ba_pcg(vsl_ctx* ctx, int64_t* solves, int64_t* iterations_total, int* iterations_last,
                         double* rel_residual_last);
+/* Parity hook of the iterative route, the counterpart of vsl_ba_fused_system: the Jacobi-scaled, damped reduced system
+ * the LM loop's FIRST step solves at the poses / points handed in, through the loop's own code (the recompute form's
+ * init, scale, reduce at radius = 1 / inv_radius, the camera damping, then the PCG with the damped operator).  Works at
+ * every size; inv_radius = 0 is the scaled system without a damping term.  With n = 6 * n_free (every output nullable):
+ *   scale_c  [n] D of the camera unknowns;  rhs [n] the reduced gradient in the scaled variables;  cost as above
+ *   Minv     [36 * n_free] the preconditioner blocks M_c^-1, M_c = the 6 x 6 diagonal block of the damped S'
+ *            (all zeros for a camera whose block has a non-positive pivot)
+ *   x        [n] the solve of S' x = b (b NULL: rhs) stopped at ||r|| <= tol ||b|| or after max_iterations, as the PCG
+ *            left it -- the loop's step is -x --, zeros after a numeric failure
+ *   y        [n] S' v for an input vector v (NULL: no product), by the product the PCG iterates with
+ *   record   status 1 converged / 2 numeric failure / 3 iteration cap, iterations, pivot_fail, ||r||^2, ||b||^2, the last
+ *            alpha and beta, and the host plan's segments per camera and landmark runs
+ * A numeric failure is reported in the record with VSL_OK.  Changes no state of a later solve. */
+typedef struct {
+  int status, iterations, pivot_fail, segments, landmark_runs, n_free;
+  double rr, bb, alpha, beta;
+} vsl_ba_pcg_record;
+int vsl_ba_pcg_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, double inv_radius,
+                      const double* b /* NULL = rhs */, const double* v /* NULL = no product */, double tol, int max_iterations,
+                      double* scale_c, double* rhs, double* cost, double* Minv, double* x, double* y,
+                      vsl_ba_pcg_record* record);
 /* Plain synchronous copy on the context's device (kind 0 host->device, 1 device->host, 2 device->device): for
  * callers that hold device pointers handed out by this library (all-reduce callbacks). */
 int vsl_ctx_memcpy(vsl_ctx* ctx, void* dst, const void* src, size_t bytes, int kind);

@@ -65,6 +65,12 @@ class BaRig(C.Structure):
     _fields_ = [("n_bodies", C.c_int32), ("body_poses", f64p), ("body_fixed", u8p), ("cam_body", i32p), ("T_b_c", f64p)]
 
 
+class BaPcgRecord(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("pivot_fail", C.c_int32), ("segments", C.c_int32),
+                ("landmark_runs", C.c_int32), ("n_free", C.c_int32), ("rr", C.c_double), ("bb", C.c_double),
+                ("alpha", C.c_double), ("beta", C.c_double)]
+
+
 class PgoProblem(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("poses", f64p), ("node_fixed", u8p),
                 ("edge_a", i32p), ("edge_b", i32p), ("edge_meas", f64p)]
@@ -741,6 +747,34 @@ class Context:
                                          C.c_double(float(tol)), C.c_int(4 * n if max_iterations is None else int(max_iterations)),
                                          x.ctypes.data_as(f64p), C.byref(it), C.byref(rel)))
         return x, it.value, rel.value
+
+    def ba_pcg_system(self, arr, inv_radius=0.0, b=None, v=None, tol=1e-8, max_iterations=None, use_huber=True, huber=1.0):
+        """The Jacobi-scaled, damped reduced system of the iterative route's first LM step and one PCG solve on it, by
+        the LM loop's own code (vsl_ba_pcg_system).  b None: the system's rhs; v: a vector for y = S' v (None: no
+        product); max_iterations None: 4 n.  Returns a dict with scale_c, rhs, x, y (None without v) [n], Minv
+        [n_free, 6, 6], cost and the record: status (1 converged, 2 numeric failure, 3 cap), iterations, pivot_fail, rr,
+        bb, alpha, beta, segments (per camera), landmark_runs."""
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        nf = int((arr.cam_fixed == 0).sum())
+        n = 6 * nf
+        vec = {}
+        for name, a in (("b", b), ("v", v)):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64).reshape(-1)
+                if len(a) != n:
+                    raise ValueError("%s has %d entries, the problem %d unknowns" % (name, len(a), n))
+            vec[name] = a
+        scale_c, rhs, x, y, Minv = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((nf, 6, 6))
+        cost, rec = C.c_double(), BaPcgRecord()
+        ptr = lambda a: None if a is None else a.ctypes.data_as(f64p)
+        self._ck(self.L.vsl_ba_pcg_system(self.h, C.byref(st), C.byref(o), C.c_double(float(inv_radius)), ptr(vec["b"]), ptr(vec["v"]),
+                                          C.c_double(float(tol)), C.c_int(4 * n if max_iterations is None else int(max_iterations)),
+                                          ptr(scale_c), ptr(rhs), C.byref(cost), ptr(Minv), ptr(x), ptr(y), C.byref(rec)))
+        assert rec.n_free == nf
+        return dict(scale_c=scale_c, rhs=rhs, cost=cost.value, Minv=Minv, x=x, y=None if v is None else y, status=rec.status,
+                    iterations=rec.iterations, pivot_fail=rec.pivot_fail, rr=rec.rr, bb=rec.bb, alpha=rec.alpha, beta=rec.beta,
+                    segments=rec.segments, landmark_runs=rec.landmark_runs)
 
     def last_ba_pcg(self):
         """(solves, iterations_total, iterations_last, rel_residual_last) of the matrix-free route in the last

@@ -14,7 +14,9 @@
 // enqueued behind the one that finished change nothing -- the solution's bits do not depend on the batch size.
 // Every sum runs in a fixed order (observation order, xor tree inside a wavefront, wavefront / segment / camera-stride
 // order afterwards) and there are no floating-point atomics: two solves return the same bits.
-// The preconditioner is block Jacobi with the TRUE diagonal block of S, M_c = H_c + D_c - sum_{i in c} Z_i Z_i^T,
+// The preconditioner is block Jacobi with the TRUE diagonal block of S,
+//   M_c = H_c + D_c - sum_l (sum_{i in c, l} Z_i)(sum_{i in c, l} Z_i)^T      (i: the observations of landmark l by camera c;
+//                                                                              one per landmark unless c sees l more than once),
 // inverted by a 6 x 6 Cholesky per camera.  A pivot that is not positive sets rec->pivot_fail and leaves M_c^-1 = 0:
 // the solve ends as a numeric failure with x = 0, nothing non-finite is produced.
 #pragma once
@@ -152,7 +154,9 @@ __global__ __launch_bounds__(256) void bpcg_apply_finish_kernel(BpcgOp a, const 
   for (int x = 0; x < 6; x++) y[6 * (size_t)fc + x] = qv[x];
 }
 
-// M_c^-1 (36 doubles, symmetric) of M_c = H_c + D_c - sum_{i in c} Z_i Z_i^T; one workgroup per free camera
+// M_c^-1 (36 doubles, symmetric) of M_c = H_c + D_c - sum_l (sum_{i in c, l} Z_i)(sum_{i in c, l} Z_i)^T: the squares
+// Z_i Z_i^T of every observation, plus the cross terms of a landmark the camera observes more than once; one workgroup
+// per free camera
 __global__ __launch_bounds__(256) void bpcg_precond_kernel(BpcgOp a, double* __restrict__ Minv, BpcgRec* __restrict__ rec) {
   __shared__ double sh[4][21];
   const int fc = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -168,6 +172,21 @@ __global__ __launch_bounds__(256) void bpcg_precond_kernel(BpcgOp a, double* __r
     for (int x = 0; x < 6; x++)
 #pragma unroll
       for (int y = x; y < 6; y++) acc[e++] += z[3 * x] * z[3 * y] + z[3 * x + 1] * z[3 * y + 1] + z[3 * x + 2] * z[3 * y + 2];
+    // a landmark this camera observes more than once: the block of S holds (sum_i Z_i)(sum_i Z_i)^T, so the cross terms
+    // with the earlier observations of the same landmark are added (they are adjacent: the camera's list is in
+    // landmark order).  No trip for a camera that sees every landmark once.
+    const int lm = a.cam_lm[k];
+    for (int j = k - 1; j >= a.cam_start[cam] && a.cam_lm[j] == lm; j--) {
+      double w[18];
+      bpcg_load_z(a.Z, (size_t)j, w);
+      e = 0;
+#pragma unroll
+      for (int x = 0; x < 6; x++)
+#pragma unroll
+        for (int y = x; y < 6; y++)
+          acc[e++] += (z[3 * x] * w[3 * y] + z[3 * x + 1] * w[3 * y + 1] + z[3 * x + 2] * w[3 * y + 2]) +
+                      (w[3 * x] * z[3 * y] + w[3 * x + 1] * z[3 * y + 1] + w[3 * x + 2] * z[3 * y + 2]);
+    }
   }
 #pragma unroll
   for (int e = 0; e < 21; e++) {

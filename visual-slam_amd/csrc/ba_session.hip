@@ -317,19 +317,32 @@ struct RecomputeForm {
 
   // everything is enqueued, nothing is read back here: a failed factorisation leaves flag[1] = 0 and numbers nobody
   // uses (the loop's one read of packC per iteration sees the step as unusable)
-  int step(const double* packB, double radius, int refresh, double* packC) {
+  // the camera damping of a step: S += diag(diag_c / radius) (a stored S only), rhs unpacked from the all-reduced packB
+  int damp(const double* packB, double radius, int refresh) {
     const BaDims& D = st.D;
     if (!in_place && !st.matrix_free)
       VSL_HIP(ctx, hipMemcpyAsync(st.S, packB, sizeof(double) * st.s_elems, hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(sess_damp_kernel, dim3((D.n + 255) / 256), dim3(256), 0, ctx->stream, D.n, st.s_elems, packB, 1.0 / radius,
                        refresh, st.diagc_keep, st.matrix_free ? (double*)nullptr : st.S_eff(), st.ldS, st.rhs, st.flag);  // (sets both flags)
     VSL_CHECK_LAUNCH(ctx);
+    return VSL_OK;
+  }
+
+  // the operator of the damped, Jacobi-scaled system a step solves (after damp()), and the PCG on it
+  BpcgOp pcg_damped_op(double radius) const { return pcg_op(st.diagc_keep, 1.0 / radius); }
+  int pcg_damped(double radius, const double* b, double tol, int max_it, BpcgRec* h) {
+    return pcg_solve(pcg_damped_op(radius), b, tol, max_it, h);
+  }
+
+  int step(const double* packB, double radius, int refresh, double* packC) {
+    const BaDims& D = st.D;
     int e;
+    if ((e = damp(packB, radius, refresh))) return e;
     if (st.matrix_free) {
       // dc = -(S^-1 rhs) by the PCG on the same damped, Jacobi-scaled system (same H, Z, rhs, diagonal); a failed pivot or
       // a breakdown clears flag[1] like a failed factorisation.  The host reads the solve's record once per batch.
       BpcgRec h;
-      if ((e = pcg_solve(pcg_op(st.diagc_keep, 1.0 / radius), st.rhs, ba_pcg_tol_of_exp(ctx->ba_pcg_tol_exp), ba_pcg_cap(D.n), &h))) return e;
+      if ((e = pcg_damped(radius, st.rhs, ba_pcg_tol_of_exp(ctx->ba_pcg_tol_exp), ba_pcg_cap(D.n), &h))) return e;
       hipLaunchKernelGGL(bpcg_finish_kernel, dim3((D.n + 255) / 256), dim3(256), 0, ctx->stream, D.n, rc.pcg_x, rc.pcg_rec, -1.0, st.dc,
                          st.flag + 1);
       VSL_CHECK_LAUNCH(ctx);
@@ -751,5 +764,89 @@ extern "C" int vsl_ba_schur_pcg(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
   if (h.status == BPCG_NUMERIC)
     return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_schur_pcg: %s after %d iterations (S is not positive definite to working precision); x = 0",
                     h.pivot_fail ? "a preconditioner block has a non-positive pivot" : "breakdown (p.Sp <= 0 or a non-finite value)", h.iterations);
+  return VSL_OK;
+}
+
+// Diagnostic hook (include/vslam_hip.h): the damped, Jacobi-scaled system of the LM loop's FIRST step at the point handed
+// in, through the loop's own functions -- RecomputeForm::init, scale, reduce, damp, pcg_damped -- and what the solve
+// leaves behind.  Nothing here is a copy of the loop: a change to those functions changes what this reports.
+extern "C" int vsl_ba_pcg_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, double inv_radius,
+                                 const double* b, const double* v, double tol, int max_iterations, double* scale_c, double* rhs,
+                                 double* cost, double* Minv, double* x, double* y, vsl_ba_pcg_record* record) {
+  int nfree = 0;
+  int rc = mf_check(ctx, prob, opt, "vsl_ba_pcg_system", &nfree);
+  if (rc) return rc;
+  if (!(inv_radius >= 0.0) || !std::isfinite(inv_radius) || !(tol >= 0.0) || max_iterations < 0 || (v && !y))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_pcg_system: 1 / radius = %g, tol = %g or max_iterations = %d out of range, or v without y",
+                    inv_radius, tol, max_iterations);
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  BaState st;
+  BaCaller caller{BaUse::SESSION, nullptr, BL_THREADS, BL_LMW};
+  caller.matrix_free = true;
+  caller.runs_at_any_size = true;
+  if ((rc = ba_setup(ctx, prob, opt, st, caller))) return rc;
+  const int n = st.D.n;
+  const size_t nB = st.s_elems + 3 * (size_t)n + 2;
+  double *bufA, *packB, *gl;
+  ArenaPlan plan(3);
+  plan.add(bufA, (size_t)n + 1);
+  plan.add(packB, nB);
+  plan.add(gl, 1);
+  DevArena arena;
+  if (arena.acquire(ctx, ArenaPolicy::OWNED, plan) != hipSuccess) return vsl_fail(ctx, VSL_ERR_NOMEM, "vsl_ba_pcg_system: device allocation failed");
+  struct Sync {  // (the arenas are freed when this function returns: nothing may still be running on them)
+    vsl_ctx* c;
+    ~Sync() { (void)hipStreamSynchronize(c->stream); }
+  } sync{ctx};
+  RecomputeForm f{ctx, st, st.rc, true};
+  const double radius = 1.0 / inv_radius;  // (inf at inv_radius = 0: every 1 / radius below is 0, no damping term)
+  VSL_HIP(ctx, hipMemsetAsync(gl, 0, 8, ctx->stream));
+  if ((rc = f.prepare())) return rc;
+  if ((rc = f.init(bufA))) return rc;
+  if ((rc = f.scale(bufA))) return rc;
+  if ((rc = f.reduce(radius, packB, gl))) return rc;
+  if ((rc = f.damp(packB, radius, 1))) return rc;
+  const double* rhs_dev = st.rhs;
+  if (b) {
+    VSL_HIP(ctx, hipMemcpyAsync(st.dc, b, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    rhs_dev = st.dc;
+  }
+  BpcgRec h;
+  if ((rc = f.pcg_damped(radius, rhs_dev, tol, max_iterations, &h))) return rc;
+  // x as the solve left it (sign + 1: the loop's step is its negative), zeros after a numeric failure
+  hipLaunchKernelGGL(bpcg_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, (const double*)st.rc.pcg_x,
+                     (const BpcgRec*)st.rc.pcg_rec, 1.0, st.rc.pcg_q, (int*)nullptr);
+  VSL_CHECK_LAUNCH(ctx);
+  auto down = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  };
+  VSL_HIP(ctx, down(x, st.rc.pcg_q, sizeof(double) * n));
+  VSL_HIP(ctx, down(scale_c, st.scale_c, sizeof(double) * n));
+  VSL_HIP(ctx, down(rhs, st.rhs, sizeof(double) * n));
+  VSL_HIP(ctx, down(cost, packB + st.s_elems + 3 * (size_t)n, sizeof(double)));
+  VSL_HIP(ctx, down(Minv, st.rc.pcg_minv, sizeof(double) * 36 * (size_t)nfree));
+  if (v) {
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (x has left pcg_q)
+    VSL_HIP(ctx, hipMemcpyAsync(st.rc.pcg_p, v, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    const BpcgOp a = f.pcg_damped_op(radius);
+    if ((rc = f.pcg_product(a, nullptr, st.rc.pcg_p))) return rc;
+    hipLaunchKernelGGL(bpcg_apply_finish_kernel, dim3((nfree + 255) / 256), dim3(256), 0, ctx->stream, a, (const double*)st.rc.pcg_p,
+                       (const double*)st.rc.pcg_part, st.rc.pcg_q);
+    VSL_CHECK_LAUNCH(ctx);
+    VSL_HIP(ctx, down(y, st.rc.pcg_q, sizeof(double) * n));
+  }
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (record) {
+    record->status = h.status;
+    record->iterations = h.iterations;
+    record->pivot_fail = h.pivot_fail;
+    record->segments = st.rc.bl_seg;
+    record->landmark_runs = st.rc.n_wg;
+    record->n_free = nfree;
+    record->rr = h.rr;
+    record->bb = h.bb;
+    record->alpha = h.alpha;
+    record->beta = h.beta;
+  }
   return VSL_OK;
 }
