@@ -276,3 +276,86 @@ def test_existing_bundle_adjust_bits(ctx, vsl, synth, route):
         h.update(np.ascontiguousarray(a).tobytes())
     print("bundle_adjust %s: sha256 %s" % (route, h.hexdigest()))
     assert h.hexdigest() == PARENT_SHA[route]
+
+
+# ------------------------------------------------------------------------------------------ parent-commit pins (rig)
+# SHA-256 values computed with the library built from the parent commit on an MI355X.  The rig chain now runs on
+# ba.hip's shared kernels and on the one host LM loop of lm_policy.h; the arithmetic and its order are the parent's, so
+# every bit stays.  Each test prints its digest (`pytest -s`).
+def _sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def _solve_digest(ctx, vsl, rp, **kw):
+    arr, rig = _arrays(vsl, rp)
+    s = ctx.bundle_adjust_rig(arr, rig, use_huber=rp.use_huber, huber=rp.huber, **kw)
+    return _sha(rig.body_poses, arr.points, arr.poses, np.array([s.final_cost]), np.array([s.iterations], np.int64)), s
+
+
+def _system_digest(ctx, vsl, rp):
+    arr, rig = _arrays(vsl, rp)
+    out = ctx.ba_rig_system(arr, rig, 1e-4, use_huber=rp.use_huber, huber=rp.huber)
+    return _sha(out["S"], out["rhs"], out["scale_b"], out["db"], np.array([out["cost"]]))
+
+
+_MULTI = []
+
+
+def _multi_segment():
+    """3 bodies x 2 cameras x 600 landmarks, everything seen by everything: 3600 observations, 1200 per body -- three
+    segments per body in the body-block sum, two per block in the Schur gather, 15 observation workgroups, 3 update
+    workgroups.  No long-double reference: a parent-bits pin only."""
+    if not _MULTI:
+        _MULTI.append(ref.rig_scene(3, 1, 600, 509))
+    return _MULTI[0]
+
+
+PARENT_RIG_SOLVE = {"a_base": "748f1a0e6c16c471070bf901e6eba85f5f9d51826999937b3801f6627b0e6894",
+                    "g_huber_outliers": "6ec40faefa184110913a39475362734bbca922c7ad78d40d932e8e1ee632f06c",
+                    "h_23_free": "8498a21a92239697c03edd1ae3239f16b16ecf5569bde47d450c2a8136a8d07f"}
+PARENT_RIG_SYSTEM = {"a_base": "05e12a7cacaf28fc10f40f6977574482e80f71c8226ac345632163d5eaab2c6d",
+                     "h_23_free": "86399a26cf2a8690c6652c404c7853671fd94fb583ecb422d7a09d3237d56f09"}
+PARENT_RIG_MULTI = {"system": "bc0630cca3c0e2097aabd2c3ab363aa7fc2adc3783ef821f4add5e51dac1a85d",
+                    "solve5": "1cd3bbcb1ff8af1799555dc80b0299d6c1b128ba2c943b00084d67ce83cbad45"}
+PARENT_RIG_COV = "5b12b0e8b513573658714f6d32d06221a086cbff4c3b8891641f8bec052f26ca"
+
+
+@pytest.mark.parametrize("name", sorted(PARENT_RIG_SOLVE))
+def test_rig_solve_parent_bits(ctx, vsl, name):
+    d, s = _solve_digest(ctx, vsl, ref.cases()[name])
+    print("bundle_adjust_rig %s: %d iterations, termination %d, sha256 %s" % (name, s.iterations, s.termination, d))
+    assert s.iterations >= 1
+    assert d == PARENT_RIG_SOLVE[name]
+
+
+@pytest.mark.parametrize("name", sorted(PARENT_RIG_SYSTEM))
+def test_rig_system_parent_bits(ctx, vsl, name):
+    d = _system_digest(ctx, vsl, ref.cases()[name])
+    print("ba_rig_system %s 1/radius 1e-4: sha256 %s" % (name, d))
+    assert d == PARENT_RIG_SYSTEM[name]
+
+
+def test_rig_multi_segment_parent_bits(ctx, vsl):
+    rp = _multi_segment()
+    assert len(rp.obs_lm) == 3600 and np.array_equal(np.bincount(rp.cam_body[rp.obs_camera]), [1200, 1200, 1200])
+    d_sys = _system_digest(ctx, vsl, rp)
+    d_solve, s = _solve_digest(ctx, vsl, rp, max_iters=5)
+    print("multi-segment: ba_rig_system sha256 %s; 5-iteration solve (%d iterations, termination %d, cost %.9g -> %.9g) sha256 %s" %
+          (d_sys, s.iterations, s.termination, s.initial_cost, s.final_cost, d_solve))
+    assert s.iterations >= 1
+    assert d_sys == PARENT_RIG_MULTI["system"]
+    assert d_solve == PARENT_RIG_MULTI["solve5"]
+
+
+def test_rig_covariance_parent_bits(ctx, vsl):
+    rp = ref.cases()["a_base"]
+    arr, rig = _arrays(vsl, rp)
+    cams = np.flatnonzero(rp.cam_fixed[rp.cam_body] == 0)                       # (a camera of a fixed body has no block)
+    cb, cc, cl, nd = ctx.ba_rig_covariance(arr, rig, cams=cams, lms=np.arange(len(rp.points)), use_huber=rp.use_huber, huber=rp.huber)
+    d = _sha(cb, cc, cl)
+    print("ba_rig_covariance a_base: %d body, %d camera, %d point blocks, %d degenerate, sha256 %s" % (len(cb), len(cc), len(cl), nd, d))
+    assert len(cb) == rp.n_free and nd == 0
+    assert d == PARENT_RIG_COV

@@ -148,3 +148,100 @@ def test_radius_is_clamped_at_1e16(run):
     radii = [r[1] for r in rows]
     assert radii[24] < 1e16 and all(r == 1e16 for r in radii[25:])
     assert all(abs(radii[k] / (1e4 * 3.0 ** (k + 1)) - 1.0) < 1e-14 for k in range(25))
+
+
+# ------------------------------------------------------------------------------------------ lm_speculative_loop
+# The one host loop of vsl_bundle_adjust and vsl_bundle_adjust_rig on scripted callables.  A script row is what one
+# iteration's enqueue / fetch deliver: (enqueue rc, flag finite, flag factorised, model change, step^2, x^2, candidate
+# cost, candidate max |gradient|).  Expected radii, verdicts and counts are worked out by hand from lm_policy.h's constants.
+def _row(rc=0, finite=1, chol=1, model=50.0, step2=1.0, x2=1.0, cand=50.0, gcand=1.0):
+    return (rc, finite, chol, model, step2, x2, cand, gcand)
+
+
+@pytest.fixture(scope="module")
+def loop(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("lm_loop") / "lm_policy_test"
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Werror", "-I", str(ROOT / "visual-slam_amd" / "csrc"),
+                    str(ROOT / "tests" / "cpp" / "lm_policy_test.cpp"), "-o", str(exe)], check=True)
+
+    def go(max_iterations, cost, gmax, rows):
+        """-> (radii handed to enqueue, settle(accepted) calls, (rc, iterations, termination, successful_steps, final_cost)).
+        A run consumes exactly the rows it enqueues: one left over, or one missing, fails here."""
+        text = "%d %s %s\n" % (max_iterations, float(cost).hex(), float(gmax).hex())
+        text += "".join("%d %d %d %s\n" % (r[0], r[1], r[2], " ".join(float(v).hex() for v in r[3:])) for r in rows)
+        p = subprocess.run([str(exe), "loop"], input=text, capture_output=True, text=True)
+        assert p.returncode == 0, (p.returncode, p.stdout, p.stderr)
+        lines = [ln.split() for ln in p.stdout.splitlines()]
+        assert lines[-1][0] == "end" and all(ln[0] in ("enqueue", "settle") for ln in lines[:-1])
+        radii = [float.fromhex(ln[1]) for ln in lines[:-1] if ln[0] == "enqueue"]
+        assert len(radii) == len(rows)
+        e = lines[-1]
+        return radii, [ln[0][0] + ln[1] for ln in lines[:-1]], (int(e[1]), int(e[2]), int(e[3]), int(e[4]), float.fromhex(e[5]))
+
+    return go
+
+
+def test_loop_accept_reject_accept(loop):
+    # 100 -> 50 over a model change of 50: rho = 1, the radius is divided by max(1/3, 1 - 1) = 1/3.  50 -> 75: rho = -0.5,
+    # rejected, radius / 2; its candidate gradient (0: it would end the solve at the gate) must not be taken.
+    # 50 -> 25 over 50: rho = 0.5, (2 rho - 1)^3 = 0, the radius stays; three iterations allowed, three taken.
+    r1 = 1e4 / (1.0 / 3.0)
+    radii, calls, end = loop(3, 100.0, 1.0, [_row(cand=50.0, gcand=0.5), _row(cand=75.0, gcand=0.0), _row(cand=25.0, gcand=0.25)])
+    assert radii == [1e4, r1, r1 / 2.0]
+    # every iteration: enqueue, then settle; accepted, rejected, accepted
+    assert [c[0] for c in calls] == ["e", "s"] * 3 and calls[1::2] == ["s1", "s0", "s1"]
+    assert end == (0, 3, 0, 2, 25.0)
+
+
+def test_loop_takes_the_accepted_candidates_gradient(loop):
+    # the accepted step's max |gradient| (slot 6) feeds the next gate: 1e-11 <= 1e-10 ends the solve with 2 after one iteration
+    radii, calls, end = loop(9, 100.0, 1.0, [_row(gcand=1e-11)])
+    assert radii == [1e4] and calls[1:] == ["s1"] and end == (0, 1, 2, 1, 50.0)
+
+
+def test_loop_five_invalid_steps_end_with_4(loop):
+    # not finite, not factorised, no model decrease (0, then negative), not finite: each halves the radius, the fifth ends
+    # the solve; every one settles as 'not accepted' (the speculative set is handed back), the cost stays
+    rows = [_row(finite=0), _row(chol=0), _row(model=0.0), _row(model=-1.0), _row(finite=0, chol=0)]
+    radii, calls, end = loop(99, 100.0, 1.0, rows)
+    assert radii == [1e4 / 2 ** k for k in range(5)]
+    assert [c for c in calls if c[0] == "s"] == ["s0"] * 5 and [c[0] for c in calls] == ["e", "s"] * 5
+    assert end == (0, 5, 4, 0, 100.0)
+
+
+def test_loop_gradient_gate_before_any_step(loop):
+    assert loop(9, 100.0, 1e-10, []) == ([], [], (0, 0, 2, 0, 100.0))       # <=: the boundary terminates; nothing is enqueued
+    assert loop(0, 100.0, 1e-10, []) == ([], [], (0, 0, 0, 0, 100.0))       # the iteration cap is tested first
+
+
+def test_loop_iteration_cap(loop):
+    # rho = 0.5 every time: the radius stays at 1e4; two iterations allowed, two taken, termination 0
+    rows = [_row(model=20.0, cand=90.0), _row(model=20.0, cand=80.0)]
+    radii, calls, end = loop(2, 100.0, 1.0, rows)
+    assert radii == [1e4, 1e4] and [c for c in calls if c[0] == "s"] == ["s1", "s1"]
+    assert end == (0, 2, 0, 2, 80.0)
+    assert loop(0, 100.0, 1.0, []) == ([], [], (0, 0, 0, 0, 100.0))
+
+
+def test_loop_function_tolerance(loop):
+    # |cost change| == 1e-6 * cost exactly (test_termination_1_function_tolerance): termination 1, the point is kept
+    cost, change = 1e6, 1.0
+    radii, calls, end = loop(9, cost, 1.0, [_row(model=1.0, cand=cost - change)])
+    assert radii == [1e4] and calls[1:] == ["s0"]
+    assert end == (0, 1, 1, 0, cost)
+
+
+def test_loop_parameter_tolerance_takes_square_roots(loop):
+    # slots 3 / 4 are SQUARED norms: step^2 = (1e-8 (3 + 1e-8))^2 against x^2 = 9 is the boundary of termination 3
+    bound = 1e-8 * (3.0 + 1e-8)
+    assert math.sqrt(bound * bound) == bound and math.sqrt(9.0) == 3.0
+    assert loop(9, 100.0, 1.0, [_row(step2=bound * bound, x2=9.0)])[2] == (0, 1, 3, 0, 100.0)
+
+
+def test_loop_enqueue_error_is_returned_at_once(loop):
+    # the second iteration's enqueue fails with -5: returned as it is, no settle behind it, the result struct untouched
+    # (the driver presets it to -7)
+    radii, calls, end = loop(9, 100.0, 1.0, [_row(), _row(rc=-5)])
+    assert radii == [1e4, 1e4 / (1.0 / 3.0)]
+    assert [c[0] for c in calls] == ["e", "s", "e"] and calls[1] == "s1"
+    assert end == (-5, -7, -7, -7, -7.0)

@@ -24,7 +24,11 @@
 //
 // The host-side state (BaState) and the launchers declared in ba_state.h are shared with ba_session.hip, the session
 // solver behind vsl_global_bundle_adjust (large maps, multi-GPU): its recompute-form kernels are ba_large.h, its
-// stored-blocks form runs the kernels of this file.
+// stored-blocks form runs the kernels of this file.  The rig-constrained solver (ba_rig.hip) runs on them too: every
+// kernel that does not depend on how observations group into pose blocks (linearisation -- a template instantiation
+// applies the rig's adjoint --, reductions, landmark columns, block finish, Jacobi scaling, LM diagonals, model change,
+// update) has ONE launch site here, a plain-pointer launcher (vsl_ba_*_launch, ba_state.h) that both chains call.  The
+// speculative host loop itself is lm_speculative_loop (lm_policy.h), shared with vsl_bundle_adjust_rig.
 //
 // Algorithmic bytes per LM iteration: n_obs*(16 + 8) + n_lms*24 + n_cams*56 + 128 in;
 // (6C)^2*8 + 6C*8 + n_lms*96 out.
@@ -44,7 +48,10 @@ namespace {
 
 // ---------------------------------------------------------------------------------------- kernels
 // K6.  One thread per observation (observations sorted by landmark).  Writes the robustified (and, when
-// scale_c/scale_l are given, Jacobi-scaled) blocks and a per-workgroup cost partial.
+// scale_c/scale_l are given, Jacobi-scaled) blocks and a per-workgroup cost partial.  RIG (ba_rig.hip): `poses` are the
+// camera poses derived from the bodies, cam_free maps a camera to its BODY's slot, and F becomes the block against the
+// body pose, F Ad(T_c_b) with tcb[12 k] the inverse extrinsic of intrinsics block k; RIG = false never reads tcb.
+template <bool RIG>
 __global__ __launch_bounds__(256) void ba_linearize_kernel(BaDims D, const double* __restrict__ poses,
                                                            const double* __restrict__ points,
                                                            const double* __restrict__ intr,
@@ -56,7 +63,8 @@ __global__ __launch_bounds__(256) void ba_linearize_kernel(BaDims D, const doubl
                                                            const double* __restrict__ scale_c,
                                                            const double* __restrict__ scale_l, double* __restrict__ r_out,
                                                            double* __restrict__ F_out, double* __restrict__ E_out,
-                                                           double* __restrict__ partials, int robust) {
+                                                           double* __restrict__ partials, int robust,
+                                                           const double* __restrict__ tcb) {
   __shared__ double sh[256];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double c = 0;
@@ -65,6 +73,7 @@ __global__ __launch_bounds__(256) void ba_linearize_kernel(BaDims D, const doubl
     double r[2], F[12], E[6];
     residual_blocks(k ? D.model1 : D.model0, intr + 8 * k, poses + 7 * cam, points + 3 * lm, obs_uv + 2 * i, r, F, E,
                     true);
+    if (RIG) rig_body_jacobian(tcb + 12 * k, F);
     const double s = r[0] * r[0] + r[1] * r[1];
     double rho0 = s, rho1 = 1.0;
     if (D.use_huber) huber(s, D.huber, rho0, rho1);
@@ -232,10 +241,11 @@ __global__ void ba_apply_scale_kernel(int O, const int* __restrict__ cam_free, c
 
 // gradient max-norm of the UNSCALED problem: |g_scaled / scale|, and LM diagonals
 //   diag = clamp(col norm^2, 1e-6, 1e32) (kept when reuse != 0), D2 = diag / radius
-__global__ void ba_diag_kernel(int nfree, int L, const double* __restrict__ H, const double* __restrict__ n2l,
-                               const double* __restrict__ g_c, const double* __restrict__ grad_l,
-                               const double* __restrict__ scale_c, const double* __restrict__ scale_l,
-                               double* __restrict__ diag_c, double* __restrict__ diag_l, double* __restrict__ gabs) {
+__global__ __launch_bounds__(256) void ba_diag_kernel(int nfree, int L, const double* __restrict__ H, const double* __restrict__ n2l,
+                                                      const double* __restrict__ g_c, const double* __restrict__ grad_l,
+                                                      const double* __restrict__ scale_c, const double* __restrict__ scale_l,
+                                                      double* __restrict__ diag_c, double* __restrict__ diag_l,
+                                                      double* __restrict__ gabs) {
   // gabs[blockIdx.x] = the workgroup's maximum (one 45k-entry max by a single workgroup afterwards cost ~40 us)
   __shared__ double sh[256];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1518,32 +1528,104 @@ int ba_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_options* o, BaS
   return VSL_OK;
 }
 
-int ba_linearize(vsl_ctx* ctx, BaCommon& st, BaStored& sb, bool scaled, int cost_slot) {
-  const BaDims& D = st.D;
-  {
-    VslStage s(ctx, VSL_STAGE_BA_LIN);
-    hipLaunchKernelGGL(ba_linearize_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr,
-                       st.cam_intr, st.cam_free, st.obs_cam, st.obs_lm, st.obs_uv, scaled ? st.scale_c : nullptr,
-                       scaled ? st.scale_l : nullptr, sb.r, sb.F, sb.E, sb.partials, 1);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, cost_slot, 0);
-    VSL_CHECK_LAUNCH(ctx);
-  }
+// ---- the plain-pointer launchers of ba_state.h: the ONE launch site of each of these kernels.  The BaCommon launchers
+// below, the host loop and the intrinsics solver go through them, and so does the rig chain of ba_rig.hip.
+int vsl_ba_linearize_launch(vsl_ctx* ctx, const BaDims& D, const double* poses, const double* points, const double* intr,
+                            const double* tcb, const int* cam_intr, const int* cam_free, const int* obs_cam, const int* obs_lm,
+                            const double* obs_uv, const double* scale_c, const double* scale_l, double* r, double* F, double* E,
+                            double* partials) {
+  const dim3 grid((D.O + 255) / 256);
+  if (tcb)
+    hipLaunchKernelGGL(ba_linearize_kernel<true>, grid, dim3(256), 0, ctx->stream, D, poses, points, intr, cam_intr, cam_free, obs_cam,
+                       obs_lm, obs_uv, scale_c, scale_l, r, F, E, partials, 1, tcb);
+  else
+    hipLaunchKernelGGL(ba_linearize_kernel<false>, grid, dim3(256), 0, ctx->stream, D, poses, points, intr, cam_intr, cam_free, obs_cam,
+                       obs_lm, obs_uv, scale_c, scale_l, r, F, E, partials, 1, (const double*)nullptr);
+  VSL_CHECK_LAUNCH(ctx);
   return VSL_OK;
+}
+
+int vsl_ba_reduce_launch(vsl_ctx* ctx, const double* partials, int n, double* scalars, int slot, bool is_max) {
+  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, partials, n, scalars, slot, is_max ? 1 : 0);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_ba_reduce2_launch(vsl_ctx* ctx, const double* partials, int n, double* scalars, int slot) {
+  hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, partials, n, scalars, slot);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_ba_lm_cols_launch(vsl_ctx* ctx, int L, const int* lm_start, const double* r, const double* E, double* n2l, double* grad_l) {
+  BaDims D{};
+  D.L = L;  // all the kernel reads
+  hipLaunchKernelGGL(ba_lm_cols_kernel, dim3((L + 255) / 256), dim3(256), 0, ctx->stream, D, lm_start, r, E, n2l, grad_l);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_ba_block_finish_launch(vsl_ctx* ctx, int nfree, int nseg, const double* part, double* H, double* g) {
+  hipLaunchKernelGGL(ba_cam_block_finish_kernel, dim3((nfree * 27 + 255) / 256), dim3(256), 0, ctx->stream, nfree, nseg, part, H, g);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_ba_make_scale_launch(vsl_ctx* ctx, int nfree, int L, const double* H, const double* n2l, double* scale_c, double* scale_l) {
+  hipLaunchKernelGGL(ba_make_scale_kernel, dim3((std::max(6 * nfree, 3 * L) + 255) / 256), dim3(256), 0, ctx->stream, nfree, L, H, n2l,
+                     scale_c, scale_l);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_ba_diag_gmax_launch(vsl_ctx* ctx, int nfree, int L, const double* H, const double* n2l, const double* g_c, const double* grad_l,
+                            const double* scale_c, const double* scale_l, double* diag_c, double* diag_l, double* gabs,
+                            double* scalars, int slot) {
+  const int nb = (std::max(6 * nfree, 3 * L) + 255) / 256;
+  hipLaunchKernelGGL(ba_diag_kernel, dim3(nb), dim3(256), 0, ctx->stream, nfree, L, H, n2l, g_c, grad_l, scale_c, scale_l, diag_c,
+                     diag_l, gabs);
+  return vsl_ba_reduce_launch(ctx, gabs, nb, scalars, slot, true);
+}
+
+int vsl_ba_model_launch(vsl_ctx* ctx, int O, const int* obs_cam, const int* obs_lm, const int* cam_free, const double* r,
+                        const double* F, const double* E, const double* dc, const double* dl, double* partials) {
+  BaDims D{};
+  D.O = O;  // all the kernel reads
+  hipLaunchKernelGGL(ba_model_kernel, dim3((O + 255) / 256), dim3(256), 0, ctx->stream, D, obs_cam, obs_lm, cam_free, r, F, E, dc, dl,
+                     partials);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int vsl_ba_update_launch(vsl_ctx* ctx, int n_poses, int L, const int* pose_free, const double* poses, const double* points,
+                         const double* dc, const double* dl, const double* scale_c, const double* scale_l, double* cand_poses,
+                         double* cand_points, double* partials, double* scalars, int slot) {
+  BaDims D{};
+  D.C = n_poses;  // the kernel reads the two counts
+  D.L = L;
+  const int nb = (std::max(n_poses, L) + 255) / 256;
+  hipLaunchKernelGGL(ba_update_kernel, dim3(nb), dim3(256), 0, ctx->stream, D, pose_free, poses, points, dc, dl, scale_c, scale_l,
+                     cand_poses, cand_points, partials, nb);
+  return vsl_ba_reduce2_launch(ctx, partials, nb, scalars, slot);
+}
+
+int ba_linearize(vsl_ctx* ctx, BaCommon& st, BaStored& sb, bool scaled, int cost_slot) {
+  VslStage s(ctx, VSL_STAGE_BA_LIN);
+  int rc = vsl_ba_linearize_launch(ctx, st.D, st.poses, st.points, st.intr, nullptr, st.cam_intr, st.cam_free, st.obs_cam, st.obs_lm,
+                                   st.obs_uv, scaled ? st.scale_c : nullptr, scaled ? st.scale_l : nullptr, sb.r, sb.F, sb.E,
+                                   sb.partials);
+  if (rc) return rc;
+  return vsl_ba_reduce_launch(ctx, sb.partials, st.nb_obs, st.scalars, cost_slot, false);
 }
 
 int ba_columns(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
   const BaDims& D = st.D;
   VslStage s(ctx, VSL_STAGE_BA_LIN);
-  hipLaunchKernelGGL(ba_lm_cols_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, sb.r, sb.E, st.n2l,
-                     sb.grad_l);
-  if (D.nfree > 0) {
-    hipLaunchKernelGGL(ba_cam_block_kernel, dim3(D.nfree, st.cb_seg), dim3(256), 0, ctx->stream, st.free_cams, st.cam_start,
-                       st.cam_obs, sb.r, sb.F, st.cam_part);
-    hipLaunchKernelGGL(ba_cam_block_finish_kernel, dim3((D.nfree * 27 + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, st.cb_seg,
-                       st.cam_part, st.H, st.g_c);
-  }
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
+  int rc = vsl_ba_lm_cols_launch(ctx, D.L, st.lm_start, sb.r, sb.E, st.n2l, sb.grad_l);
+  if (rc || D.nfree == 0) return rc;
+  hipLaunchKernelGGL(ba_cam_block_kernel, dim3(D.nfree, st.cb_seg), dim3(256), 0, ctx->stream, st.free_cams, st.cam_start, st.cam_obs,
+                     sb.r, sb.F, st.cam_part);
+  return vsl_ba_block_finish_launch(ctx, D.nfree, st.cb_seg, st.cam_part, st.H, st.g_c);
 }
 
 // workgroups of ba_schur_gather_kernel: one per slot; in band form eight equal row ranges (see the kernel)
@@ -1646,14 +1728,11 @@ int ba_step_from_dc(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
   const BaDims& D = st.D;
   hipLaunchKernelGGL(ba_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, ctx->stream, D, st.lm_start, st.obs_cam,
                      st.cam_free, sb.F, sb.E, st.Pinv, st.bl, st.dc, sb.dl, st.flag);
-  hipLaunchKernelGGL(ba_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.obs_cam, st.obs_lm, st.cam_free, sb.r,
-                     sb.F, sb.E, st.dc, sb.dl, sb.partials);
-  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 2, 0);
-  hipLaunchKernelGGL(ba_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, D, st.cam_free, st.poses, st.points, st.dc,
-                     sb.dl, st.scale_c, st.scale_l, st.cand_poses, st.cand_points, sb.partials, st.nb_upd);
-  hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, sb.partials, st.nb_upd, st.scalars, 3);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
+  int rc = vsl_ba_model_launch(ctx, D.O, st.obs_cam, st.obs_lm, st.cam_free, sb.r, sb.F, sb.E, st.dc, sb.dl, sb.partials);
+  if (rc) return rc;
+  if ((rc = vsl_ba_reduce_launch(ctx, sb.partials, st.nb_obs, st.scalars, 2, false))) return rc;
+  return vsl_ba_update_launch(ctx, D.C, D.L, st.cam_free, st.poses, st.points, st.dc, sb.dl, st.scale_c, st.scale_l, st.cand_poses,
+                              st.cand_points, sb.partials, st.scalars, 3);
 }
 
 int read_scalars(vsl_ctx* ctx, BaCommon& st, double* out, int n) {
@@ -1704,11 +1783,7 @@ int ba_schur_gather(vsl_ctx* ctx, BaCommon& st, const double* W, const double* Y
   return VSL_OK;
 }
 
-int ba_max_of(vsl_ctx* ctx, const double* v, int n, double* dst) {
-  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, v, n, dst, 0, 1);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
-}
+int ba_max_of(vsl_ctx* ctx, const double* v, int n, double* dst) { return vsl_ba_reduce_launch(ctx, v, n, dst, 0, true); }
 
 int ba_candidate(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
   const BaDims& D = st.D;
@@ -1718,9 +1793,7 @@ int ba_candidate(vsl_ctx* ctx, BaCommon& st, BaStored& sb) {
                      st.scalars);
   hipLaunchKernelGGL(ba_cost_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.cand_poses, st.cand_points, st.intr,
                      st.cam_intr, st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, sb.partials);
-  hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, st.nb_obs, st.scalars, 5, 0);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
+  return vsl_ba_reduce_launch(ctx, sb.partials, st.nb_obs, st.scalars, 5, false);
 }
 
 int vsl_ba_chol_small_launch(vsl_ctx* ctx, int n, const double* S, const double* rhs, double* dc, int* ok_flag) {
@@ -1795,8 +1868,7 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
     if (nb > 0)
       hipLaunchKernelGGL(ba_cost_kernel, dim3(nb), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr, st.cam_intr,
                          st.obs_cam, st.obs_lm, st.obs_uv, (int)o0, oc, sb.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.partials, nb, st.scalars, 0, 0);
-    VSL_CHECK_LAUNCH(ctx);
+    if ((rc = vsl_ba_reduce_launch(ctx, sb.partials, nb, st.scalars, 0, false))) return rc;
   }
   if ((rc = ba_columns(ctx, st, sb))) return rc;
   if ((rc = ba_schur(ctx, st, sb, false, 1.0, l0, lc, false, false))) return rc;
@@ -1808,6 +1880,119 @@ extern "C" int vsl_ba_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const 
     VSL_HIP(ctx, hipMemcpy(S, st.S, sizeof(double) * (size_t)D.n * D.n, hipMemcpyDeviceToHost));
     VSL_HIP(ctx, hipMemcpy(g, st.rhs, sizeof(double) * D.n, hipMemcpyDeviceToHost));
   }
+  return VSL_OK;
+}
+
+// ---- what the two speculative host loops (vsl_bundle_adjust below, vsl_bundle_adjust_rig in ba_rig.hip) share besides
+// lm_speculative_loop: the one copy per iteration and the summary's tail
+int ba_fetch_step(vsl_ctx* ctx, const double* scalars, double* sc16, int* flags2) {
+  void* hp = nullptr;
+  int rc = vsl_ctx_hpinned(ctx, 256, &hp);
+  if (rc) return rc;
+  VSL_HIP(ctx, hipMemcpyAsync(hp, scalars, 16 * sizeof(double) + 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(sc16, hp, 16 * sizeof(double));
+  memcpy(flags2, (const char*)hp + 16 * sizeof(double), 2 * sizeof(int));
+  return VSL_OK;
+}
+
+// per-stage device times (summary.linearize_ms / schur_ms / solve_ms) only when the context has profiling switched
+// on (vsl_ctx_set_profiling): the HIP events around every stage cost ~60 us per LM iteration of a local window
+// (0.36 -> 0.30 ms per iteration), so a plain call goes without them
+BaSolveTimes::BaSolveTimes(vsl_ctx* ctx, double t_start_ms) : t_start(t_start_ms), prof_was(ctx->profiling) {
+  for (int k = 0; k < 3; k++) base_ms[k] = ctx->stage_ms[VSL_STAGE_BA_LIN + k];
+}
+
+void ba_finish_summary(vsl_ctx* ctx, const BaSolveTimes& t, int verbosity, const char* label, vsl_ba_summary& sum,
+                       vsl_ba_summary* out) {
+  double ms;
+  int64_t cnt;
+  vsl_ctx_stage_ms(ctx, VSL_STAGE_BA_LIN, &ms, &cnt);
+  sum.linearize_ms = ctx->stage_ms[VSL_STAGE_BA_LIN] - t.base_ms[0];
+  sum.schur_ms = ctx->stage_ms[VSL_STAGE_BA_SCHUR] - t.base_ms[1];
+  sum.solve_ms = ctx->stage_ms[VSL_STAGE_BA_SOLVE] - t.base_ms[2];
+  vsl_ctx_set_profiling(ctx, t.prof_was ? 1 : 0);
+  sum.total_ms = now_ms() - t.t_start;
+  if (verbosity >= 1)
+    fprintf(stderr, "%s iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", label, sum.iterations,
+            sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
+  if (out) *out = sum;
+}
+
+// vsl_bundle_adjust behind the set-up: the speculative host loop (lm_policy.h) on the stored-blocks chain
+static int ba_host_loop_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, BaState& st, bool no_fused,
+                              double t_start, vsl_ba_summary* summary) {
+  int rc;
+  BaStored& sb = st.sb;
+  const BaDims& D = st.D;
+  const int nc = D.n;
+  // A window without a free camera (the application's first keyframe).  [upstream] Ceres moves the landmarks alone, and
+  // so do this loop under "ba_no_fused" and the session.  The DEFAULT path never has: ba_schur used to return before P^-1
+  // and b existed, every step came out invalid and the landmarks stayed (termination 4).  The application's trajectories
+  // rest on that, so the default path keeps it -- now with zeroed blocks instead of unwritten ones -- until it is changed
+  // on purpose (DESIGN.md section 6).
+  const bool hold_landmarks = nc == 0 && !no_fused;
+  if (hold_landmarks) {
+    VSL_HIP(ctx, hipMemsetAsync(st.Pinv, 0, sizeof(double) * 9 * (size_t)D.L, ctx->stream));
+    VSL_HIP(ctx, hipMemsetAsync(st.bl, 0, sizeof(double) * 3 * (size_t)D.L, ctx->stream));
+  }
+  vsl_ba_summary sum;
+  memset(&sum, 0, sizeof(sum));
+  const BaSolveTimes times(ctx, t_start);
+
+  // iteration 0: evaluate, Jacobi scaling from the unscaled Jacobian, then scale it
+  if ((rc = ba_linearize(ctx, st, sb, false))) return rc;
+  if ((rc = ba_columns(ctx, st, sb))) return rc;
+  if ((rc = vsl_ba_make_scale_launch(ctx, D.nfree, D.L, st.H, st.n2l, st.scale_c, st.scale_l))) return rc;
+  if ((rc = ba_apply_scale(ctx, st, sb))) return rc;
+  if ((rc = ba_columns(ctx, st, sb))) return rc;
+
+  auto diag_and_gmax = [&](int slot) -> int {
+    return vsl_ba_diag_gmax_launch(ctx, D.nfree, D.L, st.H, st.n2l, st.g_c, sb.grad_l, st.scale_c, st.scale_l, sb.diag_c, sb.diag_l,
+                                   sb.gabs, st.scalars, slot);
+  };
+  if ((rc = diag_and_gmax(1))) return rc;
+  double sc[2];
+  if ((rc = read_scalars(ctx, st, sc, 2))) return rc;
+  sum.initial_cost = sc[0];
+
+  // One host round trip per LM iteration (lm_speculative_loop, lm_policy.h): the whole iteration is enqueued without
+  // waiting -- Schur, Cholesky, back-substitution, model / step norms, candidate parameters AND the linearisation at the
+  // candidate (into the second set of blocks: its cost is the candidate's cost, and if the step is accepted it is the
+  // next iteration's linearisation already) -- then ONE copy brings back [Cholesky ok, finite] + 7 scalars and the host
+  // applies the [upstream] Ceres step policy.  A rejected or invalid step swaps the sets back; its speculative work
+  // (~60 us of device time) is the price.  (The first version synchronised three times per iteration: after the
+  // Cholesky, after the candidate cost, after the re-linearisation.)
+  auto enqueue = [&](double radius) -> int {
+    int e;
+    if ((e = ba_schur(ctx, st, sb, true, radius, 0, D.L, !hold_landmarks, true))) return e;
+    if ((e = ba_solve_enqueue(ctx, st))) return e;  // flag[1] = Cholesky ok
+    {
+      VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+      if ((e = ba_step_from_dc(ctx, st, sb))) return e;
+    }
+    // speculative: the candidate becomes the current point, its linearisation goes to the other set;
+    // scalars[5] = cost there, scalars[6] = max |gradient| there (slots 0/1 keep the current point's values)
+    st.swap_sets();
+    if ((e = ba_linearize(ctx, st, sb, true, 5))) return e;
+    if ((e = ba_columns(ctx, st, sb))) return e;
+    return diag_and_gmax(6);
+  };
+  auto fetch = [&](double* s16, int* flags) -> int { return ba_fetch_step(ctx, st.scalars, s16, flags); };
+  // (accepted: the sets stay swapped, the speculative linearisation is the current one)
+  auto settle = [&](bool accepted) {
+    if (!accepted) st.swap_sets();
+  };
+  LmLoopResult lm;
+  if ((rc = lm_speculative_loop(opt->max_num_iterations, opt->verbosity, sc[0], sc[1], enqueue, fetch, settle, &lm))) return rc;
+  sum.iterations = lm.iterations;
+  sum.successful_steps = lm.successful_steps;
+  sum.termination = lm.termination;
+  sum.final_cost = lm.final_cost;
+  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.poses, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ba_finish_summary(ctx, times, opt->verbosity, "vsl BA:", sum, summary);
   return VSL_OK;
 }
 
@@ -1828,7 +2013,7 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     // Large maps (more free cameras than the fused window takes: the reduced system goes through the pair-list gather
     // and the band solver): the session solver at world size 1 -- the recompute-form iteration of ba_large.h, the cyclic
     // band form, one host round trip per iteration -- the same LM policy on the same numbers
-    // (tests/test_ba_dist_gpu.py::test_session_world1_matches_single_call_and_oracle).  What follows below remains for
+    // (tests/test_ba_dist_gpu.py::test_session_world1_matches_single_call_and_oracle).  ba_host_loop_solve remains for
     // mid-size windows the fused kernels decline (more than 64 cameras, a landmark seen more than 64 times), for
     // "ba_no_fused" and as the cross-check of both.
     int nfree = 0;
@@ -1836,126 +2021,13 @@ extern "C" int vsl_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     if (6 * nfree > 128) return vsl_global_bundle_adjust(ctx, prob, opt, nullptr, nullptr, 0, 1, summary);
   }
   const double t_start = now_ms();
-  BaState st;
+  BaState st;  // holds the loan of the context's arena
   if ((rc = ba_setup(ctx, prob, opt, st, BaCaller{BaUse::HOST_LOOP}))) return rc;
-  BaStored& sb = st.sb;
-  const BaDims& D = st.D;
-  const int nc = D.n, nl = 3 * D.L;
-  // A window without a free camera (the application's first keyframe).  [upstream] Ceres moves the landmarks alone, and
-  // so do this loop under "ba_no_fused" and the session.  The DEFAULT path never has: ba_schur used to return before P^-1
-  // and b existed, every step came out invalid and the landmarks stayed (termination 4).  The application's trajectories
-  // rest on that, so the default path keeps it -- now with zeroed blocks instead of unwritten ones -- until it is changed
-  // on purpose (DESIGN.md section 6).
-  const bool hold_landmarks = nc == 0 && !no_fused;
-  if (hold_landmarks) {
-    VSL_HIP(ctx, hipMemsetAsync(st.Pinv, 0, sizeof(double) * 9 * (size_t)D.L, ctx->stream));
-    VSL_HIP(ctx, hipMemsetAsync(st.bl, 0, sizeof(double) * 3 * (size_t)D.L, ctx->stream));
-  }
-  vsl_ba_summary sum;
-  memset(&sum, 0, sizeof(sum));
-  // per-stage device times (summary.linearize_ms / schur_ms / solve_ms) only when the context has profiling switched
-  // on (vsl_ctx_set_profiling): the HIP events around every stage cost ~60 us per LM iteration of a local window
-  // (0.36 -> 0.30 ms per iteration), so a plain call goes without them
-  const bool prof_was = ctx->profiling;
-  double base_ms[3];
-  for (int k = 0; k < 3; k++) base_ms[k] = ctx->stage_ms[VSL_STAGE_BA_LIN + k];
-
-  double sc[8];
-  // iteration 0: evaluate, Jacobi scaling from the unscaled Jacobian, then scale it
-  if ((rc = ba_linearize(ctx, st, sb, false))) return rc;
-  if ((rc = ba_columns(ctx, st, sb))) return rc;
-  const int nmax = std::max(nc, nl);
-  hipLaunchKernelGGL(ba_make_scale_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, st.H, st.n2l,
-                     st.scale_c, st.scale_l);
-  hipLaunchKernelGGL(ba_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D.O, st.cam_free, st.obs_cam, st.obs_lm,
-                     st.scale_c, st.scale_l, sb.F, sb.E);
-  VSL_CHECK_LAUNCH(ctx);
-  if ((rc = ba_columns(ctx, st, sb))) return rc;
-
-  auto diag_and_gmax = [&](int slot) -> int {
-    hipLaunchKernelGGL(ba_diag_kernel, dim3((nmax + 255) / 256), dim3(256), 0, ctx->stream, D.nfree, D.L, st.H, st.n2l, st.g_c,
-                       sb.grad_l, st.scale_c, st.scale_l, sb.diag_c, sb.diag_l, sb.gabs);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, sb.gabs, (nmax + 255) / 256, st.scalars, slot, 1);
-    VSL_CHECK_LAUNCH(ctx);
-    return VSL_OK;
-  };
-  if ((rc = diag_and_gmax(1))) return rc;
-  if ((rc = read_scalars(ctx, st, sc, 2))) return rc;
-  double cost = sc[0], gmax = sc[1];
-  sum.initial_cost = cost;
-
-  LmState lm;
-  int iteration = 0, term;
-  sum.termination = 0;
-  if (opt->verbosity >= 2) lm_print_header(cost);
-  // One host round trip per LM iteration: the whole iteration is enqueued without waiting -- Schur, Cholesky,
-  // back-substitution, model / step norms, candidate parameters AND the linearisation at the candidate (into the
-  // second set of blocks: its cost is the candidate's cost, and if the step is accepted it is the next iteration's
-  // linearisation already) -- then ONE copy brings back [Cholesky ok, finite] + 7 scalars and the host applies the
-  // [upstream] Ceres step policy (lm_policy.h).  A rejected or invalid step swaps the sets back; its speculative work (~60 us of
-  // device time) is the price.  (The first version synchronised three times per iteration: after the Cholesky, after
-  // the candidate cost, after the re-linearisation.)
-  double* hsc = nullptr;
-  {
-    void* hp = nullptr;
-    if ((rc = vsl_ctx_hpinned(ctx, 256, &hp))) return rc;
-    hsc = (double*)hp;
-  }
-  const int* hflag = (const int*)(hsc + 16);
-  while (true) {
-    if (iteration >= opt->max_num_iterations) { sum.termination = 0; break; }
-    if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
-    iteration++;
-    if ((rc = ba_schur(ctx, st, sb, true, lm.radius, 0, D.L, !hold_landmarks, true))) return rc;
-    if ((rc = ba_solve_enqueue(ctx, st))) return rc;  // flag[1] = Cholesky ok
-    {
-      VslStage s(ctx, VSL_STAGE_BA_SOLVE);
-      if ((rc = ba_step_from_dc(ctx, st, sb))) return rc;
-    }
-    // speculative: the candidate becomes the current point, its linearisation goes to the other set;
-    // scalars[5] = cost there, scalars[6] = max |gradient| there (slots 0/1 keep the current point's values)
-    st.swap_sets();
-    if ((rc = ba_linearize(ctx, st, sb, true, 5))) return rc;
-    if ((rc = ba_columns(ctx, st, sb))) return rc;
-    if ((rc = diag_and_gmax(6))) return rc;
-    VSL_HIP(ctx, hipMemcpyAsync(hsc, st.scalars, 16 * sizeof(double) + 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const double model_change = hsc[2], step_norm = sqrt(hsc[3]), x_norm = sqrt(hsc[4]), cand_cost = hsc[5];
-    const bool ok = hflag[0] != 0 && hflag[1] != 0 && model_change > 0.0;
-    const double radius_used = lm.radius;
-    LmInfo info;
-    const int verdict = lm_judge(lm, ok, cost, cand_cost, model_change, step_norm, x_norm, &info);
-    if (verdict != LM_ACCEPTED) st.swap_sets();  // (accepted: the sets stay swapped, the speculative linearisation is the current one)
-    if (verdict >= 0) { sum.termination = verdict; break; }
-    if (verdict == LM_INVALID) {
-      if (opt->verbosity >= 2) lm_print_invalid(iteration, lm.radius);
-      continue;  // the LM diagonal is reused (the Jacobian is unchanged)
-    }
-    if (opt->verbosity >= 2) lm_print_row(iteration, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
-    if (verdict == LM_ACCEPTED) {
-      cost = cand_cost;
-      gmax = hsc[6];
-      sum.successful_steps++;
-    }
-  }
-  sum.iterations = iteration;
-  sum.final_cost = cost;
-  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.poses, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  double ms;
-  int64_t cnt;
-  vsl_ctx_stage_ms(ctx, VSL_STAGE_BA_LIN, &ms, &cnt);
-  sum.linearize_ms = ctx->stage_ms[VSL_STAGE_BA_LIN] - base_ms[0];
-  sum.schur_ms = ctx->stage_ms[VSL_STAGE_BA_SCHUR] - base_ms[1];
-  sum.solve_ms = ctx->stage_ms[VSL_STAGE_BA_SOLVE] - base_ms[2];
-  vsl_ctx_set_profiling(ctx, prof_was ? 1 : 0);
-  sum.total_ms = now_ms() - t_start;
-  if (opt->verbosity >= 1)
-    fprintf(stderr, "vsl BA: iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", sum.iterations,
-            sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
-  if (summary) *summary = sum;
-  return VSL_OK;
+  rc = ba_host_loop_solve(ctx, prob, opt, st, no_fused, t_start, summary);
+  // an error return may leave kernels and copies queued on the arena: drain the stream before the loan ends (the next
+  // solve on this context gets the same block)
+  if (rc) (void)hipStreamSynchronize(ctx->stream);
+  return rc;
 }
 
 // =================================================================================================
@@ -2396,16 +2468,14 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   vsl_ba_summary sum;
   memset(&sum, 0, sizeof(sum));
   hipStream_t q = ctx->stream;
-  const int nbo = st.nb_obs, nbu = st.nb_upd;
+  const int nbo = st.nb_obs;
   double* scal = st.scalars;
 
   auto linearize = [&](bool scaled) -> int {  // at the CURRENT point; scalars[0] = cost
     hipLaunchKernelGGL(bai_linearize_kernel, dim3(nbo), dim3(256), 0, q, D, st.poses, st.points, st.intr, st.cam_intr, st.cam_free,
                        st.obs_cam, st.obs_lm, st.obs_uv, scaled ? scale : (const double*)nullptr,
                        scaled ? st.scale_l : (const double*)nullptr, sb.r, sb.F, sb.E, G, sb.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, sb.partials, nbo, scal, 0, 0);
-    VSL_CHECK_LAUNCH(ctx);
-    return VSL_OK;
+    return vsl_ba_reduce_launch(ctx, sb.partials, nbo, scal, 0, false);
   };
   auto stats = [&](bool write_diag) -> int {  // column norms / gradient of the current blocks; scalars[1] = max |gradient|
     VSL_HIP(ctx, hipMemsetAsync(n2, 0, 8 * (size_t)nt, q));
@@ -2461,16 +2531,15 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     hipLaunchKernelGGL(ba_all_finite2_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, df, L3, sb.dl, st.flag);
     hipLaunchKernelGGL(bai_model_kernel, dim3(nbo), dim3(256), 0, q, D, st.obs_cam, st.obs_lm, st.cam_free, st.cam_intr, sb.r, sb.F,
                        sb.E, G, df, sb.dl, sb.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, sb.partials, nbo, scal, 2, 0);
+    if ((rc = vsl_ba_reduce_launch(ctx, sb.partials, nbo, scal, 2, false))) return rc;
     // candidate point and its cost
-    hipLaunchKernelGGL(ba_update_kernel, dim3(nbu), dim3(256), 0, q, D, st.cam_free, st.poses, st.points, df, sb.dl, scale,
-                       st.scale_l, st.cand_poses, st.cand_points, sb.partials, nbu);
-    hipLaunchKernelGGL(ba_reduce2_kernel, dim3(2), dim3(256), 0, q, sb.partials, nbu, scal, 3);
+    if ((rc = vsl_ba_update_launch(ctx, D.C, D.L, st.cam_free, st.poses, st.points, df, sb.dl, scale, st.scale_l, st.cand_poses,
+                                   st.cand_points, sb.partials, scal, 3)))
+      return rc;
     hipLaunchKernelGGL(bai_intr_update_kernel, dim3(1), dim3(64), 0, q, n, st.intr, df, scale, cand_intr, scal, 6);
     hipLaunchKernelGGL(ba_cost_kernel, dim3(nbo), dim3(256), 0, q, D, st.cand_poses, st.cand_points, cand_intr, st.cam_intr,
                        st.obs_cam, st.obs_lm, st.obs_uv, 0, D.O, sb.partials);
-    hipLaunchKernelGGL(ba_reduce_kernel, dim3(1), dim3(256), 0, q, sb.partials, nbo, scal, 5, 0);
-    VSL_CHECK_LAUNCH(ctx);
+    if ((rc = vsl_ba_reduce_launch(ctx, sb.partials, nbo, scal, 5, false))) return rc;
     int hflag[2];
     VSL_HIP(ctx, hipMemcpyAsync(h, scal, sizeof(double) * 8, hipMemcpyDeviceToHost, q));
     VSL_HIP(ctx, hipMemcpyAsync(hflag, st.flag, sizeof(int) * 2, hipMemcpyDeviceToHost, q));

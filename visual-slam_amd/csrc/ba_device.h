@@ -6,6 +6,15 @@
 #pragma once
 #include "vsl_common.h"
 
+// Problem sizes and robust-loss settings, passed to the kernels by value.  Outside the anonymous namespace: the host
+// launchers that cross translation units (ba_state.h) name it in their signatures.
+struct BaDims {
+  int C, L, O, nfree, n;
+  int model0, model1;
+  int use_huber;
+  double huber;
+};
+
 namespace {
 
 // ------------------------------------------------------------------------------- device helpers
@@ -140,6 +149,26 @@ __device__ __forceinline__ void residual_blocks(int model, const double* __restr
   residual_blocks_Rt(model, intr, Rt, pw, uv, r, F, E, want_jac);
 }
 
+// rig-constrained BA (ba_rig.hip): F (2 x 6, camera tangent) -> F Ad(T_c_b), the block against the BODY pose;
+// T_c_b = (R row-major 9, t 3), Ad = [[R, [t]x R], [0, R]] in the (upsilon, omega) order
+__device__ __forceinline__ void rig_body_jacobian(const double* __restrict__ Rt, double* F) {
+  const double* R = Rt;
+  const double tx = Rt[9], ty = Rt[10], tz = Rt[11];
+#pragma unroll
+  for (int a = 0; a < 2; a++) {
+    const double u0 = F[6 * a], u1 = F[6 * a + 1], u2 = F[6 * a + 2];
+    // u^T [t]x + w^T, [t]x = [0 -tz ty; tz 0 -tx; -ty tx 0]
+    const double w0 = (u1 * tz - u2 * ty) + F[6 * a + 3];
+    const double w1 = (u2 * tx - u0 * tz) + F[6 * a + 4];
+    const double w2 = (u0 * ty - u1 * tx) + F[6 * a + 5];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      F[6 * a + j] = u0 * R[j] + u1 * R[3 + j] + u2 * R[6 + j];
+      F[6 * a + 3 + j] = w0 * R[j] + w1 * R[3 + j] + w2 * R[6 + j];
+    }
+  }
+}
+
 // candidate pose = T * exp(d) (include/visnav/local_parameterization_se3.hpp:43-50; [upstream] Sophus SE3::exp):
 // T = qx qy qz qw tx ty tz, d = (upsilon, omega); o receives the 7 values of the candidate
 __device__ __forceinline__ void se3_plus(const double* T, const double* d, double* o) {
@@ -205,13 +234,6 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh) {
   }
   return sh[0];
 }
-
-struct BaDims {
-  int C, L, O, nfree, n;
-  int model0, model1;
-  int use_huber;
-  double huber;
-};
 
 inline __device__ bool inv3(const double* P, double* Pi) {
   const double a = P[0], b = P[1], c = P[2], d = P[4], e = P[5], f = P[8];

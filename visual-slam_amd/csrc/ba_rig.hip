@@ -7,28 +7,39 @@
 // Residual, camera models, Huber corrector and cost are those of vsl_bundle_adjust (ba_device.h); what changes is the
 // pose block an observation differentiates against.  With T_c_b = T_b_c^-1 = (R, t),
 //   T_w_b exp(d) T_b_c = T_w_c exp(Ad(T_c_b) d),   Ad = [[R, [t]x R], [0, R]]  in the (upsilon, omega) order,
-// so F_b = F_c Ad = [F_u R, (F_u [t]x + F_w) R], formed in registers per observation (rig_body_jacobian).  Everything
-// downstream of the stored blocks works on BODY columns: Jacobi scaling, LM damping, the Schur complement, the step.
+// so F_b = F_c Ad = [F_u R, (F_u [t]x + F_w) R], formed in registers per observation (rig_body_jacobian, ba_device.h).
+// Everything downstream of the stored blocks works on BODY columns: Jacobi scaling, LM damping, the Schur complement, the
+// step.  So everything that does not depend on how a landmark's observations group into bodies runs on the kernels of
+// ba.hip, through the plain-pointer launchers of ba_state.h (a kernel is launched from the file that defines it), with
+// the body slot of a camera (cam_slot) where the free solver has its free-camera index.
 //
-// The chain (all reductions in a fixed order: two solves give the same bits; no floating-point atomics anywhere):
-//   rig_cams_kernel        camera poses from the bodies
-//   rig_linearize_kernel   r, F_b, E per observation (robustified, scaled when scales are given), cost partials
-//   rig_lm_cols_kernel     per landmark: squared column norms of E, E^T r
-//   rig_body_block_kernel  per free body and segment: partial H = sum F_b^T F_b, g = sum F_b^T r over a slice of the body's
-//                          observations; rig_body_block_finish_kernel adds the segments in order
-//   rig_lm_groups_kernel   per landmark: P (+ damping), P^-1, b; per (landmark, free body) GROUP W = sum F_b^T E over
-//                          the group's observations -- a landmark seen by both cameras of a body is one group of two --
-//                          and Y = W P^-1
-//   rig_schur_block_kernel workgroups per 6 x 6 block (a, b), a >= b, of the reduced system and segment: walks a slice of
-//                          the groups of body a (ascending landmark), finds body b's group of the same landmark by
-//                          bisection, sums Y_a W_b^T per thread, reduces in a fixed tree; rig_schur_finish_kernel adds the
-//                          segments in order and writes the block and its mirror image (S is exactly symmetric).
-//                          A landmark with any number of observations is the same code: the per-landmark kernels
-//                          loop, the gather sees one group per body.
-//   dense SPD solve        ba_chol_small_kernel up to 128 unknowns, the dense panel factorisation of chol.hip beyond
-//   rig_backsub_kernel, rig_model_kernel, rig_update_kernel: landmark step, model cost change, T_w_b * exp(step)
-// The LM loop is host-decided with ONE synchronisation per iteration (the candidate is linearised speculatively into a
-// second set of blocks, as in vsl_bundle_adjust's host loop) under the policy of lm_policy.h.
+// The chain (all reductions in a fixed order: two solves give the same bits; no floating-point atomics anywhere).
+// OWN = a kernel of this file, ba = a kernel of ba.hip:
+//   OWN rig_cams_kernel         camera poses from the bodies
+//   ba  ba_linearize_kernel<RIG> r, F_b, E per observation (robustified, scaled when scales are given), cost partials
+//   ba  ba_reduce_kernel        sums / maxima of partials into the scalars
+//   ba  ba_lm_cols_kernel       per landmark: squared column norms of E, E^T r
+//   OWN rig_body_block_kernel   per free body and segment: partial H = sum F_b^T F_b, g = sum F_b^T r over a slice of the
+//                               body's observations.  NOT ba_cam_block_kernel: this one sums the lanes of a wave by
+//                               shuffle and then the four waves in order, that one goes through a 256-wide LDS tree -- two
+//                               summation orders, two sets of bits, and both solvers' results are pinned
+//   ba  ba_cam_block_finish_kernel  adds the segments of a block in order
+//   ba  ba_make_scale_kernel, ba_diag_kernel   Jacobi scaling (once), LM diagonals and max |gradient|
+//   OWN rig_lm_groups_kernel    per landmark: P (+ damping), P^-1, b; per (landmark, free body) GROUP W = sum F_b^T E over
+//                               the group's observations -- a landmark seen by both cameras of a body is one group of two
+//                               -- and Y = W P^-1
+//   OWN rig_schur_block_kernel  workgroups per 6 x 6 block (a, b), a >= b, of the reduced system and segment: walks a slice
+//                               of the groups of body a (ascending landmark), finds body b's group of the same landmark by
+//                               bisection, sums Y_a W_b^T per thread, reduces in a fixed tree; rig_schur_finish_kernel adds
+//                               the segments in order and writes the block and its mirror image (S is exactly symmetric).
+//                               A landmark with any number of observations is the same code: the per-landmark kernels
+//                               loop, the gather sees one group per body.
+//   ba  dense SPD solve         ba_chol_small_kernel up to 128 unknowns, the dense panel factorisation of chol.hip beyond
+//   OWN rig_backsub_kernel      landmark step from the groups' W, finite check
+//   ba  ba_model_kernel, ba_update_kernel, ba_reduce2_kernel   model cost change, T_w_b * exp(step) (the pose blocks are
+//                               the bodies), squared step / x norms
+// The LM loop is lm_speculative_loop (lm_policy.h), the one vsl_bundle_adjust's host path runs: host-decided with ONE
+// synchronisation per iteration, the candidate linearised speculatively into a second set of blocks.
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -38,37 +49,12 @@
 #include "lm_policy.h"
 #include "dev_arena.h"
 #include "ba_device.h"
+#include "ba_state.h"
 #include "ba_rig_plan.h"
 #include "ba_rig_cov_plan.h"
 #include "pgo_cov_plan.h"
 
 namespace {
-
-struct RigDims {
-  int C, B, L, O, G, nfree, n;
-  int model0, model1;
-  int use_huber;
-  double huber;
-};
-
-// F (2 x 6, camera tangent) -> F Ad(T_c_b), T_c_b = (R row-major 9, t 3)
-__device__ __forceinline__ void rig_body_jacobian(const double* __restrict__ Rt, double* F) {
-  const double* R = Rt;
-  const double tx = Rt[9], ty = Rt[10], tz = Rt[11];
-#pragma unroll
-  for (int a = 0; a < 2; a++) {
-    const double u0 = F[6 * a], u1 = F[6 * a + 1], u2 = F[6 * a + 2];
-    // u^T [t]x + w^T, [t]x = [0 -tz ty; tz 0 -tx; -ty tx 0]
-    const double w0 = (u1 * tz - u2 * ty) + F[6 * a + 3];
-    const double w1 = (u2 * tx - u0 * tz) + F[6 * a + 4];
-    const double w2 = (u0 * ty - u1 * tx) + F[6 * a + 5];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      F[6 * a + j] = u0 * R[j] + u1 * R[3 + j] + u2 * R[6 + j];
-      F[6 * a + 3 + j] = w0 * R[j] + w1 * R[3 + j] + w2 * R[6 + j];
-    }
-  }
-}
 
 // sums of N per-thread values over a 256-thread workgroup in a fixed order (lanes by shuffle, then the four waves in
 // order): every thread gets the sums back in acc.  sh: 4 * N doubles
@@ -105,81 +91,6 @@ __global__ void rig_cams_kernel(int C, const double* __restrict__ bodies, const 
   for (int i = 0; i < 3; i++) o[4 + i] = T[4 + i] + (R[3 * i] * e[4] + R[3 * i + 1] * e[5] + R[3 * i + 2] * e[6]);
 }
 
-__global__ __launch_bounds__(256) void rig_linearize_kernel(RigDims D, const double* __restrict__ cams,
-                                                            const double* __restrict__ points, const double* __restrict__ intr,
-                                                            const double* __restrict__ tcb, const int* __restrict__ cam_intr,
-                                                            const int* __restrict__ cam_slot, const int* __restrict__ obs_cam,
-                                                            const int* __restrict__ obs_lm, const double* __restrict__ obs_uv,
-                                                            const double* __restrict__ scale_c, const double* __restrict__ scale_l,
-                                                            double* __restrict__ r_out, double* __restrict__ F_out,
-                                                            double* __restrict__ E_out, double* __restrict__ partials) {
-  __shared__ double sh[256];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double c = 0;
-  if (i < D.O) {
-    const int cam = obs_cam[i], lm = obs_lm[i], k = cam_intr[cam];
-    double r[2], F[12], E[6];
-    residual_blocks(k ? D.model1 : D.model0, intr + 8 * k, cams + 7 * (size_t)cam, points + 3 * (size_t)lm, obs_uv + 2 * (size_t)i, r, F,
-                    E, true);
-    rig_body_jacobian(tcb + 12 * k, F);
-    const double s = r[0] * r[0] + r[1] * r[1];
-    double rho0 = s, rho1 = 1.0;
-    if (D.use_huber) huber(s, D.huber, rho0, rho1);
-    c = 0.5 * rho0;
-    const double sr = sqrt(rho1);
-    r_out[2 * (size_t)i] = r[0] * sr;
-    r_out[2 * (size_t)i + 1] = r[1] * sr;
-    const int slot = cam_slot[cam];
-    for (int j = 0; j < 6; j++) {
-      const double sc = (scale_c && slot >= 0) ? scale_c[6 * (size_t)slot + j] : 1.0;
-      F_out[12 * (size_t)i + j] = F[j] * sr * sc;
-      F_out[12 * (size_t)i + 6 + j] = F[6 + j] * sr * sc;
-    }
-    for (int j = 0; j < 3; j++) {
-      const double sc = scale_l ? scale_l[3 * (size_t)lm + j] : 1.0;
-      E_out[6 * (size_t)i + j] = E[j] * sr * sc;
-      E_out[6 * (size_t)i + 3 + j] = E[3 + j] * sr * sc;
-    }
-  }
-  const double t = block_sum_256(c, sh);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-
-// scalars[slot] = sum / max of partials[0..n) in a fixed order (one workgroup)
-__global__ __launch_bounds__(256) void rig_reduce_kernel(const double* __restrict__ partials, int n, double* __restrict__ scalars,
-                                                         int slot, int is_max) {
-  __shared__ double sh[256];
-  double v = 0;
-  for (int i = threadIdx.x; i < n; i += 256) v = is_max ? fmax(v, partials[i]) : v + partials[i];
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = is_max ? fmax(sh[threadIdx.x], sh[threadIdx.x + o]) : sh[threadIdx.x] + sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) scalars[slot] = sh[0];
-}
-
-__global__ __launch_bounds__(256) void rig_lm_cols_kernel(RigDims D, const int* __restrict__ lm_start, const double* __restrict__ r,
-                                                          const double* __restrict__ E, double* __restrict__ n2l,
-                                                          double* __restrict__ grad_l) {
-  const int l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= D.L) return;
-  double n2[3] = {0, 0, 0}, g[3] = {0, 0, 0};
-  for (int i = lm_start[l]; i < lm_start[l + 1]; i++) {
-    const double* e = E + 6 * (size_t)i;
-    const double r0 = r[2 * (size_t)i], r1 = r[2 * (size_t)i + 1];
-    for (int j = 0; j < 3; j++) {
-      n2[j] += e[j] * e[j] + e[3 + j] * e[3 + j];
-      g[j] += e[j] * r0 + e[3 + j] * r1;
-    }
-  }
-  for (int j = 0; j < 3; j++) {
-    n2l[3 * (size_t)l + j] = n2[j];
-    grad_l[3 * (size_t)l + j] = g[j];
-  }
-}
-
 // grid (free bodies, segments): a workgroup sums every `segments`-th 256-observation slice of its body -- the 21 upper
 // entries of H = sum F^T F and the 6 of g = sum F^T r -- into part[(body, segment)][27].  (One workgroup per body walked
 // 22 k observations of the benchmark's window in 88 dependent trips: 120 us with six workgroups on the chip.)
@@ -211,67 +122,10 @@ __global__ __launch_bounds__(256) void rig_body_block_kernel(const int* __restri
   }
 }
 
-// the segments of a body in order: H (mirrored, exactly symmetric) and g
-__global__ void rig_body_block_finish_kernel(int nfree, int nseg, const double* __restrict__ part, double* __restrict__ H,
-                                             double* __restrict__ g) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nfree * 27) return;
-  const int s = t / 27, k = t - s * 27;
-  double v = 0;
-  for (int q = 0; q < nseg; q++) v += part[((size_t)s * nseg + q) * 27 + k];
-  if (k >= 21) {
-    g[6 * (size_t)s + (k - 21)] = v;
-  } else {
-    int a = 0, rem = k;  // k-th entry of the upper triangle, row-major
-    while (rem >= 6 - a) {
-      rem -= 6 - a;
-      a++;
-    }
-    const int b = a + rem;
-    H[36 * (size_t)s + 6 * a + b] = v;
-    H[36 * (size_t)s + 6 * b + a] = v;
-  }
-}
-
-// Jacobi scaling (computed once, from the unscaled blocks): 1 / (1 + sqrt(column norm^2)), bodies from diag H
-__global__ void rig_make_scale_kernel(int nfree, int L, const double* __restrict__ H, const double* __restrict__ n2l,
-                                      double* __restrict__ scale_c, double* __restrict__ scale_l) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 6 * nfree) scale_c[i] = 1.0 / (1.0 + sqrt(H[36 * (size_t)(i / 6) + 7 * (i % 6)]));
-  if (i < 3 * L) scale_l[i] = 1.0 / (1.0 + sqrt(n2l[i]));
-}
-
-// LM diagonals clamp(column norm^2, 1e-6, 1e32) of the scaled blocks and the workgroup's max |gradient| of the
-// UNSCALED problem
-__global__ __launch_bounds__(256) void rig_diag_kernel(int nfree, int L, const double* __restrict__ H, const double* __restrict__ n2l,
-                                                       const double* __restrict__ g_b, const double* __restrict__ grad_l,
-                                                       const double* __restrict__ scale_c, const double* __restrict__ scale_l,
-                                                       double* __restrict__ diag_c, double* __restrict__ diag_l,
-                                                       double* __restrict__ gabs) {
-  __shared__ double sh[256];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double m = 0;
-  if (i < 6 * nfree) {
-    diag_c[i] = fmin(fmax(H[36 * (size_t)(i / 6) + 7 * (i % 6)], 1e-6), 1e32);
-    m = fabs(g_b[i] / scale_c[i]);
-  }
-  if (i < 3 * L) {
-    diag_l[i] = fmin(fmax(n2l[i], 1e-6), 1e32);
-    m = fmax(m, fabs(grad_l[i] / scale_l[i]));
-  }
-  sh[threadIdx.x] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) gabs[blockIdx.x] = sh[0];
-}
-
 // per landmark: P = sum E^T E (+ diag_l * inv_radius), P^-1, b = sum E^T r; per group of the landmark W = sum F^T E
 // (6 x 3 row-major) over the group's observations and Y = W P^-1.  A landmark whose P cannot be inverted gets
 // P^-1 = 0: it contributes nothing to S and does not move.
-__global__ __launch_bounds__(256) void rig_lm_groups_kernel(RigDims D, const int* __restrict__ lm_start, const int* __restrict__ lm_grp,
+__global__ __launch_bounds__(256) void rig_lm_groups_kernel(BaDims D, const int* __restrict__ lm_start, const int* __restrict__ lm_grp,
                                                             const int* __restrict__ grp_begin, const int* __restrict__ grp_end,
                                                             const double* __restrict__ r, const double* __restrict__ F,
                                                             const double* __restrict__ E, const double* __restrict__ diag_l,
@@ -396,7 +250,7 @@ __global__ __launch_bounds__(64) void rig_schur_finish_kernel(int n, int nseg, c
 }
 
 // delta_l = -P^-1 (b_l + sum over the landmark's groups of W^T delta_body); flag[0] cleared on a non-finite step
-__global__ __launch_bounds__(256) void rig_backsub_kernel(RigDims D, const int* __restrict__ lm_grp, const int* __restrict__ grp_slot,
+__global__ __launch_bounds__(256) void rig_backsub_kernel(BaDims D, const int* __restrict__ lm_grp, const int* __restrict__ grp_slot,
                                                           const double* __restrict__ W, const double* __restrict__ Pinv,
                                                           const double* __restrict__ bl, const double* __restrict__ dc,
                                                           double* __restrict__ dl, int* __restrict__ finite_flag) {
@@ -419,95 +273,6 @@ __global__ __launch_bounds__(256) void rig_backsub_kernel(RigDims D, const int* 
   }
 }
 
-// model cost change partials: -(J d)^T (r + J d / 2)
-__global__ __launch_bounds__(256) void rig_model_kernel(RigDims D, const int* __restrict__ obs_cam, const int* __restrict__ obs_lm,
-                                                        const int* __restrict__ cam_slot, const double* __restrict__ r,
-                                                        const double* __restrict__ F, const double* __restrict__ E,
-                                                        const double* __restrict__ dc, const double* __restrict__ dl,
-                                                        double* __restrict__ partials) {
-  __shared__ double sh[256];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double v = 0;
-  if (i < D.O) {
-    const int slot = cam_slot[obs_cam[i]], lm = obs_lm[i];
-    const double* f = F + 12 * (size_t)i;
-    const double* e = E + 6 * (size_t)i;
-    double m0 = 0, m1 = 0;
-    if (slot >= 0)
-      for (int j = 0; j < 6; j++) {
-        m0 += f[j] * dc[6 * (size_t)slot + j];
-        m1 += f[6 + j] * dc[6 * (size_t)slot + j];
-      }
-    for (int j = 0; j < 3; j++) {
-      m0 += e[j] * dl[3 * (size_t)lm + j];
-      m1 += e[3 + j] * dl[3 * (size_t)lm + j];
-    }
-    v = -(m0 * (r[2 * (size_t)i] + m0 / 2.0) + m1 * (r[2 * (size_t)i + 1] + m1 / 2.0));
-  }
-  const double t = block_sum_256(v, sh);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-
-// candidate bodies T_w_b * exp(step .* scale) and points p + step .* scale; partials [0, nb): squared step norm,
-// [nb, 2 nb): squared norm of the current free bodies and points
-__global__ __launch_bounds__(256) void rig_update_kernel(RigDims D, const int* __restrict__ body_slot, const double* __restrict__ bodies,
-                                                         const double* __restrict__ points, const double* __restrict__ dc,
-                                                         const double* __restrict__ dl, const double* __restrict__ scale_c,
-                                                         const double* __restrict__ scale_l, double* __restrict__ cand_bodies,
-                                                         double* __restrict__ cand_points, double* __restrict__ partials, int nb) {
-  __shared__ double sh[256];
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  double step2 = 0, x2 = 0;
-  if (t < D.B) {
-    const int slot = body_slot[t];
-    const double* T = bodies + 7 * (size_t)t;
-    double* o = cand_bodies + 7 * (size_t)t;
-    if (slot < 0) {
-      for (int j = 0; j < 7; j++) o[j] = T[j];
-    } else {
-      double d[6];
-      for (int j = 0; j < 6; j++) {
-        d[j] = dc[6 * (size_t)slot + j] * scale_c[6 * (size_t)slot + j];
-        step2 += d[j] * d[j];
-      }
-      for (int j = 0; j < 7; j++) x2 += T[j] * T[j];
-      se3_plus(T, d, o);
-    }
-  }
-  if (t < D.L) {
-    for (int j = 0; j < 3; j++) {
-      const double dd = dl[3 * (size_t)t + j] * scale_l[3 * (size_t)t + j];
-      step2 += dd * dd;
-      const double xv = points[3 * (size_t)t + j];
-      x2 += xv * xv;
-      cand_points[3 * (size_t)t + j] = xv + dd;
-    }
-  }
-  const double a = block_sum_256(step2, sh);
-  __syncthreads();
-  const double b = block_sum_256(x2, sh);
-  if (threadIdx.x == 0) {
-    partials[blockIdx.x] = a;
-    partials[nb + blockIdx.x] = b;
-  }
-}
-
-// scalars[slot] and scalars[slot + 1] = sums of partials[0..n) and partials[n..2n): a workgroup each
-__global__ __launch_bounds__(256) void rig_reduce2_kernel(const double* __restrict__ partials, int n, double* __restrict__ scalars,
-                                                          int slot) {
-  __shared__ double sh[256];
-  const double* p = partials + (size_t)blockIdx.x * n;
-  double v = 0;
-  for (int i = threadIdx.x; i < n; i += 256) v += p[i];
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) scalars[slot + blockIdx.x] = sh[0];
-}
-
 // ------------------------------------------------------------------------------------------------ host state
 // what a linearisation point owns: the LM loop keeps two and swaps them when a step is accepted
 struct RigSet {
@@ -517,10 +282,11 @@ struct RigSet {
 };
 
 struct RigState {
-  RigDims D;
+  BaDims D;  // of the shared kernels: C cameras, nfree free BODIES, n = 6 nfree
+  int B = 0, G = 0;  // bodies, (landmark, free body) groups
   RigPlan plan;
   DevArena arena;
-  int nb_obs = 1, nb_upd = 1, nb_diag = 1;
+  int nb_obs = 1;
   int body_seg = 1, schur_seg = 1;  // workgroups per free body in rig_body_block_kernel / per block in rig_schur_block_kernel
   RigSet cur, cand;
   double *intr = nullptr, *tbc = nullptr, *tcb = nullptr, *obs_uv = nullptr;
@@ -555,15 +321,16 @@ int rig_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const v
 int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt, RigState& st,
               size_t extra_bytes = 0) {
   const RigPlan& hp = st.plan;
-  RigDims& D = st.D;
-  D.C = p->n_cams; D.B = rig->n_bodies; D.L = p->n_lms; D.O = p->n_obs; D.G = hp.n_groups();
+  BaDims& D = st.D;
+  D.C = p->n_cams; D.L = p->n_lms; D.O = p->n_obs;
   D.nfree = hp.n_free; D.n = 6 * hp.n_free;
   D.model0 = p->cam_model[0]; D.model1 = p->cam_model[1];
   D.use_huber = opt->use_huber; D.huber = opt->huber_parameter;
-  const size_t C = D.C, B = D.B, L = D.L, O = D.O, G = D.G, n = D.n, nf = D.nfree;
+  st.B = rig->n_bodies; st.G = hp.n_groups();
+  const size_t C = D.C, B = st.B, L = D.L, O = D.O, G = st.G, n = D.n, nf = D.nfree;
   st.nb_obs = (int)((O + 255) / 256);
-  st.nb_upd = (int)((std::max(B, L) + 255) / 256);
-  st.nb_diag = (int)((std::max(n, 3 * L) + 255) / 256);
+  // partials of the shared launchers (ba_state.h): observations, 2 x pose blocks / landmarks, LM diagonal entries
+  const size_t nb_upd = (std::max(B, L) + 255) / 256, nb_diag = (std::max(n, 3 * L) + 255) / 256;
   // a workgroup of the two gathers takes about two 256-entry trips of the longest body list (at most 64 segments)
   int max_obs = 0, max_grp = 0;
   for (int b = 0; b < hp.n_free; b++) {
@@ -583,7 +350,7 @@ int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, cons
   plan.add(st.scale_c, n); plan.add(st.scale_l, 3 * L);
   plan.add(st.W, 18 * G); plan.add(st.Y, 18 * G); plan.add(st.Pinv, 9 * L); plan.add(st.bl, 3 * L);
   plan.add(st.S, n * n); plan.add(st.rhs, n); plan.add(st.dc, n); plan.add(st.dl, 3 * L);
-  plan.add(st.partials, (size_t)std::max(std::max(st.nb_obs, 2 * st.nb_upd), st.nb_diag));
+  plan.add(st.partials, std::max(std::max((size_t)st.nb_obs, 2 * nb_upd), nb_diag));
   plan.add(st.scalars, 32);  // 16 doubles, then the flags
   plan.add(st.body_part, nf * st.body_seg * 27); plan.add(st.schur_part, nf * (nf + 1) / 2 * st.schur_seg * 42);
   plan.add(st.cam_intr, C); plan.add(st.cam_body, C); plan.add(st.cam_slot, C); plan.add(st.body_slot, B);
@@ -644,32 +411,25 @@ int rig_linearize(vsl_ctx* ctx, RigState& st, RigSet& s, bool scaled, int cost_s
   VslStage stage(ctx, VSL_STAGE_BA_LIN);
   int rc = rig_cams(ctx, st, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(rig_linearize_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D, s.cams, s.points, st.intr, st.tcb,
-                     st.cam_intr, st.cam_slot, st.obs_cam, st.obs_lm, st.obs_uv, scaled ? st.scale_c : nullptr,
-                     scaled ? st.scale_l : nullptr, s.r, s.F, s.E, st.partials);
-  hipLaunchKernelGGL(rig_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, cost_slot, 0);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
+  if ((rc = vsl_ba_linearize_launch(ctx, st.D, s.cams, s.points, st.intr, st.tcb, st.cam_intr, st.cam_slot, st.obs_cam, st.obs_lm,
+                                    st.obs_uv, scaled ? st.scale_c : nullptr, scaled ? st.scale_l : nullptr, s.r, s.F, s.E,
+                                    st.partials)))
+    return rc;
+  return vsl_ba_reduce_launch(ctx, st.partials, st.nb_obs, st.scalars, cost_slot, false);
 }
 
 int rig_columns(vsl_ctx* ctx, RigState& st, RigSet& s) {
   VslStage stage(ctx, VSL_STAGE_BA_LIN);
-  hipLaunchKernelGGL(rig_lm_cols_kernel, dim3((st.D.L + 255) / 256), dim3(256), 0, ctx->stream, st.D, st.lm_start, s.r, s.E, s.n2l,
-                     s.grad_l);
+  int rc = vsl_ba_lm_cols_launch(ctx, st.D.L, st.lm_start, s.r, s.E, s.n2l, s.grad_l);
+  if (rc) return rc;
   hipLaunchKernelGGL(rig_body_block_kernel, dim3(st.D.nfree, st.body_seg), dim3(256), 0, ctx->stream, st.bo_start, st.bo_obs, s.r, s.F,
                      st.body_part);
-  hipLaunchKernelGGL(rig_body_block_finish_kernel, dim3((st.D.nfree * 27 + 255) / 256), dim3(256), 0, ctx->stream, st.D.nfree,
-                     st.body_seg, st.body_part, s.H, s.g_b);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
+  return vsl_ba_block_finish_launch(ctx, st.D.nfree, st.body_seg, st.body_part, s.H, s.g_b);
 }
 
 int rig_diag_gmax(vsl_ctx* ctx, RigState& st, RigSet& s, int slot) {
-  hipLaunchKernelGGL(rig_diag_kernel, dim3(st.nb_diag), dim3(256), 0, ctx->stream, st.D.nfree, st.D.L, s.H, s.n2l, s.g_b, s.grad_l,
-                     st.scale_c, st.scale_l, s.diag_c, s.diag_l, st.partials);
-  hipLaunchKernelGGL(rig_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_diag, st.scalars, slot, 1);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
+  return vsl_ba_diag_gmax_launch(ctx, st.D.nfree, st.D.L, s.H, s.n2l, s.g_b, s.grad_l, st.scale_c, st.scale_l, s.diag_c, s.diag_l,
+                                 st.partials, st.scalars, slot);
 }
 
 // the reduced body system of the current set; damped by inv_radius when `damp`
@@ -701,14 +461,12 @@ int rig_step(vsl_ctx* ctx, RigState& st) {
   const RigSet& s = st.cur;
   hipLaunchKernelGGL(rig_backsub_kernel, dim3((st.D.L + 255) / 256), dim3(256), 0, ctx->stream, st.D, st.lm_grp, st.grp_slot, st.W,
                      st.Pinv, st.bl, st.dc, st.dl, st.flag);
-  hipLaunchKernelGGL(rig_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D, st.obs_cam, st.obs_lm, st.cam_slot, s.r, s.F,
-                     s.E, st.dc, st.dl, st.partials);
-  hipLaunchKernelGGL(rig_reduce_kernel, dim3(1), dim3(256), 0, ctx->stream, st.partials, st.nb_obs, st.scalars, 2, 0);
-  hipLaunchKernelGGL(rig_update_kernel, dim3(st.nb_upd), dim3(256), 0, ctx->stream, st.D, st.body_slot, s.bodies, s.points, st.dc,
-                     st.dl, st.scale_c, st.scale_l, st.cand.bodies, st.cand.points, st.partials, st.nb_upd);
-  hipLaunchKernelGGL(rig_reduce2_kernel, dim3(2), dim3(256), 0, ctx->stream, st.partials, st.nb_upd, st.scalars, 3);
-  VSL_CHECK_LAUNCH(ctx);
-  return VSL_OK;
+  int rc = vsl_ba_model_launch(ctx, st.D.O, st.obs_cam, st.obs_lm, st.cam_slot, s.r, s.F, s.E, st.dc, st.dl, st.partials);
+  if (rc) return rc;
+  if ((rc = vsl_ba_reduce_launch(ctx, st.partials, st.nb_obs, st.scalars, 2, false))) return rc;
+  // (the pose blocks of the update are the bodies)
+  return vsl_ba_update_launch(ctx, st.B, st.D.L, st.body_slot, s.bodies, s.points, st.dc, st.dl, st.scale_c, st.scale_l,
+                              st.cand.bodies, st.cand.points, st.partials, st.scalars, 3);
 }
 
 // iteration 0 of the solve: blocks at the start, Jacobi scaling from the unscaled columns, the scaled blocks, their
@@ -717,12 +475,25 @@ int rig_first_linearization(vsl_ctx* ctx, RigState& st) {
   int rc;
   if ((rc = rig_linearize(ctx, st, st.cur, false, 0))) return rc;
   if ((rc = rig_columns(ctx, st, st.cur))) return rc;
-  hipLaunchKernelGGL(rig_make_scale_kernel, dim3(st.nb_diag), dim3(256), 0, ctx->stream, st.D.nfree, st.D.L, st.cur.H, st.cur.n2l,
-                     st.scale_c, st.scale_l);
-  VSL_CHECK_LAUNCH(ctx);
+  if ((rc = vsl_ba_make_scale_launch(ctx, st.D.nfree, st.D.L, st.cur.H, st.cur.n2l, st.scale_c, st.scale_l))) return rc;
   if ((rc = rig_linearize(ctx, st, st.cur, true, 0))) return rc;
   if ((rc = rig_columns(ctx, st, st.cur))) return rc;
   return rig_diag_gmax(ctx, st, st.cur, 1);
+}
+
+// the S of vsl_ba_rig_linearize (unscaled, undamped) in st.S, the stored blocks in st.cur
+int rig_unscaled_system(vsl_ctx* ctx, RigState& st) {
+  int rc;
+  if ((rc = rig_linearize(ctx, st, st.cur, false, 0))) return rc;
+  if ((rc = rig_columns(ctx, st, st.cur))) return rc;
+  return rig_schur(ctx, st, false, 0.0);
+}
+
+// An error behind the set-up may leave kernels and copies queued that use the borrowed arena (and the caller's host
+// buffers): the stream is drained before the loan ends -- a later solve on this context gets the same block.  Returns rc.
+int rig_drain(vsl_ctx* ctx, int rc) {
+  (void)hipStreamSynchronize(ctx->stream);
+  return rc;
 }
 
 }  // namespace
@@ -737,16 +508,19 @@ extern "C" int vsl_ba_rig_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, co
     return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_rig_linearize: no fixed body: the gauge is free and the reduced system singular");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   if ((rc = rig_setup(ctx, prob, rig, opt, st))) return rc;
-  if ((rc = rig_linearize(ctx, st, st.cur, false, 0))) return rc;
-  if ((rc = rig_columns(ctx, st, st.cur))) return rc;
-  if ((rc = rig_schur(ctx, st, false, 0.0))) return rc;
   const size_t n = st.D.n;
-  std::vector<double> hS(n * n), hg(n);
+  std::vector<double> hS(n * n), hg(n);  // (the targets of queued copies: they outlive the drain below)
   double c = 0;
-  VSL_HIP(ctx, hipMemcpyAsync(hS.data(), st.S, 8 * n * n, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(hg.data(), st.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  auto run = [&]() -> int {
+    int e;
+    if ((e = rig_unscaled_system(ctx, st))) return e;
+    VSL_HIP(ctx, hipMemcpyAsync(hS.data(), st.S, 8 * n * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hg.data(), st.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VSL_OK;
+  };
+  if ((rc = run())) return rig_drain(ctx, rc);
   memcpy(S, hS.data(), 8 * n * n);
   memcpy(g, hg.data(), 8 * n);
   *cost = c;
@@ -764,21 +538,26 @@ extern "C" int vsl_ba_rig_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const
     return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_rig_system: no fixed body: the gauge is free and the reduced system singular");
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   if ((rc = rig_setup(ctx, prob, rig, opt, st))) return rc;
-  if ((rc = rig_first_linearization(ctx, st))) return rc;
-  if ((rc = rig_schur(ctx, st, true, inv_radius))) return rc;
   const size_t n = st.D.n;
-  std::vector<double> hS(n * n), hv(3 * n);
+  std::vector<double> hS(n * n), hv(3 * n);  // (the targets of queued copies: they outlive the drain below)
   double c = 0;
   int flags[2] = {0, 0};
-  // (the large-system factorisation works in place: S and rhs are read before it runs)
-  VSL_HIP(ctx, hipMemcpyAsync(hS.data(), st.S, 8 * n * n, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(hv.data(), st.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(hv.data() + n, st.scale_c, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
-  if ((rc = rig_solve(ctx, st))) return rc;
-  VSL_HIP(ctx, hipMemcpyAsync(hv.data() + 2 * n, st.dc, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(flags, st.flag, 8, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  auto run = [&]() -> int {
+    int e;
+    if ((e = rig_first_linearization(ctx, st))) return e;
+    if ((e = rig_schur(ctx, st, true, inv_radius))) return e;
+    // (the large-system factorisation works in place: S and rhs are read before it runs)
+    VSL_HIP(ctx, hipMemcpyAsync(hS.data(), st.S, 8 * n * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data(), st.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + n, st.scale_c, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((e = rig_solve(ctx, st))) return e;
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + 2 * n, st.dc, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(flags, st.flag, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VSL_OK;
+  };
+  if ((rc = run())) return rig_drain(ctx, rc);
   if (S) memcpy(S, hS.data(), 8 * n * n);
   if (rhs) memcpy(rhs, hv.data(), 8 * n);
   if (scale_b) memcpy(scale_b, hv.data() + n, 8 * n);
@@ -789,92 +568,70 @@ extern "C" int vsl_ba_rig_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const
   return VSL_OK;
 }
 
+namespace {
+
+// vsl_bundle_adjust_rig behind the set-up
+int rig_solve_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt, RigState& st,
+                  double t_start, vsl_ba_summary* summary) {
+  int rc;
+  const BaDims& D = st.D;
+  vsl_ba_summary sum;
+  memset(&sum, 0, sizeof(sum));
+  const BaSolveTimes times(ctx, t_start);
+
+  if ((rc = rig_first_linearization(ctx, st))) return rc;
+  double sc[16];  // [0] cost, [1] max |gradient| at the start
+  int unused_flags[2];
+  if ((rc = ba_fetch_step(ctx, st.scalars, sc, unused_flags))) return rc;
+  sum.initial_cost = sc[0];
+
+  // lm_speculative_loop: Schur, solve, step, candidate AND the candidate's linearisation (into the other set: its cost is
+  // the candidate's cost, and an accepted step has its next linearisation already) are enqueued, one copy brings the
+  // flags and scalars back, the host applies lm_policy.h.
+  auto enqueue = [&](double radius) -> int {
+    int e;
+    if ((e = rig_schur(ctx, st, true, 1.0 / radius))) return e;
+    if ((e = rig_solve(ctx, st))) return e;
+    if ((e = rig_step(ctx, st))) return e;
+    if ((e = rig_linearize(ctx, st, st.cand, true, 5))) return e;
+    if ((e = rig_columns(ctx, st, st.cand))) return e;
+    return rig_diag_gmax(ctx, st, st.cand, 6);
+  };
+  auto fetch = [&](double* s16, int* flags) -> int { return ba_fetch_step(ctx, st.scalars, s16, flags); };
+  auto settle = [&](bool accepted) {
+    if (accepted) std::swap(st.cur, st.cand);
+  };
+  LmLoopResult lm;
+  if ((rc = lm_speculative_loop(opt->max_num_iterations, opt->verbosity, sc[0], sc[1], enqueue, fetch, settle, &lm))) return rc;
+  sum.iterations = lm.iterations;
+  sum.successful_steps = lm.successful_steps;
+  sum.termination = lm.termination;
+  sum.final_cost = lm.final_cost;
+  // the cameras of the final bodies (the current set's were derived when it was linearised)
+  VSL_HIP(ctx, hipMemcpyAsync(rig->body_poses, st.cur.bodies, sizeof(double) * 7 * (size_t)st.B, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.cur.cams, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.cur.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  char label[64];
+  snprintf(label, sizeof(label), "vsl rig BA: %d free bodies,", D.nfree);
+  ba_finish_summary(ctx, times, opt->verbosity, label, sum, summary);
+  return VSL_OK;
+}
+
+}  // namespace
+
 // [upstream] ceres::Solve, TRUST_REGION / LEVENBERG_MARQUARDT / Schur on the problem whose parameter blocks are the body
-// poses and the landmarks: the loop of vsl_bundle_adjust's host path (ba.hip) on the rig's kernels.
+// poses and the landmarks: the loop of vsl_bundle_adjust's host path (lm_speculative_loop) on the rig's chain.
 extern "C" int vsl_bundle_adjust_rig(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
                                      vsl_ba_summary* summary) {
   const double t_start = now_ms();
-  RigState st;
+  RigState st;  // holds the loan of the context's arena
   int rc = rig_validate(ctx, "vsl_bundle_adjust_rig", prob, rig, opt, st.plan);
   if (rc) return rc;
   VSL_HIP(ctx, hipSetDevice(ctx->device));
   if ((rc = rig_setup(ctx, prob, rig, opt, st))) return rc;
-  const RigDims& D = st.D;
-  vsl_ba_summary sum;
-  memset(&sum, 0, sizeof(sum));
-  const bool prof_was = ctx->profiling;
-  double base_ms[3];
-  for (int k = 0; k < 3; k++) base_ms[k] = ctx->stage_ms[VSL_STAGE_BA_LIN + k];
-
-  if ((rc = rig_first_linearization(ctx, st))) return rc;
-  double* hsc = nullptr;
-  {
-    void* hp = nullptr;
-    if ((rc = vsl_ctx_hpinned(ctx, 256, &hp))) return rc;
-    hsc = (double*)hp;
-  }
-  const int* hflag = (const int*)(hsc + 16);
-  VSL_HIP(ctx, hipMemcpyAsync(hsc, st.scalars, 16 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  double cost = hsc[0], gmax = hsc[1];
-  sum.initial_cost = cost;
-
-  LmState lm;
-  int iteration = 0, term;
-  if (opt->verbosity >= 2) lm_print_header(cost);
-  // One host round trip per iteration: Schur, solve, step, candidate AND the candidate's linearisation (into the other
-  // set: its cost is the candidate's cost, and an accepted step has its next linearisation already) are enqueued, one
-  // copy brings the flags and scalars back, the host applies lm_policy.h.
-  while (true) {
-    if (iteration >= opt->max_num_iterations) { sum.termination = 0; break; }
-    if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
-    iteration++;
-    if ((rc = rig_schur(ctx, st, true, 1.0 / lm.radius))) return rc;
-    if ((rc = rig_solve(ctx, st))) return rc;
-    if ((rc = rig_step(ctx, st))) return rc;
-    if ((rc = rig_linearize(ctx, st, st.cand, true, 5))) return rc;
-    if ((rc = rig_columns(ctx, st, st.cand))) return rc;
-    if ((rc = rig_diag_gmax(ctx, st, st.cand, 6))) return rc;
-    VSL_HIP(ctx, hipMemcpyAsync(hsc, st.scalars, 16 * sizeof(double) + 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const double model_change = hsc[2], step_norm = sqrt(hsc[3]), x_norm = sqrt(hsc[4]), cand_cost = hsc[5];
-    const bool ok = hflag[0] != 0 && hflag[1] != 0 && model_change > 0.0;
-    const double radius_used = lm.radius;
-    LmInfo info;
-    const int verdict = lm_judge(lm, ok, cost, cand_cost, model_change, step_norm, x_norm, &info);
-    if (verdict == LM_ACCEPTED) std::swap(st.cur, st.cand);
-    if (verdict >= 0) { sum.termination = verdict; break; }
-    if (verdict == LM_INVALID) {
-      if (opt->verbosity >= 2) lm_print_invalid(iteration, lm.radius);
-      continue;
-    }
-    if (opt->verbosity >= 2) lm_print_row(iteration, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
-    if (verdict == LM_ACCEPTED) {
-      cost = cand_cost;
-      gmax = hsc[6];
-      sum.successful_steps++;
-    }
-  }
-  sum.iterations = iteration;
-  sum.final_cost = cost;
-  // the cameras of the final bodies (the current set's were derived when it was linearised)
-  VSL_HIP(ctx, hipMemcpyAsync(rig->body_poses, st.cur.bodies, sizeof(double) * 7 * (size_t)D.B, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.cur.cams, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.cur.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
-  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  double ms;
-  int64_t cnt;
-  vsl_ctx_stage_ms(ctx, VSL_STAGE_BA_LIN, &ms, &cnt);
-  sum.linearize_ms = ctx->stage_ms[VSL_STAGE_BA_LIN] - base_ms[0];
-  sum.schur_ms = ctx->stage_ms[VSL_STAGE_BA_SCHUR] - base_ms[1];
-  sum.solve_ms = ctx->stage_ms[VSL_STAGE_BA_SOLVE] - base_ms[2];
-  vsl_ctx_set_profiling(ctx, prof_was ? 1 : 0);
-  sum.total_ms = now_ms() - t_start;
-  if (opt->verbosity >= 1)
-    fprintf(stderr, "vsl rig BA: %d free bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", D.nfree,
-            sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
-  if (summary) *summary = sum;
-  return VSL_OK;
+  rc = rig_solve_run(ctx, prob, rig, opt, st, t_start, summary);
+  return rc ? rig_drain(ctx, rc) : VSL_OK;
 }
 
 // ================================================================================================== COVARIANCES
@@ -1075,14 +832,6 @@ __global__ __launch_bounds__(64) void rig_cov_landmark_kernel(int n, const int* 
   }
 }
 
-// the S of vsl_ba_rig_linearize in st.S, the stored blocks in st.cur
-int rig_cov_system(vsl_ctx* ctx, RigState& st) {
-  int rc;
-  if ((rc = rig_linearize(ctx, st, st.cur, false, 0))) return rc;
-  if ((rc = rig_columns(ctx, st, st.cur))) return rc;
-  return rig_schur(ctx, st, false, 0.0);
-}
-
 const char* const RIG_NOT_PD = "%s: the reduced body system is not positive definite";
 
 // everything of the marginal call behind the validation; host_in / host_out outlive the stream work (the caller
@@ -1108,7 +857,7 @@ int rig_cov_run(vsl_ctx* ctx, const char* who, const vsl_ba_problem* prob, const
   VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), P.in_bytes, hipMemcpyHostToDevice, ctx->stream));
   int* ok = (int*)(dev + P.off_ok);
   double* X = (double*)(dev + P.off_X);
-  if ((rc = rig_cov_system(ctx, st))) return rc;
+  if ((rc = rig_unscaled_system(ctx, st))) return rc;
   if (P.nQ > 0) {
     VslStage s(ctx, VSL_STAGE_BA_SOLVE);
     const VslCovInverse inv{n, 0, 0, st.S, nullptr, (double*)(dev + P.off_Linv), (double*)(dev + P.off_Sdiag),
@@ -1161,7 +910,7 @@ int rig_rel_run(vsl_ctx* ctx, const char* who, const vsl_ba_problem* prob, const
   const PgcPairDev* pairs = (const PgcPairDev*)(dev + P.off_pairs);
   double* X = (double*)(dev + P.off_X);
   double* joint = (double*)(dev + P.out_off + P.off_joint);
-  if ((rc = rig_cov_system(ctx, st))) return rc;
+  if ((rc = rig_unscaled_system(ctx, st))) return rc;
   {
     VslStage s(ctx, VSL_STAGE_BA_SOLVE);
     const VslCovInverse inv{n, 0, 0, st.S, nullptr, (double*)(dev + P.off_Linv), (double*)(dev + P.off_Sdiag),

@@ -1,6 +1,8 @@
 // ba_state.h -- host-side state of the general bundle-adjustment path (ba.hip) and the host launchers that ba.hip, the
-// home of the ba_* kernels, shares with the session solver (ba_session.hip).  The build has no relocatable device code:
-// a kernel is launched from the file that defines it, so ba_session.hip reaches the ba_* kernels through these.
+// home of the ba_* kernels, shares with the session solver (ba_session.hip), the covariances (ba_cov.hip) and the
+// rig-constrained solver (ba_rig.hip).  The build has no relocatable device code: a kernel is launched from the file that
+// defines it, so the other files reach the ba_* kernels through these -- the session and the covariances through the
+// BaCommon launchers, the rig chain (its own state) through the plain-pointer launchers at the end of this file.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -170,3 +172,54 @@ int ba_candidate(vsl_ctx* ctx, BaCommon& st, BaStored& sb);
 int ba_max_of(vsl_ctx* ctx, const double* v, int n, double* dst);
 // the first n scalars, on the host.  Synchronises.
 int read_scalars(vsl_ctx* ctx, BaCommon& st, double* out, int n);
+
+// ---- ba.hip: plain-pointer launchers.  They take device pointers and counts, no BaCommon / BaStored, so the rig chain
+// (ba_rig.hip, its own state and plan) runs on the same kernels; the launchers above are written on them, and each of
+// these kernels has this one launch site.  All enqueue on ctx->stream and check the launch.
+// dc = -(S^-1 rhs) for n <= 128 by one workgroup; *ok_flag (device-visible memory) = 1 / 0
+int vsl_ba_chol_small_launch(vsl_ctx* ctx, int n, const double* S, const double* rhs, double* dc, int* ok_flag);
+// ba_linearize_kernel over the D.O observations (reads O, model0 / model1, use_huber, huber of D): robustified r, F, E,
+// scaled when scale_c / scale_l are given, cost partials [(O + 255) / 256].  tcb == nullptr: F against the camera pose
+// (cam_free: camera -> free-camera slot).  tcb = T_c_b tables [2][12] (rig): poses are the cameras derived from the
+// bodies, cam_free maps a camera to its body's slot, F = F_c Ad(T_c_b) against the body pose
+int vsl_ba_linearize_launch(vsl_ctx* ctx, const BaDims& D, const double* poses, const double* points, const double* intr,
+                            const double* tcb, const int* cam_intr, const int* cam_free, const int* obs_cam, const int* obs_lm,
+                            const double* obs_uv, const double* scale_c, const double* scale_l, double* r, double* F, double* E,
+                            double* partials);
+// scalars[slot] = sum (or max) of partials[0, n) in a fixed order
+int vsl_ba_reduce_launch(vsl_ctx* ctx, const double* partials, int n, double* scalars, int slot, bool is_max);
+// scalars[slot], scalars[slot + 1] = sums of partials[0, n), partials[n, 2 n)
+int vsl_ba_reduce2_launch(vsl_ctx* ctx, const double* partials, int n, double* scalars, int slot);
+// per landmark: squared column norms of E (n2l) and E^T r (grad_l)
+int vsl_ba_lm_cols_launch(vsl_ctx* ctx, int L, const int* lm_start, const double* r, const double* E, double* n2l, double* grad_l);
+// part[(block, segment)][27] -> H (6 x 6, mirrored) and g per pose block, segments in order
+int vsl_ba_block_finish_launch(vsl_ctx* ctx, int nfree, int nseg, const double* part, double* H, double* g);
+// Jacobi scaling 1 / (1 + sqrt(column norm^2)) from diag H and n2l
+int vsl_ba_make_scale_launch(vsl_ctx* ctx, int nfree, int L, const double* H, const double* n2l, double* scale_c, double* scale_l);
+// LM diagonals clamp(column norm^2, 1e-6, 1e32) and scalars[slot] = max |gradient| of the unscaled problem; gabs: one
+// double per 256 of max(6 nfree, 3 L)
+int vsl_ba_diag_gmax_launch(vsl_ctx* ctx, int nfree, int L, const double* H, const double* n2l, const double* g_c, const double* grad_l,
+                            const double* scale_c, const double* scale_l, double* diag_c, double* diag_l, double* gabs,
+                            double* scalars, int slot);
+// model cost change partials [(O + 255) / 256]; cam_free: camera -> slot of its pose block in dc (-1: fixed)
+int vsl_ba_model_launch(vsl_ctx* ctx, int O, const int* obs_cam, const int* obs_lm, const int* cam_free, const double* r,
+                        const double* F, const double* E, const double* dc, const double* dl, double* partials);
+// candidate pose blocks T * exp(step .* scale) (n_poses of them, pose_free: block -> slot or -1) and points; scalars[slot] /
+// [slot + 1] = squared step / x norms; partials: 2 * ((max(n_poses, L) + 255) / 256)
+int vsl_ba_update_launch(vsl_ctx* ctx, int n_poses, int L, const int* pose_free, const double* poses, const double* points,
+                         const double* dc, const double* dl, const double* scale_c, const double* scale_l, double* cand_poses,
+                         double* cand_points, double* partials, double* scalars, int slot);
+
+// ---- ba.hip: what the two speculative host loops (vsl_bundle_adjust, vsl_bundle_adjust_rig) share besides
+// lm_speculative_loop (lm_policy.h)
+// the loop's one copy per iteration: the 16 scalars and the two flags behind them, through the context's pinned block.
+// Synchronises.
+int ba_fetch_step(vsl_ctx* ctx, const double* scalars, double* sc16, int* flags2);
+// taken before the first stage of a solve; ba_finish_summary fills the times of `sum` from it (stage times only under
+// profiling), prints "<label> iterations ..." at verbosity >= 1 and copies sum to *out when out is not null
+struct BaSolveTimes {
+  double t_start, base_ms[3];
+  bool prof_was;
+  BaSolveTimes(vsl_ctx* ctx, double t_start_ms);
+};
+void ba_finish_summary(vsl_ctx* ctx, const BaSolveTimes& t, int verbosity, const char* label, vsl_ba_summary& sum, vsl_ba_summary* out);

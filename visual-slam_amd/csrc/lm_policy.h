@@ -4,6 +4,8 @@
 // LEVENBERG_MARQUARDT, monotonic steps, default options: initial_trust_region_radius 1e4, max_ / min_trust_region_radius
 // 1e16 / 1e-32, min_relative_decrease 1e-3, function_ / gradient_ / parameter_tolerance 1e-6 / 1e-10 / 1e-8,
 // max_num_consecutive_invalid_steps 5 (max_num_iterations is tested by the caller: its place differs from loop to loop).
+// lm_speculative_loop at the end is the whole host loop of the two solvers whose loops have one shape (ba.hip's host path,
+// ba_rig.hip).
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -88,3 +90,58 @@ inline void lm_print_row(int it, double cand_cost, double cost_change, double gm
   fprintf(stderr, "%4d % .6e % .3e % .3e % .3e % .3e % .3e\n", it, cand_cost, cost_change, gmax, step_norm, rel, radius_used);
 }
 inline void lm_print_invalid(int iteration, double radius) { fprintf(stderr, "%4d  invalid step, radius %.3e\n", iteration, radius); }
+
+// The speculative host loop of vsl_bundle_adjust (ba.hip, "ba_no_fused" and mid-size windows) and vsl_bundle_adjust_rig
+// (ba_rig.hip), host only and free of HIP types (tests/cpp/lm_policy_test.cpp drives it with scripted callables).  ONE
+// host round trip per iteration:
+//   enqueue(radius) -> rc   Schur complement, solve, step, candidate AND the candidate's linearisation into the solver's
+//                           second set of blocks, nothing waited for
+//   fetch(sc, flags) -> rc  the one copy and synchronisation: sc[2] model cost change, sc[3] / sc[4] squared step / x norms,
+//                           sc[5] / sc[6] cost / max |gradient| at the candidate; flags[0] step finite, flags[1]
+//                           factorisation succeeded
+//   settle(accepted)        after the verdict: the candidate's set becomes the current one, or stays the spare
+// cost / gmax: of the starting point.  A non-zero rc of enqueue or fetch is returned at once, out untouched, settle not
+// called.
+struct LmLoopResult {
+  int iterations = 0, successful_steps = 0, termination = 0;
+  double final_cost = 0.0;
+};
+
+template <class Enqueue, class Fetch, class Settle>
+int lm_speculative_loop(int max_num_iterations, int verbosity, double cost, double gmax, Enqueue&& enqueue, Fetch&& fetch,
+                        Settle&& settle, LmLoopResult* out) {
+  LmState lm;
+  LmLoopResult res;
+  if (verbosity >= 2) lm_print_header(cost);
+  while (true) {
+    if (res.iterations >= max_num_iterations) { res.termination = 0; break; }
+    const int gate = lm_gate(lm, gmax);
+    if (gate >= 0) { res.termination = gate; break; }
+    res.iterations++;
+    int rc;
+    double sc[16];
+    int flags[2];
+    if ((rc = enqueue(lm.radius))) return rc;
+    if ((rc = fetch(sc, flags))) return rc;
+    const double model_change = sc[2], step_norm = sqrt(sc[3]), x_norm = sqrt(sc[4]), cand_cost = sc[5];
+    const bool ok = flags[0] != 0 && flags[1] != 0 && model_change > 0.0;
+    const double radius_used = lm.radius;
+    LmInfo info;
+    const int verdict = lm_judge(lm, ok, cost, cand_cost, model_change, step_norm, x_norm, &info);
+    settle(verdict == LM_ACCEPTED);
+    if (verdict >= 0) { res.termination = verdict; break; }
+    if (verdict == LM_INVALID) {
+      if (verbosity >= 2) lm_print_invalid(res.iterations, lm.radius);
+      continue;  // the LM diagonal is reused (the Jacobian is unchanged)
+    }
+    if (verbosity >= 2) lm_print_row(res.iterations, cand_cost, info.cost_change, gmax, step_norm, info.rel, radius_used);
+    if (verdict == LM_ACCEPTED) {
+      cost = cand_cost;
+      gmax = sc[6];
+      res.successful_steps++;
+    }
+  }
+  res.final_cost = cost;
+  *out = res;
+  return 0;
+}

@@ -123,8 +123,6 @@ int vsl_fail(vsl_ctx* ctx, int code, const char* fmt, ...);
 
 // ba_fused.hip: the local-window LM loop in four launches per iteration; *handled = 0 when the problem does not fit it
 int vsl_ba_fused_solve(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, vsl_ba_summary* summary, int* handled);
-// ba.hip: dc = -(S^-1 rhs) for n <= 128 by one workgroup (enqueued); *ok_flag (device-visible memory) = 1 / 0
-int vsl_ba_chol_small_launch(vsl_ctx* ctx, int n, const double* S, const double* rhs, double* dc, int* ok_flag);
 
 #define VSL_HIP(ctx, call)                                                                        \
   do {                                                                                            \
