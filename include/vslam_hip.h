@@ -315,6 +315,10 @@ int vsl_find_inliers_essential(vsl_ctx* ctx, int model_a, const double* intr8_a,
  * the first n_images slots produced in its last detect call -- the input size of the selection
  * stage, needed to price its traffic. */
 int vsl_frames_download_candidate_counts(vsl_ctx* ctx, vsl_frames* f, int n_images, int32_t* n_candidates);
+/* Diagnostic: the response maximum the selection stage of the last detect call used for each of the first n_images
+ * slots (the response kernel takes it over the candidates and the image border, detect.hip "Image maximum"); equal to
+ * the maximum of the response image whenever that is positive, and <= 0 otherwise. */
+int vsl_frames_download_response_max(vsl_ctx* ctx, vsl_frames* f, int n_images, float* response_max);
 
 /* Diagnostic: the response kernel evaluates sqrt as rsq + one fused correction step; this compares that sequence
  * with the correctly rounded sqrtf on EVERY float bit pattern in [lo_bits, hi_bits] (non-negative floats) on the

@@ -1268,6 +1268,12 @@ class Frames:
                                                                      nc.ctypes.data_as(i32p)))
         return nc[:n_images].copy()
 
+    def response_max(self, n_images):
+        mx = np.zeros(max(n_images, 1), np.float32)
+        self.ctx._ck(self.ctx.L.vsl_frames_download_response_max(self.ctx.h, self.h, int(n_images),
+                                                                 mx.ctypes.data_as(C.POINTER(C.c_float))))
+        return mx[:n_images].copy()
+
     def counts(self, n_images, n_pairs):
         nk = np.zeros(max(n_images, 1), np.int32)
         nm = np.zeros(max(n_pairs, 1), np.int32)

@@ -448,6 +448,17 @@ extern "C" int vsl_frames_download_candidate_counts(vsl_ctx* ctx, vsl_frames* f,
   return VSL_OK;
 }
 
+extern "C" int vsl_frames_download_response_max(vsl_ctx* ctx, vsl_frames* f, int n_images, float* response_max) {
+  if (!ctx || !f || n_images < 0 || n_images > f->max_images || !response_max)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_frames_download_response_max: bad arguments");
+  if (n_images == 0) return VSL_OK;
+  std::vector<int32_t> m((size_t)n_images * VSL_META_STRIDE);
+  VSL_HIP(ctx, hipMemcpyAsync(m.data(), f->meta, sizeof(int32_t) * m.size(), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < n_images; i++) response_max[i] = vsl_ordered_to_float(m[(size_t)i * VSL_META_STRIDE + VSL_META_MAX_LAST]);
+  return VSL_OK;
+}
+
 extern "C" int vsl_frames_download_keypoints(vsl_ctx* ctx, vsl_frames* f, int slot, int cap, double* corners_xy,
                                              double* angles, uint64_t* desc, int* n_out) {
   if (!ctx || !f || slot < 0 || slot >= f->max_images || !n_out || cap < 0)

@@ -19,19 +19,22 @@
 
 #include "vsl_common.h"
 
-// rows per wave strip; (K1_ROWS + 4) % 6 is 3 or 4 (that many opening steps, then the row loop unrolled by six).  Every
-// strip recomputes 4 halo rows, so taller strips waste less; 60 rows: 480 rows = 8 strips = 2 workgroups of 4 waves with
-// no idle wave, and 1024 images are exactly 13 rounds of 8 workgroups per compute unit (measured per 1024 images,
-// older kernel: 29 rows 0.771 ms, 32: 0.740, 41: 0.712, 44: 0.716; this kernel: 41 rows 0.654, 60 rows 0.638)
+// rows per wave strip.  Every strip recomputes 4 halo rows and pays one reloading step, one maximum reduction, one
+// quality cut and one list flush, so taller strips waste less (a 480-row image: 60 rows = 512 row steps, 120 = 496,
+// 160 = 492, 240 = 488).  The strips of an image are numbered column strip by column strip and dealt to workgroups
+// four at a time (see the kernel), so any height fills the waves; DESIGN.md 8.2 has the measured table.
 #ifndef K1_ROWS
-#define K1_ROWS 60
+#define K1_ROWS 120
 #endif
 #ifndef K1_ROWS_SMALL
-#define K1_ROWS_SMALL 29  // strips of launches of fewer than 8 images (17 strips of a 480-row image instead of 8)
+#define K1_ROWS_SMALL 30  // strips of launches of fewer than 8 images (16 strips of a 480-row image)
 #endif
 // goodFeaturesToTrack's qualityLevel as the reference passes it (keypoints.h:138): threshold = max response * 0.01
 #define VSL_QUALITY_LEVEL 0.01
-#define K1_WLIST 384  // LDS candidate slots per wave strip (60 x 60 pixels); overflow goes straight to global memory
+#define K1_WLIST 384  // LDS candidate slots per wave; a strip that collects more drains its list on the way (K1_FLUSH_ROOM)
+// the list is checked once per six row steps and drained when fewer than this many slots are left (noise images make
+// ~7 candidates per row step, real frames 2 to 3); a plateau that outruns it takes the direct global append
+#define K1_FLUSH_ROOM 96
 #define K1_COLS 60  // owned columns per wave: 64 lanes minus two halo lanes on each side
 
 __device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
@@ -162,8 +165,9 @@ __global__ void detect_init_kernel(int32_t* meta, int first, int n) {
   }
 }
 
-// K1 + K2a fused.  One workgroup of 256 threads per tile (ceil(w/60) x ceil(h/(4*K1_ROWS)) tiles per image, 1-D grid, see
-// below): wave v owns the K1_ROWS-row strip (tile_y*4 + v) of the 60-column strip tile_x.
+// K1 + K2a fused.  An image is cut into ceil(w/60) x ceil(h/ROWS) strips of 60 columns x ROWS rows, numbered down the
+// rows of a column strip first; a workgroup of 256 threads takes four consecutive strips, one per wave (1-D grid, see
+// below), so only the last workgroup of an image can hold idle waves whatever ROWS is.
 // One image column per lane; rows
 // are walked top to bottom with the row-filter results, the fp64 row sums and three response rows held
 // in registers; column neighbours come from DPP lane shifts.  Nothing but the image is read and -- in
@@ -181,11 +185,37 @@ __global__ void detect_init_kernel(int32_t* meta, int first, int n) {
 // Key = (order-preserving fp32 bits << 32) | y << 16 | x (ordered like the pixel index y * w + x, and the selection
 // kernel gets the position back without a division): a descending sort on the key is the
 // reference's order (value descending, equal values by address descending).
+//
+// Image maximum.  A pixel that holds a positive image maximum has no larger neighbour, so it is a provisional candidate
+// wherever a pixel may be one; only row 0, row h - 1, column 0 and column w - 1 may not.  The maximum over the emitted
+// candidates and those border pixels is therefore the image maximum whenever that is positive, bit for bit; when it is
+// not, the value stored is <= 0 as well and there are no corners either way.  Interior row steps update no maximum.
+
+// Quality cut of a wave's LDS list against a maximum `vmax` that the image maximum is known to reach: the selection
+// kernel drops every candidate at or below (float)(max * 0.01) (monotone in max), so a key at or below the threshold
+// of ANY lower bound of the image maximum can never survive.  Exact: only keys the selection kernel would discard are
+// removed.  In-place, order-preserving compaction by the whole wave; returns the number of keys kept.
+__device__ __forceinline__ int k1_quality_cut(uint64_t* list, int have, float vmax, int lane) {
+  if (!(vmax > 0.f) || have <= 0) return have;
+  const float thr = (float)((double)vmax * VSL_QUALITY_LEVEL);
+  const uint32_t floor_hi = (uint32_t)vsl_float_to_ordered(thr) ^ 0x80000000u;
+  int kept = 0;
+  for (int i0 = 0; i0 < have; i0 += 64) {
+    const int i = i0 + lane;
+    const uint64_t key = i < have ? list[i] : 0ull;
+    const bool keep = i < have && (uint32_t)(key >> 32) > floor_hi;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
+    if (keep) list[kept + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = key;
+    kept += __popcll(m);
+  }
+  return kept;
+}
+
 template <bool STORE_RESPONSE, int ROWS>
 __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __restrict__ images,
                                                                float* __restrict__ response, int32_t* __restrict__ meta,
                                                                uint64_t* __restrict__ cand, size_t cand_cap, int w, int h,
-                                                               int first, int wlist_cap, int n_images, int tiles_x, int tiles_y) {
+                                                               int first, int wlist_cap, int n_images, int tiles_x, int strips_y) {
   __shared__ uint64_t list[4][K1_WLIST];  // wave-private lists: appended with a scalar counter, no atomics
   __shared__ int wave_n[4], wave_max[4], g_base;
   __shared__ double xbuf[4][2][66];  // lane exchange of two of the three products: slot lane + 1 of the wave's row (slots 0 / 65 are
@@ -195,7 +225,8 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
   // (x, y, image) grid every XCD fetched most of every image (FETCH_SIZE, calibrated: 3.75 x the image bytes per
   // launch); here workgroup b works for XCD b % 8, which takes the images congruent to it modulo 8, all tiles of one
   // image consecutively -- the same trick as the describe kernel.  Speed only: any placement computes the same.
-  const int tiles = tiles_x * tiles_y;
+  const int strips = tiles_x * strips_y;  // of one image
+  const int tiles = (strips + 3) >> 2;    // workgroups of one image
   int img_i, tile;
   if (n_images >= 8) {
     const int xcd = blockIdx.x & 7, sl = blockIdx.x >> 3;
@@ -206,17 +237,20 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
     tile = blockIdx.x - img_i * tiles;
   }
   if (img_i >= n_images) return;  // workgroup-uniform (the padded tail of the last group of eight)
-  const int bx = tile % tiles_x, by = tile / tiles_x;
   const int slot = first + img_i;
   const ImgSrd img = __builtin_amdgcn_make_buffer_rsrc((void*)(images + (size_t)slot * w * h), 0, w * h, 0x00020000);
   float* __restrict__ resp = response + (size_t)slot * w * h;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // row bookkeeping below stays scalar
+  const int strip = tile * 4 + wave;  // wave-uniform, like everything derived from it
+  const int bx = strip / strips_y;
   const int xs = bx * K1_COLS;
-  const int y0 = (by * 4 + wave) * ROWS;
+  const int y0 = (strip - bx * strips_y) * ROWS;
+  int* const ncand = &meta[(size_t)slot * VSL_META_STRIDE + VSL_META_NCAND];
+  uint64_t* const cand_img = cand + (size_t)slot * cand_cap;
   int n_wave = 0;  // wave-uniform
-  int own_max = INT32_MIN;  // ordered bits of the largest response of this wave's strip
-  if (y0 < h) {
+  int own_max = INT32_MIN;  // ordered bits of the wave's maximum: its candidates and its pixels on the image border
+  if (strip < strips) {
     const float s = (float)(1.0 / (4.0 * 3.0 * 255.0));
     const float s2 = 2.0f * s;
     const int x = xs - 2 + lane;
@@ -225,6 +259,9 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
     const bool own_col = lane >= 2 && lane < 2 + K1_COLS && x < w;
     const bool cand_col = own_col && x >= 1 && x < w - 1;
     const unsigned long long cand_lanes = __builtin_amdgcn_ballot_w64(cand_col);
+    // pixels that can hold the image maximum without being candidates (see "Image maximum" above)
+    const bool edge_strip = xs == 0 || xs + K1_COLS >= w;  // the strip holds image column 0 or w - 1
+    const bool edge_lane = own_col && (x == 0 || x == w - 1);
 
     // Register state of the walk down the strip (roles rotated by NAME, no register-to-register moves):
     //  * two generations of fp64 row sums R(x, q) and one PAIR sum.  Every fp64 sum here is exact (each product is a
@@ -332,9 +369,13 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
                    "v_max_f32_dpp %1, %2, %0 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
                    : "=&v"(h_tmp), "=&v"(h_dn)
                    : "v"(v_dn));
-      if (own_col && y >= y0 && y < y_end) {
-        if (STORE_RESPONSE) resp[y * w + x] = v_dn;
-        vmax = fmax2(vmax, v_dn);
+      if (STORE_RESPONSE) {
+        if (own_col && y >= y0 && y < y_end) resp[y * w + x] = v_dn;
+      }
+      // the maximum of the border pixels; a STEADY step owns no pixel of row 0 or row h - 1
+      const bool edge_row = !STEADY && (y == 0 || y == h - 1);
+      if ((edge_strip || edge_row) && y >= y0 && y < y_end) {  // scalar
+        if (edge_row ? own_col : edge_lane) vmax = fmax2(vmax, v_dn);
       }
       // candidate test for row yc = q - 2: v_mid > 0 and no larger value among its 8 neighbours  <=>  v_mid > 0 and
       // v_mid >= the maximum of the 3 x 3 block (itself included) = max3 of the three H rows.  The sign test waits
@@ -348,21 +389,39 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
           const bool ge = ge0 && v_mid > 0.f;
           const unsigned long long mask = __builtin_amdgcn_ballot_w64(ge) & cand_lanes;
           if (cand_col && ge) {
+            vmax = fmax2(vmax, v_mid);  // ... and of the candidates
             const uint32_t ob = (uint32_t)vsl_float_to_ordered(v_mid) ^ 0x80000000u;
             const uint64_t key = ((uint64_t)ob << 32) | ((uint32_t)yc << 16) | (uint32_t)x;
             const int p = n_wave + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
             if (__builtin_expect(p < wlist_cap, 1)) {
               list[wave][p] = key;
-            } else {  // more than K1_WLIST candidates in one 60 x 41 strip (plateaus): rare direct append
-              const int g = atomicAdd(&meta[(size_t)slot * VSL_META_STRIDE + VSL_META_NCAND], 1);
-              if ((size_t)g < cand_cap) cand[(size_t)slot * cand_cap + g] = key;
+            } else {  // the list filled up between two flush checks (plateaus): rare direct append
+              const int g = atomicAdd(ncand, 1);
+              if ((size_t)g < cand_cap) cand_img[g] = key;
             }
           }
           n_wave += __popcll(mask);
         }
       }
       v_dn_slot = v_dn;
+    };
+    // Mid-strip flush: the quality cut against the wave's running maximum (the image maximum is at least that), then
+    // the survivors go to the image's global list behind one reservation.  Wave-private, no barrier; the keys are
+    // unique and the selection kernel sorts them, so their order in the global list is free.
+    auto flush = [&]() {
+      float m = vmax;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      const int kept = k1_quality_cut(list[wave], min(n_wave, wlist_cap), m, lane);
+      if (kept > 0) {
+        int g = 0;
+        if (lane == 0) g = atomicAdd(ncand, kept);
+        g = __builtin_amdgcn_readfirstlane(g);
+        for (int i = lane; i < kept; i += 64)
+          if ((size_t)(g + i) < cand_cap) cand_img[g + i] = list[wave][i];
+      }
+      n_wave = 0;
     };
     const int q_first = y0 - 2, q_last = y_end + 1;
     typedef std::integral_constant<bool, true> Steady;
@@ -376,39 +435,61 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
 #define K1_STEP_O3(T, q) step(T{}, Odd{}, q, rb, ra, vb, va, hA, hB, hC, fA, fB, fC)
 #define K1_STEP_E4(T, q) step(T{}, Even{}, q, ra, rb, va, vb, hB, hC, hA, fB, fC, fA)
 #define K1_STEP_O5(T, q) step(T{}, Odd{}, q, rb, ra, vb, va, hC, hA, hB, fC, fA, fB)
-    // K1_OPEN opening steps (the first one reloads everything), then the loop unrolled by six starting at role K1_OPEN
-    constexpr int K1_OPEN = (ROWS + 4) % 6;
-    static_assert(K1_OPEN == 3 || K1_OPEN == 4, "opening sequence written for 3 or 4 steps");
-#define K1_STRIP(T)                                \
-  K1_STEP_E0(Generic, q_first);                    \
-  K1_STEP_O1(T, q_first + 1);                      \
-  K1_STEP_E2(T, q_first + 2);                      \
-  if constexpr (K1_OPEN == 3) {                    \
-    for (int q = q_first + 3; q <= q_last; q += 6) { \
-      K1_STEP_O3(T, q);                            \
-      K1_STEP_E4(T, q + 1);                        \
-      K1_STEP_O5(T, q + 2);                        \
-      K1_STEP_E0(T, q + 3);                        \
-      K1_STEP_O1(T, q + 4);                        \
-      K1_STEP_E2(T, q + 5);                        \
-    }                                              \
-  } else {                                         \
-    K1_STEP_O3(T, q_first + 3);                    \
-    for (int q = q_first + 4; q <= q_last; q += 6) { \
-      K1_STEP_E4(T, q);                            \
-      K1_STEP_O5(T, q + 1);                        \
-      K1_STEP_E0(T, q + 2);                        \
-      K1_STEP_O1(T, q + 3);                        \
-      K1_STEP_E2(T, q + 4);                        \
-      K1_STEP_O3(T, q + 5);                        \
-    }                                              \
-  }
-    if (q_first >= 1 && q_last + 1 < h) {  // scalar: a strip whose halo rows are all interior
-      K1_STRIP(Steady)
+    // the step of role r (any r >= 0)
+#define K1_STEP_R(r, T, q)                            \
+  do {                                                \
+    if constexpr ((r) % 6 == 0) K1_STEP_E0(T, q);      \
+    else if constexpr ((r) % 6 == 1) K1_STEP_O1(T, q); \
+    else if constexpr ((r) % 6 == 2) K1_STEP_E2(T, q); \
+    else if constexpr ((r) % 6 == 3) K1_STEP_O3(T, q); \
+    else if constexpr ((r) % 6 == 4) K1_STEP_E4(T, q); \
+    else K1_STEP_O5(T, q);                            \
+  } while (0)
+    // a strip is ROWS + 4 steps: K1_OPEN (4 to 9) opening steps, the first of which reloads everything, then groups of
+    // six starting at role K1_OPEN.  Four at least, so that the first group starts at q >= 2 in every strip.
+    constexpr int K1_OPEN = ROWS % 6 + 4;
+#define K1_OPENING(T)                                          \
+  K1_STEP_R(1, T, q_first + 1);                                \
+  K1_STEP_R(2, T, q_first + 2);                                \
+  K1_STEP_R(3, T, q_first + 3);                                \
+  if constexpr (K1_OPEN > 4) K1_STEP_R(4, T, q_first + 4);     \
+  if constexpr (K1_OPEN > 5) K1_STEP_R(5, T, q_first + 5);     \
+  if constexpr (K1_OPEN > 6) K1_STEP_R(6, T, q_first + 6);     \
+  if constexpr (K1_OPEN > 7) K1_STEP_R(7, T, q_first + 7);     \
+  if constexpr (K1_OPEN > 8) K1_STEP_R(8, T, q_first + 8);
+#define K1_SIX(T, q)               \
+  K1_STEP_R(K1_OPEN, T, q);        \
+  K1_STEP_R(K1_OPEN + 1, T, q + 1); \
+  K1_STEP_R(K1_OPEN + 2, T, q + 2); \
+  K1_STEP_R(K1_OPEN + 3, T, q + 3); \
+  K1_STEP_R(K1_OPEN + 4, T, q + 4); \
+  K1_STEP_R(K1_OPEN + 5, T, q + 5);
+    // STEADY is decided per group of steps, not per strip (all scalar): rows q - 1 .. q + 1 of every step of the group
+    // are interior, none of its response rows is row 0 or h - 1 (q >= 2), and the step in front of it left row q - 1's
+    // state behind.  So a tall strip that touches the top or the bottom of the image runs generic steps only there: the
+    // opening, then a loop of steady groups, then at most two generic groups at the bottom of the image (a loop of its
+    // own: one loop with both kinds of group costs 26 more registers).
+    K1_STEP_E0(Generic, q_first);
+    if (q_first >= 1 && q_first + K1_OPEN < h) {
+      K1_OPENING(Steady)
     } else {
-      K1_STRIP(Generic)
+      K1_OPENING(Generic)
     }
-#undef K1_STRIP
+    const int flush_mark = max(wlist_cap - K1_FLUSH_ROOM, 0);
+    int q = q_first + K1_OPEN;
+    for (; q <= q_last && q + 6 < h; q += 6) {
+      K1_SIX(Steady, q)
+      if (n_wave > flush_mark) flush();
+    }
+    // steady steps keep no row bookkeeping: restored here for the generic ones
+    prev_ye = q - 1;
+    pre_row = min(q + 1, h - 1);
+    for (; q <= q_last; q += 6) {
+      K1_SIX(Generic, q)
+    }
+#undef K1_STEP_R
+#undef K1_OPENING
+#undef K1_SIX
 #undef K1_STEP_E0
 #undef K1_STEP_O1
 #undef K1_STEP_E2
@@ -422,40 +503,22 @@ __global__ __launch_bounds__(256) void min_eig_response_kernel(const uint8_t* __
   }
   if (lane == 0) wave_max[wave] = own_max;
   __syncthreads();
-  // Early quality cut: the image maximum is at least the maximum of this workgroup's four strips, and the selection
-  // kernel drops every candidate at or below (float)(max * 0.01) (monotone in max), so a candidate at or below the
-  // threshold of the workgroup's OWN maximum can never survive -- it is dropped here, before it costs 8 bytes of
-  // traffic each way (15.5k -> ~4.7k keys per synthetic frame, 17k -> ~9k on EuRoC frames).  Exact: only keys the
-  // selection kernel would discard are removed.
-  int kept = min(n_wave, wlist_cap);
-  {
-    const float wg_max = vsl_ordered_to_float(max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3])));
-    if (wg_max > 0.f && kept > 0) {
-      const float thr = (float)((double)wg_max * VSL_QUALITY_LEVEL);
-      const uint32_t floor_hi = (uint32_t)vsl_float_to_ordered(thr) ^ 0x80000000u;
-      const int have = kept;
-      kept = 0;
-      for (int i0 = 0; i0 < have; i0 += 64) {  // in-place, order-preserving compaction of the wave's own list
-        const int i = i0 + lane;
-        const uint64_t key = i < have ? list[wave][i] : 0ull;
-        const bool keep = i < have && (uint32_t)(key >> 32) > floor_hi;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
-        if (keep) list[wave][kept + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = key;
-        kept += __popcll(m);
-      }
-    }
-  }
+  // Final quality cut: the image maximum is at least the maximum of this workgroup's four waves, so what is left in the
+  // lists is cut against that (k1_quality_cut) before it costs 8 bytes of traffic each way (15.5k -> ~4.7k keys per
+  // synthetic frame, 17k -> ~9k on EuRoC frames).
+  const float wg_max = vsl_ordered_to_float(max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3])));
+  const int kept = k1_quality_cut(list[wave], min(n_wave, wlist_cap), wg_max, lane);
   if (lane == 0) wave_n[wave] = kept;
   __syncthreads();
   const int c0 = wave_n[0], c1 = wave_n[1], c2 = wave_n[2], c3 = wave_n[3];
   const int n = c0 + c1 + c2 + c3;
   if (n == 0) return;
-  if (threadIdx.x == 0) g_base = atomicAdd(&meta[(size_t)slot * VSL_META_STRIDE + VSL_META_NCAND], n);
+  if (threadIdx.x == 0) g_base = atomicAdd(ncand, n);
   __syncthreads();
   const int base = g_base + (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + (wave > 2 ? c2 : 0);
   const int mine = wave_n[wave];
   for (int i = lane; i < mine; i += 64)
-    if ((size_t)(base + i) < cand_cap) cand[(size_t)slot * cand_cap + base + i] = list[wave][i];
+    if ((size_t)(base + i) < cand_cap) cand_img[base + i] = list[wave][i];
 }
 
 // ------------------------------------------------------------------------------------------ K2b
@@ -1038,6 +1101,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(const uint64_t* __r
     kp_count[slot] = n_out;
     // every thread read MAX / NCAND before the first barrier: leave them reset for the next detect call
     meta[(size_t)slot * VSL_META_STRIDE + VSL_META_NCAND_LAST] = n_cand_raw;
+    meta[(size_t)slot * VSL_META_STRIDE + VSL_META_MAX_LAST] = vsl_float_to_ordered(maxv);
     meta[(size_t)slot * VSL_META_STRIDE + VSL_META_MAX] = INT32_MIN;
     meta[(size_t)slot * VSL_META_STRIDE + VSL_META_NCAND] = 0;
   }
@@ -1080,19 +1144,19 @@ int vsl_launch_detect(vsl_ctx* ctx, vsl_frames* f, int first, int n, int num_fea
     // a lone wave per SIMD issues one instruction per ~7 cycles, so such a launch is as long as its longest wave
     const bool small = n < 8 && !f->store_response;
     const int rows = small ? K1_ROWS_SMALL : K1_ROWS;
-    const int tiles_y = (h + 4 * rows - 1) / (4 * rows);
+    const int strips_y = (h + rows - 1) / rows;
     const int tiles_x = (w + K1_COLS - 1) / K1_COLS;
-    const dim3 k1_grid((unsigned)(tiles_x * tiles_y) * (unsigned)(n >= 8 ? 8 * ((n + 7) / 8) : n));
+    const dim3 k1_grid((unsigned)((tiles_x * strips_y + 3) / 4) * (unsigned)(n >= 8 ? 8 * ((n + 7) / 8) : n));  // four strips per workgroup
     const int wcap = ctx->k1_list_cap < 0 ? K1_WLIST : min(ctx->k1_list_cap, K1_WLIST);
     if (f->store_response)
       hipLaunchKernelGGL((min_eig_response_kernel<true, K1_ROWS>), k1_grid, dim3(256), 0, ctx->stream, f->images, f->response, f->meta,
-                         f->cand, f->cand_cap, w, h, first, wcap, n, tiles_x, tiles_y);
+                         f->cand, f->cand_cap, w, h, first, wcap, n, tiles_x, strips_y);
     else if (small)
       hipLaunchKernelGGL((min_eig_response_kernel<false, K1_ROWS_SMALL>), k1_grid, dim3(256), 0, ctx->stream, f->images, f->response, f->meta,
-                         f->cand, f->cand_cap, w, h, first, wcap, n, tiles_x, tiles_y);
+                         f->cand, f->cand_cap, w, h, first, wcap, n, tiles_x, strips_y);
     else
       hipLaunchKernelGGL((min_eig_response_kernel<false, K1_ROWS>), k1_grid, dim3(256), 0, ctx->stream, f->images, f->response, f->meta,
-                         f->cand, f->cand_cap, w, h, first, wcap, n, tiles_x, tiles_y);
+                         f->cand, f->cand_cap, w, h, first, wcap, n, tiles_x, strips_y);
     VSL_CHECK_LAUNCH(ctx);
   }
   {

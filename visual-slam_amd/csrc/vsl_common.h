@@ -23,6 +23,7 @@
 // detect / describe call needs no separate clearing launch; the last values stay readable here:
 #define VSL_META_NCAND_LAST 4
 #define VSL_META_NEXACT_LAST 5
+#define VSL_META_MAX_LAST 6
 #define VSL_EXACT_CAP 16384 // capacity of that per-image list
 #ifndef VSL_TILE_LX
 #define VSL_TILE_LX 7  // log2 width / height of the keypoint tiles of the batched describe kernel (describe.hip)
