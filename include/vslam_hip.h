@@ -654,9 +654,37 @@ int vsl_ctx_memcpy(vsl_ctx* ctx, void* dst, const void* src, size_t bytes, int k
 /* visnav::bundle_adjustment with BundleAdjustmentOptions::optimize_intrinsics = true (include/visnav/map_utils.h:324,
  * :397-403: the two intrinsics blocks are not set constant; wired to a hidden GUI variable, src/slam.cpp:304, :1545):
  * poses, landmarks AND the two 8-parameter intrinsics blocks are optimised jointly (same restated Ceres policy; the
- * parameters a model does not use keep their values).  intr_io [16] in/out; prob->intr is ignored. */
+ * parameters a model does not use keep their values).  intr_io [16] in/out; prob->intr is ignored.
+ * Unknowns of the reduced system, nt = 6 * n_free + 16: the free cameras in ascending id, 6 each, then intrinsics block
+ * 0 (8) and block 1 (8); it goes to the small dense Cholesky kernel while nt <= 128 (18 free cameras) and to the general
+ * SPD solver beyond.  An observation in a fixed camera still carries its intrinsics and landmark columns.  A problem
+ * with NO free camera is accepted (nt = 16: calibration against fixed poses; the landmarks still move): the pose part of
+ * every kernel is skipped by its cam_free test and no launch has an empty grid.  An intrinsics block that no camera
+ * uses has zero columns: scale 1, LM diagonal 1e-6 / radius, and its eight values keep their bits. */
 int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, double* intr_io,
                                  vsl_ba_summary* summary);
+/* Parity hook of vsl_bundle_adjust_intrinsics, the counterpart of vsl_ba_fused_system / vsl_ba_rig_system: the first
+ * linearisation of the solve and ONE system at 1 / radius = inv_radius (0 = no damping), built and solved by the routines
+ * and kernels the solve's loop itself calls, at the poses, points and intr16 handed in (prob->intr is ignored).  Nothing
+ * is optimised: every input is only read, opt->max_num_iterations is ignored, opt's Huber setting is used.
+ * With J = [F | G | E] per observation (G = d r / d intrinsics, 2 x 8, in the columns of the camera's block), H = J^T J
+ * with the Huber corrector, D = 1 / (1 + sqrt(diag H)) over ALL columns (1 where the column is zero) and
+ * H' = D H D + inv_radius * clamp(diag(D H D), 1e-6, 1e32):
+ *   G        [16 * n_obs] per observation in the caller's order, row-major 2 x 8: UNSCALED and WITHOUT the robustifier,
+ *            as vsl_ba_residuals_jacobians reports F and E; columns the model does not use are 0
+ *   scale    [nt] D of the camera and intrinsics columns
+ *   S        [nt * nt] row-major, full (both triangles are accumulated by atomics: equal up to rounding, not bitwise),
+ *            rhs [nt]: the landmarks eliminated from H', exactly as handed to the factorisation
+ *   cost     1/2 sum rho(|r|^2)
+ *   d        [nt] = -(S^-1 rhs), dl [3 * n_lms] the back-substituted landmark step, both in the SCALED variables
+ *            (undefined when *chol_ok == 0)
+ *   chol_ok  0 when a pivot of the factorisation was not positive and finite: reported with VSL_OK; with chol_ok NULL it
+ *            is VSL_ERR_NUMERIC after the other outputs are written
+ * Every output pointer may be NULL.  VSL_ERR_INVALID, nothing written: ctx, prob, opt or intr16 null, whatever
+ * vsl_bundle_adjust refuses in prob, inv_radius negative or not finite. */
+int vsl_ba_intrinsics_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const double* intr16,
+                             double inv_radius, double* G, double* scale, double* S, double* rhs, double* cost, double* d,
+                             double* dl, int* chol_ok);
 /* ---- rig-constrained bundle adjustment: one pose per stereo frame (visual-slam_amd/csrc/ba_rig.hip) ----
  * Every other solve above treats the left and the right camera of a stereo frame as two independent SE(3) blocks, as
  * the reference does (src/slam.cpp:1215 sets T_w_c_right = pose * T_0_1 once and Ceres then moves the two apart).  Here

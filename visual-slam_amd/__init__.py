@@ -608,6 +608,24 @@ class Context:
                                                      C.byref(out)))
         return out
 
+    def ba_intrinsics_system(self, arr, inv_radius=0.0, use_huber=True, huber=1.0):
+        """The first linearisation of bundle_adjust_intrinsics and one scaled, damped reduced system [poses | intrinsics]
+        at 1 / radius = inv_radius, built and solved by the solve's own routines (vsl_ba_intrinsics_system): a dict with
+        G [n_obs, 2, 8] (unscaled, no robustifier), scale [nt], S [nt, nt], rhs [nt], cost, d [nt], dl [n_lms, 3] (scaled
+        variables), chol_ok, n_free; nt = 6 * n_free + 16.  Nothing in arr is changed."""
+        st = self._ba_struct(arr)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        nf = int((arr.cam_fixed == 0).sum())
+        nt = 6 * nf + 16
+        G = np.zeros((len(arr.obs_cam), 2, 8))
+        S, rhs, scale, d, dl = np.zeros((nt, nt)), np.zeros(nt), np.zeros(nt), np.zeros(nt), np.zeros((len(arr.points), 3))
+        cost, ok = C.c_double(), C.c_int32()
+        self._ck(self.L.vsl_ba_intrinsics_system(self.h, C.byref(st), C.byref(o), arr.intr.ctypes.data_as(f64p),
+                                                 C.c_double(inv_radius), G.ctypes.data_as(f64p), scale.ctypes.data_as(f64p),
+                                                 S.ctypes.data_as(f64p), rhs.ctypes.data_as(f64p), C.byref(cost),
+                                                 d.ctypes.data_as(f64p), dl.ctypes.data_as(f64p), C.byref(ok)))
+        return dict(G=G, scale=scale, S=S, rhs=rhs, cost=cost.value, d=d, dl=dl, chol_ok=ok.value, n_free=nf)
+
     def ba_linearize(self, arr, use_huber=True, huber=1.0, lm_first=0, lm_count=-1):
         st = self._ba_struct(arr)
         o = self._ba_opts(use_huber, huber, 0, 0)

@@ -2435,6 +2435,108 @@ __global__ void bai_intr_update_kernel(int n, const double* __restrict__ intr, c
   scalars[slot + 1] = x2;
 }
 
+// ---- host side of the intrinsics solver: its buffers beside BaState, and the three routines that the LM loop
+// (vsl_bundle_adjust_intrinsics) and the parity hook (vsl_ba_intrinsics_system) share, so that the hook cannot drift
+// from the solve
+struct BaiBuffers {
+  double *G, *scale, *n2, *grad, *diag, *Sf, *rhsf, *df, *cand_intr, *Tl;
+  DevArena arena;
+};
+
+int bai_acquire(vsl_ctx* ctx, const BaState& st, BaiBuffers& B) {
+  const BaDims& D = st.D;
+  const int nt = D.n + 16;
+  ArenaPlan plan(10);
+  plan.add(B.G, 16 * (size_t)D.O);
+  plan.add(B.scale, (size_t)nt);
+  plan.add(B.n2, (size_t)nt);
+  plan.add(B.grad, (size_t)nt);
+  plan.add(B.diag, (size_t)nt);
+  plan.add(B.Sf, (size_t)nt * nt);
+  plan.add(B.rhsf, (size_t)nt);
+  plan.add(B.df, (size_t)nt);
+  plan.add(B.cand_intr, 16);
+  plan.add(B.Tl, 48 * (size_t)D.L);
+  VSL_HIP(ctx, B.arena.acquire(ctx, ArenaPolicy::OWNED, plan));
+  return VSL_OK;
+}
+
+// at the CURRENT point; scalars[0] = cost.  D is passed so that the hook can ask for the blocks without the robustifier.
+int bai_linearize(vsl_ctx* ctx, BaState& st, BaiBuffers& B, const BaDims& D, bool scaled) {
+  BaStored& sb = st.sb;
+  hipLaunchKernelGGL(bai_linearize_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.poses, st.points, st.intr, st.cam_intr,
+                     st.cam_free, st.obs_cam, st.obs_lm, st.obs_uv, scaled ? B.scale : (const double*)nullptr,
+                     scaled ? st.scale_l : (const double*)nullptr, sb.r, sb.F, sb.E, B.G, sb.partials);
+  return vsl_ba_reduce_launch(ctx, sb.partials, st.nb_obs, st.scalars, 0, false);
+}
+
+// column norms / gradient of the current blocks; scalars[1] = max |gradient|
+int bai_stats(vsl_ctx* ctx, BaState& st, BaiBuffers& B, bool write_diag) {
+  BaStored& sb = st.sb;
+  const BaDims& D = st.D;
+  const int nt = D.n + 16, L3 = 3 * D.L;
+  hipStream_t q = ctx->stream;
+  VSL_HIP(ctx, hipMemsetAsync(B.n2, 0, 8 * (size_t)nt, q));
+  VSL_HIP(ctx, hipMemsetAsync(B.grad, 0, 8 * (size_t)nt, q));
+  VSL_HIP(ctx, hipMemsetAsync(st.n2l, 0, 8 * (size_t)L3, q));
+  VSL_HIP(ctx, hipMemsetAsync(sb.grad_l, 0, 8 * (size_t)L3, q));
+  hipLaunchKernelGGL(bai_stats_kernel, dim3(st.nb_obs), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, sb.r, sb.F,
+                     sb.E, B.G, B.n2, B.grad, st.n2l, sb.grad_l);
+  hipLaunchKernelGGL(bai_diag_gmax_kernel, dim3(1), dim3(256), 0, q, nt, L3, B.n2, st.n2l, B.grad, sb.grad_l, write_diag ? 1 : 0,
+                     B.diag, sb.diag_l, st.scalars, 1);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+// initial linearisation, Jacobi scaling from the unscaled column norms (once), statistics of the scaled blocks (they
+// write the LM diagonal); scalars[0] = cost, scalars[1] = max |gradient|
+int bai_first_linearization(vsl_ctx* ctx, BaState& st, BaiBuffers& B) {
+  BaStored& sb = st.sb;
+  const BaDims& D = st.D;
+  const int nt = D.n + 16, L3 = 3 * D.L;
+  int rc;
+  if ((rc = bai_linearize(ctx, st, B, D, false))) return rc;
+  if ((rc = bai_stats(ctx, st, B, false))) return rc;
+  hipLaunchKernelGGL(bai_make_scale_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, ctx->stream, nt, L3, B.n2, st.n2l,
+                     B.scale, st.scale_l);
+  hipLaunchKernelGGL(bai_apply_scale_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, D, st.cam_free, st.cam_intr, st.obs_cam,
+                     st.obs_lm, B.scale, st.scale_l, sb.F, sb.E, B.G);
+  return bai_stats(ctx, st, B, true);
+}
+
+// one system, built and solved: the reduced system [poses | intrinsics] of the stored blocks at 1 / radius = inv_radius
+// (J^T J of the camera side, damping, the Schur corrections camera-camera and border), its factorisation (flag[1] = 0 when
+// a pivot fails), B.df = -(Sf^-1 rhsf) and the back-substituted sb.dl.  host_S / host_rhs (nullable; the hook's) receive
+// the system as it is handed to the factorisation, by copies queued BEFORE it (the large solver works in place).
+int bai_build_and_solve(vsl_ctx* ctx, BaState& st, BaiBuffers& B, double inv_radius, double* host_S, double* host_rhs) {
+  BaStored& sb = st.sb;
+  const BaDims& D = st.D;
+  const int nt = D.n + 16;
+  hipStream_t q = ctx->stream;
+  int rc;
+  VSL_HIP(ctx, hipMemsetAsync(B.Sf, 0, 8 * (size_t)nt * nt, q));
+  VSL_HIP(ctx, hipMemsetAsync(B.rhsf, 0, 8 * (size_t)nt, q));
+  hipLaunchKernelGGL(bai_hess_kernel, dim3(st.nb_obs), dim3(256), 0, q, D, nt, st.cam_free, st.cam_intr, st.obs_cam, sb.r, sb.F, B.G,
+                     B.Sf, B.rhsf);
+  hipLaunchKernelGGL(bai_damp_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, B.diag, inv_radius, B.Sf);
+  hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free, sb.r,
+                     sb.F, sb.E, sb.diag_l, inv_radius, 0, D.L, B.Sf, B.rhsf, st.Pinv, st.bl, 0, nt);
+  hipLaunchKernelGGL(bai_border_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, nt, st.lm_start, st.obs_cam, st.cam_free,
+                     st.cam_intr, sb.F, sb.E, B.G, st.Pinv, st.bl, B.Tl, B.Sf, B.rhsf);
+  hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, q, st.flag);
+  if (host_S) VSL_HIP(ctx, hipMemcpyAsync(host_S, B.Sf, 8 * (size_t)nt * nt, hipMemcpyDeviceToHost, q));
+  if (host_rhs) VSL_HIP(ctx, hipMemcpyAsync(host_rhs, B.rhsf, 8 * (size_t)nt, hipMemcpyDeviceToHost, q));
+  if (nt <= 128) {
+    hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, q, nt, B.Sf, B.rhsf, B.df, st.flag + 1);
+  } else {
+    if ((rc = vsl_chol_solve_band_dev(ctx, B.Sf, B.rhsf, nt, nt, nt, st.flag + 1, 0, B.df))) return rc;  // df = -(Sf^-1 rhsf)
+  }
+  hipLaunchKernelGGL(bai_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free,
+                     st.cam_intr, sb.F, sb.E, B.G, st.Pinv, st.bl, B.df, sb.dl);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
 }  // namespace
 
 extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, double* intr_io,
@@ -2451,57 +2553,21 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
   BaStored& sb = st.sb;
   const BaDims& D = st.D;
   const int n = D.n, nt = n + 16, L3 = 3 * D.L;
-  double *G, *scale, *n2, *grad, *diag, *Sf, *rhsf, *df, *cand_intr, *Tl;
-  ArenaPlan plan(10);
-  plan.add(G, 16 * (size_t)D.O);
-  plan.add(scale, (size_t)nt);
-  plan.add(n2, (size_t)nt);
-  plan.add(grad, (size_t)nt);
-  plan.add(diag, (size_t)nt);
-  plan.add(Sf, (size_t)nt * nt);
-  plan.add(rhsf, (size_t)nt);
-  plan.add(df, (size_t)nt);
-  plan.add(cand_intr, 16);
-  plan.add(Tl, 48 * (size_t)D.L);
-  DevArena arena;
-  VSL_HIP(ctx, arena.acquire(ctx, ArenaPolicy::OWNED, plan));
+  BaiBuffers B;
+  if ((rc = bai_acquire(ctx, st, B))) return rc;
+  double *const G = B.G, *const scale = B.scale, *const df = B.df, *const cand_intr = B.cand_intr;
   vsl_ba_summary sum;
   memset(&sum, 0, sizeof(sum));
   hipStream_t q = ctx->stream;
   const int nbo = st.nb_obs;
   double* scal = st.scalars;
 
-  auto linearize = [&](bool scaled) -> int {  // at the CURRENT point; scalars[0] = cost
-    hipLaunchKernelGGL(bai_linearize_kernel, dim3(nbo), dim3(256), 0, q, D, st.poses, st.points, st.intr, st.cam_intr, st.cam_free,
-                       st.obs_cam, st.obs_lm, st.obs_uv, scaled ? scale : (const double*)nullptr,
-                       scaled ? st.scale_l : (const double*)nullptr, sb.r, sb.F, sb.E, G, sb.partials);
-    return vsl_ba_reduce_launch(ctx, sb.partials, nbo, scal, 0, false);
-  };
-  auto stats = [&](bool write_diag) -> int {  // column norms / gradient of the current blocks; scalars[1] = max |gradient|
-    VSL_HIP(ctx, hipMemsetAsync(n2, 0, 8 * (size_t)nt, q));
-    VSL_HIP(ctx, hipMemsetAsync(grad, 0, 8 * (size_t)nt, q));
-    VSL_HIP(ctx, hipMemsetAsync(st.n2l, 0, 8 * (size_t)L3, q));
-    VSL_HIP(ctx, hipMemsetAsync(sb.grad_l, 0, 8 * (size_t)L3, q));
-    hipLaunchKernelGGL(bai_stats_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, sb.r, sb.F,
-                       sb.E, G, n2, grad, st.n2l, sb.grad_l);
-    hipLaunchKernelGGL(bai_diag_gmax_kernel, dim3(1), dim3(256), 0, q, nt, L3, n2, st.n2l, grad, sb.grad_l, write_diag ? 1 : 0,
-                       diag, sb.diag_l, scal, 1);
-    VSL_CHECK_LAUNCH(ctx);
-    return VSL_OK;
-  };
   double h[16];
-  // initial linearisation, Jacobi scaling from the unscaled column norms (once), statistics of the scaled blocks
-  if ((rc = linearize(false))) return rc;
-  if ((rc = stats(false))) return rc;
-  hipLaunchKernelGGL(bai_make_scale_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, L3, n2, st.n2l, scale,
-                     st.scale_l);
-  hipLaunchKernelGGL(bai_apply_scale_kernel, dim3(nbo), dim3(256), 0, q, D, st.cam_free, st.cam_intr, st.obs_cam, st.obs_lm, scale,
-                     st.scale_l, sb.F, sb.E, G);
-  if ((rc = stats(true))) return rc;
+  if ((rc = bai_first_linearization(ctx, st, B))) return rc;
   if ((rc = read_scalars(ctx, st, h, 2))) return rc;
   double cost = h[0], gmax = h[1];
   sum.initial_cost = cost;
-  LmState lm;  // (stats(true) above wrote the LM diagonal of the current Jacobian)
+  LmState lm;  // (the first linearisation wrote the LM diagonal of the current Jacobian)
   int iteration = 0, term;
   sum.termination = 0;
   if (opt->verbosity >= 2) lm_print_header(cost);
@@ -2510,24 +2576,7 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     if ((term = lm_gate(lm, gmax)) >= 0) { sum.termination = term; break; }
     iteration++;
     const double inv_radius = 1.0 / lm.radius;
-    // reduced system: J^T J of the camera side, damping, Schur corrections (camera-camera, then the border)
-    VSL_HIP(ctx, hipMemsetAsync(Sf, 0, 8 * (size_t)nt * nt, q));
-    VSL_HIP(ctx, hipMemsetAsync(rhsf, 0, 8 * (size_t)nt, q));
-    hipLaunchKernelGGL(bai_hess_kernel, dim3(nbo), dim3(256), 0, q, D, nt, st.cam_free, st.cam_intr, st.obs_cam, sb.r, sb.F, G, Sf,
-                       rhsf);
-    hipLaunchKernelGGL(bai_damp_kernel, dim3((nt + 255) / 256), dim3(256), 0, q, nt, diag, inv_radius, Sf);
-    hipLaunchKernelGGL(ba_schur_atomic_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free, sb.r,
-                       sb.F, sb.E, sb.diag_l, inv_radius, 0, D.L, Sf, rhsf, st.Pinv, st.bl, 0, nt);
-    hipLaunchKernelGGL(bai_border_kernel, dim3((D.L + 3) / 4), dim3(256), 0, q, D, nt, st.lm_start, st.obs_cam, st.cam_free,
-                       st.cam_intr, sb.F, sb.E, G, st.Pinv, st.bl, Tl, Sf, rhsf);
-    hipLaunchKernelGGL(ba_set_flags_kernel, dim3(1), dim3(64), 0, q, st.flag);
-    if (nt <= 128) {
-      hipLaunchKernelGGL(ba_chol_small_kernel, dim3(1), dim3(256), 0, q, nt, Sf, rhsf, df, st.flag + 1);
-    } else {
-      if ((rc = vsl_chol_solve_band_dev(ctx, Sf, rhsf, nt, nt, nt, st.flag + 1, 0, df))) return rc;  // df = -(Sf^-1 rhsf)
-    }
-    hipLaunchKernelGGL(bai_backsub_kernel, dim3((D.L + 255) / 256), dim3(256), 0, q, D, st.lm_start, st.obs_cam, st.cam_free,
-                       st.cam_intr, sb.F, sb.E, G, st.Pinv, st.bl, df, sb.dl);
+    if ((rc = bai_build_and_solve(ctx, st, B, inv_radius, nullptr, nullptr))) return rc;
     hipLaunchKernelGGL(ba_all_finite2_kernel, dim3((std::max(nt, L3) + 255) / 256), dim3(256), 0, q, nt, df, L3, sb.dl, st.flag);
     hipLaunchKernelGGL(bai_model_kernel, dim3(nbo), dim3(256), 0, q, D, st.obs_cam, st.obs_lm, st.cam_free, st.cam_intr, sb.r, sb.F,
                        sb.E, G, df, sb.dl, sb.partials);
@@ -2560,8 +2609,8 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
       std::swap(st.points, st.cand_points);
       VSL_HIP(ctx, hipMemcpyAsync(st.intr, cand_intr, 8 * 16, hipMemcpyDeviceToDevice, q));
       cost = cand_cost;
-      if ((rc = linearize(true))) return rc;
-      if ((rc = stats(true))) return rc;   // new LM diagonal
+      if ((rc = bai_linearize(ctx, st, B, D, true))) return rc;
+      if ((rc = bai_stats(ctx, st, B, true))) return rc;   // new LM diagonal
       if ((rc = read_scalars(ctx, st, h, 2))) return rc;
       gmax = h[1];
       sum.successful_steps++;
@@ -2578,5 +2627,61 @@ extern "C" int vsl_bundle_adjust_intrinsics(vsl_ctx* ctx, const vsl_ba_problem* 
     fprintf(stderr, "vsl BA (intrinsics): iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n", sum.iterations,
             sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
   if (summary) *summary = sum;
+  return VSL_OK;
+}
+
+extern "C" int vsl_ba_intrinsics_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt, const double* intr16,
+                                        double inv_radius, double* G, double* scale, double* S, double* rhs, double* cost,
+                                        double* d, double* dl, int* chol_ok) {
+  int rc = ba_validate(ctx, prob);
+  if (rc) return rc;
+  if (!opt || !intr16) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_intrinsics_system: null argument");
+  if (!(inv_radius >= 0.0) || !std::isfinite(inv_radius))
+    return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_intrinsics_system: 1 / radius = %g is not a finite non-negative number", inv_radius);
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  vsl_ba_problem p2 = *prob;
+  p2.intr = intr16;
+  BaState st;
+  if ((rc = ba_setup(ctx, &p2, opt, st, BaCaller{BaUse::SINGLE_LINEARIZE}))) return rc;
+  const BaDims& D = st.D;
+  const size_t nt = (size_t)D.n + 16, O = (size_t)D.O, L3 = 3 * (size_t)D.L;
+  BaiBuffers B;
+  if ((rc = bai_acquire(ctx, st, B))) return rc;
+  hipStream_t q = ctx->stream;
+  std::vector<double> hG(G ? 16 * O : 0), hS(nt * nt), hv(3 * nt), hdl(L3);  // (targets of queued copies: they outlive the drain)
+  double c = 0;
+  int flags[2] = {0, 0};
+  auto run = [&]() -> int {
+    int e;
+    if (G) {  // the blocks as vsl_ba_residuals_jacobians reports F and E: without the robustifier, unscaled
+      BaDims raw = D;
+      raw.use_huber = 0;
+      if ((e = bai_linearize(ctx, st, B, raw, false))) return e;
+      VSL_HIP(ctx, hipMemcpyAsync(hG.data(), B.G, 8 * 16 * O, hipMemcpyDeviceToHost, q));
+    }
+    if ((e = bai_first_linearization(ctx, st, B))) return e;
+    VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, q));
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + nt, B.scale, 8 * nt, hipMemcpyDeviceToHost, q));
+    if ((e = bai_build_and_solve(ctx, st, B, inv_radius, hS.data(), hv.data()))) return e;
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + 2 * nt, B.df, 8 * nt, hipMemcpyDeviceToHost, q));
+    VSL_HIP(ctx, hipMemcpyAsync(hdl.data(), st.sb.dl, 8 * L3, hipMemcpyDeviceToHost, q));
+    VSL_HIP(ctx, hipMemcpyAsync(flags, st.flag, 8, hipMemcpyDeviceToHost, q));
+    VSL_HIP(ctx, hipStreamSynchronize(q));
+    return VSL_OK;
+  };
+  if ((rc = run())) {
+    (void)hipStreamSynchronize(q);  // kernels and copies may still be queued on the buffers that die here
+    return rc;
+  }
+  if (G) memcpy(G, hG.data(), 8 * 16 * O);
+  if (scale) memcpy(scale, hv.data() + nt, 8 * nt);
+  if (S) memcpy(S, hS.data(), 8 * nt * nt);
+  if (rhs) memcpy(rhs, hv.data(), 8 * nt);
+  if (cost) *cost = c;
+  if (d) memcpy(d, hv.data() + 2 * nt, 8 * nt);
+  if (dl) memcpy(dl, hdl.data(), 8 * L3);
+  if (chol_ok) *chol_ok = flags[1] != 0;
+  if (!flags[1] && !chol_ok)
+    return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_intrinsics_system: the reduced system is not positive definite");
   return VSL_OK;
 }
