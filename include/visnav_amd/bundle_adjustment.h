@@ -26,6 +26,8 @@
 #pragma weak vsl_global_ba_relative_pose_covariance
 // bundle_adjustment_rig (below): likewise
 #pragma weak vsl_bundle_adjust_rig
+// global_bundle_adjustment_rig (below): likewise
+#pragma weak vsl_global_bundle_adjust_rig
 // bundle_adjustment_rig_covariance, rig_relative_pose_covariance, rig_map_edge_information (below): likewise
 #pragma weak vsl_ba_rig_covariance
 #pragma weak vsl_ba_rig_relative_pose_covariance
@@ -246,12 +248,14 @@ struct RigFlat {
     return it == body_frame.end() || *it != frame ? -1 : (int32_t)(it - body_frame.begin());
   }
 };
-// false: the map has no observation (nothing is filled)
+// false: the map has no observation (nothing is filled).  GLOBAL: the flattening of global_bundle_adjustment (ALL
+// observations of the landmarks) instead of bundle_adjustment's
+template <bool GLOBAL = false>
 inline bool flatten_rig(const char* what, const Corners& feature_corners, const std::set<FrameCamId>& fixed_cameras,
                         Calibration& calib_cam, Cameras& cameras, Landmarks& landmarks, RigFlat& r) {
   if (calib_cam.T_i_c.size() < 2) throw std::invalid_argument(std::string(what) + ": the calibration needs two extrinsics");
   BaFlat& f = r.f;
-  if (!flatten_ba<false>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f)) return false;
+  if (!flatten_ba<GLOBAL>(feature_corners, fixed_cameras, calib_cam, cameras, landmarks, f)) return false;
   double inv0[7];
   se3_inv7(calib_cam.T_i_c[0].data(), inv0);
   se3_mul7(inv0, calib_cam.T_i_c[1].data(), r.T_b_c + 7);
@@ -304,6 +308,35 @@ inline void bundle_adjustment_rig(const Corners& feature_corners, const BundleAd
     for (int j = 0; j < 3; j++) f.lm_ptr[l]->p.data()[j] = f.points[3 * l + j];
   if (options.verbosity_level >= 1)
     std::printf("vslam_hip rig BA: %d bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n",
+                (int)r.rig.n_bodies, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
+}
+
+// The rig form of global_bundle_adjustment (vsl_global_bundle_adjust_rig): the reference's global_bundle_adjustment
+// signature (include/visnav/loop_closure_utils.h:672-748) on ALL observations of the landmarks, with bundle_adjustment_rig's
+// body conventions -- body = FrameId, camera 0 is the body frame, a frame with one camera derives its body from it, a body
+// is fixed if any of its cameras is in fixed_cameras.  The reduced body system is gathered over co-visible frames only and
+// stored dense / band / cyclic band.  All camera poses come back ON the calibration.  One GPU.
+inline void global_bundle_adjustment_rig(const Corners& feature_corners, const GlobalBundleAdjustmentOptions& options,
+                                         const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                         Landmarks& landmarks) {
+  if (&vsl_global_bundle_adjust_rig == nullptr)
+    throw std::runtime_error("global_bundle_adjustment_rig: libvslam_hip.so has no vsl_global_bundle_adjust_rig");
+  amd::RigFlat r;
+  if (!amd::flatten_rig<true>("global_bundle_adjustment_rig", feature_corners, fixed_cameras, calib_cam, cameras, landmarks, r)) return;
+  if (!r.any_free) return;
+  amd::BaFlat& f = r.f;
+  vsl_ba_options opt;
+  opt.use_huber = options.use_huber ? 1 : 0;
+  opt.huber_parameter = options.huber_parameter;
+  opt.max_num_iterations = options.max_num_iterations;
+  opt.verbosity = 0;
+  vsl_ba_summary sum;
+  amd::check(vsl_global_bundle_adjust_rig(amd::ctx(), &f.prob, &r.rig, &opt, &sum), "global_bundle_adjustment_rig");
+  for (size_t c = 0; c < f.cam_ptr.size(); c++) std::copy(&f.poses[7 * c], &f.poses[7 * c] + 7, f.cam_ptr[c]->T_w_c.data());
+  for (size_t l = 0; l < f.lm_ptr.size(); l++)
+    for (int j = 0; j < 3; j++) f.lm_ptr[l]->p.data()[j] = f.points[3 * l + j];
+  if (options.verbosity_level >= 1)
+    std::printf("vslam_hip rig global BA: %d bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n",
                 (int)r.rig.n_bodies, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
 }
 

@@ -60,6 +60,8 @@ inline bool ba_covariance_available() { return &vsl_ba_covariance != nullptr; }
 inline bool rig_ba_available() { return &vsl_bundle_adjust_rig != nullptr; }
 // ... and its covariances (OdometryOptions::rig_ba_covariance_path; weak in bundle_adjustment.h)
 inline bool rig_ba_covariance_available() { return &vsl_ba_rig_covariance != nullptr; }
+// the rig form of the loop-closing global bundle adjustment (OdometryOptions::rig_global_ba; weak in bundle_adjustment.h)
+inline bool rig_global_ba_available() { return &vsl_global_bundle_adjust_rig != nullptr; }
 inline bool device_stereo_available() { return &vsl_frames_stereo_inliers != nullptr && &vsl_frames_download_inliers != nullptr; }
 // the device keyframe database (OdometryOptions::device_place_db) is referenced weakly in the same way (bow.h)
 inline bool device_place_db_available() { return KeyframeDatabaseAmd::available(); }
@@ -125,6 +127,10 @@ struct OdometryOptions {  // defaults = the pangolin::Var defaults of src/slam.c
   // with rig_ba: after every rig local BA one line per free keyframe of the window from the BODY block of the rig
   // posterior, in the format of ba_covariance_path (empty: off)
   std::string rig_ba_covariance_path;
+  // the global bundle adjustment after a loop closure optimises ONE pose per stereo keyframe too
+  // (visnav::global_bundle_adjustment_rig) instead of going back to two free cameras per frame, which pulls apart what
+  // the rig local BAs kept on the calibration.  Off by default: nothing changes without it.
+  bool rig_global_ba = false;
   double motion_threshold = 0.5;
   int num_cov_threshold = 10;
   int num_ess_threshold = 30;
@@ -339,6 +345,7 @@ class Odometry {
   std::vector<std::pair<FrameCamId, FrameCamId>> loop_edges;
   bool pose_graph_opt_done = false;
   int n_tracking_lost = 0, n_relocalized = 0, n_loops_closed = 0, n_global_ba = 0;
+  double gba_stereo_dev_ulp = -1.0;  // worst stereo_deviation_ulp (below) right after a global bundle adjustment; -1: none ran
   LandmarkFusionResult fusion_total;  // counts of landmark_fusion over all closed loops (the edit lists stay empty)
   double loop_ms = 0, gba_ms = 0;
 
@@ -848,6 +855,37 @@ class Odometry {
                    (long long)fcidl.frame_id, (long long)cand.frame_id, r.added, r.merged, r.conflicts, r.refused, landmarks.size());
   }
 
+  // Worst distance, over the frames that have both cameras, of the right camera from left * T_0_1 (T_0_1 =
+  // T_i_c[0]^-1 T_i_c[1] as the rig wrappers derive it, the product in long double): in ulp of the translation's norm and,
+  // for the unit quaternion, of 1.  A diagnostic of the headless application (slam_headless prints the figure of the
+  // global bundle adjustments of a run).
+  static double stereo_deviation_ulp(const Cameras& cams, const Calibration& calib) {
+    double inv0[7], t01[7];
+    amd::se3_inv7(calib.T_i_c[0].data(), inv0);
+    amd::se3_mul7(inv0, calib.T_i_c[1].data(), t01);
+    double worst = 0.0;
+    for (const auto& kv : cams) {
+      if (kv.first.cam_id != 0) continue;
+      const auto it = cams.find(FrameCamId(kv.first.frame_id, 1));
+      if (it == cams.end()) continue;
+      const double *a = kv.second.T_w_c.data(), *r = it->second.T_w_c.data();
+      const long double ax = a[0], ay = a[1], az = a[2], aw = a[3], bx = t01[0], by = t01[1], bz = t01[2], bw = t01[3];
+      long double q[4] = {aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                          aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz};
+      const long double R[9] = {1 - 2 * (ay * ay + az * az), 2 * (ax * ay - az * aw),     2 * (ax * az + ay * aw),
+                                2 * (ax * ay + az * aw),     1 - 2 * (ax * ax + az * az), 2 * (ay * az - ax * aw),
+                                2 * (ax * az - ay * aw),     2 * (ay * az + ax * aw),     1 - 2 * (ax * ax + ay * ay)};
+      long double t[3], dot = 0, tn = 0;
+      for (int i = 0; i < 3; i++) t[i] = a[4 + i] + R[3 * i] * t01[4] + R[3 * i + 1] * t01[5] + R[3 * i + 2] * t01[6];
+      for (int i = 0; i < 4; i++) dot += q[i] * r[i];
+      for (int i = 0; i < 3; i++) tn += (long double)r[4 + i] * r[4 + i];
+      const double ulp_t = std::nextafter((double)std::sqrt(tn), INFINITY) - (double)std::sqrt(tn), ulp_q = std::nextafter(1.0, 2.0) - 1.0;
+      for (int i = 0; i < 4; i++) worst = std::max(worst, (double)std::fabs((dot < 0 ? -q[i] : q[i]) - r[i]) / ulp_q);
+      for (int i = 0; i < 3; i++) worst = std::max(worst, (double)std::fabs(t[i] - r[4 + i]) / ulp_t);
+    }
+    return worst;
+  }
+
   // src/slam.cpp:1741-1788 + the merge-back of :1410-1447.  The reference runs it in global_ba_thread and merges at a
   // later non-keyframe step, skipping what the local BA modified meanwhile; here it runs synchronously (reproducible
   // runs), so nothing is modified in between and every landmark / camera is taken over.
@@ -868,8 +906,10 @@ class Odometry {
     ba_options.max_num_iterations = opt.gba_max_iterations;
     ba_options.verbosity_level = opt.ba_verbose;
     const std::set<FrameCamId> fixed_cameras = {FrameCamId(0, 0), FrameCamId(0, 1)};
-    global_bundle_adjustment(corners_gba, ba_options, fixed_cameras, calib_cam_gba, cameras_gba, landmarks_gba);
+    if (opt.rig_global_ba) global_bundle_adjustment_rig(corners_gba, ba_options, fixed_cameras, calib_cam_gba, cameras_gba, landmarks_gba);
+    else global_bundle_adjustment(corners_gba, ba_options, fixed_cameras, calib_cam_gba, cameras_gba, landmarks_gba);
     n_global_ba++;
+    gba_stereo_dev_ulp = std::max(gba_stereo_dev_ulp, stereo_deviation_ulp(cameras_gba, calib_cam_gba));
     for (const auto& kv : landmarks_gba) {
       Landmark& lm = landmarks.at(kv.first);
       lm.p = kv.second.p;

@@ -579,7 +579,8 @@ typedef int (*vsl_allreduce_fn)(void* user, double* buf, int64_t count, int op, 
 int vsl_global_bundle_adjust(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_options* opt,
                              vsl_allreduce_fn allreduce, void* user, int rank, int world, vsl_ba_summary* summary);
 /* Diagnostic: storage of the reduced camera system in the last solve the general path (vsl_bundle_adjust beyond the
- * local window, vsl_global_bundle_adjust) set up on this context: doubles of S, *banded = 0 dense / 1 band (cameras
+ * local window, vsl_global_bundle_adjust) or the rig map route (vsl_global_bundle_adjust_rig, vsl_ba_rig_map_system:
+ * the reduced BODY system, forms 0 / 1 / 2) set up on this context: doubles of S, *banded = 0 dense / 1 band (cameras
  * in reverse Cuthill-McKee order) / 2 cyclic band (cameras as they came, the band closes around the loop) / 3
  * matrix-free (iterative Schur below: S is not stored, *s_elems = 0), bandwidth.
  * Diagnostic "ba_no_cyclic" / VSL_BA_NO_CYCLIC keep form 1 where form 2 would be taken. */
@@ -707,8 +708,9 @@ int vsl_ba_intrinsics_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl
  * No fixed body (the gauge is free): the hooks return VSL_ERR_NUMERIC without writing anything -- the undamped reduced
  * system is singular by construction --; the solve runs the LM policy on the damped system as for any input, a failed
  * factorisation is an unsuccessful step, and no non-finite value reaches a pose.
- * NOT COVERED: rig global bundle adjustment / sessions / multi-GPU, the intrinsics variant, optimising the extrinsics,
- * band / ring / matrix-free routes for the reduced system. */
+ * Whole maps go through vsl_global_bundle_adjust_rig below (band / ring routes for the reduced body system).
+ * NOT COVERED: sessions / multi-GPU, the intrinsics variant, optimising the extrinsics, a matrix-free route for the
+ * reduced system. */
 typedef struct vsl_ba_rig {
   int32_t n_bodies;
   double* body_poses;         /* [7*n_bodies] qx qy qz qw tx ty tz (T_w_b), in/out          */
@@ -731,6 +733,24 @@ int vsl_ba_rig_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_
  * with chol_ok NULL it is VSL_ERR_NUMERIC after the other outputs are written. */
 int vsl_ba_rig_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
                       double inv_radius, double* S, double* rhs, double* scale_b, double* db, double* cost, int* chol_ok);
+/* ---- rig bundle adjustment of a whole map (visual-slam_amd/csrc/ba_rig.hip "the map route") ----
+ * The contract of vsl_bundle_adjust_rig -- inputs, outputs, validation codes, LM policy -- on one GPU, for maps whose
+ * reduced body system must not be built dense: the Schur complement is gathered over the CO-VISIBLE body pairs only
+ * (two free bodies are co-visible iff some landmark is seen from both) and stored as the general path stores its reduced
+ * camera system: dense up to 128 unknowns or where no band pays, a linear band with the free bodies in reverse
+ * Cuthill-McKee order, or a cyclic band in the bodies' own order where the trajectory closes (the rule and the switches
+ * of vsl_bundle_adjust; "ba_force_dense", "ba_no_cyclic" act here as well), then solved by the dense / band / ring
+ * Cholesky.  A dense layout still uses the pair gather.  vsl_ctx_last_ba_layout reports the form and bandwidth.  Two
+ * solves return the same bits; the result agrees with vsl_bundle_adjust_rig to rounding, not bit for bit (a renumbered
+ * pair computes the transposed product, the solver is another).
+ * NOT COVERED: multi-GPU, sessions, a matrix-free route, the extrinsics as unknowns. */
+int vsl_global_bundle_adjust_rig(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                                 vsl_ba_summary* summary);
+/* Parity hook of the map route: signature and contract of vsl_ba_rig_system, through the map route's own host code and
+ * kernels.  S is what the layout's storage held before the factorisation, every stored position of it, expanded on the
+ * host to dense row-major n x n (mirrored) in ASCENDING-BODY order; rhs, scale_b, db in that order too. */
+int vsl_ba_rig_map_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                          double inv_radius, double* S, double* rhs, double* scale_b, double* db, double* cost, int* chol_ok);
 
 /* ---- covariances in rig form (visual-slam_amd/csrc/ba_rig.hip "COVARIANCES", csrc/ba_rig_cov_plan.h) ----
  * The rig counterparts of vsl_ba_covariance and vsl_ba_relative_pose_covariance: the posterior of the problem the rig

@@ -700,6 +700,28 @@ class Context:
                                           db.ctypes.data_as(f64p), C.byref(cost), C.byref(ok)))
         return dict(S=S, rhs=rhs, scale_b=scale_b, db=db, cost=cost.value, chol_ok=ok.value)
 
+    def global_bundle_adjust_rig(self, arr, rig, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
+        """vsl_global_bundle_adjust_rig: bundle_adjust_rig for a whole map -- the reduced body system gathered over the
+        co-visible body pairs only and stored dense / band / cyclic band (last_ba_layout tells which)."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        o = self._ba_opts(use_huber, huber, max_iters, verbosity)
+        s = BaSummary()
+        self._ck(self.L.vsl_global_bundle_adjust_rig(self.h, C.byref(st), C.byref(rg), C.byref(o), C.byref(s)))
+        return s
+
+    def ba_rig_map_system(self, arr, rig, inv_radius=0.0, use_huber=True, huber=1.0):
+        """ba_rig_system through the map route (vsl_ba_rig_map_system): S is the layout's storage expanded to dense [n, n]
+        in ascending-body order; rhs, scale_b, db [n] in that order, cost, chol_ok."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * rig.n_free
+        S, rhs, scale_b, db = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n)
+        cost, ok = C.c_double(), C.c_int32()
+        self._ck(self.L.vsl_ba_rig_map_system(self.h, C.byref(st), C.byref(rg), C.byref(o), C.c_double(inv_radius),
+                                              S.ctypes.data_as(f64p), rhs.ctypes.data_as(f64p), scale_b.ctypes.data_as(f64p),
+                                              db.ctypes.data_as(f64p), C.byref(cost), C.byref(ok)))
+        return dict(S=S, rhs=rhs, scale_b=scale_b, db=db, cost=cost.value, chol_ok=ok.value)
+
     def ba_rig_covariance(self, arr, rig, bodies=None, cams=None, lms=None, use_huber=True, huber=1.0):
         """Marginal covariances of the RIG problem at rig's bodies / arr's points (vsl_ba_rig_covariance; nothing is
         optimised).  bodies: body ids (None: all free bodies), cams: camera ids (None: none), lms: landmark ids (None:

@@ -5,7 +5,7 @@
 // libvslam_hip.so; there is no CPU fallback.
 //
 //   slam_headless --dataset-path <dir with cam0/ cam1/ ...> --cam-calib <calib.json>
-//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N] [--ba-covariance FILE] [--rig-ba [--rig-ba-covariance FILE]]
+//                 [--voc-path ORBvoc.txt] [--replicas N] [--frames N] [--async-ba] [--fused [--device-stereo] [--device-place-db [--device-bow]]] [--traj out.csv] [--kf-min-inliers N] [--max-kfs N] [--ba-covariance FILE] [--rig-ba [--rig-ba-covariance FILE]] [--rig-global-ba]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -61,6 +61,7 @@ int main(int argc, char** argv) {
     else if (a == "--num-features") opt.num_features_per_image = std::atoi(need("--num-features").c_str());
     else if (a == "--ba-covariance") opt.ba_covariance_path = need("--ba-covariance");  // pose uncertainty of the window after every local BA
     else if (a == "--rig-ba") opt.rig_ba = true;  // local BA with one pose per stereo keyframe (visnav::bundle_adjustment_rig)
+    else if (a == "--rig-global-ba") opt.rig_global_ba = true;  // the loop-closing global BA with one pose per stereo keyframe (visnav::global_bundle_adjustment_rig)
     else if (a == "--rig-ba-covariance") opt.rig_ba_covariance_path = need("--rig-ba-covariance");  // body uncertainty of the window after every rig local BA
     else if (a == "--ba-verbose") opt.ba_verbose = 1;
     else if (a == "--ba-iterations") opt.ba_max_iterations = std::atoi(need("--ba-iterations").c_str());
@@ -127,6 +128,10 @@ int main(int argc, char** argv) {
       return 2;
     }
     std::fclose(f);
+  }
+  if (opt.rig_global_ba && !rig_global_ba_available()) {
+    std::fprintf(stderr, "--rig-global-ba: this build's C ABI has no rig global bundle adjustment (vsl_global_bundle_adjust_rig)\n");
+    return 2;
   }
   if (!opt.rig_ba_covariance_path.empty()) {
     if (!opt.rig_ba) {
@@ -341,6 +346,8 @@ int main(int argc, char** argv) {
       n_frames, n_kf, replicas, replicas_agree ? "true" : "false", replicas * n_frames / run_s, 1e3 * run_s / n_frames, decode_s, ate, n_assoc, odo.landmarks.size(), n_active,
       opt.async_ba ? "true" : "false", opt.fused_tracking ? "true" : "false", opt.device_stereo ? "true" : "false", opt.device_place_db ? "true" : "false", c.detect_ms, c.stereo_match_ms, c.project_match_ms, c.localize_ms, c.map_ms, c.ba_ms, c.bow_ms, odo.loop_ms, odo.gba_ms, c.ba_runs, odo.bow_vectors.size(),
       odo.n_tracking_lost, odo.n_relocalized, odo.n_loops_closed, odo.n_global_ba, reloc_ok, reloc_err_m);
+  if (opt.rig_ba || opt.rig_global_ba)  // the line is unchanged without the options
+    std::printf(", \"rig_global_ba\": %s, \"gba_stereo_deviation_ulp\": %.3f", opt.rig_global_ba ? "true" : "false", odo.gba_stereo_dev_ulp);
   if (opt.device_bow) std::printf(", \"device_bow\": true");  // the line is unchanged without the option
   if (opt.landmark_fusion)  // the line is unchanged without the option
     std::printf(", \"landmark_fusion\": {\"added\": %d, \"merged\": %d, \"conflicts\": %d, \"refused\": %d}", odo.fusion_total.added,

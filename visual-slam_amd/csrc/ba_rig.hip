@@ -1,6 +1,8 @@
 // ba_rig.hip -- rig-constrained bundle adjustment: ONE SE(3) block per stereo frame (the body), the calibrated
 // extrinsics T_b_c held fixed, T_w_c = T_w_b * T_b_c[cam_intr].  vsl_bundle_adjust_rig, and the two parity hooks
 // vsl_ba_rig_linearize / vsl_ba_rig_system (include/vslam_hip.h "rig-constrained bundle adjustment").
+// vsl_global_bundle_adjust_rig / vsl_ba_rig_map_system run the same chain for whole maps: the reduced body
+// system gathered over co-visible body pairs only (rig_schur_pairs_kernel) into dense / band / cyclic-band storage.
 // The covariances of the rig posterior (vsl_ba_rig_covariance, vsl_ba_rig_relative_pose_covariance) are
 // the section "COVARIANCES" at the end of this file.
 //
@@ -249,6 +251,94 @@ __global__ __launch_bounds__(64) void rig_schur_finish_kernel(int n, int nseg, c
   }
 }
 
+// ---- the map route (vsl_global_bundle_adjust_rig): the gather over the CO-VISIBLE pairs only
+// grid (items): item = (listed pair, segment) of RigMapPlan; the workgroup sums every nseg-th 256-group slice of body
+// hi's groups, exactly as rig_schur_block_kernel does for its block (hi, lo): Y_hi W_lo^T over the landmarks both bodies
+// see and, on the diagonal, Y_hi b_l, into spart[item][42].  A pair that shares no landmark is not in the list: no
+// workgroup walks it.
+__global__ __launch_bounds__(256) void rig_schur_pairs_kernel(const int* __restrict__ item_pair, const int* __restrict__ pair_first,
+                                                              const int* __restrict__ pair_hi, const int* __restrict__ pair_lo,
+                                                              const int* __restrict__ bg_start, const int* __restrict__ bg_grp,
+                                                              const int* __restrict__ bg_lm, const double* __restrict__ W,
+                                                              const double* __restrict__ Y, const double* __restrict__ bl,
+                                                              double* __restrict__ spart) {
+  __shared__ double sh[4 * 42];
+  const int item = blockIdx.x, pr = item_pair[item];
+  const int seg = item - pair_first[pr], nseg = pair_first[pr + 1] - pair_first[pr];
+  const int a = pair_hi[pr], b = pair_lo[pr];
+  double acc[42];
+#pragma unroll
+  for (int k = 0; k < 42; k++) acc[k] = 0;
+  const int b0 = bg_start[b], b1 = bg_start[b + 1];
+  for (int k = bg_start[a] + seg * 256 + threadIdx.x; k < bg_start[a + 1]; k += 256 * nseg) {
+    const int lm = bg_lm[k];
+    int p = k;
+    if (a != b) {
+      int lo = b0, hi = b1;  // first position in [b0, b1) whose landmark is >= lm
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (bg_lm[mid] < lm) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo >= b1 || bg_lm[lo] != lm) continue;
+      p = lo;
+    }
+    const double* y = Y + 18 * (size_t)bg_grp[k];
+    const double* w = W + 18 * (size_t)bg_grp[p];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j < 6; j++) acc[6 * i + j] += y[3 * i] * w[3 * j] + y[3 * i + 1] * w[3 * j + 1] + y[3 * i + 2] * w[3 * j + 2];
+    if (a == b) {
+      const double* bb = bl + 3 * (size_t)lm;
+#pragma unroll
+      for (int i = 0; i < 6; i++) acc[36 + i] += y[3 * i] * bb[0] + y[3 * i + 1] * bb[1] + y[3 * i + 2] * bb[2];
+    }
+  }
+  rig_block_sum<42>(acc, sh);
+  if (threadIdx.x == 0) {
+    double* o = spart + (size_t)item * 42;
+#pragma unroll
+    for (int k = 0; k < 42; k++) o[k] = acc[k];
+  }
+}
+
+// grid (listed pairs), 64 threads: the segments of pair (hi, lo) in order, then the block into the storage of the layout
+// (rig_map_entry_at, ba_rig_plan.h): dense with its mirror image; the band forms keep the lower triangle, the cyclic one
+// its wrap-around blocks transposed at negative columns.  The storage was cleared before (rig_schur): what no listed
+// pair owns is zero.  hi == lo also: rhs = g - sum.  Pair 0 arms the two flags of the step.
+__global__ __launch_bounds__(64) void rig_schur_band_finish_kernel(int form, int ldS, int offS, int nfree, int half_cyc,
+                                                                   const int* __restrict__ pair_first, const int* __restrict__ pair_hi,
+                                                                   const int* __restrict__ pair_lo, const double* __restrict__ spart,
+                                                                   const double* __restrict__ H, const double* __restrict__ g_b,
+                                                                   const double* __restrict__ diag_c, double inv_radius,
+                                                                   double* __restrict__ S, double* __restrict__ rhs,
+                                                                   int* __restrict__ flag) {
+  const int pr = blockIdx.x, a = pair_hi[pr], b = pair_lo[pr];
+  if (pr == 0 && threadIdx.x < 2) flag[threadIdx.x] = 1;
+  const int e = threadIdx.x;
+  if (e >= 42) return;
+  const int first = pair_first[pr], nseg = pair_first[pr + 1] - first;
+  const double* p = spart + (size_t)first * 42;
+  double sum = 0;
+  for (int q = 0; q < nseg; q++) sum += p[(size_t)q * 42 + e];
+  if (e < 36) {
+    const int i = e / 6, j = e - 6 * i;
+    if (a != b) {
+      S[rig_map_entry_at(form, ldS, offS, nfree, half_cyc, a, b, i, j)] = -sum;
+      if (form == 0) S[(size_t)(6 * b + j) * ldS + 6 * a + i] = -sum;
+    } else if (i >= j) {
+      double h = H[36 * (size_t)a + e];
+      if (i == j && diag_c) h += diag_c[6 * (size_t)a + i] * inv_radius;
+      const double v = h - sum;
+      S[rig_map_entry_at(form, ldS, offS, nfree, half_cyc, a, a, i, j)] = v;
+      if (form == 0) S[(size_t)(6 * a + j) * ldS + 6 * a + i] = v;
+    }
+  } else if (a == b) {
+    rhs[6 * (size_t)a + (e - 36)] = g_b[6 * (size_t)a + (e - 36)] - sum;
+  }
+}
+
 // delta_l = -P^-1 (b_l + sum over the landmark's groups of W^T delta_body); flag[0] cleared on a non-finite step
 __global__ __launch_bounds__(256) void rig_backsub_kernel(BaDims D, const int* __restrict__ lm_grp, const int* __restrict__ grp_slot,
                                                           const double* __restrict__ W, const double* __restrict__ Pinv,
@@ -298,10 +388,29 @@ struct RigState {
   int *lm_start = nullptr, *lm_grp = nullptr, *grp_slot = nullptr, *grp_begin = nullptr, *grp_end = nullptr;
   int *bg_start = nullptr, *bg_grp = nullptr, *bg_lm = nullptr, *bo_start = nullptr, *bo_obs = nullptr;
   char* extra = nullptr;  // the covariance calls' share of the arena (behind everything else: no other offset moves)
+  // the map route (vsl_global_bundle_adjust_rig): S in the layout's storage, the gather over the listed pairs
+  bool map = false;
+  RigMapPlan mp;
+  int *item_pair = nullptr, *pair_first = nullptr, *pair_hi = nullptr, *pair_lo = nullptr;
+  double* S_eff() { return S + (map ? mp.layout.offS : 0); }
 };
 
+// the layout switches of the map route: those of the general path's host loop (ba.hip ba_layout_switches), no rule of its own
+BaLayoutSwitches rig_map_switches(vsl_ctx* ctx) {
+  static const bool env_no_cyclic = getenv("VSL_BA_NO_CYCLIC") != nullptr;
+  BaLayoutSwitches sw;
+  sw.allow_band = true;
+  sw.force_dense = ctx->ba_force_dense;
+  sw.no_cyclic = ctx->ba_no_cyclic || env_no_cyclic;
+  sw.schur_atomics = ctx->ba_schur_atomics;
+  sw.chol_no_bcr = ctx->chol_no_bcr;
+  sw.chol_no_fused = ctx->chol_no_fused;
+  return sw;
+}
+
+// mp: the map route -- the plan comes from rig_map_plan_build (slots in band order where the layout renumbers)
 int rig_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt,
-                 RigPlan& plan) {
+                 RigPlan& plan, RigMapPlan* mp = nullptr) {
   if (!ctx) return VSL_ERR_INVALID;
   if (!p || !rig || !opt || !p->poses || !p->cam_intr || !p->intr || !p->points || !p->obs_cam || !p->obs_lm || !p->obs_uv ||
       !rig->body_poses || !rig->body_fixed || !rig->cam_body || !rig->T_b_c)
@@ -312,7 +421,16 @@ int rig_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const v
   in.n_cams = p->n_cams; in.n_lms = p->n_lms; in.n_obs = p->n_obs;
   in.cam_intr = p->cam_intr; in.obs_cam = p->obs_cam; in.obs_lm = p->obs_lm;
   in.n_bodies = rig->n_bodies; in.body_fixed = rig->body_fixed; in.cam_body = rig->cam_body; in.T_b_c = rig->T_b_c;
-  const int st = rig_plan_build(in, plan);
+  int st;
+  if (mp) {
+    try {
+      st = rig_map_plan_build(in, rig_map_switches(ctx), plan, *mp);
+    } catch (const std::bad_alloc&) {
+      return vsl_fail(ctx, VSL_ERR_NOMEM, "%s: out of host memory", who);
+    }
+  } else {
+    st = rig_plan_build(in, plan);
+  }
   if (st != RIG_PLAN_OK) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: %s (index %d)", who, rig_plan_message(st), plan.first_bad);
   return VSL_OK;
 }
@@ -338,7 +456,7 @@ int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, cons
     max_grp = std::max(max_grp, hp.bg_start[b + 1] - hp.bg_start[b]);
   }
   st.body_seg = std::min(64, std::max(1, (max_obs + 511) / 512));
-  st.schur_seg = std::min(64, std::max(1, (max_grp + 511) / 512));
+  st.schur_seg = std::min(64, std::max(1, (max_grp + 511) / 512));  // (the map route takes its segments per pair from the plan)
   ArenaPlan plan(80);
   for (RigSet* s : {&st.cur, &st.cand}) {
     plan.add(s->bodies, 7 * B); plan.add(s->cams, 7 * C); plan.add(s->points, 3 * L);
@@ -349,10 +467,10 @@ int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, cons
   plan.add(st.intr, 16); plan.add(st.tbc, 14); plan.add(st.tcb, 24); plan.add(st.obs_uv, 2 * O);
   plan.add(st.scale_c, n); plan.add(st.scale_l, 3 * L);
   plan.add(st.W, 18 * G); plan.add(st.Y, 18 * G); plan.add(st.Pinv, 9 * L); plan.add(st.bl, 3 * L);
-  plan.add(st.S, n * n); plan.add(st.rhs, n); plan.add(st.dc, n); plan.add(st.dl, 3 * L);
+  plan.add(st.S, st.map ? st.mp.layout.s_elems : n * n); plan.add(st.rhs, n); plan.add(st.dc, n); plan.add(st.dl, 3 * L);
   plan.add(st.partials, std::max(std::max((size_t)st.nb_obs, 2 * nb_upd), nb_diag));
   plan.add(st.scalars, 32);  // 16 doubles, then the flags
-  plan.add(st.body_part, nf * st.body_seg * 27); plan.add(st.schur_part, nf * (nf + 1) / 2 * st.schur_seg * 42);
+  plan.add(st.body_part, nf * st.body_seg * 27); plan.add(st.schur_part, st.map ? (size_t)st.mp.n_items() * 42 : nf * (nf + 1) / 2 * st.schur_seg * 42);
   plan.add(st.cam_intr, C); plan.add(st.cam_body, C); plan.add(st.cam_slot, C); plan.add(st.body_slot, B);
   plan.add(st.obs_cam, O); plan.add(st.obs_lm, O);
   plan.add(st.lm_start, L + 1); plan.add(st.lm_grp, L + 1);
@@ -360,6 +478,10 @@ int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, cons
   plan.add(st.bg_start, nf + 1); plan.add(st.bg_grp, G); plan.add(st.bg_lm, G);
   plan.add(st.bo_start, nf + 1); plan.add(st.bo_obs, hp.bo_obs.size());
   if (extra_bytes) plan.add(st.extra, extra_bytes);
+  if (st.map) {
+    plan.add(st.item_pair, st.mp.item_pair.size()); plan.add(st.pair_first, st.mp.pair_first.size());
+    plan.add(st.pair_hi, st.mp.pair_hi.size()); plan.add(st.pair_lo, st.mp.pair_lo.size());
+  }
   hipError_t e = st.arena.acquire(ctx, ArenaPolicy::BORROWED, plan);
   if (e != hipSuccess) return vsl_fail(ctx, e == hipErrorOutOfMemory ? VSL_ERR_NOMEM : VSL_ERR_HIP, "rig bundle adjustment: %zu bytes of device memory: %s", plan.total(), hipGetErrorString(e));
   st.flag = (int*)(st.scalars + 16);
@@ -395,6 +517,12 @@ int rig_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, cons
   VSL_HIP(ctx, up(st.bg_lm, hp.bg_lm.data(), 4 * G));
   VSL_HIP(ctx, up(st.bo_start, hp.bo_start.data(), 4 * (nf + 1)));
   VSL_HIP(ctx, up(st.bo_obs, hp.bo_obs.data(), 4 * hp.bo_obs.size()));
+  if (st.map) {
+    VSL_HIP(ctx, up(st.item_pair, st.mp.item_pair.data(), 4 * st.mp.item_pair.size()));
+    VSL_HIP(ctx, up(st.pair_first, st.mp.pair_first.data(), 4 * st.mp.pair_first.size()));
+    VSL_HIP(ctx, up(st.pair_hi, st.mp.pair_hi.data(), 4 * st.mp.pair_hi.size()));
+    VSL_HIP(ctx, up(st.pair_lo, st.mp.pair_lo.data(), 4 * st.mp.pair_lo.size()));
+  }
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the uploads read host vectors that die here
   return VSL_OK;
 }
@@ -438,6 +566,19 @@ int rig_schur(vsl_ctx* ctx, RigState& st, bool damp, double inv_radius) {
   const RigSet& s = st.cur;
   hipLaunchKernelGGL(rig_lm_groups_kernel, dim3((st.D.L + 255) / 256), dim3(256), 0, ctx->stream, st.D, st.lm_start, st.lm_grp,
                      st.grp_begin, st.grp_end, s.r, s.F, s.E, damp ? s.diag_l : nullptr, inv_radius, st.W, st.Y, st.Pinv, st.bl);
+  if (st.map) {
+    // The solver destroys S in place and the finish kernel writes the blocks of the listed pairs only: the WHOLE storage
+    // is cleared per build (in-band blocks of pairs that share no landmark, the padding rows, the slack), as ba_schur does
+    const BaLayout& y = st.mp.layout;
+    VSL_HIP(ctx, hipMemsetAsync(st.S, 0, sizeof(double) * y.s_elems, ctx->stream));
+    hipLaunchKernelGGL(rig_schur_pairs_kernel, dim3(st.mp.n_items()), dim3(256), 0, ctx->stream, st.item_pair, st.pair_first, st.pair_hi,
+                       st.pair_lo, st.bg_start, st.bg_grp, st.bg_lm, st.W, st.Y, st.bl, st.schur_part);
+    hipLaunchKernelGGL(rig_schur_band_finish_kernel, dim3(st.mp.n_pairs()), dim3(64), 0, ctx->stream, st.mp.form, y.ldS, y.offS,
+                       st.D.nfree, st.mp.half_cyc, st.pair_first, st.pair_hi, st.pair_lo, st.schur_part, s.H, s.g_b,
+                       damp ? s.diag_c : nullptr, inv_radius, st.S, st.rhs, st.flag);
+    VSL_CHECK_LAUNCH(ctx);
+    return VSL_OK;
+  }
   hipLaunchKernelGGL(rig_schur_block_kernel, dim3(st.D.nfree, st.D.nfree, st.schur_seg), dim3(256), 0, ctx->stream, st.bg_start,
                      st.bg_grp, st.bg_lm, st.W, st.Y, st.bl, st.schur_part);
   hipLaunchKernelGGL(rig_schur_finish_kernel, dim3(st.D.nfree, st.D.nfree), dim3(64), 0, ctx->stream, st.D.n, st.schur_seg,
@@ -451,6 +592,10 @@ int rig_solve(vsl_ctx* ctx, RigState& st) {
   VslStage stage(ctx, VSL_STAGE_BA_SOLVE);
   const int n = st.D.n;
   if (n <= 128) return vsl_ba_chol_small_launch(ctx, n, st.S, st.rhs, st.dc, st.flag + 1);
+  if (st.map) {  // dense, band or ring by the layout (dense: ldS = bw = n, no offset -- the call below)
+    const BaLayout& y = st.mp.layout;
+    return vsl_chol_solve_band_dev(ctx, st.S_eff(), st.rhs, n, y.ldS, y.bw, st.flag + 1, y.cyclic ? 1 : 0, st.dc);
+  }
   return vsl_chol_solve_band_dev(ctx, st.S, st.rhs, n, n, n, st.flag + 1, 0, st.dc);
 }
 
@@ -613,7 +758,7 @@ int rig_solve_run(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* ri
   VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.cur.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
   VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   char label[64];
-  snprintf(label, sizeof(label), "vsl rig BA: %d free bodies,", D.nfree);
+  snprintf(label, sizeof(label), "vsl rig %sBA: %d free bodies,", st.map ? "map " : "", D.nfree);
   ba_finish_summary(ctx, times, opt->verbosity, label, sum, summary);
   return VSL_OK;
 }
@@ -632,6 +777,79 @@ extern "C" int vsl_bundle_adjust_rig(vsl_ctx* ctx, const vsl_ba_problem* prob, c
   if ((rc = rig_setup(ctx, prob, rig, opt, st))) return rc;
   rc = rig_solve_run(ctx, prob, rig, opt, st, t_start, summary);
   return rc ? rig_drain(ctx, rc) : VSL_OK;
+}
+
+// ---- the map route: the same chain and the same LM loop; the reduced body system is gathered over the
+// co-visible body pairs only (rig_schur_pairs_kernel), stored as ba_reduced_layout says (dense / band in reverse
+// Cuthill-McKee order of the bodies / cyclic band in the bodies' own order) and solved by vsl_chol_solve_band_dev.
+namespace {
+
+// validation and plan of the map route; the read-out of vsl_ctx_last_ba_layout
+int rig_map_begin(vsl_ctx* ctx, const char* who, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                  RigState& st) {
+  st.map = true;
+  const int rc = rig_validate(ctx, who, prob, rig, opt, st.plan, &st.mp);
+  if (rc) return rc;
+  ctx->last_ba_s_elems = (int64_t)st.mp.layout.s_elems;
+  ctx->last_ba_banded = st.mp.form;
+  ctx->last_ba_bw = st.mp.layout.bw;
+  return VSL_OK;
+}
+
+}  // namespace
+
+extern "C" int vsl_global_bundle_adjust_rig(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig,
+                                            const vsl_ba_options* opt, vsl_ba_summary* summary) {
+  const double t_start = now_ms();
+  RigState st;  // holds the loan of the context's arena
+  int rc = rig_map_begin(ctx, "vsl_global_bundle_adjust_rig", prob, rig, opt, st);
+  if (rc) return rc;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = rig_setup(ctx, prob, rig, opt, st))) return rc;
+  rc = rig_solve_run(ctx, prob, rig, opt, st, t_start, summary);
+  return rc ? rig_drain(ctx, rc) : VSL_OK;
+}
+
+extern "C" int vsl_ba_rig_map_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                                     double inv_radius, double* S, double* rhs, double* scale_b, double* db, double* cost,
+                                     int* chol_ok) {
+  RigState st;
+  int rc = rig_map_begin(ctx, "vsl_ba_rig_map_system", prob, rig, opt, st);
+  if (rc) return rc;
+  if (!(inv_radius >= 0.0) || !std::isfinite(inv_radius)) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_rig_map_system: inv_radius %g", inv_radius);
+  if (st.plan.n_fixed == 0)
+    return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_rig_map_system: no fixed body: the gauge is free and the reduced system singular");
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = rig_setup(ctx, prob, rig, opt, st))) return rc;
+  const size_t n = st.D.n, se = st.mp.layout.s_elems;
+  std::vector<double> hS(se), hv(3 * n);  // (the targets of queued copies: they outlive the drain below)
+  double c = 0;
+  int flags[2] = {0, 0};
+  auto run = [&]() -> int {
+    int e;
+    if ((e = rig_first_linearization(ctx, st))) return e;
+    if ((e = rig_schur(ctx, st, true, inv_radius))) return e;
+    // (the factorisation works in place: the storage and rhs are read before it runs)
+    VSL_HIP(ctx, hipMemcpyAsync(hS.data(), st.S, 8 * se, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data(), st.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + n, st.scale_c, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((e = rig_solve(ctx, st))) return e;
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + 2 * n, st.dc, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(flags, st.flag, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VSL_OK;
+  };
+  if ((rc = run())) return rig_drain(ctx, rc);
+  // the band expanded on the host, slots back to ascending body id
+  if (S) rig_map_expand(st.mp, st.D.nfree, hS.data(), S);
+  if (rhs) rig_map_unpermute(st.mp, st.D.nfree, hv.data(), rhs);
+  if (scale_b) rig_map_unpermute(st.mp, st.D.nfree, hv.data() + n, scale_b);
+  if (db) rig_map_unpermute(st.mp, st.D.nfree, hv.data() + 2 * n, db);
+  if (cost) *cost = c;
+  if (chol_ok) *chol_ok = flags[1] != 0;
+  if (!flags[1] && !chol_ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_rig_map_system: the reduced system is not positive definite");
+  return VSL_OK;
 }
 
 // ================================================================================================== COVARIANCES

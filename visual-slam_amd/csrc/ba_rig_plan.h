@@ -12,12 +12,21 @@
 //                 observations -- the normal stereo case
 //   body lists    groups / observations of a free body in ascending group / sorted-observation number (so a body's
 //                 groups are in ascending landmark: the Schur gather finds a partner by bisection)
+//
+// The MAP route (vsl_global_bundle_adjust_rig) adds rig_map_plan_build at the end of this file: the body
+// covisibility graph, its band order through camera_band_order and the storage of the reduced body system through
+// ba_reduced_layout (both of ba_host_plan.h, unchanged: the camera -> body slot table stands where the free solver has
+// its camera -> free-camera table), the free-body slots in band order where the layout renumbers, and the list of
+// co-visible slot pairs with their segments.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <numeric>
 #include <vector>
+
+#include "ba_host_plan.h"
 
 enum RigPlanStatus {
   RIG_PLAN_OK = 0,
@@ -73,8 +82,9 @@ struct RigPlan {
   int n_groups() const { return (int)grp_lm.size(); }
 };
 
-// 0 and the plan, or the first rule broken (nothing of `out` is then meaningful except first_bad)
-inline int rig_plan_build(const RigPlanIn& in, RigPlan& out) {
+// 0 and the plan, or the first rule broken (nothing of `out` is then meaningful except first_bad).  slot_bodies (the map
+// route): the free bodies in the order of their slots, a permutation of the free body ids; null: ascending body id.
+inline int rig_plan_build(const RigPlanIn& in, RigPlan& out, const std::vector<int>* slot_bodies = nullptr) {
   out = RigPlan();
   if (in.n_cams <= 0 || in.n_lms <= 0 || in.n_obs <= 0 || in.n_bodies <= 0) return RIG_PLAN_EMPTY;
   if (!in.cam_intr || !in.obs_cam || !in.obs_lm || !in.body_fixed || !in.cam_body || !in.T_b_c) return RIG_PLAN_NULL;
@@ -97,6 +107,10 @@ inline int rig_plan_build(const RigPlanIn& in, RigPlan& out) {
     out.free_bodies.push_back(b);
   }
   if (out.n_free == 0) return RIG_PLAN_NO_FREE_BODY;
+  if (slot_bodies) {
+    out.free_bodies = *slot_bodies;
+    for (int k = 0; k < out.n_free; k++) out.body_slot[out.free_bodies[k]] = k;
+  }
   for (int k = 0; k < 2; k++) {
     const double* T = in.T_b_c + 7 * k;
     double nn = 0;
@@ -210,4 +224,133 @@ inline bool rig_plan_check(const RigPlanIn& in, const RigPlan& p) {
     }
   }
   return true;
+}
+
+// ------------------------------------------------------------------------------------------------ the map route
+#if defined(__HIPCC__)
+#define RIG_PLAN_HD __host__ __device__
+#else
+#define RIG_PLAN_HD
+#endif
+
+// Where entry (x, y) of the 6 x 6 block S_(hi, lo), hi >= lo in slot order, lives in the storage of a layout, as an
+// offset from the START of the allocation (BaLayout::offS included); -1: the entry is not stored (y > x of a diagonal
+// block in the band forms: only the lower triangle exists).  form 0 dense (ldS = n, the caller mirrors), 1 linear band,
+// 2 cyclic band: a pair further apart than half_cyc slots is a neighbour AROUND the ring and its block is stored
+// TRANSPOSED in row block lo at the negative column block hi - n_free (BaCommon in ba_state.h, ba_pair_list_kernel).
+// The kernel and the host (expansion, tests) share this one rule.
+RIG_PLAN_HD inline long long rig_map_entry_at(int form, int ldS, int offS, int n_free, int half_cyc, int hi, int lo, int x, int y) {
+  if (form == 0) return (long long)(6 * hi + x) * ldS + 6 * lo + y;
+  if (hi == lo && y > x) return -1;
+  if (form == 2 && hi - lo > half_cyc) return (long long)(6 * lo + y) * ldS + (6 * (hi - n_free) + x) + offS;
+  return (long long)(6 * hi + x) * ldS + (6 * lo + y) + offS;
+}
+
+struct RigMapPlan {
+  BaLayout layout;
+  int form = 0;                      // 0 dense / 1 linear band / 2 cyclic band: what vsl_ctx_last_ba_layout reports
+  int half_lin = 0, half_cyc = 0;    // block half-bandwidths of the body graph (0 where the layout did not ask)
+  std::vector<int> natural_slot;     // [n_free] k-th free body in ascending id -> slot (the identity unless layout.renumber)
+  std::vector<int> pair_hi, pair_lo; // co-visible slot pairs, hi >= lo: the n_free diagonal pairs first (ascending slot),
+                                     // then the others ascending in (hi, lo)
+  std::vector<int> pair_first;       // [pairs + 1] first (pair, segment) item of a pair = first 42-entry partial sum
+  std::vector<int> item_pair;        // [items] pair of an item (its segment: item - pair_first[pair])
+  int n_pairs() const { return (int)pair_hi.size(); }
+  int n_items() const { return (int)item_pair.size(); }
+};
+
+// segments of a gather over a list of `len` entries: one per 512, at most 64 (the rule of the dense rig route)
+inline int rig_segments(int len) { return std::min(64, std::max(1, (len + 511) / 512)); }
+
+// The plan of the map route: `plan` as rig_plan_build gives it, except that the slots follow the band order where the
+// layout renumbers; returns rig_plan_build's status.
+inline int rig_map_plan_build(const RigPlanIn& in, const BaLayoutSwitches& sw, RigPlan& plan, RigMapPlan& mp,
+                              const HostTeamConfig& threads = HostTeamConfig()) {
+  mp = RigMapPlan();
+  int st = rig_plan_build(in, plan);
+  if (st != RIG_PLAN_OK) return st;
+  const int nf = plan.n_free, n = 6 * nf;
+  mp.natural_slot.resize(nf);
+  std::iota(mp.natural_slot.begin(), mp.natural_slot.end(), 0);
+  if (ba_layout_considers_band(n, sw)) {
+    // the body graph: camera_band_order reads the counts and the two index arrays of the problem and nothing else
+    vsl_ba_problem gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.n_cams = in.n_cams; gp.n_lms = in.n_lms; gp.n_obs = in.n_obs;
+    gp.obs_cam = in.obs_cam; gp.obs_lm = in.obs_lm;
+    std::vector<int> start((size_t)in.n_lms + 1), order;
+    const bool sorted_in = ba_landmark_csr(&gp, start.data());
+    mp.half_lin = camera_band_order(&gp, start.data(), sorted_in, plan.cam_slot, nf, order, &mp.half_cyc, threads);
+    mp.layout = ba_reduced_layout(n, mp.half_lin, mp.half_cyc, sw);
+    if (mp.layout.renumber) {
+      std::vector<int> slot_bodies(nf);
+      for (int k = 0; k < nf; k++) {
+        slot_bodies[k] = plan.free_bodies[order[k]];
+        mp.natural_slot[order[k]] = k;
+      }
+      if ((st = rig_plan_build(in, plan, &slot_bodies)) != RIG_PLAN_OK) return st;
+    }
+  } else {
+    mp.layout = ba_reduced_layout(n, 0, 0, sw);
+  }
+  mp.form = mp.layout.cyclic ? 2 : (mp.layout.banded ? 1 : 0);
+  // co-visible pairs: the groups of a landmark come in ascending slot
+  std::vector<long long> keys;
+  for (int l = 0; l < in.n_lms; l++)
+    for (int g = plan.lm_grp[l]; g < plan.lm_grp[l + 1]; g++)
+      for (int h = g + 1; h < plan.lm_grp[l + 1]; h++) keys.push_back((long long)plan.grp_slot[h] * nf + plan.grp_slot[g]);
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  mp.pair_hi.reserve(nf + keys.size());
+  mp.pair_lo.reserve(nf + keys.size());
+  for (int s = 0; s < nf; s++) {
+    mp.pair_hi.push_back(s);
+    mp.pair_lo.push_back(s);
+  }
+  for (long long k : keys) {
+    mp.pair_hi.push_back((int)(k / nf));
+    mp.pair_lo.push_back((int)(k % nf));
+  }
+  mp.pair_first.assign(1, 0);
+  for (int p = 0; p < mp.n_pairs(); p++) {
+    const int hi = mp.pair_hi[p], lo = mp.pair_lo[p];
+    const int nseg = rig_segments(std::max(plan.bg_start[hi + 1] - plan.bg_start[hi], plan.bg_start[lo + 1] - plan.bg_start[lo]));
+    for (int q = 0; q < nseg; q++) mp.item_pair.push_back(p);
+    mp.pair_first.push_back(mp.n_items());
+  }
+  return RIG_PLAN_OK;
+}
+
+// S of the map route, as the device leaves it in the layout's storage (s_elems doubles), to dense row-major n x n in
+// ASCENDING-BODY order.  Every stored position of a row is read, the padding between bw and bw + VSL_CHOL_NB included:
+// what the storage holds that the solver would see is what comes out (mirrored: the band keeps the lower triangle).
+inline void rig_map_expand(const RigMapPlan& mp, int n_free, const double* store, double* dense) {
+  const int n = 6 * n_free;
+  const BaLayout& y = mp.layout;
+  std::vector<double> slot((size_t)n * n, 0.0);
+  if (!y.banded) {
+    std::copy(store, store + (size_t)n * n, slot.begin());
+  } else {
+    for (int i = 0; i < n; i++)
+      for (int c = i - y.ldS; c <= i; c++) {
+        const double v = store[(size_t)i * y.ldS + c + y.offS];  // (c + offS >= i - ldS + offS = i >= 0)
+        int j = c;
+        if (j < 0) {
+          if (!y.cyclic) continue;  // outside the matrix: never read by the linear forms
+          j += n;  // the wrap-around corner (the ring has at least 8 blocks wider than the band: j > i + ldS)
+        }
+        slot[(size_t)i * n + j] = slot[(size_t)j * n + i] = v;
+      }
+  }
+  for (int a = 0; a < n_free; a++)
+    for (int b = 0; b < n_free; b++)
+      for (int x = 0; x < 6; x++)
+        for (int z = 0; z < 6; z++)
+          dense[(size_t)(6 * a + x) * n + 6 * b + z] = slot[(size_t)(6 * mp.natural_slot[a] + x) * n + 6 * mp.natural_slot[b] + z];
+}
+
+// a vector of the slot order (6 per slot) to ascending-body order
+inline void rig_map_unpermute(const RigMapPlan& mp, int n_free, const double* in_slots, double* out) {
+  for (int a = 0; a < n_free; a++)
+    for (int x = 0; x < 6; x++) out[6 * a + x] = in_slots[6 * mp.natural_slot[a] + x];
 }
