@@ -26,6 +26,8 @@
 #pragma weak vsl_global_ba_relative_pose_covariance
 // bundle_adjustment_rig (below): likewise
 #pragma weak vsl_bundle_adjust_rig
+// bundle_adjustment_rig_extrinsics (below): likewise
+#pragma weak vsl_bundle_adjust_rig_ext
 // global_bundle_adjustment_rig (below): likewise
 #pragma weak vsl_global_bundle_adjust_rig
 // bundle_adjustment_rig_covariance, rig_relative_pose_covariance, rig_map_edge_information (below): likewise
@@ -309,6 +311,51 @@ inline void bundle_adjustment_rig(const Corners& feature_corners, const BundleAd
   if (options.verbosity_level >= 1)
     std::printf("vslam_hip rig BA: %d bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n",
                 (int)r.rig.n_bodies, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
+}
+
+// bundle_adjustment_rig with the extrinsic of ONE camera estimated beside the bodies (vsl_bundle_adjust_rig_ext, online
+// extrinsic refinement): the argument list of bundle_adjustment_rig plus free_extrinsic_camera, the camera (0 or 1) whose
+// T_i_c is an unknown; -1: none, which is bundle_adjustment_rig itself.  The flattening and the body rules are
+// bundle_adjustment_rig's (amd::flatten_rig: the body frame is camera 0 AT THE CALIBRATION HANDED IN).  On return
+// calib_cam.T_i_c[free_extrinsic_camera] = T_i_c[0] * (refined T_b_c) -- for camera 0 itself the refined T_b_c[0] is no
+// longer the identity --, every camera pose is body * refined T_b_c, and the landmarks are updated.  A window whose
+// frames are all fixed is still solved when an extrinsic is free (calibration against fixed poses); with none free it
+// returns untouched.  The baseline's LENGTH is observable only with two fixed frames at different places (the header's
+// gauge statement).  optimize_intrinsics is not offered (std::invalid_argument).
+inline void bundle_adjustment_rig_extrinsics(const Corners& feature_corners, const BundleAdjustmentOptions& options,
+                                             const std::set<FrameCamId>& fixed_cameras, Calibration& calib_cam, Cameras& cameras,
+                                             Landmarks& landmarks, int free_extrinsic_camera) {
+  if (&vsl_bundle_adjust_rig_ext == nullptr)
+    throw std::runtime_error("bundle_adjustment_rig_extrinsics: libvslam_hip.so has no vsl_bundle_adjust_rig_ext");
+  if (options.optimize_intrinsics)
+    throw std::invalid_argument("bundle_adjustment_rig_extrinsics: optimize_intrinsics is not offered in rig form");
+  if (free_extrinsic_camera < -1 || free_extrinsic_camera > 1)
+    throw std::invalid_argument("bundle_adjustment_rig_extrinsics: free_extrinsic_camera is -1, 0 or 1");
+  amd::RigFlat r;
+  if (!amd::flatten_rig("bundle_adjustment_rig_extrinsics", feature_corners, fixed_cameras, calib_cam, cameras, landmarks, r)) return;
+  if (!r.any_free && free_extrinsic_camera < 0) return;
+  amd::BaFlat& f = r.f;
+  vsl_ba_options opt;
+  opt.use_huber = options.use_huber ? 1 : 0;
+  opt.huber_parameter = options.huber_parameter;
+  opt.max_num_iterations = options.max_num_iterations;
+  opt.verbosity = 0;
+  vsl_ba_summary sum;
+  const uint8_t ext_free[2] = {(uint8_t)(free_extrinsic_camera == 0), (uint8_t)(free_extrinsic_camera == 1)};
+  double T_b_c[14];
+  std::copy(r.T_b_c, r.T_b_c + 14, T_b_c);
+  amd::check(vsl_bundle_adjust_rig_ext(amd::ctx(), &f.prob, &r.rig, ext_free, T_b_c, &opt, &sum), "bundle_adjustment_rig_extrinsics");
+  if (free_extrinsic_camera >= 0) {
+    double T_i_c[7];
+    amd::se3_mul7(calib_cam.T_i_c[0].data(), T_b_c + 7 * free_extrinsic_camera, T_i_c);
+    std::copy(T_i_c, T_i_c + 7, calib_cam.T_i_c[free_extrinsic_camera].data());
+  }
+  for (size_t c = 0; c < f.cam_ptr.size(); c++) std::copy(&f.poses[7 * c], &f.poses[7 * c] + 7, f.cam_ptr[c]->T_w_c.data());
+  for (size_t l = 0; l < f.lm_ptr.size(); l++)
+    for (int j = 0; j < 3; j++) f.lm_ptr[l]->p.data()[j] = f.points[3 * l + j];
+  if (options.verbosity_level >= 1)
+    std::printf("vslam_hip rig BA (extrinsic of camera %d): %d bodies, iterations %d, initial cost %.6e, final cost %.6e, termination %d, %.3f ms\n",
+                free_extrinsic_camera, (int)r.rig.n_bodies, sum.iterations, sum.initial_cost, sum.final_cost, sum.termination, sum.total_ms);
 }
 
 // The rig form of global_bundle_adjustment (vsl_global_bundle_adjust_rig): the reference's global_bundle_adjustment

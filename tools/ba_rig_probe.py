@@ -1,7 +1,8 @@
 """Rig-constrained local BA against the host-decided free loop on the benchmark's local window (7 stereo keyframes =
 14 cameras, ~15k landmarks): ms per LM iteration of Context.bundle_adjust_rig and of Context.bundle_adjust under
 "ba_no_fused", median of 20 solves, with the reduced-system sizes and the device stage times of a separate profiled run.
-One variant per process (argv[1] = rig | free): run three processes per variant, alternating.  One JSON line.
+One variant per process (argv[1] = rig | free | rig_ext): run three processes per variant, alternating.  One JSON line.
+rig_ext: Context.bundle_adjust_rig_ext on the same window with extrinsic block 1 free (one more 6-dof slot and the border).
 
 argv[1] = map_dense | map | map_free: the benchmark's 500-keyframe loop (the scene of bench.py's global-BA leg: 500
 bodies, 1000 cameras, ~100 k landmark candidates; argv[2] = keyframes) through (a) Context.bundle_adjust_rig, the dense rig
@@ -81,6 +82,15 @@ if variant == "rig":
         rig = vsl.RigArrays(bodies, fixed, np.arange(n_cams) // 2, T_b_c)
         return ctx.bundle_adjust_rig(arr, rig, max_iters=max_iters)
     n_unknowns = 6 * int((fixed == 0).sum())
+elif variant == "rig_ext":
+    bodies = np.asarray(d["poses"]).reshape(-1, 7)[0::2]
+    fixed = np.asarray(d["cam_fixed"])[0::2]
+
+    def solve(max_iters):
+        arr = vsl.BaArrays.from_dict(d)
+        rig = vsl.RigArrays(bodies, fixed, np.arange(n_cams) // 2, T_b_c)
+        return ctx.bundle_adjust_rig_ext(arr, rig, T_b_c.copy(), ext_free=(0, 1), max_iters=max_iters)
+    n_unknowns = 6 * (int((fixed == 0).sum()) + 1)
 else:
     ctx.set_diagnostic("ba_no_fused", 1)
 

@@ -700,6 +700,58 @@ class Context:
                                           db.ctypes.data_as(f64p), C.byref(cost), C.byref(ok)))
         return dict(S=S, rhs=rhs, scale_b=scale_b, db=db, cost=cost.value, chol_ok=ok.value)
 
+    # ---- rig bundle adjustment with the extrinsics as unknowns (include/vslam_hip.h)
+    @staticmethod
+    def _ext_args(T_b_c, ext_free):
+        """(the caller's T_b_c as a contiguous float64 [2, 7] -- the SAME memory when it already is one --, the uint8 pair)."""
+        T = np.asarray(T_b_c)
+        if T.dtype != np.float64 or not T.flags.c_contiguous or T.size != 14:
+            raise ValueError("T_b_c: a C-contiguous float64 array of 14 values (it is updated in place)")
+        ef = np.ascontiguousarray([1 if f else 0 for f in ext_free], np.uint8)
+        if ef.shape != (2,):
+            raise ValueError("ext_free: two flags")
+        return T, ef
+
+    def bundle_adjust_rig_ext(self, arr, rig, T_b_c, ext_free=(0, 1), use_huber=True, huber=1.0, max_iters=20, verbosity=0):
+        """vsl_bundle_adjust_rig_ext: bundle_adjust_rig with the extrinsic blocks flagged in ext_free estimated beside the
+        bodies.  Updates rig.body_poses, arr.points, arr.poses and T_b_c ([2, 7] float64) in place; rig.T_b_c is ignored."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        T, ef = self._ext_args(T_b_c, ext_free)
+        o = self._ba_opts(use_huber, huber, max_iters, verbosity)
+        s = BaSummary()
+        self._ck(self.L.vsl_bundle_adjust_rig_ext(self.h, C.byref(st), C.byref(rg), ef.ctypes.data_as(u8p), T.ctypes.data_as(f64p),
+                                                  C.byref(o), C.byref(s)))
+        return s
+
+    def ba_rig_ext_linearize(self, arr, rig, T_b_c, ext_free=(0, 1), use_huber=True, huber=1.0):
+        """(S, g, cost) of the reduced system over [free bodies | free extrinsic blocks]: Huber corrector, no scaling, no
+        damping (vsl_ba_rig_ext_linearize)."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        T, ef = self._ext_args(T_b_c, ext_free)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * (rig.n_free + int(ef.sum()))
+        S, g = np.zeros((n, n)), np.zeros(n)
+        cost, nb, ne = C.c_double(), C.c_int32(), C.c_int32()
+        self._ck(self.L.vsl_ba_rig_ext_linearize(self.h, C.byref(st), C.byref(rg), ef.ctypes.data_as(u8p), T.ctypes.data_as(f64p),
+                                                 C.byref(o), S.ctypes.data_as(f64p), g.ctypes.data_as(f64p), C.byref(cost),
+                                                 C.byref(nb), C.byref(ne)))
+        assert nb.value == rig.n_free and ne.value == int(ef.sum())
+        return S, g, cost.value
+
+    def ba_rig_ext_system(self, arr, rig, T_b_c, inv_radius=0.0, ext_free=(0, 1), use_huber=True, huber=1.0):
+        """The scaled, damped reduced system of the extrinsics solve's first step (vsl_ba_rig_ext_system): a dict with
+        S [nt, nt], rhs, scale, d [nt], cost, chol_ok; nt = 6 * (free bodies + free blocks)."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        T, ef = self._ext_args(T_b_c, ext_free)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        n = 6 * (rig.n_free + int(ef.sum()))
+        S, rhs, scale, d = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n)
+        cost, ok = C.c_double(), C.c_int32()
+        self._ck(self.L.vsl_ba_rig_ext_system(self.h, C.byref(st), C.byref(rg), ef.ctypes.data_as(u8p), T.ctypes.data_as(f64p),
+                                              C.byref(o), C.c_double(inv_radius), S.ctypes.data_as(f64p), rhs.ctypes.data_as(f64p),
+                                              scale.ctypes.data_as(f64p), d.ctypes.data_as(f64p), C.byref(cost), C.byref(ok)))
+        return dict(S=S, rhs=rhs, scale=scale, d=d, cost=cost.value, chol_ok=ok.value)
+
     def global_bundle_adjust_rig(self, arr, rig, use_huber=True, huber=1.0, max_iters=20, verbosity=0):
         """vsl_global_bundle_adjust_rig: bundle_adjust_rig for a whole map -- the reduced body system gathered over the
         co-visible body pairs only and stored dense / band / cyclic band (last_ba_layout tells which)."""

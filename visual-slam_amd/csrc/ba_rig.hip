@@ -4,7 +4,8 @@
 // vsl_global_bundle_adjust_rig / vsl_ba_rig_map_system run the same chain for whole maps: the reduced body
 // system gathered over co-visible body pairs only (rig_schur_pairs_kernel) into dense / band / cyclic-band storage.
 // The covariances of the rig posterior (vsl_ba_rig_covariance, vsl_ba_rig_relative_pose_covariance) are
-// the section "COVARIANCES" at the end of this file.
+// the section "COVARIANCES" of this file; the extrinsics as unknowns (vsl_bundle_adjust_rig_ext) the section
+// "EXTRINSICS" at its end.
 //
 // Residual, camera models, Huber corrector and cost are those of vsl_bundle_adjust (ba_device.h); what changes is the
 // pose block an observation differentiates against.  With T_c_b = T_b_c^-1 = (R, t),
@@ -1251,4 +1252,659 @@ extern "C" int vsl_ba_rig_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_pr
   for (size_t q = 0; q < np; q++) ns += sing[q] ? 1 : 0;
   if (n_singular) *n_singular = ns;
   return VSL_OK;
+}
+
+// ================================================================================================== EXTRINSICS
+// vsl_bundle_adjust_rig_ext / vsl_ba_rig_ext_linearize / vsl_ba_rig_ext_system (include/vslam_hip.h "rig bundle
+// adjustment with the extrinsics as unknowns"): the rig solve with T_b_c[k] <- T_b_c[k] exp(eps_k) of the
+// free blocks estimated beside the bodies.  T_w_c = T_w_b T_b_c[k] exp(eps_k), so the block of an observation against
+// eps_k is the CAMERA Jacobian F_x = F_c, before the adjoint that makes it F_b.  A free block is one more pose slot
+// behind the free bodies (RigExtPlan, ba_rig_plan.h): the solver's pose-block array is [bodies | block 0 | block 1], the
+// cameras and Ad(T_b_c^-1) are derived from it per linearisation, and the kernels of ba.hip that work on slots (scaling,
+// diagonals, update, norms) and the gathers of this file that work on per-slot lists (rig_body_block_kernel,
+// rig_schur_block_kernel, rig_backsub_kernel) run unchanged on n_slots = free bodies + free blocks.  New here:
+//   rigx_linearize_kernel      r, F_b, F_x, E per observation (robustified, scaled), cost partials
+//   rigx_border_kernel         per (slot, free block, segment): a body slot sums H_be = sum F_b^T F_x over its observations
+//                              in that block (36); the block's own slot sums H_ee (21) and g_e (6); the other free block's
+//                              slot sums nothing (H_ee' = 0: no observation is in both) and its zeros are written
+//   rigx_border_finish_kernel  segments in order -> Hbe per (slot, block), H and g of the extrinsic slots
+//   rigx_lm_groups_kernel      rig_lm_groups_kernel on index lists: an extrinsic group's observations are not adjacent
+//   rigx_schur_finish_kernel   rig_schur_finish_kernel plus S_eb = H_eb - sum Y_e W_b^T on the border blocks
+//   rigx_model_kernel          model cost change with both pose slots of an observation
+// No free body: the body launches (grids over free bodies) are skipped, nothing else changes.  Every sum in a fixed
+// order, no atomics.  ext_free = {0, 0} never gets here: the three calls hand over to the rig calls.
+namespace {
+
+__global__ __launch_bounds__(256) void rigx_linearize_kernel(BaDims D, int B, const double* __restrict__ pose_blocks,
+                                                             const double* __restrict__ cams, const double* __restrict__ points,
+                                                             const double* __restrict__ intr, const int* __restrict__ cam_intr,
+                                                             const int* __restrict__ cam_slot, const int* __restrict__ cam_eslot,
+                                                             const int* __restrict__ obs_cam, const int* __restrict__ obs_lm,
+                                                             const double* __restrict__ obs_uv, const double* __restrict__ scale_c,
+                                                             const double* __restrict__ scale_l, double* __restrict__ r_out,
+                                                             double* __restrict__ F_out, double* __restrict__ Fx_out,
+                                                             double* __restrict__ E_out, double* __restrict__ partials) {
+  __shared__ double sh[256];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double c = 0;
+  if (i < D.O) {
+    const int cam = obs_cam[i], lm = obs_lm[i], k = cam_intr[cam];
+    double r[2], F[12], Fx[12], E[6];
+    residual_blocks(k ? D.model1 : D.model0, intr + 8 * k, cams + 7 * (size_t)cam, points + 3 * (size_t)lm, obs_uv + 2 * (size_t)i, r,
+                    F, E, true);
+#pragma unroll
+    for (int j = 0; j < 12; j++) Fx[j] = F[j];
+    // T_c_b = (R^T, -R^T t) of the extrinsic at this linearisation point
+    const double* e = pose_blocks + 7 * (size_t)(B + k);
+    double Re[9], Rt[12];
+    quat_R(e, Re);
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) Rt[3 * a + b] = Re[3 * b + a];
+#pragma unroll
+    for (int a = 0; a < 3; a++) Rt[9 + a] = -(Rt[3 * a] * e[4] + Rt[3 * a + 1] * e[5] + Rt[3 * a + 2] * e[6]);
+    rig_body_jacobian(Rt, F);
+    const double s = r[0] * r[0] + r[1] * r[1];
+    double rho0 = s, rho1 = 1.0;
+    if (D.use_huber) huber(s, D.huber, rho0, rho1);
+    c = 0.5 * rho0;
+    const double sr = sqrt(rho1);
+    r_out[2 * (size_t)i] = r[0] * sr;
+    r_out[2 * (size_t)i + 1] = r[1] * sr;
+    const int fb = cam_slot[cam], fe = cam_eslot[cam];
+    for (int j = 0; j < 6; j++) {
+      const double sb = (scale_c && fb >= 0) ? scale_c[6 * fb + j] : 1.0;
+      F_out[12 * (size_t)i + j] = F[j] * sr * sb;
+      F_out[12 * (size_t)i + 6 + j] = F[6 + j] * sr * sb;
+      const double se = (scale_c && fe >= 0) ? scale_c[6 * fe + j] : 1.0;
+      Fx_out[12 * (size_t)i + j] = Fx[j] * sr * se;
+      Fx_out[12 * (size_t)i + 6 + j] = Fx[6 + j] * sr * se;
+    }
+    for (int j = 0; j < 3; j++) {
+      const double sc = scale_l ? scale_l[3 * (size_t)lm + j] : 1.0;
+      E_out[6 * (size_t)i + j] = E[j] * sr * sc;
+      E_out[6 * (size_t)i + 3 + j] = E[3 + j] * sr * sc;
+    }
+  }
+  const double t = block_sum_256(c, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// grid (slots, free blocks, segments): a workgroup sums every `segments`-th 256-observation slice of its slot's
+// observation list into part[((slot, block), segment)][36].  Slot of a body: H_be = sum F_b^T F_x (6 x 6 row-major) over
+// the observations whose camera is of that block.  The block's own slot: [0, 21) the upper triangle of sum F_x^T F_x,
+// [21, 27) sum F_x^T r, the rest zero.  The slot of the other free block: 36 zeros.
+__global__ __launch_bounds__(256) void rigx_border_kernel(int nfb, const int* __restrict__ so_start, const int* __restrict__ so_obs,
+                                                          const int* __restrict__ obs_cam, const int* __restrict__ cam_eslot,
+                                                          const double* __restrict__ r, const double* __restrict__ F,
+                                                          const double* __restrict__ Fx, double* __restrict__ part) {
+  __shared__ double sh[4 * 36];
+  const int s = blockIdx.x, kx = blockIdx.y, ne = gridDim.y, seg = blockIdx.z, nseg = gridDim.z;
+  const int es = nfb + kx;
+  double acc[36];
+#pragma unroll
+  for (int k = 0; k < 36; k++) acc[k] = 0;
+  if (s < nfb) {
+    for (int q = so_start[s] + seg * 256 + threadIdx.x; q < so_start[s + 1]; q += 256 * nseg) {
+      const int i = so_obs[q];
+      if (cam_eslot[obs_cam[i]] != es) continue;
+      const double* f = F + 12 * (size_t)i;
+      const double* x = Fx + 12 * (size_t)i;
+#pragma unroll
+      for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = 0; b < 6; b++) acc[6 * a + b] += f[a] * x[b] + f[6 + a] * x[6 + b];
+    }
+  } else if (s == es) {
+    for (int q = so_start[s] + seg * 256 + threadIdx.x; q < so_start[s + 1]; q += 256 * nseg) {
+      const int i = so_obs[q];
+      const double* x = Fx + 12 * (size_t)i;
+      const double r0 = r[2 * (size_t)i], r1 = r[2 * (size_t)i + 1];
+      int k = 0;
+#pragma unroll
+      for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = a; b < 6; b++) acc[k++] += x[a] * x[b] + x[6 + a] * x[6 + b];
+#pragma unroll
+      for (int a = 0; a < 6; a++) acc[21 + a] += x[a] * r0 + x[6 + a] * r1;
+    }
+  }
+  rig_block_sum<36>(acc, sh);
+  if (threadIdx.x == 0) {
+    double* o = part + (((size_t)s * ne + kx) * nseg + seg) * 36;
+#pragma unroll
+    for (int k = 0; k < 36; k++) o[k] = acc[k];
+  }
+}
+
+// grid (slots, free blocks), 64 threads: the segments in order.  Hbe[(slot, block)][36] for every slot but the block's
+// own (H_be of a body, the zeros of H_ee'); the block's own slot gets H (6 x 6, mirrored) and g
+__global__ __launch_bounds__(64) void rigx_border_finish_kernel(int nfb, int nseg, const double* __restrict__ part,
+                                                                double* __restrict__ Hbe, double* __restrict__ H,
+                                                                double* __restrict__ g) {
+  const int s = blockIdx.x, kx = blockIdx.y, ne = gridDim.y, e = threadIdx.x;
+  if (e >= 36) return;
+  const double* p = part + ((size_t)s * ne + kx) * nseg * 36;
+  double v = 0;
+  for (int q = 0; q < nseg; q++) v += p[(size_t)q * 36 + e];
+  if (s != nfb + kx) {
+    Hbe[((size_t)s * ne + kx) * 36 + e] = v;
+  } else if (e >= 21) {
+    if (e < 27) g[6 * (size_t)s + (e - 21)] = v;
+  } else {
+    int a = 0, rem = e;  // e-th entry of the upper triangle, row-major
+    while (rem >= 6 - a) {
+      rem -= 6 - a;
+      a++;
+    }
+    const int b = a + rem;
+    H[36 * (size_t)s + 6 * a + b] = v;
+    H[36 * (size_t)s + 6 * b + a] = v;
+  }
+}
+
+// rig_lm_groups_kernel with every group's observations named through an index list (grp_first / grp_obs); a group of a
+// slot >= nfb is an extrinsic group and reads F_x
+__global__ __launch_bounds__(256) void rigx_lm_groups_kernel(BaDims D, int nfb, const int* __restrict__ lm_start,
+                                                             const int* __restrict__ lm_grp, const int* __restrict__ grp_slot,
+                                                             const int* __restrict__ grp_first, const int* __restrict__ grp_obs,
+                                                             const double* __restrict__ r, const double* __restrict__ F,
+                                                             const double* __restrict__ Fx, const double* __restrict__ E,
+                                                             const double* __restrict__ diag_l, double inv_radius,
+                                                             double* __restrict__ W, double* __restrict__ Y,
+                                                             double* __restrict__ Pinv, double* __restrict__ bl) {
+  const int l = blockIdx.x * 256 + threadIdx.x;
+  if (l >= D.L) return;
+  double P[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+  for (int i = lm_start[l]; i < lm_start[l + 1]; i++) {
+    const double* e = E + 6 * (size_t)i;
+    const double r0 = r[2 * (size_t)i], r1 = r[2 * (size_t)i + 1];
+    for (int j = 0; j < 3; j++) {
+      for (int k = j; k < 3; k++) P[3 * j + k] += e[j] * e[k] + e[3 + j] * e[3 + k];
+      b[j] += e[j] * r0 + e[3 + j] * r1;
+    }
+  }
+  if (diag_l)
+    for (int j = 0; j < 3; j++) P[4 * j] += diag_l[3 * (size_t)l + j] * inv_radius;
+  P[3] = P[1]; P[6] = P[2]; P[7] = P[5];
+  double Pi[9];
+  if (!inv3(P, Pi))
+    for (int j = 0; j < 9; j++) Pi[j] = 0.0;
+  for (int j = 0; j < 9; j++) Pinv[9 * (size_t)l + j] = Pi[j];
+  for (int j = 0; j < 3; j++) bl[3 * (size_t)l + j] = b[j];
+  for (int g = lm_grp[l]; g < lm_grp[l + 1]; g++) {
+    const double* Fs = grp_slot[g] < nfb ? F : Fx;
+    double w[18];
+    for (int j = 0; j < 18; j++) w[j] = 0;
+    for (int q = grp_first[g]; q < grp_first[g + 1]; q++) {
+      const int i = grp_obs[q];
+      const double* f = Fs + 12 * (size_t)i;
+      const double* e = E + 6 * (size_t)i;
+      for (int a = 0; a < 6; a++)
+        for (int j = 0; j < 3; j++) w[3 * a + j] += f[a] * e[j] + f[6 + a] * e[3 + j];
+    }
+    for (int a = 0; a < 6; a++)
+      for (int j = 0; j < 3; j++) {
+        W[18 * (size_t)g + 3 * a + j] = w[3 * a + j];
+        Y[18 * (size_t)g + 3 * a + j] = w[3 * a] * Pi[j] + w[3 * a + 1] * Pi[3 + j] + w[3 * a + 2] * Pi[6 + j];
+      }
+  }
+}
+
+// grid (slots, slots), 64 threads: rig_schur_finish_kernel with the border.  Block (a, b), a > b, of an extrinsic slot a
+// (body slot or the other block b): S_ab = H_eb - sum, H_eb = Hbe[(b, a - nfb)]^T; two body slots: -sum; the diagonal as
+// there.  Mirrored: S is exactly symmetric.  Workgroup (0, 0) arms the two flags of the step.
+__global__ __launch_bounds__(64) void rigx_schur_finish_kernel(int n, int nfb, int ne, int nseg, const double* __restrict__ spart,
+                                                               const double* __restrict__ H, const double* __restrict__ g_b,
+                                                               const double* __restrict__ Hbe, const double* __restrict__ diag_c,
+                                                               double inv_radius, double* __restrict__ S, double* __restrict__ rhs,
+                                                               int* __restrict__ flag) {
+  const int a = blockIdx.x, b = blockIdx.y;
+  if (b > a) return;
+  if (a == 0 && threadIdx.x < 2) flag[threadIdx.x] = 1;
+  const int e = threadIdx.x;
+  if (e >= 42) return;
+  const double* p = spart + ((size_t)a * (a + 1) / 2 + b) * nseg * 42;
+  double sum = 0;
+  for (int q = 0; q < nseg; q++) sum += p[(size_t)q * 42 + e];
+  if (e < 36) {
+    const int i = e / 6, j = e - 6 * i;
+    const size_t at = (size_t)(6 * a + i) * n + 6 * b + j, mirror = (size_t)(6 * b + j) * n + 6 * a + i;
+    if (a != b) {
+      const double v = a >= nfb ? Hbe[((size_t)b * ne + (a - nfb)) * 36 + 6 * j + i] - sum : -sum;
+      S[at] = v;
+      S[mirror] = v;
+    } else if (i >= j) {
+      double h = H[36 * (size_t)a + e];
+      if (i == j && diag_c) h += diag_c[6 * (size_t)a + i] * inv_radius;
+      const double v = h - sum;
+      S[at] = v;
+      S[mirror] = v;
+    }
+  } else if (a == b) {
+    rhs[6 * (size_t)a + (e - 36)] = g_b[6 * (size_t)a + (e - 36)] - sum;
+  }
+}
+
+// model cost change partials -(J d)^T (r + J d / 2) with J d = F_b d_body + F_x d_ext + E d_l
+__global__ __launch_bounds__(256) void rigx_model_kernel(int O, const int* __restrict__ obs_cam, const int* __restrict__ obs_lm,
+                                                         const int* __restrict__ cam_slot, const int* __restrict__ cam_eslot,
+                                                         const double* __restrict__ r, const double* __restrict__ F,
+                                                         const double* __restrict__ Fx, const double* __restrict__ E,
+                                                         const double* __restrict__ dc, const double* __restrict__ dl,
+                                                         double* __restrict__ partials) {
+  __shared__ double sh[256];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double v = 0;
+  if (i < O) {
+    const int cam = obs_cam[i], fb = cam_slot[cam], fe = cam_eslot[cam], lm = obs_lm[i];
+    const double* f = F + 12 * (size_t)i;
+    const double* x = Fx + 12 * (size_t)i;
+    const double* e = E + 6 * (size_t)i;
+    double m0 = 0, m1 = 0;
+    if (fb >= 0)
+      for (int j = 0; j < 6; j++) {
+        m0 += f[j] * dc[6 * fb + j];
+        m1 += f[6 + j] * dc[6 * fb + j];
+      }
+    if (fe >= 0)
+      for (int j = 0; j < 6; j++) {
+        m0 += x[j] * dc[6 * fe + j];
+        m1 += x[6 + j] * dc[6 * fe + j];
+      }
+    for (int j = 0; j < 3; j++) {
+      m0 += e[j] * dl[3 * (size_t)lm + j];
+      m1 += e[3 + j] * dl[3 * (size_t)lm + j];
+    }
+    v = -(m0 * (r[2 * (size_t)i] + m0 / 2.0) + m1 * (r[2 * (size_t)i + 1] + m1 / 2.0));
+  }
+  const double t = block_sum_256(v, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// ---- host state of the extrinsics solve
+struct RigxSet {
+  double *blocks = nullptr, *cams = nullptr, *points = nullptr;  // blocks: [bodies | extrinsic 0 | extrinsic 1], 7 each
+  double *r = nullptr, *F = nullptr, *Fx = nullptr, *E = nullptr, *n2l = nullptr, *grad_l = nullptr, *H = nullptr, *g = nullptr;
+  double *diag_c = nullptr, *diag_l = nullptr;
+  double* Hbe = nullptr;  // [(slot, free block)][36]: H_be of the body slots, the zeros of H_ee'
+};
+
+struct RigxState {
+  BaDims D;  // of the shared kernels: nfree = SLOTS (free bodies + free blocks), n = 6 nfree
+  int B = 0, G = 0, nfb = 0, ne = 0;
+  RigPlan plan;
+  RigExtPlan xp;
+  DevArena arena;
+  int nb_obs = 1, obs_seg = 1, grp_seg = 1;
+  RigxSet cur, cand;
+  double *intr = nullptr, *obs_uv = nullptr, *scale_c = nullptr, *scale_l = nullptr, *W = nullptr, *Y = nullptr, *Pinv = nullptr;
+  double *bl = nullptr, *S = nullptr, *rhs = nullptr, *dc = nullptr, *dl = nullptr, *partials = nullptr;
+  double *scalars = nullptr, *body_part = nullptr, *border_part = nullptr, *schur_part = nullptr;
+  int* flag = nullptr;
+  int *cam_intr = nullptr, *cam_body = nullptr, *cam_slot = nullptr, *cam_eslot = nullptr, *pose_free = nullptr;
+  int *obs_cam = nullptr, *obs_lm = nullptr, *lm_start = nullptr, *lm_grp = nullptr, *grp_slot = nullptr, *grp_first = nullptr;
+  int *grp_obs = nullptr, *sg_start = nullptr, *sg_grp = nullptr, *sg_lm = nullptr, *so_start = nullptr, *so_obs = nullptr;
+};
+
+int rigx_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const vsl_ba_rig* rig, const uint8_t* ext_free,
+                  const double* T_b_c, const vsl_ba_options* opt, RigxState& st) {
+  if (!p || !rig || !opt || !ext_free || !T_b_c || !p->poses || !p->cam_intr || !p->intr || !p->points || !p->obs_cam || !p->obs_lm ||
+      !p->obs_uv || !rig->body_poses || !rig->body_fixed || !rig->cam_body)
+    return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null pointer", who);
+  for (int k = 0; k < 2; k++)
+    if (p->cam_model[k] < 0 || p->cam_model[k] > 3) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: unknown camera model %d", who, p->cam_model[k]);
+  RigPlanIn in;
+  in.n_cams = p->n_cams; in.n_lms = p->n_lms; in.n_obs = p->n_obs;
+  in.cam_intr = p->cam_intr; in.obs_cam = p->obs_cam; in.obs_lm = p->obs_lm;
+  in.n_bodies = rig->n_bodies; in.body_fixed = rig->body_fixed; in.cam_body = rig->cam_body; in.T_b_c = T_b_c;
+  int rc;
+  try {
+    rc = rig_ext_plan_build(in, ext_free, st.plan, st.xp);
+  } catch (const std::bad_alloc&) {
+    return vsl_fail(ctx, VSL_ERR_NOMEM, "%s: out of host memory", who);
+  }
+  if (rc != RIG_PLAN_OK) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: %s (index %d)", who, rig_plan_message(rc), st.plan.first_bad);
+  return VSL_OK;
+}
+
+// plans -> ONE arena (the context's), uploads; synchronises
+int rigx_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt, RigxState& st) {
+  const RigPlan& hp = st.plan;
+  const RigExtPlan& xp = st.xp;
+  BaDims& D = st.D;
+  D.C = p->n_cams; D.L = p->n_lms; D.O = p->n_obs;
+  D.nfree = xp.n_slots; D.n = 6 * xp.n_slots;
+  D.model0 = p->cam_model[0]; D.model1 = p->cam_model[1];
+  D.use_huber = opt->use_huber; D.huber = opt->huber_parameter;
+  st.B = rig->n_bodies; st.G = xp.n_groups(); st.nfb = hp.n_free; st.ne = xp.n_ext;
+  const size_t C = D.C, B = st.B, L = D.L, O = D.O, G = st.G, n = D.n, ns = D.nfree, ne = st.ne, nfb = st.nfb;
+  st.nb_obs = (int)((O + 255) / 256);
+  const size_t nb_upd = (std::max(B + 2, L) + 255) / 256, nb_diag = (std::max(n, 3 * L) + 255) / 256;
+  // segments as the rig solve takes them (rig_segments), from the longest slot list: the extrinsic slots' are the long ones
+  int max_obs = 0, max_grp = 0;
+  for (int s = 0; s < xp.n_slots; s++) {
+    max_obs = std::max(max_obs, xp.so_start[s + 1] - xp.so_start[s]);
+    max_grp = std::max(max_grp, xp.sg_start[s + 1] - xp.sg_start[s]);
+  }
+  st.obs_seg = rig_segments(max_obs);
+  st.grp_seg = rig_segments(max_grp);
+  ArenaPlan plan(80);
+  for (RigxSet* s : {&st.cur, &st.cand}) {
+    plan.add(s->blocks, 7 * (B + 2)); plan.add(s->cams, 7 * C); plan.add(s->points, 3 * L);
+    plan.add(s->r, 2 * O); plan.add(s->F, 12 * O); plan.add(s->Fx, 12 * O); plan.add(s->E, 6 * O);
+    plan.add(s->n2l, 3 * L); plan.add(s->grad_l, 3 * L); plan.add(s->H, 36 * ns); plan.add(s->g, n);
+    plan.add(s->diag_c, n); plan.add(s->diag_l, 3 * L); plan.add(s->Hbe, 36 * ns * ne);
+  }
+  plan.add(st.intr, 16); plan.add(st.obs_uv, 2 * O);
+  plan.add(st.scale_c, n); plan.add(st.scale_l, 3 * L);
+  plan.add(st.W, 18 * G); plan.add(st.Y, 18 * G); plan.add(st.Pinv, 9 * L); plan.add(st.bl, 3 * L);
+  plan.add(st.S, n * n); plan.add(st.rhs, n); plan.add(st.dc, n); plan.add(st.dl, 3 * L);
+  plan.add(st.partials, std::max(std::max((size_t)st.nb_obs, 2 * nb_upd), nb_diag));
+  plan.add(st.scalars, 32);  // 16 doubles, then the flags
+  plan.add(st.body_part, std::max<size_t>(1, nfb) * st.obs_seg * 27);
+  plan.add(st.border_part, ns * ne * st.obs_seg * 36);
+  plan.add(st.schur_part, ns * (ns + 1) / 2 * st.grp_seg * 42);
+  plan.add(st.cam_intr, C); plan.add(st.cam_body, C); plan.add(st.cam_slot, C); plan.add(st.cam_eslot, C);
+  plan.add(st.pose_free, B + 2); plan.add(st.obs_cam, O); plan.add(st.obs_lm, O);
+  plan.add(st.lm_start, L + 1); plan.add(st.lm_grp, L + 1);
+  plan.add(st.grp_slot, G); plan.add(st.grp_first, G + 1); plan.add(st.grp_obs, xp.grp_obs.size());
+  plan.add(st.sg_start, ns + 1); plan.add(st.sg_grp, G); plan.add(st.sg_lm, G);
+  plan.add(st.so_start, ns + 1); plan.add(st.so_obs, xp.so_obs.size());
+  hipError_t e = st.arena.acquire(ctx, ArenaPolicy::BORROWED, plan);
+  if (e != hipSuccess) return vsl_fail(ctx, e == hipErrorOutOfMemory ? VSL_ERR_NOMEM : VSL_ERR_HIP, "rig bundle adjustment (extrinsics): %zu bytes of device memory: %s", plan.total(), hipGetErrorString(e));
+  st.flag = (int*)(st.scalars + 16);
+
+  std::vector<double> uv(2 * O);
+  for (size_t q = 0; q < O; q++) {
+    uv[2 * q] = p->obs_uv[2 * (size_t)hp.perm[q]];
+    uv[2 * q + 1] = p->obs_uv[2 * (size_t)hp.perm[q] + 1];
+  }
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+  };
+  VSL_HIP(ctx, hipMemsetAsync(st.scalars, 0, 256, ctx->stream));
+  VSL_HIP(ctx, up(st.cur.blocks, rig->body_poses, 56 * B));
+  VSL_HIP(ctx, up(st.cur.blocks + 7 * B, hp.T_b_c, sizeof(hp.T_b_c)));  // normalised by the plan
+  VSL_HIP(ctx, up(st.cur.points, p->points, 24 * L));
+  VSL_HIP(ctx, up(st.intr, p->intr, 128));
+  VSL_HIP(ctx, up(st.obs_uv, uv.data(), 16 * O));
+  VSL_HIP(ctx, up(st.cam_intr, p->cam_intr, 4 * C));
+  VSL_HIP(ctx, up(st.cam_body, rig->cam_body, 4 * C));
+  VSL_HIP(ctx, up(st.cam_slot, hp.cam_slot.data(), 4 * C));
+  VSL_HIP(ctx, up(st.cam_eslot, xp.cam_eslot.data(), 4 * C));
+  VSL_HIP(ctx, up(st.pose_free, xp.pose_free.data(), 4 * (B + 2)));
+  VSL_HIP(ctx, up(st.obs_cam, hp.obs_cam.data(), 4 * O));
+  VSL_HIP(ctx, up(st.obs_lm, hp.obs_lm.data(), 4 * O));
+  VSL_HIP(ctx, up(st.lm_start, hp.lm_start.data(), 4 * (L + 1)));
+  VSL_HIP(ctx, up(st.lm_grp, xp.lm_grp.data(), 4 * (L + 1)));
+  VSL_HIP(ctx, up(st.grp_slot, xp.grp_slot.data(), 4 * G));
+  VSL_HIP(ctx, up(st.grp_first, xp.grp_first.data(), 4 * (G + 1)));
+  VSL_HIP(ctx, up(st.grp_obs, xp.grp_obs.data(), 4 * xp.grp_obs.size()));
+  VSL_HIP(ctx, up(st.sg_start, xp.sg_start.data(), 4 * (ns + 1)));
+  VSL_HIP(ctx, up(st.sg_grp, xp.sg_grp.data(), 4 * G));
+  VSL_HIP(ctx, up(st.sg_lm, xp.sg_lm.data(), 4 * G));
+  VSL_HIP(ctx, up(st.so_start, xp.so_start.data(), 4 * (ns + 1)));
+  VSL_HIP(ctx, up(st.so_obs, xp.so_obs.data(), 4 * xp.so_obs.size()));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the uploads read host vectors that die here
+  return VSL_OK;
+}
+
+// cameras (rig_cams_kernel reads the extrinsics from the tail of the pose blocks), blocks and cost (-> scalars[cost_slot])
+int rigx_linearize(vsl_ctx* ctx, RigxState& st, RigxSet& s, bool scaled, int cost_slot) {
+  VslStage stage(ctx, VSL_STAGE_BA_LIN);
+  hipLaunchKernelGGL(rig_cams_kernel, dim3((st.D.C + 255) / 256), dim3(256), 0, ctx->stream, st.D.C, s.blocks, s.blocks + 7 * (size_t)st.B,
+                     st.cam_body, st.cam_intr, s.cams);
+  hipLaunchKernelGGL(rigx_linearize_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D, st.B, s.blocks, s.cams, s.points, st.intr,
+                     st.cam_intr, st.cam_slot, st.cam_eslot, st.obs_cam, st.obs_lm, st.obs_uv, scaled ? st.scale_c : nullptr,
+                     scaled ? st.scale_l : nullptr, s.r, s.F, s.Fx, s.E, st.partials);
+  VSL_CHECK_LAUNCH(ctx);
+  return vsl_ba_reduce_launch(ctx, st.partials, st.nb_obs, st.scalars, cost_slot, false);
+}
+
+// landmark columns; H, g of the body slots (skipped without a free body) and of the extrinsic slots; the border blocks
+int rigx_columns(vsl_ctx* ctx, RigxState& st, RigxSet& s) {
+  VslStage stage(ctx, VSL_STAGE_BA_LIN);
+  int rc = vsl_ba_lm_cols_launch(ctx, st.D.L, st.lm_start, s.r, s.E, s.n2l, s.grad_l);
+  if (rc) return rc;
+  if (st.nfb > 0) {
+    hipLaunchKernelGGL(rig_body_block_kernel, dim3(st.nfb, st.obs_seg), dim3(256), 0, ctx->stream, st.so_start, st.so_obs, s.r, s.F,
+                       st.body_part);
+    if ((rc = vsl_ba_block_finish_launch(ctx, st.nfb, st.obs_seg, st.body_part, s.H, s.g))) return rc;
+  }
+  hipLaunchKernelGGL(rigx_border_kernel, dim3(st.D.nfree, st.ne, st.obs_seg), dim3(256), 0, ctx->stream, st.nfb, st.so_start, st.so_obs,
+                     st.obs_cam, st.cam_eslot, s.r, s.F, s.Fx, st.border_part);
+  hipLaunchKernelGGL(rigx_border_finish_kernel, dim3(st.D.nfree, st.ne), dim3(64), 0, ctx->stream, st.nfb, st.obs_seg, st.border_part,
+                     s.Hbe, s.H, s.g);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int rigx_diag_gmax(vsl_ctx* ctx, RigxState& st, RigxSet& s, int slot) {
+  return vsl_ba_diag_gmax_launch(ctx, st.D.nfree, st.D.L, s.H, s.n2l, s.g, s.grad_l, st.scale_c, st.scale_l, s.diag_c, s.diag_l,
+                                 st.partials, st.scalars, slot);
+}
+
+// the reduced system over [free bodies | free blocks] of the current set; damped by inv_radius when `damp`
+int rigx_schur(vsl_ctx* ctx, RigxState& st, bool damp, double inv_radius) {
+  VslStage stage(ctx, VSL_STAGE_BA_SCHUR);
+  const RigxSet& s = st.cur;
+  const int ns = st.D.nfree;
+  hipLaunchKernelGGL(rigx_lm_groups_kernel, dim3((st.D.L + 255) / 256), dim3(256), 0, ctx->stream, st.D, st.nfb, st.lm_start, st.lm_grp,
+                     st.grp_slot, st.grp_first, st.grp_obs, s.r, s.F, s.Fx, s.E, damp ? s.diag_l : nullptr, inv_radius, st.W, st.Y,
+                     st.Pinv, st.bl);
+  hipLaunchKernelGGL(rig_schur_block_kernel, dim3(ns, ns, st.grp_seg), dim3(256), 0, ctx->stream, st.sg_start, st.sg_grp, st.sg_lm, st.W,
+                     st.Y, st.bl, st.schur_part);
+  hipLaunchKernelGGL(rigx_schur_finish_kernel, dim3(ns, ns), dim3(64), 0, ctx->stream, st.D.n, st.nfb, st.ne, st.grp_seg, st.schur_part,
+                     s.H, s.g, s.Hbe, damp ? s.diag_c : nullptr, inv_radius, st.S, st.rhs, st.flag);
+  VSL_CHECK_LAUNCH(ctx);
+  return VSL_OK;
+}
+
+int rigx_solve(vsl_ctx* ctx, RigxState& st) {
+  VslStage stage(ctx, VSL_STAGE_BA_SOLVE);
+  const int n = st.D.n;
+  if (n <= 128) return vsl_ba_chol_small_launch(ctx, n, st.S, st.rhs, st.dc, st.flag + 1);
+  return vsl_chol_solve_band_dev(ctx, st.S, st.rhs, n, n, n, st.flag + 1, 0, st.dc);
+}
+
+int rigx_step(vsl_ctx* ctx, RigxState& st) {
+  VslStage stage(ctx, VSL_STAGE_BA_SOLVE);
+  const RigxSet& s = st.cur;
+  hipLaunchKernelGGL(rig_backsub_kernel, dim3((st.D.L + 255) / 256), dim3(256), 0, ctx->stream, st.D, st.lm_grp, st.grp_slot, st.W,
+                     st.Pinv, st.bl, st.dc, st.dl, st.flag);
+  hipLaunchKernelGGL(rigx_model_kernel, dim3(st.nb_obs), dim3(256), 0, ctx->stream, st.D.O, st.obs_cam, st.obs_lm, st.cam_slot,
+                     st.cam_eslot, s.r, s.F, s.Fx, s.E, st.dc, st.dl, st.partials);
+  VSL_CHECK_LAUNCH(ctx);
+  int rc = vsl_ba_reduce_launch(ctx, st.partials, st.nb_obs, st.scalars, 2, false);
+  if (rc) return rc;
+  // (the pose blocks of the update are the bodies and the two extrinsics)
+  return vsl_ba_update_launch(ctx, st.B + 2, st.D.L, st.pose_free, s.blocks, s.points, st.dc, st.dl, st.scale_c, st.scale_l,
+                              st.cand.blocks, st.cand.points, st.partials, st.scalars, 3);
+}
+
+int rigx_first_linearization(vsl_ctx* ctx, RigxState& st) {
+  int rc;
+  if ((rc = rigx_linearize(ctx, st, st.cur, false, 0))) return rc;
+  if ((rc = rigx_columns(ctx, st, st.cur))) return rc;
+  if ((rc = vsl_ba_make_scale_launch(ctx, st.D.nfree, st.D.L, st.cur.H, st.cur.n2l, st.scale_c, st.scale_l))) return rc;
+  if ((rc = rigx_linearize(ctx, st, st.cur, true, 0))) return rc;
+  if ((rc = rigx_columns(ctx, st, st.cur))) return rc;
+  return rigx_diag_gmax(ctx, st, st.cur, 1);
+}
+
+// T_b_c normalised as the plan does it: what a call without a free block hands back
+void rigx_normalised(const double* T_b_c, double* out) {
+  for (int k = 0; k < 2; k++) {
+    const double* T = T_b_c + 7 * k;
+    double nn = 0;
+    for (int j = 0; j < 4; j++) nn += T[j] * T[j];
+    nn = std::sqrt(nn);
+    for (int j = 0; j < 4; j++) out[7 * k + j] = T[j] / nn;
+    for (int j = 4; j < 7; j++) out[7 * k + j] = T[j];
+  }
+}
+
+}  // namespace
+
+extern "C" int vsl_ba_rig_ext_linearize(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const uint8_t* ext_free,
+                                        const double* T_b_c, const vsl_ba_options* opt, double* S, double* g, double* cost,
+                                        int* n_free_bodies, int* n_free_ext) {
+  if (!ctx) return VSL_ERR_INVALID;
+  if (!rig || !ext_free || !T_b_c) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_rig_ext_linearize: null pointer");
+  if (!S || !g || !cost || !n_free_bodies || !n_free_ext) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_rig_ext_linearize: null output");
+  if (!ext_free[0] && !ext_free[1]) {  // the rig call itself
+    vsl_ba_rig held = *rig;
+    held.T_b_c = T_b_c;
+    int nfb = 0;
+    const int rc = vsl_ba_rig_linearize(ctx, prob, &held, opt, S, g, cost, &nfb);
+    if (rc) return rc;
+    *n_free_bodies = nfb;
+    *n_free_ext = 0;
+    return VSL_OK;
+  }
+  RigxState st;
+  int rc = rigx_validate(ctx, "vsl_ba_rig_ext_linearize", prob, rig, ext_free, T_b_c, opt, st);
+  if (rc) return rc;
+  if (st.plan.n_fixed == 0)
+    return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_rig_ext_linearize: no fixed body: the gauge is free and the reduced system singular");
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = rigx_setup(ctx, prob, rig, opt, st))) return rc;
+  const size_t n = st.D.n;
+  std::vector<double> hS(n * n), hg(n);  // (the targets of queued copies: they outlive the drain below)
+  double c = 0;
+  auto run = [&]() -> int {
+    int e;
+    if ((e = rigx_linearize(ctx, st, st.cur, false, 0))) return e;
+    if ((e = rigx_columns(ctx, st, st.cur))) return e;
+    if ((e = rigx_schur(ctx, st, false, 0.0))) return e;
+    VSL_HIP(ctx, hipMemcpyAsync(hS.data(), st.S, 8 * n * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hg.data(), st.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VSL_OK;
+  };
+  if ((rc = run())) return rig_drain(ctx, rc);
+  memcpy(S, hS.data(), 8 * n * n);
+  memcpy(g, hg.data(), 8 * n);
+  *cost = c;
+  *n_free_bodies = st.nfb;
+  *n_free_ext = st.ne;
+  return VSL_OK;
+}
+
+extern "C" int vsl_ba_rig_ext_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const uint8_t* ext_free,
+                                     const double* T_b_c, const vsl_ba_options* opt, double inv_radius, double* S, double* rhs,
+                                     double* scale, double* d, double* cost, int* chol_ok) {
+  if (!ctx) return VSL_ERR_INVALID;
+  if (!rig || !ext_free || !T_b_c) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_rig_ext_system: null pointer");
+  if (!ext_free[0] && !ext_free[1]) {  // the rig call itself
+    vsl_ba_rig held = *rig;
+    held.T_b_c = T_b_c;
+    return vsl_ba_rig_system(ctx, prob, &held, opt, inv_radius, S, rhs, scale, d, cost, chol_ok);
+  }
+  RigxState st;
+  int rc = rigx_validate(ctx, "vsl_ba_rig_ext_system", prob, rig, ext_free, T_b_c, opt, st);
+  if (rc) return rc;
+  if (!(inv_radius >= 0.0) || !std::isfinite(inv_radius)) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_ba_rig_ext_system: inv_radius %g", inv_radius);
+  if (st.plan.n_fixed == 0)
+    return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_rig_ext_system: no fixed body: the gauge is free and the reduced system singular");
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = rigx_setup(ctx, prob, rig, opt, st))) return rc;
+  const size_t n = st.D.n;
+  std::vector<double> hS(n * n), hv(3 * n);  // (the targets of queued copies: they outlive the drain below)
+  double c = 0;
+  int flags[2] = {0, 0};
+  auto run = [&]() -> int {
+    int e;
+    if ((e = rigx_first_linearization(ctx, st))) return e;
+    if ((e = rigx_schur(ctx, st, true, inv_radius))) return e;
+    // (the large-system factorisation works in place: S and rhs are read before it runs)
+    VSL_HIP(ctx, hipMemcpyAsync(hS.data(), st.S, 8 * n * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data(), st.rhs, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + n, st.scale_c, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(&c, st.scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((e = rigx_solve(ctx, st))) return e;
+    VSL_HIP(ctx, hipMemcpyAsync(hv.data() + 2 * n, st.dc, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(flags, st.flag, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VSL_OK;
+  };
+  if ((rc = run())) return rig_drain(ctx, rc);
+  if (S) memcpy(S, hS.data(), 8 * n * n);
+  if (rhs) memcpy(rhs, hv.data(), 8 * n);
+  if (scale) memcpy(scale, hv.data() + n, 8 * n);
+  if (d) memcpy(d, hv.data() + 2 * n, 8 * n);
+  if (cost) *cost = c;
+  if (chol_ok) *chol_ok = flags[1] != 0;
+  if (!flags[1] && !chol_ok) return vsl_fail(ctx, VSL_ERR_NUMERIC, "vsl_ba_rig_ext_system: the reduced system is not positive definite");
+  return VSL_OK;
+}
+
+extern "C" int vsl_bundle_adjust_rig_ext(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const uint8_t* ext_free,
+                                         double* T_b_c_io, const vsl_ba_options* opt, vsl_ba_summary* summary) {
+  const double t_start = now_ms();
+  if (!ctx) return VSL_ERR_INVALID;
+  if (!rig || !ext_free || !T_b_c_io) return vsl_fail(ctx, VSL_ERR_INVALID, "vsl_bundle_adjust_rig_ext: null pointer");
+  if (!ext_free[0] && !ext_free[1]) {  // the rig call itself; the extrinsics come back normalised and otherwise untouched
+    vsl_ba_rig held = *rig;
+    held.T_b_c = T_b_c_io;
+    const int rc = vsl_bundle_adjust_rig(ctx, prob, &held, opt, summary);
+    if (rc) return rc;
+    double nrm[14];
+    rigx_normalised(T_b_c_io, nrm);
+    memcpy(T_b_c_io, nrm, sizeof(nrm));
+    return VSL_OK;
+  }
+  RigxState st;  // holds the loan of the context's arena
+  int rc = rigx_validate(ctx, "vsl_bundle_adjust_rig_ext", prob, rig, ext_free, T_b_c_io, opt, st);
+  if (rc) return rc;
+  VSL_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = rigx_setup(ctx, prob, rig, opt, st))) return rc;
+  double ext[14];  // (the target of a queued copy: it outlives the drain below)
+  auto run = [&]() -> int {
+    int e;
+    const BaDims& D = st.D;
+    vsl_ba_summary sum;
+    memset(&sum, 0, sizeof(sum));
+    const BaSolveTimes times(ctx, t_start);
+    if ((e = rigx_first_linearization(ctx, st))) return e;
+    double sc[16];  // [0] cost, [1] max |gradient| at the start
+    int unused_flags[2];
+    if ((e = ba_fetch_step(ctx, st.scalars, sc, unused_flags))) return e;
+    sum.initial_cost = sc[0];
+    // the loop of vsl_bundle_adjust_rig on the chain above
+    auto enqueue = [&](double radius) -> int {
+      int q;
+      if ((q = rigx_schur(ctx, st, true, 1.0 / radius))) return q;
+      if ((q = rigx_solve(ctx, st))) return q;
+      if ((q = rigx_step(ctx, st))) return q;
+      if ((q = rigx_linearize(ctx, st, st.cand, true, 5))) return q;
+      if ((q = rigx_columns(ctx, st, st.cand))) return q;
+      return rigx_diag_gmax(ctx, st, st.cand, 6);
+    };
+    auto fetch = [&](double* s16, int* flags) -> int { return ba_fetch_step(ctx, st.scalars, s16, flags); };
+    auto settle = [&](bool accepted) {
+      if (accepted) std::swap(st.cur, st.cand);
+    };
+    LmLoopResult lm;
+    if ((e = lm_speculative_loop(opt->max_num_iterations, opt->verbosity, sc[0], sc[1], enqueue, fetch, settle, &lm))) return e;
+    sum.iterations = lm.iterations;
+    sum.successful_steps = lm.successful_steps;
+    sum.termination = lm.termination;
+    sum.final_cost = lm.final_cost;
+    VSL_HIP(ctx, hipMemcpyAsync(rig->body_poses, st.cur.blocks, sizeof(double) * 7 * (size_t)st.B, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(ext, st.cur.blocks + 7 * (size_t)st.B, sizeof(ext), hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(prob->poses, st.cur.cams, sizeof(double) * 7 * (size_t)D.C, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipMemcpyAsync(prob->points, st.cur.points, sizeof(double) * 3 * (size_t)D.L, hipMemcpyDeviceToHost, ctx->stream));
+    VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(T_b_c_io, ext, sizeof(ext));
+    char label[80];
+    snprintf(label, sizeof(label), "vsl rig BA (extrinsics): %d free bodies, %d free blocks,", st.nfb, st.ne);
+    ba_finish_summary(ctx, times, opt->verbosity, label, sum, summary);
+    return VSL_OK;
+  };
+  rc = run();
+  return rc ? rig_drain(ctx, rc) : VSL_OK;
 }

@@ -18,6 +18,9 @@
 // ba_reduced_layout (both of ba_host_plan.h, unchanged: the camera -> body slot table stands where the free solver has
 // its camera -> free-camera table), the free-body slots in band order where the layout renumbers, and the list of
 // co-visible slot pairs with their segments.
+//
+// The EXTRINSICS as unknowns (vsl_bundle_adjust_rig_ext) add rig_ext_plan_build at the end of this file: the
+// slots of the free extrinsic blocks behind the free bodies and the group / observation lists of every slot.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -37,7 +40,9 @@ enum RigPlanStatus {
   RIG_PLAN_BODY_NO_CAMERA,  // a body that carries no camera
   RIG_PLAN_SHARED_INTR,     // two cameras of one body with the same intrinsics block
   RIG_PLAN_NO_FREE_BODY,    // every body is fixed
-  RIG_PLAN_EXTRINSIC        // an extrinsic that is not finite or has a zero quaternion
+  RIG_PLAN_EXTRINSIC,       // an extrinsic that is not finite or has a zero quaternion
+  RIG_PLAN_EXT_NO_CAMERA,   // (extrinsics as unknowns) a free extrinsic block that no camera carries
+  RIG_PLAN_NOTHING_FREE     // (extrinsics as unknowns) no free body and no free extrinsic block
 };
 
 inline const char* rig_plan_message(int status) {
@@ -50,6 +55,8 @@ inline const char* rig_plan_message(int status) {
     case RIG_PLAN_BODY_NO_CAMERA: return "a body carries no camera";
     case RIG_PLAN_SHARED_INTR: return "two cameras of one body share an intrinsics block";
     case RIG_PLAN_NO_FREE_BODY: return "no free body";
+    case RIG_PLAN_EXT_NO_CAMERA: return "a free extrinsic block that no camera carries";
+    case RIG_PLAN_NOTHING_FREE: return "no free body and no free extrinsic block";
     default: return "extrinsic not finite or its quaternion zero";
   }
 }
@@ -84,7 +91,9 @@ struct RigPlan {
 
 // 0 and the plan, or the first rule broken (nothing of `out` is then meaningful except first_bad).  slot_bodies (the map
 // route): the free bodies in the order of their slots, a permutation of the free body ids; null: ascending body id.
-inline int rig_plan_build(const RigPlanIn& in, RigPlan& out, const std::vector<int>* slot_bodies = nullptr) {
+// allow_no_free_body (rig_ext_plan_build): every body fixed is a plan with empty group and body lists, not an error.
+inline int rig_plan_build(const RigPlanIn& in, RigPlan& out, const std::vector<int>* slot_bodies = nullptr,
+                          bool allow_no_free_body = false) {
   out = RigPlan();
   if (in.n_cams <= 0 || in.n_lms <= 0 || in.n_obs <= 0 || in.n_bodies <= 0) return RIG_PLAN_EMPTY;
   if (!in.cam_intr || !in.obs_cam || !in.obs_lm || !in.body_fixed || !in.cam_body || !in.T_b_c) return RIG_PLAN_NULL;
@@ -106,7 +115,7 @@ inline int rig_plan_build(const RigPlanIn& in, RigPlan& out, const std::vector<i
     out.body_slot[b] = out.n_free++;
     out.free_bodies.push_back(b);
   }
-  if (out.n_free == 0) return RIG_PLAN_NO_FREE_BODY;
+  if (out.n_free == 0 && !allow_no_free_body) return RIG_PLAN_NO_FREE_BODY;
   if (slot_bodies) {
     out.free_bodies = *slot_bodies;
     for (int k = 0; k < out.n_free; k++) out.body_slot[out.free_bodies[k]] = k;
@@ -353,4 +362,142 @@ inline void rig_map_expand(const RigMapPlan& mp, int n_free, const double* store
 inline void rig_map_unpermute(const RigMapPlan& mp, int n_free, const double* in_slots, double* out) {
   for (int a = 0; a < n_free; a++)
     for (int x = 0; x < 6; x++) out[6 * a + x] = in_slots[6 * mp.natural_slot[a] + x];
+}
+
+// ------------------------------------------------------------------------------------------------ EXTRINSICS
+// The extrinsics as unknowns (vsl_bundle_adjust_rig_ext, ba_rig.hip "EXTRINSICS").  A free extrinsic
+// block k is one more 6-dof POSE SLOT behind the free bodies: slot n_free + (number of free blocks below k).  An
+// observation in a camera of block k touches the slot of its body (when that body is free) AND the slot of block k
+// (when that block is free, whether the body is free or not).  The plan is rig_plan_build's (observation order, body
+// slots, body groups, every body fixed allowed) plus
+//   cam_eslot   camera -> slot of its extrinsic block, -1 when that block is held
+//   pose_free   the pose-block array of the solver is [bodies | block 0 | block 1]: block -> slot or -1
+//   groups      one per (landmark, slot) with an observation: the landmark's body groups in rig_plan_build's order
+//               (ascending slot), then its extrinsic groups in ascending block.  The observations of an extrinsic group
+//               are NOT adjacent in the sorted order (they are spread over the bodies), so EVERY group names its
+//               observations through an index list, grp_obs[grp_first[g] .. grp_first[g + 1]), ascending
+//   slot lists  sg_*: a slot's groups in ascending landmark (the Schur gather's bisection and the back-substitution
+//               serve the border through the same lists); so_*: a slot's sorted observations, ascending
+struct RigExtPlan {
+  int n_ext = 0, n_slots = 0;
+  int ext_slot[2] = {-1, -1};
+  std::vector<int> cam_eslot;                      // [cams]
+  std::vector<int> pose_free;                      // [bodies + 2]
+  std::vector<int> lm_grp;                         // [lms + 1]
+  std::vector<int> grp_lm, grp_slot, grp_first;    // [groups], [groups], [groups + 1]
+  std::vector<int> grp_obs;                        // [sum of group sizes]
+  std::vector<int> sg_start, sg_grp, sg_lm;        // [n_slots + 1], [groups], [groups]
+  std::vector<int> so_start, so_obs;               // [n_slots + 1], [sum of slot list sizes]
+  int n_groups() const { return (int)grp_lm.size(); }
+};
+
+// 0 and the two plans, or the first rule broken: whatever rig_plan_build refuses (except "no free body" while a block
+// is free), a null ext_free, a free block that no camera carries, nothing free at all.  in.T_b_c is the explicit
+// extrinsic argument of the call.
+inline int rig_ext_plan_build(const RigPlanIn& in, const uint8_t* ext_free, RigPlan& base, RigExtPlan& x) {
+  x = RigExtPlan();
+  if (!ext_free) { base = RigPlan(); return RIG_PLAN_NULL; }
+  const int st = rig_plan_build(in, base, nullptr, true);
+  if (st != RIG_PLAN_OK) return st;
+  const int C = in.n_cams, L = in.n_lms, B = in.n_bodies, nfb = base.n_free;
+  for (int k = 0; k < 2; k++) {
+    if (!ext_free[k]) continue;
+    bool carried = false;
+    for (int c = 0; c < C && !carried; c++) carried = in.cam_intr[c] == k;
+    if (!carried) { base.first_bad = k; return RIG_PLAN_EXT_NO_CAMERA; }
+    x.ext_slot[k] = nfb + x.n_ext++;
+  }
+  x.n_slots = nfb + x.n_ext;
+  if (x.n_slots == 0) return RIG_PLAN_NOTHING_FREE;
+  x.cam_eslot.resize(C);
+  for (int c = 0; c < C; c++) x.cam_eslot[c] = x.ext_slot[in.cam_intr[c]];
+  x.pose_free.assign(base.body_slot.begin(), base.body_slot.end());
+  x.pose_free.push_back(x.ext_slot[0]);
+  x.pose_free.push_back(x.ext_slot[1]);
+  (void)B;
+
+  x.lm_grp.assign(L + 1, 0);
+  x.sg_start.assign(x.n_slots + 1, 0);
+  x.so_start.assign(x.n_slots + 1, 0);
+  x.grp_first.assign(1, 0);
+  for (int l = 0; l < L; l++) {
+    for (int g = base.lm_grp[l]; g < base.lm_grp[l + 1]; g++) {
+      x.grp_lm.push_back(l);
+      x.grp_slot.push_back(base.grp_slot[g]);
+      for (int q = base.grp_begin[g]; q < base.grp_end[g]; q++) x.grp_obs.push_back(q);
+      x.grp_first.push_back((int)x.grp_obs.size());
+    }
+    for (int k = 0; k < 2; k++) {
+      if (x.ext_slot[k] < 0) continue;
+      const size_t before = x.grp_obs.size();
+      for (int q = base.lm_start[l]; q < base.lm_start[l + 1]; q++)
+        if (in.cam_intr[base.obs_cam[q]] == k) x.grp_obs.push_back(q);
+      if (x.grp_obs.size() == before) continue;
+      x.grp_lm.push_back(l);
+      x.grp_slot.push_back(x.ext_slot[k]);
+      x.grp_first.push_back((int)x.grp_obs.size());
+    }
+    x.lm_grp[l + 1] = x.n_groups();
+  }
+  const int G = x.n_groups();
+  for (int g = 0; g < G; g++) {
+    x.sg_start[x.grp_slot[g] + 1]++;
+    x.so_start[x.grp_slot[g] + 1] += x.grp_first[g + 1] - x.grp_first[g];
+  }
+  for (int s = 0; s < x.n_slots; s++) {
+    x.sg_start[s + 1] += x.sg_start[s];
+    x.so_start[s + 1] += x.so_start[s];
+  }
+  x.sg_grp.resize(G);
+  x.sg_lm.resize(G);
+  x.so_obs.resize(x.so_start[x.n_slots]);
+  std::vector<int> gpos(x.sg_start.begin(), x.sg_start.end() - 1), opos(x.so_start.begin(), x.so_start.end() - 1);
+  for (int g = 0; g < G; g++) {
+    const int s = x.grp_slot[g];
+    x.sg_grp[gpos[s]] = g;
+    x.sg_lm[gpos[s]++] = x.grp_lm[g];
+    for (int q = x.grp_first[g]; q < x.grp_first[g + 1]; q++) x.so_obs[opos[s]++] = x.grp_obs[q];
+  }
+  return RIG_PLAN_OK;
+}
+
+// the properties the EXTRINSICS kernels rely on -- every index they form stays inside its array: true when they hold
+inline bool rig_ext_plan_check(const RigPlanIn& in, const RigPlan& base, const RigExtPlan& x) {
+  const int O = in.n_obs, L = in.n_lms, G = x.n_groups(), ns = x.n_slots;
+  if (ns != base.n_free + x.n_ext || ns <= 0) return false;
+  if ((int)x.cam_eslot.size() != in.n_cams || (int)x.pose_free.size() != in.n_bodies + 2) return false;
+  for (int p : x.pose_free)
+    if (p < -1 || p >= ns) return false;
+  if ((int)x.lm_grp.size() != L + 1 || x.lm_grp[0] != 0 || x.lm_grp[L] != G) return false;
+  if ((int)x.grp_first.size() != G + 1 || x.grp_first[0] != 0 || x.grp_first[G] != (int)x.grp_obs.size()) return false;
+  for (int g = 0; g < G; g++) {
+    const int l = x.grp_lm[g], s = x.grp_slot[g];
+    if (l < 0 || l >= L || s < 0 || s >= ns || g < x.lm_grp[l] || g >= x.lm_grp[l + 1]) return false;
+    if (x.grp_first[g] >= x.grp_first[g + 1]) return false;
+    if (g > 0 && (x.grp_lm[g - 1] > l || (x.grp_lm[g - 1] == l && x.grp_slot[g - 1] >= s))) return false;
+    for (int k = x.grp_first[g]; k < x.grp_first[g + 1]; k++) {
+      const int q = x.grp_obs[k];
+      if (q < base.lm_start[l] || q >= base.lm_start[l + 1]) return false;
+      if (k > x.grp_first[g] && x.grp_obs[k - 1] >= q) return false;
+      const int cam = base.obs_cam[q];
+      if ((s < base.n_free ? base.cam_slot[cam] : x.cam_eslot[cam]) != s) return false;
+    }
+  }
+  if ((int)x.sg_start.size() != ns + 1 || (int)x.so_start.size() != ns + 1 || x.sg_start[0] != 0 || x.so_start[0] != 0) return false;
+  if (x.sg_start[ns] != G || x.so_start[ns] != (int)x.so_obs.size() || x.so_obs.size() != x.grp_obs.size()) return false;
+  for (int s = 0; s < ns; s++) {
+    if (x.sg_start[s] > x.sg_start[s + 1] || x.so_start[s] > x.so_start[s + 1]) return false;
+    for (int k = x.sg_start[s]; k < x.sg_start[s + 1]; k++) {
+      if (x.sg_grp[k] < 0 || x.sg_grp[k] >= G || x.grp_slot[x.sg_grp[k]] != s || x.sg_lm[k] != x.grp_lm[x.sg_grp[k]]) return false;
+      if (k > x.sg_start[s] && x.sg_lm[k - 1] >= x.sg_lm[k]) return false;  // strictly ascending: bisection finds at most one
+    }
+    for (int k = x.so_start[s]; k < x.so_start[s + 1]; k++) {
+      const int q = x.so_obs[k];
+      if (q < 0 || q >= O) return false;
+      if (k > x.so_start[s] && x.so_obs[k - 1] >= q) return false;
+      const int cam = base.obs_cam[q];
+      if ((s < base.n_free ? base.cam_slot[cam] : x.cam_eslot[cam]) != s) return false;
+    }
+  }
+  return true;
 }
