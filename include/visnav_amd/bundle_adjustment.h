@@ -33,6 +33,7 @@
 // bundle_adjustment_rig_covariance, rig_relative_pose_covariance, rig_map_edge_information (below): likewise
 #pragma weak vsl_ba_rig_covariance
 #pragma weak vsl_ba_rig_relative_pose_covariance
+#pragma weak vsl_ba_rig_ext_covariance
 
 namespace visnav {
 
@@ -662,6 +663,91 @@ inline int bundle_adjustment_rig_covariance(const Corners& feature_corners, cons
       for (int j = 0; j < 3; j++) m(i, j) = cl[9 * q + 3 * i + j];
   }
   return n_degenerate;
+}
+
+// Covariances of the posterior bundle_adjustment_rig_extrinsics adjusts (vsl_ba_rig_ext_covariance): how well the window
+// determines the extrinsic of free_extrinsic_camera (0 or 1), and the frame / camera / landmark blocks with that
+// extrinsic NOT taken as known.  Flattening and rules are bundle_adjustment_rig_extrinsics' (amd::flatten_rig); nothing is
+// optimised, nothing is written to the map.  query_frames: free frames; query_cameras: any camera but one of a fixed frame
+// whose extrinsic is held; query_landmarks: ids of `landmarks` (unknown id: std::out_of_range; a rule broken:
+// std::invalid_argument).  extrinsic_cov: 6 x 6 over the tangent (upsilon, omega) of T_b_c * exp(eps), T_b_c =
+// T_i_c[0]^-1 T_i_c[camera] at the calibration handed in.  A window that does not determine the extrinsic -- one fixed
+// frame: the baseline's length is a gauge direction; no fixed frame -- is EXPECTED input: observable = false, `reason`
+// says why, every map is empty, nothing is thrown.
+struct RigExtrinsicsCovariance {
+  bool observable = false;
+  std::string reason;
+  PoseCovariance extrinsic_cov;
+  std::map<FrameId, PoseCovariance> body_cov;
+  std::map<FrameId, PoseCovariance> body_extrinsic_cov;  // [S^-1] at (frame, extrinsic): rows the frame's tangent
+  std::map<FrameCamId, PoseCovariance> cam_cov;
+  std::unordered_map<TrackId, Eigen::Matrix3d> landmark_cov;  // NaN for a landmark whose own block is singular
+  int n_degenerate = 0;
+};
+inline RigExtrinsicsCovariance bundle_adjustment_rig_extrinsics_covariance(
+    const Corners& feature_corners, const BundleAdjustmentOptions& options, const std::set<FrameCamId>& fixed_cameras,
+    Calibration& calib_cam, Cameras& cameras, Landmarks& landmarks, int free_extrinsic_camera,
+    const std::vector<FrameId>& query_frames, const std::vector<FrameCamId>& query_cameras,
+    const std::vector<TrackId>& query_landmarks) {
+  const char* what = "bundle_adjustment_rig_extrinsics_covariance";
+  RigExtrinsicsCovariance out;
+  if (&vsl_ba_rig_ext_covariance == nullptr) throw std::runtime_error(std::string(what) + ": this library has no vsl_ba_rig_ext_covariance");
+  if (options.optimize_intrinsics) throw std::invalid_argument(std::string(what) + ": optimize_intrinsics is not offered in rig form");
+  if (free_extrinsic_camera != 0 && free_extrinsic_camera != 1) throw std::invalid_argument(std::string(what) + ": free_extrinsic_camera is 0 or 1");
+  amd::RigFlat r;
+  if (!amd::flatten_rig(what, feature_corners, fixed_cameras, calib_cam, cameras, landmarks, r))
+    throw std::out_of_range(std::string(what) + ": the map has no observation");
+  const amd::BaFlat& f = r.f;
+  std::vector<int32_t> bodies, cams, lms;
+  for (const FrameId id : query_frames) {
+    bodies.push_back(r.body_of(id));
+    if (bodies.back() < 0) throw std::out_of_range(std::string(what) + ": unknown frame");
+    if (r.body_fixed[bodies.back()]) throw std::invalid_argument(std::string(what) + ": a queried frame is fixed");
+  }
+  for (const FrameCamId& id : query_cameras) {
+    const auto it = std::lower_bound(f.cam_id.begin(), f.cam_id.end(), id);
+    if (it == f.cam_id.end() || !(*it == id)) throw std::out_of_range(std::string(what) + ": unknown camera");
+    cams.push_back((int32_t)(it - f.cam_id.begin()));
+    if (r.body_fixed[r.cam_body[cams.back()]] && (int)id.cam_id != free_extrinsic_camera)
+      throw std::invalid_argument(std::string(what) + ": a queried camera's frame is fixed and its extrinsic is held");
+  }
+  if (!query_landmarks.empty()) {
+    std::unordered_map<TrackId, int32_t> index;
+    for (size_t l = 0; l < f.lm_id.size(); l++) index.emplace(f.lm_id[l], (int32_t)l);
+    for (const TrackId id : query_landmarks) lms.push_back(index.at(id));
+  }
+  vsl_ba_options opt;
+  opt.use_huber = options.use_huber ? 1 : 0;
+  opt.huber_parameter = options.huber_parameter;
+  opt.max_num_iterations = 0;
+  opt.verbosity = 0;
+  const uint8_t ext_free[2] = {(uint8_t)(free_extrinsic_camera == 0), (uint8_t)(free_extrinsic_camera == 1)};
+  std::vector<double> cb(36 * bodies.size()), cc(36 * cams.size()), cl(9 * lms.size()), ce(36), cx(36 * bodies.size());
+  const int rc = vsl_ba_rig_ext_covariance(amd::ctx(), &f.prob, &r.rig, ext_free, r.T_b_c, &opt, bodies.data(), (int)bodies.size(),
+                                           cb.data(), cams.data(), (int)cams.size(), cc.data(), lms.data(), (int)lms.size(), cl.data(),
+                                           ce.data(), cx.data(), &out.n_degenerate);
+  if (rc == VSL_ERR_NUMERIC) {  // a gauge window: an answer, not a failure
+    out.reason = vsl_last_error(amd::ctx());
+    return out;
+  }
+  amd::check(rc, what);
+  out.observable = true;
+  auto block = [](const std::vector<double>& v, size_t q, PoseCovariance& m) {
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) m(i, j) = v[36 * q + 6 * i + j];
+  };
+  block(ce, 0, out.extrinsic_cov);
+  for (size_t q = 0; q < bodies.size(); q++) {
+    block(cb, q, out.body_cov[query_frames[q]]);
+    block(cx, q, out.body_extrinsic_cov[query_frames[q]]);
+  }
+  for (size_t q = 0; q < cams.size(); q++) block(cc, q, out.cam_cov[query_cameras[q]]);
+  for (size_t q = 0; q < lms.size(); q++) {
+    Eigen::Matrix3d& m = out.landmark_cov[query_landmarks[q]];
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) m(i, j) = cl[9 * q + 3 * i + j];
+  }
+  return out;
 }
 
 // relative_pose_covariance for pairs of FRAMES (bodies) of the rig posterior: out[q] as there, measurement =

@@ -789,8 +789,9 @@ int vsl_ba_rig_map_system(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba
  * commute with their relative pose (the screw about its axis, 2 dof) free, and three fixed bodies in general position
  * are needed.  The hooks then report *chol_ok = 0 when the factorisation notices; the solve runs the LM policy on the
  * damped system as for any gauge-free input, and no non-finite value reaches a pose, an extrinsic or a point.
- * NOT COVERED: the map route (vsl_global_bundle_adjust_rig), sessions and multi-GPU, covariances of the extrinsic, a
- * prior on the extrinsic, the intrinsics variant, a matrix-free route. */
+ * The covariances of this posterior, the extrinsic's among them: vsl_ba_rig_ext_covariance below.
+ * NOT COVERED: the map route (vsl_global_bundle_adjust_rig), sessions and multi-GPU, a prior on the extrinsic, the
+ * intrinsics variant, a matrix-free route. */
 /* The solve: updates rig->body_poses, T_b_c_io [2][7], prob->points and prob->poses (the cameras on the refined rig). */
 int vsl_bundle_adjust_rig_ext(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const uint8_t ext_free[2],
                               double* T_b_c_io, const vsl_ba_options* opt, vsl_ba_summary* summary);
@@ -842,6 +843,52 @@ int vsl_ba_rig_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba
 int vsl_ba_rig_relative_pose_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig,
                                         const vsl_ba_options* opt, const int32_t* body_a, const int32_t* body_b, int n_pairs,
                                         double* joint, double* meas, double* cov, double* info, int* n_singular);
+
+/* ---- covariances with the extrinsics as unknowns (visual-slam_amd/csrc/ba_rig.hip "EXTRINSICS: COVARIANCES",
+ * csrc/ba_rig_cov_plan.h rxcp_plan) ----
+ * The posterior of the problem vsl_bundle_adjust_rig_ext adjusts: how well the window determines the refined extrinsic,
+ * and the body / camera / landmark uncertainty with the extrinsic NOT taken as known (vsl_ba_rig_covariance after an
+ * extrinsic refinement conditions on it and under-reports all three).  Inputs exactly those of vsl_ba_rig_ext_linearize:
+ * prob, rig, ext_free [2], T_b_c [2][7], opt; rig->T_b_c is ignored; nothing is optimised.
+ *   Unknowns: free bodies in ascending id, then free blocks in ascending k, then landmarks; the tangents above.
+ *   H = J^T J with the Huber corrector, no Jacobi scaling, no damping; Sigma = H^-1 in units of 1 px^2 of observation
+ *   noise.  S: the reduced system of vsl_ba_rig_ext_linearize over n_slots = free bodies + free blocks; P_l = sum E^T E of
+ *   landmark l; W_s of group (landmark l, slot s) = sum F_b^T E (body slot) or sum F_x^T E (extrinsic slot) over the
+ *   group's observations.
+ *   body block        the 6 x 6 diagonal block of S^-1 at the body's slot
+ *   extrinsic block   cov_ext [(6 m)^2], m = free blocks: the joint block of S^-1 over the extrinsic slots, 6 x 6 or
+ *                     12 x 12 row-major, ascending k -- "is the refinement observable"
+ *   cross blocks      cov_body_ext [n_body_q][m][36] (nullable): [S^-1] at (body slot, extrinsic slot)
+ *   camera block      the camera's own right perturbation is xi_c = Ad(T_b_c^-1) delta_b + eps_k to first order:
+ *                     Sigma_cc = A Sigma_joint A^T, A = [Ad(T_b_c^-1) | I_6], on the joint (body, block) 12 x 12 block of
+ *                     S^-1.  Free body, held block: vsl_ba_rig_covariance's formula.  Fixed body, free block: Sigma_ee of
+ *                     that block.  Both held: VSL_ERR_INVALID.
+ *   landmark block    P_l^-1 + P_l^-1 (sum_s sum_s' W_s^T [S^-1]_ss' W_s') P_l^-1 over ALL groups of the landmark, the
+ *                     extrinsic groups included; P_l^-1 alone for a landmark with no group.  The 2^-44 pivot rule, nine
+ *                     NaN and *n_degenerate as for vsl_ba_rig_covariance.  At most 256 groups per queried landmark.
+ * Arguments as vsl_ba_rig_covariance plus ext_free, T_b_c, cov_ext, cov_body_ext (both nullable): duplicates are
+ * allowed, counts may be 0; with all counts 0 and null extrinsic outputs the call validates, launches nothing and
+ * returns VSL_OK.
+ * VSL_ERR_INVALID, nothing written: everything vsl_ba_rig_ext_linearize refuses; a fixed body in a query; a camera whose
+ * body is fixed and whose block is held; an id out of range; a queried landmark with more than 256 groups.
+ * VSL_ERR_NUMERIC, nothing written: no fixed body (before any device work); S failing the pivot rule L_ii^2 <= 2^-36 S_ii
+ * of the covariance chain, tested by the factorisation and again in the form S_uu [S^-1]_uu >= 2^36 on every solved
+ * column (the ratio unknown u would have if eliminated last: independent of the elimination order; once an extrinsic
+ * slot is needed the columns of every slot are solved).  That rule is the gauge detector the solve lacks: with one fixed body (the baseline length is
+ * a gauge direction, cond(S) ~ 1e18) the call reports VSL_ERR_NUMERIC where the solve returns finite numbers; the
+ * smallest pivot ratio of the regular cases is six orders above the threshold.
+ * On every error return the stream is drained before the arena loan ends.
+ * Bit-level: every block is exactly symmetric (cov_ext as a whole); a subset query returns the bits of a full query; two
+ * calls return the same bits; the diagonal 6 x 6 blocks of a 12 x 12 cov_ext are what a camera query of a fixed body
+ * returns for each block; with ext_free = {0, 0} the call hands over to vsl_ba_rig_covariance at the T_b_c argument (its
+ * bits; cov_ext and cov_body_ext have no entry and are not written).  No floating-point atomics, every sum in a fixed
+ * order.
+ * NOT COVERED: relative-pose covariances of body pairs with a free extrinsic, the map route, sessions, a prior on the
+ * extrinsic. */
+int vsl_ba_rig_ext_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const uint8_t ext_free[2],
+                              const double* T_b_c, const vsl_ba_options* opt, const int32_t* bodies, int n_body_q,
+                              double* cov_body, const int32_t* cams, int n_cam_q, double* cov_cam, const int32_t* lms,
+                              int n_lm_q, double* cov_point, double* cov_ext, double* cov_body_ext, int* n_degenerate);
 
 /* The solver behind the reduced camera system, on its own (the place Ceres' SPARSE_SCHUR hands S to a Cholesky,
  * include/visnav/map_utils.h:406-411, loop_closure_utils.h:735): solves S x = b for a symmetric positive definite S

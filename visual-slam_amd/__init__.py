@@ -793,6 +793,31 @@ class Context:
                                               cl.ctypes.data_as(f64p), C.byref(nd)))
         return cb, cc, cl, nd.value
 
+    def ba_rig_ext_covariance(self, arr, rig, T_b_c, ext_free=(0, 1), bodies=None, cams=None, lms=None, use_huber=True, huber=1.0):
+        """Marginal covariances of the problem bundle_adjust_rig_ext adjusts, at rig's bodies, T_b_c and arr's points
+        (vsl_ba_rig_ext_covariance; nothing is optimised, rig.T_b_c is ignored).  bodies: body ids (None: all free bodies),
+        cams: camera ids (None: none), lms: landmark ids (None: none).  Returns a dict: cov_body [n, 6, 6], cov_ext
+        [6 m, 6 m] over the m free blocks in ascending k, cov_body_ext [n, m, 6, 6], cov_cam [c, 6, 6], cov_point [k, 3, 3],
+        n_degenerate.  VslError -7 (VSL_ERR_NUMERIC) when the window does not determine the extrinsic (a free gauge)."""
+        st, rg = self._ba_rig_structs(arr, rig)
+        T, ef = self._ext_args(T_b_c, ext_free)
+        o = self._ba_opts(use_huber, huber, 0, 0)
+        m = int(ef.sum())
+        bodies = np.flatnonzero(rig.body_fixed == 0) if bodies is None else bodies
+        bodies = np.ascontiguousarray(bodies, np.int32).reshape(-1)
+        cams = np.ascontiguousarray([] if cams is None else cams, np.int32).reshape(-1)
+        lms = np.ascontiguousarray([] if lms is None else lms, np.int32).reshape(-1)
+        cb, cc, cl = np.zeros((len(bodies), 6, 6)), np.zeros((len(cams), 6, 6)), np.zeros((len(lms), 3, 3))
+        ce, cx = np.zeros((6 * m, 6 * m)), np.zeros((len(bodies), m, 6, 6))
+        nd = C.c_int(0)
+        self._ck(self.L.vsl_ba_rig_ext_covariance(self.h, C.byref(st), C.byref(rg), ef.ctypes.data_as(u8p), T.ctypes.data_as(f64p),
+                                                  C.byref(o), bodies.ctypes.data_as(i32p), len(bodies), cb.ctypes.data_as(f64p),
+                                                  cams.ctypes.data_as(i32p), len(cams), cc.ctypes.data_as(f64p),
+                                                  lms.ctypes.data_as(i32p), len(lms), cl.ctypes.data_as(f64p),
+                                                  ce.ctypes.data_as(f64p) if m else None, cx.ctypes.data_as(f64p) if m else None,
+                                                  C.byref(nd)))
+        return dict(cov_body=cb, cov_ext=ce, cov_body_ext=cx, cov_cam=cc, cov_point=cl, n_degenerate=nd.value)
+
     def ba_rig_relative_pose_covariance(self, arr, rig, pairs, use_huber=True, huber=1.0):
         """ba_relative_pose_covariance for pairs of BODIES of the rig problem (vsl_ba_rig_relative_pose_covariance).
         pairs: [n, 2] body ids (a, b); one of the two may be fixed.  Returns (joint [n, 12, 12], meas [n, 6], cov

@@ -5,7 +5,8 @@
 // system gathered over co-visible body pairs only (rig_schur_pairs_kernel) into dense / band / cyclic-band storage.
 // The covariances of the rig posterior (vsl_ba_rig_covariance, vsl_ba_rig_relative_pose_covariance) are
 // the section "COVARIANCES" of this file; the extrinsics as unknowns (vsl_bundle_adjust_rig_ext) the section
-// "EXTRINSICS" at its end.
+// "EXTRINSICS" behind them, and the covariances of THAT posterior (vsl_ba_rig_ext_covariance) the section
+// "EXTRINSICS: COVARIANCES" at its end.
 //
 // Residual, camera models, Huber corrector and cost are those of vsl_bundle_adjust (ba_device.h); what changes is the
 // pose block an observation differentiates against.  With T_c_b = T_b_c^-1 = (R, t),
@@ -1546,6 +1547,7 @@ struct RigxState {
   int *cam_intr = nullptr, *cam_body = nullptr, *cam_slot = nullptr, *cam_eslot = nullptr, *pose_free = nullptr;
   int *obs_cam = nullptr, *obs_lm = nullptr, *lm_start = nullptr, *lm_grp = nullptr, *grp_slot = nullptr, *grp_first = nullptr;
   int *grp_obs = nullptr, *sg_start = nullptr, *sg_grp = nullptr, *sg_lm = nullptr, *so_start = nullptr, *so_obs = nullptr;
+  char* extra = nullptr;  // the covariance call's share of the arena (behind everything else: no other offset moves)
 };
 
 int rigx_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const vsl_ba_rig* rig, const uint8_t* ext_free,
@@ -1570,7 +1572,8 @@ int rigx_validate(vsl_ctx* ctx, const char* who, const vsl_ba_problem* p, const 
 }
 
 // plans -> ONE arena (the context's), uploads; synchronises
-int rigx_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt, RigxState& st) {
+int rigx_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, const vsl_ba_options* opt, RigxState& st,
+               size_t extra_bytes = 0) {
   const RigPlan& hp = st.plan;
   const RigExtPlan& xp = st.xp;
   BaDims& D = st.D;
@@ -1612,6 +1615,7 @@ int rigx_setup(vsl_ctx* ctx, const vsl_ba_problem* p, const vsl_ba_rig* rig, con
   plan.add(st.grp_slot, G); plan.add(st.grp_first, G + 1); plan.add(st.grp_obs, xp.grp_obs.size());
   plan.add(st.sg_start, ns + 1); plan.add(st.sg_grp, G); plan.add(st.sg_lm, G);
   plan.add(st.so_start, ns + 1); plan.add(st.so_obs, xp.so_obs.size());
+  if (extra_bytes) plan.add(st.extra, extra_bytes);
   hipError_t e = st.arena.acquire(ctx, ArenaPolicy::BORROWED, plan);
   if (e != hipSuccess) return vsl_fail(ctx, e == hipErrorOutOfMemory ? VSL_ERR_NOMEM : VSL_ERR_HIP, "rig bundle adjustment (extrinsics): %zu bytes of device memory: %s", plan.total(), hipGetErrorString(e));
   st.flag = (int*)(st.scalars + 16);
@@ -1907,4 +1911,358 @@ extern "C" int vsl_bundle_adjust_rig_ext(vsl_ctx* ctx, const vsl_ba_problem* pro
   };
   rc = run();
   return rc ? rig_drain(ctx, rc) : VSL_OK;
+}
+
+// ================================================================================ EXTRINSICS: COVARIANCES
+// vsl_ba_rig_ext_covariance (include/vslam_hip.h "covariances with the extrinsics as unknowns"): the
+// posterior of the problem vsl_bundle_adjust_rig_ext adjusts, H = J^T J over [free bodies | free blocks | landmarks],
+// Sigma = H^-1, at the bodies / extrinsics / points handed in.  Nothing is optimised.  One arena loan, one
+// synchronisation:
+//   rigx_linearize -> rigx_columns -> rigx_schur     the solve's own kernels, unscaled and undamped: the S of
+//                                                    vsl_ba_rig_ext_linearize, bit for bit; F_b, F_x, E stay resident
+//   vsl_cov_inverse_dev                              the six unit columns of every slot of Q (rxcp_plan); its 2^-36 pivot
+//                                                    rule is the gauge detector the solve lacks
+//   rigx_cov_gauge_kernel                            the same rule on S_uu [S^-1]_uu of every solved column: independent of
+//                                                    the elimination order
+//   vsl_cov_pair_blocks_dev                          the (body slot, block slot) and (block 0, block 1) joint blocks
+//   rigx_cov_pose_kernel      one thread per pose item: body / extrinsic / cross blocks, the camera sandwich with
+//                             A = [Ad(T_b_c^-1) | I]
+//   rigx_cov_landmark_kernel  one wavefront per queried landmark over ALL its groups, extrinsic groups included
+// No floating-point atomics; every sum in a fixed order.  ext_free = {0, 0} never gets here: the call hands over to
+// vsl_ba_rig_covariance.
+namespace {
+
+// One thread per pose item (RigExtCovItem, ba_rig_cov_plan.h).  A diagonal block is read from the slot's own columns, the
+// two mirror entries averaged -- the rule of rig_cov_pose_kernel and of a joint block's diagonal (ba_pair_blocks_kernel):
+// the same bits.  RXC_CAM_FREE_HELD is rig_cov_pose_kernel's sequence.  RXC_CAM_FREE_FREE: with the joint block
+// [[Sbb, Sbe], [Seb, See]] of the pair, M = Ad Sbb Ad^T + Ad Sbe + (Ad Sbe)^T + See, summed in that order per entry,
+// then (M + M^T) / 2.
+__global__ __launch_bounds__(64) void rigx_cov_pose_kernel(int n, int n_items, const RigExtCovItem* __restrict__ items,
+                                                           const int* __restrict__ q_slot, const double* __restrict__ X,
+                                                           const double* __restrict__ joint, const double* __restrict__ tcb,
+                                                           const int* __restrict__ ok, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_items || !*ok) return;
+  const RigExtCovItem it = items[t];
+  double* o = out + 36 * (size_t)t;
+  if (it.kind == RXC_CROSS) {
+    const double* J = joint + 144 * (size_t)it.pair;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+      for (int b = 0; b < 6; b++) o[6 * a + b] = J[12 * a + 6 + b];
+    return;
+  }
+  const int q = it.q, f = q_slot[q];
+  double A[36];
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++)
+      A[6 * a + b] = 0.5 * (X[vsl_cov_x_at(n, 6 * f + a, 6 * q + b)] + X[vsl_cov_x_at(n, 6 * f + b, 6 * q + a)]);
+  if (it.kind == RXC_BODY || it.kind == RXC_CAM_FIXED_FREE || it.kind == RXC_EXT) {
+#pragma unroll
+    for (int e = 0; e < 36; e++) o[e] = A[e];
+    return;
+  }
+  const double* Rt = tcb + 12 * it.blk;
+  double B[36], M[36];
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    double v[6], w[6];
+#pragma unroll
+    for (int r = 0; r < 6; r++) v[r] = A[6 * r + c];
+    rig_adjoint_apply(Rt, v, w);
+#pragma unroll
+    for (int r = 0; r < 6; r++) B[6 * r + c] = w[r];
+  }
+#pragma unroll
+  for (int r = 0; r < 6; r++) {
+    double w[6];
+    rig_adjoint_apply(Rt, B + 6 * r, w);  // row r of B Ad^T = Ad (row r of B)^T
+#pragma unroll
+    for (int c = 0; c < 6; c++) M[6 * r + c] = w[c];
+  }
+  if (it.kind == RXC_CAM_FREE_FREE) {
+    const double* J = joint + 144 * (size_t)it.pair;
+    double Cx[36];  // Ad Sbe, column by column
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      double v[6], w[6];
+#pragma unroll
+      for (int r = 0; r < 6; r++) v[r] = J[12 * r + 6 + c];
+      rig_adjoint_apply(Rt, v, w);
+#pragma unroll
+      for (int r = 0; r < 6; r++) Cx[6 * r + c] = w[r];
+    }
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+      for (int b = 0; b < 6; b++) B[6 * a + b] = ((M[6 * a + b] + Cx[6 * a + b]) + Cx[6 * b + a]) + J[12 * (6 + a) + 6 + b];
+#pragma unroll
+    for (int e = 0; e < 36; e++) M[e] = B[e];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++) o[6 * a + b] = 0.5 * (M[6 * a + b] + M[6 * b + a]);
+}
+
+// The 2^-36 pivot rule made independent of the elimination order.  1 / (S_uu [S^-1]_uu) is the pivot ratio unknown u would
+// have if it were eliminated LAST; the factorisation tests each unknown at its own place in [bodies | blocks] only, and in
+// float64 the pivot of a gauge direction whose component in the last unknowns is small is rounding noise near the
+// threshold (7e-11 against 1.5e-11 on the one-fixed-body window, 3e-15 in long double).  One thread per
+// solved column: S_uu [S^-1]_uu >= 2^36, or an entry that is not positive and finite, clears *ok (every failing thread
+// stores the same 0).  Sdiag: diag S before the factorisation.
+__global__ void rigx_cov_gauge_kernel(int n, int n_cols, const int* __restrict__ q_slot, const double* __restrict__ Sdiag,
+                                      const double* __restrict__ X, int* __restrict__ ok) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_cols || !*ok) return;
+  const int u = 6 * q_slot[j / 6] + j % 6;
+  const double v = Sdiag[u] * X[vsl_cov_x_at(n, u, j)];
+  if (!(v > 0.0) || !(v < 68719476736.0)) *ok = 0;  // 2^36
+}
+
+// rig_cov_landmark_kernel on the groups of RigExtPlan: one wavefront per unique queried landmark u (l = u_lm[u]), its
+// groups lm_grp[l] .. lm_grp[l + 1] in ascending slot (bodies, then blocks), each naming its observations through
+// grp_obs[grp_first[g] .. grp_first[g + 1]) (ascending); a group of a slot >= nfb is an extrinsic group and reads F_x.
+// P_l and W in the sum orders of rigx_lm_groups_kernel.  Dynamic LDS only: M [16 doubles] | W [18 K] | T [9 K], K = groups
+// of the landmark (at most RCP_GMAX).
+__global__ __launch_bounds__(64) void rigx_cov_landmark_kernel(int n, int nfb, const int* __restrict__ u_lm,
+                                                               const int* __restrict__ lm_start, const int* __restrict__ lm_grp,
+                                                               const int* __restrict__ grp_slot, const int* __restrict__ grp_first,
+                                                               const int* __restrict__ grp_obs, const double* __restrict__ F,
+                                                               const double* __restrict__ Fx, const double* __restrict__ E,
+                                                               const int* __restrict__ qpos, const double* __restrict__ X,
+                                                               const int* __restrict__ ok, double* __restrict__ out,
+                                                               int* __restrict__ degenerate) {
+  extern __shared__ __attribute__((aligned(16))) double rigx_cov_sh[];
+  if (!*ok) return;
+  const int u = blockIdx.x, lane = threadIdx.x, l = u_lm[u];
+  const int g0 = lm_grp[l], K = lm_grp[l + 1] - g0;
+  double* M = rigx_cov_sh;
+  double* W = rigx_cov_sh + 16;
+  double* T = W + 18 * (size_t)K;
+  double P[6] = {0, 0, 0, 0, 0, 0};  // xx xy xz yy yz zz
+  for (int i = lm_start[l]; i < lm_start[l + 1]; i++) {
+    const double* e = E + 6 * (size_t)i;
+    P[0] += e[0] * e[0] + e[3] * e[3];
+    P[1] += e[0] * e[1] + e[3] * e[4];
+    P[2] += e[0] * e[2] + e[3] * e[5];
+    P[3] += e[1] * e[1] + e[4] * e[4];
+    P[4] += e[1] * e[2] + e[4] * e[5];
+    P[5] += e[2] * e[2] + e[5] * e[5];
+  }
+  for (int i = lane; i < K; i += 64) {
+    const double* Fs = grp_slot[g0 + i] < nfb ? F : Fx;
+    double w[18];
+#pragma unroll
+    for (int j = 0; j < 18; j++) w[j] = 0.0;
+    for (int k = grp_first[g0 + i]; k < grp_first[g0 + i + 1]; k++) {
+      const int ob = grp_obs[k];
+      const double* f = Fs + 12 * (size_t)ob;
+      const double* e = E + 6 * (size_t)ob;
+#pragma unroll
+      for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) w[3 * a + j] += f[a] * e[j] + f[6 + a] * e[3 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 18; j++) W[18 * i + j] = w[j];
+  }
+  // P = L D L^T: positive definite to working precision iff every pivot is a fair share of its diagonal entry
+  const double d0 = P[0];
+  const double l1 = P[1] / d0, l2 = P[2] / d0;
+  const double d1 = P[3] - l1 * P[1];
+  const double m = P[4] - l1 * P[2];
+  const double d2 = P[5] - l2 * P[2] - (m / d1) * m;
+  const double P9[9] = {P[0], P[1], P[2], P[1], P[3], P[4], P[2], P[4], P[5]};
+  double Pi[9];
+  const bool pd = d0 > 0.0 && d1 > RIG_COV_LM_TOL * P[3] && d2 > RIG_COV_LM_TOL * P[5] && isfinite(d0 + d1 + d2) && inv3(P9, Pi);
+  if (!pd) {  // (wave-uniform: every lane holds the same P)
+    if (lane < 9) out[9 * (size_t)u + lane] = __builtin_nan("");
+    if (lane == 0) degenerate[u] = 1;
+    return;
+  }
+  if (lane == 0) degenerate[u] = 0;
+  __syncthreads();
+  // T_i = W_i^T sum_j [S^-1]_{s(i) s(j)} W_j, j ascending
+  for (int i = lane; i < K; i += 64) {
+    const int row = 6 * grp_slot[g0 + i];
+    double Z[18];
+#pragma unroll
+    for (int e = 0; e < 18; e++) Z[e] = 0.0;
+    for (int j = 0; j < K; j++) {
+      const int col = 6 * qpos[grp_slot[g0 + j]];
+      const double* Wj = W + 18 * j;
+#pragma unroll
+      for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+          const double s = X[vsl_cov_x_at(n, row + r, col + b)];
+#pragma unroll
+          for (int y = 0; y < 3; y++) Z[3 * r + y] += s * Wj[3 * b + y];
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < 3; x++)
+#pragma unroll
+      for (int y = 0; y < 3; y++) {
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) s += W[18 * i + 3 * r + x] * Z[3 * r + y];
+        T[9 * i + 3 * x + y] = s;
+      }
+  }
+  __syncthreads();
+  if (lane < 9) {
+    double s = 0.0;
+    for (int i = 0; i < K; i++) s += T[9 * i + lane];  // ascending slot
+    M[lane] = s;
+  }
+  __syncthreads();
+  if (lane < 9) {
+    const int x = lane / 3, y = lane % 3;
+    // Q = P^-1 M P^-1, entries (x, y) and (y, x); the result is symmetrised like the pose blocks
+    double qxy = 0.0, qyx = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        qxy += Pi[3 * x + r] * M[3 * r + c] * Pi[3 * c + y];
+        qyx += Pi[3 * y + r] * M[3 * r + c] * Pi[3 * c + x];
+      }
+    out[9 * (size_t)u + lane] = Pi[3 * x + y] + 0.5 * (qxy + qyx);
+  }
+}
+
+// everything behind the validation; host_in / host_out outlive the stream work (the caller synchronises on an error)
+int rigx_cov_run(vsl_ctx* ctx, const char* who, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const vsl_ba_options* opt,
+                 RigxState& st, const RigExtCovPlan& P, std::vector<char>& host_in, std::vector<char>& host_out) {
+  int rc;
+  if ((rc = rigx_setup(ctx, prob, rig, opt, st, P.total))) return rc;
+  char* dev = st.extra;
+  const int n = st.D.n;
+  host_in.assign(P.in_bytes, 0);
+  auto put = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes) memcpy(host_in.data() + off, src, bytes);
+  };
+  const int one = 1;
+  put(P.off_ok, &one, sizeof(int));
+  put(P.off_col_unk, P.col_unk.data(), sizeof(int) * P.col_unk.size());
+  put(P.off_q_slot, P.q_slot.data(), sizeof(int) * P.q_slot.size());
+  put(P.off_qpos, P.qpos.data(), sizeof(int) * P.qpos.size());
+  put(P.off_items, P.items.data(), sizeof(RigExtCovItem) * P.items.size());
+  put(P.off_pairs, P.pairs.data(), sizeof(PgcPairDev) * P.pairs.size());
+  put(P.off_u_lm, P.u_lm.data(), sizeof(int) * P.u_lm.size());
+  put(P.off_tcb, st.plan.T_c_b, sizeof(st.plan.T_c_b));
+  VSL_HIP(ctx, hipMemcpyAsync(dev, host_in.data(), P.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  int* ok = (int*)(dev + P.off_ok);
+  double* X = (double*)(dev + P.off_X);
+  double* joint = (double*)(dev + P.out_off + P.off_joint);
+  // the S of vsl_ba_rig_ext_linearize: the same three calls
+  if ((rc = rigx_linearize(ctx, st, st.cur, false, 0))) return rc;
+  if ((rc = rigx_columns(ctx, st, st.cur))) return rc;
+  if ((rc = rigx_schur(ctx, st, false, 0.0))) return rc;
+  if (P.nQ > 0) {
+    VslStage s(ctx, VSL_STAGE_BA_SOLVE);
+    const VslCovInverse inv{n, 0, 0, st.S, nullptr, (double*)(dev + P.off_Linv), (double*)(dev + P.off_Sdiag),
+                            (const int*)(dev + P.off_col_unk), nullptr, P.nblk, X, ok};
+    if ((rc = vsl_cov_inverse_dev(ctx, inv))) return rc;
+    hipLaunchKernelGGL(rigx_cov_gauge_kernel, dim3((6 * P.nQ + 255) / 256), dim3(256), 0, ctx->stream, n, 6 * P.nQ,
+                       (const int*)(dev + P.off_q_slot), (const double*)(dev + P.off_Sdiag), X, ok);
+    VSL_CHECK_LAUNCH(ctx);
+    if ((rc = vsl_cov_pair_blocks_dev(ctx, n, P.n_pairs, (const PgcPairDev*)(dev + P.off_pairs), 0, nullptr, 0, X, ok, joint))) return rc;
+    if (P.n_items > 0) {
+      hipLaunchKernelGGL(rigx_cov_pose_kernel, dim3((P.n_items + 63) / 64), dim3(64), 0, ctx->stream, n, P.n_items,
+                         (const RigExtCovItem*)(dev + P.off_items), (const int*)(dev + P.off_q_slot), X, joint,
+                         (const double*)(dev + P.off_tcb), ok, (double*)(dev + P.out_off + P.off_pose));
+      VSL_CHECK_LAUNCH(ctx);
+    }
+  }
+  if (P.nu > 0) {
+    const size_t lds = sizeof(double) * (16 + 27 * (size_t)std::max(P.gmax, 1));
+    hipLaunchKernelGGL(rigx_cov_landmark_kernel, dim3(P.nu), dim3(64), lds, ctx->stream, n, st.nfb, (const int*)(dev + P.off_u_lm),
+                       st.lm_start, st.lm_grp, st.grp_slot, st.grp_first, st.grp_obs, st.cur.F, st.cur.Fx, st.cur.E,
+                       (const int*)(dev + P.off_qpos), X, ok, (double*)(dev + P.out_off + P.off_point),
+                       (int*)(dev + P.out_off + P.off_deg));
+    VSL_CHECK_LAUNCH(ctx);
+  }
+  host_out.assign(P.out_bytes + sizeof(int), 0);
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data(), dev + P.out_off, P.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipMemcpyAsync(host_out.data() + P.out_bytes, ok, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VSL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int ok_host;
+  memcpy(&ok_host, host_out.data() + P.out_bytes, sizeof(int));
+  if (!ok_host)
+    return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: the reduced system over bodies and extrinsics is not positive definite to working precision (a gauge direction is free?)", who);
+  return VSL_OK;
+}
+
+}  // namespace
+
+extern "C" int vsl_ba_rig_ext_covariance(vsl_ctx* ctx, const vsl_ba_problem* prob, const vsl_ba_rig* rig, const uint8_t* ext_free,
+                                         const double* T_b_c, const vsl_ba_options* opt, const int32_t* bodies, int n_body_q,
+                                         double* cov_body, const int32_t* cams, int n_cam_q, double* cov_cam, const int32_t* lms,
+                                         int n_lm_q, double* cov_point, double* cov_ext, double* cov_body_ext, int* n_degenerate) {
+  const char* who = "vsl_ba_rig_ext_covariance";
+  if (!ctx) return VSL_ERR_INVALID;
+  if (!rig || !ext_free || !T_b_c) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null pointer", who);
+  if (!ext_free[0] && !ext_free[1]) {  // the rig call itself; cov_ext / cov_body_ext have no entry (m = 0): not written
+    vsl_ba_rig held = *rig;
+    held.T_b_c = T_b_c;
+    return vsl_ba_rig_covariance(ctx, prob, &held, opt, bodies, n_body_q, cov_body, cams, n_cam_q, cov_cam, lms, n_lm_q, cov_point,
+                                 n_degenerate);
+  }
+  std::vector<char> host_in, host_out;  // read / written by copies on the stream: they outlive the synchronisation below
+  RigExtCovPlan P;
+  int rc;
+  {
+    RigxState st;  // holds the loan of the context's arena
+    if ((rc = rigx_validate(ctx, who, prob, rig, ext_free, T_b_c, opt, st))) return rc;
+    if ((n_body_q > 0 && !cov_body) || (n_cam_q > 0 && !cov_cam) || (n_lm_q > 0 && !cov_point))
+      return vsl_fail(ctx, VSL_ERR_INVALID, "%s: null output", who);
+    try {
+      const int e = rxcp_plan(st.plan, st.xp, rig->n_bodies, prob->n_cams, prob->n_lms, prob->cam_intr, bodies, n_body_q, cams,
+                              n_cam_q, lms, n_lm_q, cov_ext != nullptr, cov_body_ext != nullptr, P);
+      if (e != RCP_OK) return vsl_fail(ctx, VSL_ERR_INVALID, "%s: %s (%d)", who, rxcp_message(e), P.first_bad);
+    } catch (const std::bad_alloc&) {
+      return vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    if (st.plan.n_fixed == 0)
+      return vsl_fail(ctx, VSL_ERR_NUMERIC, "%s: no fixed body: the gauge is free and the reduced system singular", who);
+    if (n_body_q == 0 && n_cam_q == 0 && n_lm_q == 0 && !cov_ext && !cov_body_ext) {  // nothing is launched
+      if (n_degenerate) *n_degenerate = 0;
+      return VSL_OK;
+    }
+    VSL_HIP(ctx, hipSetDevice(ctx->device));
+    try {
+      rc = rigx_cov_run(ctx, who, prob, rig, opt, st, P, host_in, host_out);
+    } catch (const std::bad_alloc&) {
+      rc = vsl_fail(ctx, VSL_ERR_NOMEM, "out of host memory");
+    }
+    // an error return may leave kernels and copies queued that use the arena and the host buffers: drain the stream
+    // before the loan ends
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+  }
+  if (rc) return rc;
+  const double* pose = (const double*)(host_out.data() + P.off_pose);
+  const double* jnt = (const double*)(host_out.data() + P.off_joint);
+  const double* point = (const double*)(host_out.data() + P.off_point);
+  const int* deg = (const int*)(host_out.data() + P.off_deg);
+  if (n_body_q > 0) memcpy(cov_body, pose, 36 * sizeof(double) * (size_t)n_body_q);
+  if (n_cam_q > 0) memcpy(cov_cam, pose + 36 * (size_t)n_body_q, 36 * sizeof(double) * (size_t)n_cam_q);
+  const size_t behind = (size_t)n_body_q + (size_t)n_cam_q;
+  if (cov_ext) {
+    if (P.n_ext == 1) memcpy(cov_ext, pose + 36 * behind, 36 * sizeof(double));
+    else memcpy(cov_ext, jnt + 144 * (size_t)P.ext_pair, 144 * sizeof(double));
+  }
+  if (cov_body_ext && P.n_cross > 0) memcpy(cov_body_ext, pose + 36 * (behind + P.n_ext_items), 36 * sizeof(double) * (size_t)P.n_cross);
+  int nd = 0;
+  for (int q = 0; q < n_lm_q; q++) {
+    memcpy(cov_point + 9 * (size_t)q, point + 9 * (size_t)P.lm_q2u[q], 9 * sizeof(double));
+    nd += deg[P.lm_q2u[q]] ? 1 : 0;
+  }
+  if (n_degenerate) *n_degenerate = nd;
+  return VSL_OK;
 }
